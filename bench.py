@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: 20 s-segments/sec (+ RTF) of the SonicScribe hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" = one pass of the hot path (log-mel -> encoder -> projector -> prefill -> 150 greedy tokens) over one batch of 32
@@ -9,14 +9,26 @@ synthetic 20 s segments per GPU (BASELINE.json configs[1]; GLM-ASR-Nano dimensio
 checkpoint exists offline).  PCM is HBM-resident before the timed region.  Segments are sharded across ranks (one engine
 replica per GPU, no data-path collective): weak scaling, value = all ranks' segments / max-over-ranks time.
 
-Two timed legs per run, both K steps bracketed by barrier + synchronize:
+A plain run does only what the headline needs: engine + handles, warm-up, the K timed steps of the headline leg, the outputs of
+--dump-outputs, the JSON line (metric, value, unit, ms_per_step = wall / K, dtype, config).  The headline leg, K steps bracketed by
+barrier + synchronize:
+  value         --pipeline DxR+P (default 3x64+1): the bulk pipeline, D decoding handles looping continuously over R rows each + P prefill
+                slots on ONE engine = ONE weight copy; the K batches are submitted at once and timed from an empty pipeline to the last
+                fetched row; every row must equal the same request in a plain batch run.  --pipeline off: the --slots leg below
+                (--slots 1: single_batch).
+--dump-outputs DIR writes the token ids of the last timed batch (what a caller of the headline leg receives) as DIR/tokens.npy
+(float32 [rows, max_new], -1 past a row's end; rank r > 0 of a multi-rank run: tokens_rank<r>.npy).  Inputs are seeded: the same
+arguments give the same inputs in every run.
+
+--full measures and checks everything else, each leg K steps bracketed the same way:
   single_batch  one batch of 32 at a time (rounds 1-3's headline definition, kept so rounds stay comparable); stages_ms_per_step and
                 roofline are measured here, where the decode kernels have the GPU to themselves
-  value         --slots S (default 2) batches of 32 in flight on ONE engine = ONE weight copy (sonic_slot_create: per-slot stream, buffers,
-                KV cache, graphs); the K batches go round-robin to the slots through sonic_run_staged_async / sonic_wait, every batch a
-                full 32 x 20 s x 150-token run; ms_per_step = wall / K.  --slots 1: value = single_batch.
+  batches_in_flight_slots  --slots S (default 3) batches of 32 in flight on ONE engine = ONE weight copy (sonic_slot_create: per-slot stream,
+                buffers, KV cache, graphs); the K batches go round-robin to the slots through sonic_run_staged_async / sonic_wait, every
+                batch a full 32 x 20 s x 150-token run
+  the pipeline's verification pass (different batches through the pipeline before the clock), and the objects below.
 
-The JSON line also carries
+The JSON line of --full also carries
   roofline      the time-dominant part of a step, the greedy decode loop (HBM-bound: decoder weights + tied lm_head + KV cache once per
                 token step): algorithmic bytes per token step / its average duration, measured with HIP events on the engine's stream
                 around the decode loop of every timed step; traffic_from_profile = the committed PMC passes (profiles/, with their commit)
@@ -31,7 +43,7 @@ The JSON line also carries
                 `cores` = those threads, `quota_cpus` / `visible_cpus` say what the host gave; `threads64` = the same pass at 64 threads
                 (rounds 1-4's figure, oversubscribed inside the quota).  The worker process is spawned before this process
                 initialises the GPU and stays idle until the GPU legs are done (2 warm-ups + up to 3 full passes then)
-(--no-extras skips int8_b64 / bf16_b64 / streaming / pcie_inclusive; a default run takes about five minutes, most of it the CPU passes.)
+(--no-extras skips int8_b64 / bf16_b64 / streaming / pcie_inclusive; a --full run takes about three minutes, most of it the CPU passes and the extra objects.)
 
   python bench.py --mode int8 --batch 64     BASELINE config 4 alone
   python bench.py --streaming                BASELINE config 5's call pattern (sessions x partial / final decodes through the coalescer)
@@ -78,6 +90,16 @@ def segment_flops(d, prompt_len: int) -> dict:
     lin = d.dec_layers * (d.dec_d * (qd + 2 * kvd) + qd * d.dec_d + 3 * d.dec_d * d.dec_ff)
     pre = 2.0 * prompt_len * lin + d.dec_layers * 2 * 2.0 * (prompt_len * (prompt_len + 1) / 2) * qd + 2.0 * d.vocab * d.dec_d
     return {"encoder": enc_gemm + enc_att, "encoder_gemm": enc_gemm, "encoder_attention": enc_att, "prefill": pre}
+
+
+def dump_outputs(out_dir: str, name: str, rows, max_new: int):
+    """--dump-outputs: the token ids a caller of the timed path received for the rows of its last batch, as float32 [rows, max_new]
+    (ids < 2^24 are exact; -1 past a row's end)."""
+    arr = np.full((len(rows), max_new), -1.0, np.float32)
+    for r, ids in enumerate(rows):
+        arr[r, :len(ids)] = ids
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def host_cpu_quota():
@@ -483,7 +505,12 @@ def main():
     ap.add_argument("--pipeline-host", default="native", choices=["native", "python"], help="who drives the bulk pipeline's hand-overs: threads inside libsonic_hip.so "
                     "(sonic_pipeline_*, round 5) or round 4's Python threads (sonicscribe_amd/pipeline.py ContinuousPipeline; A/B)")
     ap.add_argument("--no-extras", action="store_true", help="skip the extra objects int8_b64 / streaming / pcie_inclusive of the N=1 line")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline: single_batch and batches_in_flight_slots "
+                    "legs, the pipeline's verification pass, stages / roofline / per-GEMM figures, cpu_baseline and the extra objects (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the token ids of the last timed batch to DIR/tokens.npy (float32)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.cpu_baseline_worker:
         _cpu_reference_worker(a.cpu_threads, a.cpu_timed, a.cpu_budget, a.cpu_wait_go, a.cpu_threads2)
         return
@@ -503,7 +530,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     n_gpus = world if world > 1 else 1
     cpu = None
-    if n_gpus == 1 and rank == 0 and not a.no_cpu_baseline:
+    if a.full and n_gpus == 1 and rank == 0 and not a.no_cpu_baseline:
         cpu = CpuBaseline()
         cpu.start()                                      # a child process, spawned before this process initialises the GPU; it idles until collect()
     import torch
@@ -549,6 +576,7 @@ def main():
     prompt = [1, 17, 23, 5] + [dims.audio_token_id] * n_audio + [7, 301, 302, 303, 9, 11]
     eng.stage_pcm(segs)                                        # PCM resident in HBM before any timed region
     eng.run_staged([prompt] * len(segs), [a.max_new] * len(segs))
+    ids = eng.fetch_tokens(len(segs), a.max_new)               # every timed batch must give these tokens
 
     def barrier():
         if dist is not None:
@@ -571,7 +599,8 @@ def main():
 
     # further batches in flight on the SAME weights: slot engines (their own stream / buffers / KV cache / graphs), each with the batch staged
     n_slots = max(1, a.slots)
-    n_handles = max(n_slots, pipe_cfg[0] + pipe_cfg[2]) if pipe_cfg else n_slots
+    run_slots = n_slots > 1 and (a.full or not pipe_cfg)      # leg B: the headline without the pipeline, else --full only
+    n_handles = max(n_slots if run_slots else 1, pipe_cfg[0] + pipe_cfg[2] if pipe_cfg else 1)
     engines = [eng]
     for k in range(1, n_handles):
         sl = eng.slot()
@@ -583,28 +612,32 @@ def main():
     from sonicscribe_amd.engine import runtime_info
     hwq = runtime_info(device_index)
 
-    # ---- leg A: one batch at a time (the headline definition of rounds 1-3; stages and roofline are measured here)
-    for _ in range(max(0, a.warmup - 1)):
-        eng.rerun_staged()
-    barrier()
+    # ---- leg A: one batch at a time (the headline definition of rounds 1-3; stages and roofline are measured here): --full, or the headline itself
+    host_cpu = {}
     stage = {"mel_ms": 0.0, "encoder_ms": 0.0, "prefill_ms": 0.0, "decode_ms": 0.0}
-    c0 = cpu_s()
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        eng.rerun_staged()                                     # synchronous: returns after the stream drained
-        t = eng.timings()
-        for k in stage:
-            stage[k] += t[k]
-    barrier()
-    host_cpu = {"single_batch": (cpu_s() - c0) / (time.perf_counter() - t0)}
-    dt_single = max_over_ranks(time.perf_counter() - t0)
-    ids = eng.fetch_tokens(len(segs), a.max_new)
+    dt_single = None
+    if a.full or (not pipe_cfg and n_slots == 1):
+        for _ in range(max(0, a.warmup - 1)):
+            eng.rerun_staged()
+        barrier()
+        c0 = cpu_s()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            eng.rerun_staged()                                     # synchronous: returns after the stream drained
+            t = eng.timings()
+            for k in stage:
+                stage[k] += t[k]
+        barrier()
+        host_cpu["single_batch"] = (cpu_s() - c0) / (time.perf_counter() - t0)
+        dt_single = max_over_ranks(time.perf_counter() - t0)
+        ids = eng.fetch_tokens(len(segs), a.max_new)
+        last_tokens = ids
     assert all(len(x) == a.max_new for x in ids)
 
     # ---- leg B: the K batches round-robin over the slots, sonic_run_staged_async / sonic_wait from this one thread
     dt = dt_single
     slots_identical = None
-    if n_slots > 1:
+    if run_slots:
         def pipeline(n_batches):
             started = 0
             for k in range(min(n_slots, n_batches)):
@@ -623,6 +656,7 @@ def main():
         dt = max_over_ranks(time.perf_counter() - t0)
         slots_identical = all(all(np.array_equal(x, y) for x, y in zip(sl.fetch_tokens(len(segs), a.max_new), ids)) for sl in engines[1:n_slots])
         assert slots_identical, "a slot's tokens differ from the single-batch run of the same segments"
+        last_tokens = engines[(a.steps - 1) % n_slots].fetch_tokens(len(segs), a.max_new)     # the handle that ran the last timed batch
     dt_slots = dt
 
     # ---- leg C (headline): the bulk pipeline - decoding handles loop continuously over their rows, prefill slots splice whole batches in
@@ -633,48 +667,58 @@ def main():
         native = a.pipeline_host == "native"
         want_ids = ids
         prompts_b, budgets_b = [prompt] * len(segs), [a.max_new] * len(segs)
-        # Verification pass (untimed): the timed batches are identical, which cannot show a batch that was prefilled with its
-        # neighbour's plan.  Here every batch is DIFFERENT - segments rotated and restaged, a different text tail per row, a different budget per
-        # row - and every row must give the tokens of the same request in a plain run_staged batch.
-        n_var = 3
-        var = []
-        for v in range(n_var):
-            segs_v = segs[v + 1:] + segs[:v + 1]
-            prompts_v = [prompt + [40 + v, 50 + (i * 5 + v) % 23] * (1 + (i + v) % 3) for i in range(len(segs))]
-            budgets_v = [max(1, a.max_new - (i * 7 + v * 13) % 41) for i in range(len(segs))]
-            eng_v = engines[nd]                                  # a prefill slot computes the expected tokens as a plain batch
-            eng_v.stage_pcm(segs_v); eng_v.run_staged(prompts_v, budgets_v)
-            var.append((segs_v, prompts_v, budgets_v, eng_v.fetch_tokens(len(segs), a.max_new)))
-        n_ver = 2 * n_var + 1
+        last_rows = {}
+
+        def check_row(i, got):                                 # rows are checked batch after batch: those of the batch checked last stay
+            last_rows[i] = got
+            return np.array_equal(got, want_ids[i])
+        res_v = None
+        if a.full:
+            # Verification pass (untimed): the timed batches are identical, which cannot show a batch that was prefilled with its
+            # neighbour's plan.  Here every batch is DIFFERENT - segments rotated and restaged, a different text tail per row, a different budget per
+            # row - and every row must give the tokens of the same request in a plain run_staged batch.
+            n_var = 3
+            var = []
+            for v in range(n_var):
+                segs_v = segs[v + 1:] + segs[:v + 1]
+                prompts_v = [prompt + [40 + v, 50 + (i * 5 + v) % 23] * (1 + (i + v) % 3) for i in range(len(segs))]
+                budgets_v = [max(1, a.max_new - (i * 7 + v * 13) % 41) for i in range(len(segs))]
+                eng_v = engines[nd]                                  # a prefill slot computes the expected tokens as a plain batch
+                eng_v.stage_pcm(segs_v); eng_v.run_staged(prompts_v, budgets_v)
+                var.append((segs_v, prompts_v, budgets_v, eng_v.fetch_tokens(len(segs), a.max_new)))
+            n_ver = 2 * n_var + 1
         if native:
             pipe = NativePipeline(engines[:nd], engines[nd:nd + npre], block=B)
-            tick = [pipe.submit(var[j % n_var][1], var[j % n_var][2], segments=var[j % n_var][0]) for j in range(n_ver)]
-            wrong = 0
-            for j, t in enumerate(tick):
-                got = pipe.wait(t)
-                wrong += sum(0 if (len(g) == var[j % n_var][2][i] and np.array_equal(g, var[j % n_var][3][i])) else 1 for i, g in enumerate(got))
-            res_v = {"batches": n_ver, "wrong_rows": wrong}
-            for p_ in engines[nd:nd + npre]:
-                p_.stage_pcm(segs)                              # back to the timed workload's staged PCM
-            run_pipe = lambda n: pipe.run(n, prompts_b, budgets_b, lambda i, got: np.array_equal(got, want_ids[i]))
+            if a.full:
+                tick = [pipe.submit(var[j % n_var][1], var[j % n_var][2], segments=var[j % n_var][0]) for j in range(n_ver)]
+                wrong = 0
+                for j, t in enumerate(tick):
+                    got = pipe.wait(t)
+                    wrong += sum(0 if (len(g) == var[j % n_var][2][i] and np.array_equal(g, var[j % n_var][3][i])) else 1 for i, g in enumerate(got))
+                res_v = {"batches": n_ver, "wrong_rows": wrong}
+                for p_ in engines[nd:nd + npre]:
+                    p_.stage_pcm(segs)                              # back to the timed workload's staged PCM
+            run_pipe = lambda n: pipe.run(n, prompts_b, budgets_b, check_row)
         else:
             pipe = ContinuousPipeline(engines[:nd], engines[nd:nd + npre], block=B)
-            run_pipe = lambda n: pipe.run(n, lambda p: p.prefill(prompts_b, budgets_b, wait=False), lambda i, got: np.array_equal(got, want_ids[i]))
-            run_pipe(pipe.batches_in_flight)                   # graphs of the row count, every handle touched
-            import itertools
-            ctr, ctr_lock = itertools.count(), threading.Lock()
+            run_pipe = lambda n: pipe.run(n, lambda p: p.prefill(prompts_b, budgets_b, wait=False), check_row)
+            if a.full:
+                run_pipe(pipe.batches_in_flight)                   # graphs of the row count, every handle touched
+                import itertools
+                ctr, ctr_lock = itertools.count(), threading.Lock()
 
-            def prefill_var(p):
-                with ctr_lock:
-                    v = next(ctr) % n_var
-                p.stage_pcm(var[v][0])
-                p.prefill(var[v][1], var[v][2], wait=False)
-                return v
-            res_v = pipe.run(n_ver, prefill_var, lambda i, got, v: len(got) == var[v][2][i] and np.array_equal(got, var[v][3][i]))
-            for p_ in engines[nd:nd + npre]:
-                p_.stage_pcm(segs)
-        assert res_v["batches"] == n_ver and res_v["wrong_rows"] == 0, f"pipeline verification pass (varied batches): {res_v}"
-        run_pipe(pipe.batches_in_flight)                       # warm-up in the timed pattern
+                def prefill_var(p):
+                    with ctr_lock:
+                        v = next(ctr) % n_var
+                    p.stage_pcm(var[v][0])
+                    p.prefill(var[v][1], var[v][2], wait=False)
+                    return v
+                res_v = pipe.run(n_ver, prefill_var, lambda i, got, v: len(got) == var[v][2][i] and np.array_equal(got, var[v][3][i]))
+                for p_ in engines[nd:nd + npre]:
+                    p_.stage_pcm(segs)
+        if a.full:
+            assert res_v["batches"] == n_ver and res_v["wrong_rows"] == 0, f"pipeline verification pass (varied batches): {res_v}"
+        run_pipe(max(a.warmup, pipe.batches_in_flight))        # warm-up in the timed pattern, every handle touched
         barrier()
         c0 = cpu_s()
         t0 = time.perf_counter()
@@ -683,65 +727,30 @@ def main():
         host_cpu["pipeline"] = (cpu_s() - c0) / (time.perf_counter() - t0)
         dt = max_over_ranks(time.perf_counter() - t0)
         assert res["batches"] == a.steps and res["wrong_rows"] == 0, f"pipeline: {res}"
+        last_tokens = [last_rows[i] for i in range(len(segs))]
         pipe.close()
         pipe_info = {"decoders": nd, "rows_per_decoder": prow, "prefill_slots": npre, "batches_in_flight": pipe.batches_in_flight, "rows_bit_identical_to_single_batch": True,
                      "decode_chunks_queued": res["decode_chunks"],
                      "host": ("native threads inside libsonic_hip.so (sonic_pipeline_*: condition variables + blocking events, no interpreter in the loop)" if native
                               else "Python threads over the C ABI (round 4's driver)"),
-                     "verification_pass": {"batches": res_v["batches"], "wrong_rows": res_v["wrong_rows"],
-                                           "what": f"{n_var} different batches (segments rotated and restaged, per-row text tails and budgets) cycled through the pipeline "
-                                                   "before the clock: every row equals the same request in a plain batch run"}}
+                     "verification_pass": ({"batches": res_v["batches"], "wrong_rows": res_v["wrong_rows"],
+                                            "what": f"{n_var} different batches (segments rotated and restaged, per-row text tails and budgets) cycled through the pipeline "
+                                                    "before the clock: every row equals the same request in a plain batch run"} if res_v else None)}
 
-    # one extra, untimed step with HIP events around every encoder-layer GEMM launch (the 256 event records stay out of the timed region)
-    eng.set_option("gemm_timing", 1)
-    eng.rerun_staged()
-    tg = eng.timings()
-    eng.set_option("gemm_timing", 0)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, "tokens" if rank == 0 else f"tokens_rank{rank}", last_tokens, a.max_new)
+
+    if a.full:
+        # one extra, untimed step with HIP events around every encoder-layer GEMM launch (the 256 event records stay out of the timed region)
+        eng.set_option("gemm_timing", 1)
+        eng.rerun_staged()
+        tg = eng.timings()
+        eng.set_option("gemm_timing", 0)
 
     if rank == 0:
         total_segments = n_gpus * B * a.steps
         value = total_segments / dt
-        value_single = total_segments / dt_single
-        value_slots = total_segments / dt_slots
         in_flight_n = pipe_info["batches_in_flight"] if pipe_info else n_slots
-        PEAK_HBM_GBS = 8000.0
-        d_ = dims
-        qd, kvd = d_.dec_heads * d_.dec_head_dim, d_.dec_kv_heads * d_.dec_head_dim
-        wbytes_per_el = 1 if a.mode == "int8" else 2                  # int8 mode: quantised linears stream 1 byte per weight, lm_head stays 16-bit
-        w_bytes = wbytes_per_el * d_.dec_layers * (d_.dec_d * (qd + 2 * kvd) + qd * d_.dec_d + 3 * d_.dec_d * d_.dec_ff) + 2 * d_.vocab * d_.dec_d
-        n_dec = max(1, a.max_new - 1)                                  # token 1 comes out of prefill
-        avg_ctx = len(prompt) + (n_dec + 1) / 2.0
-        kv_bytes = B * d_.dec_layers * 2 * kvd * 2 * avg_ctx
-        dec_ms = stage["decode_ms"] / a.steps / n_dec
-        dec_gbs = (w_bytes + kv_bytes) / (dec_ms * 1e-3) / 1e9 if dec_ms > 0 else 0.0
-        # Headline leg, honest accounting: a decode loop streams the weights ONCE per token step whatever number of its rows are
-        # occupied (two batches of 32 in one 64-row loop share them), every batch reads its own KV.  The steps the loops really ran are counted by
-        # the pipeline (decode chunks queued x steps per chunk); without the pipeline every batch runs its own chain.
-        if pipe_info:
-            loop_steps = pipe_info["decode_chunks_queued"] * max(1, DECODE_CHUNK_STEPS)
-            dec_bytes_leg = loop_steps * w_bytes + a.steps * n_dec * kv_bytes
-            if_note = (f"{loop_steps} decode-loop token steps queued by the pipeline x weight bytes (once per loop step, shared by the batches riding the loop) + "
-                       f"{a.steps} batches x {n_dec} steps x KV bytes, over the wall time of the headline leg (encoder and prefill of other batches run concurrently)")
-        else:
-            loop_steps = a.steps * n_dec
-            dec_bytes_leg = loop_steps * (w_bytes + kv_bytes)
-            if_note = "every batch runs its own chain: algorithmic decode bytes of all timed batches / wall time of the headline leg"
-        in_flight_obj = {"batches_in_flight": in_flight_n, "achieved": dec_bytes_leg / dt / 1e9, "unit": "GB/s", "frac": dec_bytes_leg / dt / 1e9 / PEAK_HBM_GBS,
-                         "decode_loop_steps": loop_steps, "bytes": dec_bytes_leg, "note": if_note}
-        # whole step against the two rooflines it is made of: encoder + projector + prefill on the matrix pipe, the decode loop + mel on HBM;
-        # the serial bound adds them (nothing overlaps), the overlapped bound takes the larger one
-        seg_flops = segment_flops(d_, len(prompt))
-        mfma_ms = B * (seg_flops["encoder"] + seg_flops["prefill"]) / (PEAK_BF16_TFLOPS * (2.0 if a.mode == "int8" else 1.0) * 1e12) * 1e3
-        hbm_bytes_batch = dec_bytes_leg / a.steps + B * (n_samples * 2 + 128 * 3000 * 2)
-        hbm_ms = hbm_bytes_batch / (PEAK_HBM_GBS * 1e9) * 1e3
-        whole_step = {"mfma_ms_at_peak": mfma_ms, "hbm_ms_at_peak": hbm_ms, "measured_ms_per_step": dt / a.steps * 1e3,
-                      "serial_bound_ms": mfma_ms + hbm_ms, "overlapped_bound_ms": max(mfma_ms, hbm_ms),
-                      "frac_of_serial_bound": (mfma_ms + hbm_ms) / (dt / a.steps * 1e3), "frac_of_overlapped_bound": max(mfma_ms, hbm_ms) / (dt / a.steps * 1e3),
-                      "flops_per_batch": B * (seg_flops["encoder"] + seg_flops["prefill"]), "hbm_bytes_per_batch": hbm_bytes_batch,
-                      "mfma_frac_in_leg": B * (seg_flops["encoder"] + seg_flops["prefill"]) / (dt / a.steps) / 1e12 / (PEAK_BF16_TFLOPS * (2.0 if a.mode == "int8" else 1.0)),
-                      "segment_flops": seg_flops,
-                      "note": "per batch of the headline leg: FLOPs of encoder + projector + prompt forward at the dense MFMA peak, decode-loop + log-mel bytes at the HBM peak "
-                              "(weights charged once per decode-loop step), against the measured wall time per batch"}
         out = {
             "metric": "20s-segments/sec/node + RTF, GLM-ASR-Nano bf16, batch=32, 1/2/4/8 MI355X" if a.mode == "native" and B == BATCH else
                       f"20s-segments/sec/node + RTF, GLM-ASR-Nano {a.mode}, batch={B} (BASELINE config {4 if a.mode == 'int8' else 2} variant)",
@@ -758,126 +767,170 @@ def main():
                                     else "one batch in flight: ") +
                                    f"every batch = {B} synthetic {SEG_SECONDS} s 16 kHz segments per GPU, GLM-ASR-Nano dims ({a.dims}), {a.mode}, "
                                    f"log-mel + encoder + prefill + {a.max_new} greedy tokens, portable-PRNG weights; int16 PCM HBM-resident before the "
-                                   f"timed region, token ids fetched to the host " + ("row by row as rows finish" if pipe_info else "after the clock stops") + " (see pcie_inclusive for the host-to-host rate); "
-                                   f"ms_per_step = wall / batches; batches_in_flight_slots = the same K batches as {n_slots} whole batches in flight (sonic_run_staged_async; round 4's first form); "
-                                   f"single_batch = the same K batches one at a time (the headline definition of rounds 1-3)",
+                                   f"timed region, token ids fetched to the host " + ("row by row as rows finish" if pipe_info else "after the clock stops") + "; ms_per_step = wall / batches" +
+                                   (f" (see pcie_inclusive for the host-to-host rate); batches_in_flight_slots = the same K batches as {n_slots} whole batches in flight "
+                                    f"(sonic_run_staged_async; round 4's first form); single_batch = the same K batches one at a time (the headline definition of rounds 1-3)"
+                                    if a.full else ""),
                        "pipeline": pipe_info,
                        "hw_queues": hwq,                # hardware queues the HIP runtime of this process really has (measured, sonic_runtime_info), GPU_MAX_HW_QUEUES, wanted
                        "host_cpus_busy": host_cpu,      # CPU seconds per wall second of this process in each timed leg (rank 0): how much host the legs need
                        "batches_in_flight": in_flight_n, "weight_copies": 1, "weight_bytes": weight_bytes, "weights_mb": round(weight_bytes / 2 ** 20, 1), "slots_bit_identical_to_single_batch": slots_identical,
                        "segments_per_gpu": B, "max_new_tokens": a.max_new, "parallelism": f"replica x{n_gpus} (segments sharded, no collective)",
                        "shard_of_rank0": [lo, hi], "dist_backend": (a.dist_backend if dist is not None else None), "share_gpu": bool(a.share_gpu)},
-            # one batch at a time: the K steps of leg A (same barriers, same max over ranks); stages and roofline below are ITS device times
-            "single_batch": {"value": value_single, "unit": "20s-segments/sec", "ms_per_step": dt_single / a.steps * 1e3, "steps": a.steps,
-                             "rtf": 1.0 / (SEG_SECONDS * value_single)},
-            # whole batches in flight: the K steps of leg B (each slot runs complete batches through sonic_run_staged_async / sonic_wait; host-robust:
-            # a batch is queued whole by a native thread)
-            "batches_in_flight_slots": {"value": value_slots, "unit": "20s-segments/sec", "ms_per_step": dt_slots / a.steps * 1e3, "steps": a.steps, "slots": n_slots,
-                                        "bit_identical_to_single_batch": slots_identical},
-            "stages_ms_per_step": {k: stage[k] / a.steps for k in ("mel_ms", "encoder_ms", "prefill_ms", "decode_ms")},
-            "whole_step": whole_step,
-            # The time-dominant part of a step is the greedy decode loop (~2/3 of it): every token step streams the decoder's weights,
-            # the tied lm_head and each sequence's KV cache exactly once -- HBM-bound.  One "launch" here is one token step (one hipGraph
-            # replay of the captured kernel chain); its duration is measured live: HIP events on the engine stream around the decode
-            # loop of every timed step, divided by the token steps.  `traffic` (HBM bytes from PMC counters) cannot be read inside
-            # the run: the rocprofv3 passes are committed under profiles/ and quoted as traffic_from_profile.
-            "roofline": {"bound": "hbm", "achieved": dec_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": dec_gbs / PEAK_HBM_GBS, "traffic": None,
-                         "kernel": "decode token step (hipGraph chunk replay: per layer qkv / attention / o_proj / gate-up / down kernels + lm_head + greedy)",
-                         "measured_in": "single_batch leg (the chain alone on the GPU); in_flight below is the whole-GPU rate of the headline leg",
-                         # headline leg: every batch streams the same algorithmic decode bytes; divided by the WHOLE wall time (encoder and prefill
-                         # of the other slot included), i.e. a lower bound of the HBM rate while several chains overlap
-                         "in_flight": in_flight_obj,
-                         "bytes_per_launch": w_bytes + kv_bytes, "avg_launch_ms": dec_ms, "launches_timed": n_dec * a.steps,
-                         "algorithmic_bytes": {"weights": w_bytes, "kv_cache_avg": kv_bytes}},
         }
-        # `traffic`: HBM bytes per launch (= per token step) from the PMC counters.  Counters cannot be read inside this run (rocprofv3 --pmc serialises the
-        # kernels); the value is the newest committed pass of THIS command line's decode chain (tools/round_profiles.sh: FETCH_SIZE and WRITE_SIZE in separate
-        # runs, FETCH_SIZE doubled as the guide prescribes for gfx950), taken at the same --max-new so the contexts match; a pass of another batch size, mode
-        # or token budget is quoted under traffic_from_profile only and `traffic` stays null
-        for prof in ("round6_pmc_decode.json", "round5_pmc_decode.json", "round4_pmc_decode.json", "round3_pmc_decode.json", "round2_pmc_decode.json"):
-            try:
-                with open(os.path.join(ROOT, "profiles", prof)) as f:
-                    pm = json.load(f)
-                out["roofline"]["traffic_from_profile"] = {k: pm[k] for k in ("hbm_bytes_per_token_step", "fetch_bytes_x2", "write_bytes", "note", "source", "commit", "max_new", "batch", "mode") if k in pm}
-                out["roofline"]["traffic_from_profile"]["file"] = "profiles/" + prof
-                if pm.get("max_new") == a.max_new and pm.get("batch", BATCH) == B and pm.get("mode", "native") == a.mode and a.dims == "full":
-                    out["roofline"]["traffic"] = pm["hbm_bytes_per_token_step"]
-                    out["roofline"]["traffic_over_algorithmic"] = pm["hbm_bytes_per_token_step"] / (w_bytes + kv_bytes)
-                break
-            except Exception:
-                pass
-        # the other rooflines SURVEY.md 8d names:
-        #   mel front-end vs HBM: 1.408 MB of algorithmic bytes per 20 s segment (int16 PCM in, bf16 features out), timed region
-        #   encoder GEMMs vs MFMA: all encoder-layer GEMM launches (QKV, o, fc1, fc2) with HIP events around each, from the extra step
-        mel_bytes = B * (n_samples * 2 + 128 * 3000 * 2)
-        mel_gbs = mel_bytes / (stage["mel_ms"] / a.steps * 1e-3) / 1e9 if stage["mel_ms"] > 0 else 0.0
-        # ... and what the kernel is actually bound by in its DFT-as-GEMM form: exact-fp32 MFMA (v_mfma_f32_32x32x2_f32, 157.3 TFLOP/s peak): four 100-long
-        # sums x 128 bin columns per live frame (frames in whole 32-frame tiles)
-        live_frames = ((min(n_samples, 480000) + 200 + 159) // 160 + 31) // 32 * 32
-        mel_flops = B * live_frames * 4 * 100 * 128 * 2.0
-        mel_tf = mel_flops / (stage["mel_ms"] / a.steps * 1e-3) / 1e12 if stage["mel_ms"] > 0 else 0.0
-        out["mel_frontend"] = {"bound": "hbm", "achieved": mel_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": mel_gbs / PEAK_HBM_GBS,
-                               "bytes_per_step": mel_bytes, "ms_per_step": stage["mel_ms"] / a.steps,
-                               "compute": {"bound": "mfma fp32", "achieved": mel_tf, "peak": 157.3, "unit": "TFLOP/s", "frac": mel_tf / 157.3, "flops_per_step": mel_flops,
-                                           "note": "the folded 400-point DFT runs as an exact-fp32 MFMA GEMM: by bytes the kernel is HBM-bound, in this form it is not"}}
-        peak_mm = PEAK_BF16_TFLOPS * (2.0 if a.mode == "int8" else 1.0)
-        if tg["enc_gemm_ms"] > 0:
-            eg = tg["enc_gemm_flops"] / (tg["enc_gemm_ms"] * 1e-3) / 1e12
-            out["encoder_gemms"] = {"bound": "mfma", "achieved": eg, "peak": peak_mm, "unit": "TFLOP/s", "frac": eg / peak_mm,
-                                    "ms_per_step": tg["enc_gemm_ms"], "flops_per_step": tg["enc_gemm_flops"],
-                                    "note": "HIP events around each of the 128 encoder-layer GEMM launches of one extra untimed step"}
-        if tg["gemm_launches"] > 0:
-            gm = tg["gemm_ms"] / tg["gemm_launches"]; fl = tg["gemm_flops"] / tg["gemm_launches"]
-            out["encoder_fc1_gemm"] = {"bound": "mfma", "achieved": fl / (gm * 1e-3) / 1e12, "peak": peak_mm, "unit": "TFLOP/s",
-                                       "frac": fl / (gm * 1e-3) / 1e12 / peak_mm, "avg_launch_ms": gm, "flops_per_launch": fl, "launches_timed": tg["gemm_launches"]}
-        extras = n_gpus == 1 and a.dims == "full" and a.mode == "native" and B == BATCH and not a.no_extras
-        if extras:
-            # host-to-host rate of the same batch through the one-call boundary (sonic_transcribe_batch: H2D of the int16 PCM, the device
-            # work, D2H of the ids) - never the headline `value`
-            t1 = time.perf_counter()
-            for _ in range(a.steps):
-                eng.transcribe_batch(segs, [prompt] * len(segs), [a.max_new] * len(segs))
-            d1 = time.perf_counter() - t1
-            out["pcie_inclusive"] = {"value": B * a.steps / d1, "unit": "20s-segments/sec", "ms_per_step": d1 / a.steps * 1e3,
-                                     "note": "sonic_transcribe_batch host buffers in, host ids out (32 x 640 kB of PCM over PCIe per step); not the headline"}
-        if extras:
-            import contextlib
-            eng.close(); eng = None; engines = []
-            _quiet = contextlib.redirect_stdout(sys.stderr)       # the facade prints a banner; stdout carries the one JSON line only
-            _quiet.__enter__()
-            # BASELINE config 4 (the repo's INT8 option, batch 64) and the bf16 batch-64 figure it has to beat, same process, same box
-            for key, mode_ in (("int8_b64", "int8"), ("bf16_b64", "native")):     # (separate try blocks: one failure must not erase the other's figure)
+        if a.full:
+            value_single = total_segments / dt_single
+            value_slots = total_segments / dt_slots
+            PEAK_HBM_GBS = 8000.0
+            d_ = dims
+            qd, kvd = d_.dec_heads * d_.dec_head_dim, d_.dec_kv_heads * d_.dec_head_dim
+            wbytes_per_el = 1 if a.mode == "int8" else 2                  # int8 mode: quantised linears stream 1 byte per weight, lm_head stays 16-bit
+            w_bytes = wbytes_per_el * d_.dec_layers * (d_.dec_d * (qd + 2 * kvd) + qd * d_.dec_d + 3 * d_.dec_d * d_.dec_ff) + 2 * d_.vocab * d_.dec_d
+            n_dec = max(1, a.max_new - 1)                                  # token 1 comes out of prefill
+            avg_ctx = len(prompt) + (n_dec + 1) / 2.0
+            kv_bytes = B * d_.dec_layers * 2 * kvd * 2 * avg_ctx
+            dec_ms = stage["decode_ms"] / a.steps / n_dec
+            dec_gbs = (w_bytes + kv_bytes) / (dec_ms * 1e-3) / 1e9 if dec_ms > 0 else 0.0
+            # Headline leg, honest accounting: a decode loop streams the weights ONCE per token step whatever number of its rows are
+            # occupied (two batches of 32 in one 64-row loop share them), every batch reads its own KV.  The steps the loops really ran are counted by
+            # the pipeline (decode chunks queued x steps per chunk); without the pipeline every batch runs its own chain.
+            if pipe_info:
+                loop_steps = pipe_info["decode_chunks_queued"] * max(1, DECODE_CHUNK_STEPS)
+                dec_bytes_leg = loop_steps * w_bytes + a.steps * n_dec * kv_bytes
+                if_note = (f"{loop_steps} decode-loop token steps queued by the pipeline x weight bytes (once per loop step, shared by the batches riding the loop) + "
+                           f"{a.steps} batches x {n_dec} steps x KV bytes, over the wall time of the headline leg (encoder and prefill of other batches run concurrently)")
+            else:
+                loop_steps = a.steps * n_dec
+                dec_bytes_leg = loop_steps * (w_bytes + kv_bytes)
+                if_note = "every batch runs its own chain: algorithmic decode bytes of all timed batches / wall time of the headline leg"
+            in_flight_obj = {"batches_in_flight": in_flight_n, "achieved": dec_bytes_leg / dt / 1e9, "unit": "GB/s", "frac": dec_bytes_leg / dt / 1e9 / PEAK_HBM_GBS,
+                             "decode_loop_steps": loop_steps, "bytes": dec_bytes_leg, "note": if_note}
+            # whole step against the two rooflines it is made of: encoder + projector + prefill on the matrix pipe, the decode loop + mel on HBM;
+            # the serial bound adds them (nothing overlaps), the overlapped bound takes the larger one
+            seg_flops = segment_flops(d_, len(prompt))
+            mfma_ms = B * (seg_flops["encoder"] + seg_flops["prefill"]) / (PEAK_BF16_TFLOPS * (2.0 if a.mode == "int8" else 1.0) * 1e12) * 1e3
+            hbm_bytes_batch = dec_bytes_leg / a.steps + B * (n_samples * 2 + 128 * 3000 * 2)
+            hbm_ms = hbm_bytes_batch / (PEAK_HBM_GBS * 1e9) * 1e3
+            whole_step = {"mfma_ms_at_peak": mfma_ms, "hbm_ms_at_peak": hbm_ms, "measured_ms_per_step": dt / a.steps * 1e3,
+                          "serial_bound_ms": mfma_ms + hbm_ms, "overlapped_bound_ms": max(mfma_ms, hbm_ms),
+                          "frac_of_serial_bound": (mfma_ms + hbm_ms) / (dt / a.steps * 1e3), "frac_of_overlapped_bound": max(mfma_ms, hbm_ms) / (dt / a.steps * 1e3),
+                          "flops_per_batch": B * (seg_flops["encoder"] + seg_flops["prefill"]), "hbm_bytes_per_batch": hbm_bytes_batch,
+                          "mfma_frac_in_leg": B * (seg_flops["encoder"] + seg_flops["prefill"]) / (dt / a.steps) / 1e12 / (PEAK_BF16_TFLOPS * (2.0 if a.mode == "int8" else 1.0)),
+                          "segment_flops": seg_flops,
+                          "note": "per batch of the headline leg: FLOPs of encoder + projector + prompt forward at the dense MFMA peak, decode-loop + log-mel bytes at the HBM peak "
+                                  "(weights charged once per decode-loop step), against the measured wall time per batch"}
+            out.update({
+                # one batch at a time: the K steps of leg A (same barriers, same max over ranks); stages and roofline below are ITS device times
+                "single_batch": {"value": value_single, "unit": "20s-segments/sec", "ms_per_step": dt_single / a.steps * 1e3, "steps": a.steps,
+                                 "rtf": 1.0 / (SEG_SECONDS * value_single)},
+                # whole batches in flight: the K steps of leg B (each slot runs complete batches through sonic_run_staged_async / sonic_wait; host-robust:
+                # a batch is queued whole by a native thread)
+                "batches_in_flight_slots": {"value": value_slots, "unit": "20s-segments/sec", "ms_per_step": dt_slots / a.steps * 1e3, "steps": a.steps, "slots": n_slots,
+                                            "bit_identical_to_single_batch": slots_identical},
+                "stages_ms_per_step": {k: stage[k] / a.steps for k in ("mel_ms", "encoder_ms", "prefill_ms", "decode_ms")},
+                "whole_step": whole_step,
+                # The time-dominant part of a step is the greedy decode loop (~2/3 of it): every token step streams the decoder's weights,
+                # the tied lm_head and each sequence's KV cache exactly once -- HBM-bound.  One "launch" here is one token step (one hipGraph
+                # replay of the captured kernel chain); its duration is measured live: HIP events on the engine stream around the decode
+                # loop of every timed step, divided by the token steps.  `traffic` (HBM bytes from PMC counters) cannot be read inside
+                # the run: the rocprofv3 passes are committed under profiles/ and quoted as traffic_from_profile.
+                "roofline": {"bound": "hbm", "achieved": dec_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": dec_gbs / PEAK_HBM_GBS, "traffic": None,
+                             "kernel": "decode token step (hipGraph chunk replay: per layer qkv / attention / o_proj / gate-up / down kernels + lm_head + greedy)",
+                             "measured_in": "single_batch leg (the chain alone on the GPU); in_flight below is the whole-GPU rate of the headline leg",
+                             # headline leg: every batch streams the same algorithmic decode bytes; divided by the WHOLE wall time (encoder and prefill
+                             # of the other slot included), i.e. a lower bound of the HBM rate while several chains overlap
+                             "in_flight": in_flight_obj,
+                             "bytes_per_launch": w_bytes + kv_bytes, "avg_launch_ms": dec_ms, "launches_timed": n_dec * a.steps,
+                             "algorithmic_bytes": {"weights": w_bytes, "kv_cache_avg": kv_bytes}},
+            })
+            # `traffic`: HBM bytes per launch (= per token step) from the PMC counters.  Counters cannot be read inside this run (rocprofv3 --pmc serialises the
+            # kernels); the value is the newest committed pass of THIS command line's decode chain (tools/round_profiles.sh: FETCH_SIZE and WRITE_SIZE in separate
+            # runs, FETCH_SIZE doubled as the guide prescribes for gfx950), taken at the same --max-new so the contexts match; a pass of another batch size, mode
+            # or token budget is quoted under traffic_from_profile only and `traffic` stays null
+            for prof in ("round6_pmc_decode.json", "round5_pmc_decode.json", "round4_pmc_decode.json", "round3_pmc_decode.json", "round2_pmc_decode.json"):
                 try:
-                    out[key] = extra_batch_run(dims, device_index, mode_, 64, a.max_new, steps=2, slots=a.slots)
+                    with open(os.path.join(ROOT, "profiles", prof)) as f:
+                        pm = json.load(f)
+                    out["roofline"]["traffic_from_profile"] = {k: pm[k] for k in ("hbm_bytes_per_token_step", "fetch_bytes_x2", "write_bytes", "note", "source", "commit", "max_new", "batch", "mode") if k in pm}
+                    out["roofline"]["traffic_from_profile"]["file"] = "profiles/" + prof
+                    if pm.get("max_new") == a.max_new and pm.get("batch", BATCH) == B and pm.get("mode", "native") == a.mode and a.dims == "full":
+                        out["roofline"]["traffic"] = pm["hbm_bytes_per_token_step"]
+                        out["roofline"]["traffic_over_algorithmic"] = pm["hbm_bytes_per_token_step"] / (w_bytes + kv_bytes)
+                    break
+                except Exception:
+                    pass
+            # the other rooflines SURVEY.md 8d names:
+            #   mel front-end vs HBM: 1.408 MB of algorithmic bytes per 20 s segment (int16 PCM in, bf16 features out), timed region
+            #   encoder GEMMs vs MFMA: all encoder-layer GEMM launches (QKV, o, fc1, fc2) with HIP events around each, from the extra step
+            mel_bytes = B * (n_samples * 2 + 128 * 3000 * 2)
+            mel_gbs = mel_bytes / (stage["mel_ms"] / a.steps * 1e-3) / 1e9 if stage["mel_ms"] > 0 else 0.0
+            # ... and what the kernel is actually bound by in its DFT-as-GEMM form: exact-fp32 MFMA (v_mfma_f32_32x32x2_f32, 157.3 TFLOP/s peak): four 100-long
+            # sums x 128 bin columns per live frame (frames in whole 32-frame tiles)
+            live_frames = ((min(n_samples, 480000) + 200 + 159) // 160 + 31) // 32 * 32
+            mel_flops = B * live_frames * 4 * 100 * 128 * 2.0
+            mel_tf = mel_flops / (stage["mel_ms"] / a.steps * 1e-3) / 1e12 if stage["mel_ms"] > 0 else 0.0
+            out["mel_frontend"] = {"bound": "hbm", "achieved": mel_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": mel_gbs / PEAK_HBM_GBS,
+                                   "bytes_per_step": mel_bytes, "ms_per_step": stage["mel_ms"] / a.steps,
+                                   "compute": {"bound": "mfma fp32", "achieved": mel_tf, "peak": 157.3, "unit": "TFLOP/s", "frac": mel_tf / 157.3, "flops_per_step": mel_flops,
+                                               "note": "the folded 400-point DFT runs as an exact-fp32 MFMA GEMM: by bytes the kernel is HBM-bound, in this form it is not"}}
+            peak_mm = PEAK_BF16_TFLOPS * (2.0 if a.mode == "int8" else 1.0)
+            if tg["enc_gemm_ms"] > 0:
+                eg = tg["enc_gemm_flops"] / (tg["enc_gemm_ms"] * 1e-3) / 1e12
+                out["encoder_gemms"] = {"bound": "mfma", "achieved": eg, "peak": peak_mm, "unit": "TFLOP/s", "frac": eg / peak_mm,
+                                        "ms_per_step": tg["enc_gemm_ms"], "flops_per_step": tg["enc_gemm_flops"],
+                                        "note": "HIP events around each of the 128 encoder-layer GEMM launches of one extra untimed step"}
+            if tg["gemm_launches"] > 0:
+                gm = tg["gemm_ms"] / tg["gemm_launches"]; fl = tg["gemm_flops"] / tg["gemm_launches"]
+                out["encoder_fc1_gemm"] = {"bound": "mfma", "achieved": fl / (gm * 1e-3) / 1e12, "peak": peak_mm, "unit": "TFLOP/s",
+                                           "frac": fl / (gm * 1e-3) / 1e12 / peak_mm, "avg_launch_ms": gm, "flops_per_launch": fl, "launches_timed": tg["gemm_launches"]}
+            extras = n_gpus == 1 and a.dims == "full" and a.mode == "native" and B == BATCH and not a.no_extras
+            if extras:
+                # host-to-host rate of the same batch through the one-call boundary (sonic_transcribe_batch: H2D of the int16 PCM, the device
+                # work, D2H of the ids) - never the headline `value`
+                t1 = time.perf_counter()
+                for _ in range(a.steps):
+                    eng.transcribe_batch(segs, [prompt] * len(segs), [a.max_new] * len(segs))
+                d1 = time.perf_counter() - t1
+                out["pcie_inclusive"] = {"value": B * a.steps / d1, "unit": "20s-segments/sec", "ms_per_step": d1 / a.steps * 1e3,
+                                         "note": "sonic_transcribe_batch host buffers in, host ids out (32 x 640 kB of PCM over PCIe per step); not the headline"}
+            if extras:
+                import contextlib
+                eng.close(); eng = None; engines = []
+                _quiet = contextlib.redirect_stdout(sys.stderr)       # the facade prints a banner; stdout carries the one JSON line only
+                _quiet.__enter__()
+                # BASELINE config 4 (the repo's INT8 option, batch 64) and the bf16 batch-64 figure it has to beat, same process, same box
+                for key, mode_ in (("int8_b64", "int8"), ("bf16_b64", "native")):     # (separate try blocks: one failure must not erase the other's figure)
+                    try:
+                        out[key] = extra_batch_run(dims, device_index, mode_, 64, a.max_new, steps=2, slots=a.slots)
+                    except Exception as ex:
+                        out[key] = {"value": None, "note": f"not measured: {ex!r}"}
+                # the facade's bulk shape: the same pipeline behind ASRModel.submit() - host float tensors in (peak-normalise + PCM_16 on the host, H2D),
+                # transcripts out - 10 batches' worth of segments submitted at once
+                try:
+                    out["facade_bulk"] = facade_bulk_measure(dims, device_index, B, a.max_new)
                 except Exception as ex:
-                    out[key] = {"value": None, "note": f"not measured: {ex!r}"}
-            # the facade's bulk shape: the same pipeline behind ASRModel.submit() - host float tensors in (peak-normalise + PCM_16 on the host, H2D),
-            # transcripts out - 10 batches' worth of segments submitted at once
-            try:
-                out["facade_bulk"] = facade_bulk_measure(dims, device_index, B, a.max_new)
-            except Exception as ex:
-                out["facade_bulk"] = {"value": None, "note": f"not measured: {ex!r}"}
-            # BASELINE config 5's call pattern at its per-GPU share (128 sessions / 8 GPUs = 16), real-time schedule, device-resident ingest
-            try:
-                # continuous scheduling (dispatch._ContinuousReplica: the engine decodes forever over its rows, one slot prefills), decode chunks of 2 steps
-                sa = argparse.Namespace(dims="full", sessions=16, gpus=1, replicas_per_gpu=1, mode="native", batch=BATCH, ingest="ring", slots=2, single=True,
-                                        continuous=True, opt=["decode_chunk=2"])
-                st = streaming_measure(sa)
-                out["streaming"] = {k: st[k] for k in ("sessions", "partial_latency_ms", "final_latency_ms", "value", "unit", "wall_s", "ingest", "device_batches_per_replica", "slots", "continuous")}
-                for k in ("single_5s", "single_20s"):            # BASELINE config 1's call shape, measured on the same model object
-                    if k in st:
-                        out[k] = st[k]
-                out["streaming"]["note"] = ("BASELINE config 5 call pattern: 16 sessions (128 / 8 GPUs) x (64 ms chunks into device rings, 1 s partials of 1.28 s / 15 "
-                                            "tokens, one 20 s final / 150 tokens), real-time schedule through ASRModel.submit(); latency = submit -> transcript; row-level "
-                                            "scheduling (ASRModel(continuous=True)): requests join and leave a running greedy loop row by row")
-            except Exception as ex:
-                out["streaming"] = {"value": None, "note": f"not measured: {ex!r}"}
-            _quiet.__exit__(None, None, None)
-        if cpu is not None:
-            try:
-                out["cpu_baseline"] = cpu.collect()
-            except Exception as ex:   # transformers missing on the box: report that rather than a wrong number
-                out["cpu_baseline"] = {"value": None, "unit": "20s-segments/sec", "cores": 0, "kind": "reference", "sample": f"unavailable: {ex!r}"}
+                    out["facade_bulk"] = {"value": None, "note": f"not measured: {ex!r}"}
+                # BASELINE config 5's call pattern at its per-GPU share (128 sessions / 8 GPUs = 16), real-time schedule, device-resident ingest
+                try:
+                    # continuous scheduling (dispatch._ContinuousReplica: the engine decodes forever over its rows, one slot prefills), decode chunks of 2 steps
+                    sa = argparse.Namespace(dims="full", sessions=16, gpus=1, replicas_per_gpu=1, mode="native", batch=BATCH, ingest="ring", slots=2, single=True,
+                                            continuous=True, opt=["decode_chunk=2"])
+                    st = streaming_measure(sa)
+                    out["streaming"] = {k: st[k] for k in ("sessions", "partial_latency_ms", "final_latency_ms", "value", "unit", "wall_s", "ingest", "device_batches_per_replica", "slots", "continuous")}
+                    for k in ("single_5s", "single_20s"):            # BASELINE config 1's call shape, measured on the same model object
+                        if k in st:
+                            out[k] = st[k]
+                    out["streaming"]["note"] = ("BASELINE config 5 call pattern: 16 sessions (128 / 8 GPUs) x (64 ms chunks into device rings, 1 s partials of 1.28 s / 15 "
+                                                "tokens, one 20 s final / 150 tokens), real-time schedule through ASRModel.submit(); latency = submit -> transcript; row-level "
+                                                "scheduling (ASRModel(continuous=True)): requests join and leave a running greedy loop row by row")
+                except Exception as ex:
+                    out["streaming"] = {"value": None, "note": f"not measured: {ex!r}"}
+                _quiet.__exit__(None, None, None)
+            if cpu is not None:
+                try:
+                    out["cpu_baseline"] = cpu.collect()
+                except Exception as ex:   # transformers missing on the box: report that rather than a wrong number
+                    out["cpu_baseline"] = {"value": None, "unit": "20s-segments/sec", "cores": 0, "kind": "reference", "sample": f"unavailable: {ex!r}"}
         print(json.dumps(out), flush=True)
     if eng is not None:
         eng.close()

@@ -22,7 +22,7 @@ def test_two_ranks_share_one_gpu_through_torchrun():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29731",
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup", "1", "--dims", "tiny", "--batch", str(B), "--max-new", "12",
-           "--dist-backend", "gloo", "--share-gpu", "--no-cpu-baseline", "--slots", "2", "--pipeline", "2x8+1"]
+           "--dist-backend", "gloo", "--share-gpu", "--no-cpu-baseline", "--slots", "2", "--pipeline", "2x8+1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -45,7 +45,7 @@ def test_rccl_branch_at_world_size_one():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29733",
            os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1", "--dims", "tiny", "--batch", str(B), "--max-new", "12",
-           "--dist-backend", "nccl", "--no-cpu-baseline", "--slots", "2", "--pipeline", "2x8+1"]
+           "--dist-backend", "nccl", "--no-cpu-baseline", "--slots", "2", "--pipeline", "2x8+1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -69,7 +69,7 @@ def test_eight_ranks_share_one_gpu_and_leave_the_host_alone():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1", "--master-port", "29735",
            os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", str(steps), "--warmup", "1", "--dims", "tiny", "--batch", str(B), "--max-new", "12",
-           "--dist-backend", "gloo", "--share-gpu", "--no-cpu-baseline", "--slots", "2", "--pipeline", "2x8+1"]
+           "--dist-backend", "gloo", "--share-gpu", "--no-cpu-baseline", "--slots", "2", "--pipeline", "2x8+1", "--full"]
     # The host-CPU criterion is a load measurement over legs that last tens of milliseconds at these dimensions: on a cold box (eight interpreters paging
     # in torch at once) one leg has been seen above the bound once in five runs.  A second run on the then warm box must meet it; everything else is
     # asserted on every run.

@@ -12,7 +12,7 @@ for l in sys.stdin:
     except Exception: print("PARSE FAIL", l[:200]); continue
     print(json.dumps({k:d.get(k) for k in ("value","ms_per_step","single_batch","stages_ms_per_step")}), "roofline.frac", d["roofline"]["frac"], "in_flight", d["roofline"].get("in_flight",{}).get("frac"))
 ' >> $LOG; }
-B="python3 bench.py --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-extras"
+B="python3 bench.py --full --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-extras"
 for s in 1 2 3 4; do run $B --slots $s; done
 for c in 1 2 8 16; do run $B --slots 2 --opt decode_chunk=$c; done
 echo "### SONIC_NO_UC=1" >> $LOG

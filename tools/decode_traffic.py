@@ -22,6 +22,6 @@ for k in per_layer + per_step:
     rows.append({"kernel": k[0], "grid_threads": k[1], "launches_per_step": mult, "fetch_bytes_x2": f, "write_bytes": w})
     tot_f += f; tot_w += w
 print(json.dumps({"max_new": max_new, "batch": 32, "mode": "native", "hbm_bytes_per_token_step": tot_f + tot_w, "fetch_bytes_x2": tot_f, "write_bytes": tot_w, "kernels": rows,
-                  "note": "separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `bench.py --slots 1 --pipeline off --steps 1 --warmup 1 --no-cpu-baseline --no-extras --max-new %d` "
+                  "note": "separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `bench.py --full --slots 1 --pipeline off --steps 1 --warmup 1 --no-cpu-baseline --no-extras --max-new %d` "
                           "(the per-dispatch averages run over the token steps of that run: at --max-new 150 the contexts are the bench's own, 264..413); FETCH_SIZE doubled (gfx950 correction)" % max_new,
                   "source": [sys.argv[1], sys.argv[2]]}, indent=1))
