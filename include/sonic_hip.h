@@ -28,6 +28,11 @@
  *   sonic_memory_info          torch.cuda.memory_allocated() / memory_reserved() in the debug dict  asr.py:453-457
  *   sonic_destroy              `del asr_model.model` + torch.cuda.empty_cache(): every device byte goes back   backend/main.py:84-90
  *   sonic_last_error           the exception text re-raised at            asr.py:469-481
+ *   sonic_vad_create / sonic_vad_load_tensor / sonic_vad_destroy / sonic_vad_last_error
+ *                              VADProcessor.__init__ (load_silero_vad)    backend/vad.py:7-22
+ *                              (models_manager.vad_model_init             models_manager.py:34-49)
+ *   sonic_vad_probs            the model(chunk, 16000) loop inside get_speech_timestamps as called from
+ *                              VADProcessor.detect_voice_activity / is_voice_active   backend/vad.py:41-126
  */
 #ifndef SONIC_HIP_H
 #define SONIC_HIP_H
@@ -39,7 +44,7 @@ extern "C" {
 /* The library is built with -fvisibility=hidden: these declarations are its whole dynamic symbol table (tests/test_host_logic.py checks
  * `nm -D` against this header).  SONIC_ABI_VERSION moves whenever a signature or a struct layout below changes. */
 #define SONIC_API __attribute__((visibility("default")))
-#define SONIC_ABI_VERSION 7
+#define SONIC_ABI_VERSION 8
 SONIC_API int sonic_abi_version(void);
 
 typedef struct sonic_engine sonic_engine;
@@ -315,6 +320,26 @@ SONIC_API int sonic_debug_ktrace(sonic_engine* e, int64_t* out, int64_t n);
  * "decode_attn_occ2" (experiments that lost: profiles/round6_*), "f32_synth_bf16" (SONIC_MODE_F32: sonic_load_synthetic writes the bf16-rounded values),
  * "inject_dev_err" (tests: sets / clears the device error word) */
 SONIC_API int sonic_set_option(sonic_engine* e, const char* key, int value);
+
+/* ---- Silero VAD network (silero-vad 5.x / 6.x, 16 kHz branch; csrc/vad.hip, layer table in sonicscribe_amd/vad_net.py) ----
+ * A handle of its own, not part of sonic_engine: the reference builds the VAD apart from the ASR model (models_manager.py:34-49), and a
+ * VAD call never queues behind a decoding batch.  Own stream and lock: thread-safe, calls from several threads serialise on the handle.
+ *   sonic_vad_create(device_id, max_windows, &v)   max_windows: windows the first buffers hold; a larger call grows them (never refused)
+ *   sonic_vad_last_error(v)      v may be NULL: the error of the last failed sonic_vad_create on this thread
+ *   sonic_vad_load_tensor(v, name, data, shape, ndim)   fp32, names of load_silero_vad()'s state dict without the `_model.` prefix; name
+ *                                and shape are checked.  Until all 15 tensors are loaded sonic_vad_probs returns SONIC_ERR_INVALID naming
+ *                                the first missing one
+ *   sonic_vad_probs(v, pcm_i16, pcm_f32, off, B, probs)   exactly one of pcm_i16 / pcm_f32; sequence b = samples off[b] .. off[b+1]-1
+ *                                (16 kHz).  int16 means x / 32768; float is divided by max|x| when that exceeds 1 (backend/vad.py:24-38).
+ *                                A sequence is cut into ceil(n / 512) windows (the last zero-padded), each scored with the model state
+ *                                carried from the previous window (reset per sequence); probs[sum of ceil(n_b / 512)] in sequence order.
+ *                                All fp32; a sequence's probabilities do not depend on the rest of the call (bit for bit). */
+typedef struct sonic_vad sonic_vad;
+SONIC_API int sonic_vad_create(int device_id, int max_windows, sonic_vad** out);
+SONIC_API void sonic_vad_destroy(sonic_vad* v);
+SONIC_API const char* sonic_vad_last_error(sonic_vad* v);
+SONIC_API int sonic_vad_load_tensor(sonic_vad* v, const char* name, const float* data, const int64_t* shape, int ndim);
+SONIC_API int sonic_vad_probs(sonic_vad* v, const int16_t* pcm_i16, const float* pcm_f32, const int64_t* off, int B, float* probs);
 
 #ifdef __cplusplus
 }

@@ -34,8 +34,9 @@ EXPORTS = [
     "sonic_runtime_info", "sonic_engine_info",
     "sonic_dispatch_create", "sonic_dispatch_submit", "sonic_dispatch_cancel", "sonic_dispatch_next", "sonic_dispatch_stats", "sonic_dispatch_close", "sonic_dispatch_destroy",
     "sonic_pipeline_create", "sonic_pipeline_submit", "sonic_pipeline_wait", "sonic_pipeline_stats", "sonic_pipeline_last_error", "sonic_pipeline_destroy",
+    "sonic_vad_create", "sonic_vad_destroy", "sonic_vad_last_error", "sonic_vad_load_tensor", "sonic_vad_probs",
 ]
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 class SonicDims(C.Structure):
@@ -161,6 +162,13 @@ def load_library():
     lib.sonic_service_step.argtypes = [vp, C.c_int, C.c_int, vp, vp, i64p, ip]
     lib.sonic_fetch_row.argtypes = [vp, C.c_int, C.c_int, vp]
     lib.sonic_fetch_rows.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int]
+    lib.sonic_vad_create.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]
+    lib.sonic_vad_destroy.argtypes = [vp]
+    lib.sonic_vad_destroy.restype = None
+    lib.sonic_vad_last_error.argtypes = [vp]
+    lib.sonic_vad_last_error.restype = C.c_char_p
+    lib.sonic_vad_load_tensor.argtypes = [vp, C.c_char_p, vp, i64p, C.c_int]
+    lib.sonic_vad_probs.argtypes = [vp, vp, vp, vp, C.c_int, vp]
     for name in EXPORTS:
         getattr(lib, name)
     if lib.sonic_abi_version() != ABI_VERSION:
