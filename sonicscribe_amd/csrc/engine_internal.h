@@ -1,0 +1,264 @@
+// What the translation units of the engine (engine.cpp, engine_weights.cpp, engine_stages.cpp, engine_f32.cpp, engine_ingest.cpp,
+// engine_service.cpp, engine_hooks.cpp) share: the engine struct and its parts, the constants, the error / entry macros and the helpers that
+// cross a unit boundary.  Not part of the C ABI (include/sonic_hip.h); a function used by one unit only is static there.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <atomic>
+#include <algorithm>
+#include <chrono>
+#include <condition_variable>
+#include <map>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/sonic_hip.h"
+#include "common.h"
+#include "kernels.h"
+
+#define T_PAD_ALIGN 64
+#define CHK_RING 64            // check events / pinned n_active words of the decode loop
+#define DEV_ERR_ACTIVE (-(1 << 23))   // a running-row count below this: the device error word was set (greedy_kernel), the step's outputs are invalid
+#define SVC_WORDS 132           // per check of the continuous loop: finished[64], n_new[64], n_active, padding
+#define CHK_MAX_AHEAD 32       // deepest lookahead in chunks (a host that is frozen for tens of ms at a time - CPU quota, a busy event loop)
+
+struct DevTensor {
+    std::vector<int64_t> shape;
+    bf16_t* p = nullptr;
+    size_t n = 0;
+};
+
+// int8 mode (asr.py:169-210): a quantised Linear keeps row-wise int8 weights + row absmax instead of its 16-bit matrix
+struct QW { int8_t* cb = nullptr; float* scb = nullptr; int8_t* cbt = nullptr; int8_t* cbk = nullptr; bool cb_rowmajor_kept = true; };   // cbt: fragment-tiled copy, cbk: k-major copy (decode step)
+struct EncLayerW { float *ln1w, *ln1b, *bqkv, *bo, *ln2w, *ln2b, *b1, *b2; bf16_t *wqkv, *wo, *w1, *w2; QW qqkv, qo, q1, q2; };
+#define KT_SLOT_BLOCKS 512                                   // "ktrace" diagnostics: blocks recorded per kernel slot, 8 timestamps each
+struct DecLayerW { float *ln1, *ln2; bf16_t *wqkv, *wo, *wgu, *wdown;          // row-major (prefill GEMM)
+                   bf16_t *wqkv_t, *wo_t, *wgu_t, *wgu_t8, *wdown_t;                    // fragment-tiled copies (decode skinny GEMM)
+                   QW qqkv, qo, qgu, qdown; };
+
+// SONIC_MODE_F32 (test only, f32kind.hip): fp32 weights as loaded (torch Linear layout, nothing packed but the conv taps) and fp32 activation buffers
+struct F32EncL { float *ln1w, *ln1b, *wq, *bq, *wk, *wv, *bv, *wo, *bo, *ln2w, *ln2b, *w1, *b1, *w2, *b2; };
+struct F32DecL { float *ln1, *wq, *wk, *wv, *wo, *ln2, *wg, *wu, *wd; };
+struct F32State {
+    std::map<std::string, float*> raw;               // name -> device tensor (owned by the engine's alloc list)
+    float *conv1w = nullptr, *conv1b = nullptr, *conv2w = nullptr, *conv2b = nullptr, *enc_nw = nullptr, *enc_nb = nullptr;
+    float *pj1w = nullptr, *pj1b = nullptr, *pj2w = nullptr, *pj2b = nullptr, *embed = nullptr, *dec_nw = nullptr;
+    std::vector<F32EncL> enc; std::vector<F32DecL> dec;
+    // encoder: time-major padded features, conv1 output (padded), residual stream, norm output, q / k / v, attention output, MLP, projector
+    float *featT = nullptr, *h1 = nullptr, *x = nullptr, *ln = nullptr, *q = nullptr, *k = nullptr, *v = nullptr, *att = nullptr, *ff = nullptr, *ph = nullptr, *pe = nullptr;
+    // decoder: token rows of the prefill (or the R rows of a token step), KV cache [layer][seq][ctx][KD], logits [64][vocab]
+    float *dx = nullptr, *dhn = nullptr, *dq = nullptr, *dk = nullptr, *dv = nullptr, *datt = nullptr, *dg = nullptr, *du = nullptr, *dact = nullptr;
+    float *Kc = nullptr, *Vc = nullptr, *logits = nullptr, *hlast = nullptr;
+};
+
+struct sonic_engine {
+    sonic_dims d;
+    int device = 0, mode = 0, Bm = 0, max_ctx = 0;
+    int dt = DT_BF16;          // activation / 16-bit weight element type: bf16 (native) or fp16 (int8 mode, asr.py:61)
+    bool i8 = false;           // LLM.int8 linears
+    bool f32 = false;          // SONIC_MODE_F32: the fp32 kind of every stage (test only; F32State, f32kind.hip)
+    F32State* f = nullptr;
+    hipStream_t st = nullptr;
+    std::mutex mu;
+    std::string err;
+    std::vector<void*> allocs;
+    bool cap_svc = false;                           // a continuous loop's chunk graph is being captured (chunk_graph)
+    int64_t weight_bytes = 0, alloc_bytes = 0;      // alloc_bytes: every live device allocation of this engine (sonic_memory_info)
+    bool finalized = false;
+
+    std::map<std::string, DevTensor> raw;
+    // packed weights
+    bf16_t *conv1w = nullptr, *conv2w = nullptr; float *conv1b = nullptr, *conv2b = nullptr;
+    std::vector<EncLayerW> enc;
+    float *enc_nw = nullptr, *enc_nb = nullptr;
+    unsigned short* gelu_lut = nullptr;     // bf16 GELU table (gemm256 EPI_BIAS_GELU epilogue), native mode
+    bf16_t *pj1w = nullptr, *pj2w = nullptr; float *pj1b = nullptr, *pj2b = nullptr; QW qpj1, qpj2;
+    // int8 mode scratch: quantised activations of the GEMM in flight, row statistics, outlier columns per request, window -> request map
+    int8_t* qa = nullptr; float* q_sca = nullptr; unsigned char* q_flags = nullptr; int *q_oc_cnt = nullptr, *q_oc_list = nullptr, *win_req = nullptr;
+    int q_kmax = 0; bf16_t* qkv_rm = nullptr;
+    bf16_t* defer_tmp = nullptr; size_t defer_cap = 0; int opt_i8_defer_thr = 8; int opt_i8_no_xq = 0; int opt_i8_no_lnq = 0; int opt_i8_dbg = 0; int opt_i8_no_qkv_fuse = 0;   // rows deferred to the outlier side product leave the GEMM here
+    // int8 decode step: the three quantised row sets (input norm output, attention output, SwiGLU output)
+    int8_t *hn_q = nullptr, *att_q = nullptr, *act_q = nullptr; float *sca_hn = nullptr, *sca_att = nullptr, *sca_act = nullptr;
+    int *oc_hn = nullptr, *oc_att = nullptr, *oc_act = nullptr, *ol_hn = nullptr, *ol_att = nullptr, *ol_act = nullptr;
+    float *ov_hn = nullptr, *ov_att = nullptr, *ov_act = nullptr;      // the outliers' values beside the lists
+    int* big_att = nullptr;                                             // [64][4] per-block counts of attention outputs >= 6.0
+    float *amax_att = nullptr, *amax_act = nullptr;                     // [64][4] partial row maxima written by producers that do not own whole rows
+    std::map<std::string, bool> raw_f16;   // int8 mode: tensors already converted to fp16 at load
+    bf16_t* embed = nullptr; bf16_t* embed_t = nullptr;
+    std::vector<DecLayerW> dec;
+    float* dec_nw = nullptr;
+
+    // derived sizes
+    int T = 0, Tp = 0, Ta = 0, hd_e = 0, qkvN = 0, QD = 0, KD = 0, tok_cap = 0, out_cap = 0;
+    long slabN = 0;
+
+    // front-end
+    int16_t* pcm = nullptr; int* n_samples_d = nullptr; std::vector<int> n_samples_h; int W = 0;
+    float* logspec = nullptr; int* segmax = nullptr; bf16_t* feats_fm = nullptr; float* feats_f32 = nullptr;
+    LogmelConst lc{};
+    // encoder
+    bf16_t *h1 = nullptr, *x = nullptr, *ln = nullptr, *qk = nullptr, *vt = nullptr, *att = nullptr, *ff = nullptr, *ph = nullptr, *pe = nullptr;
+    float* enc_cs = nullptr;
+    // decoder
+    bf16_t *dx = nullptr, *dhn = nullptr, *dqkv = nullptr, *dq = nullptr, *datt = nullptr, *dact = nullptr;
+    bf16_t *Kc = nullptr, *Vc = nullptr, *Vts = nullptr;
+    float* dec_cs = nullptr;
+    float *slab = nullptr, *lslab = nullptr, *ssq = nullptr;
+    float* slab2 = nullptr;                                         // down_proj's slabs when the next q|k|v (or the lm_head) consumes them itself (PRE form, <= 2 rows)
+    bf16_t *sx = nullptr, *shn = nullptr, *sq = nullptr, *satt = nullptr, *sact = nullptr;
+    bf16_t* sx2 = nullptr;                                          // ... and the second residual buffer of that form (the stream ping-pongs layer by layer)
+    int *kv_len = nullptr, *tok_pos = nullptr, *n_new = nullptr, *finished = nullptr, *max_new_d = nullptr, *n_active = nullptr;
+    int *out_ids = nullptr, *step_ctr = nullptr, *seq_iota = nullptr;
+    int *src = nullptr, *tok_seq = nullptr, *tok_pos_pf = nullptr, *q_off = nullptr, *q_len = nullptr, *last_row = nullptr;
+    float* dump = nullptr; size_t dump_cap = 0; int dump_steps = 0;
+    bf16_t* taps = nullptr; int taps_on = 0; int last_ntok = 0;   // debug: prefill hidden states after embedding + each layer
+    int* n_active_h = nullptr;  // pinned
+    int R = 0, max_steps = 0, greedy_calls = 0, steps_run = 0; bool run_logits = false;   // state of the staged batch between the stage entry points
+    int* force_d = nullptr; int force_ld = 0, force_R = 0;   // teacher forcing for the next runs (sonic_set_forced_ids)
+    std::vector<int> last_qlen, last_maxnew;
+    std::map<std::pair<int, int>, hipGraphExec_t> graphs;        // (rows, token steps) -> captured chunk of the decode loop
+    // the pipelined early-stop check: behind every chunk the device's count of running rows is copied to n_active_h[chunk % CHK_RING] and an
+    // event is recorded; the host reads check k only when chunk k + lookahead is already queued (run_decode_steps)
+    hipEvent_t chk_ev[CHK_RING]{};
+    bool run_starved = false;                                      // the current batch saw the queue run dry (lookahead grew)
+    int lookahead = 1;                                             // chunks queued beyond the one whose check the host waits for; adapts (1..CHK_MAX_AHEAD)
+    int* plan_h = nullptr; size_t plan_cap = 0;                    // pinned staging of a batch's prompt plan (no stream synchronise between encoder and prefill)
+    // Two staging buffers used alternately, each with an event recorded behind the last copy that reads it: sonic_prefill_enqueue returns with those
+    // copies still queued behind the encoder, and the next run on this handle must not overwrite a buffer the stream has not read yet
+    int* plan_buf[2] = {nullptr, nullptr}; hipEvent_t plan_ev[2] = {nullptr, nullptr}; bool plan_busy[2] = {false, false}; int plan_idx = 0;
+
+    // Slots (sonic_slot_create): further in-flight batches on ONE weight copy.  A slot is an engine of its own in every respect - stream, activation
+    // buffers, KV cache, PCM staging, decode graphs, lock, options - except that its weight / constant pointers are the owner's.
+    sonic_engine* owner = nullptr;                                 // slot: whose weights these are (never a slot itself)
+    std::vector<sonic_engine*> slots;                              // owner: its slots (destroyed with it at the latest)
+    std::mutex rings_mu;                                           // owner: guards `rings` (the registry every slot stages from)
+
+    // continuous decoding (sonic_service_*): this engine's rows are a pool - requests prefilled on another handle of the same weights are spliced
+    // into free rows between chunks of an endless greedy loop, finished rows are fetched and freed one by one
+    bool svc_on = false;
+    int64_t svc_launched = 0, svc_checked = 0;                     // chunks queued / checks read since sonic_service_begin
+    int64_t svc_dry = 0;                                           // launches that found the stream empty with rows running (diagnostics)
+    int svc_calm = 0;                                              // chunks since the queue last ran dry (the lookahead shrinks again after 256 of them)
+    int* svc_h = nullptr;                                          // pinned ring [CHK_RING][SVC_WORDS]: finished[64] | n_new[64] | n_active
+    int svc_fin[64]{}, svc_nn[64]{}, svc_active = 0; int64_t svc_seq = 0;   // the newest check read: state after chunk number svc_seq
+    hipEvent_t sync_ev = nullptr;                                  // blocking-sync event behind stream_sync()
+    hipStream_t st_io = nullptr;                                   // row fetches (a finished row's ids are stable: no ordering against the queued chunks needed)
+    hipEvent_t xfer_ev = nullptr, splice_ev = nullptr, wait_ev = nullptr; bool wait_pending = false;   // cross-handle ordering of a splice
+
+    // sonic_run_staged_async / sonic_wait: a worker thread of the engine's own runs the batch, the caller's thread returns at once
+    struct AsyncJob { std::vector<int32_t> req_win, prompt_ids, max_new; std::vector<int64_t> prompt_off; int R = 0; bool has_rw = false; int want_logits = 0; } a_job;
+    std::thread a_thread; std::mutex a_mu; std::condition_variable a_cv;
+    bool a_started = false, a_pending = false, a_running = false, a_done = false, a_stop = false; int a_status = 0;
+
+    // experiment knobs (sonic_set_option): per engine, copied into the launchers' thread-local view by ENTER()
+    LaunchOpts opts;
+    int opt_no_graph = 0, opt_gemm_timing = 0, opt_no_fused_rope = 0, opt_no_gelu_lut = 0, opt_gemm_trace = 0, opt_no_rope_tiles = 0, opt_prefill_rowmajor = 0;
+    double host_launch_ms = 0, host_wait_ms = 0; int host_launches = 0;   // host time of the last run's decode loop: inside hipGraphLaunch / waiting for a check
+    int step_launches_per_layer = 0;   // of the token step built last (decode_step): sonic_timings.decode_launches_per_layer
+    int opt_f32_synth_bf16 = 0;    // SONIC_MODE_F32: sonic_load_synthetic writes the bf16-rounded values (the weights a bf16 engine gets from the same seed) as fp32
+    int opt_decode_gemv = 0;       // 1: token steps of <= 4 rows run the GEMV chain (gemv.hip: five launches per layer, no MFMA tiles); opt-in - another summation order than the
+                                   // MFMA chain, so a request's low bits then depend on whether its step had <= 4 rows.  Measured slower than the MFMA chain (profiles/round6_gemv_ab.txt): an experiment, off
+    int opt_no_pre_norm = 0;       // 1: never the PRE form of the <= 2-row decode step (standalone add+RMSNorm launches as for more rows; A/B - same bits)
+    int opt_decode_chunk = 2;      // token steps per captured graph = granularity of the early-stop check (sonic_set_option "decode_chunk")
+    long long* kt = nullptr; int kt_layer = -1;     // diagnostics ("ktrace" option): in-kernel timestamps of one decoder layer's kernels
+    int* ring_peak = nullptr;                        // [Bm] per-request max |s| of a ring-staged batch (ingest.hip)
+    std::vector<struct sonic_ring*> rings;          // rings created on this engine and not yet destroyed (freed with the engine at the latest)
+
+    // timing
+    hipEvent_t ev[5]{};
+    std::vector<hipEvent_t> gemm_ev;
+    int gemm_ev_used = 0;
+    sonic_timings tim{};
+};
+
+// Rows -> reference-call groups for LLM.int8's outlier columns: group of row r = gmap ? gmap[r / gdiv] : r / gdiv, G groups
+struct QGroup { const int* gmap; int gdiv; int G; };
+// the encoder's fused q|k|v linear in int8 mode: where V^T goes when the 256x256 kernel can take the whole epilogue (RoPE on q / k on the way out
+// of the staged tile, V transposed while staging)
+struct QkvVt { bf16_t* Vt; int n_split, seg_T, vt_ld; long vt_seg_stride; };
+
+struct HostPlan {
+    std::vector<int> src, tok_seq, tok_pos, q_off, q_len, last_row, max_new;
+    int n_tok = 0, max_p = 0, max_steps = 0;
+};
+
+#define HIPC(e, call)                                                                                      \
+    do {                                                                                                   \
+        hipError_t _r = (call);                                                                            \
+        if (_r != hipSuccess) {                                                                            \
+            const bool oom = (_r == hipErrorOutOfMemory);                                                  \
+            return fail(e, oom ? SONIC_ERR_OOM : SONIC_ERR_HIP, "%s%s failed: %s (%s:%d)",                 \
+                        oom ? "HIP out of memory: " : "", #call, hipGetErrorString(_r), __FILE__, __LINE__); \
+        }                                                                                                  \
+    } while (0)
+
+#define TRY(x) do { int _s = (x); if (_s != SONIC_OK) return _s; } while (0)
+// every locked C-ABI entry: serialise on the engine, select its device, and hand its experiment knobs to the launchers
+// (hipGetLastError first: the slot is per thread and sticky, so a failure some earlier call of this thread ignored would otherwise
+// surface at this call's closing hipGetLastError check)
+#define ENTER(e) std::lock_guard<std::mutex> lk((e)->mu); (void)hipGetLastError(); HIPC(e, hipSetDevice((e)->device)); g_opts = (e)->opts
+
+// ------------------------------------------------------------------------------------------ helpers (engine.cpp)
+int fail(sonic_engine* e, int code, const char* fmt, ...);
+hipError_t stream_sync(sonic_engine* e);
+hipError_t h2d(sonic_engine* e, void* dst, const void* src, size_t bytes);
+hipError_t d2h_async(sonic_engine* e, void* dst, const void* src, size_t bytes);
+hipError_t d2h(sonic_engine* e, void* dst, const void* src, size_t bytes);
+void zero_fill(sonic_engine* e, void* q, size_t bytes);
+// Every device buffer is an ordinary hipMalloc allocation that sonic_destroy hands back to the driver (`del asr_model.model` is expected to
+// return the VRAM: backend/main.py:84-90).  Rounds 2-3 kept the per-step activation buffers (and, in round 2, the KV cache and the tiled
+// weights) in uncached (MTYPE UC) memory, parked in a process-wide pool that was never freed, because memory recycled between uncached and
+// ordinary allocations came back with stale cache lines on this stack (tests/test_gemm256_path failed in 3 of 5 full-suite runs; root cause
+// never found, tools/uc_recycle_repro.hip excludes two mechanisms).  Round 4 measured what the uncached buffers were still worth: nothing
+// (bench.py, one box, SONIC_NO_UC=1 vs default: 126.27 vs 126.17 segments/s with two slots, 103.3 vs 103.6 one batch at a time - inside the
+// run-to-run spread), so the uncached path, its pool and sonic_release_pool are gone rather than kept alive for an unmeasurable gain.
+template <typename Tt> static int dalloc(sonic_engine* e, Tt** p, size_t n, bool zero = true) {
+    void* q = nullptr;
+    const size_t bytes = ((n ? n : 1) * sizeof(Tt) + 3) / 4 * 4;
+    HIPC(e, hipMalloc(&q, bytes));
+    e->allocs.push_back(q); e->alloc_bytes += (int64_t)bytes;
+    if (zero) zero_fill(e, q, bytes);
+    *p = (Tt*)q;
+    return SONIC_OK;
+}
+
+// ------------------------------------------------------------------------------------------ pipeline stages (engine_stages.cpp)
+void gemm(sonic_engine* e, int epi, const bf16_t* A, long lda, const bf16_t* W, const float* bias, bf16_t* C, long ldc,
+          int M, int N, int K, const bf16_t* R = nullptr, long ldr = 0, int w_tiled = 0, int gu8 = 0);
+bool qlinear(sonic_engine* e, int epi, const bf16_t* X, long ldx, const bf16_t* w16, const QW& q, const float* bias, bf16_t* C, long ldc,
+             int M, int N, int K, const bf16_t* R, long ldr, const QGroup& grp, const float* rope_cs = nullptr, int rope_T = 0, int rope_ncols = 0,
+             bool prequant = false, const QkvVt* vt = nullptr);
+int run_mel(sonic_engine* e, int W, bool want_f32);
+int run_encoder(sonic_engine* e, int W, float* enc_layers_out, float* enc_out_host, int n_groups);
+int keep_rows(const sonic_dims& d, int n_valid_frames);
+int frames_of(int n_samples);
+void skinny(sonic_engine* e, const bf16_t* X, long ldx, const bf16_t* W, float* P, int M, int N, int K, int* ks_out, long long* kt = nullptr);
+GreedyArgs greedy_args(sonic_engine* e, int R, bool dump);
+void decode_step_i8(sonic_engine* e, int R, bool dump);
+int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off,
+                       const int32_t* max_new, bool want_logits);
+int chunk_graph(sonic_engine* e, int R, int n, hipGraphExec_t* out, bool svc = false);
+int run_decode_steps(sonic_engine* e, int n_steps, int* done_out);
+int run_all(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off,
+            const int32_t* max_new, bool want_logits);
+
+// ------------------------------------------------------------------------------------------ SONIC_MODE_F32 (engine_f32.cpp)
+int f32_alloc(sonic_engine* e);
+int f32_finalize(sonic_engine* e);
+int f32_run_encoder(sonic_engine* e, int W, float* enc_layers_out, float* enc_out_host);
+GreedyArgs f32_greedy_args(sonic_engine* e, int R, bool dump);
+int f32_run_prefill(sonic_engine* e, int R, const HostPlan& hp);
+void decode_step_f32(sonic_engine* e, int R, bool dump);
+
+// ------------------------------------------------------------------------------------------ ingest (engine_ingest.cpp), service (engine_service.cpp)
+int stage_pcm_locked(sonic_engine* e, const int16_t* pcm, const int64_t* offsets, int W);
+void ring_free(sonic_ring* r);
+void async_shutdown(sonic_engine* e);
+int fetch_locked(sonic_engine* e, int32_t* out_ids, int out_ld, int32_t* out_len, float* step_logits);

@@ -1,0 +1,696 @@
+// sonic_hip engine: the stages of the bf16 / fp16 / int8 pipeline on the engine stream - GEMM wrappers, log-mel, encoder, request plan, prefill,
+// the token step and its captured chunk graphs, the greedy loop.
+#include "engine_internal.h"
+
+// ------------------------------------------------------------------------------------------ pipeline stages
+void gemm(sonic_engine* e, int epi, const bf16_t* A, long lda, const bf16_t* W, const float* bias, bf16_t* C, long ldc,
+          int M, int N, int K, const bf16_t* R, long ldr, int w_tiled, int gu8) {
+    GemmArgs a{};
+    a.A = A; a.lda = lda; a.W = W; a.C = C; a.ldc = ldc; a.bias = bias; a.R = R; a.ldr = ldr; a.M = M; a.N = N; a.K = K; a.batch = 1; a.dt = e->dt;
+    a.w_tiled = w_tiled; a.gu8 = gu8;
+    a.gelu_lut = e->opt_no_gelu_lut ? nullptr : e->gelu_lut;
+    launch_gemm(a, epi, e->st);
+}
+// One nn.Linear of the model on X [M][K] (row stride ldx).  Native mode: the 16-bit GEMM.  int8 mode and a swapped module (q.cb):
+// Linear8bitLt = activation quantisation (3 streaming passes) + int8 MFMA GEMM whose epilogue dequantises and adds the outlier columns.
+// rope_cs (optional): fuse the encoder's partial RoPE on columns < rope_ncols into the epilogue; returns whether it was fused (only the
+// 256x256 kernel does it), else the caller runs the separate RoPE pass.
+static QuantActArgs make_qa(sonic_engine* e, const bf16_t* X, long ldx, int M, int K, const QGroup& grp) {
+    QuantActArgs qa{};
+    qa.X = X; qa.ld = ldx; qa.M = M; qa.K = K; qa.gmap = grp.gmap; qa.gdiv = grp.gdiv; qa.G = grp.G; qa.flags = e->q_flags;
+    qa.q = e->qa; qa.sca = e->q_sca; qa.oc_cnt = e->q_oc_cnt; qa.oc_list = e->q_oc_list; qa.oc_ld = e->q_kmax;
+    return qa;
+}
+// LayerNorm whose output feeds a Linear8bitLt directly (ld == K == d): in int8 mode the norm kernel also quantises the row
+static bool layernorm_q(sonic_engine* e, const bf16_t* x, const float* w, const float* b, bf16_t* y, int M, int d, float eps, const QGroup& grp) {
+    if (e->i8 && !e->opt_i8_no_lnq) {
+        const QuantActArgs qa = make_qa(e, y, d, M, d, grp);
+        launch_quant_act_begin(qa, e->st);
+        launch_layernorm(x, w, b, y, M, d, eps, e->st, e->dt, &qa);
+        return true;
+    }
+    launch_layernorm(x, w, b, y, M, d, eps, e->st, e->dt);
+    return false;
+}
+static bool rmsnorm_q(sonic_engine* e, const bf16_t* x, const float* w, bf16_t* y, int M, int d, float eps, const QGroup& grp) {
+    if (e->i8 && !e->opt_i8_no_lnq) {
+        const QuantActArgs qa = make_qa(e, y, d, M, d, grp);
+        launch_quant_act_begin(qa, e->st);
+        launch_rmsnorm(x, w, y, M, d, eps, nullptr, e->st, e->dt, &qa);
+        return true;
+    }
+    launch_rmsnorm(x, w, y, M, d, eps, nullptr, e->st, e->dt);
+    return false;
+}
+bool qlinear(sonic_engine* e, int epi, const bf16_t* X, long ldx, const bf16_t* w16, const QW& q, const float* bias, bf16_t* C, long ldc,
+             int M, int N, int K, const bf16_t* R, long ldr, const QGroup& grp, const float* rope_cs, int rope_T, int rope_ncols,
+             bool prequant, const QkvVt* vt) {
+    if (!e->i8 || !(q.cb || q.cbt)) { gemm(e, epi, X, ldx, w16, bias, C, ldc, M, N, K, R, ldr); return false; }
+    const QuantActArgs qa = make_qa(e, X, ldx, M, K, grp);
+    if (prequant) launch_quant_act_finish(qa, e->st);      // the LayerNorm that wrote X also wrote its codes, absmax and flags
+    else launch_quant_act(qa, e->st);
+    GemmArgs a{};
+    a.A = (const bf16_t*)e->qa; a.lda = K; a.W = (const bf16_t*)q.cb; a.C = C; a.ldc = ldc; a.bias = bias; a.R = R; a.ldr = ldr; a.M = M; a.N = N; a.K = K; a.batch = 1; a.dt = DT_F16;
+    // decoder projections: ONE int8 operand copy since round 5 - the fragment-tiled one of the decode step (+ the k-major copy for outlier columns)
+    if (q.cbt && (!e->opt_prefill_rowmajor || !q.cb_rowmajor_kept)) { a.W = (const bf16_t*)q.cbt; a.w_tiled = 1; }     // (outlier columns are gathered from the tiled copy)
+    a.q.sca = e->q_sca; a.q.scb = q.scb; a.q.x16 = X; a.q.ldx16 = ldx; a.q.oc_cnt = e->q_oc_cnt; a.q.oc_list = e->q_oc_list; a.q.oc_ld = e->q_kmax;
+    a.q.row_group = grp.gmap; a.q.group_div = grp.gdiv;
+    // int8 q|k|v: RoPE + V^T inside the GEMM's epilogue (round 3; the register form of the 16-bit kinds spilled beside the dequantisation, the int8
+    // kind does both on the staged tile).  Returns true: the caller skips its RoPE and transpose passes.
+    bool fuse = false;
+    if (vt && rope_cs && !e->opt_i8_no_qkv_fuse && !g_opts.gemm_force128) {
+        GemmArgs t = a; t.Vt = vt->Vt; t.n_split = vt->n_split; t.seg_T = vt->seg_T; t.vt_ld = vt->vt_ld; t.vt_seg_stride = vt->vt_seg_stride;
+        if (gemm256_eligible(t, EPI_QKV_VT)) { a = t; a.rope_cs = rope_cs; a.rope_T = rope_T; a.rope_ncols = rope_ncols; epi = EPI_QKV_VT; fuse = true; }
+    }
+    // residual-epilogue linears (o_proj, fc2, down_proj: their inputs are activation outputs, where long outlier lists occur): requests with
+    // more than `i8_defer_thr` outlier columns are finished by the dense side product instead of the epilogue's per-element list walk
+    const bool defer = epi == EPI_BIAS_RESID && e->defer_tmp && e->opt_i8_defer_thr >= 0 && (size_t)M * ldc <= e->defer_cap;
+    if (defer) { a.q.defer_out = e->defer_tmp; a.q.defer_thr = e->opt_i8_defer_thr; }
+    launch_gemm(a, epi, e->st);
+    if (defer) launch_i8_outlier_side(a, e->st);
+    return fuse;
+}
+
+int run_mel(sonic_engine* e, int W, bool want_f32) {
+    const sonic_dims& d = e->d;
+    if (want_f32 && !e->feats_f32) {
+        HIPC(e, hipMalloc((void**)&e->feats_f32, (size_t)e->Bm * d.n_mels * d.n_frames * 4));
+    }
+    int mx = 0; for (int i = 0; i < W; ++i) mx = e->n_samples_h[i] > mx ? e->n_samples_h[i] : mx;
+    launch_logmel(e->pcm, (long)d.n_frames * 160, e->n_samples_d, mx, e->lc, e->logspec, e->segmax, W, d.n_frames, d.n_mels,
+                  e->feats_fm, want_f32 ? e->feats_f32 : nullptr, e->st, e->dt);
+    return SONIC_OK;
+}
+
+// feats_fm (16-bit, frame-major, padded) -> pe [W*Ta][dec_d].  win_group: request of each window (int8 mode: LLM.int8 finds its outlier
+// columns over all rows of one reference call, i.e. over all windows of a request - HF runs them as one encoder batch)
+int run_encoder(sonic_engine* e, int W, float* enc_layers_out, float* enc_out_host, int n_groups) {
+    const sonic_dims& d = e->d;
+    const int C = d.enc_d, T = e->T, M = W * T, H = d.enc_heads, dt = e->dt;
+    const QGroup grp{e->win_req, T, n_groups}, grp_p{e->win_req, e->Ta, n_groups};
+    {   // conv stem as two batched im2col-free GEMMs (modeling_glmasr.py:313-316); nn.Conv1d is not swapped in int8 mode
+        GemmArgs a{};
+        a.A = e->feats_fm; a.lda = d.n_mels; a.W = e->conv1w; a.bias = e->conv1b; a.C = e->h1 + C; a.ldc = C; a.dt = dt;
+        a.M = d.n_frames; a.N = C; a.K = 3 * d.n_mels; a.batch = W;
+        a.strideA = (long)(d.n_frames + 2) * d.n_mels; a.strideC = (long)(d.n_frames + 2) * C;
+        launch_gemm(a, EPI_BIAS_GELU, e->st);
+        GemmArgs b{};
+        b.A = e->h1; b.lda = 2L * C; b.W = e->conv2w; b.bias = e->conv2b; b.C = e->x; b.ldc = C; b.dt = dt;
+        b.M = T; b.N = C; b.K = 3 * C; b.batch = W; b.strideA = (long)(d.n_frames + 2) * C; b.strideC = (long)T * C;
+        launch_gemm(b, EPI_BIAS_GELU, e->st);
+    }
+    float* tap = nullptr;
+    if (enc_layers_out || enc_out_host) HIPC(e, hipMalloc((void**)&tap, (size_t)M * C * 4));
+    e->gemm_ev_used = 0;
+    for (int l = 0; l < d.enc_layers; ++l) {
+        const EncLayerW& L = e->enc[l];
+        const bool pq1 = layernorm_q(e, e->x, L.ln1w, L.ln1b, e->ln, M, C, d.enc_ln_eps, grp);
+        const bool tev = e->opt_gemm_timing && (size_t)(8 * l + 7) < e->gemm_ev.size();
+        auto mark = [&](int i) { if (tev) (void)hipEventRecord(e->gemm_ev[8 * l + i], e->st); };
+        FlashArgs f{};
+        f.dt = dt; f.T = T; f.Hq = H; f.Hkv = H; f.scale = 1.0f / sqrtf((float)e->hd_e); f.Vt = e->vt; f.vt_ld = e->Tp; f.O = e->att; f.o_ld = C;
+        f.k_head_stride = e->hd_e; f.vt_seq_stride = (long)C * e->Tp; f.vt_head_stride = (long)e->hd_e * e->Tp;
+        if (e->i8) {
+            // Linear8bitLt q / k / v share their input, hence one quantisation and one fused int8 GEMM; Q | K | V land row-major
+            // ([M][3C]) and V is transposed by its own pass (the fused V^T epilogue plus the dequantisation spills registers)
+            mark(0);
+            const bool can_fuse = e->hd_e == 64 && d.enc_rotary_dim == 32 && !e->opt_no_fused_rope;
+            const QkvVt vt{e->vt, 2 * C, T, e->Tp, (long)C * e->Tp};
+            const bool fused = qlinear(e, EPI_BIAS, e->ln, C, nullptr, L.qqkv, L.bqkv, e->qkv_rm, 3L * C, M, 3 * C, C, nullptr, 0, grp,
+                                       can_fuse ? e->enc_cs : nullptr, T, 2 * C, pq1, &vt);
+            mark(1);
+            if (!fused) {
+                launch_rope_enc(e->qkv_rm, 3L * C, M, T, 2 * H, e->hd_e, d.enc_rotary_dim, e->enc_cs, e->st, dt);
+                launch_transpose_v(e->qkv_rm, 3L * C, 2 * C, e->vt, W, T, C, e->Tp, (long)C * e->Tp, e->st);
+            }
+            f.Q = e->qkv_rm; f.q_ld = 3L * C; f.K = e->qkv_rm + C; f.k_ld = 3L * C;
+            f.q_seq_stride = (long)T * 3 * C; f.k_seq_stride = (long)T * 3 * C;
+        } else {
+            GemmArgs a{};
+            a.A = e->ln; a.lda = C; a.W = L.wqkv; a.bias = L.bqkv; a.C = e->qk; a.ldc = 2L * C; a.M = M; a.N = 3 * C; a.K = C; a.batch = 1; a.dt = dt;
+            a.Vt = e->vt; a.n_split = 2 * C; a.seg_T = T; a.vt_ld = e->Tp; a.vt_seg_stride = (long)C * e->Tp;
+            // partial RoPE of q / k in the GEMM's epilogue (the rotation pairs are in one lane's accumulators): no separate HBM pass
+            const bool roped = e->hd_e == 64 && d.enc_rotary_dim == 32 && !e->opt_no_fused_rope && !g_opts.gemm_force128 && gemm256_eligible(a, EPI_QKV_VT);
+            if (roped) { a.rope_cs = e->enc_cs; a.rope_T = T; a.rope_ncols = 2 * C; }
+            mark(0);
+            launch_gemm(a, EPI_QKV_VT, e->st);
+            mark(1);
+            if (!roped) launch_rope_enc(e->qk, 2L * C, M, T, 2 * H, e->hd_e, d.enc_rotary_dim, e->enc_cs, e->st, dt);
+            f.Q = e->qk; f.q_ld = 2L * C; f.K = e->qk + C; f.k_ld = 2L * C;
+            f.q_seq_stride = (long)T * 2 * C; f.k_seq_stride = (long)T * 2 * C;
+        }
+        launch_flash(f, 64, false, W, T, e->st);
+        mark(2);
+        qlinear(e, EPI_BIAS_RESID, e->att, C, L.wo, L.qo, L.bo, e->x, C, M, C, C, e->x, C, grp);
+        mark(3);
+        const bool pq2 = layernorm_q(e, e->x, L.ln2w, L.ln2b, e->ln, M, C, d.enc_ln_eps, grp);
+        mark(4);
+        qlinear(e, EPI_BIAS_GELU, e->ln, C, L.w1, L.q1, L.b1, e->ff, d.enc_ff, M, d.enc_ff, C, nullptr, 0, grp, nullptr, 0, 0, pq2);
+        mark(5);
+        if (tev) e->gemm_ev_used = l + 1;
+        mark(6);
+        qlinear(e, EPI_BIAS_RESID, e->ff, d.enc_ff, L.w2, L.q2, L.b2, e->x, C, M, C, d.enc_ff, e->x, C, grp);
+        mark(7);
+        if (enc_layers_out) {
+            launch_bf16_to_f32(e->x, tap, (long)M * C, e->st, dt);
+            HIPC(e, stream_sync(e));
+            for (int b = 0; b < W; ++b)
+                HIPC(e, d2h(e, enc_layers_out + ((size_t)b * d.enc_layers + l) * T * C, tap + (size_t)b * T * C, (size_t)T * C * 4));
+        }
+    }
+    launch_layernorm(e->x, e->enc_nw, e->enc_nb, e->ln, M, C, d.enc_ln_eps, e->st, dt);
+    if (enc_out_host) {
+        launch_bf16_to_f32(e->ln, tap, (long)M * C, e->st, dt);
+        HIPC(e, stream_sync(e));
+        HIPC(e, d2h(e, enc_out_host, tap, (size_t)M * C * 4));
+    }
+    if (tap) (void)hipFree(tap);
+    // 4-frame merge is a view: [M][C] == [W*Ta][4C] (modeling_glmasr.py:392-397)
+    const int Mp = W * e->Ta, PI = C * d.merge, PM = 2 * d.dec_d;
+    qlinear(e, EPI_BIAS_GELU, e->ln, PI, e->pj1w, e->qpj1, e->pj1b, e->ph, PM, Mp, PM, PI, nullptr, 0, grp_p);
+    qlinear(e, EPI_BIAS, e->ph, PM, e->pj2w, e->qpj2, e->pj2b, e->pe, d.dec_d, Mp, d.dec_d, PM, nullptr, 0, grp_p);
+    return SONIC_OK;
+}
+
+static int floordiv(int a, int b) { int q = a / b; return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q; }
+int keep_rows(const sonic_dims& d, int n_valid_frames) {  // modeling_glmasr.py:399-403 (python floor division)
+    int L = n_valid_frames;
+    L = floordiv(L + 2 - 2 - 1, 1) + 1;
+    L = floordiv(L + 2 - 2 - 1, 2) + 1;
+    const int k = floordiv(L - d.merge, d.merge) + 1;
+    const int Ta = d.enc_T / d.merge;
+    return k < 0 ? 0 : (k > Ta ? Ta : k);
+}
+int frames_of(int n_samples) { return n_samples > 0 ? (n_samples + 159) / 160 : 0; }
+
+static long long* kt_slot(sonic_engine* e, int l, int slot) { return (e->kt && l == e->kt_layer) ? e->kt + (long)slot * KT_SLOT_BLOCKS * 8 : nullptr; }
+void skinny(sonic_engine* e, const bf16_t* X, long ldx, const bf16_t* W, float* P, int M, int N, int K, int* ks_out, long long* kt) {
+    SkinnyArgs a{}; a.kt = kt;
+    a.X = X; a.ldx = ldx; a.W = W; a.P = P; a.M = M; a.N = N; a.K = K; a.ksplit = skinny_pick_ksplit(N, K); a.dt = e->dt;
+    if (ks_out) *ks_out = a.ksplit;
+    launch_skinny(a, e->st);
+}
+// int8 decode step: quantised rows Xq [M][K] x fragment-tiled int8 weights -> int32 slabs (dequantised by the consumer)
+// the same projection on UNQUANTISED fp16 rows with their gathered absmax: the kernel quantises its X slice while staging it
+static int skinny_i8_xq(sonic_engine* e, const bf16_t* X16, const float* amax, const int8_t* Wt, float* P, int M, int N, int K) {
+    SkinnyArgs a{};
+    a.X = X16; a.ldx = K; a.W = (const bf16_t*)Wt; a.P = P; a.M = M; a.N = N; a.K = K; a.ksplit = skinny_pick_ksplit_i8(N, K); a.i8 = 1; a.x_amax = amax;
+    launch_skinny(a, e->st);
+    return a.ksplit;
+}
+static int skinny_i8(sonic_engine* e, const int8_t* Xq, const int8_t* Wt, float* P, int M, int N, int K) {
+    SkinnyArgs a{};
+    a.X = (const bf16_t*)Xq; a.ldx = K; a.W = (const bf16_t*)Wt; a.P = P; a.M = M; a.N = N; a.K = K; a.ksplit = skinny_pick_ksplit_i8(N, K); a.i8 = 1;
+    launch_skinny(a, e->st);
+    return a.ksplit;
+}
+
+GreedyArgs greedy_args(sonic_engine* e, int R, bool dump) {
+    const sonic_dims& d = e->d;
+    GreedyArgs g{};
+    g.logits = e->lslab; g.ksplit = skinny_pick_ksplit(d.vocab, d.dec_d); g.mpad = ((R + 15) / 16) * 16; g.V = d.vocab; g.B = R; g.table = e->embed; g.x = e->sx; g.d = d.dec_d;
+    g.out_ids = e->out_ids; g.out_ld = e->out_cap; g.n_new = e->n_new; g.finished = e->finished; g.kv_len = e->kv_len; g.tok_pos = e->tok_pos;
+    g.max_new = e->max_new_d; g.n_active = e->n_active; g.dev_err = e->n_active + 1; g.n_eos = d.n_eos; g.pad_id = d.n_eos > 0 ? d.eos[0] : 0;
+    for (int i = 0; i < d.n_eos; ++i) g.eos[i] = d.eos[i];
+    g.logits_dump = dump ? e->dump : nullptr; g.dump_stride_step = (long)R * d.vocab; g.step_counter = dump ? e->step_ctr : nullptr;
+    g.norm_w = e->dec.empty() ? nullptr : e->dec[0].ln1; g.norm_eps = d.dec_rms_eps; g.y = e->dec.empty() ? nullptr : e->shn;        // the next step's first RMSNorm rides along (d <= 8192)
+    g.force_ids = e->force_d; g.force_ld = e->force_ld;
+    g.dt = e->dt;
+    if (e->i8) g.qo = QuantOut{e->hn_q, d.dec_d, e->sca_hn, e->oc_hn, e->ol_hn, d.dec_d, e->ov_hn};     // layer 0's q/k/v input, quantised
+    return g;
+}
+
+// one decode step for R rows: sx ([R][d]) -> next token (generation/utils.py:2876-2943)
+static void decode_step(sonic_engine* e, int R, bool dump) {
+    if (e->f32) { decode_step_f32(e, R, dump); return; }
+    if (e->i8) { decode_step_i8(e, R, dump); return; }
+    const sonic_dims& d = e->d;
+    const int D = d.dec_d, mpad = ((R + 15) / 16) * 16, dt = e->dt;
+    if (e->opt_decode_gemv && R <= GEMV_MAX_ROWS && d.dec_layers > 0 && e->dec[0].wgu_t8 && gemv_eligible(R, e->qkvN, D, GEMV_SLAB_NORM) && gemv_eligible(R, D, e->QD, GEMV_RESID) &&
+        gemv_eligible(R, 2 * d.dec_ff, D, GEMV_SWIGLU_NORM) && gemv_eligible(R, D, d.dec_ff, GEMV_RESID) && gemv_eligible(R, d.vocab, D, GEMV_SLAB_NORM)) {
+        // 1 - 4 rows, opt-in (gemv.hip): q|k|v (norm inside) -> attention -> o_proj (+ residual) -> gate/up (norm inside, SwiGLU) -> down_proj (+ residual); lm_head (norm inside)
+        e->step_launches_per_layer = 5;
+        auto gv = [&](int mode, const bf16_t* X, long ldx, const bf16_t* W, int N, int K, const float* nw, float* P, bf16_t* resid, bf16_t* act) {
+            GemvArgs g{}; g.X = X; g.ldx = ldx; g.W = W; g.M = R; g.N = N; g.K = K; g.dt = dt; g.norm_w = nw; g.eps = d.dec_rms_eps; g.P = P; g.resid = resid; g.ldr = D; g.act = act;
+            launch_gemv(g, mode, e->st);
+        };
+        for (int l = 0; l < d.dec_layers; ++l) {
+            const DecLayerW& L = e->dec[l];
+            const size_t kvoff = (size_t)l * e->Bm * d.dec_kv_heads * e->max_ctx * d.dec_head_dim;
+            gv(GEMV_SLAB_NORM, e->sx, D, L.wqkv_t, e->qkvN, D, L.ln1, e->slab, nullptr, nullptr);
+            DecodeAttnArgs da{};
+            da.P = e->slab; da.ksplit = 1; da.mpad = mpad; da.cs = e->dec_cs; da.dt = dt;
+            da.Kc = e->Kc + kvoff; da.Vc = e->Vc + kvoff; da.O = e->satt; da.kv_len = e->kv_len; da.Hq = d.dec_heads; da.Hkv = d.dec_kv_heads;
+            da.ctx_max = e->max_ctx; da.scale = 1.0f / sqrtf((float)d.dec_head_dim);
+            launch_decode_attn(da, R, e->st);
+            gv(GEMV_RESID, e->satt, e->QD, L.wo_t, D, e->QD, nullptr, nullptr, e->sx, nullptr);
+            gv(GEMV_SWIGLU_NORM, e->sx, D, L.wgu_t8, 2 * d.dec_ff, D, L.ln2, nullptr, nullptr, e->sact);
+            gv(GEMV_RESID, e->sact, d.dec_ff, L.wdown_t, D, d.dec_ff, nullptr, nullptr, e->sx, nullptr);
+        }
+        gv(GEMV_SLAB_NORM, e->sx, D, e->embed_t, d.vocab, D, e->dec_nw, e->lslab, nullptr, nullptr);
+        GreedyArgs g = greedy_args(e, R, dump);
+        g.ksplit = 1;
+        launch_greedy(g, e->st);
+        return;
+    }
+    int ks;
+    if (D > 8192) launch_rmsnorm(e->sx, e->dec[0].ln1, e->shn, R, D, d.dec_rms_eps, nullptr, e->st, dt);   // else: done by the greedy kernel of the previous step
+    // <= 2 rows (the B = 1 call shape of BASELINE configs 1 and 5; round 6): no standalone add+RMSNorm launch behind down_proj - the next q|k|v projection
+    // (and, behind the last layer, the lm_head) sums the slabs, adds the residual and normalises its rows itself (skinny_xs_kernel<.., PRE>, the same
+    // arithmetic statement by statement: same bits).  Five launches per layer instead of six.  down_proj then writes its slabs to slab2 (the consumer
+    // writes slab while other blocks of it still read) and the residual stream alternates between sx and sx2.
+    const bool fuse_all = !d.dec_layers ? false : (e->dec[0].wgu_t8 && skinny_gu_eligible(R, 2 * d.dec_ff, D) && skinny_o_eligible(R, D, e->QD));
+    const bool pre = fuse_all && !e->opt_no_pre_norm && skinny_pre_eligible(R, e->qkvN, D) && skinny_pre_eligible(R, d.vocab, D) && D % 8 == 0;
+    bf16_t* resid = e->sx;                               // where the residual rows live right now
+    int ks_down = 0;
+    e->step_launches_per_layer = !fuse_all ? 8 : pre ? 5 : ((e->opts.gu64_split_norm > 0 || (e->opts.gu64_split_norm == 0 && e->cap_svc)) && R > 32 && D % 128 == 0 && D <= 2048) ? 7 : 6;
+    auto skinny_pre = [&](const bf16_t* W, float* P, int N, const float* nw, bf16_t* xout, int* ks_out, long long* kt) {
+        SkinnyArgs a{}; a.kt = kt;
+        a.X = resid; a.ldx = D; a.W = W; a.P = P; a.M = R; a.N = N; a.K = D; a.ksplit = skinny_pick_ksplit(N, D); a.dt = dt;
+        a.pre_P = e->slab2; a.pre_ks = ks_down; a.pre_mpad = mpad; a.pre_x = resid; a.pre_xout = xout; a.pre_w = nw; a.pre_eps = d.dec_rms_eps;
+        if (ks_out) *ks_out = a.ksplit;
+        launch_skinny(a, e->st);
+    };
+    for (int l = 0; l < d.dec_layers; ++l) {
+        const DecLayerW& L = e->dec[l];
+        const size_t kvoff = (size_t)l * e->Bm * d.dec_kv_heads * e->max_ctx * d.dec_head_dim;
+        if (pre && l > 0) {
+            bf16_t* other = resid == e->sx ? e->sx2 : e->sx;
+            skinny_pre(L.wqkv_t, e->slab, e->qkvN, L.ln1, other, &ks, kt_slot(e, l, 0));
+            resid = other;
+        } else
+        skinny(e, e->shn, D, L.wqkv_t, e->slab, R, e->qkvN, D, &ks, kt_slot(e, l, 0));
+        DecodeAttnArgs da{}; da.kt = kt_slot(e, l, 1);
+        da.P = e->slab; da.ksplit = ks; da.mpad = mpad; da.cs = e->dec_cs; da.dt = dt;     // RoPE + KV append fused into the attention kernel
+        da.Kc = e->Kc + kvoff; da.Vc = e->Vc + kvoff; da.O = e->satt; da.kv_len = e->kv_len; da.Hq = d.dec_heads; da.Hkv = d.dec_kv_heads;
+        da.ctx_max = e->max_ctx; da.scale = 1.0f / sqrtf((float)d.dec_head_dim);
+        if ((e->opts.decode_prefetch & 3) && R * d.dec_kv_heads <= 128 && L.wo_t) {
+            // experiment: the attention launch covers R x Hkv of the 256 CUs - the others stream the weights of the kernels behind it
+            da.pf_y = (256 - R * d.dec_kv_heads) / R;
+            if (e->opts.decode_prefetch & 1) da.pf[0] = PrefetchRange{L.wo_t, (long)D * e->QD * 2};
+            if ((e->opts.decode_prefetch & 2) && L.wgu_t8) da.pf[1] = PrefetchRange{L.wgu_t8, (long)d.dec_ff * D * 2};       // the first half of gate/up (25 MB)
+        }
+        launch_decode_attn(da, R, e->st);
+        const bool fuse_gu = L.wgu_t8 && skinny_gu_eligible(R, 2 * d.dec_ff, D);
+        const bool fuse_o = fuse_gu && skinny_o_eligible(R, D, e->QD);
+        if (fuse_o) {
+            // o_proj + residual add (+ row sum-of-squares partials) -> gate/up with RMSNorm applied while staging X + SwiGLU:
+            // two kernels instead of o_proj, add+RMSNorm, gate/up, SwiGLU
+            SkinnyArgs oa{}; oa.X = e->satt; oa.ldx = e->QD; oa.W = L.wo_t; oa.M = R; oa.N = D; oa.K = e->QD; oa.ksplit = 1; oa.dt = dt; oa.kt = kt_slot(e, l, 2);
+            launch_skinny_o(oa, resid, D, e->ssq, e->st);
+            SkinnyArgs ga{}; ga.X = resid; ga.ldx = D; ga.W = L.wgu_t8; ga.M = R; ga.N = 2 * d.dec_ff; ga.K = D; ga.ksplit = 1; ga.dt = dt; ga.kt = kt_slot(e, l, 3); ga.err = e->n_active + 1;
+            if ((e->opts.gu64_split_norm > 0 || (e->opts.gu64_split_norm == 0 && e->cap_svc)) && R > 32 && D % 128 == 0 && D <= 2048) {
+                // 33 .. 64 rows: the rows are normalised ONCE by their own small kernel (from the same partials, in the same order: same bits) and
+                // gate/up stages them as they are - 256 blocks each normalising all 64 rows was the longest single piece of the 64-row step
+                launch_rmsnorm_ss(e->sx, e->ssq, L.ln2, e->shn, R, D, d.dec_rms_eps, e->st, dt);
+                ga.X = e->shn; launch_skinny_gu(ga, e->sact, e->st);
+            } else
+            launch_skinny_gu_norm(ga, e->sact, e->ssq, D / 16, L.ln2, d.dec_rms_eps, e->st);
+        } else {
+        skinny(e, e->satt, e->QD, L.wo_t, e->slab, R, D, e->QD, &ks);
+        launch_add_rmsnorm(e->sx, e->slab, ks, mpad, L.ln2, e->shn, R, D, d.dec_rms_eps, e->st, dt);
+        if (fuse_gu) {          // gate/up + SwiGLU in one kernel, no slabs
+            SkinnyArgs ga{}; ga.X = e->shn; ga.ldx = D; ga.W = L.wgu_t8; ga.M = R; ga.N = 2 * d.dec_ff; ga.K = D; ga.ksplit = 1; ga.dt = dt;
+            launch_skinny_gu(ga, e->sact, e->st);
+        } else {
+            skinny(e, e->shn, D, L.wgu_t ? L.wgu_t : L.wgu_t8, e->slab, R, 2 * d.dec_ff, D, &ks);
+            launch_swiglu_slab(e->slab, ks, mpad, 2 * d.dec_ff, e->sact, R, e->st, dt, L.wgu_t ? 0 : 1);
+        }
+        }
+        skinny(e, e->sact, d.dec_ff, L.wdown_t, pre ? e->slab2 : e->slab, R, D, d.dec_ff, &ks, kt_slot(e, l, 4));
+        ks_down = ks;
+        if (pre) continue;                               // the next layer's q|k|v (or the lm_head) consumes the slabs
+        const float* nw = (l + 1 < d.dec_layers) ? e->dec[l + 1].ln1 : e->dec_nw;
+        PrefetchRange pfq{nullptr, 0};
+        if ((e->opts.decode_prefetch & 4) && l + 1 < d.dec_layers && e->dec[l + 1].wqkv_t) pfq = PrefetchRange{e->dec[l + 1].wqkv_t, (long)e->qkvN * D * 2};
+        launch_add_rmsnorm(e->sx, e->slab, ks, mpad, nw, e->shn, R, D, d.dec_rms_eps, e->st, dt, nullptr, nullptr, &pfq, R < 256 ? 256 - R : 0);
+    }
+    if (pre) skinny_pre(e->embed_t, e->lslab, d.vocab, e->dec_nw, nullptr, nullptr, nullptr);   // tied lm_head behind the last layer's slabs (the updated residual is not needed again)
+    else
+    skinny(e, e->shn, D, e->embed_t, e->lslab, R, d.vocab, D, nullptr);   // tied lm_head (modeling_glmasr.py:517)
+    launch_greedy(greedy_args(e, R, dump), e->st);
+}
+
+// int8 mode (asr.py:169-210): every decoder projection is a Linear8bitLt.  In a decode step each row is one reference call, so its
+// outlier "columns" are its own elements >= 6.0.  Producers that own whole rows emit them quantised (greedy / add+RMSNorm / SwiGLU
+// kernels; the attention output by its own one-block-per-row pass), the skinny int8 GEMM streams the fragment-tiled int8 weights
+// (half the bytes of the bf16 step) into exact int32 slabs, and the consumer dequantises them (int8_util.h deq4).
+void decode_step_i8(sonic_engine* e, int R, bool dump) {
+    const sonic_dims& d = e->d;
+    e->step_launches_per_layer = 8;
+    const int D = d.dec_d, FF = d.dec_ff, mpad = ((R + 15) / 16) * 16;
+    const QuantOut q_hn{e->hn_q, D, e->sca_hn, e->oc_hn, e->ol_hn, D, e->ov_hn};
+    const QuantOut q_att{e->att_q, e->QD, e->sca_att, e->oc_att, e->ol_att, e->QD, e->ov_att};
+    const QuantOut q_act{e->act_q, FF, e->sca_act, e->oc_act, e->ol_act, FF, e->ov_act};
+    auto deq = [&](const QuantOut& q, const QW& w, int K, const bf16_t* x16, int N) {
+        DeqInfo dq{}; dq.sca = q.sca; dq.scb = w.scb; dq.cb = w.cb; dq.cbt = w.cbt; dq.cbk = w.cbk; dq.N = N; dq.K = K; dq.x16 = x16; dq.ldx16 = K; dq.oc_cnt = q.oc_cnt; dq.oc_list = q.oc_list; dq.oc_ld = q.oc_ld;
+        dq.row_group = nullptr; dq.group_div = 1; dq.oc_val = q.oc_val; dq.dbg = e->opt_i8_dbg;
+        return dq;
+    };
+    for (int l = 0; l < d.dec_layers; ++l) {
+        const DecLayerW& L = e->dec[l];
+        const size_t kvoff = (size_t)l * e->Bm * d.dec_kv_heads * e->max_ctx * d.dec_head_dim;
+        int ks = skinny_i8(e, e->hn_q, L.qqkv.cbt, e->slab, R, e->qkvN, D);
+        DecodeAttnArgs da{};
+        da.P = e->slab; da.ksplit = ks; da.mpad = mpad; da.cs = e->dec_cs; da.dt = DT_F16; da.dq = deq(q_hn, L.qqkv, D, e->shn, e->qkvN);
+        da.Kc = e->Kc + kvoff; da.Vc = e->Vc + kvoff; da.O = e->satt; da.kv_len = e->kv_len; da.Hq = d.dec_heads; da.Hkv = d.dec_kv_heads;
+        da.ctx_max = e->max_ctx; da.scale = 1.0f / sqrtf((float)d.dec_head_dim);
+        // o_proj's input rows are spread over the attention blocks of 4 kv heads: they gather the row absmax (atomicMax), o_proj quantises on the
+        // fly and its consumer lists the outliers itself - no one-block-per-row quantisation launch in between (option i8_no_xq: the round-2 form)
+        const bool xq = !e->opt_i8_no_xq && d.dec_kv_heads <= 4 && !e->opts.decode_attn_v1;   // the partials are [64][4]: one per kv-head block
+        if (xq) { da.amax_out = e->amax_att; da.big_out = e->big_att; }
+        launch_decode_attn(da, R, e->st);
+        DeqInfo dq;
+        if (xq) {
+            ks = skinny_i8_xq(e, e->satt, e->amax_att, L.qo.cbt, e->slab, R, D, e->QD);
+            dq = deq(q_att, L.qo, e->QD, e->satt, D); dq.sca = e->amax_att; dq.scan = 1; dq.scan_cnt = e->big_att;
+        } else {
+            launch_quant_rows(e->satt, e->QD, R, e->QD, q_att, e->st);
+            ks = skinny_i8(e, e->att_q, L.qo.cbt, e->slab, R, D, e->QD);
+            dq = deq(q_att, L.qo, e->QD, e->satt, D);
+        }
+        launch_add_rmsnorm(e->sx, e->slab, ks, mpad, L.ln2, e->shn, R, D, d.dec_rms_eps, e->st, DT_F16, &dq, &q_hn);
+        ks = skinny_i8(e, e->hn_q, L.qgu.cbt, e->slab, R, 2 * FF, D);
+        launch_swiglu_quant(e->slab, ks, mpad, FF, e->sact, R, deq(q_hn, L.qgu, D, e->shn, 2 * FF), q_act, e->st);
+        ks = skinny_i8(e, e->act_q, L.qdown.cbt, e->slab, R, D, FF);
+        dq = deq(q_act, L.qdown, FF, e->sact, D);
+        const float* nw = (l + 1 < d.dec_layers) ? e->dec[l + 1].ln1 : e->dec_nw;
+        launch_add_rmsnorm(e->sx, e->slab, ks, mpad, nw, e->shn, R, D, d.dec_rms_eps, e->st, DT_F16, &dq, &q_hn);
+    }
+    skinny(e, e->shn, D, e->embed_t, e->lslab, R, d.vocab, D, nullptr);   // lm_head is not swapped (asr.py:177): fp16 skinny GEMM
+    launch_greedy(greedy_args(e, R, dump), e->st);
+}
+
+static int plan_requests(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off,
+                         const int32_t* max_new, HostPlan& hp) {
+    const sonic_dims& d = e->d;
+    const int W = e->W;
+    if (R < 1 || R > e->Bm) return fail(e, SONIC_ERR_INVALID, "request count %d out of range 1..%d", R, e->Bm);
+    if (!req_win && R != W) return fail(e, SONIC_ERR_INVALID, "R (%d) must equal staged windows (%d) when req_win is NULL", R, W);
+    if (req_win && (req_win[0] != 0 || req_win[R] != W)) return fail(e, SONIC_ERR_INVALID, "req_win must cover exactly the staged windows");
+    hp.q_off.resize(R); hp.q_len.resize(R); hp.last_row.resize(R); hp.max_new.resize(R);
+    for (int r = 0; r < R; ++r) {
+        const int w0 = req_win ? req_win[r] : r, w1 = req_win ? req_win[r + 1] : r + 1;
+        if (w1 <= w0) return fail(e, SONIC_ERR_INVALID, "request %d has no audio window", r);
+        std::vector<int> rows;  // audio rows of this request in order
+        for (int w = w0; w < w1; ++w) {
+            const int k = keep_rows(d, frames_of(e->n_samples_h[w]));
+            for (int j = 0; j < k; ++j) rows.push_back(w * e->Ta + j);
+        }
+        const int64_t p0 = prompt_off[r], p1 = prompt_off[r + 1];
+        const int P = (int)(p1 - p0);
+        if (P < 1) return fail(e, SONIC_ERR_INVALID, "request %d has an empty prompt", r);
+        if (max_new[r] < 1) return fail(e, SONIC_ERR_INVALID, "max_new_tokens must be >= 1");
+        if (P + max_new[r] > e->max_ctx) return fail(e, SONIC_ERR_INVALID, "prompt (%d) + max_new_tokens (%d) exceeds max_ctx (%d)", P, max_new[r], e->max_ctx);
+        if (max_new[r] > e->out_cap) return fail(e, SONIC_ERR_INVALID, "max_new_tokens too large");
+        size_t used = 0; int n_ph = 0;
+        for (int i = 0; i < P; ++i) n_ph += (prompt_ids[p0 + i] == d.audio_token_id);
+        if ((size_t)n_ph != rows.size())
+            return fail(e, SONIC_ERR_MISMATCH, "Audio features and audio tokens do not match, tokens: %d, features: %zu", n_ph, rows.size());
+        hp.q_off[r] = hp.n_tok; hp.q_len[r] = P;
+        for (int i = 0; i < P; ++i) {
+            const int id = prompt_ids[p0 + i];
+            if (id == d.audio_token_id) hp.src.push_back(-(1 + rows[used++]));
+            else {
+                if (id < 0 || id >= d.vocab) return fail(e, SONIC_ERR_INVALID, "token id %d out of vocabulary", id);
+                hp.src.push_back(id);
+            }
+            hp.tok_seq.push_back(r); hp.tok_pos.push_back(i);
+        }
+        hp.n_tok += P;
+        hp.last_row[r] = hp.n_tok - 1;
+        hp.max_new[r] = max_new[r];
+        if (P > hp.max_p) hp.max_p = P;
+        if (max_new[r] > hp.max_steps) hp.max_steps = max_new[r];
+    }
+    if (hp.n_tok > e->tok_cap) return fail(e, SONIC_ERR_INVALID, "too many prompt tokens");
+    return SONIC_OK;
+}
+
+static int run_prefill(sonic_engine* e, int R, const HostPlan& hp) {
+    const sonic_dims& d = e->d;
+    const int D = d.dec_d, M = hp.n_tok, dt = e->dt;
+    const QGroup grp{e->tok_seq, 1, R};        // one reference call = the prompt rows of one request
+    // The plan goes through pinned memory, so the copies are truly asynchronous and nothing here waits for the encoder that is still running
+    // on this stream (a pageable source forced a stream synchronise between encoder and prefill: a host-dependent bubble in every batch).
+    // plan_h = the staging buffer run_to_first_token picked for this run (free: the run that used it last has had its copies waited for).
+    {
+        int* h = e->plan_h; size_t o = 0;
+        auto put = [&](int* dst, const int* srcv, size_t n) -> hipError_t {
+            if (o + n > e->plan_cap) return hipErrorInvalidValue;
+            memcpy(h + o, srcv, n * 4);
+            hipError_t r = hipMemcpyAsync(dst, h + o, n * 4, hipMemcpyHostToDevice, e->st);
+            o += n; return r;
+        };
+        HIPC(e, put(e->src, hp.src.data(), (size_t)M)); HIPC(e, put(e->tok_seq, hp.tok_seq.data(), (size_t)M)); HIPC(e, put(e->tok_pos_pf, hp.tok_pos.data(), (size_t)M));
+        HIPC(e, put(e->q_off, hp.q_off.data(), (size_t)R)); HIPC(e, put(e->q_len, hp.q_len.data(), (size_t)R)); HIPC(e, put(e->kv_len, hp.q_len.data(), (size_t)R));
+        HIPC(e, put(e->last_row, hp.last_row.data(), (size_t)R)); HIPC(e, put(e->max_new_d, hp.max_new.data(), (size_t)R));
+        HIPC(e, put(e->n_active, &R, 1));
+        HIPC(e, hipEventRecord(e->plan_ev[e->plan_idx], e->st));       // every copy out of this buffer (win_req included) is older than this event
+        e->plan_busy[e->plan_idx] = true;
+    }
+    launch_fill_i32(e->n_new, 0, 64, e->st);
+    if (e->amax_att) { launch_fill_i32((int*)e->amax_att, 0, 64 * 4, e->st); launch_fill_i32((int*)e->amax_act, 0, 64 * 4, e->st); launch_fill_i32(e->big_att, 0, 64 * 4, e->st); }   // (partials nobody writes stay 0)
+    launch_fill_i32(e->finished, 0, 64, e->st);
+    launch_fill_i32(e->step_ctr, 0, 64, e->st);
+    launch_assemble_embeds(e->src, e->embed, e->pe, e->dx, M, D, e->st);
+    e->last_ntok = M;
+    if (e->taps_on) {
+        if (!e->taps) HIPC(e, hipMalloc((void**)&e->taps, (size_t)(d.dec_layers + 1) * e->tok_cap * D * sizeof(bf16_t)));
+        HIPC(e, hipMemcpyAsync(e->taps, e->dx, (size_t)M * D * 2, hipMemcpyDeviceToDevice, e->st));
+    }
+    for (int l = 0; l < d.dec_layers; ++l) {
+        const DecLayerW& L = e->dec[l];
+        const size_t kvoff = (size_t)l * e->Bm * d.dec_kv_heads * e->max_ctx * d.dec_head_dim;
+        // 16-bit modes: the prefill GEMMs read the decode step's fragment-tiled weights (GemmArgs.w_tiled) - one copy of every decoder projection
+        // since round 5 (the row-major ones are freed at load unless SONIC_KEEP_ROWMAJOR=1; option prefill_rowmajor then selects them for the A/B)
+        auto lin = [&](int epi, const bf16_t* X, long ldx, const bf16_t* w16, const bf16_t* wt, int gu8, const QW& q, bf16_t* C, long ldc, int N, int K,
+                       const bf16_t* Rr, long ldr, bool pq) {
+            if (!e->i8 && wt && (!w16 || !e->opt_prefill_rowmajor)) gemm(e, epi, X, ldx, wt, nullptr, C, ldc, M, N, K, Rr, ldr, 1, gu8);
+            else qlinear(e, epi, X, ldx, w16, q, nullptr, C, ldc, M, N, K, Rr, ldr, grp, nullptr, 0, 0, pq);
+        };
+        const bool pq1 = rmsnorm_q(e, e->dx, L.ln1, e->dhn, M, D, d.dec_rms_eps, grp);
+        lin(EPI_BIAS, e->dhn, D, L.wqkv, L.wqkv_t, 0, L.qqkv, e->dqkv, e->qkvN, e->qkvN, D, nullptr, 0, pq1);
+        RopeAppendArgs ra{}; ra.dt = dt;
+        ra.qkv = e->dqkv; ra.ld = e->qkvN; ra.q_out = e->dq; ra.Kc = e->Kc + kvoff; ra.Vc = e->Vc + kvoff; ra.Vt = e->Vts; ra.vt_ld = e->max_ctx;
+        ra.tok_seq = e->tok_seq; ra.tok_pos = e->tok_pos_pf; ra.cs = e->dec_cs; ra.Hq = d.dec_heads; ra.Hkv = d.dec_kv_heads; ra.ctx_max = e->max_ctx; ra.n_tok = M;
+        if (!e->opt_no_rope_tiles) { ra.q_off = e->q_off; ra.q_len = e->q_len; ra.n_seq = R; ra.max_p = hp.max_p; }       // tiles of 16 positions per sequence (round 5)
+        launch_rope_append(ra, false, e->st);
+        FlashArgs f{}; f.dt = dt;
+        f.Q = e->dq; f.q_ld = e->QD; f.K = e->Kc + kvoff; f.k_ld = d.dec_head_dim; f.Vt = e->Vts; f.vt_ld = e->max_ctx; f.O = e->datt; f.o_ld = e->QD;
+        f.k_seq_stride = (long)d.dec_kv_heads * e->max_ctx * d.dec_head_dim; f.k_head_stride = (long)e->max_ctx * d.dec_head_dim;
+        f.vt_seq_stride = (long)d.dec_kv_heads * d.dec_head_dim * e->max_ctx; f.vt_head_stride = (long)d.dec_head_dim * e->max_ctx;
+        f.q_off = e->q_off; f.q_len = e->q_len; f.kv_len = e->q_len; f.Hq = d.dec_heads; f.Hkv = d.dec_kv_heads;
+        f.scale = 1.0f / sqrtf((float)d.dec_head_dim);
+        launch_flash(f, 128, true, R, hp.max_p, e->st);
+        lin(EPI_BIAS_RESID, e->datt, e->QD, L.wo, L.wo_t, 0, L.qo, e->dx, D, D, e->QD, e->dx, D, false);
+        const bool pq2 = rmsnorm_q(e, e->dx, L.ln2, e->dhn, M, D, d.dec_rms_eps, grp);
+        lin(EPI_SWIGLU, e->dhn, D, L.wgu, L.wgu_t8 ? L.wgu_t8 : L.wgu_t, L.wgu_t8 ? 1 : 0, L.qgu, e->dact, d.dec_ff, 2 * d.dec_ff, D, nullptr, 0, pq2);
+        lin(EPI_BIAS_RESID, e->dact, d.dec_ff, L.wdown, L.wdown_t, 0, L.qdown, e->dx, D, D, d.dec_ff, e->dx, D, false);
+        if (e->taps_on) HIPC(e, hipMemcpyAsync(e->taps + (size_t)(l + 1) * e->tok_cap * D, e->dx, (size_t)M * D * 2, hipMemcpyDeviceToDevice, e->st));
+    }
+    // logits only for the last prompt position of each request (logits_to_keep=1, generation/utils.py:2612-2616)
+    launch_rmsnorm(e->dx, e->dec_nw, e->shn, R, D, d.dec_rms_eps, e->last_row, e->st, dt);
+    skinny(e, e->shn, D, e->embed_t, e->lslab, R, d.vocab, D, nullptr);
+    return SONIC_OK;
+}
+
+// log-mel -> encoder -> projector -> prefill -> first greedy token (generation/utils.py:2612-2616, 2876-2943 for the first step)
+int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off,
+                       const int32_t* max_new, bool want_logits) {
+    const sonic_dims& d = e->d;
+    if (!e->finalized) return fail(e, SONIC_ERR_INVALID, "weights not finalized");
+    if (e->W < 1) return fail(e, SONIC_ERR_INVALID, "no PCM staged");
+    if (e->svc_on) return fail(e, SONIC_ERR_INVALID, "this handle is decoding continuously (sonic_service_begin): prefill on another slot and splice the rows in");
+    if (e->wait_pending) {                                  // rows of the previous batch were spliced into another handle: its copy kernels read this
+        HIPC(e, hipStreamWaitEvent(e->st, e->wait_ev, 0));  // engine's KV cache and row state, which this run is about to overwrite
+        e->wait_pending = false;
+    }
+    HostPlan hp;
+    TRY(plan_requests(e, req_win, R, prompt_ids, prompt_off, max_new, hp));
+    {   // staging buffer of this run: the one used two runs ago; its copies are almost always long done (a blocking wait otherwise)
+        const int i = e->plan_idx ^ 1;
+        if (e->plan_busy[i]) { HIPC(e, hipEventSynchronize(e->plan_ev[i])); e->plan_busy[i] = false; }
+        e->plan_idx = i; e->plan_h = e->plan_buf[i];
+    }
+    if (e->force_d && (e->force_R != R || e->force_ld < hp.max_steps))
+        return fail(e, SONIC_ERR_INVALID, "forced ids are [%d][%d] but the run has %d requests / %d steps", e->force_R, e->force_ld, R, hp.max_steps);
+    e->R = R; e->max_steps = hp.max_steps; e->last_qlen = hp.q_len; e->last_maxnew = hp.max_new;
+    if (want_logits) {
+        const size_t need_n = (size_t)hp.max_steps * R * d.vocab;
+        if (need_n > e->dump_cap) {
+            if (e->dump) (void)hipFree(e->dump);
+            e->dump = nullptr; e->dump_cap = 0;
+            HIPC(e, hipMalloc((void**)&e->dump, need_n * 4));
+            e->dump_cap = need_n;
+        }
+        e->dump_steps = hp.max_steps;
+    } else e->dump_steps = 0;
+    e->run_logits = want_logits;
+
+    if (e->f32) {
+        (void)hipEventRecord(e->ev[0], e->st);
+        TRY(run_mel(e, e->W, true));
+        (void)hipEventRecord(e->ev[1], e->st);
+        TRY(f32_run_encoder(e, e->W, nullptr, nullptr));
+        (void)hipEventRecord(e->ev[2], e->st);
+        TRY(f32_run_prefill(e, R, hp));
+        launch_greedy(f32_greedy_args(e, R, want_logits), e->st);
+        (void)hipEventRecord(e->ev[3], e->st);
+        e->steps_run = 0; e->greedy_calls = 1;
+        return SONIC_OK;
+    }
+    (void)hipEventRecord(e->ev[0], e->st);
+    TRY(run_mel(e, e->W, false));
+    (void)hipEventRecord(e->ev[1], e->st);
+    {   // window -> request map (int8 mode: outlier columns are found per request)
+        std::vector<int> wr(64, 0);
+        for (int r = 0; r < R; ++r) {
+            const int w0 = req_win ? req_win[r] : r, w1 = req_win ? req_win[r + 1] : r + 1;
+            for (int w = w0; w < w1 && w < 64; ++w) wr[w] = r;
+        }
+        if (e->i8) {                                           // (pinned: the last 64 words of plan_h, beyond what run_prefill uses)
+            int* h = e->plan_h + e->plan_cap - 64;
+            memcpy(h, wr.data(), 64 * 4);
+            HIPC(e, hipMemcpyAsync(e->win_req, h, 64 * 4, hipMemcpyHostToDevice, e->st));
+        }
+    }
+    TRY(run_encoder(e, e->W, nullptr, nullptr, R));
+    (void)hipEventRecord(e->ev[2], e->st);
+    TRY(run_prefill(e, R, hp));
+    launch_greedy(greedy_args(e, R, want_logits), e->st);
+    (void)hipEventRecord(e->ev[3], e->st);
+    e->steps_run = 0;
+    e->greedy_calls = 1;
+    return SONIC_OK;
+}
+
+// A captured chunk of the greedy loop: `n` token steps for `R` rows as ONE hipGraph (kv_len / tok_pos / the token ids live on the device, so
+// the steps of a chunk need nothing from the host).
+// svc: the chunk belongs to a continuous decode loop (sonic_service_*), i.e. it runs beside a prefill slot and other loops by design - decode_step then
+// picks the forms that cost the fewest CU-microseconds rather than the shortest chain (gu64_split_norm).  Same bits either way; cached separately.
+int chunk_graph(sonic_engine* e, int R, int n, hipGraphExec_t* out, bool svc) {
+    const std::pair<int, int> key{R + (svc ? 4096 : 0), n};
+    auto it = e->graphs.find(key);
+    if (it != e->graphs.end()) { *out = it->second; return SONIC_OK; }
+    hipGraph_t g = nullptr; hipGraphExec_t gx = nullptr;
+    HIPC(e, hipStreamBeginCapture(e->st, hipStreamCaptureModeThreadLocal));
+    e->cap_svc = svc;
+    for (int i = 0; i < n; ++i) decode_step(e, R, false);
+    e->cap_svc = false;
+    HIPC(e, hipStreamEndCapture(e->st, &g));
+    hipError_t r = hipGraphInstantiate(&gx, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g);
+    HIPC(e, r);
+    e->graphs[key] = gx;
+    *out = gx;
+    return SONIC_OK;
+}
+
+// up to n_steps further token steps of the staged batch (HF:generation/utils.py:2876-2943), in chunks of `decode_chunk` steps: one hipGraph
+// launch per chunk (eager under teacher forcing / when the step logits are wanted; a launch costs the host ~4 us, tools/host_cost.py).
+// Ragged termination without a host round trip on the critical path: behind every chunk the device's count of running rows is copied to
+// pinned memory and an event is recorded; the host reads check k only when chunk k + lookahead is already queued, so the stream never runs
+// dry while the host looks, and the loop stops `lookahead` chunks after every row hit EOS / its budget (finished rows are frozen: the
+// queued steps rewrite their own cache slot and emit nothing).  lookahead ADAPTS: it is 1 on a host that keeps up (waste at a stop: one
+// chunk) and doubles whenever the host, about to launch the next chunk, finds the one it queued last already complete - the stream is empty,
+// the device idle: a host that is descheduled for tens of milliseconds at a time (CPU quota shared with other work) or simply behind (a busy
+// interpreter) - up to CHK_MAX_AHEAD chunks; a batch without such an observation takes one chunk off again.
+int run_decode_steps(sonic_engine* e, int n_steps, int* done_out) {
+    const int R = e->R, left = e->max_steps - 1 - e->steps_run;
+    if (n_steps > left) n_steps = left;
+    const bool want_logits = e->run_logits;
+    const bool use_graph = !want_logits && !e->opt_no_graph && !e->force_d && !e->f32;
+    const int C = e->opt_decode_chunk > 0 ? e->opt_decode_chunk : 1;
+    int done = 0;
+    int launched = 0, checked = 0, last_grow = 0;   // chunks queued with a check behind them / checks the host has read
+    bool all_stopped = false, starved = false, dev_err = false;
+    typedef std::chrono::steady_clock clk;
+    auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
+    auto read_check = [&](bool block) -> int {  // 1: read (all_stopped updated), 0: not complete yet, < 0: error
+        const int i = checked % CHK_RING;
+        if (!block) { const hipError_t q = hipEventQuery(e->chk_ev[i]); if (q == hipErrorNotReady) { (void)hipGetLastError(); return 0; } if (q != hipSuccess) return -1; }
+        else { const auto t_w = clk::now(); if (hipEventSynchronize(e->chk_ev[i]) != hipSuccess) return -1; e->host_wait_ms += ms_since(t_w); }
+        if (e->n_active_h[i] <= 0) all_stopped = true;
+        if (e->n_active_h[i] < DEV_ERR_ACTIVE) dev_err = true;
+        ++checked;
+        return 1;
+    };
+    while (done < n_steps && !all_stopped) {
+        const int n = n_steps - done < C ? n_steps - done : C;
+        // The chunk queued last is already complete as the next one is about to go out: the stream is empty, the device has been idle since -
+        // this thread is late by more than a chunk (descheduled, or behind other host work).  Keep more chunks queued.
+        if (launched > 0 && hipEventQuery(e->chk_ev[(launched - 1) % CHK_RING]) == hipSuccess) {
+            if (launched - last_grow > e->lookahead && e->lookahead < CHK_MAX_AHEAD) {      // (the deeper queue gets `lookahead` launches to show before it grows again)
+                e->lookahead = e->lookahead * 2 < CHK_MAX_AHEAD ? e->lookahead * 2 : CHK_MAX_AHEAD;
+                last_grow = launched;
+            }
+            starved = true;
+        }
+        (void)hipGetLastError();
+        const auto t_l = clk::now();
+        if (use_graph) {
+            hipGraphExec_t gx = nullptr;
+            TRY(chunk_graph(e, R, n, &gx));
+            HIPC(e, hipGraphLaunch(gx, e->st));
+        } else {
+            for (int i = 0; i < n; ++i) decode_step(e, R, want_logits);
+        }
+        e->host_launch_ms += ms_since(t_l); e->host_launches += 1;
+        done += n; e->steps_run += n; e->greedy_calls += n;
+        if (e->steps_run + 1 >= e->max_steps) break;           // the budget is exhausted: nothing left to stop early
+        const int slot = launched % CHK_RING;
+        HIPC(e, hipMemcpyAsync(e->n_active_h + slot, e->n_active, 4, hipMemcpyDeviceToHost, e->st));
+        HIPC(e, hipEventRecord(e->chk_ev[slot], e->st));
+        ++launched;
+        (void)hipGetLastError();
+        while (!all_stopped && checked < launched) {           // read what is there; block only for checks older than the lookahead
+            const int r = read_check(launched - checked > e->lookahead);
+            if (r < 0) return fail(e, SONIC_ERR_HIP, "decode loop: check event failed: %s", hipGetErrorString(hipGetLastError()));
+            if (r == 0) break;
+        }
+    }
+    e->run_starved = e->run_starved || starved;
+    if (dev_err) return fail(e, SONIC_ERR_HIP, "a decode kernel gave up on an in-kernel wait: the batch's tokens are invalid");
+    if (!all_stopped && done >= n_steps && e->steps_run + 1 < e->max_steps) {
+        // the caller asked for fewer steps than the budget (sonic_decode_step) and synchronises next: read the outstanding checks now
+        while (!all_stopped && checked < launched) if (read_check(true) < 0) return fail(e, SONIC_ERR_HIP, "decode loop: check event failed");
+    }
+    if (all_stopped) e->steps_run = e->max_steps - 1;
+    if (done_out) *done_out = done;
+    return SONIC_OK;
+}
+
+int run_all(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off,
+            const int32_t* max_new, bool want_logits) {
+    const sonic_dims& d = e->d;
+    const auto t_host0 = std::chrono::steady_clock::now();
+    TRY(run_to_first_token(e, req_win, R, prompt_ids, prompt_off, max_new, want_logits));
+    const double host_enqueue_first = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
+    e->host_launch_ms = e->host_wait_ms = 0; e->host_launches = 0; e->run_starved = false;
+    int steps_done = 0;
+    TRY(run_decode_steps(e, e->max_steps - 1, &steps_done));
+    (void)hipEventRecord(e->ev[4], e->st);
+    HIPC(e, stream_sync(e));
+    HIPC(e, hipGetLastError());
+    sonic_timings& t = e->tim;
+    memset(&t, 0, sizeof t);
+    (void)hipEventElapsedTime(&t.mel_ms, e->ev[0], e->ev[1]);
+    (void)hipEventElapsedTime(&t.encoder_ms, e->ev[1], e->ev[2]);
+    (void)hipEventElapsedTime(&t.prefill_ms, e->ev[2], e->ev[3]);
+    (void)hipEventElapsedTime(&t.decode_ms, e->ev[3], e->ev[4]);
+    (void)hipEventElapsedTime(&t.total_ms, e->ev[0], e->ev[4]);
+    for (int l = 0; l < e->gemm_ev_used; ++l) {
+        float ms = 0; (void)hipEventElapsedTime(&ms, e->gemm_ev[8 * l + 4], e->gemm_ev[8 * l + 5]);
+        t.gemm_ms += ms; t.gemm_launches += 1;
+        const double MT = (double)e->W * e->T, C = d.enc_d, F = d.enc_ff;
+        t.gemm_flops += 2.0 * MT * F * C;
+        for (int g = 0; g < 4; ++g) { float m2 = 0; (void)hipEventElapsedTime(&m2, e->gemm_ev[8 * l + 2 * g], e->gemm_ev[8 * l + 2 * g + 1]); t.enc_gemm_ms += m2; }
+        t.enc_gemm_flops += 2.0 * MT * C * (3 * C) + 2.0 * MT * C * C + 4.0 * MT * F * C;      // QKV, o, fc1, fc2
+    }
+    t.decode_steps = steps_done;
+    t.host_prefill_enqueue_ms = (float)host_enqueue_first; t.host_decode_launch_ms = (float)e->host_launch_ms; t.host_decode_wait_ms = (float)e->host_wait_ms;
+    t.host_decode_launches = e->host_launches; t.decode_lookahead = e->lookahead; t.decode_launches_per_layer = e->step_launches_per_layer;
+    if (!e->run_starved && e->lookahead > 1) e->lookahead -= 1;       // a batch whose queue never ran dry: one chunk less ahead next time
+    return SONIC_OK;
+}

@@ -1,4 +1,4 @@
-// Attempt to isolate the corruption that made engine.cpp park uncached (hipDeviceMallocUncached) blocks in a process-lifetime pool
+// Attempt to isolate the corruption that made the engine (csrc/engine.cpp, the history note above dalloc in csrc/engine_internal.h) park uncached (hipDeviceMallocUncached) blocks in a process-lifetime pool
 // instead of hipFree-ing them: test buffers that reused formerly-uncached pages read back wrong cache lines (round 2).
 // Hypothesis: an XCD's L2 keeps lines of a physical page from an earlier ORDINARY tenant; the page is then mapped uncached and written
 // (stores bypass L2, the old lines stay); freed; mapped ordinary again and filled by a host->device copy; a kernel then reads the stale
