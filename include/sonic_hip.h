@@ -44,7 +44,7 @@ extern "C" {
 /* The library is built with -fvisibility=hidden: these declarations are its whole dynamic symbol table (tests/test_host_logic.py checks
  * `nm -D` against this header).  SONIC_ABI_VERSION moves whenever a signature or a struct layout below changes. */
 #define SONIC_API __attribute__((visibility("default")))
-#define SONIC_ABI_VERSION 8
+#define SONIC_ABI_VERSION 9
 SONIC_API int sonic_abi_version(void);
 
 typedef struct sonic_engine sonic_engine;
@@ -301,6 +301,19 @@ SONIC_API int sonic_test_attention(sonic_engine* e, const float* q, const float*
                          int B, int Tq, int Tk, int Hq, int Hkv, int hd, int causal);
 SONIC_API int sonic_test_decode_attention(sonic_engine* e, const float* q, const float* k, const float* v, float* out,
                                 int B, int Tk, int Hq, int Hkv);
+/* the decode attention as the decode step launches it, over caller-filled caches [B][Hkv][ctx_max][128] (the caller decides what lies behind kv_len) and
+ * per-row kv_len[B] in 1..ctx_max (new token included).  Fused mode (slabs != NULL, q == NULL): q|k|v partial slabs [ksplit][mpad][(Hq + 2 Hkv) * 128] fp32
+ * (ksplit 1..8, mpad >= B) and the RoPE table rope_cs [ctx_max][128] fp32 (cos | sin); the kernel sums the slabs, applies RoPE at kv_len - 1 and appends the
+ * K / V row.  Given-q mode (q != NULL, slabs == NULL): q [B][Hq * 128], nothing appended.  out [B][Hq * 128]; kcache_out / vcache_out (optional) receive the
+ * caches as the launch left them.  Hq / Hkv <= 4.  The int8 dequantising prologue is not reachable from here. */
+SONIC_API int sonic_test_decode_attention_cache(sonic_engine* e, const float* q, const float* slabs, int ksplit, int mpad, const float* rope_cs,
+                                      const float* kcache, const float* vcache, const int32_t* kv_len, float* out, float* kcache_out, float* vcache_out,
+                                      int B, int Hq, int Hkv, int ctx_max);
+/* the prefill's causal attention (head dim 128) with its own strides: packed q [n_tok][Hq * 128] with q_off / q_len / kv_len [B] (1 <= q_len <= kv_len <=
+ * ctx_max: query t of a sequence sits at position kv_len - q_len + t), K [B][Hkv][ctx_max][128], V^T [B][Hkv][128][ctx_max], ctx_max a multiple of 64.
+ * out [n_tok][Hq * 128] is read first: rows outside every [q_off, q_off + q_len) come back as they went in. */
+SONIC_API int sonic_test_prefill_attention(sonic_engine* e, const float* q, const float* kcache, const float* vt, const int32_t* q_off, const int32_t* q_len,
+                                 const int32_t* kv_len, float* out, int n_tok, int B, int Hq, int Hkv, int ctx_max);
 SONIC_API int sonic_test_layernorm(sonic_engine* e, const float* x, const float* w, const float* b, float* y, int rows, int d, float eps, int rms);
 /* times `iters` launches of the encoder's dominant GEMM shape on the engine stream with HIP events */
 SONIC_API int sonic_bench_gemm(sonic_engine* e, int M, int N, int K, int epi, int iters, float* ms_per_launch);

@@ -214,6 +214,69 @@ extern "C" int sonic_test_decode_attention(sonic_engine* e, const float* q, cons
     return down_bf16(e, tb, dO, out, (size_t)B * Hq * hd);
 }
 
+// The decode attention as decode_step() launches it - fused mode (slabs != null: slab sum, RoPE at kv_len - 1, K/V append, kv_len - 1 cached keys + the new one
+// from LDS) - or with a given q (slabs == null), over caller-filled caches and per-row kv_len.  The caches are read back after the launch.
+extern "C" int sonic_test_decode_attention_cache(sonic_engine* e, const float* q, const float* slabs, int ksplit, int mpad, const float* rope_cs,
+                                                 const float* kcache, const float* vcache, const int32_t* kv_len, float* out, float* kcache_out, float* vcache_out,
+                                                 int B, int Hq, int Hkv, int ctx_max) {
+    if (!e || !kcache || !vcache || !kv_len || !out || (q == nullptr) == (slabs == nullptr)) return SONIC_ERR_INVALID;
+    ENTER(e);
+    const int hd = 128;
+    if (e->f32) return fail(e, SONIC_ERR_INVALID, "decode attention hook needs a 16-bit engine");
+    if (B < 1 || B > 4096 || Hkv < 1 || Hq < Hkv || Hq % Hkv || Hq / Hkv > 4 || ctx_max < 1) return fail(e, SONIC_ERR_INVALID, "bad decode attention test shape");
+    if (slabs && (!rope_cs || ksplit < 1 || ksplit > 8 || mpad < B)) return fail(e, SONIC_ERR_INVALID, "fused decode attention: rope table, 1 <= ksplit <= 8, mpad >= B");
+    for (int b = 0; b < B; ++b)
+        if (kv_len[b] < 1 || kv_len[b] > ctx_max) return fail(e, SONIC_ERR_INVALID, "kv_len[%d] = %d outside 1..%d", b, kv_len[b], ctx_max);
+    TmpBuf tb(e->st);
+    const size_t nc = (size_t)B * Hkv * ctx_max * hd, no = (size_t)B * Hq * hd, N = (size_t)(Hq + 2 * Hkv) * hd;
+    bf16_t* dk = up_bf16(e, tb, kcache, nc); bf16_t* dv = up_bf16(e, tb, vcache, nc);
+    bf16_t* dq = q ? up_bf16(e, tb, q, no) : nullptr;
+    float* dP = slabs ? up_f32(e, tb, slabs, (size_t)ksplit * mpad * N) : nullptr;
+    float* dcs = slabs ? up_f32(e, tb, rope_cs, (size_t)ctx_max * hd) : nullptr;
+    bf16_t* dO = tb.get<bf16_t>(no); int* kl = tb.get<int>(B);
+    if (!dk || !dv || !dO || !kl || (q && !dq) || (slabs && (!dP || !dcs))) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    HIPC(e, h2d(e, kl, kv_len, (size_t)B * 4));
+    DecodeAttnArgs a{};
+    a.Q = dq; a.P = dP; a.ksplit = ksplit; a.mpad = mpad; a.cs = dcs; a.Kc = dk; a.Vc = dv; a.O = dO; a.kv_len = kl; a.Hq = Hq; a.Hkv = Hkv; a.ctx_max = ctx_max;
+    a.scale = 1.0f / sqrtf((float)hd); a.dt = e->dt;
+    launch_decode_attn(a, B, e->st);
+    TRY(down_bf16(e, tb, dO, out, no));
+    if (kcache_out) TRY(down_bf16(e, tb, dk, kcache_out, nc));
+    if (vcache_out) TRY(down_bf16(e, tb, dv, vcache_out, nc));
+    return SONIC_OK;
+}
+
+// The causal attention of the prefill as run_prefill() launches it: packed ragged queries (q_off / q_len / kv_len), K in cache layout, V^T with the
+// context as its leading dimension, head dim 128.  `out` [n_tok][Hq * 128] is uploaded first, so rows the kernel leaves alone keep the caller's values.
+extern "C" int sonic_test_prefill_attention(sonic_engine* e, const float* q, const float* kcache, const float* vt, const int32_t* q_off, const int32_t* q_len,
+                                            const int32_t* kv_len, float* out, int n_tok, int B, int Hq, int Hkv, int ctx_max) {
+    if (!e || !q || !kcache || !vt || !q_off || !q_len || !kv_len || !out) return SONIC_ERR_INVALID;
+    ENTER(e);
+    const int hd = 128;
+    if (e->f32) return fail(e, SONIC_ERR_INVALID, "prefill attention hook needs a 16-bit engine");
+    if (B < 1 || B > 4096 || n_tok < 1 || Hkv < 1 || Hq < Hkv || Hq % Hkv || ctx_max < 64 || ctx_max % 64) return fail(e, SONIC_ERR_INVALID, "bad prefill attention test shape");
+    int max_p = 0;
+    for (int b = 0; b < B; ++b) {
+        if (q_len[b] < 1 || kv_len[b] < q_len[b] || kv_len[b] > ctx_max || q_off[b] < 0 || (long)q_off[b] + q_len[b] > n_tok)
+            return fail(e, SONIC_ERR_INVALID, "sequence %d: q_off %d, q_len %d, kv_len %d do not fit %d tokens / a context of %d", b, q_off[b], q_len[b], kv_len[b], n_tok, ctx_max);
+        max_p = q_len[b] > max_p ? q_len[b] : max_p;
+    }
+    TmpBuf tb(e->st);
+    const size_t nq = (size_t)n_tok * Hq * hd, nc = (size_t)B * Hkv * ctx_max * hd;
+    bf16_t* dq = up_bf16(e, tb, q, nq); bf16_t* dk = up_bf16(e, tb, kcache, nc); bf16_t* dvt = up_bf16(e, tb, vt, nc); bf16_t* dO = up_bf16(e, tb, out, nq);
+    int* di = tb.get<int>((size_t)3 * B);
+    if (!dq || !dk || !dvt || !dO || !di) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    HIPC(e, h2d(e, di, q_off, (size_t)B * 4)); HIPC(e, h2d(e, di + B, q_len, (size_t)B * 4)); HIPC(e, h2d(e, di + 2 * B, kv_len, (size_t)B * 4));
+    FlashArgs f{}; f.dt = e->dt;
+    f.Q = dq; f.q_ld = (long)Hq * hd; f.K = dk; f.k_ld = hd; f.Vt = dvt; f.vt_ld = ctx_max; f.O = dO; f.o_ld = (long)Hq * hd;
+    f.k_seq_stride = (long)Hkv * ctx_max * hd; f.k_head_stride = (long)ctx_max * hd;
+    f.vt_seq_stride = (long)Hkv * hd * ctx_max; f.vt_head_stride = (long)hd * ctx_max;
+    f.q_off = di; f.q_len = di + B; f.kv_len = di + 2 * B; f.Hq = Hq; f.Hkv = Hkv;
+    f.scale = 1.0f / sqrtf((float)hd);
+    launch_flash(f, hd, true, B, max_p, e->st);
+    return down_bf16(e, tb, dO, out, nq);
+}
+
 extern "C" int sonic_test_layernorm(sonic_engine* e, const float* x, const float* w, const float* b, float* y, int rows, int d, float eps, int rms) {
     if (!e) return SONIC_ERR_INVALID;
     ENTER(e);

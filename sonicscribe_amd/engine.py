@@ -26,7 +26,7 @@ EXPORTS = [
     "sonic_finalize_weights", "sonic_weight_bytes", "sonic_logmel", "sonic_encode", "sonic_transcribe_batch", "sonic_stage_pcm",
     "sonic_run_staged", "sonic_fetch_tokens", "sonic_get_timings", "sonic_synchronize", "sonic_test_gemm", "sonic_test_skinny",
     "sonic_test_attention", "sonic_test_decode_attention", "sonic_test_layernorm", "sonic_bench_gemm", "sonic_bench_skinny", "sonic_set_option", "sonic_debug_read", "sonic_debug_ktrace", "sonic_test_skinny_gu",
-    "sonic_set_forced_ids", "sonic_test_greedy", "sonic_test_linear_int8",
+    "sonic_set_forced_ids", "sonic_test_greedy", "sonic_test_linear_int8", "sonic_test_decode_attention_cache", "sonic_test_prefill_attention",
     "sonic_ring_create", "sonic_ring_destroy", "sonic_ring_append", "sonic_ring_head", "sonic_transcribe_mixed", "sonic_stage_mixed",
     "sonic_prefill", "sonic_decode_step", "sonic_device_info", "sonic_memory_info",
     "sonic_abi_version", "sonic_slot_create", "sonic_slot_count", "sonic_run_staged_async", "sonic_wait",
@@ -36,7 +36,7 @@ EXPORTS = [
     "sonic_pipeline_create", "sonic_pipeline_submit", "sonic_pipeline_wait", "sonic_pipeline_stats", "sonic_pipeline_last_error", "sonic_pipeline_destroy",
     "sonic_vad_create", "sonic_vad_destroy", "sonic_vad_last_error", "sonic_vad_load_tensor", "sonic_vad_probs",
 ]
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 class SonicDims(C.Structure):
@@ -121,6 +121,8 @@ def load_library():
     lib.sonic_test_skinny.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int]
     lib.sonic_test_attention.argtypes = [vp, vp, vp, vp, vp] + [C.c_int] * 7
     lib.sonic_test_decode_attention.argtypes = [vp, vp, vp, vp, vp] + [C.c_int] * 4
+    lib.sonic_test_decode_attention_cache.argtypes = [vp, vp, vp, C.c_int, C.c_int] + [vp] * 7 + [C.c_int] * 4
+    lib.sonic_test_prefill_attention.argtypes = [vp] * 8 + [C.c_int] * 5
     lib.sonic_test_layernorm.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_float, C.c_int]
     lib.sonic_bench_gemm.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
     lib.sonic_bench_skinny.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]
@@ -648,6 +650,48 @@ def _test_linear_int8(self, X, W, bias=None, resid=None, group_rows=None, epi=EP
     return out
 
 
+def _test_decode_attention_cache(self, kcache, vcache, kv_len, Hq: int, q=None, slabs=None, rope_cs=None, want_caches: bool = True):
+    """The decode attention as decode_step launches it.  kcache / vcache [B][Hkv][ctx_max][128] (whole, the caller fills what lies behind kv_len),
+    kv_len [B] (new token included).  Either q [B][Hq][128] (nothing appended) or slabs [ksplit][mpad][(Hq + 2 Hkv) * 128] with rope_cs [ctx_max][128]
+    (fused slab sum + RoPE + append).  Returns (out [B][Hq][128], kcache after, vcache after); the caches are None unless want_caches."""
+    kc = np.ascontiguousarray(kcache, np.float32); vc = np.ascontiguousarray(vcache, np.float32)
+    B, Hkv, ctx, hd = kc.shape
+    assert hd == 128 and vc.shape == kc.shape and (q is None) != (slabs is None)
+    kl = np.ascontiguousarray(kv_len, np.int32)
+    assert kl.shape == (B,)
+    ks = mpad = 0
+    if q is not None:
+        q = np.ascontiguousarray(q, np.float32)
+        assert q.shape == (B, Hq, 128)
+    else:
+        slabs = np.ascontiguousarray(slabs, np.float32); rope_cs = np.ascontiguousarray(rope_cs, np.float32)
+        ks, mpad = slabs.shape[:2]
+        assert slabs.shape == (ks, mpad, (Hq + 2 * Hkv) * 128) and rope_cs.shape == (ctx, 128)
+    out = np.empty((B, Hq, 128), np.float32)
+    ko = np.empty_like(kc) if want_caches else None
+    vo = np.empty_like(vc) if want_caches else None
+    self._check(self.lib.sonic_test_decode_attention_cache(self.h, _p(q), _p(slabs), ks, mpad, _p(rope_cs), _p(kc), _p(vc), _p(kl), _p(out), _p(ko), _p(vo),
+                                                           B, Hq, Hkv, ctx))
+    return out, ko, vo
+
+
+def _test_prefill_attention(self, q, kcache, vt, q_off, q_len, kv_len, out_init=None):
+    """The prefill's causal attention with run_prefill's strides.  q [n_tok][Hq][128] packed, kcache [B][Hkv][ctx_max][128], vt [B][Hkv][128][ctx_max],
+    q_off / q_len / kv_len [B].  out_init [n_tok][Hq][128] is what the output buffer holds before the launch (default zeros).  -> [n_tok][Hq][128]"""
+    q = np.ascontiguousarray(q, np.float32); kc = np.ascontiguousarray(kcache, np.float32); vt = np.ascontiguousarray(vt, np.float32)
+    n_tok, Hq, hd = q.shape
+    B, Hkv, ctx, _ = kc.shape
+    assert hd == 128 and kc.shape[3] == 128 and vt.shape == (B, Hkv, 128, ctx)
+    qo, ql, kl = (np.ascontiguousarray(x, np.int32) for x in (q_off, q_len, kv_len))
+    assert qo.shape == ql.shape == kl.shape == (B,)
+    out = np.zeros_like(q) if out_init is None else np.array(out_init, np.float32, order="C")
+    assert out.shape == q.shape
+    self._check(self.lib.sonic_test_prefill_attention(self.h, _p(q), _p(kc), _p(vt), _p(qo), _p(ql), _p(kl), _p(out), n_tok, B, Hq, Hkv, ctx))
+    return out
+
+
+Engine.test_decode_attention_cache = _test_decode_attention_cache
+Engine.test_prefill_attention = _test_prefill_attention
 Engine.test_linear_int8 = _test_linear_int8
 Engine.set_forced_ids = _set_forced_ids
 Engine.test_greedy = _test_greedy
