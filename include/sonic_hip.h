@@ -33,6 +33,9 @@
  *                              (models_manager.vad_model_init             models_manager.py:34-49)
  *   sonic_vad_probs            the model(chunk, 16000) loop inside get_speech_timestamps as called from
  *                              VADProcessor.detect_voice_activity / is_voice_active   backend/vad.py:41-126
+ *   sonic_vad_probs_rings      the same loop over audio that already lies in device rings: the whole-file VAD call of
+ *                              /transcribe/file (backend/main.py:308-314, the file tensor uploaded for it) and the per-tick
+ *                              window of vad_processor_manager.py:95-104 (int16 / 32768 of the accumulated chunks)
  */
 #ifndef SONIC_HIP_H
 #define SONIC_HIP_H
@@ -44,7 +47,7 @@ extern "C" {
 /* The library is built with -fvisibility=hidden: these declarations are its whole dynamic symbol table (tests/test_host_logic.py checks
  * `nm -D` against this header).  SONIC_ABI_VERSION moves whenever a signature or a struct layout below changes. */
 #define SONIC_API __attribute__((visibility("default")))
-#define SONIC_ABI_VERSION 9
+#define SONIC_ABI_VERSION 10
 SONIC_API int sonic_abi_version(void);
 
 typedef struct sonic_engine sonic_engine;
@@ -266,6 +269,14 @@ SONIC_API void sonic_ring_destroy(sonic_ring* r);
  * copied to a pinned mirror and their H2D copy is queued; decodes that name them order behind it */
 SONIC_API int sonic_ring_append(sonic_ring* r, const int16_t* pcm, int64_t n, int64_t* first_index);
 SONIC_API int64_t sonic_ring_head(sonic_ring* r);     /* samples appended so far */
+/* sonic_pipeline_submit with the windows of sonic_stage_mixed: window w is a range of ring rings[w] (raw wire PCM, a1 + a2 on the device,
+ * peak over the windows of its request) or, where rings[w] is NULL, host PCM as in sonic_pipeline_submit.  The ring arrays are copied; the
+ * ranges are checked, and the rings locked, when a prefill thread stages the batch (a range that has left its ring by then fails the batch
+ * with sonic_stage_mixed's message).  File mode submits its segments this way on a bulk model (backend/main.py:429-445). */
+SONIC_API int sonic_pipeline_submit_mixed(sonic_pipeline* p, const int16_t* host_pcm, const int64_t* host_off, sonic_ring* const* rings,
+                                          const int64_t* ring_start, const int32_t* ring_n, int W, const int32_t* req_win, int R,
+                                          const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new,
+                                          int32_t* out_ids, int out_ld, int32_t* out_len, int64_t* ticket_out);
 /* sonic_transcribe_batch with every window either host samples (rings == NULL or rings[w] == NULL: int16 PCM already peak-normalised,
  * host_off[W+1]; ring windows have empty host ranges) or samples [ring_start[w], ring_start[w] + ring_n[w]) of rings[w], which must
  * still be inside the ring's last `capacity` samples.  The windows of one request (req_win) share one peak.  Without req_win R == W. */
@@ -353,6 +364,19 @@ SONIC_API void sonic_vad_destroy(sonic_vad* v);
 SONIC_API const char* sonic_vad_last_error(sonic_vad* v);
 SONIC_API int sonic_vad_load_tensor(sonic_vad* v, const char* name, const float* data, const int64_t* shape, int ndim);
 SONIC_API int sonic_vad_probs(sonic_vad* v, const int16_t* pcm_i16, const float* pcm_f32, const int64_t* off, int B, float* probs);
+/* sonic_vad_probs over audio that is already resident in device rings (sonic_ring_*), read in place: replaces the upload of the whole
+ * file tensor for backend/main.py:308-314 (vad_processor.detect_voice_activity(full_audio_tensor)) and the second upload of every tick's
+ * window bytes (vad_processor_manager.py:95-104).  Sequence b is the concatenation of pieces seq_piece[b] .. seq_piece[b+1]-1 (seq_piece[0]
+ * = 0), piece p the samples [piece_start[p], piece_start[p] + piece_n[p]) (absolute indices, as sonic_ring_append returns them) of ring
+ * piece_ring[p]; a file is one piece, a gate window whose chunk ids skip is several.  A sequence is windowed exactly as a host sequence
+ * of sonic_vad_probs (int16 form: x / 32768): ceil(n / 512) windows, the last zero-padded, state and context reset per sequence - the
+ * first window has no context whatever precedes it in the ring - and gives the same bits.  Windows may straddle the ring's wrap and
+ * piece boundaries.  The rules of sonic_stage_mixed hold: rings are looked up in the registry of e's weight owner (a destroyed ring or one
+ * of another engine is refused, never dereferenced), a ring on another device than v is refused, a piece outside [head - capacity, head)
+ * is refused, ring locks are taken in one global order and held until the kernel that reads the rings has completed, and the VAD's
+ * stream orders behind each ring's last append.  Does not take e's lock: it never queues behind a decoding batch. */
+SONIC_API int sonic_vad_probs_rings(sonic_vad* v, sonic_engine* e, sonic_ring* const* piece_ring, const int64_t* piece_start,
+                                    const int32_t* piece_n, const int64_t* seq_piece, int B, float* probs);
 
 #ifdef __cplusplus
 }

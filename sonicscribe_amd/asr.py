@@ -151,6 +151,11 @@ class AudioStream:
                 raise ValueError("chunk range is not contiguous in the buffer")
         return self._chunks[ids[0]][0], sum(self._chunks[c][1] for c in ids)
 
+    def chunk_samples(self, chunk_id: int):
+        """(first sample index, sample count) of a chunk still in the buffer, else None"""
+        c = self._chunks.get(int(chunk_id))
+        return None if c is None else (c[0], c[1])
+
     def submit_samples(self, first: int, n: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None) -> "Future[str]":
         """Transcribe ring samples [first, first + n) (the >30 s split of connection_manager.py:206-214 cuts at byte offsets, not chunks)."""
         m = self.model
@@ -331,6 +336,22 @@ class ASRModel:
             futs = [self._dispatcher.submit(segs[req_win[i]:req_win[i + 1]], prompts[i], mn[i]) for i in range(len(audios))]
             ids = [f.result() for f in futs]
         return [self.prompt.decode(i).strip() for i in ids]
+
+    def transcribe_file(self, audio, vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
+                        max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filename: str = ""):
+        """The body of the reference's /transcribe/file endpoint (main.py:193-649) as a generator of its records (dicts with the
+        reference's keys: initialization, segments_summary, segment_result / segment_error in segment order, final_summary).  `audio`:
+        16 kHz mono int16 PCM, or the reference's float tensor [1, N] of int16 / 32768 values; `vad`: a vad.VADProcessor.  The file is
+        appended once to a device ring, VAD-scored there, and every segment is queued at once as a range of that ring on this model's
+        scheduler; the ring is destroyed when the generator is exhausted or closed (filemode.py)."""
+        from . import filemode
+        return filemode.transcribe_file(self, audio, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filename)
+
+    def transcribe_files(self, audios: Sequence[Any], vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
+                         max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filenames: Optional[Sequence[str]] = None):
+        """transcribe_file for several files: all VAD passes in one device call, one record iterator per file (filemode.transcribe_files)."""
+        from . import filemode
+        return filemode.transcribe_files(self, audios, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filenames)
 
     def get_model_info(self) -> Dict[str, Any]:
         """asr.py:490-513: the reference's keys for a GPU device (`cuda_version` carries the HIP runtime version: torch.version.cuda is

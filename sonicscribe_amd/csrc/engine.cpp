@@ -500,7 +500,8 @@ extern "C" int sonic_device_info(int device_id, char* name, int name_cap, int64_
 extern "C" int sonic_memory_info(sonic_engine* e, int64_t* allocated_bytes, int64_t* reserved_bytes) {
     if (!e) return SONIC_ERR_INVALID;
     std::lock_guard<std::mutex> lk(e->mu);
-    if (allocated_bytes) *allocated_bytes = e->alloc_bytes;
-    if (reserved_bytes) *reserved_bytes = e->alloc_bytes;
+    const int64_t live = e->alloc_bytes + (e->owner ? 0 : e->ring_bytes.load());      // rings are charged to the weight owner that registers them
+    if (allocated_bytes) *allocated_bytes = live;
+    if (reserved_bytes) *reserved_bytes = live;
     return SONIC_OK;
 }

@@ -1,5 +1,6 @@
 // sonic_hip engine: PCM staging from the host, device-resident rings, mixed staging, and the batch entry points that start from staged PCM.
 #include "engine_internal.h"
+#include "ring_access.h"
 
 // ------------------------------------------------------------------------------------------ C ABI: hot path
 int stage_pcm_locked(sonic_engine* e, const int16_t* pcm, const int64_t* offsets, int W) {
@@ -55,6 +56,7 @@ extern "C" int sonic_ring_create(sonic_engine* e, int64_t capacity_samples, soni
     sonic_engine* root = e->owner ? e->owner : e;
     r->e = root;
     { std::lock_guard<std::mutex> rl(root->rings_mu); root->rings.push_back(r); }
+    root->ring_bytes += capacity_samples * 2;
     *out = r;
     return SONIC_OK;
 }
@@ -64,6 +66,7 @@ void ring_free(sonic_ring* r) {
         (void)hipSetDevice(r->e->device);
         (void)hipStreamSynchronize(r->st);
         (void)hipFree(r->buf); (void)hipHostFree(r->host); (void)hipStreamDestroy(r->st); (void)hipEventDestroy(r->read_ev); (void)hipEventDestroy(r->app_ev);
+        r->e->ring_bytes -= r->cap * 2;
     }
     delete r;
 }
@@ -188,6 +191,49 @@ static int stage_mixed_locked(sonic_engine* e, int W, const int16_t* host_pcm, c
     e->W = W;
     return SONIC_OK;
 }
+// sample ranges of rings for a reader outside the engine (sonic_vad_probs_rings): the registry, lock and range rules of stage_mixed_locked
+int ring_ranges_acquire(sonic_engine* e, sonic_ring* const* ring, const int64_t* start, const int32_t* n, int64_t P, int device, hipStream_t st,
+                        RingView* view, std::vector<std::unique_lock<std::mutex>>& held, std::string& err) {
+    char msg[256];
+    sonic_engine* root = e->owner ? e->owner : e;
+    if (root->device != device) {
+        snprintf(msg, sizeof msg, "the engine's rings are on device %d, the VAD handle on device %d", root->device, device);
+        err = msg; return SONIC_ERR_INVALID;
+    }
+    std::vector<sonic_ring*> used;
+    {
+        std::lock_guard<std::mutex> rl(root->rings_mu);        // registry lookup + ring locks as one step against sonic_ring_destroy
+        for (int64_t p = 0; p < P; ++p)
+            if (std::find(used.begin(), used.end(), ring[p]) == used.end()) {
+                if (!ring[p] || std::find(root->rings.begin(), root->rings.end(), ring[p]) == root->rings.end()) {
+                    snprintf(msg, sizeof msg, "piece %lld: ring belongs to another engine (or was destroyed)", (long long)p);
+                    err = msg; return SONIC_ERR_INVALID;
+                }
+                used.push_back(ring[p]);
+            }
+        std::sort(used.begin(), used.end());                   // the lock order of every batch and every VAD call
+        held.reserve(used.size());
+        for (sonic_ring* rg : used) held.emplace_back(rg->mu);
+    }
+    for (int64_t p = 0; p < P; ++p) {
+        sonic_ring* rg = ring[p];
+        const int64_t len = n[p], s0 = start[p];
+        if (len < 0 || s0 < 0 || s0 + len > rg->head || s0 < rg->head - rg->cap) {
+            snprintf(msg, sizeof msg, "piece %lld: samples [%lld, %lld) are not in the ring (holds [%lld, %lld))", (long long)p, (long long)s0,
+                     (long long)(s0 + len), (long long)(rg->head > rg->cap ? rg->head - rg->cap : 0), (long long)rg->head);
+            err = msg; held.clear(); return SONIC_ERR_INVALID;
+        }
+        view[p].buf = rg->buf; view[p].cap = rg->cap;
+    }
+    for (sonic_ring* rg : used)                                 // the appended samples are (or will be) in HBM first
+        if (rg->app_pending && hipStreamWaitEvent(st, rg->app_ev, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            const hipError_t er = hipEventSynchronize(rg->app_ev);
+            if (er != hipSuccess) { err = std::string("hipEventSynchronize(app_ev) failed: ") + hipGetErrorString(er); held.clear(); return SONIC_ERR_HIP; }
+        }
+    return SONIC_OK;
+}
+
 extern "C" int sonic_stage_mixed(sonic_engine* e, const int16_t* host_pcm, const int64_t* host_off, sonic_ring* const* rings, const int64_t* ring_start,
                                  const int32_t* ring_n, int W, const int32_t* req_win, int R) {
     if (!e) return SONIC_ERR_INVALID;

@@ -33,6 +33,7 @@ namespace {
 struct Batch {
     int64_t ticket = 0;
     const int16_t* pcm = nullptr; std::vector<int64_t> offsets; int W = 0;      // pcm == nullptr: what the prefill handle has staged
+    std::vector<sonic_ring*> rings; std::vector<int64_t> ring_start; std::vector<int32_t> ring_n;   // non-empty: windows staged by sonic_stage_mixed
     std::vector<int32_t> req_win; bool has_req_win = false;
     int R = 0;
     std::vector<int32_t> prompt_ids; std::vector<int64_t> prompt_off; std::vector<int32_t> max_new;
@@ -89,7 +90,10 @@ void prefill_thread(sonic_pipeline* p, sonic_engine* h) {
             b = p->queue.front(); p->queue.pop_front();
         }
         int rc = SONIC_OK;
-        if (b->pcm) rc = sonic_stage_pcm(h, b->pcm, b->offsets.data(), b->W);
+        if (!b->rings.empty())
+            rc = sonic_stage_mixed(h, b->pcm, b->offsets.empty() ? nullptr : b->offsets.data(), b->rings.data(), b->ring_start.data(), b->ring_n.data(), b->W,
+                                   b->has_req_win ? b->req_win.data() : nullptr, b->R);
+        else if (b->pcm) rc = sonic_stage_pcm(h, b->pcm, b->offsets.data(), b->W);
         if (rc == SONIC_OK)
             rc = sonic_prefill_enqueue(h, b->has_req_win ? b->req_win.data() : nullptr, b->R, b->prompt_ids.data(), b->prompt_off.data(), b->max_new.data());
         std::unique_lock<std::mutex> lk(p->mu);
@@ -240,14 +244,16 @@ SONIC_API int sonic_pipeline_create(sonic_engine* const* decoders, int n_dec, so
     return SONIC_OK;
 }
 
-SONIC_API int sonic_pipeline_submit(sonic_pipeline* p, const int16_t* pcm, const int64_t* offsets, int W, const int32_t* req_win, int R,
-                                    const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new,
-                                    int32_t* out_ids, int out_ld, int32_t* out_len, int64_t* ticket_out) {
+static int submit_batch(sonic_pipeline* p, const int16_t* pcm, const int64_t* offsets, sonic_ring* const* rings, const int64_t* ring_start,
+                        const int32_t* ring_n, int W, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new,
+                        int32_t* out_ids, int out_ld, int32_t* out_len, int64_t* ticket_out) {
     if (!p || !prompt_ids || !prompt_off || !max_new || !out_ids || !out_len || R < 1 || R > p->block || out_ld < 1) return SONIC_ERR_INVALID;
     if (pcm && (!offsets || W < 1)) return SONIC_ERR_INVALID;
+    if (rings && (!ring_start || !ring_n || W < 1)) return SONIC_ERR_INVALID;
     auto b = std::make_shared<Batch>();
     b->pcm = pcm; b->W = W;
     if (pcm) b->offsets.assign(offsets, offsets + W + 1);
+    if (rings) { b->rings.assign(rings, rings + W); b->ring_start.assign(ring_start, ring_start + W); b->ring_n.assign(ring_n, ring_n + W); }
     if (req_win) { b->req_win.assign(req_win, req_win + R + 1); b->has_req_win = true; }
     b->R = R;
     b->prompt_off.assign(prompt_off, prompt_off + R + 1);
@@ -262,6 +268,19 @@ SONIC_API int sonic_pipeline_submit(sonic_pipeline* p, const int16_t* pcm, const
     if (ticket_out) *ticket_out = b->ticket;
     p->cv.notify_all();
     return SONIC_OK;
+}
+
+SONIC_API int sonic_pipeline_submit(sonic_pipeline* p, const int16_t* pcm, const int64_t* offsets, int W, const int32_t* req_win, int R,
+                                    const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new,
+                                    int32_t* out_ids, int out_ld, int32_t* out_len, int64_t* ticket_out) {
+    return submit_batch(p, pcm, offsets, nullptr, nullptr, nullptr, W, req_win, R, prompt_ids, prompt_off, max_new, out_ids, out_ld, out_len, ticket_out);
+}
+SONIC_API int sonic_pipeline_submit_mixed(sonic_pipeline* p, const int16_t* host_pcm, const int64_t* host_off, sonic_ring* const* rings,
+                                          const int64_t* ring_start, const int32_t* ring_n, int W, const int32_t* req_win, int R,
+                                          const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new,
+                                          int32_t* out_ids, int out_ld, int32_t* out_len, int64_t* ticket_out) {
+    if (!rings) return SONIC_ERR_INVALID;
+    return submit_batch(p, host_pcm, host_off, rings, ring_start, ring_n, W, req_win, R, prompt_ids, prompt_off, max_new, out_ids, out_ld, out_len, ticket_out);
 }
 
 // ticket > 0: blocks until that batch is complete and returns ITS status (then forgets it); ticket 0: until every batch submitted so far is

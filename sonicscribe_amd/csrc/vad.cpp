@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 #include "vad_dev.h"
+#include "ring_access.h"
 #include "../../include/sonic_hip.h"
 
 namespace {
@@ -57,6 +58,7 @@ struct sonic_vad {
     size_t up_cap = 0;
     float *d_gin = nullptr, *d_probs = nullptr, *h_probs = nullptr;
     int64_t win_cap = 0;
+    hipEvent_t front_ev = nullptr;      // behind the front kernel of a ring call: the ring locks go back when it has completed
 };
 
 static int fail(sonic_vad* v, int code, const std::string& msg) {
@@ -95,6 +97,14 @@ static hipError_t grow_upload(sonic_vad* v, size_t bytes) {
     return hipSuccess;
 }
 
+static VadWeights device_weights(const sonic_vad* v) {
+    VadWeights wt;
+    const float** p[] = {&wt.basisT, &wt.w0T, &wt.b0, &wt.w1T, &wt.b1, &wt.w2T, &wt.b2, &wt.w3T, &wt.b3,
+                               &wt.wihT, &wt.bih, &wt.bhh, &wt.whh, &wt.hw, &wt.hb};
+    for (int i = 0; i < kNT; ++i) *p[i] = v->d_w + v->off[i];
+    return wt;
+}
+
 extern "C" {
 
 SONIC_API int sonic_vad_create(int device_id, int max_windows, sonic_vad** out) {
@@ -110,6 +120,7 @@ SONIC_API int sonic_vad_create(int device_id, int max_windows, sonic_vad** out) 
     v->dev = device_id;
     hipError_t e = hipSetDevice(device_id);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&v->st, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&v->front_ev, hipEventDisableTiming);
     int64_t total = 0;
     for (int i = 0; i < kNT; ++i) { v->off[i] = total; total += (numel(kTensors[i]) + 3) / 4 * 4; }   // 16-byte aligned tensors
     if (e == hipSuccess) e = hipMalloc(&v->d_w, total * sizeof(float));
@@ -131,6 +142,7 @@ SONIC_API void sonic_vad_destroy(sonic_vad* v) {
     if (v->st) (void)hipStreamSynchronize(v->st);
     (void)hipFree(v->d_w); (void)hipFree(v->d_gin); (void)hipFree(v->d_probs); (void)hipFree(v->d_up);
     (void)hipHostFree(v->h_probs); (void)hipHostFree(v->h_up);
+    if (v->front_ev) (void)hipEventDestroy(v->front_ev);
     if (v->st) (void)hipStreamDestroy(v->st);
     delete v;
 }
@@ -216,16 +228,84 @@ SONIC_API int sonic_vad_probs(sonic_vad* v, const int16_t* pcm_i16, const float*
     }
     memcpy(v->h_up + pcm_bytes + win_bytes, seq.data(), seq_bytes);
     e = hipMemcpyAsync(v->d_up, v->h_up, pcm_bytes + win_bytes + seq_bytes, hipMemcpyHostToDevice, v->st);
-    VadWeights wt;
-    const float** p[] = {&wt.basisT, &wt.w0T, &wt.b0, &wt.w1T, &wt.b1, &wt.w2T, &wt.b2, &wt.w3T, &wt.b3,
-                               &wt.wihT, &wt.bih, &wt.bhh, &wt.whh, &wt.hw, &wt.hb};
-    for (int i = 0; i < kNT; ++i) *p[i] = v->d_w + v->off[i];
+    const VadWeights wt = device_weights(v);
     if (e == hipSuccess)
         e = vad_launch(v->d_up, pcm_f32 != nullptr, reinterpret_cast<const VadWindow*>(v->d_up + pcm_bytes), (int)W,
                        reinterpret_cast<const int64_t*>(v->d_up + pcm_bytes + win_bytes), B, wt, v->d_gin, v->d_probs, v->st);
     if (e == hipSuccess) e = hipMemcpyAsync(v->h_probs, v->d_probs, W * sizeof(float), hipMemcpyDeviceToHost, v->st);
     if (e == hipSuccess) e = hipStreamSynchronize(v->st);
     if (e != hipSuccess) return hip_fail(v, e, "sonic_vad_probs");
+    memcpy(probs, v->h_probs, W * sizeof(float));
+    return SONIC_OK;
+}
+
+SONIC_API int sonic_vad_probs_rings(sonic_vad* v, sonic_engine* eng, sonic_ring* const* piece_ring, const int64_t* piece_start, const int32_t* piece_n,
+                                    const int64_t* seq_piece, int B, float* probs) {
+    if (!v) return SONIC_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(v->mu);
+    for (int i = 0; i < kNT; ++i)
+        if (!v->loaded[i]) return fail(v, SONIC_ERR_INVALID, std::string("sonic_vad_probs_rings: weight tensor ") + kTensors[i].name + " not loaded");
+    if (!eng || B < 0 || (B > 0 && (!seq_piece || !probs)))
+        return fail(v, SONIC_ERR_INVALID, "sonic_vad_probs_rings: needs an engine, seq_piece[B + 1] and probs");
+    if (B == 0) return SONIC_OK;
+    if (seq_piece[0] != 0) return fail(v, SONIC_ERR_INVALID, "sonic_vad_probs_rings: seq_piece[0] must be 0");
+    for (int b = 0; b < B; ++b)
+        if (seq_piece[b + 1] < seq_piece[b]) return fail(v, SONIC_ERR_INVALID, "sonic_vad_probs_rings: seq_piece must not decrease");
+    const int64_t P = seq_piece[B];
+    if (P > INT32_MAX) return fail(v, SONIC_ERR_INVALID, "sonic_vad_probs_rings: too many pieces");
+    if (P > 0 && (!piece_ring || !piece_start || !piece_n)) return fail(v, SONIC_ERR_INVALID, "sonic_vad_probs_rings: NULL piece arrays");
+    (void)hipSetDevice(v->dev);
+    (void)hipGetLastError();
+    std::vector<RingView> view(P);
+    std::vector<std::unique_lock<std::mutex>> held;            // ring locks: from the range check until the front kernel has completed
+    std::string why;
+    const int rc = ring_ranges_acquire(eng, piece_ring, piece_start, piece_n, P, v->dev, v->st, view.data(), held, why);
+    if (rc != SONIC_OK) return fail(v, rc, "sonic_vad_probs_rings: " + why);
+    std::vector<int64_t> seq(B + 1, 0), len(B, 0);
+    for (int b = 0; b < B; ++b) {
+        for (int64_t p = seq_piece[b]; p < seq_piece[b + 1]; ++p) len[b] += piece_n[p];
+        seq[b + 1] = seq[b] + (len[b] + VAD_NEW - 1) / VAD_NEW;
+    }
+    const int64_t W = seq[B];
+    if (W > INT32_MAX / VAD_G) return fail(v, SONIC_ERR_INVALID, "sonic_vad_probs_rings: too many windows");
+    if (W == 0) return SONIC_OK;
+    const size_t piece_bytes = (P * sizeof(VadPiece) + 15) / 16 * 16, win_bytes = W * sizeof(VadRingWindow), seq_bytes = (B + 1) * sizeof(int64_t);
+    hipError_t e = grow_windows(v, W);
+    if (e == hipSuccess) e = grow_upload(v, piece_bytes + win_bytes + seq_bytes);
+    if (e != hipSuccess) return hip_fail(v, e, "sonic_vad_probs_rings: buffers");
+    VadPiece* pc = reinterpret_cast<VadPiece*>(v->h_up);
+    VadRingWindow* win = reinterpret_cast<VadRingWindow*>(v->h_up + piece_bytes);
+    for (int b = 0; b < B; ++b) {
+        int64_t at = 0;
+        for (int64_t p = seq_piece[b]; p < seq_piece[b + 1]; ++p) {
+            pc[p].ring = view[p].buf; pc[p].cap = view[p].cap; pc[p].start = piece_start[p] % view[p].cap;
+            pc[p].seq_off = at; pc[p].n = piece_n[p]; pc[p].pad_ = 0;
+            at += piece_n[p];
+        }
+        int64_t p = seq_piece[b];                               // piece of the first sample each window reads; only moves forward
+        for (int64_t w = 0; w < seq[b + 1] - seq[b]; ++w) {
+            VadRingWindow& wd = win[seq[b] + w];
+            wd.pos = w * VAD_NEW;
+            wd.n_valid = (int32_t)std::min<int64_t>(VAD_NEW, len[b] - w * VAD_NEW);
+            wd.has_ctx = w > 0;                                 // a sequence's first window has no context, whatever precedes it in the ring
+            const int64_t first = wd.pos - (w > 0 ? VAD_CTX : 0);
+            while (p + 1 < seq_piece[b + 1] && first >= pc[p].seq_off + pc[p].n) ++p;
+            wd.piece = (int32_t)p; wd.piece_end = (int32_t)seq_piece[b + 1];
+        }
+    }
+    memcpy(v->h_up + piece_bytes + win_bytes, seq.data(), seq_bytes);
+    e = hipMemcpyAsync(v->d_up, v->h_up, piece_bytes + win_bytes + seq_bytes, hipMemcpyHostToDevice, v->st);
+    if (e == hipSuccess)
+        e = vad_launch_rings(reinterpret_cast<const VadPiece*>(v->d_up), reinterpret_cast<const VadRingWindow*>(v->d_up + piece_bytes), (int)W,
+                             reinterpret_cast<const int64_t*>(v->d_up + piece_bytes + win_bytes), B, device_weights(v), v->d_gin, v->d_probs,
+                             v->st, v->front_ev);
+    if (e == hipSuccess) e = hipMemcpyAsync(v->h_probs, v->d_probs, W * sizeof(float), hipMemcpyDeviceToHost, v->st);
+    // the rings stay locked until their last reader, the front kernel, is through (on any failure: until the stream is empty)
+    if (e == hipSuccess) e = hipEventSynchronize(v->front_ev);
+    if (e != hipSuccess) (void)hipStreamSynchronize(v->st);
+    held.clear();
+    if (e == hipSuccess) e = hipStreamSynchronize(v->st);
+    if (e != hipSuccess) return hip_fail(v, e, "sonic_vad_probs_rings");
     memcpy(probs, v->h_probs, W * sizeof(float));
     return SONIC_OK;
 }

@@ -53,27 +53,8 @@ __device__ __forceinline__ void conv_k3(const float* __restrict__ wT, const floa
     }
 }
 
-__global__ void __launch_bounds__(NT) vad_front_kernel(const void* __restrict__ pcm, int is_f32, const VadWindow* __restrict__ win, int W,
-                                                      VadWeights wt, float* __restrict__ gin) {
-    __shared__ FrontSmem sm;
-    const int w0 = blockIdx.x * VAD_G;
-    // 1. samples: context (64 before the window's first new sample; zeros for a sequence's first window), 512 new ones (zeros past
-    //    the end of the sequence), then the reflection pad on the right: pad[576 + k] = x[574 - k]
-    for (int i = threadIdx.x; i < VAD_G * VAD_IN; i += NT) {
-        const int g = i / VAD_IN, s = i % VAD_IN;
-        float v = 0.f;
-        if (w0 + g < W) {
-            const VadWindow wd = win[w0 + g];
-            const int rel = s - VAD_CTX;                          // sample index relative to the window's first new sample
-            const bool ok = rel < 0 ? wd.has_ctx != 0 : rel < wd.n_valid;
-            if (ok) {
-                const int64_t idx = wd.start + rel;
-                v = is_f32 ? static_cast<const float*>(pcm)[idx] / wd.div
-                           : static_cast<float>(static_cast<const int16_t*>(pcm)[idx]) * (1.0f / 32768.0f);
-            }
-        }
-        sm.sig[g][s] = v;
-    }
+// everything behind the sample load: sm.sig[g][0 .. 575] of the block's windows -> their 512 gate inputs
+__device__ __forceinline__ void front_rest(FrontSmem& sm, int w0, int W, const VadWeights& wt, float* __restrict__ gin) {
     __syncthreads();
     for (int i = threadIdx.x; i < VAD_G * (VAD_PADDED - VAD_IN); i += NT) {
         const int g = i / (VAD_PADDED - VAD_IN), k = i % (VAD_PADDED - VAD_IN);
@@ -123,6 +104,61 @@ __global__ void __launch_bounds__(NT) vad_front_kernel(const void* __restrict__ 
         for (int g = 0; g < VAD_G; ++g)
             if (w0 + g < W) gin[(int64_t)(w0 + g) * VAD_GATES + j] = acc[g] + bb;
     }
+}
+
+__global__ void __launch_bounds__(NT) vad_front_kernel(const void* __restrict__ pcm, int is_f32, const VadWindow* __restrict__ win, int W,
+                                                      VadWeights wt, float* __restrict__ gin) {
+    __shared__ FrontSmem sm;
+    const int w0 = blockIdx.x * VAD_G;
+    // 1. samples: context (64 before the window's first new sample; zeros for a sequence's first window), 512 new ones (zeros past
+    //    the end of the sequence), then the reflection pad on the right: pad[576 + k] = x[574 - k]
+    for (int i = threadIdx.x; i < VAD_G * VAD_IN; i += NT) {
+        const int g = i / VAD_IN, s = i % VAD_IN;
+        float v = 0.f;
+        if (w0 + g < W) {
+            const VadWindow wd = win[w0 + g];
+            const int rel = s - VAD_CTX;                          // sample index relative to the window's first new sample
+            const bool ok = rel < 0 ? wd.has_ctx != 0 : rel < wd.n_valid;
+            if (ok) {
+                const int64_t idx = wd.start + rel;
+                v = is_f32 ? static_cast<const float*>(pcm)[idx] / wd.div
+                           : static_cast<float>(static_cast<const int16_t*>(pcm)[idx]) * (1.0f / 32768.0f);
+            }
+        }
+        sm.sig[g][s] = v;
+    }
+    front_rest(sm, w0, W, wt, gin);
+}
+
+// The ring source: the same windows cut from int16 rings in HBM, in place (VadPiece / VadRingWindow in vad_dev.h).  A ring range starts at
+// an arbitrary sample, so the loads are 2-byte loads, consecutive threads on consecutive samples; the value path is the int16 path above.
+__global__ void __launch_bounds__(NT) vad_front_ring_kernel(const VadPiece* __restrict__ pieces, const VadRingWindow* __restrict__ win, int W,
+                                                           VadWeights wt, float* __restrict__ gin) {
+    __shared__ FrontSmem sm;
+    const int w0 = blockIdx.x * VAD_G;
+    for (int i = threadIdx.x; i < VAD_G * VAD_IN; i += NT) {
+        const int g = i / VAD_IN, s = i % VAD_IN;
+        float v = 0.f;
+        if (w0 + g < W) {
+            const VadRingWindow wd = win[w0 + g];
+            const int rel = s - VAD_CTX;
+            const bool ok = rel < 0 ? wd.has_ctx != 0 : rel < wd.n_valid;
+            if (ok) {
+                const int64_t q = wd.pos + rel;                    // index within the sequence
+                int p = wd.piece;
+                while (p + 1 < wd.piece_end && q >= pieces[p].seq_off + pieces[p].n) ++p;
+                const VadPiece pc = pieces[p];
+                const int64_t o = q - pc.seq_off;
+                if (o >= 0 && o < pc.n) {
+                    int64_t idx = pc.start + o;                     // < 2 * cap
+                    if (idx >= pc.cap) idx -= pc.cap;
+                    v = static_cast<float>(pc.ring[idx]) * (1.0f / 32768.0f);
+                }
+            }
+        }
+        sm.sig[g][s] = v;
+    }
+    front_rest(sm, w0, W, wt, gin);
 }
 
 __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
@@ -178,6 +214,16 @@ __global__ void __launch_bounds__(VAD_GATES) vad_recur_kernel(const float* __res
 hipError_t vad_launch(const void* pcm, int is_f32, const VadWindow* win, int W, const int64_t* seq_base, int B, const VadWeights& wt,
                       float* gin, float* probs, hipStream_t st) {
     if (W > 0) hipLaunchKernelGGL(vad_front_kernel, dim3((W + VAD_G - 1) / VAD_G), dim3(NT), 0, st, pcm, is_f32, win, W, wt, gin);
+    if (B > 0) hipLaunchKernelGGL(vad_recur_kernel, dim3(B), dim3(VAD_GATES), 0, st, gin, seq_base, wt, probs);
+    return hipGetLastError();
+}
+
+hipError_t vad_launch_rings(const VadPiece* pieces, const VadRingWindow* win, int W, const int64_t* seq_base, int B, const VadWeights& wt,
+                            float* gin, float* probs, hipStream_t st, hipEvent_t front_done) {
+    if (W > 0) hipLaunchKernelGGL(vad_front_ring_kernel, dim3((W + VAD_G - 1) / VAD_G), dim3(NT), 0, st, pieces, win, W, wt, gin);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && front_done) e = hipEventRecord(front_done, st);
+    if (e != hipSuccess) return e;
     if (B > 0) hipLaunchKernelGGL(vad_recur_kernel, dim3(B), dim3(VAD_GATES), 0, st, gin, seq_base, wt, probs);
     return hipGetLastError();
 }

@@ -561,8 +561,9 @@ class _BulkReplica:
             return sum(len(r.windows) for r in self.q) + sum(sum(len(r.windows) for r in b) for _, b in self.inflight)
 
     def put(self, req: Request):
-        if not all(isinstance(w, np.ndarray) for w in req.windows):
-            raise TypeError("bulk mode takes host PCM windows (device ring slices are decoded by the row-level dispatcher: continuous=True, bulk=False)")
+        from .engine import RingSlice
+        if not all(isinstance(w, (np.ndarray, RingSlice)) for w in req.windows):
+            raise TypeError("bulk mode takes host PCM windows or slices of device rings")
         with self.cv:
             if self.stop:
                 raise RuntimeError("ASR engine is closed")

@@ -33,10 +33,10 @@ EXPORTS = [
     "sonic_service_begin", "sonic_service_end", "sonic_splice_rows", "sonic_service_step", "sonic_fetch_row", "sonic_fetch_rows", "sonic_prefill_enqueue",
     "sonic_runtime_info", "sonic_engine_info",
     "sonic_dispatch_create", "sonic_dispatch_submit", "sonic_dispatch_cancel", "sonic_dispatch_next", "sonic_dispatch_stats", "sonic_dispatch_close", "sonic_dispatch_destroy",
-    "sonic_pipeline_create", "sonic_pipeline_submit", "sonic_pipeline_wait", "sonic_pipeline_stats", "sonic_pipeline_last_error", "sonic_pipeline_destroy",
-    "sonic_vad_create", "sonic_vad_destroy", "sonic_vad_last_error", "sonic_vad_load_tensor", "sonic_vad_probs",
+    "sonic_pipeline_create", "sonic_pipeline_submit", "sonic_pipeline_submit_mixed", "sonic_pipeline_wait", "sonic_pipeline_stats", "sonic_pipeline_last_error", "sonic_pipeline_destroy",
+    "sonic_vad_create", "sonic_vad_destroy", "sonic_vad_last_error", "sonic_vad_load_tensor", "sonic_vad_probs", "sonic_vad_probs_rings",
 ]
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 class SonicDims(C.Structure):
@@ -137,6 +137,7 @@ def load_library():
     lib.sonic_runtime_info.argtypes = [C.c_int, ip, ip, ip]
     lib.sonic_pipeline_create.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     lib.sonic_pipeline_submit.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, i64p]
+    lib.sonic_pipeline_submit_mixed.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, i64p]
     lib.sonic_pipeline_wait.argtypes = [vp, C.c_int64]
     lib.sonic_pipeline_stats.argtypes = [vp, i64p, i64p, ip]
     lib.sonic_pipeline_last_error.argtypes = [vp]
@@ -171,6 +172,7 @@ def load_library():
     lib.sonic_vad_last_error.restype = C.c_char_p
     lib.sonic_vad_load_tensor.argtypes = [vp, C.c_char_p, vp, i64p, C.c_int]
     lib.sonic_vad_probs.argtypes = [vp, vp, vp, vp, C.c_int, vp]
+    lib.sonic_vad_probs_rings.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp]
     for name in EXPORTS:
         getattr(lib, name)
     if lib.sonic_abi_version() != ABI_VERSION:

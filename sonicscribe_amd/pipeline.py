@@ -163,9 +163,9 @@ class NativePipeline:
 
     def submit(self, prompts: Sequence[Sequence[int]], max_new: Sequence[int], segments: Optional[Sequence[np.ndarray]] = None,
                req_win: Optional[Sequence[int]] = None) -> int:
-        """One batch of len(prompts) <= block requests.  segments: int16 PCM windows (staged by the pipeline's prefill thread), or None = the
+        """One batch of len(prompts) <= block requests.  segments: int16 PCM windows and / or engine.RingSlice ranges of device rings (staged by the pipeline's prefill thread), or None = the
         batch is what every prefill handle has staged already.  Returns the ticket."""
-        from .engine import Engine, _p
+        from .engine import Engine, RingSlice, _p
         ids, poffs = Engine._pack_prompts(prompts)
         mn = np.ascontiguousarray(max_new, dtype=np.int32)
         rw = np.ascontiguousarray(req_win, dtype=np.int32) if req_win is not None else None
@@ -175,11 +175,18 @@ class NativePipeline:
         out_len = np.zeros(R, np.int32)
         pcm = offs = None
         W = 0
-        if segments is not None:
-            pcm, offs = self.decoders[0]._pack_pcm(segments)
-            W = len(segments)
         t = C.c_int64(0)
-        rc = self.lib.sonic_pipeline_submit(self.h, _p(pcm), _p(offs), W, _p(rw), R, _p(ids), _p(poffs), _p(mn), _p(out), ld, _p(out_len), C.byref(t))
+        if segments is not None and any(isinstance(s, RingSlice) for s in segments):
+            # windows that are ranges of device rings (file mode, streams): staged by sonic_stage_mixed on the prefill thread
+            pcm, offs, rings, start, n = self.decoders[0]._pack_mixed(segments)
+            W = len(segments)
+            rc = self.lib.sonic_pipeline_submit_mixed(self.h, _p(pcm), _p(offs), rings, _p(start), _p(n), W, _p(rw), R, _p(ids), _p(poffs), _p(mn),
+                                                      _p(out), ld, _p(out_len), C.byref(t))
+        else:
+            if segments is not None:
+                pcm, offs = self.decoders[0]._pack_pcm(segments)
+                W = len(segments)
+            rc = self.lib.sonic_pipeline_submit(self.h, _p(pcm), _p(offs), W, _p(rw), R, _p(ids), _p(poffs), _p(mn), _p(out), ld, _p(out_len), C.byref(t))
         if rc != 0:
             raise RuntimeError(self._err() or f"sonic_pipeline_submit failed with status {rc}")
         self._keep[t.value] = (pcm, offs, out, out_len)

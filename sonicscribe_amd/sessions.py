@@ -12,7 +12,8 @@ and every decode it triggers is a chunk / sample range of the session's ring in 
 
 The VAD network is a caller-supplied function: `vad(rows, windows_pcm, thresholds) -> bool[len(rows)]` gets, for every session with
 a complete 640 ms window, that window's int16 samples and the session's current dynamic threshold (Silero stays outside, as in the
-reference: its weights are not available offline).
+reference: its weights are not available offline).  With `device_vad=True` no window bytes are kept or built on the host: the callable
+gets, in the windows' place, each window's ring pieces `(ring, first_sample, n)` (vad.VADProcessor.ring_scorer scores them in place).
 """
 from __future__ import annotations
 
@@ -37,8 +38,9 @@ def committed_max_new_tokens(seconds: float) -> int:
 
 class GatedSessions:
     def __init__(self, model, session_ids: Sequence[str], buffer_seconds: float = 30.0, hotwords: Optional[List[str]] = None,
-                 cfg: GateConfig = GateConfig()):
+                 cfg: GateConfig = GateConfig(), device_vad: bool = False):
         self.model, self.ids, self.hotwords, self.cfg = model, list(session_ids), hotwords, cfg
+        self.device_vad = bool(device_vad)            # opt-in: windows are ring ranges, `recent` stays empty
         n = len(self.ids)
         self.streams = [model.open_stream(s, buffer_seconds) for s in self.ids]
         self.gate = BatchedVADGate(n, cfg)
@@ -54,12 +56,28 @@ class GatedSessions:
     def add_audio_chunk(self, s: int, audio_data: bytes, timestamp: Optional[float] = None) -> int:
         """main.py:813-842 -> connection_manager.py:108-125: one wire chunk of session s (timestamp: its arrival time, data_basic.py:11-20)."""
         cid = self.streams[s].add_audio_chunk(audio_data, timestamp)
-        self.recent[s][cid] = audio_data
+        if not self.device_vad:
+            self.recent[s][cid] = audio_data
         return cid
 
     def _window_pcm(self, s: int, ids: np.ndarray) -> np.ndarray:
         have = self.recent[s]
         return np.frombuffer(b"".join(have.get(int(c), b"") for c in ids), dtype=np.int16)
+
+    def _window_pieces(self, s: int, ids: np.ndarray) -> list:
+        """the window's chunks as ranges of the session's ring, neighbours merged; a chunk that left the buffer contributes nothing
+        (as a chunk without bytes in _window_pcm), so a window whose chunks have all left is empty = invalid"""
+        st = self.streams[s]
+        out: list = []
+        for c in ids:
+            ch = st.chunk_samples(int(c))
+            if ch is None or ch[1] == 0:
+                continue
+            if out and out[-1][1] + out[-1][2] == ch[0]:
+                out[-1] = (st.ring, out[-1][1], out[-1][2] + ch[1])
+            else:
+                out.append((st.ring, ch[0], ch[1]))
+        return out
 
     def _prune_recent(self):
         """drop the bytes of chunks that neither the gate's accumulator names nor the next look-back can offer again"""
@@ -83,11 +101,15 @@ class GatedSessions:
         rows = np.nonzero(ready)[0]
         sp, valid = np.zeros(n, bool), np.ones(n, bool)
         if rows.size:
-            pcm = [self._window_pcm(int(r), windows[r]) for r in rows]
+            if self.device_vad:
+                pcm = [self._window_pieces(int(r), windows[r]) for r in rows]
+            else:
+                pcm = [self._window_pcm(int(r), windows[r]) for r in rows]
             valid[rows] = [len(p) > 0 for p in pcm]
             sp[rows] = np.asarray(vad(rows, pcm, thr[rows]), bool)
         changed, start_id, end_id = self.gate.decide(ready, sp, valid)
-        self._prune_recent()
+        if not self.device_vad:
+            self._prune_recent()
         events: List[Dict] = []
         for s in np.nonzero(changed)[0]:
             s = int(s)

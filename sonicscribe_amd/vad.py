@@ -1,7 +1,9 @@
 """VADProcessor: a drop-in for the reference's backend/vad.py class with the Silero network on the GPU (sonic_vad_* of
 include/sonic_hip.h, csrc/vad.hip).  Construction, thresholds and both detection methods keep the reference's signatures and parameters;
 what `get_speech_timestamps` does after its model loop is vad_net.speech_timestamps.  New: `is_voice_active_batch` scores the windows of
-many sessions in one device call, and `scorer()` is the `vad` argument of sessions.GatedSessions.tick.
+many sessions in one device call, and `scorer()` is the `vad` argument of sessions.GatedSessions.tick.  Audio that already lies in device
+rings (engine.Ring) is scored in place: `probs_rings`, `detect_voice_activity_ring` (file mode, filemode.py) and `ring_scorer()` (the `vad`
+argument of a GatedSessions built with device_vad=True).
 
 Swap in the reference (models_manager.vad_model_init, models_manager.py:49): `_vad_processor = sonicscribe_amd.vad.VADProcessor()`.
 """
@@ -23,6 +25,7 @@ class VADProcessor:
         None = silero_vad.load_silero_vad() when the package is importable.  Raises ValueError for a rate other than 8000 / 16000
         (vad.py:21-22) and RuntimeError when the HIP library or the GPU is missing (no CPU fallback)."""
         self.sampling_rate = sampling_rate
+        self.device_id = int(device_id)
         self.threshold = threshold
         self.min_speech_duration = 0.3      # vad.py:16-17
         self.max_silence_duration = 1.0
@@ -70,6 +73,41 @@ class VADProcessor:
                                                  off.ctypes.data_as(C.c_void_p), len(seqs), out.ctypes.data_as(C.c_void_p)))
         return np.split(out[:int(nw.sum())], np.cumsum(nw)[:-1])
 
+    def probs_rings(self, engine_or_model, sequences: Sequence[Sequence[Tuple[object, int, int]]]) -> List[np.ndarray]:
+        """probs() of sequences that lie in device rings, read in place (sonic_vad_probs_rings): each sequence is a list of pieces
+        `(ring, first_sample, n)` and is scored as the int16 concatenation of its pieces would be by probs(), bit for bit.
+        engine_or_model: the Engine (or a slot of it, or the ASRModel) that owns the rings; None = the engine of the first ring."""
+        sequences = [list(sq) for sq in sequences]
+        if not sequences:
+            return []
+        pieces = [pc for sq in sequences for pc in sq]
+        eng = engine_or_model
+        if eng is None:
+            if not pieces:
+                return [np.zeros(0, np.float32) for _ in sequences]
+            eng = pieces[0][0].engine
+        elif hasattr(eng, "models"):                # an ASRModel: the replica that owns the rings
+            owners = {id(pc[0].engine.root) for pc in pieces}
+            eng = next((m for m in eng.models if id(m.root) in owners), eng.models[0])
+        if self.sampling_rate != 16000:
+            raise ValueError("VADProcessor.probs_rings: rings hold 16 kHz audio; this processor was built for another rate")
+        seq_piece = np.zeros(len(sequences) + 1, np.int64)
+        np.cumsum([len(sq) for sq in sequences], out=seq_piece[1:])
+        P = len(pieces)
+        rings = (C.c_void_p * max(1, P))(*[pc[0].h for pc in pieces])
+        start = np.array([int(pc[1]) for pc in pieces] or [0], np.int64)
+        n = np.array([int(pc[2]) for pc in pieces] or [0], np.int32)
+        nw = np.array([vad_net.n_windows(sum(int(pc[2]) for pc in sq)) for sq in sequences], np.int64)
+        out = np.zeros(max(1, int(nw.sum())), np.float32)
+        with self._lock:
+            if self.h is None:
+                raise RuntimeError("VADProcessor is closed")
+            if eng.h is None:
+                raise RuntimeError("VADProcessor.probs_rings: the engine is closed")
+            self._check(self.lib.sonic_vad_probs_rings(self.h, eng.h, rings, start.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.c_void_p),
+                                                       seq_piece.ctypes.data_as(C.c_void_p), len(sequences), out.ctypes.data_as(C.c_void_p)))
+        return np.split(out[:int(nw.sum())], np.cumsum(nw)[:-1])
+
     def _to16k(self, audio) -> np.ndarray:
         """vad.py:24-38 and :60-67 / :104-111: float, peak-normalised only above 1, resampled to 16 kHz"""
         a = audio.detach().cpu().numpy() if hasattr(audio, "detach") else np.asarray(audio)
@@ -90,6 +128,18 @@ class VADProcessor:
             return [], False
         ts = vad_net.speech_timestamps(self.probs([a])[0], a.size, threshold, int(self.min_speech_duration * 1000), float("inf"),
                                        int(self.max_silence_duration * 1000))
+        return ts, len(ts) > 0
+
+    def detect_voice_activity_ring(self, ring, first: int, n: int, threshold: Optional[float] = None) -> Tuple[List[Dict[str, int]], bool]:
+        """detect_voice_activity over samples [first, first + n) of a device ring (int16 wire PCM, scored as x / 32768 - what the
+        reference's float file tensor holds): the same timestamps logic on probabilities computed where the audio already is."""
+        if threshold is None:
+            threshold = self.threshold
+        n = int(n)
+        if n == 0:
+            return [], False
+        ts = vad_net.speech_timestamps(self.probs_rings(ring.engine, [[(ring, int(first), n)]])[0], n, threshold,
+                                       int(self.min_speech_duration * 1000), float("inf"), int(self.max_silence_duration * 1000))
         return ts, len(ts) > 0
 
     def is_voice_active(self, audio_chunk, threshold: Optional[float] = None) -> bool:
@@ -132,6 +182,24 @@ class VADProcessor:
         device call (what vad_processor_manager.py:95-104 does per session: int16 / 32768 -> is_voice_active at the dynamic threshold)."""
         def vad(rows, pcm, thr):
             return self.is_voice_active_batch(pcm, thr)
+        return vad
+
+    def ring_scorer(self):
+        """The `vad` callable of a sessions.GatedSessions built with device_vad=True: there the second argument carries, per row, the
+        ring pieces `(ring, first_sample, n)` of the gate's window ids and no bytes; the windows of one tick are scored in place in
+        one sonic_vad_probs_rings call per engine replica (the pieces name their rings themselves)."""
+        def vad(rows, pieces, thr):
+            thr = np.broadcast_to(np.asarray(thr, np.float64), (len(pieces),))
+            out = np.zeros(len(pieces), bool)
+            by_engine: Dict[int, List[int]] = {}
+            for i, sq in enumerate(pieces):
+                if sum(int(pc[2]) for pc in sq) > 0:
+                    by_engine.setdefault(id(sq[0][0].engine.root), []).append(i)
+            for live in by_engine.values():
+                for i, p in zip(live, self.probs_rings(pieces[live[0]][0][0].engine, [pieces[i] for i in live])):
+                    n = sum(int(pc[2]) for pc in pieces[i])
+                    out[i] = len(vad_net.speech_timestamps(p, n, float(thr[i]), **vad_net.CHUNK_PARAMS)) > 0
+            return out
         return vad
 
     def close(self) -> None:
