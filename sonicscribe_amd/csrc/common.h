@@ -133,7 +133,7 @@ __device__ __forceinline__ void prefetch_share(const PrefetchRange& r, int blk, 
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(t) :: "memory");
 }
 
-// ---- GEMM launch descriptors (gemm.hip) ----
+// ---- GEMM launch descriptors (gemm.hip, gemm256.hip; SkinnyArgs: skinny.hip, skinny_fused.hip) ----
 enum GemmEpi {
     EPI_BIAS = 0,       // C = bf16(acc + bias)
     EPI_BIAS_GELU = 1,  // C = bf16(gelu(bf16(acc + bias)))
@@ -224,6 +224,12 @@ struct KI8 {   // v_mfma_i32_16x16x64_i8: 16 int8 of k per lane and step, lane l
 // host-side dispatch: KD_SWITCH(args, KD, launch<KD>(...))
 #define KD_SWITCH(a, KD, ...) do { if ((a).q.sca) { typedef KI8 KD; __VA_ARGS__; } else if ((a).dt == DT_F16) { typedef KF16 KD; __VA_ARGS__; } \
                                    else { typedef KBF16 KD; __VA_ARGS__; } } while (0)
+// ... on the 16-row blocks of a decode step's activations (1 .. 4): MB_SWITCH((M + 15) / 16, MB, launch<MB>(...))
+#define MB_SWITCH(mb, MB, ...) do { if ((mb) <= 1) { constexpr int MB = 1; __VA_ARGS__; } else if ((mb) == 2) { constexpr int MB = 2; __VA_ARGS__; } \
+                                    else if ((mb) == 3) { constexpr int MB = 3; __VA_ARGS__; } else { constexpr int MB = 4; __VA_ARGS__; } } while (0)
+// ... on the K of the fused decode kernels, as KS8 = K / 256 (the k-steps of 32 in a wave's K eighth): KS8_SWITCH(K, KS8, launch<KS8>(...))
+#define KS8_SWITCH(K, KS8, ...) do { switch (K) { case 256: { constexpr int KS8 = 1; __VA_ARGS__; } break; case 512: { constexpr int KS8 = 2; __VA_ARGS__; } break; \
+                                     case 1024: { constexpr int KS8 = 4; __VA_ARGS__; } break; default: { constexpr int KS8 = 8; __VA_ARGS__; } break; } } while (0)
 
 struct SkinnyArgs {
     const bf16_t* X; long ldx;       // [M<=64][K]   (i8: int8_t data)

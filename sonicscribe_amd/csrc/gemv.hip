@@ -5,7 +5,7 @@
 // like the other experiments that lost; the expectation it was built on is left below as written.
 //
 // Why: BASELINE configs 1 and 5 are latency shapes - one `transcribe()` call at a time (backend/transcription_manager.py:43-65), a 20 s final of one session.  At one row the
-// MFMA decode kernels of gemm.hip still stage a 16-row X image, reduce 16 x 16 accumulator tiles through LDS and hand K slabs to a separate add + RMSNorm launch: 1.19 ms per token
+// MFMA decode kernels of skinny.hip / skinny_fused.hip still stage a 16-row X image, reduce 16 x 16 accumulator tiles through LDS and hand K slabs to a separate add + RMSNorm launch: 1.19 ms per token
 // step, 42 us per layer, barely less than at 32 rows.  A row count this small needs none of that: the weights go through every lane once (v_dot2c on the 16-byte fragments of the
 // SAME fragment-tiled copies the MFMA kernels read - one weight copy), the few activation rows sit in LDS, every projection sees its whole K inside one block (no slabs), and the
 // norms ride in the consumer.  Five launches per layer:

@@ -9,7 +9,7 @@
 #define INT8_DEQ_W 7.874015718698502e-3f        // 1 / 127, int8_vectorwise_dequant
 
 // int8 weight W[n][k] out of the row-major matrix or, when present, the fragment-tiled copy (element (n, k) at
-// ((n/16)*(K/64) + k/64)*1024 + (((k%64)/16)*16 + n%16)*16 + k%16, gemm.hip tile_weights_i8_kernel)
+// ((n/16)*(K/64) + k/64)*1024 + (((k%64)/16)*16 + n%16)*16 + k%16, tile_weights.hip tile_weights_i8_kernel)
 __device__ __forceinline__ float deq_w(const DeqInfo& q, int n, int k) {
     if (q.cbt) return (float)q.cbt[((long)(n >> 4) * (q.K >> 6) + (k >> 6)) * 1024 + ((((k & 63) >> 4) * 16) + (n & 15)) * 16 + (k & 15)];
     return (float)q.cb[(long)n * q.K + k];
