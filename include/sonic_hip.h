@@ -36,6 +36,12 @@
  *   sonic_vad_probs_rings      the same loop over audio that already lies in device rings: the whole-file VAD call of
  *                              /transcribe/file (backend/main.py:308-314, the file tensor uploaded for it) and the per-tick
  *                              window of vad_processor_manager.py:95-104 (int16 / 32768 of the accumulated chunks)
+ *   sonic_resample             torchaudio.transforms.Resample(sampling_rate, target_sr)(wav)             backend/asr.py:255-261
+ *   sonic_ring_create_rate     the host resampling in front of everything that reads a session's or a file's audio:
+ *                              Resample(sampling_rate, 16000) at backend/vad.py:63-67 and :108-112,
+ *                              audio.set_frame_rate(16000) at backend/utils.py:18
+ *   sonic_ring_flush           the end of such a stream (the trailing samples of Resample's output)      backend/asr.py:255-261
+ *   sonic_ring_read            the per-session debug WAV dump                                            backend/debug.py:14-72
  */
 #ifndef SONIC_HIP_H
 #define SONIC_HIP_H
@@ -47,7 +53,7 @@ extern "C" {
 /* The library is built with -fvisibility=hidden: these declarations are its whole dynamic symbol table (tests/test_host_logic.py checks
  * `nm -D` against this header).  SONIC_ABI_VERSION moves whenever a signature or a struct layout below changes. */
 #define SONIC_API __attribute__((visibility("default")))
-#define SONIC_ABI_VERSION 10
+#define SONIC_ABI_VERSION 11
 SONIC_API int sonic_abi_version(void);
 
 typedef struct sonic_engine sonic_engine;
@@ -269,6 +275,28 @@ SONIC_API void sonic_ring_destroy(sonic_ring* r);
  * copied to a pinned mirror and their H2D copy is queued; decodes that name them order behind it */
 SONIC_API int sonic_ring_append(sonic_ring* r, const int16_t* pcm, int64_t n, int64_t* first_index);
 SONIC_API int64_t sonic_ring_head(sonic_ring* r);     /* samples appended so far */
+/* Rings at any input rate (ABI 11).  A ring made by sonic_ring_create_rate takes, in sonic_ring_append, samples at in_rate; a polyphase
+ * windowed-sinc kernel (csrc/resample.hip: torchaudio's sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99) writes them into the ring
+ * as 16 kHz int16, q = clip(rint(y * 32768)).  capacity_samples, the ring's content, its indices, sonic_ring_head, *first_index and every
+ * reader stay in 16 kHz samples; *first_index is the head before the call and the head after it tells how many outputs the chunk made
+ * (possibly none).  With of = in_rate / g, nf = 16000 / g, width = ceil(6 * of / (min(of, nf) * 0.99)): after N input samples in total the ring
+ * holds the outputs j < nf * (floor((N - width - of) / of) + 1) (0 for N < width + of) - the frames whose taps all exist - and keeps the input
+ * samples the next frames still need on the device.  An output's bits do not depend on how the stream was cut into appends.  A chunk whose
+ * outputs exceed the capacity is refused.  in_rate == 16000 gives exactly the ring of sonic_ring_create.  Refused (SONIC_ERR_INVALID, the
+ * message names the numbers): in_rate <= 0, and rates whose coefficient bank nf * (2 * width + of) exceeds 2^22 entries (16001 Hz).  The bank
+ * is built once per rate pair, in double, rounded to fp32, and shared by every ring and slot of the engine.
+ * sonic_ring_flush ends the stream: it emits the remaining outputs up to ceil(nf * N / of) with zeros beyond the last sample; the next
+ * append starts a new stream without history.  It does nothing on a 16 kHz ring.
+ * sonic_ring_read copies the ring samples [first, first + n) to the host, behind every append so far; the range rule is that of
+ * sonic_stage_mixed.  Appends, flushes and reads report failures through sonic_last_error(NULL) of the calling thread. */
+SONIC_API int sonic_ring_create_rate(sonic_engine* e, int64_t capacity_samples, int32_t in_rate, sonic_ring** out);
+SONIC_API int sonic_ring_flush(sonic_ring* r);
+SONIC_API int sonic_ring_read(sonic_ring* r, int64_t first, int64_t n, int16_t* out_i16);
+/* One-shot resampler over a whole host buffer of n samples (exactly one of pcm_i16 - taken as s / 32768 - and pcm_f32 is given), zeros
+ * beyond both ends: *n_out = ceil(nf * n / of) fp32 outputs, the same bits the rate ring rounds.  out_f32 == NULL asks for *n_out only.
+ * Takes its own lock and stream, never the engine's batch lock: it does not queue behind a decode.  Errors: sonic_last_error(NULL). */
+SONIC_API int sonic_resample(sonic_engine* e, const int16_t* pcm_i16, const float* pcm_f32, int64_t n, int32_t in_rate, int32_t out_rate,
+                             float* out_f32, int64_t out_cap, int64_t* n_out);
 /* sonic_pipeline_submit with the windows of sonic_stage_mixed: window w is a range of ring rings[w] (raw wire PCM, a1 + a2 on the device,
  * peak over the windows of its request) or, where rings[w] is NULL, host PCM as in sonic_pipeline_submit.  The ring arrays are copied; the
  * ranges are checked, and the rings locked, when a prefill thread stages the batch (a range that has left its ring by then fails the batch

@@ -107,14 +107,20 @@ class AudioStream:
     int16 -> float -> peak-normalise -> PCM_16 steps run on the device (csrc/ingest.hip), bit-identical with the host path.
     """
 
-    def __init__(self, model: "ASRModel", session: str, replica: int, buffer_seconds: float, margin_seconds: float = 10.0):
+    def __init__(self, model: "ASRModel", session: str, replica: int, buffer_seconds: float, margin_seconds: float = 10.0,
+                 sampling_rate: int = 16000):
         self.model, self.session, self.replica = model, session, replica
+        # wire chunks at another rate than the model's (8 kHz telephony, 48 kHz capture) are resampled by the ring's append
+        # (engine.Ring rate=): chunk c maps to the 16 kHz range [head before, head after) of its append - possibly empty - and
+        # everything below stays in 16 kHz samples
+        self.sampling_rate = int(sampling_rate)
         # A decode names a sample range and the range is only read when the replica reaches the request, so the ring is LARGER than the
         # buffer the session sees: chunks stay addressable for `buffer_seconds` (the reference's MAX_AUDIO_BUFFER_SECONDS, config.py:25),
         # and a queued request survives `margin_seconds` of further appends before the ring overwrites its oldest samples (the
         # reference concatenates on the host at call time and cannot lose audio that way).
         self.visible = int(buffer_seconds * model.target_sr)
-        self.ring = model.models[replica].ring_create(int((buffer_seconds + margin_seconds) * model.target_sr))
+        cap = int((buffer_seconds + margin_seconds) * model.target_sr)
+        self.ring = model.models[replica].ring_create(cap) if self.sampling_rate == model.target_sr else model.models[replica].ring_create(cap, rate=self.sampling_rate)
         self._chunks: Dict[int, tuple] = {}       # chunk id -> (first sample index, samples)
         self.next_chunk_id = 0
         self._oldest = 0                          # smallest chunk id still in the buffer
@@ -124,8 +130,9 @@ class AudioStream:
         first = self.ring.append(audio_data)
         cid = self.next_chunk_id
         self.next_chunk_id += 1
-        self._chunks[cid] = (first, len(audio_data) // 2, time.time() if timestamp is None else float(timestamp))
-        floor = first + len(audio_data) // 2 - self.visible           # chunks older than the buffer (audio_manager.py:35-59 drops them by age)
+        n = len(audio_data) // 2 if self.sampling_rate == self.model.target_sr else self.ring.head - first     # a rate ring: what the append emitted
+        self._chunks[cid] = (first, n, time.time() if timestamp is None else float(timestamp))
+        floor = first + n - self.visible           # chunks older than the buffer (audio_manager.py:35-59 drops them by age)
         while self._oldest < cid and self._chunks[self._oldest][0] < floor:
             del self._chunks[self._oldest]
             self._oldest += 1
@@ -282,13 +289,15 @@ class ASRModel:
         inner = self._dispatcher.submit(windows, prompt, int(max_new_tokens), session=session)
         return _text_future(inner, self.prompt.decode)
 
-    def open_stream(self, session: str, buffer_seconds: float = 30.0, margin_seconds: float = 10.0) -> AudioStream:
+    def open_stream(self, session: str, buffer_seconds: float = 30.0, margin_seconds: float = 10.0, sampling_rate: int = 16000) -> AudioStream:
         """A streaming session whose audio stays on the device (config.py:25 MAX_AUDIO_BUFFER_SECONDS = 30): chunks are appended to a
         ring on the session's GPU, partial / final decodes name chunk ranges (AudioStream).  The ring holds `margin_seconds` more than
         the buffer, so a max-length final that waits in the queue is not overwritten by the chunks that keep arriving."""
         if not hasattr(self, "model"):
             raise RuntimeError("ASR model has been released")
-        return AudioStream(self, session, self._dispatcher.home(session), buffer_seconds, margin_seconds)
+        if sampling_rate == self.target_sr:
+            return AudioStream(self, session, self._dispatcher.home(session), buffer_seconds, margin_seconds)
+        return AudioStream(self, session, self._dispatcher.home(session), buffer_seconds, margin_seconds, sampling_rate=sampling_rate)
 
     async def transcribe_async(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128,
                                hotwords: Optional[List[str]] = None, session: Optional[str] = None) -> str:
@@ -338,20 +347,22 @@ class ASRModel:
         return [self.prompt.decode(i).strip() for i in ids]
 
     def transcribe_file(self, audio, vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
-                        max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filename: str = ""):
+                        max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filename: str = "", sampling_rate: int = 16000):
         """The body of the reference's /transcribe/file endpoint (main.py:193-649) as a generator of its records (dicts with the
         reference's keys: initialization, segments_summary, segment_result / segment_error in segment order, final_summary).  `audio`:
-        16 kHz mono int16 PCM, or the reference's float tensor [1, N] of int16 / 32768 values; `vad`: a vad.VADProcessor.  The file is
-        appended once to a device ring, VAD-scored there, and every segment is queued at once as a range of that ring on this model's
-        scheduler; the ring is destroyed when the generator is exhausted or closed (filemode.py)."""
+        mono int16 PCM at `sampling_rate`, or the reference's float tensor [1, N] of int16 / 32768 values; `vad`: a vad.VADProcessor.  The
+        file is appended once to a device ring (resampled to 16 kHz by the append when `sampling_rate` is another rate: utils.py:18),
+        VAD-scored there, and every segment is queued at once as a range of that ring on this model's scheduler; the ring is destroyed when
+        the generator is exhausted or closed (filemode.py).  Sizes and times in the records are those of the 16 kHz content."""
         from . import filemode
-        return filemode.transcribe_file(self, audio, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filename)
+        return filemode.transcribe_file(self, audio, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filename, sampling_rate)
 
     def transcribe_files(self, audios: Sequence[Any], vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
-                         max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filenames: Optional[Sequence[str]] = None):
+                         max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filenames: Optional[Sequence[str]] = None,
+                         sampling_rate: int = 16000):
         """transcribe_file for several files: all VAD passes in one device call, one record iterator per file (filemode.transcribe_files)."""
         from . import filemode
-        return filemode.transcribe_files(self, audios, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filenames)
+        return filemode.transcribe_files(self, audios, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filenames, sampling_rate)
 
     def get_model_info(self) -> Dict[str, Any]:
         """asr.py:490-513: the reference's keys for a GPU device (`cuda_version` carries the HIP runtime version: torch.version.cuda is

@@ -446,6 +446,7 @@ extern "C" void sonic_destroy(sonic_engine* e) {
     }
     for (sonic_ring* r : e->rings) ring_free(r);       // rings the caller left behind go with their engine
     e->rings.clear();
+    resample_release(e);
     for (auto& g : e->graphs) (void)hipGraphExecDestroy(g.second);
     for (void* p : e->allocs) (void)hipFree(p);
     if (e->dump) (void)hipFree(e->dump);

@@ -35,11 +35,21 @@ struct sonic_ring {
     hipEvent_t read_ev = nullptr; bool read_pending = false;   // last staging kernel that read this ring (appends order behind it)
     hipEvent_t app_ev = nullptr; bool app_pending = false;     // last append (staging kernels order behind it)
     int64_t unsynced = 0;                  // samples whose H2D copy may still be reading the pinned mirror
+    // Rate ring (sonic_ring_create_rate, in_rate != 16000): appends take samples at in_rate, the resampler kernel (resample.hip) writes the
+    // ring's 16 kHz int16 content; indices, head and every reader stay in 16 kHz samples.  The raw samples go through `lin`: the carry - the
+    // last input samples the next frames still need, fewer than K - right-aligned in front of the piece that was just uploaded.
+    bool rated = false;
+    RsBank bank;
+    int16_t* lin = nullptr;                // device: [carry_max | piece] samples at in_rate
+    int16_t* host_in = nullptr;            // pinned mirror of the raw chunks: 2 * piece samples, used circularly (`mpos`, `unsynced`)
+    int64_t carry_max = 0, piece = 0, carry = 0, mpos = 0;
+    int64_t n_in = 0, emitted = 0;         // of the current stream: input samples so far, outputs already in the ring (= J(n_in))
+    int64_t dev_bytes = 0;                 // what this ring added to the owner's ring_bytes
 };
+// outputs whose taps all exist after N input samples: whole frames only
+static int64_t rate_emitted(const RsBank& b, int64_t N) { return N >= b.width + b.of ? (int64_t)b.nf * ((N - b.width - b.of) / b.of + 1) : 0; }
 
-extern "C" int sonic_ring_create(sonic_engine* e, int64_t capacity_samples, sonic_ring** out) {
-    if (!e || !out) return SONIC_ERR_INVALID;
-    ENTER(e);
+static int ring_create_locked(sonic_engine* e, int64_t capacity_samples, const RsBank* bank, sonic_ring** out) {
     if (capacity_samples < 1024 || capacity_samples > ((int64_t)1 << 31)) return fail(e, SONIC_ERR_INVALID, "ring capacity %lld out of range", (long long)capacity_samples);
     sonic_ring* r = new sonic_ring();
     r->e = e; r->cap = capacity_samples;
@@ -50,15 +60,50 @@ extern "C" int sonic_ring_create(sonic_engine* e, int64_t capacity_samples, soni
         (void)hipFree(r->buf); (void)hipHostFree(r->host); if (r->st) (void)hipStreamDestroy(r->st); if (r->read_ev) (void)hipEventDestroy(r->read_ev);
         delete r; return fail(e, SONIC_ERR_HIP, "ring stream / event creation failed");
     }
+    r->dev_bytes = capacity_samples * 2;
+    if (bank) {
+        r->rated = true; r->bank = *bank;
+        r->carry_max = (int64_t)bank->K + bank->of;
+        // the largest chunk whose outputs can fit the ring, cut into pieces of at most 2^18 samples (chunking does not change a bit)
+        const int64_t n_max = (capacity_samples / bank->nf + 2) * bank->of + bank->K;
+        r->piece = n_max < ((int64_t)1 << 18) ? n_max : ((int64_t)1 << 18);
+        const size_t lin_bytes = (size_t)(r->carry_max + r->piece) * 2;
+        hipError_t er = hipMalloc((void**)&r->lin, lin_bytes);
+        if (er == hipSuccess) er = hipHostMalloc((void**)&r->host_in, (size_t)r->piece * 4, hipHostMallocDefault);
+        if (er != hipSuccess) {
+            (void)hipGetLastError();
+            if (r->lin) (void)hipFree(r->lin);
+            (void)hipFree(r->buf); (void)hipHostFree(r->host); (void)hipStreamDestroy(r->st); (void)hipEventDestroy(r->read_ev); (void)hipEventDestroy(r->app_ev);
+            delete r; return fail(e, SONIC_ERR_OOM, "out of memory (rate ring: %zu bytes of input staging)", lin_bytes);
+        }
+        r->dev_bytes += (int64_t)lin_bytes;
+    }
     zero_fill(e, r->buf, (size_t)capacity_samples * 2);
     HIPC(e, stream_sync(e));
     // rings live in the registry of the weight owner: every slot of an engine may stage from every ring of it
     sonic_engine* root = e->owner ? e->owner : e;
     r->e = root;
     { std::lock_guard<std::mutex> rl(root->rings_mu); root->rings.push_back(r); }
-    root->ring_bytes += capacity_samples * 2;
+    root->ring_bytes += r->dev_bytes;
     *out = r;
     return SONIC_OK;
+}
+extern "C" int sonic_ring_create(sonic_engine* e, int64_t capacity_samples, sonic_ring** out) {
+    if (!e || !out) return SONIC_ERR_INVALID;
+    ENTER(e);
+    return ring_create_locked(e, capacity_samples, nullptr, out);
+}
+// A ring fed at in_rate (8 kHz telephony, 44.1 kHz files, 48 kHz capture): what the reference resamples on the host before anything else sees
+// the audio (torchaudio Resample at backend/vad.py:63-67 and :108-112, set_frame_rate(16000) at backend/utils.py:18).  in_rate == 16000 is
+// exactly sonic_ring_create's ring.
+extern "C" int sonic_ring_create_rate(sonic_engine* e, int64_t capacity_samples, int32_t in_rate, sonic_ring** out) {
+    if (!e || !out) return SONIC_ERR_INVALID;
+    ENTER(e);
+    if (in_rate == 16000) return ring_create_locked(e, capacity_samples, nullptr, out);
+    RsBank b; std::string err;
+    const int rc = resample_bank_get(e->owner ? e->owner : e, in_rate, 16000, &b, err);
+    if (rc != SONIC_OK) return fail(e, rc, "%s", err.c_str());
+    return ring_create_locked(e, capacity_samples, &b, out);
 }
 void ring_free(sonic_ring* r) {
     {
@@ -66,7 +111,9 @@ void ring_free(sonic_ring* r) {
         (void)hipSetDevice(r->e->device);
         (void)hipStreamSynchronize(r->st);
         (void)hipFree(r->buf); (void)hipHostFree(r->host); (void)hipStreamDestroy(r->st); (void)hipEventDestroy(r->read_ev); (void)hipEventDestroy(r->app_ev);
-        r->e->ring_bytes -= r->cap * 2;
+        if (r->lin) (void)hipFree(r->lin);
+        if (r->host_in) (void)hipHostFree(r->host_in);
+        r->e->ring_bytes -= r->dev_bytes;
     }
     delete r;
 }
@@ -86,11 +133,102 @@ extern "C" int64_t sonic_ring_head(sonic_ring* r) {
     std::lock_guard<std::mutex> lk(r->mu);
     return r->head;
 }
+// kernel arguments of a rate ring's next outputs: the source is carry + chunk in `lin`, the first output lands at the ring's head
+static ResampleArgs rate_args(sonic_ring* r) {
+    const RsBank& b = r->bank;
+    ResampleArgs a{};
+    a.src = r->lin + r->carry_max - r->carry; a.src_base = r->n_in - r->carry;
+    a.bank = b.dev; a.of = b.of; a.nf = b.nf; a.width = b.width; a.K = b.K; a.tile = b.tile; a.kc = b.kc;
+    a.j0 = r->emitted; a.ring = r->buf; a.ring_cap = r->cap; a.ring_pos = r->head % r->cap;
+    return a;
+}
+// sonic_ring_append on a rate ring (under the ring's lock): n samples at in_rate.  After N input samples in total the ring holds the outputs
+// j < J(N) (rate_emitted: the frames whose taps all exist); the chunk is refused when its outputs exceed the capacity.  Non-blocking like the
+// plain append: pinned mirror of the raw chunk, async H2D, the kernel and the carry move on the ring's stream, app_ev behind them.
+static int rate_append_locked(sonic_ring* r, const int16_t* pcm, int64_t n, int64_t* first_index) {
+    const RsBank& b = r->bank;
+    const int64_t total = rate_emitted(b, r->n_in + n) - r->emitted;
+    if (total > r->cap)
+        return fail(nullptr, SONIC_ERR_INVALID, "sonic_ring_append: a chunk of %lld samples makes %lld outputs, the ring holds %lld", (long long)n, (long long)total, (long long)r->cap);
+    auto hip_fail = [&](const char* what, hipError_t er) { (void)hipGetLastError(); return fail(nullptr, SONIC_ERR_HIP, "sonic_ring_append: %s failed: %s", what, hipGetErrorString(er)); };
+    hipError_t er = hipSetDevice(r->e->device);
+    if (er != hipSuccess) return hip_fail("hipSetDevice", er);
+    if (first_index) *first_index = r->head;
+    const int64_t M = 2 * r->piece;
+    for (int64_t off = 0; off < n;) {
+        const int64_t m = n - off < r->piece ? n - off : r->piece;
+        // the mirror is a circular buffer of contiguous slots; the stream is drained before a slot could be rewritten under a pending copy
+        if (r->mpos + m > M) { r->unsynced += M - r->mpos; r->mpos = 0; }
+        if (r->unsynced + m > M) { er = hipStreamSynchronize(r->st); if (er != hipSuccess) return hip_fail("hipStreamSynchronize", er); r->unsynced = 0; }
+        memcpy(r->host_in + r->mpos, pcm + off, (size_t)m * 2);
+        er = hipMemcpyAsync(r->lin + r->carry_max, r->host_in + r->mpos, (size_t)m * 2, hipMemcpyHostToDevice, r->st);
+        if (er != hipSuccess) return hip_fail("hipMemcpyAsync", er);
+        r->mpos += m; r->unsynced += m;
+        const int64_t N = r->n_in + m, J = rate_emitted(b, N);
+        ResampleArgs a = rate_args(r);
+        a.src_n = r->carry + m; a.n_out = J - r->emitted;
+        launch_resample(a, false, r->st);
+        // what the next frame (J / nf) still needs: the samples from its first tap on
+        const int64_t lowest = (J / b.nf) * b.of - b.width > 0 ? (J / b.nf) * b.of - b.width : 0, keep = N - lowest;
+        launch_resample_carry(r->lin, r->carry_max - keep, r->carry_max + m - keep, keep, r->st);
+        if ((er = hipGetLastError()) != hipSuccess) return hip_fail("resample kernel launch", er);
+        r->head += a.n_out; r->emitted = J; r->n_in = N; r->carry = keep;
+        off += m;
+    }
+    if (n > 0) { er = hipEventRecord(r->app_ev, r->st); if (er != hipSuccess) return hip_fail("hipEventRecord", er); r->app_pending = true; }
+    return SONIC_OK;
+}
+// Ends the stream of a rate ring: emits the outputs J(N) .. ceil(nf * N / of) - 1 with zeros beyond the N samples appended (the trim of the
+// one-shot resampler); the next append starts a new stream with zero history.  Nothing to do on a 16 kHz ring.
+extern "C" int sonic_ring_flush(sonic_ring* r) {
+    if (!r) return SONIC_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(r->mu);
+    if (!r->rated || r->n_in == 0) return SONIC_OK;
+    const RsBank& b = r->bank;
+    const int64_t total = ((int64_t)b.nf * r->n_in + b.of - 1) / b.of, n_out = total - r->emitted;
+    if (n_out > r->cap) return fail(nullptr, SONIC_ERR_INVALID, "sonic_ring_flush: %lld outputs, the ring holds %lld", (long long)n_out, (long long)r->cap);
+    auto hip_fail = [&](const char* what, hipError_t er) { (void)hipGetLastError(); return fail(nullptr, SONIC_ERR_HIP, "sonic_ring_flush: %s failed: %s", what, hipGetErrorString(er)); };
+    hipError_t er = hipSetDevice(r->e->device);
+    if (er != hipSuccess) return hip_fail("hipSetDevice", er);
+    if (n_out > 0) {
+        ResampleArgs a = rate_args(r);
+        a.src_n = r->carry; a.n_out = n_out;
+        launch_resample(a, false, r->st);
+        if ((er = hipGetLastError()) != hipSuccess) return hip_fail("resample kernel launch", er);
+        if ((er = hipEventRecord(r->app_ev, r->st)) != hipSuccess) return hip_fail("hipEventRecord", er);
+        r->app_pending = true;
+        r->head += n_out;
+    }
+    r->n_in = 0; r->emitted = 0; r->carry = 0;
+    return SONIC_OK;
+}
+// Ring samples [first, first + n) to the host, behind every append so far: the device session's counterpart of the reference's per-session
+// debug WAV dump (backend/debug.py:14-72).  The range rule is sonic_stage_mixed's.
+extern "C" int sonic_ring_read(sonic_ring* r, int64_t first, int64_t n, int16_t* out_i16) {
+    if (!r || (!out_i16 && n > 0)) return SONIC_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(r->mu);
+    if (n < 0 || first < 0 || first + n > r->head || first < r->head - r->cap)
+        return fail(nullptr, SONIC_ERR_INVALID, "sonic_ring_read: samples [%lld, %lld) are not in the ring (holds [%lld, %lld))", (long long)first, (long long)(first + n),
+                    (long long)(r->head > r->cap ? r->head - r->cap : 0), (long long)r->head);
+    if (n == 0) return SONIC_OK;
+    auto hip_fail = [&](const char* what, hipError_t er) { (void)hipGetLastError(); return fail(nullptr, SONIC_ERR_HIP, "sonic_ring_read: %s failed: %s", what, hipGetErrorString(er)); };
+    hipError_t er = hipSetDevice(r->e->device);
+    if (er != hipSuccess) return hip_fail("hipSetDevice", er);
+    const int64_t pos = first % r->cap, head_n = n < r->cap - pos ? n : r->cap - pos;
+    // on the ring's own stream: in order behind the appends (and their kernels)
+    if ((er = hipMemcpyAsync(out_i16, r->buf + pos, (size_t)head_n * 2, hipMemcpyDeviceToHost, r->st)) != hipSuccess) return hip_fail("hipMemcpyAsync", er);
+    if (n > head_n && (er = hipMemcpyAsync(out_i16 + head_n, r->buf, (size_t)(n - head_n) * 2, hipMemcpyDeviceToHost, r->st)) != hipSuccess) return hip_fail("hipMemcpyAsync (wrap)", er);
+    if ((er = hipStreamSynchronize(r->st)) != hipSuccess) return hip_fail("hipStreamSynchronize", er);
+    r->unsynced = 0;
+    return SONIC_OK;
+}
 // append n samples; *first_index = absolute index of pcm[0].  Returns at once (the samples are copied to the pinned mirror, the caller may
 // reuse pcm); the H2D copy is queued on the ring's stream and every later staging kernel orders behind it.
+// (A rate ring: n samples at its input rate, *first_index = the head before the call; rate_append_locked.)
 extern "C" int sonic_ring_append(sonic_ring* r, const int16_t* pcm, int64_t n, int64_t* first_index) {
     if (!r || (!pcm && n > 0) || n < 0) return SONIC_ERR_INVALID;
     std::lock_guard<std::mutex> lk(r->mu);
+    if (r->rated) return rate_append_locked(r, pcm, n, first_index);
     if (n > r->cap) return SONIC_ERR_INVALID;
     // failures are reported through sonic_last_error(NULL) of the calling thread (appends do not take the engine lock, so they cannot
     // write the engine's own error string)

@@ -58,6 +58,10 @@ struct F32State {
     float *Kc = nullptr, *Vc = nullptr, *logits = nullptr, *hlast = nullptr;
 };
 
+// resampler bank of one rate pair (engine_resample.cpp): built in double on the host, rounded once to fp32, k-major on the device
+struct RsBank { float* dev = nullptr; int of = 0, nf = 0, width = 0, K = 0, tile = 0, kc = 0; };
+#define RS_BANK_MAX_COEF ((int64_t)1 << 22)
+
 struct sonic_engine {
     sonic_dims d;
     int device = 0, mode = 0, Bm = 0, max_ctx = 0;
@@ -171,6 +175,10 @@ struct sonic_engine {
     int* ring_peak = nullptr;                        // [Bm] per-request max |s| of a ring-staged batch (ingest.hip)
     std::atomic<int64_t> ring_bytes{0};             // owner: device bytes of those rings (part of sonic_memory_info of the owner)
     std::vector<struct sonic_ring*> rings;          // rings created on this engine and not yet destroyed (freed with the engine at the latest)
+    // resampler (owner only; engine_resample.cpp): the banks every rate ring and every slot share, and sonic_resample's own lock, stream and buffers
+    std::mutex rs_mu;                               // guards everything below; never taken together with `mu` by sonic_resample
+    std::map<std::pair<int, int>, RsBank> rs_banks; // (of, nf) -> bank; bytes counted in ring_bytes
+    hipStream_t rs_st = nullptr; void* rs_in = nullptr; float* rs_out = nullptr; size_t rs_in_cap = 0, rs_out_cap = 0;
 
     // timing
     hipEvent_t ev[5]{};
@@ -261,5 +269,9 @@ void decode_step_f32(sonic_engine* e, int R, bool dump);
 // ------------------------------------------------------------------------------------------ ingest (engine_ingest.cpp), service (engine_service.cpp)
 int stage_pcm_locked(sonic_engine* e, const int16_t* pcm, const int64_t* offsets, int W);
 void ring_free(sonic_ring* r);
+// resampler (engine_resample.cpp): the bank of in_rate -> out_rate from the owner's cache (built and uploaded on first use); refusals
+// (rate <= 0, more than RS_BANK_MAX_COEF coefficients) come back as SONIC_ERR_INVALID with `err` naming the numbers
+int resample_bank_get(sonic_engine* root, int64_t in_rate, int64_t out_rate, RsBank* out, std::string& err);
+void resample_release(sonic_engine* e);
 void async_shutdown(sonic_engine* e);
 int fetch_locked(sonic_engine* e, int32_t* out_ids, int out_ld, int32_t* out_len, float* step_logits);

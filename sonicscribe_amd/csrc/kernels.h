@@ -149,6 +149,21 @@ struct RingStageArgs {
     short* pcm; long win_cap;          // engine PCM staging [W][win_cap]
 };
 void launch_ring_stage(const RingStageArgs& a, int W, int max_n, hipStream_t s);
+// polyphase windowed-sinc resampler (resample.hip): outputs j0 .. j0 + n_out of the stream whose samples src_base .. src_base + src_n lie in
+// `src` (zeros elsewhere), as fp32 and / or rounded into an int16 ring
+#define RS_LDS_FLOATS 8192
+struct ResampleArgs {
+    const void* src; long src_base, src_n;   // int16 or fp32 samples: stream index of src[0], count
+    const float* bank;                       // [K][nf], k-major
+    int of, nf, width, K;
+    long j0, n_out;
+    float* out_f32;                          // [n_out] or null
+    short* ring; long ring_cap, ring_pos;    // or null; ring_pos: buffer position of output j0 (< ring_cap), n_out <= ring_cap
+    int tile, kc;                            // resample_plan: outputs per block (<= 256), taps per LDS pass
+};
+void resample_plan(int of, int nf, int K, int* tile, int* kc);
+void launch_resample(const ResampleArgs& a, bool src_f32, hipStream_t s);
+void launch_resample_carry(short* buf, long dst, long src, long n, hipStream_t s);   // buf[dst ..) = buf[src .. src + n), dst < src, overlap allowed
 void launch_f32_to_bf16(const float* in, bf16_t* out, long n, hipStream_t s, int dt = DT_BF16);      // fp32 -> element type
 void launch_bf16_to_f32(const bf16_t* in, float* out, long n, hipStream_t s, int dt = DT_BF16);      // element type -> fp32
 void launch_bf16_to_f16(const bf16_t* in, bf16_t* out, long n, hipStream_t s);                       // bf16 storage -> fp16 storage (RNE), in place allowed

@@ -28,6 +28,7 @@ EXPORTS = [
     "sonic_test_attention", "sonic_test_decode_attention", "sonic_test_layernorm", "sonic_bench_gemm", "sonic_bench_skinny", "sonic_set_option", "sonic_debug_read", "sonic_debug_ktrace", "sonic_test_skinny_gu",
     "sonic_set_forced_ids", "sonic_test_greedy", "sonic_test_linear_int8", "sonic_test_decode_attention_cache", "sonic_test_prefill_attention",
     "sonic_ring_create", "sonic_ring_destroy", "sonic_ring_append", "sonic_ring_head", "sonic_transcribe_mixed", "sonic_stage_mixed",
+    "sonic_ring_create_rate", "sonic_ring_flush", "sonic_ring_read", "sonic_resample",
     "sonic_prefill", "sonic_decode_step", "sonic_device_info", "sonic_memory_info",
     "sonic_abi_version", "sonic_slot_create", "sonic_slot_count", "sonic_run_staged_async", "sonic_wait",
     "sonic_service_begin", "sonic_service_end", "sonic_splice_rows", "sonic_service_step", "sonic_fetch_row", "sonic_fetch_rows", "sonic_prefill_enqueue",
@@ -36,7 +37,7 @@ EXPORTS = [
     "sonic_pipeline_create", "sonic_pipeline_submit", "sonic_pipeline_submit_mixed", "sonic_pipeline_wait", "sonic_pipeline_stats", "sonic_pipeline_last_error", "sonic_pipeline_destroy",
     "sonic_vad_create", "sonic_vad_destroy", "sonic_vad_last_error", "sonic_vad_load_tensor", "sonic_vad_probs", "sonic_vad_probs_rings",
 ]
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class SonicDims(C.Structure):
@@ -111,6 +112,10 @@ def load_library():
     lib.sonic_ring_append.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int64)]
     lib.sonic_ring_head.argtypes = [vp]
     lib.sonic_ring_head.restype = C.c_int64
+    lib.sonic_ring_create_rate.argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(vp)]
+    lib.sonic_ring_flush.argtypes = [vp]
+    lib.sonic_ring_read.argtypes = [vp, C.c_int64, C.c_int64, vp]
+    lib.sonic_resample.argtypes = [vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int64, i64p]
     lib.sonic_transcribe_mixed.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp]
     lib.sonic_stage_mixed.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int]
     lib.sonic_run_staged.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int]
@@ -201,25 +206,51 @@ class RingSlice:
 
 
 class Ring:
-    """Raw wire PCM (int16) of one streaming session in HBM (sonic_ring_*)."""
+    """PCM (int16, 16 kHz) of one streaming session or one file in HBM (sonic_ring_*).  With `rate` other than 16000 the appends take
+    samples at that rate and the device resampler (csrc/resample.hip) writes the ring: content, indices, `head` and every reader stay in
+    16 kHz samples (sonic_ring_create_rate)."""
 
-    def __init__(self, engine: "Engine", capacity_samples: int):
-        self.engine, self.capacity = engine, int(capacity_samples)
+    def __init__(self, engine: "Engine", capacity_samples: int, rate: int = 16000):
+        self.engine, self.capacity, self.rate = engine, int(capacity_samples), int(rate)
         h = C.c_void_p()
-        engine._check(engine.lib.sonic_ring_create(engine.h, self.capacity, C.byref(h)))
+        if self.rate == 16000:
+            engine._check(engine.lib.sonic_ring_create(engine.h, self.capacity, C.byref(h)))
+        else:
+            from . import frontend
+            frontend.resample_geometry(self.rate, 16000)          # ValueError for a rate the library refuses
+            engine._check(engine.lib.sonic_ring_create_rate(engine.h, self.capacity, self.rate, C.byref(h)))
         self.h = h
         if not hasattr(engine, "_rings"):
             engine._rings = []
         engine._rings.append(self)
 
+    def _fail(self, what: str, rc: int):
+        raise RuntimeError(f"{what} failed with status {rc}: " + (self.engine.lib.sonic_last_error(None) or b"").decode())
+
     def append(self, pcm) -> int:
-        """pcm: bytes (little-endian int16, as on the wire) or an int16 array.  Returns the absolute index of its first sample."""
+        """pcm: bytes (little-endian int16, as on the wire) or an int16 array, at the ring's rate.  Returns the ring's head before the
+        call: the absolute index of the first sample this chunk put into the ring (a rate ring: `head` afterwards tells how many)."""
         a = np.frombuffer(pcm, dtype=np.int16) if isinstance(pcm, (bytes, bytearray, memoryview)) else np.ascontiguousarray(pcm, dtype=np.int16)
         first = C.c_int64(0)
         rc = self.engine.lib.sonic_ring_append(self.h, _p(a) if a.size else None, a.size, C.byref(first))
         if rc != 0:
-            raise RuntimeError(f"sonic_ring_append failed with status {rc}: " + (self.engine.lib.sonic_last_error(None) or b"").decode())
+            self._fail("sonic_ring_append", rc)
         return int(first.value)
+
+    def flush(self) -> None:
+        """End the stream of a rate ring: the remaining outputs, up to ceil(n * 16000 / rate) in all, with zeros beyond the last sample;
+        the next append starts a new stream.  Nothing to do on a 16 kHz ring."""
+        rc = self.engine.lib.sonic_ring_flush(self.h)
+        if rc != 0:
+            self._fail("sonic_ring_flush", rc)
+
+    def read(self, first: int, n: int) -> np.ndarray:
+        """int16 ring samples [first, first + n), behind every append so far (sonic_ring_read; the reference's debug WAV dump)."""
+        out = np.empty(int(n), np.int16)
+        rc = self.engine.lib.sonic_ring_read(self.h, int(first), int(n), _p(out) if out.size else None)
+        if rc != 0:
+            self._fail("sonic_ring_read", rc)
+        return out
 
     @property
     def head(self) -> int:
@@ -305,9 +336,31 @@ class Engine:
             if self.owner is not None and self in self.owner._slots:
                 self.owner._slots.remove(self)
 
-    def ring_create(self, capacity_samples: int) -> "Ring":
-        """Device-resident PCM ring of one streaming session (include/sonic_hip.h sonic_ring_*)."""
-        return Ring(self, capacity_samples)
+    def ring_create(self, capacity_samples: int, rate: int = 16000) -> "Ring":
+        """Device-resident PCM ring of one streaming session (include/sonic_hip.h sonic_ring_*).  capacity_samples counts
+        16 kHz samples; `rate` is the rate of the samples the appends bring (resampled on the device when it is not 16000)."""
+        return Ring(self, capacity_samples, rate)
+
+    def resample(self, x, in_rate: int, out_rate: int = 16000) -> np.ndarray:
+        """torchaudio.transforms.Resample(in_rate, out_rate)(x) on the device (sonic_resample; asr.py:255-261): x is int16 PCM (taken as
+        s / 32768) or float samples, mono; returns fp32 [ceil(n * out_rate / in_rate)].  Does not wait for a decoding batch."""
+        from . import frontend
+        a = x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+        if a.ndim == 2 and a.shape[0] == 1:
+            a = a[0]
+        if a.ndim != 1:
+            raise ValueError(f"resample takes mono audio ([N] or [1, N]), got shape {tuple(a.shape)}")
+        frontend.resample_geometry(in_rate, out_rate)
+        a = np.ascontiguousarray(a) if a.dtype == np.int16 else np.ascontiguousarray(a, dtype=np.float32)
+        i16, f32 = (_p(a), None) if a.dtype == np.int16 else (None, _p(a))
+        n_out = C.c_int64(0)
+        rc = self.lib.sonic_resample(self.h, i16, f32, a.size, int(in_rate), int(out_rate), None, 0, C.byref(n_out))
+        out = np.empty(int(n_out.value), np.float32)
+        if rc == 0 and out.size:
+            rc = self.lib.sonic_resample(self.h, i16, f32, a.size, int(in_rate), int(out_rate), _p(out), out.size, C.byref(n_out))
+        if rc != 0:
+            raise SonicError((self.lib.sonic_last_error(None) or b"").decode())
+        return out
 
     def __del__(self):
         try:

@@ -11,7 +11,9 @@ identical with `transcribe()` of the same samples.
   transcribe_file      the generator of main.py:385-483's records (dicts; the endpoint serialises them as NDJSON lines)
   transcribe_files     several files, their VAD passes in one device call
 
-Decoding / resampling a container format (ffmpeg / pydub in the reference) stays with the host application: input is 16 kHz mono PCM.
+Decoding a container format (ffmpeg / pydub in the reference) stays with the host application: input is mono 16-bit PCM.  At another
+rate than 16 kHz (`sampling_rate=`) the file's ring is a rate ring: the one append resamples on the device (csrc/resample.hip, the
+reference's set_frame_rate(16000), utils.py:18), the flush ends the stream, and everything from there on is the 16 kHz path unchanged.
 """
 from __future__ import annotations
 
@@ -88,8 +90,8 @@ def segments_summary(segments: Sequence[Dict[str, Any]]) -> List[Dict[str, Any]]
 
 
 def as_pcm16(audio) -> np.ndarray:
-    """16 kHz mono int16 PCM of `audio`: an int16 array ([N] or [1, N]) as it is, or the reference's float tensor of int16 / 32768 values
-    (audiosegment_to_tensor of a 16-bit file).  Any other float content is refused: decoding and resampling files is not done here."""
+    """Mono int16 PCM of `audio`: an int16 array ([N] or [1, N]) as it is, or the reference's float tensor of int16 / 32768 values
+    (audiosegment_to_tensor of a 16-bit file).  Any other float content is refused: decoding files is not done here."""
     a = audio.detach().cpu().numpy() if hasattr(audio, "detach") else np.asarray(audio)
     if a.ndim == 2 and a.shape[0] == 1:
         a = a[0]
@@ -102,8 +104,8 @@ def as_pcm16(audio) -> np.ndarray:
     scaled = a.astype(np.float64) * 32768.0
     pcm = np.rint(scaled)
     if a.size and (not np.isfinite(scaled).all() or (pcm != scaled).any() or pcm.min() < -32768 or pcm.max() > 32767):
-        raise ValueError("file mode: the float audio is not int16 / 32768 (16-bit PCM at 16 kHz mono) - decode / resample the file to "
-                         "16-bit PCM first (ffmpeg in the reference); nothing is rounded or rescaled here")
+        raise ValueError("file mode: the float audio is not int16 / 32768 (16-bit mono PCM) - decode the file to 16-bit PCM first (ffmpeg "
+                         "in the reference) and pass its rate as sampling_rate=; nothing is rounded or rescaled here")
     return pcm.astype(np.int16)
 
 
@@ -111,7 +113,8 @@ def as_pcm16(audio) -> np.ndarray:
 class _FileJob:
     """One file on the device: its ring, its plan and its queued decodes."""
 
-    def __init__(self, model, audio, vad, vad_enabled: bool, hotwords, max_segment_duration, max_new_tokens: int, filename: str):
+    def __init__(self, model, audio, vad, vad_enabled: bool, hotwords, max_segment_duration, max_new_tokens: int, filename: str,
+                 sampling_rate: int = SAMPLE_RATE):
         if not hasattr(model, "model"):
             raise RuntimeError("ASR model has been released")
         self.model, self.filename = model, filename
@@ -122,8 +125,13 @@ class _FileJob:
         pcm = as_pcm16(audio)
         if pcm.size == 0:
             raise ValueError("file mode: empty audio")
-        self.total = int(pcm.size)
         self.sr = model.target_sr
+        self.in_rate = int(sampling_rate)
+        # a file at another rate: its 16 kHz length is the resampler's trim, ceil(nf * N / of); every record counts the 16 kHz content
+        self.total = int(pcm.size)
+        if self.in_rate != self.sr:
+            of, nf, _, _ = frontend.resample_geometry(self.in_rate, self.sr)
+            self.total = -(-nf * int(pcm.size) // of)
         self.duration = self.total / self.sr
         self.replica = model._dispatcher.home(f"file:{next(_file_ids)}:{filename}")
         if self.wants_vad:
@@ -133,9 +141,14 @@ class _FileJob:
                 raise ValueError(f"file mode: the VADProcessor is on device {dev}, the model on {model.device_indices}: build the VADProcessor "
                                  "with device_id= one of the model's GPUs")
             self.replica = model.device_indices.index(dev)
-        self.ring = model.models[self.replica].ring_create(max(1024, self.total))     # the file's only copy on the device
+        eng = model.models[self.replica]
+        self.ring = eng.ring_create(max(1024, self.total)) if self.in_rate == self.sr else eng.ring_create(max(1024, self.total), rate=self.in_rate)
         try:
-            self.first = self.ring.append(pcm)
+            self.first = self.ring.append(pcm)      # the file's only copy on the device
+            if self.in_rate != self.sr:
+                self.ring.flush()
+                if self.ring.head - self.first != self.total:
+                    raise RuntimeError(f"file mode: the rate ring holds {self.ring.head - self.first} samples, expected {self.total}")
         except BaseException:
             self.release()
             raise
@@ -250,9 +263,10 @@ def _detect(vad, jobs: Sequence[_FileJob]) -> List[Any]:
 
 
 def transcribe_file(model, audio, vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
-                    max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filename: str = "") -> Iterator[Dict[str, Any]]:
+                    max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filename: str = "",
+                    sampling_rate: int = SAMPLE_RATE) -> Iterator[Dict[str, Any]]:
     """Generator of the reference's file-mode records for one file (see ASRModel.transcribe_file)."""
-    job = _FileJob(model, audio, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filename)
+    job = _FileJob(model, audio, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filename, sampling_rate)
     try:
         ts = vad.detect_voice_activity_ring(job.ring, job.first, job.total)[0] if job.wants_vad else None
         job.plan(ts)
@@ -265,14 +279,14 @@ def transcribe_file(model, audio, vad, vad_enabled: bool = True, hotwords: Optio
 
 def transcribe_files(model, audios: Sequence[Any], vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                      max_segment_duration: Optional[float] = None, max_new_tokens: int = 256,
-                     filenames: Optional[Sequence[str]] = None) -> List[FileRecords]:
+                     filenames: Optional[Sequence[str]] = None, sampling_rate: int = SAMPLE_RATE) -> List[FileRecords]:
     """One record iterator per file; the VAD of all files runs in one device call and every file's segments are queued before the call
     returns.  Each iterator must be exhausted or closed (its ring lives until then)."""
     names = list(filenames) if filenames is not None else [""] * len(audios)
     jobs: List[_FileJob] = []
     try:
         for a, name in zip(audios, names):
-            jobs.append(_FileJob(model, a, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, name))
+            jobs.append(_FileJob(model, a, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, name, sampling_rate))
         for job, ts in zip(jobs, _detect(vad, jobs)):
             job.plan(ts)
         for job in jobs:

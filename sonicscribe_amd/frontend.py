@@ -96,14 +96,11 @@ def max_new_tokens_committed(segment_duration: float) -> int:
     return min(50 + int(segment_duration * 5), 200)
 
 
-def resample_sinc_hann(wav: np.ndarray, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> np.ndarray:
-    """asr.py:255-261: ``torchaudio.transforms.Resample(orig, new)`` with its defaults (sinc_interp_hann, width 6,
-    rolloff 0.99), restated in numpy.  Never taken on the reference's own call sites (both pass 16 kHz); torchaudio is
-    absent offline, so this branch is unpinned (DESIGN.md)."""
+def resample_bank(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> Tuple[np.ndarray, int, int, int]:
+    """(bank fp32 [nf][K], of, nf, width) of ``torchaudio.transforms.Resample(orig, new)`` with its defaults (sinc_interp_hann, width 6,
+    rolloff 0.99): of = orig / gcd, nf = new / gcd, K = 2 * width + of, and output ``i * nf + p`` is ``bank[p] . x[i * of - width : i * of - width + K]``
+    with zeros outside the signal.  The device resampler (csrc/resample.hip, engine.Engine.resample, rate rings) builds the same bank."""
     import math
-    wav = np.asarray(wav, dtype=np.float32)
-    if orig_freq == new_freq or wav.size == 0:
-        return wav
     g = math.gcd(int(orig_freq), int(new_freq))
     of, nf = int(orig_freq) // g, int(new_freq) // g
     base = min(of, nf) * rolloff
@@ -116,6 +113,18 @@ def resample_sinc_hann(wav: np.ndarray, orig_freq: int, new_freq: int, lowpass_f
     with np.errstate(divide="ignore", invalid="ignore"):
         kern = np.where(t == 0, 1.0, np.sin(t) / t)
     kern = (kern * window * (base / of)).astype(np.float32)          # [nf][2*width + of]
+    return kern, of, nf, width
+
+
+def resample_sinc_hann(wav: np.ndarray, orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> np.ndarray:
+    """asr.py:255-261: ``torchaudio.transforms.Resample(orig, new)`` with its defaults (sinc_interp_hann, width 6,
+    rolloff 0.99), restated in numpy.  Never taken on the reference's own call sites (both pass 16 kHz); torchaudio is
+    absent offline, so this branch is unpinned (DESIGN.md)."""
+    import math
+    wav = np.asarray(wav, dtype=np.float32)
+    if orig_freq == new_freq or wav.size == 0:
+        return wav
+    kern, of, nf, width = resample_bank(orig_freq, new_freq, lowpass_filter_width, rolloff)
     length = wav.shape[-1]
     x = np.pad(wav, (width, width + of))
     n_out = (x.size - kern.shape[1]) // of + 1
@@ -123,3 +132,28 @@ def resample_sinc_hann(wav: np.ndarray, orig_freq: int, new_freq: int, lowpass_f
     out = (frames @ kern.T).reshape(-1)
     target = int(math.ceil(nf * length / of))
     return out[:target].astype(np.float32)
+
+
+def resample_emitted(n_in: int, of: int, nf: int, width: int) -> int:
+    """J(N): the 16 kHz samples a rate ring holds after N input samples of a stream - the frames whose taps all exist."""
+    return nf * ((n_in - width - of) // of + 1) if n_in >= width + of else 0
+
+
+RESAMPLE_BANK_MAX = 1 << 22          # coefficients (nf * K) of the largest bank the device resampler builds
+
+
+def resample_geometry(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99) -> Tuple[int, int, int, int]:
+    """(of, nf, width, K) of resample_bank without building it; ValueError for what the library refuses too: a rate <= 0, or a bank
+    above RESAMPLE_BANK_MAX coefficients (16001 -> 16000 Hz would need a gigabyte)."""
+    import math
+    orig_freq, new_freq = int(orig_freq), int(new_freq)
+    if orig_freq <= 0 or new_freq <= 0:
+        raise ValueError(f"resampler: sampling rates must be positive (got {orig_freq} -> {new_freq} Hz)")
+    g = math.gcd(orig_freq, new_freq)
+    of, nf = orig_freq // g, new_freq // g
+    width = math.ceil(lowpass_filter_width * of / (min(of, nf) * rolloff))
+    K = 2 * width + of
+    if nf * K > RESAMPLE_BANK_MAX:
+        raise ValueError(f"resampler: {orig_freq} -> {new_freq} Hz needs a bank of {nf} phases x {K} taps = {nf * K} coefficients "
+                         f"(limit {RESAMPLE_BANK_MAX})")
+    return of, nf, width, K
