@@ -42,6 +42,11 @@
  *                              audio.set_frame_rate(16000) at backend/utils.py:18
  *   sonic_ring_flush           the end of such a stream (the trailing samples of Resample's output)      backend/asr.py:255-261
  *   sonic_ring_read            the per-session debug WAV dump                                            backend/debug.py:14-72
+ *   sonic_fetch_logprobs / sonic_fetch_rows_lp / sonic_dispatch_next_lp / sonic_pipeline_submit_lp
+ *                              the "confidence" field of the wire messages, which the reference can only fill with the constants
+ *                              "tentative" and "high": every emitted token's log-probability, on every scheduler
+ *                                                                                                        backend/connection_manager.py:159,274
+ *   sonic_test_greedy_lp       (test hook of the kernel behind them)                                     backend/connection_manager.py:159,274
  */
 #ifndef SONIC_HIP_H
 #define SONIC_HIP_H
@@ -53,7 +58,7 @@ extern "C" {
 /* The library is built with -fvisibility=hidden: these declarations are its whole dynamic symbol table (tests/test_host_logic.py checks
  * `nm -D` against this header).  SONIC_ABI_VERSION moves whenever a signature or a struct layout below changes. */
 #define SONIC_API __attribute__((visibility("default")))
-#define SONIC_ABI_VERSION 11
+#define SONIC_ABI_VERSION 12
 SONIC_API int sonic_abi_version(void);
 
 typedef struct sonic_engine sonic_engine;
@@ -201,6 +206,15 @@ SONIC_API int sonic_stage_pcm(sonic_engine* e, const int16_t* pcm, const int64_t
 SONIC_API int sonic_run_staged(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off,
                      const int32_t* max_new, int want_step_logits);
 SONIC_API int sonic_fetch_tokens(sonic_engine* e, int32_t* out_ids, int out_ld, int32_t* out_len, float* step_logits);
+/* Per-token log-probabilities (option "token_logprobs", off by default; set it on the owner before its slots are created, they copy it).  For
+ * token n of request r, with l the vocabulary-long vector of logits that step's argmax compared (the values step_logits returns):
+ *   logprob[r][n] = l[tok] - max(l) - log(sum_i exp(l_i - max(l))),   tok = the token written to out_ids (the argmax, or the forced id)
+ * = HF compute_transition_scores(sequences, scores, normalize_logits=True) of a greedy generate().  The greedy kernel sums while it searches the
+ * maximum: no second pass, the decode loops keep their hipGraph form, and a request's values are the same bits on every scheduler.
+ * sonic_fetch_logprobs: the rows and counts of sonic_fetch_tokens (row r's out_len[r] values at out_lp + r * out_ld; nothing beyond them is
+ * written), valid whenever that call is.  Every fetch / submit form (sonic_fetch_logprobs, sonic_fetch_rows_lp, sonic_dispatch_next_lp,
+ * sonic_pipeline_submit_lp) returns SONIC_ERR_INVALID, the message naming token_logprobs, while the option is off. */
+SONIC_API int sonic_fetch_logprobs(sonic_engine* e, float* out_lp, int out_ld);
 /* sonic_run_staged without blocking the caller: the arguments are copied, a worker thread owned by the handle runs the batch, the call
  * returns at once (the reference's counterpart is loop.run_in_executor(None, asr_model.transcribe, ...), backend/main.py:616-624).  One
  * outstanding run per handle; until sonic_wait has returned the handle takes no other call (ring appends excepted).
@@ -239,6 +253,9 @@ SONIC_API int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const i
 SONIC_API int sonic_service_step(sonic_engine* d, int n_chunks, int rows, int32_t* finished_out, int32_t* n_new_out, int64_t* seq_out, int32_t* n_active_out);
 SONIC_API int sonic_fetch_row(sonic_engine* d, int row, int n, int32_t* out_ids);
 SONIC_API int sonic_fetch_rows(sonic_engine* d, int n, const int32_t* rows, const int32_t* counts, int32_t* out_ids, int out_ld);
+/* sonic_fetch_rows with both arrays in one call (the fetch releases the rows): row i's log-probabilities at out_lp + i * out_ld, as its ids.
+ * sonic_splice_rows refuses a source without option token_logprobs when the destination has it (the first token's value comes from the prefill). */
+SONIC_API int sonic_fetch_rows_lp(sonic_engine* d, int n, const int32_t* rows, const int32_t* counts, int32_t* out_ids, int out_ld, float* out_lp);
 
 /* Request-level scheduling for live traffic as native threads (csrc/dispatch.cpp): what the reference does with one `await
  * transcribe()` per partial / final of every WebSocket session (backend/connection_manager.py:127-245, backend/transcription_manager.py:19-65) and
@@ -256,6 +273,10 @@ SONIC_API int sonic_dispatch_cancel(sonic_dispatch* d, int64_t ticket);         
 /* next completed request in completion order; blocks up to timeout_ms (< 0: until one completes or the dispatcher is closed and drained); *ticket_out = 0: none */
 SONIC_API int sonic_dispatch_next(sonic_dispatch* d, int timeout_ms, int64_t* ticket_out, int32_t* status_out, int32_t* out_ids, int out_cap, int32_t* n_out,
                                   char* err, int err_cap);
+/* sonic_dispatch_next plus the log-probabilities of the completed request (out_lp[i] belongs to out_ids[i]; at most out_cap are copied).  Every handle of
+ * the dispatcher needs option token_logprobs: SONIC_ERR_INVALID otherwise, err naming the option. */
+SONIC_API int sonic_dispatch_next_lp(sonic_dispatch* d, int timeout_ms, int64_t* ticket_out, int32_t* status_out, int32_t* out_ids, int out_cap, int32_t* n_out,
+                                     char* err, int err_cap, float* out_lp);
 SONIC_API int sonic_dispatch_stats(sonic_dispatch* d, int64_t* prefill_batches, int64_t* decode_chunks, int32_t* load_windows, int32_t* free_rows);
 SONIC_API int sonic_dispatch_close(sonic_dispatch* d);     /* queued requests fail, running ones complete (still collectable); handles leave continuous mode */
 SONIC_API int sonic_dispatch_destroy(sonic_dispatch* d);
@@ -305,6 +326,13 @@ SONIC_API int sonic_pipeline_submit_mixed(sonic_pipeline* p, const int16_t* host
                                           const int64_t* ring_start, const int32_t* ring_n, int W, const int32_t* req_win, int R,
                                           const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new,
                                           int32_t* out_ids, int out_ld, int32_t* out_len, int64_t* ticket_out);
+/* sonic_pipeline_submit_mixed (rings may be NULL: host windows only) plus out_lp [R][out_ld]: token i of request r gets its log-probability at
+ * out_lp[r * out_ld + i] (the same out_ld as out_ids); it stays valid until the ticket has been waited for.  Needs option token_logprobs on every
+ * handle of the pipeline: SONIC_ERR_INVALID otherwise, sonic_pipeline_last_error naming the option. */
+SONIC_API int sonic_pipeline_submit_lp(sonic_pipeline* p, const int16_t* host_pcm, const int64_t* host_off, sonic_ring* const* rings,
+                                       const int64_t* ring_start, const int32_t* ring_n, int W, const int32_t* req_win, int R,
+                                       const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new,
+                                       int32_t* out_ids, int out_ld, int32_t* out_len, float* out_lp, int64_t* ticket_out);
 /* sonic_transcribe_batch with every window either host samples (rings == NULL or rings[w] == NULL: int16 PCM already peak-normalised,
  * host_off[W+1]; ring windows have empty host ranges) or samples [ring_start[w], ring_start[w] + ring_n[w]) of rings[w], which must
  * still be inside the ring's last `capacity` samples.  The windows of one request (req_win) share one peak.  Without req_win R == W. */
@@ -336,6 +364,10 @@ SONIC_API int sonic_test_skinny_gu(sonic_engine* e, const float* X, const float*
 SONIC_API int sonic_test_linear_int8(sonic_engine* e, const float* X, const float* W, const float* bias, const float* resid, float* out,
                            int M, int N, int K, int group_rows, int epi);
 SONIC_API int sonic_test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, int32_t* tok_out, float* logits_out);
+/* sonic_test_greedy through the log-probability instantiation of the kernel (greedy_kernel<T, true>): tok_out / logits_out as above, lp_out[B] = the
+ * log-probability of the token each row emits; force_ids (optional, [B]): that token instead of the argmax, as under sonic_set_forced_ids */
+SONIC_API int sonic_test_greedy_lp(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const int32_t* force_ids, int32_t* tok_out,
+                                   float* logits_out, float* lp_out);
 SONIC_API int sonic_test_attention(sonic_engine* e, const float* q, const float* k, const float* v, float* out,
                          int B, int Tq, int Tk, int Hq, int Hkv, int hd, int causal);
 SONIC_API int sonic_test_decode_attention(sonic_engine* e, const float* q, const float* k, const float* v, float* out,
@@ -370,7 +402,7 @@ SONIC_API int sonic_debug_ktrace(sonic_engine* e, int64_t* out, int64_t n);
  * "no_fused_rope" (encoder RoPE as its own pass), "no_gelu_lut" (fc1 GELU by arithmetic instead of the LDS table); the full list with what each one measured is in
  * DESIGN.md 1.  Round 6: "no_pre_norm" (<= 2 rows: standalone add + RMSNorm launches instead of the five-launch chain; same bits), "decode_gemv" / "decode_prefetch" /
  * "decode_attn_occ2" (experiments that lost: profiles/round6_*), "f32_synth_bf16" (SONIC_MODE_F32: sonic_load_synthetic writes the bf16-rounded values),
- * "inject_dev_err" (tests: sets / clears the device error word) */
+ * "inject_dev_err" (tests: sets / clears the device error word); "token_logprobs" (not an experiment: per-token log-probabilities, see sonic_fetch_logprobs) */
 SONIC_API int sonic_set_option(sonic_engine* e, const char* key, int value);
 
 /* ---- Silero VAD network (silero-vad 5.x / 6.x, 16 kHz branch; csrc/vad.hip, layer table in sonicscribe_amd/vad_net.py) ----

@@ -18,6 +18,7 @@ sessions' decodes in flight (INTEGRATION.md shows the change in transcription_ma
 from __future__ import annotations
 
 import asyncio
+import math
 import time
 from concurrent.futures import Future
 from pathlib import Path
@@ -79,16 +80,37 @@ class HFPrompt:
         return self.processor.batch_decode([list(map(int, ids))], skip_special_tokens=True)[0]
 
 
-def _text_future(inner: "Future", decode) -> "Future[str]":
+class Transcription:
+    """What a `detailed=True` request resolves to (ASRModel(token_logprobs=True)): the transcript, the emitted token ids (EOS included), every
+    token's log-probability under the model (float32; HF compute_transition_scores(..., normalize_logits=True) of the greedy generate()) and their
+    mean - the number a caller turns into the wire messages' "confidence" (connection_manager.py:159,274 can only send constants)."""
+    __slots__ = ("text", "token_ids", "token_logprobs", "avg_logprob")
+
+    def __init__(self, text: str, token_ids, token_logprobs):
+        self.text = text
+        self.token_ids = np.asarray(token_ids, np.int32)
+        self.token_logprobs = np.asarray(token_logprobs, np.float32)
+        # over all emitted tokens, the EOS that stopped the row included; nothing emitted: nan
+        self.avg_logprob = float(np.mean(self.token_logprobs, dtype=np.float64)) if self.token_logprobs.size else float("nan")
+
+    def __repr__(self):
+        return f"Transcription(text={self.text!r}, tokens={self.token_ids.size}, avg_logprob={self.avg_logprob:.4f})"
+
+
+def _text_future(inner: "Future", decode, detailed: bool = False) -> "Future[str]":
     """Future of the transcript behind a dispatcher future of token ids.  Cancelling it (a session that went away) cancels the queued
-    request as well, so it never reaches the device."""
+    request as well, so it never reaches the device.  detailed: the inner future carries (ids, log-probabilities), the result is a Transcription."""
     out: "Future[str]" = Future()
 
     def done(f):
         if out.done():
             return
         try:
-            out.set_result(decode(f.result()).strip())
+            if detailed:
+                ids, lps = f.result()
+                out.set_result(Transcription(decode(ids).strip(), ids, lps))
+            else:
+                out.set_result(decode(f.result()).strip())
         except BaseException as ex:
             if not out.done():
                 out.set_exception(ex)
@@ -163,19 +185,22 @@ class AudioStream:
         c = self._chunks.get(int(chunk_id))
         return None if c is None else (c[0], c[1])
 
-    def submit_samples(self, first: int, n: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None) -> "Future[str]":
-        """Transcribe ring samples [first, first + n) (the >30 s split of connection_manager.py:206-214 cuts at byte offsets, not chunks)."""
+    def submit_samples(self, first: int, n: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None, detailed: bool = False) -> "Future[str]":
+        """Transcribe ring samples [first, first + n) (the >30 s split of connection_manager.py:206-214 cuts at byte offsets, not chunks).
+        detailed (a model built with token_logprobs=True): the future gives a Transcription instead of the text."""
         m = self.model
+        m._check_detailed(detailed)
         windows = [self.ring.slice(first + s, e - s) for s, e in frontend.split_windows(n, m.dims)]
         n_audio, _ = frontend.request_audio_tokens(n, m.dims)
         prompt = m.prompt.build(frontend.build_instruction(hotwords), n_audio)
-        inner = m._dispatcher.submit(windows, prompt, int(max_new_tokens), replica=self.replica)
-        return _text_future(inner, m.prompt.decode)
+        inner = m._dispatcher.submit(windows, prompt, int(max_new_tokens), replica=self.replica, want_logprobs=detailed)
+        return _text_future(inner, m.prompt.decode, detailed)
 
-    def submit_chunks(self, start_chunk_id: int, end_chunk_id: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None) -> "Future[str]":
+    def submit_chunks(self, start_chunk_id: int, end_chunk_id: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None,
+                      detailed: bool = False) -> "Future[str]":
         """Transcribe chunks start..end inclusive (audio_manager.py:76-79 get_chunks_by_range + :115-123 concatenation)."""
         first, n = self.chunk_range_samples(start_chunk_id, end_chunk_id)
-        return self.submit_samples(first, n, max_new_tokens, hotwords)
+        return self.submit_samples(first, n, max_new_tokens, hotwords, detailed)
 
     async def transcribe_chunks(self, start_chunk_id: int, end_chunk_id: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None) -> str:
         return await asyncio.wrap_future(self.submit_chunks(start_chunk_id, end_chunk_id, max_new_tokens, hotwords))
@@ -189,7 +214,7 @@ class AudioStream:
 class ASRModel:
     def __init__(self, checkpoint_dir: str, device: str = "cuda", mode: str = "native",
                  cpu_threads: Optional[int] = None, cpu_interop_threads: Optional[int] = None,
-                 *, max_batch: int = 32, max_ctx: int = 1024, slots: int = DEFAULT_SLOTS, continuous: bool = DEFAULT_CONTINUOUS, decoders: int = 1, bulk: bool = False, native_dispatch: Optional[bool] = None, _dims: Optional[ModelDims] = None,
+                 *, max_batch: int = 32, max_ctx: int = 1024, slots: int = DEFAULT_SLOTS, continuous: bool = DEFAULT_CONTINUOUS, decoders: int = 1, bulk: bool = False, native_dispatch: Optional[bool] = None, token_logprobs: bool = False, _dims: Optional[ModelDims] = None,
                  _synthetic_seed: Optional[int] = None, _allow_synthetic_prompt: bool = False, _options: Optional[Dict[str, int]] = None):
         if mode not in ["native", "int8"]:
             raise ValueError("mode must be either 'native' or 'int8'")            # asr.py:46-47
@@ -238,9 +263,14 @@ class ASRModel:
                 if not _allow_synthetic_prompt:
                     raise RuntimeError(f"could not load the processor / tokenizer from {self.checkpoint_dir}: {ex}") from ex
                 self.prompt = SyntheticPrompt(self.dims)
+        # token_logprobs: every greedy step also returns the emitted token's log-probability (engine option of the same name; off by default:
+        # nothing changes).  Set on every replica before its slots exist; `detailed=True` requests and transcribe(return_debug_info=True) read it
+        self.token_logprobs = bool(token_logprobs)
         for eng in self.models:                      # experiment knobs (sonic_set_option) before the slots copy them
             for k, v in (_options or {}).items():
                 eng.set_option(k, int(v))
+            if self.token_logprobs:
+                eng.set_option("token_logprobs", 1)
         self.model = self.models[0]                  # main.py:84-86 checks and deletes `.model`
         # continuous: `decoders` handles per replica run a greedy loop over max_batch rows each, the other handles prefill (>= 1).  Streaming:
         # decoders=1, slots=2.  Bulk transcription of many segments: max_batch=64, decoders=3, slots=4 (the bench's pipeline shape since round 5; decoders=2, slots=3 before).
@@ -278,16 +308,22 @@ class ASRModel:
         n_audio, _ = frontend.request_audio_tokens(len(pcm), self.dims)
         return pcm, [pcm[s:e] for s, e in wins], n_audio
 
+    def _check_detailed(self, detailed: bool):
+        if detailed and not getattr(self, "token_logprobs", False):
+            raise ValueError("detailed=True needs a model built with token_logprobs=True (ASRModel(..., token_logprobs=True))")
+
     def submit(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None,
-               session: Optional[str] = None) -> "Future[str]":
+               session: Optional[str] = None, detailed: bool = False) -> "Future[str]":
         """Non-blocking form of transcribe(): queues the request on a replica and returns a Future of the transcript.  `session`
-        (e.g. the WebSocket client id) keeps a session's decodes on one GPU."""
+        (e.g. the WebSocket client id) keeps a session's decodes on one GPU.  detailed (a model built with token_logprobs=True): the future
+        gives a Transcription - text, token_ids, token_logprobs, avg_logprob - instead of the text."""
         if not hasattr(self, "model"):
             raise RuntimeError("ASR model has been released")
+        self._check_detailed(detailed)
         pcm, windows, n_audio = self._prepare(audio_tensor, sampling_rate)
         prompt = self.prompt.build(frontend.build_instruction(hotwords), n_audio)
-        inner = self._dispatcher.submit(windows, prompt, int(max_new_tokens), session=session)
-        return _text_future(inner, self.prompt.decode)
+        inner = self._dispatcher.submit(windows, prompt, int(max_new_tokens), session=session, want_logprobs=detailed)
+        return _text_future(inner, self.prompt.decode, detailed)
 
     def open_stream(self, session: str, buffer_seconds: float = 30.0, margin_seconds: float = 10.0, sampling_rate: int = 16000) -> AudioStream:
         """A streaming session whose audio stays on the device (config.py:25 MAX_AUDIO_BUFFER_SECONDS = 30): chunks are appended to a
@@ -300,10 +336,10 @@ class ASRModel:
         return AudioStream(self, session, self._dispatcher.home(session), buffer_seconds, margin_seconds, sampling_rate=sampling_rate)
 
     async def transcribe_async(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128,
-                               hotwords: Optional[List[str]] = None, session: Optional[str] = None) -> str:
+                               hotwords: Optional[List[str]] = None, session: Optional[str] = None, detailed: bool = False) -> str:
         """Awaitable transcribe() for the asyncio callers (connection_manager.py:127-245): the event loop is not blocked while the
         device works, so all sessions' partial and final decodes can be in flight (and batched) together."""
-        return await asyncio.wrap_future(self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, session))
+        return await asyncio.wrap_future(self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, session, detailed))
 
     def transcribe(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128,
                    hotwords: Optional[List[str]] = None, return_debug_info: bool = False) -> Union[str, Dict[str, Any]]:
@@ -311,14 +347,20 @@ class ASRModel:
             raise RuntimeError("ASR model has been released")
         t0 = time.time()
         try:
-            transcript = self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords).result()
+            want = bool(return_debug_info and getattr(self, "token_logprobs", False))
+            res = self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, detailed=want).result()
+            det, transcript = (res, res.text) if want else (None, res)
             elapsed = time.time() - t0
             if return_debug_info:
                 n = audio_tensor.shape[-1] if hasattr(audio_tensor, "shape") else len(audio_tensor)
                 alloc, reserved = self.model.memory_info()           # asr.py:453-457: allocator state, not the weight size
-                return {"transcript": transcript, "processing_time": elapsed, "audio_length_sec": n / sampling_rate,
+                info = {"transcript": transcript, "processing_time": elapsed, "audio_length_sec": n / sampling_rate,
                         "mode": self.mode, "device": str(self.device),
                         "gpu_memory_allocated_mb": alloc / 1024 ** 2, "gpu_memory_reserved_mb": reserved / 1024 ** 2}
+                if det is not None:                                  # a token_logprobs model: what fills the wire messages' "confidence"
+                    info.update({"token_ids": det.token_ids, "token_logprobs": det.token_logprobs, "avg_logprob": det.avg_logprob,
+                                 "confidence": math.exp(det.avg_logprob)})
+                return info
             return transcript
         except RuntimeError as e:
             if "out of memory" in str(e).lower():

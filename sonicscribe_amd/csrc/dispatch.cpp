@@ -16,7 +16,8 @@
 //   * one thread per DECODING handle: splices handed-over rows into its lowest free rows between two chunks, queues chunks over the occupied
 //     rows (sonic_service_step), fetches every row the moment the pipelined check shows it finished (sonic_fetch_rows) and completes its ticket;
 //   * completions are collected by sonic_dispatch_next (blocking, from any thread): the host side keeps one thread that turns them into futures.
-// No thread polls: condition variables here, blocking HIP events inside the engine.  Only the C ABI of include/sonic_hip.h is used.
+// No thread polls: condition variables here, blocking HIP events inside the engine.  Only the C ABI of include/sonic_hip.h is used, plus the library's
+// own engine_token_logprobs_on (is the option on for a handle: then the rows' log-probabilities are fetched with their ids, sonic_dispatch_next_lp).
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -32,6 +33,7 @@
 #include <vector>
 
 #include "../../include/sonic_hip.h"
+extern "C" int engine_token_logprobs_on(sonic_engine* e);   // engine.cpp
 
 namespace {
 
@@ -42,6 +44,7 @@ struct Req {
     std::vector<sonic_ring*> rings; std::vector<int64_t> ring_start; std::vector<int32_t> ring_n; bool any_ring = false;
     std::vector<int32_t> prompt; int max_new = 0;
     int status = -1; std::string err; std::vector<int32_t> ids;    // result
+    std::vector<float> lp;                                         // ... and, with option token_logprobs on the handles, every token's log-probability
     bool cancelled = false;
 };
 typedef std::shared_ptr<Req> ReqP;
@@ -53,6 +56,7 @@ struct sonic_dispatch {
     std::vector<sonic_engine*> dec, pre;
     int n_rows = 0, pre_cap = 0;
     bool adaptive_tiles = true;
+    bool lp = false;                                               // every handle has option token_logprobs on
     std::mutex mu;
     std::condition_variable cv;                                    // queue, hand-overs, free rows, state
     std::condition_variable cv_done;                               // completions
@@ -228,10 +232,12 @@ void decode_thread(sonic_dispatch* d, int k) {
         std::vector<int32_t> dr, dc;
         for (int i = 0; i < n_rows; ++i) if (rows[i] && seq > valid_after[i] && fin[i]) { dr.push_back(i); dc.push_back(nn[i]); }
         int ld = 1; for (int c : dc) ld = c > ld ? c : ld;
-        std::vector<int32_t> out;
+        std::vector<int32_t> out; std::vector<float> olp;
         if (!dr.empty()) {                                         // one call for all of them: one wait, one release launch
             out.assign((size_t)dr.size() * ld, 0);
-            rc = sonic_fetch_rows(e, (int)dr.size(), dr.data(), dc.data(), out.data(), ld);
+            if (d->lp) olp.assign((size_t)dr.size() * ld, 0.f);
+            rc = d->lp ? sonic_fetch_rows_lp(e, (int)dr.size(), dr.data(), dc.data(), out.data(), ld, olp.data())
+                       : sonic_fetch_rows(e, (int)dr.size(), dr.data(), dc.data(), out.data(), ld);
             if (rc != SONIC_OK) { fail_all(rc); return; }
         }
         std::unique_lock<std::mutex> lk(d->mu);
@@ -239,6 +245,7 @@ void decode_thread(sonic_dispatch* d, int k) {
         for (size_t j = 0; j < dr.size(); ++j) {
             ReqP r = rows[dr[j]]; rows[dr[j]].reset(); --occupied;
             r->ids.assign(out.begin() + j * ld, out.begin() + j * ld + dc[j]);
+            if (d->lp) r->lp.assign(olp.begin() + j * ld, olp.begin() + j * ld + dc[j]);
             finish(d, r, SONIC_OK, "");
         }
         if (!dr.empty()) release_rows(d, k, (int)dr.size());
@@ -270,6 +277,8 @@ SONIC_API int sonic_dispatch_create(sonic_engine* const* decoders, int n_dec, so
     sonic_dispatch* d = new sonic_dispatch();
     d->dec.assign(decoders, decoders + n_dec); d->pre.assign(prefills, prefills + n_pre);
     d->n_rows = rows; d->pre_cap = cap; d->adaptive_tiles = adaptive_tiles != 0;
+    d->lp = true;
+    for (int i = 0; i < n_dec + n_pre; ++i) d->lp = d->lp && engine_token_logprobs_on(i < n_dec ? decoders[i] : prefills[i - n_dec]);
     d->free_rows.assign(n_dec, rows); d->hand.resize(n_dec);
     for (int i = 0; i < n_dec; ++i) {
         const int rc = sonic_service_begin(d->dec[i]);
@@ -320,9 +329,8 @@ SONIC_API int sonic_dispatch_cancel(sonic_dispatch* d, int64_t ticket) {
 // The next completed request, in completion order.  Blocks up to timeout_ms (< 0: until one completes, or the dispatcher has been closed and every
 // request has been collected).  *ticket_out = 0: none (timeout, or closed and drained).  Otherwise *status_out is the request's sonic_status, its *n_out tokens are in out_ids
 // (at most out_cap are copied) and err (if given) holds the engine's message for a failed request.
-SONIC_API int sonic_dispatch_next(sonic_dispatch* d, int timeout_ms, int64_t* ticket_out, int32_t* status_out, int32_t* out_ids, int out_cap, int32_t* n_out,
-                                  char* err, int err_cap) {
-    if (!d || !ticket_out) return SONIC_ERR_INVALID;
+static int dispatch_next(sonic_dispatch* d, int timeout_ms, int64_t* ticket_out, int32_t* status_out, int32_t* out_ids, int out_cap, int32_t* n_out,
+                         char* err, int err_cap, float* out_lp) {
     *ticket_out = 0;
     std::unique_lock<std::mutex> lk(d->mu);
     auto ready = [&] { return !d->done.empty() || (d->stop && d->outstanding == 0); };
@@ -335,9 +343,28 @@ SONIC_API int sonic_dispatch_next(sonic_dispatch* d, int timeout_ms, int64_t* ti
     const int n = (int)r->ids.size();
     if (n_out) *n_out = n;
     if (out_ids) memcpy(out_ids, r->ids.data(), (size_t)(n < out_cap ? n : out_cap) * 4);
+    if (out_lp && (int)r->lp.size() == n) memcpy(out_lp, r->lp.data(), (size_t)(n < out_cap ? n : out_cap) * 4);
     if (err && err_cap > 0) { strncpy(err, r->err.c_str(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
     if (d->stop && d->outstanding == 0) d->cv_done.notify_all();
     return SONIC_OK;
+}
+
+SONIC_API int sonic_dispatch_next(sonic_dispatch* d, int timeout_ms, int64_t* ticket_out, int32_t* status_out, int32_t* out_ids, int out_cap, int32_t* n_out,
+                                  char* err, int err_cap) {
+    if (!d || !ticket_out) return SONIC_ERR_INVALID;
+    return dispatch_next(d, timeout_ms, ticket_out, status_out, out_ids, out_cap, n_out, err, err_cap, nullptr);
+}
+// sonic_dispatch_next plus the completed request's log-probabilities: out_lp[i] belongs to out_ids[i] (at most out_cap are copied).  Needs option
+// token_logprobs on every handle of the dispatcher (set on the owner before its slots were created): SONIC_ERR_INVALID otherwise, err names the option.
+SONIC_API int sonic_dispatch_next_lp(sonic_dispatch* d, int timeout_ms, int64_t* ticket_out, int32_t* status_out, int32_t* out_ids, int out_cap, int32_t* n_out,
+                                     char* err, int err_cap, float* out_lp) {
+    if (!d || !ticket_out || !out_lp) return SONIC_ERR_INVALID;
+    if (!d->lp) {
+        *ticket_out = 0;
+        if (err && err_cap > 0) snprintf(err, (size_t)err_cap, "sonic_dispatch_next_lp: option token_logprobs is off on a handle of this dispatcher");
+        return SONIC_ERR_INVALID;
+    }
+    return dispatch_next(d, timeout_ms, ticket_out, status_out, out_ids, out_cap, n_out, err, err_cap, out_lp);
 }
 
 SONIC_API int sonic_dispatch_stats(sonic_dispatch* d, int64_t* prefill_batches, int64_t* decode_chunks, int32_t* load_windows, int32_t* free_rows) {

@@ -550,12 +550,20 @@ __global__ void assemble_embeds_kernel(const int* src, const bf16_t* table, cons
 }
 
 // ---------------------------------------------------------------- argmax + greedy controller (generation/utils.py:2894-2936)
-template <typename T>
+// LP (option token_logprobs): the block also returns log_softmax(l)[tok] of the token it emits.  Every thread keeps the sum lp_s of
+// exp(r - lp_m) over the values it visits, lp_m being its running maximum `best`: one rescale per trip of the unrolled loop, then the trip's (up to
+// 16) terms.  Threads are brought to their wave's maximum and added by the xor butterfly, waves to the block's maximum and added as a fixed tree by
+// thread 0: one block, one order, whatever the grid.  exp is v_exp_f32 of the argument times log2(e); the closing log and subtraction are fp64.
+// LP = false is the kernel as it was: everything below that belongs to the sum sits behind `if constexpr (LP)`.
+__device__ __forceinline__ float lp_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
+template <typename T, bool LP>
 __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
     typedef typename ET<T>::v8 V8;
     __shared__ float sv[16];
     __shared__ int si[17];
     __shared__ int s_tok;
+    __shared__ float ss_lp[LP ? 16 : 1];
+    float lp_m = -INFINITY, lp_s = 0.f;      // LP: the thread's sum is lp_s * exp(lp_m); a thread that saw nothing holds (-inf, 0)
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const float* lg = a.logits + (long)b * a.V;
     const long ks_stride = (long)a.mpad * a.V;
@@ -587,6 +595,19 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
                 const float r = rT<T>(t[j]);        // logits are T in the reference, compared as fp32
                 if (dump) dump[i + j] = r;
                 if (r > best) { best = r; bi = i + j; }   // strict > keeps the first maximum within a thread
+                if constexpr (LP) v[u][j] = r;
+            }
+        }
+        if constexpr (LP) {
+            // the trip's values against the maximum so far (`best` covers them): the old sum is rescaled once (exp2(0) = 1 and s * 1 are exact when
+            // the maximum did not move), then the terms are added in visiting order.  While nothing finite has been seen (the first trip, or trips
+            // of -inf logits only) the sum stays 0: -inf - -inf is not formed, here or in the terms (exp(-inf - finite) = 0 is fine)
+            lp_s = lp_m > -INFINITY ? lp_s * lp_exp(lp_m - best) : 0.f; lp_m = best;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (i0 + u * 4096 >= a.V) break;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) lp_s += best > -INFINITY ? lp_exp(v[u][j] - best) : 0.f;
             }
         }
     }
@@ -595,10 +616,29 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
         const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
         if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
     }
+    if constexpr (LP) {
+        // every lane now holds the wave's maximum: bring the lane's sum to it (an empty lane is the identity: 0, not 0 * exp(-inf + inf)) and add
+        // across the wave; the butterfly gives every lane the same tree, and a + b = b + a bit for bit
+        lp_s = lp_m > -INFINITY ? lp_s * lp_exp(lp_m - best) : 0.f;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) lp_s += __shfl_xor(lp_s, o, 64);
+        if (lane == 0) ss_lp[wid] = lp_s;
+    }
     if (lane == 0) { sv[wid] = best; si[wid] = bi; }
     __syncthreads();
     if (tid == 0) {
         for (int w = 1; w < 16; ++w) if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
+        float lp_sum = 0.f;
+        if constexpr (LP) {
+            float q[16];                          // the 16 waves at the block's maximum (an empty wave: 0), added as a fixed binary tree
+#pragma unroll
+            for (int w = 0; w < 16; ++w) q[w] = sv[w] > -INFINITY ? ss_lp[w] * lp_exp(sv[w] - best) : 0.f;
+#pragma unroll
+            for (int h = 8; h > 0; h >>= 1)
+#pragma unroll
+                for (int w = 0; w < h; ++w) q[w] = q[2 * w] + q[2 * w + 1];
+            lp_sum = q[0];
+        }
         int tok = bi;
         const int fin = a.finished[b];
         bool running = false;
@@ -606,6 +646,16 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
         else {
             if (a.force_ids) tok = a.force_ids[(long)b * a.force_ld + a.n_new[b]];   // teacher forcing (parity tests): feed this id instead
             a.out_ids[(long)b * a.out_ld + a.n_new[b]] = tok;
+            if constexpr (LP) {
+                float lt = best;                  // the emitted token's logit: the maximum, or under teacher forcing the forced id's value, summed
+                if (a.force_ids) {                // from the slabs in the main loop's order (v + w, then ks = 2 ...): the bits of the dumped logit
+                    float f = lg[tok];
+                    if (a.ksplit > 1) f += lg[ks_stride + tok];
+                    for (int ks = 2; ks < a.ksplit; ++ks) f += lg[ks * ks_stride + tok];
+                    lt = rT<T>(f);
+                }
+                a.out_lp[(long)b * a.out_ld + a.n_new[b]] = (float)(((double)lt - (double)best) - log((double)lp_sum));
+            }
             const int nn = a.n_new[b] + 1;
             a.n_new[b] = nn;
             bool stop = nn >= a.max_new[b];
@@ -751,8 +801,13 @@ void launch_assemble_embeds(const int* src, const bf16_t* table, const bf16_t* a
     if (n_tok > 0) hipLaunchKernelGGL(assemble_embeds_kernel, dim3(n_tok), dim3(256), 0, s, src, table, audio, x, n_tok, d);
 }
 void launch_greedy(const GreedyArgs& a, hipStream_t s) {
-    if (a.dt == DT_F32) { hipLaunchKernelGGL(greedy_kernel<float>, dim3(a.B), dim3(1024), 0, s, a); return; }   // SONIC_MODE_F32: fp32 logits, table and rows
-    DT_SWITCH(a.dt, T, hipLaunchKernelGGL(greedy_kernel<T>, dim3(a.B), dim3(1024), 0, s, a));
+    if (a.out_lp) {                                                                                              // token_logprobs: the LP instantiation
+        if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, true>), dim3(a.B), dim3(1024), 0, s, a); return; }
+        DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, true>), dim3(a.B), dim3(1024), 0, s, a));
+        return;
+    }
+    if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, false>), dim3(a.B), dim3(1024), 0, s, a); return; }   // SONIC_MODE_F32: fp32 logits, table and rows
+    DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, false>), dim3(a.B), dim3(1024), 0, s, a));
 }
 void launch_f32_to_bf16(const float* in, bf16_t* out, long n, hipStream_t s, int dt) {
     if (n > 0) DT_SWITCH(dt, T, hipLaunchKernelGGL(f32_to_t_kernel<T>, dim3((n + 255) / 256), dim3(256), 0, s, in, (T*)out, n));

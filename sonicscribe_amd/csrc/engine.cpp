@@ -346,6 +346,21 @@ static int alloc_state(sonic_engine* e) {
     return SONIC_OK;
 }
 
+// option token_logprobs: the log-probability buffer beside out_ids, allocated by the first handle state that needs it (counted by sonic_memory_info)
+int lp_alloc(sonic_engine* e) {
+    if (e->out_lp) return SONIC_OK;
+    HIPC(e, hipSetDevice(e->device));
+    TRY(dalloc(e, &e->out_lp, (size_t)64 * e->out_cap));
+    HIPC(e, stream_sync(e));
+    return SONIC_OK;
+}
+int lp_check(sonic_engine* e, const char* who) {
+    if (e->opt_token_logprobs && e->out_lp) return SONIC_OK;
+    return fail(e, SONIC_ERR_INVALID, "%s: option token_logprobs is off on this handle (sonic_set_option(e, \"token_logprobs\", 1) on the owner before its slots are created)", who);
+}
+// dispatch.cpp / pipeline.cpp (same library, not exported): does this handle produce log-probabilities
+extern "C" int engine_token_logprobs_on(sonic_engine* e) { return e && e->opt_token_logprobs && e->out_lp ? 1 : 0; }
+
 extern "C" int sonic_create(const sonic_dims* dims, int device_id, int mode, int max_batch, int max_ctx, sonic_engine** out) {
     if (!dims || !out) return fail(nullptr, SONIC_ERR_INVALID, "null argument");
     *out = nullptr;
@@ -401,6 +416,8 @@ extern "C" int sonic_slot_create(sonic_engine* parent, sonic_engine** out) {
     e->opts = root->opts; e->opt_no_graph = root->opt_no_graph; e->opt_no_fused_rope = root->opt_no_fused_rope; e->opt_no_gelu_lut = root->opt_no_gelu_lut;
     e->opt_i8_defer_thr = root->opt_i8_defer_thr; e->opt_i8_no_xq = root->opt_i8_no_xq; e->opt_i8_no_lnq = root->opt_i8_no_lnq; e->opt_i8_no_qkv_fuse = root->opt_i8_no_qkv_fuse;
     e->opt_decode_chunk = root->opt_decode_chunk; e->opt_no_pre_norm = root->opt_no_pre_norm; e->opt_decode_gemv = root->opt_decode_gemv;
+    e->opt_token_logprobs = root->opt_token_logprobs;
+    if (e->opt_token_logprobs && (s = lp_alloc(e)) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }
     e->weight_bytes = 0; e->finalized = true; e->owner = root;
     root->slots.push_back(e);
     *out = e;

@@ -422,6 +422,7 @@ static const OptRow OPTIONS[] = {
     {"no_graph", ENG(opt_no_graph), false, nullptr},                // eager decode loop (debugging)
     {"decode_lookahead", ENG(lookahead), false, [](int v) { return v < 1 ? 1 : (v > CHK_MAX_AHEAD ? CHK_MAX_AHEAD : v); }},   // start value (it adapts)
     {"decode_chunk", ENG(opt_decode_chunk), false, [](int v) { return v > 0 ? (v > 64 ? 64 : v) : 1; }},   // token steps per graph launch / early-stop check
+    {"token_logprobs", ENG(opt_token_logprobs), true, [](int v) { return v ? 1 : 0; }},   // per-token log-probabilities beside the ids (greedy_kernel<T, true>); out_lp is allocated below
     {"prefill_rowmajor", ENG(opt_prefill_rowmajor), false, nullptr},   // prefill GEMMs read the row-major decoder weights (kept only under SONIC_KEEP_ROWMAJOR=1; A/B)
     {"no_rope_tiles", ENG(opt_no_rope_tiles), false, nullptr},      // prefill RoPE + KV append per token (rounds 1-4) instead of per 16-position tile (A/B)
     {"gemm_trace", ENG(opt_gemm_trace), false, nullptr},            // sonic_bench_gemm prints an in-kernel timeline of one launch to stderr
@@ -442,6 +443,7 @@ extern "C" int sonic_set_option(sonic_engine* e, const char* key, int value) {
         const int v = r.clamp ? r.clamp(value) : value;
         if (r.field) e->*r.field = v; else e->opts.*r.lfield = v;
         if (r.drop_graphs) drop_graphs(e);
+        if (r.field == &sonic_engine::opt_token_logprobs && v) TRY(lp_alloc(e));      // first use: 64 x out_cap fp32
         return SONIC_OK;
     }
     // the two knobs that do device work
@@ -530,25 +532,30 @@ extern "C" int sonic_test_linear_int8(sonic_engine* e, const float* X, const flo
 
 // greedy_kernel on caller-provided lm_head partial slabs [ksplit][mpad][V] (fp32): returns the token each row picks (first maximum of
 // the bf16-rounded slab sum, HF:generation/utils.py:2925 / torch.argmax semantics) and, optionally, the bf16 logits it compared.
-extern "C" int sonic_test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, int32_t* tok_out, float* logits_out) {
-    if (!e || !slabs || !tok_out) return SONIC_ERR_INVALID;
-    ENTER(e);
+// sonic_test_greedy_lp: the same launch through greedy_kernel<T, true>, optionally under teacher forcing (force_ids[B]: the token every row emits
+// instead of its argmax); lp_out[B] = the emitted token's log-probability.
+static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const int32_t* force_ids, int32_t* tok_out, float* logits_out, float* lp_out) {
     if (ksplit < 1 || ksplit > 8 || B < 1 || B > 64 || mpad < B || V < 4 || V % 4) return fail(e, SONIC_ERR_INVALID, "bad greedy test shape");
+    if (force_ids) for (int b = 0; b < B; ++b) if (force_ids[b] < 0 || force_ids[b] >= V) return fail(e, SONIC_ERR_INVALID, "forced id %d out of vocabulary", force_ids[b]);
     TmpBuf tb(e->st);
     const size_t n = (size_t)ksplit * mpad * V;
     float* dl = up_f32(e, tb, slabs, n);
     bf16_t* table = tb.get<bf16_t>((size_t)V * 8); bf16_t* x = tb.get<bf16_t>((size_t)64 * 8);
     int* st = tb.get<int>(64 * 8 + 4); int* ids = tb.get<int>(64);
     float* dump = logits_out ? tb.get<float>((size_t)B * V) : nullptr;
-    if (!dl || !table || !x || !st || !ids || (logits_out && !dump)) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    float* lp = lp_out ? tb.get<float>(64) : nullptr;
+    int* fd = force_ids ? tb.get<int>(64) : nullptr;
+    if (!dl || !table || !x || !st || !ids || (logits_out && !dump) || (lp_out && !lp) || (force_ids && !fd)) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     std::vector<int> h(64 * 8 + 4, 0);
     for (int b = 0; b < 64; ++b) { h[64 * 2 + b] = 1; h[64 * 4 + b] = 4; }       // kv_len = 1, max_new = 4
     h[64 * 8] = B;
     HIPC(e, h2d(e, st, h.data(), h.size() * 4));
+    if (fd) HIPC(e, h2d(e, fd, force_ids, (size_t)B * 4));
     GreedyArgs g{};
     g.logits = dl; g.ksplit = ksplit; g.mpad = mpad; g.V = V; g.B = B; g.table = table; g.x = x; g.d = 8;
     g.out_ids = ids; g.out_ld = 1; g.n_new = st; g.finished = st + 64; g.kv_len = st + 128; g.tok_pos = st + 192; g.max_new = st + 256;
     g.n_active = st + 512; g.n_eos = 0; g.pad_id = 0; g.logits_dump = dump; g.dump_stride_step = (long)B * V; g.step_counter = dump ? st + 320 : nullptr;
+    g.out_lp = lp; g.force_ids = fd; g.force_ld = 1;
     launch_greedy(g, e->st);
     HIPC(e, stream_sync(e));
     HIPC(e, hipGetLastError());
@@ -556,7 +563,19 @@ extern "C" int sonic_test_greedy(sonic_engine* e, const float* slabs, int ksplit
     HIPC(e, d2h(e, out.data(), ids, 64 * 4));
     for (int b = 0; b < B; ++b) tok_out[b] = out[b];
     if (logits_out) HIPC(e, d2h(e, logits_out, dump, (size_t)B * V * 4));
+    if (lp_out) HIPC(e, d2h(e, lp_out, lp, (size_t)B * 4));
     return SONIC_OK;
+}
+extern "C" int sonic_test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, int32_t* tok_out, float* logits_out) {
+    if (!e || !slabs || !tok_out) return SONIC_ERR_INVALID;
+    ENTER(e);
+    return test_greedy(e, slabs, ksplit, mpad, V, B, nullptr, tok_out, logits_out, nullptr);
+}
+extern "C" int sonic_test_greedy_lp(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const int32_t* force_ids, int32_t* tok_out,
+                                    float* logits_out, float* lp_out) {
+    if (!e || !slabs || !tok_out || !lp_out) return SONIC_ERR_INVALID;
+    ENTER(e);
+    return test_greedy(e, slabs, ksplit, mpad, V, B, force_ids, tok_out, logits_out, lp_out);
 }
 
 extern "C" int sonic_test_skinny_gu(sonic_engine* e, const float* X, const float* Wgu_interleaved, float* act, int M, int N, int K) {

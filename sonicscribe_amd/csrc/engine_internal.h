@@ -120,6 +120,7 @@ struct sonic_engine {
     bf16_t* sx2 = nullptr;                                          // ... and the second residual buffer of that form (the stream ping-pongs layer by layer)
     int *kv_len = nullptr, *tok_pos = nullptr, *n_new = nullptr, *finished = nullptr, *max_new_d = nullptr, *n_active = nullptr;
     int *out_ids = nullptr, *step_ctr = nullptr, *seq_iota = nullptr;
+    float* out_lp = nullptr;                                        // [64][out_cap] log-probability of every emitted token, beside out_ids (option token_logprobs; lp_alloc)
     int *src = nullptr, *tok_seq = nullptr, *tok_pos_pf = nullptr, *q_off = nullptr, *q_len = nullptr, *last_row = nullptr;
     float* dump = nullptr; size_t dump_cap = 0; int dump_steps = 0;
     bf16_t* taps = nullptr; int taps_on = 0; int last_ntok = 0;   // debug: prefill hidden states after embedding + each layer
@@ -171,6 +172,8 @@ struct sonic_engine {
                                    // MFMA chain, so a request's low bits then depend on whether its step had <= 4 rows.  Measured slower than the MFMA chain (profiles/round6_gemv_ab.txt): an experiment, off
     int opt_no_pre_norm = 0;       // 1: never the PRE form of the <= 2-row decode step (standalone add+RMSNorm launches as for more rows; A/B - same bits)
     int opt_decode_chunk = 2;      // token steps per captured graph = granularity of the early-stop check (sonic_set_option "decode_chunk")
+    int opt_token_logprobs = 0;    // 1: every greedy launch also writes log_softmax(logits)[token] to out_lp (greedy_kernel<T, true>); set on the owner before
+                                   // its slots exist (they copy it).  The decode loops keep their hipGraph form; graphs are cached per value
     long long* kt = nullptr; int kt_layer = -1;     // diagnostics ("ktrace" option): in-kernel timestamps of one decoder layer's kernels
     int* ring_peak = nullptr;                        // [Bm] per-request max |s| of a ring-staged batch (ingest.hip)
     std::atomic<int64_t> ring_bytes{0};             // owner: device bytes of those rings (part of sonic_memory_info of the owner)
@@ -274,4 +277,6 @@ void ring_free(sonic_ring* r);
 int resample_bank_get(sonic_engine* root, int64_t in_rate, int64_t out_rate, RsBank* out, std::string& err);
 void resample_release(sonic_engine* e);
 void async_shutdown(sonic_engine* e);
-int fetch_locked(sonic_engine* e, int32_t* out_ids, int out_ld, int32_t* out_len, float* step_logits);
+int fetch_locked(sonic_engine* e, int32_t* out_ids, int out_ld, int32_t* out_len, float* step_logits, float* out_lp = nullptr);
+int lp_alloc(sonic_engine* e);                      // out_lp on first use (engine.cpp)
+int lp_check(sonic_engine* e, const char* who);     // SONIC_ERR_INVALID naming the option when token_logprobs is off on this handle

@@ -13,6 +13,7 @@ struct SpliceArgs {
     const bf16_t *Ks, *Vs; bf16_t *Kd, *Vd; int layers, Bm, Hkv, ctx, hd;
     int src[64], dst[64];
     const int *kv_len_s, *tok_pos_s, *n_new_s, *fin_s, *max_new_s, *out_s; int out_ld;
+    const float* lp_s; float* lp_d;                      // option token_logprobs on the destination: the first token's log-probability travels with its id
     int *kv_len_d, *tok_pos_d, *n_new_d, *fin_d, *max_new_d, *out_d, *n_active_d;
     const bf16_t *sx_s, *shn_s; bf16_t *sx_d, *shn_d; int D;
     const int8_t* hq_s; int8_t* hq_d; const float *sca_s, *ov_s; float *sca_d, *ov_d; const int *oc_s, *ol_s; int *oc_d, *ol_d;   // int8 mode: layer 0's quantised input row
@@ -42,6 +43,7 @@ __global__ __launch_bounds__(256) void splice_state_kernel(SpliceArgs a) {
     if (t == 0) {
         const int fin = a.fin_s[s];
         a.out_d[(long)d * a.out_ld] = a.out_s[(long)s * a.out_ld];            // the first token came out of the prefill
+        if (a.lp_d) a.lp_d[(long)d * a.out_ld] = a.lp_s[(long)s * a.out_ld];
         a.kv_len_d[d] = a.kv_len_s[s]; a.tok_pos_d[d] = a.tok_pos_s[s]; a.n_new_d[d] = a.n_new_s[s]; a.max_new_d[d] = a.max_new_s[s];
         a.fin_d[d] = fin;
         if (!fin) atomicAdd(a.n_active_d, 1);
@@ -109,6 +111,8 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
     if (!d->svc_on) return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: the destination is not decoding continuously (sonic_service_begin)");
     if ((d->owner ? d->owner : d) != (p->owner ? p->owner : p)) return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: the handles do not share weights");
     if (d->Bm != p->Bm || d->max_ctx != p->max_ctx) return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: the handles differ in max_batch / max_ctx");
+    if (d->opt_token_logprobs && !(p->opt_token_logprobs && p->out_lp))
+        return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: the destination has option token_logprobs on, the source prefilled without it");
     if (n < 1 || n > 64 || p->greedy_calls < 1 || n > p->R) return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: %d rows, the source has %d prefilled requests", n, p->greedy_calls < 1 ? 0 : p->R);
     SpliceArgs a{};
     for (int i = 0; i < n; ++i) {
@@ -121,6 +125,7 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
     a.kv_len_s = p->kv_len; a.tok_pos_s = p->tok_pos; a.n_new_s = p->n_new; a.fin_s = p->finished; a.max_new_s = p->max_new_d; a.out_s = p->out_ids; a.out_ld = d->out_cap;
     a.kv_len_d = d->kv_len; a.tok_pos_d = d->tok_pos; a.n_new_d = d->n_new; a.fin_d = d->finished; a.max_new_d = d->max_new_d; a.out_d = d->out_ids; a.n_active_d = d->n_active;
     a.sx_s = p->sx; a.shn_s = p->shn; a.sx_d = d->sx; a.shn_d = d->shn; a.D = dm.dec_d;
+    if (d->opt_token_logprobs && d->out_lp) { a.lp_s = p->out_lp; a.lp_d = d->out_lp; }
     if (d->i8) { a.hq_s = p->hn_q; a.hq_d = d->hn_q; a.sca_s = p->sca_hn; a.sca_d = d->sca_hn; a.oc_s = p->oc_hn; a.oc_d = d->oc_hn; a.ol_s = p->ol_hn; a.ol_d = d->ol_hn; a.ov_s = p->ov_hn; a.ov_d = d->ov_hn; }
     HIPC(d, hipEventRecord(p->xfer_ev, p->st));
     HIPC(d, hipStreamWaitEvent(d->st, p->xfer_ev, 0));
@@ -213,9 +218,7 @@ __global__ void release_rows_kernel(int* kv_len, int* tok_pos, int* finished, Sp
     const int i = threadIdx.x;
     if (i < n) { const int row = a.dst[i]; kv_len[row] = 1; tok_pos[row] = 0; finished[row] = 1; }
 }
-extern "C" int sonic_fetch_rows(sonic_engine* e, int n, const int32_t* rows, const int32_t* counts, int32_t* out_ids, int out_ld) {
-    if (!e || !rows || !counts || !out_ids) return SONIC_ERR_INVALID;
-    ENTER(e);
+static int fetch_rows_locked(sonic_engine* e, int n, const int32_t* rows, const int32_t* counts, int32_t* out_ids, int out_ld, float* out_lp) {
     if (!e->svc_on) return fail(e, SONIC_ERR_INVALID, "sonic_fetch_rows needs sonic_service_begin");
     if (n < 1 || n > 64) return fail(e, SONIC_ERR_INVALID, "sonic_fetch_rows: %d rows", n);
     SpliceArgs a{};
@@ -227,11 +230,26 @@ extern "C" int sonic_fetch_rows(sonic_engine* e, int n, const int32_t* rows, con
         a.dst[i] = row;
     }
     for (int i = 0; i < n; ++i)
-        if (counts[i] > 0) HIPC(e, hipMemcpyAsync(out_ids + (size_t)i * out_ld, e->out_ids + (size_t)rows[i] * e->out_cap, (size_t)counts[i] * 4, hipMemcpyDeviceToHost, e->st_io));
+        if (counts[i] > 0) {
+            HIPC(e, hipMemcpyAsync(out_ids + (size_t)i * out_ld, e->out_ids + (size_t)rows[i] * e->out_cap, (size_t)counts[i] * 4, hipMemcpyDeviceToHost, e->st_io));
+            if (out_lp) HIPC(e, hipMemcpyAsync(out_lp + (size_t)i * out_ld, e->out_lp + (size_t)rows[i] * e->out_cap, (size_t)counts[i] * 4, hipMemcpyDeviceToHost, e->st_io));
+        }
     HIPC(e, hipStreamSynchronize(e->st_io));
     hipLaunchKernelGGL(release_rows_kernel, dim3(1), dim3(64), 0, e->st, e->kv_len, e->tok_pos, e->finished, a, n);
     HIPC(e, hipGetLastError());
     return SONIC_OK;
+}
+extern "C" int sonic_fetch_rows(sonic_engine* e, int n, const int32_t* rows, const int32_t* counts, int32_t* out_ids, int out_ld) {
+    if (!e || !rows || !counts || !out_ids) return SONIC_ERR_INVALID;
+    ENTER(e);
+    return fetch_rows_locked(e, n, rows, counts, out_ids, out_ld, nullptr);
+}
+// sonic_fetch_rows with the rows' log-probabilities in the same call (the fetch releases the rows): row i's at out_lp + i * out_ld, as its ids
+extern "C" int sonic_fetch_rows_lp(sonic_engine* e, int n, const int32_t* rows, const int32_t* counts, int32_t* out_ids, int out_ld, float* out_lp) {
+    if (!e || !rows || !counts || !out_ids || !out_lp) return SONIC_ERR_INVALID;
+    ENTER(e);
+    TRY(lp_check(e, "sonic_fetch_rows_lp"));
+    return fetch_rows_locked(e, n, rows, counts, out_ids, out_ld, out_lp);
 }
 
 // ---- asynchronous form: the batch runs on a worker thread of the engine's own; the caller's thread returns at once and may drive other slots.
@@ -335,7 +353,7 @@ extern "C" int sonic_decode_step(sonic_engine* e, int n_steps, int32_t* n_active
     return SONIC_OK;
 }
 
-int fetch_locked(sonic_engine* e, int32_t* out_ids, int out_ld, int32_t* out_len, float* step_logits) {
+int fetch_locked(sonic_engine* e, int32_t* out_ids, int out_ld, int32_t* out_len, float* step_logits, float* out_lp) {
     const int R = e->R;
     if (R < 1) return fail(e, SONIC_ERR_INVALID, "nothing to fetch");
     std::vector<int> nn(64), kvl(64), tps(64), fin(64);
@@ -363,6 +381,10 @@ int fetch_locked(sonic_engine* e, int32_t* out_ids, int out_ld, int32_t* out_len
             if (nn[r] > out_ld) return fail(e, SONIC_ERR_INVALID, "out_ld too small");
             HIPC(e, d2h_async(e, out_ids + (size_t)r * out_ld, e->out_ids + (size_t)r * e->out_cap, (size_t)nn[r] * 4));
         }
+        if (out_lp) {
+            if (nn[r] > out_ld) return fail(e, SONIC_ERR_INVALID, "out_ld too small");
+            HIPC(e, d2h_async(e, out_lp + (size_t)r * out_ld, e->out_lp + (size_t)r * e->out_cap, (size_t)nn[r] * 4));
+        }
     }
     if (step_logits) {
         if (!e->dump_steps) return fail(e, SONIC_ERR_INVALID, "step logits were not requested for the last run");
@@ -376,6 +398,15 @@ extern "C" int sonic_fetch_tokens(sonic_engine* e, int32_t* out_ids, int out_ld,
     if (!e) return SONIC_ERR_INVALID;
     ENTER(e);
     return fetch_locked(e, out_ids, out_ld, out_len, step_logits);
+}
+
+// the log-probabilities of the tokens sonic_fetch_tokens returns (same rows, same counts: row r's n_new[r] values at out_lp + r * out_ld; entries
+// beyond are not written); valid whenever that call is
+extern "C" int sonic_fetch_logprobs(sonic_engine* e, float* out_lp, int out_ld) {
+    if (!e || !out_lp) return SONIC_ERR_INVALID;
+    ENTER(e);
+    TRY(lp_check(e, "sonic_fetch_logprobs"));
+    return fetch_locked(e, nullptr, out_ld, nullptr, nullptr, out_lp);
 }
 
 extern "C" int sonic_transcribe_batch(sonic_engine* e, const int16_t* pcm, const int64_t* offsets, int W, const int32_t* req_win, int R,

@@ -209,7 +209,7 @@ GreedyArgs greedy_args(sonic_engine* e, int R, bool dump) {
     const sonic_dims& d = e->d;
     GreedyArgs g{};
     g.logits = e->lslab; g.ksplit = skinny_pick_ksplit(d.vocab, d.dec_d); g.mpad = ((R + 15) / 16) * 16; g.V = d.vocab; g.B = R; g.table = e->embed; g.x = e->sx; g.d = d.dec_d;
-    g.out_ids = e->out_ids; g.out_ld = e->out_cap; g.n_new = e->n_new; g.finished = e->finished; g.kv_len = e->kv_len; g.tok_pos = e->tok_pos;
+    g.out_ids = e->out_ids; g.out_lp = e->opt_token_logprobs ? e->out_lp : nullptr; g.out_ld = e->out_cap; g.n_new = e->n_new; g.finished = e->finished; g.kv_len = e->kv_len; g.tok_pos = e->tok_pos;
     g.max_new = e->max_new_d; g.n_active = e->n_active; g.dev_err = e->n_active + 1; g.n_eos = d.n_eos; g.pad_id = d.n_eos > 0 ? d.eos[0] : 0;
     for (int i = 0; i < d.n_eos; ++i) g.eos[i] = d.eos[i];
     g.logits_dump = dump ? e->dump : nullptr; g.dump_stride_step = (long)R * d.vocab; g.step_counter = dump ? e->step_ctr : nullptr;
@@ -570,7 +570,7 @@ int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int
 // svc: the chunk belongs to a continuous decode loop (sonic_service_*), i.e. it runs beside a prefill slot and other loops by design - decode_step then
 // picks the forms that cost the fewest CU-microseconds rather than the shortest chain (gu64_split_norm).  Same bits either way; cached separately.
 int chunk_graph(sonic_engine* e, int R, int n, hipGraphExec_t* out, bool svc) {
-    const std::pair<int, int> key{R + (svc ? 4096 : 0), n};
+    const std::pair<int, int> key{R + (svc ? 4096 : 0) + (e->opt_token_logprobs ? 8192 : 0), n};   // (the LP greedy kernel and its out_lp pointer are part of the capture)
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) { *out = it->second; return SONIC_OK; }
     hipGraph_t g = nullptr; hipGraphExec_t gx = nullptr;

@@ -107,6 +107,8 @@ struct GreedyArgs {
     const int* force_ids; int force_ld;                // optional teacher forcing: token n of row b is force_ids[b * force_ld + n] (oracle force_ids)
     int dt;
     QuantOut qo;                                       // int8 mode: y is also emitted quantised (input of layer 0's q/k/v Linear8bitLt)
+    float* out_lp;                                     // optional [B][out_ld], indexed like out_ids: log-probability of every emitted token (greedy_kernel<T, true>;
+                                                       // option token_logprobs); NULL = off.  Last: the offsets of the fields above are what they were
 };
 void launch_greedy(const GreedyArgs& a, hipStream_t s);
 

@@ -11,7 +11,7 @@
 //     chunks (sonic_service_step: blocking, sleeps on an event), fetches the rows of a block the moment the pipelined check shows every row of
 //     it finished, completes the batch's ticket.  An EMPTY loop leaves the next batch to a loop that is running part-filled (two batches in one
 //     64-row loop stream the weights once).
-// No thread polls: every wait is a condition variable or a blocking HIP event inside the engine.  Only the C ABI of include/sonic_hip.h is used.
+// No thread polls: every wait is a condition variable or a blocking HIP event inside the engine.  Only the C ABI of include/sonic_hip.h is used (and engine_token_logprobs_on).
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/sonic_hip.h"
+extern "C" int engine_token_logprobs_on(sonic_engine* e);   // engine.cpp
 
 namespace {
 
@@ -38,6 +39,7 @@ struct Batch {
     int R = 0;
     std::vector<int32_t> prompt_ids; std::vector<int64_t> prompt_off; std::vector<int32_t> max_new;
     int32_t* out_ids = nullptr; int out_ld = 0; int32_t* out_len = nullptr;
+    float* out_lp = nullptr;                            // sonic_pipeline_submit_lp: the tokens' log-probabilities, laid out as out_ids
     int status = -1;                                    // -1 running, else a sonic_status
     std::string err;
 };
@@ -189,7 +191,8 @@ void decode_thread(sonic_pipeline* p, int k) {
             Batch& b = *occ[i].b;
             std::vector<int32_t> rows(b.R), counts(b.R);
             for (int r = 0; r < b.R; ++r) { rows[r] = i * B + r; counts[r] = nn[i * B + r]; if (counts[r] > b.out_ld) counts[r] = b.out_ld; }
-            rc = sonic_fetch_rows(d, b.R, rows.data(), counts.data(), b.out_ids, b.out_ld);
+            rc = b.out_lp ? sonic_fetch_rows_lp(d, b.R, rows.data(), counts.data(), b.out_ids, b.out_ld, b.out_lp)
+                          : sonic_fetch_rows(d, b.R, rows.data(), counts.data(), b.out_ids, b.out_ld);
             if (rc != SONIC_OK) { fail_all(rc); return; }
             for (int r = 0; r < b.R; ++r) b.out_len[r] = counts[r];
             std::unique_lock<std::mutex> lk(p->mu);
@@ -246,8 +249,14 @@ SONIC_API int sonic_pipeline_create(sonic_engine* const* decoders, int n_dec, so
 
 static int submit_batch(sonic_pipeline* p, const int16_t* pcm, const int64_t* offsets, sonic_ring* const* rings, const int64_t* ring_start,
                         const int32_t* ring_n, int W, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new,
-                        int32_t* out_ids, int out_ld, int32_t* out_len, int64_t* ticket_out) {
+                        int32_t* out_ids, int out_ld, int32_t* out_len, int64_t* ticket_out, float* out_lp = nullptr) {
     if (!p || !prompt_ids || !prompt_off || !max_new || !out_ids || !out_len || R < 1 || R > p->block || out_ld < 1) return SONIC_ERR_INVALID;
+    if (out_lp) {
+        bool on = true;
+        for (auto* h : p->dec) on = on && engine_token_logprobs_on(h);
+        for (auto* h : p->pre) on = on && engine_token_logprobs_on(h);
+        if (!on) { std::unique_lock<std::mutex> lk(p->mu); p->last_err = "sonic_pipeline_submit_lp: option token_logprobs is off on a handle of this pipeline"; return SONIC_ERR_INVALID; }
+    }
     if (pcm && (!offsets || W < 1)) return SONIC_ERR_INVALID;
     if (rings && (!ring_start || !ring_n || W < 1)) return SONIC_ERR_INVALID;
     auto b = std::make_shared<Batch>();
@@ -259,7 +268,7 @@ static int submit_batch(sonic_pipeline* p, const int16_t* pcm, const int64_t* of
     b->prompt_off.assign(prompt_off, prompt_off + R + 1);
     b->prompt_ids.assign(prompt_ids, prompt_ids + prompt_off[R]);
     b->max_new.assign(max_new, max_new + R);
-    b->out_ids = out_ids; b->out_ld = out_ld; b->out_len = out_len;
+    b->out_ids = out_ids; b->out_ld = out_ld; b->out_len = out_len; b->out_lp = out_lp;
     std::unique_lock<std::mutex> lk(p->mu);
     if (p->stop) { p->last_err = "pipeline is closed"; return SONIC_ERR_INVALID; }
     if (p->failed) { p->last_err = p->fail_msg; return p->failed; }
@@ -281,6 +290,16 @@ SONIC_API int sonic_pipeline_submit_mixed(sonic_pipeline* p, const int16_t* host
                                           int32_t* out_ids, int out_ld, int32_t* out_len, int64_t* ticket_out) {
     if (!rings) return SONIC_ERR_INVALID;
     return submit_batch(p, host_pcm, host_off, rings, ring_start, ring_n, W, req_win, R, prompt_ids, prompt_off, max_new, out_ids, out_ld, out_len, ticket_out);
+}
+
+// sonic_pipeline_submit_mixed (rings may be NULL: host windows only) plus out_lp [R][out_ld]: token i of request r gets its log-probability at
+// out_lp[r * out_ld + i]; like out_ids it must stay valid until the ticket has been waited for.  Needs option token_logprobs on every handle.
+SONIC_API int sonic_pipeline_submit_lp(sonic_pipeline* p, const int16_t* host_pcm, const int64_t* host_off, sonic_ring* const* rings,
+                                       const int64_t* ring_start, const int32_t* ring_n, int W, const int32_t* req_win, int R,
+                                       const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new,
+                                       int32_t* out_ids, int out_ld, int32_t* out_len, float* out_lp, int64_t* ticket_out) {
+    if (!out_lp) return SONIC_ERR_INVALID;
+    return submit_batch(p, host_pcm, host_off, rings, ring_start, ring_n, W, req_win, R, prompt_ids, prompt_off, max_new, out_ids, out_ld, out_len, ticket_out, out_lp);
 }
 
 // ticket > 0: blocks until that batch is complete and returns ITS status (then forgets it); ticket 0: until every batch submitted so far is

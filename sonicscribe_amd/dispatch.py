@@ -46,10 +46,11 @@ def step_class(max_new: int) -> int:
 
 
 class Request:
-    __slots__ = ("windows", "prompt", "max_new", "future", "t_submit", "cls")
+    __slots__ = ("windows", "prompt", "max_new", "future", "t_submit", "cls", "want_logprobs")
 
-    def __init__(self, windows: Sequence[Any], prompt: Sequence[int], max_new: int):
+    def __init__(self, windows: Sequence[Any], prompt: Sequence[int], max_new: int, want_logprobs: bool = False):
         self.windows, self.prompt, self.max_new = list(windows), prompt, int(max_new)
+        self.want_logprobs = bool(want_logprobs)      # the future resolves to (ids, float32 log-probabilities) instead of ids (engine option token_logprobs)
         self.future: Future = Future()
         self.t_submit = time.perf_counter()
         self.cls = step_class(self.max_new)
@@ -126,15 +127,24 @@ class _Replica:
         for r in batch:
             segs.extend(r.windows)
             req_win.append(len(segs))
+        want = any(r.want_logprobs for r in batch)      # (the keyword only goes to the engine when somebody asked: duck-typed engines need not know it)
         try:
-            ids, _ = engine.transcribe_batch(segs, [r.prompt for r in batch], [r.max_new for r in batch], req_win=req_win)
+            if want:
+                ids, _, lps = engine.transcribe_batch(segs, [r.prompt for r in batch], [r.max_new for r in batch], req_win=req_win, want_logprobs=True)
+                ids = [(i, l) if r.want_logprobs else i for r, i, l in zip(batch, ids, lps)]
+            else:
+                ids, _ = engine.transcribe_batch(segs, [r.prompt for r in batch], [r.max_new for r in batch], req_win=req_win)
         except BaseException as ex:              # a per-request validation error must not poison its neighbours: retry one by one
             if len(batch) == 1:
                 self._finish(batch[0], error=ex)
                 return
             for r in batch:
                 try:
-                    one, _ = engine.transcribe_batch(r.windows, [r.prompt], [r.max_new], req_win=[0, len(r.windows)])
+                    if r.want_logprobs:
+                        one, _, lp1 = engine.transcribe_batch(r.windows, [r.prompt], [r.max_new], req_win=[0, len(r.windows)], want_logprobs=True)
+                        one = [(one[0], lp1[0])]
+                    else:
+                        one, _ = engine.transcribe_batch(r.windows, [r.prompt], [r.max_new], req_win=[0, len(r.windows)])
                 except BaseException as ex2:
                     self._finish(r, error=ex2)
                 else:
@@ -230,6 +240,9 @@ class _ContinuousReplica:
             return (self.n_rows * len(self.decoders) - sum(self.free)) + sum(len(r.windows) for r in self.q)
 
     def put(self, req: Request):
+        if req.want_logprobs and not all(getattr(e, "token_logprobs", False) for e in self.engines):
+            # refused here: inside the decode thread the failing fetch would take the neighbours' rows with it
+            raise ValueError("log-probabilities need the engine option token_logprobs on every handle (ASRModel(token_logprobs=True))")
         with self.cv:
             if self.stop:
                 raise RuntimeError("ASR engine is closed")
@@ -357,7 +370,11 @@ class _ContinuousReplica:
                 self.steps += 1
                 done = [i for i, r in enumerate(rows) if r is not None and seq > valid_after[i] and fin[i]]
                 if done:                                 # one call for all of them: one wait, one release launch (sonic_fetch_rows)
-                    got = d.fetch_rows(done, [int(nn[i]) for i in done]) if len(done) > 1 else [d.fetch_row(done[0], int(nn[done[0]]))]
+                    if any(rows[i].want_logprobs for i in done):      # ids and log-probabilities in one call: the fetch releases the rows
+                        got, lps = d.fetch_rows(done, [int(nn[i]) for i in done], want_logprobs=True)
+                        got = [(g, l) if rows[i].want_logprobs else g for i, g, l in zip(done, got, lps)]
+                    else:
+                        got = d.fetch_rows(done, [int(nn[i]) for i in done]) if len(done) > 1 else [d.fetch_row(done[0], int(nn[done[0]]))]
                     for i, ids in zip(done, got):
                         r, rows[i] = rows[i], None
                         occupied -= 1
@@ -425,6 +442,7 @@ class _NativeContinuousReplica:
         self.pending = {}                                # ticket -> Request
         self.stop = False
         self.out_cap = int(engine.max_ctx)
+        self.lp = all(getattr(e, "token_logprobs", False) for e in self.engines)      # then completions are collected with their log-probabilities
         self.thread = threading.Thread(target=self._complete_loop, name=f"sonic-dispatch-{index}.complete", daemon=True)
         self.thread.start()
 
@@ -454,6 +472,8 @@ class _NativeContinuousReplica:
     def put(self, req: Request):
         import ctypes as C
         from .engine import RingSlice, _p
+        if req.want_logprobs and not self.lp:
+            raise ValueError("log-probabilities need the engine option token_logprobs on every handle (ASRModel(token_logprobs=True))")
         wins = req.windows
         W = len(wins)
         offs = np.zeros(W + 1, np.int64)
@@ -487,11 +507,30 @@ class _NativeContinuousReplica:
         import ctypes as C
         from .engine import SONIC_ERR_MISMATCH, SonicError
         ids = np.zeros(self.out_cap, np.int32)
+        lps = np.zeros(self.out_cap, np.float32)
         err = C.create_string_buffer(512)
         t, st, n = C.c_int64(0), C.c_int32(0), C.c_int32(0)
         while True:
-            rc = self.lib.sonic_dispatch_next(self.h, -1, C.byref(t), C.byref(st), ids.ctypes.data_as(C.c_void_p), self.out_cap, C.byref(n), err, 512)
-            if rc != 0 or t.value == 0:
+            if self.lp:
+                rc = self.lib.sonic_dispatch_next_lp(self.h, -1, C.byref(t), C.byref(st), ids.ctypes.data_as(C.c_void_p), self.out_cap, C.byref(n), err, 512,
+                                                     lps.ctypes.data_as(C.c_void_p))
+            else:
+                rc = self.lib.sonic_dispatch_next(self.h, -1, C.byref(t), C.byref(st), ids.ctypes.data_as(C.c_void_p), self.out_cap, C.byref(n), err, 512)
+            if rc != 0:
+                # the library refused the collector itself (sonic_dispatch_next_lp on handles without token_logprobs): nothing can be delivered
+                # any more - fail what is pending and every later put() instead of leaving the futures hanging
+                ex = SonicError(err.value.decode(errors="replace") or f"sonic_dispatch_next failed with status {rc}")
+                with self.lock:
+                    self.stop = True
+                    pending, self.pending = list(self.pending.values()), {}
+                for r in pending:
+                    if not r.future.done():
+                        try:
+                            r.future.set_exception(ex)
+                        except BaseException:
+                            pass
+                return
+            if t.value == 0:
                 return                                   # closed and drained
             with self.lock:
                 req = self.pending.pop(int(t.value), None)
@@ -499,7 +538,7 @@ class _NativeContinuousReplica:
                 continue
             try:
                 if st.value == 0:
-                    req.future.set_result(ids[:n.value].copy())
+                    req.future.set_result((ids[:n.value].copy(), lps[:n.value].copy()) if req.want_logprobs else ids[:n.value].copy())
                 else:
                     msg = err.value.decode(errors="replace")
                     if "audio spans" in msg or st.value == SONIC_ERR_MISMATCH:
@@ -598,7 +637,16 @@ class _BulkReplica:
         for r in batch:
             segs.extend(r.windows)
             req_win.append(len(segs))
+        if any(r.want_logprobs for r in batch):
+            return self.pipe.submit([r.prompt for r in batch], [r.max_new for r in batch], segments=segs, req_win=req_win, want_logprobs=True)
         return self.pipe.submit([r.prompt for r in batch], [r.max_new for r in batch], segments=segs, req_win=req_win)
+
+    @staticmethod
+    def _results(batch: List[Request], got):
+        """pipe.wait's value per request: ids, or (ids, log-probabilities) for those that asked (the batch was then submitted with want_logprobs)"""
+        if isinstance(got, tuple):
+            return [(i, l) if r.want_logprobs else i for r, i, l in zip(batch, got[0], got[1])]
+        return list(got)
 
     def _submit_loop(self):
         while True:
@@ -647,7 +695,7 @@ class _BulkReplica:
                 self.inflight.pop(0)
                 self.cv.notify_all()
             if rows is not None:
-                for r, ids in zip(batch, rows):
+                for r, ids in zip(batch, self._results(batch, rows)):
                     self._finish(r, ids)
             elif len(batch) == 1:
                 self._finish(batch[0], error=err)
@@ -656,7 +704,7 @@ class _BulkReplica:
                 for r in batch:
                     try:
                         t = self._submit([r])
-                        self._finish(r, self.pipe.wait(t)[0])
+                        self._finish(r, self._results([r], self.pipe.wait(t))[0])
                     except BaseException as ex2:
                         self._finish(r, error=ex2)
 
@@ -713,9 +761,10 @@ class Dispatcher:
             return self.replicas[least]                                     # rebalance: the home replica is more than a batch behind
         return self.replicas[home]
 
-    def submit(self, windows, prompt, max_new: int, session: Optional[str] = None, replica: Optional[int] = None) -> Future:
-        """`replica` pins the request (windows that are slices of a device ring can only be decoded where the ring lives)."""
-        req = Request(windows, prompt, max_new)
+    def submit(self, windows, prompt, max_new: int, session: Optional[str] = None, replica: Optional[int] = None, want_logprobs: bool = False) -> Future:
+        """`replica` pins the request (windows that are slices of a device ring can only be decoded where the ring lives).  want_logprobs: the
+        future resolves to (ids, log-probabilities) - the engines need option token_logprobs."""
+        req = Request(windows, prompt, max_new, want_logprobs)
         (self.replicas[replica] if replica is not None else self.pick(session)).put(req)
         return req.future
 

@@ -36,8 +36,9 @@ EXPORTS = [
     "sonic_dispatch_create", "sonic_dispatch_submit", "sonic_dispatch_cancel", "sonic_dispatch_next", "sonic_dispatch_stats", "sonic_dispatch_close", "sonic_dispatch_destroy",
     "sonic_pipeline_create", "sonic_pipeline_submit", "sonic_pipeline_submit_mixed", "sonic_pipeline_wait", "sonic_pipeline_stats", "sonic_pipeline_last_error", "sonic_pipeline_destroy",
     "sonic_vad_create", "sonic_vad_destroy", "sonic_vad_last_error", "sonic_vad_load_tensor", "sonic_vad_probs", "sonic_vad_probs_rings",
+    "sonic_fetch_logprobs", "sonic_fetch_rows_lp", "sonic_dispatch_next_lp", "sonic_pipeline_submit_lp", "sonic_test_greedy_lp",
 ]
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 class SonicDims(C.Structure):
@@ -120,6 +121,7 @@ def load_library():
     lib.sonic_stage_mixed.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int]
     lib.sonic_run_staged.argtypes = [vp, vp, C.c_int, vp, vp, vp, C.c_int]
     lib.sonic_fetch_tokens.argtypes = [vp, vp, C.c_int, vp, vp]
+    lib.sonic_fetch_logprobs.argtypes = [vp, vp, C.c_int]
     lib.sonic_get_timings.argtypes = [vp, C.POINTER(SonicTimings)]
     lib.sonic_synchronize.argtypes = [vp]
     lib.sonic_test_gemm.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -143,6 +145,7 @@ def load_library():
     lib.sonic_pipeline_create.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     lib.sonic_pipeline_submit.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, i64p]
     lib.sonic_pipeline_submit_mixed.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, i64p]
+    lib.sonic_pipeline_submit_lp.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, i64p]
     lib.sonic_pipeline_wait.argtypes = [vp, C.c_int64]
     lib.sonic_pipeline_stats.argtypes = [vp, i64p, i64p, ip]
     lib.sonic_pipeline_last_error.argtypes = [vp]
@@ -151,6 +154,7 @@ def load_library():
     lib.sonic_memory_info.argtypes = [vp, i64p, i64p]
     lib.sonic_set_forced_ids.argtypes = [vp, vp, C.c_int, C.c_int]
     lib.sonic_test_greedy.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    lib.sonic_test_greedy_lp.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.sonic_test_linear_int8.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.sonic_slot_create.argtypes = [vp, C.POINTER(vp)]
     lib.sonic_slot_count.argtypes = [vp]
@@ -158,6 +162,7 @@ def load_library():
     lib.sonic_dispatch_submit.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, i64p]
     lib.sonic_dispatch_cancel.argtypes = [vp, C.c_int64]
     lib.sonic_dispatch_next.argtypes = [vp, C.c_int, i64p, ip, vp, C.c_int, ip, C.c_char_p, C.c_int]
+    lib.sonic_dispatch_next_lp.argtypes = [vp, C.c_int, i64p, ip, vp, C.c_int, ip, C.c_char_p, C.c_int, vp]
     lib.sonic_dispatch_stats.argtypes = [vp, i64p, i64p, ip, ip]
     lib.sonic_dispatch_close.argtypes = [vp]
     lib.sonic_dispatch_destroy.argtypes = [vp]
@@ -170,6 +175,7 @@ def load_library():
     lib.sonic_service_step.argtypes = [vp, C.c_int, C.c_int, vp, vp, i64p, ip]
     lib.sonic_fetch_row.argtypes = [vp, C.c_int, C.c_int, vp]
     lib.sonic_fetch_rows.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int]
+    lib.sonic_fetch_rows_lp.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp]
     lib.sonic_vad_create.argtypes = [C.c_int, C.c_int, C.POINTER(vp)]
     lib.sonic_vad_destroy.argtypes = [vp]
     lib.sonic_vad_destroy.restype = None
@@ -304,6 +310,7 @@ class Engine:
         KV cache, graphs, lock - that shares the owner's weight allocations.  Closed with its owner at the latest."""
         root = self.root
         s = Engine(self.dims, 0, 0, self.max_batch, self.max_ctx, _slot_of=root)
+        s.token_logprobs = bool(getattr(root, "token_logprobs", False))
         root._slots.append(s)
         return s
 
@@ -450,9 +457,10 @@ class Engine:
         return pcm, offs, rings, start, n
 
     def transcribe_batch(self, segments: Sequence[Any], prompts: Sequence[Sequence[int]], max_new: Sequence[int],
-                         req_win: Optional[Sequence[int]] = None, want_logits: bool = False):
+                         req_win: Optional[Sequence[int]] = None, want_logits: bool = False, want_logprobs: bool = False):
         """segments: int16 PCM windows (<= 30 s each, already peak-normalised) or RingSlice objects (raw wire PCM resident in a device
-        ring; normalised on the device over the windows of their request); one prompt per request. Returns (ids list, logits or None)."""
+        ring; normalised on the device over the windows of their request); one prompt per request. Returns (ids list, logits or None);
+        with want_logprobs (option token_logprobs on this handle) one more element: the float32 log-probability of every returned token, per request."""
         if any(isinstance(s, RingSlice) for s in segments):
             pcm, offs, rings, start, n = self._pack_mixed(segments)
             ids, poffs = self._pack_prompts(prompts)
@@ -465,7 +473,8 @@ class Engine:
             logits = np.zeros((out_ld, R, self.dims.vocab), np.float32) if want_logits else None
             self._check(self.lib.sonic_transcribe_mixed(self.h, _p(pcm), _p(offs), rings, _p(start), _p(n), len(segments), _p(rw), R, _p(ids), _p(poffs),
                                                         _p(mn), _p(out), out_ld, _p(out_len), _p(logits)))
-            return [out[r, : out_len[r]].copy() for r in range(R)], logits
+            res = [out[r, : out_len[r]].copy() for r in range(R)]
+            return (res, logits, self._fetch_logprobs(out_len, out_ld)) if want_logprobs else (res, logits)
         pcm, offs = self._pack_pcm(segments)
         ids, poffs = self._pack_prompts(prompts)
         R = len(prompts)
@@ -477,7 +486,14 @@ class Engine:
         logits = np.zeros((out_ld, R, self.dims.vocab), np.float32) if want_logits else None
         self._check(self.lib.sonic_transcribe_batch(self.h, _p(pcm), _p(offs), len(segments), _p(rw), R, _p(ids), _p(poffs), _p(mn),
                                                     _p(out), out_ld, _p(out_len), _p(logits)))
-        return [out[r, : out_len[r]].copy() for r in range(R)], logits
+        res = [out[r, : out_len[r]].copy() for r in range(R)]
+        return (res, logits, self._fetch_logprobs(out_len, out_ld)) if want_logprobs else (res, logits)
+
+    def _fetch_logprobs(self, out_len, out_ld: int) -> List[np.ndarray]:
+        """sonic_fetch_logprobs for the batch whose token counts are out_len: one float32 array per request (entries beyond a row's count are never written)"""
+        lp = np.full((len(out_len), max(1, int(out_ld))), np.nan, np.float32)
+        self._check(self.lib.sonic_fetch_logprobs(self.h, _p(lp), lp.shape[1]))
+        return [lp[r, : out_len[r]].copy() for r in range(len(out_len))]
 
     def stage_pcm(self, segments: Sequence[Any], req_win: Optional[Sequence[int]] = None):
         if any(isinstance(s, RingSlice) for s in segments):
@@ -567,11 +583,16 @@ class Engine:
         self._check(self.lib.sonic_fetch_row(self.h, int(row), int(n), _p(out)))
         return out[:n].copy()
 
-    def fetch_rows(self, rows: Sequence[int], counts: Sequence[int]) -> List[np.ndarray]:
-        """fetch_row for several finished rows in one call (one wait, one release launch)"""
+    def fetch_rows(self, rows: Sequence[int], counts: Sequence[int], want_logprobs: bool = False):
+        """fetch_row for several finished rows in one call (one wait, one release launch); want_logprobs: (ids list, log-probability list) from
+        sonic_fetch_rows_lp (both in one call: the fetch releases the rows)"""
         r, c = np.asarray(rows, np.int32), np.asarray(counts, np.int32)
         ld = max(1, int(c.max()) if len(c) else 1)
         out = np.zeros((len(r), ld), np.int32)
+        if want_logprobs:
+            lp = np.full((len(r), ld), np.nan, np.float32)
+            self._check(self.lib.sonic_fetch_rows_lp(self.h, len(r), _p(r), _p(c), _p(out), ld, _p(lp)))
+            return [out[i, :int(c[i])].copy() for i in range(len(r))], [lp[i, :int(c[i])].copy() for i in range(len(r))]
         self._check(self.lib.sonic_fetch_rows(self.h, len(r), _p(r), _p(c), _p(out), ld))
         return [out[i, :int(c[i])].copy() for i in range(len(r))]
 
@@ -585,11 +606,12 @@ class Engine:
         self._check(self.lib.sonic_wait(self.h, int(block), C.byref(busy)))
         return not busy.value
 
-    def fetch_tokens(self, R: int, out_ld: int):
+    def fetch_tokens(self, R: int, out_ld: int, want_logprobs: bool = False):
         out = np.zeros((R, out_ld), np.int32)
         out_len = np.zeros(R, np.int32)
         self._check(self.lib.sonic_fetch_tokens(self.h, _p(out), out_ld, _p(out_len), None))
-        return [out[r, : out_len[r]].copy() for r in range(R)]
+        res = [out[r, : out_len[r]].copy() for r in range(R)]
+        return (res, self._fetch_logprobs(out_len, out_ld)) if want_logprobs else res
 
     def timings(self) -> Dict[str, float]:
         t = SonicTimings()
@@ -651,6 +673,8 @@ def _bench_skinny(self, M: int, N: int, K: int, variant: int, iters: int = 50) -
 
 def _set_option(self, key: str, value: int):
     self._check(self.lib.sonic_set_option(self.h, key.encode(), value))
+    if key == "token_logprobs":
+        self.token_logprobs = bool(value)        # (a slot created from now on copies it, in the library and here)
 
 
 def _debug_ktrace(self) -> np.ndarray:
@@ -692,6 +716,19 @@ def _test_greedy(self, slabs, B: int, want_logits: bool = False):
     lg = np.zeros((B, V), np.float32) if want_logits else None
     self._check(self.lib.sonic_test_greedy(self.h, _p(s), ks, mpad, V, B, _p(tok), _p(lg)))
     return tok, lg
+
+
+def _test_greedy_lp(self, slabs, B: int, force_ids=None):
+    """sonic_test_greedy through greedy_kernel<T, true>: slabs [ksplit][mpad][V] fp32 -> (token per row [B], logits [B][V], log-probability of the
+    emitted token [B]); force_ids [B]: the token every row emits instead of its argmax"""
+    s = np.ascontiguousarray(slabs, np.float32)
+    ks, mpad, V = s.shape
+    tok = np.zeros(B, np.int32)
+    lg = np.zeros((B, V), np.float32)
+    lp = np.full(B, np.nan, np.float32)
+    f = np.ascontiguousarray(force_ids, np.int32) if force_ids is not None else None
+    self._check(self.lib.sonic_test_greedy_lp(self.h, _p(s), ks, mpad, V, B, _p(f), _p(tok), _p(lg), _p(lp)))
+    return tok, lg, lp
 
 
 def _test_linear_int8(self, X, W, bias=None, resid=None, group_rows=None, epi=EPI_BIAS):
@@ -750,6 +787,7 @@ Engine.test_prefill_attention = _test_prefill_attention
 Engine.test_linear_int8 = _test_linear_int8
 Engine.set_forced_ids = _set_forced_ids
 Engine.test_greedy = _test_greedy
+Engine.test_greedy_lp = _test_greedy_lp
 Engine.test_skinny_gu = _test_skinny_gu
 Engine.debug_read = _debug_read
 Engine.debug_ktrace = _debug_ktrace

@@ -43,10 +43,12 @@ class ContinuousPipeline:
         for d in self.decoders:
             d.service_end()
 
-    def run(self, n_batches: int, prefill: Callable[[Any], None], check: Optional[Callable[[int, np.ndarray], bool]] = None) -> dict:
+    def run(self, n_batches: int, prefill: Callable[[Any], None], check: Optional[Callable[[int, np.ndarray], bool]] = None,
+            want_logprobs: bool = False) -> dict:
         """n_batches batches of `block` requests through the pipeline.  prefill(slot): run the slot's staged batch up to its first tokens
         (Engine.prefill); it may return a tag that names the batch.  check(i, ids) - or check(i, ids, tag) for a tagged batch - for row i of
-        every finished batch (returns False for a wrong row).  Returns wall time and counts."""
+        every finished batch (returns False for a wrong row).  want_logprobs (engine option token_logprobs on every handle): the rows are
+        fetched with their log-probabilities and check gets the pair (ids, logprobs) in place of ids.  Returns wall time and counts."""
         ready: "queue.Queue" = queue.Queue()
         lock = threading.Lock()
         state = {"todo": n_batches, "done": 0, "bad": 0, "steps": 0}
@@ -110,7 +112,10 @@ class ContinuousPipeline:
                     for b, va in list(occupied.items()):
                         if b in done_blocks:
                             bad = 0
-                            got = d.fetch_rows(self.blocks[b], [int(nn[r]) for r in self.blocks[b]])
+                            if want_logprobs:
+                                got = list(zip(*d.fetch_rows(self.blocks[b], [int(nn[r]) for r in self.blocks[b]], want_logprobs=True)))
+                            else:
+                                got = d.fetch_rows(self.blocks[b], [int(nn[r]) for r in self.blocks[b]])
                             for i, ids in enumerate(got):
                                 if check is not None and not (check(i, ids) if tags[b] is None else check(i, ids, tags[b])):
                                     bad += 1
@@ -162,8 +167,9 @@ class NativePipeline:
         return (self.lib.sonic_pipeline_last_error(self.h) or b"").decode()
 
     def submit(self, prompts: Sequence[Sequence[int]], max_new: Sequence[int], segments: Optional[Sequence[np.ndarray]] = None,
-               req_win: Optional[Sequence[int]] = None) -> int:
-        """One batch of len(prompts) <= block requests.  segments: int16 PCM windows and / or engine.RingSlice ranges of device rings (staged by the pipeline's prefill thread), or None = the
+               req_win: Optional[Sequence[int]] = None, want_logprobs: bool = False) -> int:
+        """want_logprobs (engine option token_logprobs on every handle): wait() then returns (ids, log-probabilities), sonic_pipeline_submit_lp.
+        One batch of len(prompts) <= block requests.  segments: int16 PCM windows and / or engine.RingSlice ranges of device rings (staged by the pipeline's prefill thread), or None = the
         batch is what every prefill handle has staged already.  Returns the ticket."""
         from .engine import Engine, RingSlice, _p
         ids, poffs = Engine._pack_prompts(prompts)
@@ -176,7 +182,18 @@ class NativePipeline:
         pcm = offs = None
         W = 0
         t = C.c_int64(0)
-        if segments is not None and any(isinstance(s, RingSlice) for s in segments):
+        lp = np.full((R, ld), np.nan, np.float32) if want_logprobs else None
+        if want_logprobs:
+            rings = start = n = None
+            if segments is not None and any(isinstance(s, RingSlice) for s in segments):
+                pcm, offs, rings, start, n = self.decoders[0]._pack_mixed(segments)
+                W = len(segments)
+            elif segments is not None:
+                pcm, offs = self.decoders[0]._pack_pcm(segments)
+                W = len(segments)
+            rc = self.lib.sonic_pipeline_submit_lp(self.h, _p(pcm), _p(offs), rings, _p(start), _p(n), W, _p(rw), R, _p(ids), _p(poffs), _p(mn),
+                                                   _p(out), ld, _p(out_len), _p(lp), C.byref(t))
+        elif segments is not None and any(isinstance(s, RingSlice) for s in segments):
             # windows that are ranges of device rings (file mode, streams): staged by sonic_stage_mixed on the prefill thread
             pcm, offs, rings, start, n = self.decoders[0]._pack_mixed(segments)
             W = len(segments)
@@ -189,16 +206,17 @@ class NativePipeline:
             rc = self.lib.sonic_pipeline_submit(self.h, _p(pcm), _p(offs), W, _p(rw), R, _p(ids), _p(poffs), _p(mn), _p(out), ld, _p(out_len), C.byref(t))
         if rc != 0:
             raise RuntimeError(self._err() or f"sonic_pipeline_submit failed with status {rc}")
-        self._keep[t.value] = (pcm, offs, out, out_len)
+        self._keep[t.value] = (pcm, offs, out, out_len, lp)
         return int(t.value)
 
     def wait(self, ticket: int) -> List[np.ndarray]:
         """Blocks until the batch is complete; returns its rows' token ids.  Raises what the batch failed with."""
         rc = self.lib.sonic_pipeline_wait(self.h, int(ticket))
-        _, _, out, out_len = self._keep.pop(ticket)
+        _, _, out, out_len, lp = self._keep.pop(ticket)
         if rc != 0:
             raise RuntimeError(self._err() or f"batch failed with status {rc}")
-        return [out[r, : out_len[r]].copy() for r in range(len(out_len))]
+        rows = [out[r, : out_len[r]].copy() for r in range(len(out_len))]
+        return (rows, [lp[r, : out_len[r]].copy() for r in range(len(out_len))]) if lp is not None else rows
 
     def stats(self) -> dict:
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_int32(0)
