@@ -47,6 +47,9 @@
  *                              "tentative" and "high": every emitted token's log-probability, on every scheduler
  *                                                                                                        backend/connection_manager.py:159,274
  *   sonic_test_greedy_lp       (test hook of the kernel behind them)                                     backend/connection_manager.py:159,274
+ *   sonic_set_generation       the LogitsProcessorList that generate() builds from the checkpoint's generation_config.json
+ *                              (repetition_penalty, no_repeat_ngram_size, suppress_tokens)               backend/asr.py:411-422
+ *   sonic_get_generation / sonic_test_greedy_guard   (what is in force; test hook of the kernel behind it)
  */
 #ifndef SONIC_HIP_H
 #define SONIC_HIP_H
@@ -215,6 +218,21 @@ SONIC_API int sonic_fetch_tokens(sonic_engine* e, int32_t* out_ids, int out_ld, 
  * written), valid whenever that call is.  Every fetch / submit form (sonic_fetch_logprobs, sonic_fetch_rows_lp, sonic_dispatch_next_lp,
  * sonic_pipeline_submit_lp) returns SONIC_ERR_INVALID, the message naming token_logprobs, while the option is off. */
 SONIC_API int sonic_fetch_logprobs(sonic_engine* e, float* out_lp, int out_ld);
+/* HF generate()'s logits processors for greedy decoding (generation/logits_process.py), applied inside the greedy kernel to the fp32 scores the argmax
+ * compares, in HF's order.  input_ids = the request's prompt ids (audio placeholders included) followed by every id emitted so far, forced ids included:
+ *   repetition_penalty p   every id that occurs in input_ids: s = s < 0 ? s * p : s / p, once (fp32 multiply, correctly rounded fp32 divide); 1.0 = none
+ *   no_repeat_ngram_size n every id that followed an earlier occurrence of the last n - 1 ids becomes -inf (n = 1: every id seen); 0 = none
+ *   suppress_tokens        the listed ids are -inf at every step; at most 256 ids, n_suppress = 0 = none
+ * A row whose scores are all -inf emits token 0.  step_logits stay the raw logits (HF output_logits); with option token_logprobs the log-probabilities are
+ * those of the processed scores (HF compute_transition_scores over `scores`; a banned forced id gives -inf).  The neutral values switch everything off:
+ * the engine then launches exactly what it launched before.  Set it on the owner before its slots are created (they copy it); sonic_splice_rows refuses
+ * a source whose values differ from the destination's.  SONIC_ERR_INVALID: p not finite or <= 0, n outside 0 .. 64, more than 256 ids, an id outside the
+ * vocabulary, or the handle has work in hand (a prefilled batch whose decode loop has not ended, an asynchronous run, a continuous loop).
+ * sonic_set_option keys "gen_repetition_penalty_milli", "gen_no_repeat_ngram_size", "gen_suppress_token" (one id, -1 = none) set one value each for
+ * drivers that only pass integers. */
+SONIC_API int sonic_set_generation(sonic_engine* e, float repetition_penalty, int no_repeat_ngram_size, const int32_t* suppress, int n_suppress);
+/* the values in force on this handle; at most `cap` ids are copied to suppress, *n_suppress is their full count (any pointer may be NULL) */
+SONIC_API int sonic_get_generation(sonic_engine* e, float* repetition_penalty, int32_t* no_repeat_ngram_size, int32_t* suppress, int cap, int32_t* n_suppress);
 /* sonic_run_staged without blocking the caller: the arguments are copied, a worker thread owned by the handle runs the batch, the call
  * returns at once (the reference's counterpart is loop.run_in_executor(None, asr_model.transcribe, ...), backend/main.py:616-624).  One
  * outstanding run per handle; until sonic_wait has returned the handle takes no other call (ring appends excepted).
@@ -368,6 +386,11 @@ SONIC_API int sonic_test_greedy(sonic_engine* e, const float* slabs, int ksplit,
  * log-probability of the token each row emits; force_ids (optional, [B]): that token instead of the argmax, as under sonic_set_forced_ids */
 SONIC_API int sonic_test_greedy_lp(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const int32_t* force_ids, int32_t* tok_out,
                                    float* logits_out, float* lp_out);
+/* the same launch through the guard instantiation (greedy_kernel<T, LP, true>): row b decides with the history hist[b * hist_ld .. + hist_len[b]) and the three
+ * parameters of sonic_set_generation; logits_out stays the raw logits, lp_out (optional) is over the processed scores, force_ids (optional) as above */
+SONIC_API int sonic_test_greedy_guard(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const int32_t* hist, int hist_ld, const int32_t* hist_len,
+                                      float repetition_penalty, int no_repeat_ngram_size, const int32_t* suppress, int n_suppress, const int32_t* force_ids,
+                                      int32_t* tok_out, float* logits_out, float* lp_out);
 SONIC_API int sonic_test_attention(sonic_engine* e, const float* q, const float* k, const float* v, float* out,
                          int B, int Tq, int Tk, int Hq, int Hkv, int hd, int causal);
 SONIC_API int sonic_test_decode_attention(sonic_engine* e, const float* q, const float* k, const float* v, float* out,

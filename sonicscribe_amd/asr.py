@@ -214,8 +214,14 @@ class AudioStream:
 class ASRModel:
     def __init__(self, checkpoint_dir: str, device: str = "cuda", mode: str = "native",
                  cpu_threads: Optional[int] = None, cpu_interop_threads: Optional[int] = None,
-                 *, max_batch: int = 32, max_ctx: int = 1024, slots: int = DEFAULT_SLOTS, continuous: bool = DEFAULT_CONTINUOUS, decoders: int = 1, bulk: bool = False, native_dispatch: Optional[bool] = None, token_logprobs: bool = False, _dims: Optional[ModelDims] = None,
-                 _synthetic_seed: Optional[int] = None, _allow_synthetic_prompt: bool = False, _options: Optional[Dict[str, int]] = None):
+                 *, max_batch: int = 32, max_ctx: int = 1024, slots: int = DEFAULT_SLOTS, continuous: bool = DEFAULT_CONTINUOUS, decoders: int = 1, bulk: bool = False, native_dispatch: Optional[bool] = None, token_logprobs: bool = False,
+                 repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None, _dims: Optional[ModelDims] = None,
+                 _synthetic_seed: Optional[int] = None, _allow_synthetic_prompt: bool = False, _options: Optional[Dict[str, int]] = None,
+                 _engine_mode: Optional[int] = None):
+        """The reference's ASRModel surface over the HIP engine.  `repetition_penalty`, `no_repeat_ngram_size`, `suppress_tokens`: None = the value of the
+        checkpoint's generation_config.json, anything else overrides it (genconfig.py).  The arguments with a leading underscore are not part of the
+        supported surface: they exist for the test-suite and the benchmark and may change without notice.  `_engine_mode` in particular (an engine.MODE_*
+        value in place of the one `mode` selects) is unsupported outside the tests: MODE_F32 has no slots, so it needs slots=1, continuous=False."""
         if mode not in ["native", "int8"]:
             raise ValueError("mode must be either 'native' or 'int8'")            # asr.py:46-47
         dev = str(device)
@@ -232,11 +238,19 @@ class ASRModel:
         self.mode = mode
         self.model_dtype = "bfloat16" if mode == "native" else "float16"                     # asr.py:61
         emode = MODE_NATIVE if mode == "native" else MODE_INT8
+        if _engine_mode is not None:                 # tests only, unsupported (docstring): another kind behind the same façade
+            emode = int(_engine_mode)
         self.checkpoint_dir = Path(checkpoint_dir)
         self.target_sr = 16000
         self.is_glm_asr = True
         self.processor = None
         self.models: List[Engine] = []
+        # The checkpoint's generation_config.json, as generate() would merge it into the reference's call (asr.py:411-422): repetition_penalty,
+        # no_repeat_ngram_size and suppress_tokens run inside the greedy kernel; a field that would change a do_sample=False run and that the engine
+        # does not implement raises here, by name (genconfig.py).  None = the checkpoint's value; an explicit argument overrides it
+        from . import genconfig
+        file_guards = genconfig.GenerationGuards() if _synthetic_seed is not None else genconfig.load(str(checkpoint_dir))
+        self.generation_guards = file_guards.override(repetition_penalty, no_repeat_ngram_size, suppress_tokens)
         if _synthetic_seed is not None:
             self.dims = _dims or FULL
             for di in self.device_indices:
@@ -271,6 +285,9 @@ class ASRModel:
                 eng.set_option(k, int(v))
             if self.token_logprobs:
                 eng.set_option("token_logprobs", 1)
+            if self.generation_guards.active:
+                g = self.generation_guards
+                eng.set_generation(g.repetition_penalty, g.no_repeat_ngram_size, g.suppress_tokens)
         self.model = self.models[0]                  # main.py:84-86 checks and deletes `.model`
         # continuous: `decoders` handles per replica run a greedy loop over max_batch rows each, the other handles prefill (>= 1).  Streaming:
         # decoders=1, slots=2.  Bulk transcription of many segments: max_batch=64, decoders=3, slots=4 (the bench's pipeline shape since round 5; decoders=2, slots=3 before).
@@ -417,6 +434,9 @@ class ASRModel:
                      "gpu_memory_total_mb": di["total_bytes"] / 1024 ** 2})
         info.update({"engine": "sonicscribe_amd/gfx950", "replicas": len(self.__dict__.get("models", [])), "slots_per_replica": self.__dict__.get("slots", 1), "continuous": self.__dict__.get("continuous", False), "bulk": self.__dict__.get("bulk", False),
                      "weights_mb": self.model.weight_bytes() / 1024 ** 2 if hasattr(self, "model") else 0.0})
+        g = self.__dict__.get("generation_guards")
+        if g is not None:                            # the logits processors in force: the checkpoint's generation_config.json unless the constructor overrode it
+            info.update(g.as_dict())
         return info
 
     def close(self):

@@ -555,8 +555,22 @@ __global__ void assemble_embeds_kernel(const int* src, const bf16_t* table, cons
 // 16) terms.  Threads are brought to their wave's maximum and added by the xor butterfly, waves to the block's maximum and added as a fixed tree by
 // thread 0: one block, one order, whatever the grid.  exp is v_exp_f32 of the argument times log2(e); the closing log and subtraction are fp64.
 // LP = false is the kernel as it was: everything below that belongs to the sum sits behind `if constexpr (LP)`.
+// GUARD (sonic_set_generation): HF's repetition_penalty, no_repeat_ngram_size and suppress_tokens on the fp32 scores the argmax compares.
+// The block first builds two vocabulary bitmaps in LDS from the row's history hist[b][0 .. kv_len[b]) (prompt ids, then every id emitted): "seen" (ids of
+// the history) and "banned" (continuations of earlier occurrences of the last n - 1 ids, and the suppress list).  Integer ORs: no order in them.  The
+// loop then reads the 4 bits of each map that belong to its f32x4 group: a seen score becomes s < 0 ? s * p : s / p (fp32 multiply, correctly rounded
+// fp32 divide), a banned one -inf, in that order, behind the dump (raw logits) and ahead of the compare and the LP sum.  Thread 0 appends the emitted
+// id at hist[b][kv_len[b]].  A row whose scores are all -inf emits token 0 (torch.argmax of equal values).  GUARD = false is the kernel as it was.
+extern __shared__ unsigned g_bits[];
+__device__ __forceinline__ float guard_score(float r, unsigned seen, unsigned banned, float p) {
+    if (seen & 1u) r = r < 0.f ? r * p : __fdiv_rn(r, p);
+    return (banned & 1u) ? -INFINITY : r;
+}
+__device__ __forceinline__ void guard_set(unsigned* map, int id, int V) {
+    if ((unsigned)id < (unsigned)V) atomicOr(&map[id >> 5], 1u << (id & 31));
+}
 __device__ __forceinline__ float lp_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-template <typename T, bool LP>
+template <typename T, bool LP, bool GUARD = false>
 __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
     typedef typename ET<T>::v8 V8;
     __shared__ float sv[16];
@@ -573,6 +587,26 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
     // embedding row it was one more dependent round trip)
     f32x4 gw0 = {0.f, 0.f, 0.f, 0.f}, gw1 = {0.f, 0.f, 0.f, 0.f};
     if (a.y && (a.d >> 3) <= 1024 && tid < (a.d >> 3)) { gw0 = *(const f32x4*)(a.norm_w + tid * 8); gw1 = *(const f32x4*)(a.norm_w + tid * 8 + 4); }
+    [[maybe_unused]] unsigned* g_seen = nullptr; [[maybe_unused]] unsigned* g_ban = nullptr;
+    if constexpr (GUARD) {
+        const int nw = (a.V + 31) >> 5;
+        g_seen = g_bits; g_ban = g_bits + nw;
+        for (int w = tid; w < 2 * nw; w += 1024) g_bits[w] = 0u;
+        __syncthreads();
+        const int* h = a.hist + (long)b * a.hist_ld;
+        const int len = min(max(a.kv_len[b], 0), a.hist_ld), n = a.ngram;
+        for (int j = tid; j < len; j += 1024) guard_set(g_seen, h[j], a.V);
+        if (n > 0) {                              // every n-gram h[j .. j + n) of the history whose first n - 1 ids are the history's last n - 1 bans its last id
+            const int* last = h + len - (n - 1);  // (read only when an n-gram exists: j + n <= len)
+            for (int j = tid; j + n <= len; j += 1024) {
+                bool m = true;
+                for (int k = 0; k < n - 1; ++k) m = m && h[j + k] == last[k];
+                if (m) guard_set(g_ban, h[j + n - 1], a.V);
+            }
+        }
+        for (int j = tid; j < a.n_suppress; j += 1024) guard_set(g_ban, a.suppress[j], a.V);
+        __syncthreads();
+    }
     // four strides per trip with all their slab loads issued first (the rolled form paid one L2 round trip per stride)
     constexpr int U = 4;
     for (int i0 = tid * 4; i0 < a.V; i0 += 1024 * 4 * U) {
@@ -590,10 +624,13 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
             f32x4 t = v[u];
             if (a.ksplit > 1) t += w[u];
             for (int ks = 2; ks < a.ksplit; ++ks) t += *(const f32x4*)(lg + ks * ks_stride + i);
+            [[maybe_unused]] unsigned sb = 0u, bb = 0u;      // GUARD: the group's 4 bits of each map (i is a multiple of 4)
+            if constexpr (GUARD) { sb = g_seen[i >> 5] >> (i & 31); bb = g_ban[i >> 5] >> (i & 31); }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float r = rT<T>(t[j]);        // logits are T in the reference, compared as fp32
+                float r = rT<T>(t[j]);              // logits are T in the reference, compared as fp32
                 if (dump) dump[i + j] = r;
+                if constexpr (GUARD) r = guard_score(r, sb >> j, bb >> j, a.rep_penalty);
                 if (r > best) { best = r; bi = i + j; }   // strict > keeps the first maximum within a thread
                 if constexpr (LP) v[u][j] = r;
             }
@@ -639,6 +676,7 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
                 for (int w = 0; w < h; ++w) q[w] = q[2 * w] + q[2 * w + 1];
             lp_sum = q[0];
         }
+        if constexpr (GUARD) if (bi == 0x7fffffff) bi = 0;      // every score -inf: the first of equal values
         int tok = bi;
         const int fin = a.finished[b];
         bool running = false;
@@ -653,9 +691,11 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
                     if (a.ksplit > 1) f += lg[ks_stride + tok];
                     for (int ks = 2; ks < a.ksplit; ++ks) f += lg[ks * ks_stride + tok];
                     lt = rT<T>(f);
+                    if constexpr (GUARD) lt = guard_score(lt, g_seen[tok >> 5] >> (tok & 31), g_ban[tok >> 5] >> (tok & 31), a.rep_penalty);
                 }
                 a.out_lp[(long)b * a.out_ld + a.n_new[b]] = (float)(((double)lt - (double)best) - log((double)lp_sum));
             }
+            if constexpr (GUARD) { const int pos = a.kv_len[b]; if (pos >= 0 && pos < a.hist_ld) a.hist[(long)b * a.hist_ld + pos] = tok; }   // the token's position
             const int nn = a.n_new[b] + 1;
             a.n_new[b] = nn;
             bool stop = nn >= a.max_new[b];
@@ -800,7 +840,30 @@ void launch_rope_append(const RopeAppendArgs& a, bool slab, hipStream_t s) {
 void launch_assemble_embeds(const int* src, const bf16_t* table, const bf16_t* audio, bf16_t* x, int n_tok, int d, hipStream_t s) {
     if (n_tok > 0) hipLaunchKernelGGL(assemble_embeds_kernel, dim3(n_tok), dim3(256), 0, s, src, table, audio, x, n_tok, d);
 }
+// a request's prompt ids into its history row (option generation guards): token t of the packed prompt plan is position tok_pos[t] of request
+// tok_seq[t]; audio positions (src < 0) hold the placeholder id, as in HF's input_ids
+__global__ void hist_prompt_kernel(const int* src, const int* tok_seq, const int* tok_pos, int n_tok, int audio_id, int* hist, int hist_ld) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_tok) return;
+    const int s = src[t], r = tok_seq[t], p = tok_pos[t];
+    if (r >= 0 && r < 64 && p >= 0 && p < hist_ld) hist[(long)r * hist_ld + p] = s >= 0 ? s : audio_id;
+}
+void launch_hist_prompt(const int* src, const int* tok_seq, const int* tok_pos, int n_tok, int audio_id, int* hist, int hist_ld, hipStream_t s) {
+    if (n_tok > 0) hipLaunchKernelGGL(hist_prompt_kernel, dim3((n_tok + 255) / 256), dim3(256), 0, s, src, tok_seq, tok_pos, n_tok, audio_id, hist, hist_ld);
+}
+size_t greedy_guard_lds(int V) { return (size_t)2 * ((V + 31) / 32) * 4; }
 void launch_greedy(const GreedyArgs& a, hipStream_t s) {
+    if (a.hist) {                                                                                                // generation guards: the GUARD instantiations, two bitmaps of dynamic LDS
+        const size_t lds = greedy_guard_lds(a.V);
+        if (a.out_lp) {
+            if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, true, true>), dim3(a.B), dim3(1024), lds, s, a); return; }
+            DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, true, true>), dim3(a.B), dim3(1024), lds, s, a));
+            return;
+        }
+        if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, false, true>), dim3(a.B), dim3(1024), lds, s, a); return; }
+        DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, false, true>), dim3(a.B), dim3(1024), lds, s, a));
+        return;
+    }
     if (a.out_lp) {                                                                                              // token_logprobs: the LP instantiation
         if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, true>), dim3(a.B), dim3(1024), 0, s, a); return; }
         DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, true>), dim3(a.B), dim3(1024), 0, s, a));

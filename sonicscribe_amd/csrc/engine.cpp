@@ -361,6 +361,63 @@ int lp_check(sonic_engine* e, const char* who) {
 // dispatch.cpp / pipeline.cpp (same library, not exported): does this handle produce log-probabilities
 extern "C" int engine_token_logprobs_on(sonic_engine* e) { return e && e->opt_token_logprobs && e->out_lp ? 1 : 0; }
 
+// ---- generation guards: validation, the history / suppress buffers on first use, the upload.  The caller holds the lock and has made sure nothing is in flight.
+#define GEN_MAX_SUPPRESS 256
+int gen_apply(sonic_engine* e, float penalty, int ngram, const int32_t* suppress, int n_suppress) {
+    if (!(penalty > 0.f) || !std::isfinite(penalty)) return fail(e, SONIC_ERR_INVALID, "sonic_set_generation: repetition_penalty must be a finite value > 0 (got %g)", (double)penalty);
+    if (ngram < 0 || ngram > 64) return fail(e, SONIC_ERR_INVALID, "sonic_set_generation: no_repeat_ngram_size %d is outside 0 .. 64", ngram);
+    if (n_suppress < 0 || n_suppress > GEN_MAX_SUPPRESS || (n_suppress > 0 && !suppress))
+        return fail(e, SONIC_ERR_INVALID, "sonic_set_generation: suppress_tokens holds %d ids (at most %d)", n_suppress, GEN_MAX_SUPPRESS);
+    for (int i = 0; i < n_suppress; ++i)
+        if (suppress[i] < 0 || suppress[i] >= e->d.vocab) return fail(e, SONIC_ERR_INVALID, "sonic_set_generation: suppressed token id %d out of vocabulary (%d)", suppress[i], e->d.vocab);
+    const bool on = penalty != 1.0f || ngram > 0 || n_suppress > 0;
+    if (on && greedy_guard_lds(e->d.vocab) > 60000) return fail(e, SONIC_ERR_UNSUPPORTED, "sonic_set_generation: a vocabulary of %d ids does not fit the guard bitmaps", e->d.vocab);
+    HIPC(e, hipSetDevice(e->device));
+    HIPC(e, stream_sync(e));
+    if (on && !e->hist) { TRY(dalloc(e, &e->hist, (size_t)64 * e->max_ctx)); TRY(dalloc(e, &e->gen_suppress_d, (size_t)GEN_MAX_SUPPRESS)); HIPC(e, stream_sync(e)); }
+    if (n_suppress > 0) HIPC(e, h2d(e, e->gen_suppress_d, suppress, (size_t)n_suppress * 4));
+    e->gen_penalty = penalty; e->gen_ngram = ngram; e->gen_suppress.assign(suppress, suppress + n_suppress); e->gen_on = on;
+    drop_graphs(e);                                      // the greedy kernel and its arguments are part of every captured chunk
+    return SONIC_OK;
+}
+// Both ways in (sonic_set_generation, the gen_* keys of sonic_set_option) ask this first, under the handle's lock: SONIC_ERR_INVALID while the handle has work in
+// hand.  A prefilled batch counts until its decode loop has ended or every one of its rows has been handed to a continuous loop (sonic_splice_rows): a prefill
+// slot whose rows were all spliced away is free again.  (No path takes e->mu while it holds a_mu, so the short a_mu section below cannot deadlock.)
+int gen_busy(sonic_engine* e, const char* who) {
+    { std::lock_guard<std::mutex> lk(e->a_mu); if (e->a_pending || e->a_running) return fail(e, SONIC_ERR_INVALID, "%s: an asynchronous run of this handle is in flight", who); }
+    if (e->svc_on) return fail(e, SONIC_ERR_INVALID, "%s: this handle is decoding continuously (sonic_service_end first)", who);
+    if (e->R >= 1 && e->greedy_calls >= 1 && e->steps_run + 1 < e->max_steps) {
+        const uint64_t all = e->R >= 64 ? ~0ull : (1ull << e->R) - 1;
+        if ((e->spliced & all) != all)
+            return fail(e, SONIC_ERR_INVALID, "%s: the handle holds a prefilled batch of %d requests whose rows are still running (its decode loop has not ended and they were not all handed to a continuous loop)", who, e->R);
+    }
+    return SONIC_OK;
+}
+// HF generate()'s logits processors for greedy decoding, as the checkpoint's generation_config.json (or the caller) sets them: repetition_penalty (1.0 = none),
+// no_repeat_ngram_size (0 = none), suppress_tokens (n_suppress = 0: none; at most 256 ids).  The neutral values switch the guards off: the engine then launches
+// the kernels it launched before.  Set it on the owner before slots are created (they copy it).  SONIC_ERR_INVALID for a value out of range, and while the handle
+// has work in hand (gen_busy): a prefilled batch whose decode loop has not ended, an asynchronous run, a continuous loop (sonic_service_begin).  The first check
+// below is the same one without the engine lock, which an asynchronous run holds until it ends: the call answers at once instead of waiting for it.
+extern "C" int sonic_set_generation(sonic_engine* e, float repetition_penalty, int no_repeat_ngram_size, const int32_t* suppress, int n_suppress) {
+    if (!e) return SONIC_ERR_INVALID;
+    { std::lock_guard<std::mutex> lk(e->a_mu); if (e->a_pending || e->a_running) return fail(nullptr, SONIC_ERR_INVALID, "sonic_set_generation: an asynchronous run of this handle is in flight"); }
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipGetLastError();
+    TRY(gen_busy(e, "sonic_set_generation"));
+    return gen_apply(e, repetition_penalty, no_repeat_ngram_size, suppress, n_suppress);
+}
+// what is in force on this handle (get_model_info, tests): *n_suppress = ids copied to suppress[0 .. cap)
+extern "C" int sonic_get_generation(sonic_engine* e, float* repetition_penalty, int32_t* no_repeat_ngram_size, int32_t* suppress, int cap, int32_t* n_suppress) {
+    if (!e) return SONIC_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (repetition_penalty) *repetition_penalty = e->gen_penalty;
+    if (no_repeat_ngram_size) *no_repeat_ngram_size = e->gen_ngram;
+    const int n = (int)e->gen_suppress.size();
+    if (n_suppress) *n_suppress = n;
+    if (suppress) for (int i = 0; i < n && i < cap; ++i) suppress[i] = e->gen_suppress[i];
+    return SONIC_OK;
+}
+
 extern "C" int sonic_create(const sonic_dims* dims, int device_id, int mode, int max_batch, int max_ctx, sonic_engine** out) {
     if (!dims || !out) return fail(nullptr, SONIC_ERR_INVALID, "null argument");
     *out = nullptr;
@@ -418,6 +475,7 @@ extern "C" int sonic_slot_create(sonic_engine* parent, sonic_engine** out) {
     e->opt_decode_chunk = root->opt_decode_chunk; e->opt_no_pre_norm = root->opt_no_pre_norm; e->opt_decode_gemv = root->opt_decode_gemv;
     e->opt_token_logprobs = root->opt_token_logprobs;
     if (e->opt_token_logprobs && (s = lp_alloc(e)) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }
+    if (root->gen_on && (s = gen_apply(e, root->gen_penalty, root->gen_ngram, root->gen_suppress.data(), (int)root->gen_suppress.size())) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }
     e->weight_bytes = 0; e->finalized = true; e->owner = root;
     root->slots.push_back(e);
     *out = e;

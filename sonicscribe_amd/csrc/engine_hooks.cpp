@@ -432,7 +432,7 @@ static const OptRow OPTIONS[] = {
 };
 #undef ENG
 #undef LOP
-static void drop_graphs(sonic_engine* e) { for (auto& g : e->graphs) (void)hipGraphExecDestroy(g.second); e->graphs.clear(); }
+void drop_graphs(sonic_engine* e) { for (auto& g : e->graphs) (void)hipGraphExecDestroy(g.second); e->graphs.clear(); }
 extern "C" int sonic_set_option(sonic_engine* e, const char* key, int value) {
     if (!e || !key) return SONIC_ERR_INVALID;
     std::lock_guard<std::mutex> lk(e->mu);
@@ -445,6 +445,17 @@ extern "C" int sonic_set_option(sonic_engine* e, const char* key, int value) {
         if (r.drop_graphs) drop_graphs(e);
         if (r.field == &sonic_engine::opt_token_logprobs && v) TRY(lp_alloc(e));      // first use: 64 x out_cap fp32
         return SONIC_OK;
+    }
+    // the generation guards one integer at a time, for drivers that only speak key = value (bench.py --opt; tools/ab_generation_guards.sh): the penalty in
+    // thousandths, the n-gram size, ONE suppressed id (-1: none).  Same rules and refusals as sonic_set_generation; the other two values stay as they are
+    if (!strncmp(key, "gen_", 4)) {
+        float p = e->gen_penalty; int n = e->gen_ngram; std::vector<int> sup = e->gen_suppress;
+        if (!strcmp(key, "gen_repetition_penalty_milli")) p = (float)((double)value / 1000.0);
+        else if (!strcmp(key, "gen_no_repeat_ngram_size")) n = value;
+        else if (!strcmp(key, "gen_suppress_token")) { sup.clear(); if (value >= 0) sup.push_back(value); }
+        else return fail(e, SONIC_ERR_INVALID, "unknown option %s", key);
+        TRY(gen_busy(e, key));
+        return gen_apply(e, p, n, sup.data(), (int)sup.size());
     }
     // the two knobs that do device work
     if (!strcmp(key, "ktrace")) {              // diagnostics: record in-kernel timestamps of decoder layer `value` (-1: off); sonic_debug_ktrace reads them
@@ -534,7 +545,11 @@ extern "C" int sonic_test_linear_int8(sonic_engine* e, const float* X, const flo
 // the bf16-rounded slab sum, HF:generation/utils.py:2925 / torch.argmax semantics) and, optionally, the bf16 logits it compared.
 // sonic_test_greedy_lp: the same launch through greedy_kernel<T, true>, optionally under teacher forcing (force_ids[B]: the token every row emits
 // instead of its argmax); lp_out[B] = the emitted token's log-probability.
-static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const int32_t* force_ids, int32_t* tok_out, float* logits_out, float* lp_out) {
+// sonic_test_greedy_guard: the launch through greedy_kernel<T, LP, true> (LP when lp_out is given): row b's history is hist[b * hist_ld .. + hist_len[b]), the three
+// parameters are sonic_set_generation's; logits_out stays the raw logits.
+struct GuardTest { const int32_t* hist; int hist_ld; const int32_t* hist_len; float penalty; int ngram; const int32_t* suppress; int n_suppress; };
+static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const int32_t* force_ids, int32_t* tok_out, float* logits_out, float* lp_out,
+                       const GuardTest* gt = nullptr) {
     if (ksplit < 1 || ksplit > 8 || B < 1 || B > 64 || mpad < B || V < 4 || V % 4) return fail(e, SONIC_ERR_INVALID, "bad greedy test shape");
     if (force_ids) for (int b = 0; b < B; ++b) if (force_ids[b] < 0 || force_ids[b] >= V) return fail(e, SONIC_ERR_INVALID, "forced id %d out of vocabulary", force_ids[b]);
     TmpBuf tb(e->st);
@@ -549,6 +564,28 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
     std::vector<int> h(64 * 8 + 4, 0);
     for (int b = 0; b < 64; ++b) { h[64 * 2 + b] = 1; h[64 * 4 + b] = 4; }       // kv_len = 1, max_new = 4
     h[64 * 8] = B;
+    int *ghist = nullptr, *gsup = nullptr; int gld = 0;
+    if (gt) {                                                                     // the history rows with room for the appended id; kv_len = the history's length
+        if (gt->hist_ld < 0 || gt->hist_ld > (1 << 20) || !gt->hist_len || (gt->hist_ld > 0 && !gt->hist) || !(gt->penalty > 0.f) || !std::isfinite(gt->penalty) || gt->ngram < 0 || gt->ngram > 64 ||
+            gt->n_suppress < 0 || gt->n_suppress > 256 || (gt->n_suppress > 0 && !gt->suppress) || greedy_guard_lds(V) > 60000)
+            return fail(e, SONIC_ERR_INVALID, "bad greedy guard test arguments");
+        gld = gt->hist_ld + 1;
+        std::vector<int> hh((size_t)B * gld, 0);
+        for (int b = 0; b < B; ++b) {
+            if (gt->hist_len[b] < 0 || gt->hist_len[b] > gt->hist_ld) return fail(e, SONIC_ERR_INVALID, "history length %d outside 0 .. %d", gt->hist_len[b], gt->hist_ld);
+            for (int j = 0; j < gt->hist_len[b]; ++j) {
+                const int id = gt->hist[(size_t)b * gt->hist_ld + j];
+                if (id < 0 || id >= V) return fail(e, SONIC_ERR_INVALID, "history id %d out of vocabulary", id);
+                hh[(size_t)b * gld + j] = id;
+            }
+            h[64 * 2 + b] = gt->hist_len[b];
+        }
+        for (int i = 0; i < gt->n_suppress; ++i) if (gt->suppress[i] < 0 || gt->suppress[i] >= V) return fail(e, SONIC_ERR_INVALID, "suppressed id %d out of vocabulary", gt->suppress[i]);
+        ghist = tb.get<int>(hh.size()); gsup = tb.get<int>(256);
+        if (!ghist || !gsup) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+        HIPC(e, h2d(e, ghist, hh.data(), hh.size() * 4));
+        if (gt->n_suppress > 0) HIPC(e, h2d(e, gsup, gt->suppress, (size_t)gt->n_suppress * 4));
+    }
     HIPC(e, h2d(e, st, h.data(), h.size() * 4));
     if (fd) HIPC(e, h2d(e, fd, force_ids, (size_t)B * 4));
     GreedyArgs g{};
@@ -556,6 +593,7 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
     g.out_ids = ids; g.out_ld = 1; g.n_new = st; g.finished = st + 64; g.kv_len = st + 128; g.tok_pos = st + 192; g.max_new = st + 256;
     g.n_active = st + 512; g.n_eos = 0; g.pad_id = 0; g.logits_dump = dump; g.dump_stride_step = (long)B * V; g.step_counter = dump ? st + 320 : nullptr;
     g.out_lp = lp; g.force_ids = fd; g.force_ld = 1;
+    if (gt) { g.hist = ghist; g.hist_ld = gld; g.rep_penalty = gt->penalty; g.ngram = gt->ngram; g.suppress = gsup; g.n_suppress = gt->n_suppress; }
     launch_greedy(g, e->st);
     HIPC(e, stream_sync(e));
     HIPC(e, hipGetLastError());
@@ -576,6 +614,15 @@ extern "C" int sonic_test_greedy_lp(sonic_engine* e, const float* slabs, int ksp
     if (!e || !slabs || !tok_out || !lp_out) return SONIC_ERR_INVALID;
     ENTER(e);
     return test_greedy(e, slabs, ksplit, mpad, V, B, force_ids, tok_out, logits_out, lp_out);
+}
+
+extern "C" int sonic_test_greedy_guard(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const int32_t* hist, int hist_ld, const int32_t* hist_len,
+                                       float repetition_penalty, int no_repeat_ngram_size, const int32_t* suppress, int n_suppress, const int32_t* force_ids,
+                                       int32_t* tok_out, float* logits_out, float* lp_out) {
+    if (!e || !slabs || !tok_out || !hist_len) return SONIC_ERR_INVALID;
+    ENTER(e);
+    const GuardTest gt{hist, hist_ld, hist_len, repetition_penalty, no_repeat_ngram_size, suppress, n_suppress};
+    return test_greedy(e, slabs, ksplit, mpad, V, B, force_ids, tok_out, logits_out, lp_out, &gt);
 }
 
 extern "C" int sonic_test_skinny_gu(sonic_engine* e, const float* X, const float* Wgu_interleaved, float* act, int M, int N, int K) {

@@ -174,6 +174,12 @@ struct sonic_engine {
     int opt_decode_chunk = 2;      // token steps per captured graph = granularity of the early-stop check (sonic_set_option "decode_chunk")
     int opt_token_logprobs = 0;    // 1: every greedy launch also writes log_softmax(logits)[token] to out_lp (greedy_kernel<T, true>); set on the owner before
                                    // its slots exist (they copy it).  The decode loops keep their hipGraph form; graphs are cached per value
+    // generation guards (sonic_set_generation; greedy_kernel<T, LP, true>): HF's repetition_penalty / no_repeat_ngram_size / suppress_tokens inside the greedy
+    // kernel.  gen_on: any of them is set; set on the owner before its slots exist (they copy it).  hist[64][max_ctx]: every row's input_ids (prompt, then the emitted ids),
+    // written by the prefill and the greedy kernel, copied by the splice; allocated with gen_suppress_d[256] by the first gen_apply that switches a guard on
+    bool gen_on = false; float gen_penalty = 1.0f; int gen_ngram = 0; std::vector<int> gen_suppress;
+    int* hist = nullptr; int* gen_suppress_d = nullptr;
+    uint64_t spliced = 0;          // rows of the last prefill that sonic_splice_rows handed to a continuous loop (bit r = request r); cleared by every prefill (gen_busy)
     long long* kt = nullptr; int kt_layer = -1;     // diagnostics ("ktrace" option): in-kernel timestamps of one decoder layer's kernels
     int* ring_peak = nullptr;                        // [Bm] per-request max |s| of a ring-staged batch (ingest.hip)
     std::atomic<int64_t> ring_bytes{0};             // owner: device bytes of those rings (part of sonic_memory_info of the owner)
@@ -279,4 +285,7 @@ void resample_release(sonic_engine* e);
 void async_shutdown(sonic_engine* e);
 int fetch_locked(sonic_engine* e, int32_t* out_ids, int out_ld, int32_t* out_len, float* step_logits, float* out_lp = nullptr);
 int lp_alloc(sonic_engine* e);                      // out_lp on first use (engine.cpp)
+int gen_apply(sonic_engine* e, float penalty, int ngram, const int32_t* suppress, int n_suppress);   // sonic_set_generation behind the lock and the busy check (engine.cpp)
+int gen_busy(sonic_engine* e, const char* who);     // that busy check: SONIC_ERR_INVALID while the handle has work in hand (engine.cpp)
+void drop_graphs(sonic_engine* e);                  // the captured decode chunks of this handle (engine_hooks.cpp)
 int lp_check(sonic_engine* e, const char* who);     // SONIC_ERR_INVALID naming the option when token_logprobs is off on this handle

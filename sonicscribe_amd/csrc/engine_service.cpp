@@ -13,6 +13,7 @@ struct SpliceArgs {
     const bf16_t *Ks, *Vs; bf16_t *Kd, *Vd; int layers, Bm, Hkv, ctx, hd;
     int src[64], dst[64];
     const int *kv_len_s, *tok_pos_s, *n_new_s, *fin_s, *max_new_s, *out_s; int out_ld;
+    const int* hist_s; int* hist_d;                      // generation guards on the destination: the row's history (prompt + first token) travels with it, [.][ctx]
     const float* lp_s; float* lp_d;                      // option token_logprobs on the destination: the first token's log-probability travels with its id
     int *kv_len_d, *tok_pos_d, *n_new_d, *fin_d, *max_new_d, *out_d, *n_active_d;
     const bf16_t *sx_s, *shn_s; bf16_t *sx_d, *shn_d; int D;
@@ -39,6 +40,10 @@ __global__ __launch_bounds__(256) void splice_state_kernel(SpliceArgs a) {
         const int cnt = a.oc_s[s];
         for (int j = t; j < cnt; j += 256) { a.ol_d[(long)d * a.D + j] = a.ol_s[(long)s * a.D + j]; a.ov_d[(long)d * a.D + j] = a.ov_s[(long)s * a.D + j]; }
         if (t == 0) { a.sca_d[d] = a.sca_s[s]; a.oc_d[d] = cnt; }
+    }
+    if (a.hist_d) {
+        const int len = min(max(a.kv_len_s[s], 0) + 1, a.ctx);      // (a row that stopped at its first token kept kv_len = prompt: its token sits at [kv_len])
+        for (int j = t; j < len; j += 256) a.hist_d[(long)d * a.ctx + j] = a.hist_s[(long)s * a.ctx + j];
     }
     if (t == 0) {
         const int fin = a.fin_s[s];
@@ -113,6 +118,9 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
     if (d->Bm != p->Bm || d->max_ctx != p->max_ctx) return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: the handles differ in max_batch / max_ctx");
     if (d->opt_token_logprobs && !(p->opt_token_logprobs && p->out_lp))
         return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: the destination has option token_logprobs on, the source prefilled without it");
+    // (either way round: a row whose first token was chosen with guards must not go on without them, nor the reverse)
+    if (d->gen_on != p->gen_on || (d->gen_on && !(p->hist && d->hist && p->gen_penalty == d->gen_penalty && p->gen_ngram == d->gen_ngram && p->gen_suppress == d->gen_suppress)))
+        return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in their generation guards (sonic_set_generation): set them on the owner before its slots are created");
     if (n < 1 || n > 64 || p->greedy_calls < 1 || n > p->R) return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: %d rows, the source has %d prefilled requests", n, p->greedy_calls < 1 ? 0 : p->R);
     SpliceArgs a{};
     for (int i = 0; i < n; ++i) {
@@ -126,6 +134,7 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
     a.kv_len_d = d->kv_len; a.tok_pos_d = d->tok_pos; a.n_new_d = d->n_new; a.fin_d = d->finished; a.max_new_d = d->max_new_d; a.out_d = d->out_ids; a.n_active_d = d->n_active;
     a.sx_s = p->sx; a.shn_s = p->shn; a.sx_d = d->sx; a.shn_d = d->shn; a.D = dm.dec_d;
     if (d->opt_token_logprobs && d->out_lp) { a.lp_s = p->out_lp; a.lp_d = d->out_lp; }
+    if (d->gen_on) { a.hist_s = p->hist; a.hist_d = d->hist; }
     if (d->i8) { a.hq_s = p->hn_q; a.hq_d = d->hn_q; a.sca_s = p->sca_hn; a.sca_d = d->sca_hn; a.oc_s = p->oc_hn; a.oc_d = d->oc_hn; a.ol_s = p->ol_hn; a.ol_d = d->ol_hn; a.ov_s = p->ov_hn; a.ov_d = d->ov_hn; }
     HIPC(d, hipEventRecord(p->xfer_ev, p->st));
     HIPC(d, hipStreamWaitEvent(d->st, p->xfer_ev, 0));
@@ -136,6 +145,7 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
     if (p->wait_pending && p->wait_ev != d->splice_ev) HIPC(d, hipStreamWaitEvent(p->st, p->wait_ev, 0));
     p->wait_ev = d->splice_ev; p->wait_pending = true;
     HIPC(d, hipGetLastError());
+    for (int i = 0; i < n; ++i) p->spliced |= 1ull << src_rows[i];      // (gen_busy: a prefill slot whose rows have all left is free again)
     if (seq_out) *seq_out = d->svc_launched;
     return SONIC_OK;
 }

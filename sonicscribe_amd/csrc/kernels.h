@@ -108,9 +108,16 @@ struct GreedyArgs {
     int dt;
     QuantOut qo;                                       // int8 mode: y is also emitted quantised (input of layer 0's q/k/v Linear8bitLt)
     float* out_lp;                                     // optional [B][out_ld], indexed like out_ids: log-probability of every emitted token (greedy_kernel<T, true>;
-                                                       // option token_logprobs); NULL = off.  Last: the offsets of the fields above are what they were
+                                                       // option token_logprobs); NULL = off.  Behind the fields above: their offsets are what they were
+    // generation guards (greedy_kernel<T, LP, true>, sonic_set_generation); hist = NULL: off.  hist[row][hist_ld]: the row's input_ids - prompt ids, then every
+    // emitted id; its length is kv_len[row] as the launch finds it, the emitted id is appended there
+    int* hist; int hist_ld;
+    float rep_penalty; int ngram;                      // repetition_penalty (1.0: none), no_repeat_ngram_size (0: none)
+    const int* suppress; int n_suppress;               // suppress_tokens on the device
 };
 void launch_greedy(const GreedyArgs& a, hipStream_t s);
+size_t greedy_guard_lds(int V);                        // dynamic LDS of the GUARD instantiations: two bitmaps over the vocabulary
+void launch_hist_prompt(const int* src, const int* tok_seq, const int* tok_pos, int n_tok, int audio_id, int* hist, int hist_ld, hipStream_t s);
 
 struct LogmelConst {
     const float* win;      // [400]

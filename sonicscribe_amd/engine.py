@@ -37,6 +37,7 @@ EXPORTS = [
     "sonic_pipeline_create", "sonic_pipeline_submit", "sonic_pipeline_submit_mixed", "sonic_pipeline_wait", "sonic_pipeline_stats", "sonic_pipeline_last_error", "sonic_pipeline_destroy",
     "sonic_vad_create", "sonic_vad_destroy", "sonic_vad_last_error", "sonic_vad_load_tensor", "sonic_vad_probs", "sonic_vad_probs_rings",
     "sonic_fetch_logprobs", "sonic_fetch_rows_lp", "sonic_dispatch_next_lp", "sonic_pipeline_submit_lp", "sonic_test_greedy_lp",
+    "sonic_set_generation", "sonic_get_generation", "sonic_test_greedy_guard",
 ]
 ABI_VERSION = 12
 
@@ -156,6 +157,9 @@ def load_library():
     lib.sonic_test_greedy.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
     lib.sonic_test_greedy_lp.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.sonic_test_linear_int8.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.sonic_set_generation.argtypes = [vp, C.c_float, C.c_int, vp, C.c_int]
+    lib.sonic_get_generation.argtypes = [vp, C.POINTER(C.c_float), ip, vp, C.c_int, ip]
+    lib.sonic_test_greedy_guard.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_float, C.c_int, vp, C.c_int, vp, vp, vp, vp]
     lib.sonic_slot_create.argtypes = [vp, C.POINTER(vp)]
     lib.sonic_slot_count.argtypes = [vp]
     lib.sonic_dispatch_create.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(vp)]
@@ -731,6 +735,39 @@ def _test_greedy_lp(self, slabs, B: int, force_ids=None):
     return tok, lg, lp
 
 
+def _set_generation(self, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, suppress_tokens: Sequence[int] = ()):
+    """HF generate()'s logits processors inside the greedy kernel (sonic_set_generation): the neutral values (1.0, 0, no ids) switch them off.  On the
+    owner before its slots are created (they copy it); refused (SonicError) for values out of range and while the handle has rows running."""
+    sup = np.ascontiguousarray(list(suppress_tokens), dtype=np.int32)
+    self._check(self.lib.sonic_set_generation(self.h, float(repetition_penalty), int(no_repeat_ngram_size), _p(sup) if sup.size else None, int(sup.size)))
+
+
+def _get_generation(self) -> dict:
+    """the values in force on this handle (sonic_get_generation)"""
+    p, n, ns = C.c_float(0), C.c_int32(0), C.c_int32(0)
+    sup = np.zeros(256, np.int32)
+    self._check(self.lib.sonic_get_generation(self.h, C.byref(p), C.byref(n), _p(sup), 256, C.byref(ns)))
+    return {"repetition_penalty": float(p.value), "no_repeat_ngram_size": int(n.value), "suppress_tokens": [int(x) for x in sup[:ns.value]]}
+
+
+def _test_greedy_guard(self, slabs, B: int, hist, hist_len, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, suppress_tokens=(), force_ids=None,
+                       want_lp: bool = False):
+    """sonic_test_greedy through greedy_kernel<T, LP, true>: slabs [ksplit][mpad][V] fp32, hist [B][ld] int (row b's first hist_len[b] entries are its
+    history) -> (token per row [B], RAW logits [B][V], log-probability of the emitted token over the processed scores [B] or None)"""
+    s = np.ascontiguousarray(slabs, np.float32)
+    ks, mpad, V = s.shape
+    h = np.ascontiguousarray(hist, np.int32).reshape(B, -1)
+    hl = np.ascontiguousarray(hist_len, np.int32)
+    sup = np.ascontiguousarray(list(suppress_tokens), dtype=np.int32)
+    tok = np.zeros(B, np.int32)
+    lg = np.zeros((B, V), np.float32)
+    lp = np.full(B, np.nan, np.float32) if want_lp else None
+    f = np.ascontiguousarray(force_ids, np.int32) if force_ids is not None else None
+    self._check(self.lib.sonic_test_greedy_guard(self.h, _p(s), ks, mpad, V, B, _p(h) if h.size else None, h.shape[1], _p(hl), float(repetition_penalty),
+                                                 int(no_repeat_ngram_size), _p(sup) if sup.size else None, int(sup.size), _p(f), _p(tok), _p(lg), _p(lp)))
+    return tok, lg, lp
+
+
 def _test_linear_int8(self, X, W, bias=None, resid=None, group_rows=None, epi=EPI_BIAS):
     """One Linear8bitLt call; X [M][K], W [N][K] fp16-valued. group_rows: rows per reference call (default: all rows one call)."""
     X = np.ascontiguousarray(X, np.float32); W = np.ascontiguousarray(W, np.float32)
@@ -788,6 +825,9 @@ Engine.test_linear_int8 = _test_linear_int8
 Engine.set_forced_ids = _set_forced_ids
 Engine.test_greedy = _test_greedy
 Engine.test_greedy_lp = _test_greedy_lp
+Engine.test_greedy_guard = _test_greedy_guard
+Engine.set_generation = _set_generation
+Engine.get_generation = _get_generation
 Engine.test_skinny_gu = _test_skinny_gu
 Engine.debug_read = _debug_read
 Engine.debug_ktrace = _debug_ktrace
