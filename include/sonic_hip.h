@@ -408,6 +408,25 @@ SONIC_API int sonic_test_decode_attention_cache(sonic_engine* e, const float* q,
  * out [n_tok][Hq * 128] is read first: rows outside every [q_off, q_off + q_len) come back as they went in. */
 SONIC_API int sonic_test_prefill_attention(sonic_engine* e, const float* q, const float* kcache, const float* vt, const int32_t* q_off, const int32_t* q_len,
                                  const int32_t* kv_len, float* out, int n_tok, int B, int Hq, int Hkv, int ctx_max);
+/* the decode step's and the prefill's glue kernels, one launch each, on caller-made data (fp32 buffers holding element-type values; 16-bit engines only; every
+ * shape and index is checked before the launch).  x / y / resid / qk and the three caches are in-out: uploaded, then read back.  csrc/engine_hooks.cpp has the layouts.
+ *   sonic_test_add_rmsnorm   x[r] += sum of slabs [ksplit][mpad][d], y[r] = RMSNorm(x[r]) * w for r < rows <= rows_alloc; d % 8 == 0, d <= 2048, ksplit 1..8, mpad >= rows.
+ *                            q_out != NULL (fp16 engine): also the row quantised for a Linear8bitLt - q [rows][d], sca / oc_cnt [rows], oc_list / oc_val [rows][d]
+ *   sonic_test_quant_rows    the same five outputs for X [M][ld] (first K columns; fp16 engine; K % 8 == 0, K <= 8192, ld % 8 == 0)
+ *   sonic_test_swiglu_slab   gate / up slabs [ksplit][mpad][2 ff], columns interleaved in groups of 16 (gu8 = 0) or 8 (gu8 = 1) -> act [rows][ff]
+ *   sonic_test_decode_o_gu   o_proj + residual -> RMSNorm -> gate/up + SwiGLU; form 0 fused (default step), 1 split norm (rmsnorm_ss), 2 unfused (slabs + add_rmsnorm);
+ *                            shapes as skinny_o_eligible / skinny_gu_eligible accept them; hn_out [M][D] for forms 1, 2; ss_out (optional, forms 0, 1) [2][D / 64][32][4]
+ *   sonic_test_rope_append   prefill RoPE + K / V / V^T append, tiled = 1 per 16-position tile, 0 per token; sequence b = tokens q_off[b] .. + q_len[b] at positions 0 ..
+ *   sonic_test_rope_enc      encoder partial RoPE in place on qk [M][ld], table row m mod T */
+SONIC_API int sonic_test_add_rmsnorm(sonic_engine* e, float* x, const float* slabs, int ksplit, int mpad, const float* w, float eps, float* y, int rows, int rows_alloc, int d,
+                                     int8_t* q_out, float* sca_out, int32_t* oc_cnt_out, int32_t* oc_list_out, float* oc_val_out);
+SONIC_API int sonic_test_quant_rows(sonic_engine* e, const float* X, int M, int K, int ld, int8_t* q_out, float* sca_out, int32_t* oc_cnt_out, int32_t* oc_list_out, float* oc_val_out);
+SONIC_API int sonic_test_swiglu_slab(sonic_engine* e, const float* slabs, int ksplit, int mpad, int ff, int rows, int gu8, float* act);
+SONIC_API int sonic_test_decode_o_gu(sonic_engine* e, const float* att, const float* Wo, float* resid, const float* ln_w, float eps, const float* Wgu, int form,
+                                     int M, int K, int D, int ff, int rows_alloc, float* hn_out, float* act_out, float* ss_out);
+SONIC_API int sonic_test_rope_append(sonic_engine* e, const float* qkv, const float* cs, const int32_t* tok_seq, const int32_t* tok_pos, const int32_t* q_off, const int32_t* q_len,
+                                     int n_tok, int B, int Hq, int Hkv, int ctx_max, int vt_ld, int tiled, float* q_out, float* Kc, float* Vc, float* Vt);
+SONIC_API int sonic_test_rope_enc(sonic_engine* e, float* qk, int M, int ld, int T, int heads2, int hd, int rd, const float* cs);
 SONIC_API int sonic_test_layernorm(sonic_engine* e, const float* x, const float* w, const float* b, float* y, int rows, int d, float eps, int rms);
 /* times `iters` launches of the encoder's dominant GEMM shape on the engine stream with HIP events */
 SONIC_API int sonic_bench_gemm(sonic_engine* e, int M, int N, int K, int epi, int iters, float* ms_per_launch);

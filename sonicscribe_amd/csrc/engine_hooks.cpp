@@ -639,6 +639,194 @@ extern "C" int sonic_test_skinny_gu(sonic_engine* e, const float* X, const float
     return down_bf16(e, tb, dA, act, (size_t)M * (N / 2));
 }
 
+// ------------------------------------------------------------------------------------------ decode-step and prefill glue kernels, one launch each
+// (tests/test_gpu_decode_glue.py; the references with the kernels' rounding points are in tests/glue_ref.py).  Every hook checks every shape and index
+// before its first launch and refuses what the kernel behind it does not handle.
+static int glue_16bit(sonic_engine* e, const char* what) { return e->f32 ? fail(e, SONIC_ERR_INVALID, "%s needs a 16-bit engine", what) : SONIC_OK; }
+// the five outputs of quant_emit_row for `rows` rows of width K: the lists are pre-filled with -1 so that entries the kernel leaves alone show
+struct QuantHost { int8_t* q; float* sca; int32_t* oc_cnt; int32_t* oc_list; float* oc_val; };
+static int quant_alloc(sonic_engine* e, TmpBuf& tb, int rows, int K, QuantOut* qo) {
+    qo->q = tb.get<int8_t>((size_t)rows * K); qo->ldq = K; qo->sca = tb.get<float>(rows); qo->oc_cnt = tb.get<int>(rows);
+    qo->oc_list = tb.get<int>((size_t)rows * K); qo->oc_ld = K; qo->oc_val = tb.get<float>((size_t)rows * K);
+    if (!qo->q || !qo->sca || !qo->oc_cnt || !qo->oc_list || !qo->oc_val) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    size_t left = (size_t)rows * K; int* p = qo->oc_list;
+    while (left > 0) { const int c = left > (1u << 30) ? (1 << 30) : (int)left; launch_fill_i32(p, -1, c, e->st); p += c; left -= c; }
+    return SONIC_OK;
+}
+static int quant_fetch(sonic_engine* e, const QuantOut& qo, int rows, int K, const QuantHost& h) {
+    HIPC(e, stream_sync(e));
+    HIPC(e, hipGetLastError());
+    HIPC(e, d2h(e, h.q, qo.q, (size_t)rows * K)); HIPC(e, d2h(e, h.sca, qo.sca, (size_t)rows * 4)); HIPC(e, d2h(e, h.oc_cnt, qo.oc_cnt, (size_t)rows * 4));
+    HIPC(e, d2h(e, h.oc_list, qo.oc_list, (size_t)rows * K * 4)); HIPC(e, d2h(e, h.oc_val, qo.oc_val, (size_t)rows * K * 4));
+    return SONIC_OK;
+}
+
+// add_rmsnorm_kernel as decode_step() launches it behind o_proj / down_proj: x[r] += sum of the slabs, y[r] = RMSNorm(x[r]) * w for r < rows.  x and y are
+// [rows_alloc][d] and both are uploaded first, so rows the kernel leaves alone come back as they went in.  q_out != NULL (fp16 engine): the launch also gets a
+// QuantOut (quant_emit_row<true>, DeqInfo off) and the five outputs come back: q [rows][d], sca / oc_cnt [rows], oc_list / oc_val [rows][d] (-1 / 0 where unwritten).
+extern "C" int sonic_test_add_rmsnorm(sonic_engine* e, float* x, const float* slabs, int ksplit, int mpad, const float* w, float eps, float* y, int rows, int rows_alloc, int d,
+                                      int8_t* q_out, float* sca_out, int32_t* oc_cnt_out, int32_t* oc_list_out, float* oc_val_out) {
+    if (!e || !x || !slabs || !w || !y) return SONIC_ERR_INVALID;
+    ENTER(e);
+    TRY(glue_16bit(e, "sonic_test_add_rmsnorm"));
+    if (d < 8 || d % 8 || d > 2048 || ksplit < 1 || ksplit > 8 || rows < 1 || rows > 4096 || rows_alloc < rows || rows_alloc > 8192 || mpad < rows || mpad > 8192)
+        return fail(e, SONIC_ERR_INVALID, "add_rmsnorm: d %% 8 == 0, d <= 2048, 1 <= ksplit <= 8, 1 <= rows <= rows_alloc, mpad >= rows");
+    if (q_out && (e->dt != DT_F16 || !sca_out || !oc_cnt_out || !oc_list_out || !oc_val_out))
+        return fail(e, SONIC_ERR_INVALID, "add_rmsnorm: the quantised outputs need an fp16 engine and all five buffers");
+    TmpBuf tb(e->st);
+    const size_t n = (size_t)rows_alloc * d;
+    bf16_t* dx = up_bf16(e, tb, x, n); bf16_t* dy = up_bf16(e, tb, y, n);
+    float* dP = up_f32(e, tb, slabs, (size_t)ksplit * mpad * d); float* dw = up_f32(e, tb, w, d);
+    if (!dx || !dy || !dP || !dw) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    QuantOut qo{};
+    if (q_out) TRY(quant_alloc(e, tb, rows, d, &qo));
+    launch_add_rmsnorm(dx, dP, ksplit, mpad, dw, dy, rows, d, eps, e->st, e->dt, nullptr, q_out ? &qo : nullptr);
+    TRY(down_bf16(e, tb, dx, x, n));
+    TRY(down_bf16(e, tb, dy, y, n));
+    if (q_out) TRY(quant_fetch(e, qo, rows, d, QuantHost{q_out, sca_out, oc_cnt_out, oc_list_out, oc_val_out}));
+    return SONIC_OK;
+}
+
+// quant_rows_kernel (launch_quant_rows, the decode flavour of the activation quantiser): X [M][ld] fp16 values, the first K of every row are quantised
+extern "C" int sonic_test_quant_rows(sonic_engine* e, const float* X, int M, int K, int ld, int8_t* q_out, float* sca_out, int32_t* oc_cnt_out, int32_t* oc_list_out, float* oc_val_out) {
+    if (!e || !X || !q_out || !sca_out || !oc_cnt_out || !oc_list_out || !oc_val_out) return SONIC_ERR_INVALID;
+    ENTER(e);
+    if (e->f32 || e->dt != DT_F16) return fail(e, SONIC_ERR_INVALID, "sonic_test_quant_rows needs an fp16 engine");
+    if (M < 1 || M > 4096 || K < 8 || K % 8 || K > 8192 || ld < K || ld % 8 || ld > (1 << 20))
+        return fail(e, SONIC_ERR_INVALID, "quant_rows: 1 <= M <= 4096, K %% 8 == 0, K <= 8192, ld >= K, ld %% 8 == 0");
+    TmpBuf tb(e->st);
+    bf16_t* dX = up_bf16(e, tb, X, (size_t)M * ld);
+    if (!dX) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    QuantOut qo{};
+    TRY(quant_alloc(e, tb, M, K, &qo));
+    launch_quant_rows(dX, ld, M, K, qo, e->st);
+    return quant_fetch(e, qo, M, K, QuantHost{q_out, sca_out, oc_cnt_out, oc_list_out, oc_val_out});
+}
+
+// swiglu_slab_kernel: slabs [ksplit][mpad][2 ff] fp32 with gate / up columns interleaved in groups of 16 (gu8 = 0) or 8 (gu8 = 1) -> act [rows][ff]
+extern "C" int sonic_test_swiglu_slab(sonic_engine* e, const float* slabs, int ksplit, int mpad, int ff, int rows, int gu8, float* act) {
+    if (!e || !slabs || !act) return SONIC_ERR_INVALID;
+    ENTER(e);
+    TRY(glue_16bit(e, "sonic_test_swiglu_slab"));
+    if (ff < 16 || ff % 16 || ff > (1 << 16) || ksplit < 1 || ksplit > 8 || rows < 1 || rows > 4096 || mpad < rows || mpad > 8192 || (gu8 != 0 && gu8 != 1))
+        return fail(e, SONIC_ERR_INVALID, "swiglu_slab: ff %% 16 == 0, 1 <= ksplit <= 8, 1 <= rows <= mpad, gu8 0 or 1");
+    TmpBuf tb(e->st);
+    float* dP = up_f32(e, tb, slabs, (size_t)ksplit * mpad * 2 * ff); bf16_t* dA = tb.get<bf16_t>((size_t)rows * ff);
+    if (!dP || !dA) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    launch_swiglu_slab(dP, ksplit, mpad, 2 * ff, dA, rows, e->st, e->dt, gu8);
+    return down_bf16(e, tb, dA, act, (size_t)rows * ff);
+}
+
+// The o_proj -> RMSNorm -> gate/up chain of one decoder layer as decode_step() launches it.  att [M][K], Wo [D][K], resid [rows_alloc][D] (in place: rows >= M must
+// come back untouched), ln_w [D], Wgu [2 ff][D] with gate / up rows interleaved in groups of 16 (as for sonic_test_skinny_gu).
+//   form 0: launch_skinny_o + launch_skinny_gu_norm                          (the default step)
+//   form 1: launch_skinny_o + launch_rmsnorm_ss + launch_skinny_gu           (the continuous loops' split form; hn_out [M][D])
+//   form 2: launch_skinny into slabs + launch_add_rmsnorm + launch_skinny_gu (the unfused form; hn_out [M][D])
+// act_out [M][ff]; ss_out (optional, forms 0 / 1): the raw sum-of-squares partials [2 regions][D / 64][32 rows][4].
+// rmsnorm_ss_kernel splits a row's D / 64 partial groups into two halves and is launched with D / 8 <= 256 threads: form 1 needs D % 128 == 0 and D <= 2048.
+extern "C" int sonic_test_decode_o_gu(sonic_engine* e, const float* att, const float* Wo, float* resid, const float* ln_w, float eps, const float* Wgu, int form,
+                                      int M, int K, int D, int ff, int rows_alloc, float* hn_out, float* act_out, float* ss_out) {
+    if (!e || !att || !Wo || !resid || !ln_w || !Wgu || !act_out) return SONIC_ERR_INVALID;
+    ENTER(e);
+    TRY(glue_16bit(e, "sonic_test_decode_o_gu"));
+    if (form < 0 || form > 2 || M < 1 || M > 64 || rows_alloc < M || rows_alloc > 4096 || ff < 16 || ff > (1 << 16) || D % 64 || D > 2048)
+        return fail(e, SONIC_ERR_INVALID, "decode_o_gu: form 0..2, 1 <= M <= 64, rows_alloc >= M, D %% 64 == 0, D <= 2048");
+    if (!skinny_gu_eligible(M, 2 * ff, D)) return fail(e, SONIC_ERR_INVALID, "decode_o_gu: gate/up shape not handled by the fused gate/up kernel");
+    if (form < 2 && !skinny_o_eligible(M, D, K)) return fail(e, SONIC_ERR_INVALID, "decode_o_gu: o_proj shape not handled by the fused o_proj kernel");
+    if (form == 1 && D % 128) return fail(e, SONIC_ERR_INVALID, "decode_o_gu: the split norm needs D %% 128 == 0");
+    if (form == 2 && (D % 16 || K % 256 || K < 256 || skinny_pick_ksplit(D, K) < 1 || skinny_pick_ksplit(D, K) > 8)) return fail(e, SONIC_ERR_INVALID, "decode_o_gu: o_proj shape not handled by the skinny GEMM");
+    if (form != 0 && !hn_out) return fail(e, SONIC_ERR_INVALID, "decode_o_gu: forms 1 and 2 return hn_out");
+    if (form == 2 && ss_out) return fail(e, SONIC_ERR_INVALID, "decode_o_gu: the unfused form has no sum-of-squares partials");
+    TmpBuf tb(e->st);
+    const size_t nss = (size_t)2 * (D / 64) * 32 * 4;
+    bf16_t* dA = up_bf16(e, tb, att, (size_t)M * K); bf16_t* dWo = up_bf16(e, tb, Wo, (size_t)D * K); bf16_t* dWot = tb.get<bf16_t>((size_t)D * K);
+    bf16_t* dR = up_bf16(e, tb, resid, (size_t)rows_alloc * D); float* dw = up_f32(e, tb, ln_w, D);
+    bf16_t* dWg = up_bf16(e, tb, Wgu, (size_t)2 * ff * D); bf16_t* dWgt = tb.get<bf16_t>((size_t)2 * ff * D);
+    bf16_t* dH = tb.get<bf16_t>((size_t)M * D); bf16_t* dAct = tb.get<bf16_t>((size_t)M * ff); float* dSS = tb.get<float>(nss);
+    if (!dA || !dWo || !dWot || !dR || !dw || !dWg || !dWgt || !dH || !dAct || !dSS) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    launch_tile_weights(dWo, dWot, D, K, e->st);
+    launch_tile_weights_gu8(dWg, dWgt, 2 * ff, D, e->st);
+    SkinnyArgs ga{}; ga.X = dR; ga.ldx = D; ga.W = dWgt; ga.M = M; ga.N = 2 * ff; ga.K = D; ga.ksplit = 1; ga.dt = e->dt; ga.err = e->n_active + 1;
+    if (form < 2) {
+        SkinnyArgs oa{}; oa.X = dA; oa.ldx = K; oa.W = dWot; oa.M = M; oa.N = D; oa.K = K; oa.ksplit = 1; oa.dt = e->dt;
+        launch_skinny_o(oa, dR, D, dSS, e->st);
+        if (form == 1) {
+            launch_rmsnorm_ss(dR, dSS, dw, dH, M, D, eps, e->st, e->dt);
+            ga.X = dH; launch_skinny_gu(ga, dAct, e->st);
+        } else
+            launch_skinny_gu_norm(ga, dAct, dSS, D / 16, dw, eps, e->st);
+    } else {
+        const int ks = skinny_pick_ksplit(D, K), mpad = ((M + 15) / 16) * 16;
+        float* P = tb.get<float>((size_t)ks * mpad * D);
+        if (!P) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+        SkinnyArgs a{}; a.X = dA; a.ldx = K; a.W = dWot; a.P = P; a.M = M; a.N = D; a.K = K; a.ksplit = ks; a.dt = e->dt;
+        launch_skinny(a, e->st);
+        launch_add_rmsnorm(dR, P, ks, mpad, dw, dH, M, D, eps, e->st, e->dt);
+        ga.X = dH; launch_skinny_gu(ga, dAct, e->st);
+    }
+    TRY(down_bf16(e, tb, dR, resid, (size_t)rows_alloc * D));
+    if (form != 0) TRY(down_bf16(e, tb, dH, hn_out, (size_t)M * D));
+    TRY(down_bf16(e, tb, dAct, act_out, (size_t)M * ff));
+    if (ss_out) HIPC(e, d2h(e, ss_out, dSS, nss * 4));
+    return SONIC_OK;
+}
+
+// The prefill's RoPE + KV append as run_prefill() launches it: packed qkv [n_tok][(Hq + 2 Hkv) * 128], the RoPE table cs [ctx_max][128], per token its sequence
+// and position, per sequence its first packed token and length.  tiled = 1: rope_append_pf_kernel (q_off / q_len / n_seq / max_p passed); tiled = 0:
+// rope_append_kernel<T, false> (they stay null: option no_rope_tiles).  Kc / Vc [B][Hkv][ctx_max][128] and Vt [B][Hkv][128][vt_ld] are uploaded, and read back
+// after the launch; q_out [n_tok][Hq * 128].  The tile kernel takes a tile's first position from tok_pos of its first token and writes V^T for the 16 positions
+// behind it: the contract is that sequence b's tokens are packed at q_off[b] .. + q_len[b] with positions 0 .. q_len[b] - 1, which is checked here.
+extern "C" int sonic_test_rope_append(sonic_engine* e, const float* qkv, const float* cs, const int32_t* tok_seq, const int32_t* tok_pos, const int32_t* q_off, const int32_t* q_len,
+                                      int n_tok, int B, int Hq, int Hkv, int ctx_max, int vt_ld, int tiled, float* q_out, float* Kc, float* Vc, float* Vt) {
+    if (!e || !qkv || !cs || !tok_seq || !tok_pos || !q_off || !q_len || !q_out || !Kc || !Vc || !Vt) return SONIC_ERR_INVALID;
+    ENTER(e);
+    TRY(glue_16bit(e, "sonic_test_rope_append"));
+    if (B < 1 || B > 4096 || n_tok < 1 || n_tok > (1 << 20) || Hq < 1 || Hq > 64 || Hkv < 1 || Hkv > 16 || ctx_max < 1 || ctx_max > (1 << 20) || vt_ld < ctx_max || vt_ld > (1 << 21))
+        return fail(e, SONIC_ERR_INVALID, "rope_append: 1 <= Hkv <= 16, vt_ld >= ctx_max >= 1");
+    long covered = 0; int max_p = 0;
+    for (int b = 0; b < B; ++b) {
+        if (q_len[b] < 1 || q_len[b] > ctx_max || q_off[b] < 0 || (long)q_off[b] + q_len[b] > n_tok)
+            return fail(e, SONIC_ERR_INVALID, "sequence %d: q_off %d, q_len %d do not fit %d tokens / a context of %d", b, q_off[b], q_len[b], n_tok, ctx_max);
+        for (int i = 0; i < q_len[b]; ++i)
+            if (tok_seq[q_off[b] + i] != b || tok_pos[q_off[b] + i] != i)
+                return fail(e, SONIC_ERR_INVALID, "token %d: sequence %d position %d where sequence %d position %d is packed", q_off[b] + i, tok_seq[q_off[b] + i], tok_pos[q_off[b] + i], b, i);
+        covered += q_len[b]; max_p = q_len[b] > max_p ? q_len[b] : max_p;
+    }
+    if (covered != n_tok) return fail(e, SONIC_ERR_INVALID, "the sequences cover %ld of %d tokens", covered, n_tok);     // (with the loop above: every token in exactly one sequence)
+    TmpBuf tb(e->st);
+    const int N = (Hq + 2 * Hkv) * 128;
+    const size_t nc = (size_t)B * Hkv * ctx_max * 128, nvt = (size_t)B * Hkv * 128 * vt_ld, nq = (size_t)n_tok * Hq * 128;
+    bf16_t* dqkv = up_bf16(e, tb, qkv, (size_t)n_tok * N); float* dcs = up_f32(e, tb, cs, (size_t)ctx_max * 128);
+    bf16_t* dk = up_bf16(e, tb, Kc, nc); bf16_t* dv = up_bf16(e, tb, Vc, nc); bf16_t* dvt = up_bf16(e, tb, Vt, nvt); bf16_t* dq = tb.get<bf16_t>(nq);
+    int* di = tb.get<int>((size_t)2 * n_tok + 2 * B);
+    if (!dqkv || !dcs || !dk || !dv || !dvt || !dq || !di) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    HIPC(e, h2d(e, di, tok_seq, (size_t)n_tok * 4)); HIPC(e, h2d(e, di + n_tok, tok_pos, (size_t)n_tok * 4));
+    HIPC(e, h2d(e, di + 2 * n_tok, q_off, (size_t)B * 4)); HIPC(e, h2d(e, di + 2 * n_tok + B, q_len, (size_t)B * 4));
+    RopeAppendArgs ra{}; ra.dt = e->dt;
+    ra.qkv = dqkv; ra.ld = N; ra.q_out = dq; ra.Kc = dk; ra.Vc = dv; ra.Vt = dvt; ra.vt_ld = vt_ld;
+    ra.tok_seq = di; ra.tok_pos = di + n_tok; ra.cs = dcs; ra.Hq = Hq; ra.Hkv = Hkv; ra.ctx_max = ctx_max; ra.n_tok = n_tok;
+    if (tiled) { ra.q_off = di + 2 * n_tok; ra.q_len = di + 2 * n_tok + B; ra.n_seq = B; ra.max_p = max_p; }
+    launch_rope_append(ra, false, e->st);
+    TRY(down_bf16(e, tb, dq, q_out, nq));
+    TRY(down_bf16(e, tb, dk, Kc, nc));
+    TRY(down_bf16(e, tb, dv, Vc, nc));
+    return down_bf16(e, tb, dvt, Vt, nvt);
+}
+
+// rope_enc_kernel in place on qk [M][ld]: heads2 heads of hd = 64 at the front of every row, the first rd dims of each rotated with row (m mod T) of cs [T][rd]
+extern "C" int sonic_test_rope_enc(sonic_engine* e, float* qk, int M, int ld, int T, int heads2, int hd, int rd, const float* cs) {
+    if (!e || !qk || !cs) return SONIC_ERR_INVALID;
+    ENTER(e);
+    TRY(glue_16bit(e, "sonic_test_rope_enc"));
+    if (hd != 64 || rd < 16 || rd > hd || rd % 16 || heads2 < 1 || heads2 > 256 || M < 1 || M > (1 << 20) || T < 1 || ld < heads2 * hd || ld % 8 || ld > (1 << 20))
+        return fail(e, SONIC_ERR_INVALID, "rope_enc: hd == 64, rd %% 16 == 0, 16 <= rd <= hd, ld >= heads2 * hd, ld %% 8 == 0");
+    TmpBuf tb(e->st);
+    bf16_t* dqk = up_bf16(e, tb, qk, (size_t)M * ld); float* dcs = up_f32(e, tb, cs, (size_t)T * rd);
+    if (!dqk || !dcs) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    launch_rope_enc(dqk, ld, M, T, heads2, hd, rd, dcs, e->st, e->dt);
+    return down_bf16(e, tb, dqk, qk, (size_t)M * ld);
+}
+
 extern "C" int sonic_debug_ktrace(sonic_engine* e, int64_t* out, int64_t n) {
     if (!e || !out) return SONIC_ERR_INVALID;
     ENTER(e);

@@ -38,6 +38,7 @@ EXPORTS = [
     "sonic_vad_create", "sonic_vad_destroy", "sonic_vad_last_error", "sonic_vad_load_tensor", "sonic_vad_probs", "sonic_vad_probs_rings",
     "sonic_fetch_logprobs", "sonic_fetch_rows_lp", "sonic_dispatch_next_lp", "sonic_pipeline_submit_lp", "sonic_test_greedy_lp",
     "sonic_set_generation", "sonic_get_generation", "sonic_test_greedy_guard",
+    "sonic_test_add_rmsnorm", "sonic_test_quant_rows", "sonic_test_swiglu_slab", "sonic_test_decode_o_gu", "sonic_test_rope_append", "sonic_test_rope_enc",
 ]
 ABI_VERSION = 12
 
@@ -160,6 +161,12 @@ def load_library():
     lib.sonic_set_generation.argtypes = [vp, C.c_float, C.c_int, vp, C.c_int]
     lib.sonic_get_generation.argtypes = [vp, C.POINTER(C.c_float), ip, vp, C.c_int, ip]
     lib.sonic_test_greedy_guard.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_float, C.c_int, vp, C.c_int, vp, vp, vp, vp]
+    lib.sonic_test_add_rmsnorm.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_float, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    lib.sonic_test_quant_rows.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    lib.sonic_test_swiglu_slab.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    lib.sonic_test_decode_o_gu.argtypes = [vp, vp, vp, vp, vp, C.c_float, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.sonic_test_rope_append.argtypes = [vp] * 7 + [C.c_int] * 7 + [vp] * 4
+    lib.sonic_test_rope_enc.argtypes = [vp, vp] + [C.c_int] * 6 + [vp]
     lib.sonic_slot_create.argtypes = [vp, C.POINTER(vp)]
     lib.sonic_slot_count.argtypes = [vp]
     lib.sonic_dispatch_create.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(vp)]
@@ -819,6 +826,82 @@ def _test_prefill_attention(self, q, kcache, vt, q_off, q_len, kv_len, out_init=
     return out
 
 
+def _quant_bufs(rows: int, K: int):
+    return (np.zeros((rows, K), np.int8), np.zeros(rows, np.float32), np.zeros(rows, np.int32), np.zeros((rows, K), np.int32), np.zeros((rows, K), np.float32))
+
+
+def _test_add_rmsnorm(self, x, slabs, w, eps: float, rows: int, y_init=None, quant: bool = False):
+    """add_rmsnorm_kernel as the decode step launches it.  x [rows_alloc][d], slabs [ksplit][mpad][d] fp32, w [d]; y_init [rows_alloc][d] is what the output
+    buffer holds before the launch (default zeros).  -> (x after, y after[, (q int8 [rows][d], sca [rows], oc_cnt [rows], oc_list [rows][d], oc_val [rows][d])]);
+    list entries the kernel did not write are -1 / 0.  quant needs an fp16 engine."""
+    x = np.array(x, np.float32, order="C"); s = np.ascontiguousarray(slabs, np.float32); w = np.ascontiguousarray(w, np.float32)
+    rows_alloc, d = x.shape
+    ks, mpad = s.shape[:2]
+    assert s.shape == (ks, mpad, d) and w.shape == (d,)
+    y = np.zeros_like(x) if y_init is None else np.array(y_init, np.float32, order="C")
+    assert y.shape == x.shape
+    qb = _quant_bufs(rows, d) if quant else (None,) * 5
+    self._check(self.lib.sonic_test_add_rmsnorm(self.h, _p(x), _p(s), ks, mpad, _p(w), float(eps), _p(y), int(rows), rows_alloc, d, *[_p(b) for b in qb]))
+    return (x, y, qb) if quant else (x, y)
+
+
+def _test_quant_rows(self, X, K: Optional[int] = None):
+    """quant_rows_kernel on X [M][ld] (fp16 values; the first K columns of every row, default all) -> (q, sca, oc_cnt, oc_list, oc_val) as test_add_rmsnorm"""
+    X = np.ascontiguousarray(X, np.float32)
+    M, ld = X.shape
+    K = ld if K is None else int(K)
+    qb = _quant_bufs(M, K)
+    self._check(self.lib.sonic_test_quant_rows(self.h, _p(X), M, K, ld, *[_p(b) for b in qb]))
+    return qb
+
+
+def _test_swiglu_slab(self, slabs, rows: int, gu8: int):
+    """swiglu_slab_kernel: slabs [ksplit][mpad][2 ff] fp32 -> act [rows][ff]"""
+    s = np.ascontiguousarray(slabs, np.float32)
+    ks, mpad, n2 = s.shape
+    act = np.empty((rows, n2 // 2), np.float32)
+    self._check(self.lib.sonic_test_swiglu_slab(self.h, _p(s), ks, mpad, n2 // 2, int(rows), int(gu8), _p(act)))
+    return act
+
+
+def _test_decode_o_gu(self, att, Wo, resid, ln_w, eps: float, Wgu, form: int, want_ss: bool = False):
+    """One layer's o_proj -> RMSNorm -> gate/up chain (sonic_test_decode_o_gu).  att [M][K], Wo [D][K], resid [rows_alloc][D], ln_w [D], Wgu [2 ff][D] (gate / up rows
+    interleaved in groups of 16).  -> dict: resid [rows_alloc][D], act [M][ff], hn [M][D] (forms 1, 2), ss [2][D / 64][32][4] (want_ss, forms 0, 1)"""
+    att = np.ascontiguousarray(att, np.float32); Wo = np.ascontiguousarray(Wo, np.float32); Wgu = np.ascontiguousarray(Wgu, np.float32)
+    r = np.array(resid, np.float32, order="C"); w = np.ascontiguousarray(ln_w, np.float32)
+    M, K = att.shape; D = Wo.shape[0]; ff = Wgu.shape[0] // 2
+    assert Wo.shape == (D, K) and r.shape[1] == D and w.shape == (D,) and Wgu.shape == (2 * ff, D)
+    hn = np.empty((M, D), np.float32) if form != 0 else None
+    act = np.empty((M, ff), np.float32)
+    ss = np.empty((2, D // 64, 32, 4), np.float32) if want_ss else None
+    self._check(self.lib.sonic_test_decode_o_gu(self.h, _p(att), _p(Wo), _p(r), _p(w), float(eps), _p(Wgu), int(form), M, K, D, ff, r.shape[0], _p(hn), _p(act), _p(ss)))
+    return {"resid": r, "act": act, "hn": hn, "ss": ss}
+
+
+def _test_rope_append(self, qkv, cs, tok_seq, tok_pos, q_off, q_len, Hq: int, kcache, vcache, vt, tiled: bool):
+    """The prefill's RoPE + KV append.  qkv [n_tok][(Hq + 2 Hkv) * 128], cs [ctx_max][128], kcache / vcache [B][Hkv][ctx_max][128], vt [B][Hkv][128][vt_ld] as the
+    buffers are before the launch.  -> (q [n_tok][Hq][128], kcache, vcache, vt after)"""
+    qkv = np.ascontiguousarray(qkv, np.float32); cs = np.ascontiguousarray(cs, np.float32)
+    kc = np.array(kcache, np.float32, order="C"); vc = np.array(vcache, np.float32, order="C"); vt = np.array(vt, np.float32, order="C")
+    B, Hkv, ctx, hd = kc.shape
+    n_tok = qkv.shape[0]
+    assert hd == 128 and vc.shape == kc.shape and vt.shape[:3] == (B, Hkv, 128) and cs.shape == (ctx, 128) and qkv.shape[1] == (Hq + 2 * Hkv) * 128
+    ts, tp, qo, ql = (np.ascontiguousarray(a, np.int32) for a in (tok_seq, tok_pos, q_off, q_len))
+    assert ts.shape == tp.shape == (n_tok,) and qo.shape == ql.shape == (B,)
+    q = np.empty((n_tok, Hq, 128), np.float32)
+    self._check(self.lib.sonic_test_rope_append(self.h, _p(qkv), _p(cs), _p(ts), _p(tp), _p(qo), _p(ql), n_tok, B, Hq, Hkv, ctx, vt.shape[3], int(tiled),
+                                                _p(q), _p(kc), _p(vc), _p(vt)))
+    return q, kc, vc, vt
+
+
+def _test_rope_enc(self, qk, T: int, heads2: int, rd: int, cs, hd: int = 64):
+    """rope_enc_kernel on a copy of qk [M][ld]; cs [T][rd]"""
+    qk = np.array(qk, np.float32, order="C"); cs = np.ascontiguousarray(cs, np.float32)
+    assert cs.shape == (T, rd)
+    self._check(self.lib.sonic_test_rope_enc(self.h, _p(qk), qk.shape[0], qk.shape[1], int(T), int(heads2), int(hd), int(rd), _p(cs)))
+    return qk
+
+
 Engine.test_decode_attention_cache = _test_decode_attention_cache
 Engine.test_prefill_attention = _test_prefill_attention
 Engine.test_linear_int8 = _test_linear_int8
@@ -833,6 +916,12 @@ Engine.debug_read = _debug_read
 Engine.debug_ktrace = _debug_ktrace
 Engine.bench_skinny = _bench_skinny
 Engine.set_option = _set_option
+Engine.test_add_rmsnorm = _test_add_rmsnorm
+Engine.test_quant_rows = _test_quant_rows
+Engine.test_swiglu_slab = _test_swiglu_slab
+Engine.test_decode_o_gu = _test_decode_o_gu
+Engine.test_rope_append = _test_rope_append
+Engine.test_rope_enc = _test_rope_enc
 
 
 def device_info(device_id: int = 0) -> dict:
