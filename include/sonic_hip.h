@@ -50,6 +50,10 @@
  *   sonic_set_generation       the LogitsProcessorList that generate() builds from the checkpoint's generation_config.json
  *                              (repetition_penalty, no_repeat_ngram_size, suppress_tokens)               backend/asr.py:411-422
  *   sonic_get_generation / sonic_test_greedy_guard   (what is in force; test hook of the kernel behind it)
+ *   sonic_set_request_bias     `hotwords` of a request as a bias on the scores: HF's sequence_bias / bad_words_ids
+ *                              (SequenceBiasLogitsProcessor, NoBadWordsLogitsProcessor; generation/logits_process.py),
+ *                              one table per request                                                      backend/asr.py:303-333
+ *   sonic_dispatch_submit_bias / sonic_test_greedy_bias   (the same through the dispatcher; test hook of the kernel behind it)
  */
 #ifndef SONIC_HIP_H
 #define SONIC_HIP_H
@@ -231,6 +235,21 @@ SONIC_API int sonic_fetch_logprobs(sonic_engine* e, float* out_lp, int out_ld);
  * sonic_set_option keys "gen_repetition_penalty_milli", "gen_no_repeat_ngram_size", "gen_suppress_token" (one id, -1 = none) set one value each for
  * drivers that only pass integers. */
 SONIC_API int sonic_set_generation(sonic_engine* e, float repetition_penalty, int no_repeat_ngram_size, const int32_t* suppress, int n_suppress);
+/* Per-request sequence bias: HF's SequenceBiasLogitsProcessor, with NoBadWordsLogitsProcessor folded in as entries of bias -inf (generation/logits_process.py),
+ * on a table that belongs to the request - the reference's per-connection / per-upload hotwords (backend/asr.py:303-333) as shallow biasing of the scores.
+ * A table is a list of entries, each a token sequence of 1 .. 8 ids and an fp32 bias; equal sequences are merged as HF's list-to-dict conversion merges them (the
+ * last bias wins, at the first position).  Per token a fp32 sum starts at +0.0, takes the length-1 entry of that token, then - in list order - every longer
+ * entry that ends on the token, has L <= len(input_ids) and whose first L - 1 ids equal the last L - 1 ids of input_ids (the prompt ids, audio placeholders
+ * included, then every emitted id); score = score + sum, once, in fp32, ahead of the processors of sonic_set_generation.  A bad word is an entry of bias -inf
+ * (with finite biases the fold gives HF's bits: (s + b) -> penalty -> -inf and s + (b + -inf) -> penalty are both -inf for p > 0).  step_logits stay raw;
+ * with option token_logprobs the log-probabilities are over the biased scores.  A row whose scores are all -inf emits token 0.
+ *   option "request_bias" (sonic_set_option): on the owner before its slots are created (they copy it); allocates the rows' history and tables (counted by
+ *       sonic_memory_info); refused while the handle has work in hand, as sonic_set_generation is.  sonic_splice_rows refuses handles whose options differ.
+ *   sonic_set_request_bias: the tables of the R requests of the NEXT sonic_prefill / sonic_prefill_enqueue / sonic_run_staged[_async] / sonic_transcribe_* on this
+ *       handle, which consumes them on success and on failure alike - a sonic_transcribe_* that fails while staging drops them too (a later batch starts without tables).  Request r owns entries req_off[r] .. req_off[r + 1]; entry i is
+ *       seq_ids[seq_off[i] .. seq_off[i + 1]) with bias[i].  SONIC_ERR_INVALID, nothing truncated: the option is off (the message names it), more than 256
+ *       entries in a request, a sequence outside 1 .. 8 ids, an id outside the vocabulary, a NaN or +inf bias; at the prefill, an R that is not the batch's. */
+SONIC_API int sonic_set_request_bias(sonic_engine* e, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, const int32_t* req_off, int R);
 /* the values in force on this handle; at most `cap` ids are copied to suppress, *n_suppress is their full count (any pointer may be NULL) */
 SONIC_API int sonic_get_generation(sonic_engine* e, float* repetition_penalty, int32_t* no_repeat_ngram_size, int32_t* suppress, int cap, int32_t* n_suppress);
 /* sonic_run_staged without blocking the caller: the arguments are copied, a worker thread owned by the handle runs the batch, the call
@@ -287,6 +306,12 @@ struct sonic_ring;
 SONIC_API int sonic_dispatch_create(sonic_engine* const* decoders, int n_dec, sonic_engine* const* prefills, int n_pre, int adaptive_tiles, sonic_dispatch** out);
 SONIC_API int sonic_dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, const int64_t* host_off, struct sonic_ring* const* rings, const int64_t* ring_start,
                                     const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, int64_t* ticket_out);
+/* sonic_dispatch_submit with the request's own sequence-bias table (one request's entries in sonic_set_request_bias's form; the request owns a copy).  The table
+ * reaches the prefill of whichever batch the request lands in.  SONIC_ERR_INVALID unless every handle of the dispatcher has option request_bias on, and for a
+ * table that breaks the caps; sonic_last_error(NULL) of the calling thread says which. */
+SONIC_API int sonic_dispatch_submit_bias(sonic_dispatch* d, const int16_t* host_pcm, const int64_t* host_off, struct sonic_ring* const* rings, const int64_t* ring_start,
+                                         const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, const int32_t* seq_ids,
+                                         const int32_t* seq_off, const float* bias, int n_seq, int64_t* ticket_out);
 SONIC_API int sonic_dispatch_cancel(sonic_dispatch* d, int64_t ticket);                 /* queued requests only */
 /* next completed request in completion order; blocks up to timeout_ms (< 0: until one completes or the dispatcher is closed and drained); *ticket_out = 0: none */
 SONIC_API int sonic_dispatch_next(sonic_dispatch* d, int timeout_ms, int64_t* ticket_out, int32_t* status_out, int32_t* out_ids, int out_cap, int32_t* n_out,
@@ -391,6 +416,12 @@ SONIC_API int sonic_test_greedy_lp(sonic_engine* e, const float* slabs, int kspl
 SONIC_API int sonic_test_greedy_guard(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const int32_t* hist, int hist_ld, const int32_t* hist_len,
                                       float repetition_penalty, int no_repeat_ngram_size, const int32_t* suppress, int n_suppress, const int32_t* force_ids,
                                       int32_t* tok_out, float* logits_out, float* lp_out);
+/* the same launch through the bias instantiation (greedy_kernel<T, LP, true, true>): sonic_test_greedy_guard's arguments plus the B rows' tables in
+ * sonic_set_request_bias's packed form (req_off[B + 1]) */
+SONIC_API int sonic_test_greedy_bias(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const int32_t* hist, int hist_ld, const int32_t* hist_len,
+                                     float repetition_penalty, int no_repeat_ngram_size, const int32_t* suppress, int n_suppress, const int32_t* force_ids,
+                                     const int32_t* seq_ids, const int32_t* seq_off, const float* bias, const int32_t* req_off,
+                                     int32_t* tok_out, float* logits_out, float* lp_out);
 SONIC_API int sonic_test_attention(sonic_engine* e, const float* q, const float* k, const float* v, float* out,
                          int B, int Tq, int Tk, int Hq, int Hkv, int hd, int causal);
 SONIC_API int sonic_test_decode_attention(sonic_engine* e, const float* q, const float* k, const float* v, float* out,

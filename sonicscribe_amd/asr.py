@@ -185,22 +185,24 @@ class AudioStream:
         c = self._chunks.get(int(chunk_id))
         return None if c is None else (c[0], c[1])
 
-    def submit_samples(self, first: int, n: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None, detailed: bool = False) -> "Future[str]":
+    def submit_samples(self, first: int, n: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None, detailed: bool = False,
+                       sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None) -> "Future[str]":
         """Transcribe ring samples [first, first + n) (the >30 s split of connection_manager.py:206-214 cuts at byte offsets, not chunks).
         detailed (a model built with token_logprobs=True): the future gives a Transcription instead of the text."""
         m = self.model
         m._check_detailed(detailed)
+        bias = m._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost)
         windows = [self.ring.slice(first + s, e - s) for s, e in frontend.split_windows(n, m.dims)]
         n_audio, _ = frontend.request_audio_tokens(n, m.dims)
         prompt = m.prompt.build(frontend.build_instruction(hotwords), n_audio)
-        inner = m._dispatcher.submit(windows, prompt, int(max_new_tokens), replica=self.replica, want_logprobs=detailed)
+        inner = m._dispatcher.submit(windows, prompt, int(max_new_tokens), replica=self.replica, want_logprobs=detailed, **({"bias": bias} if bias else {}))
         return _text_future(inner, m.prompt.decode, detailed)
 
     def submit_chunks(self, start_chunk_id: int, end_chunk_id: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None,
-                      detailed: bool = False) -> "Future[str]":
+                      detailed: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None) -> "Future[str]":
         """Transcribe chunks start..end inclusive (audio_manager.py:76-79 get_chunks_by_range + :115-123 concatenation)."""
         first, n = self.chunk_range_samples(start_chunk_id, end_chunk_id)
-        return self.submit_samples(first, n, max_new_tokens, hotwords, detailed)
+        return self.submit_samples(first, n, max_new_tokens, hotwords, detailed, sequence_bias, bad_words_ids, hotword_boost)
 
     async def transcribe_chunks(self, start_chunk_id: int, end_chunk_id: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None) -> str:
         return await asyncio.wrap_future(self.submit_chunks(start_chunk_id, end_chunk_id, max_new_tokens, hotwords))
@@ -215,11 +217,14 @@ class ASRModel:
     def __init__(self, checkpoint_dir: str, device: str = "cuda", mode: str = "native",
                  cpu_threads: Optional[int] = None, cpu_interop_threads: Optional[int] = None,
                  *, max_batch: int = 32, max_ctx: int = 1024, slots: int = DEFAULT_SLOTS, continuous: bool = DEFAULT_CONTINUOUS, decoders: int = 1, bulk: bool = False, native_dispatch: Optional[bool] = None, token_logprobs: bool = False,
-                 repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None, _dims: Optional[ModelDims] = None,
+                 repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None,
+                 request_bias: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: float = 0.0, _dims: Optional[ModelDims] = None,
                  _synthetic_seed: Optional[int] = None, _allow_synthetic_prompt: bool = False, _options: Optional[Dict[str, int]] = None,
                  _engine_mode: Optional[int] = None):
         """The reference's ASRModel surface over the HIP engine.  `repetition_penalty`, `no_repeat_ngram_size`, `suppress_tokens`: None = the value of the
-        checkpoint's generation_config.json, anything else overrides it (genconfig.py).  The arguments with a leading underscore are not part of the
+        checkpoint's generation_config.json, anything else overrides it (genconfig.py).  `request_bias`: requests may bring their own sequence-bias table
+        (HF's sequence_bias / bad_words_ids, and `hotword_boost` > 0: the call's hotwords as entries; reqbias.py); `sequence_bias`, `bad_words_ids`,
+        `hotword_boost` here are defaults for every request and switch `request_bias` on.  The arguments with a leading underscore are not part of the
         supported surface: they exist for the test-suite and the benchmark and may change without notice.  `_engine_mode` in particular (an engine.MODE_*
         value in place of the one `mode` selects) is unsupported outside the tests: MODE_F32 has no slots, so it needs slots=1, continuous=False."""
         if mode not in ["native", "int8"]:
@@ -288,6 +293,19 @@ class ASRModel:
             if self.generation_guards.active:
                 g = self.generation_guards
                 eng.set_generation(g.repetition_penalty, g.no_repeat_ngram_size, g.suppress_tokens)
+        # request_bias: every request may carry a sequence-bias table of its own (engine option of the same name, set before the slots exist).  The three
+        # value arguments are defaults for every request and switch the option on.  Combined per call as lists - these sequence_bias entries, these bad words, the
+        # call's own, then the hotword entries - and de-duplicated as HF de-duplicates one list (reqbias.combine)
+        from . import reqbias
+        self.hotword_boost = float(hotword_boost or 0.0)
+        self._default_bias = reqbias.RequestBias(sequence_bias, bad_words_ids, self._eos_ids(), vocab=self.dims.vocab)
+        reqbias.hotword_entries([], self.hotword_boost, None)         # (validates the value)
+        self.request_bias = bool(request_bias) or bool(self._default_bias) or self.hotword_boost > 0
+        if self.request_bias and bool(bulk):
+            raise ValueError("request_bias is not supported with bulk=True: the bulk pipeline carries no per-request tables")
+        if self.request_bias:
+            for eng in self.models:
+                eng.set_option("request_bias", 1)
         self.model = self.models[0]                  # main.py:84-86 checks and deletes `.model`
         # continuous: `decoders` handles per replica run a greedy loop over max_batch rows each, the other handles prefill (>= 1).  Streaming:
         # decoders=1, slots=2.  Bulk transcription of many segments: max_batch=64, decoders=3, slots=4 (the bench's pipeline shape since round 5; decoders=2, slots=3 before).
@@ -325,21 +343,51 @@ class ASRModel:
         n_audio, _ = frontend.request_audio_tokens(len(pcm), self.dims)
         return pcm, [pcm[s:e] for s, e in wins], n_audio
 
+    def _eos_ids(self) -> List[int]:
+        return [int(t) for t in self.dims.eos_ids]       # (NoBadWordsLogitsProcessor drops a bad word equal to [eos])
+
+    def _request_bias(self, hotwords, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None):
+        """One call's table: the constructor's defaults, the call's sequence_bias / bad_words_ids, then - for a boost > 0 (None: the constructor's) - the call's
+        hotwords as entries (reqbias.hotword_entries: each hotword as it stands and with one leading space, every prefix of 1 .. 8 tokens).  None when nothing
+        applies.  ValueError naming request_bias when the call gives a value and the model was built without the option."""
+        from . import reqbias
+        explicit = sequence_bias is not None or bad_words_ids is not None or (hotword_boost is not None and float(hotword_boost) != 0.0)
+        if explicit and not getattr(self, "request_bias", False):
+            raise ValueError("sequence_bias / bad_words_ids / hotword_boost need a model built with request_bias=True (ASRModel(..., request_bias=True))")
+        if not getattr(self, "request_bias", False):
+            return None
+        if getattr(self, "bulk", False):
+            raise ValueError("a sequence bias is not supported with bulk=True")
+        boost = self.hotword_boost if hotword_boost is None else float(hotword_boost)
+        hot = None
+        if boost != 0.0 and hotwords:
+            if not isinstance(self.prompt, HFPrompt):
+                raise ValueError("hotword_boost needs a tokenizer (a checkpoint with its processor): the synthetic prompt has none")
+            tok = self.prompt.processor.tokenizer
+            hot = reqbias.RequestBias(reqbias.hotword_entries(hotwords, boost, lambda t: tok.encode(t, add_special_tokens=False)), vocab=self.dims.vocab)
+        else:
+            reqbias.hotword_entries([], boost, None)     # (validates the value)
+        call = reqbias.RequestBias(sequence_bias, bad_words_ids, self._eos_ids(), vocab=self.dims.vocab) if explicit else None
+        out = reqbias.combine(self._default_bias, call, hot)
+        return out if out else None
+
     def _check_detailed(self, detailed: bool):
         if detailed and not getattr(self, "token_logprobs", False):
             raise ValueError("detailed=True needs a model built with token_logprobs=True (ASRModel(..., token_logprobs=True))")
 
     def submit(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None,
-               session: Optional[str] = None, detailed: bool = False) -> "Future[str]":
+               session: Optional[str] = None, detailed: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None) -> "Future[str]":
         """Non-blocking form of transcribe(): queues the request on a replica and returns a Future of the transcript.  `session`
         (e.g. the WebSocket client id) keeps a session's decodes on one GPU.  detailed (a model built with token_logprobs=True): the future
-        gives a Transcription - text, token_ids, token_logprobs, avg_logprob - instead of the text."""
+        gives a Transcription - text, token_ids, token_logprobs, avg_logprob - instead of the text.  sequence_bias / bad_words_ids / hotword_boost (a model
+        built with request_bias=True): this request's own table, on top of the constructor's defaults (_request_bias)."""
         if not hasattr(self, "model"):
             raise RuntimeError("ASR model has been released")
         self._check_detailed(detailed)
+        bias = self._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost)
         pcm, windows, n_audio = self._prepare(audio_tensor, sampling_rate)
         prompt = self.prompt.build(frontend.build_instruction(hotwords), n_audio)
-        inner = self._dispatcher.submit(windows, prompt, int(max_new_tokens), session=session, want_logprobs=detailed)
+        inner = self._dispatcher.submit(windows, prompt, int(max_new_tokens), session=session, want_logprobs=detailed, **({"bias": bias} if bias else {}))
         return _text_future(inner, self.prompt.decode, detailed)
 
     def open_stream(self, session: str, buffer_seconds: float = 30.0, margin_seconds: float = 10.0, sampling_rate: int = 16000) -> AudioStream:
@@ -353,19 +401,22 @@ class ASRModel:
         return AudioStream(self, session, self._dispatcher.home(session), buffer_seconds, margin_seconds, sampling_rate=sampling_rate)
 
     async def transcribe_async(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128,
-                               hotwords: Optional[List[str]] = None, session: Optional[str] = None, detailed: bool = False) -> str:
+                               hotwords: Optional[List[str]] = None, session: Optional[str] = None, detailed: bool = False,
+                               sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None) -> str:
         """Awaitable transcribe() for the asyncio callers (connection_manager.py:127-245): the event loop is not blocked while the
         device works, so all sessions' partial and final decodes can be in flight (and batched) together."""
-        return await asyncio.wrap_future(self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, session, detailed))
+        return await asyncio.wrap_future(self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, session, detailed, sequence_bias, bad_words_ids, hotword_boost))
 
     def transcribe(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128,
-                   hotwords: Optional[List[str]] = None, return_debug_info: bool = False) -> Union[str, Dict[str, Any]]:
+                   hotwords: Optional[List[str]] = None, return_debug_info: bool = False,
+                   sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None) -> Union[str, Dict[str, Any]]:
         if not hasattr(self, "model"):
             raise RuntimeError("ASR model has been released")
         t0 = time.time()
         try:
             want = bool(return_debug_info and getattr(self, "token_logprobs", False))
-            res = self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, detailed=want).result()
+            res = self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, detailed=want, sequence_bias=sequence_bias, bad_words_ids=bad_words_ids,
+                              hotword_boost=hotword_boost).result()
             det, transcript = (res, res.text) if want else (None, res)
             elapsed = time.time() - t0
             if return_debug_info:
@@ -388,8 +439,10 @@ class ASRModel:
             raise
 
     def transcribe_batch(self, audios: Sequence[Any], sampling_rate: int = 16000, max_new_tokens: Union[int, Sequence[int]] = 128,
-                         hotwords: Optional[List[str]] = None) -> List[str]:
+                         hotwords: Optional[List[str]] = None, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None) -> List[str]:
         """Batched extension (the reference is B=1 per call): one device batch, per-segment results identical to transcribe()."""
+        bias = self._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost)
+        kw = {"request_bias": [bias] * len(audios)} if bias else {}
         mn = [int(max_new_tokens)] * len(audios) if isinstance(max_new_tokens, int) else [int(x) for x in max_new_tokens]
         segs, req_win, prompts = [], [0], []
         instruction = frontend.build_instruction(hotwords)
@@ -399,14 +452,15 @@ class ASRModel:
             req_win.append(len(segs))
             prompts.append(self.prompt.build(instruction, n_audio))
         if len(self.models) == 1 and not self.continuous:
-            ids, _ = self.model.transcribe_batch(segs, prompts, mn, req_win=req_win)
+            ids, _ = self.model.transcribe_batch(segs, prompts, mn, req_win=req_win, **kw)
         else:            # independent segments: spread over the replicas (least-loaded placement), results in input order
-            futs = [self._dispatcher.submit(segs[req_win[i]:req_win[i + 1]], prompts[i], mn[i]) for i in range(len(audios))]
+            futs = [self._dispatcher.submit(segs[req_win[i]:req_win[i + 1]], prompts[i], mn[i], **({"bias": bias} if bias else {})) for i in range(len(audios))]
             ids = [f.result() for f in futs]
         return [self.prompt.decode(i).strip() for i in ids]
 
     def transcribe_file(self, audio, vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
-                        max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filename: str = "", sampling_rate: int = 16000):
+                        max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filename: str = "", sampling_rate: int = 16000,
+                        sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None):
         """The body of the reference's /transcribe/file endpoint (main.py:193-649) as a generator of its records (dicts with the
         reference's keys: initialization, segments_summary, segment_result / segment_error in segment order, final_summary).  `audio`:
         mono int16 PCM at `sampling_rate`, or the reference's float tensor [1, N] of int16 / 32768 values; `vad`: a vad.VADProcessor.  The
@@ -414,14 +468,16 @@ class ASRModel:
         VAD-scored there, and every segment is queued at once as a range of that ring on this model's scheduler; the ring is destroyed when
         the generator is exhausted or closed (filemode.py).  Sizes and times in the records are those of the 16 kHz content."""
         from . import filemode
-        return filemode.transcribe_file(self, audio, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filename, sampling_rate)
+        return filemode.transcribe_file(self, audio, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filename, sampling_rate,
+                                        sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotword_boost=hotword_boost)
 
     def transcribe_files(self, audios: Sequence[Any], vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                          max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filenames: Optional[Sequence[str]] = None,
-                         sampling_rate: int = 16000):
+                         sampling_rate: int = 16000, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None):
         """transcribe_file for several files: all VAD passes in one device call, one record iterator per file (filemode.transcribe_files)."""
         from . import filemode
-        return filemode.transcribe_files(self, audios, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filenames, sampling_rate)
+        return filemode.transcribe_files(self, audios, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filenames, sampling_rate,
+                                         sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotword_boost=hotword_boost)
 
     def get_model_info(self) -> Dict[str, Any]:
         """asr.py:490-513: the reference's keys for a GPU device (`cuda_version` carries the HIP runtime version: torch.version.cuda is

@@ -34,6 +34,9 @@
 
 #include "../../include/sonic_hip.h"
 extern "C" int engine_token_logprobs_on(sonic_engine* e);   // engine.cpp
+extern "C" int engine_request_bias_on(sonic_engine* e);     // engine.cpp: option request_bias on this handle
+extern "C" int engine_bias_validate(sonic_engine* e, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n);   // engine.cpp: one request's table against the caps and this handle's vocabulary
+extern "C" int engine_thread_fail(int code, const char* msg);   // engine.cpp: the calling thread's sonic_last_error(NULL)
 
 namespace {
 
@@ -45,6 +48,7 @@ struct Req {
     std::vector<int32_t> prompt; int max_new = 0;
     int status = -1; std::string err; std::vector<int32_t> ids;    // result
     std::vector<float> lp;                                         // ... and, with option token_logprobs on the handles, every token's log-probability
+    std::vector<int32_t> b_ids, b_off; std::vector<float> b_val;  // its own sequence-bias table (sonic_dispatch_submit_bias): ids, offsets [n + 1] (empty: none), biases
     bool cancelled = false;
 };
 typedef std::shared_ptr<Req> ReqP;
@@ -57,6 +61,7 @@ struct sonic_dispatch {
     int n_rows = 0, pre_cap = 0;
     bool adaptive_tiles = true;
     bool lp = false;                                               // every handle has option token_logprobs on
+    bool bias = false;                                             // every handle has option request_bias on
     std::mutex mu;
     std::condition_variable cv;                                    // queue, hand-overs, free rows, state
     std::condition_variable cv_done;                               // completions
@@ -105,6 +110,20 @@ int prefill_batch(sonic_dispatch* d, sonic_engine* h, const std::vector<ReqP>& b
     if (d->adaptive_tiles) (void)sonic_set_option(h, "gemm_small_eff", busy ? 0 : 75);
     int rc = any_ring ? sonic_stage_mixed(h, pcm.data(), off.data(), rings.data(), rstart.data(), rn.data(), W, req_win.data(), R)
                       : sonic_stage_pcm(h, pcm.data(), off.data(), W);
+    bool any_bias = false;
+    for (auto& r : batch) any_bias = any_bias || !r->b_val.empty();
+    if (rc == SONIC_OK && any_bias) {                              // the requests' tables in sonic_set_request_bias's per-batch form; the prefill below consumes them
+        std::vector<int32_t> s_ids, s_off{0}, r_off{0}; std::vector<float> s_val;
+        for (auto& r : batch) {
+            for (size_t i = 0; i + 1 < r->b_off.size(); ++i) {
+                s_ids.insert(s_ids.end(), r->b_ids.begin() + r->b_off[i], r->b_ids.begin() + r->b_off[i + 1]);
+                s_off.push_back((int32_t)s_ids.size());
+            }
+            s_val.insert(s_val.end(), r->b_val.begin(), r->b_val.end());
+            r_off.push_back((int32_t)s_val.size());
+        }
+        rc = sonic_set_request_bias(h, s_ids.data(), s_off.data(), s_val.data(), r_off.data(), R);
+    }
     if (rc == SONIC_OK) rc = sonic_prefill(h, req_win.data(), R, ids.data(), poff.data(), mn.data(), 0);
     if (rc != SONIC_OK && err) *err = sonic_last_error(h);
     return rc;
@@ -279,6 +298,8 @@ SONIC_API int sonic_dispatch_create(sonic_engine* const* decoders, int n_dec, so
     d->n_rows = rows; d->pre_cap = cap; d->adaptive_tiles = adaptive_tiles != 0;
     d->lp = true;
     for (int i = 0; i < n_dec + n_pre; ++i) d->lp = d->lp && engine_token_logprobs_on(i < n_dec ? decoders[i] : prefills[i - n_dec]);
+    d->bias = true;
+    for (int i = 0; i < n_dec + n_pre; ++i) d->bias = d->bias && engine_request_bias_on(i < n_dec ? decoders[i] : prefills[i - n_dec]);
     d->free_rows.assign(n_dec, rows); d->hand.resize(n_dec);
     for (int i = 0; i < n_dec; ++i) {
         const int rc = sonic_service_begin(d->dec[i]);
@@ -293,8 +314,9 @@ SONIC_API int sonic_dispatch_create(sonic_engine* const* decoders, int n_dec, so
 // One request of W windows.  Window w: host samples host_pcm[host_off[w] .. host_off[w + 1]) (int16, already peak-normalised over the request, as
 // sonic_stage_pcm takes them) when rings is NULL or rings[w] is NULL, else samples [ring_start[w], ring_start[w] + ring_n[w]) of rings[w] (raw wire
 // PCM, normalised on the device over the request's windows).  Everything is copied before the call returns.
-SONIC_API int sonic_dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, const int64_t* host_off, sonic_ring* const* rings, const int64_t* ring_start,
-                                    const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, int64_t* ticket_out) {
+static int dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, const int64_t* host_off, sonic_ring* const* rings, const int64_t* ring_start,
+                           const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, const int32_t* seq_ids, const int32_t* seq_off,
+                           const float* bias, int n_seq, int64_t* ticket_out) {
     if (!d || !ticket_out || W < 1 || !prompt_ids || prompt_len < 1 || max_new < 1 || !host_off) return SONIC_ERR_INVALID;
     if (rings && (!ring_start || !ring_n)) return SONIC_ERR_INVALID;
     auto r = std::make_shared<Req>();
@@ -307,6 +329,8 @@ SONIC_API int sonic_dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, 
         for (int w = 0; w < W; ++w) r->any_ring = r->any_ring || rings[w];
     }
     r->prompt.assign(prompt_ids, prompt_ids + prompt_len); r->max_new = max_new;
+    if (n_seq > 0) { r->b_off.assign(seq_off, seq_off + n_seq + 1); r->b_ids.assign(seq_ids + seq_off[0], seq_ids + seq_off[n_seq]); r->b_val.assign(bias, bias + n_seq);
+                     for (auto& o : r->b_off) o -= seq_off[0]; }
     std::unique_lock<std::mutex> lk(d->mu);
     if (d->stop) return SONIC_ERR_INVALID;
     if (d->failed) return d->failed;
@@ -315,6 +339,23 @@ SONIC_API int sonic_dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, 
     *ticket_out = r->ticket;
     d->cv.notify_all();
     return SONIC_OK;
+}
+
+SONIC_API int sonic_dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, const int64_t* host_off, sonic_ring* const* rings, const int64_t* ring_start,
+                                    const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, int64_t* ticket_out) {
+    return dispatch_submit(d, host_pcm, host_off, rings, ring_start, ring_n, W, prompt_ids, prompt_len, max_new, nullptr, nullptr, nullptr, 0, ticket_out);
+}
+// sonic_dispatch_submit with the request's own sequence-bias table (n_seq entries in sonic_set_request_bias's form for one request; the request owns a copy): the
+// prefill thread hands it to the prefill of the batch the request lands in.  SONIC_ERR_INVALID unless every handle of the dispatcher has option request_bias on,
+// and for a table that breaks the caps; sonic_last_error(NULL) of the calling thread says which
+SONIC_API int sonic_dispatch_submit_bias(sonic_dispatch* d, const int16_t* host_pcm, const int64_t* host_off, sonic_ring* const* rings, const int64_t* ring_start,
+                                         const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, const int32_t* seq_ids,
+                                         const int32_t* seq_off, const float* bias, int n_seq, int64_t* ticket_out) {
+    if (!d) return SONIC_ERR_INVALID;
+    if (!d->bias) return engine_thread_fail(SONIC_ERR_INVALID, "sonic_dispatch_submit_bias: option request_bias is off on a handle of this dispatcher (set it on the owner before its slots are created)");
+    if (n_seq < 0 || (n_seq > 0 && (!seq_ids || !seq_off || !bias))) return SONIC_ERR_INVALID;
+    if (n_seq > 0) { const int rc = engine_bias_validate(d->pre[0], seq_ids, seq_off, bias, n_seq); if (rc != SONIC_OK) return rc; }
+    return dispatch_submit(d, host_pcm, host_off, rings, ring_start, ring_n, W, prompt_ids, prompt_len, max_new, seq_ids, seq_off, bias, n_seq, ticket_out);
 }
 
 // a request that is still queued leaves the queue (it completes with status SONIC_ERR_INVALID, "cancelled"); one that has reached a handle runs on

@@ -561,6 +561,13 @@ __global__ void assemble_embeds_kernel(const int* src, const bf16_t* table, cons
 // loop then reads the 4 bits of each map that belong to its f32x4 group: a seen score becomes s < 0 ? s * p : s / p (fp32 multiply, correctly rounded
 // fp32 divide), a banned one -inf, in that order, behind the dump (raw logits) and ahead of the compare and the LP sum.  Thread 0 appends the emitted
 // id at hist[b][kv_len[b]].  A row whose scores are all -inf emits token 0 (torch.argmax of equal values).  GUARD = false is the kernel as it was.
+// BIAS (option request_bias; implies GUARD): HF's SequenceBiasLogitsProcessor, with NoBadWordsLogitsProcessor folded in as entries of bias -inf
+// (generation/logits_process.py; the reference's hotwords, backend/asr.py:303-333, are what it serves), on the row's own table GreedyArgs.bias_tab.  Thread e of the
+// prologue decides whether entry e applies to the history (L = 1: always; else L <= len and the last L - 1 ids equal its prefix) and leaves a flag in LDS; the first
+// entry of every last-id group then adds the group's flagged biases to +0.0 in stored order - HF's order: the length-1 value, then the longer sequences in list
+// order - and leaves (id, sum) in the LDS list and the id's bit in a third bitmap, "biased".  The loop reads that map's 4 bits with the others; a set bit scans the
+// list (every lane reads the same word: a broadcast) and adds the sum, once, ahead of guard_score: the bias is HF's first processor.  An unset bit adds nothing
+// (HF adds +0.0 there, which changes no compare and no exponential).  BIAS = false is the kernel as it was, GUARD or not.
 extern __shared__ unsigned g_bits[];
 __device__ __forceinline__ float guard_score(float r, unsigned seen, unsigned banned, float p) {
     if (seen & 1u) r = r < 0.f ? r * p : __fdiv_rn(r, p);
@@ -569,9 +576,15 @@ __device__ __forceinline__ float guard_score(float r, unsigned seen, unsigned ba
 __device__ __forceinline__ void guard_set(unsigned* map, int id, int V) {
     if ((unsigned)id < (unsigned)V) atomicOr(&map[id >> 5], 1u << (id & 31));
 }
+__device__ __forceinline__ float bias_of(const int* ids, const float* sums, int n, int id) {
+    float b = 0.f;
+    for (int k = 0; k < n; ++k) if (ids[k] == id) b = sums[k];      // (ids are unique: one group per last id)
+    return b;
+}
 __device__ __forceinline__ float lp_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-template <typename T, bool LP, bool GUARD = false>
+template <typename T, bool LP, bool GUARD = false, bool BIAS = false>
 __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
+    static_assert(GUARD || !BIAS, "the request bias lives in the guard instantiations (it needs their history)");
     typedef typename ET<T>::v8 V8;
     __shared__ float sv[16];
     __shared__ int si[17];
@@ -588,13 +601,38 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
     f32x4 gw0 = {0.f, 0.f, 0.f, 0.f}, gw1 = {0.f, 0.f, 0.f, 0.f};
     if (a.y && (a.d >> 3) <= 1024 && tid < (a.d >> 3)) { gw0 = *(const f32x4*)(a.norm_w + tid * 8); gw1 = *(const f32x4*)(a.norm_w + tid * 8 + 4); }
     [[maybe_unused]] unsigned* g_seen = nullptr; [[maybe_unused]] unsigned* g_ban = nullptr;
+    [[maybe_unused]] unsigned* g_bia = nullptr; [[maybe_unused]] int* q_id = nullptr; [[maybe_unused]] float* q_sum = nullptr; [[maybe_unused]] int q_n = 0;
     if constexpr (GUARD) {
         const int nw = (a.V + 31) >> 5;
         g_seen = g_bits; g_ban = g_bits + nw;
-        for (int w = tid; w < 2 * nw; w += 1024) g_bits[w] = 0u;
+        for (int w = tid; w < (BIAS ? 3 : 2) * nw; w += 1024) g_bits[w] = 0u;
         __syncthreads();
         const int* h = a.hist + (long)b * a.hist_ld;
         const int len = min(max(a.kv_len[b], 0), a.hist_ld), n = a.ngram;
+        if constexpr (BIAS) {
+            // dynamic LDS behind the three maps: the group sums' ids [256], the sums [256], the entries' flags [256] (greedy_guard_lds)
+            g_bia = g_bits + 2 * nw; q_id = (int*)(g_bits + 3 * nw); q_sum = (float*)(q_id + BIAS_MAX_ENTRIES);
+            int* q_flag = q_id + 2 * BIAS_MAX_ENTRIES;
+            const int* tab = a.bias_tab + 64 + (long)b * BIAS_ROW_WORDS;
+            q_n = min(max(a.bias_tab[b], 0), BIAS_MAX_ENTRIES);
+            const int* en = tab + tid * BIAS_ENTRY_WORDS;
+            int last = -1;
+            if (tid < q_n) {
+                last = en[0];
+                const int L = en[1];
+                bool m = L >= 1 && L <= BIAS_MAX_LEN && L <= len;          // (L == len + 1 would fit its prefix; HF ignores it, so does this)
+                if (m) { const int* tail = h + len - (L - 1); for (int k = 0; k < L - 1; ++k) m = m && tail[k] == en[3 + k]; }
+                q_flag[tid] = (L == 1 || m) ? 1 : 0;                       // a single id has no prefix to match: it applies whatever the history holds
+                q_id[tid] = -1;
+            }
+            __syncthreads();
+            if (tid < q_n && (unsigned)last < (unsigned)a.V && (tid == 0 || en[-BIAS_ENTRY_WORDS] != last)) {      // the first entry of its last-id group
+                float acc = 0.f; bool any = false;
+                for (int k = tid; k < q_n && tab[k * BIAS_ENTRY_WORDS] == last; ++k)
+                    if (q_flag[k]) { acc += __int_as_float(tab[k * BIAS_ENTRY_WORDS + 2]); any = true; }
+                if (any) { q_id[tid] = last; q_sum[tid] = acc; guard_set(g_bia, last, a.V); }
+            }
+        }
         for (int j = tid; j < len; j += 1024) guard_set(g_seen, h[j], a.V);
         if (n > 0) {                              // every n-gram h[j .. j + n) of the history whose first n - 1 ids are the history's last n - 1 bans its last id
             const int* last = h + len - (n - 1);  // (read only when an n-gram exists: j + n <= len)
@@ -626,10 +664,13 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
             for (int ks = 2; ks < a.ksplit; ++ks) t += *(const f32x4*)(lg + ks * ks_stride + i);
             [[maybe_unused]] unsigned sb = 0u, bb = 0u;      // GUARD: the group's 4 bits of each map (i is a multiple of 4)
             if constexpr (GUARD) { sb = g_seen[i >> 5] >> (i & 31); bb = g_ban[i >> 5] >> (i & 31); }
+            [[maybe_unused]] unsigned qb = 0u;               // BIAS: the group's 4 bits of the "biased" map
+            if constexpr (BIAS) qb = (g_bia[i >> 5] >> (i & 31)) & 15u;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float r = rT<T>(t[j]);              // logits are T in the reference, compared as fp32
                 if (dump) dump[i + j] = r;
+                if constexpr (BIAS) if ((qb >> j) & 1u) r += bias_of(q_id, q_sum, q_n, i + j);      // HF's order: the bias first, the penalty sees the biased score
                 if constexpr (GUARD) r = guard_score(r, sb >> j, bb >> j, a.rep_penalty);
                 if (r > best) { best = r; bi = i + j; }   // strict > keeps the first maximum within a thread
                 if constexpr (LP) v[u][j] = r;
@@ -691,6 +732,7 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
                     if (a.ksplit > 1) f += lg[ks_stride + tok];
                     for (int ks = 2; ks < a.ksplit; ++ks) f += lg[ks * ks_stride + tok];
                     lt = rT<T>(f);
+                    if constexpr (BIAS) if ((g_bia[tok >> 5] >> (tok & 31)) & 1u) lt += bias_of(q_id, q_sum, q_n, tok);
                     if constexpr (GUARD) lt = guard_score(lt, g_seen[tok >> 5] >> (tok & 31), g_ban[tok >> 5] >> (tok & 31), a.rep_penalty);
                 }
                 a.out_lp[(long)b * a.out_ld + a.n_new[b]] = (float)(((double)lt - (double)best) - log((double)lp_sum));
@@ -851,8 +893,19 @@ __global__ void hist_prompt_kernel(const int* src, const int* tok_seq, const int
 void launch_hist_prompt(const int* src, const int* tok_seq, const int* tok_pos, int n_tok, int audio_id, int* hist, int hist_ld, hipStream_t s) {
     if (n_tok > 0) hipLaunchKernelGGL(hist_prompt_kernel, dim3((n_tok + 255) / 256), dim3(256), 0, s, src, tok_seq, tok_pos, n_tok, audio_id, hist, hist_ld);
 }
-size_t greedy_guard_lds(int V) { return (size_t)2 * ((V + 31) / 32) * 4; }
+size_t greedy_guard_lds(int V, bool bias) { return (size_t)(bias ? 3 : 2) * ((V + 31) / 32) * 4 + (bias ? (size_t)3 * BIAS_MAX_ENTRIES * 4 : 0); }
 void launch_greedy(const GreedyArgs& a, hipStream_t s) {
+    if (a.hist && a.bias_tab) {                                                                                  // request bias: the BIAS instantiations (a third bitmap and the matched list)
+        const size_t lds = greedy_guard_lds(a.V, true);
+        if (a.out_lp) {
+            if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, true, true, true>), dim3(a.B), dim3(1024), lds, s, a); return; }
+            DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, true, true, true>), dim3(a.B), dim3(1024), lds, s, a));
+            return;
+        }
+        if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, false, true, true>), dim3(a.B), dim3(1024), lds, s, a); return; }
+        DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, false, true, true>), dim3(a.B), dim3(1024), lds, s, a));
+        return;
+    }
     if (a.hist) {                                                                                                // generation guards: the GUARD instantiations, two bitmaps of dynamic LDS
         const size_t lds = greedy_guard_lds(a.V);
         if (a.out_lp) {

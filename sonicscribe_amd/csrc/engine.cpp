@@ -374,7 +374,8 @@ int gen_apply(sonic_engine* e, float penalty, int ngram, const int32_t* suppress
     if (on && greedy_guard_lds(e->d.vocab) > 60000) return fail(e, SONIC_ERR_UNSUPPORTED, "sonic_set_generation: a vocabulary of %d ids does not fit the guard bitmaps", e->d.vocab);
     HIPC(e, hipSetDevice(e->device));
     HIPC(e, stream_sync(e));
-    if (on && !e->hist) { TRY(dalloc(e, &e->hist, (size_t)64 * e->max_ctx)); TRY(dalloc(e, &e->gen_suppress_d, (size_t)GEN_MAX_SUPPRESS)); HIPC(e, stream_sync(e)); }
+    if (on && !e->hist) { TRY(dalloc(e, &e->hist, (size_t)64 * e->max_ctx)); HIPC(e, stream_sync(e)); }          // (option request_bias may have brought the history already)
+    if (on && !e->gen_suppress_d) { TRY(dalloc(e, &e->gen_suppress_d, (size_t)GEN_MAX_SUPPRESS)); HIPC(e, stream_sync(e)); }
     if (n_suppress > 0) HIPC(e, h2d(e, e->gen_suppress_d, suppress, (size_t)n_suppress * 4));
     e->gen_penalty = penalty; e->gen_ngram = ngram; e->gen_suppress.assign(suppress, suppress + n_suppress); e->gen_on = on;
     drop_graphs(e);                                      // the greedy kernel and its arguments are part of every captured chunk
@@ -393,6 +394,113 @@ int gen_busy(sonic_engine* e, const char* who) {
     }
     return SONIC_OK;
 }
+// ---- option request_bias: HF's SequenceBiasLogitsProcessor / NoBadWordsLogitsProcessor (generation/logits_process.py) with one table per request -
+// the reference's hotwords (backend/asr.py:303-333) as a bias on the scores instead of a sentence in the prompt.  The caller holds the lock and has asked gen_busy.
+int bias_enable(sonic_engine* e, int on) {
+    if (on && greedy_guard_lds(e->d.vocab, true) > 60000) return fail(e, SONIC_ERR_UNSUPPORTED, "request_bias: a vocabulary of %d ids does not fit the bias bitmaps", e->d.vocab);
+    HIPC(e, hipSetDevice(e->device));
+    HIPC(e, stream_sync(e));
+    if (on) {
+        if (!e->hist) TRY(dalloc(e, &e->hist, (size_t)64 * e->max_ctx));
+        if (!e->bias_tab) TRY(dalloc(e, &e->bias_tab, (size_t)BIAS_TAB_WORDS));                      // (zero-filled: every row starts without a table)
+        if (!e->bias_h && hipHostMalloc((void**)&e->bias_h, (size_t)BIAS_TAB_WORDS * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(e, SONIC_ERR_OOM, "request_bias: pinned host memory exhausted"); }
+        if (!e->bias_ev) HIPC(e, hipEventCreateWithFlags(&e->bias_ev, hipEventDisableTiming));
+        HIPC(e, stream_sync(e));
+    }
+    e->opt_request_bias = on ? 1 : 0; e->bias_pending = -1; e->bias_take = false;
+    drop_graphs(e);                                      // the greedy kernel and its arguments are part of every captured chunk
+    return SONIC_OK;
+}
+int bias_pack(sonic_engine* e, const char* who, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n, int V, int* row, int* count) {
+    if (n < 0 || n > BIAS_MAX_ENTRIES) return fail(e, SONIC_ERR_INVALID, "%s: a request's table holds %d entries (at most %d; nothing is truncated)", who, n, BIAS_MAX_ENTRIES);
+    if (n > 0 && (!seq_ids || !seq_off || !bias)) return fail(e, SONIC_ERR_INVALID, "%s: null table", who);
+    struct Ent { const int32_t* ids; int L; float b; };
+    std::vector<Ent> v;
+    for (int i = 0; i < n; ++i) {
+        const int L = seq_off[i + 1] - seq_off[i];
+        if (L < 1 || L > BIAS_MAX_LEN) return fail(e, SONIC_ERR_INVALID, "%s: entry %d has %d ids (1 .. %d)", who, i, L, BIAS_MAX_LEN);
+        const int32_t* ids = seq_ids + seq_off[i];
+        for (int k = 0; k < L; ++k) if (ids[k] < 0 || ids[k] >= V) return fail(e, SONIC_ERR_INVALID, "%s: token id %d out of vocabulary (%d)", who, ids[k], V);
+        if (std::isnan(bias[i]) || bias[i] == INFINITY) return fail(e, SONIC_ERR_INVALID, "%s: entry %d has bias %g (finite values, or -inf for a bad word)", who, i, (double)bias[i]);
+        bool dup = false;                                // HF's list -> dict conversion: the last bias of equal sequences wins, at the first one's position
+        for (Ent& o : v) if (o.L == L && !memcmp(o.ids, ids, (size_t)L * 4)) { o.b = bias[i]; dup = true; break; }
+        if (!dup) v.push_back(Ent{ids, L, bias[i]});
+    }
+    // grouped by last id; inside a group the length-1 entry first (HF starts from length_1_bias), then list order: the order the kernel's one thread adds in
+    std::stable_sort(v.begin(), v.end(), [](const Ent& a, const Ent& b) {
+        const int la = a.ids[a.L - 1], lb = b.ids[b.L - 1];
+        if (la != lb) return la < lb;
+        return (a.L == 1) > (b.L == 1);
+    });
+    for (size_t i = 0; i < v.size(); ++i) {
+        int* w = row + i * BIAS_ENTRY_WORDS;
+        w[0] = v[i].ids[v[i].L - 1]; w[1] = v[i].L; memcpy(&w[2], &v[i].b, 4);
+        for (int k = 0; k < BIAS_MAX_LEN - 1; ++k) w[3 + k] = k < v[i].L - 1 ? v[i].ids[k] : -1;
+    }
+    *count = (int)v.size();
+    return SONIC_OK;
+}
+// The tables of the R requests of the next prefill on this handle (sonic_prefill / sonic_prefill_enqueue / sonic_run_staged[_async] / sonic_transcribe_*), which
+// consumes them: a later batch starts without tables.  Request r's entries are seq_off[req_off[r]] .. seq_off[req_off[r + 1]] of seq_ids, with bias[req_off[r] ..].
+extern "C" int sonic_set_request_bias(sonic_engine* e, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, const int32_t* req_off, int R) {
+    if (!e) return SONIC_ERR_INVALID;
+    { std::lock_guard<std::mutex> lk(e->a_mu); if (e->a_pending || e->a_running) return fail(nullptr, SONIC_ERR_INVALID, "sonic_set_request_bias: an asynchronous run of this handle is in flight"); }
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipGetLastError();
+    if (!e->opt_request_bias || !e->bias_tab)
+        return fail(e, SONIC_ERR_INVALID, "sonic_set_request_bias: option request_bias is off on this handle (sonic_set_option(e, \"request_bias\", 1) on the owner before its slots are created)");
+    e->bias_pending = -1;
+    if (R < 1 || R > e->Bm || R > 64 || !req_off || req_off[0] != 0) return fail(e, SONIC_ERR_INVALID, "sonic_set_request_bias: %d requests (1 .. %d), offsets from 0", R, e->Bm);
+    HIPC(e, hipSetDevice(e->device));
+    if (e->bias_ev_busy) { HIPC(e, hipEventSynchronize(e->bias_ev)); e->bias_ev_busy = false; }      // the previous batch's copies out of bias_h
+    for (int r = 0; r < 64; ++r) e->bias_h[r] = 0;
+    for (int r = 0; r < R; ++r) {
+        const int a = req_off[r], n = req_off[r + 1] - req_off[r];
+        if (n < 0) return fail(e, SONIC_ERR_INVALID, "sonic_set_request_bias: request offsets decrease");
+        if (n == 0) continue;
+        if (!seq_off || !bias) return fail(e, SONIC_ERR_INVALID, "sonic_set_request_bias: null table");
+        TRY(bias_pack(e, "sonic_set_request_bias", seq_ids, seq_off + a, bias + a, n, e->d.vocab, e->bias_h + 64 + (size_t)r * BIAS_ROW_WORDS, &e->bias_h[r]));
+    }
+    e->bias_pending = R;
+    return SONIC_OK;
+}
+int bias_upload(sonic_engine* e, int R) {
+    if (!e->opt_request_bias) return SONIC_OK;
+    if (!e->bias_take && e->opt_bias_fill > 0) {
+        // option request_bias_fill = n (drivers that only pass integers: bench.py --opt; tools/ab_request_bias.sh): every request of a batch without tables gets n
+        // length-1 entries of bias +0.0 on ids spread over the vocabulary.  s + 0.0 changes no token, but the kernel does all its work for them: the prologue's
+        // flags and group sums, n bits in the "biased" map, the list scan at every one of those ids
+        if (e->bias_ev_busy) { HIPC(e, hipEventSynchronize(e->bias_ev)); e->bias_ev_busy = false; }
+        const int n = e->opt_bias_fill, V = e->d.vocab;
+        for (int r = 0; r < 64; ++r) e->bias_h[r] = r < R ? n : 0;
+        for (int r = 0; r < R; ++r)
+            for (int k = 0; k < n; ++k) {
+                int* w = e->bias_h + 64 + (size_t)r * BIAS_ROW_WORDS + (size_t)k * BIAS_ENTRY_WORDS;
+                w[0] = (int)((long)k * V / n); w[1] = 1; w[2] = 0;
+                for (int j = 3; j < BIAS_ENTRY_WORDS; ++j) w[j] = -1;
+            }
+        e->bias_take = true;
+    }
+    if (!e->bias_take) { launch_fill_i32(e->bias_tab, 0, 64, e->st); return SONIC_OK; }             // a batch without tables: every count 0
+    HIPC(e, hipMemcpyAsync(e->bias_tab, e->bias_h, 64 * 4, hipMemcpyHostToDevice, e->st));
+    for (int r = 0; r < R; ++r) {
+        const size_t o = 64 + (size_t)r * BIAS_ROW_WORDS;
+        if (e->bias_h[r] > 0) HIPC(e, hipMemcpyAsync(e->bias_tab + o, e->bias_h + o, (size_t)e->bias_h[r] * BIAS_ENTRY_WORDS * 4, hipMemcpyHostToDevice, e->st));
+    }
+    HIPC(e, hipEventRecord(e->bias_ev, e->st));
+    e->bias_ev_busy = true; e->bias_take = false;
+    return SONIC_OK;
+}
+// dispatch.cpp (same library, not exported): is the option on for a handle; is one request's table well-formed for it (the message lands on the handle)
+extern "C" int engine_request_bias_on(sonic_engine* e) { return e && e->opt_request_bias && e->bias_tab ? 1 : 0; }
+// (the handle is only read for its vocabulary: the message goes to the calling thread's sonic_last_error(NULL), no lock is needed)
+extern "C" int engine_bias_validate(sonic_engine* e, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n) {
+    if (!e) return SONIC_ERR_INVALID;
+    std::vector<int> row((size_t)BIAS_ROW_WORDS); int cnt = 0;
+    return bias_pack(nullptr, "sonic_dispatch_submit_bias", seq_ids, seq_off, bias, n, e->d.vocab, row.data(), &cnt);
+}
+extern "C" int engine_thread_fail(int code, const char* msg) { return fail(nullptr, code, "%s", msg); }
+
 // HF generate()'s logits processors for greedy decoding, as the checkpoint's generation_config.json (or the caller) sets them: repetition_penalty (1.0 = none),
 // no_repeat_ngram_size (0 = none), suppress_tokens (n_suppress = 0: none; at most 256 ids).  The neutral values switch the guards off: the engine then launches
 // the kernels it launched before.  Set it on the owner before slots are created (they copy it).  SONIC_ERR_INVALID for a value out of range, and while the handle
@@ -476,6 +584,8 @@ extern "C" int sonic_slot_create(sonic_engine* parent, sonic_engine** out) {
     e->opt_token_logprobs = root->opt_token_logprobs;
     if (e->opt_token_logprobs && (s = lp_alloc(e)) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }
     if (root->gen_on && (s = gen_apply(e, root->gen_penalty, root->gen_ngram, root->gen_suppress.data(), (int)root->gen_suppress.size())) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }
+    if (root->opt_request_bias && (s = bias_enable(e, 1)) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }
+    e->opt_bias_fill = root->opt_bias_fill;
     e->weight_bytes = 0; e->finalized = true; e->owner = root;
     root->slots.push_back(e);
     *out = e;
@@ -531,6 +641,8 @@ extern "C" void sonic_destroy(sonic_engine* e) {
     if (e->n_active_h) (void)hipHostFree(e->n_active_h);
     for (int i = 0; i < 2; ++i) { if (e->plan_buf[i]) (void)hipHostFree(e->plan_buf[i]); if (e->plan_ev[i]) (void)hipEventDestroy(e->plan_ev[i]); }
     if (e->svc_h) (void)hipHostFree(e->svc_h);
+    if (e->bias_h) (void)hipHostFree(e->bias_h);
+    if (e->bias_ev) (void)hipEventDestroy(e->bias_ev);
     if (e->st_io) { (void)hipStreamSynchronize(e->st_io); (void)hipStreamDestroy(e->st_io); }
     if (e->xfer_ev) (void)hipEventDestroy(e->xfer_ev);
     if (e->splice_ev) (void)hipEventDestroy(e->splice_ev);

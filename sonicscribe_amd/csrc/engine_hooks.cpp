@@ -457,6 +457,18 @@ extern "C" int sonic_set_option(sonic_engine* e, const char* key, int value) {
         TRY(gen_busy(e, key));
         return gen_apply(e, p, n, sup.data(), (int)sup.size());
     }
+    // per-request sequence bias (sonic_set_request_bias): on the owner before its slots are created (they copy it); allocates the rows' history, if the
+    // guards have not, and their tables.  Refused while the handle has work in hand, by sonic_set_generation's rule
+    if (!strcmp(key, "request_bias")) {
+        TRY(gen_busy(e, key));
+        return bias_enable(e, value ? 1 : 0);
+    }
+    if (!strcmp(key, "request_bias_fill")) {      // measurement aid (bias_upload, engine.cpp): 0 .. min(256, vocabulary) neutral entries for every request without a table
+        if (value < 0 || value > BIAS_MAX_ENTRIES || value > e->d.vocab) return fail(e, SONIC_ERR_INVALID, "request_bias_fill: %d is outside 0 .. %d", value, BIAS_MAX_ENTRIES);
+        TRY(gen_busy(e, key));
+        e->opt_bias_fill = value;
+        return SONIC_OK;
+    }
     // the two knobs that do device work
     if (!strcmp(key, "ktrace")) {              // diagnostics: record in-kernel timestamps of decoder layer `value` (-1: off); sonic_debug_ktrace reads them
         HIPC(e, hipSetDevice(e->device));
@@ -547,7 +559,9 @@ extern "C" int sonic_test_linear_int8(sonic_engine* e, const float* X, const flo
 // instead of its argmax); lp_out[B] = the emitted token's log-probability.
 // sonic_test_greedy_guard: the launch through greedy_kernel<T, LP, true> (LP when lp_out is given): row b's history is hist[b * hist_ld .. + hist_len[b]), the three
 // parameters are sonic_set_generation's; logits_out stays the raw logits.
-struct GuardTest { const int32_t* hist; int hist_ld; const int32_t* hist_len; float penalty; int ngram; const int32_t* suppress; int n_suppress; };
+// sonic_test_greedy_bias: the launch through greedy_kernel<T, LP, true, true>: the guard test plus row b's table (sonic_set_request_bias's packed form, B requests).
+struct GuardTest { const int32_t* hist; int hist_ld; const int32_t* hist_len; float penalty; int ngram; const int32_t* suppress; int n_suppress;
+                   bool bias = false; const int32_t* seq_ids = nullptr; const int32_t* seq_off = nullptr; const float* seq_bias = nullptr; const int32_t* req_off = nullptr; };
 static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const int32_t* force_ids, int32_t* tok_out, float* logits_out, float* lp_out,
                        const GuardTest* gt = nullptr) {
     if (ksplit < 1 || ksplit > 8 || B < 1 || B > 64 || mpad < B || V < 4 || V % 4) return fail(e, SONIC_ERR_INVALID, "bad greedy test shape");
@@ -586,6 +600,20 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
         HIPC(e, h2d(e, ghist, hh.data(), hh.size() * 4));
         if (gt->n_suppress > 0) HIPC(e, h2d(e, gsup, gt->suppress, (size_t)gt->n_suppress * 4));
     }
+    int* gbias = nullptr;
+    if (gt && gt->bias) {
+        if (!gt->req_off || gt->req_off[0] != 0 || greedy_guard_lds(V, true) > 60000) return fail(e, SONIC_ERR_INVALID, "bad greedy bias test arguments");
+        std::vector<int> tab((size_t)BIAS_TAB_WORDS, 0);
+        for (int b = 0; b < B; ++b) {
+            const int a = gt->req_off[b], n = gt->req_off[b + 1] - a;
+            if (n < 0) return fail(e, SONIC_ERR_INVALID, "bad greedy bias test arguments");
+            if (n > 0 && (!gt->seq_off || !gt->seq_bias)) return fail(e, SONIC_ERR_INVALID, "bad greedy bias test arguments");
+            if (n > 0) TRY(bias_pack(e, "sonic_test_greedy_bias", gt->seq_ids, gt->seq_off + a, gt->seq_bias + a, n, V, tab.data() + 64 + (size_t)b * BIAS_ROW_WORDS, &tab[b]));
+        }
+        gbias = tb.get<int>(tab.size());
+        if (!gbias) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+        HIPC(e, h2d(e, gbias, tab.data(), tab.size() * 4));
+    }
     HIPC(e, h2d(e, st, h.data(), h.size() * 4));
     if (fd) HIPC(e, h2d(e, fd, force_ids, (size_t)B * 4));
     GreedyArgs g{};
@@ -593,7 +621,7 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
     g.out_ids = ids; g.out_ld = 1; g.n_new = st; g.finished = st + 64; g.kv_len = st + 128; g.tok_pos = st + 192; g.max_new = st + 256;
     g.n_active = st + 512; g.n_eos = 0; g.pad_id = 0; g.logits_dump = dump; g.dump_stride_step = (long)B * V; g.step_counter = dump ? st + 320 : nullptr;
     g.out_lp = lp; g.force_ids = fd; g.force_ld = 1;
-    if (gt) { g.hist = ghist; g.hist_ld = gld; g.rep_penalty = gt->penalty; g.ngram = gt->ngram; g.suppress = gsup; g.n_suppress = gt->n_suppress; }
+    if (gt) { g.hist = ghist; g.hist_ld = gld; g.rep_penalty = gt->penalty; g.ngram = gt->ngram; g.suppress = gsup; g.n_suppress = gt->n_suppress; g.bias_tab = gbias; }
     launch_greedy(g, e->st);
     HIPC(e, stream_sync(e));
     HIPC(e, hipGetLastError());
@@ -622,6 +650,17 @@ extern "C" int sonic_test_greedy_guard(sonic_engine* e, const float* slabs, int 
     if (!e || !slabs || !tok_out || !hist_len) return SONIC_ERR_INVALID;
     ENTER(e);
     const GuardTest gt{hist, hist_ld, hist_len, repetition_penalty, no_repeat_ngram_size, suppress, n_suppress};
+    return test_greedy(e, slabs, ksplit, mpad, V, B, force_ids, tok_out, logits_out, lp_out, &gt);
+}
+
+extern "C" int sonic_test_greedy_bias(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const int32_t* hist, int hist_ld, const int32_t* hist_len,
+                                      float repetition_penalty, int no_repeat_ngram_size, const int32_t* suppress, int n_suppress, const int32_t* force_ids,
+                                      const int32_t* seq_ids, const int32_t* seq_off, const float* bias, const int32_t* req_off,
+                                      int32_t* tok_out, float* logits_out, float* lp_out) {
+    if (!e || !slabs || !tok_out || !hist_len || !req_off) return SONIC_ERR_INVALID;
+    ENTER(e);
+    GuardTest gt{hist, hist_ld, hist_len, repetition_penalty, no_repeat_ngram_size, suppress, n_suppress};
+    gt.bias = true; gt.seq_ids = seq_ids; gt.seq_off = seq_off; gt.seq_bias = bias; gt.req_off = req_off;
     return test_greedy(e, slabs, ksplit, mpad, V, B, force_ids, tok_out, logits_out, lp_out, &gt);
 }
 

@@ -381,8 +381,9 @@ extern "C" int sonic_stage_mixed(sonic_engine* e, const int16_t* host_pcm, const
 extern "C" int sonic_transcribe_mixed(sonic_engine* e, const int16_t* host_pcm, const int64_t* host_off, sonic_ring* const* rings, const int64_t* ring_start,
                                       const int32_t* ring_n, int W, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off,
                                       const int32_t* max_new, int32_t* out_ids, int out_ld, int32_t* out_len, float* step_logits) {
-    if (!e || !prompt_ids || !prompt_off || !max_new) return SONIC_ERR_INVALID;
-    ENTER(e);
+    if (!e) return SONIC_ERR_INVALID;
+    ENTER_CONSUME(e);
+    if (!prompt_ids || !prompt_off || !max_new) return SONIC_ERR_INVALID;
     TRY(stage_mixed_locked(e, W, host_pcm, host_off, rings, ring_start, ring_n, req_win, R));
     TRY(run_all(e, req_win, R, prompt_ids, prompt_off, max_new, step_logits != nullptr));
     return fetch_locked(e, out_ids, out_ld, out_len, step_logits);
@@ -396,7 +397,8 @@ extern "C" int sonic_stage_pcm(sonic_engine* e, const int16_t* pcm, const int64_
 
 extern "C" int sonic_run_staged(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off,
                                 const int32_t* max_new, int want_step_logits) {
-    if (!e || !prompt_ids || !prompt_off || !max_new) return SONIC_ERR_INVALID;
-    ENTER(e);
+    if (!e) return SONIC_ERR_INVALID;
+    ENTER_CONSUME(e);
+    if (!prompt_ids || !prompt_off || !max_new) return SONIC_ERR_INVALID;
     return run_all(e, req_win, R, prompt_ids, prompt_off, max_new, want_step_logits != 0);
 }

@@ -179,6 +179,13 @@ struct sonic_engine {
     // written by the prefill and the greedy kernel, copied by the splice; allocated with gen_suppress_d[256] by the first gen_apply that switches a guard on
     bool gen_on = false; float gen_penalty = 1.0f; int gen_ngram = 0; std::vector<int> gen_suppress;
     int* hist = nullptr; int* gen_suppress_d = nullptr;
+    // option request_bias (sonic_set_request_bias; greedy_kernel<T, LP, true, true>): every row's own sequence-bias table.  bias_tab[BIAS_TAB_WORDS] on the
+    // device (kernels.h), written by the prefill from the pinned bias_h, copied by the splice; allocated, with hist, by the option.  bias_pending: the R of the
+    // tables sonic_set_request_bias left in bias_h for the next prefill (-1: none); bias_take: that prefill is under way and uploads them
+    int opt_request_bias = 0;
+    int opt_bias_fill = 0;         // measurement aid (option request_bias_fill, tools/ab_request_bias.sh): a prefill that was given no tables writes this many neutral entries per request
+    int* bias_tab = nullptr; int* bias_h = nullptr; hipEvent_t bias_ev = nullptr; bool bias_ev_busy = false;
+    std::atomic<int> bias_pending{-1}; bool bias_take = false;
     uint64_t spliced = 0;          // rows of the last prefill that sonic_splice_rows handed to a continuous loop (bit r = request r); cleared by every prefill (gen_busy)
     long long* kt = nullptr; int kt_layer = -1;     // diagnostics ("ktrace" option): in-kernel timestamps of one decoder layer's kernels
     int* ring_peak = nullptr;                        // [Bm] per-request max |s| of a ring-staged batch (ingest.hip)
@@ -222,6 +229,10 @@ struct HostPlan {
 // (hipGetLastError first: the slot is per thread and sticky, so a failure some earlier call of this thread ignored would otherwise
 // surface at this call's closing hipGetLastError check)
 #define ENTER(e) std::lock_guard<std::mutex> lk((e)->mu); (void)hipGetLastError(); HIPC(e, hipSetDevice((e)->device)); g_opts = (e)->opts
+// ENTER for the entry points that consume the tables of sonic_set_request_bias (sonic_prefill*, sonic_run_staged, sonic_transcribe_*): whatever way the call
+// leaves - a staging error ahead of the prefill included - the pending tables are dropped, so they can never reach a later batch
+struct BiasConsume { sonic_engine* e; ~BiasConsume(); };
+#define ENTER_CONSUME(e) std::lock_guard<std::mutex> lk((e)->mu); BiasConsume bias_consume_{e}; (void)hipGetLastError(); HIPC(e, hipSetDevice((e)->device)); g_opts = (e)->opts
 
 // ------------------------------------------------------------------------------------------ helpers (engine.cpp)
 int fail(sonic_engine* e, int code, const char* fmt, ...);
@@ -288,4 +299,11 @@ int lp_alloc(sonic_engine* e);                      // out_lp on first use (engi
 int gen_apply(sonic_engine* e, float penalty, int ngram, const int32_t* suppress, int n_suppress);   // sonic_set_generation behind the lock and the busy check (engine.cpp)
 int gen_busy(sonic_engine* e, const char* who);     // that busy check: SONIC_ERR_INVALID while the handle has work in hand (engine.cpp)
 void drop_graphs(sonic_engine* e);                  // the captured decode chunks of this handle (engine_hooks.cpp)
+int bias_enable(sonic_engine* e, int on);           // option request_bias behind the lock and the busy check: hist, the tables and their staging buffer on first use (engine.cpp)
+// one request's table as sonic_set_request_bias takes it -> its BIAS_ROW_WORDS device words, grouped and ordered as the kernel reads them; *count = its entries.
+// SONIC_ERR_INVALID (message on e, naming `who`) for more than BIAS_MAX_ENTRIES entries, a length outside 1 .. BIAS_MAX_LEN, an id outside [0, V), a NaN or +inf bias
+int bias_pack(sonic_engine* e, const char* who, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n, int V, int* row, int* count);
+int bias_upload(sonic_engine* e, int R);            // the prefill's part: the pending tables (or zero counts) into bias_tab, on the stream (engine.cpp)
+inline BiasConsume::~BiasConsume() { e->bias_pending = -1; }
+static inline bool hist_on(const sonic_engine* e) { return e->gen_on || e->opt_request_bias; }   // the rows' input_ids are kept: a guard or the request bias reads them
 int lp_check(sonic_engine* e, const char* who);     // SONIC_ERR_INVALID naming the option when token_logprobs is off on this handle

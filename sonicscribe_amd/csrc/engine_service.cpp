@@ -14,6 +14,7 @@ struct SpliceArgs {
     int src[64], dst[64];
     const int *kv_len_s, *tok_pos_s, *n_new_s, *fin_s, *max_new_s, *out_s; int out_ld;
     const int* hist_s; int* hist_d;                      // generation guards on the destination: the row's history (prompt + first token) travels with it, [.][ctx]
+    const int* bias_s; int* bias_d;                      // option request_bias on both: the row's table travels with it (count first, then only the used entries)
     const float* lp_s; float* lp_d;                      // option token_logprobs on the destination: the first token's log-probability travels with its id
     int *kv_len_d, *tok_pos_d, *n_new_d, *fin_d, *max_new_d, *out_d, *n_active_d;
     const bf16_t *sx_s, *shn_s; bf16_t *sx_d, *shn_d; int D;
@@ -44,6 +45,11 @@ __global__ __launch_bounds__(256) void splice_state_kernel(SpliceArgs a) {
     if (a.hist_d) {
         const int len = min(max(a.kv_len_s[s], 0) + 1, a.ctx);      // (a row that stopped at its first token kept kv_len = prompt: its token sits at [kv_len])
         for (int j = t; j < len; j += 256) a.hist_d[(long)d * a.ctx + j] = a.hist_s[(long)s * a.ctx + j];
+    }
+    if (a.bias_d) {
+        const int cnt = min(max(a.bias_s[s], 0), BIAS_MAX_ENTRIES);
+        if (t == 0) a.bias_d[d] = cnt;
+        for (int j = t; j < cnt * BIAS_ENTRY_WORDS; j += 256) a.bias_d[64 + (long)d * BIAS_ROW_WORDS + j] = a.bias_s[64 + (long)s * BIAS_ROW_WORDS + j];
     }
     if (t == 0) {
         const int fin = a.fin_s[s];
@@ -121,6 +127,8 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
     // (either way round: a row whose first token was chosen with guards must not go on without them, nor the reverse)
     if (d->gen_on != p->gen_on || (d->gen_on && !(p->hist && d->hist && p->gen_penalty == d->gen_penalty && p->gen_ngram == d->gen_ngram && p->gen_suppress == d->gen_suppress)))
         return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in their generation guards (sonic_set_generation): set them on the owner before its slots are created");
+    if (d->opt_request_bias != p->opt_request_bias || (d->opt_request_bias && !(p->bias_tab && d->bias_tab && p->hist && d->hist)))
+        return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in option request_bias: set it on the owner before its slots are created");
     if (n < 1 || n > 64 || p->greedy_calls < 1 || n > p->R) return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: %d rows, the source has %d prefilled requests", n, p->greedy_calls < 1 ? 0 : p->R);
     SpliceArgs a{};
     for (int i = 0; i < n; ++i) {
@@ -134,7 +142,8 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
     a.kv_len_d = d->kv_len; a.tok_pos_d = d->tok_pos; a.n_new_d = d->n_new; a.fin_d = d->finished; a.max_new_d = d->max_new_d; a.out_d = d->out_ids; a.n_active_d = d->n_active;
     a.sx_s = p->sx; a.shn_s = p->shn; a.sx_d = d->sx; a.shn_d = d->shn; a.D = dm.dec_d;
     if (d->opt_token_logprobs && d->out_lp) { a.lp_s = p->out_lp; a.lp_d = d->out_lp; }
-    if (d->gen_on) { a.hist_s = p->hist; a.hist_d = d->hist; }
+    if (hist_on(d)) { a.hist_s = p->hist; a.hist_d = d->hist; }
+    if (d->opt_request_bias) { a.bias_s = p->bias_tab; a.bias_d = d->bias_tab; }
     if (d->i8) { a.hq_s = p->hn_q; a.hq_d = d->hn_q; a.sca_s = p->sca_hn; a.sca_d = d->sca_hn; a.oc_s = p->oc_hn; a.oc_d = d->oc_hn; a.ol_s = p->ol_hn; a.ol_d = d->ol_hn; a.ov_s = p->ov_hn; a.ov_d = d->ov_hn; }
     HIPC(d, hipEventRecord(p->xfer_ev, p->st));
     HIPC(d, hipStreamWaitEvent(d->st, p->xfer_ev, 0));
@@ -296,7 +305,10 @@ void async_shutdown(sonic_engine* e) {
 }
 extern "C" int sonic_run_staged_async(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off,
                                       const int32_t* max_new, int want_step_logits) {
-    if (!e || !prompt_ids || !prompt_off || !max_new || R < 1 || R > 64) return SONIC_ERR_INVALID;
+    if (!e) return SONIC_ERR_INVALID;
+    // (a refusal below drops the tables of sonic_set_request_bias: this call was their consumer; an accepted run consumes them in its prefill)
+    struct Drop { sonic_engine* e; bool keep = false; ~Drop() { if (!keep) e->bias_pending = -1; } } drop{e};
+    if (!prompt_ids || !prompt_off || !max_new || R < 1 || R > 64) return SONIC_ERR_INVALID;
     std::lock_guard<std::mutex> lk(e->a_mu);
     if (e->a_stop) return SONIC_ERR_INVALID;
     if (e->a_pending || e->a_running || e->a_done) {         // (e->err belongs to the engine lock; report through the creating thread's slot)
@@ -310,7 +322,7 @@ extern "C" int sonic_run_staged_async(sonic_engine* e, const int32_t* req_win, i
     j.prompt_ids.assign(prompt_ids, prompt_ids + prompt_off[R]);
     j.max_new.assign(max_new, max_new + R);
     if (!e->a_started) { e->a_thread = std::thread(async_loop, e); e->a_started = true; }
-    e->a_pending = true;
+    e->a_pending = true; drop.keep = true;
     e->a_cv.notify_all();
     return SONIC_OK;
 }
@@ -333,8 +345,9 @@ extern "C" int sonic_wait(sonic_engine* e, int block, int32_t* busy_out) {
 // *steps_done_out = steps actually run (fewer than asked once the largest budget is reached).  sonic_fetch_tokens reads the result at any point.
 extern "C" int sonic_prefill(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off,
                              const int32_t* max_new, int want_step_logits) {
-    if (!e || !prompt_ids || !prompt_off || !max_new) return SONIC_ERR_INVALID;
-    ENTER(e);
+    if (!e) return SONIC_ERR_INVALID;
+    ENTER_CONSUME(e);
+    if (!prompt_ids || !prompt_off || !max_new) return SONIC_ERR_INVALID;
     TRY(run_to_first_token(e, req_win, R, prompt_ids, prompt_off, max_new, want_step_logits != 0));
     HIPC(e, stream_sync(e));
     HIPC(e, hipGetLastError());
@@ -343,8 +356,9 @@ extern "C" int sonic_prefill(sonic_engine* e, const int32_t* req_win, int R, con
 // sonic_prefill without the closing wait: everything up to the first token is QUEUED on the handle's stream when the call returns.  For the
 // pipeline form: sonic_splice_rows orders its copies behind this work on the device, so the host need not come back between prefill and splice.
 extern "C" int sonic_prefill_enqueue(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new) {
-    if (!e || !prompt_ids || !prompt_off || !max_new) return SONIC_ERR_INVALID;
-    ENTER(e);
+    if (!e) return SONIC_ERR_INVALID;
+    ENTER_CONSUME(e);
+    if (!prompt_ids || !prompt_off || !max_new) return SONIC_ERR_INVALID;
     TRY(run_to_first_token(e, req_win, R, prompt_ids, prompt_off, max_new, false));
     HIPC(e, hipGetLastError());
     return SONIC_OK;
@@ -422,8 +436,9 @@ extern "C" int sonic_fetch_logprobs(sonic_engine* e, float* out_lp, int out_ld) 
 extern "C" int sonic_transcribe_batch(sonic_engine* e, const int16_t* pcm, const int64_t* offsets, int W, const int32_t* req_win, int R,
                                       const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new,
                                       int32_t* out_ids, int out_ld, int32_t* out_len, float* step_logits) {
-    if (!e || !prompt_ids || !prompt_off || !max_new) return SONIC_ERR_INVALID;
-    ENTER(e);
+    if (!e) return SONIC_ERR_INVALID;
+    ENTER_CONSUME(e);
+    if (!prompt_ids || !prompt_off || !max_new) return SONIC_ERR_INVALID;
     TRY(stage_pcm_locked(e, pcm, offsets, W));
     TRY(run_all(e, req_win, R, prompt_ids, prompt_off, max_new, step_logits != nullptr));
     return fetch_locked(e, out_ids, out_ld, out_len, step_logits);

@@ -114,9 +114,19 @@ struct GreedyArgs {
     int* hist; int hist_ld;
     float rep_penalty; int ngram;                      // repetition_penalty (1.0: none), no_repeat_ngram_size (0: none)
     const int* suppress; int n_suppress;               // suppress_tokens on the device
+    // per-request sequence bias (greedy_kernel<T, LP, true, true>, option request_bias); bias_tab = NULL: off.  BIAS_TAB_WORDS words: the 64 rows'
+    // entry counts (0 .. BIAS_MAX_ENTRIES), then BIAS_ROW_WORDS words per row: BIAS_ENTRY_WORDS words per entry - the sequence's last id, its length L
+    // (1 .. BIAS_MAX_LEN), the fp32 bias (its bits), the L - 1 ids in front of the last one.  The host stores a row's entries grouped by last id, the length-1
+    // entry of a group first and the others in list order (bias_pack, engine.cpp): one thread adds a group in the contract's order.  Needs hist.
+    const int* bias_tab;
 };
+#define BIAS_MAX_ENTRIES 256
+#define BIAS_MAX_LEN 8
+#define BIAS_ENTRY_WORDS (3 + BIAS_MAX_LEN - 1)
+#define BIAS_ROW_WORDS (BIAS_MAX_ENTRIES * BIAS_ENTRY_WORDS)
+#define BIAS_TAB_WORDS (64 + 64 * BIAS_ROW_WORDS)
 void launch_greedy(const GreedyArgs& a, hipStream_t s);
-size_t greedy_guard_lds(int V);                        // dynamic LDS of the GUARD instantiations: two bitmaps over the vocabulary
+size_t greedy_guard_lds(int V, bool bias = false);     // dynamic LDS of the GUARD instantiations: two bitmaps over the vocabulary; with the request bias a third one and the matched list
 void launch_hist_prompt(const int* src, const int* tok_seq, const int* tok_pos, int n_tok, int audio_id, int* hist, int hist_ld, hipStream_t s);
 
 struct LogmelConst {

@@ -46,10 +46,11 @@ def step_class(max_new: int) -> int:
 
 
 class Request:
-    __slots__ = ("windows", "prompt", "max_new", "future", "t_submit", "cls", "want_logprobs")
+    __slots__ = ("windows", "prompt", "max_new", "future", "t_submit", "cls", "want_logprobs", "bias")
 
-    def __init__(self, windows: Sequence[Any], prompt: Sequence[int], max_new: int, want_logprobs: bool = False):
+    def __init__(self, windows: Sequence[Any], prompt: Sequence[int], max_new: int, want_logprobs: bool = False, bias=None):
         self.windows, self.prompt, self.max_new = list(windows), prompt, int(max_new)
+        self.bias = bias if bias else None            # its own sequence-bias table (reqbias.RequestBias; engine option request_bias): it travels with the request
         self.want_logprobs = bool(want_logprobs)      # the future resolves to (ids, float32 log-probabilities) instead of ids (engine option token_logprobs)
         self.future: Future = Future()
         self.t_submit = time.perf_counter()
@@ -128,23 +129,28 @@ class _Replica:
             segs.extend(r.windows)
             req_win.append(len(segs))
         want = any(r.want_logprobs for r in batch)      # (the keyword only goes to the engine when somebody asked: duck-typed engines need not know it)
+        # (likewise; an engine with option request_bias is ALWAYS told its batch's tables, None for a request without one: a batch never depends on what an
+        # earlier, failed one left behind)
+        stated = bool(getattr(engine, "request_bias", False))
+        kw = {"request_bias": [r.bias for r in batch]} if stated or any(r.bias for r in batch) else {}
         try:
             if want:
-                ids, _, lps = engine.transcribe_batch(segs, [r.prompt for r in batch], [r.max_new for r in batch], req_win=req_win, want_logprobs=True)
+                ids, _, lps = engine.transcribe_batch(segs, [r.prompt for r in batch], [r.max_new for r in batch], req_win=req_win, want_logprobs=True, **kw)
                 ids = [(i, l) if r.want_logprobs else i for r, i, l in zip(batch, ids, lps)]
             else:
-                ids, _ = engine.transcribe_batch(segs, [r.prompt for r in batch], [r.max_new for r in batch], req_win=req_win)
+                ids, _ = engine.transcribe_batch(segs, [r.prompt for r in batch], [r.max_new for r in batch], req_win=req_win, **kw)
         except BaseException as ex:              # a per-request validation error must not poison its neighbours: retry one by one
             if len(batch) == 1:
                 self._finish(batch[0], error=ex)
                 return
             for r in batch:
+                kw1 = {"request_bias": [r.bias]} if stated or r.bias else {}
                 try:
                     if r.want_logprobs:
-                        one, _, lp1 = engine.transcribe_batch(r.windows, [r.prompt], [r.max_new], req_win=[0, len(r.windows)], want_logprobs=True)
+                        one, _, lp1 = engine.transcribe_batch(r.windows, [r.prompt], [r.max_new], req_win=[0, len(r.windows)], want_logprobs=True, **kw1)
                         one = [(one[0], lp1[0])]
                     else:
-                        one, _ = engine.transcribe_batch(r.windows, [r.prompt], [r.max_new], req_win=[0, len(r.windows)])
+                        one, _ = engine.transcribe_batch(r.windows, [r.prompt], [r.max_new], req_win=[0, len(r.windows)], **kw1)
                 except BaseException as ex2:
                     self._finish(r, error=ex2)
                 else:
@@ -243,6 +249,8 @@ class _ContinuousReplica:
         if req.want_logprobs and not all(getattr(e, "token_logprobs", False) for e in self.engines):
             # refused here: inside the decode thread the failing fetch would take the neighbours' rows with it
             raise ValueError("log-probabilities need the engine option token_logprobs on every handle (ASRModel(token_logprobs=True))")
+        if req.bias and not all(getattr(e, "request_bias", False) for e in self.engines):
+            raise ValueError("a sequence bias needs the engine option request_bias on every handle (ASRModel(request_bias=True))")
         with self.cv:
             if self.stop:
                 raise RuntimeError("ASR engine is closed")
@@ -286,6 +294,10 @@ class _ContinuousReplica:
                 busy = sum(self.n_rows - f for f in self.free) > len(batch)        # rows running or reserved besides this batch's own
             eng.set_option("gemm_small_eff", 0 if busy else 75)
         eng.stage_pcm(segs, req_win)
+        # the tables follow their requests: row i of this prefill is batch[i]; the prefill consumes them.  With the option on every prefill states its tables
+        # (None: none), so a batch never depends on what an earlier, failed one left behind
+        if getattr(eng, "request_bias", False) or any(r.bias for r in batch):
+            eng.set_request_bias([r.bias for r in batch])
         # waited for: a splice queued behind a prefill that is still running would hold the decoder's whole stream (every running row) at the
         # event until the prefill is done - final p50 at 128 sessions 438 -> 657 ms when the hand-over came early.  (The bulk pipeline hands over
         # early, sonicscribe_amd/pipeline.py: its next batch is long done when a block frees up.)
@@ -443,6 +455,7 @@ class _NativeContinuousReplica:
         self.stop = False
         self.out_cap = int(engine.max_ctx)
         self.lp = all(getattr(e, "token_logprobs", False) for e in self.engines)      # then completions are collected with their log-probabilities
+        self.bias = all(getattr(e, "request_bias", False) for e in self.engines)      # then a request may bring its own sequence-bias table
         self.thread = threading.Thread(target=self._complete_loop, name=f"sonic-dispatch-{index}.complete", daemon=True)
         self.thread.start()
 
@@ -474,6 +487,10 @@ class _NativeContinuousReplica:
         from .engine import RingSlice, _p
         if req.want_logprobs and not self.lp:
             raise ValueError("log-probabilities need the engine option token_logprobs on every handle (ASRModel(token_logprobs=True))")
+        if req.bias and not self.bias:
+            raise ValueError("a sequence bias needs the engine option request_bias on every handle (ASRModel(request_bias=True))")
+        if req.bias:
+            req.bias.check_vocab(self.engine.dims.vocab)
         wins = req.windows
         W = len(wins)
         offs = np.zeros(W + 1, np.int64)
@@ -495,8 +512,17 @@ class _NativeContinuousReplica:
         with self.lock:
             if self.stop:
                 raise RuntimeError("ASR engine is closed")
-            rc = self.lib.sonic_dispatch_submit(self.h, _p(pcm), _p(offs), ring_arr, _p(start) if any_ring else None, _p(n) if any_ring else None, W,
-                                                _p(prompt), len(prompt), int(req.max_new), C.byref(t))
+            if req.bias:
+                b_ids, b_off, b_val = req.bias.table()
+                rc = self.lib.sonic_dispatch_submit_bias(self.h, _p(pcm), _p(offs), ring_arr, _p(start) if any_ring else None, _p(n) if any_ring else None, W,
+                                                         _p(prompt), len(prompt), int(req.max_new), _p(b_ids), _p(b_off), _p(b_val), len(b_val), C.byref(t))
+            else:
+                rc = self.lib.sonic_dispatch_submit(self.h, _p(pcm), _p(offs), ring_arr, _p(start) if any_ring else None, _p(n) if any_ring else None, W,
+                                                    _p(prompt), len(prompt), int(req.max_new), C.byref(t))
+            if rc != 0 and req.bias:
+                msg = (self.lib.sonic_last_error(None) or b"").decode()
+                if "request_bias" in msg or "sonic_dispatch_submit_bias" in msg:
+                    raise ValueError(msg)
             if rc != 0:
                 raise RuntimeError("ASR engine failed" if rc not in (1,) else "ASR engine is closed or the request is malformed")
             self.pending[int(t.value)] = req
@@ -603,6 +629,8 @@ class _BulkReplica:
         from .engine import RingSlice
         if not all(isinstance(w, (np.ndarray, RingSlice)) for w in req.windows):
             raise TypeError("bulk mode takes host PCM windows or slices of device rings")
+        if req.bias:                                      # refused, not dropped: the bulk pipeline (csrc/pipeline.cpp) carries no per-request tables
+            raise ValueError("a sequence bias is not supported with bulk=True (the bulk pipeline carries no per-request tables): use the continuous or the batch dispatcher")
         with self.cv:
             if self.stop:
                 raise RuntimeError("ASR engine is closed")
@@ -761,10 +789,11 @@ class Dispatcher:
             return self.replicas[least]                                     # rebalance: the home replica is more than a batch behind
         return self.replicas[home]
 
-    def submit(self, windows, prompt, max_new: int, session: Optional[str] = None, replica: Optional[int] = None, want_logprobs: bool = False) -> Future:
+    def submit(self, windows, prompt, max_new: int, session: Optional[str] = None, replica: Optional[int] = None, want_logprobs: bool = False, bias=None) -> Future:
         """`replica` pins the request (windows that are slices of a device ring can only be decoded where the ring lives).  want_logprobs: the
-        future resolves to (ids, log-probabilities) - the engines need option token_logprobs."""
-        req = Request(windows, prompt, max_new, want_logprobs)
+        future resolves to (ids, log-probabilities) - the engines need option token_logprobs.  bias: the request's own sequence-bias table
+        (reqbias.RequestBias) - the engines need option request_bias; refused with bulk=True."""
+        req = Request(windows, prompt, max_new, want_logprobs, bias)
         (self.replicas[replica] if replica is not None else self.pick(session)).put(req)
         return req.future
 

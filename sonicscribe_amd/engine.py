@@ -39,6 +39,7 @@ EXPORTS = [
     "sonic_fetch_logprobs", "sonic_fetch_rows_lp", "sonic_dispatch_next_lp", "sonic_pipeline_submit_lp", "sonic_test_greedy_lp",
     "sonic_set_generation", "sonic_get_generation", "sonic_test_greedy_guard",
     "sonic_test_add_rmsnorm", "sonic_test_quant_rows", "sonic_test_swiglu_slab", "sonic_test_decode_o_gu", "sonic_test_rope_append", "sonic_test_rope_enc",
+    "sonic_set_request_bias", "sonic_dispatch_submit_bias", "sonic_test_greedy_bias",
 ]
 ABI_VERSION = 12
 
@@ -167,10 +168,13 @@ def load_library():
     lib.sonic_test_decode_o_gu.argtypes = [vp, vp, vp, vp, vp, C.c_float, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     lib.sonic_test_rope_append.argtypes = [vp] * 7 + [C.c_int] * 7 + [vp] * 4
     lib.sonic_test_rope_enc.argtypes = [vp, vp] + [C.c_int] * 6 + [vp]
+    lib.sonic_set_request_bias.argtypes = [vp, vp, vp, vp, vp, C.c_int]
+    lib.sonic_test_greedy_bias.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_float, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.sonic_slot_create.argtypes = [vp, C.POINTER(vp)]
     lib.sonic_slot_count.argtypes = [vp]
     lib.sonic_dispatch_create.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(vp)]
     lib.sonic_dispatch_submit.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, i64p]
+    lib.sonic_dispatch_submit_bias.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, i64p]
     lib.sonic_dispatch_cancel.argtypes = [vp, C.c_int64]
     lib.sonic_dispatch_next.argtypes = [vp, C.c_int, i64p, ip, vp, C.c_int, ip, C.c_char_p, C.c_int]
     lib.sonic_dispatch_next_lp.argtypes = [vp, C.c_int, i64p, ip, vp, C.c_int, ip, C.c_char_p, C.c_int, vp]
@@ -322,6 +326,7 @@ class Engine:
         root = self.root
         s = Engine(self.dims, 0, 0, self.max_batch, self.max_ctx, _slot_of=root)
         s.token_logprobs = bool(getattr(root, "token_logprobs", False))
+        s.request_bias = bool(getattr(root, "request_bias", False))
         root._slots.append(s)
         return s
 
@@ -468,10 +473,11 @@ class Engine:
         return pcm, offs, rings, start, n
 
     def transcribe_batch(self, segments: Sequence[Any], prompts: Sequence[Sequence[int]], max_new: Sequence[int],
-                         req_win: Optional[Sequence[int]] = None, want_logits: bool = False, want_logprobs: bool = False):
+                         req_win: Optional[Sequence[int]] = None, want_logits: bool = False, want_logprobs: bool = False, request_bias=None):
         """segments: int16 PCM windows (<= 30 s each, already peak-normalised) or RingSlice objects (raw wire PCM resident in a device
         ring; normalised on the device over the windows of their request); one prompt per request. Returns (ids list, logits or None);
-        with want_logprobs (option token_logprobs on this handle) one more element: the float32 log-probability of every returned token, per request."""
+        with want_logprobs (option token_logprobs on this handle) one more element: the float32 log-probability of every returned token, per request.
+        request_bias: one reqbias.RequestBias or None per request (option request_bias on this handle; set_request_bias)."""
         if any(isinstance(s, RingSlice) for s in segments):
             pcm, offs, rings, start, n = self._pack_mixed(segments)
             ids, poffs = self._pack_prompts(prompts)
@@ -482,6 +488,8 @@ class Engine:
             out_len = np.zeros(R, np.int32)
             rw = np.ascontiguousarray(req_win, dtype=np.int32) if req_win is not None else None
             logits = np.zeros((out_ld, R, self.dims.vocab), np.float32) if want_logits else None
+            if request_bias is not None:             # (right ahead of the call that consumes them, on success or failure: nothing in between can raise)
+                self.set_request_bias(request_bias)
             self._check(self.lib.sonic_transcribe_mixed(self.h, _p(pcm), _p(offs), rings, _p(start), _p(n), len(segments), _p(rw), R, _p(ids), _p(poffs),
                                                         _p(mn), _p(out), out_ld, _p(out_len), _p(logits)))
             res = [out[r, : out_len[r]].copy() for r in range(R)]
@@ -495,6 +503,8 @@ class Engine:
         out_len = np.zeros(R, np.int32)
         rw = np.ascontiguousarray(req_win, dtype=np.int32) if req_win is not None else None
         logits = np.zeros((out_ld, R, self.dims.vocab), np.float32) if want_logits else None
+        if request_bias is not None:
+            self.set_request_bias(request_bias)
         self._check(self.lib.sonic_transcribe_batch(self.h, _p(pcm), _p(offs), len(segments), _p(rw), R, _p(ids), _p(poffs), _p(mn),
                                                     _p(out), out_ld, _p(out_len), _p(logits)))
         res = [out[r, : out_len[r]].copy() for r in range(R)]
@@ -524,12 +534,15 @@ class Engine:
         self._run_cache = (ids, poffs, mn, rw)
         self._check(self.lib.sonic_run_staged(self.h, _p(rw), len(prompts), _p(ids), _p(poffs), _p(mn), int(want_logits)))
 
-    def prefill(self, prompts: Sequence[Sequence[int]], max_new: Sequence[int], req_win: Optional[Sequence[int]] = None, want_logits: bool = False, wait: bool = True):
+    def prefill(self, prompts: Sequence[Sequence[int]], max_new: Sequence[int], req_win: Optional[Sequence[int]] = None, want_logits: bool = False, wait: bool = True,
+                request_bias=None):
         """Stage entry point: everything up to and including the first greedy token of the staged batch (sonic_prefill).  wait=False: the
         work is only queued when the call returns (sonic_prefill_enqueue; a following splice_rows orders itself behind it on the device)."""
         ids, poffs = self._pack_prompts(prompts)
         mn = np.ascontiguousarray(max_new, dtype=np.int32)
         rw = np.ascontiguousarray(req_win, dtype=np.int32) if req_win is not None else None
+        if request_bias is not None:                     # one reqbias.RequestBias or None per request: this prefill consumes them, on success or failure
+            self.set_request_bias(request_bias)
         if not wait:
             self._check(self.lib.sonic_prefill_enqueue(self.h, _p(rw), len(prompts), _p(ids), _p(poffs), _p(mn)))
             return
@@ -684,6 +697,8 @@ def _bench_skinny(self, M: int, N: int, K: int, variant: int, iters: int = 50) -
 
 def _set_option(self, key: str, value: int):
     self._check(self.lib.sonic_set_option(self.h, key.encode(), value))
+    if key == "request_bias":
+        self.request_bias = bool(value)          # (likewise)
     if key == "token_logprobs":
         self.token_logprobs = bool(value)        # (a slot created from now on copies it, in the library and here)
 
@@ -772,6 +787,51 @@ def _test_greedy_guard(self, slabs, B: int, hist, hist_len, repetition_penalty: 
     f = np.ascontiguousarray(force_ids, np.int32) if force_ids is not None else None
     self._check(self.lib.sonic_test_greedy_guard(self.h, _p(s), ks, mpad, V, B, _p(h) if h.size else None, h.shape[1], _p(hl), float(repetition_penalty),
                                                  int(no_repeat_ngram_size), _p(sup) if sup.size else None, int(sup.size), _p(f), _p(tok), _p(lg), _p(lp)))
+    return tok, lg, lp
+
+
+def pack_request_bias(tables):
+    """one table per request (reqbias.RequestBias, or None for a request without one) -> sonic_set_request_bias's arrays (seq_ids, seq_off, bias, req_off)"""
+    ids, lens, vals, req_off = [], [], [], [0]
+    for t in tables:
+        if t is not None:
+            i, o, b = t.table()
+            ids.append(i); lens.append(np.diff(o)); vals.append(b)
+        req_off.append(req_off[-1] + (len(t) if t is not None else 0))
+    seq_ids = np.ascontiguousarray(np.concatenate(ids) if ids else np.zeros(0), dtype=np.int32)
+    ln = np.concatenate(lens) if lens else np.zeros(0, np.int64)
+    seq_off = np.zeros(len(ln) + 1, np.int32)
+    seq_off[1:] = np.cumsum(ln)
+    bias = np.ascontiguousarray(np.concatenate(vals) if vals else np.zeros(0), dtype=np.float32)
+    return seq_ids, seq_off, bias, np.asarray(req_off, dtype=np.int32)
+
+
+def _set_request_bias(self, tables):
+    """The sequence-bias tables of the requests of the NEXT prefill / run on this handle (sonic_set_request_bias), one reqbias.RequestBias or None per request;
+    that call consumes them.  Needs option request_bias (SonicError naming it otherwise); the caps were checked when the tables were built, the vocabulary is
+    checked here."""
+    tables = list(tables)
+    seq_ids, seq_off, bias, req_off = pack_request_bias(tables)
+    self._check(self.lib.sonic_set_request_bias(self.h, _p(seq_ids) if seq_ids.size else None, _p(seq_off), _p(bias) if bias.size else None, _p(req_off), len(tables)))
+
+
+def _test_greedy_bias(self, slabs, B: int, hist, hist_len, tables, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, suppress_tokens=(), force_ids=None,
+                      want_lp: bool = False):
+    """sonic_test_greedy_guard through greedy_kernel<T, LP, true, true>: `tables` holds one reqbias.RequestBias or None per row -> (token per row [B], RAW
+    logits [B][V], log-probability of the emitted token over the processed scores [B] or None)"""
+    s = np.ascontiguousarray(slabs, np.float32)
+    ks, mpad, V = s.shape
+    h = np.ascontiguousarray(hist, np.int32).reshape(B, -1)
+    hl = np.ascontiguousarray(hist_len, np.int32)
+    sup = np.ascontiguousarray(list(suppress_tokens), dtype=np.int32)
+    seq_ids, seq_off, bias, req_off = pack_request_bias(list(tables))
+    tok = np.zeros(B, np.int32)
+    lg = np.zeros((B, V), np.float32)
+    lp = np.full(B, np.nan, np.float32) if want_lp else None
+    f = np.ascontiguousarray(force_ids, np.int32) if force_ids is not None else None
+    self._check(self.lib.sonic_test_greedy_bias(self.h, _p(s), ks, mpad, V, B, _p(h) if h.size else None, h.shape[1], _p(hl), float(repetition_penalty),
+                                                int(no_repeat_ngram_size), _p(sup) if sup.size else None, int(sup.size), _p(f),
+                                                _p(seq_ids) if seq_ids.size else None, _p(seq_off), _p(bias) if bias.size else None, _p(req_off), _p(tok), _p(lg), _p(lp)))
     return tok, lg, lp
 
 
@@ -910,6 +970,8 @@ Engine.test_greedy = _test_greedy
 Engine.test_greedy_lp = _test_greedy_lp
 Engine.test_greedy_guard = _test_greedy_guard
 Engine.set_generation = _set_generation
+Engine.set_request_bias = _set_request_bias
+Engine.test_greedy_bias = _test_greedy_bias
 Engine.get_generation = _get_generation
 Engine.test_skinny_gu = _test_skinny_gu
 Engine.debug_read = _debug_read

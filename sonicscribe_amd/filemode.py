@@ -114,9 +114,11 @@ class _FileJob:
     """One file on the device: its ring, its plan and its queued decodes."""
 
     def __init__(self, model, audio, vad, vad_enabled: bool, hotwords, max_segment_duration, max_new_tokens: int, filename: str,
-                 sampling_rate: int = SAMPLE_RATE):
+                 sampling_rate: int = SAMPLE_RATE, sequence_bias=None, bad_words_ids=None, hotword_boost=None):
         if not hasattr(model, "model"):
             raise RuntimeError("ASR model has been released")
+        # the file's sequence-bias table (a model built with request_bias=True; ASRModel._request_bias): every segment of the file carries it
+        self.bias = model._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost) if hasattr(model, "_request_bias") else None
         self.model, self.filename = model, filename
         self.vad_enabled, self.hotwords = bool(vad_enabled), list(hotwords) if hotwords else None
         self.max_seg = float(max_segment_duration or DEFAULT_MAX_SEGMENT_S)
@@ -176,7 +178,7 @@ class _FileJob:
             # > 30 s: one request of several windows sharing one peak, as transcribe() makes it (frontend.split_windows)
             windows = [self.ring.slice(self.first + a + s, e - s) for s, e in frontend.split_windows(n, m.dims)]
             n_audio, _ = frontend.request_audio_tokens(n, m.dims)
-            self.futures.append(m._dispatcher.submit(windows, m.prompt.build(instruction, n_audio), self.max_new, replica=self.replica))
+            self.futures.append(m._dispatcher.submit(windows, m.prompt.build(instruction, n_audio), self.max_new, replica=self.replica, **({"bias": self.bias} if self.bias else {})))
 
     def records(self) -> Iterator[Dict[str, Any]]:
         total_segments = len(self.segments)
@@ -264,9 +266,9 @@ def _detect(vad, jobs: Sequence[_FileJob]) -> List[Any]:
 
 def transcribe_file(model, audio, vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                     max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filename: str = "",
-                    sampling_rate: int = SAMPLE_RATE) -> Iterator[Dict[str, Any]]:
+                    sampling_rate: int = SAMPLE_RATE, sequence_bias=None, bad_words_ids=None, hotword_boost=None) -> Iterator[Dict[str, Any]]:
     """Generator of the reference's file-mode records for one file (see ASRModel.transcribe_file)."""
-    job = _FileJob(model, audio, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filename, sampling_rate)
+    job = _FileJob(model, audio, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filename, sampling_rate, sequence_bias, bad_words_ids, hotword_boost)
     try:
         ts = vad.detect_voice_activity_ring(job.ring, job.first, job.total)[0] if job.wants_vad else None
         job.plan(ts)
@@ -279,14 +281,15 @@ def transcribe_file(model, audio, vad, vad_enabled: bool = True, hotwords: Optio
 
 def transcribe_files(model, audios: Sequence[Any], vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                      max_segment_duration: Optional[float] = None, max_new_tokens: int = 256,
-                     filenames: Optional[Sequence[str]] = None, sampling_rate: int = SAMPLE_RATE) -> List[FileRecords]:
+                     filenames: Optional[Sequence[str]] = None, sampling_rate: int = SAMPLE_RATE, sequence_bias=None, bad_words_ids=None,
+                     hotword_boost=None) -> List[FileRecords]:
     """One record iterator per file; the VAD of all files runs in one device call and every file's segments are queued before the call
     returns.  Each iterator must be exhausted or closed (its ring lives until then)."""
     names = list(filenames) if filenames is not None else [""] * len(audios)
     jobs: List[_FileJob] = []
     try:
         for a, name in zip(audios, names):
-            jobs.append(_FileJob(model, a, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, name, sampling_rate))
+            jobs.append(_FileJob(model, a, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, name, sampling_rate, sequence_bias, bad_words_ids, hotword_boost))
         for job, ts in zip(jobs, _detect(vad, jobs)):
             job.plan(ts)
         for job in jobs:

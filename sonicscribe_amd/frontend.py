@@ -45,21 +45,26 @@ def normalise_to_int16(wav: np.ndarray) -> np.ndarray:
     return np.clip(q, -32768, 32767).astype(np.int16)
 
 
-def format_hotwords_prompt(hotwords: Optional[Sequence[str]], max_hotwords: int = 10) -> str:
-    """asr.py:303-333.  The reference de-duplicates the RAW strings through ``set()`` (asr.py:318-322) and only then strips and
+def clean_hotwords(hotwords: Optional[Sequence[str]], max_hotwords: int = 10) -> List[str]:
+    """asr.py:303-333, the cleaning: the reference de-duplicates the RAW strings through ``set()`` (asr.py:318-322) and only then strips and
     lower-cases them, so ``["Alpha", "alpha "]`` yields two entries, ``"alpha", "alpha"``; only exact repeats of a raw string
     collapse.  ``set()`` iterates in an order that changes from process to process (string hash randomisation); this restatement
     keeps the first-seen order of the raw strings, which is one of the orders the reference can produce."""
     if not hotwords:
-        return ""
+        return []
     raw = []
     for hw in hotwords:
         if hw not in raw:            # set(hotwords): exact duplicates of the raw value only
             raw.append(hw)
     cleaned = [hw.strip().lower() for hw in raw if hw and isinstance(hw, str) and hw.strip()]
+    return cleaned[:max_hotwords]
+
+
+def format_hotwords_prompt(hotwords: Optional[Sequence[str]], max_hotwords: int = 10) -> str:
+    """asr.py:303-333: the cleaned hotwords (clean_hotwords) as the sentence the instruction ends with."""
+    cleaned = clean_hotwords(hotwords, max_hotwords)
     if not cleaned:
         return ""
-    cleaned = cleaned[:max_hotwords]
     return ". Pay special attention to these important terms: " + ", ".join(f'"{h}"' for h in cleaned)
 
 

@@ -38,8 +38,10 @@ def committed_max_new_tokens(seconds: float) -> int:
 
 class GatedSessions:
     def __init__(self, model, session_ids: Sequence[str], buffer_seconds: float = 30.0, hotwords: Optional[List[str]] = None,
-                 cfg: GateConfig = GateConfig(), device_vad: bool = False):
+                 cfg: GateConfig = GateConfig(), device_vad: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None):
         self.model, self.ids, self.hotwords, self.cfg = model, list(session_ids), hotwords, cfg
+        # beside the hotwords: the sessions' sequence-bias values (a model built with request_bias=True), handed to every decode only when one is given
+        self._bias_kw = {k: v for k, v in (("sequence_bias", sequence_bias), ("bad_words_ids", bad_words_ids), ("hotword_boost", hotword_boost)) if v is not None}
         self.device_vad = bool(device_vad)            # opt-in: windows are ring ranges, `recent` stays empty
         n = len(self.ids)
         self.streams = [model.open_stream(s, buffer_seconds) for s in self.ids]
@@ -134,7 +136,7 @@ class GatedSessions:
             if ns * 2 < CHUNK_BYTES:                                      # transcription_manager.py:21-22
                 continue
             events.append({"session": self.ids[s], "type": "partial", "start_chunk_id": lo, "end_chunk_id": hi, "first_sample": first, "n_samples": ns,
-                           "future": st.submit_samples(first, ns, PARTIAL_TOKENS, self.hotwords)})
+                           "future": st.submit_samples(first, ns, PARTIAL_TOKENS, self.hotwords, **self._bias_kw)})
         return events
 
     def _final(self, s: int, st, seg0: int, end_chunk_id: int) -> List[Dict]:
@@ -152,7 +154,7 @@ class GatedSessions:
         if seg_dur <= MAX_SEGMENT_S:                                      # one request, whatever its audio length (the processor windows it)
             return [{"session": self.ids[s], "type": "final", "start_chunk_id": seg0, "end_chunk_id": end_chunk_id, "part": 0, "parts": 1,
                      "seconds": seg_dur, "first_sample": first, "n_samples": ns,
-                     "future": st.submit_samples(first, ns, committed_max_new_tokens(seg_dur), self.hotwords)}]
+                     "future": st.submit_samples(first, ns, committed_max_new_tokens(seg_dur), self.hotwords, **self._bias_kw)}]
         n_sub = -(-ns // piece)
         for i in range(n_sub):                                            # longer: pieces cut at sample 480000 * i, each with its own duration
             a, b = i * piece, min(ns, (i + 1) * piece)
@@ -160,7 +162,7 @@ class GatedSessions:
                 continue
             out.append({"session": self.ids[s], "type": "final", "start_chunk_id": seg0, "end_chunk_id": end_chunk_id, "part": i, "parts": n_sub,
                         "seconds": (b - a) / self.sr, "first_sample": first + a, "n_samples": b - a,
-                        "future": st.submit_samples(first + a, b - a, committed_max_new_tokens((b - a) / self.sr), self.hotwords)})
+                        "future": st.submit_samples(first + a, b - a, committed_max_new_tokens((b - a) / self.sr), self.hotwords, **self._bias_kw)})
         return out
 
     def close(self):
