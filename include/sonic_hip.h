@@ -54,6 +54,9 @@
  *                              (SequenceBiasLogitsProcessor, NoBadWordsLogitsProcessor; generation/logits_process.py),
  *                              one table per request                                                      backend/asr.py:303-333
  *   sonic_dispatch_submit_bias / sonic_test_greedy_bias   (the same through the dispatcher; test hook of the kernel behind it)
+ *   sonic_set_request_sampling temperature sampling with a seed per request (HF's TemperatureLogitsWarper + multinomial as one Gumbel-max draw): what
+ *                              openai-whisper's decode_with_fallback retries a poor segment with
+ *   sonic_dispatch_submit_sampled / sonic_test_greedy_sample   (the same through the dispatcher; test hook of the kernel behind it)
  */
 #ifndef SONIC_HIP_H
 #define SONIC_HIP_H
@@ -250,6 +253,20 @@ SONIC_API int sonic_set_generation(sonic_engine* e, float repetition_penalty, in
  *       seq_ids[seq_off[i] .. seq_off[i + 1]) with bias[i].  SONIC_ERR_INVALID, nothing truncated: the option is off (the message names it), more than 256
  *       entries in a request, a sequence outside 1 .. 8 ids, an id outside the vocabulary, a NaN or +inf bias; at the prefill, an R that is not the batch's. */
 SONIC_API int sonic_set_request_bias(sonic_engine* e, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, const int32_t* req_off, int R);
+/* Temperature sampling.  A request with temperature t > 0 and a 64-bit seed emits, as its n-th token (n = 0 for the prefill's), the first maximum over
+ * the vocabulary of y_i = fdiv_rn(s_i, t) + g_i in fp32: s the fully processed score (request bias, repetition penalty, bans: HF's order, then its
+ * TemperatureLogitsWarper), g_i = -ln(-ln(u_i)), u_i = ((w_i >> 9) + 0.5) * 2^-23, w_i = word i & 3 of Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and
+ * counter (i >> 2, n, 0, 0).  By the Gumbel-max identity this is an exact draw from softmax(s / t); it depends on (scores, t, seed, n) alone - never on batch, row,
+ * slot or scheduler - so a sampled transcript is as reproducible as a greedy one.  The kernel's g is within 3.2e-6 of the exact value.  t = 0 is
+ * greedy decoding, bit for bit.  The log-probabilities (option token_logprobs) stay log_softmax(s)[token] at temperature 1: openai-whisper's convention, the one the
+ * thresholds of its fallback are calibrated on.  step_logits stay raw; teacher forcing wins over sampling; a row whose scores are all -inf emits token 0.
+ *   option "sampling" (sonic_set_option): on the owner before its slots are created (they copy it) and after option token_logprobs (SONIC_ERR_INVALID naming
+ *       token_logprobs otherwise); allocates three words per row (counted by sonic_memory_info); refused while the handle has work in hand.  sonic_splice_rows
+ *       copies a row's words and refuses handles whose options differ.
+ *   sonic_set_request_sampling: the values of the R requests of the NEXT prefill on this handle (the entry points sonic_set_request_bias names), which consumes them
+ *       on success and on failure alike; a batch without values is greedy.  SONIC_ERR_INVALID, nothing clamped: the option is off (the message names it), a
+ *       temperature that is neither 0 nor in [1e-3, 100] (NaN included); at the prefill, an R that is not the batch's. */
+SONIC_API int sonic_set_request_sampling(sonic_engine* e, const float* temperature, const uint64_t* seed, int R);
 /* the values in force on this handle; at most `cap` ids are copied to suppress, *n_suppress is their full count (any pointer may be NULL) */
 SONIC_API int sonic_get_generation(sonic_engine* e, float* repetition_penalty, int32_t* no_repeat_ngram_size, int32_t* suppress, int cap, int32_t* n_suppress);
 /* sonic_run_staged without blocking the caller: the arguments are copied, a worker thread owned by the handle runs the batch, the call
@@ -312,6 +329,12 @@ SONIC_API int sonic_dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, 
 SONIC_API int sonic_dispatch_submit_bias(sonic_dispatch* d, const int16_t* host_pcm, const int64_t* host_off, struct sonic_ring* const* rings, const int64_t* ring_start,
                                          const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, const int32_t* seq_ids,
                                          const int32_t* seq_off, const float* bias, int n_seq, int64_t* ticket_out);
+/* sonic_dispatch_submit with the request's own (temperature, seed) and, for n_seq > 0, its sequence-bias table as sonic_dispatch_submit_bias takes it.
+ * SONIC_ERR_INVALID unless every handle of the dispatcher has option sampling on (and request_bias, for a table), and for an invalid temperature;
+ * sonic_last_error(NULL) of the calling thread says which. */
+SONIC_API int sonic_dispatch_submit_sampled(sonic_dispatch* d, const int16_t* host_pcm, const int64_t* host_off, struct sonic_ring* const* rings, const int64_t* ring_start,
+                                            const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, float temperature, uint64_t seed,
+                                            const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n_seq, int64_t* ticket_out);
 SONIC_API int sonic_dispatch_cancel(sonic_dispatch* d, int64_t ticket);                 /* queued requests only */
 /* next completed request in completion order; blocks up to timeout_ms (< 0: until one completes or the dispatcher is closed and drained); *ticket_out = 0: none */
 SONIC_API int sonic_dispatch_next(sonic_dispatch* d, int timeout_ms, int64_t* ticket_out, int32_t* status_out, int32_t* out_ids, int out_cap, int32_t* n_out,
@@ -422,6 +445,15 @@ SONIC_API int sonic_test_greedy_bias(sonic_engine* e, const float* slabs, int ks
                                      float repetition_penalty, int no_repeat_ngram_size, const int32_t* suppress, int n_suppress, const int32_t* force_ids,
                                      const int32_t* seq_ids, const int32_t* seq_off, const float* bias, const int32_t* req_off,
                                      int32_t* tok_out, float* logits_out, float* lp_out);
+/* the same launch through the sampling instantiations (greedy_kernel<T, true, GUARD, BIAS, true>) in the handle's own type: hist_len = NULL: the plain family (the
+ * guard arguments are ignored); hist_len without req_off: the guard family; both: the bias family.  Row b draws with temperature[b] and seed[b] as its step[b]-th
+ * token (0 .. 65535).  lp_out is required (log_softmax over the processed scores at temperature 1); noise_out[B][V] (may be NULL) receives the Gumbel value the
+ * kernel added at every id of a row with temperature > 0 and stays 0 for the others. */
+SONIC_API int sonic_test_greedy_sample(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const int32_t* hist, int hist_ld, const int32_t* hist_len,
+                                       float repetition_penalty, int no_repeat_ngram_size, const int32_t* suppress, int n_suppress, const int32_t* force_ids,
+                                       const int32_t* seq_ids, const int32_t* seq_off, const float* bias, const int32_t* req_off,
+                                       const float* temperature, const uint64_t* seed, const int32_t* step,
+                                       int32_t* tok_out, float* logits_out, float* lp_out, float* noise_out);
 SONIC_API int sonic_test_attention(sonic_engine* e, const float* q, const float* k, const float* v, float* out,
                          int B, int Tq, int Tk, int Hq, int Hkv, int hd, int causal);
 SONIC_API int sonic_test_decode_attention(sonic_engine* e, const float* q, const float* k, const float* v, float* out,

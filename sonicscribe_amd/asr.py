@@ -83,11 +83,15 @@ class HFPrompt:
 class Transcription:
     """What a `detailed=True` request resolves to (ASRModel(token_logprobs=True)): the transcript, the emitted token ids (EOS included), every
     token's log-probability under the model (float32; HF compute_transition_scores(..., normalize_logits=True) of the greedy generate()) and their
-    mean - the number a caller turns into the wire messages' "confidence" (connection_manager.py:159,274 can only send constants)."""
-    __slots__ = ("text", "token_ids", "token_logprobs", "avg_logprob")
+    mean - the number a caller turns into the wire messages' "confidence" (connection_manager.py:159,274 can only send constants).  `temperature`: the one this
+    transcript was decoded at (0: greedy); `compression_ratio`: fallback.compression_ratio of the text; `attempts`: how many decodes the fallback ladder took (1
+    without a ladder).  The log-probabilities are at temperature 1 whatever the sampling temperature (openai-whisper's convention)."""
+    __slots__ = ("text", "token_ids", "token_logprobs", "avg_logprob", "temperature", "compression_ratio", "attempts")
 
-    def __init__(self, text: str, token_ids, token_logprobs):
+    def __init__(self, text: str, token_ids, token_logprobs, temperature: float = 0.0):
+        from .fallback import compression_ratio
         self.text = text
+        self.temperature, self.compression_ratio, self.attempts = float(temperature), compression_ratio(text), 1
         self.token_ids = np.asarray(token_ids, np.int32)
         self.token_logprobs = np.asarray(token_logprobs, np.float32)
         # over all emitted tokens, the EOS that stopped the row included; nothing emitted: nan
@@ -97,7 +101,7 @@ class Transcription:
         return f"Transcription(text={self.text!r}, tokens={self.token_ids.size}, avg_logprob={self.avg_logprob:.4f})"
 
 
-def _text_future(inner: "Future", decode, detailed: bool = False) -> "Future[str]":
+def _text_future(inner: "Future", decode, detailed: bool = False, temperature: float = 0.0) -> "Future[str]":
     """Future of the transcript behind a dispatcher future of token ids.  Cancelling it (a session that went away) cancels the queued
     request as well, so it never reaches the device.  detailed: the inner future carries (ids, log-probabilities), the result is a Transcription."""
     out: "Future[str]" = Future()
@@ -108,7 +112,7 @@ def _text_future(inner: "Future", decode, detailed: bool = False) -> "Future[str
         try:
             if detailed:
                 ids, lps = f.result()
-                out.set_result(Transcription(decode(ids).strip(), ids, lps))
+                out.set_result(Transcription(decode(ids).strip(), ids, lps, temperature))
             else:
                 out.set_result(decode(f.result()).strip())
         except BaseException as ex:
@@ -186,23 +190,26 @@ class AudioStream:
         return None if c is None else (c[0], c[1])
 
     def submit_samples(self, first: int, n: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None, detailed: bool = False,
-                       sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None) -> "Future[str]":
+                       sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature: Optional[float] = None,
+                       seed: Optional[int] = None) -> "Future[str]":
         """Transcribe ring samples [first, first + n) (the >30 s split of connection_manager.py:206-214 cuts at byte offsets, not chunks).
-        detailed (a model built with token_logprobs=True): the future gives a Transcription instead of the text."""
+        detailed (a model built with token_logprobs=True): the future gives a Transcription instead of the text.  temperature / seed (a model built with
+        sampling=True): one attempt at that temperature - a float only, stream decodes take no fallback ladder."""
         m = self.model
         m._check_detailed(detailed)
         bias = m._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost)
+        samp = m._request_sampling(temperature, seed, ladder_ok=False)
         windows = [self.ring.slice(first + s, e - s) for s, e in frontend.split_windows(n, m.dims)]
         n_audio, _ = frontend.request_audio_tokens(n, m.dims)
         prompt = m.prompt.build(frontend.build_instruction(hotwords), n_audio)
-        inner = m._dispatcher.submit(windows, prompt, int(max_new_tokens), replica=self.replica, want_logprobs=detailed, **({"bias": bias} if bias else {}))
-        return _text_future(inner, m.prompt.decode, detailed)
+        return m._dispatch(windows, prompt, int(max_new_tokens), detailed, bias, samp, replica=self.replica)
 
     def submit_chunks(self, start_chunk_id: int, end_chunk_id: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None,
-                      detailed: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None) -> "Future[str]":
+                      detailed: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
+                      temperature: Optional[float] = None, seed: Optional[int] = None) -> "Future[str]":
         """Transcribe chunks start..end inclusive (audio_manager.py:76-79 get_chunks_by_range + :115-123 concatenation)."""
         first, n = self.chunk_range_samples(start_chunk_id, end_chunk_id)
-        return self.submit_samples(first, n, max_new_tokens, hotwords, detailed, sequence_bias, bad_words_ids, hotword_boost)
+        return self.submit_samples(first, n, max_new_tokens, hotwords, detailed, sequence_bias, bad_words_ids, hotword_boost, temperature, seed)
 
     async def transcribe_chunks(self, start_chunk_id: int, end_chunk_id: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None) -> str:
         return await asyncio.wrap_future(self.submit_chunks(start_chunk_id, end_chunk_id, max_new_tokens, hotwords))
@@ -218,17 +225,33 @@ class ASRModel:
                  cpu_threads: Optional[int] = None, cpu_interop_threads: Optional[int] = None,
                  *, max_batch: int = 32, max_ctx: int = 1024, slots: int = DEFAULT_SLOTS, continuous: bool = DEFAULT_CONTINUOUS, decoders: int = 1, bulk: bool = False, native_dispatch: Optional[bool] = None, token_logprobs: bool = False,
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None,
-                 request_bias: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: float = 0.0, _dims: Optional[ModelDims] = None,
+                 request_bias: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: float = 0.0,
+                 sampling: bool = False, temperature=0.0, seed: int = 0, compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
+                 _dims: Optional[ModelDims] = None,
                  _synthetic_seed: Optional[int] = None, _allow_synthetic_prompt: bool = False, _options: Optional[Dict[str, int]] = None,
                  _engine_mode: Optional[int] = None):
         """The reference's ASRModel surface over the HIP engine.  `repetition_penalty`, `no_repeat_ngram_size`, `suppress_tokens`: None = the value of the
         checkpoint's generation_config.json, anything else overrides it (genconfig.py).  `request_bias`: requests may bring their own sequence-bias table
         (HF's sequence_bias / bad_words_ids, and `hotword_boost` > 0: the call's hotwords as entries; reqbias.py); `sequence_bias`, `bad_words_ids`,
-        `hotword_boost` here are defaults for every request and switch `request_bias` on.  The arguments with a leading underscore are not part of the
+        `hotword_boost` here are defaults for every request and switch `request_bias` on.  `sampling` (needs token_logprobs=True): requests may be decoded at a
+        temperature with a seed, or down a fallback ladder of temperatures (fallback.py); `temperature` (a float: one attempt; a sequence: the
+        ladder), `seed` and the two thresholds of the ladder here are the defaults of every call.  The arguments with a leading underscore are not part of the
         supported surface: they exist for the test-suite and the benchmark and may change without notice.  `_engine_mode` in particular (an engine.MODE_*
         value in place of the one `mode` selects) is unsupported outside the tests: MODE_F32 has no slots, so it needs slots=1, continuous=False."""
         if mode not in ["native", "int8"]:
             raise ValueError("mode must be either 'native' or 'int8'")            # asr.py:46-47
+        from . import fallback as fallback_, sampling as sampling_
+        self.sampling = bool(sampling)
+        self._default_temperature, self._default_seed = temperature, sampling_.check_seed(seed)
+        ts_, _ = sampling_.temperatures(temperature)
+        fallback_.FallbackPolicy(ts_, compression_ratio_threshold, logprob_threshold)      # (validates the values)
+        self.compression_ratio_threshold, self.logprob_threshold = compression_ratio_threshold, logprob_threshold
+        if not self.sampling and (any(t != 0.0 for t in ts_) or self._default_seed != 0):
+            raise ValueError("temperature / seed need a model built with sampling=True (ASRModel(..., token_logprobs=True, sampling=True))")
+        if self.sampling and not token_logprobs:
+            raise ValueError("sampling=True needs token_logprobs=True: the sampling kernels are log-probability kernels, and the fallback ladder reads avg_logprob")
+        if self.sampling and bool(bulk):
+            raise ValueError("sampling is not supported with bulk=True: the bulk pipeline carries no per-request values")
         dev = str(device)
         if dev.startswith("cpu"):
             raise RuntimeError("sonicscribe_amd runs on MI355X only: DEVICE=cpu has no HIP path (no CPU fallback by design)")
@@ -306,6 +329,14 @@ class ASRModel:
         if self.request_bias:
             for eng in self.models:
                 eng.set_option("request_bias", 1)
+        # sampling: every request may be decoded at its own temperature with its own seed (engine option of the same name, behind token_logprobs and before the slots
+        # exist), or down a ladder of temperatures until its transcript passes the two thresholds (fallback.py)
+        # (the values were checked before any engine was built)
+        from . import fallback
+        if self.sampling:
+            for eng in self.models:
+                eng.set_option("sampling", 1)
+        self._retrier = fallback.Retrier()
         self.model = self.models[0]                  # main.py:84-86 checks and deletes `.model`
         # continuous: `decoders` handles per replica run a greedy loop over max_batch rows each, the other handles prefill (>= 1).  Streaming:
         # decoders=1, slots=2.  Bulk transcription of many segments: max_batch=64, decoders=3, slots=4 (the bench's pipeline shape since round 5; decoders=2, slots=3 before).
@@ -371,24 +402,76 @@ class ASRModel:
         out = reqbias.combine(self._default_bias, call, hot)
         return out if out else None
 
+    def _request_sampling(self, temperature=None, seed=None, ladder_ok: bool = True):
+        """One call's sampling: None (a model without the option, nothing asked), or (temperatures, is it a ladder, seed) from the call's values over the
+        constructor's defaults.  ValueError naming sampling when the call gives a value and the model was built without the option."""
+        from . import sampling as sampling_
+        if not getattr(self, "sampling", False):
+            if temperature is not None or seed is not None:
+                raise ValueError("temperature / seed need a model built with sampling=True (ASRModel(..., token_logprobs=True, sampling=True))")
+            return None
+        if getattr(self, "bulk", False):
+            raise ValueError("a temperature is not supported with bulk=True")
+        ts, ladder = sampling_.temperatures(self._default_temperature if temperature is None else temperature)
+        if ladder and not ladder_ok:
+            raise ValueError("stream decodes take one temperature (a float), not a fallback ladder")
+        return ts, ladder, sampling_.check_seed(self._default_seed if seed is None else seed)
+
+    def _dispatch(self, windows, prompt, max_new: int, detailed: bool, bias, samp, **route) -> "Future":
+        """One request on the scheduler -> a future of its text (detailed: its Transcription).  samp (from _request_sampling): None, one attempt at a temperature,
+        or the fallback ladder - each attempt a new request for the same windows, prompt, table and seed; the future resolves after the last one.  Retries
+        are submitted by the model's worker thread, never by a completion callback and never by the caller (fallback.py)."""
+        from . import fallback
+        kw = dict(route)
+        if bias:
+            kw["bias"] = bias
+        if samp is None:
+            return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=detailed, **kw), self.prompt.decode, detailed)
+        ts, ladder, seed = samp
+        if not ladder:
+            return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=detailed, sampling=(ts[0], seed), **kw), self.prompt.decode, detailed, ts[0])
+
+        def one(temperature, seed):
+            return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=True, sampling=(temperature, seed), **kw), self.prompt.decode, True, temperature)
+        policy = fallback.FallbackPolicy(ts, self.compression_ratio_threshold, self.logprob_threshold)
+        fut = fallback.decode_with_fallback(one, policy, seed, retrier=self._retrier)
+        if detailed:
+            return fut
+        out: "Future[str]" = Future()
+
+        def done(f):
+            if out.done():
+                return
+            try:
+                out.set_result(f.result().text)
+            except BaseException as ex:
+                if not out.done():
+                    out.set_exception(ex)
+        fut.add_done_callback(done)
+        out.add_done_callback(lambda f: fut.cancel() if f.cancelled() else None)
+        return out
+
     def _check_detailed(self, detailed: bool):
         if detailed and not getattr(self, "token_logprobs", False):
             raise ValueError("detailed=True needs a model built with token_logprobs=True (ASRModel(..., token_logprobs=True))")
 
     def submit(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None,
-               session: Optional[str] = None, detailed: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None) -> "Future[str]":
+               session: Optional[str] = None, detailed: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
+               temperature=None, seed: Optional[int] = None) -> "Future[str]":
         """Non-blocking form of transcribe(): queues the request on a replica and returns a Future of the transcript.  `session`
         (e.g. the WebSocket client id) keeps a session's decodes on one GPU.  detailed (a model built with token_logprobs=True): the future
         gives a Transcription - text, token_ids, token_logprobs, avg_logprob - instead of the text.  sequence_bias / bad_words_ids / hotword_boost (a model
-        built with request_bias=True): this request's own table, on top of the constructor's defaults (_request_bias)."""
+        built with request_bias=True): this request's own table, on top of the constructor's defaults (_request_bias).  temperature / seed (a model built with
+        sampling=True): a float decodes once at that temperature, a sequence is the fallback ladder - the future resolves after its last attempt, and this
+        thread never waits for one (_dispatch)."""
         if not hasattr(self, "model"):
             raise RuntimeError("ASR model has been released")
         self._check_detailed(detailed)
         bias = self._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost)
+        samp = self._request_sampling(temperature, seed)
         pcm, windows, n_audio = self._prepare(audio_tensor, sampling_rate)
         prompt = self.prompt.build(frontend.build_instruction(hotwords), n_audio)
-        inner = self._dispatcher.submit(windows, prompt, int(max_new_tokens), session=session, want_logprobs=detailed, **({"bias": bias} if bias else {}))
-        return _text_future(inner, self.prompt.decode, detailed)
+        return self._dispatch(windows, prompt, int(max_new_tokens), detailed, bias, samp, session=session)
 
     def open_stream(self, session: str, buffer_seconds: float = 30.0, margin_seconds: float = 10.0, sampling_rate: int = 16000) -> AudioStream:
         """A streaming session whose audio stays on the device (config.py:25 MAX_AUDIO_BUFFER_SECONDS = 30): chunks are appended to a
@@ -402,21 +485,21 @@ class ASRModel:
 
     async def transcribe_async(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128,
                                hotwords: Optional[List[str]] = None, session: Optional[str] = None, detailed: bool = False,
-                               sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None) -> str:
+                               sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None, seed: Optional[int] = None) -> str:
         """Awaitable transcribe() for the asyncio callers (connection_manager.py:127-245): the event loop is not blocked while the
         device works, so all sessions' partial and final decodes can be in flight (and batched) together."""
-        return await asyncio.wrap_future(self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, session, detailed, sequence_bias, bad_words_ids, hotword_boost))
+        return await asyncio.wrap_future(self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, session, detailed, sequence_bias, bad_words_ids, hotword_boost, temperature, seed))
 
     def transcribe(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128,
                    hotwords: Optional[List[str]] = None, return_debug_info: bool = False,
-                   sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None) -> Union[str, Dict[str, Any]]:
+                   sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None, seed: Optional[int] = None) -> Union[str, Dict[str, Any]]:
         if not hasattr(self, "model"):
             raise RuntimeError("ASR model has been released")
         t0 = time.time()
         try:
             want = bool(return_debug_info and getattr(self, "token_logprobs", False))
             res = self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, detailed=want, sequence_bias=sequence_bias, bad_words_ids=bad_words_ids,
-                              hotword_boost=hotword_boost).result()
+                              hotword_boost=hotword_boost, temperature=temperature, seed=seed).result()
             det, transcript = (res, res.text) if want else (None, res)
             elapsed = time.time() - t0
             if return_debug_info:
@@ -428,6 +511,8 @@ class ASRModel:
                 if det is not None:                                  # a token_logprobs model: what fills the wire messages' "confidence"
                     info.update({"token_ids": det.token_ids, "token_logprobs": det.token_logprobs, "avg_logprob": det.avg_logprob,
                                  "confidence": math.exp(det.avg_logprob)})
+                    if getattr(self, "sampling", False):             # a sampling model: what the transcript was decoded at, and the ladder's other measure
+                        info.update({"temperature": det.temperature, "compression_ratio": det.compression_ratio})
                 return info
             return transcript
         except RuntimeError as e:
@@ -439,10 +524,15 @@ class ASRModel:
             raise
 
     def transcribe_batch(self, audios: Sequence[Any], sampling_rate: int = 16000, max_new_tokens: Union[int, Sequence[int]] = 128,
-                         hotwords: Optional[List[str]] = None, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None) -> List[str]:
-        """Batched extension (the reference is B=1 per call): one device batch, per-segment results identical to transcribe()."""
+                         hotwords: Optional[List[str]] = None, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
+                         temperature=None, seed: Optional[int] = None) -> List[str]:
+        """Batched extension (the reference is B=1 per call): one device batch, per-segment results identical to transcribe().  temperature / seed: every
+        segment is decoded with them (a sequence: every segment goes down its own ladder, as independent requests on the scheduler)."""
         bias = self._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost)
+        samp = self._request_sampling(temperature, seed)
         kw = {"request_bias": [bias] * len(audios)} if bias else {}
+        if samp is not None and not samp[1]:
+            kw["request_sampling"] = [(samp[0][0], samp[2])] * len(audios)
         mn = [int(max_new_tokens)] * len(audios) if isinstance(max_new_tokens, int) else [int(x) for x in max_new_tokens]
         segs, req_win, prompts = [], [0], []
         instruction = frontend.build_instruction(hotwords)
@@ -451,16 +541,20 @@ class ASRModel:
             segs.extend(wins)
             req_win.append(len(segs))
             prompts.append(self.prompt.build(instruction, n_audio))
+        if samp is not None and samp[1]:
+            futs = [self._dispatch(segs[req_win[i]:req_win[i + 1]], prompts[i], mn[i], False, bias, samp) for i in range(len(audios))]
+            return [f.result() for f in futs]
         if len(self.models) == 1 and not self.continuous:
             ids, _ = self.model.transcribe_batch(segs, prompts, mn, req_win=req_win, **kw)
         else:            # independent segments: spread over the replicas (least-loaded placement), results in input order
-            futs = [self._dispatcher.submit(segs[req_win[i]:req_win[i + 1]], prompts[i], mn[i], **({"bias": bias} if bias else {})) for i in range(len(audios))]
+            skw = {"sampling": kw["request_sampling"][0]} if "request_sampling" in kw else {}
+            futs = [self._dispatcher.submit(segs[req_win[i]:req_win[i + 1]], prompts[i], mn[i], **({"bias": bias} if bias else {}), **skw) for i in range(len(audios))]
             ids = [f.result() for f in futs]
         return [self.prompt.decode(i).strip() for i in ids]
 
     def transcribe_file(self, audio, vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                         max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filename: str = "", sampling_rate: int = 16000,
-                        sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None):
+                        sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None, seed: Optional[int] = None):
         """The body of the reference's /transcribe/file endpoint (main.py:193-649) as a generator of its records (dicts with the
         reference's keys: initialization, segments_summary, segment_result / segment_error in segment order, final_summary).  `audio`:
         mono int16 PCM at `sampling_rate`, or the reference's float tensor [1, N] of int16 / 32768 values; `vad`: a vad.VADProcessor.  The
@@ -469,15 +563,16 @@ class ASRModel:
         the generator is exhausted or closed (filemode.py).  Sizes and times in the records are those of the 16 kHz content."""
         from . import filemode
         return filemode.transcribe_file(self, audio, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filename, sampling_rate,
-                                        sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotword_boost=hotword_boost)
+                                        sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotword_boost=hotword_boost, temperature=temperature, seed=seed)
 
     def transcribe_files(self, audios: Sequence[Any], vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                          max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filenames: Optional[Sequence[str]] = None,
-                         sampling_rate: int = 16000, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None):
+                         sampling_rate: int = 16000, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None,
+                         seed: Optional[int] = None):
         """transcribe_file for several files: all VAD passes in one device call, one record iterator per file (filemode.transcribe_files)."""
         from . import filemode
         return filemode.transcribe_files(self, audios, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filenames, sampling_rate,
-                                         sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotword_boost=hotword_boost)
+                                         sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotword_boost=hotword_boost, temperature=temperature, seed=seed)
 
     def get_model_info(self) -> Dict[str, Any]:
         """asr.py:490-513: the reference's keys for a GPU device (`cuda_version` carries the HIP runtime version: torch.version.cuda is
@@ -496,6 +591,9 @@ class ASRModel:
         return info
 
     def close(self):
+        r = self.__dict__.pop("_retrier", None)
+        if r is not None:
+            r.close()
         c = self.__dict__.pop("_dispatcher", None)
         if c is not None:
             c.close()

@@ -36,6 +36,8 @@
 extern "C" int engine_token_logprobs_on(sonic_engine* e);   // engine.cpp
 extern "C" int engine_request_bias_on(sonic_engine* e);     // engine.cpp: option request_bias on this handle
 extern "C" int engine_bias_validate(sonic_engine* e, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n);   // engine.cpp: one request's table against the caps and this handle's vocabulary
+extern "C" int engine_sampling_on(sonic_engine* e);         // engine.cpp: option sampling on this handle
+extern "C" int engine_sampling_validate(float temperature); // engine.cpp: 0 or 1e-3 .. 100 (the message goes to the calling thread's sonic_last_error(NULL))
 extern "C" int engine_thread_fail(int code, const char* msg);   // engine.cpp: the calling thread's sonic_last_error(NULL)
 
 namespace {
@@ -49,6 +51,7 @@ struct Req {
     int status = -1; std::string err; std::vector<int32_t> ids;    // result
     std::vector<float> lp;                                         // ... and, with option token_logprobs on the handles, every token's log-probability
     std::vector<int32_t> b_ids, b_off; std::vector<float> b_val;  // its own sequence-bias table (sonic_dispatch_submit_bias): ids, offsets [n + 1] (empty: none), biases
+    bool sampled = false; float temperature = 0.f; uint64_t seed = 0;   // its own (temperature, seed) (sonic_dispatch_submit_sampled); unsampled requests of a batch are greedy
     bool cancelled = false;
 };
 typedef std::shared_ptr<Req> ReqP;
@@ -62,6 +65,7 @@ struct sonic_dispatch {
     bool adaptive_tiles = true;
     bool lp = false;                                               // every handle has option token_logprobs on
     bool bias = false;                                             // every handle has option request_bias on
+    bool samp = false;                                             // every handle has option sampling on
     std::mutex mu;
     std::condition_variable cv;                                    // queue, hand-overs, free rows, state
     std::condition_variable cv_done;                               // completions
@@ -123,6 +127,13 @@ int prefill_batch(sonic_dispatch* d, sonic_engine* h, const std::vector<ReqP>& b
             r_off.push_back((int32_t)s_val.size());
         }
         rc = sonic_set_request_bias(h, s_ids.data(), s_off.data(), s_val.data(), r_off.data(), R);
+    }
+    bool any_samp = false;
+    for (auto& r : batch) any_samp = any_samp || r->sampled;
+    if (rc == SONIC_OK && any_samp) {                              // the requests' (temperature, seed); the prefill below consumes them
+        std::vector<float> t; std::vector<uint64_t> sd;
+        for (auto& r : batch) { t.push_back(r->sampled ? r->temperature : 0.f); sd.push_back(r->sampled ? r->seed : 0); }
+        rc = sonic_set_request_sampling(h, t.data(), sd.data(), R);
     }
     if (rc == SONIC_OK) rc = sonic_prefill(h, req_win.data(), R, ids.data(), poff.data(), mn.data(), 0);
     if (rc != SONIC_OK && err) *err = sonic_last_error(h);
@@ -300,6 +311,8 @@ SONIC_API int sonic_dispatch_create(sonic_engine* const* decoders, int n_dec, so
     for (int i = 0; i < n_dec + n_pre; ++i) d->lp = d->lp && engine_token_logprobs_on(i < n_dec ? decoders[i] : prefills[i - n_dec]);
     d->bias = true;
     for (int i = 0; i < n_dec + n_pre; ++i) d->bias = d->bias && engine_request_bias_on(i < n_dec ? decoders[i] : prefills[i - n_dec]);
+    d->samp = true;
+    for (int i = 0; i < n_dec + n_pre; ++i) d->samp = d->samp && engine_sampling_on(i < n_dec ? decoders[i] : prefills[i - n_dec]);
     d->free_rows.assign(n_dec, rows); d->hand.resize(n_dec);
     for (int i = 0; i < n_dec; ++i) {
         const int rc = sonic_service_begin(d->dec[i]);
@@ -316,7 +329,7 @@ SONIC_API int sonic_dispatch_create(sonic_engine* const* decoders, int n_dec, so
 // PCM, normalised on the device over the request's windows).  Everything is copied before the call returns.
 static int dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, const int64_t* host_off, sonic_ring* const* rings, const int64_t* ring_start,
                            const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, const int32_t* seq_ids, const int32_t* seq_off,
-                           const float* bias, int n_seq, int64_t* ticket_out) {
+                           const float* bias, int n_seq, int64_t* ticket_out, bool sampled = false, float temperature = 0.f, uint64_t seed = 0) {
     if (!d || !ticket_out || W < 1 || !prompt_ids || prompt_len < 1 || max_new < 1 || !host_off) return SONIC_ERR_INVALID;
     if (rings && (!ring_start || !ring_n)) return SONIC_ERR_INVALID;
     auto r = std::make_shared<Req>();
@@ -329,6 +342,7 @@ static int dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, const int
         for (int w = 0; w < W; ++w) r->any_ring = r->any_ring || rings[w];
     }
     r->prompt.assign(prompt_ids, prompt_ids + prompt_len); r->max_new = max_new;
+    r->sampled = sampled; r->temperature = temperature; r->seed = seed;
     if (n_seq > 0) { r->b_off.assign(seq_off, seq_off + n_seq + 1); r->b_ids.assign(seq_ids + seq_off[0], seq_ids + seq_off[n_seq]); r->b_val.assign(bias, bias + n_seq);
                      for (auto& o : r->b_off) o -= seq_off[0]; }
     std::unique_lock<std::mutex> lk(d->mu);
@@ -356,6 +370,20 @@ SONIC_API int sonic_dispatch_submit_bias(sonic_dispatch* d, const int16_t* host_
     if (n_seq < 0 || (n_seq > 0 && (!seq_ids || !seq_off || !bias))) return SONIC_ERR_INVALID;
     if (n_seq > 0) { const int rc = engine_bias_validate(d->pre[0], seq_ids, seq_off, bias, n_seq); if (rc != SONIC_OK) return rc; }
     return dispatch_submit(d, host_pcm, host_off, rings, ring_start, ring_n, W, prompt_ids, prompt_len, max_new, seq_ids, seq_off, bias, n_seq, ticket_out);
+}
+
+// sonic_dispatch_submit with the request's own (temperature, seed), and its sequence-bias table where one is given (n_seq > 0): SONIC_ERR_INVALID unless every
+// handle of the dispatcher has option sampling on (and request_bias for a table), and for a temperature that is neither 0 nor in 1e-3 .. 100
+SONIC_API int sonic_dispatch_submit_sampled(sonic_dispatch* d, const int16_t* host_pcm, const int64_t* host_off, sonic_ring* const* rings, const int64_t* ring_start,
+                                            const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, float temperature, uint64_t seed,
+                                            const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n_seq, int64_t* ticket_out) {
+    if (!d) return SONIC_ERR_INVALID;
+    if (!d->samp) return engine_thread_fail(SONIC_ERR_INVALID, "sonic_dispatch_submit_sampled: option sampling is off on a handle of this dispatcher (set it on the owner before its slots are created)");
+    { const int rc = engine_sampling_validate(temperature); if (rc != SONIC_OK) return rc; }
+    if (n_seq < 0 || (n_seq > 0 && (!seq_ids || !seq_off || !bias))) return SONIC_ERR_INVALID;
+    if (n_seq > 0 && !d->bias) return engine_thread_fail(SONIC_ERR_INVALID, "sonic_dispatch_submit_sampled: option request_bias is off on a handle of this dispatcher (set it on the owner before its slots are created)");
+    if (n_seq > 0) { const int rc = engine_bias_validate(d->pre[0], seq_ids, seq_off, bias, n_seq); if (rc != SONIC_OK) return rc; }
+    return dispatch_submit(d, host_pcm, host_off, rings, ring_start, ring_n, W, prompt_ids, prompt_len, max_new, seq_ids, seq_off, bias, n_seq, ticket_out, true, temperature, seed);
 }
 
 // a request that is still queued leaves the queue (it completes with status SONIC_ERR_INVALID, "cancelled"); one that has reached a handle runs on

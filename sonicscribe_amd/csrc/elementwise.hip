@@ -568,6 +568,15 @@ __global__ void assemble_embeds_kernel(const int* src, const bf16_t* table, cons
 // order - and leaves (id, sum) in the LDS list and the id's bit in a third bitmap, "biased".  The loop reads that map's 4 bits with the others; a set bit scans the
 // list (every lane reads the same word: a broadcast) and adds the sum, once, ahead of guard_score: the bias is HF's first processor.  An unset bit adds nothing
 // (HF adds +0.0 there, which changes no compare and no exponential).  BIAS = false is the kernel as it was, GUARD or not.
+// SAMPLE (option sampling; LP only): temperature sampling by the Gumbel-max identity.  Row b reads GreedyArgs.samp[3b ..]: the bits of its
+// temperature t, its seed's low and high word.  t == 0: no division, no noise - the row's token and out_lp are the bits of the LP kernel.  t > 0: the compare runs
+// on y_i = fdiv_rn(s_i, t) + g_i, s the fully processed score (bias, penalty, bans: HF's order, then TemperatureLogitsWarper), g_i = -ln(-ln(u_i)) Gumbel noise
+// from Philox4x32-10 with key = the seed, counter = (i >> 2, n_new[b], 0, 0), word i & 3: one call per f32x4 group; u = ((word >> 9) + 0.5) * 2^-23 lies
+// strictly inside (0, 1).  The first maximum of y is an exact draw from softmax(s / t); it depends on (scores, t, seed, step) alone - not on batch, row or
+// slot.  The log-probability sum still runs over s, against its own running maximum (`rmax`; without SAMPLE that maximum is `best`), and out_lp is
+// log_softmax(s)[tok] at temperature 1 - openai-whisper's convention, the one its fallback thresholds are calibrated on; the emitted token's s is recomputed
+// from the slabs as the forced id's is.  Teacher forcing wins over sampling; step_logits stay raw.  The two logs are logf - v_log_f32 (1 ulp) times ln 2 in extended precision, a relative error
+// of at most 1.5 * 2^-23 each: |g - exact| <= (1 + 16.64) * 1.5 * 2^-23 < 3.2e-6.
 extern __shared__ unsigned g_bits[];
 __device__ __forceinline__ float guard_score(float r, unsigned seen, unsigned banned, float p) {
     if (seen & 1u) r = r < 0.f ? r * p : __fdiv_rn(r, p);
@@ -582,20 +591,47 @@ __device__ __forceinline__ float bias_of(const int* ids, const float* sums, int 
     return b;
 }
 __device__ __forceinline__ float lp_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-template <typename T, bool LP, bool GUARD = false, bool BIAS = false>
+// Philox4x32-10 (Salmon et al., SC'11): ten rounds, the key bumped between them
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned* out) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0, h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// 23 bits, centred: every value is exact in fp32 and inside (0, 1).  logf is the library's: relatively accurate also at u next to 1, where -ln(u) is tiny (the
+// hardware logarithm's 1 ulp is of ITS result): no 1 - u form needed
+__device__ __forceinline__ float gumbel_of(unsigned word) {
+    const float u = ((float)(word >> 9) + 0.5f) * 1.1920928955078125e-7f;
+    return -logf(-logf(u));
+}
+#define LPB (SAMPLE ? rmax : best)      // what the LP sum is taken against: the running maximum of s
+template <typename T, bool LP, bool GUARD = false, bool BIAS = false, bool SAMPLE = false>
 __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
     static_assert(GUARD || !BIAS, "the request bias lives in the guard instantiations (it needs their history)");
+    static_assert(LP || !SAMPLE, "sampling lives in the log-probability instantiations (the fallback ladder reads them)");
     typedef typename ET<T>::v8 V8;
     __shared__ float sv[16];
     __shared__ int si[17];
     __shared__ int s_tok;
-    __shared__ float ss_lp[LP ? 16 : 1];
+    __shared__ float ss_lp[LP ? (SAMPLE ? 32 : 16) : 1];
+    [[maybe_unused]] float* const ss_m = ss_lp + (SAMPLE ? 16 : 0);      // SAMPLE: the waves' maxima of the unperturbed scores (sv holds those of y)
     float lp_m = -INFINITY, lp_s = 0.f;      // LP: the thread's sum is lp_s * exp(lp_m); a thread that saw nothing holds (-inf, 0)
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const float* lg = a.logits + (long)b * a.V;
     const long ks_stride = (long)a.mpad * a.V;
     float* dump = a.logits_dump ? a.logits_dump + (long)a.step_counter[b] * a.dump_stride_step + (long)b * a.V : nullptr;
     float best = -INFINITY; int bi = 0x7fffffff;
+    // SAMPLE: the row's temperature, seed and step (block-uniform); rmax = the running maximum of s, which `best` (now over y) no longer is
+    [[maybe_unused]] float temp = 0.f, rmax = -INFINITY; [[maybe_unused]] unsigned k0 = 0u, k1 = 0u, step_n = 0u; [[maybe_unused]] bool noisy = false;
+    [[maybe_unused]] float* noise = nullptr;
+    if constexpr (SAMPLE) {
+        temp = __uint_as_float(a.samp[3 * b]); k0 = a.samp[3 * b + 1]; k1 = a.samp[3 * b + 2]; step_n = (unsigned)a.n_new[b];
+        noisy = temp > 0.f;
+        if (a.noise_out) noise = a.noise_out + (long)b * a.V;
+    }
     // the first layer's norm weight for the tail of this kernel, requested before anything else (cold every step; behind the token's
     // embedding row it was one more dependent round trip)
     f32x4 gw0 = {0.f, 0.f, 0.f, 0.f}, gw1 = {0.f, 0.f, 0.f, 0.f};
@@ -666,13 +702,26 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
             if constexpr (GUARD) { sb = g_seen[i >> 5] >> (i & 31); bb = g_ban[i >> 5] >> (i & 31); }
             [[maybe_unused]] unsigned qb = 0u;               // BIAS: the group's 4 bits of the "biased" map
             if constexpr (BIAS) qb = (g_bia[i >> 5] >> (i & 31)) & 15u;
+            [[maybe_unused]] float gz[4] = {0.f, 0.f, 0.f, 0.f};      // SAMPLE: the group's Gumbel values, one Philox call
+            if constexpr (SAMPLE) if (noisy) {
+                unsigned pw[4];
+                philox4x32_10((unsigned)i >> 2, step_n, 0u, 0u, k0, k1, pw);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { gz[j] = gumbel_of(pw[j]); if (noise) noise[i + j] = gz[j]; }
+            }
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float r = rT<T>(t[j]);              // logits are T in the reference, compared as fp32
                 if (dump) dump[i + j] = r;
                 if constexpr (BIAS) if ((qb >> j) & 1u) r += bias_of(q_id, q_sum, q_n, i + j);      // HF's order: the bias first, the penalty sees the biased score
                 if constexpr (GUARD) r = guard_score(r, sb >> j, bb >> j, a.rep_penalty);
-                if (r > best) { best = r; bi = i + j; }   // strict > keeps the first maximum within a thread
+                if constexpr (SAMPLE) {
+                    const float y = noisy ? __fdiv_rn(r, temp) + gz[j] : r;      // (-inf stays -inf: g is finite)
+                    if (y > best) { best = y; bi = i + j; }
+                    rmax = fmaxf(rmax, r);                                       // (t == 0: rmax == best, bit for bit)
+                } else {
+                    if (r > best) { best = r; bi = i + j; }   // strict > keeps the first maximum within a thread
+                }
                 if constexpr (LP) v[u][j] = r;
             }
         }
@@ -680,12 +729,12 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
             // the trip's values against the maximum so far (`best` covers them): the old sum is rescaled once (exp2(0) = 1 and s * 1 are exact when
             // the maximum did not move), then the terms are added in visiting order.  While nothing finite has been seen (the first trip, or trips
             // of -inf logits only) the sum stays 0: -inf - -inf is not formed, here or in the terms (exp(-inf - finite) = 0 is fine)
-            lp_s = lp_m > -INFINITY ? lp_s * lp_exp(lp_m - best) : 0.f; lp_m = best;
+            lp_s = lp_m > -INFINITY ? lp_s * lp_exp(lp_m - LPB) : 0.f; lp_m = LPB;
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if (i0 + u * 4096 >= a.V) break;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) lp_s += best > -INFINITY ? lp_exp(v[u][j] - best) : 0.f;
+                for (int j = 0; j < 4; ++j) lp_s += LPB > -INFINITY ? lp_exp(v[u][j] - LPB) : 0.f;
             }
         }
     }
@@ -694,10 +743,15 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
         const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
         if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
     }
+    if constexpr (SAMPLE) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) rmax = fmaxf(rmax, __shfl_xor(rmax, o, 64));
+        if (lane == 0) ss_m[wid] = rmax;
+    }
     if constexpr (LP) {
         // every lane now holds the wave's maximum: bring the lane's sum to it (an empty lane is the identity: 0, not 0 * exp(-inf + inf)) and add
         // across the wave; the butterfly gives every lane the same tree, and a + b = b + a bit for bit
-        lp_s = lp_m > -INFINITY ? lp_s * lp_exp(lp_m - best) : 0.f;
+        lp_s = lp_m > -INFINITY ? lp_s * lp_exp(lp_m - LPB) : 0.f;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) lp_s += __shfl_xor(lp_s, o, 64);
         if (lane == 0) ss_lp[wid] = lp_s;
@@ -709,15 +763,17 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
         float lp_sum = 0.f;
         if constexpr (LP) {
             float q[16];                          // the 16 waves at the block's maximum (an empty wave: 0), added as a fixed binary tree
+            const float* wm = SAMPLE ? ss_m : sv; // the waves' maxima of the scores the sum ran over
+            if constexpr (SAMPLE) for (int w = 1; w < 16; ++w) rmax = fmaxf(rmax, ss_m[w]);
 #pragma unroll
-            for (int w = 0; w < 16; ++w) q[w] = sv[w] > -INFINITY ? ss_lp[w] * lp_exp(sv[w] - best) : 0.f;
+            for (int w = 0; w < 16; ++w) q[w] = wm[w] > -INFINITY ? ss_lp[w] * lp_exp(wm[w] - LPB) : 0.f;
 #pragma unroll
             for (int h = 8; h > 0; h >>= 1)
 #pragma unroll
                 for (int w = 0; w < h; ++w) q[w] = q[2 * w] + q[2 * w + 1];
             lp_sum = q[0];
         }
-        if constexpr (GUARD) if (bi == 0x7fffffff) bi = 0;      // every score -inf: the first of equal values
+        if constexpr (GUARD || SAMPLE) if (bi == 0x7fffffff) bi = 0;      // every score -inf: the first of equal values
         int tok = bi;
         const int fin = a.finished[b];
         bool running = false;
@@ -726,8 +782,9 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
             if (a.force_ids) tok = a.force_ids[(long)b * a.force_ld + a.n_new[b]];   // teacher forcing (parity tests): feed this id instead
             a.out_ids[(long)b * a.out_ld + a.n_new[b]] = tok;
             if constexpr (LP) {
-                float lt = best;                  // the emitted token's logit: the maximum, or under teacher forcing the forced id's value, summed
-                if (a.force_ids) {                // from the slabs in the main loop's order (v + w, then ks = 2 ...): the bits of the dumped logit
+                float lt = LPB;                   // the emitted token's logit: the maximum, or under teacher forcing the forced id's value, summed
+                // from the slabs in the main loop's order (v + w, then ks = 2 ...): the bits of the dumped logit.  SAMPLE: a sampled token is rarely the maximum of s
+                if (SAMPLE ? (a.force_ids || noisy) && (unsigned)tok < (unsigned)a.V : a.force_ids != nullptr) {
                     float f = lg[tok];
                     if (a.ksplit > 1) f += lg[ks_stride + tok];
                     for (int ks = 2; ks < a.ksplit; ++ks) f += lg[ks * ks_stride + tok];
@@ -735,7 +792,7 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
                     if constexpr (BIAS) if ((g_bia[tok >> 5] >> (tok & 31)) & 1u) lt += bias_of(q_id, q_sum, q_n, tok);
                     if constexpr (GUARD) lt = guard_score(lt, g_seen[tok >> 5] >> (tok & 31), g_ban[tok >> 5] >> (tok & 31), a.rep_penalty);
                 }
-                a.out_lp[(long)b * a.out_ld + a.n_new[b]] = (float)(((double)lt - (double)best) - log((double)lp_sum));
+                a.out_lp[(long)b * a.out_ld + a.n_new[b]] = (float)(((double)lt - (double)LPB) - log((double)lp_sum));
             }
             if constexpr (GUARD) { const int pos = a.kv_len[b]; if (pos >= 0 && pos < a.hist_ld) a.hist[(long)b * a.hist_ld + pos] = tok; }   // the token's position
             const int nn = a.n_new[b] + 1;
@@ -792,6 +849,7 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
     }
     if (a.qo.q) quant_emit_row(yo, c < nv, c, b, a.qo, sv, si);
 }
+#undef LPB
 
 // ---------------------------------------------------------------- misc
 // In-stream fill of small control words.  hipMemsetAsync of a few bytes was observed not to be reliably ordered against
@@ -895,6 +953,23 @@ void launch_hist_prompt(const int* src, const int* tok_seq, const int* tok_pos, 
 }
 size_t greedy_guard_lds(int V, bool bias) { return (size_t)(bias ? 3 : 2) * ((V + 31) / 32) * 4 + (bias ? (size_t)3 * BIAS_MAX_ENTRIES * 4 : 0); }
 void launch_greedy(const GreedyArgs& a, hipStream_t s) {
+    if (a.samp && a.out_lp) {                                                                                    // option sampling: the SAMPLE instantiations of the three LP families
+        if (a.hist && a.bias_tab) {
+            const size_t lds = greedy_guard_lds(a.V, true);
+            if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, true, true, true, true>), dim3(a.B), dim3(1024), lds, s, a); return; }
+            DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, true, true, true, true>), dim3(a.B), dim3(1024), lds, s, a));
+            return;
+        }
+        if (a.hist) {
+            const size_t lds = greedy_guard_lds(a.V);
+            if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, true, true, false, true>), dim3(a.B), dim3(1024), lds, s, a); return; }
+            DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, true, true, false, true>), dim3(a.B), dim3(1024), lds, s, a));
+            return;
+        }
+        if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, true, false, false, true>), dim3(a.B), dim3(1024), 0, s, a); return; }
+        DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, true, false, false, true>), dim3(a.B), dim3(1024), 0, s, a));
+        return;
+    }
     if (a.hist && a.bias_tab) {                                                                                  // request bias: the BIAS instantiations (a third bitmap and the matched list)
         const size_t lds = greedy_guard_lds(a.V, true);
         if (a.out_lp) {

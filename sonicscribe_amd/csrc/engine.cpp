@@ -491,6 +491,71 @@ int bias_upload(sonic_engine* e, int R) {
     e->bias_ev_busy = true; e->bias_take = false;
     return SONIC_OK;
 }
+// ---- option sampling: temperature sampling in the greedy kernel by the Gumbel-max identity, one (temperature, seed) per request - what Whisper's
+// decode_with_fallback retries with.  The caller holds the lock and has asked gen_busy.
+int samp_enable(sonic_engine* e, int on) {
+    if (on && !(e->opt_token_logprobs && e->out_lp)) return fail(e, SONIC_ERR_INVALID, "sampling: option token_logprobs must be on first (the sampling kernels are log-probability kernels; sonic_set_option(e, \"token_logprobs\", 1))");
+    HIPC(e, hipSetDevice(e->device));
+    HIPC(e, stream_sync(e));
+    if (on) {
+        if (!e->samp) TRY(dalloc(e, &e->samp, (size_t)SAMP_WORDS));                                   // (zero-filled: every row starts greedy)
+        if (!e->samp_h && hipHostMalloc((void**)&e->samp_h, (size_t)SAMP_WORDS * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(e, SONIC_ERR_OOM, "sampling: pinned host memory exhausted"); }
+        if (!e->samp_ev) HIPC(e, hipEventCreateWithFlags(&e->samp_ev, hipEventDisableTiming));
+        HIPC(e, stream_sync(e));
+    }
+    e->opt_sampling = on ? 1 : 0; e->samp_pending = -1; e->samp_take = false;
+    drop_graphs(e);                                      // the greedy kernel and its arguments are part of every captured chunk
+    return SONIC_OK;
+}
+int samp_check(sonic_engine* e, const char* who, const float* temperature, int n) {
+    for (int r = 0; r < n; ++r) {
+        const float t = temperature[r];
+        if (!(t == 0.f || (t >= 1e-3f && t <= 100.f)))     // (NaN fails every compare)
+            return fail(e, SONIC_ERR_INVALID, "%s: temperature %g of request %d is invalid (0 = greedy, or 1e-3 .. 100; nothing is clamped)", who, (double)t, r);
+    }
+    return SONIC_OK;
+}
+// The (temperature, seed) of the R requests of the next prefill on this handle (the entry points of sonic_set_request_bias), which consumes them: a later batch
+// starts greedy.
+extern "C" int sonic_set_request_sampling(sonic_engine* e, const float* temperature, const uint64_t* seed, int R) {
+    if (!e) return SONIC_ERR_INVALID;
+    { std::lock_guard<std::mutex> lk(e->a_mu); if (e->a_pending || e->a_running) return fail(nullptr, SONIC_ERR_INVALID, "sonic_set_request_sampling: an asynchronous run of this handle is in flight"); }
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipGetLastError();
+    if (!e->opt_sampling || !e->samp)
+        return fail(e, SONIC_ERR_INVALID, "sonic_set_request_sampling: option sampling is off on this handle (sonic_set_option(e, \"sampling\", 1) on the owner before its slots are created)");
+    e->samp_pending = -1;
+    if (R < 1 || R > e->Bm || R > 64 || !temperature || !seed) return fail(e, SONIC_ERR_INVALID, "sonic_set_request_sampling: %d requests (1 .. %d), values for each", R, e->Bm);
+    TRY(samp_check(e, "sonic_set_request_sampling", temperature, R));
+    HIPC(e, hipSetDevice(e->device));
+    if (e->samp_ev_busy) { HIPC(e, hipEventSynchronize(e->samp_ev)); e->samp_ev_busy = false; }      // the previous batch's copy out of samp_h
+    for (int i = 0; i < SAMP_WORDS; ++i) e->samp_h[i] = 0u;
+    for (int r = 0; r < R; ++r) {
+        memcpy(&e->samp_h[3 * r], &temperature[r], 4);
+        e->samp_h[3 * r + 1] = (unsigned)(seed[r] & 0xffffffffull); e->samp_h[3 * r + 2] = (unsigned)(seed[r] >> 32);
+    }
+    e->samp_pending = R;
+    return SONIC_OK;
+}
+int samp_upload(sonic_engine* e, int R) {
+    if (!e->opt_sampling) return SONIC_OK;
+    if (!e->samp_take && e->opt_samp_fill_milli > 0) {
+        // option sampling_fill_milli = m (drivers that only pass integers: bench.py --opt; tools/ab_sampling.sh): request r of a batch without values gets temperature
+        // m / 1000 and seed r.  A batch is then the same draw every time it runs, on whichever handle: a benchmark can still check its tokens
+        if (e->samp_ev_busy) { HIPC(e, hipEventSynchronize(e->samp_ev)); e->samp_ev_busy = false; }
+        const float t = (float)((double)e->opt_samp_fill_milli / 1000.0);
+        for (int i = 0; i < SAMP_WORDS; ++i) e->samp_h[i] = 0u;
+        for (int r = 0; r < R && r < 64; ++r) { memcpy(&e->samp_h[3 * r], &t, 4); e->samp_h[3 * r + 1] = (unsigned)r; }
+        e->samp_take = true;
+    }
+    if (!e->samp_take) { launch_fill_i32((int*)e->samp, 0, SAMP_WORDS, e->st); return SONIC_OK; }     // a batch without values: every row greedy
+    HIPC(e, hipMemcpyAsync(e->samp, e->samp_h, (size_t)SAMP_WORDS * 4, hipMemcpyHostToDevice, e->st));
+    HIPC(e, hipEventRecord(e->samp_ev, e->st));
+    e->samp_ev_busy = true; e->samp_take = false;
+    return SONIC_OK;
+}
+extern "C" int engine_sampling_on(sonic_engine* e) { return e && e->opt_sampling && e->samp ? 1 : 0; }
+extern "C" int engine_sampling_validate(float temperature) { return samp_check(nullptr, "sonic_dispatch_submit_sampled", &temperature, 1); }
 // dispatch.cpp (same library, not exported): is the option on for a handle; is one request's table well-formed for it (the message lands on the handle)
 extern "C" int engine_request_bias_on(sonic_engine* e) { return e && e->opt_request_bias && e->bias_tab ? 1 : 0; }
 // (the handle is only read for its vocabulary: the message goes to the calling thread's sonic_last_error(NULL), no lock is needed)
@@ -586,6 +651,8 @@ extern "C" int sonic_slot_create(sonic_engine* parent, sonic_engine** out) {
     if (root->gen_on && (s = gen_apply(e, root->gen_penalty, root->gen_ngram, root->gen_suppress.data(), (int)root->gen_suppress.size())) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }
     if (root->opt_request_bias && (s = bias_enable(e, 1)) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }
     e->opt_bias_fill = root->opt_bias_fill;
+    if (root->opt_sampling && (s = samp_enable(e, 1)) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }
+    e->opt_samp_fill_milli = root->opt_samp_fill_milli;
     e->weight_bytes = 0; e->finalized = true; e->owner = root;
     root->slots.push_back(e);
     *out = e;
@@ -643,6 +710,8 @@ extern "C" void sonic_destroy(sonic_engine* e) {
     if (e->svc_h) (void)hipHostFree(e->svc_h);
     if (e->bias_h) (void)hipHostFree(e->bias_h);
     if (e->bias_ev) (void)hipEventDestroy(e->bias_ev);
+    if (e->samp_h) (void)hipHostFree(e->samp_h);
+    if (e->samp_ev) (void)hipEventDestroy(e->samp_ev);
     if (e->st_io) { (void)hipStreamSynchronize(e->st_io); (void)hipStreamDestroy(e->st_io); }
     if (e->xfer_ev) (void)hipEventDestroy(e->xfer_ev);
     if (e->splice_ev) (void)hipEventDestroy(e->splice_ev);

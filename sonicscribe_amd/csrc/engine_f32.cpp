@@ -179,6 +179,7 @@ int f32_run_prefill(sonic_engine* e, int R, const HostPlan& hp) {
     launch_fill_i32(e->n_new, 0, 64, e->st); launch_fill_i32(e->finished, 0, 64, e->st); launch_fill_i32(e->step_ctr, 0, 64, e->st);
     if (hist_on(e)) launch_hist_prompt(e->src, e->tok_seq, e->tok_pos_pf, M, d.audio_token_id, e->hist, e->max_ctx, e->st);
     TRY(bias_upload(e, R));
+    TRY(samp_upload(e, R));
     launch_f32_assemble(e->src, f.embed, f.pe, f.dx, M, D, e->st);
     e->last_ntok = M;
     if (e->taps_on) {

@@ -441,6 +441,7 @@ extern "C" int sonic_set_option(sonic_engine* e, const char* key, int value) {
     for (const OptRow& r : OPTIONS) {
         if (strcmp(key, r.key)) continue;
         const int v = r.clamp ? r.clamp(value) : value;
+        if (r.field == &sonic_engine::opt_token_logprobs && !v && e->opt_sampling) return fail(e, SONIC_ERR_INVALID, "token_logprobs cannot be switched off while option sampling is on (its kernels are log-probability kernels)");
         if (r.field) e->*r.field = v; else e->opts.*r.lfield = v;
         if (r.drop_graphs) drop_graphs(e);
         if (r.field == &sonic_engine::opt_token_logprobs && v) TRY(lp_alloc(e));      // first use: 64 x out_cap fp32
@@ -456,6 +457,18 @@ extern "C" int sonic_set_option(sonic_engine* e, const char* key, int value) {
         else return fail(e, SONIC_ERR_INVALID, "unknown option %s", key);
         TRY(gen_busy(e, key));
         return gen_apply(e, p, n, sup.data(), (int)sup.size());
+    }
+    // temperature sampling (sonic_set_request_sampling): on the owner before its slots are created (they copy it), after token_logprobs (refused by
+    // name otherwise); allocates the rows' (temperature, seed) words.  Refused while the handle has work in hand, by sonic_set_generation's rule
+    if (!strcmp(key, "sampling")) {
+        TRY(gen_busy(e, key));
+        return samp_enable(e, value ? 1 : 0);
+    }
+    if (!strcmp(key, "sampling_fill_milli")) {    // measurement aid (samp_upload, engine.cpp): 0 (off) or 1 .. 100000 thousandths, for every request without values
+        if (value != 0 && (value < 1 || value > 100000)) return fail(e, SONIC_ERR_INVALID, "sampling_fill_milli: %d is outside 0, 1 .. 100000", value);
+        TRY(gen_busy(e, key));
+        e->opt_samp_fill_milli = value;
+        return SONIC_OK;
     }
     // per-request sequence bias (sonic_set_request_bias): on the owner before its slots are created (they copy it); allocates the rows' history, if the
     // guards have not, and their tables.  Refused while the handle has work in hand, by sonic_set_generation's rule
@@ -562,18 +575,27 @@ extern "C" int sonic_test_linear_int8(sonic_engine* e, const float* X, const flo
 // sonic_test_greedy_bias: the launch through greedy_kernel<T, LP, true, true>: the guard test plus row b's table (sonic_set_request_bias's packed form, B requests).
 struct GuardTest { const int32_t* hist; int hist_ld; const int32_t* hist_len; float penalty; int ngram; const int32_t* suppress; int n_suppress;
                    bool bias = false; const int32_t* seq_ids = nullptr; const int32_t* seq_off = nullptr; const float* seq_bias = nullptr; const int32_t* req_off = nullptr; };
+// sonic_test_greedy_sample: the launch through greedy_kernel<T, true, GUARD, BIAS, true> in the handle's own type (bf16, fp16, the fp32 kind's float): row b draws at
+// temperature[b] with seed[b] as its step[b]-th token (n_new = step: ids, log-probabilities and forced ids sit at that column); noise_out[B][V] = the Gumbel values used.
+struct SampTest { const float* temperature; const uint64_t* seed; const int32_t* step; float* noise_out; };
 static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const int32_t* force_ids, int32_t* tok_out, float* logits_out, float* lp_out,
-                       const GuardTest* gt = nullptr) {
+                       const GuardTest* gt = nullptr, const SampTest* sp = nullptr) {
     if (ksplit < 1 || ksplit > 8 || B < 1 || B > 64 || mpad < B || V < 4 || V % 4) return fail(e, SONIC_ERR_INVALID, "bad greedy test shape");
     if (force_ids) for (int b = 0; b < B; ++b) if (force_ids[b] < 0 || force_ids[b] >= V) return fail(e, SONIC_ERR_INVALID, "forced id %d out of vocabulary", force_ids[b]);
+    int old = 1;                                                                  // columns of ids / lp / forced ids: one, or up to the largest step of a sampling test
+    if (sp) {
+        if (!sp->temperature || !sp->seed || !sp->step || !lp_out) return fail(e, SONIC_ERR_INVALID, "bad greedy sample test arguments");
+        TRY(samp_check(e, "sonic_test_greedy_sample", sp->temperature, B));
+        for (int b = 0; b < B; ++b) { if (sp->step[b] < 0 || sp->step[b] > 65535) return fail(e, SONIC_ERR_INVALID, "step %d outside 0 .. 65535", sp->step[b]); old = std::max(old, sp->step[b] + 1); }
+    }
     TmpBuf tb(e->st);
     const size_t n = (size_t)ksplit * mpad * V;
     float* dl = up_f32(e, tb, slabs, n);
-    bf16_t* table = tb.get<bf16_t>((size_t)V * 8); bf16_t* x = tb.get<bf16_t>((size_t)64 * 8);
-    int* st = tb.get<int>(64 * 8 + 4); int* ids = tb.get<int>(64);
+    bf16_t* table = tb.get<bf16_t>((size_t)V * 8 * (sp ? 2 : 1)); bf16_t* x = tb.get<bf16_t>((size_t)64 * 8 * (sp ? 2 : 1));      // (sp: rows of 8 floats in the fp32 kind)
+    int* st = tb.get<int>(64 * 8 + 4); int* ids = tb.get<int>((size_t)64 * old);
     float* dump = logits_out ? tb.get<float>((size_t)B * V) : nullptr;
-    float* lp = lp_out ? tb.get<float>(64) : nullptr;
-    int* fd = force_ids ? tb.get<int>(64) : nullptr;
+    float* lp = lp_out ? tb.get<float>((size_t)64 * old) : nullptr;
+    int* fd = force_ids ? tb.get<int>((size_t)64 * old) : nullptr;
     if (!dl || !table || !x || !st || !ids || (logits_out && !dump) || (lp_out && !lp) || (force_ids && !fd)) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     std::vector<int> h(64 * 8 + 4, 0);
     for (int b = 0; b < 64; ++b) { h[64 * 2 + b] = 1; h[64 * 4 + b] = 4; }       // kv_len = 1, max_new = 4
@@ -614,22 +636,46 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
         if (!gbias) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
         HIPC(e, h2d(e, gbias, tab.data(), tab.size() * 4));
     }
+    unsigned* gsamp = nullptr; float* gnoise = nullptr;
+    if (sp) {
+        std::vector<unsigned> w((size_t)SAMP_WORDS, 0u);
+        for (int b = 0; b < B; ++b) {
+            memcpy(&w[3 * b], &sp->temperature[b], 4); w[3 * b + 1] = (unsigned)(sp->seed[b] & 0xffffffffull); w[3 * b + 2] = (unsigned)(sp->seed[b] >> 32);
+            h[b] = sp->step[b]; h[64 * 4 + b] = sp->step[b] + 4;                 // n_new = step, max_new beyond it
+        }
+        gsamp = tb.get<unsigned>(w.size());
+        if (sp->noise_out) gnoise = tb.get<float>((size_t)B * V);
+        if (!gsamp || (sp->noise_out && !gnoise)) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+        HIPC(e, h2d(e, gsamp, w.data(), w.size() * 4));
+    }
     HIPC(e, h2d(e, st, h.data(), h.size() * 4));
-    if (fd) HIPC(e, h2d(e, fd, force_ids, (size_t)B * 4));
+    if (fd && !sp) HIPC(e, h2d(e, fd, force_ids, (size_t)B * 4));
+    if (fd && sp) {
+        std::vector<int> fw((size_t)64 * old, 0);
+        for (int b = 0; b < B; ++b) fw[(size_t)b * old + sp->step[b]] = force_ids[b];
+        HIPC(e, h2d(e, fd, fw.data(), fw.size() * 4));
+    }
     GreedyArgs g{};
     g.logits = dl; g.ksplit = ksplit; g.mpad = mpad; g.V = V; g.B = B; g.table = table; g.x = x; g.d = 8;
-    g.out_ids = ids; g.out_ld = 1; g.n_new = st; g.finished = st + 64; g.kv_len = st + 128; g.tok_pos = st + 192; g.max_new = st + 256;
+    g.out_ids = ids; g.out_ld = old; g.n_new = st; g.finished = st + 64; g.kv_len = st + 128; g.tok_pos = st + 192; g.max_new = st + 256;
     g.n_active = st + 512; g.n_eos = 0; g.pad_id = 0; g.logits_dump = dump; g.dump_stride_step = (long)B * V; g.step_counter = dump ? st + 320 : nullptr;
-    g.out_lp = lp; g.force_ids = fd; g.force_ld = 1;
+    g.out_lp = lp; g.force_ids = fd; g.force_ld = old;
+    if (sp) { g.samp = gsamp; g.noise_out = gnoise; g.dt = e->f32 ? DT_F32 : e->dt; }
     if (gt) { g.hist = ghist; g.hist_ld = gld; g.rep_penalty = gt->penalty; g.ngram = gt->ngram; g.suppress = gsup; g.n_suppress = gt->n_suppress; g.bias_tab = gbias; }
     launch_greedy(g, e->st);
     HIPC(e, stream_sync(e));
     HIPC(e, hipGetLastError());
-    std::vector<int> out(64);
-    HIPC(e, d2h(e, out.data(), ids, 64 * 4));
-    for (int b = 0; b < B; ++b) tok_out[b] = out[b];
+    std::vector<int> out((size_t)64 * old);
+    HIPC(e, d2h(e, out.data(), ids, out.size() * 4));
+    for (int b = 0; b < B; ++b) tok_out[b] = out[(size_t)b * old + (sp ? sp->step[b] : 0)];
     if (logits_out) HIPC(e, d2h(e, logits_out, dump, (size_t)B * V * 4));
-    if (lp_out) HIPC(e, d2h(e, lp_out, lp, (size_t)B * 4));
+    if (lp_out && !sp) HIPC(e, d2h(e, lp_out, lp, (size_t)B * 4));
+    if (sp) {
+        std::vector<float> lw((size_t)64 * old);
+        HIPC(e, d2h(e, lw.data(), lp, lw.size() * 4));
+        for (int b = 0; b < B; ++b) lp_out[b] = lw[(size_t)b * old + sp->step[b]];
+        if (sp->noise_out) HIPC(e, d2h(e, sp->noise_out, gnoise, (size_t)B * V * 4));
+    }
     return SONIC_OK;
 }
 extern "C" int sonic_test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, int32_t* tok_out, float* logits_out) {
@@ -662,6 +708,22 @@ extern "C" int sonic_test_greedy_bias(sonic_engine* e, const float* slabs, int k
     GuardTest gt{hist, hist_ld, hist_len, repetition_penalty, no_repeat_ngram_size, suppress, n_suppress};
     gt.bias = true; gt.seq_ids = seq_ids; gt.seq_off = seq_off; gt.seq_bias = bias; gt.req_off = req_off;
     return test_greedy(e, slabs, ksplit, mpad, V, B, force_ids, tok_out, logits_out, lp_out, &gt);
+}
+
+// hist_len = NULL: greedy_kernel<T, true, false, false, true>; hist_len without req_off: <T, true, true, false, true>; both: <T, true, true, true, true>
+extern "C" int sonic_test_greedy_sample(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const int32_t* hist, int hist_ld, const int32_t* hist_len,
+                                        float repetition_penalty, int no_repeat_ngram_size, const int32_t* suppress, int n_suppress, const int32_t* force_ids,
+                                        const int32_t* seq_ids, const int32_t* seq_off, const float* bias, const int32_t* req_off,
+                                        const float* temperature, const uint64_t* seed, const int32_t* step,
+                                        int32_t* tok_out, float* logits_out, float* lp_out, float* noise_out) {
+    if (!e || !slabs || !tok_out || !lp_out || !temperature || !seed || !step) return SONIC_ERR_INVALID;
+    ENTER(e);
+    if (req_off && !hist_len) return fail(e, SONIC_ERR_INVALID, "sonic_test_greedy_sample: tables need the histories");
+    const SampTest sp{temperature, seed, step, noise_out};
+    if (!hist_len) return test_greedy(e, slabs, ksplit, mpad, V, B, force_ids, tok_out, logits_out, lp_out, nullptr, &sp);
+    GuardTest gt{hist, hist_ld, hist_len, repetition_penalty, no_repeat_ngram_size, suppress, n_suppress};
+    if (req_off) { gt.bias = true; gt.seq_ids = seq_ids; gt.seq_off = seq_off; gt.seq_bias = bias; gt.req_off = req_off; }
+    return test_greedy(e, slabs, ksplit, mpad, V, B, force_ids, tok_out, logits_out, lp_out, &gt, &sp);
 }
 
 extern "C" int sonic_test_skinny_gu(sonic_engine* e, const float* X, const float* Wgu_interleaved, float* act, int M, int N, int K) {

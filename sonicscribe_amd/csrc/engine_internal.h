@@ -186,6 +186,12 @@ struct sonic_engine {
     int opt_bias_fill = 0;         // measurement aid (option request_bias_fill, tools/ab_request_bias.sh): a prefill that was given no tables writes this many neutral entries per request
     int* bias_tab = nullptr; int* bias_h = nullptr; hipEvent_t bias_ev = nullptr; bool bias_ev_busy = false;
     std::atomic<int> bias_pending{-1}; bool bias_take = false;
+    // option sampling (sonic_set_request_sampling; greedy_kernel<T, true, ., ., true>): every row's temperature bits and seed words, samp[SAMP_WORDS]
+    // on the device (kernels.h), written by the prefill from the pinned samp_h, copied by the splice; allocated by the option.  samp_pending / samp_take: as bias_*
+    int opt_sampling = 0;
+    int opt_samp_fill_milli = 0;   // measurement aid (option sampling_fill_milli, tools/ab_sampling.sh): a prefill that was given no values decodes request r at this temperature (in thousandths) with seed r
+    unsigned* samp = nullptr; unsigned* samp_h = nullptr; hipEvent_t samp_ev = nullptr; bool samp_ev_busy = false;
+    std::atomic<int> samp_pending{-1}; bool samp_take = false;
     uint64_t spliced = 0;          // rows of the last prefill that sonic_splice_rows handed to a continuous loop (bit r = request r); cleared by every prefill (gen_busy)
     long long* kt = nullptr; int kt_layer = -1;     // diagnostics ("ktrace" option): in-kernel timestamps of one decoder layer's kernels
     int* ring_peak = nullptr;                        // [Bm] per-request max |s| of a ring-staged batch (ingest.hip)
@@ -230,7 +236,8 @@ struct HostPlan {
 // surface at this call's closing hipGetLastError check)
 #define ENTER(e) std::lock_guard<std::mutex> lk((e)->mu); (void)hipGetLastError(); HIPC(e, hipSetDevice((e)->device)); g_opts = (e)->opts
 // ENTER for the entry points that consume the tables of sonic_set_request_bias (sonic_prefill*, sonic_run_staged, sonic_transcribe_*): whatever way the call
-// leaves - a staging error ahead of the prefill included - the pending tables are dropped, so they can never reach a later batch
+// leaves - a staging error ahead of the prefill included - the pending tables are dropped, so they can never reach a later batch (the values of
+// sonic_set_request_sampling likewise)
 struct BiasConsume { sonic_engine* e; ~BiasConsume(); };
 #define ENTER_CONSUME(e) std::lock_guard<std::mutex> lk((e)->mu); BiasConsume bias_consume_{e}; (void)hipGetLastError(); HIPC(e, hipSetDevice((e)->device)); g_opts = (e)->opts
 
@@ -304,6 +311,9 @@ int bias_enable(sonic_engine* e, int on);           // option request_bias behin
 // SONIC_ERR_INVALID (message on e, naming `who`) for more than BIAS_MAX_ENTRIES entries, a length outside 1 .. BIAS_MAX_LEN, an id outside [0, V), a NaN or +inf bias
 int bias_pack(sonic_engine* e, const char* who, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n, int V, int* row, int* count);
 int bias_upload(sonic_engine* e, int R);            // the prefill's part: the pending tables (or zero counts) into bias_tab, on the stream (engine.cpp)
-inline BiasConsume::~BiasConsume() { e->bias_pending = -1; }
+inline BiasConsume::~BiasConsume() { e->bias_pending = -1; e->samp_pending = -1; }
+int samp_enable(sonic_engine* e, int on);           // option sampling behind the lock and the busy check: the rows' words and their staging buffer on first use (engine.cpp)
+int samp_check(sonic_engine* e, const char* who, const float* temperature, int n);   // SONIC_ERR_INVALID (message on e, or the calling thread's for e = NULL) unless every value is 0 or in [1e-3, 100]
+int samp_upload(sonic_engine* e, int R);            // the prefill's part: the pending values (or zeros: greedy) into samp, on the stream (engine.cpp)
 static inline bool hist_on(const sonic_engine* e) { return e->gen_on || e->opt_request_bias; }   // the rows' input_ids are kept: a guard or the request bias reads them
 int lp_check(sonic_engine* e, const char* who);     // SONIC_ERR_INVALID naming the option when token_logprobs is off on this handle

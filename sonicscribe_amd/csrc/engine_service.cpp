@@ -15,6 +15,7 @@ struct SpliceArgs {
     const int *kv_len_s, *tok_pos_s, *n_new_s, *fin_s, *max_new_s, *out_s; int out_ld;
     const int* hist_s; int* hist_d;                      // generation guards on the destination: the row's history (prompt + first token) travels with it, [.][ctx]
     const int* bias_s; int* bias_d;                      // option request_bias on both: the row's table travels with it (count first, then only the used entries)
+    const unsigned* samp_s; unsigned* samp_d;            // option sampling on both: the row's temperature and seed travel with it (its step index is n_new)
     const float* lp_s; float* lp_d;                      // option token_logprobs on the destination: the first token's log-probability travels with its id
     int *kv_len_d, *tok_pos_d, *n_new_d, *fin_d, *max_new_d, *out_d, *n_active_d;
     const bf16_t *sx_s, *shn_s; bf16_t *sx_d, *shn_d; int D;
@@ -51,6 +52,7 @@ __global__ __launch_bounds__(256) void splice_state_kernel(SpliceArgs a) {
         if (t == 0) a.bias_d[d] = cnt;
         for (int j = t; j < cnt * BIAS_ENTRY_WORDS; j += 256) a.bias_d[64 + (long)d * BIAS_ROW_WORDS + j] = a.bias_s[64 + (long)s * BIAS_ROW_WORDS + j];
     }
+    if (a.samp_d && t < 3) a.samp_d[3 * d + t] = a.samp_s[3 * s + t];
     if (t == 0) {
         const int fin = a.fin_s[s];
         a.out_d[(long)d * a.out_ld] = a.out_s[(long)s * a.out_ld];            // the first token came out of the prefill
@@ -129,6 +131,8 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
         return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in their generation guards (sonic_set_generation): set them on the owner before its slots are created");
     if (d->opt_request_bias != p->opt_request_bias || (d->opt_request_bias && !(p->bias_tab && d->bias_tab && p->hist && d->hist)))
         return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in option request_bias: set it on the owner before its slots are created");
+    if (d->opt_sampling != p->opt_sampling || (d->opt_sampling && !(p->samp && d->samp)))
+        return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in option sampling: set it on the owner before its slots are created");
     if (n < 1 || n > 64 || p->greedy_calls < 1 || n > p->R) return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: %d rows, the source has %d prefilled requests", n, p->greedy_calls < 1 ? 0 : p->R);
     SpliceArgs a{};
     for (int i = 0; i < n; ++i) {
@@ -144,6 +148,7 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
     if (d->opt_token_logprobs && d->out_lp) { a.lp_s = p->out_lp; a.lp_d = d->out_lp; }
     if (hist_on(d)) { a.hist_s = p->hist; a.hist_d = d->hist; }
     if (d->opt_request_bias) { a.bias_s = p->bias_tab; a.bias_d = d->bias_tab; }
+    if (d->opt_sampling) { a.samp_s = p->samp; a.samp_d = d->samp; }
     if (d->i8) { a.hq_s = p->hn_q; a.hq_d = d->hn_q; a.sca_s = p->sca_hn; a.sca_d = d->sca_hn; a.oc_s = p->oc_hn; a.oc_d = d->oc_hn; a.ol_s = p->ol_hn; a.ol_d = d->ol_hn; a.ov_s = p->ov_hn; a.ov_d = d->ov_hn; }
     HIPC(d, hipEventRecord(p->xfer_ev, p->st));
     HIPC(d, hipStreamWaitEvent(d->st, p->xfer_ev, 0));
@@ -307,7 +312,7 @@ extern "C" int sonic_run_staged_async(sonic_engine* e, const int32_t* req_win, i
                                       const int32_t* max_new, int want_step_logits) {
     if (!e) return SONIC_ERR_INVALID;
     // (a refusal below drops the tables of sonic_set_request_bias: this call was their consumer; an accepted run consumes them in its prefill)
-    struct Drop { sonic_engine* e; bool keep = false; ~Drop() { if (!keep) e->bias_pending = -1; } } drop{e};
+    struct Drop { sonic_engine* e; bool keep = false; ~Drop() { if (!keep) { e->bias_pending = -1; e->samp_pending = -1; } } } drop{e};
     if (!prompt_ids || !prompt_off || !max_new || R < 1 || R > 64) return SONIC_ERR_INVALID;
     std::lock_guard<std::mutex> lk(e->a_mu);
     if (e->a_stop) return SONIC_ERR_INVALID;

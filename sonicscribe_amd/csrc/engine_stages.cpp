@@ -219,6 +219,7 @@ GreedyArgs greedy_args(sonic_engine* e, int R, bool dump) {
     // (request bias without guards: the guard values are the neutral ones - r * 1.0 and __fdiv_rn(r, 1.0) are exact, n = 0, no suppress list)
     if (hist_on(e)) { g.hist = e->hist; g.hist_ld = e->max_ctx; g.rep_penalty = e->gen_penalty; g.ngram = e->gen_ngram; g.suppress = e->gen_suppress_d; g.n_suppress = (int)e->gen_suppress.size(); }
     if (e->opt_request_bias) g.bias_tab = e->bias_tab;
+    if (e->opt_sampling && g.out_lp) g.samp = e->samp;      // (the option is refused without token_logprobs, and token_logprobs cannot leave while it is on)
     if (e->i8) g.qo = QuantOut{e->hn_q, d.dec_d, e->sca_hn, e->oc_hn, e->ol_hn, d.dec_d, e->ov_hn};     // layer 0's q/k/v input, quantised
     return g;
 }
@@ -458,6 +459,7 @@ static int run_prefill(sonic_engine* e, int R, const HostPlan& hp) {
     launch_fill_i32(e->step_ctr, 0, 64, e->st);
     if (hist_on(e)) launch_hist_prompt(e->src, e->tok_seq, e->tok_pos_pf, M, d.audio_token_id, e->hist, e->max_ctx, e->st);    // the rows' input_ids for the guards / the request bias
     TRY(bias_upload(e, R));                                                                                                     // every request's table, or a zero count, into its row
+    TRY(samp_upload(e, R));                                                                                                     // every request's (temperature, seed), or zeros: greedy
     launch_assemble_embeds(e->src, e->embed, e->pe, e->dx, M, D, e->st);
     e->last_ntok = M;
     if (e->taps_on) {
@@ -513,10 +515,13 @@ int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int
     }
     const int bias_R = e->bias_pending.exchange(-1);        // sonic_set_request_bias: this batch consumes the tables whatever becomes of it (the entry points that
     e->bias_take = false;                                   // lead here drop them on every other exit too: ENTER_CONSUME)
+    const int samp_R = e->samp_pending.exchange(-1);        // sonic_set_request_sampling: the same rule
+    e->samp_take = false;
     if (bias_R >= 0 && bias_R != R) return fail(e, SONIC_ERR_INVALID, "sonic_set_request_bias gave tables for %d requests, the batch has %d", bias_R, R);
+    if (samp_R >= 0 && samp_R != R) return fail(e, SONIC_ERR_INVALID, "sonic_set_request_sampling gave values for %d requests, the batch has %d", samp_R, R);
     HostPlan hp;
     TRY(plan_requests(e, req_win, R, prompt_ids, prompt_off, max_new, hp));
-    e->bias_take = bias_R >= 0;
+    e->bias_take = bias_R >= 0; e->samp_take = samp_R >= 0;
     {   // staging buffer of this run: the one used two runs ago; its copies are almost always long done (a blocking wait otherwise)
         const int i = e->plan_idx ^ 1;
         if (e->plan_busy[i]) { HIPC(e, hipEventSynchronize(e->plan_ev[i])); e->plan_busy[i] = false; }
@@ -580,7 +585,7 @@ int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int
 // svc: the chunk belongs to a continuous decode loop (sonic_service_*), i.e. it runs beside a prefill slot and other loops by design - decode_step then
 // picks the forms that cost the fewest CU-microseconds rather than the shortest chain (gu64_split_norm).  Same bits either way; cached separately.
 int chunk_graph(sonic_engine* e, int R, int n, hipGraphExec_t* out, bool svc) {
-    const std::pair<int, int> key{R + (svc ? 4096 : 0) + (e->opt_token_logprobs ? 8192 : 0) + (e->gen_on ? 16384 : 0) + (e->opt_request_bias ? 32768 : 0), n};   // (the LP / GUARD / BIAS greedy kernel and its pointers are part of the capture)
+    const std::pair<int, int> key{R + (svc ? 4096 : 0) + (e->opt_token_logprobs ? 8192 : 0) + (e->gen_on ? 16384 : 0) + (e->opt_request_bias ? 32768 : 0) + (e->opt_sampling ? 65536 : 0), n};   // (the LP / GUARD / BIAS / SAMPLE greedy kernel and its pointers are part of the capture)
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) { *out = it->second; return SONIC_OK; }
     hipGraph_t g = nullptr; hipGraphExec_t gx = nullptr;

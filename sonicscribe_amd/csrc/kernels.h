@@ -119,7 +119,13 @@ struct GreedyArgs {
     // (1 .. BIAS_MAX_LEN), the fp32 bias (its bits), the L - 1 ids in front of the last one.  The host stores a row's entries grouped by last id, the length-1
     // entry of a group first and the others in list order (bias_pack, engine.cpp): one thread adds a group in the contract's order.  Needs hist.
     const int* bias_tab;
+    // temperature sampling (greedy_kernel<T, true, ., ., true>, option sampling).  noise_out: optional [B][V], the Gumbel value the kernel added at
+    // every id of a row with t > 0 (test hook; production passes NULL, as for the dump).  samp = NULL: off; else three words per row, 64 rows: the bits of the row's
+    // fp32 temperature (0: greedy), its seed's low word, its high word.  The row's step index is n_new[row].  Needs out_lp.  Last: every offset above is what it was
+    float* noise_out;
+    const unsigned* samp;
 };
+#define SAMP_WORDS (64 * 3)
 #define BIAS_MAX_ENTRIES 256
 #define BIAS_MAX_LEN 8
 #define BIAS_ENTRY_WORDS (3 + BIAS_MAX_LEN - 1)

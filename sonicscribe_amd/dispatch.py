@@ -46,9 +46,10 @@ def step_class(max_new: int) -> int:
 
 
 class Request:
-    __slots__ = ("windows", "prompt", "max_new", "future", "t_submit", "cls", "want_logprobs", "bias")
+    __slots__ = ("windows", "prompt", "max_new", "future", "t_submit", "cls", "want_logprobs", "bias", "sampling")
 
-    def __init__(self, windows: Sequence[Any], prompt: Sequence[int], max_new: int, want_logprobs: bool = False, bias=None):
+    def __init__(self, windows: Sequence[Any], prompt: Sequence[int], max_new: int, want_logprobs: bool = False, bias=None, sampling=None):
+        self.sampling = None if sampling is None else (float(sampling[0]), int(sampling[1]))      # its own (temperature, seed) (engine option sampling); None: greedy
         self.windows, self.prompt, self.max_new = list(windows), prompt, int(max_new)
         self.bias = bias if bias else None            # its own sequence-bias table (reqbias.RequestBias; engine option request_bias): it travels with the request
         self.want_logprobs = bool(want_logprobs)      # the future resolves to (ids, float32 log-probabilities) instead of ids (engine option token_logprobs)
@@ -133,6 +134,9 @@ class _Replica:
         # earlier, failed one left behind)
         stated = bool(getattr(engine, "request_bias", False))
         kw = {"request_bias": [r.bias for r in batch]} if stated or any(r.bias for r in batch) else {}
+        samp_on = bool(getattr(engine, "sampling", False))
+        if samp_on or any(r.sampling for r in batch):
+            kw["request_sampling"] = [r.sampling for r in batch]
         try:
             if want:
                 ids, _, lps = engine.transcribe_batch(segs, [r.prompt for r in batch], [r.max_new for r in batch], req_win=req_win, want_logprobs=True, **kw)
@@ -145,6 +149,8 @@ class _Replica:
                 return
             for r in batch:
                 kw1 = {"request_bias": [r.bias]} if stated or r.bias else {}
+                if samp_on or r.sampling:
+                    kw1["request_sampling"] = [r.sampling]
                 try:
                     if r.want_logprobs:
                         one, _, lp1 = engine.transcribe_batch(r.windows, [r.prompt], [r.max_new], req_win=[0, len(r.windows)], want_logprobs=True, **kw1)
@@ -251,6 +257,8 @@ class _ContinuousReplica:
             raise ValueError("log-probabilities need the engine option token_logprobs on every handle (ASRModel(token_logprobs=True))")
         if req.bias and not all(getattr(e, "request_bias", False) for e in self.engines):
             raise ValueError("a sequence bias needs the engine option request_bias on every handle (ASRModel(request_bias=True))")
+        if req.sampling and not all(getattr(e, "sampling", False) for e in self.engines):
+            raise ValueError("a temperature needs the engine option sampling on every handle (ASRModel(sampling=True))")
         with self.cv:
             if self.stop:
                 raise RuntimeError("ASR engine is closed")
@@ -298,6 +306,8 @@ class _ContinuousReplica:
         # (None: none), so a batch never depends on what an earlier, failed one left behind
         if getattr(eng, "request_bias", False) or any(r.bias for r in batch):
             eng.set_request_bias([r.bias for r in batch])
+        if getattr(eng, "sampling", False) or any(r.sampling for r in batch):      # (likewise: every prefill states its values, None = greedy)
+            eng.set_request_sampling([r.sampling for r in batch])
         # waited for: a splice queued behind a prefill that is still running would hold the decoder's whole stream (every running row) at the
         # event until the prefill is done - final p50 at 128 sessions 438 -> 657 ms when the hand-over came early.  (The bulk pipeline hands over
         # early, sonicscribe_amd/pipeline.py: its next batch is long done when a block frees up.)
@@ -456,6 +466,7 @@ class _NativeContinuousReplica:
         self.out_cap = int(engine.max_ctx)
         self.lp = all(getattr(e, "token_logprobs", False) for e in self.engines)      # then completions are collected with their log-probabilities
         self.bias = all(getattr(e, "request_bias", False) for e in self.engines)      # then a request may bring its own sequence-bias table
+        self.samp = all(getattr(e, "sampling", False) for e in self.engines)          # then a request may bring its own (temperature, seed)
         self.thread = threading.Thread(target=self._complete_loop, name=f"sonic-dispatch-{index}.complete", daemon=True)
         self.thread.start()
 
@@ -489,6 +500,8 @@ class _NativeContinuousReplica:
             raise ValueError("log-probabilities need the engine option token_logprobs on every handle (ASRModel(token_logprobs=True))")
         if req.bias and not self.bias:
             raise ValueError("a sequence bias needs the engine option request_bias on every handle (ASRModel(request_bias=True))")
+        if req.sampling and not self.samp:
+            raise ValueError("a temperature needs the engine option sampling on every handle (ASRModel(sampling=True))")
         if req.bias:
             req.bias.check_vocab(self.engine.dims.vocab)
         wins = req.windows
@@ -512,16 +525,22 @@ class _NativeContinuousReplica:
         with self.lock:
             if self.stop:
                 raise RuntimeError("ASR engine is closed")
-            if req.bias:
+            if req.sampling:
+                from . import sampling as _sampling
+                b_ids, b_off, b_val = req.bias.table() if req.bias else (None, None, np.zeros(0, np.float32))
+                rc = self.lib.sonic_dispatch_submit_sampled(self.h, _p(pcm), _p(offs), ring_arr, _p(start) if any_ring else None, _p(n) if any_ring else None, W,
+                                                            _p(prompt), len(prompt), int(req.max_new), _sampling.check_temperature(req.sampling[0]),
+                                                            _sampling.check_seed(req.sampling[1]), _p(b_ids), _p(b_off), _p(b_val) if len(b_val) else None, len(b_val), C.byref(t))
+            elif req.bias:
                 b_ids, b_off, b_val = req.bias.table()
                 rc = self.lib.sonic_dispatch_submit_bias(self.h, _p(pcm), _p(offs), ring_arr, _p(start) if any_ring else None, _p(n) if any_ring else None, W,
                                                          _p(prompt), len(prompt), int(req.max_new), _p(b_ids), _p(b_off), _p(b_val), len(b_val), C.byref(t))
             else:
                 rc = self.lib.sonic_dispatch_submit(self.h, _p(pcm), _p(offs), ring_arr, _p(start) if any_ring else None, _p(n) if any_ring else None, W,
                                                     _p(prompt), len(prompt), int(req.max_new), C.byref(t))
-            if rc != 0 and req.bias:
+            if rc != 0 and (req.bias or req.sampling):
                 msg = (self.lib.sonic_last_error(None) or b"").decode()
-                if "request_bias" in msg or "sonic_dispatch_submit_bias" in msg:
+                if "request_bias" in msg or "sonic_dispatch_submit_bias" in msg or "sampling" in msg or "sonic_dispatch_submit_sampled" in msg:
                     raise ValueError(msg)
             if rc != 0:
                 raise RuntimeError("ASR engine failed" if rc not in (1,) else "ASR engine is closed or the request is malformed")
@@ -631,6 +650,8 @@ class _BulkReplica:
             raise TypeError("bulk mode takes host PCM windows or slices of device rings")
         if req.bias:                                      # refused, not dropped: the bulk pipeline (csrc/pipeline.cpp) carries no per-request tables
             raise ValueError("a sequence bias is not supported with bulk=True (the bulk pipeline carries no per-request tables): use the continuous or the batch dispatcher")
+        if req.sampling:                                  # likewise: no per-request values travel through the bulk pipeline
+            raise ValueError("a temperature is not supported with bulk=True (the bulk pipeline carries no per-request values): use the continuous or the batch dispatcher")
         with self.cv:
             if self.stop:
                 raise RuntimeError("ASR engine is closed")
@@ -789,11 +810,12 @@ class Dispatcher:
             return self.replicas[least]                                     # rebalance: the home replica is more than a batch behind
         return self.replicas[home]
 
-    def submit(self, windows, prompt, max_new: int, session: Optional[str] = None, replica: Optional[int] = None, want_logprobs: bool = False, bias=None) -> Future:
+    def submit(self, windows, prompt, max_new: int, session: Optional[str] = None, replica: Optional[int] = None, want_logprobs: bool = False, bias=None, sampling=None) -> Future:
         """`replica` pins the request (windows that are slices of a device ring can only be decoded where the ring lives).  want_logprobs: the
         future resolves to (ids, log-probabilities) - the engines need option token_logprobs.  bias: the request's own sequence-bias table
-        (reqbias.RequestBias) - the engines need option request_bias; refused with bulk=True."""
-        req = Request(windows, prompt, max_new, want_logprobs, bias)
+        (reqbias.RequestBias) - the engines need option request_bias; refused with bulk=True.  sampling: the request's own (temperature, seed) - the engines
+        need option sampling; refused with bulk=True."""
+        req = Request(windows, prompt, max_new, want_logprobs, bias, sampling)
         (self.replicas[replica] if replica is not None else self.pick(session)).put(req)
         return req.future
 

@@ -40,6 +40,7 @@ EXPORTS = [
     "sonic_set_generation", "sonic_get_generation", "sonic_test_greedy_guard",
     "sonic_test_add_rmsnorm", "sonic_test_quant_rows", "sonic_test_swiglu_slab", "sonic_test_decode_o_gu", "sonic_test_rope_append", "sonic_test_rope_enc",
     "sonic_set_request_bias", "sonic_dispatch_submit_bias", "sonic_test_greedy_bias",
+    "sonic_set_request_sampling", "sonic_dispatch_submit_sampled", "sonic_test_greedy_sample",
 ]
 ABI_VERSION = 12
 
@@ -170,11 +171,15 @@ def load_library():
     lib.sonic_test_rope_enc.argtypes = [vp, vp] + [C.c_int] * 6 + [vp]
     lib.sonic_set_request_bias.argtypes = [vp, vp, vp, vp, vp, C.c_int]
     lib.sonic_test_greedy_bias.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_float, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.sonic_set_request_sampling.argtypes = [vp, vp, vp, C.c_int]
+    lib.sonic_test_greedy_sample.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, C.c_float, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp,
+                                             vp, vp, vp, vp]
     lib.sonic_slot_create.argtypes = [vp, C.POINTER(vp)]
     lib.sonic_slot_count.argtypes = [vp]
     lib.sonic_dispatch_create.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.POINTER(vp)]
     lib.sonic_dispatch_submit.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, i64p]
     lib.sonic_dispatch_submit_bias.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, i64p]
+    lib.sonic_dispatch_submit_sampled.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, C.c_int, C.c_float, C.c_uint64, vp, vp, vp, C.c_int, i64p]
     lib.sonic_dispatch_cancel.argtypes = [vp, C.c_int64]
     lib.sonic_dispatch_next.argtypes = [vp, C.c_int, i64p, ip, vp, C.c_int, ip, C.c_char_p, C.c_int]
     lib.sonic_dispatch_next_lp.argtypes = [vp, C.c_int, i64p, ip, vp, C.c_int, ip, C.c_char_p, C.c_int, vp]
@@ -327,6 +332,7 @@ class Engine:
         s = Engine(self.dims, 0, 0, self.max_batch, self.max_ctx, _slot_of=root)
         s.token_logprobs = bool(getattr(root, "token_logprobs", False))
         s.request_bias = bool(getattr(root, "request_bias", False))
+        s.sampling = bool(getattr(root, "sampling", False))
         root._slots.append(s)
         return s
 
@@ -473,11 +479,13 @@ class Engine:
         return pcm, offs, rings, start, n
 
     def transcribe_batch(self, segments: Sequence[Any], prompts: Sequence[Sequence[int]], max_new: Sequence[int],
-                         req_win: Optional[Sequence[int]] = None, want_logits: bool = False, want_logprobs: bool = False, request_bias=None):
+                         req_win: Optional[Sequence[int]] = None, want_logits: bool = False, want_logprobs: bool = False, request_bias=None, request_sampling=None):
         """segments: int16 PCM windows (<= 30 s each, already peak-normalised) or RingSlice objects (raw wire PCM resident in a device
         ring; normalised on the device over the windows of their request); one prompt per request. Returns (ids list, logits or None);
         with want_logprobs (option token_logprobs on this handle) one more element: the float32 log-probability of every returned token, per request.
-        request_bias: one reqbias.RequestBias or None per request (option request_bias on this handle; set_request_bias)."""
+        request_bias: one reqbias.RequestBias or None per request (option request_bias on this handle; set_request_bias).
+        request_sampling: one (temperature, seed) or None (greedy) per request (option sampling on this handle; set_request_sampling)."""
+        samp = None if request_sampling is None else pack_request_sampling(request_sampling)      # (validated before anything is armed)
         if any(isinstance(s, RingSlice) for s in segments):
             pcm, offs, rings, start, n = self._pack_mixed(segments)
             ids, poffs = self._pack_prompts(prompts)
@@ -490,6 +498,8 @@ class Engine:
             logits = np.zeros((out_ld, R, self.dims.vocab), np.float32) if want_logits else None
             if request_bias is not None:             # (right ahead of the call that consumes them, on success or failure: nothing in between can raise)
                 self.set_request_bias(request_bias)
+            if samp is not None:
+                self._arm_sampling(samp)
             self._check(self.lib.sonic_transcribe_mixed(self.h, _p(pcm), _p(offs), rings, _p(start), _p(n), len(segments), _p(rw), R, _p(ids), _p(poffs),
                                                         _p(mn), _p(out), out_ld, _p(out_len), _p(logits)))
             res = [out[r, : out_len[r]].copy() for r in range(R)]
@@ -505,6 +515,8 @@ class Engine:
         logits = np.zeros((out_ld, R, self.dims.vocab), np.float32) if want_logits else None
         if request_bias is not None:
             self.set_request_bias(request_bias)
+        if samp is not None:
+            self._arm_sampling(samp)
         self._check(self.lib.sonic_transcribe_batch(self.h, _p(pcm), _p(offs), len(segments), _p(rw), R, _p(ids), _p(poffs), _p(mn),
                                                     _p(out), out_ld, _p(out_len), _p(logits)))
         res = [out[r, : out_len[r]].copy() for r in range(R)]
@@ -535,14 +547,17 @@ class Engine:
         self._check(self.lib.sonic_run_staged(self.h, _p(rw), len(prompts), _p(ids), _p(poffs), _p(mn), int(want_logits)))
 
     def prefill(self, prompts: Sequence[Sequence[int]], max_new: Sequence[int], req_win: Optional[Sequence[int]] = None, want_logits: bool = False, wait: bool = True,
-                request_bias=None):
+                request_bias=None, request_sampling=None):
         """Stage entry point: everything up to and including the first greedy token of the staged batch (sonic_prefill).  wait=False: the
         work is only queued when the call returns (sonic_prefill_enqueue; a following splice_rows orders itself behind it on the device)."""
         ids, poffs = self._pack_prompts(prompts)
         mn = np.ascontiguousarray(max_new, dtype=np.int32)
         rw = np.ascontiguousarray(req_win, dtype=np.int32) if req_win is not None else None
+        samp = None if request_sampling is None else pack_request_sampling(request_sampling)
         if request_bias is not None:                     # one reqbias.RequestBias or None per request: this prefill consumes them, on success or failure
             self.set_request_bias(request_bias)
+        if samp is not None:                             # one (temperature, seed) or None per request: likewise
+            self._arm_sampling(samp)
         if not wait:
             self._check(self.lib.sonic_prefill_enqueue(self.h, _p(rw), len(prompts), _p(ids), _p(poffs), _p(mn)))
             return
@@ -699,6 +714,8 @@ def _set_option(self, key: str, value: int):
     self._check(self.lib.sonic_set_option(self.h, key.encode(), value))
     if key == "request_bias":
         self.request_bias = bool(value)          # (likewise)
+    if key == "sampling":
+        self.sampling = bool(value)              # (likewise)
     if key == "token_logprobs":
         self.token_logprobs = bool(value)        # (a slot created from now on copies it, in the library and here)
 
@@ -833,6 +850,56 @@ def _test_greedy_bias(self, slabs, B: int, hist, hist_len, tables, repetition_pe
                                                 int(no_repeat_ngram_size), _p(sup) if sup.size else None, int(sup.size), _p(f),
                                                 _p(seq_ids) if seq_ids.size else None, _p(seq_off), _p(bias) if bias.size else None, _p(req_off), _p(tok), _p(lg), _p(lp)))
     return tok, lg, lp
+
+
+def pack_request_sampling(values):
+    """one (temperature, seed) per request, or None for a greedy one -> sonic_set_request_sampling's arrays, validated (sampling.check_temperature / check_seed)"""
+    from . import sampling
+    vals = [(0.0, 0) if v is None else v for v in values]
+    return sampling.pack_sampling([v[0] for v in vals], [v[1] for v in vals])
+
+
+def _arm_sampling(self, packed):
+    t, s = packed
+    self._check(self.lib.sonic_set_request_sampling(self.h, _p(t), _p(s), len(t)))
+
+
+def _set_request_sampling(self, values):
+    """The (temperature, seed) of the requests of the NEXT prefill / run on this handle (sonic_set_request_sampling), one pair or None (greedy) per request; that
+    call consumes them.  Needs option sampling (SonicError naming it otherwise).  ValueError for a temperature that is neither 0 nor in [1e-3, 100]."""
+    self._arm_sampling(pack_request_sampling(list(values)))
+
+
+def _test_greedy_sample(self, slabs, B: int, temperature, seed, step, hist=None, hist_len=None, tables=None, repetition_penalty: float = 1.0,
+                        no_repeat_ngram_size: int = 0, suppress_tokens=(), force_ids=None, want_noise: bool = True):
+    """sonic_test_greedy_sample: the sampling instantiations of the greedy kernel in this handle's type.  hist_len None: the plain family; tables None: the guard
+    family; else the bias family -> (token [B], RAW logits [B][V], log-probability over the processed scores at temperature 1 [B], Gumbel noise used [B][V] or None)"""
+    s = np.ascontiguousarray(slabs, np.float32)
+    ks, mpad, V = s.shape
+    t = np.ascontiguousarray(temperature, np.float32)
+    sd = np.ascontiguousarray([int(x) for x in seed], np.uint64)
+    stp = np.ascontiguousarray(step, np.int32)
+    assert t.shape == sd.shape == stp.shape == (B,)
+    h = hl = None
+    hld = 0
+    if hist_len is not None:
+        h = np.ascontiguousarray(hist, np.int32).reshape(B, -1)
+        hl = np.ascontiguousarray(hist_len, np.int32)
+        hld = h.shape[1]
+    sup = np.ascontiguousarray(list(suppress_tokens), dtype=np.int32)
+    seq_ids = seq_off = bias = req_off = None
+    if tables is not None:
+        seq_ids, seq_off, bias, req_off = pack_request_bias(list(tables))
+    tok = np.zeros(B, np.int32)
+    lg = np.zeros((B, V), np.float32)
+    lp = np.full(B, np.nan, np.float32)
+    noise = np.zeros((B, V), np.float32) if want_noise else None
+    f = np.ascontiguousarray(force_ids, np.int32) if force_ids is not None else None
+    self._check(self.lib.sonic_test_greedy_sample(self.h, _p(s), ks, mpad, V, B, _p(h) if h is not None and h.size else None, hld, _p(hl), float(repetition_penalty),
+                                                  int(no_repeat_ngram_size), _p(sup) if sup.size else None, int(sup.size), _p(f),
+                                                  _p(seq_ids) if seq_ids is not None and seq_ids.size else None, _p(seq_off), _p(bias) if bias is not None and bias.size else None,
+                                                  _p(req_off), _p(t), _p(sd), _p(stp), _p(tok), _p(lg), _p(lp), _p(noise)))
+    return tok, lg, lp, noise
 
 
 def _test_linear_int8(self, X, W, bias=None, resid=None, group_rows=None, epi=EPI_BIAS):
@@ -972,6 +1039,9 @@ Engine.test_greedy_guard = _test_greedy_guard
 Engine.set_generation = _set_generation
 Engine.set_request_bias = _set_request_bias
 Engine.test_greedy_bias = _test_greedy_bias
+Engine.set_request_sampling = _set_request_sampling
+Engine._arm_sampling = _arm_sampling
+Engine.test_greedy_sample = _test_greedy_sample
 Engine.get_generation = _get_generation
 Engine.test_skinny_gu = _test_skinny_gu
 Engine.debug_read = _debug_read

@@ -114,9 +114,12 @@ class _FileJob:
     """One file on the device: its ring, its plan and its queued decodes."""
 
     def __init__(self, model, audio, vad, vad_enabled: bool, hotwords, max_segment_duration, max_new_tokens: int, filename: str,
-                 sampling_rate: int = SAMPLE_RATE, sequence_bias=None, bad_words_ids=None, hotword_boost=None):
+                 sampling_rate: int = SAMPLE_RATE, sequence_bias=None, bad_words_ids=None, hotword_boost=None, temperature=None, seed=None):
         if not hasattr(model, "model"):
             raise RuntimeError("ASR model has been released")
+        # the file's temperature (a float) or fallback ladder (a sequence) and seed (a model built with sampling=True; ASRModel._request_sampling): every segment
+        # of the file is decoded with them, each as its own request (DESIGN.md 6.6)
+        self.samp = model._request_sampling(temperature, seed) if hasattr(model, "_request_sampling") else None
         # the file's sequence-bias table (a model built with request_bias=True; ASRModel._request_bias): every segment of the file carries it
         self.bias = model._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost) if hasattr(model, "_request_bias") else None
         self.model, self.filename = model, filename
@@ -178,6 +181,9 @@ class _FileJob:
             # > 30 s: one request of several windows sharing one peak, as transcribe() makes it (frontend.split_windows)
             windows = [self.ring.slice(self.first + a + s, e - s) for s, e in frontend.split_windows(n, m.dims)]
             n_audio, _ = frontend.request_audio_tokens(n, m.dims)
+            if self.samp is not None:              # (a future of the TEXT: the ladder judges texts; records() takes either)
+                self.futures.append(m._dispatch(windows, m.prompt.build(instruction, n_audio), self.max_new, False, self.bias, self.samp, replica=self.replica))
+                continue
             self.futures.append(m._dispatcher.submit(windows, m.prompt.build(instruction, n_audio), self.max_new, replica=self.replica, **({"bias": self.bias} if self.bias else {})))
 
     def records(self) -> Iterator[Dict[str, Any]]:
@@ -193,7 +199,8 @@ class _FileJob:
                 try:
                     if isinstance(fut, Exception):
                         raise fut
-                    text = self.model.prompt.decode(fut.result()).strip()
+                    got = fut.result()
+                    text = got if isinstance(got, str) else self.model.prompt.decode(got).strip()
                     rec = {"type": "segment_result", "segment_index": seg["segment_index"], "original_index": seg["original_index"],
                            "start_time": round(seg["start_time"], 3), "end_time": round(seg["end_time"], 3), "duration": round(seg["duration"], 3),
                            "text": text, "processing_time": 0, "is_long_segment": seg["is_long_segment"], "hotwords_used": hot,
@@ -266,9 +273,10 @@ def _detect(vad, jobs: Sequence[_FileJob]) -> List[Any]:
 
 def transcribe_file(model, audio, vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                     max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filename: str = "",
-                    sampling_rate: int = SAMPLE_RATE, sequence_bias=None, bad_words_ids=None, hotword_boost=None) -> Iterator[Dict[str, Any]]:
+                    sampling_rate: int = SAMPLE_RATE, sequence_bias=None, bad_words_ids=None, hotword_boost=None, temperature=None, seed=None) -> Iterator[Dict[str, Any]]:
     """Generator of the reference's file-mode records for one file (see ASRModel.transcribe_file)."""
-    job = _FileJob(model, audio, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filename, sampling_rate, sequence_bias, bad_words_ids, hotword_boost)
+    job = _FileJob(model, audio, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filename, sampling_rate, sequence_bias, bad_words_ids, hotword_boost,
+                   temperature, seed)
     try:
         ts = vad.detect_voice_activity_ring(job.ring, job.first, job.total)[0] if job.wants_vad else None
         job.plan(ts)
@@ -282,14 +290,15 @@ def transcribe_file(model, audio, vad, vad_enabled: bool = True, hotwords: Optio
 def transcribe_files(model, audios: Sequence[Any], vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                      max_segment_duration: Optional[float] = None, max_new_tokens: int = 256,
                      filenames: Optional[Sequence[str]] = None, sampling_rate: int = SAMPLE_RATE, sequence_bias=None, bad_words_ids=None,
-                     hotword_boost=None) -> List[FileRecords]:
+                     hotword_boost=None, temperature=None, seed=None) -> List[FileRecords]:
     """One record iterator per file; the VAD of all files runs in one device call and every file's segments are queued before the call
     returns.  Each iterator must be exhausted or closed (its ring lives until then)."""
     names = list(filenames) if filenames is not None else [""] * len(audios)
     jobs: List[_FileJob] = []
     try:
         for a, name in zip(audios, names):
-            jobs.append(_FileJob(model, a, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, name, sampling_rate, sequence_bias, bad_words_ids, hotword_boost))
+            jobs.append(_FileJob(model, a, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, name, sampling_rate, sequence_bias, bad_words_ids, hotword_boost,
+                                 temperature, seed))
         for job, ts in zip(jobs, _detect(vad, jobs)):
             job.plan(ts)
         for job in jobs:

@@ -38,10 +38,13 @@ def committed_max_new_tokens(seconds: float) -> int:
 
 class GatedSessions:
     def __init__(self, model, session_ids: Sequence[str], buffer_seconds: float = 30.0, hotwords: Optional[List[str]] = None,
-                 cfg: GateConfig = GateConfig(), device_vad: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None):
+                 cfg: GateConfig = GateConfig(), device_vad: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
+                 temperature: Optional[float] = None, seed: Optional[int] = None):
         self.model, self.ids, self.hotwords, self.cfg = model, list(session_ids), hotwords, cfg
         # beside the hotwords: the sessions' sequence-bias values (a model built with request_bias=True), handed to every decode only when one is given
-        self._bias_kw = {k: v for k, v in (("sequence_bias", sequence_bias), ("bad_words_ids", bad_words_ids), ("hotword_boost", hotword_boost)) if v is not None}
+        # (likewise the sessions' temperature - a float - and seed, for a model built with sampling=True)
+        self._bias_kw = {k: v for k, v in (("sequence_bias", sequence_bias), ("bad_words_ids", bad_words_ids), ("hotword_boost", hotword_boost),
+                                           ("temperature", temperature), ("seed", seed)) if v is not None}
         self.device_vad = bool(device_vad)            # opt-in: windows are ring ranges, `recent` stays empty
         n = len(self.ids)
         self.streams = [model.open_stream(s, buffer_seconds) for s in self.ids]
