@@ -1,61 +1,17 @@
-// Memory-bound glue kernels (SURVEY.md §8a K6, K7, K11, K12): LayerNorm / RMSNorm with wavefront
+// Memory-bound glue kernels (SURVEY.md §8a K6, K7, K11): LayerNorm / RMSNorm with wavefront
 // reductions, rotate-half RoPE (partial-32 encoder, full-128 decoder) fused with the KV-cache append,
-// the decode-step consumers of the skinny-GEMM partial slabs, embedding gather, fused argmax + greedy
-// controller, synthetic weight generator.  All 16-bit traffic is 16 B per lane (8 elements).
+// the decode-step consumers of the skinny-GEMM partial slabs, embedding gather, in-stream fill and dtype
+// conversions, synthetic weight generator.  All 16-bit traffic is 16 B per lane (8 elements).  (The fused
+// argmax + greedy controller, K12, lives in greedy.hip.)
 //
 // Rounding boundaries reproduce torch's op sequence of the reference path: every torch op output is rounded to the
 // activation dtype once, arithmetic inside an op is fp32.  Kernels are templated on that dtype T: bf16 (`mode="native"`) or
 // IEEE half (`mode="int8"`, asr.py:61,296).  In int8 mode the decode-step consumers read int32 slabs of a quantised skinny
-// GEMM (deq4) and producers that own whole rows also emit them quantised for the next Linear8bitLt (quant_emit_row).
+// GEMM (deq4) and producers that own whole rows also emit them quantised for the next Linear8bitLt (quant_emit_row, int8_util.h).
 #include "common.h"
 #include "kernels.h"
 
 #include "int8_util.h"
-
-// A block that owns one whole row (thread c holds its elements [8c, 8c+8) as fp16 values in y, threads with !active hold nothing)
-// emits the row quantised: absmax without the elements >= 6.0, int8 = rn(y * 127 / absmax) (0 for outliers), and the ascending
-// list of the outlier positions.  Every thread of the block must call it.  s_f: >= 16 floats, s_i: >= 17 ints of LDS scratch.
-// FRESH: nobody has touched s_f / s_i in this kernel before (no barrier needed in front of the first write).
-template <bool FRESH = false>
-__device__ __forceinline__ void quant_emit_row(const float (&y)[8], bool active, int c, int row, const QuantOut& qo, float* s_f, int* s_i) {
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nw = (blockDim.x + 63) >> 6;
-    float amax = -1.17549435e-38f;
-    int cnt = 0;
-    if (active) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { const float a = fabsf(y[j]); if (a < LLM_INT8_THRESHOLD) amax = fmaxf(amax, a); else ++cnt; }
-    }
-    amax = wave_max(amax);
-    int incl = cnt;                                   // inclusive scan of the outlier counts inside the wave (only where the wave holds any)
-    if (__ballot(cnt > 0)) {
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
-    }
-    if constexpr (!FRESH) __syncthreads();           // scratch may still be in use by the caller
-    if (lane == 63) s_i[wid] = incl;
-    if (lane == 0) s_f[wid] = amax;
-    __syncthreads();
-    float bm = s_f[0]; int base = 0, total = 0;
-    for (int w = 0; w < nw; ++w) { bm = fmaxf(bm, s_f[w]); if (w < wid) base += s_i[w]; total += s_i[w]; }
-    const float scale = 127.0f / bm;
-    if (tid == 0) { qo.sca[row] = bm; qo.oc_cnt[row] = total; }
-    if (active) {
-        int pos = base + incl - cnt;
-        int pk[2] = {0, 0};
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const bool out = !(fabsf(y[j]) < LLM_INT8_THRESHOLD);
-            int qv = (out || !(bm > 0.f)) ? 0 : (int)rintf(y[j] * scale);
-            pk[j >> 2] |= (qv & 0xFF) << ((j & 3) * 8);
-            if (out) {
-                const long at = (long)row * qo.oc_ld + pos++;
-                qo.oc_list[at] = c * 8 + j;
-                if (qo.oc_val) qo.oc_val[at] = y[j];
-            }
-        }
-        *(int2*)(qo.q + (long)row * qo.ldq + c * 8) = make_int2(pk[0], pk[1]);
-    }
-}
 
 // ---------------------------------------------------------------- LayerNorm (modeling_glmasr.py:246-247,305)
 // one wave per row, d % 8 == 0, d <= 2048; two-pass in registers (mean, then centred variance).
@@ -549,308 +505,6 @@ __global__ void assemble_embeds_kernel(const int* src, const bf16_t* table, cons
     for (int c = threadIdx.x; c < (d >> 3); c += blockDim.x) *(bf16x8*)(x + (long)tok * d + c * 8) = *(const bf16x8*)(from + c * 8);
 }
 
-// ---------------------------------------------------------------- argmax + greedy controller (generation/utils.py:2894-2936)
-// LP (option token_logprobs): the block also returns log_softmax(l)[tok] of the token it emits.  Every thread keeps the sum lp_s of
-// exp(r - lp_m) over the values it visits, lp_m being its running maximum `best`: one rescale per trip of the unrolled loop, then the trip's (up to
-// 16) terms.  Threads are brought to their wave's maximum and added by the xor butterfly, waves to the block's maximum and added as a fixed tree by
-// thread 0: one block, one order, whatever the grid.  exp is v_exp_f32 of the argument times log2(e); the closing log and subtraction are fp64.
-// LP = false is the kernel as it was: everything below that belongs to the sum sits behind `if constexpr (LP)`.
-// GUARD (sonic_set_generation): HF's repetition_penalty, no_repeat_ngram_size and suppress_tokens on the fp32 scores the argmax compares.
-// The block first builds two vocabulary bitmaps in LDS from the row's history hist[b][0 .. kv_len[b]) (prompt ids, then every id emitted): "seen" (ids of
-// the history) and "banned" (continuations of earlier occurrences of the last n - 1 ids, and the suppress list).  Integer ORs: no order in them.  The
-// loop then reads the 4 bits of each map that belong to its f32x4 group: a seen score becomes s < 0 ? s * p : s / p (fp32 multiply, correctly rounded
-// fp32 divide), a banned one -inf, in that order, behind the dump (raw logits) and ahead of the compare and the LP sum.  Thread 0 appends the emitted
-// id at hist[b][kv_len[b]].  A row whose scores are all -inf emits token 0 (torch.argmax of equal values).  GUARD = false is the kernel as it was.
-// BIAS (option request_bias; implies GUARD): HF's SequenceBiasLogitsProcessor, with NoBadWordsLogitsProcessor folded in as entries of bias -inf
-// (generation/logits_process.py; the reference's hotwords, backend/asr.py:303-333, are what it serves), on the row's own table GreedyArgs.bias_tab.  Thread e of the
-// prologue decides whether entry e applies to the history (L = 1: always; else L <= len and the last L - 1 ids equal its prefix) and leaves a flag in LDS; the first
-// entry of every last-id group then adds the group's flagged biases to +0.0 in stored order - HF's order: the length-1 value, then the longer sequences in list
-// order - and leaves (id, sum) in the LDS list and the id's bit in a third bitmap, "biased".  The loop reads that map's 4 bits with the others; a set bit scans the
-// list (every lane reads the same word: a broadcast) and adds the sum, once, ahead of guard_score: the bias is HF's first processor.  An unset bit adds nothing
-// (HF adds +0.0 there, which changes no compare and no exponential).  BIAS = false is the kernel as it was, GUARD or not.
-// SAMPLE (option sampling; LP only): temperature sampling by the Gumbel-max identity.  Row b reads GreedyArgs.samp[3b ..]: the bits of its
-// temperature t, its seed's low and high word.  t == 0: no division, no noise - the row's token and out_lp are the bits of the LP kernel.  t > 0: the compare runs
-// on y_i = fdiv_rn(s_i, t) + g_i, s the fully processed score (bias, penalty, bans: HF's order, then TemperatureLogitsWarper), g_i = -ln(-ln(u_i)) Gumbel noise
-// from Philox4x32-10 with key = the seed, counter = (i >> 2, n_new[b], 0, 0), word i & 3: one call per f32x4 group; u = ((word >> 9) + 0.5) * 2^-23 lies
-// strictly inside (0, 1).  The first maximum of y is an exact draw from softmax(s / t); it depends on (scores, t, seed, step) alone - not on batch, row or
-// slot.  The log-probability sum still runs over s, against its own running maximum (`rmax`; without SAMPLE that maximum is `best`), and out_lp is
-// log_softmax(s)[tok] at temperature 1 - openai-whisper's convention, the one its fallback thresholds are calibrated on; the emitted token's s is recomputed
-// from the slabs as the forced id's is.  Teacher forcing wins over sampling; step_logits stay raw.  The two logs are logf - v_log_f32 (1 ulp) times ln 2 in extended precision, a relative error
-// of at most 1.5 * 2^-23 each: |g - exact| <= (1 + 16.64) * 1.5 * 2^-23 < 3.2e-6.
-extern __shared__ unsigned g_bits[];
-__device__ __forceinline__ float guard_score(float r, unsigned seen, unsigned banned, float p) {
-    if (seen & 1u) r = r < 0.f ? r * p : __fdiv_rn(r, p);
-    return (banned & 1u) ? -INFINITY : r;
-}
-__device__ __forceinline__ void guard_set(unsigned* map, int id, int V) {
-    if ((unsigned)id < (unsigned)V) atomicOr(&map[id >> 5], 1u << (id & 31));
-}
-__device__ __forceinline__ float bias_of(const int* ids, const float* sums, int n, int id) {
-    float b = 0.f;
-    for (int k = 0; k < n; ++k) if (ids[k] == id) b = sums[k];      // (ids are unique: one group per last id)
-    return b;
-}
-__device__ __forceinline__ float lp_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-// Philox4x32-10 (Salmon et al., SC'11): ten rounds, the key bumped between them
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned* out) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0, h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-// 23 bits, centred: every value is exact in fp32 and inside (0, 1).  logf is the library's: relatively accurate also at u next to 1, where -ln(u) is tiny (the
-// hardware logarithm's 1 ulp is of ITS result): no 1 - u form needed
-__device__ __forceinline__ float gumbel_of(unsigned word) {
-    const float u = ((float)(word >> 9) + 0.5f) * 1.1920928955078125e-7f;
-    return -logf(-logf(u));
-}
-#define LPB (SAMPLE ? rmax : best)      // what the LP sum is taken against: the running maximum of s
-template <typename T, bool LP, bool GUARD = false, bool BIAS = false, bool SAMPLE = false>
-__global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
-    static_assert(GUARD || !BIAS, "the request bias lives in the guard instantiations (it needs their history)");
-    static_assert(LP || !SAMPLE, "sampling lives in the log-probability instantiations (the fallback ladder reads them)");
-    typedef typename ET<T>::v8 V8;
-    __shared__ float sv[16];
-    __shared__ int si[17];
-    __shared__ int s_tok;
-    __shared__ float ss_lp[LP ? (SAMPLE ? 32 : 16) : 1];
-    [[maybe_unused]] float* const ss_m = ss_lp + (SAMPLE ? 16 : 0);      // SAMPLE: the waves' maxima of the unperturbed scores (sv holds those of y)
-    float lp_m = -INFINITY, lp_s = 0.f;      // LP: the thread's sum is lp_s * exp(lp_m); a thread that saw nothing holds (-inf, 0)
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const float* lg = a.logits + (long)b * a.V;
-    const long ks_stride = (long)a.mpad * a.V;
-    float* dump = a.logits_dump ? a.logits_dump + (long)a.step_counter[b] * a.dump_stride_step + (long)b * a.V : nullptr;
-    float best = -INFINITY; int bi = 0x7fffffff;
-    // SAMPLE: the row's temperature, seed and step (block-uniform); rmax = the running maximum of s, which `best` (now over y) no longer is
-    [[maybe_unused]] float temp = 0.f, rmax = -INFINITY; [[maybe_unused]] unsigned k0 = 0u, k1 = 0u, step_n = 0u; [[maybe_unused]] bool noisy = false;
-    [[maybe_unused]] float* noise = nullptr;
-    if constexpr (SAMPLE) {
-        temp = __uint_as_float(a.samp[3 * b]); k0 = a.samp[3 * b + 1]; k1 = a.samp[3 * b + 2]; step_n = (unsigned)a.n_new[b];
-        noisy = temp > 0.f;
-        if (a.noise_out) noise = a.noise_out + (long)b * a.V;
-    }
-    // the first layer's norm weight for the tail of this kernel, requested before anything else (cold every step; behind the token's
-    // embedding row it was one more dependent round trip)
-    f32x4 gw0 = {0.f, 0.f, 0.f, 0.f}, gw1 = {0.f, 0.f, 0.f, 0.f};
-    if (a.y && (a.d >> 3) <= 1024 && tid < (a.d >> 3)) { gw0 = *(const f32x4*)(a.norm_w + tid * 8); gw1 = *(const f32x4*)(a.norm_w + tid * 8 + 4); }
-    [[maybe_unused]] unsigned* g_seen = nullptr; [[maybe_unused]] unsigned* g_ban = nullptr;
-    [[maybe_unused]] unsigned* g_bia = nullptr; [[maybe_unused]] int* q_id = nullptr; [[maybe_unused]] float* q_sum = nullptr; [[maybe_unused]] int q_n = 0;
-    if constexpr (GUARD) {
-        const int nw = (a.V + 31) >> 5;
-        g_seen = g_bits; g_ban = g_bits + nw;
-        for (int w = tid; w < (BIAS ? 3 : 2) * nw; w += 1024) g_bits[w] = 0u;
-        __syncthreads();
-        const int* h = a.hist + (long)b * a.hist_ld;
-        const int len = min(max(a.kv_len[b], 0), a.hist_ld), n = a.ngram;
-        if constexpr (BIAS) {
-            // dynamic LDS behind the three maps: the group sums' ids [256], the sums [256], the entries' flags [256] (greedy_guard_lds)
-            g_bia = g_bits + 2 * nw; q_id = (int*)(g_bits + 3 * nw); q_sum = (float*)(q_id + BIAS_MAX_ENTRIES);
-            int* q_flag = q_id + 2 * BIAS_MAX_ENTRIES;
-            const int* tab = a.bias_tab + 64 + (long)b * BIAS_ROW_WORDS;
-            q_n = min(max(a.bias_tab[b], 0), BIAS_MAX_ENTRIES);
-            const int* en = tab + tid * BIAS_ENTRY_WORDS;
-            int last = -1;
-            if (tid < q_n) {
-                last = en[0];
-                const int L = en[1];
-                bool m = L >= 1 && L <= BIAS_MAX_LEN && L <= len;          // (L == len + 1 would fit its prefix; HF ignores it, so does this)
-                if (m) { const int* tail = h + len - (L - 1); for (int k = 0; k < L - 1; ++k) m = m && tail[k] == en[3 + k]; }
-                q_flag[tid] = (L == 1 || m) ? 1 : 0;                       // a single id has no prefix to match: it applies whatever the history holds
-                q_id[tid] = -1;
-            }
-            __syncthreads();
-            if (tid < q_n && (unsigned)last < (unsigned)a.V && (tid == 0 || en[-BIAS_ENTRY_WORDS] != last)) {      // the first entry of its last-id group
-                float acc = 0.f; bool any = false;
-                for (int k = tid; k < q_n && tab[k * BIAS_ENTRY_WORDS] == last; ++k)
-                    if (q_flag[k]) { acc += __int_as_float(tab[k * BIAS_ENTRY_WORDS + 2]); any = true; }
-                if (any) { q_id[tid] = last; q_sum[tid] = acc; guard_set(g_bia, last, a.V); }
-            }
-        }
-        for (int j = tid; j < len; j += 1024) guard_set(g_seen, h[j], a.V);
-        if (n > 0) {                              // every n-gram h[j .. j + n) of the history whose first n - 1 ids are the history's last n - 1 bans its last id
-            const int* last = h + len - (n - 1);  // (read only when an n-gram exists: j + n <= len)
-            for (int j = tid; j + n <= len; j += 1024) {
-                bool m = true;
-                for (int k = 0; k < n - 1; ++k) m = m && h[j + k] == last[k];
-                if (m) guard_set(g_ban, h[j + n - 1], a.V);
-            }
-        }
-        for (int j = tid; j < a.n_suppress; j += 1024) guard_set(g_ban, a.suppress[j], a.V);
-        __syncthreads();
-    }
-    // four strides per trip with all their slab loads issued first (the rolled form paid one L2 round trip per stride)
-    constexpr int U = 4;
-    for (int i0 = tid * 4; i0 < a.V; i0 += 1024 * 4 * U) {
-        f32x4 v[U], w[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int i = i0 + u * 4096, ic = i < a.V ? i : 0;
-            v[u] = *(const f32x4*)(lg + ic);
-            w[u] = *(const f32x4*)(lg + (a.ksplit > 1 ? ks_stride : 0) + ic);
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int i = i0 + u * 4096;
-            if (i >= a.V) break;
-            f32x4 t = v[u];
-            if (a.ksplit > 1) t += w[u];
-            for (int ks = 2; ks < a.ksplit; ++ks) t += *(const f32x4*)(lg + ks * ks_stride + i);
-            [[maybe_unused]] unsigned sb = 0u, bb = 0u;      // GUARD: the group's 4 bits of each map (i is a multiple of 4)
-            if constexpr (GUARD) { sb = g_seen[i >> 5] >> (i & 31); bb = g_ban[i >> 5] >> (i & 31); }
-            [[maybe_unused]] unsigned qb = 0u;               // BIAS: the group's 4 bits of the "biased" map
-            if constexpr (BIAS) qb = (g_bia[i >> 5] >> (i & 31)) & 15u;
-            [[maybe_unused]] float gz[4] = {0.f, 0.f, 0.f, 0.f};      // SAMPLE: the group's Gumbel values, one Philox call
-            if constexpr (SAMPLE) if (noisy) {
-                unsigned pw[4];
-                philox4x32_10((unsigned)i >> 2, step_n, 0u, 0u, k0, k1, pw);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { gz[j] = gumbel_of(pw[j]); if (noise) noise[i + j] = gz[j]; }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float r = rT<T>(t[j]);              // logits are T in the reference, compared as fp32
-                if (dump) dump[i + j] = r;
-                if constexpr (BIAS) if ((qb >> j) & 1u) r += bias_of(q_id, q_sum, q_n, i + j);      // HF's order: the bias first, the penalty sees the biased score
-                if constexpr (GUARD) r = guard_score(r, sb >> j, bb >> j, a.rep_penalty);
-                if constexpr (SAMPLE) {
-                    const float y = noisy ? __fdiv_rn(r, temp) + gz[j] : r;      // (-inf stays -inf: g is finite)
-                    if (y > best) { best = y; bi = i + j; }
-                    rmax = fmaxf(rmax, r);                                       // (t == 0: rmax == best, bit for bit)
-                } else {
-                    if (r > best) { best = r; bi = i + j; }   // strict > keeps the first maximum within a thread
-                }
-                if constexpr (LP) v[u][j] = r;
-            }
-        }
-        if constexpr (LP) {
-            // the trip's values against the maximum so far (`best` covers them): the old sum is rescaled once (exp2(0) = 1 and s * 1 are exact when
-            // the maximum did not move), then the terms are added in visiting order.  While nothing finite has been seen (the first trip, or trips
-            // of -inf logits only) the sum stays 0: -inf - -inf is not formed, here or in the terms (exp(-inf - finite) = 0 is fine)
-            lp_s = lp_m > -INFINITY ? lp_s * lp_exp(lp_m - LPB) : 0.f; lp_m = LPB;
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                if (i0 + u * 4096 >= a.V) break;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) lp_s += LPB > -INFINITY ? lp_exp(v[u][j] - LPB) : 0.f;
-            }
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
-    if constexpr (SAMPLE) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) rmax = fmaxf(rmax, __shfl_xor(rmax, o, 64));
-        if (lane == 0) ss_m[wid] = rmax;
-    }
-    if constexpr (LP) {
-        // every lane now holds the wave's maximum: bring the lane's sum to it (an empty lane is the identity: 0, not 0 * exp(-inf + inf)) and add
-        // across the wave; the butterfly gives every lane the same tree, and a + b = b + a bit for bit
-        lp_s = lp_m > -INFINITY ? lp_s * lp_exp(lp_m - LPB) : 0.f;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) lp_s += __shfl_xor(lp_s, o, 64);
-        if (lane == 0) ss_lp[wid] = lp_s;
-    }
-    if (lane == 0) { sv[wid] = best; si[wid] = bi; }
-    __syncthreads();
-    if (tid == 0) {
-        for (int w = 1; w < 16; ++w) if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
-        float lp_sum = 0.f;
-        if constexpr (LP) {
-            float q[16];                          // the 16 waves at the block's maximum (an empty wave: 0), added as a fixed binary tree
-            const float* wm = SAMPLE ? ss_m : sv; // the waves' maxima of the scores the sum ran over
-            if constexpr (SAMPLE) for (int w = 1; w < 16; ++w) rmax = fmaxf(rmax, ss_m[w]);
-#pragma unroll
-            for (int w = 0; w < 16; ++w) q[w] = wm[w] > -INFINITY ? ss_lp[w] * lp_exp(wm[w] - LPB) : 0.f;
-#pragma unroll
-            for (int h = 8; h > 0; h >>= 1)
-#pragma unroll
-                for (int w = 0; w < h; ++w) q[w] = q[2 * w] + q[2 * w + 1];
-            lp_sum = q[0];
-        }
-        if constexpr (GUARD || SAMPLE) if (bi == 0x7fffffff) bi = 0;      // every score -inf: the first of equal values
-        int tok = bi;
-        const int fin = a.finished[b];
-        bool running = false;
-        if (fin) tok = a.pad_id;                 // finished rows emit the pad token (:2928-2929)
-        else {
-            if (a.force_ids) tok = a.force_ids[(long)b * a.force_ld + a.n_new[b]];   // teacher forcing (parity tests): feed this id instead
-            a.out_ids[(long)b * a.out_ld + a.n_new[b]] = tok;
-            if constexpr (LP) {
-                float lt = LPB;                   // the emitted token's logit: the maximum, or under teacher forcing the forced id's value, summed
-                // from the slabs in the main loop's order (v + w, then ks = 2 ...): the bits of the dumped logit.  SAMPLE: a sampled token is rarely the maximum of s
-                if (SAMPLE ? (a.force_ids || noisy) && (unsigned)tok < (unsigned)a.V : a.force_ids != nullptr) {
-                    float f = lg[tok];
-                    if (a.ksplit > 1) f += lg[ks_stride + tok];
-                    for (int ks = 2; ks < a.ksplit; ++ks) f += lg[ks * ks_stride + tok];
-                    lt = rT<T>(f);
-                    if constexpr (BIAS) if ((g_bia[tok >> 5] >> (tok & 31)) & 1u) lt += bias_of(q_id, q_sum, q_n, tok);
-                    if constexpr (GUARD) lt = guard_score(lt, g_seen[tok >> 5] >> (tok & 31), g_ban[tok >> 5] >> (tok & 31), a.rep_penalty);
-                }
-                a.out_lp[(long)b * a.out_ld + a.n_new[b]] = (float)(((double)lt - (double)LPB) - log((double)lp_sum));
-            }
-            if constexpr (GUARD) { const int pos = a.kv_len[b]; if (pos >= 0 && pos < a.hist_ld) a.hist[(long)b * a.hist_ld + pos] = tok; }   // the token's position
-            const int nn = a.n_new[b] + 1;
-            a.n_new[b] = nn;
-            bool stop = nn >= a.max_new[b];
-            for (int e = 0; e < a.n_eos; ++e) stop |= (tok == a.eos[e]);
-            if (stop) { a.finished[b] = 1; atomicSub(a.n_active, 1); } else running = true;
-        }
-        // device error word (SkinnyArgs.err = n_active[1]): a kernel of this step gave up on an in-kernel wait, its outputs are garbage.  The count of
-        // running rows goes (and stays) far below zero: the loop stops at its next check and the host fails the batch (DEV_ERR_ACTIVE in engine_internal.h)
-        if (a.dev_err && b == 0 && *a.dev_err) atomicMin(a.n_active, -(1 << 24));
-        // Only a row that keeps running advances its context.  A finished row stays where it is (its later steps rewrite the same
-        // cache slot and are discarded), so kv_len never exceeds prompt + max_new - 1 < max_ctx whatever the other rows' budgets are:
-        // before, a [long prompt, small budget] row riding a [short prompt, large budget] batch walked past its cache region.
-        if (running) {
-            a.tok_pos[b] = a.kv_len[b];          // the new token sits right after the current context
-            a.kv_len[b] += 1;
-        }
-        s_tok = tok;
-        if (a.step_counter) a.step_counter[b] += 1;
-    }
-    __syncthreads();
-    const T* row = (const T*)a.table + (long)s_tok * a.d;
-    T* xo = (T*)a.x;
-    if (!a.y || (a.d >> 3) > 1024) {
-        for (int c = tid; c < (a.d >> 3); c += 1024) *(V8*)(xo + (long)b * a.d + c * 8) = *(const V8*)(row + c * 8);
-        return;
-    }
-    // next step's input row and, in the same pass, the first decoder layer's input RMSNorm of it (modeling_llama.py:60-65, :306):
-    // one launch less per token step
-    const int c = tid, nv = a.d >> 3;
-    V8 xv;
-    float ss = 0.f;
-    if (c < nv) {
-        xv = *(const V8*)(row + c * 8);
-        *(V8*)(xo + (long)b * a.d + c * 8) = xv;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { const float f = (float)xv[j]; ss += f * f; }
-    }
-    ss = wave_sum(ss);
-    __syncthreads();                         // sv is reused below
-    if (lane == 0) sv[wid] = ss;
-    __syncthreads();
-    float tot = 0.f;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) tot += sv[w];
-    const float r = 1.0f / sqrtf(tot / a.d + a.norm_eps);
-    float yo[8];
-    if (c < nv) {
-        V8 o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { o[j] = (T)((j < 4 ? gw0[j & 3] : gw1[j & 3]) * rT<T>((float)xv[j] * r)); yo[j] = (float)o[j]; }
-        *(V8*)((T*)a.y + (long)b * a.d + c * 8) = o;
-    }
-    if (a.qo.q) quant_emit_row(yo, c < nv, c, b, a.qo, sv, si);
-}
-#undef LPB
-
 // ---------------------------------------------------------------- misc
 // In-stream fill of small control words.  hipMemsetAsync of a few bytes was observed not to be reliably ordered against
 // the neighbouring kernels of a non-blocking stream (a stale per-segment log-mel maximum survived a reset on some runs);
@@ -939,66 +593,6 @@ void launch_rope_append(const RopeAppendArgs& a, bool slab, hipStream_t s) {
 }
 void launch_assemble_embeds(const int* src, const bf16_t* table, const bf16_t* audio, bf16_t* x, int n_tok, int d, hipStream_t s) {
     if (n_tok > 0) hipLaunchKernelGGL(assemble_embeds_kernel, dim3(n_tok), dim3(256), 0, s, src, table, audio, x, n_tok, d);
-}
-// a request's prompt ids into its history row (option generation guards): token t of the packed prompt plan is position tok_pos[t] of request
-// tok_seq[t]; audio positions (src < 0) hold the placeholder id, as in HF's input_ids
-__global__ void hist_prompt_kernel(const int* src, const int* tok_seq, const int* tok_pos, int n_tok, int audio_id, int* hist, int hist_ld) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_tok) return;
-    const int s = src[t], r = tok_seq[t], p = tok_pos[t];
-    if (r >= 0 && r < 64 && p >= 0 && p < hist_ld) hist[(long)r * hist_ld + p] = s >= 0 ? s : audio_id;
-}
-void launch_hist_prompt(const int* src, const int* tok_seq, const int* tok_pos, int n_tok, int audio_id, int* hist, int hist_ld, hipStream_t s) {
-    if (n_tok > 0) hipLaunchKernelGGL(hist_prompt_kernel, dim3((n_tok + 255) / 256), dim3(256), 0, s, src, tok_seq, tok_pos, n_tok, audio_id, hist, hist_ld);
-}
-size_t greedy_guard_lds(int V, bool bias) { return (size_t)(bias ? 3 : 2) * ((V + 31) / 32) * 4 + (bias ? (size_t)3 * BIAS_MAX_ENTRIES * 4 : 0); }
-void launch_greedy(const GreedyArgs& a, hipStream_t s) {
-    if (a.samp && a.out_lp) {                                                                                    // option sampling: the SAMPLE instantiations of the three LP families
-        if (a.hist && a.bias_tab) {
-            const size_t lds = greedy_guard_lds(a.V, true);
-            if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, true, true, true, true>), dim3(a.B), dim3(1024), lds, s, a); return; }
-            DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, true, true, true, true>), dim3(a.B), dim3(1024), lds, s, a));
-            return;
-        }
-        if (a.hist) {
-            const size_t lds = greedy_guard_lds(a.V);
-            if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, true, true, false, true>), dim3(a.B), dim3(1024), lds, s, a); return; }
-            DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, true, true, false, true>), dim3(a.B), dim3(1024), lds, s, a));
-            return;
-        }
-        if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, true, false, false, true>), dim3(a.B), dim3(1024), 0, s, a); return; }
-        DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, true, false, false, true>), dim3(a.B), dim3(1024), 0, s, a));
-        return;
-    }
-    if (a.hist && a.bias_tab) {                                                                                  // request bias: the BIAS instantiations (a third bitmap and the matched list)
-        const size_t lds = greedy_guard_lds(a.V, true);
-        if (a.out_lp) {
-            if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, true, true, true>), dim3(a.B), dim3(1024), lds, s, a); return; }
-            DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, true, true, true>), dim3(a.B), dim3(1024), lds, s, a));
-            return;
-        }
-        if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, false, true, true>), dim3(a.B), dim3(1024), lds, s, a); return; }
-        DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, false, true, true>), dim3(a.B), dim3(1024), lds, s, a));
-        return;
-    }
-    if (a.hist) {                                                                                                // generation guards: the GUARD instantiations, two bitmaps of dynamic LDS
-        const size_t lds = greedy_guard_lds(a.V);
-        if (a.out_lp) {
-            if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, true, true>), dim3(a.B), dim3(1024), lds, s, a); return; }
-            DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, true, true>), dim3(a.B), dim3(1024), lds, s, a));
-            return;
-        }
-        if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, false, true>), dim3(a.B), dim3(1024), lds, s, a); return; }
-        DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, false, true>), dim3(a.B), dim3(1024), lds, s, a));
-        return;
-    }
-    if (a.out_lp) {                                                                                              // token_logprobs: the LP instantiation
-        if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, true>), dim3(a.B), dim3(1024), 0, s, a); return; }
-        DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, true>), dim3(a.B), dim3(1024), 0, s, a));
-        return;
-    }
-    if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, false>), dim3(a.B), dim3(1024), 0, s, a); return; }   // SONIC_MODE_F32: fp32 logits, table and rows
-    DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, false>), dim3(a.B), dim3(1024), 0, s, a));
 }
 void launch_f32_to_bf16(const float* in, bf16_t* out, long n, hipStream_t s, int dt) {
     if (n > 0) DT_SWITCH(dt, T, hipLaunchKernelGGL(f32_to_t_kernel<T>, dim3((n + 255) / 256), dim3(256), 0, s, in, (T*)out, n));

@@ -394,22 +394,47 @@ int gen_busy(sonic_engine* e, const char* who) {
     }
     return SONIC_OK;
 }
+// ---- values left for the requests of the next prefill (ReqStage, engine_internal.h): what the options request_bias and sampling share.  A setter fills the pinned
+// mirror and leaves pending = R; the next prefill claims it (run_to_first_token), uploads it on the stream and marks the mirror busy until those copies are done; every
+// other way out of a consuming entry point drops it (ReqDrop).  The caller holds the lock.
+// The option's switch (the caller has asked gen_busy): on first use the zero-filled device words - every row starts neutral; `hist`: the rows' input_ids too - the
+// pinned mirror and the event.  `opt` names the option in the message
+template <typename W> static int stage_enable(sonic_engine* e, ReqStage<W>& s, int on, int* flag, const char* opt, int words, bool hist) {
+    HIPC(e, hipSetDevice(e->device));
+    HIPC(e, stream_sync(e));
+    if (on) {
+        if (hist && !e->hist) TRY(dalloc(e, &e->hist, (size_t)64 * e->max_ctx));
+        if (!s.dev) TRY(dalloc(e, &s.dev, (size_t)words));
+        if (!s.host && hipHostMalloc((void**)&s.host, (size_t)words * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(e, SONIC_ERR_OOM, "%s: pinned host memory exhausted", opt); }
+        if (!s.ev) HIPC(e, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+        HIPC(e, stream_sync(e));
+    }
+    *flag = on ? 1 : 0; s.pending = -1; s.take = false;
+    drop_graphs(e);                                      // the greedy kernel and its arguments are part of every captured chunk
+    return SONIC_OK;
+}
+// open the mirror for writing (the previous batch's copies out of it are awaited first); the upload's copies are on the stream; the destroy path
+template <typename W> static int stage_open(sonic_engine* e, ReqStage<W>& s) { if (s.busy) { HIPC(e, hipEventSynchronize(s.ev)); s.busy = false; } return SONIC_OK; }
+template <typename W> static int stage_sent(sonic_engine* e, ReqStage<W>& s) { HIPC(e, hipEventRecord(s.ev, e->st)); s.busy = true; s.take = false; return SONIC_OK; }
+template <typename W> static void stage_free(ReqStage<W>& s) { if (s.host) (void)hipHostFree(s.host); if (s.ev) (void)hipEventDestroy(s.ev); }
+int stage_count(sonic_engine* e, int got, int R, const char* setter, const char* what) {
+    return got >= 0 && got != R ? fail(e, SONIC_ERR_INVALID, "%s gave %s for %d requests, the batch has %d", setter, what, got, R) : SONIC_OK;
+}
+// What both setters open with: refused during an asynchronous run (without waiting for the engine lock that run holds), then the lock (`lk`), then refused while
+// the option `opt` (flag `on`) is off.  From here on nothing is pending
+template <typename W> static int stage_enter(sonic_engine* e, std::unique_lock<std::mutex>& lk, const char* who, const char* opt, const int& on, ReqStage<W>& s) {
+    { std::lock_guard<std::mutex> ak(e->a_mu); if (e->a_pending || e->a_running) return fail(nullptr, SONIC_ERR_INVALID, "%s: an asynchronous run of this handle is in flight", who); }
+    lk = std::unique_lock<std::mutex>(e->mu);
+    (void)hipGetLastError();
+    if (!on || !s.dev) return fail(e, SONIC_ERR_INVALID, "%s: option %s is off on this handle (sonic_set_option(e, \"%s\", 1) on the owner before its slots are created)", who, opt, opt);
+    s.pending = -1;
+    return SONIC_OK;
+}
 // ---- option request_bias: HF's SequenceBiasLogitsProcessor / NoBadWordsLogitsProcessor (generation/logits_process.py) with one table per request -
 // the reference's hotwords (backend/asr.py:303-333) as a bias on the scores instead of a sentence in the prompt.  The caller holds the lock and has asked gen_busy.
 int bias_enable(sonic_engine* e, int on) {
     if (on && greedy_guard_lds(e->d.vocab, true) > 60000) return fail(e, SONIC_ERR_UNSUPPORTED, "request_bias: a vocabulary of %d ids does not fit the bias bitmaps", e->d.vocab);
-    HIPC(e, hipSetDevice(e->device));
-    HIPC(e, stream_sync(e));
-    if (on) {
-        if (!e->hist) TRY(dalloc(e, &e->hist, (size_t)64 * e->max_ctx));
-        if (!e->bias_tab) TRY(dalloc(e, &e->bias_tab, (size_t)BIAS_TAB_WORDS));                      // (zero-filled: every row starts without a table)
-        if (!e->bias_h && hipHostMalloc((void**)&e->bias_h, (size_t)BIAS_TAB_WORDS * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(e, SONIC_ERR_OOM, "request_bias: pinned host memory exhausted"); }
-        if (!e->bias_ev) HIPC(e, hipEventCreateWithFlags(&e->bias_ev, hipEventDisableTiming));
-        HIPC(e, stream_sync(e));
-    }
-    e->opt_request_bias = on ? 1 : 0; e->bias_pending = -1; e->bias_take = false;
-    drop_graphs(e);                                      // the greedy kernel and its arguments are part of every captured chunk
-    return SONIC_OK;
+    return stage_enable(e, e->bias, on, &e->opt_request_bias, "request_bias", BIAS_TAB_WORDS, true);      // (zero-filled: every row starts without a table)
 }
 int bias_pack(sonic_engine* e, const char* who, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n, int V, int* row, int* count) {
     if (n < 0 || n > BIAS_MAX_ENTRIES) return fail(e, SONIC_ERR_INVALID, "%s: a request's table holds %d entries (at most %d; nothing is truncated)", who, n, BIAS_MAX_ENTRIES);
@@ -444,69 +469,53 @@ int bias_pack(sonic_engine* e, const char* who, const int32_t* seq_ids, const in
 // consumes them: a later batch starts without tables.  Request r's entries are seq_off[req_off[r]] .. seq_off[req_off[r + 1]] of seq_ids, with bias[req_off[r] ..].
 extern "C" int sonic_set_request_bias(sonic_engine* e, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, const int32_t* req_off, int R) {
     if (!e) return SONIC_ERR_INVALID;
-    { std::lock_guard<std::mutex> lk(e->a_mu); if (e->a_pending || e->a_running) return fail(nullptr, SONIC_ERR_INVALID, "sonic_set_request_bias: an asynchronous run of this handle is in flight"); }
-    std::lock_guard<std::mutex> lk(e->mu);
-    (void)hipGetLastError();
-    if (!e->opt_request_bias || !e->bias_tab)
-        return fail(e, SONIC_ERR_INVALID, "sonic_set_request_bias: option request_bias is off on this handle (sonic_set_option(e, \"request_bias\", 1) on the owner before its slots are created)");
-    e->bias_pending = -1;
+    std::unique_lock<std::mutex> lk; TRY(stage_enter(e, lk, "sonic_set_request_bias", "request_bias", e->opt_request_bias, e->bias));
     if (R < 1 || R > e->Bm || R > 64 || !req_off || req_off[0] != 0) return fail(e, SONIC_ERR_INVALID, "sonic_set_request_bias: %d requests (1 .. %d), offsets from 0", R, e->Bm);
     HIPC(e, hipSetDevice(e->device));
-    if (e->bias_ev_busy) { HIPC(e, hipEventSynchronize(e->bias_ev)); e->bias_ev_busy = false; }      // the previous batch's copies out of bias_h
-    for (int r = 0; r < 64; ++r) e->bias_h[r] = 0;
+    TRY(stage_open(e, e->bias));
+    for (int r = 0; r < 64; ++r) e->bias.host[r] = 0;
     for (int r = 0; r < R; ++r) {
         const int a = req_off[r], n = req_off[r + 1] - req_off[r];
         if (n < 0) return fail(e, SONIC_ERR_INVALID, "sonic_set_request_bias: request offsets decrease");
         if (n == 0) continue;
         if (!seq_off || !bias) return fail(e, SONIC_ERR_INVALID, "sonic_set_request_bias: null table");
-        TRY(bias_pack(e, "sonic_set_request_bias", seq_ids, seq_off + a, bias + a, n, e->d.vocab, e->bias_h + 64 + (size_t)r * BIAS_ROW_WORDS, &e->bias_h[r]));
+        TRY(bias_pack(e, "sonic_set_request_bias", seq_ids, seq_off + a, bias + a, n, e->d.vocab, e->bias.host + 64 + (size_t)r * BIAS_ROW_WORDS, &e->bias.host[r]));
     }
-    e->bias_pending = R;
+    e->bias.pending = R;
     return SONIC_OK;
 }
 int bias_upload(sonic_engine* e, int R) {
     if (!e->opt_request_bias) return SONIC_OK;
-    if (!e->bias_take && e->opt_bias_fill > 0) {
+    if (!e->bias.take && e->opt_bias_fill > 0) {
         // option request_bias_fill = n (drivers that only pass integers: bench.py --opt; tools/ab_request_bias.sh): every request of a batch without tables gets n
         // length-1 entries of bias +0.0 on ids spread over the vocabulary.  s + 0.0 changes no token, but the kernel does all its work for them: the prologue's
         // flags and group sums, n bits in the "biased" map, the list scan at every one of those ids
-        if (e->bias_ev_busy) { HIPC(e, hipEventSynchronize(e->bias_ev)); e->bias_ev_busy = false; }
+        TRY(stage_open(e, e->bias));
         const int n = e->opt_bias_fill, V = e->d.vocab;
-        for (int r = 0; r < 64; ++r) e->bias_h[r] = r < R ? n : 0;
+        for (int r = 0; r < 64; ++r) e->bias.host[r] = r < R ? n : 0;
         for (int r = 0; r < R; ++r)
             for (int k = 0; k < n; ++k) {
-                int* w = e->bias_h + 64 + (size_t)r * BIAS_ROW_WORDS + (size_t)k * BIAS_ENTRY_WORDS;
+                int* w = e->bias.host + 64 + (size_t)r * BIAS_ROW_WORDS + (size_t)k * BIAS_ENTRY_WORDS;
                 w[0] = (int)((long)k * V / n); w[1] = 1; w[2] = 0;
                 for (int j = 3; j < BIAS_ENTRY_WORDS; ++j) w[j] = -1;
             }
-        e->bias_take = true;
+        e->bias.take = true;
     }
-    if (!e->bias_take) { launch_fill_i32(e->bias_tab, 0, 64, e->st); return SONIC_OK; }             // a batch without tables: every count 0
-    HIPC(e, hipMemcpyAsync(e->bias_tab, e->bias_h, 64 * 4, hipMemcpyHostToDevice, e->st));
+    if (!e->bias.take) { launch_fill_i32(e->bias.dev, 0, 64, e->st); return SONIC_OK; }             // a batch without tables: every count 0
+    HIPC(e, hipMemcpyAsync(e->bias.dev, e->bias.host, 64 * 4, hipMemcpyHostToDevice, e->st));
     for (int r = 0; r < R; ++r) {
         const size_t o = 64 + (size_t)r * BIAS_ROW_WORDS;
-        if (e->bias_h[r] > 0) HIPC(e, hipMemcpyAsync(e->bias_tab + o, e->bias_h + o, (size_t)e->bias_h[r] * BIAS_ENTRY_WORDS * 4, hipMemcpyHostToDevice, e->st));
+        if (e->bias.host[r] > 0) HIPC(e, hipMemcpyAsync(e->bias.dev + o, e->bias.host + o, (size_t)e->bias.host[r] * BIAS_ENTRY_WORDS * 4, hipMemcpyHostToDevice, e->st));
     }
-    HIPC(e, hipEventRecord(e->bias_ev, e->st));
-    e->bias_ev_busy = true; e->bias_take = false;
-    return SONIC_OK;
+    return stage_sent(e, e->bias);
 }
 // ---- option sampling: temperature sampling in the greedy kernel by the Gumbel-max identity, one (temperature, seed) per request - what Whisper's
 // decode_with_fallback retries with.  The caller holds the lock and has asked gen_busy.
 int samp_enable(sonic_engine* e, int on) {
     if (on && !(e->opt_token_logprobs && e->out_lp)) return fail(e, SONIC_ERR_INVALID, "sampling: option token_logprobs must be on first (the sampling kernels are log-probability kernels; sonic_set_option(e, \"token_logprobs\", 1))");
-    HIPC(e, hipSetDevice(e->device));
-    HIPC(e, stream_sync(e));
-    if (on) {
-        if (!e->samp) TRY(dalloc(e, &e->samp, (size_t)SAMP_WORDS));                                   // (zero-filled: every row starts greedy)
-        if (!e->samp_h && hipHostMalloc((void**)&e->samp_h, (size_t)SAMP_WORDS * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(e, SONIC_ERR_OOM, "sampling: pinned host memory exhausted"); }
-        if (!e->samp_ev) HIPC(e, hipEventCreateWithFlags(&e->samp_ev, hipEventDisableTiming));
-        HIPC(e, stream_sync(e));
-    }
-    e->opt_sampling = on ? 1 : 0; e->samp_pending = -1; e->samp_take = false;
-    drop_graphs(e);                                      // the greedy kernel and its arguments are part of every captured chunk
-    return SONIC_OK;
+    return stage_enable(e, e->samp, on, &e->opt_sampling, "sampling", SAMP_WORDS, false);                  // (zero-filled: every row starts greedy)
 }
+void samp_pack(unsigned* w, float t, uint64_t seed) { memcpy(&w[0], &t, 4); w[1] = (unsigned)(seed & 0xffffffffull); w[2] = (unsigned)(seed >> 32); }
 int samp_check(sonic_engine* e, const char* who, const float* temperature, int n) {
     for (int r = 0; r < n; ++r) {
         const float t = temperature[r];
@@ -519,45 +528,35 @@ int samp_check(sonic_engine* e, const char* who, const float* temperature, int n
 // starts greedy.
 extern "C" int sonic_set_request_sampling(sonic_engine* e, const float* temperature, const uint64_t* seed, int R) {
     if (!e) return SONIC_ERR_INVALID;
-    { std::lock_guard<std::mutex> lk(e->a_mu); if (e->a_pending || e->a_running) return fail(nullptr, SONIC_ERR_INVALID, "sonic_set_request_sampling: an asynchronous run of this handle is in flight"); }
-    std::lock_guard<std::mutex> lk(e->mu);
-    (void)hipGetLastError();
-    if (!e->opt_sampling || !e->samp)
-        return fail(e, SONIC_ERR_INVALID, "sonic_set_request_sampling: option sampling is off on this handle (sonic_set_option(e, \"sampling\", 1) on the owner before its slots are created)");
-    e->samp_pending = -1;
+    std::unique_lock<std::mutex> lk; TRY(stage_enter(e, lk, "sonic_set_request_sampling", "sampling", e->opt_sampling, e->samp));
     if (R < 1 || R > e->Bm || R > 64 || !temperature || !seed) return fail(e, SONIC_ERR_INVALID, "sonic_set_request_sampling: %d requests (1 .. %d), values for each", R, e->Bm);
     TRY(samp_check(e, "sonic_set_request_sampling", temperature, R));
     HIPC(e, hipSetDevice(e->device));
-    if (e->samp_ev_busy) { HIPC(e, hipEventSynchronize(e->samp_ev)); e->samp_ev_busy = false; }      // the previous batch's copy out of samp_h
-    for (int i = 0; i < SAMP_WORDS; ++i) e->samp_h[i] = 0u;
-    for (int r = 0; r < R; ++r) {
-        memcpy(&e->samp_h[3 * r], &temperature[r], 4);
-        e->samp_h[3 * r + 1] = (unsigned)(seed[r] & 0xffffffffull); e->samp_h[3 * r + 2] = (unsigned)(seed[r] >> 32);
-    }
-    e->samp_pending = R;
+    TRY(stage_open(e, e->samp));
+    for (int i = 0; i < SAMP_WORDS; ++i) e->samp.host[i] = 0u;
+    for (int r = 0; r < R; ++r) samp_pack(e->samp.host + 3 * r, temperature[r], seed[r]);
+    e->samp.pending = R;
     return SONIC_OK;
 }
 int samp_upload(sonic_engine* e, int R) {
     if (!e->opt_sampling) return SONIC_OK;
-    if (!e->samp_take && e->opt_samp_fill_milli > 0) {
+    if (!e->samp.take && e->opt_samp_fill_milli > 0) {
         // option sampling_fill_milli = m (drivers that only pass integers: bench.py --opt; tools/ab_sampling.sh): request r of a batch without values gets temperature
         // m / 1000 and seed r.  A batch is then the same draw every time it runs, on whichever handle: a benchmark can still check its tokens
-        if (e->samp_ev_busy) { HIPC(e, hipEventSynchronize(e->samp_ev)); e->samp_ev_busy = false; }
+        TRY(stage_open(e, e->samp));
         const float t = (float)((double)e->opt_samp_fill_milli / 1000.0);
-        for (int i = 0; i < SAMP_WORDS; ++i) e->samp_h[i] = 0u;
-        for (int r = 0; r < R && r < 64; ++r) { memcpy(&e->samp_h[3 * r], &t, 4); e->samp_h[3 * r + 1] = (unsigned)r; }
-        e->samp_take = true;
+        for (int i = 0; i < SAMP_WORDS; ++i) e->samp.host[i] = 0u;
+        for (int r = 0; r < R && r < 64; ++r) samp_pack(e->samp.host + 3 * r, t, (uint64_t)r);
+        e->samp.take = true;
     }
-    if (!e->samp_take) { launch_fill_i32((int*)e->samp, 0, SAMP_WORDS, e->st); return SONIC_OK; }     // a batch without values: every row greedy
-    HIPC(e, hipMemcpyAsync(e->samp, e->samp_h, (size_t)SAMP_WORDS * 4, hipMemcpyHostToDevice, e->st));
-    HIPC(e, hipEventRecord(e->samp_ev, e->st));
-    e->samp_ev_busy = true; e->samp_take = false;
-    return SONIC_OK;
+    if (!e->samp.take) { launch_fill_i32((int*)e->samp.dev, 0, SAMP_WORDS, e->st); return SONIC_OK; } // a batch without values: every row greedy
+    HIPC(e, hipMemcpyAsync(e->samp.dev, e->samp.host, (size_t)SAMP_WORDS * 4, hipMemcpyHostToDevice, e->st));
+    return stage_sent(e, e->samp);
 }
-extern "C" int engine_sampling_on(sonic_engine* e) { return e && e->opt_sampling && e->samp ? 1 : 0; }
+extern "C" int engine_sampling_on(sonic_engine* e) { return e && e->opt_sampling && e->samp.dev ? 1 : 0; }
 extern "C" int engine_sampling_validate(float temperature) { return samp_check(nullptr, "sonic_dispatch_submit_sampled", &temperature, 1); }
 // dispatch.cpp (same library, not exported): is the option on for a handle; is one request's table well-formed for it (the message lands on the handle)
-extern "C" int engine_request_bias_on(sonic_engine* e) { return e && e->opt_request_bias && e->bias_tab ? 1 : 0; }
+extern "C" int engine_request_bias_on(sonic_engine* e) { return e && e->opt_request_bias && e->bias.dev ? 1 : 0; }
 // (the handle is only read for its vocabulary: the message goes to the calling thread's sonic_last_error(NULL), no lock is needed)
 extern "C" int engine_bias_validate(sonic_engine* e, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n) {
     if (!e) return SONIC_ERR_INVALID;
@@ -708,10 +707,7 @@ extern "C" void sonic_destroy(sonic_engine* e) {
     if (e->n_active_h) (void)hipHostFree(e->n_active_h);
     for (int i = 0; i < 2; ++i) { if (e->plan_buf[i]) (void)hipHostFree(e->plan_buf[i]); if (e->plan_ev[i]) (void)hipEventDestroy(e->plan_ev[i]); }
     if (e->svc_h) (void)hipHostFree(e->svc_h);
-    if (e->bias_h) (void)hipHostFree(e->bias_h);
-    if (e->bias_ev) (void)hipEventDestroy(e->bias_ev);
-    if (e->samp_h) (void)hipHostFree(e->samp_h);
-    if (e->samp_ev) (void)hipEventDestroy(e->samp_ev);
+    stage_free(e->bias); stage_free(e->samp);
     if (e->st_io) { (void)hipStreamSynchronize(e->st_io); (void)hipStreamDestroy(e->st_io); }
     if (e->xfer_ev) (void)hipEventDestroy(e->xfer_ev);
     if (e->splice_ev) (void)hipEventDestroy(e->splice_ev);

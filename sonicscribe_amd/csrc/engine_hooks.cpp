@@ -640,7 +640,7 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
     if (sp) {
         std::vector<unsigned> w((size_t)SAMP_WORDS, 0u);
         for (int b = 0; b < B; ++b) {
-            memcpy(&w[3 * b], &sp->temperature[b], 4); w[3 * b + 1] = (unsigned)(sp->seed[b] & 0xffffffffull); w[3 * b + 2] = (unsigned)(sp->seed[b] >> 32);
+            samp_pack(&w[3 * b], sp->temperature[b], sp->seed[b]);
             h[b] = sp->step[b]; h[64 * 4 + b] = sp->step[b] + 4;                 // n_new = step, max_new beyond it
         }
         gsamp = tb.get<unsigned>(w.size());

@@ -62,6 +62,14 @@ struct F32State {
 struct RsBank { float* dev = nullptr; int of = 0, nf = 0, width = 0, K = 0, tile = 0, kc = 0; };
 #define RS_BANK_MAX_COEF ((int64_t)1 << 22)
 
+// Values the caller leaves for the requests of the next prefill (options request_bias and sampling; the protocol is stage_* in engine.cpp).  dev: the rows'
+// words on the device, written by the prefill from the pinned mirror `host`, copied by the splice.  pending: the R of the values a setter left in `host` for the
+// next prefill (-1: none); take: that prefill is under way and uploads them.  ev / busy: the last upload's copies out of `host` are older than this event.
+template <typename W> struct ReqStage {
+    W* dev = nullptr; W* host = nullptr; hipEvent_t ev = nullptr; bool busy = false;
+    std::atomic<int> pending{-1}; bool take = false;
+    int claim() { take = false; return pending.exchange(-1); }      // run_to_first_token: this batch consumes what is pending whatever becomes of it
+};
 struct sonic_engine {
     sonic_dims d;
     int device = 0, mode = 0, Bm = 0, max_ctx = 0;
@@ -179,19 +187,14 @@ struct sonic_engine {
     // written by the prefill and the greedy kernel, copied by the splice; allocated with gen_suppress_d[256] by the first gen_apply that switches a guard on
     bool gen_on = false; float gen_penalty = 1.0f; int gen_ngram = 0; std::vector<int> gen_suppress;
     int* hist = nullptr; int* gen_suppress_d = nullptr;
-    // option request_bias (sonic_set_request_bias; greedy_kernel<T, LP, true, true>): every row's own sequence-bias table.  bias_tab[BIAS_TAB_WORDS] on the
-    // device (kernels.h), written by the prefill from the pinned bias_h, copied by the splice; allocated, with hist, by the option.  bias_pending: the R of the
-    // tables sonic_set_request_bias left in bias_h for the next prefill (-1: none); bias_take: that prefill is under way and uploads them
+    // option request_bias (sonic_set_request_bias; greedy_kernel<T, LP, true, true>): every row's own table, bias.dev[BIAS_TAB_WORDS] (kernels.h); allocated, with hist, by the option
     int opt_request_bias = 0;
     int opt_bias_fill = 0;         // measurement aid (option request_bias_fill, tools/ab_request_bias.sh): a prefill that was given no tables writes this many neutral entries per request
-    int* bias_tab = nullptr; int* bias_h = nullptr; hipEvent_t bias_ev = nullptr; bool bias_ev_busy = false;
-    std::atomic<int> bias_pending{-1}; bool bias_take = false;
-    // option sampling (sonic_set_request_sampling; greedy_kernel<T, true, ., ., true>): every row's temperature bits and seed words, samp[SAMP_WORDS]
-    // on the device (kernels.h), written by the prefill from the pinned samp_h, copied by the splice; allocated by the option.  samp_pending / samp_take: as bias_*
+    ReqStage<int> bias;
+    // option sampling (sonic_set_request_sampling; greedy_kernel<T, true, ., ., true>): every row's temperature bits and seed words, samp.dev[SAMP_WORDS] (kernels.h); allocated by the option
     int opt_sampling = 0;
     int opt_samp_fill_milli = 0;   // measurement aid (option sampling_fill_milli, tools/ab_sampling.sh): a prefill that was given no values decodes request r at this temperature (in thousandths) with seed r
-    unsigned* samp = nullptr; unsigned* samp_h = nullptr; hipEvent_t samp_ev = nullptr; bool samp_ev_busy = false;
-    std::atomic<int> samp_pending{-1}; bool samp_take = false;
+    ReqStage<unsigned> samp;
     uint64_t spliced = 0;          // rows of the last prefill that sonic_splice_rows handed to a continuous loop (bit r = request r); cleared by every prefill (gen_busy)
     long long* kt = nullptr; int kt_layer = -1;     // diagnostics ("ktrace" option): in-kernel timestamps of one decoder layer's kernels
     int* ring_peak = nullptr;                        // [Bm] per-request max |s| of a ring-staged batch (ingest.hip)
@@ -237,9 +240,9 @@ struct HostPlan {
 #define ENTER(e) std::lock_guard<std::mutex> lk((e)->mu); (void)hipGetLastError(); HIPC(e, hipSetDevice((e)->device)); g_opts = (e)->opts
 // ENTER for the entry points that consume the tables of sonic_set_request_bias (sonic_prefill*, sonic_run_staged, sonic_transcribe_*): whatever way the call
 // leaves - a staging error ahead of the prefill included - the pending tables are dropped, so they can never reach a later batch (the values of
-// sonic_set_request_sampling likewise)
-struct BiasConsume { sonic_engine* e; ~BiasConsume(); };
-#define ENTER_CONSUME(e) std::lock_guard<std::mutex> lk((e)->mu); BiasConsume bias_consume_{e}; (void)hipGetLastError(); HIPC(e, hipSetDevice((e)->device)); g_opts = (e)->opts
+// sonic_set_request_sampling likewise).  keep: sonic_run_staged_async accepted the run, whose prefill is now their consumer
+struct ReqDrop { sonic_engine* e; bool keep = false; ~ReqDrop() { if (!keep) { e->bias.pending = -1; e->samp.pending = -1; } } };
+#define ENTER_CONSUME(e) std::lock_guard<std::mutex> lk((e)->mu); ReqDrop req_drop_{e}; (void)hipGetLastError(); HIPC(e, hipSetDevice((e)->device)); g_opts = (e)->opts
 
 // ------------------------------------------------------------------------------------------ helpers (engine.cpp)
 int fail(sonic_engine* e, int code, const char* fmt, ...);
@@ -310,10 +313,11 @@ int bias_enable(sonic_engine* e, int on);           // option request_bias behin
 // one request's table as sonic_set_request_bias takes it -> its BIAS_ROW_WORDS device words, grouped and ordered as the kernel reads them; *count = its entries.
 // SONIC_ERR_INVALID (message on e, naming `who`) for more than BIAS_MAX_ENTRIES entries, a length outside 1 .. BIAS_MAX_LEN, an id outside [0, V), a NaN or +inf bias
 int bias_pack(sonic_engine* e, const char* who, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n, int V, int* row, int* count);
-int bias_upload(sonic_engine* e, int R);            // the prefill's part: the pending tables (or zero counts) into bias_tab, on the stream (engine.cpp)
-inline BiasConsume::~BiasConsume() { e->bias_pending = -1; e->samp_pending = -1; }
+int bias_upload(sonic_engine* e, int R);            // the prefill's part: the pending tables (or zero counts) into bias.dev, on the stream (engine.cpp)
+int stage_count(sonic_engine* e, int got, int R, const char* setter, const char* what);   // SONIC_ERR_INVALID when a claim (ReqStage::claim) was set for another count than the batch's (engine.cpp)
 int samp_enable(sonic_engine* e, int on);           // option sampling behind the lock and the busy check: the rows' words and their staging buffer on first use (engine.cpp)
 int samp_check(sonic_engine* e, const char* who, const float* temperature, int n);   // SONIC_ERR_INVALID (message on e, or the calling thread's for e = NULL) unless every value is 0 or in [1e-3, 100]
-int samp_upload(sonic_engine* e, int R);            // the prefill's part: the pending values (or zeros: greedy) into samp, on the stream (engine.cpp)
+int samp_upload(sonic_engine* e, int R);            // the prefill's part: the pending values (or zeros: greedy) into samp.dev, on the stream (engine.cpp)
+void samp_pack(unsigned* w, float t, uint64_t seed);   // one row's three words as the kernel reads them: the temperature's bits, the seed's low and high word (engine.cpp)
 static inline bool hist_on(const sonic_engine* e) { return e->gen_on || e->opt_request_bias; }   // the rows' input_ids are kept: a guard or the request bias reads them
 int lp_check(sonic_engine* e, const char* who);     // SONIC_ERR_INVALID naming the option when token_logprobs is off on this handle

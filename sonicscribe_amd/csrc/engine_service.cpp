@@ -129,9 +129,9 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
     // (either way round: a row whose first token was chosen with guards must not go on without them, nor the reverse)
     if (d->gen_on != p->gen_on || (d->gen_on && !(p->hist && d->hist && p->gen_penalty == d->gen_penalty && p->gen_ngram == d->gen_ngram && p->gen_suppress == d->gen_suppress)))
         return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in their generation guards (sonic_set_generation): set them on the owner before its slots are created");
-    if (d->opt_request_bias != p->opt_request_bias || (d->opt_request_bias && !(p->bias_tab && d->bias_tab && p->hist && d->hist)))
+    if (d->opt_request_bias != p->opt_request_bias || (d->opt_request_bias && !(p->bias.dev && d->bias.dev && p->hist && d->hist)))
         return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in option request_bias: set it on the owner before its slots are created");
-    if (d->opt_sampling != p->opt_sampling || (d->opt_sampling && !(p->samp && d->samp)))
+    if (d->opt_sampling != p->opt_sampling || (d->opt_sampling && !(p->samp.dev && d->samp.dev)))
         return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in option sampling: set it on the owner before its slots are created");
     if (n < 1 || n > 64 || p->greedy_calls < 1 || n > p->R) return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: %d rows, the source has %d prefilled requests", n, p->greedy_calls < 1 ? 0 : p->R);
     SpliceArgs a{};
@@ -147,8 +147,8 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
     a.sx_s = p->sx; a.shn_s = p->shn; a.sx_d = d->sx; a.shn_d = d->shn; a.D = dm.dec_d;
     if (d->opt_token_logprobs && d->out_lp) { a.lp_s = p->out_lp; a.lp_d = d->out_lp; }
     if (hist_on(d)) { a.hist_s = p->hist; a.hist_d = d->hist; }
-    if (d->opt_request_bias) { a.bias_s = p->bias_tab; a.bias_d = d->bias_tab; }
-    if (d->opt_sampling) { a.samp_s = p->samp; a.samp_d = d->samp; }
+    if (d->opt_request_bias) { a.bias_s = p->bias.dev; a.bias_d = d->bias.dev; }
+    if (d->opt_sampling) { a.samp_s = p->samp.dev; a.samp_d = d->samp.dev; }
     if (d->i8) { a.hq_s = p->hn_q; a.hq_d = d->hn_q; a.sca_s = p->sca_hn; a.sca_d = d->sca_hn; a.oc_s = p->oc_hn; a.oc_d = d->oc_hn; a.ol_s = p->ol_hn; a.ol_d = d->ol_hn; a.ov_s = p->ov_hn; a.ov_d = d->ov_hn; }
     HIPC(d, hipEventRecord(p->xfer_ev, p->st));
     HIPC(d, hipStreamWaitEvent(d->st, p->xfer_ev, 0));
@@ -312,7 +312,7 @@ extern "C" int sonic_run_staged_async(sonic_engine* e, const int32_t* req_win, i
                                       const int32_t* max_new, int want_step_logits) {
     if (!e) return SONIC_ERR_INVALID;
     // (a refusal below drops the tables of sonic_set_request_bias: this call was their consumer; an accepted run consumes them in its prefill)
-    struct Drop { sonic_engine* e; bool keep = false; ~Drop() { if (!keep) { e->bias_pending = -1; e->samp_pending = -1; } } } drop{e};
+    ReqDrop drop{e};
     if (!prompt_ids || !prompt_off || !max_new || R < 1 || R > 64) return SONIC_ERR_INVALID;
     std::lock_guard<std::mutex> lk(e->a_mu);
     if (e->a_stop) return SONIC_ERR_INVALID;

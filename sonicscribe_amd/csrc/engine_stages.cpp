@@ -218,8 +218,8 @@ GreedyArgs greedy_args(sonic_engine* e, int R, bool dump) {
     g.dt = e->dt;
     // (request bias without guards: the guard values are the neutral ones - r * 1.0 and __fdiv_rn(r, 1.0) are exact, n = 0, no suppress list)
     if (hist_on(e)) { g.hist = e->hist; g.hist_ld = e->max_ctx; g.rep_penalty = e->gen_penalty; g.ngram = e->gen_ngram; g.suppress = e->gen_suppress_d; g.n_suppress = (int)e->gen_suppress.size(); }
-    if (e->opt_request_bias) g.bias_tab = e->bias_tab;
-    if (e->opt_sampling && g.out_lp) g.samp = e->samp;      // (the option is refused without token_logprobs, and token_logprobs cannot leave while it is on)
+    if (e->opt_request_bias) g.bias_tab = e->bias.dev;
+    if (e->opt_sampling && g.out_lp) g.samp = e->samp.dev;      // (the option is refused without token_logprobs, and token_logprobs cannot leave while it is on)
     if (e->i8) g.qo = QuantOut{e->hn_q, d.dec_d, e->sca_hn, e->oc_hn, e->ol_hn, d.dec_d, e->ov_hn};     // layer 0's q/k/v input, quantised
     return g;
 }
@@ -513,15 +513,12 @@ int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int
         HIPC(e, hipStreamWaitEvent(e->st, e->wait_ev, 0));  // engine's KV cache and row state, which this run is about to overwrite
         e->wait_pending = false;
     }
-    const int bias_R = e->bias_pending.exchange(-1);        // sonic_set_request_bias: this batch consumes the tables whatever becomes of it (the entry points that
-    e->bias_take = false;                                   // lead here drop them on every other exit too: ENTER_CONSUME)
-    const int samp_R = e->samp_pending.exchange(-1);        // sonic_set_request_sampling: the same rule
-    e->samp_take = false;
-    if (bias_R >= 0 && bias_R != R) return fail(e, SONIC_ERR_INVALID, "sonic_set_request_bias gave tables for %d requests, the batch has %d", bias_R, R);
-    if (samp_R >= 0 && samp_R != R) return fail(e, SONIC_ERR_INVALID, "sonic_set_request_sampling gave values for %d requests, the batch has %d", samp_R, R);
+    const int bias_R = e->bias.claim(), samp_R = e->samp.claim();      // sonic_set_request_bias / _sampling: this batch consumes what they left whatever becomes of it (ENTER_CONSUME drops it on every other exit)
+    TRY(stage_count(e, bias_R, R, "sonic_set_request_bias", "tables"));
+    TRY(stage_count(e, samp_R, R, "sonic_set_request_sampling", "values"));
     HostPlan hp;
     TRY(plan_requests(e, req_win, R, prompt_ids, prompt_off, max_new, hp));
-    e->bias_take = bias_R >= 0; e->samp_take = samp_R >= 0;
+    e->bias.take = bias_R >= 0; e->samp.take = samp_R >= 0;
     {   // staging buffer of this run: the one used two runs ago; its copies are almost always long done (a blocking wait otherwise)
         const int i = e->plan_idx ^ 1;
         if (e->plan_busy[i]) { HIPC(e, hipEventSynchronize(e->plan_ev[i])); e->plan_busy[i] = false; }

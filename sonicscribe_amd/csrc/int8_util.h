@@ -1,4 +1,4 @@
-// LLM.int8 device helpers shared by the decode-step consumers (elementwise.hip, attn.hip) and the int8 GEMM epilogues (gemm_i8.hip).
+// LLM.int8 device helpers shared by the decode-step consumers (elementwise.hip, greedy.hip, attn.hip) and the int8 GEMM epilogues (gemm_i8.hip).
 // Spec: oracle/sonic_oracle.c linear_int8 (bitsandbytes Linear8bitLt, threshold 6.0, asr.py:182-198).
 #pragma once
 #include "common.h"
@@ -166,6 +166,52 @@ __device__ __forceinline__ OutlStage outl_scan_commit(const DeqInfo& q, int row,
         __syncthreads();
     }
     return o;
+}
+
+// ---- producers: a row leaves quantised for the next Linear8bitLt (add_rmsnorm / swiglu_quant / quant_rows in elementwise.hip, the greedy tail in greedy.hip)
+// A block that owns one whole row (thread c holds its elements [8c, 8c+8) as fp16 values in y, threads with !active hold nothing)
+// emits the row quantised: absmax without the elements >= 6.0, int8 = rn(y * 127 / absmax) (0 for outliers), and the ascending
+// list of the outlier positions.  Every thread of the block must call it.  s_f: >= 16 floats, s_i: >= 17 ints of LDS scratch.
+// FRESH: nobody has touched s_f / s_i in this kernel before (no barrier needed in front of the first write).
+template <bool FRESH = false>
+__device__ __forceinline__ void quant_emit_row(const float (&y)[8], bool active, int c, int row, const QuantOut& qo, float* s_f, int* s_i) {
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, nw = (blockDim.x + 63) >> 6;
+    float amax = -1.17549435e-38f;
+    int cnt = 0;
+    if (active) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float a = fabsf(y[j]); if (a < LLM_INT8_THRESHOLD) amax = fmaxf(amax, a); else ++cnt; }
+    }
+    amax = wave_max(amax);
+    int incl = cnt;                                   // inclusive scan of the outlier counts inside the wave (only where the wave holds any)
+    if (__ballot(cnt > 0)) {
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o, 64); if (lane >= o) incl += t; }
+    }
+    if constexpr (!FRESH) __syncthreads();           // scratch may still be in use by the caller
+    if (lane == 63) s_i[wid] = incl;
+    if (lane == 0) s_f[wid] = amax;
+    __syncthreads();
+    float bm = s_f[0]; int base = 0, total = 0;
+    for (int w = 0; w < nw; ++w) { bm = fmaxf(bm, s_f[w]); if (w < wid) base += s_i[w]; total += s_i[w]; }
+    const float scale = 127.0f / bm;
+    if (tid == 0) { qo.sca[row] = bm; qo.oc_cnt[row] = total; }
+    if (active) {
+        int pos = base + incl - cnt;
+        int pk[2] = {0, 0};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const bool out = !(fabsf(y[j]) < LLM_INT8_THRESHOLD);
+            int qv = (out || !(bm > 0.f)) ? 0 : (int)rintf(y[j] * scale);
+            pk[j >> 2] |= (qv & 0xFF) << ((j & 3) * 8);
+            if (out) {
+                const long at = (long)row * qo.oc_ld + pos++;
+                qo.oc_list[at] = c * 8 + j;
+                if (qo.oc_val) qo.oc_val[at] = y[j];
+            }
+        }
+        *(int2*)(qo.q + (long)row * qo.ldq + c * 8) = make_int2(pk[0], pk[1]);
+    }
 }
 
 // outlier i of the row: from LDS, or (lists longer than OUTL_CAP) from memory

@@ -1,4 +1,4 @@
-// Launch descriptors and host-callable launchers of the HIP kernels (attn.hip, elementwise.hip, logmel.hip).
+// Launch descriptors and host-callable launchers of the HIP kernels (attn.hip, elementwise.hip, greedy.hip, logmel.hip).
 #pragma once
 #include "common.h"
 

@@ -3,7 +3,7 @@
 //   skinny_kernel  partial[ks][M<=64][N] = X . W^T over a K slice  -- decode-step weight streaming (K10/K11)
 //
 // Three kernels (the one-shot register kernel, its bench-only read floor, the shared-X kernel), then the pickers that choose
-// a tiling per shape, then the launchers, ending in launch_skinny.  The slabs are summed by the consumer (elementwise.hip);
+// a tiling per shape, then the launchers, ending in launch_skinny.  The slabs are summed by the consumer (elementwise.hip, greedy.hip);
 // the fused RMSNorm / SwiGLU / residual forms of the same step are in skinny_fused.hip.
 #include <type_traits>
 
@@ -223,7 +223,7 @@ __global__ __launch_bounds__(512) void skinny_xs_kernel(SkinnyArgs a) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
     if constexpr (XQ) {
-        // quantise (elementwise.hip quant_emit_row's arithmetic) and park in the image: byte (row m, element k) of a 128-element k-block at
+        // quantise (int8_util.h quant_emit_row's arithmetic) and park in the image: byte (row m, element k) of a 128-element k-block at
         // kblock * KBS + m * 128 + ((chunk ^ (m & 7)) << 4) + k % 16
 #pragma unroll
         for (int p = 0; p < XP; ++p) {

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B: the generation guards (sonic_set_generation: repetition_penalty, no_repeat_ngram_size and suppress_tokens inside greedy_kernel<T, LP, true>,
-# csrc/elementwise.hip) against the default engine.  `python bench.py` without and with all three guards on, alternating, on one MI355X;
+# csrc/greedy.hip) against the default engine.  `python bench.py` without and with all three guards on, alternating, on one MI355X;
 # the headline (segments/s) and ms_per_step of every run go to profiles/generation_guards_ab.txt.  Arguments are handed to bench.py
 # (e.g. --gpus 1 --steps 20 --warmup 3).
 #   AB_PARENT=<dir>  a built checkout of the parent commit: its `python bench.py` runs first in every repetition, as the control of "off did not move"

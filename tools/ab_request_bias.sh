@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B: option request_bias (greedy_kernel<T, LP, true, true>, csrc/elementwise.hip) against the default engine.  `python bench.py` for the parent
+# A/B: option request_bias (greedy_kernel<T, LP, true, true>, csrc/greedy.hip) against the default engine.  `python bench.py` for the parent
 # commit, this tree untouched and this tree with --opt request_bias=1, back to back on one MI355X; the headline (segments/s) and ms_per_step of every run go
 # to profiles/request_bias_ab.txt.  Arguments are handed to bench.py (e.g. --gpus 1 --no-extras --no-cpu-baseline).
 #   AB_PARENT=<dir>  a built checkout of the parent commit: its `python bench.py` runs first in every repetition, as the control of "off did not move"

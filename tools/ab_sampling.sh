@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B: option sampling (greedy_kernel<T, true, ., ., true>, csrc/elementwise.hip) against the default engine.  `python bench.py` for the parent
+# A/B: option sampling (greedy_kernel<T, true, ., ., true>, csrc/greedy.hip) against the default engine.  `python bench.py` for the parent
 # commit and this tree untouched (the headline: the bulk pipeline), then this tree through a non-bulk scheduler (--pipeline off: batches in flight on slots)
 # with log-probabilities only, with the sampling kernels at temperature 0 and with them at temperature 0.6, back to back on one MI355X; the headline
 # (segments/s) and ms_per_step of every run go to profiles/sampling_ab.txt.  Arguments are handed to bench.py (e.g. --gpus 1 --no-extras --no-cpu-baseline).

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B: per-token log-probabilities (option token_logprobs: greedy_kernel<T, true> in every decode step, csrc/elementwise.hip) against the
+# A/B: per-token log-probabilities (option token_logprobs: greedy_kernel<T, true> in every decode step, csrc/greedy.hip) against the
 # default engine.  `python bench.py` with and without `--opt token_logprobs=1`, alternating, two repetitions on one MI355X; the headline (segments/s)
 # and ms_per_step of every run go to profiles/token_logprobs_ab.txt.  Arguments are handed to bench.py (e.g. --gpus 1 --steps 20 --warmup 3).
 # The first run that fails - a non-zero status of bench.py, its time limit, or a result line that does not parse - ends the script: nothing more is
