@@ -1,79 +1,15 @@
-// sonic_hip engine: stage entry points, kernel test and bench hooks, experiment knobs (sonic_set_option) and debug read-back.
+// sonic_hip engine: the kernel test hooks (sonic_test_*) and bench hooks (sonic_bench_*) of the C ABI, and the temporary device buffers they work in.
 #include "engine_internal.h"
 
-// [B][n_mels][n_frames] fp32 (HF layout) -> frame-major bf16 with one zero row each side
-template <typename T> __global__ void feats_to_fm_kernel(const float* in, T* out, int n_mels, int n_frames) {
-    const int b = blockIdx.y;
-    const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (long)n_mels * n_frames) return;
-    const int t = e / n_mels, m = e % n_mels;
-    out[((long)b * (n_frames + 2) + 1 + t) * n_mels + m] = (T)in[((long)b * n_mels + m) * n_frames + t];   // asr.py:280-301: cast to the model dtype
+static void fill_words(int* p, int value, size_t n, hipStream_t st) {      // n words of `value`, in launches of at most 2^30 words
+    while (n > 0) { const int c = n > (1u << 30) ? (1 << 30) : (int)n; launch_fill_i32(p, value, c, st); p += c; n -= c; }
 }
-
-// ------------------------------------------------------------------------------------------ C ABI: stage entry points
-extern "C" int sonic_logmel(sonic_engine* e, const int16_t* pcm, const int64_t* offsets, int B, float* feats_out, int32_t* mask_out) {
-    if (!e) return SONIC_ERR_INVALID;
-    ENTER(e);
-    TRY(stage_pcm_locked(e, pcm, offsets, B));
-    TRY(run_mel(e, B, feats_out != nullptr));
-    HIPC(e, stream_sync(e));
-    HIPC(e, hipGetLastError());
-    const sonic_dims& d = e->d;
-    if (feats_out) HIPC(e, d2h(e, feats_out, e->feats_f32, (size_t)B * d.n_mels * d.n_frames * 4));
-    if (mask_out)
-        for (int b = 0; b < B; ++b) {
-            const int v = frames_of(e->n_samples_h[b]);
-            for (int t = 0; t < d.n_frames; ++t) mask_out[(size_t)b * d.n_frames + t] = t < v ? 1 : 0;   // attention_mask[:, ::160]
-        }
-    return SONIC_OK;
-}
-
-extern "C" int sonic_encode(sonic_engine* e, const float* feats, const int32_t* n_valid_frames, int B,
-                            float* embeds_out, int32_t* n_audio_out, float* enc_layers_out, float* enc_out) {
-    if (!e || !feats || !n_valid_frames) return SONIC_ERR_INVALID;
-    ENTER(e);
-    if (!e->finalized) return fail(e, SONIC_ERR_INVALID, "weights not finalized");
-    if (B < 1 || B > e->Bm) return fail(e, SONIC_ERR_INVALID, "batch out of range");
-    const sonic_dims& d = e->d;
-    const size_t n = (size_t)B * d.n_mels * d.n_frames;
-    if (e->f32) {
-        if (!e->feats_f32) HIPC(e, hipMalloc((void**)&e->feats_f32, (size_t)e->Bm * d.n_mels * d.n_frames * 4));
-        HIPC(e, h2d(e, e->feats_f32, feats, n * 4));
-        TRY(f32_run_encoder(e, B, enc_layers_out, enc_out));
-        HIPC(e, stream_sync(e)); HIPC(e, hipGetLastError());
-        if (embeds_out) HIPC(e, d2h(e, embeds_out, e->f->pe, (size_t)B * e->Ta * d.dec_d * 4));
-        if (n_audio_out) for (int b = 0; b < B; ++b) n_audio_out[b] = keep_rows(d, n_valid_frames[b]);
-        return SONIC_OK;
-    }
-    float* tmp = nullptr;
-    HIPC(e, hipMalloc((void**)&tmp, n * 4));
-    hipError_t r = h2d(e, tmp, feats, n * 4);
-    if (r != hipSuccess) { (void)hipFree(tmp); HIPC(e, r); }
-    const long per = (long)d.n_mels * d.n_frames;
-    DT_SWITCH(e->dt, T, hipLaunchKernelGGL(feats_to_fm_kernel<T>, dim3((per + 255) / 256, B), dim3(256), 0, e->st, tmp, (T*)e->feats_fm, d.n_mels, d.n_frames));
-    if (e->i8) HIPC(e, hipMemcpyAsync(e->win_req, e->seq_iota, (size_t)B * 4, hipMemcpyDeviceToDevice, e->st));   // every window its own request
-    int s = run_encoder(e, B, enc_layers_out, enc_out, B);
-    hipError_t r2 = stream_sync(e);
-    (void)hipFree(tmp);
-    TRY(s); HIPC(e, r2); HIPC(e, hipGetLastError());
-    if (embeds_out) {
-        float* t2 = nullptr;
-        const size_t m = (size_t)B * e->Ta * d.dec_d;
-        HIPC(e, hipMalloc((void**)&t2, m * 4));
-        launch_bf16_to_f32(e->pe, t2, (long)m, e->st, e->dt);
-        hipError_t r3 = stream_sync(e);
-        if (r3 == hipSuccess) r3 = d2h(e, embeds_out, t2, m * 4);
-        (void)hipFree(t2);
-        HIPC(e, r3);
-    }
-    if (n_audio_out) for (int b = 0; b < B; ++b) n_audio_out[b] = keep_rows(d, n_valid_frames[b]);
-    return SONIC_OK;
-}
-
-// ------------------------------------------------------------------------------------------ C ABI: kernel test hooks
+// The device buffers of one hook call, freed when it returns.  bad(): an allocation (get) or an upload (up_bf16 / up_f32) of this call has failed; every hook asks
+// once, before its first launch on the buffers, instead of testing each pointer.
 struct TmpBuf {
     std::vector<void*> v;
     hipStream_t st;
+    bool failed = false; bool bad() const { return failed; }
     explicit TmpBuf(hipStream_t s) : st(s) {}
     ~TmpBuf() { for (void* p : v) (void)hipFree(p); }
     // Zero-fill with a KERNEL on the engine stream.  hipMemsetAsync on this non-blocking stream was seen not to be reliably ordered
@@ -83,9 +19,8 @@ struct TmpBuf {
     template <typename Tt> Tt* get(size_t n) {
         void* p = nullptr;
         const size_t bytes = (((n ? n : 1) * sizeof(Tt)) + 3) / 4 * 4;
-        if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-        size_t left = bytes / 4; int* q = (int*)p;
-        while (left > 0) { const int c = left > (1u << 30) ? (1 << 30) : (int)left; launch_fill_i32(q, 0, c, st); q += c; left -= c; }
+        if (hipMalloc(&p, bytes) != hipSuccess) { failed = true; return nullptr; }
+        fill_words((int*)p, 0, bytes / 4, st);
         (void)hipStreamSynchronize(st);
         v.push_back(p);
         return (Tt*)p;
@@ -94,13 +29,13 @@ struct TmpBuf {
 static bf16_t* up_bf16(sonic_engine* e, TmpBuf& tb, const float* h, size_t n, size_t pad = 0) {
     float* f = tb.get<float>(n); bf16_t* b = tb.get<bf16_t>(n + pad);
     if (!f || !b) return nullptr;
-    if (h2d(e, f, h, n * 4) != hipSuccess) return nullptr;
+    if (h2d(e, f, h, n * 4) != hipSuccess) { tb.failed = true; return nullptr; }
     launch_f32_to_bf16(f, b, (long)n, e->st, e->dt);     // the engine's element type: bf16, or fp16 on an int8-mode engine
     return b;
 }
 static float* up_f32(sonic_engine* e, TmpBuf& tb, const float* h, size_t n) {
     float* f = tb.get<float>(n);
-    if (f && h2d(e, f, h, n * 4) != hipSuccess) return nullptr;
+    if (f && h2d(e, f, h, n * 4) != hipSuccess) { tb.failed = true; return nullptr; }
     return f;
 }
 static int down_bf16(sonic_engine* e, TmpBuf& tb, const bf16_t* d, float* h, size_t n) {
@@ -112,7 +47,9 @@ static int down_bf16(sonic_engine* e, TmpBuf& tb, const bf16_t* d, float* h, siz
     HIPC(e, d2h(e, h, f, n * 4));
     return SONIC_OK;
 }
+int read_back_16(sonic_engine* e, const bf16_t* d, float* h, size_t n) { TmpBuf tb(e->st); return down_bf16(e, tb, d, h, n); }
 
+// ------------------------------------------------------------------------------------------ C ABI: kernel test hooks
 extern "C" int sonic_test_gemm(sonic_engine* e, const float* A, const float* W, const float* bias, const float* resid, float* C,
                                int M, int N, int K, int epi) {
     if (!e) return SONIC_ERR_INVALID;
@@ -124,7 +61,7 @@ extern "C" int sonic_test_gemm(sonic_engine* e, const float* A, const float* W, 
     float* db = bias ? up_f32(e, tb, bias, N) : nullptr;
     bf16_t* dR = resid ? up_bf16(e, tb, resid, (size_t)M * Nout) : nullptr;
     bf16_t* dC = tb.get<bf16_t>((size_t)M * Nout);
-    if (!dA || !dW || !dC) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     gemm(e, epi, dA, K, dW, db, dC, Nout, M, N, K, dR, Nout);
     return down_bf16(e, tb, dC, C, (size_t)M * Nout);
 }
@@ -138,7 +75,7 @@ extern "C" int sonic_test_skinny(sonic_engine* e, const float* X, const float* W
     bf16_t* dWt = tb.get<bf16_t>((size_t)N * K);
     const int ks = skinny_pick_ksplit(N, K), mpad = ((M + 15) / 16) * 16;
     float* P = tb.get<float>((size_t)ks * mpad * N);
-    if (!dX || !dW || !dWt || !P) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     launch_tile_weights(dW, dWt, N, K, e->st);
     SkinnyArgs a{}; a.X = dX; a.ldx = K; a.W = dWt; a.P = P; a.M = M; a.N = N; a.K = K; a.ksplit = ks; a.dt = e->dt;
     launch_skinny(a, e->st);
@@ -175,7 +112,7 @@ extern "C" int sonic_test_attention(sonic_engine* e, const float* q, const float
     bf16_t* dv = up_bf16(e, tb, v, (size_t)B * Tk * Hkv * hd);
     bf16_t* dvt = tb.get<bf16_t>((size_t)B * Hkv * hd * Tkp);
     bf16_t* dO = tb.get<bf16_t>((size_t)B * Tq * Hq * hd);
-    if (!dq || !dk || !dv || !dvt || !dO) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     const long nv = (long)B * Tk * Hkv * hd;
     hipLaunchKernelGGL(test_transpose_v_kernel, dim3((nv + 255) / 256), dim3(256), 0, e->st, dv, dvt, B, Tk, Hkv, hd, Tkp);
     FlashArgs f{};
@@ -207,7 +144,7 @@ extern "C" int sonic_test_decode_attention(sonic_engine* e, const float* q, cons
     }
     bf16_t* dq = up_bf16(e, tb, q, (size_t)B * Hq * hd); bf16_t* dk = up_bf16(e, tb, kc.data(), kc.size()); bf16_t* dv = up_bf16(e, tb, vc.data(), vc.size());
     bf16_t* dO = tb.get<bf16_t>((size_t)B * Hq * hd); int* kl = tb.get<int>(B);
-    if (!dq || !dk || !dv || !dO || !kl) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     std::vector<int> l(B, Tk); HIPC(e, h2d(e, kl, l.data(), B * 4));
     DecodeAttnArgs a{}; a.Q = dq; a.P = nullptr; a.Kc = dk; a.Vc = dv; a.O = dO; a.kv_len = kl; a.Hq = Hq; a.Hkv = Hkv; a.ctx_max = ctx; a.scale = 1.0f / sqrtf(128.f); a.dt = e->dt;
     launch_decode_attn(a, B, e->st);
@@ -234,7 +171,7 @@ extern "C" int sonic_test_decode_attention_cache(sonic_engine* e, const float* q
     float* dP = slabs ? up_f32(e, tb, slabs, (size_t)ksplit * mpad * N) : nullptr;
     float* dcs = slabs ? up_f32(e, tb, rope_cs, (size_t)ctx_max * hd) : nullptr;
     bf16_t* dO = tb.get<bf16_t>(no); int* kl = tb.get<int>(B);
-    if (!dk || !dv || !dO || !kl || (q && !dq) || (slabs && (!dP || !dcs))) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     HIPC(e, h2d(e, kl, kv_len, (size_t)B * 4));
     DecodeAttnArgs a{};
     a.Q = dq; a.P = dP; a.ksplit = ksplit; a.mpad = mpad; a.cs = dcs; a.Kc = dk; a.Vc = dv; a.O = dO; a.kv_len = kl; a.Hq = Hq; a.Hkv = Hkv; a.ctx_max = ctx_max;
@@ -265,7 +202,7 @@ extern "C" int sonic_test_prefill_attention(sonic_engine* e, const float* q, con
     const size_t nq = (size_t)n_tok * Hq * hd, nc = (size_t)B * Hkv * ctx_max * hd;
     bf16_t* dq = up_bf16(e, tb, q, nq); bf16_t* dk = up_bf16(e, tb, kcache, nc); bf16_t* dvt = up_bf16(e, tb, vt, nc); bf16_t* dO = up_bf16(e, tb, out, nq);
     int* di = tb.get<int>((size_t)3 * B);
-    if (!dq || !dk || !dvt || !dO || !di) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     HIPC(e, h2d(e, di, q_off, (size_t)B * 4)); HIPC(e, h2d(e, di + B, q_len, (size_t)B * 4)); HIPC(e, h2d(e, di + 2 * B, kv_len, (size_t)B * 4));
     FlashArgs f{}; f.dt = e->dt;
     f.Q = dq; f.q_ld = (long)Hq * hd; f.K = dk; f.k_ld = hd; f.Vt = dvt; f.vt_ld = ctx_max; f.O = dO; f.o_ld = (long)Hq * hd;
@@ -284,10 +221,24 @@ extern "C" int sonic_test_layernorm(sonic_engine* e, const float* x, const float
     TmpBuf tb(e->st);
     bf16_t* dx = up_bf16(e, tb, x, (size_t)rows * d); float* dw = up_f32(e, tb, w, d); float* db = b ? up_f32(e, tb, b, d) : nullptr;
     bf16_t* dy = tb.get<bf16_t>((size_t)rows * d);
-    if (!dx || !dw || !dy) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     if (rms) launch_rmsnorm(dx, dw, dy, rows, d, eps, nullptr, e->st, e->dt);
     else launch_layernorm(dx, dw, db, dy, rows, d, eps, e->st, e->dt);
     return down_bf16(e, tb, dy, y, (size_t)rows * d);
+}
+
+// `iters` launches between two events -> *ms for all of them.  g_opts goes back to the engine's own before the checks: sonic_bench_skinny runs a variant of its own
+template <typename F> static int time_launches(sonic_engine* e, int iters, F launch, float* ms) {
+    hipEvent_t ea, eb; HIPC(e, hipEventCreate(&ea)); HIPC(e, hipEventCreate(&eb));
+    (void)hipEventRecord(ea, e->st);
+    for (int i = 0; i < iters; ++i) launch(i);
+    (void)hipEventRecord(eb, e->st);
+    hipError_t r = stream_sync(e);
+    *ms = 0; (void)hipEventElapsedTime(ms, ea, eb);
+    (void)hipEventDestroy(ea); (void)hipEventDestroy(eb);
+    g_opts = e->opts;
+    HIPC(e, r); HIPC(e, hipGetLastError());
+    return SONIC_OK;
 }
 
 extern "C" int sonic_bench_gemm(sonic_engine* e, int M, int N, int K, int epi, int iters, float* ms_per_launch) {
@@ -305,7 +256,7 @@ extern "C" int sonic_bench_gemm(sonic_engine* e, int M, int N, int K, int epi, i
         dVt = tb.get<bf16_t>((size_t)(M / 1500) * (N / 3) * 1536);
         a.Vt = dVt; a.n_split = 2 * N / 3; a.seg_T = 1500; a.vt_ld = 1536; a.vt_seg_stride = (long)(N / 3) * 1536;
     }
-    if (!dA || !dW || !dC || !db || (epi == EPI_QKV_VT && !dVt)) return fail(e, SONIC_ERR_OOM, "HIP out of memory in gemm bench");
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in gemm bench");
     // random (not zero) operands: zero data reads high on this chip (cdna_hip_programming.md rule 25)
     launch_synth_fill(0x1234, (long)M * K, 1.0f, 0.f, dA, nullptr, e->st);
     launch_synth_fill(0x5678, (long)N * K, 0.05f, 0.f, dW, nullptr, e->st);
@@ -342,14 +293,8 @@ extern "C" int sonic_bench_gemm(sonic_engine* e, int M, int N, int K, int epi, i
             }
         }
     }
-    hipEvent_t ea, eb; HIPC(e, hipEventCreate(&ea)); HIPC(e, hipEventCreate(&eb));
-    (void)hipEventRecord(ea, e->st);
-    for (int i = 0; i < iters; ++i) launch_gemm(a, epi, e->st);
-    (void)hipEventRecord(eb, e->st);
-    hipError_t r = stream_sync(e);
-    float ms = 0; (void)hipEventElapsedTime(&ms, ea, eb);
-    (void)hipEventDestroy(ea); (void)hipEventDestroy(eb);
-    HIPC(e, r); HIPC(e, hipGetLastError());
+    float ms;
+    TRY(time_launches(e, iters, [&](int) { launch_gemm(a, epi, e->st); }, &ms));
     *ms_per_launch = ms / iters;
     return SONIC_OK;
 }
@@ -365,176 +310,16 @@ extern "C" int sonic_bench_skinny(sonic_engine* e, int M, int N, int K, int vari
     bf16_t* dW = tb.get<bf16_t>((size_t)copies * N * K); bf16_t* dX = tb.get<bf16_t>((size_t)64 * K);
     const int ks = skinny_pick_ksplit(N, K), mpad = ((M + 15) / 16) * 16;
     float* P = tb.get<float>((size_t)ks * mpad * N);
-    if (!dW || !dX || !P) return fail(e, SONIC_ERR_OOM, "HIP out of memory in skinny bench");
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in skinny bench");
     launch_synth_fill(0x77, (long)copies * N * K, 0.05f, 0.f, dW, nullptr, e->st);
     launch_synth_fill(0x78, (long)64 * K, 1.0f, 0.f, dX, nullptr, e->st);
     SkinnyArgs a{}; a.X = dX; a.ldx = K; a.P = P; a.M = M; a.N = N; a.K = K; a.ksplit = ks; a.dt = e->dt;
     for (int i = 0; i < copies; ++i) { a.W = dW + (size_t)(i % copies) * N * K; launch_skinny(a, e->st); }
-    hipEvent_t ea, eb; HIPC(e, hipEventCreate(&ea)); HIPC(e, hipEventCreate(&eb));
-    (void)hipEventRecord(ea, e->st);
-    for (int i = 0; i < iters; ++i) { a.W = dW + (size_t)(i % copies) * N * K; launch_skinny(a, e->st); }
-    (void)hipEventRecord(eb, e->st);
-    hipError_t r = stream_sync(e);
-    float ms = 0; (void)hipEventElapsedTime(&ms, ea, eb);
-    (void)hipEventDestroy(ea); (void)hipEventDestroy(eb);
-    g_opts = e->opts;
-    HIPC(e, r); HIPC(e, hipGetLastError());
+    float ms;
+    TRY(time_launches(e, iters, [&](int i) { a.W = dW + (size_t)(i % copies) * N * K; launch_skinny(a, e->st); }, &ms));
     *us_per_launch = ms * 1e3f / iters;
     return SONIC_OK;
 }
-// The experiment knobs of sonic_set_option, one row each: the key, where the value lives (a member of the engine, or of its LaunchOpts - common.h
-// describes those), whether the captured decode graphs of the engine are dropped (the knob changes the captured kernels), and the clamp of the value.
-struct OptRow { const char* key; int sonic_engine::* field; int LaunchOpts::* lfield; bool drop_graphs; int (*clamp)(int); };
-#define ENG(m) &sonic_engine::m, nullptr
-#define LOP(m) nullptr, &LaunchOpts::m
-static const OptRow OPTIONS[] = {
-    {"skinny_variant", LOP(skinny_variant), true, nullptr},
-    {"gemm_force128", LOP(gemm_force128), false, nullptr},
-    {"no_fused_gu", LOP(no_fused_gu), true, nullptr},
-    {"no_fused_gu64", LOP(no_fused_gu64), true, nullptr},
-    {"gu64_two_pass", LOP(gu64_two_pass), true, nullptr},
-    {"gu64_split_norm", LOP(gu64_split_norm), true, nullptr},
-    {"ktrace_wave", LOP(ktrace_wave), true, nullptr},
-    {"no_skinny768", LOP(no_skinny768), true, nullptr},
-    {"no_skinny48", LOP(no_skinny48), true, nullptr},
-    {"o64_16rows", LOP(o64_16rows), true, nullptr},
-    {"i8_no_lnq", ENG(opt_i8_no_lnq), false, nullptr},              // int8 encoder: LayerNorm does not quantise its rows (A/B)
-    {"i8_no_qkv_fuse", ENG(opt_i8_no_qkv_fuse), false, nullptr},    // int8 encoder: RoPE and V^T as their own passes (A/B)
-    {"i8_dbg", ENG(opt_i8_dbg), true, nullptr},                     // timing experiments (wrong results)
-    {"i8_no_xq", ENG(opt_i8_no_xq), true, nullptr},
-    {"gemm_small_eff", LOP(gemm_small_eff), false, nullptr},
-    {"gemm128_shallow", LOP(gemm128_shallow), false, nullptr},
-    {"no_skinny_i8_wide", LOP(no_skinny_i8_wide), true, nullptr},
-    {"gemm256_stagger", LOP(gemm256_stagger), false, nullptr},
-    {"flash_variant", LOP(flash_variant), false, nullptr},
-    {"flash_enc", LOP(flash_enc), false, nullptr},                  // 0: rounds 1-4's encoder attention; v > 0: flash_enc_kernel mode v - 1
-    {"gemm256_persist", LOP(gemm256_persist), false, nullptr},
-    {"gemm256_persist_cus", LOP(gemm256_persist_cus), false, [](int v) { return v > 0 ? v : 256; }},
-    {"gemm256_gm", LOP(gemm256_gm), false, [](int v) { return v > 0 ? v : 8; }},   // raster group height of the 256x256 GEMM (experiments)
-    {"i8_defer_thr", ENG(opt_i8_defer_thr), false, nullptr},        // int8: outlier lists longer than this go to the dense side product (-1: never)
-    {"decode_prefetch", LOP(decode_prefetch), true, nullptr},       // idle-CU weight prefetch (experiment)
-    {"decode_attn_occ2", LOP(decode_attn_occ2), true, nullptr},     // decode attention at 128 VGPRs (two blocks per CU can co-reside; A/B)
-    {"decode_attn_v1", LOP(decode_attn_v1), true, nullptr},         // round 2's VALU P.V decode attention (A/B)
-    {"prefill_taps", ENG(taps_on), false, nullptr},
-    {"no_pre_norm", ENG(opt_no_pre_norm), true, nullptr},           // <= 2 rows: standalone add+RMSNorm launches as for more rows (A/B, same bits)
-    {"decode_gemv", ENG(opt_decode_gemv), true, nullptr},
-    {"f32_synth_bf16", ENG(opt_f32_synth_bf16), false, nullptr},
-    {"no_graph", ENG(opt_no_graph), false, nullptr},                // eager decode loop (debugging)
-    {"decode_lookahead", ENG(lookahead), false, [](int v) { return v < 1 ? 1 : (v > CHK_MAX_AHEAD ? CHK_MAX_AHEAD : v); }},   // start value (it adapts)
-    {"decode_chunk", ENG(opt_decode_chunk), false, [](int v) { return v > 0 ? (v > 64 ? 64 : v) : 1; }},   // token steps per graph launch / early-stop check
-    {"token_logprobs", ENG(opt_token_logprobs), true, [](int v) { return v ? 1 : 0; }},   // per-token log-probabilities beside the ids (greedy_kernel<T, true>); out_lp is allocated below
-    {"prefill_rowmajor", ENG(opt_prefill_rowmajor), false, nullptr},   // prefill GEMMs read the row-major decoder weights (kept only under SONIC_KEEP_ROWMAJOR=1; A/B)
-    {"no_rope_tiles", ENG(opt_no_rope_tiles), false, nullptr},      // prefill RoPE + KV append per token (rounds 1-4) instead of per 16-position tile (A/B)
-    {"gemm_trace", ENG(opt_gemm_trace), false, nullptr},            // sonic_bench_gemm prints an in-kernel timeline of one launch to stderr
-    {"gemm_timing", ENG(opt_gemm_timing), false, nullptr},          // HIP events around every encoder-layer GEMM launch
-    {"no_fused_rope", ENG(opt_no_fused_rope), false, nullptr},      // encoder RoPE as its own pass (A/B against the fused epilogue)
-    {"no_gelu_lut", ENG(opt_no_gelu_lut), false, nullptr},          // GELU by arithmetic instead of the LDS table (A/B)
-};
-#undef ENG
-#undef LOP
-void drop_graphs(sonic_engine* e) { for (auto& g : e->graphs) (void)hipGraphExecDestroy(g.second); e->graphs.clear(); }
-extern "C" int sonic_set_option(sonic_engine* e, const char* key, int value) {
-    if (!e || !key) return SONIC_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
-    // knobs live in the engine: two engines in one process do not see each other's settings; captured decode graphs of THIS engine
-    // are dropped whenever a knob that changes the captured kernels moves
-    for (const OptRow& r : OPTIONS) {
-        if (strcmp(key, r.key)) continue;
-        const int v = r.clamp ? r.clamp(value) : value;
-        if (r.field == &sonic_engine::opt_token_logprobs && !v && e->opt_sampling) return fail(e, SONIC_ERR_INVALID, "token_logprobs cannot be switched off while option sampling is on (its kernels are log-probability kernels)");
-        if (r.field) e->*r.field = v; else e->opts.*r.lfield = v;
-        if (r.drop_graphs) drop_graphs(e);
-        if (r.field == &sonic_engine::opt_token_logprobs && v) TRY(lp_alloc(e));      // first use: 64 x out_cap fp32
-        return SONIC_OK;
-    }
-    // the generation guards one integer at a time, for drivers that only speak key = value (bench.py --opt; tools/ab_generation_guards.sh): the penalty in
-    // thousandths, the n-gram size, ONE suppressed id (-1: none).  Same rules and refusals as sonic_set_generation; the other two values stay as they are
-    if (!strncmp(key, "gen_", 4)) {
-        float p = e->gen_penalty; int n = e->gen_ngram; std::vector<int> sup = e->gen_suppress;
-        if (!strcmp(key, "gen_repetition_penalty_milli")) p = (float)((double)value / 1000.0);
-        else if (!strcmp(key, "gen_no_repeat_ngram_size")) n = value;
-        else if (!strcmp(key, "gen_suppress_token")) { sup.clear(); if (value >= 0) sup.push_back(value); }
-        else return fail(e, SONIC_ERR_INVALID, "unknown option %s", key);
-        TRY(gen_busy(e, key));
-        return gen_apply(e, p, n, sup.data(), (int)sup.size());
-    }
-    // temperature sampling (sonic_set_request_sampling): on the owner before its slots are created (they copy it), after token_logprobs (refused by
-    // name otherwise); allocates the rows' (temperature, seed) words.  Refused while the handle has work in hand, by sonic_set_generation's rule
-    if (!strcmp(key, "sampling")) {
-        TRY(gen_busy(e, key));
-        return samp_enable(e, value ? 1 : 0);
-    }
-    if (!strcmp(key, "sampling_fill_milli")) {    // measurement aid (samp_upload, engine.cpp): 0 (off) or 1 .. 100000 thousandths, for every request without values
-        if (value != 0 && (value < 1 || value > 100000)) return fail(e, SONIC_ERR_INVALID, "sampling_fill_milli: %d is outside 0, 1 .. 100000", value);
-        TRY(gen_busy(e, key));
-        e->opt_samp_fill_milli = value;
-        return SONIC_OK;
-    }
-    // per-request sequence bias (sonic_set_request_bias): on the owner before its slots are created (they copy it); allocates the rows' history, if the
-    // guards have not, and their tables.  Refused while the handle has work in hand, by sonic_set_generation's rule
-    if (!strcmp(key, "request_bias")) {
-        TRY(gen_busy(e, key));
-        return bias_enable(e, value ? 1 : 0);
-    }
-    if (!strcmp(key, "request_bias_fill")) {      // measurement aid (bias_upload, engine.cpp): 0 .. min(256, vocabulary) neutral entries for every request without a table
-        if (value < 0 || value > BIAS_MAX_ENTRIES || value > e->d.vocab) return fail(e, SONIC_ERR_INVALID, "request_bias_fill: %d is outside 0 .. %d", value, BIAS_MAX_ENTRIES);
-        TRY(gen_busy(e, key));
-        e->opt_bias_fill = value;
-        return SONIC_OK;
-    }
-    // the two knobs that do device work
-    if (!strcmp(key, "ktrace")) {              // diagnostics: record in-kernel timestamps of decoder layer `value` (-1: off); sonic_debug_ktrace reads them
-        HIPC(e, hipSetDevice(e->device));
-        if (value >= 0 && !e->kt) { TRY(dalloc(e, &e->kt, (size_t)8 * KT_SLOT_BLOCKS * 8)); }
-        if (e->kt) zero_fill(e, e->kt, (size_t)8 * KT_SLOT_BLOCKS * 8 * 8);
-        e->kt_layer = value; drop_graphs(e); return SONIC_OK;
-    }
-    if (!strcmp(key, "inject_dev_err")) {      // tests: set (1) / clear (0) the device error word a decode kernel raises when it gives up on an in-kernel wait
-        HIPC(e, hipSetDevice(e->device));
-        const int v = value ? 1 : 0;
-        HIPC(e, hipMemcpyAsync(e->n_active + 1, &v, 4, hipMemcpyHostToDevice, e->st));
-        HIPC(e, stream_sync(e));
-        return SONIC_OK;
-    }
-    return fail(e, SONIC_ERR_INVALID, "unknown option %s", key);
-}
-
-// Debug read-back of an internal activation buffer as fp32 (tests / diagnostics only).
-extern "C" int sonic_debug_read(sonic_engine* e, const char* name, int index, float* out, int64_t n) {
-    if (!e || !name || !out) return SONIC_ERR_INVALID;
-    ENTER(e);
-    const sonic_dims& d = e->d;
-    if (e->f32) {                                  // fp32 kind: its buffers are fp32 already
-        const float* s32 = nullptr; size_t cap32 = 0;
-        if (!strcmp(name, "prefill_tap")) { if (!e->taps) return fail(e, SONIC_ERR_INVALID, "no taps recorded"); s32 = (const float*)e->taps + (size_t)index * e->tok_cap * d.dec_d; cap32 = (size_t)e->tok_cap * d.dec_d; }
-        else if (!strcmp(name, "pe")) { s32 = e->f->pe; cap32 = (size_t)e->Bm * e->Ta * d.dec_d; }
-        else if (!strcmp(name, "dx")) { s32 = e->f->dx; cap32 = (size_t)e->tok_cap * d.dec_d; }
-        else if (!strcmp(name, "enc_x")) { s32 = e->f->ln; cap32 = (size_t)e->Bm * e->T * d.enc_d; }
-        else if (!strcmp(name, "h1")) { s32 = e->f->h1; cap32 = (size_t)e->Bm * (d.n_frames + 2) * d.enc_d; }
-        else return fail(e, SONIC_ERR_INVALID, "unknown buffer %s", name);
-        if (n < 0 || (size_t)n > cap32) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
-        HIPC(e, stream_sync(e));
-        HIPC(e, d2h(e, out, s32, (size_t)n * 4));
-        return SONIC_OK;
-    }
-    const bf16_t* src = nullptr; size_t cap = 0;
-    if (!strcmp(name, "prefill_tap")) { if (!e->taps) return fail(e, SONIC_ERR_INVALID, "no taps recorded"); src = e->taps + (size_t)index * e->tok_cap * d.dec_d; cap = (size_t)e->tok_cap * d.dec_d; }
-    else if (!strcmp(name, "pe")) { src = e->pe; cap = (size_t)e->Bm * e->Ta * d.dec_d; }
-    else if (!strcmp(name, "dx")) { src = e->dx; cap = (size_t)e->tok_cap * d.dec_d; }
-    else if (!strcmp(name, "dqkv")) { src = e->dqkv; cap = (size_t)e->tok_cap * e->qkvN; }
-    else if (!strcmp(name, "dq")) { src = e->dq; cap = (size_t)e->tok_cap * e->QD; }
-    else if (!strcmp(name, "datt")) { src = e->datt; cap = (size_t)e->tok_cap * e->QD; }
-    else if (!strcmp(name, "dact")) { src = e->dact; cap = (size_t)e->tok_cap * d.dec_ff; }
-    else if (!strcmp(name, "enc_x")) { src = e->ln; cap = (size_t)e->Bm * e->T * d.enc_d; }
-    else if (!strcmp(name, "shn")) { src = e->shn; cap = (size_t)64 * d.dec_d; }          // decode-step buffers as the last step left them
-    else if (!strcmp(name, "satt")) { src = e->satt; cap = (size_t)64 * e->QD; }
-    else if (!strcmp(name, "sact")) { src = e->sact; cap = (size_t)64 * d.dec_ff; }
-    else return fail(e, SONIC_ERR_INVALID, "unknown buffer %s", name);
-    if (n < 0 || (size_t)n > cap) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
-    TmpBuf tb(e->st);
-    return down_bf16(e, tb, src, out, (size_t)n);
-}
-
 // One Linear8bitLt (LLM.int8, threshold 6.0) through the engine's kernels: W [N][K] is quantised row-wise on the device, X [M][K] is
 // cut into groups of `group_rows` rows (one group = one reference call: its outlier columns are found over its rows), then the int8
 // MFMA GEMM with the dequantising epilogue `epi` (EPI_BIAS / _GELU / _RESID / _SWIGLU).  Inputs are fp32 holding fp16 values.
@@ -553,11 +338,11 @@ extern "C" int sonic_test_linear_int8(sonic_engine* e, const float* X, const flo
     bf16_t* dC = tb.get<bf16_t>((size_t)M * Nout);
     int8_t* cb = tb.get<int8_t>((size_t)N * K); float* scb = tb.get<float>(N);
     int8_t* qa = tb.get<int8_t>((size_t)M * K + 4096); float* sca = tb.get<float>(M);
-    if (!dX || !dW || !dC || !cb || !scb || !qa || !sca) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     launch_quant_weights(dW, cb, scb, N, K, e->st);
     QW q; q.cb = cb; q.scb = scb;
     unsigned char* fl = tb.get<unsigned char>((size_t)64 * K + 64); int* occ = tb.get<int>(64); int* ocl = tb.get<int>((size_t)64 * K);
-    if (!fl || !occ || !ocl) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     // the engine's own scratch is sized for its model, not for this test: swap in buffers of the test's shape for the call
     int8_t* s_qa = e->qa; float* s_sca = e->q_sca; unsigned char* s_fl = e->q_flags; int *s_occ = e->q_oc_cnt, *s_ocl = e->q_oc_list; const int s_k = e->q_kmax;
     e->qa = qa; e->q_sca = sca; e->q_flags = fl; e->q_oc_cnt = occ; e->q_oc_list = ocl; e->q_kmax = K;
@@ -596,7 +381,7 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
     float* dump = logits_out ? tb.get<float>((size_t)B * V) : nullptr;
     float* lp = lp_out ? tb.get<float>((size_t)64 * old) : nullptr;
     int* fd = force_ids ? tb.get<int>((size_t)64 * old) : nullptr;
-    if (!dl || !table || !x || !st || !ids || (logits_out && !dump) || (lp_out && !lp) || (force_ids && !fd)) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     std::vector<int> h(64 * 8 + 4, 0);
     for (int b = 0; b < 64; ++b) { h[64 * 2 + b] = 1; h[64 * 4 + b] = 4; }       // kv_len = 1, max_new = 4
     h[64 * 8] = B;
@@ -618,7 +403,7 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
         }
         for (int i = 0; i < gt->n_suppress; ++i) if (gt->suppress[i] < 0 || gt->suppress[i] >= V) return fail(e, SONIC_ERR_INVALID, "suppressed id %d out of vocabulary", gt->suppress[i]);
         ghist = tb.get<int>(hh.size()); gsup = tb.get<int>(256);
-        if (!ghist || !gsup) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+        if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
         HIPC(e, h2d(e, ghist, hh.data(), hh.size() * 4));
         if (gt->n_suppress > 0) HIPC(e, h2d(e, gsup, gt->suppress, (size_t)gt->n_suppress * 4));
     }
@@ -633,7 +418,7 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
             if (n > 0) TRY(bias_pack(e, "sonic_test_greedy_bias", gt->seq_ids, gt->seq_off + a, gt->seq_bias + a, n, V, tab.data() + 64 + (size_t)b * BIAS_ROW_WORDS, &tab[b]));
         }
         gbias = tb.get<int>(tab.size());
-        if (!gbias) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+        if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
         HIPC(e, h2d(e, gbias, tab.data(), tab.size() * 4));
     }
     unsigned* gsamp = nullptr; float* gnoise = nullptr;
@@ -645,7 +430,7 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
         }
         gsamp = tb.get<unsigned>(w.size());
         if (sp->noise_out) gnoise = tb.get<float>((size_t)B * V);
-        if (!gsamp || (sp->noise_out && !gnoise)) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+        if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
         HIPC(e, h2d(e, gsamp, w.data(), w.size() * 4));
     }
     HIPC(e, h2d(e, st, h.data(), h.size() * 4));
@@ -705,8 +490,7 @@ extern "C" int sonic_test_greedy_bias(sonic_engine* e, const float* slabs, int k
                                       int32_t* tok_out, float* logits_out, float* lp_out) {
     if (!e || !slabs || !tok_out || !hist_len || !req_off) return SONIC_ERR_INVALID;
     ENTER(e);
-    GuardTest gt{hist, hist_ld, hist_len, repetition_penalty, no_repeat_ngram_size, suppress, n_suppress};
-    gt.bias = true; gt.seq_ids = seq_ids; gt.seq_off = seq_off; gt.seq_bias = bias; gt.req_off = req_off;
+    const GuardTest gt{hist, hist_ld, hist_len, repetition_penalty, no_repeat_ngram_size, suppress, n_suppress, req_off != nullptr, seq_ids, seq_off, bias, req_off};      // tables: a bias test
     return test_greedy(e, slabs, ksplit, mpad, V, B, force_ids, tok_out, logits_out, lp_out, &gt);
 }
 
@@ -721,8 +505,7 @@ extern "C" int sonic_test_greedy_sample(sonic_engine* e, const float* slabs, int
     if (req_off && !hist_len) return fail(e, SONIC_ERR_INVALID, "sonic_test_greedy_sample: tables need the histories");
     const SampTest sp{temperature, seed, step, noise_out};
     if (!hist_len) return test_greedy(e, slabs, ksplit, mpad, V, B, force_ids, tok_out, logits_out, lp_out, nullptr, &sp);
-    GuardTest gt{hist, hist_ld, hist_len, repetition_penalty, no_repeat_ngram_size, suppress, n_suppress};
-    if (req_off) { gt.bias = true; gt.seq_ids = seq_ids; gt.seq_off = seq_off; gt.seq_bias = bias; gt.req_off = req_off; }
+    const GuardTest gt{hist, hist_ld, hist_len, repetition_penalty, no_repeat_ngram_size, suppress, n_suppress, req_off != nullptr, seq_ids, seq_off, bias, req_off};      // tables: a bias test
     return test_greedy(e, slabs, ksplit, mpad, V, B, force_ids, tok_out, logits_out, lp_out, &gt, &sp);
 }
 
@@ -733,7 +516,7 @@ extern "C" int sonic_test_skinny_gu(sonic_engine* e, const float* X, const float
     TmpBuf tb(e->st);
     bf16_t* dX = up_bf16(e, tb, X, (size_t)M * K); bf16_t* dW = up_bf16(e, tb, Wgu_interleaved, (size_t)N * K);
     bf16_t* dWt = tb.get<bf16_t>((size_t)N * K); bf16_t* dA = tb.get<bf16_t>((size_t)M * (N / 2));
-    if (!dX || !dW || !dWt || !dA) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     launch_tile_weights_gu8(dW, dWt, N, K, e->st);
     SkinnyArgs a{}; a.X = dX; a.ldx = K; a.W = dWt; a.M = M; a.N = N; a.K = K; a.ksplit = 1; a.dt = e->dt;
     launch_skinny_gu(a, dA, e->st);
@@ -749,9 +532,8 @@ struct QuantHost { int8_t* q; float* sca; int32_t* oc_cnt; int32_t* oc_list; flo
 static int quant_alloc(sonic_engine* e, TmpBuf& tb, int rows, int K, QuantOut* qo) {
     qo->q = tb.get<int8_t>((size_t)rows * K); qo->ldq = K; qo->sca = tb.get<float>(rows); qo->oc_cnt = tb.get<int>(rows);
     qo->oc_list = tb.get<int>((size_t)rows * K); qo->oc_ld = K; qo->oc_val = tb.get<float>((size_t)rows * K);
-    if (!qo->q || !qo->sca || !qo->oc_cnt || !qo->oc_list || !qo->oc_val) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
-    size_t left = (size_t)rows * K; int* p = qo->oc_list;
-    while (left > 0) { const int c = left > (1u << 30) ? (1 << 30) : (int)left; launch_fill_i32(p, -1, c, e->st); p += c; left -= c; }
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    fill_words(qo->oc_list, -1, (size_t)rows * K, e->st);
     return SONIC_OK;
 }
 static int quant_fetch(sonic_engine* e, const QuantOut& qo, int rows, int K, const QuantHost& h) {
@@ -778,7 +560,7 @@ extern "C" int sonic_test_add_rmsnorm(sonic_engine* e, float* x, const float* sl
     const size_t n = (size_t)rows_alloc * d;
     bf16_t* dx = up_bf16(e, tb, x, n); bf16_t* dy = up_bf16(e, tb, y, n);
     float* dP = up_f32(e, tb, slabs, (size_t)ksplit * mpad * d); float* dw = up_f32(e, tb, w, d);
-    if (!dx || !dy || !dP || !dw) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     QuantOut qo{};
     if (q_out) TRY(quant_alloc(e, tb, rows, d, &qo));
     launch_add_rmsnorm(dx, dP, ksplit, mpad, dw, dy, rows, d, eps, e->st, e->dt, nullptr, q_out ? &qo : nullptr);
@@ -797,7 +579,7 @@ extern "C" int sonic_test_quant_rows(sonic_engine* e, const float* X, int M, int
         return fail(e, SONIC_ERR_INVALID, "quant_rows: 1 <= M <= 4096, K %% 8 == 0, K <= 8192, ld >= K, ld %% 8 == 0");
     TmpBuf tb(e->st);
     bf16_t* dX = up_bf16(e, tb, X, (size_t)M * ld);
-    if (!dX) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     QuantOut qo{};
     TRY(quant_alloc(e, tb, M, K, &qo));
     launch_quant_rows(dX, ld, M, K, qo, e->st);
@@ -813,7 +595,7 @@ extern "C" int sonic_test_swiglu_slab(sonic_engine* e, const float* slabs, int k
         return fail(e, SONIC_ERR_INVALID, "swiglu_slab: ff %% 16 == 0, 1 <= ksplit <= 8, 1 <= rows <= mpad, gu8 0 or 1");
     TmpBuf tb(e->st);
     float* dP = up_f32(e, tb, slabs, (size_t)ksplit * mpad * 2 * ff); bf16_t* dA = tb.get<bf16_t>((size_t)rows * ff);
-    if (!dP || !dA) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     launch_swiglu_slab(dP, ksplit, mpad, 2 * ff, dA, rows, e->st, e->dt, gu8);
     return down_bf16(e, tb, dA, act, (size_t)rows * ff);
 }
@@ -844,7 +626,7 @@ extern "C" int sonic_test_decode_o_gu(sonic_engine* e, const float* att, const f
     bf16_t* dR = up_bf16(e, tb, resid, (size_t)rows_alloc * D); float* dw = up_f32(e, tb, ln_w, D);
     bf16_t* dWg = up_bf16(e, tb, Wgu, (size_t)2 * ff * D); bf16_t* dWgt = tb.get<bf16_t>((size_t)2 * ff * D);
     bf16_t* dH = tb.get<bf16_t>((size_t)M * D); bf16_t* dAct = tb.get<bf16_t>((size_t)M * ff); float* dSS = tb.get<float>(nss);
-    if (!dA || !dWo || !dWot || !dR || !dw || !dWg || !dWgt || !dH || !dAct || !dSS) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     launch_tile_weights(dWo, dWot, D, K, e->st);
     launch_tile_weights_gu8(dWg, dWgt, 2 * ff, D, e->st);
     SkinnyArgs ga{}; ga.X = dR; ga.ldx = D; ga.W = dWgt; ga.M = M; ga.N = 2 * ff; ga.K = D; ga.ksplit = 1; ga.dt = e->dt; ga.err = e->n_active + 1;
@@ -859,7 +641,7 @@ extern "C" int sonic_test_decode_o_gu(sonic_engine* e, const float* att, const f
     } else {
         const int ks = skinny_pick_ksplit(D, K), mpad = ((M + 15) / 16) * 16;
         float* P = tb.get<float>((size_t)ks * mpad * D);
-        if (!P) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+        if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
         SkinnyArgs a{}; a.X = dA; a.ldx = K; a.W = dWot; a.P = P; a.M = M; a.N = D; a.K = K; a.ksplit = ks; a.dt = e->dt;
         launch_skinny(a, e->st);
         launch_add_rmsnorm(dR, P, ks, mpad, dw, dH, M, D, eps, e->st, e->dt);
@@ -900,7 +682,7 @@ extern "C" int sonic_test_rope_append(sonic_engine* e, const float* qkv, const f
     bf16_t* dqkv = up_bf16(e, tb, qkv, (size_t)n_tok * N); float* dcs = up_f32(e, tb, cs, (size_t)ctx_max * 128);
     bf16_t* dk = up_bf16(e, tb, Kc, nc); bf16_t* dv = up_bf16(e, tb, Vc, nc); bf16_t* dvt = up_bf16(e, tb, Vt, nvt); bf16_t* dq = tb.get<bf16_t>(nq);
     int* di = tb.get<int>((size_t)2 * n_tok + 2 * B);
-    if (!dqkv || !dcs || !dk || !dv || !dvt || !dq || !di) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     HIPC(e, h2d(e, di, tok_seq, (size_t)n_tok * 4)); HIPC(e, h2d(e, di + n_tok, tok_pos, (size_t)n_tok * 4));
     HIPC(e, h2d(e, di + 2 * n_tok, q_off, (size_t)B * 4)); HIPC(e, h2d(e, di + 2 * n_tok + B, q_len, (size_t)B * 4));
     RopeAppendArgs ra{}; ra.dt = e->dt;
@@ -923,17 +705,7 @@ extern "C" int sonic_test_rope_enc(sonic_engine* e, float* qk, int M, int ld, in
         return fail(e, SONIC_ERR_INVALID, "rope_enc: hd == 64, rd %% 16 == 0, 16 <= rd <= hd, ld >= heads2 * hd, ld %% 8 == 0");
     TmpBuf tb(e->st);
     bf16_t* dqk = up_bf16(e, tb, qk, (size_t)M * ld); float* dcs = up_f32(e, tb, cs, (size_t)T * rd);
-    if (!dqk || !dcs) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     launch_rope_enc(dqk, ld, M, T, heads2, hd, rd, dcs, e->st, e->dt);
     return down_bf16(e, tb, dqk, qk, (size_t)M * ld);
-}
-
-extern "C" int sonic_debug_ktrace(sonic_engine* e, int64_t* out, int64_t n) {
-    if (!e || !out) return SONIC_ERR_INVALID;
-    ENTER(e);
-    if (!e->kt) return fail(e, SONIC_ERR_INVALID, "ktrace is off");
-    const int64_t have = (int64_t)8 * KT_SLOT_BLOCKS * 8;
-    HIPC(e, stream_sync(e));
-    HIPC(e, d2h(e, out, e->kt, (size_t)(n < have ? n : have) * 8));
-    return SONIC_OK;
 }

@@ -1,5 +1,5 @@
 // What the translation units of the engine (engine.cpp, engine_weights.cpp, engine_stages.cpp, engine_f32.cpp, engine_ingest.cpp,
-// engine_service.cpp, engine_hooks.cpp) share: the engine struct and its parts, the constants, the error / entry macros and the helpers that
+// engine_service.cpp, engine_options.cpp, engine_hooks.cpp) share: the engine struct and its parts, the constants, the error / entry macros and the helpers that
 // cross a unit boundary.  Not part of the C ABI (include/sonic_hip.h); a function used by one unit only is static there.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -308,7 +308,7 @@ int fetch_locked(sonic_engine* e, int32_t* out_ids, int out_ld, int32_t* out_len
 int lp_alloc(sonic_engine* e);                      // out_lp on first use (engine.cpp)
 int gen_apply(sonic_engine* e, float penalty, int ngram, const int32_t* suppress, int n_suppress);   // sonic_set_generation behind the lock and the busy check (engine.cpp)
 int gen_busy(sonic_engine* e, const char* who);     // that busy check: SONIC_ERR_INVALID while the handle has work in hand (engine.cpp)
-void drop_graphs(sonic_engine* e);                  // the captured decode chunks of this handle (engine_hooks.cpp)
+void drop_graphs(sonic_engine* e);                  // the captured decode chunks of this handle (engine_options.cpp)
 int bias_enable(sonic_engine* e, int on);           // option request_bias behind the lock and the busy check: hist, the tables and their staging buffer on first use (engine.cpp)
 // one request's table as sonic_set_request_bias takes it -> its BIAS_ROW_WORDS device words, grouped and ordered as the kernel reads them; *count = its entries.
 // SONIC_ERR_INVALID (message on e, naming `who`) for more than BIAS_MAX_ENTRIES entries, a length outside 1 .. BIAS_MAX_LEN, an id outside [0, V), a NaN or +inf bias
@@ -321,3 +321,4 @@ int samp_upload(sonic_engine* e, int R);            // the prefill's part: the p
 void samp_pack(unsigned* w, float t, uint64_t seed);   // one row's three words as the kernel reads them: the temperature's bits, the seed's low and high word (engine.cpp)
 static inline bool hist_on(const sonic_engine* e) { return e->gen_on || e->opt_request_bias; }   // the rows' input_ids are kept: a guard or the request bias reads them
 int lp_check(sonic_engine* e, const char* who);     // SONIC_ERR_INVALID naming the option when token_logprobs is off on this handle
+int read_back_16(sonic_engine* e, const bf16_t* d, float* h, size_t n);   // n elements of a 16-bit device buffer -> fp32 on the host, through a temporary (engine_hooks.cpp; sonic_debug_read)

@@ -1,0 +1,171 @@
+// sonic_hip engine: the experiment knobs (sonic_set_option) and the debug read-back (sonic_debug_read, sonic_debug_ktrace).
+#include "engine_internal.h"
+
+void drop_graphs(sonic_engine* e) { for (auto& g : e->graphs) (void)hipGraphExecDestroy(g.second); e->graphs.clear(); }
+// ---- the knobs that do more than store an integer (OptRow::apply)
+static int opt_token_logprobs(sonic_engine* e, const char*, int value) {      // per-token log-probabilities beside the ids (greedy_kernel<T, true>)
+    const int v = value ? 1 : 0;
+    if (!v && e->opt_sampling) return fail(e, SONIC_ERR_INVALID, "token_logprobs cannot be switched off while option sampling is on (its kernels are log-probability kernels)");
+    e->opt_token_logprobs = v; drop_graphs(e);
+    return v ? lp_alloc(e) : SONIC_OK;      // first use: 64 x out_cap fp32
+}
+// the generation guards one integer at a time, for drivers that only speak key = value (bench.py --opt; tools/ab_generation_guards.sh): the penalty in
+// thousandths, the n-gram size, ONE suppressed id (-1: none).  Same rules and refusals as sonic_set_generation; the other two values stay as they are
+static int opt_gen(sonic_engine* e, const char* key, int value) {
+    float p = e->gen_penalty; int n = e->gen_ngram; std::vector<int> sup = e->gen_suppress;
+    if (!strcmp(key, "gen_repetition_penalty_milli")) p = (float)((double)value / 1000.0);
+    else if (!strcmp(key, "gen_no_repeat_ngram_size")) n = value;
+    else { sup.clear(); if (value >= 0) sup.push_back(value); }      // gen_suppress_token
+    TRY(gen_busy(e, key));
+    return gen_apply(e, p, n, sup.data(), (int)sup.size());
+}
+// temperature sampling (sonic_set_request_sampling): on the owner before its slots are created (they copy it), after token_logprobs (refused by
+// name otherwise); allocates the rows' (temperature, seed) words.  Refused while the handle has work in hand, by sonic_set_generation's rule
+static int opt_sampling(sonic_engine* e, const char* key, int value) { TRY(gen_busy(e, key)); return samp_enable(e, value ? 1 : 0); }
+static int opt_sampling_fill_milli(sonic_engine* e, const char* key, int value) {    // measurement aid (samp_upload, engine.cpp): 0 (off) or 1 .. 100000 thousandths, for every request without values
+    if (value != 0 && (value < 1 || value > 100000)) return fail(e, SONIC_ERR_INVALID, "sampling_fill_milli: %d is outside 0, 1 .. 100000", value);
+    TRY(gen_busy(e, key)); e->opt_samp_fill_milli = value; return SONIC_OK;
+}
+// per-request sequence bias (sonic_set_request_bias): on the owner before its slots are created (they copy it); allocates the rows' history, if the
+// guards have not, and their tables.  Refused while the handle has work in hand, by sonic_set_generation's rule
+static int opt_request_bias(sonic_engine* e, const char* key, int value) { TRY(gen_busy(e, key)); return bias_enable(e, value ? 1 : 0); }
+static int opt_request_bias_fill(sonic_engine* e, const char* key, int value) {      // measurement aid (bias_upload, engine.cpp): 0 .. min(256, vocabulary) neutral entries for every request without a table
+    if (value < 0 || value > BIAS_MAX_ENTRIES || value > e->d.vocab) return fail(e, SONIC_ERR_INVALID, "request_bias_fill: %d is outside 0 .. %d", value, BIAS_MAX_ENTRIES);
+    TRY(gen_busy(e, key)); e->opt_bias_fill = value; return SONIC_OK;
+}
+// the two knobs that do device work
+static int opt_ktrace(sonic_engine* e, const char*, int value) {              // diagnostics: record in-kernel timestamps of decoder layer `value` (-1: off); sonic_debug_ktrace reads them
+    HIPC(e, hipSetDevice(e->device));
+    if (value >= 0 && !e->kt) { TRY(dalloc(e, &e->kt, (size_t)8 * KT_SLOT_BLOCKS * 8)); }
+    if (e->kt) zero_fill(e, e->kt, (size_t)8 * KT_SLOT_BLOCKS * 8 * 8);
+    e->kt_layer = value; drop_graphs(e); return SONIC_OK;
+}
+static int opt_inject_dev_err(sonic_engine* e, const char*, int value) {      // tests: set (1) / clear (0) the device error word a decode kernel raises when it gives up on an in-kernel wait
+    HIPC(e, hipSetDevice(e->device));
+    const int v = value ? 1 : 0;
+    HIPC(e, hipMemcpyAsync(e->n_active + 1, &v, 4, hipMemcpyHostToDevice, e->st));
+    HIPC(e, stream_sync(e));
+    return SONIC_OK;
+}
+
+// The experiment knobs of sonic_set_option, one row each: the key, where the value lives (a member of the engine, or of its LaunchOpts - common.h
+// describes those), whether the captured decode graphs of the engine are dropped (the knob changes the captured kernels), and the clamp of the value.
+// A row with `apply` names a function above instead, which does the row's whole job.
+struct OptRow { const char* key; int sonic_engine::* field; int LaunchOpts::* lfield; bool drop_graphs; int (*clamp)(int); int (*apply)(sonic_engine*, const char* key, int value); };
+#define ENG(m) &sonic_engine::m, nullptr
+#define LOP(m) nullptr, &LaunchOpts::m
+#define APPLY(f) nullptr, nullptr, false, nullptr, f
+static const OptRow OPTIONS[] = {
+    {"skinny_variant", LOP(skinny_variant), true, nullptr},
+    {"gemm_force128", LOP(gemm_force128), false, nullptr},
+    {"no_fused_gu", LOP(no_fused_gu), true, nullptr},
+    {"no_fused_gu64", LOP(no_fused_gu64), true, nullptr},
+    {"gu64_two_pass", LOP(gu64_two_pass), true, nullptr},
+    {"gu64_split_norm", LOP(gu64_split_norm), true, nullptr},
+    {"ktrace_wave", LOP(ktrace_wave), true, nullptr},
+    {"no_skinny768", LOP(no_skinny768), true, nullptr},
+    {"no_skinny48", LOP(no_skinny48), true, nullptr},
+    {"o64_16rows", LOP(o64_16rows), true, nullptr},
+    {"i8_no_lnq", ENG(opt_i8_no_lnq), false, nullptr},              // int8 encoder: LayerNorm does not quantise its rows (A/B)
+    {"i8_no_qkv_fuse", ENG(opt_i8_no_qkv_fuse), false, nullptr},    // int8 encoder: RoPE and V^T as their own passes (A/B)
+    {"i8_dbg", ENG(opt_i8_dbg), true, nullptr},                     // timing experiments (wrong results)
+    {"i8_no_xq", ENG(opt_i8_no_xq), true, nullptr},
+    {"gemm_small_eff", LOP(gemm_small_eff), false, nullptr},
+    {"gemm128_shallow", LOP(gemm128_shallow), false, nullptr},
+    {"no_skinny_i8_wide", LOP(no_skinny_i8_wide), true, nullptr},
+    {"gemm256_stagger", LOP(gemm256_stagger), false, nullptr},
+    {"flash_variant", LOP(flash_variant), false, nullptr},
+    {"flash_enc", LOP(flash_enc), false, nullptr},                  // 0: rounds 1-4's encoder attention; v > 0: flash_enc_kernel mode v - 1
+    {"gemm256_persist", LOP(gemm256_persist), false, nullptr},
+    {"gemm256_persist_cus", LOP(gemm256_persist_cus), false, [](int v) { return v > 0 ? v : 256; }},
+    {"gemm256_gm", LOP(gemm256_gm), false, [](int v) { return v > 0 ? v : 8; }},   // raster group height of the 256x256 GEMM (experiments)
+    {"i8_defer_thr", ENG(opt_i8_defer_thr), false, nullptr},        // int8: outlier lists longer than this go to the dense side product (-1: never)
+    {"decode_prefetch", LOP(decode_prefetch), true, nullptr},       // idle-CU weight prefetch (experiment)
+    {"decode_attn_occ2", LOP(decode_attn_occ2), true, nullptr},     // decode attention at 128 VGPRs (two blocks per CU can co-reside; A/B)
+    {"decode_attn_v1", LOP(decode_attn_v1), true, nullptr},         // round 2's VALU P.V decode attention (A/B)
+    {"prefill_taps", ENG(taps_on), false, nullptr},
+    {"no_pre_norm", ENG(opt_no_pre_norm), true, nullptr},           // <= 2 rows: standalone add+RMSNorm launches as for more rows (A/B, same bits)
+    {"decode_gemv", ENG(opt_decode_gemv), true, nullptr},
+    {"f32_synth_bf16", ENG(opt_f32_synth_bf16), false, nullptr},
+    {"no_graph", ENG(opt_no_graph), false, nullptr},                // eager decode loop (debugging)
+    {"decode_lookahead", ENG(lookahead), false, [](int v) { return v < 1 ? 1 : (v > CHK_MAX_AHEAD ? CHK_MAX_AHEAD : v); }},   // start value (it adapts)
+    {"decode_chunk", ENG(opt_decode_chunk), false, [](int v) { return v > 0 ? (v > 64 ? 64 : v) : 1; }},   // token steps per graph launch / early-stop check
+    {"prefill_rowmajor", ENG(opt_prefill_rowmajor), false, nullptr},   // prefill GEMMs read the row-major decoder weights (kept only under SONIC_KEEP_ROWMAJOR=1; A/B)
+    {"no_rope_tiles", ENG(opt_no_rope_tiles), false, nullptr},      // prefill RoPE + KV append per token (rounds 1-4) instead of per 16-position tile (A/B)
+    {"gemm_trace", ENG(opt_gemm_trace), false, nullptr},            // sonic_bench_gemm prints an in-kernel timeline of one launch to stderr
+    {"gemm_timing", ENG(opt_gemm_timing), false, nullptr},          // HIP events around every encoder-layer GEMM launch
+    {"no_fused_rope", ENG(opt_no_fused_rope), false, nullptr},      // encoder RoPE as its own pass (A/B against the fused epilogue)
+    {"no_gelu_lut", ENG(opt_no_gelu_lut), false, nullptr},          // GELU by arithmetic instead of the LDS table (A/B)
+    {"token_logprobs", APPLY(opt_token_logprobs)},
+    {"gen_repetition_penalty_milli", APPLY(opt_gen)},
+    {"gen_no_repeat_ngram_size", APPLY(opt_gen)},
+    {"gen_suppress_token", APPLY(opt_gen)},
+    {"sampling", APPLY(opt_sampling)},
+    {"sampling_fill_milli", APPLY(opt_sampling_fill_milli)},
+    {"request_bias", APPLY(opt_request_bias)},
+    {"request_bias_fill", APPLY(opt_request_bias_fill)},
+    {"ktrace", APPLY(opt_ktrace)},
+    {"inject_dev_err", APPLY(opt_inject_dev_err)},
+};
+extern "C" int sonic_set_option(sonic_engine* e, const char* key, int value) {
+    if (!e || !key) return SONIC_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    // knobs live in the engine: two engines in one process do not see each other's settings; captured decode graphs of THIS engine
+    // are dropped whenever a knob that changes the captured kernels moves
+    for (const OptRow& r : OPTIONS) {
+        if (strcmp(key, r.key)) continue;
+        if (r.apply) return r.apply(e, key, value);
+        const int v = r.clamp ? r.clamp(value) : value;
+        if (r.field) e->*r.field = v; else e->opts.*r.lfield = v;
+        if (r.drop_graphs) drop_graphs(e);
+        return SONIC_OK;
+    }
+    return fail(e, SONIC_ERR_INVALID, "unknown option %s", key);
+}
+
+// The buffers sonic_debug_read serves, one row each: the name, the elements it holds, and where it lives on a 16-bit handle and on the fp32 kind (null: that kind
+// has no such buffer).  prefill_tap is the one row with an index: tap `index` of the taps option prefill_taps recorded
+struct DbgRow { const char* name; size_t (*cap)(const sonic_engine*); const bf16_t* (*src16)(const sonic_engine*); const float* (*src32)(const sonic_engine*); };
+#define CAP(x) [](const sonic_engine* e) -> size_t { return x; }
+#define S16(m) [](const sonic_engine* e) -> const bf16_t* { return e->m; }
+#define S32(m) [](const sonic_engine* e) -> const float* { return e->f->m; }
+static const DbgRow DEBUG_BUFS[] = {
+    {"prefill_tap", CAP((size_t)e->tok_cap * e->d.dec_d), S16(taps), [](const sonic_engine* e) -> const float* { return (const float*)e->taps; }},
+    {"pe", CAP((size_t)e->Bm * e->Ta * e->d.dec_d), S16(pe), S32(pe)},
+    {"dx", CAP((size_t)e->tok_cap * e->d.dec_d), S16(dx), S32(dx)},
+    {"dqkv", CAP((size_t)e->tok_cap * e->qkvN), S16(dqkv), nullptr},
+    {"dq", CAP((size_t)e->tok_cap * e->QD), S16(dq), nullptr},
+    {"datt", CAP((size_t)e->tok_cap * e->QD), S16(datt), nullptr},
+    {"dact", CAP((size_t)e->tok_cap * e->d.dec_ff), S16(dact), nullptr},
+    {"enc_x", CAP((size_t)e->Bm * e->T * e->d.enc_d), S16(ln), S32(ln)},
+    {"h1", CAP((size_t)e->Bm * (e->d.n_frames + 2) * e->d.enc_d), nullptr, S32(h1)},
+    {"shn", CAP((size_t)64 * e->d.dec_d), S16(shn), nullptr},          // decode-step buffers as the last step left them
+    {"satt", CAP((size_t)64 * e->QD), S16(satt), nullptr},
+    {"sact", CAP((size_t)64 * e->d.dec_ff), S16(sact), nullptr},
+};
+// Debug read-back of an internal activation buffer as fp32 (tests / diagnostics only).
+extern "C" int sonic_debug_read(sonic_engine* e, const char* name, int index, float* out, int64_t n) {
+    if (!e || !name || !out) return SONIC_ERR_INVALID;
+    ENTER(e);
+    for (const DbgRow& r : DEBUG_BUFS) {
+        if (strcmp(name, r.name) || !(e->f32 ? (bool)r.src32 : (bool)r.src16)) continue;
+        const bool tap = &r == &DEBUG_BUFS[0];
+        if (tap && !e->taps) return fail(e, SONIC_ERR_INVALID, "no taps recorded");
+        const size_t cap = r.cap(e), off = tap ? (size_t)index * cap : 0;
+        if (n < 0 || (size_t)n > cap) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
+        if (!e->f32) return read_back_16(e, r.src16(e) + off, out, (size_t)n);
+        HIPC(e, stream_sync(e)); HIPC(e, d2h(e, out, r.src32(e) + off, (size_t)n * 4));      // fp32 kind: its buffers are fp32 already
+        return SONIC_OK;
+    }
+    return fail(e, SONIC_ERR_INVALID, "unknown buffer %s", name);
+}
+
+extern "C" int sonic_debug_ktrace(sonic_engine* e, int64_t* out, int64_t n) {
+    if (!e || !out) return SONIC_ERR_INVALID;
+    ENTER(e);
+    if (!e->kt) return fail(e, SONIC_ERR_INVALID, "ktrace is off");
+    const int64_t have = (int64_t)8 * KT_SLOT_BLOCKS * 8;
+    HIPC(e, stream_sync(e));
+    HIPC(e, d2h(e, out, e->kt, (size_t)(n < have ? n : have) * 8));
+    return SONIC_OK;
+}

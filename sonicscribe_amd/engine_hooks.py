@@ -1,0 +1,273 @@
+"""The test, bench and debug wrappers of the binding (sonic_test_*, sonic_bench_*, sonic_debug_*): a mixin of engine.Engine, which supplies `lib`, `h` and
+`_check`.  Nothing here is on the product path.  This module does not import engine (engine imports it); the two helpers both use live here."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+
+EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_SWIGLU = 0, 1, 2, 3
+
+
+def _p(a: Optional[np.ndarray]):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _arr(x, dtype):
+    """contiguous array of dtype, or None"""
+    return None if x is None else np.ascontiguousarray(x, dtype)
+
+
+def _quant_bufs(rows: int, K: int):
+    return (np.zeros((rows, K), np.int8), np.zeros(rows, np.float32), np.zeros(rows, np.int32), np.zeros((rows, K), np.int32), np.zeros((rows, K), np.float32))
+
+
+class HooksMixin:
+    def test_gemm(self, A, W, bias=None, resid=None, epi=EPI_BIAS):
+        A = np.ascontiguousarray(A, np.float32); W = np.ascontiguousarray(W, np.float32)
+        M, K = A.shape; N = W.shape[0]
+        n_out = N // 2 if epi == EPI_SWIGLU else N
+        out = np.empty((M, n_out), np.float32)
+        b = _arr(bias, np.float32)
+        r = _arr(resid, np.float32)
+        self._check(self.lib.sonic_test_gemm(self.h, _p(A), _p(W), _p(b), _p(r), _p(out), M, N, K, epi))
+        return out
+
+    def test_skinny(self, X, W):
+        X = np.ascontiguousarray(X, np.float32); W = np.ascontiguousarray(W, np.float32)
+        M, K = X.shape; N = W.shape[0]
+        out = np.empty((M, N), np.float32)
+        self._check(self.lib.sonic_test_skinny(self.h, _p(X), _p(W), _p(out), M, N, K))
+        return out
+
+    def test_attention(self, q, k, v, causal: bool):
+        """q [B][Tq][Hq][hd], k/v [B][Tk][Hkv][hd] -> [B][Tq][Hq][hd]"""
+        q = np.ascontiguousarray(q, np.float32); k = np.ascontiguousarray(k, np.float32); v = np.ascontiguousarray(v, np.float32)
+        B, Tq, Hq, hd = q.shape; Tk, Hkv = k.shape[1], k.shape[2]
+        out = np.empty_like(q)
+        self._check(self.lib.sonic_test_attention(self.h, _p(q), _p(k), _p(v), _p(out), B, Tq, Tk, Hq, Hkv, hd, int(causal)))
+        return out
+
+    def test_decode_attention(self, q, k, v):
+        """q [B][Hq][128], k/v [B][Tk][Hkv][128] -> [B][Hq][128]"""
+        q = np.ascontiguousarray(q, np.float32); k = np.ascontiguousarray(k, np.float32); v = np.ascontiguousarray(v, np.float32)
+        B, Hq, _ = q.shape; Tk, Hkv = k.shape[1], k.shape[2]
+        out = np.empty_like(q)
+        self._check(self.lib.sonic_test_decode_attention(self.h, _p(q), _p(k), _p(v), _p(out), B, Tk, Hq, Hkv))
+        return out
+
+    def test_layernorm(self, x, w, b=None, eps=1e-5, rms=False):
+        x = np.ascontiguousarray(x, np.float32); w = np.ascontiguousarray(w, np.float32)
+        bb = _arr(b, np.float32)
+        out = np.empty_like(x)
+        self._check(self.lib.sonic_test_layernorm(self.h, _p(x), _p(w), _p(bb), _p(out), x.shape[0], x.shape[1], eps, int(rms)))
+        return out
+
+    def bench_gemm(self, M: int, N: int, K: int, epi: int = EPI_BIAS_GELU, iters: int = 20) -> float:
+        ms = C.c_float(0)
+        self._check(self.lib.sonic_bench_gemm(self.h, M, N, K, epi, iters, C.byref(ms)))
+        return float(ms.value)
+
+    def bench_skinny(self, M: int, N: int, K: int, variant: int, iters: int = 50) -> float:
+        us = C.c_float(0)
+        self._check(self.lib.sonic_bench_skinny(self.h, M, N, K, variant, iters, C.byref(us)))
+        return float(us.value)
+
+    def debug_ktrace(self) -> np.ndarray:
+        """[slot 8][block 512][point 8] device wall-clock ticks (10 ns) of the decode kernels of the layer set by option "ktrace"."""
+        out = np.zeros((8, 512, 8), np.int64)
+        self._check(self.lib.sonic_debug_ktrace(self.h, _p(out), out.size))
+        return out
+
+    def debug_read(self, name: str, shape, index: int = 0) -> np.ndarray:
+        out = np.empty(shape, np.float32)
+        self._check(self.lib.sonic_debug_read(self.h, name.encode(), index, _p(out), out.size))
+        return out
+
+    def test_skinny_gu(self, X, Wi):
+        X = np.ascontiguousarray(X, np.float32); Wi = np.ascontiguousarray(Wi, np.float32)
+        M, K = X.shape; N = Wi.shape[0]
+        out = np.empty((M, N // 2), np.float32)
+        self._check(self.lib.sonic_test_skinny_gu(self.h, _p(X), _p(Wi), _p(out), M, N, K))
+        return out
+
+    def _greedy(self, entry: str, slabs, B: int, want_logits: bool = True, want_lp: bool = True, force_ids=None, guard=None, tables=None, samp=None, want_noise: bool = False):
+        """What the five greedy wrappers share: slabs, history, suppress list, tables, forced ids and outputs prepared once, then sonic_test_<entry> - the C entry
+        point of the wrapper that calls, never another family's.  guard = (hist, hist_len, repetition_penalty, no_repeat_ngram_size, suppress_tokens) for the
+        entries that take histories; samp = (temperature, seed, step).  -> (tok, logits or None, lp or None, noise or None)"""
+        s = np.ascontiguousarray(slabs, np.float32)
+        ks, mpad, V = s.shape
+        args = [_p(s), ks, mpad, V, B]
+        if guard is not None:
+            hist, hist_len, penalty, ngram, suppress_tokens = guard
+            h = hl = None
+            if hist_len is not None:
+                h = np.ascontiguousarray(hist, np.int32).reshape(B, -1)
+                hl = np.ascontiguousarray(hist_len, np.int32)
+            sup = np.ascontiguousarray(list(suppress_tokens), dtype=np.int32)
+            args += [_p(h) if h is not None and h.size else None, 0 if h is None else h.shape[1], _p(hl), float(penalty), int(ngram), _p(sup) if sup.size else None, int(sup.size)]
+        if entry != "greedy":
+            f = _arr(force_ids, np.int32)
+            args.append(_p(f))
+        if entry in ("greedy_bias", "greedy_sample"):
+            seq_ids = seq_off = bias = req_off = None
+            if tables is not None:
+                from .engine import pack_request_bias
+                seq_ids, seq_off, bias, req_off = pack_request_bias(list(tables))
+            args += [_p(seq_ids) if seq_ids is not None and seq_ids.size else None, _p(seq_off), _p(bias) if bias is not None and bias.size else None, _p(req_off)]
+        if samp is not None:
+            t = np.ascontiguousarray(samp[0], np.float32)
+            sd = np.ascontiguousarray([int(x) for x in samp[1]], np.uint64)
+            stp = np.ascontiguousarray(samp[2], np.int32)
+            assert t.shape == sd.shape == stp.shape == (B,)
+            args += [_p(t), _p(sd), _p(stp)]
+        tok = np.zeros(B, np.int32)
+        lg = np.zeros((B, V), np.float32) if want_logits else None
+        lp = np.full(B, np.nan, np.float32) if want_lp else None
+        noise = np.zeros((B, V), np.float32) if want_noise else None
+        out = [tok, lg] + ([lp] if entry != "greedy" else []) + ([noise] if samp is not None else [])
+        self._check(getattr(self.lib, "sonic_test_" + entry)(self.h, *args, *[_p(o) for o in out]))
+        return tok, lg, lp, noise
+
+    def test_greedy(self, slabs, B: int, want_logits: bool = False):
+        """slabs: [ksplit][mpad][V] fp32 -> (token per row [B], bf16 logits [B][V] or None)"""
+        return self._greedy("greedy", slabs, B, want_logits, want_lp=False)[:2]
+
+    def test_greedy_lp(self, slabs, B: int, force_ids=None):
+        """sonic_test_greedy through greedy_kernel<T, true>: slabs [ksplit][mpad][V] fp32 -> (token per row [B], logits [B][V], log-probability of the
+        emitted token [B]); force_ids [B]: the token every row emits instead of its argmax"""
+        return self._greedy("greedy_lp", slabs, B, force_ids=force_ids)[:3]
+
+    def test_greedy_guard(self, slabs, B: int, hist, hist_len, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, suppress_tokens=(), force_ids=None,
+                          want_lp: bool = False):
+        """sonic_test_greedy through greedy_kernel<T, LP, true>: slabs [ksplit][mpad][V] fp32, hist [B][ld] int (row b's first hist_len[b] entries are its
+        history) -> (token per row [B], RAW logits [B][V], log-probability of the emitted token over the processed scores [B] or None)"""
+        return self._greedy("greedy_guard", slabs, B, True, want_lp, force_ids, (hist, hist_len, repetition_penalty, no_repeat_ngram_size, suppress_tokens))[:3]
+
+    def test_greedy_bias(self, slabs, B: int, hist, hist_len, tables, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, suppress_tokens=(), force_ids=None,
+                         want_lp: bool = False):
+        """sonic_test_greedy_guard through greedy_kernel<T, LP, true, true>: `tables` holds one reqbias.RequestBias or None per row -> (token per row [B], RAW
+        logits [B][V], log-probability of the emitted token over the processed scores [B] or None)"""
+        return self._greedy("greedy_bias", slabs, B, True, want_lp, force_ids, (hist, hist_len, repetition_penalty, no_repeat_ngram_size, suppress_tokens), list(tables))[:3]
+
+    def test_greedy_sample(self, slabs, B: int, temperature, seed, step, hist=None, hist_len=None, tables=None, repetition_penalty: float = 1.0,
+                           no_repeat_ngram_size: int = 0, suppress_tokens=(), force_ids=None, want_noise: bool = True):
+        """sonic_test_greedy_sample: the sampling instantiations of the greedy kernel in this handle's type.  hist_len None: the plain family; tables None: the guard
+        family; else the bias family -> (token [B], RAW logits [B][V], log-probability over the processed scores at temperature 1 [B], Gumbel noise used [B][V] or None)"""
+        return self._greedy("greedy_sample", slabs, B, True, True, force_ids, (hist, hist_len, repetition_penalty, no_repeat_ngram_size, suppress_tokens), tables,
+                            (temperature, seed, step), want_noise)
+
+    def test_linear_int8(self, X, W, bias=None, resid=None, group_rows=None, epi=EPI_BIAS):
+        """One Linear8bitLt call; X [M][K], W [N][K] fp16-valued. group_rows: rows per reference call (default: all rows one call)."""
+        X = np.ascontiguousarray(X, np.float32); W = np.ascontiguousarray(W, np.float32)
+        M, K = X.shape; N = W.shape[0]
+        out = np.empty((M, N // 2 if epi == EPI_SWIGLU else N), np.float32)
+        b = _arr(bias, np.float32)
+        r = _arr(resid, np.float32)
+        self._check(self.lib.sonic_test_linear_int8(self.h, _p(X), _p(W), _p(b), _p(r), _p(out), M, N, K, int(group_rows or M), epi))
+        return out
+
+    def test_decode_attention_cache(self, kcache, vcache, kv_len, Hq: int, q=None, slabs=None, rope_cs=None, want_caches: bool = True):
+        """The decode attention as decode_step launches it.  kcache / vcache [B][Hkv][ctx_max][128] (whole, the caller fills what lies behind kv_len),
+        kv_len [B] (new token included).  Either q [B][Hq][128] (nothing appended) or slabs [ksplit][mpad][(Hq + 2 Hkv) * 128] with rope_cs [ctx_max][128]
+        (fused slab sum + RoPE + append).  Returns (out [B][Hq][128], kcache after, vcache after); the caches are None unless want_caches."""
+        kc = np.ascontiguousarray(kcache, np.float32); vc = np.ascontiguousarray(vcache, np.float32)
+        B, Hkv, ctx, hd = kc.shape
+        assert hd == 128 and vc.shape == kc.shape and (q is None) != (slabs is None)
+        kl = np.ascontiguousarray(kv_len, np.int32)
+        assert kl.shape == (B,)
+        ks = mpad = 0
+        if q is not None:
+            q = np.ascontiguousarray(q, np.float32)
+            assert q.shape == (B, Hq, 128)
+        else:
+            slabs = np.ascontiguousarray(slabs, np.float32); rope_cs = np.ascontiguousarray(rope_cs, np.float32)
+            ks, mpad = slabs.shape[:2]
+            assert slabs.shape == (ks, mpad, (Hq + 2 * Hkv) * 128) and rope_cs.shape == (ctx, 128)
+        out = np.empty((B, Hq, 128), np.float32)
+        ko = np.empty_like(kc) if want_caches else None
+        vo = np.empty_like(vc) if want_caches else None
+        self._check(self.lib.sonic_test_decode_attention_cache(self.h, _p(q), _p(slabs), ks, mpad, _p(rope_cs), _p(kc), _p(vc), _p(kl), _p(out), _p(ko), _p(vo),
+                                                               B, Hq, Hkv, ctx))
+        return out, ko, vo
+
+    def test_prefill_attention(self, q, kcache, vt, q_off, q_len, kv_len, out_init=None):
+        """The prefill's causal attention with run_prefill's strides.  q [n_tok][Hq][128] packed, kcache [B][Hkv][ctx_max][128], vt [B][Hkv][128][ctx_max],
+        q_off / q_len / kv_len [B].  out_init [n_tok][Hq][128] is what the output buffer holds before the launch (default zeros).  -> [n_tok][Hq][128]"""
+        q = np.ascontiguousarray(q, np.float32); kc = np.ascontiguousarray(kcache, np.float32); vt = np.ascontiguousarray(vt, np.float32)
+        n_tok, Hq, hd = q.shape
+        B, Hkv, ctx, _ = kc.shape
+        assert hd == 128 and kc.shape[3] == 128 and vt.shape == (B, Hkv, 128, ctx)
+        qo, ql, kl = (np.ascontiguousarray(x, np.int32) for x in (q_off, q_len, kv_len))
+        assert qo.shape == ql.shape == kl.shape == (B,)
+        out = np.zeros_like(q) if out_init is None else np.array(out_init, np.float32, order="C")
+        assert out.shape == q.shape
+        self._check(self.lib.sonic_test_prefill_attention(self.h, _p(q), _p(kc), _p(vt), _p(qo), _p(ql), _p(kl), _p(out), n_tok, B, Hq, Hkv, ctx))
+        return out
+
+    def test_add_rmsnorm(self, x, slabs, w, eps: float, rows: int, y_init=None, quant: bool = False):
+        """add_rmsnorm_kernel as the decode step launches it.  x [rows_alloc][d], slabs [ksplit][mpad][d] fp32, w [d]; y_init [rows_alloc][d] is what the output
+        buffer holds before the launch (default zeros).  -> (x after, y after[, (q int8 [rows][d], sca [rows], oc_cnt [rows], oc_list [rows][d], oc_val [rows][d])]);
+        list entries the kernel did not write are -1 / 0.  quant needs an fp16 engine."""
+        x = np.array(x, np.float32, order="C"); s = np.ascontiguousarray(slabs, np.float32); w = np.ascontiguousarray(w, np.float32)
+        rows_alloc, d = x.shape
+        ks, mpad = s.shape[:2]
+        assert s.shape == (ks, mpad, d) and w.shape == (d,)
+        y = np.zeros_like(x) if y_init is None else np.array(y_init, np.float32, order="C")
+        assert y.shape == x.shape
+        qb = _quant_bufs(rows, d) if quant else (None,) * 5
+        self._check(self.lib.sonic_test_add_rmsnorm(self.h, _p(x), _p(s), ks, mpad, _p(w), float(eps), _p(y), int(rows), rows_alloc, d, *[_p(b) for b in qb]))
+        return (x, y, qb) if quant else (x, y)
+
+    def test_quant_rows(self, X, K: Optional[int] = None):
+        """quant_rows_kernel on X [M][ld] (fp16 values; the first K columns of every row, default all) -> (q, sca, oc_cnt, oc_list, oc_val) as test_add_rmsnorm"""
+        X = np.ascontiguousarray(X, np.float32)
+        M, ld = X.shape
+        K = ld if K is None else int(K)
+        qb = _quant_bufs(M, K)
+        self._check(self.lib.sonic_test_quant_rows(self.h, _p(X), M, K, ld, *[_p(b) for b in qb]))
+        return qb
+
+    def test_swiglu_slab(self, slabs, rows: int, gu8: int):
+        """swiglu_slab_kernel: slabs [ksplit][mpad][2 ff] fp32 -> act [rows][ff]"""
+        s = np.ascontiguousarray(slabs, np.float32)
+        ks, mpad, n2 = s.shape
+        act = np.empty((rows, n2 // 2), np.float32)
+        self._check(self.lib.sonic_test_swiglu_slab(self.h, _p(s), ks, mpad, n2 // 2, int(rows), int(gu8), _p(act)))
+        return act
+
+    def test_decode_o_gu(self, att, Wo, resid, ln_w, eps: float, Wgu, form: int, want_ss: bool = False):
+        """One layer's o_proj -> RMSNorm -> gate/up chain (sonic_test_decode_o_gu).  att [M][K], Wo [D][K], resid [rows_alloc][D], ln_w [D], Wgu [2 ff][D] (gate / up rows
+        interleaved in groups of 16).  -> dict: resid [rows_alloc][D], act [M][ff], hn [M][D] (forms 1, 2), ss [2][D / 64][32][4] (want_ss, forms 0, 1)"""
+        att = np.ascontiguousarray(att, np.float32); Wo = np.ascontiguousarray(Wo, np.float32); Wgu = np.ascontiguousarray(Wgu, np.float32)
+        r = np.array(resid, np.float32, order="C"); w = np.ascontiguousarray(ln_w, np.float32)
+        M, K = att.shape; D = Wo.shape[0]; ff = Wgu.shape[0] // 2
+        assert Wo.shape == (D, K) and r.shape[1] == D and w.shape == (D,) and Wgu.shape == (2 * ff, D)
+        hn = np.empty((M, D), np.float32) if form != 0 else None
+        act = np.empty((M, ff), np.float32)
+        ss = np.empty((2, D // 64, 32, 4), np.float32) if want_ss else None
+        self._check(self.lib.sonic_test_decode_o_gu(self.h, _p(att), _p(Wo), _p(r), _p(w), float(eps), _p(Wgu), int(form), M, K, D, ff, r.shape[0], _p(hn), _p(act), _p(ss)))
+        return {"resid": r, "act": act, "hn": hn, "ss": ss}
+
+    def test_rope_append(self, qkv, cs, tok_seq, tok_pos, q_off, q_len, Hq: int, kcache, vcache, vt, tiled: bool):
+        """The prefill's RoPE + KV append.  qkv [n_tok][(Hq + 2 Hkv) * 128], cs [ctx_max][128], kcache / vcache [B][Hkv][ctx_max][128], vt [B][Hkv][128][vt_ld] as the
+        buffers are before the launch.  -> (q [n_tok][Hq][128], kcache, vcache, vt after)"""
+        qkv = np.ascontiguousarray(qkv, np.float32); cs = np.ascontiguousarray(cs, np.float32)
+        kc = np.array(kcache, np.float32, order="C"); vc = np.array(vcache, np.float32, order="C"); vt = np.array(vt, np.float32, order="C")
+        B, Hkv, ctx, hd = kc.shape
+        n_tok = qkv.shape[0]
+        assert hd == 128 and vc.shape == kc.shape and vt.shape[:3] == (B, Hkv, 128) and cs.shape == (ctx, 128) and qkv.shape[1] == (Hq + 2 * Hkv) * 128
+        ts, tp, qo, ql = (np.ascontiguousarray(a, np.int32) for a in (tok_seq, tok_pos, q_off, q_len))
+        assert ts.shape == tp.shape == (n_tok,) and qo.shape == ql.shape == (B,)
+        q = np.empty((n_tok, Hq, 128), np.float32)
+        self._check(self.lib.sonic_test_rope_append(self.h, _p(qkv), _p(cs), _p(ts), _p(tp), _p(qo), _p(ql), n_tok, B, Hq, Hkv, ctx, vt.shape[3], int(tiled),
+                                                    _p(q), _p(kc), _p(vc), _p(vt)))
+        return q, kc, vc, vt
+
+    def test_rope_enc(self, qk, T: int, heads2: int, rd: int, cs, hd: int = 64):
+        """rope_enc_kernel on a copy of qk [M][ld]; cs [T][rd]"""
+        qk = np.array(qk, np.float32, order="C"); cs = np.ascontiguousarray(cs, np.float32)
+        assert cs.shape == (T, rd)
+        self._check(self.lib.sonic_test_rope_enc(self.h, _p(qk), qk.shape[0], qk.shape[1], int(T), int(heads2), int(hd), int(rd), _p(cs)))
+        return qk

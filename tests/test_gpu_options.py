@@ -1,4 +1,4 @@
-"""sonic_set_option (csrc/engine_hooks.cpp): the experiment knobs are one table, and this file pins what that table has to keep - the accepted key set
+"""sonic_set_option (csrc/engine_options.cpp): the experiment knobs are one table, and this file pins what that table has to keep - the accepted key set
 written out below, the "unknown option" error for anything else, the four clamped knobs taking any integer, and the drop of the captured decode graphs
 when a knob that changes the captured kernels moves (a decode after no_fused_gu = 1 then 0 runs the default kernels again, not a stale graph)."""
 import numpy as np
