@@ -162,24 +162,8 @@ int f32_run_prefill(sonic_engine* e, int R, const HostPlan& hp) {
     F32State& f = *e->f;
     const sonic_dims& d = e->d;
     const int D = d.dec_d, M = hp.n_tok;
-    {
-        int* h = e->plan_h; size_t o = 0;
-        auto put = [&](int* dst, const int* srcv, size_t n) -> hipError_t {
-            memcpy(h + o, srcv, n * 4);
-            hipError_t r = hipMemcpyAsync(dst, h + o, n * 4, hipMemcpyHostToDevice, e->st);
-            o += n; return r;
-        };
-        HIPC(e, put(e->src, hp.src.data(), (size_t)M)); HIPC(e, put(e->tok_seq, hp.tok_seq.data(), (size_t)M)); HIPC(e, put(e->tok_pos_pf, hp.tok_pos.data(), (size_t)M));
-        HIPC(e, put(e->q_off, hp.q_off.data(), (size_t)R)); HIPC(e, put(e->q_len, hp.q_len.data(), (size_t)R)); HIPC(e, put(e->kv_len, hp.q_len.data(), (size_t)R));
-        HIPC(e, put(e->last_row, hp.last_row.data(), (size_t)R)); HIPC(e, put(e->max_new_d, hp.max_new.data(), (size_t)R));
-        HIPC(e, put(e->n_active, &R, 1));
-        HIPC(e, hipEventRecord(e->plan_ev[e->plan_idx], e->st));
-        e->plan_busy[e->plan_idx] = true;
-    }
-    launch_fill_i32(e->n_new, 0, 64, e->st); launch_fill_i32(e->finished, 0, 64, e->st); launch_fill_i32(e->step_ctr, 0, 64, e->st);
-    if (hist_on(e)) launch_hist_prompt(e->src, e->tok_seq, e->tok_pos_pf, M, d.audio_token_id, e->hist, e->max_ctx, e->st);
-    TRY(bias_upload(e, R));
-    TRY(samp_upload(e, R));
+    TRY(upload_plan(e, R, hp));
+    TRY(reset_row_state(e, R, M));
     launch_f32_assemble(e->src, f.embed, f.pe, f.dx, M, D, e->st);
     e->last_ntok = M;
     if (e->taps_on) {

@@ -77,8 +77,7 @@ extern "C" int sonic_test_skinny(sonic_engine* e, const float* X, const float* W
     float* P = tb.get<float>((size_t)ks * mpad * N);
     if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     launch_tile_weights(dW, dWt, N, K, e->st);
-    SkinnyArgs a{}; a.X = dX; a.ldx = K; a.W = dWt; a.P = P; a.M = M; a.N = N; a.K = K; a.ksplit = ks; a.dt = e->dt;
-    launch_skinny(a, e->st);
+    launch_skinny(skinny_args(dX, K, dWt, P, M, N, K, ks, e->dt), e->st);
     HIPC(e, stream_sync(e));
     HIPC(e, hipGetLastError());
     std::vector<float> h((size_t)ks * mpad * N);
@@ -146,12 +145,11 @@ extern "C" int sonic_test_decode_attention(sonic_engine* e, const float* q, cons
     bf16_t* dO = tb.get<bf16_t>((size_t)B * Hq * hd); int* kl = tb.get<int>(B);
     if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     std::vector<int> l(B, Tk); HIPC(e, h2d(e, kl, l.data(), B * 4));
-    DecodeAttnArgs a{}; a.Q = dq; a.P = nullptr; a.Kc = dk; a.Vc = dv; a.O = dO; a.kv_len = kl; a.Hq = Hq; a.Hkv = Hkv; a.ctx_max = ctx; a.scale = 1.0f / sqrtf(128.f); a.dt = e->dt;
-    launch_decode_attn(a, B, e->st);
+    launch_decode_attn(decode_attn_args(dk, dv, nullptr, dq, 0, 0, nullptr, dO, kl, Hq, Hkv, ctx, e->dt), B, e->st);
     return down_bf16(e, tb, dO, out, (size_t)B * Hq * hd);
 }
 
-// The decode attention as decode_step() launches it - fused mode (slabs != null: slab sum, RoPE at kv_len - 1, K/V append, kv_len - 1 cached keys + the new one
+// The decode attention through decode_step()'s own descriptor builder (decode_attn_args) - fused mode (slabs != null: slab sum, RoPE at kv_len - 1, K/V append, kv_len - 1 cached keys + the new one
 // from LDS) - or with a given q (slabs == null), over caller-filled caches and per-row kv_len.  The caches are read back after the launch.
 extern "C" int sonic_test_decode_attention_cache(sonic_engine* e, const float* q, const float* slabs, int ksplit, int mpad, const float* rope_cs,
                                                  const float* kcache, const float* vcache, const int32_t* kv_len, float* out, float* kcache_out, float* vcache_out,
@@ -173,17 +171,14 @@ extern "C" int sonic_test_decode_attention_cache(sonic_engine* e, const float* q
     bf16_t* dO = tb.get<bf16_t>(no); int* kl = tb.get<int>(B);
     if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     HIPC(e, h2d(e, kl, kv_len, (size_t)B * 4));
-    DecodeAttnArgs a{};
-    a.Q = dq; a.P = dP; a.ksplit = ksplit; a.mpad = mpad; a.cs = dcs; a.Kc = dk; a.Vc = dv; a.O = dO; a.kv_len = kl; a.Hq = Hq; a.Hkv = Hkv; a.ctx_max = ctx_max;
-    a.scale = 1.0f / sqrtf((float)hd); a.dt = e->dt;
-    launch_decode_attn(a, B, e->st);
+    launch_decode_attn(decode_attn_args(dk, dv, dP, dq, ksplit, mpad, dcs, dO, kl, Hq, Hkv, ctx_max, e->dt), B, e->st);
     TRY(down_bf16(e, tb, dO, out, no));
     if (kcache_out) TRY(down_bf16(e, tb, dk, kcache_out, nc));
     if (vcache_out) TRY(down_bf16(e, tb, dv, vcache_out, nc));
     return SONIC_OK;
 }
 
-// The causal attention of the prefill as run_prefill() launches it: packed ragged queries (q_off / q_len / kv_len), K in cache layout, V^T with the
+// The causal attention of the prefill through run_prefill()'s own descriptor builder (prefill_flash_args): packed ragged queries (q_off / q_len / kv_len), K in cache layout, V^T with the
 // context as its leading dimension, head dim 128.  `out` [n_tok][Hq * 128] is uploaded first, so rows the kernel leaves alone keep the caller's values.
 extern "C" int sonic_test_prefill_attention(sonic_engine* e, const float* q, const float* kcache, const float* vt, const int32_t* q_off, const int32_t* q_len,
                                             const int32_t* kv_len, float* out, int n_tok, int B, int Hq, int Hkv, int ctx_max) {
@@ -204,13 +199,7 @@ extern "C" int sonic_test_prefill_attention(sonic_engine* e, const float* q, con
     int* di = tb.get<int>((size_t)3 * B);
     if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     HIPC(e, h2d(e, di, q_off, (size_t)B * 4)); HIPC(e, h2d(e, di + B, q_len, (size_t)B * 4)); HIPC(e, h2d(e, di + 2 * B, kv_len, (size_t)B * 4));
-    FlashArgs f{}; f.dt = e->dt;
-    f.Q = dq; f.q_ld = (long)Hq * hd; f.K = dk; f.k_ld = hd; f.Vt = dvt; f.vt_ld = ctx_max; f.O = dO; f.o_ld = (long)Hq * hd;
-    f.k_seq_stride = (long)Hkv * ctx_max * hd; f.k_head_stride = (long)ctx_max * hd;
-    f.vt_seq_stride = (long)Hkv * hd * ctx_max; f.vt_head_stride = (long)hd * ctx_max;
-    f.q_off = di; f.q_len = di + B; f.kv_len = di + 2 * B; f.Hq = Hq; f.Hkv = Hkv;
-    f.scale = 1.0f / sqrtf((float)hd);
-    launch_flash(f, hd, true, B, max_p, e->st);
+    launch_flash(prefill_flash_args(dq, dk, dvt, dO, di, di + B, di + 2 * B, Hq, Hkv, ctx_max, e->dt), hd, true, B, max_p, e->st);
     return down_bf16(e, tb, dO, out, nq);
 }
 
@@ -313,7 +302,7 @@ extern "C" int sonic_bench_skinny(sonic_engine* e, int M, int N, int K, int vari
     if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in skinny bench");
     launch_synth_fill(0x77, (long)copies * N * K, 0.05f, 0.f, dW, nullptr, e->st);
     launch_synth_fill(0x78, (long)64 * K, 1.0f, 0.f, dX, nullptr, e->st);
-    SkinnyArgs a{}; a.X = dX; a.ldx = K; a.P = P; a.M = M; a.N = N; a.K = K; a.ksplit = ks; a.dt = e->dt;
+    SkinnyArgs a = skinny_args(dX, K, nullptr, P, M, N, K, ks, e->dt);
     for (int i = 0; i < copies; ++i) { a.W = dW + (size_t)(i % copies) * N * K; launch_skinny(a, e->st); }
     float ms;
     TRY(time_launches(e, iters, [&](int i) { a.W = dW + (size_t)(i % copies) * N * K; launch_skinny(a, e->st); }, &ms));
@@ -518,8 +507,7 @@ extern "C" int sonic_test_skinny_gu(sonic_engine* e, const float* X, const float
     bf16_t* dWt = tb.get<bf16_t>((size_t)N * K); bf16_t* dA = tb.get<bf16_t>((size_t)M * (N / 2));
     if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     launch_tile_weights_gu8(dW, dWt, N, K, e->st);
-    SkinnyArgs a{}; a.X = dX; a.ldx = K; a.W = dWt; a.M = M; a.N = N; a.K = K; a.ksplit = 1; a.dt = e->dt;
-    launch_skinny_gu(a, dA, e->st);
+    launch_skinny_gu(skinny_args(dX, K, dWt, nullptr, M, N, K, 1, e->dt), dA, e->st);
     return down_bf16(e, tb, dA, act, (size_t)M * (N / 2));
 }
 
@@ -600,11 +588,12 @@ extern "C" int sonic_test_swiglu_slab(sonic_engine* e, const float* slabs, int k
     return down_bf16(e, tb, dA, act, (size_t)rows * ff);
 }
 
-// The o_proj -> RMSNorm -> gate/up chain of one decoder layer as decode_step() launches it.  att [M][K], Wo [D][K], resid [rows_alloc][D] (in place: rows >= M must
-// come back untouched), ln_w [D], Wgu [2 ff][D] with gate / up rows interleaved in groups of 16 (as for sonic_test_skinny_gu).
+// The o_proj -> RMSNorm -> gate/up chain of one decoder layer through launch_o_gu, the function decode_step() launches it with (form = OGU_FUSED / _SPLIT_NORM /
+// _HALF_FUSED).  att [M][K], Wo [D][K], resid [rows_alloc][D] (in place: rows >= M must come back untouched), ln_w [D], Wgu [2 ff][D] with gate / up rows
+// interleaved in groups of 16 (as for sonic_test_skinny_gu).
 //   form 0: launch_skinny_o + launch_skinny_gu_norm                          (the default step)
 //   form 1: launch_skinny_o + launch_rmsnorm_ss + launch_skinny_gu           (the continuous loops' split form; hn_out [M][D])
-//   form 2: launch_skinny into slabs + launch_add_rmsnorm + launch_skinny_gu (the unfused form; hn_out [M][D])
+//   form 2: launch_skinny into slabs + launch_add_rmsnorm + launch_skinny_gu (fused gate/up behind an unfused o_proj; hn_out [M][D])
 // act_out [M][ff]; ss_out (optional, forms 0 / 1): the raw sum-of-squares partials [2 regions][D / 64][32 rows][4].
 // rmsnorm_ss_kernel splits a row's D / 64 partial groups into two halves and is launched with D / 8 <= 256 threads: form 1 needs D % 128 == 0 and D <= 2048.
 extern "C" int sonic_test_decode_o_gu(sonic_engine* e, const float* att, const float* Wo, float* resid, const float* ln_w, float eps, const float* Wgu, int form,
@@ -626,27 +615,11 @@ extern "C" int sonic_test_decode_o_gu(sonic_engine* e, const float* att, const f
     bf16_t* dR = up_bf16(e, tb, resid, (size_t)rows_alloc * D); float* dw = up_f32(e, tb, ln_w, D);
     bf16_t* dWg = up_bf16(e, tb, Wgu, (size_t)2 * ff * D); bf16_t* dWgt = tb.get<bf16_t>((size_t)2 * ff * D);
     bf16_t* dH = tb.get<bf16_t>((size_t)M * D); bf16_t* dAct = tb.get<bf16_t>((size_t)M * ff); float* dSS = tb.get<float>(nss);
+    float* P = form == OGU_HALF_FUSED ? tb.get<float>((size_t)skinny_pick_ksplit(D, K) * (((M + 15) / 16) * 16) * D) : nullptr;       // o_proj's slabs
     if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     launch_tile_weights(dWo, dWot, D, K, e->st);
     launch_tile_weights_gu8(dWg, dWgt, 2 * ff, D, e->st);
-    SkinnyArgs ga{}; ga.X = dR; ga.ldx = D; ga.W = dWgt; ga.M = M; ga.N = 2 * ff; ga.K = D; ga.ksplit = 1; ga.dt = e->dt; ga.err = e->n_active + 1;
-    if (form < 2) {
-        SkinnyArgs oa{}; oa.X = dA; oa.ldx = K; oa.W = dWot; oa.M = M; oa.N = D; oa.K = K; oa.ksplit = 1; oa.dt = e->dt;
-        launch_skinny_o(oa, dR, D, dSS, e->st);
-        if (form == 1) {
-            launch_rmsnorm_ss(dR, dSS, dw, dH, M, D, eps, e->st, e->dt);
-            ga.X = dH; launch_skinny_gu(ga, dAct, e->st);
-        } else
-            launch_skinny_gu_norm(ga, dAct, dSS, D / 16, dw, eps, e->st);
-    } else {
-        const int ks = skinny_pick_ksplit(D, K), mpad = ((M + 15) / 16) * 16;
-        float* P = tb.get<float>((size_t)ks * mpad * D);
-        if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
-        SkinnyArgs a{}; a.X = dA; a.ldx = K; a.W = dWot; a.P = P; a.M = M; a.N = D; a.K = K; a.ksplit = ks; a.dt = e->dt;
-        launch_skinny(a, e->st);
-        launch_add_rmsnorm(dR, P, ks, mpad, dw, dH, M, D, eps, e->st, e->dt);
-        ga.X = dH; launch_skinny_gu(ga, dAct, e->st);
-    }
+    launch_o_gu(e, form, OGuChain{dA, dWot, dR, dw, dWgt, 1, dH, dAct, dSS, P, nullptr, nullptr}, M, K, D, ff, eps);
     TRY(down_bf16(e, tb, dR, resid, (size_t)rows_alloc * D));
     if (form != 0) TRY(down_bf16(e, tb, dH, hn_out, (size_t)M * D));
     TRY(down_bf16(e, tb, dAct, act_out, (size_t)M * ff));
@@ -654,7 +627,7 @@ extern "C" int sonic_test_decode_o_gu(sonic_engine* e, const float* att, const f
     return SONIC_OK;
 }
 
-// The prefill's RoPE + KV append as run_prefill() launches it: packed qkv [n_tok][(Hq + 2 Hkv) * 128], the RoPE table cs [ctx_max][128], per token its sequence
+// The prefill's RoPE + KV append through run_prefill()'s own descriptor builder (rope_append_args): packed qkv [n_tok][(Hq + 2 Hkv) * 128], the RoPE table cs [ctx_max][128], per token its sequence
 // and position, per sequence its first packed token and length.  tiled = 1: rope_append_pf_kernel (q_off / q_len / n_seq / max_p passed); tiled = 0:
 // rope_append_kernel<T, false> (they stay null: option no_rope_tiles).  Kc / Vc [B][Hkv][ctx_max][128] and Vt [B][Hkv][128][vt_ld] are uploaded, and read back
 // after the launch; q_out [n_tok][Hq * 128].  The tile kernel takes a tile's first position from tok_pos of its first token and writes V^T for the 16 positions
@@ -685,11 +658,8 @@ extern "C" int sonic_test_rope_append(sonic_engine* e, const float* qkv, const f
     if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     HIPC(e, h2d(e, di, tok_seq, (size_t)n_tok * 4)); HIPC(e, h2d(e, di + n_tok, tok_pos, (size_t)n_tok * 4));
     HIPC(e, h2d(e, di + 2 * n_tok, q_off, (size_t)B * 4)); HIPC(e, h2d(e, di + 2 * n_tok + B, q_len, (size_t)B * 4));
-    RopeAppendArgs ra{}; ra.dt = e->dt;
-    ra.qkv = dqkv; ra.ld = N; ra.q_out = dq; ra.Kc = dk; ra.Vc = dv; ra.Vt = dvt; ra.vt_ld = vt_ld;
-    ra.tok_seq = di; ra.tok_pos = di + n_tok; ra.cs = dcs; ra.Hq = Hq; ra.Hkv = Hkv; ra.ctx_max = ctx_max; ra.n_tok = n_tok;
-    if (tiled) { ra.q_off = di + 2 * n_tok; ra.q_len = di + 2 * n_tok + B; ra.n_seq = B; ra.max_p = max_p; }
-    launch_rope_append(ra, false, e->st);
+    launch_rope_append(rope_append_args(dqkv, dq, dk, dv, dvt, vt_ld, di, di + n_tok, dcs, Hq, Hkv, ctx_max, n_tok, e->dt, tiled ? di + 2 * n_tok : nullptr, di + 2 * n_tok + B, B, max_p),
+                       false, e->st);
     TRY(down_bf16(e, tb, dq, q_out, nq));
     TRY(down_bf16(e, tb, dk, Kc, nc));
     TRY(down_bf16(e, tb, dv, Vc, nc));

@@ -322,3 +322,22 @@ void samp_pack(unsigned* w, float t, uint64_t seed);   // one row's three words 
 static inline bool hist_on(const sonic_engine* e) { return e->gen_on || e->opt_request_bias; }   // the rows' input_ids are kept: a guard or the request bias reads them
 int lp_check(sonic_engine* e, const char* who);     // SONIC_ERR_INVALID naming the option when token_logprobs is off on this handle
 int read_back_16(sonic_engine* e, const bf16_t* d, float* h, size_t n);   // n elements of a 16-bit device buffer -> fp32 on the host, through a temporary (engine_hooks.cpp; sonic_debug_read)
+
+// ------------------------------------------------------------------------------------------ launch builders and shared launch sequences (engine_stages.cpp)
+// One builder per launch descriptor: production and the hooks fill SkinnyArgs / DecodeAttnArgs / the prefill's FlashArgs and RopeAppendArgs through these and set
+// what only they need (i8, x_amax, pre_*, err, kt; dq, amax_out, big_out, pf) on the result.
+SkinnyArgs skinny_args(const bf16_t* X, long ldx, const bf16_t* W, float* P, int M, int N, int K, int ksplit, int dt);
+DecodeAttnArgs decode_attn_args(bf16_t* Kc, bf16_t* Vc, const float* P, const bf16_t* Q, int ksplit, int mpad, const float* cs, bf16_t* O, const int* kv_len,
+                                int Hq, int Hkv, int ctx_max, int dt);
+FlashArgs prefill_flash_args(const bf16_t* Q, const bf16_t* Kc, const bf16_t* Vt, bf16_t* O, const int* q_off, const int* q_len, const int* kv_len,
+                             int Hq, int Hkv, int ctx_max, int dt);
+RopeAppendArgs rope_append_args(const bf16_t* qkv, bf16_t* q_out, bf16_t* Kc, bf16_t* Vc, bf16_t* Vt, long vt_ld, const int* tok_seq, const int* tok_pos, const float* cs,
+                                int Hq, int Hkv, int ctx_max, int n_tok, int dt, const int* q_off, const int* q_len, int n_seq, int max_p);
+// the o_proj -> RMSNorm -> gate/up chain of a decoder layer (decode_step, sonic_test_decode_o_gu): its forms, and its buffers in the order of OGuChain's fields -
+// attention rows, tiled o_proj weights, residual rows (in place), norm weight, tiled gate/up weights and their interleave, norm output, SwiGLU output,
+// sum-of-squares partials (fused forms), slabs (the other two), diagnostics slots
+enum { OGU_FUSED = 0, OGU_SPLIT_NORM = 1, OGU_HALF_FUSED = 2, OGU_UNFUSED = 3 };
+struct OGuChain { const bf16_t *att, *Wo; bf16_t* x; const float* ln_w; const bf16_t* Wgu; int gu8; bf16_t *hn, *act; float *ss, *slab; long long *kt_o, *kt_gu; };
+void launch_o_gu(sonic_engine* e, int form, const OGuChain& c, int M, int K, int D, int ff, float eps);
+int upload_plan(sonic_engine* e, int R, const HostPlan& hp);       // the prefill's prologue, every kind: the request plan through the pinned staging buffer ...
+int reset_row_state(sonic_engine* e, int R, int n_tok);            // ... and the rows' counters, history, bias tables and sampling values for the greedy loop

@@ -183,26 +183,57 @@ int keep_rows(const sonic_dims& d, int n_valid_frames) {  // modeling_glmasr.py:
 }
 int frames_of(int n_samples) { return n_samples > 0 ? (n_samples + 159) / 160 : 0; }
 
+// ------------------------------------------------------------------------------------------ launch descriptors: one builder each (production and the hooks)
+SkinnyArgs skinny_args(const bf16_t* X, long ldx, const bf16_t* W, float* P, int M, int N, int K, int ksplit, int dt) {
+    SkinnyArgs a{};
+    a.X = X; a.ldx = ldx; a.W = W; a.P = P; a.M = M; a.N = N; a.K = K; a.ksplit = ksplit; a.dt = dt;
+    return a;
+}
+// P != null, the token step's form: the kernel sums the q|k|v slabs, ropes at kv_len - 1 and appends K / V itself; else Q holds the roped queries
+DecodeAttnArgs decode_attn_args(bf16_t* Kc, bf16_t* Vc, const float* P, const bf16_t* Q, int ksplit, int mpad, const float* cs, bf16_t* O, const int* kv_len,
+                                int Hq, int Hkv, int ctx_max, int dt) {
+    DecodeAttnArgs a{};
+    a.Q = Q; a.P = P; a.ksplit = ksplit; a.mpad = mpad; a.cs = cs; a.Kc = Kc; a.Vc = Vc; a.O = O; a.kv_len = kv_len; a.Hq = Hq; a.Hkv = Hkv; a.ctx_max = ctx_max;
+    a.scale = 1.0f / sqrtf(128.f); a.dt = dt;            // head dim 128: the only one the decoder's kernels have (sonic_create refuses others)
+    return a;
+}
+// the prefill's causal attention: packed ragged queries, K in cache layout [B][Hkv][ctx_max][128], V^T [B][Hkv][128][ctx_max]
+FlashArgs prefill_flash_args(const bf16_t* Q, const bf16_t* Kc, const bf16_t* Vt, bf16_t* O, const int* q_off, const int* q_len, const int* kv_len,
+                             int Hq, int Hkv, int ctx_max, int dt) {
+    FlashArgs f{}; f.dt = dt;
+    f.Q = Q; f.q_ld = Hq * 128L; f.K = Kc; f.k_ld = 128; f.Vt = Vt; f.vt_ld = ctx_max; f.O = O; f.o_ld = Hq * 128L;
+    f.k_seq_stride = (long)Hkv * ctx_max * 128; f.k_head_stride = ctx_max * 128L; f.vt_seq_stride = (long)Hkv * 128 * ctx_max; f.vt_head_stride = 128L * ctx_max;
+    f.q_off = q_off; f.q_len = q_len; f.kv_len = kv_len; f.Hq = Hq; f.Hkv = Hkv; f.scale = 1.0f / sqrtf(128.f);
+    return f;
+}
+// the prefill's RoPE + KV append on packed qkv [n_tok][(Hq + 2 Hkv) * 128].  q_off != null: tiles of 16 positions per sequence (round 5); else one token at a time
+RopeAppendArgs rope_append_args(const bf16_t* qkv, bf16_t* q_out, bf16_t* Kc, bf16_t* Vc, bf16_t* Vt, long vt_ld, const int* tok_seq, const int* tok_pos, const float* cs,
+                                int Hq, int Hkv, int ctx_max, int n_tok, int dt, const int* q_off, const int* q_len, int n_seq, int max_p) {
+    RopeAppendArgs ra{}; ra.dt = dt;
+    ra.qkv = qkv; ra.ld = (Hq + 2 * Hkv) * 128; ra.q_out = q_out; ra.Kc = Kc; ra.Vc = Vc; ra.Vt = Vt; ra.vt_ld = vt_ld;
+    ra.tok_seq = tok_seq; ra.tok_pos = tok_pos; ra.cs = cs; ra.Hq = Hq; ra.Hkv = Hkv; ra.ctx_max = ctx_max; ra.n_tok = n_tok;
+    if (q_off) { ra.q_off = q_off; ra.q_len = q_len; ra.n_seq = n_seq; ra.max_p = max_p; }
+    return ra;
+}
+
 static long long* kt_slot(sonic_engine* e, int l, int slot) { return (e->kt && l == e->kt_layer) ? e->kt + (long)slot * KT_SLOT_BLOCKS * 8 : nullptr; }
 void skinny(sonic_engine* e, const bf16_t* X, long ldx, const bf16_t* W, float* P, int M, int N, int K, int* ks_out, long long* kt) {
-    SkinnyArgs a{}; a.kt = kt;
-    a.X = X; a.ldx = ldx; a.W = W; a.P = P; a.M = M; a.N = N; a.K = K; a.ksplit = skinny_pick_ksplit(N, K); a.dt = e->dt;
+    SkinnyArgs a = skinny_args(X, ldx, W, P, M, N, K, skinny_pick_ksplit(N, K), e->dt); a.kt = kt;
     if (ks_out) *ks_out = a.ksplit;
     launch_skinny(a, e->st);
 }
-// int8 decode step: quantised rows Xq [M][K] x fragment-tiled int8 weights -> int32 slabs (dequantised by the consumer)
-// the same projection on UNQUANTISED fp16 rows with their gathered absmax: the kernel quantises its X slice while staging it
-static int skinny_i8_xq(sonic_engine* e, const bf16_t* X16, const float* amax, const int8_t* Wt, float* P, int M, int N, int K) {
-    SkinnyArgs a{};
-    a.X = X16; a.ldx = K; a.W = (const bf16_t*)Wt; a.P = P; a.M = M; a.N = N; a.K = K; a.ksplit = skinny_pick_ksplit_i8(N, K); a.i8 = 1; a.x_amax = amax;
+// int8 decode step: rows X [M][K] x fragment-tiled int8 weights -> int32 slabs (dequantised by the consumer).  amax == null: X holds the quantised rows; else the
+// UNQUANTISED fp16 rows with their gathered absmax partials, and the kernel quantises its X slice while staging it.  (The int8 kernels do not read dt.)
+static int skinny_i8(sonic_engine* e, const void* X, const float* amax, const int8_t* Wt, float* P, int M, int N, int K) {
+    SkinnyArgs a = skinny_args((const bf16_t*)X, K, (const bf16_t*)Wt, P, M, N, K, skinny_pick_ksplit_i8(N, K), DT_BF16); a.i8 = 1; a.x_amax = amax;
     launch_skinny(a, e->st);
     return a.ksplit;
 }
-static int skinny_i8(sonic_engine* e, const int8_t* Xq, const int8_t* Wt, float* P, int M, int N, int K) {
-    SkinnyArgs a{};
-    a.X = (const bf16_t*)Xq; a.ldx = K; a.W = (const bf16_t*)Wt; a.P = P; a.M = M; a.N = N; a.K = K; a.ksplit = skinny_pick_ksplit_i8(N, K); a.i8 = 1;
-    launch_skinny(a, e->st);
-    return a.ksplit;
+// a token step's attention for layer l: the q|k|v slabs -> satt, RoPE + KV append fused into the kernel
+static DecodeAttnArgs step_attn_args(sonic_engine* e, int l, int ks, int mpad, int dt) {
+    const sonic_dims& d = e->d;
+    const size_t kvoff = (size_t)l * e->Bm * d.dec_kv_heads * e->max_ctx * d.dec_head_dim;
+    return decode_attn_args(e->Kc + kvoff, e->Vc + kvoff, e->slab, nullptr, ks, mpad, e->dec_cs, e->satt, e->kv_len, d.dec_heads, d.dec_kv_heads, e->max_ctx, dt);
 }
 
 GreedyArgs greedy_args(sonic_engine* e, int R, bool dump) {
@@ -224,114 +255,130 @@ GreedyArgs greedy_args(sonic_engine* e, int R, bool dump) {
     return g;
 }
 
+// The o_proj -> RMSNorm -> gate/up chain of one decoder layer on M rows, att [M][K] -> act [M][ff], residual rows x [.][D] updated in place.  decode_step and
+// sonic_test_decode_o_gu both launch it here.  kt_o / kt_gu: the fused kernels' diagnostics slots; the error word of the fused gate/up kernel is the engine's.
+//   OGU_FUSED       o_proj + residual add + row sum-of-squares partials (ss) -> gate/up with RMSNorm applied while staging X + SwiGLU: two kernels for four
+//   OGU_SPLIT_NORM  33 .. 64 rows: the rows are normalised ONCE by their own small kernel (from the same partials, in the same order: same bits) into hn and gate/up
+//                   stages them as they are - 256 blocks each normalising all 64 rows was the longest single piece of the 64-row step
+//   OGU_HALF_FUSED  o_proj into slabs -> add+RMSNorm into hn -> gate/up + SwiGLU in one kernel, no slabs
+//   OGU_UNFUSED     ... -> gate/up into slabs -> SwiGLU (gu8: the weights' gate / up interleave, launch_swiglu_slab)
+void launch_o_gu(sonic_engine* e, int form, const OGuChain& c, int M, int K, int D, int ff, float eps) {
+    const int dt = e->dt, mpad = ((M + 15) / 16) * 16;
+    if (form == OGU_FUSED || form == OGU_SPLIT_NORM) {
+        SkinnyArgs oa = skinny_args(c.att, K, c.Wo, nullptr, M, D, K, 1, dt); oa.kt = c.kt_o;
+        launch_skinny_o(oa, c.x, D, c.ss, e->st);
+        SkinnyArgs ga = skinny_args(c.x, D, c.Wgu, nullptr, M, 2 * ff, D, 1, dt); ga.kt = c.kt_gu; ga.err = e->n_active + 1;
+        if (form == OGU_SPLIT_NORM) {
+            launch_rmsnorm_ss(c.x, c.ss, c.ln_w, c.hn, M, D, eps, e->st, dt);
+            ga.X = c.hn; launch_skinny_gu(ga, c.act, e->st);
+        } else
+            launch_skinny_gu_norm(ga, c.act, c.ss, D / 16, c.ln_w, eps, e->st);
+        return;
+    }
+    int ks;
+    skinny(e, c.att, K, c.Wo, c.slab, M, D, K, &ks);
+    launch_add_rmsnorm(c.x, c.slab, ks, mpad, c.ln_w, c.hn, M, D, eps, e->st, dt);
+    if (form == OGU_HALF_FUSED) { launch_skinny_gu(skinny_args(c.hn, D, c.Wgu, nullptr, M, 2 * ff, D, 1, dt), c.act, e->st); return; }
+    skinny(e, c.hn, D, c.Wgu, c.slab, M, 2 * ff, D, &ks);
+    launch_swiglu_slab(c.slab, ks, mpad, 2 * ff, c.act, M, e->st, dt, c.gu8);
+}
+
+// The form of the 16-bit token step for R rows, decided once: the layer loop and step_launches_per_layer read it.
+//   gemv        1 - 4 rows, opt-in (decode_gemv): the GEMV chain
+//   fuse_gu / fuse_o   the fused gate/up kernel, and the fused o_proj in front of it, take the shape (launch_o_gu's forms)
+//   pre         <= 2 rows (the B = 1 call shape of BASELINE configs 1 and 5; round 6): no standalone add+RMSNorm launch behind down_proj - the next q|k|v projection
+//               (and, behind the last layer, the lm_head) sums the slabs, adds the residual and normalises its rows itself (skinny_xs_kernel<.., PRE>, the same
+//               arithmetic statement by statement: same bits).  down_proj then writes its slabs to slab2 (the consumer writes slab while other blocks of it still
+//               read) and the residual stream alternates between sx and sx2
+//   split_norm  33 .. 64 rows, on request or inside a continuous loop's graph (gu64_split_norm): OGU_SPLIT_NORM.  Never with pre (rows), so its rows are in sx
+struct StepForm { bool gemv, pre, fuse_o, fuse_gu, split_norm; };
+static StepForm step_form(sonic_engine* e, int R) {
+    const sonic_dims& d = e->d;
+    const int D = d.dec_d;
+    // wgu_t8 is set for every decoder layer or for none: engine_weights.cpp asks skinny_gu_eligible(1, 2 ff, d) of the model's dims under one lock, the same answer
+    // layer after layer (and never in int8 mode) - so layer 0 speaks for all
+    const bool gu8 = d.dec_layers > 0 && e->dec[0].wgu_t8;
+    StepForm f{};
+    f.gemv = e->opt_decode_gemv && R <= GEMV_MAX_ROWS && gu8 && gemv_eligible(R, e->qkvN, D, GEMV_SLAB_NORM) && gemv_eligible(R, D, e->QD, GEMV_RESID) &&
+             gemv_eligible(R, 2 * d.dec_ff, D, GEMV_SWIGLU_NORM) && gemv_eligible(R, D, d.dec_ff, GEMV_RESID) && gemv_eligible(R, d.vocab, D, GEMV_SLAB_NORM);
+    f.fuse_gu = gu8 && skinny_gu_eligible(R, 2 * d.dec_ff, D);
+    f.fuse_o = f.fuse_gu && skinny_o_eligible(R, D, e->QD);
+    f.pre = f.fuse_o && !e->opt_no_pre_norm && skinny_pre_eligible(R, e->qkvN, D) && skinny_pre_eligible(R, d.vocab, D) && D % 8 == 0;
+    f.split_norm = f.fuse_o && (e->opts.gu64_split_norm > 0 || (e->opts.gu64_split_norm == 0 && e->cap_svc)) && R > 32 && D % 128 == 0 && D <= 2048;
+    return f;
+}
+// 1 - 4 rows, opt-in (gemv.hip): q|k|v (norm inside) -> attention -> o_proj (+ residual) -> gate/up (norm inside, SwiGLU) -> down_proj (+ residual); lm_head (norm inside)
+static void decode_step_gemv(sonic_engine* e, int R, bool dump) {
+    const sonic_dims& d = e->d;
+    const int D = d.dec_d, mpad = ((R + 15) / 16) * 16, dt = e->dt;
+    auto gv = [&](int mode, const bf16_t* X, long ldx, const bf16_t* W, int N, int K, const float* nw, float* P, bf16_t* resid, bf16_t* act) {
+        GemvArgs g{}; g.X = X; g.ldx = ldx; g.W = W; g.M = R; g.N = N; g.K = K; g.dt = dt; g.norm_w = nw; g.eps = d.dec_rms_eps; g.P = P; g.resid = resid; g.ldr = D; g.act = act;
+        launch_gemv(g, mode, e->st);
+    };
+    for (int l = 0; l < d.dec_layers; ++l) {
+        const DecLayerW& L = e->dec[l];
+        gv(GEMV_SLAB_NORM, e->sx, D, L.wqkv_t, e->qkvN, D, L.ln1, e->slab, nullptr, nullptr);
+        launch_decode_attn(step_attn_args(e, l, 1, mpad, dt), R, e->st);
+        gv(GEMV_RESID, e->satt, e->QD, L.wo_t, D, e->QD, nullptr, nullptr, e->sx, nullptr);
+        gv(GEMV_SWIGLU_NORM, e->sx, D, L.wgu_t8, 2 * d.dec_ff, D, L.ln2, nullptr, nullptr, e->sact);
+        gv(GEMV_RESID, e->sact, d.dec_ff, L.wdown_t, D, d.dec_ff, nullptr, nullptr, e->sx, nullptr);
+    }
+    gv(GEMV_SLAB_NORM, e->sx, D, e->embed_t, d.vocab, D, e->dec_nw, e->lslab, nullptr, nullptr);
+    GreedyArgs g = greedy_args(e, R, dump);
+    g.ksplit = 1;
+    launch_greedy(g, e->st);
+}
+// experiment (decode_prefetch bits 0 / 1): the attention launch covers R x Hkv of the 256 CUs - the others stream the weights of the kernels behind it
+static void attn_prefetch(sonic_engine* e, const DecLayerW& L, int R, DecodeAttnArgs* da) {
+    const sonic_dims& d = e->d;
+    if (!(e->opts.decode_prefetch & 3) || R * d.dec_kv_heads > 128 || !L.wo_t) return;
+    da->pf_y = (256 - R * d.dec_kv_heads) / R;
+    if (e->opts.decode_prefetch & 1) da->pf[0] = PrefetchRange{L.wo_t, (long)d.dec_d * e->QD * 2};
+    if ((e->opts.decode_prefetch & 2) && L.wgu_t8) da->pf[1] = PrefetchRange{L.wgu_t8, (long)d.dec_ff * d.dec_d * 2};       // the first half of gate/up (25 MB)
+}
+
 // one decode step for R rows: sx ([R][d]) -> next token (generation/utils.py:2876-2943)
 static void decode_step(sonic_engine* e, int R, bool dump) {
     if (e->f32) { decode_step_f32(e, R, dump); return; }
     if (e->i8) { decode_step_i8(e, R, dump); return; }
     const sonic_dims& d = e->d;
     const int D = d.dec_d, mpad = ((R + 15) / 16) * 16, dt = e->dt;
-    if (e->opt_decode_gemv && R <= GEMV_MAX_ROWS && d.dec_layers > 0 && e->dec[0].wgu_t8 && gemv_eligible(R, e->qkvN, D, GEMV_SLAB_NORM) && gemv_eligible(R, D, e->QD, GEMV_RESID) &&
-        gemv_eligible(R, 2 * d.dec_ff, D, GEMV_SWIGLU_NORM) && gemv_eligible(R, D, d.dec_ff, GEMV_RESID) && gemv_eligible(R, d.vocab, D, GEMV_SLAB_NORM)) {
-        // 1 - 4 rows, opt-in (gemv.hip): q|k|v (norm inside) -> attention -> o_proj (+ residual) -> gate/up (norm inside, SwiGLU) -> down_proj (+ residual); lm_head (norm inside)
-        e->step_launches_per_layer = 5;
-        auto gv = [&](int mode, const bf16_t* X, long ldx, const bf16_t* W, int N, int K, const float* nw, float* P, bf16_t* resid, bf16_t* act) {
-            GemvArgs g{}; g.X = X; g.ldx = ldx; g.W = W; g.M = R; g.N = N; g.K = K; g.dt = dt; g.norm_w = nw; g.eps = d.dec_rms_eps; g.P = P; g.resid = resid; g.ldr = D; g.act = act;
-            launch_gemv(g, mode, e->st);
-        };
-        for (int l = 0; l < d.dec_layers; ++l) {
-            const DecLayerW& L = e->dec[l];
-            const size_t kvoff = (size_t)l * e->Bm * d.dec_kv_heads * e->max_ctx * d.dec_head_dim;
-            gv(GEMV_SLAB_NORM, e->sx, D, L.wqkv_t, e->qkvN, D, L.ln1, e->slab, nullptr, nullptr);
-            DecodeAttnArgs da{};
-            da.P = e->slab; da.ksplit = 1; da.mpad = mpad; da.cs = e->dec_cs; da.dt = dt;
-            da.Kc = e->Kc + kvoff; da.Vc = e->Vc + kvoff; da.O = e->satt; da.kv_len = e->kv_len; da.Hq = d.dec_heads; da.Hkv = d.dec_kv_heads;
-            da.ctx_max = e->max_ctx; da.scale = 1.0f / sqrtf((float)d.dec_head_dim);
-            launch_decode_attn(da, R, e->st);
-            gv(GEMV_RESID, e->satt, e->QD, L.wo_t, D, e->QD, nullptr, nullptr, e->sx, nullptr);
-            gv(GEMV_SWIGLU_NORM, e->sx, D, L.wgu_t8, 2 * d.dec_ff, D, L.ln2, nullptr, nullptr, e->sact);
-            gv(GEMV_RESID, e->sact, d.dec_ff, L.wdown_t, D, d.dec_ff, nullptr, nullptr, e->sx, nullptr);
-        }
-        gv(GEMV_SLAB_NORM, e->sx, D, e->embed_t, d.vocab, D, e->dec_nw, e->lslab, nullptr, nullptr);
-        GreedyArgs g = greedy_args(e, R, dump);
-        g.ksplit = 1;
-        launch_greedy(g, e->st);
-        return;
-    }
-    int ks;
+    const StepForm f = step_form(e, R);
+    const int ogu = !f.fuse_gu ? OGU_UNFUSED : !f.fuse_o ? OGU_HALF_FUSED : f.split_norm ? OGU_SPLIT_NORM : OGU_FUSED;
+    e->step_launches_per_layer = f.gemv ? 5 : !f.fuse_o ? 8 : f.pre ? 5 : f.split_norm ? 7 : 6;
+    if (f.gemv) { decode_step_gemv(e, R, dump); return; }
     if (D > 8192) launch_rmsnorm(e->sx, e->dec[0].ln1, e->shn, R, D, d.dec_rms_eps, nullptr, e->st, dt);   // else: done by the greedy kernel of the previous step
-    // <= 2 rows (the B = 1 call shape of BASELINE configs 1 and 5; round 6): no standalone add+RMSNorm launch behind down_proj - the next q|k|v projection
-    // (and, behind the last layer, the lm_head) sums the slabs, adds the residual and normalises its rows itself (skinny_xs_kernel<.., PRE>, the same
-    // arithmetic statement by statement: same bits).  Five launches per layer instead of six.  down_proj then writes its slabs to slab2 (the consumer
-    // writes slab while other blocks of it still read) and the residual stream alternates between sx and sx2.
-    const bool fuse_all = !d.dec_layers ? false : (e->dec[0].wgu_t8 && skinny_gu_eligible(R, 2 * d.dec_ff, D) && skinny_o_eligible(R, D, e->QD));
-    const bool pre = fuse_all && !e->opt_no_pre_norm && skinny_pre_eligible(R, e->qkvN, D) && skinny_pre_eligible(R, d.vocab, D) && D % 8 == 0;
     bf16_t* resid = e->sx;                               // where the residual rows live right now
-    int ks_down = 0;
-    e->step_launches_per_layer = !fuse_all ? 8 : pre ? 5 : ((e->opts.gu64_split_norm > 0 || (e->opts.gu64_split_norm == 0 && e->cap_svc)) && R > 32 && D % 128 == 0 && D <= 2048) ? 7 : 6;
+    int ks, ks_down = 0;
     auto skinny_pre = [&](const bf16_t* W, float* P, int N, const float* nw, bf16_t* xout, int* ks_out, long long* kt) {
-        SkinnyArgs a{}; a.kt = kt;
-        a.X = resid; a.ldx = D; a.W = W; a.P = P; a.M = R; a.N = N; a.K = D; a.ksplit = skinny_pick_ksplit(N, D); a.dt = dt;
+        SkinnyArgs a = skinny_args(resid, D, W, P, R, N, D, skinny_pick_ksplit(N, D), dt); a.kt = kt;
         a.pre_P = e->slab2; a.pre_ks = ks_down; a.pre_mpad = mpad; a.pre_x = resid; a.pre_xout = xout; a.pre_w = nw; a.pre_eps = d.dec_rms_eps;
         if (ks_out) *ks_out = a.ksplit;
         launch_skinny(a, e->st);
     };
     for (int l = 0; l < d.dec_layers; ++l) {
         const DecLayerW& L = e->dec[l];
-        const size_t kvoff = (size_t)l * e->Bm * d.dec_kv_heads * e->max_ctx * d.dec_head_dim;
-        if (pre && l > 0) {
+        if (f.pre && l > 0) {
             bf16_t* other = resid == e->sx ? e->sx2 : e->sx;
             skinny_pre(L.wqkv_t, e->slab, e->qkvN, L.ln1, other, &ks, kt_slot(e, l, 0));
             resid = other;
         } else
-        skinny(e, e->shn, D, L.wqkv_t, e->slab, R, e->qkvN, D, &ks, kt_slot(e, l, 0));
-        DecodeAttnArgs da{}; da.kt = kt_slot(e, l, 1);
-        da.P = e->slab; da.ksplit = ks; da.mpad = mpad; da.cs = e->dec_cs; da.dt = dt;     // RoPE + KV append fused into the attention kernel
-        da.Kc = e->Kc + kvoff; da.Vc = e->Vc + kvoff; da.O = e->satt; da.kv_len = e->kv_len; da.Hq = d.dec_heads; da.Hkv = d.dec_kv_heads;
-        da.ctx_max = e->max_ctx; da.scale = 1.0f / sqrtf((float)d.dec_head_dim);
-        if ((e->opts.decode_prefetch & 3) && R * d.dec_kv_heads <= 128 && L.wo_t) {
-            // experiment: the attention launch covers R x Hkv of the 256 CUs - the others stream the weights of the kernels behind it
-            da.pf_y = (256 - R * d.dec_kv_heads) / R;
-            if (e->opts.decode_prefetch & 1) da.pf[0] = PrefetchRange{L.wo_t, (long)D * e->QD * 2};
-            if ((e->opts.decode_prefetch & 2) && L.wgu_t8) da.pf[1] = PrefetchRange{L.wgu_t8, (long)d.dec_ff * D * 2};       // the first half of gate/up (25 MB)
-        }
+            skinny(e, e->shn, D, L.wqkv_t, e->slab, R, e->qkvN, D, &ks, kt_slot(e, l, 0));
+        DecodeAttnArgs da = step_attn_args(e, l, ks, mpad, dt); da.kt = kt_slot(e, l, 1);
+        attn_prefetch(e, L, R, &da);
         launch_decode_attn(da, R, e->st);
-        const bool fuse_gu = L.wgu_t8 && skinny_gu_eligible(R, 2 * d.dec_ff, D);
-        const bool fuse_o = fuse_gu && skinny_o_eligible(R, D, e->QD);
-        if (fuse_o) {
-            // o_proj + residual add (+ row sum-of-squares partials) -> gate/up with RMSNorm applied while staging X + SwiGLU:
-            // two kernels instead of o_proj, add+RMSNorm, gate/up, SwiGLU
-            SkinnyArgs oa{}; oa.X = e->satt; oa.ldx = e->QD; oa.W = L.wo_t; oa.M = R; oa.N = D; oa.K = e->QD; oa.ksplit = 1; oa.dt = dt; oa.kt = kt_slot(e, l, 2);
-            launch_skinny_o(oa, resid, D, e->ssq, e->st);
-            SkinnyArgs ga{}; ga.X = resid; ga.ldx = D; ga.W = L.wgu_t8; ga.M = R; ga.N = 2 * d.dec_ff; ga.K = D; ga.ksplit = 1; ga.dt = dt; ga.kt = kt_slot(e, l, 3); ga.err = e->n_active + 1;
-            if ((e->opts.gu64_split_norm > 0 || (e->opts.gu64_split_norm == 0 && e->cap_svc)) && R > 32 && D % 128 == 0 && D <= 2048) {
-                // 33 .. 64 rows: the rows are normalised ONCE by their own small kernel (from the same partials, in the same order: same bits) and
-                // gate/up stages them as they are - 256 blocks each normalising all 64 rows was the longest single piece of the 64-row step
-                launch_rmsnorm_ss(e->sx, e->ssq, L.ln2, e->shn, R, D, d.dec_rms_eps, e->st, dt);
-                ga.X = e->shn; launch_skinny_gu(ga, e->sact, e->st);
-            } else
-            launch_skinny_gu_norm(ga, e->sact, e->ssq, D / 16, L.ln2, d.dec_rms_eps, e->st);
-        } else {
-        skinny(e, e->satt, e->QD, L.wo_t, e->slab, R, D, e->QD, &ks);
-        launch_add_rmsnorm(e->sx, e->slab, ks, mpad, L.ln2, e->shn, R, D, d.dec_rms_eps, e->st, dt);
-        if (fuse_gu) {          // gate/up + SwiGLU in one kernel, no slabs
-            SkinnyArgs ga{}; ga.X = e->shn; ga.ldx = D; ga.W = L.wgu_t8; ga.M = R; ga.N = 2 * d.dec_ff; ga.K = D; ga.ksplit = 1; ga.dt = dt;
-            launch_skinny_gu(ga, e->sact, e->st);
-        } else {
-            skinny(e, e->shn, D, L.wgu_t ? L.wgu_t : L.wgu_t8, e->slab, R, 2 * d.dec_ff, D, &ks);
-            launch_swiglu_slab(e->slab, ks, mpad, 2 * d.dec_ff, e->sact, R, e->st, dt, L.wgu_t ? 0 : 1);
-        }
-        }
-        skinny(e, e->sact, d.dec_ff, L.wdown_t, pre ? e->slab2 : e->slab, R, D, d.dec_ff, &ks, kt_slot(e, l, 4));
+        launch_o_gu(e, ogu, OGuChain{e->satt, L.wo_t, resid, L.ln2, L.wgu_t ? L.wgu_t : L.wgu_t8, L.wgu_t ? 0 : 1, e->shn, e->sact, e->ssq, e->slab, kt_slot(e, l, 2), kt_slot(e, l, 3)},
+                    R, e->QD, D, d.dec_ff, d.dec_rms_eps);
+        skinny(e, e->sact, d.dec_ff, L.wdown_t, f.pre ? e->slab2 : e->slab, R, D, d.dec_ff, &ks, kt_slot(e, l, 4));
         ks_down = ks;
-        if (pre) continue;                               // the next layer's q|k|v (or the lm_head) consumes the slabs
+        if (f.pre) continue;                             // the next layer's q|k|v (or the lm_head) consumes the slabs
         const float* nw = (l + 1 < d.dec_layers) ? e->dec[l + 1].ln1 : e->dec_nw;
         PrefetchRange pfq{nullptr, 0};
         if ((e->opts.decode_prefetch & 4) && l + 1 < d.dec_layers && e->dec[l + 1].wqkv_t) pfq = PrefetchRange{e->dec[l + 1].wqkv_t, (long)e->qkvN * D * 2};
         launch_add_rmsnorm(e->sx, e->slab, ks, mpad, nw, e->shn, R, D, d.dec_rms_eps, e->st, dt, nullptr, nullptr, &pfq, R < 256 ? 256 - R : 0);
     }
-    if (pre) skinny_pre(e->embed_t, e->lslab, d.vocab, e->dec_nw, nullptr, nullptr, nullptr);   // tied lm_head behind the last layer's slabs (the updated residual is not needed again)
-    else
-    skinny(e, e->shn, D, e->embed_t, e->lslab, R, d.vocab, D, nullptr);   // tied lm_head (modeling_glmasr.py:517)
+    if (f.pre) skinny_pre(e->embed_t, e->lslab, d.vocab, e->dec_nw, nullptr, nullptr, nullptr);   // tied lm_head behind the last layer's slabs (the updated residual is not needed again)
+    else skinny(e, e->shn, D, e->embed_t, e->lslab, R, d.vocab, D, nullptr);                    // tied lm_head (modeling_glmasr.py:517)
     launch_greedy(greedy_args(e, R, dump), e->st);
 }
 
@@ -353,12 +400,8 @@ void decode_step_i8(sonic_engine* e, int R, bool dump) {
     };
     for (int l = 0; l < d.dec_layers; ++l) {
         const DecLayerW& L = e->dec[l];
-        const size_t kvoff = (size_t)l * e->Bm * d.dec_kv_heads * e->max_ctx * d.dec_head_dim;
-        int ks = skinny_i8(e, e->hn_q, L.qqkv.cbt, e->slab, R, e->qkvN, D);
-        DecodeAttnArgs da{};
-        da.P = e->slab; da.ksplit = ks; da.mpad = mpad; da.cs = e->dec_cs; da.dt = DT_F16; da.dq = deq(q_hn, L.qqkv, D, e->shn, e->qkvN);
-        da.Kc = e->Kc + kvoff; da.Vc = e->Vc + kvoff; da.O = e->satt; da.kv_len = e->kv_len; da.Hq = d.dec_heads; da.Hkv = d.dec_kv_heads;
-        da.ctx_max = e->max_ctx; da.scale = 1.0f / sqrtf((float)d.dec_head_dim);
+        int ks = skinny_i8(e, e->hn_q, nullptr, L.qqkv.cbt, e->slab, R, e->qkvN, D);
+        DecodeAttnArgs da = step_attn_args(e, l, ks, mpad, DT_F16); da.dq = deq(q_hn, L.qqkv, D, e->shn, e->qkvN);
         // o_proj's input rows are spread over the attention blocks of 4 kv heads: they gather the row absmax (atomicMax), o_proj quantises on the
         // fly and its consumer lists the outliers itself - no one-block-per-row quantisation launch in between (option i8_no_xq: the round-2 form)
         const bool xq = !e->opt_i8_no_xq && d.dec_kv_heads <= 4 && !e->opts.decode_attn_v1;   // the partials are [64][4]: one per kv-head block
@@ -366,17 +409,17 @@ void decode_step_i8(sonic_engine* e, int R, bool dump) {
         launch_decode_attn(da, R, e->st);
         DeqInfo dq;
         if (xq) {
-            ks = skinny_i8_xq(e, e->satt, e->amax_att, L.qo.cbt, e->slab, R, D, e->QD);
+            ks = skinny_i8(e, e->satt, e->amax_att, L.qo.cbt, e->slab, R, D, e->QD);
             dq = deq(q_att, L.qo, e->QD, e->satt, D); dq.sca = e->amax_att; dq.scan = 1; dq.scan_cnt = e->big_att;
         } else {
             launch_quant_rows(e->satt, e->QD, R, e->QD, q_att, e->st);
-            ks = skinny_i8(e, e->att_q, L.qo.cbt, e->slab, R, D, e->QD);
+            ks = skinny_i8(e, e->att_q, nullptr, L.qo.cbt, e->slab, R, D, e->QD);
             dq = deq(q_att, L.qo, e->QD, e->satt, D);
         }
         launch_add_rmsnorm(e->sx, e->slab, ks, mpad, L.ln2, e->shn, R, D, d.dec_rms_eps, e->st, DT_F16, &dq, &q_hn);
-        ks = skinny_i8(e, e->hn_q, L.qgu.cbt, e->slab, R, 2 * FF, D);
+        ks = skinny_i8(e, e->hn_q, nullptr, L.qgu.cbt, e->slab, R, 2 * FF, D);
         launch_swiglu_quant(e->slab, ks, mpad, FF, e->sact, R, deq(q_hn, L.qgu, D, e->shn, 2 * FF), q_act, e->st);
-        ks = skinny_i8(e, e->act_q, L.qdown.cbt, e->slab, R, D, FF);
+        ks = skinny_i8(e, e->act_q, nullptr, L.qdown.cbt, e->slab, R, D, FF);
         dq = deq(q_act, L.qdown, FF, e->sact, D);
         const float* nw = (l + 1 < d.dec_layers) ? e->dec[l + 1].ln1 : e->dec_nw;
         launch_add_rmsnorm(e->sx, e->slab, ks, mpad, nw, e->shn, R, D, d.dec_rms_eps, e->st, DT_F16, &dq, &q_hn);
@@ -431,35 +474,43 @@ static int plan_requests(sonic_engine* e, const int32_t* req_win, int R, const i
     return SONIC_OK;
 }
 
-static int run_prefill(sonic_engine* e, int R, const HostPlan& hp) {
-    const sonic_dims& d = e->d;
-    const int D = d.dec_d, M = hp.n_tok, dt = e->dt;
-    const QGroup grp{e->tok_seq, 1, R};        // one reference call = the prompt rows of one request
-    // The plan goes through pinned memory, so the copies are truly asynchronous and nothing here waits for the encoder that is still running
-    // on this stream (a pageable source forced a stream synchronise between encoder and prefill: a host-dependent bubble in every batch).
-    // plan_h = the staging buffer run_to_first_token picked for this run (free: the run that used it last has had its copies waited for).
-    {
-        int* h = e->plan_h; size_t o = 0;
-        auto put = [&](int* dst, const int* srcv, size_t n) -> hipError_t {
-            if (o + n > e->plan_cap) return hipErrorInvalidValue;
-            memcpy(h + o, srcv, n * 4);
-            hipError_t r = hipMemcpyAsync(dst, h + o, n * 4, hipMemcpyHostToDevice, e->st);
-            o += n; return r;
-        };
-        HIPC(e, put(e->src, hp.src.data(), (size_t)M)); HIPC(e, put(e->tok_seq, hp.tok_seq.data(), (size_t)M)); HIPC(e, put(e->tok_pos_pf, hp.tok_pos.data(), (size_t)M));
-        HIPC(e, put(e->q_off, hp.q_off.data(), (size_t)R)); HIPC(e, put(e->q_len, hp.q_len.data(), (size_t)R)); HIPC(e, put(e->kv_len, hp.q_len.data(), (size_t)R));
-        HIPC(e, put(e->last_row, hp.last_row.data(), (size_t)R)); HIPC(e, put(e->max_new_d, hp.max_new.data(), (size_t)R));
-        HIPC(e, put(e->n_active, &R, 1));
-        HIPC(e, hipEventRecord(e->plan_ev[e->plan_idx], e->st));       // every copy out of this buffer (win_req included) is older than this event
-        e->plan_busy[e->plan_idx] = true;
-    }
+// The prologue of every kind's prefill.  upload_plan: the request plan goes through pinned memory, so the copies are truly asynchronous and nothing here waits for the
+// encoder that is still running on this stream (a pageable source forced a stream synchronise between encoder and prefill: a host-dependent bubble in every batch).
+// plan_h = the staging buffer run_to_first_token picked for this run (free: the run that used it last has had its copies waited for).
+int upload_plan(sonic_engine* e, int R, const HostPlan& hp) {
+    const size_t M = (size_t)hp.n_tok;
+    int* h = e->plan_h; size_t o = 0;
+    auto put = [&](int* dst, const int* srcv, size_t n) -> hipError_t {
+        if (o + n > e->plan_cap) return hipErrorInvalidValue;
+        memcpy(h + o, srcv, n * 4);
+        hipError_t r = hipMemcpyAsync(dst, h + o, n * 4, hipMemcpyHostToDevice, e->st);
+        o += n; return r;
+    };
+    HIPC(e, put(e->src, hp.src.data(), M)); HIPC(e, put(e->tok_seq, hp.tok_seq.data(), M)); HIPC(e, put(e->tok_pos_pf, hp.tok_pos.data(), M));
+    HIPC(e, put(e->q_off, hp.q_off.data(), (size_t)R)); HIPC(e, put(e->q_len, hp.q_len.data(), (size_t)R)); HIPC(e, put(e->kv_len, hp.q_len.data(), (size_t)R));
+    HIPC(e, put(e->last_row, hp.last_row.data(), (size_t)R)); HIPC(e, put(e->max_new_d, hp.max_new.data(), (size_t)R));
+    HIPC(e, put(e->n_active, &R, 1));
+    HIPC(e, hipEventRecord(e->plan_ev[e->plan_idx], e->st));       // every copy out of this buffer (win_req included) is older than this event
+    e->plan_busy[e->plan_idx] = true;
+    return SONIC_OK;
+}
+// ... and the rows' state for the greedy loop that follows: counters, the int8 step's partials, the guards' history, the requests' bias tables and sampling values
+int reset_row_state(sonic_engine* e, int R, int n_tok) {
     launch_fill_i32(e->n_new, 0, 64, e->st);
     if (e->amax_att) { launch_fill_i32((int*)e->amax_att, 0, 64 * 4, e->st); launch_fill_i32((int*)e->amax_act, 0, 64 * 4, e->st); launch_fill_i32(e->big_att, 0, 64 * 4, e->st); }   // (partials nobody writes stay 0)
     launch_fill_i32(e->finished, 0, 64, e->st);
     launch_fill_i32(e->step_ctr, 0, 64, e->st);
-    if (hist_on(e)) launch_hist_prompt(e->src, e->tok_seq, e->tok_pos_pf, M, d.audio_token_id, e->hist, e->max_ctx, e->st);    // the rows' input_ids for the guards / the request bias
-    TRY(bias_upload(e, R));                                                                                                     // every request's table, or a zero count, into its row
-    TRY(samp_upload(e, R));                                                                                                     // every request's (temperature, seed), or zeros: greedy
+    if (hist_on(e)) launch_hist_prompt(e->src, e->tok_seq, e->tok_pos_pf, n_tok, e->d.audio_token_id, e->hist, e->max_ctx, e->st);    // the rows' input_ids for the guards / the request bias
+    TRY(bias_upload(e, R));                                                                                                         // every request's table, or a zero count, into its row
+    return samp_upload(e, R);                                                                                                       // every request's (temperature, seed), or zeros: greedy
+}
+
+static int run_prefill(sonic_engine* e, int R, const HostPlan& hp) {
+    const sonic_dims& d = e->d;
+    const int D = d.dec_d, M = hp.n_tok, dt = e->dt;
+    const QGroup grp{e->tok_seq, 1, R};        // one reference call = the prompt rows of one request
+    TRY(upload_plan(e, R, hp));
+    TRY(reset_row_state(e, R, M));
     launch_assemble_embeds(e->src, e->embed, e->pe, e->dx, M, D, e->st);
     e->last_ntok = M;
     if (e->taps_on) {
@@ -478,17 +529,10 @@ static int run_prefill(sonic_engine* e, int R, const HostPlan& hp) {
         };
         const bool pq1 = rmsnorm_q(e, e->dx, L.ln1, e->dhn, M, D, d.dec_rms_eps, grp);
         lin(EPI_BIAS, e->dhn, D, L.wqkv, L.wqkv_t, 0, L.qqkv, e->dqkv, e->qkvN, e->qkvN, D, nullptr, 0, pq1);
-        RopeAppendArgs ra{}; ra.dt = dt;
-        ra.qkv = e->dqkv; ra.ld = e->qkvN; ra.q_out = e->dq; ra.Kc = e->Kc + kvoff; ra.Vc = e->Vc + kvoff; ra.Vt = e->Vts; ra.vt_ld = e->max_ctx;
-        ra.tok_seq = e->tok_seq; ra.tok_pos = e->tok_pos_pf; ra.cs = e->dec_cs; ra.Hq = d.dec_heads; ra.Hkv = d.dec_kv_heads; ra.ctx_max = e->max_ctx; ra.n_tok = M;
-        if (!e->opt_no_rope_tiles) { ra.q_off = e->q_off; ra.q_len = e->q_len; ra.n_seq = R; ra.max_p = hp.max_p; }       // tiles of 16 positions per sequence (round 5)
-        launch_rope_append(ra, false, e->st);
-        FlashArgs f{}; f.dt = dt;
-        f.Q = e->dq; f.q_ld = e->QD; f.K = e->Kc + kvoff; f.k_ld = d.dec_head_dim; f.Vt = e->Vts; f.vt_ld = e->max_ctx; f.O = e->datt; f.o_ld = e->QD;
-        f.k_seq_stride = (long)d.dec_kv_heads * e->max_ctx * d.dec_head_dim; f.k_head_stride = (long)e->max_ctx * d.dec_head_dim;
-        f.vt_seq_stride = (long)d.dec_kv_heads * d.dec_head_dim * e->max_ctx; f.vt_head_stride = (long)d.dec_head_dim * e->max_ctx;
-        f.q_off = e->q_off; f.q_len = e->q_len; f.kv_len = e->q_len; f.Hq = d.dec_heads; f.Hkv = d.dec_kv_heads;
-        f.scale = 1.0f / sqrtf((float)d.dec_head_dim);
+        const bool tiles = !e->opt_no_rope_tiles;
+        launch_rope_append(rope_append_args(e->dqkv, e->dq, e->Kc + kvoff, e->Vc + kvoff, e->Vts, e->max_ctx, e->tok_seq, e->tok_pos_pf, e->dec_cs, d.dec_heads, d.dec_kv_heads,
+                                            e->max_ctx, M, dt, tiles ? e->q_off : nullptr, e->q_len, R, hp.max_p), false, e->st);
+        const FlashArgs f = prefill_flash_args(e->dq, e->Kc + kvoff, e->Vts, e->datt, e->q_off, e->q_len, e->q_len, d.dec_heads, d.dec_kv_heads, e->max_ctx, dt);
         launch_flash(f, 128, true, R, hp.max_p, e->st);
         lin(EPI_BIAS_RESID, e->datt, e->QD, L.wo, L.wo_t, 0, L.qo, e->dx, D, D, e->QD, e->dx, D, false);
         const bool pq2 = rmsnorm_q(e, e->dx, L.ln2, e->dhn, M, D, d.dec_rms_eps, grp);
@@ -539,41 +583,24 @@ int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int
     } else e->dump_steps = 0;
     e->run_logits = want_logits;
 
-    if (e->f32) {
-        (void)hipEventRecord(e->ev[0], e->st);
-        TRY(run_mel(e, e->W, true));
-        (void)hipEventRecord(e->ev[1], e->st);
-        TRY(f32_run_encoder(e, e->W, nullptr, nullptr));
-        (void)hipEventRecord(e->ev[2], e->st);
-        TRY(f32_run_prefill(e, R, hp));
-        launch_greedy(f32_greedy_args(e, R, want_logits), e->st);
-        (void)hipEventRecord(e->ev[3], e->st);
-        e->steps_run = 0; e->greedy_calls = 1; e->spliced = 0;
-        return SONIC_OK;
-    }
     (void)hipEventRecord(e->ev[0], e->st);
-    TRY(run_mel(e, e->W, false));
+    TRY(run_mel(e, e->W, e->f32));
     (void)hipEventRecord(e->ev[1], e->st);
-    {   // window -> request map (int8 mode: outlier columns are found per request)
-        std::vector<int> wr(64, 0);
+    if (e->i8) {   // window -> request map (int8 mode: outlier columns are found per request); pinned: the last 64 words of plan_h, beyond what upload_plan uses
+        int* h = e->plan_h + e->plan_cap - 64;
+        memset(h, 0, 64 * 4);
         for (int r = 0; r < R; ++r) {
             const int w0 = req_win ? req_win[r] : r, w1 = req_win ? req_win[r + 1] : r + 1;
-            for (int w = w0; w < w1 && w < 64; ++w) wr[w] = r;
+            for (int w = w0; w < w1 && w < 64; ++w) h[w] = r;
         }
-        if (e->i8) {                                           // (pinned: the last 64 words of plan_h, beyond what run_prefill uses)
-            int* h = e->plan_h + e->plan_cap - 64;
-            memcpy(h, wr.data(), 64 * 4);
-            HIPC(e, hipMemcpyAsync(e->win_req, h, 64 * 4, hipMemcpyHostToDevice, e->st));
-        }
+        HIPC(e, hipMemcpyAsync(e->win_req, h, 64 * 4, hipMemcpyHostToDevice, e->st));
     }
-    TRY(run_encoder(e, e->W, nullptr, nullptr, R));
+    TRY(e->f32 ? f32_run_encoder(e, e->W, nullptr, nullptr) : run_encoder(e, e->W, nullptr, nullptr, R));
     (void)hipEventRecord(e->ev[2], e->st);
-    TRY(run_prefill(e, R, hp));
-    launch_greedy(greedy_args(e, R, want_logits), e->st);
+    TRY(e->f32 ? f32_run_prefill(e, R, hp) : run_prefill(e, R, hp));
+    launch_greedy(e->f32 ? f32_greedy_args(e, R, want_logits) : greedy_args(e, R, want_logits), e->st);
     (void)hipEventRecord(e->ev[3], e->st);
-    e->steps_run = 0;
-    e->greedy_calls = 1;
-    e->spliced = 0;
+    e->steps_run = 0; e->greedy_calls = 1; e->spliced = 0;
     return SONIC_OK;
 }
 
