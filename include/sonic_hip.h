@@ -223,7 +223,29 @@ SONIC_API int sonic_fetch_tokens(sonic_engine* e, int32_t* out_ids, int out_ld, 
  * maximum: no second pass, the decode loops keep their hipGraph form, and a request's values are the same bits on every scheduler.
  * sonic_fetch_logprobs: the rows and counts of sonic_fetch_tokens (row r's out_len[r] values at out_lp + r * out_ld; nothing beyond them is
  * written), valid whenever that call is.  Every fetch / submit form (sonic_fetch_logprobs, sonic_fetch_rows_lp, sonic_dispatch_next_lp,
- * sonic_pipeline_submit_lp) returns SONIC_ERR_INVALID, the message naming token_logprobs, while the option is off. */
+ * sonic_pipeline_submit_lp) returns SONIC_ERR_INVALID, the message naming token_logprobs, while the option is off.
+ *
+ * The best alternatives of every step (option "top_logprobs" = K in 0 .. 8, default 0; OpenAI's top_logprobs).  sonic_set_option(e, "top_logprobs", K) on the
+ * owner before its slots are created (they copy it) and after option token_logprobs (SONIC_ERR_INVALID naming token_logprobs otherwise); refused outside
+ * 0 .. 8 and while the handle has work in hand; the log-probability buffer grows with it (counted by sonic_memory_info) - it is exchanged for a new one, so
+ * fetch a finished batch's log-probabilities BEFORE changing K: afterwards they are gone.  With s the vector of fully
+ * processed scores the log-probability sum runs over (bias, repetition penalty, bans, in that order; unperturbed and at temperature 1, also when the row
+ * samples), order the ids by s descending, then id ascending: alternative k < K is the k-th id of that order among the ids with s > -inf, with
+ * log_softmax(s)[id] formed from the same maximum and sum as the emitted token's value - an emitted token that is among the alternatives carries the same
+ * bits, and on a greedy, unforced row alternative 0 IS the emitted token.  Places beyond the finite scores hold id -1 and -inf.  Teacher forcing and
+ * sampling change the emitted token, never the alternatives.  No launch and no pass over the logits is added; tokens and their log-probabilities keep
+ * their bits.
+ * Record layout: while K > 0, EVERY log-probability array of the handle holds W = 1 + 2K floats per token instead of one:
+ *   [0]            the emitted token's log-probability (what the array held before)
+ *   [1 .. K]       the K alternatives' log-probabilities, descending
+ *   [K + 1 .. 2K]  the K alternatives' ids as fp32 values (ids stay below 2^24: exact; -1 = none)
+ * and the caller sizes its array per form:
+ *   sonic_fetch_logprobs     out_ld counts floats: row r's out_len[r] records start at out_lp + r * out_ld, so out_ld >= W * the most tokens of a row
+ *   sonic_fetch_rows_lp      out_ld counts tokens, as for out_ids: row i's records start at out_lp + i * out_ld * W (n * out_ld * W floats in all)
+ *   sonic_dispatch_next_lp   out_lp holds out_cap * W floats: token i's record at out_lp + i * W
+ *   sonic_test_greedy_lp / _guard / _bias / _sample   lp_out holds B * W floats: row b's record at lp_out + b * W
+ *   sonic_pipeline_submit_lp stays one float per token: sonic_pipeline_create refuses a handle with K > 0, the message naming top_logprobs
+ * sonic_splice_rows copies a row's first record (it comes from the prefill) and refuses handles whose K differ; sonic_dispatch_create likewise. */
 SONIC_API int sonic_fetch_logprobs(sonic_engine* e, float* out_lp, int out_ld);
 /* HF generate()'s logits processors for greedy decoding (generation/logits_process.py), applied inside the greedy kernel to the fp32 scores the argmax
  * compares, in HF's order.  input_ids = the request's prompt ids (audio placeholders included) followed by every id emitted so far, forced ids included:
@@ -507,7 +529,8 @@ SONIC_API int sonic_debug_ktrace(sonic_engine* e, int64_t* out, int64_t n);
  * "no_fused_rope" (encoder RoPE as its own pass), "no_gelu_lut" (fc1 GELU by arithmetic instead of the LDS table); the full list with what each one measured is in
  * DESIGN.md 1.  Round 6: "no_pre_norm" (<= 2 rows: standalone add + RMSNorm launches instead of the five-launch chain; same bits), "decode_gemv" / "decode_prefetch" /
  * "decode_attn_occ2" (experiments that lost: profiles/round6_*), "f32_synth_bf16" (SONIC_MODE_F32: sonic_load_synthetic writes the bf16-rounded values),
- * "inject_dev_err" (tests: sets / clears the device error word); "token_logprobs" (not an experiment: per-token log-probabilities, see sonic_fetch_logprobs) */
+ * "inject_dev_err" (tests: sets / clears the device error word); "token_logprobs" (not an experiment: per-token log-probabilities, see sonic_fetch_logprobs);
+ * "top_logprobs" (not an experiment either: the K best alternatives of every step in the same records, see sonic_fetch_logprobs) */
 SONIC_API int sonic_set_option(sonic_engine* e, const char* key, int value);
 
 /* ---- Silero VAD network (silero-vad 5.x / 6.x, 16 kHz branch; csrc/vad.hip, layer table in sonicscribe_amd/vad_net.py) ----

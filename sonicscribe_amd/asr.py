@@ -28,7 +28,7 @@ import numpy as np
 
 from . import frontend
 from .dispatch import Dispatcher
-from .engine import Engine, MODE_INT8, MODE_NATIVE, SonicError, device_count, device_info
+from .engine import Engine, MODE_INT8, MODE_NATIVE, SonicError, TokenScores, device_count, device_info
 from .spec import FULL, ModelDims
 
 
@@ -85,20 +85,42 @@ class Transcription:
     token's log-probability under the model (float32; HF compute_transition_scores(..., normalize_logits=True) of the greedy generate()) and their
     mean - the number a caller turns into the wire messages' "confidence" (connection_manager.py:159,274 can only send constants).  `temperature`: the one this
     transcript was decoded at (0: greedy); `compression_ratio`: fallback.compression_ratio of the text; `attempts`: how many decodes the fallback ladder took (1
-    without a ladder).  The log-probabilities are at temperature 1 whatever the sampling temperature (openai-whisper's convention)."""
-    __slots__ = ("text", "token_ids", "token_logprobs", "avg_logprob", "temperature", "compression_ratio", "attempts")
+    without a ladder).  The log-probabilities are at temperature 1 whatever the sampling temperature (openai-whisper's convention).
+    `top_token_ids` [n, K] int32 and `top_logprobs` [n, K] float32 (ASRModel(top_logprobs=K); [n, 0] without): at every step the K best ids by (score
+    descending, id ascending) with their log-probabilities - OpenAI's top_logprobs; places beyond the ids with a finite score hold (-1, -inf).  They are what
+    the model scored, whatever token was emitted: on a greedy request column 0 is the token itself."""
+    __slots__ = ("text", "token_ids", "token_logprobs", "avg_logprob", "temperature", "compression_ratio", "attempts", "top_token_ids", "top_logprobs")
 
     def __init__(self, text: str, token_ids, token_logprobs, temperature: float = 0.0):
         from .fallback import compression_ratio
         self.text = text
         self.temperature, self.compression_ratio, self.attempts = float(temperature), compression_ratio(text), 1
         self.token_ids = np.asarray(token_ids, np.int32)
+        top_lp = top_ids = None
+        if isinstance(token_logprobs, TokenScores):      # a top_logprobs model: the engine's unpacked wide records
+            token_logprobs, top_lp, top_ids = token_logprobs
         self.token_logprobs = np.asarray(token_logprobs, np.float32)
+        n = self.token_logprobs.shape[0] if self.token_logprobs.ndim else 0
+        self.top_logprobs = np.zeros((n, 0), np.float32) if top_lp is None else np.asarray(top_lp, np.float32)
+        self.top_token_ids = np.zeros((n, 0), np.int32) if top_ids is None else np.asarray(top_ids, np.int32)
         # over all emitted tokens, the EOS that stopped the row included; nothing emitted: nan
         self.avg_logprob = float(np.mean(self.token_logprobs, dtype=np.float64)) if self.token_logprobs.size else float("nan")
 
     def __repr__(self):
         return f"Transcription(text={self.text!r}, tokens={self.token_ids.size}, avg_logprob={self.avg_logprob:.4f})"
+
+
+def check_top_logprobs(top_logprobs, token_logprobs: bool, bulk: bool) -> int:
+    """ASRModel's top_logprobs argument -> K, or ValueError by name: outside 0 .. 8, without token_logprobs, with bulk=True (the library's own refusals,
+    made before an engine is built)"""
+    if isinstance(top_logprobs, bool) or not isinstance(top_logprobs, (int, np.integer)) or not 0 <= int(top_logprobs) <= 8:
+        raise ValueError(f"top_logprobs must be an integer in 0 .. 8 (got {top_logprobs!r})")
+    K = int(top_logprobs)
+    if K and not token_logprobs:
+        raise ValueError("top_logprobs needs token_logprobs=True: the alternatives share the log-probability kernels' sum (ASRModel(..., token_logprobs=True, top_logprobs=K))")
+    if K and bool(bulk):
+        raise ValueError("top_logprobs is not supported with bulk=True: the bulk pipeline carries one log-probability per token")
+    return K
 
 
 def _text_future(inner: "Future", decode, detailed: bool = False, temperature: float = 0.0) -> "Future[str]":
@@ -223,7 +245,7 @@ class AudioStream:
 class ASRModel:
     def __init__(self, checkpoint_dir: str, device: str = "cuda", mode: str = "native",
                  cpu_threads: Optional[int] = None, cpu_interop_threads: Optional[int] = None,
-                 *, max_batch: int = 32, max_ctx: int = 1024, slots: int = DEFAULT_SLOTS, continuous: bool = DEFAULT_CONTINUOUS, decoders: int = 1, bulk: bool = False, native_dispatch: Optional[bool] = None, token_logprobs: bool = False,
+                 *, max_batch: int = 32, max_ctx: int = 1024, slots: int = DEFAULT_SLOTS, continuous: bool = DEFAULT_CONTINUOUS, decoders: int = 1, bulk: bool = False, native_dispatch: Optional[bool] = None, token_logprobs: bool = False, top_logprobs: int = 0,
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None,
                  request_bias: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: float = 0.0,
                  sampling: bool = False, temperature=0.0, seed: int = 0, compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
@@ -233,13 +255,15 @@ class ASRModel:
         """The reference's ASRModel surface over the HIP engine.  `repetition_penalty`, `no_repeat_ngram_size`, `suppress_tokens`: None = the value of the
         checkpoint's generation_config.json, anything else overrides it (genconfig.py).  `request_bias`: requests may bring their own sequence-bias table
         (HF's sequence_bias / bad_words_ids, and `hotword_boost` > 0: the call's hotwords as entries; reqbias.py); `sequence_bias`, `bad_words_ids`,
-        `hotword_boost` here are defaults for every request and switch `request_bias` on.  `sampling` (needs token_logprobs=True): requests may be decoded at a
+        `hotword_boost` here are defaults for every request and switch `request_bias` on.  `top_logprobs` = K in 1 .. 8 (needs token_logprobs=True; not with
+        bulk=True): every `detailed=True` result also carries the K best ids of every step with their log-probabilities.  `sampling` (needs token_logprobs=True): requests may be decoded at a
         temperature with a seed, or down a fallback ladder of temperatures (fallback.py); `temperature` (a float: one attempt; a sequence: the
         ladder), `seed` and the two thresholds of the ladder here are the defaults of every call.  The arguments with a leading underscore are not part of the
         supported surface: they exist for the test-suite and the benchmark and may change without notice.  `_engine_mode` in particular (an engine.MODE_*
         value in place of the one `mode` selects) is unsupported outside the tests: MODE_F32 has no slots, so it needs slots=1, continuous=False."""
         if mode not in ["native", "int8"]:
             raise ValueError("mode must be either 'native' or 'int8'")            # asr.py:46-47
+        self.top_logprobs = check_top_logprobs(top_logprobs, token_logprobs, bulk)
         from . import fallback as fallback_, sampling as sampling_
         self.sampling = bool(sampling)
         self._default_temperature, self._default_seed = temperature, sampling_.check_seed(seed)
@@ -313,6 +337,8 @@ class ASRModel:
                 eng.set_option(k, int(v))
             if self.token_logprobs:
                 eng.set_option("token_logprobs", 1)
+            if self.top_logprobs:                    # (behind token_logprobs, before the slots exist: the library's order)
+                eng.set_option("top_logprobs", self.top_logprobs)
             if self.generation_guards.active:
                 g = self.generation_guards
                 eng.set_generation(g.repetition_penalty, g.no_repeat_ngram_size, g.suppress_tokens)
@@ -511,6 +537,8 @@ class ASRModel:
                 if det is not None:                                  # a token_logprobs model: what fills the wire messages' "confidence"
                     info.update({"token_ids": det.token_ids, "token_logprobs": det.token_logprobs, "avg_logprob": det.avg_logprob,
                                  "confidence": math.exp(det.avg_logprob)})
+                    if getattr(self, "top_logprobs", 0):             # a top_logprobs model: the K best ids of every step and their log-probabilities
+                        info.update({"top_token_ids": det.top_token_ids, "top_logprobs": det.top_logprobs})
                     if getattr(self, "sampling", False):             # a sampling model: what the transcript was decoded at, and the ladder's other measure
                         info.update({"temperature": det.temperature, "compression_ratio": det.compression_ratio})
                 return info

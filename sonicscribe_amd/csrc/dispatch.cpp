@@ -34,6 +34,7 @@
 
 #include "../../include/sonic_hip.h"
 extern "C" int engine_token_logprobs_on(sonic_engine* e);   // engine.cpp
+extern "C" int engine_top_logprobs(sonic_engine* e);        // engine.cpp: option top_logprobs of this handle (K: its log-probability records hold 1 + 2K floats)
 extern "C" int engine_request_bias_on(sonic_engine* e);     // engine.cpp: option request_bias on this handle
 extern "C" int engine_bias_validate(sonic_engine* e, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n);   // engine.cpp: one request's table against the caps and this handle's vocabulary
 extern "C" int engine_sampling_on(sonic_engine* e);         // engine.cpp: option sampling on this handle
@@ -64,6 +65,7 @@ struct sonic_dispatch {
     int n_rows = 0, pre_cap = 0;
     bool adaptive_tiles = true;
     bool lp = false;                                               // every handle has option token_logprobs on
+    int lp_w = 1;                                                  // ... and their records hold this many floats per token (1 + 2K, option top_logprobs: equal on all)
     bool bias = false;                                             // every handle has option request_bias on
     bool samp = false;                                             // every handle has option sampling on
     std::mutex mu;
@@ -265,7 +267,7 @@ void decode_thread(sonic_dispatch* d, int k) {
         std::vector<int32_t> out; std::vector<float> olp;
         if (!dr.empty()) {                                         // one call for all of them: one wait, one release launch
             out.assign((size_t)dr.size() * ld, 0);
-            if (d->lp) olp.assign((size_t)dr.size() * ld, 0.f);
+            if (d->lp) olp.assign((size_t)dr.size() * ld * d->lp_w, 0.f);
             rc = d->lp ? sonic_fetch_rows_lp(e, (int)dr.size(), dr.data(), dc.data(), out.data(), ld, olp.data())
                        : sonic_fetch_rows(e, (int)dr.size(), dr.data(), dc.data(), out.data(), ld);
             if (rc != SONIC_OK) { fail_all(rc); return; }
@@ -275,7 +277,7 @@ void decode_thread(sonic_dispatch* d, int k) {
         for (size_t j = 0; j < dr.size(); ++j) {
             ReqP r = rows[dr[j]]; rows[dr[j]].reset(); --occupied;
             r->ids.assign(out.begin() + j * ld, out.begin() + j * ld + dc[j]);
-            if (d->lp) r->lp.assign(olp.begin() + j * ld, olp.begin() + j * ld + dc[j]);
+            if (d->lp) r->lp.assign(olp.begin() + j * ld * d->lp_w, olp.begin() + (j * ld + dc[j]) * d->lp_w);
             finish(d, r, SONIC_OK, "");
         }
         if (!dr.empty()) release_rows(d, k, (int)dr.size());
@@ -304,11 +306,15 @@ SONIC_API int sonic_dispatch_create(sonic_engine* const* decoders, int n_dec, so
         }
     }
     if (rows < 1 || rows > 64 || cap < 1) return SONIC_ERR_INVALID;
+    for (int i = 1; i < n_dec + n_pre; ++i)                     // (a splice between handles of different K would be refused row by row: refuse the set)
+        if (engine_top_logprobs(i < n_dec ? decoders[i] : prefills[i - n_dec]) != engine_top_logprobs(decoders[0]))
+            return engine_thread_fail(SONIC_ERR_INVALID, "sonic_dispatch_create: the handles differ in option top_logprobs (set it on the owner before its slots are created)");
     sonic_dispatch* d = new sonic_dispatch();
     d->dec.assign(decoders, decoders + n_dec); d->pre.assign(prefills, prefills + n_pre);
     d->n_rows = rows; d->pre_cap = cap; d->adaptive_tiles = adaptive_tiles != 0;
     d->lp = true;
     for (int i = 0; i < n_dec + n_pre; ++i) d->lp = d->lp && engine_token_logprobs_on(i < n_dec ? decoders[i] : prefills[i - n_dec]);
+    d->lp_w = d->lp ? 1 + 2 * engine_top_logprobs(decoders[0]) : 1;
     d->bias = true;
     for (int i = 0; i < n_dec + n_pre; ++i) d->bias = d->bias && engine_request_bias_on(i < n_dec ? decoders[i] : prefills[i - n_dec]);
     d->samp = true;
@@ -412,7 +418,7 @@ static int dispatch_next(sonic_dispatch* d, int timeout_ms, int64_t* ticket_out,
     const int n = (int)r->ids.size();
     if (n_out) *n_out = n;
     if (out_ids) memcpy(out_ids, r->ids.data(), (size_t)(n < out_cap ? n : out_cap) * 4);
-    if (out_lp && (int)r->lp.size() == n) memcpy(out_lp, r->lp.data(), (size_t)(n < out_cap ? n : out_cap) * 4);
+    if (out_lp && (int)r->lp.size() == n * d->lp_w) memcpy(out_lp, r->lp.data(), (size_t)(n < out_cap ? n : out_cap) * d->lp_w * 4);
     if (err && err_cap > 0) { strncpy(err, r->err.c_str(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
     if (d->stop && d->outstanding == 0) d->cv_done.notify_all();
     return SONIC_OK;
@@ -423,7 +429,8 @@ SONIC_API int sonic_dispatch_next(sonic_dispatch* d, int timeout_ms, int64_t* ti
     if (!d || !ticket_out) return SONIC_ERR_INVALID;
     return dispatch_next(d, timeout_ms, ticket_out, status_out, out_ids, out_cap, n_out, err, err_cap, nullptr);
 }
-// sonic_dispatch_next plus the completed request's log-probabilities: out_lp[i] belongs to out_ids[i] (at most out_cap are copied).  Needs option
+// sonic_dispatch_next plus the completed request's log-probabilities: out_lp[i] belongs to out_ids[i] (at most out_cap are copied); with option top_logprobs = K
+// on the handles, token i's record of W = 1 + 2K floats sits at out_lp + i * W (out_lp holds out_cap * W floats).  Needs option
 // token_logprobs on every handle of the dispatcher (set on the owner before its slots were created): SONIC_ERR_INVALID otherwise, err names the option.
 SONIC_API int sonic_dispatch_next_lp(sonic_dispatch* d, int timeout_ms, int64_t* ticket_out, int32_t* status_out, int32_t* out_ids, int out_cap, int32_t* n_out,
                                      char* err, int err_cap, float* out_lp) {

@@ -350,9 +350,28 @@ static int alloc_state(sonic_engine* e) {
 int lp_alloc(sonic_engine* e) {
     if (e->out_lp) return SONIC_OK;
     HIPC(e, hipSetDevice(e->device));
-    TRY(dalloc(e, &e->out_lp, (size_t)64 * e->out_cap));
+    TRY(dalloc(e, &e->out_lp, (size_t)64 * e->out_cap * lp_width(e)));
     HIPC(e, stream_sync(e));
     return SONIC_OK;
+}
+// option top_logprobs = K: the K best alternatives of every step ride in the token's log-probability record, which grows to 1 + 2K floats.  The
+// buffer is exchanged for one of the new width (sonic_memory_info follows), so the records of a finished batch that has not been fetched yet are gone with the
+// old one: fetch first (include/sonic_hip.h says so).  The caller holds the lock and has asked gen_busy.
+int top_enable(sonic_engine* e, int K) {
+    if (K < 0 || K > 8) return fail(e, SONIC_ERR_INVALID, "top_logprobs: %d is outside 0 .. 8", K);
+    if (K > 0 && !(e->opt_token_logprobs && e->out_lp)) return fail(e, SONIC_ERR_INVALID, "top_logprobs: option token_logprobs must be on first (the alternatives share the log-probability kernels' sum; sonic_set_option(e, \"token_logprobs\", 1))");
+    if (K == e->opt_top_logprobs) return SONIC_OK;
+    HIPC(e, hipSetDevice(e->device));
+    HIPC(e, stream_sync(e));
+    const bool had = e->out_lp != nullptr;
+    if (had) {
+        e->allocs.erase(std::find(e->allocs.begin(), e->allocs.end(), (void*)e->out_lp));
+        HIPC(e, hipFree(e->out_lp));
+        e->alloc_bytes -= (int64_t)64 * e->out_cap * lp_width(e) * 4; e->out_lp = nullptr;
+    }
+    e->opt_top_logprobs = K;
+    drop_graphs(e);                                      // the greedy kernel and its arguments are part of every captured chunk
+    return had ? lp_alloc(e) : SONIC_OK;
 }
 int lp_check(sonic_engine* e, const char* who) {
     if (e->opt_token_logprobs && e->out_lp) return SONIC_OK;
@@ -360,6 +379,9 @@ int lp_check(sonic_engine* e, const char* who) {
 }
 // dispatch.cpp / pipeline.cpp (same library, not exported): does this handle produce log-probabilities
 extern "C" int engine_token_logprobs_on(sonic_engine* e) { return e && e->opt_token_logprobs && e->out_lp ? 1 : 0; }
+// ... and how many alternatives ride along (option top_logprobs: its log-probability records hold 1 + 2K floats per token)
+extern "C" int engine_top_logprobs(sonic_engine* e) { return e && e->opt_token_logprobs && e->out_lp ? e->opt_top_logprobs : 0; }
+extern "C" int engine_fail(sonic_engine* e, int code, const char* msg) { std::lock_guard<std::mutex> lk(e->mu); return fail(e, code, "%s", msg); }   // a message on a handle, from outside its calls
 
 // ---- generation guards: validation, the history / suppress buffers on first use, the upload.  The caller holds the lock and has made sure nothing is in flight.
 #define GEN_MAX_SUPPRESS 256
@@ -645,7 +667,7 @@ extern "C" int sonic_slot_create(sonic_engine* parent, sonic_engine** out) {
     e->opts = root->opts; e->opt_no_graph = root->opt_no_graph; e->opt_no_fused_rope = root->opt_no_fused_rope; e->opt_no_gelu_lut = root->opt_no_gelu_lut;
     e->opt_i8_defer_thr = root->opt_i8_defer_thr; e->opt_i8_no_xq = root->opt_i8_no_xq; e->opt_i8_no_lnq = root->opt_i8_no_lnq; e->opt_i8_no_qkv_fuse = root->opt_i8_no_qkv_fuse;
     e->opt_decode_chunk = root->opt_decode_chunk; e->opt_no_pre_norm = root->opt_no_pre_norm; e->opt_decode_gemv = root->opt_decode_gemv;
-    e->opt_token_logprobs = root->opt_token_logprobs;
+    e->opt_token_logprobs = root->opt_token_logprobs; e->opt_top_logprobs = root->opt_token_logprobs ? root->opt_top_logprobs : 0;      // (before lp_alloc: the buffer comes at its width)
     if (e->opt_token_logprobs && (s = lp_alloc(e)) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }
     if (root->gen_on && (s = gen_apply(e, root->gen_penalty, root->gen_ngram, root->gen_suppress.data(), (int)root->gen_suppress.size())) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }
     if (root->opt_request_bias && (s = bias_enable(e, 1)) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }

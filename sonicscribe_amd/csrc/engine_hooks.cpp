@@ -346,6 +346,8 @@ extern "C" int sonic_test_linear_int8(sonic_engine* e, const float* X, const flo
 // instead of its argmax); lp_out[B] = the emitted token's log-probability.
 // sonic_test_greedy_guard: the launch through greedy_kernel<T, LP, true> (LP when lp_out is given): row b's history is hist[b * hist_ld .. + hist_len[b]), the three
 // parameters are sonic_set_generation's; logits_out stays the raw logits.
+// With option top_logprobs = K on the handle the four hooks that take lp_out launch the TOPK kernel of their family and return row b's whole record at
+// lp_out[b * (1 + 2K)]: the emitted token's log-probability, the K alternatives', their ids as fp32.
 // sonic_test_greedy_bias: the launch through greedy_kernel<T, LP, true, true>: the guard test plus row b's table (sonic_set_request_bias's packed form, B requests).
 struct GuardTest { const int32_t* hist; int hist_ld; const int32_t* hist_len; float penalty; int ngram; const int32_t* suppress; int n_suppress;
                    bool bias = false; const int32_t* seq_ids = nullptr; const int32_t* seq_off = nullptr; const float* seq_bias = nullptr; const int32_t* req_off = nullptr; };
@@ -356,6 +358,7 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
                        const GuardTest* gt = nullptr, const SampTest* sp = nullptr) {
     if (ksplit < 1 || ksplit > 8 || B < 1 || B > 64 || mpad < B || V < 4 || V % 4) return fail(e, SONIC_ERR_INVALID, "bad greedy test shape");
     if (force_ids) for (int b = 0; b < B; ++b) if (force_ids[b] < 0 || force_ids[b] >= V) return fail(e, SONIC_ERR_INVALID, "forced id %d out of vocabulary", force_ids[b]);
+    const int lw_ = lp_out ? lp_width(e) : 1;                                     // floats of a token's log-probability record (option top_logprobs)
     int old = 1;                                                                  // columns of ids / lp / forced ids: one, or up to the largest step of a sampling test
     if (sp) {
         if (!sp->temperature || !sp->seed || !sp->step || !lp_out) return fail(e, SONIC_ERR_INVALID, "bad greedy sample test arguments");
@@ -368,7 +371,7 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
     bf16_t* table = tb.get<bf16_t>((size_t)V * 8 * (sp ? 2 : 1)); bf16_t* x = tb.get<bf16_t>((size_t)64 * 8 * (sp ? 2 : 1));      // (sp: rows of 8 floats in the fp32 kind)
     int* st = tb.get<int>(64 * 8 + 4); int* ids = tb.get<int>((size_t)64 * old);
     float* dump = logits_out ? tb.get<float>((size_t)B * V) : nullptr;
-    float* lp = lp_out ? tb.get<float>((size_t)64 * old) : nullptr;
+    float* lp = lp_out ? tb.get<float>((size_t)64 * old * lw_) : nullptr;
     int* fd = force_ids ? tb.get<int>((size_t)64 * old) : nullptr;
     if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     std::vector<int> h(64 * 8 + 4, 0);
@@ -433,7 +436,7 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
     g.logits = dl; g.ksplit = ksplit; g.mpad = mpad; g.V = V; g.B = B; g.table = table; g.x = x; g.d = 8;
     g.out_ids = ids; g.out_ld = old; g.n_new = st; g.finished = st + 64; g.kv_len = st + 128; g.tok_pos = st + 192; g.max_new = st + 256;
     g.n_active = st + 512; g.n_eos = 0; g.pad_id = 0; g.logits_dump = dump; g.dump_stride_step = (long)B * V; g.step_counter = dump ? st + 320 : nullptr;
-    g.out_lp = lp; g.force_ids = fd; g.force_ld = old;
+    g.out_lp = lp; g.force_ids = fd; g.force_ld = old; g.topk = lp ? e->opt_top_logprobs : 0;
     if (sp) { g.samp = gsamp; g.noise_out = gnoise; g.dt = e->f32 ? DT_F32 : e->dt; }
     if (gt) { g.hist = ghist; g.hist_ld = gld; g.rep_penalty = gt->penalty; g.ngram = gt->ngram; g.suppress = gsup; g.n_suppress = gt->n_suppress; g.bias_tab = gbias; }
     launch_greedy(g, e->st);
@@ -443,11 +446,11 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
     HIPC(e, d2h(e, out.data(), ids, out.size() * 4));
     for (int b = 0; b < B; ++b) tok_out[b] = out[(size_t)b * old + (sp ? sp->step[b] : 0)];
     if (logits_out) HIPC(e, d2h(e, logits_out, dump, (size_t)B * V * 4));
-    if (lp_out && !sp) HIPC(e, d2h(e, lp_out, lp, (size_t)B * 4));
+    if (lp_out && !sp) HIPC(e, d2h(e, lp_out, lp, (size_t)B * lw_ * 4));
     if (sp) {
-        std::vector<float> lw((size_t)64 * old);
+        std::vector<float> lw((size_t)64 * old * lw_);
         HIPC(e, d2h(e, lw.data(), lp, lw.size() * 4));
-        for (int b = 0; b < B; ++b) lp_out[b] = lw[(size_t)b * old + sp->step[b]];
+        for (int b = 0; b < B; ++b) memcpy(lp_out + (size_t)b * lw_, &lw[((size_t)b * old + sp->step[b]) * lw_], (size_t)lw_ * 4);
         if (sp->noise_out) HIPC(e, d2h(e, sp->noise_out, gnoise, (size_t)B * V * 4));
     }
     return SONIC_OK;

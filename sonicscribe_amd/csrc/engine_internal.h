@@ -128,7 +128,8 @@ struct sonic_engine {
     bf16_t* sx2 = nullptr;                                          // ... and the second residual buffer of that form (the stream ping-pongs layer by layer)
     int *kv_len = nullptr, *tok_pos = nullptr, *n_new = nullptr, *finished = nullptr, *max_new_d = nullptr, *n_active = nullptr;
     int *out_ids = nullptr, *step_ctr = nullptr, *seq_iota = nullptr;
-    float* out_lp = nullptr;                                        // [64][out_cap] log-probability of every emitted token, beside out_ids (option token_logprobs; lp_alloc)
+    float* out_lp = nullptr;                                        // [64][out_cap][lp_width] log-probability of every emitted token, beside out_ids (option token_logprobs; lp_alloc);
+                                                                    // with option top_logprobs = K the token's record is 1 + 2K floats (lp_width)
     int *src = nullptr, *tok_seq = nullptr, *tok_pos_pf = nullptr, *q_off = nullptr, *q_len = nullptr, *last_row = nullptr;
     float* dump = nullptr; size_t dump_cap = 0; int dump_steps = 0;
     bf16_t* taps = nullptr; int taps_on = 0; int last_ntok = 0;   // debug: prefill hidden states after embedding + each layer
@@ -182,6 +183,8 @@ struct sonic_engine {
     int opt_decode_chunk = 2;      // token steps per captured graph = granularity of the early-stop check (sonic_set_option "decode_chunk")
     int opt_token_logprobs = 0;    // 1: every greedy launch also writes log_softmax(logits)[token] to out_lp (greedy_kernel<T, true>); set on the owner before
                                    // its slots exist (they copy it).  The decode loops keep their hipGraph form; graphs are cached per value
+    int opt_top_logprobs = 0;      // K in 0 .. 8: every greedy launch also writes the step's K best ids and their log-probabilities (greedy_kernel<T, true, ., ., ., true>);
+                                   // set on the owner, after token_logprobs, before its slots exist (they copy it); out_lp then holds 1 + 2K floats per token (top_enable)
     // generation guards (sonic_set_generation; greedy_kernel<T, LP, true>): HF's repetition_penalty / no_repeat_ngram_size / suppress_tokens inside the greedy
     // kernel.  gen_on: any of them is set; set on the owner before its slots exist (they copy it).  hist[64][max_ctx]: every row's input_ids (prompt, then the emitted ids),
     // written by the prefill and the greedy kernel, copied by the splice; allocated with gen_suppress_d[256] by the first gen_apply that switches a guard on
@@ -320,6 +323,8 @@ int samp_check(sonic_engine* e, const char* who, const float* temperature, int n
 int samp_upload(sonic_engine* e, int R);            // the prefill's part: the pending values (or zeros: greedy) into samp.dev, on the stream (engine.cpp)
 void samp_pack(unsigned* w, float t, uint64_t seed);   // one row's three words as the kernel reads them: the temperature's bits, the seed's low and high word (engine.cpp)
 static inline bool hist_on(const sonic_engine* e) { return e->gen_on || e->opt_request_bias; }   // the rows' input_ids are kept: a guard or the request bias reads them
+static inline int lp_width(const sonic_engine* e) { return 1 + 2 * e->opt_top_logprobs; }   // floats per token in every log-probability array of this handle
+int top_enable(sonic_engine* e, int K);             // option top_logprobs behind the lock and the busy check: out_lp at its new width (engine.cpp)
 int lp_check(sonic_engine* e, const char* who);     // SONIC_ERR_INVALID naming the option when token_logprobs is off on this handle
 int read_back_16(sonic_engine* e, const bf16_t* d, float* h, size_t n);   // n elements of a 16-bit device buffer -> fp32 on the host, through a temporary (engine_hooks.cpp; sonic_debug_read)
 

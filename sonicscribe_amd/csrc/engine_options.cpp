@@ -6,9 +6,13 @@ void drop_graphs(sonic_engine* e) { for (auto& g : e->graphs) (void)hipGraphExec
 static int opt_token_logprobs(sonic_engine* e, const char*, int value) {      // per-token log-probabilities beside the ids (greedy_kernel<T, true>)
     const int v = value ? 1 : 0;
     if (!v && e->opt_sampling) return fail(e, SONIC_ERR_INVALID, "token_logprobs cannot be switched off while option sampling is on (its kernels are log-probability kernels)");
+    if (!v && e->opt_top_logprobs) return fail(e, SONIC_ERR_INVALID, "token_logprobs cannot be switched off while option top_logprobs is on (its kernels are log-probability kernels)");
     e->opt_token_logprobs = v; drop_graphs(e);
     return v ? lp_alloc(e) : SONIC_OK;      // first use: 64 x out_cap fp32
 }
+// the K best alternatives of every step beside the token's log-probability (greedy_kernel<T, true, ., ., ., true>): K in 0 .. 8, on the owner before its
+// slots are created (they copy it), after token_logprobs (refused by name otherwise).  Refused while the handle has work in hand, by sonic_set_generation's rule
+static int opt_top_logprobs(sonic_engine* e, const char* key, int value) { TRY(gen_busy(e, key)); return top_enable(e, value); }
 // the generation guards one integer at a time, for drivers that only speak key = value (bench.py --opt; tools/ab_generation_guards.sh): the penalty in
 // thousandths, the n-gram size, ONE suppressed id (-1: none).  Same rules and refusals as sonic_set_generation; the other two values stay as they are
 static int opt_gen(sonic_engine* e, const char* key, int value) {
@@ -97,6 +101,7 @@ static const OptRow OPTIONS[] = {
     {"no_fused_rope", ENG(opt_no_fused_rope), false, nullptr},      // encoder RoPE as its own pass (A/B against the fused epilogue)
     {"no_gelu_lut", ENG(opt_no_gelu_lut), false, nullptr},          // GELU by arithmetic instead of the LDS table (A/B)
     {"token_logprobs", APPLY(opt_token_logprobs)},
+    {"top_logprobs", APPLY(opt_top_logprobs)},
     {"gen_repetition_penalty_milli", APPLY(opt_gen)},
     {"gen_no_repeat_ngram_size", APPLY(opt_gen)},
     {"gen_suppress_token", APPLY(opt_gen)},

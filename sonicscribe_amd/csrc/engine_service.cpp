@@ -16,7 +16,8 @@ struct SpliceArgs {
     const int* hist_s; int* hist_d;                      // generation guards on the destination: the row's history (prompt + first token) travels with it, [.][ctx]
     const int* bias_s; int* bias_d;                      // option request_bias on both: the row's table travels with it (count first, then only the used entries)
     const unsigned* samp_s; unsigned* samp_d;            // option sampling on both: the row's temperature and seed travel with it (its step index is n_new)
-    const float* lp_s; float* lp_d;                      // option token_logprobs on the destination: the first token's log-probability travels with its id
+    const float* lp_s; float* lp_d; int lp_w;            // option token_logprobs on the destination: the first token's log-probability record (lp_w floats: 1, or 1 + 2K with
+                                                         // option top_logprobs) travels with its id
     int *kv_len_d, *tok_pos_d, *n_new_d, *fin_d, *max_new_d, *out_d, *n_active_d;
     const bf16_t *sx_s, *shn_s; bf16_t *sx_d, *shn_d; int D;
     const int8_t* hq_s; int8_t* hq_d; const float *sca_s, *ov_s; float *sca_d, *ov_d; const int *oc_s, *ol_s; int *oc_d, *ol_d;   // int8 mode: layer 0's quantised input row
@@ -53,10 +54,10 @@ __global__ __launch_bounds__(256) void splice_state_kernel(SpliceArgs a) {
         for (int j = t; j < cnt * BIAS_ENTRY_WORDS; j += 256) a.bias_d[64 + (long)d * BIAS_ROW_WORDS + j] = a.bias_s[64 + (long)s * BIAS_ROW_WORDS + j];
     }
     if (a.samp_d && t < 3) a.samp_d[3 * d + t] = a.samp_s[3 * s + t];
+    if (a.lp_d && t < a.lp_w) a.lp_d[(long)d * a.out_ld * a.lp_w + t] = a.lp_s[(long)s * a.out_ld * a.lp_w + t];
     if (t == 0) {
         const int fin = a.fin_s[s];
         a.out_d[(long)d * a.out_ld] = a.out_s[(long)s * a.out_ld];            // the first token came out of the prefill
-        if (a.lp_d) a.lp_d[(long)d * a.out_ld] = a.lp_s[(long)s * a.out_ld];
         a.kv_len_d[d] = a.kv_len_s[s]; a.tok_pos_d[d] = a.tok_pos_s[s]; a.n_new_d[d] = a.n_new_s[s]; a.max_new_d[d] = a.max_new_s[s];
         a.fin_d[d] = fin;
         if (!fin) atomicAdd(a.n_active_d, 1);
@@ -126,6 +127,8 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
     if (d->Bm != p->Bm || d->max_ctx != p->max_ctx) return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: the handles differ in max_batch / max_ctx");
     if (d->opt_token_logprobs && !(p->opt_token_logprobs && p->out_lp))
         return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: the destination has option token_logprobs on, the source prefilled without it");
+    if (d->opt_token_logprobs && d->opt_top_logprobs != p->opt_top_logprobs)
+        return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in option top_logprobs (%d and %d): set it on the owner before its slots are created", p->opt_top_logprobs, d->opt_top_logprobs);
     // (either way round: a row whose first token was chosen with guards must not go on without them, nor the reverse)
     if (d->gen_on != p->gen_on || (d->gen_on && !(p->hist && d->hist && p->gen_penalty == d->gen_penalty && p->gen_ngram == d->gen_ngram && p->gen_suppress == d->gen_suppress)))
         return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in their generation guards (sonic_set_generation): set them on the owner before its slots are created");
@@ -145,7 +148,7 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
     a.kv_len_s = p->kv_len; a.tok_pos_s = p->tok_pos; a.n_new_s = p->n_new; a.fin_s = p->finished; a.max_new_s = p->max_new_d; a.out_s = p->out_ids; a.out_ld = d->out_cap;
     a.kv_len_d = d->kv_len; a.tok_pos_d = d->tok_pos; a.n_new_d = d->n_new; a.fin_d = d->finished; a.max_new_d = d->max_new_d; a.out_d = d->out_ids; a.n_active_d = d->n_active;
     a.sx_s = p->sx; a.shn_s = p->shn; a.sx_d = d->sx; a.shn_d = d->shn; a.D = dm.dec_d;
-    if (d->opt_token_logprobs && d->out_lp) { a.lp_s = p->out_lp; a.lp_d = d->out_lp; }
+    if (d->opt_token_logprobs && d->out_lp) { a.lp_s = p->out_lp; a.lp_d = d->out_lp; a.lp_w = lp_width(d); }
     if (hist_on(d)) { a.hist_s = p->hist; a.hist_d = d->hist; }
     if (d->opt_request_bias) { a.bias_s = p->bias.dev; a.bias_d = d->bias.dev; }
     if (d->opt_sampling) { a.samp_s = p->samp.dev; a.samp_d = d->samp.dev; }
@@ -243,6 +246,7 @@ __global__ void release_rows_kernel(int* kv_len, int* tok_pos, int* finished, Sp
     if (i < n) { const int row = a.dst[i]; kv_len[row] = 1; tok_pos[row] = 0; finished[row] = 1; }
 }
 static int fetch_rows_locked(sonic_engine* e, int n, const int32_t* rows, const int32_t* counts, int32_t* out_ids, int out_ld, float* out_lp) {
+    const size_t w = (size_t)lp_width(e);
     if (!e->svc_on) return fail(e, SONIC_ERR_INVALID, "sonic_fetch_rows needs sonic_service_begin");
     if (n < 1 || n > 64) return fail(e, SONIC_ERR_INVALID, "sonic_fetch_rows: %d rows", n);
     SpliceArgs a{};
@@ -256,7 +260,7 @@ static int fetch_rows_locked(sonic_engine* e, int n, const int32_t* rows, const 
     for (int i = 0; i < n; ++i)
         if (counts[i] > 0) {
             HIPC(e, hipMemcpyAsync(out_ids + (size_t)i * out_ld, e->out_ids + (size_t)rows[i] * e->out_cap, (size_t)counts[i] * 4, hipMemcpyDeviceToHost, e->st_io));
-            if (out_lp) HIPC(e, hipMemcpyAsync(out_lp + (size_t)i * out_ld, e->out_lp + (size_t)rows[i] * e->out_cap, (size_t)counts[i] * 4, hipMemcpyDeviceToHost, e->st_io));
+            if (out_lp) HIPC(e, hipMemcpyAsync(out_lp + (size_t)i * out_ld * w, e->out_lp + (size_t)rows[i] * e->out_cap * w, (size_t)counts[i] * w * 4, hipMemcpyDeviceToHost, e->st_io));
         }
     HIPC(e, hipStreamSynchronize(e->st_io));
     hipLaunchKernelGGL(release_rows_kernel, dim3(1), dim3(64), 0, e->st, e->kv_len, e->tok_pos, e->finished, a, n);
@@ -268,7 +272,8 @@ extern "C" int sonic_fetch_rows(sonic_engine* e, int n, const int32_t* rows, con
     ENTER(e);
     return fetch_rows_locked(e, n, rows, counts, out_ids, out_ld, nullptr);
 }
-// sonic_fetch_rows with the rows' log-probabilities in the same call (the fetch releases the rows): row i's at out_lp + i * out_ld, as its ids
+// sonic_fetch_rows with the rows' log-probabilities in the same call (the fetch releases the rows): row i's at out_lp + i * out_ld, as its ids; with option
+// top_logprobs = K its records of W = 1 + 2K floats at out_lp + i * out_ld * W
 extern "C" int sonic_fetch_rows_lp(sonic_engine* e, int n, const int32_t* rows, const int32_t* counts, int32_t* out_ids, int out_ld, float* out_lp) {
     if (!e || !rows || !counts || !out_ids || !out_lp) return SONIC_ERR_INVALID;
     ENTER(e);
@@ -479,8 +484,9 @@ int fetch_locked(sonic_engine* e, int32_t* out_ids, int out_ld, int32_t* out_len
             HIPC(e, d2h_async(e, out_ids + (size_t)r * out_ld, e->out_ids + (size_t)r * e->out_cap, (size_t)nn[r] * 4));
         }
         if (out_lp) {
-            if (nn[r] > out_ld) return fail(e, SONIC_ERR_INVALID, "out_ld too small");
-            HIPC(e, d2h_async(e, out_lp + (size_t)r * out_ld, e->out_lp + (size_t)r * e->out_cap, (size_t)nn[r] * 4));
+            const size_t w = (size_t)lp_width(e);            // out_ld counts floats: a token's record holds w of them (option top_logprobs)
+            if ((size_t)nn[r] * w > (size_t)out_ld) return fail(e, SONIC_ERR_INVALID, "out_ld too small");
+            HIPC(e, d2h_async(e, out_lp + (size_t)r * out_ld, e->out_lp + (size_t)r * e->out_cap * w, (size_t)nn[r] * w * 4));
         }
     }
     if (step_logits) {
@@ -498,7 +504,7 @@ extern "C" int sonic_fetch_tokens(sonic_engine* e, int32_t* out_ids, int out_ld,
 }
 
 // the log-probabilities of the tokens sonic_fetch_tokens returns (same rows, same counts: row r's n_new[r] values at out_lp + r * out_ld; entries
-// beyond are not written); valid whenever that call is
+// beyond are not written); valid whenever that call is.  With option top_logprobs = K: n_new[r] records of 1 + 2K floats, out_ld counting floats
 extern "C" int sonic_fetch_logprobs(sonic_engine* e, float* out_lp, int out_ld) {
     if (!e || !out_lp) return SONIC_ERR_INVALID;
     ENTER(e);

@@ -250,6 +250,7 @@ GreedyArgs greedy_args(sonic_engine* e, int R, bool dump) {
     // (request bias without guards: the guard values are the neutral ones - r * 1.0 and __fdiv_rn(r, 1.0) are exact, n = 0, no suppress list)
     if (hist_on(e)) { g.hist = e->hist; g.hist_ld = e->max_ctx; g.rep_penalty = e->gen_penalty; g.ngram = e->gen_ngram; g.suppress = e->gen_suppress_d; g.n_suppress = (int)e->gen_suppress.size(); }
     if (e->opt_request_bias) g.bias_tab = e->bias.dev;
+    if (g.out_lp) g.topk = e->opt_top_logprobs;                  // (likewise)
     if (e->opt_sampling && g.out_lp) g.samp = e->samp.dev;      // (the option is refused without token_logprobs, and token_logprobs cannot leave while it is on)
     if (e->i8) g.qo = QuantOut{e->hn_q, d.dec_d, e->sca_hn, e->oc_hn, e->ol_hn, d.dec_d, e->ov_hn};     // layer 0's q/k/v input, quantised
     return g;
@@ -609,7 +610,7 @@ int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int
 // svc: the chunk belongs to a continuous decode loop (sonic_service_*), i.e. it runs beside a prefill slot and other loops by design - decode_step then
 // picks the forms that cost the fewest CU-microseconds rather than the shortest chain (gu64_split_norm).  Same bits either way; cached separately.
 int chunk_graph(sonic_engine* e, int R, int n, hipGraphExec_t* out, bool svc) {
-    const std::pair<int, int> key{R + (svc ? 4096 : 0) + (e->opt_token_logprobs ? 8192 : 0) + (e->gen_on ? 16384 : 0) + (e->opt_request_bias ? 32768 : 0) + (e->opt_sampling ? 65536 : 0), n};   // (the LP / GUARD / BIAS / SAMPLE greedy kernel and its pointers are part of the capture)
+    const std::pair<int, int> key{R + (svc ? 4096 : 0) + (e->opt_token_logprobs ? 8192 : 0) + (e->gen_on ? 16384 : 0) + (e->opt_request_bias ? 32768 : 0) + (e->opt_sampling ? 65536 : 0) + e->opt_top_logprobs * 131072, n};   // (the LP / GUARD / BIAS / SAMPLE / TOPK greedy kernel and its pointers are part of the capture)
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) { *out = it->second; return SONIC_OK; }
     hipGraph_t g = nullptr; hipGraphExec_t gx = nullptr;

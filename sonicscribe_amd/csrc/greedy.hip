@@ -1,6 +1,7 @@
 // The greedy controller: fused argmax over the lm_head's partial slabs + HF's greedy loop bookkeeping + the next step's embedding row and
-// first RMSNorm, one block per row.  One kernel body, templated on the activation dtype T and four flags - LP (per-token log-probabilities), GUARD (HF's logits
-// processors), BIAS (per-request sequence bias), SAMPLE (temperature sampling) - in the nine combinations launch_greedy's table lists; and the prefill's kernel
+// first RMSNorm, one block per row.  One kernel body, templated on the activation dtype T and five flags - LP (per-token log-probabilities), GUARD (HF's logits
+// processors), BIAS (per-request sequence bias), SAMPLE (temperature sampling), TOPK (the best alternatives of every step) - in the fifteen combinations
+// launch_greedy's table lists; and the prefill's kernel
 // that writes a request's prompt ids into its history row for GUARD / BIAS.  Shares quant_emit_row (int8_util.h) with the decode-step consumers of elementwise.hip.
 #include "common.h"
 #include "kernels.h"
@@ -35,6 +36,40 @@
 // log_softmax(s)[tok] at temperature 1 - openai-whisper's convention, the one its fallback thresholds are calibrated on; the emitted token's s is recomputed
 // from the slabs as the forced id's is.  Teacher forcing wins over sampling; step_logits stay raw.  The two logs are logf - v_log_f32 (1 ulp) times ln 2 in extended precision, a relative error
 // of at most 1.5 * 2^-23 each: |g - exact| <= (1 + 16.64) * 1.5 * 2^-23 < 3.2e-6.
+// TOPK (option top_logprobs = K, 1 .. 8; LP only): beside out_lp the block returns the K best ids of the step, ordered by (s descending, id
+// ascending) over the ids with s > -inf, s the fully processed, unperturbed score the LP sum runs over, each with (float)(((double)s_k - (double)M) - log((double)lp_sum))
+// - M and lp_sum the very values out_lp is formed from, so an emitted token that is among them carries out_lp's bits.  Every thread keeps the 8 best (value, id)
+// pairs it has visited, sorted, in registers: a score is compared with the list's last value, and only a larger one is inserted (a thread visits its ids in
+// ascending order, so among equal values the earlier id stays in front).  The lists are merged by K rounds of "butterfly argmax of the lanes' heads, the winner
+// pops": per wave, then - the waves' lists in LDS, one per lane - by wave 1, while thread 0 of wave 0 does the step's bookkeeping.  The order is total (ids are
+// unique), so the result does not depend on how the reduction is arranged.  Lanes 0 .. K - 1 of wave 1 write the record [lp | K alternative lps | K ids as fp32]
+// at out_lp[(b * out_ld + n) * (1 + 2K)]; places beyond the finite scores hold (-inf, -1).  Forcing and sampling change the emitted token, never the
+// alternatives; a finished row writes nothing.  TOPK = false is the kernel as it was: everything that belongs to the lists sits behind `if constexpr (TOPK)`.
+#define TK_NONE 0x7fffffff
+__device__ __forceinline__ void tk_insert(float (&tv)[8], int (&ti)[8], float r, int id) {      // the caller has seen r > tv[7]
+    tv[7] = r; ti[7] = id;
+#pragma unroll
+    for (int k = 7; k > 0; --k)
+        if (tv[k] > tv[k - 1]) { const float fv = tv[k]; tv[k] = tv[k - 1]; tv[k - 1] = fv; const int fi = ti[k]; ti[k] = ti[k - 1]; ti[k - 1] = fi; }      // strict: equal values keep their order
+}
+// K rounds over the 64 lanes' sorted lists: lane r leaves with the r-th best pair of all of them (lanes >= K, and places without a finite score: (-inf, TK_NONE))
+__device__ __forceinline__ void tk_merge(float (&tv)[8], int (&ti)[8], int K, int lane, float& mv, int& mi) {
+    mv = -INFINITY; mi = TK_NONE;
+    for (int r = 0; r < K; ++r) {
+        float wv = tv[0]; int wi = ti[0];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ov = __shfl_xor(wv, o, 64); const int oi = __shfl_xor(wi, o, 64);
+            if (ov > wv || (ov == wv && oi < wi)) { wv = ov; wi = oi; }
+        }
+        if (lane == r) { mv = wv; mi = wi; }
+        if (wi != TK_NONE && ti[0] == wi) {          // the winner's lane pops its head
+#pragma unroll
+            for (int k = 0; k < 7; ++k) { tv[k] = tv[k + 1]; ti[k] = ti[k + 1]; }
+            tv[7] = -INFINITY; ti[7] = TK_NONE;
+        }
+    }
+}
 extern __shared__ unsigned g_bits[];
 __device__ __forceinline__ float guard_score(float r, unsigned seen, unsigned banned, float p) {
     if (seen & 1u) r = r < 0.f ? r * p : __fdiv_rn(r, p);
@@ -66,8 +101,9 @@ __device__ __forceinline__ float gumbel_of(unsigned word) {
     return -logf(-logf(u));
 }
 #define LPB (SAMPLE ? rmax : best)      // what the LP sum is taken against: the running maximum of s
-template <typename T, bool LP, bool GUARD = false, bool BIAS = false, bool SAMPLE = false>
+template <typename T, bool LP, bool GUARD = false, bool BIAS = false, bool SAMPLE = false, bool TOPK = false>
 __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
+    static_assert(LP || !TOPK, "the alternatives live in the log-probability instantiations (they share their sum)");
     static_assert(GUARD || !BIAS, "the request bias lives in the guard instantiations (it needs their history)");
     static_assert(LP || !SAMPLE, "sampling lives in the log-probability instantiations (the fallback ladder reads them)");
     typedef typename ET<T>::v8 V8;
@@ -76,6 +112,15 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
     __shared__ int s_tok;
     __shared__ float ss_lp[LP ? (SAMPLE ? 32 : 16) : 1];
     [[maybe_unused]] float* const ss_m = ss_lp + (SAMPLE ? 16 : 0);      // SAMPLE: the waves' maxima of the unperturbed scores (sv holds those of y)
+    __shared__ float s_tkv[TOPK ? 128 : 1];      // TOPK: the waves' lists, [place][wave] (lane w of wave 1 reads wave w's: consecutive words) ...
+    __shared__ int s_tki[TOPK ? 128 : 1];        // ... and their ids
+    __shared__ float s_tk_hand[TOPK ? 2 : 1];    // thread 0 -> wave 1: the block's maximum M and lp_sum, the values out_lp was formed from ...
+    __shared__ int s_tk_col[1];                  // ... and the record's column n_new (-1: a finished row)
+    [[maybe_unused]] float tv[8]; [[maybe_unused]] int ti[8]; [[maybe_unused]] float mv = -INFINITY; [[maybe_unused]] int mi = TK_NONE;
+    if constexpr (TOPK) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { tv[k] = -INFINITY; ti[k] = TK_NONE; }
+    }
     float lp_m = -INFINITY, lp_s = 0.f;      // LP: the thread's sum is lp_s * exp(lp_m); a thread that saw nothing holds (-inf, 0)
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const float* lg = a.logits + (long)b * a.V;
@@ -180,6 +225,7 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
                 } else {
                     if (r > best) { best = r; bi = i + j; }   // strict > keeps the first maximum within a thread
                 }
+                if constexpr (TOPK) if (r > tv[7]) tk_insert(tv, ti, r, i + j);
                 if constexpr (LP) v[u][j] = r;
             }
         }
@@ -214,8 +260,18 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
         for (int o = 32; o > 0; o >>= 1) lp_s += __shfl_xor(lp_s, o, 64);
         if (lane == 0) ss_lp[wid] = lp_s;
     }
+    if constexpr (TOPK) {
+        tk_merge(tv, ti, a.topk, lane, mv, mi);
+        if (lane < 8) { s_tkv[lane * 16 + wid] = mv; s_tki[lane * 16 + wid] = mi; }
+    }
     if (lane == 0) { sv[wid] = best; si[wid] = bi; }
     __syncthreads();
+    if constexpr (TOPK) if (wid == 1) {              // lane w < 16 takes wave w's list; the merge runs beside thread 0's bookkeeping
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { tv[k] = lane < 16 ? s_tkv[k * 16 + lane] : -INFINITY; ti[k] = lane < 16 ? s_tki[k * 16 + lane] : TK_NONE; }
+        tk_merge(tv, ti, a.topk, lane, mv, mi);
+    }
+    [[maybe_unused]] int tk_col = -1; [[maybe_unused]] float tk_m = 0.f, tk_sum = 0.f;
     if (tid == 0) {
         for (int w = 1; w < 16; ++w) if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
         float lp_sum = 0.f;
@@ -250,7 +306,8 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
                     if constexpr (BIAS) if ((g_bia[tok >> 5] >> (tok & 31)) & 1u) lt += bias_of(q_id, q_sum, q_n, tok);
                     if constexpr (GUARD) lt = guard_score(lt, g_seen[tok >> 5] >> (tok & 31), g_ban[tok >> 5] >> (tok & 31), a.rep_penalty);
                 }
-                a.out_lp[(long)b * a.out_ld + a.n_new[b]] = (float)(((double)lt - (double)LPB) - log((double)lp_sum));
+                a.out_lp[((long)b * a.out_ld + a.n_new[b]) * (TOPK ? 1 + 2 * a.topk : 1)] = (float)(((double)lt - (double)LPB) - log((double)lp_sum));
+                if constexpr (TOPK) { tk_col = a.n_new[b]; tk_m = LPB; tk_sum = lp_sum; }
             }
             if constexpr (GUARD) { const int pos = a.kv_len[b]; if (pos >= 0 && pos < a.hist_ld) a.hist[(long)b * a.hist_ld + pos] = tok; }   // the token's position
             const int nn = a.n_new[b] + 1;
@@ -272,7 +329,18 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
         s_tok = tok;
         if (a.step_counter) a.step_counter[b] += 1;
     }
+    if constexpr (TOPK) {
+        // (words of their own: wave 1 may still be reading the waves' lists)
+        if (tid == 0) { s_tk_hand[0] = tk_m; s_tk_hand[1] = tk_sum; s_tk_col[0] = tk_col; }
+    }
     __syncthreads();
+    if constexpr (TOPK) if (wid == 1 && lane < a.topk && s_tk_col[0] >= 0) {
+        const int K = a.topk;
+        float* rec = a.out_lp + ((long)b * a.out_ld + s_tk_col[0]) * (1 + 2 * K);
+        const bool any = mi != TK_NONE;
+        rec[1 + lane] = any ? (float)(((double)mv - (double)s_tk_hand[0]) - log((double)s_tk_hand[1])) : -INFINITY;
+        rec[1 + K + lane] = any ? (float)mi : -1.f;      // (ids stay below 2^24: exact)
+    }
     const T* row = (const T*)a.table + (long)s_tok * a.d;
     T* xo = (T*)a.x;
     if (!a.y || (a.d >> 3) > 1024) {
@@ -322,16 +390,24 @@ void launch_hist_prompt(const int* src, const int* tok_seq, const int* tok_pos, 
 }
 size_t greedy_guard_lds(int V, bool bias) { return (size_t)(bias ? 3 : 2) * ((V + 31) / 32) * 4 + (bias ? (size_t)3 * BIAS_MAX_ENTRIES * 4 : 0); }
 // One family of the table below: its grid, block and LDS request, for fp32 rows (SONIC_MODE_F32: fp32 logits, table and rows) and for the 16-bit kinds
-template <bool LP, bool GUARD, bool BIAS, bool SAMPLE>
+template <bool LP, bool GUARD, bool BIAS, bool SAMPLE, bool TOPK = false>
 static void greedy_launch(const GreedyArgs& a, hipStream_t s) {
     const size_t lds = GUARD ? greedy_guard_lds(a.V, BIAS) : 0;      // GUARD: two vocabulary bitmaps of dynamic LDS; BIAS: a third and the matched list
-    if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, LP, GUARD, BIAS, SAMPLE>), dim3(a.B), dim3(1024), lds, s, a); return; }
-    DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, LP, GUARD, BIAS, SAMPLE>), dim3(a.B), dim3(1024), lds, s, a));
+    if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, LP, GUARD, BIAS, SAMPLE, TOPK>), dim3(a.B), dim3(1024), lds, s, a); return; }
+    DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, LP, GUARD, BIAS, SAMPLE, TOPK>), dim3(a.B), dim3(1024), lds, s, a));
 }
-// The nine families, chosen from the arguments: out_lp = option token_logprobs, hist = generation guards, bias_tab (counts only together with hist) = request
-// bias, samp (counts only together with out_lp) = option sampling.  One line per family: a combination that is not listed is not instantiated.
+// The fifteen families, chosen from the arguments: out_lp = option token_logprobs, hist = generation guards, bias_tab (counts only together with hist) = request
+// bias, samp (counts only together with out_lp) = option sampling, topk in 1 .. 8 (counts only together with out_lp) = option top_logprobs.  One line per family: a
+// combination that is not listed is not instantiated.
 void launch_greedy(const GreedyArgs& a, hipStream_t s) {
-    const bool lp = a.out_lp != nullptr, guard = a.hist != nullptr, bias = guard && a.bias_tab, sample = lp && a.samp;
+    const bool lp = a.out_lp != nullptr, guard = a.hist != nullptr, bias = guard && a.bias_tab, sample = lp && a.samp, topk = lp && a.topk >= 1 && a.topk <= 8;
+    //                                        LP     GUARD  BIAS   SAMPLE TOPK
+    if (topk && sample && bias)  return greedy_launch<true,  true,  true,  true,  true >(a, s);
+    if (topk && sample && guard) return greedy_launch<true,  true,  false, true,  true >(a, s);
+    if (topk && sample)          return greedy_launch<true,  false, false, true,  true >(a, s);
+    if (topk && bias)            return greedy_launch<true,  true,  true,  false, true >(a, s);
+    if (topk && guard)           return greedy_launch<true,  true,  false, false, true >(a, s);
+    if (topk)                    return greedy_launch<true,  false, false, false, true >(a, s);
     //                                LP     GUARD  BIAS   SAMPLE
     if (sample && bias)  return greedy_launch<true,  true,  true,  true >(a, s);
     if (sample && guard) return greedy_launch<true,  true,  false, true >(a, s);

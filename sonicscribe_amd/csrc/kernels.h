@@ -124,6 +124,10 @@ struct GreedyArgs {
     // fp32 temperature (0: greedy), its seed's low word, its high word.  The row's step index is n_new[row].  Needs out_lp.  Last: every offset above is what it was
     float* noise_out;
     const unsigned* samp;
+    // the step's best alternatives (greedy_kernel<T, true, ., ., ., true>, option top_logprobs).  topk = 0: off; 1 .. 8 = K: out_lp then holds 1 + 2K
+    // floats per token, [B][out_ld][1 + 2K]: the emitted token's log-probability, the K alternatives' (descending; -inf beyond the finite scores), their ids as fp32
+    // (-1 there).  Needs out_lp.  Last: every offset above is what it was
+    int topk;
 };
 #define SAMP_WORDS (64 * 3)
 #define BIAS_MAX_ENTRIES 256

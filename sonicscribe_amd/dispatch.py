@@ -550,9 +550,10 @@ class _NativeContinuousReplica:
 
     def _complete_loop(self):
         import ctypes as C
-        from .engine import SONIC_ERR_MISMATCH, SonicError
+        from .engine import SONIC_ERR_MISMATCH, SonicError, unpack_logprobs
         ids = np.zeros(self.out_cap, np.int32)
-        lps = np.zeros(self.out_cap, np.float32)
+        K = max([int(getattr(e, "top_logprobs", 0)) for e in self.engines] or [0]) if self.lp else 0      # (equal on all: sonic_dispatch_create refuses a mixed set)
+        lps = np.zeros(self.out_cap * (1 + 2 * K), np.float32)      # sonic_dispatch_next_lp: out_cap records of 1 + 2K floats
         err = C.create_string_buffer(512)
         t, st, n = C.c_int64(0), C.c_int32(0), C.c_int32(0)
         while True:
@@ -583,7 +584,7 @@ class _NativeContinuousReplica:
                 continue
             try:
                 if st.value == 0:
-                    req.future.set_result((ids[:n.value].copy(), lps[:n.value].copy()) if req.want_logprobs else ids[:n.value].copy())
+                    req.future.set_result((ids[:n.value].copy(), unpack_logprobs(lps, n.value, K)) if req.want_logprobs else ids[:n.value].copy())
                 else:
                     msg = err.value.decode(errors="replace")
                     if "audio spans" in msg or st.value == SONIC_ERR_MISMATCH:

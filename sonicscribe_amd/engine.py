@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Any, Dict, List, Optional, Sequence, Tuple
+from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -275,6 +275,26 @@ class Ring:
             pass
 
 
+class TokenScores(NamedTuple):
+    """A request's log-probabilities on a handle with option top_logprobs = K > 0: `lp` [n] float32 (the emitted tokens'), `top_logprobs` [n, K] float32 and
+    `top_ids` [n, K] int32 - at every step the K best ids by (score descending, id ascending) among the ids with a finite score, with their log-probabilities;
+    places beyond the finite scores hold (-inf, -1)."""
+    lp: np.ndarray
+    top_logprobs: np.ndarray
+    top_ids: np.ndarray
+
+
+def unpack_logprobs(rec, n: int, K: int):
+    """The first n records of a wide log-probability array (include/sonic_hip.h, option top_logprobs: 1 + 2K floats per token - the emitted token's
+    log-probability, the K alternatives', their ids as fp32) -> (lp [n], top_lp [n, K] float32, top_ids [n, K] int32).  K = 0: the records are the
+    log-probabilities themselves, and the result is that float32 array alone - what the wrappers returned before the option existed."""
+    W = 1 + 2 * int(K)
+    r = np.asarray(rec, np.float32).reshape(-1)[: int(n) * W].reshape(int(n), W)
+    if K == 0:
+        return r[:, 0].copy()
+    return TokenScores(r[:, 0].copy(), r[:, 1:1 + K].copy(), r[:, 1 + K:].astype(np.int32))
+
+
 class Engine(HooksMixin):
     """One model replica on one MI355X."""
 
@@ -307,6 +327,7 @@ class Engine(HooksMixin):
         root = self.root
         s = Engine(self.dims, 0, 0, self.max_batch, self.max_ctx, _slot_of=root)
         s.token_logprobs = bool(getattr(root, "token_logprobs", False))
+        s.top_logprobs = int(getattr(root, "top_logprobs", 0)) if s.token_logprobs else 0
         s.request_bias = bool(getattr(root, "request_bias", False))
         s.sampling = bool(getattr(root, "sampling", False))
         root._slots.append(s)
@@ -498,11 +519,13 @@ class Engine(HooksMixin):
         res = [out[r, : out_len[r]].copy() for r in range(R)]
         return (res, logits, self._fetch_logprobs(out_len, out_ld)) if want_logprobs else (res, logits)
 
-    def _fetch_logprobs(self, out_len, out_ld: int) -> List[np.ndarray]:
-        """sonic_fetch_logprobs for the batch whose token counts are out_len: one float32 array per request (entries beyond a row's count are never written)"""
-        lp = np.full((len(out_len), max(1, int(out_ld))), np.nan, np.float32)
+    def _fetch_logprobs(self, out_len, out_ld: int) -> list:
+        """sonic_fetch_logprobs for the batch whose token counts are out_len: one float32 array per request (entries beyond a row's count are never written);
+        with option top_logprobs one TokenScores per request (unpack_logprobs)"""
+        K = int(getattr(self, "top_logprobs", 0))
+        lp = np.full((len(out_len), max(1, int(out_ld)) * (1 + 2 * K)), np.nan, np.float32)
         self._check(self.lib.sonic_fetch_logprobs(self.h, _p(lp), lp.shape[1]))
-        return [lp[r, : out_len[r]].copy() for r in range(len(out_len))]
+        return [unpack_logprobs(lp[r], int(out_len[r]), K) for r in range(len(out_len))]
 
     def stage_pcm(self, segments: Sequence[Any], req_win: Optional[Sequence[int]] = None):
         if any(isinstance(s, RingSlice) for s in segments):
@@ -605,9 +628,10 @@ class Engine(HooksMixin):
         ld = max(1, int(c.max()) if len(c) else 1)
         out = np.zeros((len(r), ld), np.int32)
         if want_logprobs:
-            lp = np.full((len(r), ld), np.nan, np.float32)
+            K = int(getattr(self, "top_logprobs", 0))
+            lp = np.full((len(r), ld * (1 + 2 * K)), np.nan, np.float32)
             self._check(self.lib.sonic_fetch_rows_lp(self.h, len(r), _p(r), _p(c), _p(out), ld, _p(lp)))
-            return [out[i, :int(c[i])].copy() for i in range(len(r))], [lp[i, :int(c[i])].copy() for i in range(len(r))]
+            return [out[i, :int(c[i])].copy() for i in range(len(r))], [unpack_logprobs(lp[i], int(c[i]), K) for i in range(len(r))]
         self._check(self.lib.sonic_fetch_rows(self.h, len(r), _p(r), _p(c), _p(out), ld))
         return [out[i, :int(c[i])].copy() for i in range(len(r))]
 
@@ -640,6 +664,8 @@ class Engine(HooksMixin):
             self.request_bias = bool(value)          # (likewise)
         if key == "sampling":
             self.sampling = bool(value)              # (likewise)
+        if key == "top_logprobs":
+            self.top_logprobs = int(value)           # (likewise: the width of every log-probability record this handle returns)
         if key == "token_logprobs":
             self.token_logprobs = bool(value)        # (a slot created from now on copies it, in the library and here)
 

@@ -95,7 +95,8 @@ class HooksMixin:
     def _greedy(self, entry: str, slabs, B: int, want_logits: bool = True, want_lp: bool = True, force_ids=None, guard=None, tables=None, samp=None, want_noise: bool = False):
         """What the five greedy wrappers share: slabs, history, suppress list, tables, forced ids and outputs prepared once, then sonic_test_<entry> - the C entry
         point of the wrapper that calls, never another family's.  guard = (hist, hist_len, repetition_penalty, no_repeat_ngram_size, suppress_tokens) for the
-        entries that take histories; samp = (temperature, seed, step).  -> (tok, logits or None, lp or None, noise or None)"""
+        entries that take histories; samp = (temperature, seed, step).  -> (tok, logits or None, lp or None, noise or None).  On a handle with option
+        top_logprobs = K > 0 the hooks return row b's whole record, and lp is an engine.TokenScores: lp [B], top_logprobs [B, K], top_ids [B, K]"""
         s = np.ascontiguousarray(slabs, np.float32)
         ks, mpad, V = s.shape
         args = [_p(s), ks, mpad, V, B]
@@ -124,10 +125,14 @@ class HooksMixin:
             args += [_p(t), _p(sd), _p(stp)]
         tok = np.zeros(B, np.int32)
         lg = np.zeros((B, V), np.float32) if want_logits else None
-        lp = np.full(B, np.nan, np.float32) if want_lp else None
+        K = int(getattr(self, "top_logprobs", 0))
+        lp = np.full(B * (1 + 2 * K), np.nan, np.float32) if want_lp else None
         noise = np.zeros((B, V), np.float32) if want_noise else None
         out = [tok, lg] + ([lp] if entry != "greedy" else []) + ([noise] if samp is not None else [])
         self._check(getattr(self.lib, "sonic_test_" + entry)(self.h, *args, *[_p(o) for o in out]))
+        if K and lp is not None:
+            from .engine import unpack_logprobs
+            lp = unpack_logprobs(lp, B, K)
         return tok, lg, lp, noise
 
     def test_greedy(self, slabs, B: int, want_logits: bool = False):
