@@ -434,7 +434,34 @@ SONIC_API int sonic_stage_mixed(sonic_engine* e, const int16_t* host_pcm, const 
 
 /* Teacher forcing (parity tests; mirrors the oracle's force_ids): while set, token n of request r is ids[r * ld + n] instead of
  * the argmax -- logits are still computed and returned, EOS / budget rules apply to the forced token (HF:generation/utils.py:2925-2936
- * with next_tokens replaced).  ids == NULL clears.  Forced runs use the eager decode loop. */
+ * with next_tokens replaced).  ids == NULL clears.  Forced runs use the eager decode loop.
+ *
+ * The parallel forced run (scoring given transcripts; options "forced_parallel", "forced_fanout", "score_chunk_rows").  Under teacher forcing no
+ * input depends on an output, so while option "forced_parallel" is 1 AND forced ids are set, a run through sonic_transcribe_batch, sonic_transcribe_mixed,
+ * sonic_run_staged or sonic_run_staged_async is computed as ONE prefill pass instead of the eager loop: sequence r is its prompt followed by
+ * ids[r][0 .. L_r - 1), where L_r = 1 + the index of the first EOS id among ids[r][0 .. max_new[r]), or max_new[r] if there is none (the rule above); the tied lm_head
+ * runs over all forced positions as one GEMM per chunk of "score_chunk_rows" rows (16 .. 4096, default 256), and a row kernel takes log_softmax(logits)[ids[r][n]] of
+ * every position.  Only ids[r][0 .. L_r) is read: pad rows with any valid id.  With the option 0, or without forced ids, the engine launches exactly what it did.
+ *   results, through the existing calls: out_ids[r][0 .. L_r) are the forced ids and out_len[r] = L_r; sonic_fetch_logprobs returns the records in its layout
+ *   (1 + 2K floats per token with option top_logprobs = K: the forced token's log-probability, the K best ids of that position by (score descending, id ascending)
+ *   with their log-probabilities, formed from the same maximum and sum) and needs option token_logprobs, as ever; step_logits [n][r][V] are returned if asked, rows
+ *   n >= L_r of a request are not written; sonic_get_timings fills mel / encoder / prefill as for a run whose decode loop took no step.  The handle then holds
+ *   a finished batch: sonic_decode_step reports 0 active rows, and the next run may follow at once.
+ *   NO logits processor is applied, whatever the handle carries: the parallel run scores the RAW model distribution at temperature 1 - HF's
+ *   compute_transition_scores over `logits`, not over `scores`.  With generation guards active this is the one difference from the step-by-step forced run.
+ *   Tables of sonic_set_request_bias or values of sonic_set_request_sampling staged for such a run are refused (SONIC_ERR_INVALID) and consumed.
+ *   "forced_fanout" = N (1 .. max_batch, default 1; read as a parallel run starts): the call's R sequences are R / N audio requests with N candidate sequences
+ *   each - sequence r takes its audio rows from audio request r / N, req_win has R / N + 1 entries (NULL: W == R / N), and log-mel, encoder and projector run once
+ *   per audio request.  R not divisible by N: SONIC_ERR_INVALID.  Each sequence prefills its own prompt; only the encoder is shared.
+ *   refusals (SONIC_ERR_INVALID, the message naming the cause): prompts and forced ids together beyond one prefill (the message says how many tokens were asked
+ *   and how many fit); the audio placeholder id among the forced ids; and the existing checks (placeholder count, vocabulary, prompt + max_new <= max_ctx).
+ *   "forced_parallel" is refused while the handle has work in hand (the rule of sonic_set_generation).  Slots copy it from their owner; it may also be set on a
+ *   slot alone.  A handle with the option on is a scoring handle: sonic_prefill, sonic_prefill_enqueue, sonic_service_begin, sonic_splice_rows (as source or
+ *   destination), sonic_dispatch_create and sonic_pipeline_create refuse it by name.  Its buffers (the chunk's logits: score_chunk_rows x vocab elements; three
+ *   words per score row) come with its first parallel run, are counted by sonic_memory_info and go with the handle.
+ *   test hook: on such a handle sonic_test_greedy_lp sends its rows to the row kernel instead - the slabs are summed over ksplit in the greedy kernel's order and
+ *   rounded to the element type, those values are the logits row the kernel reads and logits_out returns them; force_ids is required, tok_out holds the forced ids,
+ *   lp_out B records of 1 + 2K floats; B may exceed 64 (up to 4096), mpad stays the slab row stride. */
 SONIC_API int sonic_set_forced_ids(sonic_engine* e, const int32_t* ids, int R, int ld);
 SONIC_API int sonic_get_timings(sonic_engine* e, sonic_timings* out);
 SONIC_API int sonic_synchronize(sonic_engine* e);
@@ -530,7 +557,8 @@ SONIC_API int sonic_debug_ktrace(sonic_engine* e, int64_t* out, int64_t n);
  * DESIGN.md 1.  Round 6: "no_pre_norm" (<= 2 rows: standalone add + RMSNorm launches instead of the five-launch chain; same bits), "decode_gemv" / "decode_prefetch" /
  * "decode_attn_occ2" (experiments that lost: profiles/round6_*), "f32_synth_bf16" (SONIC_MODE_F32: sonic_load_synthetic writes the bf16-rounded values),
  * "inject_dev_err" (tests: sets / clears the device error word); "token_logprobs" (not an experiment: per-token log-probabilities, see sonic_fetch_logprobs);
- * "top_logprobs" (not an experiment either: the K best alternatives of every step in the same records, see sonic_fetch_logprobs) */
+ * "top_logprobs" (not an experiment either: the K best alternatives of every step in the same records, see sonic_fetch_logprobs);
+ * "forced_parallel", "forced_fanout", "score_chunk_rows" (not experiments: forced runs as one prefill pass - scoring given transcripts - see sonic_set_forced_ids) */
 SONIC_API int sonic_set_option(sonic_engine* e, const char* key, int value);
 
 /* ---- Silero VAD network (silero-vad 5.x / 6.x, 16 kHz branch; csrc/vad.hip, layer table in sonicscribe_amd/vad_net.py) ----

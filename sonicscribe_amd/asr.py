@@ -29,6 +29,7 @@ import numpy as np
 from . import frontend
 from .dispatch import Dispatcher
 from .engine import Engine, MODE_INT8, MODE_NATIVE, SonicError, TokenScores, device_count, device_info
+from .scoring import Score
 from .spec import FULL, ModelDims
 
 
@@ -249,6 +250,7 @@ class ASRModel:
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None,
                  request_bias: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: float = 0.0,
                  sampling: bool = False, temperature=0.0, seed: int = 0, compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
+                 scoring: bool = False,
                  _dims: Optional[ModelDims] = None,
                  _synthetic_seed: Optional[int] = None, _allow_synthetic_prompt: bool = False, _options: Optional[Dict[str, int]] = None,
                  _engine_mode: Optional[int] = None):
@@ -258,7 +260,8 @@ class ASRModel:
         `hotword_boost` here are defaults for every request and switch `request_bias` on.  `top_logprobs` = K in 1 .. 8 (needs token_logprobs=True; not with
         bulk=True): every `detailed=True` result also carries the K best ids of every step with their log-probabilities.  `sampling` (needs token_logprobs=True): requests may be decoded at a
         temperature with a seed, or down a fallback ladder of temperatures (fallback.py); `temperature` (a float: one attempt; a sequence: the
-        ladder), `seed` and the two thresholds of the ladder here are the defaults of every call.  The arguments with a leading underscore are not part of the
+        ladder), `seed` and the two thresholds of the ladder here are the defaults of every call.  `scoring` (needs token_logprobs=True): score() / score_batch() give the log-probability of transcripts the caller
+        brings, in one prefill pass per run on a handle of their own per replica; off, no such handle exists.  The arguments with a leading underscore are not part of the
         supported surface: they exist for the test-suite and the benchmark and may change without notice.  `_engine_mode` in particular (an engine.MODE_*
         value in place of the one `mode` selects) is unsupported outside the tests: MODE_F32 has no slots, so it needs slots=1, continuous=False."""
         if mode not in ["native", "int8"]:
@@ -276,6 +279,9 @@ class ASRModel:
             raise ValueError("sampling=True needs token_logprobs=True: the sampling kernels are log-probability kernels, and the fallback ladder reads avg_logprob")
         if self.sampling and bool(bulk):
             raise ValueError("sampling is not supported with bulk=True: the bulk pipeline carries no per-request values")
+        self.scoring = bool(scoring)
+        if self.scoring and not token_logprobs:
+            raise ValueError("scoring=True needs token_logprobs=True: a score is the candidates' token log-probabilities (ASRModel(..., token_logprobs=True, scoring=True))")
         dev = str(device)
         if dev.startswith("cpu"):
             raise RuntimeError("sonicscribe_amd runs on MI355X only: DEVICE=cpu has no HIP path (no CPU fallback by design)")
@@ -372,6 +378,17 @@ class ASRModel:
         self.continuous = bool(continuous) or self.bulk
         self.decoders = max(1, int(decoders)) if self.continuous else 0
         self.slots = max(self.decoders + 1 if self.continuous else 1, int(slots))
+        # scoring: one further slot per replica with option forced_parallel on, used for nothing else - score() runs on it from the caller's thread, beside the
+        # dispatcher's loops, on the slot's own stream (as a prefill slot does); a lock per replica serialises the calls.  Made before the dispatcher takes the others
+        import threading
+        self._score_engines: List[Engine] = []
+        if self.scoring:
+            for eng in self.models:
+                s_ = eng.slot()
+                s_.set_option("forced_parallel", 1)
+                self._score_engines.append(s_)
+        self._score_locks = [threading.Lock() for _ in self._score_engines]
+        self._score_next = 0
         self._slot_engines = [[eng.slot() for _ in range(self.slots - 1)] for eng in self.models]     # same weights, further batches in flight
         self._dispatcher = Dispatcher(self.models, slots=self._slot_engines, continuous=self.continuous, decoders=self.decoders or 1,
                                       adaptive_tiles="gemm_small_eff" not in (_options or {}), bulk=self.bulk, native=native_dispatch)
@@ -580,6 +597,62 @@ class ASRModel:
             ids = [f.result() for f in futs]
         return [self.prompt.decode(i).strip() for i in ids]
 
+    # -- scoring: how probable is THIS transcript, given THIS audio
+    def _candidate_ids(self, cand) -> List[int]:
+        if isinstance(cand, str):
+            if not isinstance(self.prompt, HFPrompt):
+                raise ValueError("a text candidate needs a tokenizer (a checkpoint with its processor): the synthetic prompt has none - pass token ids")
+            return [int(t) for t in self.prompt.processor.tokenizer.encode(cand, add_special_tokens=False)]
+        return [int(t) for t in np.asarray(cand).reshape(-1)]
+
+    def score(self, audio, candidates, sampling_rate: int = 16000, hotwords: Optional[List[str]] = None, append_eos: bool = True) -> List["Score"]:
+        """The log-probability of each candidate transcript given the audio: n-best / hotword-list rescoring, keyword verification, comparing an edited
+        transcript with the greedy one.  A candidate is a string (tokenised with the checkpoint's tokenizer) or a sequence of token ids.  The prompt is the one
+        transcribe() builds (same hotword sentence, same audio-token count); all candidates share one encoder pass.  append_eos: the first EOS id is appended as a
+        last target, so that hypotheses of different length compare as HF's sequence scores do.  The scores are those of the raw model distribution at temperature
+        1: no logits processor (repetition penalty, bias, ...) is applied, whatever the model carries.  Needs a model built with scoring=True."""
+        return self.score_batch([audio], [candidates], sampling_rate, hotwords, append_eos)[0]
+
+    def score_batch(self, audios: Sequence[Any], candidates_per_audio: Sequence[Sequence[Any]], sampling_rate: int = 16000,
+                    hotwords: Optional[List[str]] = None, append_eos: bool = True) -> List[List["Score"]]:
+        """score() for several audios, each with its own candidates: as few runs as hold them (scoring.plan_runs), the same bits as one call per audio."""
+        from . import scoring as scoring_
+        if not hasattr(self, "model"):
+            raise RuntimeError("ASR model has been released")
+        if not getattr(self, "scoring", False) or not self._score_engines:
+            raise ValueError("score() needs a model built with scoring=True (ASRModel(..., token_logprobs=True, scoring=True))")
+        if len(audios) != len(candidates_per_audio):
+            raise ValueError(f"{len(audios)} audios but {len(candidates_per_audio)} candidate lists")
+        eos = self._eos_ids()
+        instruction = frontend.build_instruction(hotwords)
+        wins_of, prompts, targets = [], [], []
+        for a, cands in zip(audios, candidates_per_audio):
+            _, wins, n_audio = self._prepare(a, sampling_rate)
+            wins_of.append(wins)
+            prompts.append(self.prompt.build(instruction, n_audio))
+            targets.append([scoring_.with_eos(self._candidate_ids(c), eos, append_eos) for c in cands])
+        i = self._score_next % len(self._score_engines)
+        self._score_next += 1
+        eng = self._score_engines[i]
+        runs = scoring_.plan_runs([len(p) for p in prompts], [[len(t) for t in ts] for ts in targets], eng.max_batch, eng.tok_cap, eng.max_ctx)
+        dummy = next(t for t in range(self.dims.vocab) if t != self.dims.audio_token_id and t not in eos)
+        out: List[List[Optional[scoring_.Score]]] = [[None] * len(ts) for ts in targets]
+        with self._score_locks[i]:
+            for run in runs:
+                segs, req_win, run_prompts = [], [0], []
+                for a, part in run.groups:
+                    segs.extend(wins_of[a])
+                    req_win.append(len(segs))
+                    run_prompts.extend([prompts[a]] * len(part))
+                ids, _, lps = eng.score_batch(segs, run_prompts, scoring_.run_targets(run, targets, dummy), req_win=req_win, fanout=run.fanout)
+                r = 0
+                for a, part in run.groups:
+                    for c in part:
+                        if c is not None:        # (a dummy's result is cut again)
+                            out[a][c] = scoring_.Score(self.prompt.decode(ids[r]).strip(), ids[r], lps[r])
+                        r += 1
+        return out      # type: ignore[return-value]
+
     def transcribe_file(self, audio, vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                         max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filename: str = "", sampling_rate: int = 16000,
                         sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None, seed: Optional[int] = None):
@@ -613,6 +686,7 @@ class ASRModel:
                      "gpu_memory_total_mb": di["total_bytes"] / 1024 ** 2})
         info.update({"engine": "sonicscribe_amd/gfx950", "replicas": len(self.__dict__.get("models", [])), "slots_per_replica": self.__dict__.get("slots", 1), "continuous": self.__dict__.get("continuous", False), "bulk": self.__dict__.get("bulk", False),
                      "weights_mb": self.model.weight_bytes() / 1024 ** 2 if hasattr(self, "model") else 0.0})
+        info["scoring"] = bool(self.__dict__.get("scoring", False))
         g = self.__dict__.get("generation_guards")
         if g is not None:                            # the logits processors in force: the checkpoint's generation_config.json unless the constructor overrode it
             info.update(g.as_dict())
@@ -627,6 +701,7 @@ class ASRModel:
             c.close()
         self.__dict__.pop("model", None)
         self.__dict__.pop("_slot_engines", None)
+        self.__dict__.pop("_score_engines", None)
         for m in self.__dict__.pop("models", []):
             m.close()                                # (an engine closes its slots first)
 

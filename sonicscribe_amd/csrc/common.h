@@ -51,7 +51,9 @@ inline void ensure_dyn_lds(const void* fn, int bytes) {
     int dev = 0;
     (void)hipGetDevice(&dev);
     std::lock_guard<std::mutex> lk(mu);
-    if (done.insert({dev, fn}).second) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    // (a refused request - more than the kernel may have beside its static part - must not stay behind as the thread's last error: the launch that follows
+    //  reports what matters, and a later hipGetLastError check would blame whatever ran in between)
+    if (done.insert({dev, fn}).second && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) (void)hipGetLastError();
 }
 
 // Experiment knobs.  They belong to an ENGINE (sonic_set_option stores them there); the launchers read this thread-local copy,

@@ -35,6 +35,7 @@
 #include "../../include/sonic_hip.h"
 extern "C" int engine_token_logprobs_on(sonic_engine* e);   // engine.cpp
 extern "C" int engine_top_logprobs(sonic_engine* e);        // engine.cpp: option top_logprobs of this handle (K: its log-probability records hold 1 + 2K floats)
+extern "C" int engine_forced_parallel_on(sonic_engine* e);  // engine.cpp: option forced_parallel of this handle (a scoring handle: refused here)
 extern "C" int engine_request_bias_on(sonic_engine* e);     // engine.cpp: option request_bias on this handle
 extern "C" int engine_bias_validate(sonic_engine* e, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n);   // engine.cpp: one request's table against the caps and this handle's vocabulary
 extern "C" int engine_sampling_on(sonic_engine* e);         // engine.cpp: option sampling on this handle
@@ -309,6 +310,9 @@ SONIC_API int sonic_dispatch_create(sonic_engine* const* decoders, int n_dec, so
     for (int i = 1; i < n_dec + n_pre; ++i)                     // (a splice between handles of different K would be refused row by row: refuse the set)
         if (engine_top_logprobs(i < n_dec ? decoders[i] : prefills[i - n_dec]) != engine_top_logprobs(decoders[0]))
             return engine_thread_fail(SONIC_ERR_INVALID, "sonic_dispatch_create: the handles differ in option top_logprobs (set it on the owner before its slots are created)");
+    for (int i = 0; i < n_dec + n_pre; ++i)
+        if (engine_forced_parallel_on(i < n_dec ? decoders[i] : prefills[i - n_dec]))
+            return engine_thread_fail(SONIC_ERR_INVALID, "sonic_dispatch_create: option forced_parallel is on on a handle: a scoring handle takes no part in the dispatcher");
     sonic_dispatch* d = new sonic_dispatch();
     d->dec.assign(decoders, decoders + n_dec); d->pre.assign(prefills, prefills + n_pre);
     d->n_rows = rows; d->pre_cap = cap; d->adaptive_tiles = adaptive_tiles != 0;

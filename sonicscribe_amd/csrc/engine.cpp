@@ -354,6 +354,26 @@ int lp_alloc(sonic_engine* e) {
     HIPC(e, stream_sync(e));
     return SONIC_OK;
 }
+// the parallel forced run's buffers, at the first such run of the handle or when score_chunk_rows has grown since: the chunk's logits
+// [score_chunk_rows][vocab] in the activation type (fp32 kind: fp32) and the score rows' plan (3 words per row, at most tok_cap rows) on the device and pinned
+int score_alloc(sonic_engine* e) {
+    const int rows = e->opt_score_chunk_rows;
+    const size_t esz = e->f32 ? 4 : 2;
+    if (e->score_logits && e->score_rows_cap < rows) {
+        HIPC(e, stream_sync(e));
+        e->allocs.erase(std::find(e->allocs.begin(), e->allocs.end(), e->score_logits));
+        HIPC(e, hipFree(e->score_logits));
+        e->alloc_bytes -= (int64_t)(((size_t)e->score_rows_cap * e->d.vocab * esz + 3) / 4 * 4); e->score_logits = nullptr; e->score_rows_cap = 0;
+    }
+    if (!e->score_logits) {
+        unsigned char* p = nullptr;
+        TRY(dalloc(e, &p, (size_t)rows * e->d.vocab * esz, false));
+        e->score_logits = p; e->score_rows_cap = rows;
+    }
+    if (!e->score_plan_d) TRY(dalloc(e, &e->score_plan_d, (size_t)3 * e->tok_cap));
+    if (!e->score_plan_h && hipHostMalloc((void**)&e->score_plan_h, ((size_t)3 * e->tok_cap + 4 * 64) * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(e, SONIC_ERR_OOM, "forced_parallel: pinned host memory exhausted"); }
+    return SONIC_OK;
+}
 // option top_logprobs = K: the K best alternatives of every step ride in the token's log-probability record, which grows to 1 + 2K floats.  The
 // buffer is exchanged for one of the new width (sonic_memory_info follows), so the records of a finished batch that has not been fetched yet are gone with the
 // old one: fetch first (include/sonic_hip.h says so).  The caller holds the lock and has asked gen_busy.
@@ -381,6 +401,7 @@ int lp_check(sonic_engine* e, const char* who) {
 extern "C" int engine_token_logprobs_on(sonic_engine* e) { return e && e->opt_token_logprobs && e->out_lp ? 1 : 0; }
 // ... and how many alternatives ride along (option top_logprobs: its log-probability records hold 1 + 2K floats per token)
 extern "C" int engine_top_logprobs(sonic_engine* e) { return e && e->opt_token_logprobs && e->out_lp ? e->opt_top_logprobs : 0; }
+extern "C" int engine_forced_parallel_on(sonic_engine* e) { return e && e->opt_forced_parallel ? 1 : 0; }      // ... and is it a scoring handle (option forced_parallel: the schedulers refuse it)
 extern "C" int engine_fail(sonic_engine* e, int code, const char* msg) { std::lock_guard<std::mutex> lk(e->mu); return fail(e, code, "%s", msg); }   // a message on a handle, from outside its calls
 
 // ---- generation guards: validation, the history / suppress buffers on first use, the upload.  The caller holds the lock and has made sure nothing is in flight.
@@ -674,6 +695,7 @@ extern "C" int sonic_slot_create(sonic_engine* parent, sonic_engine** out) {
     e->opt_bias_fill = root->opt_bias_fill;
     if (root->opt_sampling && (s = samp_enable(e, 1)) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }
     e->opt_samp_fill_milli = root->opt_samp_fill_milli;
+    e->opt_forced_parallel = root->opt_forced_parallel; e->opt_forced_fanout = root->opt_forced_fanout; e->opt_score_chunk_rows = root->opt_score_chunk_rows;      // (the buffers come with the slot's first parallel run)
     e->weight_bytes = 0; e->finalized = true; e->owner = root;
     root->slots.push_back(e);
     *out = e;
@@ -729,6 +751,7 @@ extern "C" void sonic_destroy(sonic_engine* e) {
     if (e->n_active_h) (void)hipHostFree(e->n_active_h);
     for (int i = 0; i < 2; ++i) { if (e->plan_buf[i]) (void)hipHostFree(e->plan_buf[i]); if (e->plan_ev[i]) (void)hipEventDestroy(e->plan_ev[i]); }
     if (e->svc_h) (void)hipHostFree(e->svc_h);
+    if (e->score_plan_h) (void)hipHostFree(e->score_plan_h);
     stage_free(e->bias); stage_free(e->samp);
     if (e->st_io) { (void)hipStreamSynchronize(e->st_io); (void)hipStreamDestroy(e->st_io); }
     if (e->xfer_ev) (void)hipEventDestroy(e->xfer_ev);

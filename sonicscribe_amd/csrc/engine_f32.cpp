@@ -158,7 +158,7 @@ static void f32_lm_head(sonic_engine* e, int R, const int* last_row) {
     launch_f32_rmsnorm(f.dx, f.dec_nw, f.hlast, R, d.dec_d, d.dec_rms_eps, last_row, e->st);
     f32_linear(e, f.hlast, d.dec_d, f.embed, nullptr, f.logits, d.vocab, R, d.vocab, d.dec_d);
 }
-int f32_run_prefill(sonic_engine* e, int R, const HostPlan& hp) {
+int f32_run_prefill(sonic_engine* e, int R, const HostPlan& hp, bool head) {
     F32State& f = *e->f;
     const sonic_dims& d = e->d;
     const int D = d.dec_d, M = hp.n_tok;
@@ -171,8 +171,19 @@ int f32_run_prefill(sonic_engine* e, int R, const HostPlan& hp) {
         HIPC(e, hipMemcpyAsync(e->taps, f.dx, (size_t)M * D * 4, hipMemcpyDeviceToDevice, e->st));
     }
     f32_decoder_layers(e, M, e->tok_seq, e->tok_pos_pf);
-    f32_lm_head(e, R, e->last_row);            // logits of the last prompt position only (logits_to_keep = 1, generation/utils.py:2612-2616)
+    if (head) f32_lm_head(e, R, e->last_row);  // logits of the last prompt position only (logits_to_keep = 1, generation/utils.py:2612-2616)
     return SONIC_OK;
+}
+// the parallel forced run's tail (run_forced_parallel): the final norm of the S score rows `row_map` names -> dhn [S][d] (free behind the last layer), and the tied
+// lm_head over rows row0 .. row0 + n of them -> logits [n][vocab]
+void f32_score_norm(sonic_engine* e, const int* row_map, int S) {
+    F32State& f = *e->f;
+    launch_f32_rmsnorm(f.dx, f.dec_nw, f.dhn, S, e->d.dec_d, e->d.dec_rms_eps, row_map, e->st);
+}
+void f32_score_logits(sonic_engine* e, int row0, int n, float* logits) {
+    F32State& f = *e->f;
+    const sonic_dims& d = e->d;
+    f32_linear(e, f.dhn + (size_t)row0 * d.dec_d, d.dec_d, f.embed, nullptr, logits, d.vocab, n, d.vocab, d.dec_d);
 }
 // one token step for R rows (generation/utils.py:2876-2943): the rows' input embeddings are in f.dx (greedy_kernel<float> left them there)
 void decode_step_f32(sonic_engine* e, int R, bool dump) {

@@ -455,6 +455,34 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
     }
     return SONIC_OK;
 }
+// sonic_test_greedy_lp on a handle with option forced_parallel on: the rows go to score_rows_kernel (score.hip) instead.  The slabs are summed over ksplit
+// in the greedy kernel's order and rounded to the handle's element type: those values are the logits row the kernel reads, and logits_out returns them.  force_ids is
+// required; tok_out holds the forced ids, lp_out B records of 1 + 2K floats.  B may exceed 64 on this route (one block per row); mpad stays the slab row stride
+static int test_score(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const int32_t* force_ids, int32_t* tok_out, float* logits_out, float* lp_out) {
+    if (ksplit < 1 || ksplit > 8 || B < 1 || B > 4096 || mpad < B || V < 4 || V % 4 || V > (1 << 24)) return fail(e, SONIC_ERR_INVALID, "bad score test shape");
+    if (!force_ids) return fail(e, SONIC_ERR_INVALID, "forced_parallel: the score rows need their forced ids");
+    for (int b = 0; b < B; ++b) if (force_ids[b] < 0 || force_ids[b] >= V) return fail(e, SONIC_ERR_INVALID, "forced id %d out of vocabulary", force_ids[b]);
+    const int K = e->opt_top_logprobs, W = 1 + 2 * K, dt = e->f32 ? DT_F32 : e->dt;
+    TmpBuf tb(e->st);
+    float* dl = up_f32(e, tb, slabs, (size_t)ksplit * mpad * V);
+    unsigned char* rows = tb.get<unsigned char>((size_t)B * V * (e->f32 ? 4 : 2));
+    int* plan = tb.get<int>((size_t)2 * B); int* ids = tb.get<int>(B);
+    float* lp = tb.get<float>((size_t)B * W); float* dump = logits_out ? tb.get<float>((size_t)B * V) : nullptr;
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    std::vector<int> h((size_t)2 * B);
+    for (int b = 0; b < B; ++b) { h[b] = force_ids[b]; h[B + b] = b; }      // record b = sequence b, token 0 (out_ld = 1)
+    HIPC(e, h2d(e, plan, h.data(), h.size() * 4));
+    launch_score_slab_rows(dl, ksplit, mpad, V, B, rows, dt, e->st);
+    ScoreArgs a{};
+    a.logits = rows; a.ld = V; a.V = V; a.n = B; a.dt = dt; a.target = plan; a.rec = plan + B; a.out_ids = ids; a.out_lp = lp; a.topk = K; a.dump = dump; a.out_ld = 1; a.R = B;
+    launch_score_rows(a, e->st);
+    HIPC(e, stream_sync(e));
+    HIPC(e, hipGetLastError());
+    HIPC(e, d2h(e, tok_out, ids, (size_t)B * 4));
+    if (logits_out) HIPC(e, d2h(e, logits_out, dump, (size_t)B * V * 4));
+    HIPC(e, d2h(e, lp_out, lp, (size_t)B * W * 4));
+    return SONIC_OK;
+}
 extern "C" int sonic_test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, int32_t* tok_out, float* logits_out) {
     if (!e || !slabs || !tok_out) return SONIC_ERR_INVALID;
     ENTER(e);
@@ -464,6 +492,7 @@ extern "C" int sonic_test_greedy_lp(sonic_engine* e, const float* slabs, int ksp
                                     float* logits_out, float* lp_out) {
     if (!e || !slabs || !tok_out || !lp_out) return SONIC_ERR_INVALID;
     ENTER(e);
+    if (e->opt_forced_parallel) return test_score(e, slabs, ksplit, mpad, V, B, force_ids, tok_out, logits_out, lp_out);
     return test_greedy(e, slabs, ksplit, mpad, V, B, force_ids, tok_out, logits_out, lp_out);
 }
 

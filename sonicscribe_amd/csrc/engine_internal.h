@@ -27,6 +27,7 @@
 #define CHK_RING 64            // check events / pinned n_active words of the decode loop
 #define DEV_ERR_ACTIVE (-(1 << 23))   // a running-row count below this: the device error word was set (greedy_kernel), the step's outputs are invalid
 #define SVC_WORDS 132           // per check of the continuous loop: finished[64], n_new[64], n_active, padding
+#define SCORE_CHUNK_DEFAULT 256   // score rows per lm_head GEMM + row-kernel launch of the parallel forced run (option score_chunk_rows; DESIGN.md 6.8 says why)
 #define CHK_MAX_AHEAD 32       // deepest lookahead in chunks (a host that is frozen for tens of ms at a time - CPU quota, a busy event loop)
 
 struct DevTensor {
@@ -136,6 +137,7 @@ struct sonic_engine {
     int* n_active_h = nullptr;  // pinned
     int R = 0, max_steps = 0, greedy_calls = 0, steps_run = 0; bool run_logits = false;   // state of the staged batch between the stage entry points
     int* force_d = nullptr; int force_ld = 0, force_R = 0;   // teacher forcing for the next runs (sonic_set_forced_ids)
+    std::vector<int> force_h;                                // ... and the host's copy of those ids: the parallel forced run plans from them
     std::vector<int> last_qlen, last_maxnew;
     std::map<std::pair<int, int>, hipGraphExec_t> graphs;        // (rows, token steps) -> captured chunk of the decode loop
     // the pipelined early-stop check: behind every chunk the device's count of running rows is copied to n_active_h[chunk % CHK_RING] and an
@@ -198,6 +200,13 @@ struct sonic_engine {
     int opt_sampling = 0;
     int opt_samp_fill_milli = 0;   // measurement aid (option sampling_fill_milli, tools/ab_sampling.sh): a prefill that was given no values decodes request r at this temperature (in thousandths) with seed r
     ReqStage<unsigned> samp;
+    // the parallel forced run (options forced_parallel / forced_fanout / score_chunk_rows; run_forced_parallel, engine_stages.cpp): with forced ids set,
+    // a run is ONE prefill of prompt || forced ids, the lm_head over every forced position as a GEMM per chunk of score rows, and score_rows_kernel per row.
+    // score_logits: the chunk's logits [score_rows_cap][vocab] in the activation type (fp32 kind: fp32); score_plan_d / score_plan_h: per score row its hidden-state
+    // row, its target id and its record index, on the device and in pinned memory (one buffer: the run ends with a stream synchronise).  All three come with the
+    // first parallel run, are counted by sonic_memory_info and go with the handle
+    int opt_forced_parallel = 0, opt_forced_fanout = 1, opt_score_chunk_rows = SCORE_CHUNK_DEFAULT;
+    void* score_logits = nullptr; int score_rows_cap = 0; int* score_plan_d = nullptr; int* score_plan_h = nullptr;
     uint64_t spliced = 0;          // rows of the last prefill that sonic_splice_rows handed to a continuous loop (bit r = request r); cleared by every prefill (gen_busy)
     long long* kt = nullptr; int kt_layer = -1;     // diagnostics ("ktrace" option): in-kernel timestamps of one decoder layer's kernels
     int* ring_peak = nullptr;                        // [Bm] per-request max |s| of a ring-staged batch (ingest.hip)
@@ -296,7 +305,9 @@ int f32_alloc(sonic_engine* e);
 int f32_finalize(sonic_engine* e);
 int f32_run_encoder(sonic_engine* e, int W, float* enc_layers_out, float* enc_out_host);
 GreedyArgs f32_greedy_args(sonic_engine* e, int R, bool dump);
-int f32_run_prefill(sonic_engine* e, int R, const HostPlan& hp);
+int f32_run_prefill(sonic_engine* e, int R, const HostPlan& hp, bool head = true);   // head = false: the decoder layers only (the parallel forced run scores other rows)
+void f32_score_norm(sonic_engine* e, const int* row_map, int S);                         // the final norm of the S score rows -> dhn [S][d] ...
+void f32_score_logits(sonic_engine* e, int row0, int n, float* logits);                  // ... and the tied lm_head over rows row0 .. row0 + n of them
 void decode_step_f32(sonic_engine* e, int R, bool dump);
 
 // ------------------------------------------------------------------------------------------ ingest (engine_ingest.cpp), service (engine_service.cpp)
@@ -344,5 +355,6 @@ RopeAppendArgs rope_append_args(const bf16_t* qkv, bf16_t* q_out, bf16_t* Kc, bf
 enum { OGU_FUSED = 0, OGU_SPLIT_NORM = 1, OGU_HALF_FUSED = 2, OGU_UNFUSED = 3 };
 struct OGuChain { const bf16_t *att, *Wo; bf16_t* x; const float* ln_w; const bf16_t* Wgu; int gu8; bf16_t *hn, *act; float *ss, *slab; long long *kt_o, *kt_gu; };
 void launch_o_gu(sonic_engine* e, int form, const OGuChain& c, int M, int K, int D, int ff, float eps);
+int score_alloc(sonic_engine* e);                                  // the parallel forced run's buffers at the handle's current score_chunk_rows (first use, or a larger chunk)
 int upload_plan(sonic_engine* e, int R, const HostPlan& hp);       // the prefill's prologue, every kind: the request plan through the pinned staging buffer ...
 int reset_row_state(sonic_engine* e, int R, int n_tok);            // ... and the rows' counters, history, bias tables and sampling values for the greedy loop

@@ -37,6 +37,13 @@ static int opt_request_bias_fill(sonic_engine* e, const char* key, int value) { 
     if (value < 0 || value > BIAS_MAX_ENTRIES || value > e->d.vocab) return fail(e, SONIC_ERR_INVALID, "request_bias_fill: %d is outside 0 .. %d", value, BIAS_MAX_ENTRIES);
     TRY(gen_busy(e, key)); e->opt_bias_fill = value; return SONIC_OK;
 }
+// the parallel forced run (include/sonic_hip.h beside sonic_set_forced_ids).  forced_parallel: on the owner (its slots copy it) or on a slot alone;
+// refused while the handle has work in hand, as the options above.  forced_fanout = N: the run's R sequences are R / N audio requests with N candidates each
+static int opt_forced_parallel(sonic_engine* e, const char* key, int value) { TRY(gen_busy(e, key)); e->opt_forced_parallel = value ? 1 : 0; return SONIC_OK; }
+static int opt_forced_fanout(sonic_engine* e, const char* key, int value) {
+    if (value < 1 || value > e->Bm) return fail(e, SONIC_ERR_INVALID, "forced_fanout: %d is outside 1 .. %d (max_batch)", value, e->Bm);
+    e->opt_forced_fanout = value; return SONIC_OK;      // (only read by a parallel run as it starts)
+}
 // the two knobs that do device work
 static int opt_ktrace(sonic_engine* e, const char*, int value) {              // diagnostics: record in-kernel timestamps of decoder layer `value` (-1: off); sonic_debug_ktrace reads them
     HIPC(e, hipSetDevice(e->device));
@@ -109,6 +116,9 @@ static const OptRow OPTIONS[] = {
     {"sampling_fill_milli", APPLY(opt_sampling_fill_milli)},
     {"request_bias", APPLY(opt_request_bias)},
     {"request_bias_fill", APPLY(opt_request_bias_fill)},
+    {"forced_parallel", APPLY(opt_forced_parallel)},
+    {"forced_fanout", APPLY(opt_forced_fanout)},
+    {"score_chunk_rows", ENG(opt_score_chunk_rows), false, [](int v) { return v < 16 ? 16 : (v > 4096 ? 4096 : v); }},   // score rows per lm_head GEMM + row-kernel launch (the buffer follows at the next parallel run)
     {"ktrace", APPLY(opt_ktrace)},
     {"inject_dev_err", APPLY(opt_inject_dev_err)},
 };

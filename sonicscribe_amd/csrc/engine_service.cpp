@@ -84,6 +84,7 @@ extern "C" int sonic_service_begin(sonic_engine* e) {
     ENTER(e);
     if (!e->finalized) return fail(e, SONIC_ERR_INVALID, "weights not finalized");
     if (e->svc_on) return SONIC_OK;
+    if (e->opt_forced_parallel) return fail(e, SONIC_ERR_INVALID, "sonic_service_begin: option forced_parallel is on: a scoring handle does not decode continuously");
     if (!e->st_io) HIPC(e, hipStreamCreateWithFlags(&e->st_io, hipStreamNonBlocking));
     HIPC(e, stream_sync(e));
     hipLaunchKernelGGL(service_reset_kernel, dim3(1), dim3(64), 0, e->st, e->kv_len, e->tok_pos, e->n_new, e->finished, e->max_new_d, e->n_active);
@@ -122,6 +123,7 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
     std::lock(l1, l2);
     (void)hipGetLastError();
     HIPC(d, hipSetDevice(d->device)); g_opts = d->opts;
+    if (d->opt_forced_parallel || p->opt_forced_parallel) return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: option forced_parallel is on for the %s: a scoring handle takes no part in continuous decoding", d->opt_forced_parallel ? "destination" : "source");
     if (!d->svc_on) return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: the destination is not decoding continuously (sonic_service_begin)");
     if ((d->owner ? d->owner : d) != (p->owner ? p->owner : p)) return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: the handles do not share weights");
     if (d->Bm != p->Bm || d->max_ctx != p->max_ctx) return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: the handles differ in max_batch / max_ctx");
@@ -426,6 +428,7 @@ extern "C" int sonic_prefill(sonic_engine* e, const int32_t* req_win, int R, con
     if (!e) return SONIC_ERR_INVALID;
     ENTER_CONSUME(e);
     if (!prompt_ids || !prompt_off || !max_new) return SONIC_ERR_INVALID;
+    if (e->opt_forced_parallel) return fail(e, SONIC_ERR_INVALID, "sonic_prefill: option forced_parallel is on: a scoring handle runs whole batches (sonic_run_staged / sonic_transcribe_*)");
     TRY(run_to_first_token(e, req_win, R, prompt_ids, prompt_off, max_new, want_step_logits != 0));
     HIPC(e, stream_sync(e));
     HIPC(e, hipGetLastError());
@@ -437,6 +440,7 @@ extern "C" int sonic_prefill_enqueue(sonic_engine* e, const int32_t* req_win, in
     if (!e) return SONIC_ERR_INVALID;
     ENTER_CONSUME(e);
     if (!prompt_ids || !prompt_off || !max_new) return SONIC_ERR_INVALID;
+    if (e->opt_forced_parallel) return fail(e, SONIC_ERR_INVALID, "sonic_prefill_enqueue: option forced_parallel is on: a scoring handle runs whole batches (sonic_run_staged / sonic_transcribe_*)");
     TRY(run_to_first_token(e, req_win, R, prompt_ids, prompt_off, max_new, false));
     HIPC(e, hipGetLastError());
     return SONIC_OK;
@@ -530,13 +534,14 @@ extern "C" int sonic_set_forced_ids(sonic_engine* e, const int32_t* ids, int R, 
     ENTER(e);
     HIPC(e, stream_sync(e));
     if (e->force_d) { (void)hipFree(e->force_d); e->force_d = nullptr; e->force_ld = e->force_R = 0; }
+    e->force_h.clear();
     if (!ids) return SONIC_OK;
     if (R < 1 || R > e->Bm || ld < 1) return fail(e, SONIC_ERR_INVALID, "forced ids: bad shape [%d][%d]", R, ld);
     for (long i = 0; i < (long)R * ld; ++i)
         if (ids[i] < 0 || ids[i] >= e->d.vocab) return fail(e, SONIC_ERR_INVALID, "forced id %d out of vocabulary", ids[i]);
     HIPC(e, hipMalloc((void**)&e->force_d, (size_t)R * ld * 4));
     HIPC(e, h2d(e, e->force_d, ids, (size_t)R * ld * 4));
-    e->force_R = R; e->force_ld = ld;
+    e->force_R = R; e->force_ld = ld; e->force_h.assign(ids, ids + (size_t)R * ld);
     return SONIC_OK;
 }
 

@@ -429,16 +429,17 @@ void decode_step_i8(sonic_engine* e, int R, bool dump) {
     launch_greedy(greedy_args(e, R, dump), e->st);
 }
 
+// fan (the parallel forced run's forced_fanout; 1 otherwise): sequence r takes its audio rows from audio request r / fan - req_win then has R / fan + 1 entries
 static int plan_requests(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off,
-                         const int32_t* max_new, HostPlan& hp) {
+                         const int32_t* max_new, HostPlan& hp, int fan = 1) {
     const sonic_dims& d = e->d;
-    const int W = e->W;
+    const int W = e->W, A = R / fan;
     if (R < 1 || R > e->Bm) return fail(e, SONIC_ERR_INVALID, "request count %d out of range 1..%d", R, e->Bm);
-    if (!req_win && R != W) return fail(e, SONIC_ERR_INVALID, "R (%d) must equal staged windows (%d) when req_win is NULL", R, W);
-    if (req_win && (req_win[0] != 0 || req_win[R] != W)) return fail(e, SONIC_ERR_INVALID, "req_win must cover exactly the staged windows");
+    if (!req_win && A != W) return fail(e, SONIC_ERR_INVALID, "R (%d) must equal staged windows (%d) when req_win is NULL", A, W);
+    if (req_win && (req_win[0] != 0 || req_win[A] != W)) return fail(e, SONIC_ERR_INVALID, "req_win must cover exactly the staged windows");
     hp.q_off.resize(R); hp.q_len.resize(R); hp.last_row.resize(R); hp.max_new.resize(R);
     for (int r = 0; r < R; ++r) {
-        const int w0 = req_win ? req_win[r] : r, w1 = req_win ? req_win[r + 1] : r + 1;
+        const int w0 = req_win ? req_win[r / fan] : r / fan, w1 = req_win ? req_win[r / fan + 1] : r / fan + 1;
         if (w1 <= w0) return fail(e, SONIC_ERR_INVALID, "request %d has no audio window", r);
         std::vector<int> rows;  // audio rows of this request in order
         for (int w = w0; w < w1; ++w) {
@@ -506,7 +507,8 @@ int reset_row_state(sonic_engine* e, int R, int n_tok) {
     return samp_upload(e, R);                                                                                                       // every request's (temperature, seed), or zeros: greedy
 }
 
-static int run_prefill(sonic_engine* e, int R, const HostPlan& hp) {
+// head = false (the parallel forced run): the decoder layers only - its score rows are normalised and multiplied by run_forced_parallel
+static int run_prefill(sonic_engine* e, int R, const HostPlan& hp, bool head = true) {
     const sonic_dims& d = e->d;
     const int D = d.dec_d, M = hp.n_tok, dt = e->dt;
     const QGroup grp{e->tok_seq, 1, R};        // one reference call = the prompt rows of one request
@@ -541,6 +543,7 @@ static int run_prefill(sonic_engine* e, int R, const HostPlan& hp) {
         lin(EPI_BIAS_RESID, e->dact, d.dec_ff, L.wdown, L.wdown_t, 0, L.qdown, e->dx, D, D, d.dec_ff, e->dx, D, false);
         if (e->taps_on) HIPC(e, hipMemcpyAsync(e->taps + (size_t)(l + 1) * e->tok_cap * D, e->dx, (size_t)M * D * 2, hipMemcpyDeviceToDevice, e->st));
     }
+    if (!head) return SONIC_OK;
     // logits only for the last prompt position of each request (logits_to_keep=1, generation/utils.py:2612-2616)
     launch_rmsnorm(e->dx, e->dec_nw, e->shn, R, D, d.dec_rms_eps, e->last_row, e->st, dt);
     skinny(e, e->shn, D, e->embed_t, e->lslab, R, d.vocab, D, nullptr);
@@ -701,18 +704,9 @@ int run_decode_steps(sonic_engine* e, int n_steps, int* done_out) {
     return SONIC_OK;
 }
 
-int run_all(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off,
-            const int32_t* max_new, bool want_logits) {
+// what every whole-batch run ends with: the stage times from the events and the decode loop's host figures
+static void fill_timings(sonic_engine* e, double host_enqueue_first, int steps_done) {
     const sonic_dims& d = e->d;
-    const auto t_host0 = std::chrono::steady_clock::now();
-    TRY(run_to_first_token(e, req_win, R, prompt_ids, prompt_off, max_new, want_logits));
-    const double host_enqueue_first = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
-    e->host_launch_ms = e->host_wait_ms = 0; e->host_launches = 0; e->run_starved = false;
-    int steps_done = 0;
-    TRY(run_decode_steps(e, e->max_steps - 1, &steps_done));
-    (void)hipEventRecord(e->ev[4], e->st);
-    HIPC(e, stream_sync(e));
-    HIPC(e, hipGetLastError());
     sonic_timings& t = e->tim;
     memset(&t, 0, sizeof t);
     (void)hipEventElapsedTime(&t.mel_ms, e->ev[0], e->ev[1]);
@@ -731,6 +725,157 @@ int run_all(sonic_engine* e, const int32_t* req_win, int R, const int32_t* promp
     t.decode_steps = steps_done;
     t.host_prefill_enqueue_ms = (float)host_enqueue_first; t.host_decode_launch_ms = (float)e->host_launch_ms; t.host_decode_wait_ms = (float)e->host_wait_ms;
     t.host_decode_launches = e->host_launches; t.decode_lookahead = e->lookahead; t.decode_launches_per_layer = e->step_launches_per_layer;
+}
+
+// The parallel forced run (option forced_parallel with forced ids set; include/sonic_hip.h beside sonic_set_forced_ids).  Under teacher forcing no
+// input depends on an output, so the run is ONE prefill: sequence r = prompt || forced[r][0 .. L_r - 1), L_r = 1 + the index of the first EOS id among its budget's
+// forced ids (HF's rule; the budget if there is none).  Token n of sequence r is scored by the hidden state at row q_off[r] + P - 1 + n: the S = sum L_r score rows are
+// normalised with the final norm into dhn (free behind the last layer), then, in chunks of score_chunk_rows, multiplied by the tied lm_head as one prefill-family
+// GEMM into score_logits and reduced by score_rows_kernel (score.hip), which also writes the forced ids to out_ids and, if asked, the rows to the step-logits dump.
+// No logits processor is applied.  forced_fanout = N: the R sequences are R / N audio requests (windows, log-mel, encoder, projector once each) with N candidates
+// each; the prefill's outlier groups stay per sequence.  The handle is left holding a finished batch.
+static int run_forced_parallel(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new, bool want_logits) {
+    const sonic_dims& d = e->d;
+    const auto t_host0 = std::chrono::steady_clock::now();
+    if (!e->finalized) return fail(e, SONIC_ERR_INVALID, "weights not finalized");
+    if (e->W < 1) return fail(e, SONIC_ERR_INVALID, "no PCM staged");
+    if (e->svc_on) return fail(e, SONIC_ERR_INVALID, "this handle is decoding continuously (sonic_service_begin): prefill on another slot and splice the rows in");
+    const int bias_R = e->bias.claim(), samp_R = e->samp.claim();      // consumed, as on every other exit
+    if (bias_R >= 0 || samp_R >= 0)
+        return fail(e, SONIC_ERR_INVALID, "forced_parallel: the parallel forced run applies no processors: the staged %s are refused (it scores the raw distribution; run with the option off to force step by step under them)",
+                    bias_R >= 0 ? "request bias tables (sonic_set_request_bias)" : "sampling values (sonic_set_request_sampling)");
+    const int N = e->opt_forced_fanout;
+    if (R < 1 || R > e->Bm) return fail(e, SONIC_ERR_INVALID, "request count %d out of range 1..%d", R, e->Bm);
+    if (R % N) return fail(e, SONIC_ERR_INVALID, "forced_fanout: %d sequences are not a multiple of the fan-out %d", R, N);
+    int max_steps = 0;
+    for (int r = 0; r < R; ++r) {
+        if (max_new[r] < 1) return fail(e, SONIC_ERR_INVALID, "max_new_tokens must be >= 1");
+        max_steps = std::max(max_steps, (int)max_new[r]);
+    }
+    if (e->force_R != R || e->force_ld < max_steps || e->force_h.size() != (size_t)e->force_R * e->force_ld)
+        return fail(e, SONIC_ERR_INVALID, "forced ids are [%d][%d] but the run has %d requests / %d steps", e->force_R, e->force_ld, R, max_steps);
+    // the longer sequences: prompt || forced[0 .. L - 1); their budget max_new - (L - 1) keeps plan_requests' context check at prompt + max_new
+    std::vector<int32_t> ids, left(R), L(R); std::vector<int64_t> off(R + 1, 0);
+    long asked = 0;
+    for (int r = 0; r < R; ++r) {
+        const int* f = e->force_h.data() + (size_t)r * e->force_ld;
+        int l = max_new[r];
+        for (int n = 0; n < max_new[r]; ++n) {
+            bool eos = false;
+            for (int k = 0; k < d.n_eos; ++k) eos = eos || f[n] == d.eos[k];
+            if (eos) { l = n + 1; break; }
+        }
+        for (int n = 0; n < l; ++n)
+            if (f[n] == d.audio_token_id) return fail(e, SONIC_ERR_INVALID, "forced_parallel: forced id %d of sequence %d is the audio placeholder id %d, which cannot be a target", n, r, d.audio_token_id);
+        const int64_t p0 = prompt_off[r], p1 = prompt_off[r + 1];
+        if (p1 - p0 < 1) return fail(e, SONIC_ERR_INVALID, "request %d has an empty prompt", r);
+        ids.insert(ids.end(), prompt_ids + p0, prompt_ids + p1);
+        ids.insert(ids.end(), f, f + l - 1);
+        off[r + 1] = (int64_t)ids.size(); L[r] = l; left[r] = max_new[r] - (l - 1);
+        asked += (p1 - p0) + l - 1;
+    }
+    if (asked > e->tok_cap) return fail(e, SONIC_ERR_INVALID, "forced_parallel: the run asks for %ld tokens (prompts and forced ids), %d fit one prefill (tok_cap)", asked, e->tok_cap);
+    HostPlan hp;
+    TRY(plan_requests(e, req_win, R, ids.data(), off.data(), left.data(), hp, N));
+    for (int r = 0; r < R; ++r) hp.max_new[r] = max_new[r];
+    hp.max_steps = max_steps;
+    if (max_steps > e->out_cap) return fail(e, SONIC_ERR_INVALID, "max_new_tokens too large");
+    if (e->wait_pending) { HIPC(e, hipStreamWaitEvent(e->st, e->wait_ev, 0)); e->wait_pending = false; }
+    TRY(score_alloc(e));
+    {   // staging buffer of this run (run_to_first_token)
+        const int i = e->plan_idx ^ 1;
+        if (e->plan_busy[i]) { HIPC(e, hipEventSynchronize(e->plan_ev[i])); e->plan_busy[i] = false; }
+        e->plan_idx = i; e->plan_h = e->plan_buf[i];
+    }
+    e->bias.take = false; e->samp.take = false;
+    e->R = R; e->max_steps = max_steps; e->last_maxnew = hp.max_new;
+    e->last_qlen.resize(R);
+    for (int r = 0; r < R; ++r) e->last_qlen[r] = (int)(prompt_off[r + 1] - prompt_off[r]);      // the PROMPT's length: fetch_locked expects kv_len = prompt + tokens - 1
+    if (want_logits) {
+        const size_t need_n = (size_t)max_steps * R * d.vocab;
+        if (need_n > e->dump_cap) {
+            if (e->dump) (void)hipFree(e->dump);
+            e->dump = nullptr; e->dump_cap = 0;
+            HIPC(e, hipMalloc((void**)&e->dump, need_n * 4));
+            e->dump_cap = need_n;
+        }
+        e->dump_steps = max_steps;
+    } else e->dump_steps = 0;
+    e->run_logits = want_logits;
+    // the score rows: hidden-state row | target | record index, S of each, then the rows' closing state (n_new | finished | tok_pos | n_active)
+    int S = 0;
+    for (int r = 0; r < R; ++r) S += L[r];
+    int* ph = e->score_plan_h;
+    int* st_h = ph + (size_t)3 * S;
+    memset(st_h, 0, (4 * 64) * 4);
+    for (int r = 0, s = 0; r < R; ++r) {
+        const int P = e->last_qlen[r];
+        const int* f = e->force_h.data() + (size_t)r * e->force_ld;
+        for (int n = 0; n < L[r]; ++n, ++s) { ph[s] = hp.q_off[r] + P - 1 + n; ph[S + s] = f[n]; ph[2 * S + s] = r * e->out_cap + n; }
+        st_h[r] = L[r]; st_h[64 + r] = 1; st_h[128 + r] = P + L[r] - 2;
+    }
+    for (int r = R; r < 64; ++r) st_h[64 + r] = 0;
+
+    (void)hipEventRecord(e->ev[0], e->st);
+    TRY(run_mel(e, e->W, e->f32));
+    (void)hipEventRecord(e->ev[1], e->st);
+    const int A = R / N;
+    if (e->i8) {   // window -> audio request map (run_to_first_token): the encoder's outlier groups are the audio requests, not their candidates
+        int* h = e->plan_h + e->plan_cap - 64;
+        memset(h, 0, 64 * 4);
+        for (int a = 0; a < A; ++a) {
+            const int w0 = req_win ? req_win[a] : a, w1 = req_win ? req_win[a + 1] : a + 1;
+            for (int w = w0; w < w1 && w < 64; ++w) h[w] = a;
+        }
+        HIPC(e, hipMemcpyAsync(e->win_req, h, 64 * 4, hipMemcpyHostToDevice, e->st));
+    }
+    TRY(e->f32 ? f32_run_encoder(e, e->W, nullptr, nullptr) : run_encoder(e, e->W, nullptr, nullptr, A));
+    (void)hipEventRecord(e->ev[2], e->st);
+    TRY(e->f32 ? f32_run_prefill(e, R, hp, false) : run_prefill(e, R, hp, false));
+    HIPC(e, hipMemcpyAsync(e->score_plan_d, ph, (size_t)3 * S * 4, hipMemcpyHostToDevice, e->st));
+    if (e->f32) f32_score_norm(e, e->score_plan_d, S);
+    else launch_rmsnorm(e->dx, e->dec_nw, e->dhn, S, d.dec_d, d.dec_rms_eps, e->score_plan_d, e->st, e->dt);
+    ScoreArgs sa{};
+    sa.logits = e->score_logits; sa.ld = d.vocab; sa.V = d.vocab; sa.dt = e->f32 ? DT_F32 : e->dt;
+    sa.out_ids = e->out_ids; sa.out_lp = (e->opt_token_logprobs && e->out_lp) ? e->out_lp : nullptr; sa.topk = sa.out_lp ? e->opt_top_logprobs : 0;
+    sa.dump = want_logits ? e->dump : nullptr; sa.out_ld = e->out_cap; sa.R = R;
+    const int chunk = std::min(e->opt_score_chunk_rows, e->score_rows_cap);
+    for (int c0 = 0; c0 < S; c0 += chunk) {
+        const int n = std::min(chunk, S - c0);
+        if (e->f32) f32_score_logits(e, c0, n, (float*)e->score_logits);
+        else gemm(e, EPI_BIAS, e->dhn + (size_t)c0 * d.dec_d, d.dec_d, e->embed_t, nullptr, (bf16_t*)e->score_logits, d.vocab, n, d.vocab, d.dec_d, nullptr, 0, 1);   // embed_t: launch_tile_weights' tiling, the one GemmArgs.w_tiled reads
+        sa.n = n; sa.target = e->score_plan_d + S + c0; sa.rec = e->score_plan_d + 2 * S + c0;
+        launch_score_rows(sa, e->st);
+    }
+    // the rows' state as a finished batch: n_new = L, finished, tok_pos = kv_len - 1 (kv_len = prompt + L - 1 is what the plan uploaded), nothing running
+    HIPC(e, hipMemcpyAsync(e->n_new, st_h, 64 * 4, hipMemcpyHostToDevice, e->st));
+    HIPC(e, hipMemcpyAsync(e->finished, st_h + 64, 64 * 4, hipMemcpyHostToDevice, e->st));
+    HIPC(e, hipMemcpyAsync(e->tok_pos, st_h + 128, (size_t)R * 4, hipMemcpyHostToDevice, e->st));
+    HIPC(e, hipMemcpyAsync(e->n_active, st_h + 192, 4, hipMemcpyHostToDevice, e->st));
+    (void)hipEventRecord(e->ev[3], e->st);
+    (void)hipEventRecord(e->ev[4], e->st);
+    e->steps_run = max_steps - 1; e->greedy_calls = max_steps; e->spliced = 0;      // a finished batch: sonic_decode_step has nothing left to run
+    const double host_enqueue_first = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
+    e->host_launch_ms = e->host_wait_ms = 0; e->host_launches = 0; e->run_starved = false;
+    HIPC(e, stream_sync(e));
+    HIPC(e, hipGetLastError());
+    fill_timings(e, host_enqueue_first, 0);
+    return SONIC_OK;
+}
+
+int run_all(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off,
+            const int32_t* max_new, bool want_logits) {
+    if (e->opt_forced_parallel && e->force_d) return run_forced_parallel(e, req_win, R, prompt_ids, prompt_off, max_new, want_logits);
+    const auto t_host0 = std::chrono::steady_clock::now();
+    TRY(run_to_first_token(e, req_win, R, prompt_ids, prompt_off, max_new, want_logits));
+    const double host_enqueue_first = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count();
+    e->host_launch_ms = e->host_wait_ms = 0; e->host_launches = 0; e->run_starved = false;
+    int steps_done = 0;
+    TRY(run_decode_steps(e, e->max_steps - 1, &steps_done));
+    (void)hipEventRecord(e->ev[4], e->st);
+    HIPC(e, stream_sync(e));
+    HIPC(e, hipGetLastError());
+    fill_timings(e, host_enqueue_first, steps_done);
     if (!e->run_starved && e->lookahead > 1) e->lookahead -= 1;       // a batch whose queue never ran dry: one chunk less ahead next time
     return SONIC_OK;
 }

@@ -7,6 +7,7 @@
 #include "kernels.h"
 
 #include "int8_util.h"
+#include "topk.h"
 
 // ---------------------------------------------------------------- argmax + greedy controller (generation/utils.py:2894-2936)
 // LP (option token_logprobs): the block also returns log_softmax(l)[tok] of the token it emits.  Every thread keeps the sum lp_s of
@@ -45,31 +46,7 @@
 // unique), so the result does not depend on how the reduction is arranged.  Lanes 0 .. K - 1 of wave 1 write the record [lp | K alternative lps | K ids as fp32]
 // at out_lp[(b * out_ld + n) * (1 + 2K)]; places beyond the finite scores hold (-inf, -1).  Forcing and sampling change the emitted token, never the
 // alternatives; a finished row writes nothing.  TOPK = false is the kernel as it was: everything that belongs to the lists sits behind `if constexpr (TOPK)`.
-#define TK_NONE 0x7fffffff
-__device__ __forceinline__ void tk_insert(float (&tv)[8], int (&ti)[8], float r, int id) {      // the caller has seen r > tv[7]
-    tv[7] = r; ti[7] = id;
-#pragma unroll
-    for (int k = 7; k > 0; --k)
-        if (tv[k] > tv[k - 1]) { const float fv = tv[k]; tv[k] = tv[k - 1]; tv[k - 1] = fv; const int fi = ti[k]; ti[k] = ti[k - 1]; ti[k - 1] = fi; }      // strict: equal values keep their order
-}
-// K rounds over the 64 lanes' sorted lists: lane r leaves with the r-th best pair of all of them (lanes >= K, and places without a finite score: (-inf, TK_NONE))
-__device__ __forceinline__ void tk_merge(float (&tv)[8], int (&ti)[8], int K, int lane, float& mv, int& mi) {
-    mv = -INFINITY; mi = TK_NONE;
-    for (int r = 0; r < K; ++r) {
-        float wv = tv[0]; int wi = ti[0];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(wv, o, 64); const int oi = __shfl_xor(wi, o, 64);
-            if (ov > wv || (ov == wv && oi < wi)) { wv = ov; wi = oi; }
-        }
-        if (lane == r) { mv = wv; mi = wi; }
-        if (wi != TK_NONE && ti[0] == wi) {          // the winner's lane pops its head
-#pragma unroll
-            for (int k = 0; k < 7; ++k) { tv[k] = tv[k + 1]; ti[k] = ti[k + 1]; }
-            tv[7] = -INFINITY; ti[7] = TK_NONE;
-        }
-    }
-}
+// tk_insert / tk_merge (the lists and their wave merge) and lp_exp live in topk.h: score.hip shares them
 extern __shared__ unsigned g_bits[];
 __device__ __forceinline__ float guard_score(float r, unsigned seen, unsigned banned, float p) {
     if (seen & 1u) r = r < 0.f ? r * p : __fdiv_rn(r, p);
@@ -83,7 +60,6 @@ __device__ __forceinline__ float bias_of(const int* ids, const float* sums, int 
     for (int k = 0; k < n; ++k) if (ids[k] == id) b = sums[k];      // (ids are unique: one group per last id)
     return b;
 }
-__device__ __forceinline__ float lp_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 // Philox4x32-10 (Salmon et al., SC'11): ten rounds, the key bumped between them
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned* out) {
 #pragma unroll

@@ -139,6 +139,22 @@ void launch_greedy(const GreedyArgs& a, hipStream_t s);
 size_t greedy_guard_lds(int V, bool bias = false);     // dynamic LDS of the GUARD instantiations: two bitmaps over the vocabulary; with the request bias a third one and the matched list
 void launch_hist_prompt(const int* src, const int* tok_seq, const int* tok_pos, int n_tok, int audio_id, int* hist, int hist_ld, hipStream_t s);
 
+// The parallel forced run's row kernel (score.hip: score_rows_kernel<T, TOPK>, option forced_parallel): block i takes row i of `logits` - the lm_head's
+// output for one score row, in the activation type - and writes the record of the forced token target[i]: log_softmax(row)[target] and, with topk = K in 1 .. 8,
+// the K best ids of the row by (value descending, id ascending) with their log-probabilities, in the layout GreedyArgs.out_lp has.  rec[i] = r * out_ld + n names
+// the record (sequence r, token n): out_ids[rec] = target, out_lp[rec * (1 + 2K) ..], dump[(n * R + r) * V ..] = the row as fp32 (each optional).  No processor
+// is applied: the row is the raw model distribution at temperature 1
+struct ScoreArgs {
+    const void* logits; long ld;     // [n][ld] elements of the type `dt` names
+    int V, n, dt;                    // DT_BF16 / DT_F16 / DT_F32
+    const int* target; const int* rec;
+    int* out_ids; float* out_lp; int topk;
+    float* dump; int out_ld, R;
+};
+void launch_score_rows(const ScoreArgs& a, hipStream_t s);
+// test hook route: the lm_head's fp32 slabs [ksplit][mpad][V] summed in greedy_kernel's order (v + w, then ks = 2 ...) and rounded to the element type: out [B][V]
+void launch_score_slab_rows(const float* slabs, int ksplit, int mpad, int V, int B, void* out, int dt, hipStream_t s);
+
 struct LogmelConst {
     const float* win;      // [400]
     const float* cos_t;    // [400]

@@ -330,8 +330,14 @@ class Engine(HooksMixin):
         s.top_logprobs = int(getattr(root, "top_logprobs", 0)) if s.token_logprobs else 0
         s.request_bias = bool(getattr(root, "request_bias", False))
         s.sampling = bool(getattr(root, "sampling", False))
+        s.forced_parallel = bool(getattr(root, "forced_parallel", False))
         root._slots.append(s)
         return s
+
+    @property
+    def tok_cap(self) -> int:
+        """tokens one prefill of this handle holds (the library's tok_cap: max_batch x min(max_ctx, audio rows of a window + 256))"""
+        return self.max_batch * min(self.max_ctx, self.dims.max_audio_tokens + 256)
 
     def slot_count(self) -> int:
         return int(self.lib.sonic_slot_count(self.h))
@@ -519,6 +525,29 @@ class Engine(HooksMixin):
         res = [out[r, : out_len[r]].copy() for r in range(R)]
         return (res, logits, self._fetch_logprobs(out_len, out_ld)) if want_logprobs else (res, logits)
 
+    def score_batch(self, segments: Sequence[Any], prompts: Sequence[Sequence[int]], targets, req_win: Optional[Sequence[int]] = None, fanout: int = 1,
+                    want_logits: bool = False):
+        """Score given continuations in ONE prefill pass (the parallel forced run; needs option forced_parallel on this handle).  targets: one id
+        sequence per prompt, or an int array [R][ld] padded with any valid id beyond a sequence's own length when all share a length - sequence r is scored up to
+        and including its first EOS id (HF's rule).  fanout = N: the R sequences are R / N audio requests with N candidates each; `segments` / `req_win` then
+        describe the R / N audio requests, which go through log-mel, encoder and projector once.  No logits processor is applied: the log-probabilities are those
+        of the raw model distribution at temperature 1.  Returns what transcribe_batch(..., want_logprobs=True) returns: (ids list, logits [ld][R][V] or None,
+        per sequence its float32 log-probabilities - with option top_logprobs a TokenScores); the log-probabilities need option token_logprobs (None without)."""
+        if not getattr(self, "forced_parallel", False):
+            raise SonicError("score_batch needs option forced_parallel on this handle (set_option('forced_parallel', 1))")
+        from .scoring import pack_targets
+        forced, lens = pack_targets(targets, self.dims.eos_ids, pad_id=0)
+        if len(forced) != len(prompts):
+            raise ValueError(f"{len(prompts)} prompts but {len(forced)} target sequences")
+        self.set_option("forced_fanout", int(fanout))
+        self.set_forced_ids(forced)
+        try:
+            want_lp = bool(getattr(self, "token_logprobs", False))
+            out = self.transcribe_batch(segments, prompts, [int(n) for n in lens], req_win=req_win, want_logits=want_logits, want_logprobs=want_lp)
+        finally:
+            self.set_forced_ids(None)
+        return out if want_lp else (out[0], out[1], None)
+
     def _fetch_logprobs(self, out_len, out_ld: int) -> list:
         """sonic_fetch_logprobs for the batch whose token counts are out_len: one float32 array per request (entries beyond a row's count are never written);
         with option top_logprobs one TokenScores per request (unpack_logprobs)"""
@@ -668,6 +697,8 @@ class Engine(HooksMixin):
             self.top_logprobs = int(value)           # (likewise: the width of every log-probability record this handle returns)
         if key == "token_logprobs":
             self.token_logprobs = bool(value)        # (a slot created from now on copies it, in the library and here)
+        if key == "forced_parallel":
+            self.forced_parallel = bool(value)       # (likewise; it may also be set on a slot alone)
 
     def set_forced_ids(self, ids):
         """ids: [R][ld] int array (token n of request r) or None to clear; see sonic_set_forced_ids."""
