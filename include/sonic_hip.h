@@ -461,7 +461,28 @@ SONIC_API int sonic_stage_mixed(sonic_engine* e, const int16_t* host_pcm, const 
  *   words per score row) come with its first parallel run, are counted by sonic_memory_info and go with the handle.
  *   test hook: on such a handle sonic_test_greedy_lp sends its rows to the row kernel instead - the slabs are summed over ksplit in the greedy kernel's order and
  *   rounded to the element type, those values are the logits row the kernel reads and logits_out returns them; force_ids is required, tok_out holds the forced ids,
- *   lp_out B records of 1 + 2K floats; B may exceed 64 (up to 4096), mpad stays the slab row stride. */
+ *   lp_out B records of 1 + 2K floats; B may exceed 64 (up to 4096), mpad stays the slab row stride.
+ *
+ * Word timestamps on the parallel forced run (options "forced_align", "align_head").  While option "forced_align" is 1 a parallel forced run also
+ * says WHEN every scored token was spoken: at the selected decoder heads the attention of the score rows onto the audio placeholder keys (softmax over the audio run
+ * alone), normalised over the tokens (std = 0: 0), median-filtered (width 7, reflect) and averaged over the heads, then dynamic time warping - openai-whisper's
+ * find_alignment, the decoder's self-attention onto the audio run in the place of Whisper's cross-attention.  t_n is the index into sequence r's audio run at which
+ * token n starts; one audio token is 1280 samples = 80 ms, and a request of several windows carries its windows' kept rows one after the other.
+ *   results: every log-probability record of such a run is W = 1 + 2K + 1 floats - the record above, bit for bit, and t_n as the last float (an index: exact).
+ *   sonic_fetch_logprobs' out_ld counts floats and must hold n_new[r] * W of them ("out_ld too small" otherwise).  A run without forced ids on the same handle (a
+ *   greedy run) returns records of 1 + 2K floats as ever.  The records need option token_logprobs.
+ *   "forced_align" = 1 is accepted only on a handle with "forced_parallel" = 1 (which can then not be switched off), refused on the fp32 kind and while the handle has
+ *   work in hand; slots copy it and the heads.  With it 0 the engine launches exactly what it did.
+ *   "align_head" = l * 256 + h adds head h of decoder layer l to the selection (at most 256; out of range or a full list: SONIC_ERR_INVALID; a head already in
+ *   the list is no error), -1 returns to the default: every head of the last ceil(dec_layers / 2) layers - Whisper's rule for a model without alignment heads.
+ *   Heads are added layer by layer, ascending within a layer, without atomics: the same bits on every run, whatever else the run holds.
+ *   refusals at the run (SONIC_ERR_INVALID by name): a sequence whose audio placeholders are not ONE contiguous run, or that has none; more than 4000 targets.
+ *   buffers (probabilities of one layer's heads, the matrix, the DTW's trace, t_n, the plan) come with the first align run sized to it, grow with a later run that
+ *   needs more, are counted by sonic_memory_info and go with the handle.
+ *   sonic_debug_read: "align_probs" [heads of the last selected layer][S][A_max] and "align_matrix" [S][A_max] of the last run, fp32 on every kind (S = the run's
+ *   score rows, sequence after sequence; A_max = its longest audio run).
+ *   test hook: on such a handle sonic_test_attention(q [B][Tq][Hq * 128], k [B][Tk][Hkv * 128], v = NULL, out, B, Tq, Tk, Hq, Hkv, hd = 128, causal = 0) runs the
+ *   three kernels on caller data - all Hq heads, the audio run being all Tk keys - and out is [B][Tq][Tk + 1]: the matrix's row, then t_n. */
 SONIC_API int sonic_set_forced_ids(sonic_engine* e, const int32_t* ids, int R, int ld);
 SONIC_API int sonic_get_timings(sonic_engine* e, sonic_timings* out);
 SONIC_API int sonic_synchronize(sonic_engine* e);
@@ -545,7 +566,7 @@ SONIC_API int sonic_bench_gemm(sonic_engine* e, int M, int N, int K, int epi, in
 /* times the decode-step skinny GEMM (variant: 0 LDS-DMA nt, 1 LDS-DMA default policy, 2 registers nt, 3 registers plain, 9 pure-read floor) */
 SONIC_API int sonic_bench_skinny(sonic_engine* e, int M, int N, int K, int variant, int iters, float* us_per_launch);
 /* debug read-back of an internal bf16 activation buffer as fp32 ("prefill_tap" with index = 0 (embeddings) .. dec_layers,
- * "pe", "dx", "dqkv", "dq", "datt", "dact", "enc_x"); tests / diagnostics only */
+ * "pe", "dx", "dqkv", "dq", "datt", "dact", "enc_x"; "align_probs", "align_matrix": fp32 buffers of the last align run, see sonic_set_forced_ids); tests / diagnostics only */
 SONIC_API int sonic_debug_read(sonic_engine* e, const char* name, int index, float* out, int64_t n);
 /* diagnostics: in-kernel timestamps (100 MHz device wall clock) of the decode kernels of one decoder layer, recorded while the option
  * "ktrace" = layer index is set: out[slot][block < 512][8 points], slots 0 qkv, 1 attention, 2 o_proj, 3 gate/up, 4 down */
@@ -558,7 +579,8 @@ SONIC_API int sonic_debug_ktrace(sonic_engine* e, int64_t* out, int64_t n);
  * "decode_attn_occ2" (experiments that lost: profiles/round6_*), "f32_synth_bf16" (SONIC_MODE_F32: sonic_load_synthetic writes the bf16-rounded values),
  * "inject_dev_err" (tests: sets / clears the device error word); "token_logprobs" (not an experiment: per-token log-probabilities, see sonic_fetch_logprobs);
  * "top_logprobs" (not an experiment either: the K best alternatives of every step in the same records, see sonic_fetch_logprobs);
- * "forced_parallel", "forced_fanout", "score_chunk_rows" (not experiments: forced runs as one prefill pass - scoring given transcripts - see sonic_set_forced_ids) */
+ * "forced_parallel", "forced_fanout", "score_chunk_rows" (not experiments: forced runs as one prefill pass - scoring given transcripts - see sonic_set_forced_ids);
+ * "forced_align", "align_head" (not experiments: word timestamps on that pass, see sonic_set_forced_ids) */
 SONIC_API int sonic_set_option(sonic_engine* e, const char* key, int value);
 
 /* ---- Silero VAD network (silero-vad 5.x / 6.x, 16 kHz branch; csrc/vad.hip, layer table in sonicscribe_amd/vad_net.py) ----

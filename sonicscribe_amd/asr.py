@@ -90,11 +90,13 @@ class Transcription:
     `top_token_ids` [n, K] int32 and `top_logprobs` [n, K] float32 (ASRModel(top_logprobs=K); [n, 0] without): at every step the K best ids by (score
     descending, id ascending) with their log-probabilities - OpenAI's top_logprobs; places beyond the ids with a finite score hold (-1, -inf).  They are what
     the model scored, whatever token was emitted: on a greedy request column 0 is the token itself."""
-    __slots__ = ("text", "token_ids", "token_logprobs", "avg_logprob", "temperature", "compression_ratio", "attempts", "top_token_ids", "top_logprobs")
+    __slots__ = ("text", "token_ids", "token_logprobs", "avg_logprob", "temperature", "compression_ratio", "attempts", "top_token_ids", "top_logprobs",
+                 "words", "token_start", "token_end")      # word_timestamps=True (ASRModel(timestamps=True); DESIGN.md 6.9): timestamps.Word list and the tokens' times (EOS dropped); None without
 
     def __init__(self, text: str, token_ids, token_logprobs, temperature: float = 0.0):
         from .fallback import compression_ratio
         self.text = text
+        self.words = self.token_start = self.token_end = None
         self.temperature, self.compression_ratio, self.attempts = float(temperature), compression_ratio(text), 1
         self.token_ids = np.asarray(token_ids, np.int32)
         top_lp = top_ids = None
@@ -214,11 +216,13 @@ class AudioStream:
 
     def submit_samples(self, first: int, n: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None, detailed: bool = False,
                        sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature: Optional[float] = None,
-                       seed: Optional[int] = None) -> "Future[str]":
+                       seed: Optional[int] = None, word_timestamps: bool = False) -> "Future[str]":
         """Transcribe ring samples [first, first + n) (the >30 s split of connection_manager.py:206-214 cuts at byte offsets, not chunks).
         detailed (a model built with token_logprobs=True): the future gives a Transcription instead of the text.  temperature / seed (a model built with
         sampling=True): one attempt at that temperature - a float only, stream decodes take no fallback ladder."""
         m = self.model
+        if word_timestamps:
+            raise ValueError("word_timestamps is not supported on submit() / transcribe_async() / stream decodes: align a finished transcript with ASRModel.align(), or use transcribe(..., word_timestamps=True)")
         m._check_detailed(detailed)
         bias = m._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost)
         samp = m._request_sampling(temperature, seed, ladder_ok=False)
@@ -229,10 +233,10 @@ class AudioStream:
 
     def submit_chunks(self, start_chunk_id: int, end_chunk_id: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None,
                       detailed: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
-                      temperature: Optional[float] = None, seed: Optional[int] = None) -> "Future[str]":
+                      temperature: Optional[float] = None, seed: Optional[int] = None, word_timestamps: bool = False) -> "Future[str]":
         """Transcribe chunks start..end inclusive (audio_manager.py:76-79 get_chunks_by_range + :115-123 concatenation)."""
         first, n = self.chunk_range_samples(start_chunk_id, end_chunk_id)
-        return self.submit_samples(first, n, max_new_tokens, hotwords, detailed, sequence_bias, bad_words_ids, hotword_boost, temperature, seed)
+        return self.submit_samples(first, n, max_new_tokens, hotwords, detailed, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, word_timestamps)
 
     async def transcribe_chunks(self, start_chunk_id: int, end_chunk_id: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None) -> str:
         return await asyncio.wrap_future(self.submit_chunks(start_chunk_id, end_chunk_id, max_new_tokens, hotwords))
@@ -250,7 +254,7 @@ class ASRModel:
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None,
                  request_bias: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: float = 0.0,
                  sampling: bool = False, temperature=0.0, seed: int = 0, compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
-                 scoring: bool = False,
+                 scoring: bool = False, timestamps: bool = False, alignment_heads=None,
                  _dims: Optional[ModelDims] = None,
                  _synthetic_seed: Optional[int] = None, _allow_synthetic_prompt: bool = False, _options: Optional[Dict[str, int]] = None,
                  _engine_mode: Optional[int] = None):
@@ -261,7 +265,9 @@ class ASRModel:
         bulk=True): every `detailed=True` result also carries the K best ids of every step with their log-probabilities.  `sampling` (needs token_logprobs=True): requests may be decoded at a
         temperature with a seed, or down a fallback ladder of temperatures (fallback.py); `temperature` (a float: one attempt; a sequence: the
         ladder), `seed` and the two thresholds of the ladder here are the defaults of every call.  `scoring` (needs token_logprobs=True): score() / score_batch() give the log-probability of transcripts the caller
-        brings, in one prefill pass per run on a handle of their own per replica; off, no such handle exists.  The arguments with a leading underscore are not part of the
+        brings, in one prefill pass per run on a handle of their own per replica; off, no such handle exists.  `timestamps` (needs scoring=True): align() and
+        word_timestamps=True give the time at which every token and word was spoken, from the decoder's attention onto the audio on that scoring handle (DESIGN.md 6.9);
+        `alignment_heads`: the [layer, head] pairs to read (None: the `alignment_heads` entry of the checkpoint's generation_config.json, else every head of the last half of the layers).  The arguments with a leading underscore are not part of the
         supported surface: they exist for the test-suite and the benchmark and may change without notice.  `_engine_mode` in particular (an engine.MODE_*
         value in place of the one `mode` selects) is unsupported outside the tests: MODE_F32 has no slots, so it needs slots=1, continuous=False."""
         if mode not in ["native", "int8"]:
@@ -282,6 +288,9 @@ class ASRModel:
         self.scoring = bool(scoring)
         if self.scoring and not token_logprobs:
             raise ValueError("scoring=True needs token_logprobs=True: a score is the candidates' token log-probabilities (ASRModel(..., token_logprobs=True, scoring=True))")
+        from . import timestamps as timestamps_
+        self.timestamps = bool(timestamps)
+        self.alignment_heads = timestamps_.check_timestamps(self.timestamps, self.scoring, alignment_heads, *((_dims.dec_layers, _dims.dec_heads) if _dims is not None else ()))
         dev = str(device)
         if dev.startswith("cpu"):
             raise RuntimeError("sonicscribe_amd runs on MI355X only: DEVICE=cpu has no HIP path (no CPU fallback by design)")
@@ -387,6 +396,15 @@ class ASRModel:
                 s_ = eng.slot()
                 s_.set_option("forced_parallel", 1)
                 self._score_engines.append(s_)
+        if self.timestamps:          # the scoring handles also align: their parallel runs return t_n per token
+            heads = self.alignment_heads
+            if heads is None and _synthetic_seed is None:
+                heads = timestamps_.check_timestamps(True, True, timestamps_.load_alignment_heads(str(checkpoint_dir)))
+            self.alignment_heads = timestamps_.check_timestamps(True, True, heads, self.dims.dec_layers, self.dims.dec_heads)
+            for s_ in self._score_engines:
+                s_.set_option("forced_align", 1)
+                for l, h in (self.alignment_heads or []):
+                    s_.set_option("align_head", l * 256 + h)
         self._score_locks = [threading.Lock() for _ in self._score_engines]
         self._score_next = 0
         self._slot_engines = [[eng.slot() for _ in range(self.slots - 1)] for eng in self.models]     # same weights, further batches in flight
@@ -500,7 +518,7 @@ class ASRModel:
 
     def submit(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None,
                session: Optional[str] = None, detailed: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
-               temperature=None, seed: Optional[int] = None) -> "Future[str]":
+               temperature=None, seed: Optional[int] = None, word_timestamps: bool = False) -> "Future[str]":
         """Non-blocking form of transcribe(): queues the request on a replica and returns a Future of the transcript.  `session`
         (e.g. the WebSocket client id) keeps a session's decodes on one GPU.  detailed (a model built with token_logprobs=True): the future
         gives a Transcription - text, token_ids, token_logprobs, avg_logprob - instead of the text.  sequence_bias / bad_words_ids / hotword_boost (a model
@@ -509,6 +527,8 @@ class ASRModel:
         thread never waits for one (_dispatch)."""
         if not hasattr(self, "model"):
             raise RuntimeError("ASR model has been released")
+        if word_timestamps:
+            raise ValueError("word_timestamps is not supported on submit() / transcribe_async() / stream decodes: align a finished transcript with ASRModel.align(), or use transcribe(..., word_timestamps=True)")
         self._check_detailed(detailed)
         bias = self._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost)
         samp = self._request_sampling(temperature, seed)
@@ -528,22 +548,31 @@ class ASRModel:
 
     async def transcribe_async(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128,
                                hotwords: Optional[List[str]] = None, session: Optional[str] = None, detailed: bool = False,
-                               sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None, seed: Optional[int] = None) -> str:
+                               sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None, seed: Optional[int] = None,
+                               word_timestamps: bool = False) -> str:
         """Awaitable transcribe() for the asyncio callers (connection_manager.py:127-245): the event loop is not blocked while the
         device works, so all sessions' partial and final decodes can be in flight (and batched) together."""
-        return await asyncio.wrap_future(self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, session, detailed, sequence_bias, bad_words_ids, hotword_boost, temperature, seed))
+        return await asyncio.wrap_future(self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, session, detailed, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, word_timestamps))
 
     def transcribe(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128,
                    hotwords: Optional[List[str]] = None, return_debug_info: bool = False,
-                   sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None, seed: Optional[int] = None) -> Union[str, Dict[str, Any]]:
+                   sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None, seed: Optional[int] = None,
+                   word_timestamps: bool = False) -> Union[str, Dict[str, Any]]:
+        """word_timestamps (a model built with timestamps=True): the request is decoded as always, then its tokens are aligned on the scoring
+        handle - the audio is encoded a second time there.  With return_debug_info the dictionary gains `words` (word, start, end, probability), `token_start`
+        and `token_end` (seconds, EOS dropped); without, the call returns the Transcription, which carries the same members."""
         if not hasattr(self, "model"):
             raise RuntimeError("ASR model has been released")
+        if word_timestamps:
+            self._check_timestamps()
         t0 = time.time()
         try:
-            want = bool(return_debug_info and getattr(self, "token_logprobs", False))
+            want = bool((return_debug_info or word_timestamps) and getattr(self, "token_logprobs", False))
             res = self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, detailed=want, sequence_bias=sequence_bias, bad_words_ids=bad_words_ids,
                               hotword_boost=hotword_boost, temperature=temperature, seed=seed).result()
             det, transcript = (res, res.text) if want else (None, res)
+            if word_timestamps:
+                self._attach_alignment([audio_tensor], [det], sampling_rate, hotwords)
             elapsed = time.time() - t0
             if return_debug_info:
                 n = audio_tensor.shape[-1] if hasattr(audio_tensor, "shape") else len(audio_tensor)
@@ -558,8 +587,10 @@ class ASRModel:
                         info.update({"top_token_ids": det.top_token_ids, "top_logprobs": det.top_logprobs})
                     if getattr(self, "sampling", False):             # a sampling model: what the transcript was decoded at, and the ladder's other measure
                         info.update({"temperature": det.temperature, "compression_ratio": det.compression_ratio})
+                    if word_timestamps:
+                        info.update({"words": [w.as_dict() for w in det.words], "token_start": det.token_start, "token_end": det.token_end})
                 return info
-            return transcript
+            return det if word_timestamps else transcript
         except RuntimeError as e:
             if "out of memory" in str(e).lower():
                 print("⚠️ 显存不足！建议：使用更短的音频 / 减少 max_new_tokens")
@@ -570,9 +601,18 @@ class ASRModel:
 
     def transcribe_batch(self, audios: Sequence[Any], sampling_rate: int = 16000, max_new_tokens: Union[int, Sequence[int]] = 128,
                          hotwords: Optional[List[str]] = None, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
-                         temperature=None, seed: Optional[int] = None) -> List[str]:
+                         temperature=None, seed: Optional[int] = None, word_timestamps: bool = False) -> List[str]:
         """Batched extension (the reference is B=1 per call): one device batch, per-segment results identical to transcribe().  temperature / seed: every
-        segment is decoded with them (a sequence: every segment goes down its own ladder, as independent requests on the scheduler)."""
+        segment is decoded with them (a sequence: every segment goes down its own ladder, as independent requests on the scheduler).  word_timestamps (a model
+        built with timestamps=True): every audio is decoded as its own request, then all are aligned together; the result is a list of Transcription."""
+        if word_timestamps:
+            self._check_timestamps()
+            mn_ = [int(max_new_tokens)] * len(audios) if isinstance(max_new_tokens, int) else [int(x) for x in max_new_tokens]
+            futs_ = [self.submit(a, sampling_rate, mn_[i], hotwords, detailed=True, sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotword_boost=hotword_boost,
+                                 temperature=temperature, seed=seed) for i, a in enumerate(audios)]
+            dets = [f.result() for f in futs_]
+            self._attach_alignment(list(audios), dets, sampling_rate, hotwords)
+            return dets
         bias = self._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost)
         samp = self._request_sampling(temperature, seed)
         kw = {"request_bias": [bias] * len(audios)} if bias else {}
@@ -653,9 +693,84 @@ class ASRModel:
                         r += 1
         return out      # type: ignore[return-value]
 
+    # -- word timestamps: WHEN was this transcript spoken
+    def _check_timestamps(self):
+        if not getattr(self, "timestamps", False) or not getattr(self, "_score_engines", None):
+            raise ValueError("word timestamps need a model built with timestamps=True (ASRModel(..., token_logprobs=True, scoring=True, timestamps=True))")
+
+    def _pieces_of(self, ids: Sequence[int]):
+        """the tokens' text pieces for word grouping (timestamps.split_pieces): the tokenizer's, or - the synthetic prompt has none - one word per token"""
+        from . import timestamps as timestamps_
+        if isinstance(self.prompt, HFPrompt):
+            tok = self.prompt.processor.tokenizer
+            return timestamps_.split_pieces(ids, lambda t: tok.decode(t, skip_special_tokens=False))
+        return [(" " + str(int(t)), [i]) for i, t in enumerate(ids)]
+
+    def _align_items(self, items, replica: Optional[int] = None):
+        """items: (windows, prompt ids, target ids with their EOS, samples of the audio) each -> one timestamps.Alignment each, in as few parallel forced runs on
+        a scoring handle as hold them (scoring.plan_runs, one candidate per audio).  replica: the handle of that replica (ring slices live on one GPU)."""
+        from . import scoring as scoring_, timestamps as timestamps_
+        self._check_timestamps()
+        if replica is None:
+            replica = self._score_next % len(self._score_engines)
+            self._score_next += 1
+        eng = self._score_engines[replica]
+        runs = scoring_.plan_runs([len(it[1]) for it in items], [[len(it[2])] for it in items], eng.max_batch, eng.tok_cap, eng.max_ctx)
+        out: List[Any] = [None] * len(items)
+        with self._score_locks[replica]:
+            for run in runs:
+                segs, req_win, prompts, targets, who = [], [0], [], [], []
+                for a, part in run.groups:
+                    for c in part:
+                        if c is None:
+                            continue
+                        segs.extend(items[a][0]); req_win.append(len(segs)); prompts.append(items[a][1]); targets.append(items[a][2]); who.append(a)
+                ids, _, sc = eng.score_batch(segs, prompts, targets, req_win=req_win, fanout=1, align=True)
+                for r, a in enumerate(who):
+                    n_samples = int(items[a][3])
+                    total, per_win = frontend.request_audio_tokens(n_samples, self.dims)
+                    out[a] = timestamps_.build_alignment(ids[r], sc[r].lp, sc[r].times, self._eos_ids(), per_win, total, n_samples / self.target_sr, self._pieces_of,
+                                                         self.dims.chunk_seconds)
+        return out
+
+    def _attach_alignment(self, audios, dets, sampling_rate: int, hotwords):
+        """align the decoded tokens of each Transcription and hang words / token times on it"""
+        items = []
+        instruction = frontend.build_instruction(hotwords)
+        eos = self._eos_ids()
+        from . import scoring as scoring_
+        for a, det in zip(audios, dets):
+            pcm, wins, n_audio = self._prepare(a, sampling_rate)
+            items.append((wins, self.prompt.build(instruction, n_audio), scoring_.with_eos([int(t) for t in det.token_ids], eos, True), len(pcm)))
+        for det, al in zip(dets, self._align_items(items)):
+            det.words, det.token_start, det.token_end = al.words, al.token_start, al.token_end
+
+    def align(self, audio, transcript, sampling_rate: int = 16000, hotwords: Optional[List[str]] = None):
+        """When every token and word of `transcript` (a string, tokenised with the checkpoint's tokenizer, or a sequence of token ids) was spoken in `audio`: a
+        timestamps.Alignment.  The prompt is the one transcribe() builds; the first EOS id is appended as a last target (its row takes part in the normalisation
+        over tokens and is dropped from the result).  Needs a model built with timestamps=True."""
+        return self.align_batch([audio], [transcript], sampling_rate, hotwords)[0]
+
+    def align_batch(self, audios: Sequence[Any], transcripts: Sequence[Any], sampling_rate: int = 16000, hotwords: Optional[List[str]] = None):
+        """align() for several audios, each with its transcript: as few runs as hold them, the same bits as one call per audio."""
+        from . import scoring as scoring_
+        if not hasattr(self, "model"):
+            raise RuntimeError("ASR model has been released")
+        self._check_timestamps()
+        if len(audios) != len(transcripts):
+            raise ValueError(f"{len(audios)} audios but {len(transcripts)} transcripts")
+        instruction = frontend.build_instruction(hotwords)
+        eos = self._eos_ids()
+        items = []
+        for a, t in zip(audios, transcripts):
+            pcm, wins, n_audio = self._prepare(a, sampling_rate)
+            items.append((wins, self.prompt.build(instruction, n_audio), scoring_.with_eos(self._candidate_ids(t), eos, True), len(pcm)))
+        return self._align_items(items)
+
     def transcribe_file(self, audio, vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                         max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filename: str = "", sampling_rate: int = 16000,
-                        sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None, seed: Optional[int] = None):
+                        sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None, seed: Optional[int] = None,
+                        word_timestamps: bool = False):
         """The body of the reference's /transcribe/file endpoint (main.py:193-649) as a generator of its records (dicts with the
         reference's keys: initialization, segments_summary, segment_result / segment_error in segment order, final_summary).  `audio`:
         mono int16 PCM at `sampling_rate`, or the reference's float tensor [1, N] of int16 / 32768 values; `vad`: a vad.VADProcessor.  The
@@ -664,16 +779,18 @@ class ASRModel:
         the generator is exhausted or closed (filemode.py).  Sizes and times in the records are those of the 16 kHz content."""
         from . import filemode
         return filemode.transcribe_file(self, audio, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filename, sampling_rate,
-                                        sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotword_boost=hotword_boost, temperature=temperature, seed=seed)
+                                        sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotword_boost=hotword_boost, temperature=temperature, seed=seed,
+                                        word_timestamps=word_timestamps)
 
     def transcribe_files(self, audios: Sequence[Any], vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                          max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filenames: Optional[Sequence[str]] = None,
                          sampling_rate: int = 16000, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None,
-                         seed: Optional[int] = None):
+                         seed: Optional[int] = None, word_timestamps: bool = False):
         """transcribe_file for several files: all VAD passes in one device call, one record iterator per file (filemode.transcribe_files)."""
         from . import filemode
         return filemode.transcribe_files(self, audios, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filenames, sampling_rate,
-                                         sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotword_boost=hotword_boost, temperature=temperature, seed=seed)
+                                         sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotword_boost=hotword_boost, temperature=temperature, seed=seed,
+                                         word_timestamps=word_timestamps)
 
     def get_model_info(self) -> Dict[str, Any]:
         """asr.py:490-513: the reference's keys for a GPU device (`cuda_version` carries the HIP runtime version: torch.version.cuda is
@@ -687,6 +804,7 @@ class ASRModel:
         info.update({"engine": "sonicscribe_amd/gfx950", "replicas": len(self.__dict__.get("models", [])), "slots_per_replica": self.__dict__.get("slots", 1), "continuous": self.__dict__.get("continuous", False), "bulk": self.__dict__.get("bulk", False),
                      "weights_mb": self.model.weight_bytes() / 1024 ** 2 if hasattr(self, "model") else 0.0})
         info["scoring"] = bool(self.__dict__.get("scoring", False))
+        info["timestamps"] = bool(self.__dict__.get("timestamps", False))
         g = self.__dict__.get("generation_guards")
         if g is not None:                            # the logits processors in force: the checkpoint's generation_config.json unless the constructor overrode it
             info.update(g.as_dict())

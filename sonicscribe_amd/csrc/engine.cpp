@@ -374,6 +374,32 @@ int score_alloc(sonic_engine* e) {
     if (!e->score_plan_h && hipHostMalloc((void**)&e->score_plan_h, ((size_t)3 * e->tok_cap + 4 * 64) * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(e, SONIC_ERR_OOM, "forced_parallel: pinned host memory exhausted"); }
     return SONIC_OK;
 }
+// word timestamps (option forced_align): the align run's buffers, at its first run on the handle or when a run needs more than the last one left.
+// S score rows (<= tok_cap), A_max audio keys of the longest run, heads_per_layer the most heads any layer contributes
+template <typename Tt> static int align_grow(sonic_engine* e, Tt** p, size_t* cap, size_t need) {
+    if (*p && *cap >= need) return SONIC_OK;
+    if (*p) {
+        HIPC(e, stream_sync(e));
+        e->allocs.erase(std::find(e->allocs.begin(), e->allocs.end(), (void*)*p));
+        HIPC(e, hipFree(*p));
+        e->alloc_bytes -= (int64_t)((*cap * sizeof(Tt) + 3) / 4 * 4); *p = nullptr; *cap = 0;
+    }
+    TRY(dalloc(e, p, need, false));
+    *cap = need;
+    return SONIC_OK;
+}
+int align_alloc(sonic_engine* e, int S, int A_max, int heads_per_layer) {
+    size_t tcap = e->align_M_cap;
+    TRY(align_grow(e, &e->align_P, &e->align_P_cap, (size_t)2 * heads_per_layer * S * A_max));      // probabilities | filtered z
+    e->align_Zoff = (size_t)heads_per_layer * S * A_max;
+    TRY(align_grow(e, &e->align_trace, &tcap, (size_t)S * A_max));
+    TRY(align_grow(e, &e->align_M, &e->align_M_cap, (size_t)S * A_max));
+    if (!e->align_t) TRY(dalloc(e, &e->align_t, (size_t)64 * e->out_cap));
+    const size_t plan = (size_t)2 * e->tok_cap + 4 * 64 + ALIGN_MAX_HEADS;
+    if (!e->align_plan_d) { TRY(dalloc(e, &e->align_plan_d, plan)); e->align_plan_cap = plan; }
+    if (!e->align_plan_h && hipHostMalloc((void**)&e->align_plan_h, plan * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(e, SONIC_ERR_OOM, "forced_align: pinned host memory exhausted"); }
+    return SONIC_OK;
+}
 // option top_logprobs = K: the K best alternatives of every step ride in the token's log-probability record, which grows to 1 + 2K floats.  The
 // buffer is exchanged for one of the new width (sonic_memory_info follows), so the records of a finished batch that has not been fetched yet are gone with the
 // old one: fetch first (include/sonic_hip.h says so).  The caller holds the lock and has asked gen_busy.
@@ -696,6 +722,7 @@ extern "C" int sonic_slot_create(sonic_engine* parent, sonic_engine** out) {
     if (root->opt_sampling && (s = samp_enable(e, 1)) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }
     e->opt_samp_fill_milli = root->opt_samp_fill_milli;
     e->opt_forced_parallel = root->opt_forced_parallel; e->opt_forced_fanout = root->opt_forced_fanout; e->opt_score_chunk_rows = root->opt_score_chunk_rows;      // (the buffers come with the slot's first parallel run)
+    e->opt_forced_align = root->opt_forced_align; e->align_heads = root->align_heads;      // (likewise)
     e->weight_bytes = 0; e->finalized = true; e->owner = root;
     root->slots.push_back(e);
     *out = e;
@@ -752,6 +779,7 @@ extern "C" void sonic_destroy(sonic_engine* e) {
     for (int i = 0; i < 2; ++i) { if (e->plan_buf[i]) (void)hipHostFree(e->plan_buf[i]); if (e->plan_ev[i]) (void)hipEventDestroy(e->plan_ev[i]); }
     if (e->svc_h) (void)hipHostFree(e->svc_h);
     if (e->score_plan_h) (void)hipHostFree(e->score_plan_h);
+    if (e->align_plan_h) (void)hipHostFree(e->align_plan_h);
     stage_free(e->bias); stage_free(e->samp);
     if (e->st_io) { (void)hipStreamSynchronize(e->st_io); (void)hipStreamDestroy(e->st_io); }
     if (e->xfer_ev) (void)hipEventDestroy(e->xfer_ev);

@@ -99,10 +99,52 @@ __global__ void test_transpose_v_kernel(const bf16_t* v, bf16_t* vt, int B, int 
     vt[(((long)b * Hkv + c / hd) * hd + c % hd) * ld_t + t] = v[e];
 }
 
+// sonic_test_attention on an align handle (option forced_align): the three word-timestamp kernels on caller data through production's descriptor
+// (align_probs_args).  q [B][Tq][Hq * 128], k [B][Tk][Hkv * 128]; every one of the Hq heads takes part, the audio run is all Tk keys of a sequence, its rows are its
+// Tq queries.  out [B][Tq][Tk + 1]: M's row, then t_n.  The caller holds the lock
+static int test_align(sonic_engine* e, const float* q, const float* k, float* out, int B, int Tq, int Tk, int Hq, int Hkv, int hd, int causal) {
+    if (!q || !k || !out) return fail(e, SONIC_ERR_INVALID, "align hook: q, k and out are needed");
+    if (hd != 128 || causal) return fail(e, SONIC_ERR_INVALID, "align hook: hd = 128 and causal = 0 (every audio key lies before every row)");
+    if (B < 1 || B > 64 || Tq < 1 || Tq > ALIGN_MAX_ROWS || Tk < 1 || Hkv < 1 || Hq % Hkv || Hq > ALIGN_MAX_HEADS || (long)B * Tq > e->tok_cap)
+        return fail(e, SONIC_ERR_INVALID, "align hook: bad shape (B <= 64, Tq <= %d, B * Tq <= tok_cap = %d, Hq <= %d a multiple of Hkv)", ALIGN_MAX_ROWS, e->tok_cap, ALIGN_MAX_HEADS);
+    const int S = B * Tq;
+    TRY(align_alloc(e, S, Tk, Hq));
+    TmpBuf tb(e->st);
+    bf16_t* dq = up_bf16(e, tb, q, (size_t)S * Hq * 128);
+    bf16_t* dk = up_bf16(e, tb, k, (size_t)B * Tk * Hkv * 128);
+    float* dt_out = tb.get<float>(S); int* rec = tb.get<int>(S);
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    const size_t tc = (size_t)e->tok_cap;
+    std::vector<int> plan(2 * tc + 4 * 64 + ALIGN_MAX_HEADS, 0), iota(S);
+    for (int b = 0, s = 0; b < B; ++b) {
+        int* sp = plan.data() + 2 * tc + 4 * b;
+        sp[0] = s; sp[1] = Tq; sp[2] = 0; sp[3] = Tk;
+        for (int n = 0; n < Tq; ++n, ++s) { plan[s] = s; plan[tc + s] = b; iota[s] = s; }
+    }
+    for (int h = 0; h < Hq; ++h) plan[2 * tc + 4 * 64 + h] = h;
+    HIPC(e, h2d(e, e->align_plan_d, plan.data(), plan.size() * 4));
+    HIPC(e, h2d(e, rec, iota.data(), (size_t)S * 4));
+    e->align_S = S; e->align_nseq = B; e->align_Amax = Tk; e->align_Lmax = Tq; e->align_Htot = Hq; e->align_last_heads = Hq; e->align_last = false;
+    fill_words((int*)e->align_M, 0, (size_t)S * Tk, e->st);
+    AlignArgs a = align_probs_args(e, dq, dk, Hkv * 128L, 128, (long)Tk * Hkv * 128, e->align_plan_d + 2 * tc + 4 * 64, Hq, Hq, Hkv, rec);
+    a.t_out = dt_out;
+    launch_align_probs(a, e->st);
+    launch_align_reduce(a, e->st);
+    launch_align_dtw(a, e->st);
+    HIPC(e, stream_sync(e));
+    HIPC(e, hipGetLastError());
+    std::vector<float> m((size_t)S * Tk), t(S);
+    HIPC(e, d2h(e, m.data(), e->align_M, m.size() * 4));
+    HIPC(e, d2h(e, t.data(), dt_out, (size_t)S * 4));
+    for (int s = 0; s < S; ++s) { memcpy(out + (size_t)s * (Tk + 1), m.data() + (size_t)s * Tk, (size_t)Tk * 4); out[(size_t)s * (Tk + 1) + Tk] = t[s]; }
+    return SONIC_OK;
+}
+
 extern "C" int sonic_test_attention(sonic_engine* e, const float* q, const float* k, const float* v, float* out,
                                     int B, int Tq, int Tk, int Hq, int Hkv, int hd, int causal) {
     if (!e) return SONIC_ERR_INVALID;
     ENTER(e);
+    if (e->opt_forced_align) return test_align(e, q, k, out, B, Tq, Tk, Hq, Hkv, hd, causal);
     if (hd != 64 && hd != 128) return fail(e, SONIC_ERR_INVALID, "hd must be 64 or 128");
     TmpBuf tb(e->st);
     const int Tkp = (Tk + 63) / 64 * 64;

@@ -207,6 +207,18 @@ struct sonic_engine {
     // first parallel run, are counted by sonic_memory_info and go with the handle
     int opt_forced_parallel = 0, opt_forced_fanout = 1, opt_score_chunk_rows = SCORE_CHUNK_DEFAULT;
     void* score_logits = nullptr; int score_rows_cap = 0; int* score_plan_d = nullptr; int* score_plan_h = nullptr;
+    // word timestamps on the parallel forced run (options forced_align / align_head; align.hip).  align_heads: the selected heads as l * 256 + h, sorted
+    // (empty: every head of the last ceil(dec_layers / 2) layers).  The buffers come with the first align run, sized to that run (and exchanged for larger ones by a
+    // later run that needs more), are counted by sonic_memory_info and go with the handle: align_P 2 x [heads of a layer][S][A_max] and align_M [S][A_max] fp32, the DTW's
+    // int8 trace [S][A_max], align_t [64][out_cap] (t_n beside out_lp's records), the plan (per score row its query row and sequence, per sequence row0 | L | a0 | A,
+    // the selected heads layer by layer) on the device and pinned.  align_live: the prefill under way is an align run's (run_prefill launches align_probs / _reduce
+    // behind the selected layers' RoPE); align_last: the batch in hand is one - its log-probability records carry t_n as one more float (fetch_locked)
+    int opt_forced_align = 0; std::vector<int> align_heads;
+    float *align_P = nullptr, *align_M = nullptr, *align_t = nullptr; signed char* align_trace = nullptr; int *align_plan_d = nullptr, *align_plan_h = nullptr;
+    size_t align_P_cap = 0, align_M_cap = 0, align_plan_cap = 0, align_Zoff = 0;      // align_P holds the probabilities and, align_Zoff floats on, the filtered z of one layer's heads
+    bool align_live = false, align_last = false;
+    int align_S = 0, align_nseq = 0, align_Amax = 0, align_Lmax = 0, align_Htot = 0, align_last_heads = 0;      // of the run under way / the last one
+    std::vector<std::vector<int>> align_layer_heads; std::vector<int> align_layer_off;                             // per decoder layer: its selected heads, and where they start in the plan
     uint64_t spliced = 0;          // rows of the last prefill that sonic_splice_rows handed to a continuous loop (bit r = request r); cleared by every prefill (gen_busy)
     long long* kt = nullptr; int kt_layer = -1;     // diagnostics ("ktrace" option): in-kernel timestamps of one decoder layer's kernels
     int* ring_peak = nullptr;                        // [Bm] per-request max |s| of a ring-staged batch (ingest.hip)
@@ -355,6 +367,10 @@ RopeAppendArgs rope_append_args(const bf16_t* qkv, bf16_t* q_out, bf16_t* Kc, bf
 enum { OGU_FUSED = 0, OGU_SPLIT_NORM = 1, OGU_HALF_FUSED = 2, OGU_UNFUSED = 3 };
 struct OGuChain { const bf16_t *att, *Wo; bf16_t* x; const float* ln_w; const bf16_t* Wgu; int gu8; bf16_t *hn, *act; float *ss, *slab; long long *kt_o, *kt_gu; };
 void launch_o_gu(sonic_engine* e, int form, const OGuChain& c, int M, int K, int D, int ff, float eps);
+// word timestamps: the launches' one descriptor - Q rows [tok][Hq * 128], K as the strides say, the plan and buffers of the handle - shared by
+// run_prefill / run_forced_parallel and the hook (sonic_test_attention on an align handle)
+AlignArgs align_probs_args(sonic_engine* e, const bf16_t* Q, const bf16_t* K, long k_ld, long k_head_stride, long k_seq_stride, const int* heads, int n_heads, int Hq, int Hkv, const int* rec);
+int align_alloc(sonic_engine* e, int S, int A_max, int heads_per_layer);      // the buffers at (at least) this run's need
 int score_alloc(sonic_engine* e);                                  // the parallel forced run's buffers at the handle's current score_chunk_rows (first use, or a larger chunk)
 int upload_plan(sonic_engine* e, int R, const HostPlan& hp);       // the prefill's prologue, every kind: the request plan through the pinned staging buffer ...
 int reset_row_state(sonic_engine* e, int R, int n_tok);            // ... and the rows' counters, history, bias tables and sampling values for the greedy loop

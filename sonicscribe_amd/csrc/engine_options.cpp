@@ -39,10 +39,35 @@ static int opt_request_bias_fill(sonic_engine* e, const char* key, int value) { 
 }
 // the parallel forced run (include/sonic_hip.h beside sonic_set_forced_ids).  forced_parallel: on the owner (its slots copy it) or on a slot alone;
 // refused while the handle has work in hand, as the options above.  forced_fanout = N: the run's R sequences are R / N audio requests with N candidates each
-static int opt_forced_parallel(sonic_engine* e, const char* key, int value) { TRY(gen_busy(e, key)); e->opt_forced_parallel = value ? 1 : 0; return SONIC_OK; }
+static int opt_forced_parallel(sonic_engine* e, const char* key, int value) {
+    TRY(gen_busy(e, key));
+    if (!value && e->opt_forced_align) return fail(e, SONIC_ERR_INVALID, "forced_parallel cannot be switched off while option forced_align is on (the alignment rides on the parallel forced run)");
+    e->opt_forced_parallel = value ? 1 : 0; return SONIC_OK;
+}
 static int opt_forced_fanout(sonic_engine* e, const char* key, int value) {
     if (value < 1 || value > e->Bm) return fail(e, SONIC_ERR_INVALID, "forced_fanout: %d is outside 1 .. %d (max_batch)", value, e->Bm);
     e->opt_forced_fanout = value; return SONIC_OK;      // (only read by a parallel run as it starts)
+}
+// word timestamps on the parallel forced run (include/sonic_hip.h beside sonic_set_forced_ids).  forced_align: only on a scoring handle, never on the
+// fp32 kind (its prefill keeps no roped queries), refused while the handle has work in hand.  align_head = l * 256 + h adds head h of decoder layer l to the selection
+// (-1: back to the default, every head of the last ceil(dec_layers / 2) layers)
+static int opt_forced_align(sonic_engine* e, const char* key, int value) {
+    TRY(gen_busy(e, key));
+    if (value && e->f32) return fail(e, SONIC_ERR_INVALID, "forced_align: the fp32 kind has no alignment kernels (its prefill keeps no roped queries); use a bf16 or int8-mode handle");
+    if (value && !e->opt_forced_parallel) return fail(e, SONIC_ERR_INVALID, "forced_align: option forced_parallel must be on first (the alignment rides on the parallel forced run; sonic_set_option(e, \"forced_parallel\", 1))");
+    e->opt_forced_align = value ? 1 : 0;
+    if (!value) e->align_last = false;
+    return SONIC_OK;
+}
+static int opt_align_head(sonic_engine* e, const char* key, int value) {
+    TRY(gen_busy(e, key));
+    if (value == -1) { e->align_heads.clear(); return SONIC_OK; }
+    const int l = value >> 8, h = value & 255;
+    if (value < 0 || l >= e->d.dec_layers || h >= e->d.dec_heads) return fail(e, SONIC_ERR_INVALID, "align_head: %d (layer %d, head %d) is outside %d layers x %d heads", value, l, h, e->d.dec_layers, e->d.dec_heads);
+    if (std::find(e->align_heads.begin(), e->align_heads.end(), value) != e->align_heads.end()) return SONIC_OK;
+    if (e->align_heads.size() >= ALIGN_MAX_HEADS) return fail(e, SONIC_ERR_INVALID, "align_head: the list already holds %d heads", ALIGN_MAX_HEADS);
+    e->align_heads.insert(std::upper_bound(e->align_heads.begin(), e->align_heads.end(), value), value);      // sorted: layer by layer, heads ascending
+    return SONIC_OK;
 }
 // the two knobs that do device work
 static int opt_ktrace(sonic_engine* e, const char*, int value) {              // diagnostics: record in-kernel timestamps of decoder layer `value` (-1: off); sonic_debug_ktrace reads them
@@ -118,6 +143,8 @@ static const OptRow OPTIONS[] = {
     {"request_bias_fill", APPLY(opt_request_bias_fill)},
     {"forced_parallel", APPLY(opt_forced_parallel)},
     {"forced_fanout", APPLY(opt_forced_fanout)},
+    {"forced_align", APPLY(opt_forced_align)},
+    {"align_head", APPLY(opt_align_head)},
     {"score_chunk_rows", ENG(opt_score_chunk_rows), false, [](int v) { return v < 16 ? 16 : (v > 4096 ? 4096 : v); }},   // score rows per lm_head GEMM + row-kernel launch (the buffer follows at the next parallel run)
     {"ktrace", APPLY(opt_ktrace)},
     {"inject_dev_err", APPLY(opt_inject_dev_err)},
@@ -140,7 +167,8 @@ extern "C" int sonic_set_option(sonic_engine* e, const char* key, int value) {
 
 // The buffers sonic_debug_read serves, one row each: the name, the elements it holds, and where it lives on a 16-bit handle and on the fp32 kind (null: that kind
 // has no such buffer).  prefill_tap is the one row with an index: tap `index` of the taps option prefill_taps recorded
-struct DbgRow { const char* name; size_t (*cap)(const sonic_engine*); const bf16_t* (*src16)(const sonic_engine*); const float* (*src32)(const sonic_engine*); };
+struct DbgRow { const char* name; size_t (*cap)(const sonic_engine*); const bf16_t* (*src16)(const sonic_engine*); const float* (*src32)(const sonic_engine*);
+                const float* (*f32_on_16)(const sonic_engine*) = nullptr; };      // f32_on_16: a buffer that is fp32 on a 16-bit handle too (read as it is)
 #define CAP(x) [](const sonic_engine* e) -> size_t { return x; }
 #define S16(m) [](const sonic_engine* e) -> const bf16_t* { return e->m; }
 #define S32(m) [](const sonic_engine* e) -> const float* { return e->f->m; }
@@ -157,17 +185,21 @@ static const DbgRow DEBUG_BUFS[] = {
     {"shn", CAP((size_t)64 * e->d.dec_d), S16(shn), nullptr},          // decode-step buffers as the last step left them
     {"satt", CAP((size_t)64 * e->QD), S16(satt), nullptr},
     {"sact", CAP((size_t)64 * e->d.dec_ff), S16(sact), nullptr},
+    // the last align run: the last selected layer's probabilities [its heads][S][A_max] and M [S][A_max], fp32
+    {"align_probs", CAP(e->align_P ? (size_t)e->align_last_heads * e->align_S * e->align_Amax : 0), nullptr, nullptr, [](const sonic_engine* e) -> const float* { return e->align_P; }},
+    {"align_matrix", CAP(e->align_M ? (size_t)e->align_S * e->align_Amax : 0), nullptr, nullptr, [](const sonic_engine* e) -> const float* { return e->align_M; }},
 };
 // Debug read-back of an internal activation buffer as fp32 (tests / diagnostics only).
 extern "C" int sonic_debug_read(sonic_engine* e, const char* name, int index, float* out, int64_t n) {
     if (!e || !name || !out) return SONIC_ERR_INVALID;
     ENTER(e);
     for (const DbgRow& r : DEBUG_BUFS) {
-        if (strcmp(name, r.name) || !(e->f32 ? (bool)r.src32 : (bool)r.src16)) continue;
+        if (strcmp(name, r.name) || !(e->f32 ? (bool)r.src32 : (r.src16 || r.f32_on_16))) continue;
         const bool tap = &r == &DEBUG_BUFS[0];
         if (tap && !e->taps) return fail(e, SONIC_ERR_INVALID, "no taps recorded");
         const size_t cap = r.cap(e), off = tap ? (size_t)index * cap : 0;
         if (n < 0 || (size_t)n > cap) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
+        if (!e->f32 && r.f32_on_16) { HIPC(e, stream_sync(e)); if (n > 0) HIPC(e, d2h(e, out, r.f32_on_16(e), (size_t)n * 4)); return SONIC_OK; }
         if (!e->f32) return read_back_16(e, r.src16(e) + off, out, (size_t)n);
         HIPC(e, stream_sync(e)); HIPC(e, d2h(e, out, r.src32(e) + off, (size_t)n * 4));      // fp32 kind: its buffers are fp32 already
         return SONIC_OK;

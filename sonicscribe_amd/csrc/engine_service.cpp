@@ -489,6 +489,16 @@ int fetch_locked(sonic_engine* e, int32_t* out_ids, int out_ld, int32_t* out_len
         }
         if (out_lp) {
             const size_t w = (size_t)lp_width(e);            // out_ld counts floats: a token's record holds w of them (option top_logprobs)
+            if (e->align_last && e->align_t) {      // an align run's batch: t_n rides behind the record's 1 + 2K floats, which keep their bits
+                if ((size_t)nn[r] * (w + 1) > (size_t)out_ld) return fail(e, SONIC_ERR_INVALID, "out_ld too small (an align run's records hold %zu floats)", w + 1);
+                std::vector<float> rec((size_t)nn[r] * w), tn((size_t)nn[r]);
+                HIPC(e, d2h_async(e, rec.data(), e->out_lp + (size_t)r * e->out_cap * w, rec.size() * 4));
+                HIPC(e, d2h_async(e, tn.data(), e->align_t + (size_t)r * e->out_cap, tn.size() * 4));
+                HIPC(e, stream_sync(e));
+                float* o = out_lp + (size_t)r * out_ld;
+                for (int n = 0; n < nn[r]; ++n) { memcpy(o + (size_t)n * (w + 1), rec.data() + (size_t)n * w, w * 4); o[(size_t)n * (w + 1) + w] = tn[n]; }
+                continue;
+            }
             if ((size_t)nn[r] * w > (size_t)out_ld) return fail(e, SONIC_ERR_INVALID, "out_ld too small");
             HIPC(e, d2h_async(e, out_lp + (size_t)r * out_ld, e->out_lp + (size_t)r * e->out_cap * w, (size_t)nn[r] * w * 4));
         }

@@ -216,6 +216,18 @@ RopeAppendArgs rope_append_args(const bf16_t* qkv, bf16_t* q_out, bf16_t* Kc, bf
     return ra;
 }
 
+// the word-timestamp launches (align.hip) over the handle's align plan and buffers: Q = the roped query rows, K = the audio keys as the strides say
+// (the prefill: a layer's K cache; the hook: caller rows), `heads` = n_heads ascending head ids on the device
+AlignArgs align_probs_args(sonic_engine* e, const bf16_t* Q, const bf16_t* K, long k_ld, long k_head_stride, long k_seq_stride, const int* heads, int n_heads, int Hq, int Hkv, const int* rec) {
+    AlignArgs a{};
+    a.Q = Q; a.q_ld = Hq * 128L; a.K = K; a.k_ld = k_ld; a.k_head_stride = k_head_stride; a.k_seq_stride = k_seq_stride;
+    a.qrow = e->align_plan_d; a.rseq = e->align_plan_d + e->tok_cap; a.seqp = e->align_plan_d + 2 * (size_t)e->tok_cap; a.heads = heads; a.rec = rec;
+    a.n_heads = n_heads; a.grp = Hq / Hkv; a.S = e->align_S; a.n_seq = e->align_nseq; a.A_max = e->align_Amax; a.L_max = e->align_Lmax; a.dt = e->dt;
+    a.scale = 1.0f / sqrtf(128.f); a.h_total = (float)e->align_Htot;
+    a.P = e->align_P; a.Z = e->align_P + e->align_Zoff; a.M = e->align_M; a.t_out = e->align_t; a.trace = e->align_trace;
+    return a;
+}
+
 static long long* kt_slot(sonic_engine* e, int l, int slot) { return (e->kt && l == e->kt_layer) ? e->kt + (long)slot * KT_SLOT_BLOCKS * 8 : nullptr; }
 void skinny(sonic_engine* e, const bf16_t* X, long ldx, const bf16_t* W, float* P, int M, int N, int K, int* ks_out, long long* kt) {
     SkinnyArgs a = skinny_args(X, ldx, W, P, M, N, K, skinny_pick_ksplit(N, K), e->dt); a.kt = kt;
@@ -535,6 +547,13 @@ static int run_prefill(sonic_engine* e, int R, const HostPlan& hp, bool head = t
         const bool tiles = !e->opt_no_rope_tiles;
         launch_rope_append(rope_append_args(e->dqkv, e->dq, e->Kc + kvoff, e->Vc + kvoff, e->Vts, e->max_ctx, e->tok_seq, e->tok_pos_pf, e->dec_cs, d.dec_heads, d.dec_kv_heads,
                                             e->max_ctx, M, dt, tiles ? e->q_off : nullptr, e->q_len, R, hp.max_p), false, e->st);
+        if (e->align_live && !e->align_layer_heads[l].empty()) {      // word timestamps: dq and this layer's K cache are valid here, and only here
+            const AlignArgs aa = align_probs_args(e, e->dq, e->Kc + kvoff, 128, e->max_ctx * 128L, (long)d.dec_kv_heads * e->max_ctx * 128, e->align_plan_d + 2 * (size_t)e->tok_cap + 4 * 64 + e->align_layer_off[l],
+                                                  (int)e->align_layer_heads[l].size(), d.dec_heads, d.dec_kv_heads, nullptr);
+            launch_align_probs(aa, e->st);
+            launch_align_reduce(aa, e->st);
+            e->align_last_heads = aa.n_heads;
+        }
         const FlashArgs f = prefill_flash_args(e->dq, e->Kc + kvoff, e->Vts, e->datt, e->q_off, e->q_len, e->q_len, d.dec_heads, d.dec_kv_heads, e->max_ctx, dt);
         launch_flash(f, 128, true, R, hp.max_p, e->st);
         lin(EPI_BIAS_RESID, e->datt, e->QD, L.wo, L.wo_t, 0, L.qo, e->dx, D, D, e->QD, e->dx, D, false);
@@ -574,7 +593,7 @@ int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int
     }
     if (e->force_d && (e->force_R != R || e->force_ld < hp.max_steps))
         return fail(e, SONIC_ERR_INVALID, "forced ids are [%d][%d] but the run has %d requests / %d steps", e->force_R, e->force_ld, R, hp.max_steps);
-    e->R = R; e->max_steps = hp.max_steps; e->last_qlen = hp.q_len; e->last_maxnew = hp.max_new;
+    e->R = R; e->max_steps = hp.max_steps; e->last_qlen = hp.q_len; e->last_maxnew = hp.max_new; e->align_last = false;
     if (want_logits) {
         const size_t need_n = (size_t)hp.max_steps * R * d.vocab;
         if (need_n > e->dump_cap) {
@@ -780,7 +799,33 @@ static int run_forced_parallel(sonic_engine* e, const int32_t* req_win, int R, c
     for (int r = 0; r < R; ++r) hp.max_new[r] = max_new[r];
     hp.max_steps = max_steps;
     if (max_steps > e->out_cap) return fail(e, SONIC_ERR_INVALID, "max_new_tokens too large");
+    // word timestamps (option forced_align): every sequence's audio placeholders must be one run [a0, a0 + A), A >= 1, inside its prompt
+    const bool align = e->opt_forced_align != 0;
+    std::vector<int> al_a0(R, 0), al_A(R, 0);
+    int al_S = 0, al_Amax = 0, al_Lmax = 0, al_Hmax = 0;
+    if (align) {
+        if (e->f32) return fail(e, SONIC_ERR_INVALID, "forced_align: the fp32 kind has no alignment kernels");
+        for (int r = 0; r < R; ++r) {
+            const int P = (int)(prompt_off[r + 1] - prompt_off[r]);
+            const int32_t* pi = prompt_ids + prompt_off[r];
+            int first = -1, last = -1, cnt = 0;
+            for (int i = 0; i < P; ++i) if (pi[i] == d.audio_token_id) { if (first < 0) first = i; last = i; ++cnt; }
+            if (cnt == 0) return fail(e, SONIC_ERR_INVALID, "forced_align: sequence %d has no audio placeholder in its prompt (nothing to align to)", r);
+            if (last - first + 1 != cnt) return fail(e, SONIC_ERR_INVALID, "forced_align: the audio placeholders of sequence %d are not one contiguous run (%d of them between positions %d and %d)", r, cnt, first, last);
+            if (L[r] > ALIGN_MAX_ROWS) return fail(e, SONIC_ERR_INVALID, "forced_align: sequence %d has %d targets, the DTW kernel holds %d", r, L[r], ALIGN_MAX_ROWS);
+            al_a0[r] = first; al_A[r] = cnt; al_S += L[r]; al_Amax = std::max(al_Amax, cnt); al_Lmax = std::max(al_Lmax, (int)L[r]);
+        }
+        // the selection layer by layer: the caller's list, else every head of the last ceil(dec_layers / 2) layers (Whisper's rule without alignment heads)
+        e->align_layer_heads.assign(d.dec_layers, std::vector<int>()); e->align_layer_off.assign(d.dec_layers, 0);
+        if (!e->align_heads.empty()) for (int c : e->align_heads) e->align_layer_heads[c >> 8].push_back(c & 255);
+        else for (int l = d.dec_layers - (d.dec_layers + 1) / 2; l < d.dec_layers; ++l) for (int h = 0; h < d.dec_heads; ++h) e->align_layer_heads[l].push_back(h);
+        int tot = 0;
+        for (int l = 0; l < d.dec_layers; ++l) { e->align_layer_off[l] = tot; tot += (int)e->align_layer_heads[l].size(); al_Hmax = std::max(al_Hmax, (int)e->align_layer_heads[l].size()); }
+        if (tot > ALIGN_MAX_HEADS) return fail(e, SONIC_ERR_INVALID, "forced_align: the default selection (%d heads) exceeds %d: select heads with option align_head", tot, ALIGN_MAX_HEADS);
+        e->align_Htot = tot;
+    }
     if (e->wait_pending) { HIPC(e, hipStreamWaitEvent(e->st, e->wait_ev, 0)); e->wait_pending = false; }
+    if (align) TRY(align_alloc(e, al_S, al_Amax, al_Hmax));
     TRY(score_alloc(e));
     {   // staging buffer of this run (run_to_first_token)
         const int i = e->plan_idx ^ 1;
@@ -816,6 +861,25 @@ static int run_forced_parallel(sonic_engine* e, const int32_t* req_win, int R, c
     }
     for (int r = R; r < 64; ++r) st_h[64 + r] = 0;
 
+    e->align_last = false;
+    if (align) {      // the align plan: per score row its query row and sequence, per sequence row0 | L | a0 | A, the heads layer by layer; M starts at zero
+        int* ah = e->align_plan_h;
+        const size_t tc = (size_t)e->tok_cap;
+        for (int r = 0, sr = 0; r < R; ++r) {
+            int* sp = ah + 2 * tc + 4 * r;
+            sp[0] = sr; sp[1] = L[r]; sp[2] = al_a0[r]; sp[3] = al_A[r];
+            for (int n = 0; n < L[r]; ++n, ++sr) { ah[sr] = ph[sr]; ah[tc + sr] = r; }
+        }
+        int* hh = ah + 2 * tc + 4 * 64;
+        for (int l = 0; l < d.dec_layers; ++l) for (size_t i = 0; i < e->align_layer_heads[l].size(); ++i) hh[e->align_layer_off[l] + i] = e->align_layer_heads[l][i];
+        HIPC(e, hipMemcpyAsync(e->align_plan_d, ah, (size_t)S * 4, hipMemcpyHostToDevice, e->st));
+        HIPC(e, hipMemcpyAsync(e->align_plan_d + tc, ah + tc, (size_t)S * 4, hipMemcpyHostToDevice, e->st));
+        HIPC(e, hipMemcpyAsync(e->align_plan_d + 2 * tc, ah + 2 * tc, (size_t)(4 * 64 + ALIGN_MAX_HEADS) * 4, hipMemcpyHostToDevice, e->st));
+        e->align_S = S; e->align_nseq = R; e->align_Amax = al_Amax; e->align_Lmax = al_Lmax; e->align_last_heads = 0;
+        for (size_t o = 0; o < (size_t)S * al_Amax; o += (size_t)1 << 30) launch_fill_i32((int*)e->align_M + o, 0, (int)std::min((size_t)1 << 30, (size_t)S * al_Amax - o), e->st);
+        e->align_live = true;
+    }
+    struct AlignOff { sonic_engine* e; ~AlignOff() { e->align_live = false; } } align_off{e};      // whatever way the run leaves
     (void)hipEventRecord(e->ev[0], e->st);
     TRY(run_mel(e, e->W, e->f32));
     (void)hipEventRecord(e->ev[1], e->st);
@@ -833,6 +897,10 @@ static int run_forced_parallel(sonic_engine* e, const int32_t* req_win, int R, c
     (void)hipEventRecord(e->ev[2], e->st);
     TRY(e->f32 ? f32_run_prefill(e, R, hp, false) : run_prefill(e, R, hp, false));
     HIPC(e, hipMemcpyAsync(e->score_plan_d, ph, (size_t)3 * S * 4, hipMemcpyHostToDevice, e->st));
+    if (align) {      // DTW over the finished M: t_n beside the records (rec: the score plan's record indices)
+        launch_align_dtw(align_probs_args(e, e->dq, e->Kc, 128, e->max_ctx * 128L, (long)d.dec_kv_heads * e->max_ctx * 128, nullptr, 0, d.dec_heads, d.dec_kv_heads, e->score_plan_d + 2 * S), e->st);
+        e->align_live = false; e->align_last = true;
+    }
     if (e->f32) f32_score_norm(e, e->score_plan_d, S);
     else launch_rmsnorm(e->dx, e->dec_nw, e->dhn, S, d.dec_d, d.dec_rms_eps, e->score_plan_d, e->st, e->dt);
     ScoreArgs sa{};

@@ -240,6 +240,26 @@ void launch_transpose_i8(const int8_t* w, int8_t* wt, int N, int K, hipStream_t 
 // int8 encoder: V columns [col0, col0 + C) of the row-major QKV matrix -> V^T [seg][C][vt_ld]
 void launch_transpose_v(const bf16_t* qkv, long ld, int col0, bf16_t* vt, int n_seg, int T, int C, int vt_ld, long vt_seg_stride, hipStream_t s);
 
+// ---- word timestamps on the parallel forced run (align.hip; option forced_align) ----
+// Score row s is query row qrow[s] of Q (packed tokens, [tok][Hq * 128]) and belongs to sequence rseq[s]; sequence r is seqp[4r ..]: its first score row, its
+// row count L, the position a0 of its first audio key and the length A of its audio run.  Key a of kv head g of sequence r is K + r * k_seq_stride +
+// g * k_head_stride + (a0 + a) * k_ld.  heads: the launch's n_heads query heads, ascending.  P, Z [n_heads][S][A_max], M [S][A_max] fp32; trace [S][A_max];
+// t_out[rec[s]] = row s's audio index.
+struct AlignArgs {
+    const void* Q; long q_ld;
+    const void* K; long k_ld, k_head_stride, k_seq_stride;
+    const int *qrow, *rseq, *seqp, *heads, *rec;
+    int n_heads, grp, S, n_seq, A_max, L_max, dt;
+    float scale, h_total;
+    float *P, *Z, *M, *t_out;      // Z: the heads' filtered z of one launch, laid out as P
+    signed char* trace;
+};
+void launch_align_probs(const AlignArgs& a, hipStream_t s);     // per (row, head): softmax over the audio run -> P
+void launch_align_reduce(const AlignArgs& a, hipStream_t s);    // per head: normalise over rows, median of 7 -> Z; then M += z / h_total, the launch's heads in order
+void launch_align_dtw(const AlignArgs& a, hipStream_t s);       // per sequence: DTW on -M -> t_out (needs 3 * (L_max + 1) floats of LDS: L_max <= ALIGN_MAX_ROWS)
+#define ALIGN_MAX_ROWS 4000
+#define ALIGN_MAX_HEADS 256
+
 // ---- SONIC_MODE_F32 (test only; f32kind.hip): plain fp32 stages behind the same C ABI ----
 enum { F32_EPI_NONE = 0, F32_EPI_GELU = 1, F32_EPI_RESID = 2 };
 struct F32Gemm {

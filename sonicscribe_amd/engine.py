@@ -284,12 +284,24 @@ class TokenScores(NamedTuple):
     top_ids: np.ndarray
 
 
-def unpack_logprobs(rec, n: int, K: int):
+class AlignedScores(NamedTuple):
+    """TokenScores of an align run (option forced_align): the same three members (`top_logprobs` / `top_ids` are [n, 0] on a handle without
+    top_logprobs) and `times` [n] int32 - t_n, the index into the request's audio-token run at which token n starts (one audio token = 80 ms)."""
+    lp: np.ndarray
+    top_logprobs: np.ndarray
+    top_ids: np.ndarray
+    times: np.ndarray
+
+
+def unpack_logprobs(rec, n: int, K: int, align: bool = False):
     """The first n records of a wide log-probability array (include/sonic_hip.h, option top_logprobs: 1 + 2K floats per token - the emitted token's
     log-probability, the K alternatives', their ids as fp32) -> (lp [n], top_lp [n, K] float32, top_ids [n, K] int32).  K = 0: the records are the
-    log-probabilities themselves, and the result is that float32 array alone - what the wrappers returned before the option existed."""
-    W = 1 + 2 * int(K)
+    log-probabilities themselves, and the result is that float32 array alone - what the wrappers returned before the option existed.  align: the records are an
+    align run's, one float wider (t_n last), and the result is an AlignedScores."""
+    W = 1 + 2 * int(K) + (1 if align else 0)
     r = np.asarray(rec, np.float32).reshape(-1)[: int(n) * W].reshape(int(n), W)
+    if align:        # an align run's records: W = 1 + 2K + 1, the last float is t_n (an index below 2^24: exact in fp32)
+        return AlignedScores(r[:, 0].copy(), r[:, 1:1 + K].copy(), r[:, 1 + K:1 + 2 * K].astype(np.int32), r[:, W - 1].astype(np.int32))
     if K == 0:
         return r[:, 0].copy()
     return TokenScores(r[:, 0].copy(), r[:, 1:1 + K].copy(), r[:, 1 + K:].astype(np.int32))
@@ -331,6 +343,7 @@ class Engine(HooksMixin):
         s.request_bias = bool(getattr(root, "request_bias", False))
         s.sampling = bool(getattr(root, "sampling", False))
         s.forced_parallel = bool(getattr(root, "forced_parallel", False))
+        s.forced_align = bool(getattr(root, "forced_align", False))
         root._slots.append(s)
         return s
 
@@ -526,15 +539,18 @@ class Engine(HooksMixin):
         return (res, logits, self._fetch_logprobs(out_len, out_ld)) if want_logprobs else (res, logits)
 
     def score_batch(self, segments: Sequence[Any], prompts: Sequence[Sequence[int]], targets, req_win: Optional[Sequence[int]] = None, fanout: int = 1,
-                    want_logits: bool = False):
+                    want_logits: bool = False, align: bool = False):
         """Score given continuations in ONE prefill pass (the parallel forced run; needs option forced_parallel on this handle).  targets: one id
         sequence per prompt, or an int array [R][ld] padded with any valid id beyond a sequence's own length when all share a length - sequence r is scored up to
         and including its first EOS id (HF's rule).  fanout = N: the R sequences are R / N audio requests with N candidates each; `segments` / `req_win` then
         describe the R / N audio requests, which go through log-mel, encoder and projector once.  No logits processor is applied: the log-probabilities are those
         of the raw model distribution at temperature 1.  Returns what transcribe_batch(..., want_logprobs=True) returns: (ids list, logits [ld][R][V] or None,
-        per sequence its float32 log-probabilities - with option top_logprobs a TokenScores); the log-probabilities need option token_logprobs (None without)."""
+        per sequence its float32 log-probabilities - with option top_logprobs a TokenScores); the log-probabilities need option token_logprobs (None without).
+        align (needs options forced_align and token_logprobs on this handle): per sequence an AlignedScores, whose `times` are t_n per token."""
         if not getattr(self, "forced_parallel", False):
             raise SonicError("score_batch needs option forced_parallel on this handle (set_option('forced_parallel', 1))")
+        if align and not (getattr(self, "forced_align", False) and getattr(self, "token_logprobs", False)):
+            raise SonicError("score_batch(align=True) needs options forced_align and token_logprobs on this handle (set_option('forced_align', 1))")
         from .scoring import pack_targets
         forced, lens = pack_targets(targets, self.dims.eos_ids, pad_id=0)
         if len(forced) != len(prompts):
@@ -543,18 +559,24 @@ class Engine(HooksMixin):
         self.set_forced_ids(forced)
         try:
             want_lp = bool(getattr(self, "token_logprobs", False))
+            self._lp_align = bool(getattr(self, "forced_align", False))      # (an align handle's parallel run returns the wide records, asked for or not)
             out = self.transcribe_batch(segments, prompts, [int(n) for n in lens], req_win=req_win, want_logits=want_logits, want_logprobs=want_lp)
         finally:
+            self._lp_align = False
             self.set_forced_ids(None)
+        if want_lp and getattr(self, "forced_align", False) and not align:      # the caller asked for scores alone: what a handle without the option returns
+            K = int(getattr(self, "top_logprobs", 0))
+            out = (out[0], out[1], [a.lp if K == 0 else TokenScores(a.lp, a.top_logprobs, a.top_ids) for a in out[2]])
         return out if want_lp else (out[0], out[1], None)
 
     def _fetch_logprobs(self, out_len, out_ld: int) -> list:
         """sonic_fetch_logprobs for the batch whose token counts are out_len: one float32 array per request (entries beyond a row's count are never written);
         with option top_logprobs one TokenScores per request (unpack_logprobs)"""
         K = int(getattr(self, "top_logprobs", 0))
-        lp = np.full((len(out_len), max(1, int(out_ld)) * (1 + 2 * K)), np.nan, np.float32)
+        al = bool(getattr(self, "_lp_align", False))
+        lp = np.full((len(out_len), max(1, int(out_ld)) * (1 + 2 * K + (1 if al else 0))), np.nan, np.float32)
         self._check(self.lib.sonic_fetch_logprobs(self.h, _p(lp), lp.shape[1]))
-        return [unpack_logprobs(lp[r], int(out_len[r]), K) for r in range(len(out_len))]
+        return [unpack_logprobs(lp[r], int(out_len[r]), K, al) for r in range(len(out_len))]
 
     def stage_pcm(self, segments: Sequence[Any], req_win: Optional[Sequence[int]] = None):
         if any(isinstance(s, RingSlice) for s in segments):
@@ -699,6 +721,8 @@ class Engine(HooksMixin):
             self.token_logprobs = bool(value)        # (a slot created from now on copies it, in the library and here)
         if key == "forced_parallel":
             self.forced_parallel = bool(value)       # (likewise; it may also be set on a slot alone)
+        if key == "forced_align":
+            self.forced_align = bool(value)          # (likewise: a parallel run's records then carry t_n)
 
     def set_forced_ids(self, ids):
         """ids: [R][ld] int array (token n of request r) or None to clear; see sonic_set_forced_ids."""

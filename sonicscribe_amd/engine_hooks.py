@@ -49,6 +49,15 @@ class HooksMixin:
         self._check(self.lib.sonic_test_attention(self.h, _p(q), _p(k), _p(v), _p(out), B, Tq, Tk, Hq, Hkv, hd, int(causal)))
         return out
 
+    def test_align(self, q, k):
+        """sonic_test_attention on an align handle (option forced_align): q [B][Tq][Hq][128], k [B][Tk][Hkv][128] -> (M [B][Tq][Tk] float32,
+        t [B][Tq] int32) - the three word-timestamp kernels over all Hq heads, every sequence's audio run being its Tk keys"""
+        q = np.ascontiguousarray(q, np.float32); k = np.ascontiguousarray(k, np.float32)
+        B, Tq, Hq, hd = q.shape; Tk, Hkv = k.shape[1], k.shape[2]
+        out = np.empty((B, Tq, Tk + 1), np.float32)
+        self._check(self.lib.sonic_test_attention(self.h, _p(q), _p(k), None, _p(out), B, Tq, Tk, Hq, Hkv, hd, 0))
+        return out[:, :, :Tk].copy(), out[:, :, Tk].astype(np.int32)
+
     def test_decode_attention(self, q, k, v):
         """q [B][Hq][128], k/v [B][Tk][Hkv][128] -> [B][Hq][128]"""
         q = np.ascontiguousarray(q, np.float32); k = np.ascontiguousarray(k, np.float32); v = np.ascontiguousarray(v, np.float32)

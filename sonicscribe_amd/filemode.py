@@ -114,9 +114,14 @@ class _FileJob:
     """One file on the device: its ring, its plan and its queued decodes."""
 
     def __init__(self, model, audio, vad, vad_enabled: bool, hotwords, max_segment_duration, max_new_tokens: int, filename: str,
-                 sampling_rate: int = SAMPLE_RATE, sequence_bias=None, bad_words_ids=None, hotword_boost=None, temperature=None, seed=None):
+                 sampling_rate: int = SAMPLE_RATE, sequence_bias=None, bad_words_ids=None, hotword_boost=None, temperature=None, seed=None, word_timestamps: bool = False):
         if not hasattr(model, "model"):
             raise RuntimeError("ASR model has been released")
+        # word_timestamps (a model built with timestamps=True; DESIGN.md 6.9): every segment's tokens are aligned on the replica's scoring handle as its record is
+        # made, from the same ring ranges; `words` in the record are on the file's clock (offset by the segment's start)
+        self.word_timestamps = bool(word_timestamps)
+        if self.word_timestamps:
+            model._check_timestamps()
         # the file's temperature (a float) or fallback ladder (a sequence) and seed (a model built with sampling=True; ASRModel._request_sampling): every segment
         # of the file is decoded with them, each as its own request (DESIGN.md 6.6)
         self.samp = model._request_sampling(temperature, seed) if hasattr(model, "_request_sampling") else None
@@ -157,7 +162,11 @@ class _FileJob:
         except BaseException:
             self.release()
             raise
+        if self.word_timestamps and self.samp is not None and self.samp[1]:
+            self.release()
+            raise ValueError("word_timestamps is not supported with a fallback ladder of temperatures in file mode (the ladder's futures carry texts, not tokens): pass one temperature")
         self.futures: List[Any] = []
+        self.requests: List[Any] = []          # word_timestamps: per segment (windows, prompt, samples), None for a segment that was refused
         self.segments: List[Dict[str, Any]] = []
         self.summary: List[Dict[str, Any]] = []
 
@@ -177,10 +186,16 @@ class _FileJob:
             if n < int(MIN_SEGMENT_S * self.sr):
                 # the reference's segment_error for this case (main.py:606-607); its keys, this package's own wording of the text
                 self.futures.append(ValueError(f"segment {seg['segment_index']} has too few samples: {n}"))
+                self.requests.append(None)
                 continue
             # > 30 s: one request of several windows sharing one peak, as transcribe() makes it (frontend.split_windows)
             windows = [self.ring.slice(self.first + a + s, e - s) for s, e in frontend.split_windows(n, m.dims)]
             n_audio, _ = frontend.request_audio_tokens(n, m.dims)
+            self.requests.append((windows, m.prompt.build(instruction, n_audio), n))
+            if self.samp is not None and self.word_timestamps:      # one temperature: the scheduler's own future carries the tokens
+                self.futures.append(m._dispatcher.submit(windows, m.prompt.build(instruction, n_audio), self.max_new, replica=self.replica, sampling=(self.samp[0][0], self.samp[2]),
+                                                         **({"bias": self.bias} if self.bias else {})))
+                continue
             if self.samp is not None:              # (a future of the TEXT: the ladder judges texts; records() takes either)
                 self.futures.append(m._dispatch(windows, m.prompt.build(instruction, n_audio), self.max_new, False, self.bias, self.samp, replica=self.replica))
                 continue
@@ -195,16 +210,24 @@ class _FileJob:
                    "config": {"vad_enabled": self.vad_enabled, "hotwords": hot, "max_segment_duration": self.max_seg}, "timestamp": time.time()}
             yield {"type": "segments_summary", "segments": self.summary, "total_segments": total_segments, "timestamp": time.time()}
             ok = bad = 0
-            for seg, fut in zip(self.segments, self.futures):
+            for i_seg, (seg, fut) in enumerate(zip(self.segments, self.futures)):
                 try:
                     if isinstance(fut, Exception):
                         raise fut
                     got = fut.result()
                     text = got if isinstance(got, str) else self.model.prompt.decode(got).strip()
+                    words = None
+                    if self.word_timestamps:
+                        from . import scoring as scoring_
+                        wins, prompt, n = self.requests[i_seg]
+                        al = self.model._align_items([(wins, prompt, scoring_.with_eos([int(t) for t in got], self.model._eos_ids(), True), n)], replica=self.replica)[0]
+                        words = [w.as_dict() for w in al.shifted(seg["start_time"]).words]
                     rec = {"type": "segment_result", "segment_index": seg["segment_index"], "original_index": seg["original_index"],
                            "start_time": round(seg["start_time"], 3), "end_time": round(seg["end_time"], 3), "duration": round(seg["duration"], 3),
                            "text": text, "processing_time": 0, "is_long_segment": seg["is_long_segment"], "hotwords_used": hot,
                            "timestamp": time.time()}
+                    if words is not None:
+                        rec["words"] = words
                     ok += 1
                 except Exception as ex:
                     rec = {"type": "segment_error", "segment_index": seg["segment_index"], "original_index": seg["original_index"],
@@ -273,10 +296,11 @@ def _detect(vad, jobs: Sequence[_FileJob]) -> List[Any]:
 
 def transcribe_file(model, audio, vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                     max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filename: str = "",
-                    sampling_rate: int = SAMPLE_RATE, sequence_bias=None, bad_words_ids=None, hotword_boost=None, temperature=None, seed=None) -> Iterator[Dict[str, Any]]:
+                    sampling_rate: int = SAMPLE_RATE, sequence_bias=None, bad_words_ids=None, hotword_boost=None, temperature=None, seed=None,
+                    word_timestamps: bool = False) -> Iterator[Dict[str, Any]]:
     """Generator of the reference's file-mode records for one file (see ASRModel.transcribe_file)."""
     job = _FileJob(model, audio, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filename, sampling_rate, sequence_bias, bad_words_ids, hotword_boost,
-                   temperature, seed)
+                   temperature, seed, word_timestamps)
     try:
         ts = vad.detect_voice_activity_ring(job.ring, job.first, job.total)[0] if job.wants_vad else None
         job.plan(ts)
@@ -290,7 +314,7 @@ def transcribe_file(model, audio, vad, vad_enabled: bool = True, hotwords: Optio
 def transcribe_files(model, audios: Sequence[Any], vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                      max_segment_duration: Optional[float] = None, max_new_tokens: int = 256,
                      filenames: Optional[Sequence[str]] = None, sampling_rate: int = SAMPLE_RATE, sequence_bias=None, bad_words_ids=None,
-                     hotword_boost=None, temperature=None, seed=None) -> List[FileRecords]:
+                     hotword_boost=None, temperature=None, seed=None, word_timestamps: bool = False) -> List[FileRecords]:
     """One record iterator per file; the VAD of all files runs in one device call and every file's segments are queued before the call
     returns.  Each iterator must be exhausted or closed (its ring lives until then)."""
     names = list(filenames) if filenames is not None else [""] * len(audios)
@@ -298,7 +322,7 @@ def transcribe_files(model, audios: Sequence[Any], vad, vad_enabled: bool = True
     try:
         for a, name in zip(audios, names):
             jobs.append(_FileJob(model, a, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, name, sampling_rate, sequence_bias, bad_words_ids, hotword_boost,
-                                 temperature, seed))
+                                 temperature, seed, word_timestamps))
         for job, ts in zip(jobs, _detect(vad, jobs)):
             job.plan(ts)
         for job in jobs:
