@@ -96,7 +96,7 @@ enum { SONIC_MODE_NATIVE = 0 /* bf16, asr.py mode="native" */, SONIC_MODE_INT8 =
         * "within 1e-3 on logits" literally on the GPU (tests/test_gpu_fp32_mode.py against tests/golden/\*_fp32.npz); the product kinds keep the
         * reference's bf16 / fp16 op-boundary roundings and cannot.  No slots, no continuous decoding, no graphs; speed is irrelevant. */
        SONIC_MODE_F32 = 3 };
-enum { SONIC_DTYPE_F32 = 0, SONIC_DTYPE_BF16 = 1 };
+enum { SONIC_DTYPE_F32 = 0, SONIC_DTYPE_BF16 = 1, SONIC_DTYPE_I32 = 2 /* grammars only: sonic_load_tensor "grammar:<id>" */ };
 
 /* Model dimensions (defaults: HF:configuration_glmasr.py:44-54,86-103). */
 typedef struct {
@@ -289,6 +289,38 @@ SONIC_API int sonic_set_request_bias(sonic_engine* e, const int32_t* seq_ids, co
  *       on success and on failure alike; a batch without values is greedy.  SONIC_ERR_INVALID, nothing clamped: the option is off (the message names it), a
  *       temperature that is neither 0 nor in [1e-3, 100] (NaN included); at the prefill, an R that is not the batch's. */
 SONIC_API int sonic_set_request_sampling(sonic_engine* e, const float* temperature, const uint64_t* seed, int R);
+/* Grammar-constrained decoding: a request's transcript restricted to the paths of a deterministic token automaton - HF's prefix_allowed_tokens_fn
+ * (PrefixConstrainedLogitsProcessor), Vosk's `grammar`, the strict mode of a phrase list - with the mask and the state transition inside the greedy kernel.  The
+ * feature adds no entry point: a grammar is loaded as a tensor, everything else is an option.
+ * A grammar is an automaton in CSR form: node_off[N + 1], edge_tok[E], edge_next[E]; node 0 is the start node; the edges of node n are node_off[n] .. node_off[n + 1],
+ * sorted by token id, strictly ascending.  EOS is an ordinary edge, added where a transcript may end: there is no accept flag.
+ *   Per row one state word: -1 the row is free (no grammar: the kernel behaves as without the option), n >= 0 it is at node n, -2 it has left its grammar.
+ *   A step of a running row at node n: every id that is not an edge token of n scores -inf, behind the request bias and the repetition penalty, folded into the
+ *   bans of the n-gram guard and the suppress list (HF's chain SequenceBias -> RepetitionPenalty -> NoRepeatNGram -> NoBadWords -> PrefixConstrained ->
+ *   SuppressTokens: bans commute, so the fold gives HF's tokens); then temperature and noise for a sampled row; compare, log-probabilities and alternatives run over
+ *   the masked scores.  The emitted token - argmax, sample or forced id - moves the state to its edge's `next` if n has an edge for it, else to -2 (a forced id
+ *   outside the grammar; token 0, which a row emits when the guards have banned every allowed id).  A row at -2 allows only the handle's EOS ids: it ends on
+ *   its next step.  step_logits stay raw; a finished row changes nothing.
+ *   create: sonic_load_tensor with the name "grammar:<id>" (id 1 .. 65535, the caller's choice), dtype SONIC_DTYPE_I32, ndim 1 and the words
+ *       [N | E | node_off | edge_tok | edge_next], on a finalized engine; it lands on the weight owner, is shared by all of its handles and by any number of requests,
+ *       is counted by the owner's sonic_memory_info and does not wait for a decoding batch.  SONIC_ERR_INVALID, nothing truncated, the calling thread's last error
+ *       (engine NULL) naming the cause: node_off[0] != 0, node_off not monotone, node_off[N] != E, a node without an edge, a token id outside [0, vocab) or equal to the
+ *       audio placeholder, a `next` outside [0, N), edges of a node not sorted and unique, N outside 1 .. 65536, E outside 1 .. 1048576, a length that is not
+ *       2 + N + 1 + 2E, an id that is taken, weights that are not finalized.
+ *   destroy: the same call with shape {0}.  SONIC_ERR_INVALID ("in use") while a staged or running request refers to the grammar - a reference is taken when a
+ *       request is staged or submitted; it moves with the row at a splice (the source row is free afterwards) and is dropped when the row is fetched from a
+ *       continuous loop, when a batch whose every row has ended is fetched, when the handle's next prefill overwrites the row, or with its handle.  sonic_destroy of the owner frees what is left.
+ *   option "grammar" (sonic_set_option): on the owner before its slots are created (they copy it) and after option token_logprobs (SONIC_ERR_INVALID naming
+ *       token_logprobs otherwise); allocates the rows' history, if nothing else has, their references and state words (counted by sonic_memory_info); refused while
+ *       the handle has work in hand.  sonic_splice_rows copies a row's reference and state and refuses handles whose options differ.
+ *   options "request_grammar_begin" = R, then "request_grammar" = request << 16 | id per constrained request: the grammars of the R requests of the NEXT prefill on
+ *       this handle (the entry points sonic_set_request_bias names); that prefill consumes them on success and on failure alike and starts every constrained row at
+ *       node 0.  SONIC_ERR_INVALID: option grammar is off (the message names it), an id that is no live grammar of the handle's weight owner; at the prefill, an R
+ *       that is not the batch's.  A scoring handle (option forced_parallel) refuses staged grammars, and consumes them, as it does bias tables.
+ *   dispatcher: sonic_load_tensor with the name "grammar.dispatch:<id>" (shape {0}; id 0 disarms) on any handle of the dispatcher's weight owner arms the calling
+ *       thread's NEXT sonic_dispatch_submit, _bias or _sampled with that grammar; the submit takes it whatever becomes of it; SONIC_ERR_INVALID unless every handle
+ *       of the dispatcher has option grammar on.  The call takes no engine lock (a decoding handle holds its own for a chunk at a time).  The request holds a
+ *       reference until it completes. */
 /* the values in force on this handle; at most `cap` ids are copied to suppress, *n_suppress is their full count (any pointer may be NULL) */
 SONIC_API int sonic_get_generation(sonic_engine* e, float* repetition_penalty, int32_t* no_repeat_ngram_size, int32_t* suppress, int cap, int32_t* n_suppress);
 /* sonic_run_staged without blocking the caller: the arguments are copied, a worker thread owned by the handle runs the batch, the call
@@ -524,6 +556,9 @@ SONIC_API int sonic_test_greedy_sample(sonic_engine* e, const float* slabs, int 
                                        const int32_t* seq_ids, const int32_t* seq_off, const float* bias, const int32_t* req_off,
                                        const float* temperature, const uint64_t* seed, const int32_t* step,
                                        int32_t* tok_out, float* logits_out, float* lp_out, float* noise_out);
+/* the grammar instantiations (greedy_kernel<T, true, true, BIAS, SAMPLE, TOPK, true>) ride on the three hooks above: an automaton armed on the handle - sonic_load_tensor
+ * "grammar.hook:<V>" (the packed words of a grammar, validated against V), then options hook_grammar_state = row << 20 | (state + 2) and hook_grammar_eos = id - is taken
+ * by the next of these launches that has histories and lp_out, in the handle's own type; sonic_debug_read "hook_grammar_state" returns the rows' states afterwards. */
 SONIC_API int sonic_test_attention(sonic_engine* e, const float* q, const float* k, const float* v, float* out,
                          int B, int Tq, int Tk, int Hq, int Hkv, int hd, int causal);
 SONIC_API int sonic_test_decode_attention(sonic_engine* e, const float* q, const float* k, const float* v, float* out,

@@ -91,12 +91,13 @@ class Transcription:
     descending, id ascending) with their log-probabilities - OpenAI's top_logprobs; places beyond the ids with a finite score hold (-1, -inf).  They are what
     the model scored, whatever token was emitted: on a greedy request column 0 is the token itself."""
     __slots__ = ("text", "token_ids", "token_logprobs", "avg_logprob", "temperature", "compression_ratio", "attempts", "top_token_ids", "top_logprobs",
+                 "grammar_status",      # a request decoded under a grammar: grammar.Grammar.walk over token_ids - "accepted", "incomplete" or "left"; None without
                  "words", "token_start", "token_end")      # word_timestamps=True (ASRModel(timestamps=True); DESIGN.md 6.9): timestamps.Word list and the tokens' times (EOS dropped); None without
 
     def __init__(self, text: str, token_ids, token_logprobs, temperature: float = 0.0):
         from .fallback import compression_ratio
         self.text = text
-        self.words = self.token_start = self.token_end = None
+        self.words = self.token_start = self.token_end = self.grammar_status = None
         self.temperature, self.compression_ratio, self.attempts = float(temperature), compression_ratio(text), 1
         self.token_ids = np.asarray(token_ids, np.int32)
         top_lp = top_ids = None
@@ -126,7 +127,7 @@ def check_top_logprobs(top_logprobs, token_logprobs: bool, bulk: bool) -> int:
     return K
 
 
-def _text_future(inner: "Future", decode, detailed: bool = False, temperature: float = 0.0) -> "Future[str]":
+def _text_future(inner: "Future", decode, detailed: bool = False, temperature: float = 0.0, grammar=None) -> "Future[str]":
     """Future of the transcript behind a dispatcher future of token ids.  Cancelling it (a session that went away) cancels the queued
     request as well, so it never reaches the device.  detailed: the inner future carries (ids, log-probabilities), the result is a Transcription."""
     out: "Future[str]" = Future()
@@ -137,7 +138,10 @@ def _text_future(inner: "Future", decode, detailed: bool = False, temperature: f
         try:
             if detailed:
                 ids, lps = f.result()
-                out.set_result(Transcription(decode(ids).strip(), ids, lps, temperature))
+                tr = Transcription(decode(ids).strip(), ids, lps, temperature)
+                if grammar is not None:
+                    tr.grammar_status = grammar.grammar.walk(tr.token_ids)
+                out.set_result(tr)
             else:
                 out.set_result(decode(f.result()).strip())
         except BaseException as ex:
@@ -216,7 +220,7 @@ class AudioStream:
 
     def submit_samples(self, first: int, n: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None, detailed: bool = False,
                        sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature: Optional[float] = None,
-                       seed: Optional[int] = None, word_timestamps: bool = False) -> "Future[str]":
+                       seed: Optional[int] = None, word_timestamps: bool = False, grammar=None) -> "Future[str]":
         """Transcribe ring samples [first, first + n) (the >30 s split of connection_manager.py:206-214 cuts at byte offsets, not chunks).
         detailed (a model built with token_logprobs=True): the future gives a Transcription instead of the text.  temperature / seed (a model built with
         sampling=True): one attempt at that temperature - a float only, stream decodes take no fallback ladder."""
@@ -226,17 +230,18 @@ class AudioStream:
         m._check_detailed(detailed)
         bias = m._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost)
         samp = m._request_sampling(temperature, seed, ladder_ok=False)
+        gram = m._request_grammar(grammar)
         windows = [self.ring.slice(first + s, e - s) for s, e in frontend.split_windows(n, m.dims)]
         n_audio, _ = frontend.request_audio_tokens(n, m.dims)
         prompt = m.prompt.build(frontend.build_instruction(hotwords), n_audio)
-        return m._dispatch(windows, prompt, int(max_new_tokens), detailed, bias, samp, replica=self.replica)
+        return m._dispatch(windows, prompt, int(max_new_tokens), detailed, bias, samp, gram, replica=self.replica)
 
     def submit_chunks(self, start_chunk_id: int, end_chunk_id: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None,
                       detailed: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
-                      temperature: Optional[float] = None, seed: Optional[int] = None, word_timestamps: bool = False) -> "Future[str]":
+                      temperature: Optional[float] = None, seed: Optional[int] = None, word_timestamps: bool = False, grammar=None) -> "Future[str]":
         """Transcribe chunks start..end inclusive (audio_manager.py:76-79 get_chunks_by_range + :115-123 concatenation)."""
         first, n = self.chunk_range_samples(start_chunk_id, end_chunk_id)
-        return self.submit_samples(first, n, max_new_tokens, hotwords, detailed, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, word_timestamps)
+        return self.submit_samples(first, n, max_new_tokens, hotwords, detailed, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, word_timestamps, grammar)
 
     async def transcribe_chunks(self, start_chunk_id: int, end_chunk_id: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None) -> str:
         return await asyncio.wrap_future(self.submit_chunks(start_chunk_id, end_chunk_id, max_new_tokens, hotwords))
@@ -254,7 +259,7 @@ class ASRModel:
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None,
                  request_bias: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: float = 0.0,
                  sampling: bool = False, temperature=0.0, seed: int = 0, compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
-                 scoring: bool = False, timestamps: bool = False, alignment_heads=None,
+                 scoring: bool = False, timestamps: bool = False, alignment_heads=None, grammar: bool = False,
                  _dims: Optional[ModelDims] = None,
                  _synthetic_seed: Optional[int] = None, _allow_synthetic_prompt: bool = False, _options: Optional[Dict[str, int]] = None,
                  _engine_mode: Optional[int] = None):
@@ -267,7 +272,9 @@ class ASRModel:
         ladder), `seed` and the two thresholds of the ladder here are the defaults of every call.  `scoring` (needs token_logprobs=True): score() / score_batch() give the log-probability of transcripts the caller
         brings, in one prefill pass per run on a handle of their own per replica; off, no such handle exists.  `timestamps` (needs scoring=True): align() and
         word_timestamps=True give the time at which every token and word was spoken, from the decoder's attention onto the audio on that scoring handle (DESIGN.md 6.9);
-        `alignment_heads`: the [layer, head] pairs to read (None: the `alignment_heads` entry of the checkpoint's generation_config.json, else every head of the last half of the layers).  The arguments with a leading underscore are not part of the
+        `grammar` (needs token_logprobs=True; not with bulk=True): requests may be
+        restricted to the transcripts of a grammar - compile_grammar() of a phrase list or of a grammar.Grammar, passed as `grammar=` of the transcribe calls; the mask and
+        the state run inside the greedy kernel.  `alignment_heads`: the [layer, head] pairs to read (None: the `alignment_heads` entry of the checkpoint's generation_config.json, else every head of the last half of the layers).  The arguments with a leading underscore are not part of the
         supported surface: they exist for the test-suite and the benchmark and may change without notice.  `_engine_mode` in particular (an engine.MODE_*
         value in place of the one `mode` selects) is unsupported outside the tests: MODE_F32 has no slots, so it needs slots=1, continuous=False."""
         if mode not in ["native", "int8"]:
@@ -285,6 +292,14 @@ class ASRModel:
             raise ValueError("sampling=True needs token_logprobs=True: the sampling kernels are log-probability kernels, and the fallback ladder reads avg_logprob")
         if self.sampling and bool(bulk):
             raise ValueError("sampling is not supported with bulk=True: the bulk pipeline carries no per-request values")
+        # grammar: requests may be restricted to the transcripts of a grammar made by compile_grammar() - a phrase list, or any token automaton (grammar.py;
+        # DESIGN.md 6.10; engine option of the same name, behind token_logprobs and before the slots exist)
+        self.grammar = bool(grammar)
+        if self.grammar and not token_logprobs:
+            raise ValueError("grammar=True needs token_logprobs=True: the grammar kernels are log-probability kernels (ASRModel(..., token_logprobs=True, grammar=True))")
+        if self.grammar and bool(bulk):
+            raise ValueError("grammar is not supported with bulk=True: the bulk pipeline carries no per-request grammar state")
+        self._grammars: List[Any] = []
         self.scoring = bool(scoring)
         if self.scoring and not token_logprobs:
             raise ValueError("scoring=True needs token_logprobs=True: a score is the candidates' token log-probabilities (ASRModel(..., token_logprobs=True, scoring=True))")
@@ -377,6 +392,9 @@ class ASRModel:
         if self.sampling:
             for eng in self.models:
                 eng.set_option("sampling", 1)
+        if self.grammar:
+            for eng in self.models:
+                eng.set_option("grammar", 1)
         self._retrier = fallback.Retrier()
         self.model = self.models[0]                  # main.py:84-86 checks and deletes `.model`
         # continuous: `decoders` handles per replica run a greedy loop over max_batch rows each, the other handles prefill (>= 1).  Streaming:
@@ -478,7 +496,42 @@ class ASRModel:
             raise ValueError("stream decodes take one temperature (a float), not a fallback ladder")
         return ts, ladder, sampling_.check_seed(self._default_seed if seed is None else seed)
 
-    def _dispatch(self, windows, prompt, max_new: int, detailed: bool, bias, samp, **route) -> "Future":
+    def compile_grammar(self, phrases_or_grammar, repeat: bool = False):
+        """A grammar for `grammar=` of the transcribe calls: a grammar.Grammar, or a list of phrases (grammar.Grammar.from_phrases: each phrase, cleaned as hotwords
+        are, as it stands and with one leading space, ending in EOS; repeat=True: any number of phrases in a row; needs the checkpoint's tokenizer).  Returns a
+        grammar.CompiledGrammar that lives on every replica and serves any number of requests; it is closed with the model, or earlier by its close() (refused while
+        a request still refers to it).  Needs a model built with grammar=True."""
+        from . import grammar as grammar_
+        if not hasattr(self, "model"):
+            raise RuntimeError("ASR model has been released")
+        if not getattr(self, "grammar", False):
+            raise ValueError("compile_grammar needs a model built with grammar=True (ASRModel(..., token_logprobs=True, grammar=True))")
+        g = phrases_or_grammar
+        if not isinstance(g, grammar_.Grammar):
+            if not isinstance(self.prompt, HFPrompt):
+                raise ValueError("a phrase list needs a tokenizer (a checkpoint with its processor): the synthetic prompt has none - pass a grammar.Grammar (Grammar.from_token_sequences)")
+            tok = self.prompt.processor.tokenizer
+            g = grammar_.Grammar.from_phrases(list(g), lambda t: tok.encode(t, add_special_tokens=False), self._eos_ids(), repeat=repeat,
+                                              vocab=self.dims.vocab, audio_token_id=self.dims.audio_token_id)
+        c = grammar_.CompiledGrammar(g, self.models)
+        self._grammars.append(c)
+        return c
+
+    def _request_grammar(self, grammar):
+        """One call's grammar: None, or the CompiledGrammar.  ValueError naming grammar when the model was built without the option, and for anything else than a
+        compile_grammar() result."""
+        if grammar is None:
+            return None
+        from . import grammar as grammar_
+        if not getattr(self, "grammar", False):
+            raise ValueError("grammar= needs a model built with grammar=True (ASRModel(..., token_logprobs=True, grammar=True))")
+        if getattr(self, "bulk", False):
+            raise ValueError("a grammar is not supported with bulk=True")
+        if not isinstance(grammar, grammar_.CompiledGrammar):
+            raise ValueError("grammar= takes what compile_grammar() returned (a grammar.CompiledGrammar)")
+        return grammar
+
+    def _dispatch(self, windows, prompt, max_new: int, detailed: bool, bias, samp, gram=None, **route) -> "Future":
         """One request on the scheduler -> a future of its text (detailed: its Transcription).  samp (from _request_sampling): None, one attempt at a temperature,
         or the fallback ladder - each attempt a new request for the same windows, prompt, table and seed; the future resolves after the last one.  Retries
         are submitted by the model's worker thread, never by a completion callback and never by the caller (fallback.py)."""
@@ -486,14 +539,16 @@ class ASRModel:
         kw = dict(route)
         if bias:
             kw["bias"] = bias
+        if gram is not None:
+            kw["grammar"] = gram
         if samp is None:
-            return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=detailed, **kw), self.prompt.decode, detailed)
+            return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=detailed, **kw), self.prompt.decode, detailed, grammar=gram)
         ts, ladder, seed = samp
         if not ladder:
-            return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=detailed, sampling=(ts[0], seed), **kw), self.prompt.decode, detailed, ts[0])
+            return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=detailed, sampling=(ts[0], seed), **kw), self.prompt.decode, detailed, ts[0], grammar=gram)
 
         def one(temperature, seed):
-            return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=True, sampling=(temperature, seed), **kw), self.prompt.decode, True, temperature)
+            return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=True, sampling=(temperature, seed), **kw), self.prompt.decode, True, temperature, grammar=gram)
         policy = fallback.FallbackPolicy(ts, self.compression_ratio_threshold, self.logprob_threshold)
         fut = fallback.decode_with_fallback(one, policy, seed, retrier=self._retrier)
         if detailed:
@@ -518,13 +573,14 @@ class ASRModel:
 
     def submit(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None,
                session: Optional[str] = None, detailed: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
-               temperature=None, seed: Optional[int] = None, word_timestamps: bool = False) -> "Future[str]":
+               temperature=None, seed: Optional[int] = None, word_timestamps: bool = False, grammar=None) -> "Future[str]":
         """Non-blocking form of transcribe(): queues the request on a replica and returns a Future of the transcript.  `session`
         (e.g. the WebSocket client id) keeps a session's decodes on one GPU.  detailed (a model built with token_logprobs=True): the future
         gives a Transcription - text, token_ids, token_logprobs, avg_logprob - instead of the text.  sequence_bias / bad_words_ids / hotword_boost (a model
         built with request_bias=True): this request's own table, on top of the constructor's defaults (_request_bias).  temperature / seed (a model built with
         sampling=True): a float decodes once at that temperature, a sequence is the fallback ladder - the future resolves after its last attempt, and this
-        thread never waits for one (_dispatch)."""
+        thread never waits for one (_dispatch).  grammar (a model built with grammar=True): what compile_grammar() returned - the transcript is one of its paths;
+        a detailed result carries `grammar_status`."""
         if not hasattr(self, "model"):
             raise RuntimeError("ASR model has been released")
         if word_timestamps:
@@ -532,9 +588,10 @@ class ASRModel:
         self._check_detailed(detailed)
         bias = self._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost)
         samp = self._request_sampling(temperature, seed)
+        gram = self._request_grammar(grammar)
         pcm, windows, n_audio = self._prepare(audio_tensor, sampling_rate)
         prompt = self.prompt.build(frontend.build_instruction(hotwords), n_audio)
-        return self._dispatch(windows, prompt, int(max_new_tokens), detailed, bias, samp, session=session)
+        return self._dispatch(windows, prompt, int(max_new_tokens), detailed, bias, samp, gram, session=session)
 
     def open_stream(self, session: str, buffer_seconds: float = 30.0, margin_seconds: float = 10.0, sampling_rate: int = 16000) -> AudioStream:
         """A streaming session whose audio stays on the device (config.py:25 MAX_AUDIO_BUFFER_SECONDS = 30): chunks are appended to a
@@ -549,16 +606,18 @@ class ASRModel:
     async def transcribe_async(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128,
                                hotwords: Optional[List[str]] = None, session: Optional[str] = None, detailed: bool = False,
                                sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None, seed: Optional[int] = None,
-                               word_timestamps: bool = False) -> str:
+                               word_timestamps: bool = False, grammar=None) -> str:
         """Awaitable transcribe() for the asyncio callers (connection_manager.py:127-245): the event loop is not blocked while the
         device works, so all sessions' partial and final decodes can be in flight (and batched) together."""
-        return await asyncio.wrap_future(self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, session, detailed, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, word_timestamps))
+        return await asyncio.wrap_future(self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, session, detailed, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, word_timestamps, grammar))
 
     def transcribe(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128,
                    hotwords: Optional[List[str]] = None, return_debug_info: bool = False,
                    sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None, seed: Optional[int] = None,
-                   word_timestamps: bool = False) -> Union[str, Dict[str, Any]]:
-        """word_timestamps (a model built with timestamps=True): the request is decoded as always, then its tokens are aligned on the scoring
+                   word_timestamps: bool = False, grammar=None) -> Union[str, Dict[str, Any]]:
+        """grammar (a model built with grammar=True): what compile_grammar() returned; the debug dictionary gains `grammar_status` (grammar.Grammar.walk over
+        the returned ids: "accepted", "incomplete" at a budget that ended inside the grammar, "left").
+        word_timestamps (a model built with timestamps=True): the request is decoded as always, then its tokens are aligned on the scoring
         handle - the audio is encoded a second time there.  With return_debug_info the dictionary gains `words` (word, start, end, probability), `token_start`
         and `token_end` (seconds, EOS dropped); without, the call returns the Transcription, which carries the same members."""
         if not hasattr(self, "model"):
@@ -569,7 +628,7 @@ class ASRModel:
         try:
             want = bool((return_debug_info or word_timestamps) and getattr(self, "token_logprobs", False))
             res = self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, detailed=want, sequence_bias=sequence_bias, bad_words_ids=bad_words_ids,
-                              hotword_boost=hotword_boost, temperature=temperature, seed=seed).result()
+                              hotword_boost=hotword_boost, temperature=temperature, seed=seed, grammar=grammar).result()
             det, transcript = (res, res.text) if want else (None, res)
             if word_timestamps:
                 self._attach_alignment([audio_tensor], [det], sampling_rate, hotwords)
@@ -587,6 +646,8 @@ class ASRModel:
                         info.update({"top_token_ids": det.top_token_ids, "top_logprobs": det.top_logprobs})
                     if getattr(self, "sampling", False):             # a sampling model: what the transcript was decoded at, and the ladder's other measure
                         info.update({"temperature": det.temperature, "compression_ratio": det.compression_ratio})
+                    if grammar is not None:
+                        info["grammar_status"] = det.grammar_status
                     if word_timestamps:
                         info.update({"words": [w.as_dict() for w in det.words], "token_start": det.token_start, "token_end": det.token_end})
                 return info
@@ -601,15 +662,20 @@ class ASRModel:
 
     def transcribe_batch(self, audios: Sequence[Any], sampling_rate: int = 16000, max_new_tokens: Union[int, Sequence[int]] = 128,
                          hotwords: Optional[List[str]] = None, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
-                         temperature=None, seed: Optional[int] = None, word_timestamps: bool = False) -> List[str]:
+                         temperature=None, seed: Optional[int] = None, word_timestamps: bool = False, grammar=None) -> List[str]:
         """Batched extension (the reference is B=1 per call): one device batch, per-segment results identical to transcribe().  temperature / seed: every
         segment is decoded with them (a sequence: every segment goes down its own ladder, as independent requests on the scheduler).  word_timestamps (a model
-        built with timestamps=True): every audio is decoded as its own request, then all are aligned together; the result is a list of Transcription."""
+        built with timestamps=True): every audio is decoded as its own request, then all are aligned together; the result is a list of Transcription.
+        grammar (a model built with grammar=True): one compile_grammar() result for every audio, or a sequence with one (or None) per audio."""
+        grams = list(grammar) if isinstance(grammar, (list, tuple)) else [grammar] * len(audios)
+        if len(grams) != len(audios):
+            raise ValueError(f"{len(audios)} audios but {len(grams)} grammars")
+        grams = [self._request_grammar(g) for g in grams]
         if word_timestamps:
             self._check_timestamps()
             mn_ = [int(max_new_tokens)] * len(audios) if isinstance(max_new_tokens, int) else [int(x) for x in max_new_tokens]
             futs_ = [self.submit(a, sampling_rate, mn_[i], hotwords, detailed=True, sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotword_boost=hotword_boost,
-                                 temperature=temperature, seed=seed) for i, a in enumerate(audios)]
+                                 temperature=temperature, seed=seed, grammar=grams[i]) for i, a in enumerate(audios)]
             dets = [f.result() for f in futs_]
             self._attach_alignment(list(audios), dets, sampling_rate, hotwords)
             return dets
@@ -627,13 +693,16 @@ class ASRModel:
             req_win.append(len(segs))
             prompts.append(self.prompt.build(instruction, n_audio))
         if samp is not None and samp[1]:
-            futs = [self._dispatch(segs[req_win[i]:req_win[i + 1]], prompts[i], mn[i], False, bias, samp) for i in range(len(audios))]
+            futs = [self._dispatch(segs[req_win[i]:req_win[i + 1]], prompts[i], mn[i], False, bias, samp, grams[i]) for i in range(len(audios))]
             return [f.result() for f in futs]
         if len(self.models) == 1 and not self.continuous:
+            if any(g is not None for g in grams):
+                kw["request_grammar"] = [None if g is None else g.on(self.model) for g in grams]
             ids, _ = self.model.transcribe_batch(segs, prompts, mn, req_win=req_win, **kw)
         else:            # independent segments: spread over the replicas (least-loaded placement), results in input order
             skw = {"sampling": kw["request_sampling"][0]} if "request_sampling" in kw else {}
-            futs = [self._dispatcher.submit(segs[req_win[i]:req_win[i + 1]], prompts[i], mn[i], **({"bias": bias} if bias else {}), **skw) for i in range(len(audios))]
+            futs = [self._dispatcher.submit(segs[req_win[i]:req_win[i + 1]], prompts[i], mn[i], **({"bias": bias} if bias else {}), **({"grammar": grams[i]} if grams[i] is not None else {}), **skw)
+                    for i in range(len(audios))]
             ids = [f.result() for f in futs]
         return [self.prompt.decode(i).strip() for i in ids]
 
@@ -770,7 +839,7 @@ class ASRModel:
     def transcribe_file(self, audio, vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                         max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filename: str = "", sampling_rate: int = 16000,
                         sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None, seed: Optional[int] = None,
-                        word_timestamps: bool = False):
+                        word_timestamps: bool = False, grammar=None):
         """The body of the reference's /transcribe/file endpoint (main.py:193-649) as a generator of its records (dicts with the
         reference's keys: initialization, segments_summary, segment_result / segment_error in segment order, final_summary).  `audio`:
         mono int16 PCM at `sampling_rate`, or the reference's float tensor [1, N] of int16 / 32768 values; `vad`: a vad.VADProcessor.  The
@@ -780,17 +849,17 @@ class ASRModel:
         from . import filemode
         return filemode.transcribe_file(self, audio, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filename, sampling_rate,
                                         sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotword_boost=hotword_boost, temperature=temperature, seed=seed,
-                                        word_timestamps=word_timestamps)
+                                        word_timestamps=word_timestamps, grammar=grammar)
 
     def transcribe_files(self, audios: Sequence[Any], vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                          max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filenames: Optional[Sequence[str]] = None,
                          sampling_rate: int = 16000, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None,
-                         seed: Optional[int] = None, word_timestamps: bool = False):
+                         seed: Optional[int] = None, word_timestamps: bool = False, grammar=None):
         """transcribe_file for several files: all VAD passes in one device call, one record iterator per file (filemode.transcribe_files)."""
         from . import filemode
         return filemode.transcribe_files(self, audios, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filenames, sampling_rate,
                                          sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotword_boost=hotword_boost, temperature=temperature, seed=seed,
-                                         word_timestamps=word_timestamps)
+                                         word_timestamps=word_timestamps, grammar=grammar)
 
     def get_model_info(self) -> Dict[str, Any]:
         """asr.py:490-513: the reference's keys for a GPU device (`cuda_version` carries the HIP runtime version: torch.version.cuda is
@@ -804,6 +873,7 @@ class ASRModel:
         info.update({"engine": "sonicscribe_amd/gfx950", "replicas": len(self.__dict__.get("models", [])), "slots_per_replica": self.__dict__.get("slots", 1), "continuous": self.__dict__.get("continuous", False), "bulk": self.__dict__.get("bulk", False),
                      "weights_mb": self.model.weight_bytes() / 1024 ** 2 if hasattr(self, "model") else 0.0})
         info["scoring"] = bool(self.__dict__.get("scoring", False))
+        info["grammar"] = bool(self.__dict__.get("grammar", False))
         info["timestamps"] = bool(self.__dict__.get("timestamps", False))
         g = self.__dict__.get("generation_guards")
         if g is not None:                            # the logits processors in force: the checkpoint's generation_config.json unless the constructor overrode it
@@ -817,11 +887,19 @@ class ASRModel:
         c = self.__dict__.pop("_dispatcher", None)
         if c is not None:
             c.close()
+        err = None
+        for g in self.__dict__.pop("_grammars", []):      # (behind the dispatcher: every request has completed, so no reference is left)
+            try:
+                g.close()
+            except Exception as ex:                      # (the engines below still close, and free it; the error is raised afterwards)
+                err = err or ex
         self.__dict__.pop("model", None)
         self.__dict__.pop("_slot_engines", None)
         self.__dict__.pop("_score_engines", None)
         for m in self.__dict__.pop("models", []):
             m.close()                                # (an engine closes its slots first)
+        if err is not None:
+            raise err
 
     def __delattr__(self, name):   # main.py:84-86 does `del asr_model.model`
         if name == "model":

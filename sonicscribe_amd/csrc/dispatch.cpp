@@ -40,6 +40,12 @@ extern "C" int engine_request_bias_on(sonic_engine* e);     // engine.cpp: optio
 extern "C" int engine_bias_validate(sonic_engine* e, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n);   // engine.cpp: one request's table against the caps and this handle's vocabulary
 extern "C" int engine_sampling_on(sonic_engine* e);         // engine.cpp: option sampling on this handle
 extern "C" int engine_sampling_validate(float temperature); // engine.cpp: 0 or 1e-3 .. 100 (the message goes to the calling thread's sonic_last_error(NULL))
+extern "C" int engine_grammar_on(sonic_engine* e);          // engine.cpp: option grammar on this handle
+struct sonic_grammar;
+extern "C" sonic_grammar* engine_take_dispatch_grammar(void);   // engine.cpp: the grammar sonic_load_tensor "grammar.dispatch:<id>" armed for this thread's next submit (with a reference), or NULL ...
+extern "C" void engine_grammar_unref(sonic_grammar* g);     // ... and the reference's return
+extern "C" void* engine_grammar_owner(sonic_grammar* g);    // engine.cpp: the weight owner a grammar lives on
+extern "C" int engine_set_request_grammar(sonic_engine* e, sonic_grammar* const* grammars, int R);   // engine.cpp: a batch's grammars for the handle's next prefill
 extern "C" int engine_thread_fail(int code, const char* msg);   // engine.cpp: the calling thread's sonic_last_error(NULL)
 
 namespace {
@@ -54,6 +60,7 @@ struct Req {
     std::vector<float> lp;                                         // ... and, with option token_logprobs on the handles, every token's log-probability
     std::vector<int32_t> b_ids, b_off; std::vector<float> b_val;  // its own sequence-bias table (sonic_dispatch_submit_bias): ids, offsets [n + 1] (empty: none), biases
     bool sampled = false; float temperature = 0.f; uint64_t seed = 0;   // its own (temperature, seed) (sonic_dispatch_submit_sampled); unsampled requests of a batch are greedy
+    sonic_grammar* gram = nullptr;                                 // its grammar ("grammar.dispatch:<id>" ahead of the submit): a reference held from the submit until the request completes
     bool cancelled = false;
 };
 typedef std::shared_ptr<Req> ReqP;
@@ -69,6 +76,7 @@ struct sonic_dispatch {
     int lp_w = 1;                                                  // ... and their records hold this many floats per token (1 + 2K, option top_logprobs: equal on all)
     bool bias = false;                                             // every handle has option request_bias on
     bool samp = false;                                             // every handle has option sampling on
+    bool gram = false;                                             // every handle has option grammar on
     std::mutex mu;
     std::condition_variable cv;                                    // queue, hand-overs, free rows, state
     std::condition_variable cv_done;                               // completions
@@ -87,6 +95,7 @@ namespace {
 
 void finish(sonic_dispatch* d, const ReqP& r, int status, const std::string& err) {   // d->mu held
     if (r->status != -1) return;
+    if (r->gram) { engine_grammar_unref(r->gram); r->gram = nullptr; }      // (its row was fetched - and let go of its own reference - or it never reached one)
     r->status = status; r->err = err;
     d->done.push_back(r);
     d->cv_done.notify_all();
@@ -137,6 +146,13 @@ int prefill_batch(sonic_dispatch* d, sonic_engine* h, const std::vector<ReqP>& b
         std::vector<float> t; std::vector<uint64_t> sd;
         for (auto& r : batch) { t.push_back(r->sampled ? r->temperature : 0.f); sd.push_back(r->sampled ? r->seed : 0); }
         rc = sonic_set_request_sampling(h, t.data(), sd.data(), R);
+    }
+    bool any_gram = false;
+    for (auto& r : batch) any_gram = any_gram || r->gram;
+    if (rc == SONIC_OK && any_gram) {                              // the requests' grammars (NULL: a free request); the prefill below consumes them
+        std::vector<sonic_grammar*> gs;
+        for (auto& r : batch) gs.push_back(r->gram);
+        rc = engine_set_request_grammar(h, gs.data(), R);
     }
     if (rc == SONIC_OK) rc = sonic_prefill(h, req_win.data(), R, ids.data(), poff.data(), mn.data(), 0);
     if (rc != SONIC_OK && err) *err = sonic_last_error(h);
@@ -323,6 +339,8 @@ SONIC_API int sonic_dispatch_create(sonic_engine* const* decoders, int n_dec, so
     for (int i = 0; i < n_dec + n_pre; ++i) d->bias = d->bias && engine_request_bias_on(i < n_dec ? decoders[i] : prefills[i - n_dec]);
     d->samp = true;
     for (int i = 0; i < n_dec + n_pre; ++i) d->samp = d->samp && engine_sampling_on(i < n_dec ? decoders[i] : prefills[i - n_dec]);
+    d->gram = true;
+    for (int i = 0; i < n_dec + n_pre; ++i) d->gram = d->gram && engine_grammar_on(i < n_dec ? decoders[i] : prefills[i - n_dec]);
     d->free_rows.assign(n_dec, rows); d->hand.resize(n_dec);
     for (int i = 0; i < n_dec; ++i) {
         const int rc = sonic_service_begin(d->dec[i]);
@@ -340,6 +358,9 @@ SONIC_API int sonic_dispatch_create(sonic_engine* const* decoders, int n_dec, so
 static int dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, const int64_t* host_off, sonic_ring* const* rings, const int64_t* ring_start,
                            const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, const int32_t* seq_ids, const int32_t* seq_off,
                            const float* bias, int n_seq, int64_t* ticket_out, bool sampled = false, float temperature = 0.f, uint64_t seed = 0) {
+    // the grammar armed on this thread (sonic_load_tensor "grammar.dispatch:<id>"): this submit takes it whatever becomes of it
+    struct Armed { sonic_grammar* g; ~Armed() { if (g) engine_grammar_unref(g); } } armed{engine_take_dispatch_grammar()};
+    sonic_grammar* gram = armed.g;
     if (!d || !ticket_out || W < 1 || !prompt_ids || prompt_len < 1 || max_new < 1 || !host_off) return SONIC_ERR_INVALID;
     if (rings && (!ring_start || !ring_n)) return SONIC_ERR_INVALID;
     auto r = std::make_shared<Req>();
@@ -358,6 +379,13 @@ static int dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, const int
     std::unique_lock<std::mutex> lk(d->mu);
     if (d->stop) return SONIC_ERR_INVALID;
     if (d->failed) return d->failed;
+    if (gram) {
+        if (!d->gram) return engine_thread_fail(SONIC_ERR_INVALID, "grammar.dispatch: option grammar is off on a handle of this dispatcher (set it on the owner before its slots are created)");
+        const void* wid = nullptr;
+        (void)sonic_engine_info(d->pre[0], nullptr, nullptr, nullptr, nullptr, &wid);
+        if (engine_grammar_owner(gram) != wid) return engine_thread_fail(SONIC_ERR_INVALID, "grammar.dispatch: the grammar is not a live grammar of this dispatcher's weight owner");
+        r->gram = gram; armed.g = nullptr;                          // (the request keeps the reference until it completes)
+    }
     r->ticket = d->next_ticket++;
     d->q.push_back(r); d->queued_windows += W; ++d->outstanding;
     *ticket_out = r->ticket;

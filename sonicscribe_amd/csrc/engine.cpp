@@ -474,7 +474,7 @@ template <typename W> static int stage_enable(sonic_engine* e, ReqStage<W>& s, i
     if (on) {
         if (hist && !e->hist) TRY(dalloc(e, &e->hist, (size_t)64 * e->max_ctx));
         if (!s.dev) TRY(dalloc(e, &s.dev, (size_t)words));
-        if (!s.host && hipHostMalloc((void**)&s.host, (size_t)words * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(e, SONIC_ERR_OOM, "%s: pinned host memory exhausted", opt); }
+        if (!s.host && hipHostMalloc((void**)&s.host, (size_t)words * sizeof(W), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(e, SONIC_ERR_OOM, "%s: pinned host memory exhausted", opt); }
         if (!s.ev) HIPC(e, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
         HIPC(e, stream_sync(e));
     }
@@ -623,6 +623,195 @@ int samp_upload(sonic_engine* e, int R) {
     return stage_sent(e, e->samp);
 }
 extern "C" int engine_sampling_on(sonic_engine* e) { return e && e->opt_sampling && e->samp.dev ? 1 : 0; }
+// ---- option grammar: a request's transcript restricted to the paths of a deterministic token automaton - HF's prefix_allowed_tokens_fn
+// (PrefixConstrainedLogitsProcessor), Vosk's `grammar` - with the mask and the state transition inside the greedy kernel.  Grammars live on the weight owner.
+int gram_pack(sonic_engine* e, const char* who, const int32_t* node_off, const int32_t* edge_tok, const int32_t* edge_next, int N, int E, int vocab, int audio_id, std::vector<int>* out) {
+    if (!node_off || !edge_tok || !edge_next) return fail(e, SONIC_ERR_INVALID, "%s: null array", who);
+    if (N < 1 || N > GRAM_MAX_NODES) return fail(e, SONIC_ERR_INVALID, "%s: %d nodes (1 .. %d; nothing is truncated)", who, N, GRAM_MAX_NODES);
+    if (E < 1 || E > GRAM_MAX_EDGES) return fail(e, SONIC_ERR_INVALID, "%s: %d edges (1 .. %d; nothing is truncated)", who, E, GRAM_MAX_EDGES);
+    if (node_off[0] != 0) return fail(e, SONIC_ERR_INVALID, "%s: node_off[0] is %d, not 0", who, node_off[0]);
+    if (node_off[N] != E) return fail(e, SONIC_ERR_INVALID, "%s: node_off[%d] is %d, not the edge count %d", who, N, node_off[N], E);
+    for (int n = 0; n < N; ++n) {
+        const int a = node_off[n], b = node_off[n + 1];
+        if (b < a || a < 0 || b > E) return fail(e, SONIC_ERR_INVALID, "%s: node_off is not monotone at node %d (%d then %d)", who, n, a, b);
+        if (b == a) return fail(e, SONIC_ERR_INVALID, "%s: node %d has no edge (a transcript ends through an EOS edge, never by running dry)", who, n);
+        for (int k = a; k < b; ++k) {
+            if (edge_tok[k] < 0 || edge_tok[k] >= vocab) return fail(e, SONIC_ERR_INVALID, "%s: token id %d of node %d is out of vocabulary (%d)", who, edge_tok[k], n, vocab);
+            if (edge_tok[k] == audio_id) return fail(e, SONIC_ERR_INVALID, "%s: token id %d of node %d is the audio placeholder, which cannot be emitted", who, edge_tok[k], n);
+            if (edge_next[k] < 0 || edge_next[k] >= N) return fail(e, SONIC_ERR_INVALID, "%s: edge %d of node %d leads to node %d (0 .. %d)", who, k - a, n, edge_next[k], N - 1);
+            if (k > a && edge_tok[k] <= edge_tok[k - 1]) return fail(e, SONIC_ERR_INVALID, "%s: the edges of node %d are not sorted and unique by token id (%d after %d)", who, n, edge_tok[k], edge_tok[k - 1]);
+        }
+    }
+    out->resize((size_t)GRAM_HEAD + N + 1 + 2 * (size_t)E);
+    int* w = out->data();
+    w[0] = N; w[1] = E;
+    memcpy(w + GRAM_HEAD, node_off, (size_t)(N + 1) * 4);
+    memcpy(w + GRAM_HEAD + N + 1, edge_tok, (size_t)E * 4);
+    memcpy(w + GRAM_HEAD + N + 1 + E, edge_next, (size_t)E * 4);
+    return SONIC_OK;
+}
+// the packed words [N | E | node_off[N + 1] | edge_tok[E] | edge_next[E]] taken apart again: SONIC_ERR_INVALID when the counts do not fit the length
+static int gram_unpack(const char* who, const int* w, int64_t n, const int** off, const int** tok, const int** nxt, int* N, int* E) {
+    if (!w || n < GRAM_HEAD) return fail(nullptr, SONIC_ERR_INVALID, "%s: %lld words do not hold the automaton's two counts", who, (long long)n);
+    *N = w[0]; *E = w[1];
+    if (*N < 1 || *N > GRAM_MAX_NODES) return fail(nullptr, SONIC_ERR_INVALID, "%s: %d nodes (1 .. %d; nothing is truncated)", who, *N, GRAM_MAX_NODES);
+    if (*E < 1 || *E > GRAM_MAX_EDGES) return fail(nullptr, SONIC_ERR_INVALID, "%s: %d edges (1 .. %d; nothing is truncated)", who, *E, GRAM_MAX_EDGES);
+    if (n != (int64_t)GRAM_HEAD + *N + 1 + 2 * (int64_t)*E) return fail(nullptr, SONIC_ERR_INVALID, "%s: %lld words, %d nodes and %d edges need %lld", who, (long long)n, *N, *E, (long long)GRAM_HEAD + *N + 1 + 2 * (long long)*E);
+    *off = w + GRAM_HEAD; *tok = *off + *N + 1; *nxt = *tok + *E;
+    return SONIC_OK;
+}
+// sonic_load_tensor(e, "grammar:<id>", words, SONIC_DTYPE_I32, {n}, 1): created once on a weight owner (a slot's call lands on its owner) under an id the caller
+// chooses (1 .. 65535) and shared by every handle of it; n = 0 destroys it - refused by name while a staged or running request refers to it; what is left when the owner
+// goes is freed with it.  Does not take the engine lock, so a server can compile a grammar while its handles decode.  The message of a refusal is the calling thread's
+int gram_create(sonic_engine* e, int id, const int* words, int64_t n) {
+    sonic_engine* root = e->owner ? e->owner : e;
+    if (!root->finalized) return fail(nullptr, SONIC_ERR_INVALID, "grammar: the engine's weights are not finalized");
+    if (id < 1 || id > 65535) return fail(nullptr, SONIC_ERR_INVALID, "grammar: id %d is outside 1 .. 65535", id);
+    if (n == 0) {
+        sonic_grammar* g = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(root->gram_mu);
+            auto it = std::find_if(root->grammars.begin(), root->grammars.end(), [&](sonic_grammar* x) { return x->id == id; });
+            if (it == root->grammars.end()) return fail(nullptr, SONIC_ERR_INVALID, "grammar: %d is not a live grammar of this engine", id);
+            g = *it;
+            const int r = g->refs.load();
+            if (r > 0) return fail(nullptr, SONIC_ERR_INVALID, "grammar: %d is in use: %d staged or running request%s refer%s to it (fetch or release their rows first)", id, r, r == 1 ? "" : "s", r == 1 ? "s" : "");
+            root->grammars.erase(it);
+        }
+        root->gram_bytes -= g->bytes;
+        (void)hipSetDevice(root->device);
+        (void)hipDeviceSynchronize();                         // launches queued while a row still referred to it (a finished row's block reads its node until the row is released)
+        (void)hipFree(g->dev);
+        delete g;
+        return SONIC_OK;
+    }
+    const int *off, *tok, *nxt; int N, E;
+    TRY(gram_unpack("grammar", words, n, &off, &tok, &nxt, &N, &E));
+    std::vector<int> w;
+    TRY(gram_pack(nullptr, "grammar", off, tok, nxt, N, E, root->d.vocab, root->d.audio_token_id, &w));
+    if (hipSetDevice(root->device) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, SONIC_ERR_HIP, "grammar: hipSetDevice failed"); }
+    sonic_grammar* g = new sonic_grammar();
+    g->root = root; g->id = id; g->N = N; g->E = E; g->bytes = (int64_t)w.size() * 4;
+    if (hipMalloc((void**)&g->dev, w.size() * 4) != hipSuccess) { (void)hipGetLastError(); delete g; return fail(nullptr, SONIC_ERR_OOM, "HIP out of memory (grammar of %d nodes and %d edges)", N, E); }
+    if (hipMemcpy(g->dev, w.data(), w.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(g->dev); delete g; return fail(nullptr, SONIC_ERR_HIP, "grammar: upload failed"); }
+    {
+        std::lock_guard<std::mutex> lk(root->gram_mu);
+        for (sonic_grammar* x : root->grammars) if (x->id == id) { (void)hipFree(g->dev); delete g; return fail(nullptr, SONIC_ERR_INVALID, "grammar: id %d is taken by a live grammar of this engine", id); }
+        root->grammars.push_back(g);
+    }
+    root->gram_bytes += g->bytes;
+    return SONIC_OK;
+}
+// the kernel hooks' automaton (engine_hooks.cpp test_greedy), validated as a grammar is, against the hook's own vocabulary V
+int gram_hook_arm(sonic_engine* e, int V, const int* words, int64_t n) {
+    const int *off, *tok, *nxt; int N, E;
+    if (V < 4 || V > (1 << 24)) return fail(nullptr, SONIC_ERR_INVALID, "grammar.hook: vocabulary %d", V);
+    TRY(gram_unpack("grammar.hook", words, n, &off, &tok, &nxt, &N, &E));
+    std::vector<int> w;
+    TRY(gram_pack(nullptr, "grammar.hook", off, tok, nxt, N, E, V, -1, &w));
+    std::lock_guard<std::mutex> lk(e->mu);
+    e->hook_gram.swap(w); e->hook_eos.clear();
+    for (int b = 0; b < 64; ++b) e->hook_state_in[b] = -1;
+    return SONIC_OK;
+}
+void gram_unref(sonic_grammar* g) { if (g) g->refs.fetch_sub(1); }
+void gram_drop_staged(sonic_engine* e) {
+    for (int r = 0; r < 64; ++r) { gram_unref(e->gram_staged[r]); e->gram_staged[r] = nullptr; }
+    e->gram.pending = -1;
+}
+void gram_row_release(sonic_engine* e, int row) { if (row >= 0 && row < 64) { gram_unref(e->gram_row[row]); e->gram_row[row] = nullptr; } }
+// a live grammar of `root` gains a reference (under the registry's lock: a concurrent destroy either sees it or has already removed the grammar)
+static bool gram_ref(sonic_engine* root, sonic_grammar* g) {
+    std::lock_guard<std::mutex> lk(root->gram_mu);
+    if (std::find(root->grammars.begin(), root->grammars.end(), g) == root->grammars.end()) return false;
+    g->refs.fetch_add(1);
+    return true;
+}
+static sonic_grammar* gram_ref_id(sonic_engine* root, int id) {
+    std::lock_guard<std::mutex> lk(root->gram_mu);
+    for (sonic_grammar* g : root->grammars) if (g->id == id) { g->refs.fetch_add(1); return g; }
+    return nullptr;
+}
+int gram_enable(sonic_engine* e, int on) {
+    if (on && !(e->opt_token_logprobs && e->out_lp)) return fail(e, SONIC_ERR_INVALID, "grammar: option token_logprobs must be on first (the grammar kernels are log-probability kernels; sonic_set_option(e, \"token_logprobs\", 1))");
+    if (on && greedy_guard_lds(e->d.vocab) > 60000) return fail(e, SONIC_ERR_UNSUPPORTED, "grammar: a vocabulary of %d ids does not fit the guard bitmaps", e->d.vocab);
+    if (!on && e->opt_grammar) { gram_drop_staged(e); for (int r = 0; r < 64; ++r) gram_row_release(e, r); }
+    TRY(stage_enable(e, e->gram, on, &e->opt_grammar, "grammar", GRAM_STAGE_WORDS, true));
+    if (on) { launch_fill_i32((int*)e->gram.dev, 0, 128, e->st); launch_fill_i32(gram_state_of(e), -1, 64, e->st); HIPC(e, stream_sync(e)); }      // every row starts free
+    return SONIC_OK;
+}
+// The grammars of the R requests of the next prefill on this handle (the entry points of sonic_set_request_bias), which consumes them.  Options of the handle:
+// request_grammar_begin = R stages R free requests, request_grammar = request << 16 | grammar id then names a request's grammar.  The caller holds the lock
+static void gram_stage_words(sonic_engine* e) {
+    int* st = (int*)(e->gram.host + 64);
+    for (int r = 0; r < 64; ++r) { e->gram.host[r] = e->gram_staged[r] ? (unsigned long long)(uintptr_t)e->gram_staged[r]->dev : 0ull; st[r] = e->gram_staged[r] ? 0 : -1; }
+}
+int gram_stage_begin(sonic_engine* e, int R) {
+    if (!e->opt_grammar || !e->gram.dev) return fail(e, SONIC_ERR_INVALID, "request_grammar_begin: option grammar is off on this handle (sonic_set_option(e, \"grammar\", 1) on the owner before its slots are created)");
+    gram_drop_staged(e);
+    if (R < 1 || R > e->Bm || R > 64) return fail(e, SONIC_ERR_INVALID, "request_grammar_begin: %d requests (1 .. %d)", R, e->Bm);
+    HIPC(e, hipSetDevice(e->device));
+    TRY(stage_open(e, e->gram));
+    gram_stage_words(e);
+    e->gram.pending = R;
+    return SONIC_OK;
+}
+int gram_stage_row(sonic_engine* e, int value) {
+    const int r = value >> 16, id = value & 0xffff, R = e->gram.pending.load();
+    if (!e->opt_grammar || !e->gram.dev) return fail(e, SONIC_ERR_INVALID, "request_grammar: option grammar is off on this handle (sonic_set_option(e, \"grammar\", 1) on the owner before its slots are created)");
+    if (R < 0) return fail(e, SONIC_ERR_INVALID, "request_grammar: no batch is staged (option request_grammar_begin first)");
+    if (value < 0 || r >= R) { gram_drop_staged(e); return fail(e, SONIC_ERR_INVALID, "request_grammar: request %d of a staged batch of %d", r, R); }
+    sonic_grammar* g = gram_ref_id(e->owner ? e->owner : e, id);
+    if (!g) { gram_drop_staged(e); return fail(e, SONIC_ERR_INVALID, "request_grammar: %d is not a live grammar of this handle's weight owner (a grammar serves the engine it was created on and its slots)", id); }
+    gram_unref(e->gram_staged[r]);
+    e->gram_staged[r] = g;
+    gram_stage_words(e);
+    return SONIC_OK;
+}
+// dispatch.cpp (same library, not exported): a batch's grammars by pointer (NULL: a free request), under the handle's lock
+extern "C" int engine_set_request_grammar(sonic_engine* e, sonic_grammar* const* grammars, int R) {
+    if (!e || !grammars) return SONIC_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipGetLastError();
+    TRY(gram_stage_begin(e, R));
+    sonic_engine* root = e->owner ? e->owner : e;
+    for (int r = 0; r < R; ++r) {
+        if (!grammars[r]) continue;
+        if (!gram_ref(root, grammars[r])) { gram_drop_staged(e); return fail(e, SONIC_ERR_INVALID, "request_grammar: the grammar of request %d is not a live grammar of this handle's weight owner", r); }
+        e->gram_staged[r] = grammars[r];
+    }
+    gram_stage_words(e);
+    return SONIC_OK;
+}
+// sonic_load_tensor "grammar.dispatch:<id>" on any handle of a dispatcher's weight owner: the calling thread's NEXT sonic_dispatch_submit* carries that grammar (0: none;
+// the registry's lock and a thread-local, never the engine lock: a decoding handle holds that one for a chunk at a time), which takes it - and its
+// reference - whatever becomes of the submit
+static thread_local sonic_grammar* g_dispatch_gram = nullptr;
+int gram_dispatch_arm(sonic_engine* e, int id) {
+    gram_unref(g_dispatch_gram); g_dispatch_gram = nullptr;
+    if (id == 0) return SONIC_OK;
+    g_dispatch_gram = gram_ref_id(e->owner ? e->owner : e, id);
+    if (!g_dispatch_gram) return fail(nullptr, SONIC_ERR_INVALID, "grammar.dispatch: %d is not a live grammar of this handle's weight owner", id);
+    return SONIC_OK;
+}
+extern "C" sonic_grammar* engine_take_dispatch_grammar(void) { sonic_grammar* g = g_dispatch_gram; g_dispatch_gram = nullptr; return g; }
+int gram_upload(sonic_engine* e, int R) {
+    (void)R;
+    if (!e->opt_grammar) return SONIC_OK;
+    for (int r = 0; r < 64; ++r) gram_row_release(e, r);                  // the rows' former occupants are gone (or were spliced away with references of their own)
+    if (!e->gram.take) {                                                   // a batch without grammars: every row free
+        gram_drop_staged(e);
+        launch_fill_i32((int*)e->gram.dev, 0, 128, e->st); launch_fill_i32(gram_state_of(e), -1, 64, e->st);
+        return SONIC_OK;
+    }
+    for (int r = 0; r < 64; ++r) { e->gram_row[r] = e->gram_staged[r]; e->gram_staged[r] = nullptr; }
+    HIPC(e, hipMemcpyAsync(e->gram.dev, e->gram.host, (size_t)GRAM_STAGE_WORDS * 8, hipMemcpyHostToDevice, e->st));
+    return stage_sent(e, e->gram);
+}
+// dispatch.cpp (same library, not exported): the option on a handle; whose grammar it is; a queued request's reference handed back
+extern "C" int engine_grammar_on(sonic_engine* e) { return e && e->opt_grammar && e->gram.dev ? 1 : 0; }
+extern "C" void* engine_grammar_owner(sonic_grammar* g) { return g ? (void*)g->root : nullptr; }
+extern "C" void engine_grammar_unref(sonic_grammar* g) { gram_unref(g); }
 extern "C" int engine_sampling_validate(float temperature) { return samp_check(nullptr, "sonic_dispatch_submit_sampled", &temperature, 1); }
 // dispatch.cpp (same library, not exported): is the option on for a handle; is one request's table well-formed for it (the message lands on the handle)
 extern "C" int engine_request_bias_on(sonic_engine* e) { return e && e->opt_request_bias && e->bias.dev ? 1 : 0; }
@@ -721,6 +910,7 @@ extern "C" int sonic_slot_create(sonic_engine* parent, sonic_engine** out) {
     e->opt_bias_fill = root->opt_bias_fill;
     if (root->opt_sampling && (s = samp_enable(e, 1)) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }
     e->opt_samp_fill_milli = root->opt_samp_fill_milli;
+    if (root->opt_grammar && (s = gram_enable(e, 1)) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }
     e->opt_forced_parallel = root->opt_forced_parallel; e->opt_forced_fanout = root->opt_forced_fanout; e->opt_score_chunk_rows = root->opt_score_chunk_rows;      // (the buffers come with the slot's first parallel run)
     e->opt_forced_align = root->opt_forced_align; e->align_heads = root->align_heads;      // (likewise)
     e->weight_bytes = 0; e->finalized = true; e->owner = root;
@@ -766,6 +956,10 @@ extern "C" void sonic_destroy(sonic_engine* e) {
         if (root != e && root->wait_ev == e->splice_ev) root->wait_pending = false;
         for (sonic_engine* k : root->slots) if (k != e && k->wait_ev == e->splice_ev) k->wait_pending = false;
     }
+    gram_drop_staged(e);                               // the grammar references of this handle's staged requests and rows
+    for (int r = 0; r < 64; ++r) gram_row_release(e, r);
+    for (sonic_grammar* g : e->grammars) { (void)hipFree(g->dev); delete g; }      // owner: the grammars the caller left behind (its slots are gone: nothing refers to them)
+    e->grammars.clear();
     for (sonic_ring* r : e->rings) ring_free(r);       // rings the caller left behind go with their engine
     e->rings.clear();
     resample_release(e);
@@ -780,7 +974,7 @@ extern "C" void sonic_destroy(sonic_engine* e) {
     if (e->svc_h) (void)hipHostFree(e->svc_h);
     if (e->score_plan_h) (void)hipHostFree(e->score_plan_h);
     if (e->align_plan_h) (void)hipHostFree(e->align_plan_h);
-    stage_free(e->bias); stage_free(e->samp);
+    stage_free(e->bias); stage_free(e->samp); stage_free(e->gram);
     if (e->st_io) { (void)hipStreamSynchronize(e->st_io); (void)hipStreamDestroy(e->st_io); }
     if (e->xfer_ev) (void)hipEventDestroy(e->xfer_ev);
     if (e->splice_ev) (void)hipEventDestroy(e->splice_ev);
@@ -826,7 +1020,7 @@ extern "C" int sonic_device_info(int device_id, char* name, int name_cap, int64_
 extern "C" int sonic_memory_info(sonic_engine* e, int64_t* allocated_bytes, int64_t* reserved_bytes) {
     if (!e) return SONIC_ERR_INVALID;
     std::lock_guard<std::mutex> lk(e->mu);
-    const int64_t live = e->alloc_bytes + (e->owner ? 0 : e->ring_bytes.load());      // rings are charged to the weight owner that registers them
+    const int64_t live = e->alloc_bytes + (e->owner ? 0 : e->ring_bytes.load() + e->gram_bytes.load());      // rings and grammars are charged to the weight owner that registers them
     if (allocated_bytes) *allocated_bytes = live;
     if (reserved_bytes) *reserved_bytes = live;
     return SONIC_OK;

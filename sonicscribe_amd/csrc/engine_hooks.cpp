@@ -396,6 +396,11 @@ struct GuardTest { const int32_t* hist; int hist_ld; const int32_t* hist_len; fl
 // sonic_test_greedy_sample: the launch through greedy_kernel<T, true, GUARD, BIAS, true> in the handle's own type (bf16, fp16, the fp32 kind's float): row b draws at
 // temperature[b] with seed[b] as its step[b]-th token (n_new = step: ids, log-probabilities and forced ids sit at that column); noise_out[B][V] = the Gumbel values used.
 struct SampTest { const float* temperature; const uint64_t* seed; const int32_t* step; float* noise_out; };
+// The grammar instantiations (greedy_kernel<T, true, true, BIAS, SAMPLE, TOPK, true>) ride on the guard / bias / sample hooks: an automaton armed on the
+// handle (sonic_load_tensor "grammar.hook:<V>", validated against V as a grammar is against its model; options hook_grammar_state = row << 20 | state + 2 and
+// hook_grammar_eos) is taken by the next launch that has histories and log-probabilities, in the handle's own type: row b enters at its state (-1: a free row, -2: it has
+// left), eos: the ids a row at -2 may still emit (they also end a row, as the handle's do); the states out are read with sonic_debug_read "hook_grammar_state"
+struct GramTest { const int32_t* state_in; const int32_t* eos; int n_eos; int32_t* state_out; };
 static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const int32_t* force_ids, int32_t* tok_out, float* logits_out, float* lp_out,
                        const GuardTest* gt = nullptr, const SampTest* sp = nullptr) {
     if (ksplit < 1 || ksplit > 8 || B < 1 || B > 64 || mpad < B || V < 4 || V % 4) return fail(e, SONIC_ERR_INVALID, "bad greedy test shape");
@@ -407,10 +412,19 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
         TRY(samp_check(e, "sonic_test_greedy_sample", sp->temperature, B));
         for (int b = 0; b < B; ++b) { if (sp->step[b] < 0 || sp->step[b] > 65535) return fail(e, SONIC_ERR_INVALID, "step %d outside 0 .. 65535", sp->step[b]); old = std::max(old, sp->step[b] + 1); }
     }
+    std::vector<int> gblob; std::vector<int> geos;
+    GramTest gtest{}; const GramTest* gr = nullptr;
+    if (!e->hook_gram.empty() && gt && lp_out) {      // an armed hook grammar: this launch takes it
+        gblob.swap(e->hook_gram); geos.swap(e->hook_eos);
+        for (int k = 0; k < gblob[1]; ++k) if (gblob[GRAM_HEAD + gblob[0] + 1 + k] >= V) return fail(e, SONIC_ERR_INVALID, "hook grammar: token id %d does not fit this launch's vocabulary %d", gblob[GRAM_HEAD + gblob[0] + 1 + k], V);
+        for (int id : geos) if (id >= V) return fail(e, SONIC_ERR_INVALID, "hook grammar: EOS id %d out of vocabulary", id);
+        gtest = GramTest{e->hook_state_in, geos.data(), (int)geos.size(), e->hook_state_out};
+        gr = &gtest;
+    }
     TmpBuf tb(e->st);
     const size_t n = (size_t)ksplit * mpad * V;
     float* dl = up_f32(e, tb, slabs, n);
-    bf16_t* table = tb.get<bf16_t>((size_t)V * 8 * (sp ? 2 : 1)); bf16_t* x = tb.get<bf16_t>((size_t)64 * 8 * (sp ? 2 : 1));      // (sp: rows of 8 floats in the fp32 kind)
+    bf16_t* table = tb.get<bf16_t>((size_t)V * 8 * (sp || gr ? 2 : 1)); bf16_t* x = tb.get<bf16_t>((size_t)64 * 8 * (sp || gr ? 2 : 1));      // (sp, gr: rows of 8 floats in the fp32 kind)
     int* st = tb.get<int>(64 * 8 + 4); int* ids = tb.get<int>((size_t)64 * old);
     float* dump = logits_out ? tb.get<float>((size_t)B * V) : nullptr;
     float* lp = lp_out ? tb.get<float>((size_t)64 * old * lw_) : nullptr;
@@ -467,6 +481,16 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
         if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
         HIPC(e, h2d(e, gsamp, w.data(), w.size() * 4));
     }
+    int* gdev = nullptr; unsigned long long* gref = nullptr;
+    if (gr) {
+        gdev = tb.get<int>(gblob.size()); gref = tb.get<unsigned long long>(GRAM_STAGE_WORDS);
+        if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+        std::vector<unsigned long long> w((size_t)GRAM_STAGE_WORDS, 0ull);
+        int* stw = (int*)(w.data() + 64);
+        for (int b = 0; b < 64; ++b) { w[b] = b < B && gr->state_in[b] != -1 ? (unsigned long long)(uintptr_t)gdev : 0ull; stw[b] = b < B ? gr->state_in[b] : -1; }
+        HIPC(e, h2d(e, gdev, gblob.data(), gblob.size() * 4));
+        HIPC(e, h2d(e, gref, w.data(), w.size() * 8));
+    }
     HIPC(e, h2d(e, st, h.data(), h.size() * 4));
     if (fd && !sp) HIPC(e, h2d(e, fd, force_ids, (size_t)B * 4));
     if (fd && sp) {
@@ -481,9 +505,15 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
     g.out_lp = lp; g.force_ids = fd; g.force_ld = old; g.topk = lp ? e->opt_top_logprobs : 0;
     if (sp) { g.samp = gsamp; g.noise_out = gnoise; g.dt = e->f32 ? DT_F32 : e->dt; }
     if (gt) { g.hist = ghist; g.hist_ld = gld; g.rep_penalty = gt->penalty; g.ngram = gt->ngram; g.suppress = gsup; g.n_suppress = gt->n_suppress; g.bias_tab = gbias; }
+    if (gr) { g.gram_ref = gref; g.gram_state = (int*)(gref + 64); g.n_eos = gr->n_eos; for (int i = 0; i < gr->n_eos; ++i) g.eos[i] = gr->eos[i]; g.dt = e->f32 ? DT_F32 : e->dt; }
     launch_greedy(g, e->st);
     HIPC(e, stream_sync(e));
     HIPC(e, hipGetLastError());
+    if (gr) {
+        std::vector<unsigned long long> w((size_t)GRAM_STAGE_WORDS);
+        HIPC(e, d2h(e, w.data(), gref, w.size() * 8));
+        memcpy(gr->state_out, w.data() + 64, (size_t)B * 4);
+    }
     std::vector<int> out((size_t)64 * old);
     HIPC(e, d2h(e, out.data(), ids, out.size() * 4));
     for (int b = 0; b < B; ++b) tok_out[b] = out[(size_t)b * old + (sp ? sp->step[b] : 0)];

@@ -71,6 +71,10 @@ template <typename W> struct ReqStage {
     std::atomic<int> pending{-1}; bool take = false;
     int claim() { take = false; return pending.exchange(-1); }      // run_to_first_token: this batch consumes what is pending whatever becomes of it
 };
+// A grammar (sonic_load_tensor "grammar:<id>"): a deterministic token automaton on the device, created on a weight owner and shared by all of its handles.
+// dev: GRAM_HEAD words (N, E), node_off[N + 1], edge_tok[E], edge_next[E] (kernels.h GreedyArgs.gram_ref).  refs: the requests that refer to it - staged
+// (option request_grammar, a dispatcher's queue) or on a row; the destroy refuses while it is above zero
+struct sonic_grammar { sonic_engine* root = nullptr; int id = 0; int* dev = nullptr; int N = 0, E = 0; int64_t bytes = 0; std::atomic<int> refs{0}; };
 struct sonic_engine {
     sonic_dims d;
     int device = 0, mode = 0, Bm = 0, max_ctx = 0;
@@ -200,6 +204,18 @@ struct sonic_engine {
     int opt_sampling = 0;
     int opt_samp_fill_milli = 0;   // measurement aid (option sampling_fill_milli, tools/ab_sampling.sh): a prefill that was given no values decodes request r at this temperature (in thousandths) with seed r
     ReqStage<unsigned> samp;
+    // option grammar (options request_grammar_begin / request_grammar; greedy_kernel<T, true, true, ., ., ., true>): gram.dev holds GRAM_STAGE_WORDS 64-bit words - the 64
+    // rows' grammar references (device addresses; 0: a free row), then their 64 state words (int: -1 free, n >= 0 a node, -2 left); allocated, with hist, by the
+    // option.  gram_staged / gram_row: the references (sonic_grammar::refs) the staged requests and the rows of this handle hold - taken by the setter, moved to the
+    // rows by the prefill, copied by the splice, dropped when a row is fetched, overwritten by the next prefill or goes with the handle.
+    // Owner only: `grammars`, the registry (guarded by gram_mu; freed with the owner at the latest), and gram_bytes, their device bytes (part of sonic_memory_info)
+    int opt_grammar = 0;
+    ReqStage<unsigned long long> gram;
+    sonic_grammar* gram_staged[64]{}; sonic_grammar* gram_row[64]{};
+    std::mutex gram_mu; std::vector<sonic_grammar*> grammars; std::atomic<int64_t> gram_bytes{0};
+    // the kernel hooks' grammar (sonic_load_tensor "grammar.hook:<V>", options hook_grammar_state / hook_grammar_eos; engine_hooks.cpp): the packed automaton, the rows'
+    // states in, the EOS ids, armed until the next hook launch that has histories and log-probabilities takes it; hook_state_out: that launch's states out (sonic_debug_read)
+    std::vector<int> hook_gram; int hook_state_in[64]; std::vector<int> hook_eos; int hook_state_out[64]{};
     // the parallel forced run (options forced_parallel / forced_fanout / score_chunk_rows; run_forced_parallel, engine_stages.cpp): with forced ids set,
     // a run is ONE prefill of prompt || forced ids, the lm_head over every forced position as a GEMM per chunk of score rows, and score_rows_kernel per row.
     // score_logits: the chunk's logits [score_rows_cap][vocab] in the activation type (fp32 kind: fp32); score_plan_d / score_plan_h: per score row its hidden-state
@@ -265,7 +281,8 @@ struct HostPlan {
 // ENTER for the entry points that consume the tables of sonic_set_request_bias (sonic_prefill*, sonic_run_staged, sonic_transcribe_*): whatever way the call
 // leaves - a staging error ahead of the prefill included - the pending tables are dropped, so they can never reach a later batch (the values of
 // sonic_set_request_sampling likewise).  keep: sonic_run_staged_async accepted the run, whose prefill is now their consumer
-struct ReqDrop { sonic_engine* e; bool keep = false; ~ReqDrop() { if (!keep) { e->bias.pending = -1; e->samp.pending = -1; } } };
+void gram_drop_staged(sonic_engine* e);             // the grammar references staged requests hold (engine.cpp); nothing is pending afterwards
+struct ReqDrop { sonic_engine* e; bool keep = false; ~ReqDrop() { if (!keep) { e->bias.pending = -1; e->samp.pending = -1; if (e->opt_grammar) gram_drop_staged(e); } } };
 #define ENTER_CONSUME(e) std::lock_guard<std::mutex> lk((e)->mu); ReqDrop req_drop_{e}; (void)hipGetLastError(); HIPC(e, hipSetDevice((e)->device)); g_opts = (e)->opts
 
 // ------------------------------------------------------------------------------------------ helpers (engine.cpp)
@@ -345,7 +362,20 @@ int samp_enable(sonic_engine* e, int on);           // option sampling behind th
 int samp_check(sonic_engine* e, const char* who, const float* temperature, int n);   // SONIC_ERR_INVALID (message on e, or the calling thread's for e = NULL) unless every value is 0 or in [1e-3, 100]
 int samp_upload(sonic_engine* e, int R);            // the prefill's part: the pending values (or zeros: greedy) into samp.dev, on the stream (engine.cpp)
 void samp_pack(unsigned* w, float t, uint64_t seed);   // one row's three words as the kernel reads them: the temperature's bits, the seed's low and high word (engine.cpp)
-static inline bool hist_on(const sonic_engine* e) { return e->gen_on || e->opt_request_bias; }   // the rows' input_ids are kept: a guard or the request bias reads them
+static inline bool hist_on(const sonic_engine* e) { return e->gen_on || e->opt_request_bias || e->opt_grammar; }   // the rows' input_ids are kept: a guard, the request bias or the grammar's kernels read them
+int gram_enable(sonic_engine* e, int on);           // option grammar behind the lock and the busy check: hist, the rows' references and state words and their staging buffer on first use (engine.cpp)
+int gram_create(sonic_engine* e, int id, const int* words, int64_t n);   // sonic_load_tensor "grammar:<id>": the packed automaton [N | E | node_off | edge_tok | edge_next] onto e's weight owner; n = 0 destroys it (engine.cpp)
+int gram_hook_arm(sonic_engine* e, int V, const int* words, int64_t n);  // sonic_load_tensor "grammar.hook:<V>": the hooks' automaton, validated against V; every row free, no EOS ids (engine.cpp)
+int gram_stage_begin(sonic_engine* e, int R);       // option request_grammar_begin: R requests staged for the next prefill, all free (the caller holds the lock)
+int gram_stage_row(sonic_engine* e, int value);     // option request_grammar = request << 16 | grammar id: that staged request refers to that grammar
+int gram_dispatch_arm(sonic_engine* e, int id);     // sonic_load_tensor "grammar.dispatch:<id>" (no engine lock): the calling thread's next sonic_dispatch_submit* carries grammar `id` of e's owner
+int gram_upload(sonic_engine* e, int R);            // the prefill's part: the pending references (state 0) or none (state -1) into gram.dev, on the stream; the rows take over the staged references (engine.cpp)
+void gram_unref(sonic_grammar* g);                  // one reference less (NULL: nothing)
+void gram_row_release(sonic_engine* e, int row);    // a fetched row of a continuous loop lets go of its grammar
+static inline int* gram_state_of(const sonic_engine* e) { return (int*)(e->gram.dev + 64); }   // the rows' state words behind their references
+// the automaton's arrays validated by the contract's rules (SONIC_ERR_INVALID, the message - on e, or the calling thread's for e = NULL - names `who` and the cause) and
+// packed into the device blob's words: GRAM_HEAD + N + 1 + 2E of them
+int gram_pack(sonic_engine* e, const char* who, const int32_t* node_off, const int32_t* edge_tok, const int32_t* edge_next, int N, int E, int vocab, int audio_id, std::vector<int>* out);
 static inline int lp_width(const sonic_engine* e) { return 1 + 2 * e->opt_top_logprobs; }   // floats per token in every log-probability array of this handle
 int top_enable(sonic_engine* e, int K);             // option top_logprobs behind the lock and the busy check: out_lp at its new width (engine.cpp)
 int lp_check(sonic_engine* e, const char* who);     // SONIC_ERR_INVALID naming the option when token_logprobs is off on this handle

@@ -6,6 +6,7 @@ void drop_graphs(sonic_engine* e) { for (auto& g : e->graphs) (void)hipGraphExec
 static int opt_token_logprobs(sonic_engine* e, const char*, int value) {      // per-token log-probabilities beside the ids (greedy_kernel<T, true>)
     const int v = value ? 1 : 0;
     if (!v && e->opt_sampling) return fail(e, SONIC_ERR_INVALID, "token_logprobs cannot be switched off while option sampling is on (its kernels are log-probability kernels)");
+    if (!v && e->opt_grammar) return fail(e, SONIC_ERR_INVALID, "token_logprobs cannot be switched off while option grammar is on (its kernels are log-probability kernels)");
     if (!v && e->opt_top_logprobs) return fail(e, SONIC_ERR_INVALID, "token_logprobs cannot be switched off while option top_logprobs is on (its kernels are log-probability kernels)");
     e->opt_token_logprobs = v; drop_graphs(e);
     return v ? lp_alloc(e) : SONIC_OK;      // first use: 64 x out_cap fp32
@@ -29,6 +30,22 @@ static int opt_sampling(sonic_engine* e, const char* key, int value) { TRY(gen_b
 static int opt_sampling_fill_milli(sonic_engine* e, const char* key, int value) {    // measurement aid (samp_upload, engine.cpp): 0 (off) or 1 .. 100000 thousandths, for every request without values
     if (value != 0 && (value < 1 || value > 100000)) return fail(e, SONIC_ERR_INVALID, "sampling_fill_milli: %d is outside 0, 1 .. 100000", value);
     TRY(gen_busy(e, key)); e->opt_samp_fill_milli = value; return SONIC_OK;
+}
+// grammar-constrained decoding (options request_grammar_begin / request_grammar): on the owner before its slots are created (they copy it), after token_logprobs (refused by
+// name otherwise); allocates the rows' history, if nothing else has, and their references and state words.  Refused while the handle has work in hand
+static int opt_grammar(sonic_engine* e, const char* key, int value) { TRY(gen_busy(e, key)); return gram_enable(e, value ? 1 : 0); }
+// ... and the values that travel through the options, since the feature adds no entry point: the grammars of the requests of the next prefill (begin = R requests, all
+// free; then request << 16 | grammar id per constrained request), the kernel hooks' row states and EOS ids
+static int opt_request_grammar_begin(sonic_engine* e, const char*, int value) { return gram_stage_begin(e, value); }
+static int opt_request_grammar(sonic_engine* e, const char*, int value) { return gram_stage_row(e, value); }
+static int opt_hook_grammar_state(sonic_engine* e, const char*, int value) {      // row << 20 | (state + 2)
+    const int b = value >> 20, st = (value & 0xfffff) - 2;
+    if (value < 0 || b > 63 || e->hook_gram.empty() || st >= e->hook_gram[0]) return fail(e, SONIC_ERR_INVALID, "hook_grammar_state: row %d, state %d (arm a hook grammar first: sonic_load_tensor \"grammar.hook:<V>\")", b, st);
+    e->hook_state_in[b] = st; return SONIC_OK;
+}
+static int opt_hook_grammar_eos(sonic_engine* e, const char*, int value) {
+    if (value < 0 || e->hook_gram.empty() || e->hook_eos.size() >= 8) return fail(e, SONIC_ERR_INVALID, "hook_grammar_eos: id %d (at most 8 ids, behind an armed hook grammar)", value);
+    e->hook_eos.push_back(value); return SONIC_OK;
 }
 // per-request sequence bias (sonic_set_request_bias): on the owner before its slots are created (they copy it); allocates the rows' history, if the
 // guards have not, and their tables.  Refused while the handle has work in hand, by sonic_set_generation's rule
@@ -139,6 +156,11 @@ static const OptRow OPTIONS[] = {
     {"gen_suppress_token", APPLY(opt_gen)},
     {"sampling", APPLY(opt_sampling)},
     {"sampling_fill_milli", APPLY(opt_sampling_fill_milli)},
+    {"grammar", APPLY(opt_grammar)},
+    {"request_grammar_begin", APPLY(opt_request_grammar_begin)},
+    {"request_grammar", APPLY(opt_request_grammar)},
+    {"hook_grammar_state", APPLY(opt_hook_grammar_state)},
+    {"hook_grammar_eos", APPLY(opt_hook_grammar_eos)},
     {"request_bias", APPLY(opt_request_bias)},
     {"request_bias_fill", APPLY(opt_request_bias_fill)},
     {"forced_parallel", APPLY(opt_forced_parallel)},
@@ -151,6 +173,10 @@ static const OptRow OPTIONS[] = {
 };
 extern "C" int sonic_set_option(sonic_engine* e, const char* key, int value) {
     if (!e || !key) return SONIC_ERR_INVALID;
+    if (!strncmp(key, "request_grammar", 15)) {      // as the other per-request setters: refused during an asynchronous run, without waiting for the lock that run holds
+        std::lock_guard<std::mutex> ak(e->a_mu);
+        if (e->a_pending || e->a_running) return fail(nullptr, SONIC_ERR_INVALID, "%s: an asynchronous run of this handle is in flight", key);
+    }
     std::lock_guard<std::mutex> lk(e->mu);
     // knobs live in the engine: two engines in one process do not see each other's settings; captured decode graphs of THIS engine
     // are dropped whenever a knob that changes the captured kernels moves
@@ -193,6 +219,11 @@ static const DbgRow DEBUG_BUFS[] = {
 extern "C" int sonic_debug_read(sonic_engine* e, const char* name, int index, float* out, int64_t n) {
     if (!e || !name || !out) return SONIC_ERR_INVALID;
     ENTER(e);
+    if (!strcmp(name, "hook_grammar_state")) {      // the rows' states behind the last hook launch that took a grammar (host words: exact in fp32)
+        if (n < 0 || n > 64) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
+        for (int64_t i = 0; i < n; ++i) out[i] = (float)e->hook_state_out[i];
+        return SONIC_OK;
+    }
     for (const DbgRow& r : DEBUG_BUFS) {
         if (strcmp(name, r.name) || !(e->f32 ? (bool)r.src32 : (r.src16 || r.f32_on_16))) continue;
         const bool tap = &r == &DEBUG_BUFS[0];

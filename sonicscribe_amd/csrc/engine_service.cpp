@@ -16,6 +16,7 @@ struct SpliceArgs {
     const int* hist_s; int* hist_d;                      // generation guards on the destination: the row's history (prompt + first token) travels with it, [.][ctx]
     const int* bias_s; int* bias_d;                      // option request_bias on both: the row's table travels with it (count first, then only the used entries)
     const unsigned* samp_s; unsigned* samp_d;            // option sampling on both: the row's temperature and seed travel with it (its step index is n_new)
+    unsigned long long* gram_s; unsigned long long* gram_d;            // option grammar on both: the row's grammar reference and its state word (behind the 64 references) MOVE with it: the source row is free afterwards
     const float* lp_s; float* lp_d; int lp_w;            // option token_logprobs on the destination: the first token's log-probability record (lp_w floats: 1, or 1 + 2K with
                                                          // option top_logprobs) travels with its id
     int *kv_len_d, *tok_pos_d, *n_new_d, *fin_d, *max_new_d, *out_d, *n_active_d;
@@ -54,6 +55,7 @@ __global__ __launch_bounds__(256) void splice_state_kernel(SpliceArgs a) {
         for (int j = t; j < cnt * BIAS_ENTRY_WORDS; j += 256) a.bias_d[64 + (long)d * BIAS_ROW_WORDS + j] = a.bias_s[64 + (long)s * BIAS_ROW_WORDS + j];
     }
     if (a.samp_d && t < 3) a.samp_d[3 * d + t] = a.samp_s[3 * s + t];
+    if (a.gram_d && t == 0) { a.gram_d[d] = a.gram_s[s]; ((int*)(a.gram_d + 64))[d] = ((int*)(a.gram_s + 64))[s]; a.gram_s[s] = 0ull; ((int*)(a.gram_s + 64))[s] = -1; }
     if (a.lp_d && t < a.lp_w) a.lp_d[(long)d * a.out_ld * a.lp_w + t] = a.lp_s[(long)s * a.out_ld * a.lp_w + t];
     if (t == 0) {
         const int fin = a.fin_s[s];
@@ -64,7 +66,8 @@ __global__ __launch_bounds__(256) void splice_state_kernel(SpliceArgs a) {
     }
 }
 // a fetched row goes back to the pool: it stays `finished` (frozen: it emits nothing) and looks at one key only until it is reused
-__global__ void release_row_kernel(int* kv_len, int* tok_pos, int* finished, int row) { kv_len[row] = 1; tok_pos[row] = 0; finished[row] = 1; }
+// (gram_state, option grammar: the row is free again - its blocks must not read an automaton that may be destroyed once the row's reference is gone)
+__global__ void release_row_kernel(int* kv_len, int* tok_pos, int* finished, int row, int* gram_state) { kv_len[row] = 1; tok_pos[row] = 0; finished[row] = 1; if (gram_state) gram_state[row] = -1; }
 // the pipelined check of the continuous loop: finished | n_new | n_active -> one record in pinned host memory (a kernel's stores instead of
 // three copy commands between every two chunks)
 __global__ void service_status_kernel(const int* finished, const int* n_new, const int* n_active, int* out) {
@@ -89,6 +92,7 @@ extern "C" int sonic_service_begin(sonic_engine* e) {
     HIPC(e, stream_sync(e));
     hipLaunchKernelGGL(service_reset_kernel, dim3(1), dim3(64), 0, e->st, e->kv_len, e->tok_pos, e->n_new, e->finished, e->max_new_d, e->n_active);
     if (e->force_d) return fail(e, SONIC_ERR_INVALID, "teacher forcing is set: clear it before continuous decoding");
+    if (e->opt_grammar) { launch_fill_i32(gram_state_of(e), -1, 64, e->st); for (int r = 0; r < 64; ++r) gram_row_release(e, r); }      // the pool starts with free rows
     hipGraphExec_t gx = nullptr;                            // the chunk graphs exist before the first splice: nothing captures on this stream later
     if (e->Bm >= 2 && !e->i8) TRY(chunk_graph(e, 2, e->opt_decode_chunk > 0 ? e->opt_decode_chunk : 1, &gx, true));   // a pool with at most two occupied rows (round 6: five launches per layer)
     if (e->Bm >= 4 && !e->i8 && e->opt_decode_gemv) TRY(chunk_graph(e, 4, e->opt_decode_chunk > 0 ? e->opt_decode_chunk : 1, &gx, true));   // ... four, on the GEMV chain (opt-in)
@@ -138,6 +142,8 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
         return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in option request_bias: set it on the owner before its slots are created");
     if (d->opt_sampling != p->opt_sampling || (d->opt_sampling && !(p->samp.dev && d->samp.dev)))
         return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in option sampling: set it on the owner before its slots are created");
+    if (d->opt_grammar != p->opt_grammar || (d->opt_grammar && !(p->gram.dev && d->gram.dev)))
+        return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in option grammar: set it on the owner before its slots are created");
     if (n < 1 || n > 64 || p->greedy_calls < 1 || n > p->R) return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: %d rows, the source has %d prefilled requests", n, p->greedy_calls < 1 ? 0 : p->R);
     SpliceArgs a{};
     for (int i = 0; i < n; ++i) {
@@ -154,6 +160,15 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
     if (hist_on(d)) { a.hist_s = p->hist; a.hist_d = d->hist; }
     if (d->opt_request_bias) { a.bias_s = p->bias.dev; a.bias_d = d->bias.dev; }
     if (d->opt_sampling) { a.samp_s = p->samp.dev; a.samp_d = d->samp.dev; }
+    if (d->opt_grammar) {
+        a.gram_s = p->gram.dev; a.gram_d = d->gram.dev;
+        for (int i = 0; i < n; ++i) {                      // the row is handed over and its reference with it: the source row is free (the kernel resets its words)
+            sonic_grammar* g = p->gram_row[src_rows[i]];
+            p->gram_row[src_rows[i]] = nullptr;
+            gram_row_release(d, dst_rows[i]);
+            d->gram_row[dst_rows[i]] = g;
+        }
+    }
     if (d->i8) { a.hq_s = p->hn_q; a.hq_d = d->hn_q; a.sca_s = p->sca_hn; a.sca_d = d->sca_hn; a.oc_s = p->oc_hn; a.oc_d = d->oc_hn; a.ol_s = p->ol_hn; a.ol_d = d->ol_hn; a.ov_s = p->ov_hn; a.ov_d = d->ov_hn; }
     HIPC(d, hipEventRecord(p->xfer_ev, p->st));
     HIPC(d, hipStreamWaitEvent(d->st, p->xfer_ev, 0));
@@ -236,16 +251,17 @@ extern "C" int sonic_fetch_row(sonic_engine* e, int row, int n, int32_t* out_ids
         HIPC(e, hipMemcpyAsync(out_ids, e->out_ids + (size_t)row * e->out_cap, (size_t)n * 4, hipMemcpyDeviceToHost, e->st_io));
         HIPC(e, hipStreamSynchronize(e->st_io));
     }
-    hipLaunchKernelGGL(release_row_kernel, dim3(1), dim3(1), 0, e->st, e->kv_len, e->tok_pos, e->finished, row);
+    hipLaunchKernelGGL(release_row_kernel, dim3(1), dim3(1), 0, e->st, e->kv_len, e->tok_pos, e->finished, row, e->opt_grammar ? gram_state_of(e) : nullptr);
+    gram_row_release(e, row);                               // (a finished row changes no state and reads no automaton that matters: its reference can go)
     HIPC(e, hipGetLastError());
     return SONIC_OK;
 }
 
 // sonic_fetch_row for n rows in one call: the D2H copies go out together, one wait, one release launch - what a block of 32 finished rows costs
 // the host drops from 32 lock / copy / wait / launch rounds (about a chunk's worth of time, during which the loop's queue could run dry) to one
-__global__ void release_rows_kernel(int* kv_len, int* tok_pos, int* finished, SpliceArgs a, int n) {
+__global__ void release_rows_kernel(int* kv_len, int* tok_pos, int* finished, SpliceArgs a, int n, int* gram_state) {
     const int i = threadIdx.x;
-    if (i < n) { const int row = a.dst[i]; kv_len[row] = 1; tok_pos[row] = 0; finished[row] = 1; }
+    if (i < n) { const int row = a.dst[i]; kv_len[row] = 1; tok_pos[row] = 0; finished[row] = 1; if (gram_state) gram_state[row] = -1; }
 }
 static int fetch_rows_locked(sonic_engine* e, int n, const int32_t* rows, const int32_t* counts, int32_t* out_ids, int out_ld, float* out_lp) {
     const size_t w = (size_t)lp_width(e);
@@ -265,7 +281,8 @@ static int fetch_rows_locked(sonic_engine* e, int n, const int32_t* rows, const 
             if (out_lp) HIPC(e, hipMemcpyAsync(out_lp + (size_t)i * out_ld * w, e->out_lp + (size_t)rows[i] * e->out_cap * w, (size_t)counts[i] * w * 4, hipMemcpyDeviceToHost, e->st_io));
         }
     HIPC(e, hipStreamSynchronize(e->st_io));
-    hipLaunchKernelGGL(release_rows_kernel, dim3(1), dim3(64), 0, e->st, e->kv_len, e->tok_pos, e->finished, a, n);
+    hipLaunchKernelGGL(release_rows_kernel, dim3(1), dim3(64), 0, e->st, e->kv_len, e->tok_pos, e->finished, a, n, e->opt_grammar ? gram_state_of(e) : nullptr);
+    for (int i = 0; i < n; ++i) gram_row_release(e, rows[i]);
     HIPC(e, hipGetLastError());
     return SONIC_OK;
 }
@@ -288,7 +305,9 @@ extern "C" int sonic_fetch_rows_lp(sonic_engine* e, int n, const int32_t* rows, 
 static int run_staged_entry(sonic_engine* e) {
     const sonic_engine::AsyncJob& j = e->a_job;
     ENTER(e);
-    return run_all(e, j.has_rw ? j.req_win.data() : nullptr, j.R, j.prompt_ids.data(), j.prompt_off.data(), j.max_new.data(), j.want_logits != 0);
+    const int rc = run_all(e, j.has_rw ? j.req_win.data() : nullptr, j.R, j.prompt_ids.data(), j.prompt_off.data(), j.max_new.data(), j.want_logits != 0);
+    if (e->opt_grammar) gram_drop_staged(e);               // (a run that failed ahead of its prefill still consumed its grammars)
+    return rc;
 }
 static void async_loop(sonic_engine* e) {
     for (;;) {
@@ -501,6 +520,16 @@ int fetch_locked(sonic_engine* e, int32_t* out_ids, int out_ld, int32_t* out_len
             }
             if ((size_t)nn[r] * w > (size_t)out_ld) return fail(e, SONIC_ERR_INVALID, "out_ld too small");
             HIPC(e, d2h_async(e, out_lp + (size_t)r * out_ld, e->out_lp + (size_t)r * e->out_cap * w, (size_t)nn[r] * w * 4));
+        }
+    }
+    if (e->opt_grammar && !e->svc_on) {      // a batch whose every row has ended and whose ids are being fetched lets go of its grammars: the rows are free again
+        bool ended = true;                   // (state -1: a later sonic_decode_step reads no automaton)
+        for (int r = 0; r < R; ++r) ended = ended && fin[r];
+        bool any = false;
+        for (int r = 0; r < 64; ++r) any = any || e->gram_row[r];
+        if (ended && any) {
+            launch_fill_i32((int*)e->gram.dev, 0, 128, e->st); launch_fill_i32(gram_state_of(e), -1, 64, e->st);
+            for (int r = 0; r < 64; ++r) gram_row_release(e, r);
         }
     }
     if (step_logits) {

@@ -264,6 +264,7 @@ GreedyArgs greedy_args(sonic_engine* e, int R, bool dump) {
     if (e->opt_request_bias) g.bias_tab = e->bias.dev;
     if (g.out_lp) g.topk = e->opt_top_logprobs;                  // (likewise)
     if (e->opt_sampling && g.out_lp) g.samp = e->samp.dev;      // (the option is refused without token_logprobs, and token_logprobs cannot leave while it is on)
+    if (e->opt_grammar && g.out_lp && g.hist) { g.gram_ref = e->gram.dev; g.gram_state = gram_state_of(e); }      // (likewise; the option brought the history)
     if (e->i8) g.qo = QuantOut{e->hn_q, d.dec_d, e->sca_hn, e->oc_hn, e->ol_hn, d.dec_d, e->ov_hn};     // layer 0's q/k/v input, quantised
     return g;
 }
@@ -516,6 +517,7 @@ int reset_row_state(sonic_engine* e, int R, int n_tok) {
     launch_fill_i32(e->step_ctr, 0, 64, e->st);
     if (hist_on(e)) launch_hist_prompt(e->src, e->tok_seq, e->tok_pos_pf, n_tok, e->d.audio_token_id, e->hist, e->max_ctx, e->st);    // the rows' input_ids for the guards / the request bias
     TRY(bias_upload(e, R));                                                                                                         // every request's table, or a zero count, into its row
+    TRY(gram_upload(e, R));                                                                                                         // every request's grammar at its start node, or a free row
     return samp_upload(e, R);                                                                                                       // every request's (temperature, seed), or zeros: greedy
 }
 
@@ -580,12 +582,13 @@ int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int
         HIPC(e, hipStreamWaitEvent(e->st, e->wait_ev, 0));  // engine's KV cache and row state, which this run is about to overwrite
         e->wait_pending = false;
     }
-    const int bias_R = e->bias.claim(), samp_R = e->samp.claim();      // sonic_set_request_bias / _sampling: this batch consumes what they left whatever becomes of it (ENTER_CONSUME drops it on every other exit)
+    const int bias_R = e->bias.claim(), samp_R = e->samp.claim(), gram_R = e->gram.claim();      // sonic_set_request_bias / _sampling / option request_grammar: this batch consumes what they left whatever becomes of it (ENTER_CONSUME drops it on every other exit)
     TRY(stage_count(e, bias_R, R, "sonic_set_request_bias", "tables"));
     TRY(stage_count(e, samp_R, R, "sonic_set_request_sampling", "values"));
+    TRY(stage_count(e, gram_R, R, "option request_grammar_begin", "grammars"));
     HostPlan hp;
     TRY(plan_requests(e, req_win, R, prompt_ids, prompt_off, max_new, hp));
-    e->bias.take = bias_R >= 0; e->samp.take = samp_R >= 0;
+    e->bias.take = bias_R >= 0; e->samp.take = samp_R >= 0; e->gram.take = gram_R >= 0;
     {   // staging buffer of this run: the one used two runs ago; its copies are almost always long done (a blocking wait otherwise)
         const int i = e->plan_idx ^ 1;
         if (e->plan_busy[i]) { HIPC(e, hipEventSynchronize(e->plan_ev[i])); e->plan_busy[i] = false; }
@@ -632,7 +635,7 @@ int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int
 // svc: the chunk belongs to a continuous decode loop (sonic_service_*), i.e. it runs beside a prefill slot and other loops by design - decode_step then
 // picks the forms that cost the fewest CU-microseconds rather than the shortest chain (gu64_split_norm).  Same bits either way; cached separately.
 int chunk_graph(sonic_engine* e, int R, int n, hipGraphExec_t* out, bool svc) {
-    const std::pair<int, int> key{R + (svc ? 4096 : 0) + (e->opt_token_logprobs ? 8192 : 0) + (e->gen_on ? 16384 : 0) + (e->opt_request_bias ? 32768 : 0) + (e->opt_sampling ? 65536 : 0) + e->opt_top_logprobs * 131072, n};   // (the LP / GUARD / BIAS / SAMPLE / TOPK greedy kernel and its pointers are part of the capture)
+    const std::pair<int, int> key{R + (svc ? 4096 : 0) + (e->opt_token_logprobs ? 8192 : 0) + (e->gen_on ? 16384 : 0) + (e->opt_request_bias ? 32768 : 0) + (e->opt_sampling ? 65536 : 0) + e->opt_top_logprobs * 131072 + (e->opt_grammar ? (1 << 21) : 0), n};   // (the LP / GUARD / BIAS / SAMPLE / TOPK / GRAMMAR greedy kernel and its pointers are part of the capture)
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) { *out = it->second; return SONIC_OK; }
     hipGraph_t g = nullptr; hipGraphExec_t gx = nullptr;
@@ -759,10 +762,11 @@ static int run_forced_parallel(sonic_engine* e, const int32_t* req_win, int R, c
     if (!e->finalized) return fail(e, SONIC_ERR_INVALID, "weights not finalized");
     if (e->W < 1) return fail(e, SONIC_ERR_INVALID, "no PCM staged");
     if (e->svc_on) return fail(e, SONIC_ERR_INVALID, "this handle is decoding continuously (sonic_service_begin): prefill on another slot and splice the rows in");
-    const int bias_R = e->bias.claim(), samp_R = e->samp.claim();      // consumed, as on every other exit
-    if (bias_R >= 0 || samp_R >= 0)
+    const int bias_R = e->bias.claim(), samp_R = e->samp.claim(), gram_R = e->gram.claim();      // consumed, as on every other exit
+    if (gram_R >= 0) gram_drop_staged(e);
+    if (bias_R >= 0 || samp_R >= 0 || gram_R >= 0)
         return fail(e, SONIC_ERR_INVALID, "forced_parallel: the parallel forced run applies no processors: the staged %s are refused (it scores the raw distribution; run with the option off to force step by step under them)",
-                    bias_R >= 0 ? "request bias tables (sonic_set_request_bias)" : "sampling values (sonic_set_request_sampling)");
+                    bias_R >= 0 ? "request bias tables (sonic_set_request_bias)" : samp_R >= 0 ? "sampling values (sonic_set_request_sampling)" : "grammars (option request_grammar)");
     const int N = e->opt_forced_fanout;
     if (R < 1 || R > e->Bm) return fail(e, SONIC_ERR_INVALID, "request count %d out of range 1..%d", R, e->Bm);
     if (R % N) return fail(e, SONIC_ERR_INVALID, "forced_fanout: %d sequences are not a multiple of the fan-out %d", R, N);
@@ -832,7 +836,7 @@ static int run_forced_parallel(sonic_engine* e, const int32_t* req_win, int R, c
         if (e->plan_busy[i]) { HIPC(e, hipEventSynchronize(e->plan_ev[i])); e->plan_busy[i] = false; }
         e->plan_idx = i; e->plan_h = e->plan_buf[i];
     }
-    e->bias.take = false; e->samp.take = false;
+    e->bias.take = false; e->samp.take = false; e->gram.take = false;
     e->R = R; e->max_steps = max_steps; e->last_maxnew = hp.max_new;
     e->last_qlen.resize(R);
     for (int r = 0; r < R; ++r) e->last_qlen[r] = (int)(prompt_off[r + 1] - prompt_off[r]);      // the PROMPT's length: fetch_locked expects kv_len = prompt + tokens - 1

@@ -71,6 +71,14 @@ static int raw_alloc(sonic_engine* e, const std::string& name, const std::vector
 
 extern "C" int sonic_load_tensor(sonic_engine* e, const char* name, const void* data, int dtype, const int64_t* shape, int ndim) {
     if (!e || !name || !data || !shape) return SONIC_ERR_INVALID;
+    // grammars are int32 "tensors" of a finalized engine: "grammar:<id>" creates (shape {0}: destroys) one on the weight owner, without the
+    // engine lock; "grammar.dispatch:<id>" arms the calling thread's next dispatcher submit, likewise; "grammar.hook:<V>" arms the kernel hooks' automaton
+    if (!strncmp(name, "grammar.dispatch:", 17)) return gram_dispatch_arm(e, atoi(name + 17));      // (the calling thread's next dispatcher submit; no words are read)
+    if (!strncmp(name, "grammar:", 8) || !strncmp(name, "grammar.hook:", 13)) {
+        if (dtype != SONIC_DTYPE_I32 || ndim != 1 || shape[0] < 0) return fail(nullptr, SONIC_ERR_INVALID, "%s: a grammar is one row of int32 words (SONIC_DTYPE_I32, ndim 1)", name);
+        if (name[7] == ':') return gram_create(e, atoi(name + 8), (const int*)data, shape[0]);
+        return gram_hook_arm(e, atoi(name + 13), (const int*)data, shape[0]);
+    }
     ENTER(e);
     if (e->finalized) return fail(e, SONIC_ERR_INVALID, "weights already finalized");
     std::vector<int64_t> shp(shape, shape + ndim);

@@ -1,7 +1,7 @@
 // The greedy controller: fused argmax over the lm_head's partial slabs + HF's greedy loop bookkeeping + the next step's embedding row and
-// first RMSNorm, one block per row.  One kernel body, templated on the activation dtype T and five flags - LP (per-token log-probabilities), GUARD (HF's logits
-// processors), BIAS (per-request sequence bias), SAMPLE (temperature sampling), TOPK (the best alternatives of every step) - in the fifteen combinations
-// launch_greedy's table lists; and the prefill's kernel
+// first RMSNorm, one block per row.  One kernel body, templated on the activation dtype T and six flags - LP (per-token log-probabilities), GUARD (HF's logits
+// processors), BIAS (per-request sequence bias), SAMPLE (temperature sampling), TOPK (the best alternatives of every step), GRAMMAR (a token automaton per
+// request) - in the twenty-three combinations launch_greedy's table lists; and the prefill's kernel
 // that writes a request's prompt ids into its history row for GUARD / BIAS.  Shares quant_emit_row (int8_util.h) with the decode-step consumers of elementwise.hip.
 #include "common.h"
 #include "kernels.h"
@@ -46,6 +46,15 @@
 // unique), so the result does not depend on how the reduction is arranged.  Lanes 0 .. K - 1 of wave 1 write the record [lp | K alternative lps | K ids as fp32]
 // at out_lp[(b * out_ld + n) * (1 + 2K)]; places beyond the finite scores hold (-inf, -1).  Forcing and sampling change the emitted token, never the
 // alternatives; a finished row writes nothing.  TOPK = false is the kernel as it was: everything that belongs to the lists sits behind `if constexpr (TOPK)`.
+// GRAMMAR (option grammar; LP and GUARD only): HF's PrefixConstrainedLogitsProcessor on a deterministic token automaton in CSR form that lives on
+// the device (GreedyArgs.gram_ref[row]: [N | E | node_off[N + 1] | edge_tok[E] | edge_next[E]]; the edges of a node ascend by token id).  The row's state word
+// gram_state[row] is -1 (free: the kernel as it was), n >= 0 (at node n) or -2 (it has left the grammar).  The prologue ORs the bits of the ids the row may emit -
+// the edge tokens of n; the handle's EOS ids at -2 - into the zeroed "banned" map and inverts the map's words (the pad bits beyond V come out set: banned), two more
+// barriers and one pass over the map; the n-gram and suppress bans then OR in as before.  Bans commute, so the fold gives the tokens of HF's chain SequenceBias ->
+// RepetitionPenalty -> NoRepeatNGram -> NoBadWords -> PrefixConstrained -> SuppressTokens; compare, LP sum, top-k lists and the Gumbel draw all run over the masked
+// scores.  Thread 0 looks the emitted id - argmax, sample or forced id - up among the node's edges by binary search: found, the state is that edge's `next`; not
+// found (a forced id outside the grammar, token 0 of a row whose allowed ids were all banned, any id at -2), it is -2.  A finished row changes nothing; no LDS is
+// added.  GRAMMAR = false is the kernel as it was.
 // tk_insert / tk_merge (the lists and their wave merge) and lp_exp live in topk.h: score.hip shares them
 extern __shared__ unsigned g_bits[];
 __device__ __forceinline__ float guard_score(float r, unsigned seen, unsigned banned, float p) {
@@ -77,8 +86,9 @@ __device__ __forceinline__ float gumbel_of(unsigned word) {
     return -logf(-logf(u));
 }
 #define LPB (SAMPLE ? rmax : best)      // what the LP sum is taken against: the running maximum of s
-template <typename T, bool LP, bool GUARD = false, bool BIAS = false, bool SAMPLE = false, bool TOPK = false>
+template <typename T, bool LP, bool GUARD = false, bool BIAS = false, bool SAMPLE = false, bool TOPK = false, bool GRAMMAR = false>
 __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
+    static_assert(!GRAMMAR || (LP && GUARD), "the grammar lives in the log-probability guard instantiations (it reuses their banned map)");
     static_assert(LP || !TOPK, "the alternatives live in the log-probability instantiations (they share their sum)");
     static_assert(GUARD || !BIAS, "the request bias lives in the guard instantiations (it needs their history)");
     static_assert(LP || !SAMPLE, "sampling lives in the log-probability instantiations (the fallback ladder reads them)");
@@ -117,11 +127,26 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
     if (a.y && (a.d >> 3) <= 1024 && tid < (a.d >> 3)) { gw0 = *(const f32x4*)(a.norm_w + tid * 8); gw1 = *(const f32x4*)(a.norm_w + tid * 8 + 4); }
     [[maybe_unused]] unsigned* g_seen = nullptr; [[maybe_unused]] unsigned* g_ban = nullptr;
     [[maybe_unused]] unsigned* g_bia = nullptr; [[maybe_unused]] int* q_id = nullptr; [[maybe_unused]] float* q_sum = nullptr; [[maybe_unused]] int q_n = 0;
+    [[maybe_unused]] int gst = -1, g_lo = 0, g_hi = 0; [[maybe_unused]] const int* g_tok = nullptr; [[maybe_unused]] const int* g_next = nullptr;      // GRAMMAR: the row's state and its node's edges
     if constexpr (GUARD) {
         const int nw = (a.V + 31) >> 5;
         g_seen = g_bits; g_ban = g_bits + nw;
         for (int w = tid; w < (BIAS ? 3 : 2) * nw; w += 1024) g_bits[w] = 0u;
         __syncthreads();
+        if constexpr (GRAMMAR) {
+            // the row's automaton; a state the blob does not hold (never staged by the engine) counts as "left"
+            gst = a.gram_state[b];
+            const int* gb = (const int*)a.gram_ref[b];
+            if (gst >= 0 && (!gb || gst >= gb[0])) gst = -2;
+            if (gst >= 0) { g_tok = gb + GRAM_HEAD + gb[0] + 1; g_next = g_tok + gb[1]; g_lo = max(gb[GRAM_HEAD + gst], 0); g_hi = min(gb[GRAM_HEAD + gst + 1], gb[1]); }
+            if (gst != -1) {                      // block-uniform: the barriers below are reached by every thread or by none
+                if (gst >= 0) for (int k = g_lo + tid; k < g_hi; k += 1024) guard_set(g_ban, g_tok[k], a.V);
+                else if (tid < a.n_eos) guard_set(g_ban, a.eos[tid], a.V);
+                __syncthreads();
+                for (int w = tid; w < nw; w += 1024) g_ban[w] = ~g_ban[w];      // allowed -> banned; the pad bits beyond V are banned too
+                __syncthreads();
+            }
+        }
         const int* h = a.hist + (long)b * a.hist_ld;
         const int len = min(max(a.kv_len[b], 0), a.hist_ld), n = a.ngram;
         if constexpr (BIAS) {
@@ -286,6 +311,12 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
                 if constexpr (TOPK) { tk_col = a.n_new[b]; tk_m = LPB; tk_sum = lp_sum; }
             }
             if constexpr (GUARD) { const int pos = a.kv_len[b]; if (pos >= 0 && pos < a.hist_ld) a.hist[(long)b * a.hist_ld + pos] = tok; }   // the token's position
+            if constexpr (GRAMMAR) if (gst != -1) {      // the transition: the emitted id among the node's ascending edge tokens, by bisection
+                int ns = -2, lo = g_lo, hi = g_hi;
+                while (lo < hi) { const int mid = (lo + hi) >> 1; if (g_tok[mid] < tok) lo = mid + 1; else hi = mid; }
+                if (gst >= 0 && lo < g_hi && g_tok[lo] == tok) ns = g_next[lo];
+                a.gram_state[b] = ns;
+            }
             const int nn = a.n_new[b] + 1;
             a.n_new[b] = nn;
             bool stop = nn >= a.max_new[b];
@@ -366,17 +397,29 @@ void launch_hist_prompt(const int* src, const int* tok_seq, const int* tok_pos, 
 }
 size_t greedy_guard_lds(int V, bool bias) { return (size_t)(bias ? 3 : 2) * ((V + 31) / 32) * 4 + (bias ? (size_t)3 * BIAS_MAX_ENTRIES * 4 : 0); }
 // One family of the table below: its grid, block and LDS request, for fp32 rows (SONIC_MODE_F32: fp32 logits, table and rows) and for the 16-bit kinds
-template <bool LP, bool GUARD, bool BIAS, bool SAMPLE, bool TOPK = false>
+template <bool LP, bool GUARD, bool BIAS, bool SAMPLE, bool TOPK = false, bool GRAMMAR = false>
 static void greedy_launch(const GreedyArgs& a, hipStream_t s) {
-    const size_t lds = GUARD ? greedy_guard_lds(a.V, BIAS) : 0;      // GUARD: two vocabulary bitmaps of dynamic LDS; BIAS: a third and the matched list
-    if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, LP, GUARD, BIAS, SAMPLE, TOPK>), dim3(a.B), dim3(1024), lds, s, a); return; }
-    DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, LP, GUARD, BIAS, SAMPLE, TOPK>), dim3(a.B), dim3(1024), lds, s, a));
+    const size_t lds = GUARD ? greedy_guard_lds(a.V, BIAS) : 0;      // GUARD: two vocabulary bitmaps of dynamic LDS; BIAS: a third and the matched list; GRAMMAR: nothing more
+    if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, LP, GUARD, BIAS, SAMPLE, TOPK, GRAMMAR>), dim3(a.B), dim3(1024), lds, s, a); return; }
+    DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, LP, GUARD, BIAS, SAMPLE, TOPK, GRAMMAR>), dim3(a.B), dim3(1024), lds, s, a));
 }
-// The fifteen families, chosen from the arguments: out_lp = option token_logprobs, hist = generation guards, bias_tab (counts only together with hist) = request
-// bias, samp (counts only together with out_lp) = option sampling, topk in 1 .. 8 (counts only together with out_lp) = option top_logprobs.  One line per family: a
-// combination that is not listed is not instantiated.
+// The twenty-three families, chosen from the arguments: out_lp = option token_logprobs, hist = generation guards, bias_tab (counts only together with hist) = request
+// bias, samp (counts only together with out_lp) = option sampling, topk in 1 .. 8 (counts only together with out_lp) = option top_logprobs, gram_state with gram_ref
+// (counts only together with out_lp and hist) = option grammar.  One line per family: a combination that is not listed is not instantiated.
 void launch_greedy(const GreedyArgs& a, hipStream_t s) {
     const bool lp = a.out_lp != nullptr, guard = a.hist != nullptr, bias = guard && a.bias_tab, sample = lp && a.samp, topk = lp && a.topk >= 1 && a.topk <= 8;
+    const bool gram = lp && guard && a.gram_state && a.gram_ref;
+    if (gram) {
+        //                                        LP     GUARD  BIAS   SAMPLE TOPK   GRAMMAR
+        if (topk && sample && bias)  return greedy_launch<true,  true,  true,  true,  true,  true >(a, s);
+        if (topk && sample)          return greedy_launch<true,  true,  false, true,  true,  true >(a, s);
+        if (topk && bias)            return greedy_launch<true,  true,  true,  false, true,  true >(a, s);
+        if (topk)                    return greedy_launch<true,  true,  false, false, true,  true >(a, s);
+        if (sample && bias)          return greedy_launch<true,  true,  true,  true,  false, true >(a, s);
+        if (sample)                  return greedy_launch<true,  true,  false, true,  false, true >(a, s);
+        if (bias)                    return greedy_launch<true,  true,  true,  false, false, true >(a, s);
+        return greedy_launch<true,  true,  false, false, false, true >(a, s);
+    }
     //                                        LP     GUARD  BIAS   SAMPLE TOPK
     if (topk && sample && bias)  return greedy_launch<true,  true,  true,  true,  true >(a, s);
     if (topk && sample && guard) return greedy_launch<true,  true,  false, true,  true >(a, s);

@@ -119,6 +119,12 @@ struct GreedyArgs {
     // (1 .. BIAS_MAX_LEN), the fp32 bias (its bits), the L - 1 ids in front of the last one.  The host stores a row's entries grouped by last id, the length-1
     // entry of a group first and the others in list order (bias_pack, engine.cpp): one thread adds a group in the contract's order.  Needs hist.
     const int* bias_tab;
+    // grammar-constrained decoding (greedy_kernel<T, true, true, ., ., ., true>, option grammar); gram_state = NULL: off.  gram_state[64]: the row's
+    // state word - -1 free (no grammar: the kernel behaves as without the flag), n >= 0 the node it is at, -2 it has left its grammar (only the EOS ids remain) - read
+    // by the prologue and written by thread 0 behind the emitted id.  gram_ref[64]: the device address of the row's automaton (0 for a free row), GRAM_HEAD words
+    // (nodes N, edges E), then node_off[N + 1], edge_tok[E] (ascending inside a node), edge_next[E].  Needs out_lp and hist.  (Ahead of the sampling fields, which
+    // stay the struct's last.)
+    int* gram_state; const unsigned long long* gram_ref;
     // temperature sampling (greedy_kernel<T, true, ., ., true>, option sampling).  noise_out: optional [B][V], the Gumbel value the kernel added at
     // every id of a row with t > 0 (test hook; production passes NULL, as for the dump).  samp = NULL: off; else three words per row, 64 rows: the bits of the row's
     // fp32 temperature (0: greedy), its seed's low word, its high word.  The row's step index is n_new[row].  Needs out_lp.  Last: every offset above is what it was
@@ -130,6 +136,10 @@ struct GreedyArgs {
     int topk;
 };
 #define SAMP_WORDS (64 * 3)
+#define GRAM_HEAD 2
+#define GRAM_MAX_NODES 65536
+#define GRAM_MAX_EDGES 1048576
+#define GRAM_STAGE_WORDS (64 + 32)      // 64-bit words of a handle's grammar stage: the 64 rows' references, then their 64 32-bit state words
 #define BIAS_MAX_ENTRIES 256
 #define BIAS_MAX_LEN 8
 #define BIAS_ENTRY_WORDS (3 + BIAS_MAX_LEN - 1)

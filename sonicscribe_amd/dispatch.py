@@ -46,9 +46,10 @@ def step_class(max_new: int) -> int:
 
 
 class Request:
-    __slots__ = ("windows", "prompt", "max_new", "future", "t_submit", "cls", "want_logprobs", "bias", "sampling")
+    __slots__ = ("windows", "prompt", "max_new", "future", "t_submit", "cls", "want_logprobs", "bias", "sampling", "grammar")
 
-    def __init__(self, windows: Sequence[Any], prompt: Sequence[int], max_new: int, want_logprobs: bool = False, bias=None, sampling=None):
+    def __init__(self, windows: Sequence[Any], prompt: Sequence[int], max_new: int, want_logprobs: bool = False, bias=None, sampling=None, grammar=None):
+        self.grammar = grammar                        # its grammar (grammar.CompiledGrammar: a device handle per replica; engine option grammar); None: a free request
         self.sampling = None if sampling is None else (float(sampling[0]), int(sampling[1]))      # its own (temperature, seed) (engine option sampling); None: greedy
         self.windows, self.prompt, self.max_new = list(windows), prompt, int(max_new)
         self.bias = bias if bias else None            # its own sequence-bias table (reqbias.RequestBias; engine option request_bias): it travels with the request
@@ -56,6 +57,14 @@ class Request:
         self.future: Future = Future()
         self.t_submit = time.perf_counter()
         self.cls = step_class(self.max_new)
+
+
+def _device_grammar(req: "Request", engine):
+    """the request's grammar as the handle that lives on `engine`'s weight owner (None: a free request)"""
+    return None if req.grammar is None else req.grammar.on(engine)
+
+
+GRAMMAR_OFF = "a grammar needs the engine option grammar on every handle (ASRModel(token_logprobs=True, grammar=True))"
 
 
 class _Replica:
@@ -137,6 +146,9 @@ class _Replica:
         samp_on = bool(getattr(engine, "sampling", False))
         if samp_on or any(r.sampling for r in batch):
             kw["request_sampling"] = [r.sampling for r in batch]
+        gram_on = bool(getattr(engine, "grammar", False))
+        if gram_on or any(r.grammar for r in batch):      # (likewise: every batch states its grammars, None = a free request)
+            kw["request_grammar"] = [_device_grammar(r, engine) for r in batch]
         try:
             if want:
                 ids, _, lps = engine.transcribe_batch(segs, [r.prompt for r in batch], [r.max_new for r in batch], req_win=req_win, want_logprobs=True, **kw)
@@ -151,6 +163,8 @@ class _Replica:
                 kw1 = {"request_bias": [r.bias]} if stated or r.bias else {}
                 if samp_on or r.sampling:
                     kw1["request_sampling"] = [r.sampling]
+                if gram_on or r.grammar:
+                    kw1["request_grammar"] = [_device_grammar(r, engine)]
                 try:
                     if r.want_logprobs:
                         one, _, lp1 = engine.transcribe_batch(r.windows, [r.prompt], [r.max_new], req_win=[0, len(r.windows)], want_logprobs=True, **kw1)
@@ -259,6 +273,10 @@ class _ContinuousReplica:
             raise ValueError("a sequence bias needs the engine option request_bias on every handle (ASRModel(request_bias=True))")
         if req.sampling and not all(getattr(e, "sampling", False) for e in self.engines):
             raise ValueError("a temperature needs the engine option sampling on every handle (ASRModel(sampling=True))")
+        if req.grammar and not all(getattr(e, "grammar", False) for e in self.engines):
+            raise ValueError(GRAMMAR_OFF)
+        if req.grammar:
+            req.grammar.on(self.engine)                   # (ValueError here for a grammar of another model, not in the prefill thread)
         with self.cv:
             if self.stop:
                 raise RuntimeError("ASR engine is closed")
@@ -308,6 +326,8 @@ class _ContinuousReplica:
             eng.set_request_bias([r.bias for r in batch])
         if getattr(eng, "sampling", False) or any(r.sampling for r in batch):      # (likewise: every prefill states its values, None = greedy)
             eng.set_request_sampling([r.sampling for r in batch])
+        if getattr(eng, "grammar", False) or any(r.grammar for r in batch):        # (likewise: None = a free request)
+            eng.set_request_grammar([_device_grammar(r, eng) for r in batch])
         # waited for: a splice queued behind a prefill that is still running would hold the decoder's whole stream (every running row) at the
         # event until the prefill is done - final p50 at 128 sessions 438 -> 657 ms when the hand-over came early.  (The bulk pipeline hands over
         # early, sonicscribe_amd/pipeline.py: its next batch is long done when a block frees up.)
@@ -467,6 +487,7 @@ class _NativeContinuousReplica:
         self.lp = all(getattr(e, "token_logprobs", False) for e in self.engines)      # then completions are collected with their log-probabilities
         self.bias = all(getattr(e, "request_bias", False) for e in self.engines)      # then a request may bring its own sequence-bias table
         self.samp = all(getattr(e, "sampling", False) for e in self.engines)          # then a request may bring its own (temperature, seed)
+        self.gram = all(getattr(e, "grammar", False) for e in self.engines)           # then a request may bring its grammar
         self.thread = threading.Thread(target=self._complete_loop, name=f"sonic-dispatch-{index}.complete", daemon=True)
         self.thread.start()
 
@@ -502,8 +523,11 @@ class _NativeContinuousReplica:
             raise ValueError("a sequence bias needs the engine option request_bias on every handle (ASRModel(request_bias=True))")
         if req.sampling and not self.samp:
             raise ValueError("a temperature needs the engine option sampling on every handle (ASRModel(sampling=True))")
+        if req.grammar and not self.gram:
+            raise ValueError(GRAMMAR_OFF)
         if req.bias:
             req.bias.check_vocab(self.engine.dims.vocab)
+        dev_gram = _device_grammar(req, self.engine)
         wins = req.windows
         W = len(wins)
         offs = np.zeros(W + 1, np.int64)
@@ -522,25 +546,35 @@ class _NativeContinuousReplica:
         ring_arr = (C.c_void_p * W)(*rings) if any_ring else None
         prompt = np.ascontiguousarray(req.prompt, dtype=np.int32)
         t = C.c_int64(0)
+        # everything that can raise is packed before the grammar is armed: the arm is the call right ahead of the submit
+        b_ids, b_off, b_val = req.bias.table() if req.bias else (None, None, np.zeros(0, np.float32))
+        if req.sampling:
+            from . import sampling as _sampling
+            temp, seed = _sampling.check_temperature(req.sampling[0]), _sampling.check_seed(req.sampling[1])
+        if dev_gram is not None and dev_gram.h is None:
+            raise ValueError("grammar: the grammar has been closed")
         with self.lock:
             if self.stop:
                 raise RuntimeError("ASR engine is closed")
+            if dev_gram is not None:
+                # this thread's next submit, whichever of the three below, carries the grammar (sonic_load_tensor "grammar.dispatch:<id>": the owner's registry and a
+                # thread-local, never the lock of an engine - the decode loop holds its handle's for a chunk at a time, and put() must not wait for it)
+                one = np.zeros(1, np.int32)
+                if self.lib.sonic_load_tensor(self.engine.h, f"grammar.dispatch:{int(dev_gram.id)}".encode(), _p(one), 2, (C.c_int64 * 1)(0), 1) != 0:
+                    raise ValueError("grammar: " + (self.lib.sonic_last_error(None) or b"").decode())
             if req.sampling:
-                from . import sampling as _sampling
-                b_ids, b_off, b_val = req.bias.table() if req.bias else (None, None, np.zeros(0, np.float32))
                 rc = self.lib.sonic_dispatch_submit_sampled(self.h, _p(pcm), _p(offs), ring_arr, _p(start) if any_ring else None, _p(n) if any_ring else None, W,
-                                                            _p(prompt), len(prompt), int(req.max_new), _sampling.check_temperature(req.sampling[0]),
-                                                            _sampling.check_seed(req.sampling[1]), _p(b_ids), _p(b_off), _p(b_val) if len(b_val) else None, len(b_val), C.byref(t))
+                                                            _p(prompt), len(prompt), int(req.max_new), temp, seed,
+                                                            _p(b_ids), _p(b_off), _p(b_val) if len(b_val) else None, len(b_val), C.byref(t))
             elif req.bias:
-                b_ids, b_off, b_val = req.bias.table()
                 rc = self.lib.sonic_dispatch_submit_bias(self.h, _p(pcm), _p(offs), ring_arr, _p(start) if any_ring else None, _p(n) if any_ring else None, W,
                                                          _p(prompt), len(prompt), int(req.max_new), _p(b_ids), _p(b_off), _p(b_val), len(b_val), C.byref(t))
             else:
                 rc = self.lib.sonic_dispatch_submit(self.h, _p(pcm), _p(offs), ring_arr, _p(start) if any_ring else None, _p(n) if any_ring else None, W,
                                                     _p(prompt), len(prompt), int(req.max_new), C.byref(t))
-            if rc != 0 and (req.bias or req.sampling):
+            if rc != 0 and (req.bias or req.sampling or req.grammar):
                 msg = (self.lib.sonic_last_error(None) or b"").decode()
-                if "request_bias" in msg or "sonic_dispatch_submit_bias" in msg or "sampling" in msg or "sonic_dispatch_submit_sampled" in msg:
+                if "request_bias" in msg or "sonic_dispatch_submit_bias" in msg or "sampling" in msg or "sonic_dispatch_submit_sampled" in msg or "grammar" in msg:
                     raise ValueError(msg)
             if rc != 0:
                 raise RuntimeError("ASR engine failed" if rc not in (1,) else "ASR engine is closed or the request is malformed")
@@ -651,6 +685,8 @@ class _BulkReplica:
             raise TypeError("bulk mode takes host PCM windows or slices of device rings")
         if req.bias:                                      # refused, not dropped: the bulk pipeline (csrc/pipeline.cpp) carries no per-request tables
             raise ValueError("a sequence bias is not supported with bulk=True (the bulk pipeline carries no per-request tables): use the continuous or the batch dispatcher")
+        if req.grammar:                                   # likewise: no per-request state travels through the bulk pipeline
+            raise ValueError("a grammar is not supported with bulk=True (the bulk pipeline carries no per-request grammar state): use the continuous or the batch dispatcher")
         if req.sampling:                                  # likewise: no per-request values travel through the bulk pipeline
             raise ValueError("a temperature is not supported with bulk=True (the bulk pipeline carries no per-request values): use the continuous or the batch dispatcher")
         with self.cv:
@@ -811,12 +847,12 @@ class Dispatcher:
             return self.replicas[least]                                     # rebalance: the home replica is more than a batch behind
         return self.replicas[home]
 
-    def submit(self, windows, prompt, max_new: int, session: Optional[str] = None, replica: Optional[int] = None, want_logprobs: bool = False, bias=None, sampling=None) -> Future:
+    def submit(self, windows, prompt, max_new: int, session: Optional[str] = None, replica: Optional[int] = None, want_logprobs: bool = False, bias=None, sampling=None, grammar=None) -> Future:
         """`replica` pins the request (windows that are slices of a device ring can only be decoded where the ring lives).  want_logprobs: the
         future resolves to (ids, log-probabilities) - the engines need option token_logprobs.  bias: the request's own sequence-bias table
         (reqbias.RequestBias) - the engines need option request_bias; refused with bulk=True.  sampling: the request's own (temperature, seed) - the engines
-        need option sampling; refused with bulk=True."""
-        req = Request(windows, prompt, max_new, want_logprobs, bias, sampling)
+        need option sampling; refused with bulk=True.  grammar: the request's grammar.CompiledGrammar - the engines need option grammar; refused with bulk=True."""
+        req = Request(windows, prompt, max_new, want_logprobs, bias, sampling, grammar)
         (self.replicas[replica] if replica is not None else self.pick(session)).put(req)
         return req.future
 

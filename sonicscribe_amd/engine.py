@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import threading
 from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
@@ -18,7 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "csrc", "libsonic_hip.so")
 
 MODE_NATIVE, MODE_INT8, MODE_F16, MODE_F32 = 0, 1, 2, 3
-DTYPE_F32, DTYPE_BF16 = 0, 1
+DTYPE_F32, DTYPE_BF16, DTYPE_I32 = 0, 1, 2
 SONIC_ERR_MISMATCH, SONIC_ERR_UNSUPPORTED = 4, 5
 
 ABI_VERSION = 12
@@ -275,6 +276,48 @@ class Ring:
             pass
 
 
+_GRAMMAR_IDS = threading.Lock()
+
+
+def grammar_words(grammar) -> np.ndarray:
+    """a grammar.Grammar as the int32 words the library takes (include/sonic_hip.h): N | E | node_off | edge_tok | edge_next"""
+    return np.ascontiguousarray(np.concatenate([[grammar.n_nodes, grammar.n_edges], grammar.node_off, grammar.edge_tok, grammar.edge_next]), dtype=np.int32)
+
+
+class DeviceGrammar:
+    """A grammar.Grammar on the device (sonic_load_tensor "grammar:<id>"): lives on a weight owner under `id`, serves every handle of it and any number of requests;
+    `grammar` is the host automaton it was made from.  close() raises SonicError while a staged or running request refers to it; the owner's close() takes what is left."""
+
+    def __init__(self, engine: "Engine", grammar):
+        root = engine.root
+        self.engine, self.grammar = root, grammar
+        words = grammar_words(grammar)
+        with _GRAMMAR_IDS:                                   # (two threads compiling at once must not pick the same id)
+            if not hasattr(root, "_grammars"):
+                root._grammars = []
+            used = {g.id for g in root._grammars}
+            self.id = next(i for i in range(1, 65536) if i not in used)
+            self._load(words)
+            self.h = self.id
+            root._grammars.append(self)
+
+    def _load(self, words: np.ndarray):
+        shape = (C.c_int64 * 1)(len(words))
+        w = words if len(words) else np.zeros(1, np.int32)
+        rc = self.engine.lib.sonic_load_tensor(self.engine.h, f"grammar:{self.id}".encode(), _p(w), DTYPE_I32, shape, 1)
+        if rc != 0:
+            raise SonicError((self.engine.lib.sonic_last_error(None) or b"").decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            with _GRAMMAR_IDS:
+                if getattr(self.engine, "h", None):
+                    self._load(np.zeros(0, np.int32))        # shape {0}: destroy
+                self.h = None
+                if self in getattr(self.engine, "_grammars", []):
+                    self.engine._grammars.remove(self)
+
+
 class TokenScores(NamedTuple):
     """A request's log-probabilities on a handle with option top_logprobs = K > 0: `lp` [n] float32 (the emitted tokens'), `top_logprobs` [n, K] float32 and
     `top_ids` [n, K] int32 - at every step the K best ids by (score descending, id ascending) among the ids with a finite score, with their log-probabilities;
@@ -342,6 +385,7 @@ class Engine(HooksMixin):
         s.top_logprobs = int(getattr(root, "top_logprobs", 0)) if s.token_logprobs else 0
         s.request_bias = bool(getattr(root, "request_bias", False))
         s.sampling = bool(getattr(root, "sampling", False))
+        s.grammar = bool(getattr(root, "grammar", False))
         s.forced_parallel = bool(getattr(root, "forced_parallel", False))
         s.forced_align = bool(getattr(root, "forced_align", False))
         root._slots.append(s)
@@ -376,6 +420,9 @@ class Engine(HooksMixin):
                 s.close()
             for r in list(getattr(self, "_rings", ())):      # rings belong to their engine and go first
                 r.close()
+            for g in list(getattr(self, "_grammars", ())):   # the library frees the grammars with their owner: the handles die here
+                g.h = None
+            self._grammars = []
             self.lib.sonic_destroy(self.h)
             self.h = None
             if self.owner is not None and self in self.owner._slots:
@@ -385,6 +432,23 @@ class Engine(HooksMixin):
         """Device-resident PCM ring of one streaming session (include/sonic_hip.h sonic_ring_*).  capacity_samples counts
         16 kHz samples; `rate` is the rate of the samples the appends bring (resampled on the device when it is not 16000)."""
         return Ring(self, capacity_samples, rate)
+
+    def grammar_create(self, grammar) -> "DeviceGrammar":
+        """a grammar.Grammar onto this engine's weight owner (sonic_load_tensor "grammar:<id>"): one handle for every slot and every request"""
+        return DeviceGrammar(self, grammar)
+
+    def set_request_grammar(self, grammars):
+        """The grammars of the requests of the NEXT prefill / run on this handle (options request_grammar_begin / request_grammar), one DeviceGrammar or None (a free
+        request) per request; that call consumes them.  Needs option grammar (SonicError naming it otherwise)."""
+        gs = list(grammars)
+        self._check(self.lib.sonic_set_option(self.h, b"request_grammar_begin", len(gs)))
+        for r, g in enumerate(gs):
+            if g is not None:
+                if g.h is None:
+                    raise SonicError("request_grammar: the grammar has been closed")
+                if g.engine is not self.root:         # (ids are per weight owner: another owner's id would name one of this owner's grammars)
+                    raise SonicError("request_grammar: the grammar lives on another weight owner (a grammar serves the engine it was created on and its slots)")
+                self._check(self.lib.sonic_set_option(self.h, b"request_grammar", (r << 16) | int(g.id)))
 
     def resample(self, x, in_rate: int, out_rate: int = 16000) -> np.ndarray:
         """torchaudio.transforms.Resample(in_rate, out_rate)(x) on the device (sonic_resample; asr.py:255-261): x is int16 PCM (taken as
@@ -495,12 +559,14 @@ class Engine(HooksMixin):
         return pcm, offs, rings, start, n
 
     def transcribe_batch(self, segments: Sequence[Any], prompts: Sequence[Sequence[int]], max_new: Sequence[int],
-                         req_win: Optional[Sequence[int]] = None, want_logits: bool = False, want_logprobs: bool = False, request_bias=None, request_sampling=None):
+                         req_win: Optional[Sequence[int]] = None, want_logits: bool = False, want_logprobs: bool = False, request_bias=None, request_sampling=None,
+                         request_grammar=None):
         """segments: int16 PCM windows (<= 30 s each, already peak-normalised) or RingSlice objects (raw wire PCM resident in a device
         ring; normalised on the device over the windows of their request); one prompt per request. Returns (ids list, logits or None);
         with want_logprobs (option token_logprobs on this handle) one more element: the float32 log-probability of every returned token, per request.
         request_bias: one reqbias.RequestBias or None per request (option request_bias on this handle; set_request_bias).
-        request_sampling: one (temperature, seed) or None (greedy) per request (option sampling on this handle; set_request_sampling)."""
+        request_sampling: one (temperature, seed) or None (greedy) per request (option sampling on this handle; set_request_sampling).
+        request_grammar: one DeviceGrammar or None (free) per request (option grammar on this handle; set_request_grammar)."""
         samp = None if request_sampling is None else pack_request_sampling(request_sampling)      # (validated before anything is armed)
         if any(isinstance(s, RingSlice) for s in segments):
             pcm, offs, rings, start, n = self._pack_mixed(segments)
@@ -516,6 +582,8 @@ class Engine(HooksMixin):
                 self.set_request_bias(request_bias)
             if samp is not None:
                 self._arm_sampling(samp)
+            if request_grammar is not None:
+                self.set_request_grammar(request_grammar)
             self._check(self.lib.sonic_transcribe_mixed(self.h, _p(pcm), _p(offs), rings, _p(start), _p(n), len(segments), _p(rw), R, _p(ids), _p(poffs),
                                                         _p(mn), _p(out), out_ld, _p(out_len), _p(logits)))
             res = [out[r, : out_len[r]].copy() for r in range(R)]
@@ -533,6 +601,8 @@ class Engine(HooksMixin):
             self.set_request_bias(request_bias)
         if samp is not None:
             self._arm_sampling(samp)
+        if request_grammar is not None:
+            self.set_request_grammar(request_grammar)
         self._check(self.lib.sonic_transcribe_batch(self.h, _p(pcm), _p(offs), len(segments), _p(rw), R, _p(ids), _p(poffs), _p(mn),
                                                     _p(out), out_ld, _p(out_len), _p(logits)))
         res = [out[r, : out_len[r]].copy() for r in range(R)]
@@ -597,7 +667,7 @@ class Engine(HooksMixin):
         self._check(self.lib.sonic_run_staged(self.h, _p(rw), len(prompts), _p(ids), _p(poffs), _p(mn), int(want_logits)))
 
     def prefill(self, prompts: Sequence[Sequence[int]], max_new: Sequence[int], req_win: Optional[Sequence[int]] = None, want_logits: bool = False, wait: bool = True,
-                request_bias=None, request_sampling=None):
+                request_bias=None, request_sampling=None, request_grammar=None):
         """Stage entry point: everything up to and including the first greedy token of the staged batch (sonic_prefill).  wait=False: the
         work is only queued when the call returns (sonic_prefill_enqueue; a following splice_rows orders itself behind it on the device)."""
         ids, poffs = self._pack_prompts(prompts)
@@ -608,6 +678,8 @@ class Engine(HooksMixin):
             self.set_request_bias(request_bias)
         if samp is not None:                             # one (temperature, seed) or None per request: likewise
             self._arm_sampling(samp)
+        if request_grammar is not None:                  # one DeviceGrammar or None per request: likewise
+            self.set_request_grammar(request_grammar)
         if not wait:
             self._check(self.lib.sonic_prefill_enqueue(self.h, _p(rw), len(prompts), _p(ids), _p(poffs), _p(mn)))
             return
@@ -715,6 +787,8 @@ class Engine(HooksMixin):
             self.request_bias = bool(value)          # (likewise)
         if key == "sampling":
             self.sampling = bool(value)              # (likewise)
+        if key == "grammar":
+            self.grammar = bool(value)               # (likewise)
         if key == "top_logprobs":
             self.top_logprobs = int(value)           # (likewise: the width of every log-probability record this handle returns)
         if key == "token_logprobs":

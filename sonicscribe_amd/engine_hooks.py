@@ -172,6 +172,37 @@ class HooksMixin:
         return self._greedy("greedy_sample", slabs, B, True, True, force_ids, (hist, hist_len, repetition_penalty, no_repeat_ngram_size, suppress_tokens), tables,
                             (temperature, seed, step), want_noise)
 
+    def test_greedy_grammar(self, slabs, B: int, grammar, state_in, eos_ids=(), hist=None, hist_len=None, tables=None, samp=None, repetition_penalty: float = 1.0,
+                            no_repeat_ngram_size: int = 0, suppress_tokens=(), force_ids=None, want_noise: bool = True):
+        """The grammar instantiations of the greedy kernel in this handle's type (include/sonic_hip.h beside sonic_test_greedy_sample): the automaton is armed on the
+        handle (sonic_load_tensor "grammar.hook:<V>", options hook_grammar_state / hook_grammar_eos) and the next guard / bias / sample hook launch takes it.
+        grammar: a grammar.Grammar (one automaton for the launch); state_in [B]: -1 a free row, n a node, -2 left; eos_ids: what a row at -2 may emit.  tables (one
+        reqbias.RequestBias or None per row): the bias families; samp = (temperature, seed, step): the sampling families -> (token [B], RAW logits [B][V],
+        log-probability over the masked scores [B] - a TokenScores with option top_logprobs -, Gumbel noise [B][V] or None, state out [B])"""
+        from .engine import DTYPE_I32, SonicError, grammar_words
+        V = np.asarray(slabs).shape[2]
+        w = grammar_words(grammar)
+        if self.lib.sonic_load_tensor(self.h, f"grammar.hook:{V}".encode(), _p(w), DTYPE_I32, (C.c_int64 * 1)(len(w)), 1) != 0:
+            raise SonicError((self.lib.sonic_last_error(None) or b"").decode())
+        si = np.ascontiguousarray(state_in, np.int32)
+        assert si.shape == (B,)
+        for b in range(B):
+            self._check(self.lib.sonic_set_option(self.h, b"hook_grammar_state", (b << 20) | (int(si[b]) + 2)))
+        for t in eos_ids:
+            self._check(self.lib.sonic_set_option(self.h, b"hook_grammar_eos", int(t)))
+        h = np.zeros((B, 1), np.int32) if hist is None else np.ascontiguousarray(hist, np.int32).reshape(B, -1)
+        hl = np.zeros(B, np.int32) if hist_len is None else np.ascontiguousarray(hist_len, np.int32)
+        guard = (h, hl, repetition_penalty, no_repeat_ngram_size, suppress_tokens)
+        if samp is not None:
+            tok, lg, lp, noise = self._greedy("greedy_sample", slabs, B, True, True, force_ids, guard, tables, samp, want_noise)
+        elif tables is not None:
+            tok, lg, lp, noise = self._greedy("greedy_bias", slabs, B, True, True, force_ids, guard, list(tables))
+        else:
+            tok, lg, lp, noise = self._greedy("greedy_guard", slabs, B, True, True, force_ids, guard)
+        so = np.zeros(64, np.float32)
+        self._check(self.lib.sonic_debug_read(self.h, b"hook_grammar_state", 0, _p(so), B))
+        return tok, lg, lp, noise, so[:B].astype(np.int32)
+
     def test_linear_int8(self, X, W, bias=None, resid=None, group_rows=None, epi=EPI_BIAS):
         """One Linear8bitLt call; X [M][K], W [N][K] fp16-valued. group_rows: rows per reference call (default: all rows one call)."""
         X = np.ascontiguousarray(X, np.float32); W = np.ascontiguousarray(W, np.float32)

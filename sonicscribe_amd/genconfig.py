@@ -40,7 +40,13 @@ _REFUSED = {
     "guidance_scale": lambda v: v is not None and float(v) != 1.0,
     "stop_strings": lambda v: bool(v),                 # ends a greedy run earlier than EOS / max_new_tokens would
     "watermarking_config": lambda v: bool(v),          # biases the scores ahead of the argmax
+    # constrained generation: a config cannot carry a callable or an automaton; the engine's own form is a grammar per request (_HINTS)
+    "prefix_allowed_tokens_fn": lambda v: v is not None,
+    "force_words_ids": lambda v: bool(v),
+    "constraints": lambda v: bool(v),
 }
+_HINTS = {name: " (to restrict transcripts to a closed set, build the model with grammar=True and pass ASRModel.compile_grammar(...) as grammar= of the call)"
+          for name in ("prefix_allowed_tokens_fn", "force_words_ids", "constraints")}
 # Known and let through, because a greedy run emits the same ids with and without them: renormalize_logits (log_softmax keeps the argmax; it would only
 # shift the scores HF reports) and remove_invalid_values (it rewrites nan / +-inf scores, which finite weights do not produce).  INTEGRATION.md says so.
 
@@ -111,7 +117,7 @@ def from_dict(cfg: Dict[str, Any]) -> GenerationGuards:
     """the guards of a generation config given as a dict; ValueError naming the first field the engine would have to ignore"""
     for name, on in _REFUSED.items():
         if name in cfg and on(cfg[name]):
-            raise ValueError(f"generation_config.json sets {name}={cfg[name]!r}: generate(do_sample=False) would honour it, this engine does not implement it")
+            raise ValueError(f"generation_config.json sets {name}={cfg[name]!r}: generate(do_sample=False) would honour it, this engine does not implement it" + _HINTS.get(name, ""))
     return GenerationGuards(cfg.get("repetition_penalty"), cfg.get("no_repeat_ngram_size"), cfg.get("suppress_tokens"))
 
 
