@@ -2,7 +2,8 @@
 // pipeline on one HIP stream, hipGraph-captured decode step, and the C ABI of include/sonic_hip.h.
 // One engine = one full model replica on one MI355X (replicas, no collectives).
 // This unit: the shared helpers, the constant tables, create / slot / destroy / info / synchronise.  The other sections of the engine live in
-// engine_weights.cpp, engine_stages.cpp, engine_f32.cpp, engine_ingest.cpp, engine_service.cpp, engine_options.cpp and engine_hooks.cpp; engine_internal.h is what they share.
+// engine_generation.cpp (what a handle generates with: log-probabilities, guards, the per-request stages), engine_weights.cpp, engine_stages.cpp, engine_f32.cpp,
+// engine_ingest.cpp, engine_service.cpp, engine_options.cpp and engine_hooks.cpp; engine_internal.h is what they share.
 #include "engine_internal.h"
 
 static thread_local std::string g_create_err;
@@ -346,508 +347,6 @@ static int alloc_state(sonic_engine* e) {
     return SONIC_OK;
 }
 
-// option token_logprobs: the log-probability buffer beside out_ids, allocated by the first handle state that needs it (counted by sonic_memory_info)
-int lp_alloc(sonic_engine* e) {
-    if (e->out_lp) return SONIC_OK;
-    HIPC(e, hipSetDevice(e->device));
-    TRY(dalloc(e, &e->out_lp, (size_t)64 * e->out_cap * lp_width(e)));
-    HIPC(e, stream_sync(e));
-    return SONIC_OK;
-}
-// the parallel forced run's buffers, at the first such run of the handle or when score_chunk_rows has grown since: the chunk's logits
-// [score_chunk_rows][vocab] in the activation type (fp32 kind: fp32) and the score rows' plan (3 words per row, at most tok_cap rows) on the device and pinned
-int score_alloc(sonic_engine* e) {
-    const int rows = e->opt_score_chunk_rows;
-    const size_t esz = e->f32 ? 4 : 2;
-    if (e->score_logits && e->score_rows_cap < rows) {
-        HIPC(e, stream_sync(e));
-        e->allocs.erase(std::find(e->allocs.begin(), e->allocs.end(), e->score_logits));
-        HIPC(e, hipFree(e->score_logits));
-        e->alloc_bytes -= (int64_t)(((size_t)e->score_rows_cap * e->d.vocab * esz + 3) / 4 * 4); e->score_logits = nullptr; e->score_rows_cap = 0;
-    }
-    if (!e->score_logits) {
-        unsigned char* p = nullptr;
-        TRY(dalloc(e, &p, (size_t)rows * e->d.vocab * esz, false));
-        e->score_logits = p; e->score_rows_cap = rows;
-    }
-    if (!e->score_plan_d) TRY(dalloc(e, &e->score_plan_d, (size_t)3 * e->tok_cap));
-    if (!e->score_plan_h && hipHostMalloc((void**)&e->score_plan_h, ((size_t)3 * e->tok_cap + 4 * 64) * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(e, SONIC_ERR_OOM, "forced_parallel: pinned host memory exhausted"); }
-    return SONIC_OK;
-}
-// word timestamps (option forced_align): the align run's buffers, at its first run on the handle or when a run needs more than the last one left.
-// S score rows (<= tok_cap), A_max audio keys of the longest run, heads_per_layer the most heads any layer contributes
-template <typename Tt> static int align_grow(sonic_engine* e, Tt** p, size_t* cap, size_t need) {
-    if (*p && *cap >= need) return SONIC_OK;
-    if (*p) {
-        HIPC(e, stream_sync(e));
-        e->allocs.erase(std::find(e->allocs.begin(), e->allocs.end(), (void*)*p));
-        HIPC(e, hipFree(*p));
-        e->alloc_bytes -= (int64_t)((*cap * sizeof(Tt) + 3) / 4 * 4); *p = nullptr; *cap = 0;
-    }
-    TRY(dalloc(e, p, need, false));
-    *cap = need;
-    return SONIC_OK;
-}
-int align_alloc(sonic_engine* e, int S, int A_max, int heads_per_layer) {
-    size_t tcap = e->align_M_cap;
-    TRY(align_grow(e, &e->align_P, &e->align_P_cap, (size_t)2 * heads_per_layer * S * A_max));      // probabilities | filtered z
-    e->align_Zoff = (size_t)heads_per_layer * S * A_max;
-    TRY(align_grow(e, &e->align_trace, &tcap, (size_t)S * A_max));
-    TRY(align_grow(e, &e->align_M, &e->align_M_cap, (size_t)S * A_max));
-    if (!e->align_t) TRY(dalloc(e, &e->align_t, (size_t)64 * e->out_cap));
-    const size_t plan = (size_t)2 * e->tok_cap + 4 * 64 + ALIGN_MAX_HEADS;
-    if (!e->align_plan_d) { TRY(dalloc(e, &e->align_plan_d, plan)); e->align_plan_cap = plan; }
-    if (!e->align_plan_h && hipHostMalloc((void**)&e->align_plan_h, plan * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(e, SONIC_ERR_OOM, "forced_align: pinned host memory exhausted"); }
-    return SONIC_OK;
-}
-// option top_logprobs = K: the K best alternatives of every step ride in the token's log-probability record, which grows to 1 + 2K floats.  The
-// buffer is exchanged for one of the new width (sonic_memory_info follows), so the records of a finished batch that has not been fetched yet are gone with the
-// old one: fetch first (include/sonic_hip.h says so).  The caller holds the lock and has asked gen_busy.
-int top_enable(sonic_engine* e, int K) {
-    if (K < 0 || K > 8) return fail(e, SONIC_ERR_INVALID, "top_logprobs: %d is outside 0 .. 8", K);
-    if (K > 0 && !(e->opt_token_logprobs && e->out_lp)) return fail(e, SONIC_ERR_INVALID, "top_logprobs: option token_logprobs must be on first (the alternatives share the log-probability kernels' sum; sonic_set_option(e, \"token_logprobs\", 1))");
-    if (K == e->opt_top_logprobs) return SONIC_OK;
-    HIPC(e, hipSetDevice(e->device));
-    HIPC(e, stream_sync(e));
-    const bool had = e->out_lp != nullptr;
-    if (had) {
-        e->allocs.erase(std::find(e->allocs.begin(), e->allocs.end(), (void*)e->out_lp));
-        HIPC(e, hipFree(e->out_lp));
-        e->alloc_bytes -= (int64_t)64 * e->out_cap * lp_width(e) * 4; e->out_lp = nullptr;
-    }
-    e->opt_top_logprobs = K;
-    drop_graphs(e);                                      // the greedy kernel and its arguments are part of every captured chunk
-    return had ? lp_alloc(e) : SONIC_OK;
-}
-int lp_check(sonic_engine* e, const char* who) {
-    if (e->opt_token_logprobs && e->out_lp) return SONIC_OK;
-    return fail(e, SONIC_ERR_INVALID, "%s: option token_logprobs is off on this handle (sonic_set_option(e, \"token_logprobs\", 1) on the owner before its slots are created)", who);
-}
-// dispatch.cpp / pipeline.cpp (same library, not exported): does this handle produce log-probabilities
-extern "C" int engine_token_logprobs_on(sonic_engine* e) { return e && e->opt_token_logprobs && e->out_lp ? 1 : 0; }
-// ... and how many alternatives ride along (option top_logprobs: its log-probability records hold 1 + 2K floats per token)
-extern "C" int engine_top_logprobs(sonic_engine* e) { return e && e->opt_token_logprobs && e->out_lp ? e->opt_top_logprobs : 0; }
-extern "C" int engine_forced_parallel_on(sonic_engine* e) { return e && e->opt_forced_parallel ? 1 : 0; }      // ... and is it a scoring handle (option forced_parallel: the schedulers refuse it)
-extern "C" int engine_fail(sonic_engine* e, int code, const char* msg) { std::lock_guard<std::mutex> lk(e->mu); return fail(e, code, "%s", msg); }   // a message on a handle, from outside its calls
-
-// ---- generation guards: validation, the history / suppress buffers on first use, the upload.  The caller holds the lock and has made sure nothing is in flight.
-#define GEN_MAX_SUPPRESS 256
-int gen_apply(sonic_engine* e, float penalty, int ngram, const int32_t* suppress, int n_suppress) {
-    if (!(penalty > 0.f) || !std::isfinite(penalty)) return fail(e, SONIC_ERR_INVALID, "sonic_set_generation: repetition_penalty must be a finite value > 0 (got %g)", (double)penalty);
-    if (ngram < 0 || ngram > 64) return fail(e, SONIC_ERR_INVALID, "sonic_set_generation: no_repeat_ngram_size %d is outside 0 .. 64", ngram);
-    if (n_suppress < 0 || n_suppress > GEN_MAX_SUPPRESS || (n_suppress > 0 && !suppress))
-        return fail(e, SONIC_ERR_INVALID, "sonic_set_generation: suppress_tokens holds %d ids (at most %d)", n_suppress, GEN_MAX_SUPPRESS);
-    for (int i = 0; i < n_suppress; ++i)
-        if (suppress[i] < 0 || suppress[i] >= e->d.vocab) return fail(e, SONIC_ERR_INVALID, "sonic_set_generation: suppressed token id %d out of vocabulary (%d)", suppress[i], e->d.vocab);
-    const bool on = penalty != 1.0f || ngram > 0 || n_suppress > 0;
-    if (on && greedy_guard_lds(e->d.vocab) > 60000) return fail(e, SONIC_ERR_UNSUPPORTED, "sonic_set_generation: a vocabulary of %d ids does not fit the guard bitmaps", e->d.vocab);
-    HIPC(e, hipSetDevice(e->device));
-    HIPC(e, stream_sync(e));
-    if (on && !e->hist) { TRY(dalloc(e, &e->hist, (size_t)64 * e->max_ctx)); HIPC(e, stream_sync(e)); }          // (option request_bias may have brought the history already)
-    if (on && !e->gen_suppress_d) { TRY(dalloc(e, &e->gen_suppress_d, (size_t)GEN_MAX_SUPPRESS)); HIPC(e, stream_sync(e)); }
-    if (n_suppress > 0) HIPC(e, h2d(e, e->gen_suppress_d, suppress, (size_t)n_suppress * 4));
-    e->gen_penalty = penalty; e->gen_ngram = ngram; e->gen_suppress.assign(suppress, suppress + n_suppress); e->gen_on = on;
-    drop_graphs(e);                                      // the greedy kernel and its arguments are part of every captured chunk
-    return SONIC_OK;
-}
-// Both ways in (sonic_set_generation, the gen_* keys of sonic_set_option) ask this first, under the handle's lock: SONIC_ERR_INVALID while the handle has work in
-// hand.  A prefilled batch counts until its decode loop has ended or every one of its rows has been handed to a continuous loop (sonic_splice_rows): a prefill
-// slot whose rows were all spliced away is free again.  (No path takes e->mu while it holds a_mu, so the short a_mu section below cannot deadlock.)
-int gen_busy(sonic_engine* e, const char* who) {
-    { std::lock_guard<std::mutex> lk(e->a_mu); if (e->a_pending || e->a_running) return fail(e, SONIC_ERR_INVALID, "%s: an asynchronous run of this handle is in flight", who); }
-    if (e->svc_on) return fail(e, SONIC_ERR_INVALID, "%s: this handle is decoding continuously (sonic_service_end first)", who);
-    if (e->R >= 1 && e->greedy_calls >= 1 && e->steps_run + 1 < e->max_steps) {
-        const uint64_t all = e->R >= 64 ? ~0ull : (1ull << e->R) - 1;
-        if ((e->spliced & all) != all)
-            return fail(e, SONIC_ERR_INVALID, "%s: the handle holds a prefilled batch of %d requests whose rows are still running (its decode loop has not ended and they were not all handed to a continuous loop)", who, e->R);
-    }
-    return SONIC_OK;
-}
-// ---- values left for the requests of the next prefill (ReqStage, engine_internal.h): what the options request_bias and sampling share.  A setter fills the pinned
-// mirror and leaves pending = R; the next prefill claims it (run_to_first_token), uploads it on the stream and marks the mirror busy until those copies are done; every
-// other way out of a consuming entry point drops it (ReqDrop).  The caller holds the lock.
-// The option's switch (the caller has asked gen_busy): on first use the zero-filled device words - every row starts neutral; `hist`: the rows' input_ids too - the
-// pinned mirror and the event.  `opt` names the option in the message
-template <typename W> static int stage_enable(sonic_engine* e, ReqStage<W>& s, int on, int* flag, const char* opt, int words, bool hist) {
-    HIPC(e, hipSetDevice(e->device));
-    HIPC(e, stream_sync(e));
-    if (on) {
-        if (hist && !e->hist) TRY(dalloc(e, &e->hist, (size_t)64 * e->max_ctx));
-        if (!s.dev) TRY(dalloc(e, &s.dev, (size_t)words));
-        if (!s.host && hipHostMalloc((void**)&s.host, (size_t)words * sizeof(W), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(e, SONIC_ERR_OOM, "%s: pinned host memory exhausted", opt); }
-        if (!s.ev) HIPC(e, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-        HIPC(e, stream_sync(e));
-    }
-    *flag = on ? 1 : 0; s.pending = -1; s.take = false;
-    drop_graphs(e);                                      // the greedy kernel and its arguments are part of every captured chunk
-    return SONIC_OK;
-}
-// open the mirror for writing (the previous batch's copies out of it are awaited first); the upload's copies are on the stream; the destroy path
-template <typename W> static int stage_open(sonic_engine* e, ReqStage<W>& s) { if (s.busy) { HIPC(e, hipEventSynchronize(s.ev)); s.busy = false; } return SONIC_OK; }
-template <typename W> static int stage_sent(sonic_engine* e, ReqStage<W>& s) { HIPC(e, hipEventRecord(s.ev, e->st)); s.busy = true; s.take = false; return SONIC_OK; }
-template <typename W> static void stage_free(ReqStage<W>& s) { if (s.host) (void)hipHostFree(s.host); if (s.ev) (void)hipEventDestroy(s.ev); }
-int stage_count(sonic_engine* e, int got, int R, const char* setter, const char* what) {
-    return got >= 0 && got != R ? fail(e, SONIC_ERR_INVALID, "%s gave %s for %d requests, the batch has %d", setter, what, got, R) : SONIC_OK;
-}
-// What both setters open with: refused during an asynchronous run (without waiting for the engine lock that run holds), then the lock (`lk`), then refused while
-// the option `opt` (flag `on`) is off.  From here on nothing is pending
-template <typename W> static int stage_enter(sonic_engine* e, std::unique_lock<std::mutex>& lk, const char* who, const char* opt, const int& on, ReqStage<W>& s) {
-    { std::lock_guard<std::mutex> ak(e->a_mu); if (e->a_pending || e->a_running) return fail(nullptr, SONIC_ERR_INVALID, "%s: an asynchronous run of this handle is in flight", who); }
-    lk = std::unique_lock<std::mutex>(e->mu);
-    (void)hipGetLastError();
-    if (!on || !s.dev) return fail(e, SONIC_ERR_INVALID, "%s: option %s is off on this handle (sonic_set_option(e, \"%s\", 1) on the owner before its slots are created)", who, opt, opt);
-    s.pending = -1;
-    return SONIC_OK;
-}
-// ---- option request_bias: HF's SequenceBiasLogitsProcessor / NoBadWordsLogitsProcessor (generation/logits_process.py) with one table per request -
-// the reference's hotwords (backend/asr.py:303-333) as a bias on the scores instead of a sentence in the prompt.  The caller holds the lock and has asked gen_busy.
-int bias_enable(sonic_engine* e, int on) {
-    if (on && greedy_guard_lds(e->d.vocab, true) > 60000) return fail(e, SONIC_ERR_UNSUPPORTED, "request_bias: a vocabulary of %d ids does not fit the bias bitmaps", e->d.vocab);
-    return stage_enable(e, e->bias, on, &e->opt_request_bias, "request_bias", BIAS_TAB_WORDS, true);      // (zero-filled: every row starts without a table)
-}
-int bias_pack(sonic_engine* e, const char* who, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n, int V, int* row, int* count) {
-    if (n < 0 || n > BIAS_MAX_ENTRIES) return fail(e, SONIC_ERR_INVALID, "%s: a request's table holds %d entries (at most %d; nothing is truncated)", who, n, BIAS_MAX_ENTRIES);
-    if (n > 0 && (!seq_ids || !seq_off || !bias)) return fail(e, SONIC_ERR_INVALID, "%s: null table", who);
-    struct Ent { const int32_t* ids; int L; float b; };
-    std::vector<Ent> v;
-    for (int i = 0; i < n; ++i) {
-        const int L = seq_off[i + 1] - seq_off[i];
-        if (L < 1 || L > BIAS_MAX_LEN) return fail(e, SONIC_ERR_INVALID, "%s: entry %d has %d ids (1 .. %d)", who, i, L, BIAS_MAX_LEN);
-        const int32_t* ids = seq_ids + seq_off[i];
-        for (int k = 0; k < L; ++k) if (ids[k] < 0 || ids[k] >= V) return fail(e, SONIC_ERR_INVALID, "%s: token id %d out of vocabulary (%d)", who, ids[k], V);
-        if (std::isnan(bias[i]) || bias[i] == INFINITY) return fail(e, SONIC_ERR_INVALID, "%s: entry %d has bias %g (finite values, or -inf for a bad word)", who, i, (double)bias[i]);
-        bool dup = false;                                // HF's list -> dict conversion: the last bias of equal sequences wins, at the first one's position
-        for (Ent& o : v) if (o.L == L && !memcmp(o.ids, ids, (size_t)L * 4)) { o.b = bias[i]; dup = true; break; }
-        if (!dup) v.push_back(Ent{ids, L, bias[i]});
-    }
-    // grouped by last id; inside a group the length-1 entry first (HF starts from length_1_bias), then list order: the order the kernel's one thread adds in
-    std::stable_sort(v.begin(), v.end(), [](const Ent& a, const Ent& b) {
-        const int la = a.ids[a.L - 1], lb = b.ids[b.L - 1];
-        if (la != lb) return la < lb;
-        return (a.L == 1) > (b.L == 1);
-    });
-    for (size_t i = 0; i < v.size(); ++i) {
-        int* w = row + i * BIAS_ENTRY_WORDS;
-        w[0] = v[i].ids[v[i].L - 1]; w[1] = v[i].L; memcpy(&w[2], &v[i].b, 4);
-        for (int k = 0; k < BIAS_MAX_LEN - 1; ++k) w[3 + k] = k < v[i].L - 1 ? v[i].ids[k] : -1;
-    }
-    *count = (int)v.size();
-    return SONIC_OK;
-}
-// The tables of the R requests of the next prefill on this handle (sonic_prefill / sonic_prefill_enqueue / sonic_run_staged[_async] / sonic_transcribe_*), which
-// consumes them: a later batch starts without tables.  Request r's entries are seq_off[req_off[r]] .. seq_off[req_off[r + 1]] of seq_ids, with bias[req_off[r] ..].
-extern "C" int sonic_set_request_bias(sonic_engine* e, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, const int32_t* req_off, int R) {
-    if (!e) return SONIC_ERR_INVALID;
-    std::unique_lock<std::mutex> lk; TRY(stage_enter(e, lk, "sonic_set_request_bias", "request_bias", e->opt_request_bias, e->bias));
-    if (R < 1 || R > e->Bm || R > 64 || !req_off || req_off[0] != 0) return fail(e, SONIC_ERR_INVALID, "sonic_set_request_bias: %d requests (1 .. %d), offsets from 0", R, e->Bm);
-    HIPC(e, hipSetDevice(e->device));
-    TRY(stage_open(e, e->bias));
-    for (int r = 0; r < 64; ++r) e->bias.host[r] = 0;
-    for (int r = 0; r < R; ++r) {
-        const int a = req_off[r], n = req_off[r + 1] - req_off[r];
-        if (n < 0) return fail(e, SONIC_ERR_INVALID, "sonic_set_request_bias: request offsets decrease");
-        if (n == 0) continue;
-        if (!seq_off || !bias) return fail(e, SONIC_ERR_INVALID, "sonic_set_request_bias: null table");
-        TRY(bias_pack(e, "sonic_set_request_bias", seq_ids, seq_off + a, bias + a, n, e->d.vocab, e->bias.host + 64 + (size_t)r * BIAS_ROW_WORDS, &e->bias.host[r]));
-    }
-    e->bias.pending = R;
-    return SONIC_OK;
-}
-int bias_upload(sonic_engine* e, int R) {
-    if (!e->opt_request_bias) return SONIC_OK;
-    if (!e->bias.take && e->opt_bias_fill > 0) {
-        // option request_bias_fill = n (drivers that only pass integers: bench.py --opt; tools/ab_request_bias.sh): every request of a batch without tables gets n
-        // length-1 entries of bias +0.0 on ids spread over the vocabulary.  s + 0.0 changes no token, but the kernel does all its work for them: the prologue's
-        // flags and group sums, n bits in the "biased" map, the list scan at every one of those ids
-        TRY(stage_open(e, e->bias));
-        const int n = e->opt_bias_fill, V = e->d.vocab;
-        for (int r = 0; r < 64; ++r) e->bias.host[r] = r < R ? n : 0;
-        for (int r = 0; r < R; ++r)
-            for (int k = 0; k < n; ++k) {
-                int* w = e->bias.host + 64 + (size_t)r * BIAS_ROW_WORDS + (size_t)k * BIAS_ENTRY_WORDS;
-                w[0] = (int)((long)k * V / n); w[1] = 1; w[2] = 0;
-                for (int j = 3; j < BIAS_ENTRY_WORDS; ++j) w[j] = -1;
-            }
-        e->bias.take = true;
-    }
-    if (!e->bias.take) { launch_fill_i32(e->bias.dev, 0, 64, e->st); return SONIC_OK; }             // a batch without tables: every count 0
-    HIPC(e, hipMemcpyAsync(e->bias.dev, e->bias.host, 64 * 4, hipMemcpyHostToDevice, e->st));
-    for (int r = 0; r < R; ++r) {
-        const size_t o = 64 + (size_t)r * BIAS_ROW_WORDS;
-        if (e->bias.host[r] > 0) HIPC(e, hipMemcpyAsync(e->bias.dev + o, e->bias.host + o, (size_t)e->bias.host[r] * BIAS_ENTRY_WORDS * 4, hipMemcpyHostToDevice, e->st));
-    }
-    return stage_sent(e, e->bias);
-}
-// ---- option sampling: temperature sampling in the greedy kernel by the Gumbel-max identity, one (temperature, seed) per request - what Whisper's
-// decode_with_fallback retries with.  The caller holds the lock and has asked gen_busy.
-int samp_enable(sonic_engine* e, int on) {
-    if (on && !(e->opt_token_logprobs && e->out_lp)) return fail(e, SONIC_ERR_INVALID, "sampling: option token_logprobs must be on first (the sampling kernels are log-probability kernels; sonic_set_option(e, \"token_logprobs\", 1))");
-    return stage_enable(e, e->samp, on, &e->opt_sampling, "sampling", SAMP_WORDS, false);                  // (zero-filled: every row starts greedy)
-}
-void samp_pack(unsigned* w, float t, uint64_t seed) { memcpy(&w[0], &t, 4); w[1] = (unsigned)(seed & 0xffffffffull); w[2] = (unsigned)(seed >> 32); }
-int samp_check(sonic_engine* e, const char* who, const float* temperature, int n) {
-    for (int r = 0; r < n; ++r) {
-        const float t = temperature[r];
-        if (!(t == 0.f || (t >= 1e-3f && t <= 100.f)))     // (NaN fails every compare)
-            return fail(e, SONIC_ERR_INVALID, "%s: temperature %g of request %d is invalid (0 = greedy, or 1e-3 .. 100; nothing is clamped)", who, (double)t, r);
-    }
-    return SONIC_OK;
-}
-// The (temperature, seed) of the R requests of the next prefill on this handle (the entry points of sonic_set_request_bias), which consumes them: a later batch
-// starts greedy.
-extern "C" int sonic_set_request_sampling(sonic_engine* e, const float* temperature, const uint64_t* seed, int R) {
-    if (!e) return SONIC_ERR_INVALID;
-    std::unique_lock<std::mutex> lk; TRY(stage_enter(e, lk, "sonic_set_request_sampling", "sampling", e->opt_sampling, e->samp));
-    if (R < 1 || R > e->Bm || R > 64 || !temperature || !seed) return fail(e, SONIC_ERR_INVALID, "sonic_set_request_sampling: %d requests (1 .. %d), values for each", R, e->Bm);
-    TRY(samp_check(e, "sonic_set_request_sampling", temperature, R));
-    HIPC(e, hipSetDevice(e->device));
-    TRY(stage_open(e, e->samp));
-    for (int i = 0; i < SAMP_WORDS; ++i) e->samp.host[i] = 0u;
-    for (int r = 0; r < R; ++r) samp_pack(e->samp.host + 3 * r, temperature[r], seed[r]);
-    e->samp.pending = R;
-    return SONIC_OK;
-}
-int samp_upload(sonic_engine* e, int R) {
-    if (!e->opt_sampling) return SONIC_OK;
-    if (!e->samp.take && e->opt_samp_fill_milli > 0) {
-        // option sampling_fill_milli = m (drivers that only pass integers: bench.py --opt; tools/ab_sampling.sh): request r of a batch without values gets temperature
-        // m / 1000 and seed r.  A batch is then the same draw every time it runs, on whichever handle: a benchmark can still check its tokens
-        TRY(stage_open(e, e->samp));
-        const float t = (float)((double)e->opt_samp_fill_milli / 1000.0);
-        for (int i = 0; i < SAMP_WORDS; ++i) e->samp.host[i] = 0u;
-        for (int r = 0; r < R && r < 64; ++r) samp_pack(e->samp.host + 3 * r, t, (uint64_t)r);
-        e->samp.take = true;
-    }
-    if (!e->samp.take) { launch_fill_i32((int*)e->samp.dev, 0, SAMP_WORDS, e->st); return SONIC_OK; } // a batch without values: every row greedy
-    HIPC(e, hipMemcpyAsync(e->samp.dev, e->samp.host, (size_t)SAMP_WORDS * 4, hipMemcpyHostToDevice, e->st));
-    return stage_sent(e, e->samp);
-}
-extern "C" int engine_sampling_on(sonic_engine* e) { return e && e->opt_sampling && e->samp.dev ? 1 : 0; }
-// ---- option grammar: a request's transcript restricted to the paths of a deterministic token automaton - HF's prefix_allowed_tokens_fn
-// (PrefixConstrainedLogitsProcessor), Vosk's `grammar` - with the mask and the state transition inside the greedy kernel.  Grammars live on the weight owner.
-int gram_pack(sonic_engine* e, const char* who, const int32_t* node_off, const int32_t* edge_tok, const int32_t* edge_next, int N, int E, int vocab, int audio_id, std::vector<int>* out) {
-    if (!node_off || !edge_tok || !edge_next) return fail(e, SONIC_ERR_INVALID, "%s: null array", who);
-    if (N < 1 || N > GRAM_MAX_NODES) return fail(e, SONIC_ERR_INVALID, "%s: %d nodes (1 .. %d; nothing is truncated)", who, N, GRAM_MAX_NODES);
-    if (E < 1 || E > GRAM_MAX_EDGES) return fail(e, SONIC_ERR_INVALID, "%s: %d edges (1 .. %d; nothing is truncated)", who, E, GRAM_MAX_EDGES);
-    if (node_off[0] != 0) return fail(e, SONIC_ERR_INVALID, "%s: node_off[0] is %d, not 0", who, node_off[0]);
-    if (node_off[N] != E) return fail(e, SONIC_ERR_INVALID, "%s: node_off[%d] is %d, not the edge count %d", who, N, node_off[N], E);
-    for (int n = 0; n < N; ++n) {
-        const int a = node_off[n], b = node_off[n + 1];
-        if (b < a || a < 0 || b > E) return fail(e, SONIC_ERR_INVALID, "%s: node_off is not monotone at node %d (%d then %d)", who, n, a, b);
-        if (b == a) return fail(e, SONIC_ERR_INVALID, "%s: node %d has no edge (a transcript ends through an EOS edge, never by running dry)", who, n);
-        for (int k = a; k < b; ++k) {
-            if (edge_tok[k] < 0 || edge_tok[k] >= vocab) return fail(e, SONIC_ERR_INVALID, "%s: token id %d of node %d is out of vocabulary (%d)", who, edge_tok[k], n, vocab);
-            if (edge_tok[k] == audio_id) return fail(e, SONIC_ERR_INVALID, "%s: token id %d of node %d is the audio placeholder, which cannot be emitted", who, edge_tok[k], n);
-            if (edge_next[k] < 0 || edge_next[k] >= N) return fail(e, SONIC_ERR_INVALID, "%s: edge %d of node %d leads to node %d (0 .. %d)", who, k - a, n, edge_next[k], N - 1);
-            if (k > a && edge_tok[k] <= edge_tok[k - 1]) return fail(e, SONIC_ERR_INVALID, "%s: the edges of node %d are not sorted and unique by token id (%d after %d)", who, n, edge_tok[k], edge_tok[k - 1]);
-        }
-    }
-    out->resize((size_t)GRAM_HEAD + N + 1 + 2 * (size_t)E);
-    int* w = out->data();
-    w[0] = N; w[1] = E;
-    memcpy(w + GRAM_HEAD, node_off, (size_t)(N + 1) * 4);
-    memcpy(w + GRAM_HEAD + N + 1, edge_tok, (size_t)E * 4);
-    memcpy(w + GRAM_HEAD + N + 1 + E, edge_next, (size_t)E * 4);
-    return SONIC_OK;
-}
-// the packed words [N | E | node_off[N + 1] | edge_tok[E] | edge_next[E]] taken apart again: SONIC_ERR_INVALID when the counts do not fit the length
-static int gram_unpack(const char* who, const int* w, int64_t n, const int** off, const int** tok, const int** nxt, int* N, int* E) {
-    if (!w || n < GRAM_HEAD) return fail(nullptr, SONIC_ERR_INVALID, "%s: %lld words do not hold the automaton's two counts", who, (long long)n);
-    *N = w[0]; *E = w[1];
-    if (*N < 1 || *N > GRAM_MAX_NODES) return fail(nullptr, SONIC_ERR_INVALID, "%s: %d nodes (1 .. %d; nothing is truncated)", who, *N, GRAM_MAX_NODES);
-    if (*E < 1 || *E > GRAM_MAX_EDGES) return fail(nullptr, SONIC_ERR_INVALID, "%s: %d edges (1 .. %d; nothing is truncated)", who, *E, GRAM_MAX_EDGES);
-    if (n != (int64_t)GRAM_HEAD + *N + 1 + 2 * (int64_t)*E) return fail(nullptr, SONIC_ERR_INVALID, "%s: %lld words, %d nodes and %d edges need %lld", who, (long long)n, *N, *E, (long long)GRAM_HEAD + *N + 1 + 2 * (long long)*E);
-    *off = w + GRAM_HEAD; *tok = *off + *N + 1; *nxt = *tok + *E;
-    return SONIC_OK;
-}
-// sonic_load_tensor(e, "grammar:<id>", words, SONIC_DTYPE_I32, {n}, 1): created once on a weight owner (a slot's call lands on its owner) under an id the caller
-// chooses (1 .. 65535) and shared by every handle of it; n = 0 destroys it - refused by name while a staged or running request refers to it; what is left when the owner
-// goes is freed with it.  Does not take the engine lock, so a server can compile a grammar while its handles decode.  The message of a refusal is the calling thread's
-int gram_create(sonic_engine* e, int id, const int* words, int64_t n) {
-    sonic_engine* root = e->owner ? e->owner : e;
-    if (!root->finalized) return fail(nullptr, SONIC_ERR_INVALID, "grammar: the engine's weights are not finalized");
-    if (id < 1 || id > 65535) return fail(nullptr, SONIC_ERR_INVALID, "grammar: id %d is outside 1 .. 65535", id);
-    if (n == 0) {
-        sonic_grammar* g = nullptr;
-        {
-            std::lock_guard<std::mutex> lk(root->gram_mu);
-            auto it = std::find_if(root->grammars.begin(), root->grammars.end(), [&](sonic_grammar* x) { return x->id == id; });
-            if (it == root->grammars.end()) return fail(nullptr, SONIC_ERR_INVALID, "grammar: %d is not a live grammar of this engine", id);
-            g = *it;
-            const int r = g->refs.load();
-            if (r > 0) return fail(nullptr, SONIC_ERR_INVALID, "grammar: %d is in use: %d staged or running request%s refer%s to it (fetch or release their rows first)", id, r, r == 1 ? "" : "s", r == 1 ? "s" : "");
-            root->grammars.erase(it);
-        }
-        root->gram_bytes -= g->bytes;
-        (void)hipSetDevice(root->device);
-        (void)hipDeviceSynchronize();                         // launches queued while a row still referred to it (a finished row's block reads its node until the row is released)
-        (void)hipFree(g->dev);
-        delete g;
-        return SONIC_OK;
-    }
-    const int *off, *tok, *nxt; int N, E;
-    TRY(gram_unpack("grammar", words, n, &off, &tok, &nxt, &N, &E));
-    std::vector<int> w;
-    TRY(gram_pack(nullptr, "grammar", off, tok, nxt, N, E, root->d.vocab, root->d.audio_token_id, &w));
-    if (hipSetDevice(root->device) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, SONIC_ERR_HIP, "grammar: hipSetDevice failed"); }
-    sonic_grammar* g = new sonic_grammar();
-    g->root = root; g->id = id; g->N = N; g->E = E; g->bytes = (int64_t)w.size() * 4;
-    if (hipMalloc((void**)&g->dev, w.size() * 4) != hipSuccess) { (void)hipGetLastError(); delete g; return fail(nullptr, SONIC_ERR_OOM, "HIP out of memory (grammar of %d nodes and %d edges)", N, E); }
-    if (hipMemcpy(g->dev, w.data(), w.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(g->dev); delete g; return fail(nullptr, SONIC_ERR_HIP, "grammar: upload failed"); }
-    {
-        std::lock_guard<std::mutex> lk(root->gram_mu);
-        for (sonic_grammar* x : root->grammars) if (x->id == id) { (void)hipFree(g->dev); delete g; return fail(nullptr, SONIC_ERR_INVALID, "grammar: id %d is taken by a live grammar of this engine", id); }
-        root->grammars.push_back(g);
-    }
-    root->gram_bytes += g->bytes;
-    return SONIC_OK;
-}
-// the kernel hooks' automaton (engine_hooks.cpp test_greedy), validated as a grammar is, against the hook's own vocabulary V
-int gram_hook_arm(sonic_engine* e, int V, const int* words, int64_t n) {
-    const int *off, *tok, *nxt; int N, E;
-    if (V < 4 || V > (1 << 24)) return fail(nullptr, SONIC_ERR_INVALID, "grammar.hook: vocabulary %d", V);
-    TRY(gram_unpack("grammar.hook", words, n, &off, &tok, &nxt, &N, &E));
-    std::vector<int> w;
-    TRY(gram_pack(nullptr, "grammar.hook", off, tok, nxt, N, E, V, -1, &w));
-    std::lock_guard<std::mutex> lk(e->mu);
-    e->hook_gram.swap(w); e->hook_eos.clear();
-    for (int b = 0; b < 64; ++b) e->hook_state_in[b] = -1;
-    return SONIC_OK;
-}
-void gram_unref(sonic_grammar* g) { if (g) g->refs.fetch_sub(1); }
-void gram_drop_staged(sonic_engine* e) {
-    for (int r = 0; r < 64; ++r) { gram_unref(e->gram_staged[r]); e->gram_staged[r] = nullptr; }
-    e->gram.pending = -1;
-}
-void gram_row_release(sonic_engine* e, int row) { if (row >= 0 && row < 64) { gram_unref(e->gram_row[row]); e->gram_row[row] = nullptr; } }
-// a live grammar of `root` gains a reference (under the registry's lock: a concurrent destroy either sees it or has already removed the grammar)
-static bool gram_ref(sonic_engine* root, sonic_grammar* g) {
-    std::lock_guard<std::mutex> lk(root->gram_mu);
-    if (std::find(root->grammars.begin(), root->grammars.end(), g) == root->grammars.end()) return false;
-    g->refs.fetch_add(1);
-    return true;
-}
-static sonic_grammar* gram_ref_id(sonic_engine* root, int id) {
-    std::lock_guard<std::mutex> lk(root->gram_mu);
-    for (sonic_grammar* g : root->grammars) if (g->id == id) { g->refs.fetch_add(1); return g; }
-    return nullptr;
-}
-int gram_enable(sonic_engine* e, int on) {
-    if (on && !(e->opt_token_logprobs && e->out_lp)) return fail(e, SONIC_ERR_INVALID, "grammar: option token_logprobs must be on first (the grammar kernels are log-probability kernels; sonic_set_option(e, \"token_logprobs\", 1))");
-    if (on && greedy_guard_lds(e->d.vocab) > 60000) return fail(e, SONIC_ERR_UNSUPPORTED, "grammar: a vocabulary of %d ids does not fit the guard bitmaps", e->d.vocab);
-    if (!on && e->opt_grammar) { gram_drop_staged(e); for (int r = 0; r < 64; ++r) gram_row_release(e, r); }
-    TRY(stage_enable(e, e->gram, on, &e->opt_grammar, "grammar", GRAM_STAGE_WORDS, true));
-    if (on) { launch_fill_i32((int*)e->gram.dev, 0, 128, e->st); launch_fill_i32(gram_state_of(e), -1, 64, e->st); HIPC(e, stream_sync(e)); }      // every row starts free
-    return SONIC_OK;
-}
-// The grammars of the R requests of the next prefill on this handle (the entry points of sonic_set_request_bias), which consumes them.  Options of the handle:
-// request_grammar_begin = R stages R free requests, request_grammar = request << 16 | grammar id then names a request's grammar.  The caller holds the lock
-static void gram_stage_words(sonic_engine* e) {
-    int* st = (int*)(e->gram.host + 64);
-    for (int r = 0; r < 64; ++r) { e->gram.host[r] = e->gram_staged[r] ? (unsigned long long)(uintptr_t)e->gram_staged[r]->dev : 0ull; st[r] = e->gram_staged[r] ? 0 : -1; }
-}
-int gram_stage_begin(sonic_engine* e, int R) {
-    if (!e->opt_grammar || !e->gram.dev) return fail(e, SONIC_ERR_INVALID, "request_grammar_begin: option grammar is off on this handle (sonic_set_option(e, \"grammar\", 1) on the owner before its slots are created)");
-    gram_drop_staged(e);
-    if (R < 1 || R > e->Bm || R > 64) return fail(e, SONIC_ERR_INVALID, "request_grammar_begin: %d requests (1 .. %d)", R, e->Bm);
-    HIPC(e, hipSetDevice(e->device));
-    TRY(stage_open(e, e->gram));
-    gram_stage_words(e);
-    e->gram.pending = R;
-    return SONIC_OK;
-}
-int gram_stage_row(sonic_engine* e, int value) {
-    const int r = value >> 16, id = value & 0xffff, R = e->gram.pending.load();
-    if (!e->opt_grammar || !e->gram.dev) return fail(e, SONIC_ERR_INVALID, "request_grammar: option grammar is off on this handle (sonic_set_option(e, \"grammar\", 1) on the owner before its slots are created)");
-    if (R < 0) return fail(e, SONIC_ERR_INVALID, "request_grammar: no batch is staged (option request_grammar_begin first)");
-    if (value < 0 || r >= R) { gram_drop_staged(e); return fail(e, SONIC_ERR_INVALID, "request_grammar: request %d of a staged batch of %d", r, R); }
-    sonic_grammar* g = gram_ref_id(e->owner ? e->owner : e, id);
-    if (!g) { gram_drop_staged(e); return fail(e, SONIC_ERR_INVALID, "request_grammar: %d is not a live grammar of this handle's weight owner (a grammar serves the engine it was created on and its slots)", id); }
-    gram_unref(e->gram_staged[r]);
-    e->gram_staged[r] = g;
-    gram_stage_words(e);
-    return SONIC_OK;
-}
-// dispatch.cpp (same library, not exported): a batch's grammars by pointer (NULL: a free request), under the handle's lock
-extern "C" int engine_set_request_grammar(sonic_engine* e, sonic_grammar* const* grammars, int R) {
-    if (!e || !grammars) return SONIC_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
-    (void)hipGetLastError();
-    TRY(gram_stage_begin(e, R));
-    sonic_engine* root = e->owner ? e->owner : e;
-    for (int r = 0; r < R; ++r) {
-        if (!grammars[r]) continue;
-        if (!gram_ref(root, grammars[r])) { gram_drop_staged(e); return fail(e, SONIC_ERR_INVALID, "request_grammar: the grammar of request %d is not a live grammar of this handle's weight owner", r); }
-        e->gram_staged[r] = grammars[r];
-    }
-    gram_stage_words(e);
-    return SONIC_OK;
-}
-// sonic_load_tensor "grammar.dispatch:<id>" on any handle of a dispatcher's weight owner: the calling thread's NEXT sonic_dispatch_submit* carries that grammar (0: none;
-// the registry's lock and a thread-local, never the engine lock: a decoding handle holds that one for a chunk at a time), which takes it - and its
-// reference - whatever becomes of the submit
-static thread_local sonic_grammar* g_dispatch_gram = nullptr;
-int gram_dispatch_arm(sonic_engine* e, int id) {
-    gram_unref(g_dispatch_gram); g_dispatch_gram = nullptr;
-    if (id == 0) return SONIC_OK;
-    g_dispatch_gram = gram_ref_id(e->owner ? e->owner : e, id);
-    if (!g_dispatch_gram) return fail(nullptr, SONIC_ERR_INVALID, "grammar.dispatch: %d is not a live grammar of this handle's weight owner", id);
-    return SONIC_OK;
-}
-extern "C" sonic_grammar* engine_take_dispatch_grammar(void) { sonic_grammar* g = g_dispatch_gram; g_dispatch_gram = nullptr; return g; }
-int gram_upload(sonic_engine* e, int R) {
-    (void)R;
-    if (!e->opt_grammar) return SONIC_OK;
-    for (int r = 0; r < 64; ++r) gram_row_release(e, r);                  // the rows' former occupants are gone (or were spliced away with references of their own)
-    if (!e->gram.take) {                                                   // a batch without grammars: every row free
-        gram_drop_staged(e);
-        launch_fill_i32((int*)e->gram.dev, 0, 128, e->st); launch_fill_i32(gram_state_of(e), -1, 64, e->st);
-        return SONIC_OK;
-    }
-    for (int r = 0; r < 64; ++r) { e->gram_row[r] = e->gram_staged[r]; e->gram_staged[r] = nullptr; }
-    HIPC(e, hipMemcpyAsync(e->gram.dev, e->gram.host, (size_t)GRAM_STAGE_WORDS * 8, hipMemcpyHostToDevice, e->st));
-    return stage_sent(e, e->gram);
-}
-// dispatch.cpp (same library, not exported): the option on a handle; whose grammar it is; a queued request's reference handed back
-extern "C" int engine_grammar_on(sonic_engine* e) { return e && e->opt_grammar && e->gram.dev ? 1 : 0; }
-extern "C" void* engine_grammar_owner(sonic_grammar* g) { return g ? (void*)g->root : nullptr; }
-extern "C" void engine_grammar_unref(sonic_grammar* g) { gram_unref(g); }
-extern "C" int engine_sampling_validate(float temperature) { return samp_check(nullptr, "sonic_dispatch_submit_sampled", &temperature, 1); }
-// dispatch.cpp (same library, not exported): is the option on for a handle; is one request's table well-formed for it (the message lands on the handle)
-extern "C" int engine_request_bias_on(sonic_engine* e) { return e && e->opt_request_bias && e->bias.dev ? 1 : 0; }
-// (the handle is only read for its vocabulary: the message goes to the calling thread's sonic_last_error(NULL), no lock is needed)
-extern "C" int engine_bias_validate(sonic_engine* e, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n) {
-    if (!e) return SONIC_ERR_INVALID;
-    std::vector<int> row((size_t)BIAS_ROW_WORDS); int cnt = 0;
-    return bias_pack(nullptr, "sonic_dispatch_submit_bias", seq_ids, seq_off, bias, n, e->d.vocab, row.data(), &cnt);
-}
-extern "C" int engine_thread_fail(int code, const char* msg) { return fail(nullptr, code, "%s", msg); }
-
-// HF generate()'s logits processors for greedy decoding, as the checkpoint's generation_config.json (or the caller) sets them: repetition_penalty (1.0 = none),
-// no_repeat_ngram_size (0 = none), suppress_tokens (n_suppress = 0: none; at most 256 ids).  The neutral values switch the guards off: the engine then launches
-// the kernels it launched before.  Set it on the owner before slots are created (they copy it).  SONIC_ERR_INVALID for a value out of range, and while the handle
-// has work in hand (gen_busy): a prefilled batch whose decode loop has not ended, an asynchronous run, a continuous loop (sonic_service_begin).  The first check
-// below is the same one without the engine lock, which an asynchronous run holds until it ends: the call answers at once instead of waiting for it.
-extern "C" int sonic_set_generation(sonic_engine* e, float repetition_penalty, int no_repeat_ngram_size, const int32_t* suppress, int n_suppress) {
-    if (!e) return SONIC_ERR_INVALID;
-    { std::lock_guard<std::mutex> lk(e->a_mu); if (e->a_pending || e->a_running) return fail(nullptr, SONIC_ERR_INVALID, "sonic_set_generation: an asynchronous run of this handle is in flight"); }
-    std::lock_guard<std::mutex> lk(e->mu);
-    (void)hipGetLastError();
-    TRY(gen_busy(e, "sonic_set_generation"));
-    return gen_apply(e, repetition_penalty, no_repeat_ngram_size, suppress, n_suppress);
-}
-// what is in force on this handle (get_model_info, tests): *n_suppress = ids copied to suppress[0 .. cap)
-extern "C" int sonic_get_generation(sonic_engine* e, float* repetition_penalty, int32_t* no_repeat_ngram_size, int32_t* suppress, int cap, int32_t* n_suppress) {
-    if (!e) return SONIC_ERR_INVALID;
-    std::lock_guard<std::mutex> lk(e->mu);
-    if (repetition_penalty) *repetition_penalty = e->gen_penalty;
-    if (no_repeat_ngram_size) *no_repeat_ngram_size = e->gen_ngram;
-    const int n = (int)e->gen_suppress.size();
-    if (n_suppress) *n_suppress = n;
-    if (suppress) for (int i = 0; i < n && i < cap; ++i) suppress[i] = e->gen_suppress[i];
-    return SONIC_OK;
-}
-
 extern "C" int sonic_create(const sonic_dims* dims, int device_id, int mode, int max_batch, int max_ctx, sonic_engine** out) {
     if (!dims || !out) return fail(nullptr, SONIC_ERR_INVALID, "null argument");
     *out = nullptr;
@@ -903,16 +402,7 @@ extern "C" int sonic_slot_create(sonic_engine* parent, sonic_engine** out) {
     e->opts = root->opts; e->opt_no_graph = root->opt_no_graph; e->opt_no_fused_rope = root->opt_no_fused_rope; e->opt_no_gelu_lut = root->opt_no_gelu_lut;
     e->opt_i8_defer_thr = root->opt_i8_defer_thr; e->opt_i8_no_xq = root->opt_i8_no_xq; e->opt_i8_no_lnq = root->opt_i8_no_lnq; e->opt_i8_no_qkv_fuse = root->opt_i8_no_qkv_fuse;
     e->opt_decode_chunk = root->opt_decode_chunk; e->opt_no_pre_norm = root->opt_no_pre_norm; e->opt_decode_gemv = root->opt_decode_gemv;
-    e->opt_token_logprobs = root->opt_token_logprobs; e->opt_top_logprobs = root->opt_token_logprobs ? root->opt_top_logprobs : 0;      // (before lp_alloc: the buffer comes at its width)
-    if (e->opt_token_logprobs && (s = lp_alloc(e)) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }
-    if (root->gen_on && (s = gen_apply(e, root->gen_penalty, root->gen_ngram, root->gen_suppress.data(), (int)root->gen_suppress.size())) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }
-    if (root->opt_request_bias && (s = bias_enable(e, 1)) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }
-    e->opt_bias_fill = root->opt_bias_fill;
-    if (root->opt_sampling && (s = samp_enable(e, 1)) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }
-    e->opt_samp_fill_milli = root->opt_samp_fill_milli;
-    if (root->opt_grammar && (s = gram_enable(e, 1)) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }
-    e->opt_forced_parallel = root->opt_forced_parallel; e->opt_forced_fanout = root->opt_forced_fanout; e->opt_score_chunk_rows = root->opt_score_chunk_rows;      // (the buffers come with the slot's first parallel run)
-    e->opt_forced_align = root->opt_forced_align; e->align_heads = root->align_heads;      // (likewise)
+    if ((s = gen_inherit(e, root)) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }      // the owner's generation options, with their buffers
     e->weight_bytes = 0; e->finalized = true; e->owner = root;
     root->slots.push_back(e);
     *out = e;
@@ -956,10 +446,7 @@ extern "C" void sonic_destroy(sonic_engine* e) {
         if (root != e && root->wait_ev == e->splice_ev) root->wait_pending = false;
         for (sonic_engine* k : root->slots) if (k != e && k->wait_ev == e->splice_ev) k->wait_pending = false;
     }
-    gram_drop_staged(e);                               // the grammar references of this handle's staged requests and rows
-    for (int r = 0; r < 64; ++r) gram_row_release(e, r);
-    for (sonic_grammar* g : e->grammars) { (void)hipFree(g->dev); delete g; }      // owner: the grammars the caller left behind (its slots are gone: nothing refers to them)
-    e->grammars.clear();
+    gen_release(e);                                    // the per-request stages' mirrors, the grammar references this handle holds, an owner's grammars
     for (sonic_ring* r : e->rings) ring_free(r);       // rings the caller left behind go with their engine
     e->rings.clear();
     resample_release(e);
@@ -974,7 +461,6 @@ extern "C" void sonic_destroy(sonic_engine* e) {
     if (e->svc_h) (void)hipHostFree(e->svc_h);
     if (e->score_plan_h) (void)hipHostFree(e->score_plan_h);
     if (e->align_plan_h) (void)hipHostFree(e->align_plan_h);
-    stage_free(e->bias); stage_free(e->samp); stage_free(e->gram);
     if (e->st_io) { (void)hipStreamSynchronize(e->st_io); (void)hipStreamDestroy(e->st_io); }
     if (e->xfer_ev) (void)hipEventDestroy(e->xfer_ev);
     if (e->splice_ev) (void)hipEventDestroy(e->splice_ev);

@@ -1,4 +1,4 @@
-// What the translation units of the engine (engine.cpp, engine_weights.cpp, engine_stages.cpp, engine_f32.cpp, engine_ingest.cpp,
+// What the translation units of the engine (engine.cpp, engine_generation.cpp, engine_weights.cpp, engine_stages.cpp, engine_f32.cpp, engine_ingest.cpp,
 // engine_service.cpp, engine_options.cpp, engine_hooks.cpp) share: the engine struct and its parts, the constants, the error / entry macros and the helpers that
 // cross a unit boundary.  Not part of the C ABI (include/sonic_hip.h); a function used by one unit only is static there.
 #pragma once
@@ -63,7 +63,7 @@ struct F32State {
 struct RsBank { float* dev = nullptr; int of = 0, nf = 0, width = 0, K = 0, tile = 0, kc = 0; };
 #define RS_BANK_MAX_COEF ((int64_t)1 << 22)
 
-// Values the caller leaves for the requests of the next prefill (options request_bias and sampling; the protocol is stage_* in engine.cpp).  dev: the rows'
+// Values the caller leaves for the requests of the next prefill (options request_bias and sampling; the protocol is stage_* in engine_generation.cpp, which also holds the one list of the stages: req_*).  dev: the rows'
 // words on the device, written by the prefill from the pinned mirror `host`, copied by the splice.  pending: the R of the values a setter left in `host` for the
 // next prefill (-1: none); take: that prefill is under way and uploads them.  ev / busy: the last upload's copies out of `host` are older than this event.
 template <typename W> struct ReqStage {
@@ -281,8 +281,8 @@ struct HostPlan {
 // ENTER for the entry points that consume the tables of sonic_set_request_bias (sonic_prefill*, sonic_run_staged, sonic_transcribe_*): whatever way the call
 // leaves - a staging error ahead of the prefill included - the pending tables are dropped, so they can never reach a later batch (the values of
 // sonic_set_request_sampling likewise).  keep: sonic_run_staged_async accepted the run, whose prefill is now their consumer
-void gram_drop_staged(sonic_engine* e);             // the grammar references staged requests hold (engine.cpp); nothing is pending afterwards
-struct ReqDrop { sonic_engine* e; bool keep = false; ~ReqDrop() { if (!keep) { e->bias.pending = -1; e->samp.pending = -1; if (e->opt_grammar) gram_drop_staged(e); } } };
+void req_drop_pending(sonic_engine* e);             // every per-request stage (engine_generation.cpp): nothing is pending afterwards, the staged grammar references are handed back
+struct ReqDrop { sonic_engine* e; bool keep = false; ~ReqDrop() { if (!keep) req_drop_pending(e); } };
 #define ENTER_CONSUME(e) std::lock_guard<std::mutex> lk((e)->mu); ReqDrop req_drop_{e}; (void)hipGetLastError(); HIPC(e, hipSetDevice((e)->device)); g_opts = (e)->opts
 
 // ------------------------------------------------------------------------------------------ helpers (engine.cpp)
@@ -306,6 +306,16 @@ template <typename Tt> static int dalloc(sonic_engine* e, Tt** p, size_t n, bool
     e->allocs.push_back(q); e->alloc_bytes += (int64_t)bytes;
     if (zero) zero_fill(e, q, bytes);
     *p = (Tt*)q;
+    return SONIC_OK;
+}
+// ... and hands one of them back early (a buffer exchanged for a larger one): n is the element count dalloc was given.  Waits for the stream first
+template <typename Tt> static int dfree(sonic_engine* e, Tt** p, size_t n) {
+    HIPC(e, stream_sync(e));
+    const auto it = std::find(e->allocs.begin(), e->allocs.end(), (void*)*p);
+    if (it != e->allocs.end()) e->allocs.erase(it);
+    HIPC(e, hipFree(*p));
+    e->alloc_bytes -= (int64_t)(((n ? n : 1) * sizeof(Tt) + 3) / 4 * 4);
+    *p = nullptr;
     return SONIC_OK;
 }
 
@@ -348,37 +358,7 @@ int resample_bank_get(sonic_engine* root, int64_t in_rate, int64_t out_rate, RsB
 void resample_release(sonic_engine* e);
 void async_shutdown(sonic_engine* e);
 int fetch_locked(sonic_engine* e, int32_t* out_ids, int out_ld, int32_t* out_len, float* step_logits, float* out_lp = nullptr);
-int lp_alloc(sonic_engine* e);                      // out_lp on first use (engine.cpp)
-int gen_apply(sonic_engine* e, float penalty, int ngram, const int32_t* suppress, int n_suppress);   // sonic_set_generation behind the lock and the busy check (engine.cpp)
-int gen_busy(sonic_engine* e, const char* who);     // that busy check: SONIC_ERR_INVALID while the handle has work in hand (engine.cpp)
 void drop_graphs(sonic_engine* e);                  // the captured decode chunks of this handle (engine_options.cpp)
-int bias_enable(sonic_engine* e, int on);           // option request_bias behind the lock and the busy check: hist, the tables and their staging buffer on first use (engine.cpp)
-// one request's table as sonic_set_request_bias takes it -> its BIAS_ROW_WORDS device words, grouped and ordered as the kernel reads them; *count = its entries.
-// SONIC_ERR_INVALID (message on e, naming `who`) for more than BIAS_MAX_ENTRIES entries, a length outside 1 .. BIAS_MAX_LEN, an id outside [0, V), a NaN or +inf bias
-int bias_pack(sonic_engine* e, const char* who, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n, int V, int* row, int* count);
-int bias_upload(sonic_engine* e, int R);            // the prefill's part: the pending tables (or zero counts) into bias.dev, on the stream (engine.cpp)
-int stage_count(sonic_engine* e, int got, int R, const char* setter, const char* what);   // SONIC_ERR_INVALID when a claim (ReqStage::claim) was set for another count than the batch's (engine.cpp)
-int samp_enable(sonic_engine* e, int on);           // option sampling behind the lock and the busy check: the rows' words and their staging buffer on first use (engine.cpp)
-int samp_check(sonic_engine* e, const char* who, const float* temperature, int n);   // SONIC_ERR_INVALID (message on e, or the calling thread's for e = NULL) unless every value is 0 or in [1e-3, 100]
-int samp_upload(sonic_engine* e, int R);            // the prefill's part: the pending values (or zeros: greedy) into samp.dev, on the stream (engine.cpp)
-void samp_pack(unsigned* w, float t, uint64_t seed);   // one row's three words as the kernel reads them: the temperature's bits, the seed's low and high word (engine.cpp)
-static inline bool hist_on(const sonic_engine* e) { return e->gen_on || e->opt_request_bias || e->opt_grammar; }   // the rows' input_ids are kept: a guard, the request bias or the grammar's kernels read them
-int gram_enable(sonic_engine* e, int on);           // option grammar behind the lock and the busy check: hist, the rows' references and state words and their staging buffer on first use (engine.cpp)
-int gram_create(sonic_engine* e, int id, const int* words, int64_t n);   // sonic_load_tensor "grammar:<id>": the packed automaton [N | E | node_off | edge_tok | edge_next] onto e's weight owner; n = 0 destroys it (engine.cpp)
-int gram_hook_arm(sonic_engine* e, int V, const int* words, int64_t n);  // sonic_load_tensor "grammar.hook:<V>": the hooks' automaton, validated against V; every row free, no EOS ids (engine.cpp)
-int gram_stage_begin(sonic_engine* e, int R);       // option request_grammar_begin: R requests staged for the next prefill, all free (the caller holds the lock)
-int gram_stage_row(sonic_engine* e, int value);     // option request_grammar = request << 16 | grammar id: that staged request refers to that grammar
-int gram_dispatch_arm(sonic_engine* e, int id);     // sonic_load_tensor "grammar.dispatch:<id>" (no engine lock): the calling thread's next sonic_dispatch_submit* carries grammar `id` of e's owner
-int gram_upload(sonic_engine* e, int R);            // the prefill's part: the pending references (state 0) or none (state -1) into gram.dev, on the stream; the rows take over the staged references (engine.cpp)
-void gram_unref(sonic_grammar* g);                  // one reference less (NULL: nothing)
-void gram_row_release(sonic_engine* e, int row);    // a fetched row of a continuous loop lets go of its grammar
-static inline int* gram_state_of(const sonic_engine* e) { return (int*)(e->gram.dev + 64); }   // the rows' state words behind their references
-// the automaton's arrays validated by the contract's rules (SONIC_ERR_INVALID, the message - on e, or the calling thread's for e = NULL - names `who` and the cause) and
-// packed into the device blob's words: GRAM_HEAD + N + 1 + 2E of them
-int gram_pack(sonic_engine* e, const char* who, const int32_t* node_off, const int32_t* edge_tok, const int32_t* edge_next, int N, int E, int vocab, int audio_id, std::vector<int>* out);
-static inline int lp_width(const sonic_engine* e) { return 1 + 2 * e->opt_top_logprobs; }   // floats per token in every log-probability array of this handle
-int top_enable(sonic_engine* e, int K);             // option top_logprobs behind the lock and the busy check: out_lp at its new width (engine.cpp)
-int lp_check(sonic_engine* e, const char* who);     // SONIC_ERR_INVALID naming the option when token_logprobs is off on this handle
 int read_back_16(sonic_engine* e, const bf16_t* d, float* h, size_t n);   // n elements of a 16-bit device buffer -> fp32 on the host, through a temporary (engine_hooks.cpp; sonic_debug_read)
 
 // ------------------------------------------------------------------------------------------ launch builders and shared launch sequences (engine_stages.cpp)
@@ -401,6 +381,60 @@ void launch_o_gu(sonic_engine* e, int form, const OGuChain& c, int M, int K, int
 // run_prefill / run_forced_parallel and the hook (sonic_test_attention on an align handle)
 AlignArgs align_probs_args(sonic_engine* e, const bf16_t* Q, const bf16_t* K, long k_ld, long k_head_stride, long k_seq_stride, const int* heads, int n_heads, int Hq, int Hkv, const int* rec);
 int align_alloc(sonic_engine* e, int S, int A_max, int heads_per_layer);      // the buffers at (at least) this run's need
-int score_alloc(sonic_engine* e);                                  // the parallel forced run's buffers at the handle's current score_chunk_rows (first use, or a larger chunk)
 int upload_plan(sonic_engine* e, int R, const HostPlan& hp);       // the prefill's prologue, every kind: the request plan through the pinned staging buffer ...
 int reset_row_state(sonic_engine* e, int R, int n_tok);            // ... and the rows' counters, history, bias tables and sampling values for the greedy loop
+
+// ------------------------------------------------------------------------------------------ what a handle generates with (engine_generation.cpp)
+// log-probabilities (options token_logprobs / top_logprobs)
+static inline int lp_width(const sonic_engine* e) { return 1 + 2 * e->opt_top_logprobs; }   // floats per token in every log-probability array of this handle
+int lp_alloc(sonic_engine* e);                      // out_lp on first use
+int top_enable(sonic_engine* e, int K);             // option top_logprobs behind the lock and the busy check: out_lp at its new width
+int lp_check(sonic_engine* e, const char* who);     // SONIC_ERR_INVALID naming the option when token_logprobs is off on this handle
+// generation guards (sonic_set_generation)
+int gen_apply(sonic_engine* e, float penalty, int ngram, const int32_t* suppress, int n_suppress);   // sonic_set_generation behind the lock and the busy check
+int gen_busy(sonic_engine* e, const char* who);     // that busy check: SONIC_ERR_INVALID while the handle has work in hand
+static inline bool hist_on(const sonic_engine* e) { return e->gen_on || e->opt_request_bias || e->opt_grammar; }   // the rows' input_ids are kept: a guard, the request bias or the grammar's kernels read them
+// the three per-request stages' switches (engine_options.cpp) and what the hooks and sonic_load_tensor share with them
+int bias_enable(sonic_engine* e, int on);           // option request_bias behind the lock and the busy check: hist, the tables and their staging buffer on first use
+int samp_enable(sonic_engine* e, int on);           // option sampling behind the lock and the busy check: the rows' words and their staging buffer on first use
+int gram_enable(sonic_engine* e, int on);           // option grammar behind the lock and the busy check: hist, the rows' references and state words and their staging buffer on first use
+// one request's table as sonic_set_request_bias takes it -> its BIAS_ROW_WORDS device words, grouped and ordered as the kernel reads them; *count = its entries.
+// SONIC_ERR_INVALID (message on e, naming `who`) for more than BIAS_MAX_ENTRIES entries, a length outside 1 .. BIAS_MAX_LEN, an id outside [0, V), a NaN or +inf bias
+int bias_pack(sonic_engine* e, const char* who, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n, int V, int* row, int* count);
+int samp_check(sonic_engine* e, const char* who, const float* temperature, int n);   // SONIC_ERR_INVALID (message on e, or the calling thread's for e = NULL) unless every value is 0 or in [1e-3, 100]
+void samp_pack(unsigned* w, float t, uint64_t seed);   // one row's three words as the kernel reads them: the temperature's bits, the seed's low and high word
+int gram_create(sonic_engine* e, int id, const int* words, int64_t n);   // sonic_load_tensor "grammar:<id>": the packed automaton [N | E | node_off | edge_tok | edge_next] onto e's weight owner; n = 0 destroys it
+int gram_hook_arm(sonic_engine* e, int V, const int* words, int64_t n);  // sonic_load_tensor "grammar.hook:<V>": the hooks' automaton, validated against V; every row free, no EOS ids
+int gram_stage_begin(sonic_engine* e, int R);       // option request_grammar_begin: R requests staged for the next prefill, all free (the caller holds the lock)
+int gram_stage_row(sonic_engine* e, int value);     // option request_grammar = request << 16 | grammar id: that staged request refers to that grammar
+int gram_dispatch_arm(sonic_engine* e, int id);     // sonic_load_tensor "grammar.dispatch:<id>" (no engine lock): the calling thread's next sonic_dispatch_submit* carries grammar `id` of e's owner
+// the splice's one descriptor (splice_kv_kernel / splice_state_kernel, engine_service.cpp, which fills the rest of it); declared here for req_splice_args
+struct SpliceArgs {
+    const bf16_t *Ks, *Vs; bf16_t *Kd, *Vd; int layers, Bm, Hkv, ctx, hd;
+    int src[64], dst[64];
+    const int *kv_len_s, *tok_pos_s, *n_new_s, *fin_s, *max_new_s, *out_s; int out_ld;
+    const int* hist_s; int* hist_d;                      // generation guards on the destination: the row's history (prompt + first token) travels with it, [.][ctx]
+    const int* bias_s; int* bias_d;                      // option request_bias on both: the row's table travels with it (count first, then only the used entries)
+    const unsigned* samp_s; unsigned* samp_d;            // option sampling on both: the row's temperature and seed travel with it (its step index is n_new)
+    unsigned long long* gram_s; unsigned long long* gram_d;            // option grammar on both: the row's grammar reference and its state word (behind the 64 references) MOVE with it: the source row is free afterwards
+    const float* lp_s; float* lp_d; int lp_w;            // option token_logprobs on the destination: the first token's log-probability record (lp_w floats: 1, or 1 + 2K with
+                                                         // option top_logprobs) travels with its id
+    int *kv_len_d, *tok_pos_d, *n_new_d, *fin_d, *max_new_d, *out_d, *n_active_d;
+    const bf16_t *sx_s, *shn_s; bf16_t *sx_d, *shn_d; int D;
+    const int8_t* hq_s; int8_t* hq_d; const float *sca_s, *ov_s; float *sca_d, *ov_d; const int *oc_s, *ol_s; int *oc_d, *ol_d;   // int8 mode: layer 0's quantised input row
+};
+// The per-request stages (bias, samp, gram) at every point of a request's life, one function per point: the stages are listed in these functions and nowhere else.
+// The caller holds the lock (both locks: the splice)
+int req_claim(sonic_engine* e, int R);              // a prefill begins: it consumes what the setters left; SONIC_ERR_INVALID when a setter was given another count than the batch's R
+const char* req_claim_none(sonic_engine* e);        // ... a run that applies no processors: consumed all the same; names what was staged (NULL: nothing was)
+int req_upload(sonic_engine* e, int R);             // the prefill's part: the claimed values, or the neutral ones, into the rows' words, on the stream
+void req_greedy_args(const sonic_engine* e, GreedyArgs& g);   // the rows' words into the greedy launch (g.out_lp and g.hist are set)
+int req_graph_key(const sonic_engine* e);           // the stages' bits of a captured chunk's cache key (the greedy kernel's family is part of the capture)
+int req_splice_check(sonic_engine* d, sonic_engine* p);      // SONIC_ERR_INVALID (message on d) unless source and destination agree in every stage's option
+void req_splice_args(sonic_engine* d, sonic_engine* p, SpliceArgs& a, const int32_t* src_rows, const int32_t* dst_rows, int n);   // the rows' words travel; a row's grammar reference moves with it
+void req_rows_free(sonic_engine* e);                // a continuous loop begins: every row of the pool is free
+int* req_release_state(const sonic_engine* e);      // what the release kernels reset in a fetched row beside its counters (NULL: nothing) ...
+void req_row_release(sonic_engine* e, int row);     // ... and what the row held on the host goes with it
+void req_batch_fetched(sonic_engine* e, const int* fin, int R);   // a batch is fetched: once its R rows have all ended they let go of what they held
+int gen_inherit(sonic_engine* e, const sonic_engine* root);   // sonic_slot_create: the owner's generation options (token_logprobs .. forced_align) onto the new slot, with their buffers
+void gen_release(sonic_engine* e);                  // sonic_destroy: the stages' pinned mirrors and events, the grammar references this handle holds, an owner's grammars

@@ -27,7 +27,7 @@ static int opt_gen(sonic_engine* e, const char* key, int value) {
 // temperature sampling (sonic_set_request_sampling): on the owner before its slots are created (they copy it), after token_logprobs (refused by
 // name otherwise); allocates the rows' (temperature, seed) words.  Refused while the handle has work in hand, by sonic_set_generation's rule
 static int opt_sampling(sonic_engine* e, const char* key, int value) { TRY(gen_busy(e, key)); return samp_enable(e, value ? 1 : 0); }
-static int opt_sampling_fill_milli(sonic_engine* e, const char* key, int value) {    // measurement aid (samp_upload, engine.cpp): 0 (off) or 1 .. 100000 thousandths, for every request without values
+static int opt_sampling_fill_milli(sonic_engine* e, const char* key, int value) {    // measurement aid (samp_upload, engine_generation.cpp): 0 (off) or 1 .. 100000 thousandths, for every request without values
     if (value != 0 && (value < 1 || value > 100000)) return fail(e, SONIC_ERR_INVALID, "sampling_fill_milli: %d is outside 0, 1 .. 100000", value);
     TRY(gen_busy(e, key)); e->opt_samp_fill_milli = value; return SONIC_OK;
 }
@@ -50,7 +50,7 @@ static int opt_hook_grammar_eos(sonic_engine* e, const char*, int value) {
 // per-request sequence bias (sonic_set_request_bias): on the owner before its slots are created (they copy it); allocates the rows' history, if the
 // guards have not, and their tables.  Refused while the handle has work in hand, by sonic_set_generation's rule
 static int opt_request_bias(sonic_engine* e, const char* key, int value) { TRY(gen_busy(e, key)); return bias_enable(e, value ? 1 : 0); }
-static int opt_request_bias_fill(sonic_engine* e, const char* key, int value) {      // measurement aid (bias_upload, engine.cpp): 0 .. min(256, vocabulary) neutral entries for every request without a table
+static int opt_request_bias_fill(sonic_engine* e, const char* key, int value) {      // measurement aid (bias_upload, engine_generation.cpp): 0 .. min(256, vocabulary) neutral entries for every request without a table
     if (value < 0 || value > BIAS_MAX_ENTRIES || value > e->d.vocab) return fail(e, SONIC_ERR_INVALID, "request_bias_fill: %d is outside 0 .. %d", value, BIAS_MAX_ENTRIES);
     TRY(gen_busy(e, key)); e->opt_bias_fill = value; return SONIC_OK;
 }

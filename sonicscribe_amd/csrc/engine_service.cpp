@@ -8,21 +8,7 @@
 // end and pads every batch to its slowest row.  Here a request is prefilled on ANOTHER handle of the same weights (sonic_prefill on a slot: log-mel,
 // encoder, prompt forward, first token), its row - KV cache, control words, next-step input - is copied into a free row of the decoding handle
 // between two chunks of its greedy loop, and the row is handed back the moment it hits EOS / its budget.  Rows are independent in every decode
-// kernel and sum in a fixed order (batch invariance up to 32 rows), so a request's tokens are the same bits as in a solo run.
-struct SpliceArgs {
-    const bf16_t *Ks, *Vs; bf16_t *Kd, *Vd; int layers, Bm, Hkv, ctx, hd;
-    int src[64], dst[64];
-    const int *kv_len_s, *tok_pos_s, *n_new_s, *fin_s, *max_new_s, *out_s; int out_ld;
-    const int* hist_s; int* hist_d;                      // generation guards on the destination: the row's history (prompt + first token) travels with it, [.][ctx]
-    const int* bias_s; int* bias_d;                      // option request_bias on both: the row's table travels with it (count first, then only the used entries)
-    const unsigned* samp_s; unsigned* samp_d;            // option sampling on both: the row's temperature and seed travel with it (its step index is n_new)
-    unsigned long long* gram_s; unsigned long long* gram_d;            // option grammar on both: the row's grammar reference and its state word (behind the 64 references) MOVE with it: the source row is free afterwards
-    const float* lp_s; float* lp_d; int lp_w;            // option token_logprobs on the destination: the first token's log-probability record (lp_w floats: 1, or 1 + 2K with
-                                                         // option top_logprobs) travels with its id
-    int *kv_len_d, *tok_pos_d, *n_new_d, *fin_d, *max_new_d, *out_d, *n_active_d;
-    const bf16_t *sx_s, *shn_s; bf16_t *sx_d, *shn_d; int D;
-    const int8_t* hq_s; int8_t* hq_d; const float *sca_s, *ov_s; float *sca_d, *ov_d; const int *oc_s, *ol_s; int *oc_d, *ol_d;   // int8 mode: layer 0's quantised input row
-};
+// kernel and sum in a fixed order (batch invariance up to 32 rows), so a request's tokens are the same bits as in a solo run.  (SpliceArgs, the copy's descriptor: engine_internal.h)
 __global__ __launch_bounds__(256) void splice_kv_kernel(SpliceArgs a) {
     const int i = blockIdx.x, lh = blockIdx.y, s = a.src[i], d = a.dst[i];
     const int len = min(max(a.kv_len_s[s], 1), a.ctx);
@@ -92,7 +78,7 @@ extern "C" int sonic_service_begin(sonic_engine* e) {
     HIPC(e, stream_sync(e));
     hipLaunchKernelGGL(service_reset_kernel, dim3(1), dim3(64), 0, e->st, e->kv_len, e->tok_pos, e->n_new, e->finished, e->max_new_d, e->n_active);
     if (e->force_d) return fail(e, SONIC_ERR_INVALID, "teacher forcing is set: clear it before continuous decoding");
-    if (e->opt_grammar) { launch_fill_i32(gram_state_of(e), -1, 64, e->st); for (int r = 0; r < 64; ++r) gram_row_release(e, r); }      // the pool starts with free rows
+    req_rows_free(e);                                       // the pool starts with free rows
     hipGraphExec_t gx = nullptr;                            // the chunk graphs exist before the first splice: nothing captures on this stream later
     if (e->Bm >= 2 && !e->i8) TRY(chunk_graph(e, 2, e->opt_decode_chunk > 0 ? e->opt_decode_chunk : 1, &gx, true));   // a pool with at most two occupied rows (round 6: five launches per layer)
     if (e->Bm >= 4 && !e->i8 && e->opt_decode_gemv) TRY(chunk_graph(e, 4, e->opt_decode_chunk > 0 ? e->opt_decode_chunk : 1, &gx, true));   // ... four, on the GEMV chain (opt-in)
@@ -138,12 +124,7 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
     // (either way round: a row whose first token was chosen with guards must not go on without them, nor the reverse)
     if (d->gen_on != p->gen_on || (d->gen_on && !(p->hist && d->hist && p->gen_penalty == d->gen_penalty && p->gen_ngram == d->gen_ngram && p->gen_suppress == d->gen_suppress)))
         return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in their generation guards (sonic_set_generation): set them on the owner before its slots are created");
-    if (d->opt_request_bias != p->opt_request_bias || (d->opt_request_bias && !(p->bias.dev && d->bias.dev && p->hist && d->hist)))
-        return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in option request_bias: set it on the owner before its slots are created");
-    if (d->opt_sampling != p->opt_sampling || (d->opt_sampling && !(p->samp.dev && d->samp.dev)))
-        return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in option sampling: set it on the owner before its slots are created");
-    if (d->opt_grammar != p->opt_grammar || (d->opt_grammar && !(p->gram.dev && d->gram.dev)))
-        return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in option grammar: set it on the owner before its slots are created");
+    TRY(req_splice_check(d, p));
     if (n < 1 || n > 64 || p->greedy_calls < 1 || n > p->R) return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: %d rows, the source has %d prefilled requests", n, p->greedy_calls < 1 ? 0 : p->R);
     SpliceArgs a{};
     for (int i = 0; i < n; ++i) {
@@ -158,17 +139,7 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
     a.sx_s = p->sx; a.shn_s = p->shn; a.sx_d = d->sx; a.shn_d = d->shn; a.D = dm.dec_d;
     if (d->opt_token_logprobs && d->out_lp) { a.lp_s = p->out_lp; a.lp_d = d->out_lp; a.lp_w = lp_width(d); }
     if (hist_on(d)) { a.hist_s = p->hist; a.hist_d = d->hist; }
-    if (d->opt_request_bias) { a.bias_s = p->bias.dev; a.bias_d = d->bias.dev; }
-    if (d->opt_sampling) { a.samp_s = p->samp.dev; a.samp_d = d->samp.dev; }
-    if (d->opt_grammar) {
-        a.gram_s = p->gram.dev; a.gram_d = d->gram.dev;
-        for (int i = 0; i < n; ++i) {                      // the row is handed over and its reference with it: the source row is free (the kernel resets its words)
-            sonic_grammar* g = p->gram_row[src_rows[i]];
-            p->gram_row[src_rows[i]] = nullptr;
-            gram_row_release(d, dst_rows[i]);
-            d->gram_row[dst_rows[i]] = g;
-        }
-    }
+    req_splice_args(d, p, a, src_rows, dst_rows, n);      // the per-request stages' rows; a row's grammar reference is handed over with it
     if (d->i8) { a.hq_s = p->hn_q; a.hq_d = d->hn_q; a.sca_s = p->sca_hn; a.sca_d = d->sca_hn; a.oc_s = p->oc_hn; a.oc_d = d->oc_hn; a.ol_s = p->ol_hn; a.ol_d = d->ol_hn; a.ov_s = p->ov_hn; a.ov_d = d->ov_hn; }
     HIPC(d, hipEventRecord(p->xfer_ev, p->st));
     HIPC(d, hipStreamWaitEvent(d->st, p->xfer_ev, 0));
@@ -251,8 +222,8 @@ extern "C" int sonic_fetch_row(sonic_engine* e, int row, int n, int32_t* out_ids
         HIPC(e, hipMemcpyAsync(out_ids, e->out_ids + (size_t)row * e->out_cap, (size_t)n * 4, hipMemcpyDeviceToHost, e->st_io));
         HIPC(e, hipStreamSynchronize(e->st_io));
     }
-    hipLaunchKernelGGL(release_row_kernel, dim3(1), dim3(1), 0, e->st, e->kv_len, e->tok_pos, e->finished, row, e->opt_grammar ? gram_state_of(e) : nullptr);
-    gram_row_release(e, row);                               // (a finished row changes no state and reads no automaton that matters: its reference can go)
+    hipLaunchKernelGGL(release_row_kernel, dim3(1), dim3(1), 0, e->st, e->kv_len, e->tok_pos, e->finished, row, req_release_state(e));
+    req_row_release(e, row);                                // (a finished row changes no state and reads no automaton that matters: its reference can go)
     HIPC(e, hipGetLastError());
     return SONIC_OK;
 }
@@ -281,8 +252,8 @@ static int fetch_rows_locked(sonic_engine* e, int n, const int32_t* rows, const 
             if (out_lp) HIPC(e, hipMemcpyAsync(out_lp + (size_t)i * out_ld * w, e->out_lp + (size_t)rows[i] * e->out_cap * w, (size_t)counts[i] * w * 4, hipMemcpyDeviceToHost, e->st_io));
         }
     HIPC(e, hipStreamSynchronize(e->st_io));
-    hipLaunchKernelGGL(release_rows_kernel, dim3(1), dim3(64), 0, e->st, e->kv_len, e->tok_pos, e->finished, a, n, e->opt_grammar ? gram_state_of(e) : nullptr);
-    for (int i = 0; i < n; ++i) gram_row_release(e, rows[i]);
+    hipLaunchKernelGGL(release_rows_kernel, dim3(1), dim3(64), 0, e->st, e->kv_len, e->tok_pos, e->finished, a, n, req_release_state(e));
+    for (int i = 0; i < n; ++i) req_row_release(e, rows[i]);
     HIPC(e, hipGetLastError());
     return SONIC_OK;
 }
@@ -306,7 +277,7 @@ static int run_staged_entry(sonic_engine* e) {
     const sonic_engine::AsyncJob& j = e->a_job;
     ENTER(e);
     const int rc = run_all(e, j.has_rw ? j.req_win.data() : nullptr, j.R, j.prompt_ids.data(), j.prompt_off.data(), j.max_new.data(), j.want_logits != 0);
-    if (e->opt_grammar) gram_drop_staged(e);               // (a run that failed ahead of its prefill still consumed its grammars)
+    req_drop_pending(e);                                    // (a run that failed ahead of its prefill still consumed what was staged for it)
     return rc;
 }
 static void async_loop(sonic_engine* e) {
@@ -522,16 +493,7 @@ int fetch_locked(sonic_engine* e, int32_t* out_ids, int out_ld, int32_t* out_len
             HIPC(e, d2h_async(e, out_lp + (size_t)r * out_ld, e->out_lp + (size_t)r * e->out_cap * w, (size_t)nn[r] * w * 4));
         }
     }
-    if (e->opt_grammar && !e->svc_on) {      // a batch whose every row has ended and whose ids are being fetched lets go of its grammars: the rows are free again
-        bool ended = true;                   // (state -1: a later sonic_decode_step reads no automaton)
-        for (int r = 0; r < R; ++r) ended = ended && fin[r];
-        bool any = false;
-        for (int r = 0; r < 64; ++r) any = any || e->gram_row[r];
-        if (ended && any) {
-            launch_fill_i32((int*)e->gram.dev, 0, 128, e->st); launch_fill_i32(gram_state_of(e), -1, 64, e->st);
-            for (int r = 0; r < 64; ++r) gram_row_release(e, r);
-        }
-    }
+    if (!e->svc_on) req_batch_fetched(e, fin.data(), R);      // a batch whose every row has ended lets go of what its rows held
     if (step_logits) {
         if (!e->dump_steps) return fail(e, SONIC_ERR_INVALID, "step logits were not requested for the last run");
         HIPC(e, d2h_async(e, step_logits, e->dump, (size_t)e->dump_steps * R * e->d.vocab * 4));

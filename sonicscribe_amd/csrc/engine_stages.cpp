@@ -261,10 +261,8 @@ GreedyArgs greedy_args(sonic_engine* e, int R, bool dump) {
     g.dt = e->dt;
     // (request bias without guards: the guard values are the neutral ones - r * 1.0 and __fdiv_rn(r, 1.0) are exact, n = 0, no suppress list)
     if (hist_on(e)) { g.hist = e->hist; g.hist_ld = e->max_ctx; g.rep_penalty = e->gen_penalty; g.ngram = e->gen_ngram; g.suppress = e->gen_suppress_d; g.n_suppress = (int)e->gen_suppress.size(); }
-    if (e->opt_request_bias) g.bias_tab = e->bias.dev;
-    if (g.out_lp) g.topk = e->opt_top_logprobs;                  // (likewise)
-    if (e->opt_sampling && g.out_lp) g.samp = e->samp.dev;      // (the option is refused without token_logprobs, and token_logprobs cannot leave while it is on)
-    if (e->opt_grammar && g.out_lp && g.hist) { g.gram_ref = e->gram.dev; g.gram_state = gram_state_of(e); }      // (likewise; the option brought the history)
+    if (g.out_lp) g.topk = e->opt_top_logprobs;                  // (the alternatives ride in the log-probability records)
+    req_greedy_args(e, g);                                       // the per-request stages' rows (after out_lp and hist: two of them ride on those)
     if (e->i8) g.qo = QuantOut{e->hn_q, d.dec_d, e->sca_hn, e->oc_hn, e->ol_hn, d.dec_d, e->ov_hn};     // layer 0's q/k/v input, quantised
     return g;
 }
@@ -516,9 +514,7 @@ int reset_row_state(sonic_engine* e, int R, int n_tok) {
     launch_fill_i32(e->finished, 0, 64, e->st);
     launch_fill_i32(e->step_ctr, 0, 64, e->st);
     if (hist_on(e)) launch_hist_prompt(e->src, e->tok_seq, e->tok_pos_pf, n_tok, e->d.audio_token_id, e->hist, e->max_ctx, e->st);    // the rows' input_ids for the guards / the request bias
-    TRY(bias_upload(e, R));                                                                                                         // every request's table, or a zero count, into its row
-    TRY(gram_upload(e, R));                                                                                                         // every request's grammar at its start node, or a free row
-    return samp_upload(e, R);                                                                                                       // every request's (temperature, seed), or zeros: greedy
+    return req_upload(e, R);                                                                                                        // every request's claimed values, or the neutral ones, into its row
 }
 
 // head = false (the parallel forced run): the decoder layers only - its score rows are normalised and multiplied by run_forced_parallel
@@ -582,13 +578,9 @@ int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int
         HIPC(e, hipStreamWaitEvent(e->st, e->wait_ev, 0));  // engine's KV cache and row state, which this run is about to overwrite
         e->wait_pending = false;
     }
-    const int bias_R = e->bias.claim(), samp_R = e->samp.claim(), gram_R = e->gram.claim();      // sonic_set_request_bias / _sampling / option request_grammar: this batch consumes what they left whatever becomes of it (ENTER_CONSUME drops it on every other exit)
-    TRY(stage_count(e, bias_R, R, "sonic_set_request_bias", "tables"));
-    TRY(stage_count(e, samp_R, R, "sonic_set_request_sampling", "values"));
-    TRY(stage_count(e, gram_R, R, "option request_grammar_begin", "grammars"));
+    TRY(req_claim(e, R));      // sonic_set_request_bias / _sampling / option request_grammar: this batch consumes what they left whatever becomes of it (ENTER_CONSUME drops it on every other exit)
     HostPlan hp;
     TRY(plan_requests(e, req_win, R, prompt_ids, prompt_off, max_new, hp));
-    e->bias.take = bias_R >= 0; e->samp.take = samp_R >= 0; e->gram.take = gram_R >= 0;
     {   // staging buffer of this run: the one used two runs ago; its copies are almost always long done (a blocking wait otherwise)
         const int i = e->plan_idx ^ 1;
         if (e->plan_busy[i]) { HIPC(e, hipEventSynchronize(e->plan_ev[i])); e->plan_busy[i] = false; }
@@ -635,7 +627,7 @@ int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int
 // svc: the chunk belongs to a continuous decode loop (sonic_service_*), i.e. it runs beside a prefill slot and other loops by design - decode_step then
 // picks the forms that cost the fewest CU-microseconds rather than the shortest chain (gu64_split_norm).  Same bits either way; cached separately.
 int chunk_graph(sonic_engine* e, int R, int n, hipGraphExec_t* out, bool svc) {
-    const std::pair<int, int> key{R + (svc ? 4096 : 0) + (e->opt_token_logprobs ? 8192 : 0) + (e->gen_on ? 16384 : 0) + (e->opt_request_bias ? 32768 : 0) + (e->opt_sampling ? 65536 : 0) + e->opt_top_logprobs * 131072 + (e->opt_grammar ? (1 << 21) : 0), n};   // (the LP / GUARD / BIAS / SAMPLE / TOPK / GRAMMAR greedy kernel and its pointers are part of the capture)
+    const std::pair<int, int> key{R + (svc ? 4096 : 0) + (e->opt_token_logprobs ? 8192 : 0) + (e->gen_on ? 16384 : 0) + e->opt_top_logprobs * 131072 + req_graph_key(e), n};   // (the LP / GUARD / BIAS / SAMPLE / TOPK / GRAMMAR greedy kernel and its pointers are part of the capture)
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) { *out = it->second; return SONIC_OK; }
     hipGraph_t g = nullptr; hipGraphExec_t gx = nullptr;
@@ -749,6 +741,46 @@ static void fill_timings(sonic_engine* e, double host_enqueue_first, int steps_d
     t.host_decode_launches = e->host_launches; t.decode_lookahead = e->lookahead; t.decode_launches_per_layer = e->step_launches_per_layer;
 }
 
+// the parallel forced run's buffers, at the first such run of the handle or when score_chunk_rows has grown since: the chunk's logits
+// [score_chunk_rows][vocab] in the activation type (fp32 kind: fp32) and the score rows' plan (3 words per row, at most tok_cap rows) on the device and pinned
+static int score_alloc(sonic_engine* e) {
+    const int rows = e->opt_score_chunk_rows;
+    const size_t esz = e->f32 ? 4 : 2;
+    if (e->score_logits && e->score_rows_cap < rows) {
+        unsigned char* p = (unsigned char*)e->score_logits;
+        TRY(dfree(e, &p, (size_t)e->score_rows_cap * e->d.vocab * esz));
+        e->score_logits = nullptr; e->score_rows_cap = 0;
+    }
+    if (!e->score_logits) {
+        unsigned char* p = nullptr;
+        TRY(dalloc(e, &p, (size_t)rows * e->d.vocab * esz, false));
+        e->score_logits = p; e->score_rows_cap = rows;
+    }
+    if (!e->score_plan_d) TRY(dalloc(e, &e->score_plan_d, (size_t)3 * e->tok_cap));
+    if (!e->score_plan_h && hipHostMalloc((void**)&e->score_plan_h, ((size_t)3 * e->tok_cap + 4 * 64) * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(e, SONIC_ERR_OOM, "forced_parallel: pinned host memory exhausted"); }
+    return SONIC_OK;
+}
+// word timestamps (option forced_align): the align run's buffers, at its first run on the handle or when a run needs more than the last one left.
+// S score rows (<= tok_cap), A_max audio keys of the longest run, heads_per_layer the most heads any layer contributes
+template <typename Tt> static int align_grow(sonic_engine* e, Tt** p, size_t* cap, size_t need) {
+    if (*p && *cap >= need) return SONIC_OK;
+    if (*p) { TRY(dfree(e, p, *cap)); *cap = 0; }
+    TRY(dalloc(e, p, need, false));
+    *cap = need;
+    return SONIC_OK;
+}
+int align_alloc(sonic_engine* e, int S, int A_max, int heads_per_layer) {
+    size_t tcap = e->align_M_cap;
+    TRY(align_grow(e, &e->align_P, &e->align_P_cap, (size_t)2 * heads_per_layer * S * A_max));      // probabilities | filtered z
+    e->align_Zoff = (size_t)heads_per_layer * S * A_max;
+    TRY(align_grow(e, &e->align_trace, &tcap, (size_t)S * A_max));
+    TRY(align_grow(e, &e->align_M, &e->align_M_cap, (size_t)S * A_max));
+    if (!e->align_t) TRY(dalloc(e, &e->align_t, (size_t)64 * e->out_cap));
+    const size_t plan = (size_t)2 * e->tok_cap + 4 * 64 + ALIGN_MAX_HEADS;
+    if (!e->align_plan_d) { TRY(dalloc(e, &e->align_plan_d, plan)); e->align_plan_cap = plan; }
+    if (!e->align_plan_h && hipHostMalloc((void**)&e->align_plan_h, plan * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(e, SONIC_ERR_OOM, "forced_align: pinned host memory exhausted"); }
+    return SONIC_OK;
+}
 // The parallel forced run (option forced_parallel with forced ids set; include/sonic_hip.h beside sonic_set_forced_ids).  Under teacher forcing no
 // input depends on an output, so the run is ONE prefill: sequence r = prompt || forced[r][0 .. L_r - 1), L_r = 1 + the index of the first EOS id among its budget's
 // forced ids (HF's rule; the budget if there is none).  Token n of sequence r is scored by the hidden state at row q_off[r] + P - 1 + n: the S = sum L_r score rows are
@@ -762,11 +794,8 @@ static int run_forced_parallel(sonic_engine* e, const int32_t* req_win, int R, c
     if (!e->finalized) return fail(e, SONIC_ERR_INVALID, "weights not finalized");
     if (e->W < 1) return fail(e, SONIC_ERR_INVALID, "no PCM staged");
     if (e->svc_on) return fail(e, SONIC_ERR_INVALID, "this handle is decoding continuously (sonic_service_begin): prefill on another slot and splice the rows in");
-    const int bias_R = e->bias.claim(), samp_R = e->samp.claim(), gram_R = e->gram.claim();      // consumed, as on every other exit
-    if (gram_R >= 0) gram_drop_staged(e);
-    if (bias_R >= 0 || samp_R >= 0 || gram_R >= 0)
-        return fail(e, SONIC_ERR_INVALID, "forced_parallel: the parallel forced run applies no processors: the staged %s are refused (it scores the raw distribution; run with the option off to force step by step under them)",
-                    bias_R >= 0 ? "request bias tables (sonic_set_request_bias)" : samp_R >= 0 ? "sampling values (sonic_set_request_sampling)" : "grammars (option request_grammar)");
+    if (const char* staged = req_claim_none(e))      // consumed, as on every other exit
+        return fail(e, SONIC_ERR_INVALID, "forced_parallel: the parallel forced run applies no processors: the staged %s are refused (it scores the raw distribution; run with the option off to force step by step under them)", staged);
     const int N = e->opt_forced_fanout;
     if (R < 1 || R > e->Bm) return fail(e, SONIC_ERR_INVALID, "request count %d out of range 1..%d", R, e->Bm);
     if (R % N) return fail(e, SONIC_ERR_INVALID, "forced_fanout: %d sequences are not a multiple of the fan-out %d", R, N);
@@ -836,7 +865,6 @@ static int run_forced_parallel(sonic_engine* e, const int32_t* req_win, int R, c
         if (e->plan_busy[i]) { HIPC(e, hipEventSynchronize(e->plan_ev[i])); e->plan_busy[i] = false; }
         e->plan_idx = i; e->plan_h = e->plan_buf[i];
     }
-    e->bias.take = false; e->samp.take = false; e->gram.take = false;
     e->R = R; e->max_steps = max_steps; e->last_maxnew = hp.max_new;
     e->last_qlen.resize(R);
     for (int r = 0; r < R; ++r) e->last_qlen[r] = (int)(prompt_off[r + 1] - prompt_off[r]);      // the PROMPT's length: fetch_locked expects kv_len = prompt + tokens - 1
