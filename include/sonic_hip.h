@@ -514,7 +514,50 @@ SONIC_API int sonic_stage_mixed(sonic_engine* e, const int16_t* host_pcm, const 
  *   sonic_debug_read: "align_probs" [heads of the last selected layer][S][A_max] and "align_matrix" [S][A_max] of the last run, fp32 on every kind (S = the run's
  *   score rows, sequence after sequence; A_max = its longest audio run).
  *   test hook: on such a handle sonic_test_attention(q [B][Tq][Hq * 128], k [B][Tk][Hkv * 128], v = NULL, out, B, Tq, Tk, Hq, Hkv, hd = 128, causal = 0) runs the
- *   three kernels on caller data - all Hq heads, the audio run being all Tk keys - and out is [B][Tq][Tk + 1]: the matrix's row, then t_n. */
+ *   three kernels on caller data - all Hq heads, the audio run being all Tk keys - and out is [B][Tq][Tk + 1]: the matrix's row, then t_n.
+ *
+ * Draft-verified decoding (option "draft_verify", sonic_load_tensor "request_draft" / "draft.dispatch", sonic_debug_read "draft_accepted"): HF
+ * generate()'s assisted / prompt-lookup decoding with the draft brought by the caller - a previous partial of the same audio, a first-pass model, an edited transcript.
+ * The engine accepts the longest prefix of the draft that the model itself would have emitted, takes the model's own token at the first disagreement and carries on in
+ * the ordinary greedy loop, without leaving the device.  Every emitted token is an argmax of the model's processed scores; a wrong draft costs its prefill rows.  The
+ * feature adds no entry point and no struct: it travels as an option, two named int32 "tensors" and a sonic_debug_read name.
+ *   "draft_verify" = 1: set on the owner before its slots are created (they copy it).  Refused (SONIC_ERR_INVALID by name) while the handle has work in hand (the
+ *   rule of sonic_set_generation); on the int8 kind, whose prefill quantises per request group, so that a draft would change the group; on the fp32 test kind; on a
+ *   scoring handle ("forced_parallel", which in turn is refused while this option is on).  With the option off, or on with no draft staged, the engine launches
+ *   exactly what it launched before.  The buffers (the chunk's logits of the parallel forced run, score_chunk_rows x vocab elements; five words per draft position
+ *   and 4 x 64 per batch; a choice and a log-probability record per position; 64 accepted counts) come with the handle's first drafted prefill, are counted by
+ *   sonic_memory_info and go with the handle.
+ *   sonic_load_tensor(e, "request_draft", words, SONIC_DTYPE_I32, {n}, 1), words = [R | off[0 .. R] | ids]: the drafts of the R requests of the NEXT prefill on this
+ *   handle (the entry points sonic_set_request_bias names), which consumes them on success and on failure alike.  Request r's draft is ids[off[r] .. off[r + 1]);
+ *   D_r = off[r + 1] - off[r] may be 0.  SONIC_ERR_INVALID, nothing truncated, the message naming the cause: the option is off; an id outside the vocabulary; an id that
+ *   is the audio placeholder or one of the handle's EOS ids; and at the prefill: an R that is not the batch's; D_r > max_new[r] - 1; prompts and drafts together
+ *   beyond one prefill (the message says how many tokens were asked for and how many fit); forced ids set on the handle; a drafted request that also carries a bias
+ *   table, a temperature > 0 or a grammar (undrafted requests of the same batch may carry them).
+ *   A drafted request r with prompt P_r and draft d[0 .. D): the prefill runs over prompt || d, the K/V rows written as a prefill writes them.  Draft position n is
+ *   decided from the hidden row at position P - 1 + n: final norm, the tied lm_head as the prefill-family GEMM into the chunk buffer of the parallel forced run
+ *   ("score_chunk_rows" rows per launch), one block of verify_rows_kernel per row.  s_n = the row's logits after the handle's processors (sonic_set_generation, HF's
+ *   order) with history prompt || d[0 .. n); t_n = the first maximum of s_n (ties: the lower id; all -inf: 0); a_r = the least n with t_n != d[n], or D.  The request
+ *   then stands exactly where a prefill of prompt || d[0 .. a) would have left it, with its first a tokens and their log-probability records already written:
+ *   out_ids[r][0 .. a) = d[0 .. a); record n = log_softmax(s_n)[d[n]] and, with "top_logprobs" = K, the K alternatives of s_n, in the handle's layout of 1 + 2K
+ *   floats; n_new = a, kv_len = P + a, the next position P + a, the step counter a, and the head's row map pointing at hidden row P - 1 + a.  The UNCHANGED head then
+ *   produces token a (final norm over that row, the skinny lm_head, the greedy kernel: it appends to the history and applies the EOS and budget rules), and the decode
+ *   loop follows - graphs, chunks, continuous scheduler as they are.  K/V rows behind position P + a are stale and never read: decode attention sees kv_len keys, and
+ *   the next step overwrites position P + a.
+ *   consequences: a request with D = 0 goes through the very kernels of a batch without drafts and keeps its bits, also beside drafted requests.  Token a comes
+ *   from the skinny lm_head, the decision at position a from the GEMM: around a near-tie the head may emit d[a] after all - still the model's argmax, under the
+ *   step path's rounding.  Accepted tokens carry the prefill path's rounding, not the step loop's (DESIGN.md 6.8 measured max |dlogit| 0.031 between the two), so
+ *   near a tie a drafted run may leave the undrafted run's transcript where the two roundings order two ids differently.
+ *   want_step_logits: steps 0 .. D_r of a drafted row receive the raw logits of the verify pass (as the parallel forced run dumps its rows); steps from a on are
+ *   overwritten by the head and the loop as always.
+ *   sonic_debug_read(e, "draft_accepted", 0, out, R): a_r of the handle's last prefill as fp32 values (zeros behind a prefill without drafts); tests and diagnostics.
+ *   sonic_splice_rows refuses handles whose "draft_verify" differ, and copies a row's first n_new ids and records - for every row without an accepted draft that is one.
+ *   dispatcher: sonic_load_tensor(e, "draft.dispatch", words = [n | ids], SONIC_DTYPE_I32, {n + 1}, 1) on any handle of the dispatcher's weight owner arms the calling
+ *   thread's NEXT sonic_dispatch_submit* with that draft (n = 0: none) - no engine lock is taken, as for "grammar.dispatch:<id>"; the ids are checked at the arm, the
+ *   budget (n <= max_new - 1) and the request's other values at the submit, which refuses unless every handle of the dispatcher has the option on.  With the option
+ *   on, the prefill batcher counts prompt + draft tokens against one prefill's capacity.  sonic_pipeline_create refuses a handle with the option on, by name.
+ *   test hook: on such a handle sonic_test_greedy_guard WITH force_ids sends its rows to verify_rows_kernel - the slabs become the logits row as on a scoring handle;
+ *   row b is one draft position with history hist[b][0 .. hist_len[b]) and draft id force_ids[b]; tok_out[b] = t, lp_out B records of 1 + 2K floats; neutral guard
+ *   values launch the unguarded instantiation; B may exceed 64 (up to 4096). */
 SONIC_API int sonic_set_forced_ids(sonic_engine* e, const int32_t* ids, int R, int ld);
 SONIC_API int sonic_get_timings(sonic_engine* e, sonic_timings* out);
 SONIC_API int sonic_synchronize(sonic_engine* e);
@@ -601,7 +644,7 @@ SONIC_API int sonic_bench_gemm(sonic_engine* e, int M, int N, int K, int epi, in
 /* times the decode-step skinny GEMM (variant: 0 LDS-DMA nt, 1 LDS-DMA default policy, 2 registers nt, 3 registers plain, 9 pure-read floor) */
 SONIC_API int sonic_bench_skinny(sonic_engine* e, int M, int N, int K, int variant, int iters, float* us_per_launch);
 /* debug read-back of an internal bf16 activation buffer as fp32 ("prefill_tap" with index = 0 (embeddings) .. dec_layers,
- * "pe", "dx", "dqkv", "dq", "datt", "dact", "enc_x"; "align_probs", "align_matrix": fp32 buffers of the last align run, see sonic_set_forced_ids); tests / diagnostics only */
+ * "pe", "dx", "dqkv", "dq", "datt", "dact", "enc_x"; "align_probs", "align_matrix": fp32 buffers of the last align run, see sonic_set_forced_ids; "draft_accepted": the accepted counts of the last prefill, see there); tests / diagnostics only */
 SONIC_API int sonic_debug_read(sonic_engine* e, const char* name, int index, float* out, int64_t n);
 /* diagnostics: in-kernel timestamps (100 MHz device wall clock) of the decode kernels of one decoder layer, recorded while the option
  * "ktrace" = layer index is set: out[slot][block < 512][8 points], slots 0 qkv, 1 attention, 2 o_proj, 3 gate/up, 4 down */
@@ -615,7 +658,8 @@ SONIC_API int sonic_debug_ktrace(sonic_engine* e, int64_t* out, int64_t n);
  * "inject_dev_err" (tests: sets / clears the device error word); "token_logprobs" (not an experiment: per-token log-probabilities, see sonic_fetch_logprobs);
  * "top_logprobs" (not an experiment either: the K best alternatives of every step in the same records, see sonic_fetch_logprobs);
  * "forced_parallel", "forced_fanout", "score_chunk_rows" (not experiments: forced runs as one prefill pass - scoring given transcripts - see sonic_set_forced_ids);
- * "forced_align", "align_head" (not experiments: word timestamps on that pass, see sonic_set_forced_ids) */
+ * "forced_align", "align_head" (not experiments: word timestamps on that pass, see sonic_set_forced_ids);
+ * "draft_verify" (not an experiment: a request's draft is verified in its prefill pass, see sonic_set_forced_ids) */
 SONIC_API int sonic_set_option(sonic_engine* e, const char* key, int value);
 
 /* ---- Silero VAD network (silero-vad 5.x / 6.x, 16 kHz branch; csrc/vad.hip, layer table in sonicscribe_amd/vad_net.py) ----

@@ -91,6 +91,7 @@ class Transcription:
     descending, id ascending) with their log-probabilities - OpenAI's top_logprobs; places beyond the ids with a finite score hold (-1, -inf).  They are what
     the model scored, whatever token was emitted: on a greedy request column 0 is the token itself."""
     __slots__ = ("text", "token_ids", "token_logprobs", "avg_logprob", "temperature", "compression_ratio", "attempts", "top_token_ids", "top_logprobs",
+                 "draft_len", "draft_matched",      # a request that brought a draft (ASRModel(draft_verify=True); DESIGN.md 6.11): the ids of the draft as it was submitted, and how many of them the transcript begins with; 0 without
                  "grammar_status",      # a request decoded under a grammar: grammar.Grammar.walk over token_ids - "accepted", "incomplete" or "left"; None without
                  "words", "token_start", "token_end")      # word_timestamps=True (ASRModel(timestamps=True); DESIGN.md 6.9): timestamps.Word list and the tokens' times (EOS dropped); None without
 
@@ -98,6 +99,7 @@ class Transcription:
         from .fallback import compression_ratio
         self.text = text
         self.words = self.token_start = self.token_end = self.grammar_status = None
+        self.draft_len = self.draft_matched = 0
         self.temperature, self.compression_ratio, self.attempts = float(temperature), compression_ratio(text), 1
         self.token_ids = np.asarray(token_ids, np.int32)
         top_lp = top_ids = None
@@ -114,6 +116,27 @@ class Transcription:
         return f"Transcription(text={self.text!r}, tokens={self.token_ids.size}, avg_logprob={self.avg_logprob:.4f})"
 
 
+def cut_draft(ids: Sequence[int], eos_ids: Sequence[int], max_new: int) -> List[int]:
+    """A draft as the library takes it: cut in front of its first EOS id and at max_new - 1 ids (the last token of a budget is the model's own).  The library refuses
+    such drafts instead of cutting them; a caller who hands over a previous transcript - EOS included - should not have to"""
+    out: List[int] = []
+    for t in ids:
+        if int(t) in eos_ids or len(out) >= int(max_new) - 1:
+            break
+        out.append(int(t))
+    return out
+
+
+def draft_matched(token_ids: Sequence[int], draft: Sequence[int]) -> int:
+    """the length of the common prefix of a transcript's ids and its draft"""
+    n = 0
+    for a, b in zip(token_ids, draft):
+        if int(a) != int(b):
+            break
+        n += 1
+    return n
+
+
 def check_top_logprobs(top_logprobs, token_logprobs: bool, bulk: bool) -> int:
     """ASRModel's top_logprobs argument -> K, or ValueError by name: outside 0 .. 8, without token_logprobs, with bulk=True (the library's own refusals,
     made before an engine is built)"""
@@ -127,7 +150,7 @@ def check_top_logprobs(top_logprobs, token_logprobs: bool, bulk: bool) -> int:
     return K
 
 
-def _text_future(inner: "Future", decode, detailed: bool = False, temperature: float = 0.0, grammar=None) -> "Future[str]":
+def _text_future(inner: "Future", decode, detailed: bool = False, temperature: float = 0.0, grammar=None, draft=None) -> "Future[str]":
     """Future of the transcript behind a dispatcher future of token ids.  Cancelling it (a session that went away) cancels the queued
     request as well, so it never reaches the device.  detailed: the inner future carries (ids, log-probabilities), the result is a Transcription."""
     out: "Future[str]" = Future()
@@ -141,6 +164,8 @@ def _text_future(inner: "Future", decode, detailed: bool = False, temperature: f
                 tr = Transcription(decode(ids).strip(), ids, lps, temperature)
                 if grammar is not None:
                     tr.grammar_status = grammar.grammar.walk(tr.token_ids)
+                if draft:
+                    tr.draft_len, tr.draft_matched = len(draft), draft_matched(tr.token_ids, draft)
                 out.set_result(tr)
             else:
                 out.set_result(decode(f.result()).strip())
@@ -220,10 +245,11 @@ class AudioStream:
 
     def submit_samples(self, first: int, n: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None, detailed: bool = False,
                        sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature: Optional[float] = None,
-                       seed: Optional[int] = None, word_timestamps: bool = False, grammar=None) -> "Future[str]":
+                       seed: Optional[int] = None, word_timestamps: bool = False, grammar=None, draft=None) -> "Future[str]":
         """Transcribe ring samples [first, first + n) (the >30 s split of connection_manager.py:206-214 cuts at byte offsets, not chunks).
         detailed (a model built with token_logprobs=True): the future gives a Transcription instead of the text.  temperature / seed (a model built with
-        sampling=True): one attempt at that temperature - a float only, stream decodes take no fallback ladder."""
+        sampling=True): one attempt at that temperature - a float only, stream decodes take no fallback ladder.  draft (a model built with draft_verify=True): what the
+        transcript is expected to begin with - the previous partial's text or ids (ASRModel.submit)."""
         m = self.model
         if word_timestamps:
             raise ValueError("word_timestamps is not supported on submit() / transcribe_async() / stream decodes: align a finished transcript with ASRModel.align(), or use transcribe(..., word_timestamps=True)")
@@ -231,17 +257,18 @@ class AudioStream:
         bias = m._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost)
         samp = m._request_sampling(temperature, seed, ladder_ok=False)
         gram = m._request_grammar(grammar)
+        dr = m._request_draft(draft, int(max_new_tokens), bias, samp, gram)
         windows = [self.ring.slice(first + s, e - s) for s, e in frontend.split_windows(n, m.dims)]
         n_audio, _ = frontend.request_audio_tokens(n, m.dims)
         prompt = m.prompt.build(frontend.build_instruction(hotwords), n_audio)
-        return m._dispatch(windows, prompt, int(max_new_tokens), detailed, bias, samp, gram, replica=self.replica)
+        return m._dispatch(windows, prompt, int(max_new_tokens), detailed, bias, samp, gram, draft=dr, replica=self.replica)
 
     def submit_chunks(self, start_chunk_id: int, end_chunk_id: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None,
                       detailed: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
-                      temperature: Optional[float] = None, seed: Optional[int] = None, word_timestamps: bool = False, grammar=None) -> "Future[str]":
+                      temperature: Optional[float] = None, seed: Optional[int] = None, word_timestamps: bool = False, grammar=None, draft=None) -> "Future[str]":
         """Transcribe chunks start..end inclusive (audio_manager.py:76-79 get_chunks_by_range + :115-123 concatenation)."""
         first, n = self.chunk_range_samples(start_chunk_id, end_chunk_id)
-        return self.submit_samples(first, n, max_new_tokens, hotwords, detailed, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, word_timestamps, grammar)
+        return self.submit_samples(first, n, max_new_tokens, hotwords, detailed, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, word_timestamps, grammar, draft)
 
     async def transcribe_chunks(self, start_chunk_id: int, end_chunk_id: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None) -> str:
         return await asyncio.wrap_future(self.submit_chunks(start_chunk_id, end_chunk_id, max_new_tokens, hotwords))
@@ -259,7 +286,7 @@ class ASRModel:
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None,
                  request_bias: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: float = 0.0,
                  sampling: bool = False, temperature=0.0, seed: int = 0, compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
-                 scoring: bool = False, timestamps: bool = False, alignment_heads=None, grammar: bool = False,
+                 scoring: bool = False, timestamps: bool = False, alignment_heads=None, grammar: bool = False, draft_verify: bool = False,
                  _dims: Optional[ModelDims] = None,
                  _synthetic_seed: Optional[int] = None, _allow_synthetic_prompt: bool = False, _options: Optional[Dict[str, int]] = None,
                  _engine_mode: Optional[int] = None):
@@ -274,7 +301,9 @@ class ASRModel:
         word_timestamps=True give the time at which every token and word was spoken, from the decoder's attention onto the audio on that scoring handle (DESIGN.md 6.9);
         `grammar` (needs token_logprobs=True; not with bulk=True): requests may be
         restricted to the transcripts of a grammar - compile_grammar() of a phrase list or of a grammar.Grammar, passed as `grammar=` of the transcribe calls; the mask and
-        the state run inside the greedy kernel.  `alignment_heads`: the [layer, head] pairs to read (None: the `alignment_heads` entry of the checkpoint's generation_config.json, else every head of the last half of the layers).  The arguments with a leading underscore are not part of the
+        the state run inside the greedy kernel.  `draft_verify` (not with mode="int8", not with bulk=True): requests may bring a draft of their transcript
+        as `draft=` of the transcribe calls - a previous partial, a first-pass model's output, an edited transcript; the prefill accepts the prefix the model itself would
+        have emitted and decoding starts behind it, so a right draft costs one prefill instead of its tokens' steps and a wrong one only its prefill rows.  `alignment_heads`: the [layer, head] pairs to read (None: the `alignment_heads` entry of the checkpoint's generation_config.json, else every head of the last half of the layers).  The arguments with a leading underscore are not part of the
         supported surface: they exist for the test-suite and the benchmark and may change without notice.  `_engine_mode` in particular (an engine.MODE_*
         value in place of the one `mode` selects) is unsupported outside the tests: MODE_F32 has no slots, so it needs slots=1, continuous=False."""
         if mode not in ["native", "int8"]:
@@ -300,6 +329,12 @@ class ASRModel:
         if self.grammar and bool(bulk):
             raise ValueError("grammar is not supported with bulk=True: the bulk pipeline carries no per-request grammar state")
         self._grammars: List[Any] = []
+        # draft_verify: requests may bring a draft of their transcript (engine option of the same name, before the slots exist)
+        self.draft_verify = bool(draft_verify)
+        if self.draft_verify and mode == "int8":
+            raise ValueError("draft_verify is not supported with mode='int8': its prefill quantises per request group, so a draft would change the prompt's own values")
+        if self.draft_verify and bool(bulk):
+            raise ValueError("draft_verify is not supported with bulk=True: the bulk pipeline verifies no drafts")
         self.scoring = bool(scoring)
         if self.scoring and not token_logprobs:
             raise ValueError("scoring=True needs token_logprobs=True: a score is the candidates' token log-probabilities (ASRModel(..., token_logprobs=True, scoring=True))")
@@ -395,6 +430,9 @@ class ASRModel:
         if self.grammar:
             for eng in self.models:
                 eng.set_option("grammar", 1)
+        if self.draft_verify:
+            for eng in self.models:
+                eng.set_option("draft_verify", 1)
         self._retrier = fallback.Retrier()
         self.model = self.models[0]                  # main.py:84-86 checks and deletes `.model`
         # continuous: `decoders` handles per replica run a greedy loop over max_batch rows each, the other handles prefill (>= 1).  Streaming:
@@ -412,6 +450,8 @@ class ASRModel:
         if self.scoring:
             for eng in self.models:
                 s_ = eng.slot()
+                if self.draft_verify:
+                    s_.set_option("draft_verify", 0)      # (a scoring handle verifies no drafts: the library refuses the two options together)
                 s_.set_option("forced_parallel", 1)
                 self._score_engines.append(s_)
         if self.timestamps:          # the scoring handles also align: their parallel runs return t_n per token
@@ -531,7 +571,24 @@ class ASRModel:
             raise ValueError("grammar= takes what compile_grammar() returned (a grammar.CompiledGrammar)")
         return grammar
 
-    def _dispatch(self, windows, prompt, max_new: int, detailed: bool, bias, samp, gram=None, **route) -> "Future":
+    def _request_draft(self, draft, max_new: int, bias=None, samp=None, gram=None):
+        """One call's draft: None, or its token ids - a string goes through the tokenizer (_candidate_ids) - cut in front of the first EOS id and at max_new - 1 ids
+        (cut_draft).  ValueError by name when the model was built without draft_verify=True, and beside bias values, a temperature ladder (or any temperature > 0)
+        or a grammar: the verify pass applies the model's own processors only, and what it accepts is an argmax."""
+        if draft is None:
+            return None
+        if not getattr(self, "draft_verify", False):
+            raise ValueError("draft= needs a model built with draft_verify=True (ASRModel(..., draft_verify=True))")
+        if bias:
+            raise ValueError("draft= cannot be combined with bias values (sequence_bias / bad_words_ids / hotword_boost): the verify pass applies the model's own processors only")
+        if samp is not None and (samp[1] or any(t > 0 for t in samp[0])):
+            raise ValueError("draft= cannot be combined with a temperature ladder or a temperature > 0: an accepted draft token is the model's argmax, not a sample")
+        if gram is not None:
+            raise ValueError("draft= cannot be combined with a grammar: the verify pass applies the model's own processors only")
+        ids = cut_draft(self._candidate_ids(draft), self._eos_ids(), max_new)
+        return ids or None
+
+    def _dispatch(self, windows, prompt, max_new: int, detailed: bool, bias, samp, gram=None, draft=None, **route) -> "Future":
         """One request on the scheduler -> a future of its text (detailed: its Transcription).  samp (from _request_sampling): None, one attempt at a temperature,
         or the fallback ladder - each attempt a new request for the same windows, prompt, table and seed; the future resolves after the last one.  Retries
         are submitted by the model's worker thread, never by a completion callback and never by the caller (fallback.py)."""
@@ -541,11 +598,13 @@ class ASRModel:
             kw["bias"] = bias
         if gram is not None:
             kw["grammar"] = gram
+        if draft:
+            kw["draft"] = draft
         if samp is None:
-            return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=detailed, **kw), self.prompt.decode, detailed, grammar=gram)
+            return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=detailed, **kw), self.prompt.decode, detailed, grammar=gram, draft=draft)
         ts, ladder, seed = samp
         if not ladder:
-            return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=detailed, sampling=(ts[0], seed), **kw), self.prompt.decode, detailed, ts[0], grammar=gram)
+            return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=detailed, sampling=(ts[0], seed), **kw), self.prompt.decode, detailed, ts[0], grammar=gram, draft=draft)
 
         def one(temperature, seed):
             return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=True, sampling=(temperature, seed), **kw), self.prompt.decode, True, temperature, grammar=gram)
@@ -573,14 +632,16 @@ class ASRModel:
 
     def submit(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None,
                session: Optional[str] = None, detailed: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
-               temperature=None, seed: Optional[int] = None, word_timestamps: bool = False, grammar=None) -> "Future[str]":
+               temperature=None, seed: Optional[int] = None, word_timestamps: bool = False, grammar=None, draft=None) -> "Future[str]":
         """Non-blocking form of transcribe(): queues the request on a replica and returns a Future of the transcript.  `session`
         (e.g. the WebSocket client id) keeps a session's decodes on one GPU.  detailed (a model built with token_logprobs=True): the future
         gives a Transcription - text, token_ids, token_logprobs, avg_logprob - instead of the text.  sequence_bias / bad_words_ids / hotword_boost (a model
         built with request_bias=True): this request's own table, on top of the constructor's defaults (_request_bias).  temperature / seed (a model built with
         sampling=True): a float decodes once at that temperature, a sequence is the fallback ladder - the future resolves after its last attempt, and this
         thread never waits for one (_dispatch).  grammar (a model built with grammar=True): what compile_grammar() returned - the transcript is one of its paths;
-        a detailed result carries `grammar_status`."""
+        a detailed result carries `grammar_status`.  draft (a model built with draft_verify=True): what the transcript is expected to begin with, a string or token
+        ids - cut here in front of its first EOS id and at max_new_tokens - 1; the result is the model's own greedy transcript whatever the draft says, a detailed one
+        carries `draft_len` and `draft_matched`.  Not with bias values, a temperature > 0 or a grammar (ValueError)."""
         if not hasattr(self, "model"):
             raise RuntimeError("ASR model has been released")
         if word_timestamps:
@@ -589,9 +650,10 @@ class ASRModel:
         bias = self._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost)
         samp = self._request_sampling(temperature, seed)
         gram = self._request_grammar(grammar)
+        dr = self._request_draft(draft, int(max_new_tokens), bias, samp, gram)
         pcm, windows, n_audio = self._prepare(audio_tensor, sampling_rate)
         prompt = self.prompt.build(frontend.build_instruction(hotwords), n_audio)
-        return self._dispatch(windows, prompt, int(max_new_tokens), detailed, bias, samp, gram, session=session)
+        return self._dispatch(windows, prompt, int(max_new_tokens), detailed, bias, samp, gram, draft=dr, session=session)
 
     def open_stream(self, session: str, buffer_seconds: float = 30.0, margin_seconds: float = 10.0, sampling_rate: int = 16000) -> AudioStream:
         """A streaming session whose audio stays on the device (config.py:25 MAX_AUDIO_BUFFER_SECONDS = 30): chunks are appended to a
@@ -606,16 +668,17 @@ class ASRModel:
     async def transcribe_async(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128,
                                hotwords: Optional[List[str]] = None, session: Optional[str] = None, detailed: bool = False,
                                sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None, seed: Optional[int] = None,
-                               word_timestamps: bool = False, grammar=None) -> str:
+                               word_timestamps: bool = False, grammar=None, draft=None) -> str:
         """Awaitable transcribe() for the asyncio callers (connection_manager.py:127-245): the event loop is not blocked while the
         device works, so all sessions' partial and final decodes can be in flight (and batched) together."""
-        return await asyncio.wrap_future(self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, session, detailed, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, word_timestamps, grammar))
+        return await asyncio.wrap_future(self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, session, detailed, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, word_timestamps, grammar, draft))
 
     def transcribe(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128,
                    hotwords: Optional[List[str]] = None, return_debug_info: bool = False,
                    sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None, seed: Optional[int] = None,
-                   word_timestamps: bool = False, grammar=None) -> Union[str, Dict[str, Any]]:
-        """grammar (a model built with grammar=True): what compile_grammar() returned; the debug dictionary gains `grammar_status` (grammar.Grammar.walk over
+                   word_timestamps: bool = False, grammar=None, draft=None) -> Union[str, Dict[str, Any]]:
+        """draft (a model built with draft_verify=True): see submit(); the debug dictionary gains `draft_len` and `draft_matched`.
+        grammar (a model built with grammar=True): what compile_grammar() returned; the debug dictionary gains `grammar_status` (grammar.Grammar.walk over
         the returned ids: "accepted", "incomplete" at a budget that ended inside the grammar, "left").
         word_timestamps (a model built with timestamps=True): the request is decoded as always, then its tokens are aligned on the scoring
         handle - the audio is encoded a second time there.  With return_debug_info the dictionary gains `words` (word, start, end, probability), `token_start`
@@ -628,7 +691,7 @@ class ASRModel:
         try:
             want = bool((return_debug_info or word_timestamps) and getattr(self, "token_logprobs", False))
             res = self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, detailed=want, sequence_bias=sequence_bias, bad_words_ids=bad_words_ids,
-                              hotword_boost=hotword_boost, temperature=temperature, seed=seed, grammar=grammar).result()
+                              hotword_boost=hotword_boost, temperature=temperature, seed=seed, grammar=grammar, draft=draft).result()
             det, transcript = (res, res.text) if want else (None, res)
             if word_timestamps:
                 self._attach_alignment([audio_tensor], [det], sampling_rate, hotwords)
@@ -648,6 +711,8 @@ class ASRModel:
                         info.update({"temperature": det.temperature, "compression_ratio": det.compression_ratio})
                     if grammar is not None:
                         info["grammar_status"] = det.grammar_status
+                    if draft is not None:
+                        info.update({"draft_len": det.draft_len, "draft_matched": det.draft_matched})
                     if word_timestamps:
                         info.update({"words": [w.as_dict() for w in det.words], "token_start": det.token_start, "token_end": det.token_end})
                 return info
@@ -662,11 +727,14 @@ class ASRModel:
 
     def transcribe_batch(self, audios: Sequence[Any], sampling_rate: int = 16000, max_new_tokens: Union[int, Sequence[int]] = 128,
                          hotwords: Optional[List[str]] = None, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
-                         temperature=None, seed: Optional[int] = None, word_timestamps: bool = False, grammar=None) -> List[str]:
+                         temperature=None, seed: Optional[int] = None, word_timestamps: bool = False, grammar=None, drafts=None) -> List[str]:
         """Batched extension (the reference is B=1 per call): one device batch, per-segment results identical to transcribe().  temperature / seed: every
         segment is decoded with them (a sequence: every segment goes down its own ladder, as independent requests on the scheduler).  word_timestamps (a model
         built with timestamps=True): every audio is decoded as its own request, then all are aligned together; the result is a list of Transcription.
-        grammar (a model built with grammar=True): one compile_grammar() result for every audio, or a sequence with one (or None) per audio."""
+        grammar (a model built with grammar=True): one compile_grammar() result for every audio, or a sequence with one (or None) per audio.
+        drafts (a model built with draft_verify=True): one draft (a string, token ids or None) per audio; see submit()."""
+        if drafts is not None and len(drafts) != len(audios):
+            raise ValueError(f"{len(audios)} audios but {len(drafts)} drafts")
         grams = list(grammar) if isinstance(grammar, (list, tuple)) else [grammar] * len(audios)
         if len(grams) != len(audios):
             raise ValueError(f"{len(audios)} audios but {len(grams)} grammars")
@@ -675,7 +743,7 @@ class ASRModel:
             self._check_timestamps()
             mn_ = [int(max_new_tokens)] * len(audios) if isinstance(max_new_tokens, int) else [int(x) for x in max_new_tokens]
             futs_ = [self.submit(a, sampling_rate, mn_[i], hotwords, detailed=True, sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotword_boost=hotword_boost,
-                                 temperature=temperature, seed=seed, grammar=grams[i]) for i, a in enumerate(audios)]
+                                 temperature=temperature, seed=seed, grammar=grams[i], draft=None if drafts is None else drafts[i]) for i, a in enumerate(audios)]
             dets = [f.result() for f in futs_]
             self._attach_alignment(list(audios), dets, sampling_rate, hotwords)
             return dets
@@ -685,6 +753,7 @@ class ASRModel:
         if samp is not None and not samp[1]:
             kw["request_sampling"] = [(samp[0][0], samp[2])] * len(audios)
         mn = [int(max_new_tokens)] * len(audios) if isinstance(max_new_tokens, int) else [int(x) for x in max_new_tokens]
+        drs = [None] * len(audios) if drafts is None else [self._request_draft(d, mn[i], bias, samp, grams[i]) for i, d in enumerate(drafts)]
         segs, req_win, prompts = [], [0], []
         instruction = frontend.build_instruction(hotwords)
         for a in audios:
@@ -693,15 +762,17 @@ class ASRModel:
             req_win.append(len(segs))
             prompts.append(self.prompt.build(instruction, n_audio))
         if samp is not None and samp[1]:
-            futs = [self._dispatch(segs[req_win[i]:req_win[i + 1]], prompts[i], mn[i], False, bias, samp, grams[i]) for i in range(len(audios))]
+            futs = [self._dispatch(segs[req_win[i]:req_win[i + 1]], prompts[i], mn[i], False, bias, samp, grams[i], draft=drs[i]) for i in range(len(audios))]
             return [f.result() for f in futs]
         if len(self.models) == 1 and not self.continuous:
             if any(g is not None for g in grams):
                 kw["request_grammar"] = [None if g is None else g.on(self.model) for g in grams]
+            if any(drs):
+                kw["request_draft"] = drs
             ids, _ = self.model.transcribe_batch(segs, prompts, mn, req_win=req_win, **kw)
         else:            # independent segments: spread over the replicas (least-loaded placement), results in input order
             skw = {"sampling": kw["request_sampling"][0]} if "request_sampling" in kw else {}
-            futs = [self._dispatcher.submit(segs[req_win[i]:req_win[i + 1]], prompts[i], mn[i], **({"bias": bias} if bias else {}), **({"grammar": grams[i]} if grams[i] is not None else {}), **skw)
+            futs = [self._dispatcher.submit(segs[req_win[i]:req_win[i + 1]], prompts[i], mn[i], **({"bias": bias} if bias else {}), **({"grammar": grams[i]} if grams[i] is not None else {}), **({"draft": drs[i]} if drs[i] else {}), **skw)
                     for i in range(len(audios))]
             ids = [f.result() for f in futs]
         return [self.prompt.decode(i).strip() for i in ids]
@@ -874,6 +945,7 @@ class ASRModel:
                      "weights_mb": self.model.weight_bytes() / 1024 ** 2 if hasattr(self, "model") else 0.0})
         info["scoring"] = bool(self.__dict__.get("scoring", False))
         info["grammar"] = bool(self.__dict__.get("grammar", False))
+        info["draft_verify"] = bool(self.__dict__.get("draft_verify", False))
         info["timestamps"] = bool(self.__dict__.get("timestamps", False))
         g = self.__dict__.get("generation_guards")
         if g is not None:                            # the logits processors in force: the checkpoint's generation_config.json unless the constructor overrode it

@@ -45,6 +45,9 @@ struct sonic_grammar;
 extern "C" sonic_grammar* engine_take_dispatch_grammar(void);   // engine.cpp: the grammar sonic_load_tensor "grammar.dispatch:<id>" armed for this thread's next submit (with a reference), or NULL ...
 extern "C" void engine_grammar_unref(sonic_grammar* g);     // ... and the reference's return
 extern "C" void* engine_grammar_owner(sonic_grammar* g);    // engine.cpp: the weight owner a grammar lives on
+extern "C" int engine_draft_verify_on(sonic_engine* e);     // engine_generation.cpp: option draft_verify on this handle
+extern "C" int engine_take_dispatch_draft(const int32_t** ids);   // ... the draft sonic_load_tensor "draft.dispatch" armed for this thread's next submit (-1: none; else its length)
+extern "C" int engine_tok_cap(sonic_engine* e);             // ... the tokens one prefill of a handle holds
 extern "C" int engine_set_request_grammar(sonic_engine* e, sonic_grammar* const* grammars, int R);   // engine.cpp: a batch's grammars for the handle's next prefill
 extern "C" int engine_thread_fail(int code, const char* msg);   // engine.cpp: the calling thread's sonic_last_error(NULL)
 
@@ -61,6 +64,7 @@ struct Req {
     std::vector<int32_t> b_ids, b_off; std::vector<float> b_val;  // its own sequence-bias table (sonic_dispatch_submit_bias): ids, offsets [n + 1] (empty: none), biases
     bool sampled = false; float temperature = 0.f; uint64_t seed = 0;   // its own (temperature, seed) (sonic_dispatch_submit_sampled); unsampled requests of a batch are greedy
     sonic_grammar* gram = nullptr;                                 // its grammar ("grammar.dispatch:<id>" ahead of the submit): a reference held from the submit until the request completes
+    std::vector<int32_t> draft;                                    // its draft ("draft.dispatch" ahead of the submit; option draft_verify): the prefill verifies it
     bool cancelled = false;
 };
 typedef std::shared_ptr<Req> ReqP;
@@ -77,6 +81,7 @@ struct sonic_dispatch {
     bool bias = false;                                             // every handle has option request_bias on
     bool samp = false;                                             // every handle has option sampling on
     bool gram = false;                                             // every handle has option grammar on
+    bool draft = false; int tok_cap = 0;                           // every handle has option draft_verify on; then a batch's prompts and drafts are counted against tok_cap
     std::mutex mu;
     std::condition_variable cv;                                    // queue, hand-overs, free rows, state
     std::condition_variable cv_done;                               // completions
@@ -154,6 +159,15 @@ int prefill_batch(sonic_dispatch* d, sonic_engine* h, const std::vector<ReqP>& b
         for (auto& r : batch) gs.push_back(r->gram);
         rc = engine_set_request_grammar(h, gs.data(), R);
     }
+    bool any_draft = false;
+    for (auto& r : batch) any_draft = any_draft || !r->draft.empty();
+    if (rc == SONIC_OK && any_draft) {                             // the requests' drafts as sonic_load_tensor "request_draft" takes them; the prefill below consumes them
+        std::vector<int32_t> w{R, 0};
+        for (auto& r : batch) w.push_back(w.back() + (int32_t)r->draft.size());
+        for (auto& r : batch) w.insert(w.end(), r->draft.begin(), r->draft.end());
+        const int64_t n = (int64_t)w.size();
+        rc = sonic_load_tensor(h, "request_draft", w.data(), SONIC_DTYPE_I32, &n, 1);
+    }
     if (rc == SONIC_OK) rc = sonic_prefill(h, req_win.data(), R, ids.data(), poff.data(), mn.data(), 0);
     if (rc != SONIC_OK && err) *err = sonic_last_error(h);
     return rc;
@@ -190,7 +204,7 @@ void prefill_thread(sonic_dispatch* d, sonic_engine* h) {
             d->cv.wait(lk, [&] { return d->stop || d->failed || (!d->q.empty() && *std::max_element(d->free_rows.begin(), d->free_rows.end()) > 0); });
             if (d->stop || d->failed) return;                      // closing / failed: nothing new is started (destroy / the decode side fails what is queued)
             k = (int)(std::max_element(d->free_rows.begin(), d->free_rows.end()) - d->free_rows.begin());   // the emptiest decoder takes the whole batch
-            int used = 0;
+            int used = 0; long toks = 0;
             while (!d->q.empty()) {                                // oldest first, whatever fits the handle's windows and the free rows; classes mix
                 ReqP r = d->q.front();
                 if (r->cancelled) { d->q.pop_front(); d->queued_windows -= r->W; finish(d, r, SONIC_ERR_INVALID, "cancelled"); continue; }
@@ -201,8 +215,10 @@ void prefill_thread(sonic_dispatch* d, sonic_engine* h) {
                     continue;
                 }
                 if ((int)batch.size() >= d->free_rows[k] || used + r->W > d->pre_cap) break;
+                const long rt = (long)r->prompt.size() + (long)r->draft.size();
+                if (d->draft && !batch.empty() && toks + rt > d->tok_cap) break;      // option draft_verify: prompts and drafts together fit one prefill (a request that alone does not is refused by it, by name)
                 d->q.pop_front(); d->queued_windows -= r->W;
-                batch.push_back(r); used += r->W;
+                batch.push_back(r); used += r->W; toks += rt;
             }
             if (batch.empty()) continue;
             d->free_rows[k] -= (int)batch.size();                  // reserved until the rows are fetched (or the prefill fails)
@@ -341,6 +357,9 @@ SONIC_API int sonic_dispatch_create(sonic_engine* const* decoders, int n_dec, so
     for (int i = 0; i < n_dec + n_pre; ++i) d->samp = d->samp && engine_sampling_on(i < n_dec ? decoders[i] : prefills[i - n_dec]);
     d->gram = true;
     for (int i = 0; i < n_dec + n_pre; ++i) d->gram = d->gram && engine_grammar_on(i < n_dec ? decoders[i] : prefills[i - n_dec]);
+    d->draft = true; d->tok_cap = engine_tok_cap(prefills[0]);
+    for (int i = 0; i < n_dec + n_pre; ++i) d->draft = d->draft && engine_draft_verify_on(i < n_dec ? decoders[i] : prefills[i - n_dec]);
+    for (int i = 0; i < n_pre; ++i) d->tok_cap = std::min(d->tok_cap, engine_tok_cap(prefills[i]));
     d->free_rows.assign(n_dec, rows); d->hand.resize(n_dec);
     for (int i = 0; i < n_dec; ++i) {
         const int rc = sonic_service_begin(d->dec[i]);
@@ -361,6 +380,8 @@ static int dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, const int
     // the grammar armed on this thread (sonic_load_tensor "grammar.dispatch:<id>"): this submit takes it whatever becomes of it
     struct Armed { sonic_grammar* g; ~Armed() { if (g) engine_grammar_unref(g); } } armed{engine_take_dispatch_grammar()};
     sonic_grammar* gram = armed.g;
+    const int32_t* draft = nullptr;
+    const int n_draft = engine_take_dispatch_draft(&draft);        // ... and the draft ("draft.dispatch"), likewise
     if (!d || !ticket_out || W < 1 || !prompt_ids || prompt_len < 1 || max_new < 1 || !host_off) return SONIC_ERR_INVALID;
     if (rings && (!ring_start || !ring_n)) return SONIC_ERR_INVALID;
     auto r = std::make_shared<Req>();
@@ -379,6 +400,16 @@ static int dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, const int
     std::unique_lock<std::mutex> lk(d->mu);
     if (d->stop) return SONIC_ERR_INVALID;
     if (d->failed) return d->failed;
+    if (n_draft > 0) {
+        if (!d->draft) return engine_thread_fail(SONIC_ERR_INVALID, "draft.dispatch: option draft_verify is off on a handle of this dispatcher (set it on the owner before its slots are created)");
+        if (n_draft > max_new - 1) {
+            char m[200]; snprintf(m, sizeof m, "draft.dispatch: the draft holds %d ids, the request's budget of %d tokens leaves room for %d (the last token is the model's own; nothing is truncated)", n_draft, max_new, max_new - 1);
+            return engine_thread_fail(SONIC_ERR_INVALID, m);
+        }
+        if (n_seq > 0 || (sampled && temperature > 0.f) || gram)
+            return engine_thread_fail(SONIC_ERR_INVALID, "draft.dispatch: a drafted request carries no bias table, temperature > 0 or grammar (the verify pass applies the handle's processors only)");
+        r->draft.assign(draft, draft + n_draft);
+    }
     if (gram) {
         if (!d->gram) return engine_thread_fail(SONIC_ERR_INVALID, "grammar.dispatch: option grammar is off on a handle of this dispatcher (set it on the owner before its slots are created)");
         const void* wid = nullptr;

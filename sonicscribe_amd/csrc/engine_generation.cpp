@@ -434,6 +434,117 @@ extern "C" int engine_bias_validate(sonic_engine* e, const int32_t* seq_ids, con
 }
 extern "C" int engine_thread_fail(int code, const char* msg) { return fail(nullptr, code, "%s", msg); }
 
+// ---- option draft_verify (include/sonic_hip.h beside sonic_set_forced_ids): HF generate()'s assisted / prompt-lookup decoding with the draft given by
+// the caller.  The caller holds the lock and has asked gen_busy.  No buffer comes with the option: draft_alloc brings them at the handle's first drafted prefill
+int draft_enable(sonic_engine* e, int on) {
+    if (on && e->i8) return fail(e, SONIC_ERR_INVALID, "draft_verify: the int8 kind refuses it (its prefill finds the outlier columns over the rows of a request: a draft would change the group, and with it the prompt's own values)");
+    if (on && e->f32) return fail(e, SONIC_ERR_INVALID, "draft_verify: the fp32 test kind has no verify kernels; use a bf16 or fp16 handle");
+    if (on && e->opt_forced_parallel) return fail(e, SONIC_ERR_INVALID, "draft_verify: option forced_parallel is on: a scoring handle decodes nothing a draft could shorten");
+    e->opt_draft_verify = on ? 1 : 0; e->draft_pending = -1; e->draft_take = false;
+    if (!on) e->draft_last_S = 0;
+    return SONIC_OK;
+}
+// sonic_load_tensor(e, "request_draft", words, SONIC_DTYPE_I32, {n}, 1), words = [R | off[0 .. R] | ids]: the drafts of the R requests of the next prefill on this handle
+// (the entry points of sonic_set_request_bias), which consumes them on success and on failure alike.  Refused during an asynchronous run without waiting for its lock
+int draft_stage_words(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim) {
+    { std::lock_guard<std::mutex> ak(e->a_mu); if (e->a_pending || e->a_running) return fail(nullptr, SONIC_ERR_INVALID, "request_draft: an asynchronous run of this handle is in flight"); }
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipGetLastError();
+    e->draft_pending = -1;
+    if (!e->opt_draft_verify) return fail(e, SONIC_ERR_INVALID, "request_draft: option draft_verify is off on this handle (sonic_set_option(e, \"draft_verify\", 1) on the owner before its slots are created)");
+    if (dtype != SONIC_DTYPE_I32 || ndim != 1 || shape[0] < 3) return fail(e, SONIC_ERR_INVALID, "request_draft: the drafts are one row of int32 words [R | off[0 .. R] | ids] (SONIC_DTYPE_I32, ndim 1)");
+    const int* w = (const int*)data; const int64_t n = shape[0];
+    const int R = w[0];
+    if (R < 1 || R > e->Bm || R > 64 || n < (int64_t)R + 2) return fail(e, SONIC_ERR_INVALID, "request_draft: %d requests (1 .. %d), %lld words", R, e->Bm, (long long)n);
+    const int* off = w + 1; const int* ids = w + R + 2;
+    if (off[0] != 0 || (int64_t)off[R] != n - (R + 2)) return fail(e, SONIC_ERR_INVALID, "request_draft: the offsets run from %d to %d, the words hold %lld ids", off[0], off[R], (long long)(n - (R + 2)));
+    for (int r = 0; r < R; ++r) {
+        if (off[r + 1] < off[r]) return fail(e, SONIC_ERR_INVALID, "request_draft: request offsets decrease at request %d", r);
+        for (int k = off[r]; k < off[r + 1]; ++k) {
+            const int id = ids[k];
+            if (id < 0 || id >= e->d.vocab) return fail(e, SONIC_ERR_INVALID, "request_draft: token id %d of request %d is out of vocabulary (%d)", id, r, e->d.vocab);
+            if (id == e->d.audio_token_id) return fail(e, SONIC_ERR_INVALID, "request_draft: token id %d of request %d is the audio placeholder, which cannot be emitted", id, r);
+            for (int q = 0; q < e->d.n_eos; ++q)
+                if (id == e->d.eos[q]) return fail(e, SONIC_ERR_INVALID, "request_draft: token id %d of request %d is an EOS id of this handle (a draft ends in front of it; nothing is truncated)", id, r);
+        }
+    }
+    e->draft_stage.assign(w, w + n);
+    e->draft_pending = R;
+    return SONIC_OK;
+}
+int draft_extend(sonic_engine* e, int R, const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new,
+                 std::vector<int32_t>& ids, std::vector<int64_t>& off, std::vector<int32_t>& left, std::vector<int>& dlen) {
+    dlen.clear();
+    if (!e->draft_take) return SONIC_OK;
+    const int* doff = e->draft_stage.data() + 1; const int* dids = e->draft_stage.data() + R + 2;
+    if (doff[R] == 0) return SONIC_OK;                       // every draft is empty: the prefill of today
+    if (e->force_d) return fail(e, SONIC_ERR_INVALID, "request_draft: forced ids are set on this handle (sonic_set_forced_ids): teacher forcing decides every token, a draft has nothing to offer");
+    const int* gst = e->gram.take ? (const int*)(e->gram.host + 64) : nullptr;
+    long asked = 0;
+    for (int r = 0; r < R; ++r) {
+        const int D = doff[r + 1] - doff[r];
+        if (prompt_off[r + 1] - prompt_off[r] < 1) return fail(e, SONIC_ERR_INVALID, "request %d has an empty prompt", r);
+        if (max_new[r] < 1) return fail(e, SONIC_ERR_INVALID, "max_new_tokens must be >= 1");
+        if (D > max_new[r] - 1) return fail(e, SONIC_ERR_INVALID, "request_draft: the draft of request %d holds %d ids, its budget of %d tokens leaves room for %d (the last token is the model's own; nothing is truncated)", r, D, max_new[r], max_new[r] - 1);
+        if (D > 0 && e->bias.take && e->bias.host[r] > 0) return fail(e, SONIC_ERR_INVALID, "request_draft: request %d carries a draft and a request bias table (sonic_set_request_bias): the verify pass applies the handle's processors only", r);
+        if (D > 0 && e->samp.take && e->samp.host[3 * r] != 0u) return fail(e, SONIC_ERR_INVALID, "request_draft: request %d carries a draft and a temperature > 0 (sonic_set_request_sampling): a sampled token is not the argmax a draft is checked against", r);
+        if (D > 0 && gst && gst[r] != -1) return fail(e, SONIC_ERR_INVALID, "request_draft: request %d carries a draft and a grammar (option request_grammar): the verify pass applies the handle's processors only", r);
+        asked += (prompt_off[r + 1] - prompt_off[r]) + D;
+    }
+    if (asked > e->tok_cap) return fail(e, SONIC_ERR_INVALID, "request_draft: the batch asks for %ld tokens (prompts and drafts), %d fit one prefill (tok_cap)", asked, e->tok_cap);
+    off.assign(R + 1, 0); left.resize(R); dlen.resize(R);
+    for (int r = 0; r < R; ++r) {
+        const int D = doff[r + 1] - doff[r];
+        ids.insert(ids.end(), prompt_ids + prompt_off[r], prompt_ids + prompt_off[r + 1]);
+        ids.insert(ids.end(), dids + doff[r], dids + doff[r + 1]);
+        off[r + 1] = (int64_t)ids.size(); dlen[r] = D; left[r] = max_new[r] - D;      // (plan_requests' context check stays at prompt + max_new)
+    }
+    return SONIC_OK;
+}
+int draft_alloc(sonic_engine* e) {
+    TRY(score_logits_alloc(e));
+    const size_t plan = (size_t)5 * e->tok_cap + 4 * 64;
+    if (!e->draft_plan_d) TRY(dalloc(e, &e->draft_plan_d, plan));
+    for (int i = 0; i < 2; ++i)
+        if (!e->draft_plan_h[i] && hipHostMalloc((void**)&e->draft_plan_h[i], plan * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(e, SONIC_ERR_OOM, "draft_verify: pinned host memory exhausted"); }
+    if (!e->ver_tok) TRY(dalloc(e, &e->ver_tok, (size_t)e->tok_cap));
+    if (e->ver_rec && e->ver_rec_w != lp_width(e)) TRY(dfree(e, &e->ver_rec, (size_t)e->tok_cap * e->ver_rec_w));
+    if (!e->ver_rec) { TRY(dalloc(e, &e->ver_rec, (size_t)e->tok_cap * lp_width(e))); e->ver_rec_w = lp_width(e); }
+    if (!e->draft_acc) TRY(dalloc(e, &e->draft_acc, (size_t)64));
+    return SONIC_OK;
+}
+// sonic_load_tensor "draft.dispatch" on any handle of a dispatcher's weight owner, words = [n | ids]: the calling thread's NEXT sonic_dispatch_submit* carries that draft
+// (n = 0: none), which takes it whatever becomes of the submit.  A thread-local and no engine lock, as "grammar.dispatch:<id>": a decoding handle holds its lock for a
+// chunk at a time.  The ids are checked here, against the handle's model; the budget and the dispatcher's handles at the submit
+static thread_local std::vector<int32_t> g_dispatch_draft;
+static thread_local bool g_dispatch_draft_armed = false;
+int draft_dispatch_arm(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim) {
+    g_dispatch_draft.clear(); g_dispatch_draft_armed = false;
+    if (dtype != SONIC_DTYPE_I32 || ndim != 1 || shape[0] < 1) return fail(nullptr, SONIC_ERR_INVALID, "draft.dispatch: a draft is one row of int32 words [n | ids] (SONIC_DTYPE_I32, ndim 1)");
+    const int* w = (const int*)data;
+    if (w[0] < 0 || (int64_t)w[0] != shape[0] - 1) return fail(nullptr, SONIC_ERR_INVALID, "draft.dispatch: the words name %d ids and hold %lld", w[0], (long long)(shape[0] - 1));
+    if (!e->opt_draft_verify) return fail(nullptr, SONIC_ERR_INVALID, "draft.dispatch: option draft_verify is off on this handle (sonic_set_option(e, \"draft_verify\", 1) on the owner before its slots are created)");
+    for (int k = 1; k <= w[0]; ++k) {
+        const int id = w[k];
+        if (id < 0 || id >= e->d.vocab) return fail(nullptr, SONIC_ERR_INVALID, "draft.dispatch: token id %d is out of vocabulary (%d)", id, e->d.vocab);
+        if (id == e->d.audio_token_id) return fail(nullptr, SONIC_ERR_INVALID, "draft.dispatch: token id %d is the audio placeholder, which cannot be emitted", id);
+        for (int q = 0; q < e->d.n_eos; ++q)
+            if (id == e->d.eos[q]) return fail(nullptr, SONIC_ERR_INVALID, "draft.dispatch: token id %d is an EOS id of this handle (a draft ends in front of it; nothing is truncated)", id);
+    }
+    if (w[0] == 0) return SONIC_OK;
+    g_dispatch_draft.assign(w + 1, w + 1 + w[0]); g_dispatch_draft_armed = true;
+    return SONIC_OK;
+}
+// dispatch.cpp (same library, not exported): the draft armed for this thread's next submit (-1: none; else its length, the ids valid until the thread arms again);
+// whether the option is on for a handle; the tokens one prefill of a handle holds
+extern "C" int engine_take_dispatch_draft(const int32_t** ids) {
+    if (!g_dispatch_draft_armed) return -1;
+    g_dispatch_draft_armed = false; *ids = g_dispatch_draft.data();
+    return (int)g_dispatch_draft.size();
+}
+extern "C" int engine_tok_cap(sonic_engine* e) { return e ? e->tok_cap : 0; }
+extern "C" int engine_draft_verify_on(sonic_engine* e) { return e && e->opt_draft_verify ? 1 : 0; }      // (pipeline.cpp too: the bulk pipeline refuses such a handle)
+
 // HF generate()'s logits processors for greedy decoding, as the checkpoint's generation_config.json (or the caller) sets them: repetition_penalty (1.0 = none),
 // no_repeat_ngram_size (0 = none), suppress_tokens (n_suppress = 0: none; at most 256 ids).  The neutral values switch the guards off: the engine then launches
 // the kernels it launched before.  Set it on the owner before slots are created (they copy it).  SONIC_ERR_INVALID for a value out of range, and while the handle
@@ -467,14 +578,19 @@ int req_claim(sonic_engine* e, int R) {
     TRY(stage_count(e, samp_R, R, "sonic_set_request_sampling", "values"));
     TRY(stage_count(e, gram_R, R, "option request_grammar_begin", "grammars"));
     e->bias.take = bias_R >= 0; e->samp.take = samp_R >= 0; e->gram.take = gram_R >= 0;      // (read by req_upload alone, which only a prefill that got past this reaches)
+    const int draft_R = e->draft_pending.exchange(-1);      // the drafts (option draft_verify) are no stage - their words become part of the prefill's plan - but are claimed and dropped with them
+    e->draft_take = false;
+    TRY(stage_count(e, draft_R, R, "sonic_load_tensor \"request_draft\"", "drafts"));
+    e->draft_take = draft_R >= 0;
     return SONIC_OK;
 }
 const char* req_claim_none(sonic_engine* e) {
     const int bias_R = e->bias.claim(), samp_R = e->samp.claim(), gram_R = e->gram.claim();      // (claim leaves `take` false: the run's upload writes the neutral values)
     if (gram_R >= 0) gram_drop_staged(e);
+    e->draft_pending = -1; e->draft_take = false;      // (the option is refused on a scoring handle: nothing can be staged)
     return bias_R >= 0 ? "request bias tables (sonic_set_request_bias)" : samp_R >= 0 ? "sampling values (sonic_set_request_sampling)" : gram_R >= 0 ? "grammars (option request_grammar)" : nullptr;
 }
-void req_drop_pending(sonic_engine* e) { e->bias.pending = -1; e->samp.pending = -1; if (e->opt_grammar) gram_drop_staged(e); }
+void req_drop_pending(sonic_engine* e) { e->bias.pending = -1; e->samp.pending = -1; if (e->opt_grammar) gram_drop_staged(e); e->draft_pending = -1; }
 int req_upload(sonic_engine* e, int R) {      // (in this order: the copies and fills go onto the stream in it)
     TRY(bias_upload(e, R));                   // every request's table, or a zero count, into its row
     TRY(gram_upload(e, R));                   // every request's grammar at its start node, or a free row
@@ -491,6 +607,7 @@ int req_splice_check(sonic_engine* d, sonic_engine* p) {
     if (d->opt_request_bias != p->opt_request_bias || (d->opt_request_bias && !(p->bias.dev && d->bias.dev && p->hist && d->hist))) opt = "request_bias";
     else if (d->opt_sampling != p->opt_sampling || (d->opt_sampling && !(p->samp.dev && d->samp.dev))) opt = "sampling";
     else if (d->opt_grammar != p->opt_grammar || (d->opt_grammar && !(p->gram.dev && d->gram.dev))) opt = "grammar";
+    else if (d->opt_draft_verify != p->opt_draft_verify) opt = "draft_verify";
     return opt ? fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in option %s: set it on the owner before its slots are created", opt) : SONIC_OK;
 }
 void req_splice_args(sonic_engine* d, sonic_engine* p, SpliceArgs& a, const int32_t* src_rows, const int32_t* dst_rows, int n) {
@@ -534,6 +651,7 @@ int gen_inherit(sonic_engine* e, const sonic_engine* root) {
     if (root->opt_grammar) TRY(gram_enable(e, 1));
     e->opt_forced_parallel = root->opt_forced_parallel; e->opt_forced_fanout = root->opt_forced_fanout; e->opt_score_chunk_rows = root->opt_score_chunk_rows;      // (the buffers come with the slot's first parallel run)
     e->opt_forced_align = root->opt_forced_align; e->align_heads = root->align_heads;      // (likewise)
+    e->opt_draft_verify = root->opt_draft_verify;      // (the buffers come with the slot's first drafted prefill)
     return SONIC_OK;
 }
 // sonic_destroy (the stream is drained): the references of this handle's staged requests and rows, the grammars the caller left on an owner (its slots are gone:
@@ -544,4 +662,5 @@ void gen_release(sonic_engine* e) {
     for (sonic_grammar* g : e->grammars) { (void)hipFree(g->dev); delete g; }
     e->grammars.clear();
     stage_free(e->bias); stage_free(e->samp); stage_free(e->gram);
+    for (int i = 0; i < 2; ++i) if (e->draft_plan_h[i]) (void)hipHostFree(e->draft_plan_h[i]);
 }

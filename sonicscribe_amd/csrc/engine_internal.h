@@ -235,6 +235,17 @@ struct sonic_engine {
     bool align_live = false, align_last = false;
     int align_S = 0, align_nseq = 0, align_Amax = 0, align_Lmax = 0, align_Htot = 0, align_last_heads = 0;      // of the run under way / the last one
     std::vector<std::vector<int>> align_layer_heads; std::vector<int> align_layer_off;                             // per decoder layer: its selected heads, and where they start in the plan
+    // draft-verified decoding (option draft_verify; sonic_load_tensor "request_draft"; verify.hip): a request of the next prefill may bring a draft of its
+    // transcript - the prefill runs over prompt || draft, the lm_head over every draft position as a GEMM per chunk of rows into score_logits (the parallel forced
+    // run's chunk buffer), verify_rows_kernel per row, draft_accept_kernel per request, then the unchanged head.  draft_stage: the staged words [R | off[R + 1] | ids]
+    // (draft_pending = their R, -1: none; draft_take: the prefill under way consumes them).  The buffers come with the handle's first drafted prefill, are counted by
+    // sonic_memory_info and go with the handle: draft_plan_d, 5 words per verify row (hidden row | draft id | record index | request | history length) and 4 x 64 per
+    // request (draft length | first verify row | prompt length | first packed token), with a pinned mirror beside each of the two plan staging buffers; ver_tok
+    // [tok_cap], ver_rec [tok_cap][lp_width] (ver_rec_w: the width it was allocated at), draft_acc [64] = a_r of the last drafted prefill (draft_last_S: its verify rows; 0: none)
+    int opt_draft_verify = 0;
+    std::vector<int> draft_stage; std::atomic<int> draft_pending{-1}; bool draft_take = false;
+    int* draft_plan_d = nullptr; int* draft_plan_h[2] = {nullptr, nullptr}; int* ver_tok = nullptr; float* ver_rec = nullptr; int ver_rec_w = 0; int* draft_acc = nullptr;
+    int draft_last_S = 0;
     uint64_t spliced = 0;          // rows of the last prefill that sonic_splice_rows handed to a continuous loop (bit r = request r); cleared by every prefill (gen_busy)
     long long* kt = nullptr; int kt_layer = -1;     // diagnostics ("ktrace" option): in-kernel timestamps of one decoder layer's kernels
     int* ring_peak = nullptr;                        // [Bm] per-request max |s| of a ring-staged batch (ingest.hip)
@@ -261,6 +272,8 @@ struct QkvVt { bf16_t* Vt; int n_split, seg_T, vt_ld; long vt_seg_stride; };
 struct HostPlan {
     std::vector<int> src, tok_seq, tok_pos, q_off, q_len, last_row, max_new;
     int n_tok = 0, max_p = 0, max_steps = 0;
+    // option draft_verify: the S verify rows of the batch's drafts (draft_plan_d's layout: 5 x S words, then 4 x 64); S = 0: an ordinary prefill
+    std::vector<int> draft; int S = 0;
 };
 
 #define HIPC(e, call)                                                                                      \
@@ -436,5 +449,15 @@ void req_rows_free(sonic_engine* e);                // a continuous loop begins:
 int* req_release_state(const sonic_engine* e);      // what the release kernels reset in a fetched row beside its counters (NULL: nothing) ...
 void req_row_release(sonic_engine* e, int row);     // ... and what the row held on the host goes with it
 void req_batch_fetched(sonic_engine* e, const int* fin, int R);   // a batch is fetched: once its R rows have all ended they let go of what they held
+// draft-verified decoding (option draft_verify)
+int draft_enable(sonic_engine* e, int on);          // the option behind the lock and the busy check: refused on the int8 and fp32 kinds and on a scoring handle
+int draft_stage_words(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim);   // sonic_load_tensor "request_draft": the drafts of the next prefill's requests
+// a prefill begins (behind req_claim): the claimed drafts checked against the batch (SONIC_ERR_INVALID naming the cause) and, when one of them is not empty, the
+// requests' longer sequences prompt || draft (ids, off), the budgets plan_requests checks them with (left) and the draft lengths (dlen).  dlen stays empty otherwise
+int draft_extend(sonic_engine* e, int R, const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new,
+                 std::vector<int32_t>& ids, std::vector<int64_t>& off, std::vector<int32_t>& left, std::vector<int>& dlen);
+int draft_dispatch_arm(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim);   // sonic_load_tensor "draft.dispatch" (no engine lock): the calling thread's next sonic_dispatch_submit* carries the draft
+int draft_alloc(sonic_engine* e);                   // the buffers, at the handle's first drafted prefill (and ver_rec again when top_logprobs has changed since)
+int score_logits_alloc(sonic_engine* e);            // the chunk's logits [score_chunk_rows][vocab] the parallel forced run and the verify pass share (engine_stages.cpp)
 int gen_inherit(sonic_engine* e, const sonic_engine* root);   // sonic_slot_create: the owner's generation options (token_logprobs .. forced_align) onto the new slot, with their buffers
 void gen_release(sonic_engine* e);                  // sonic_destroy: the stages' pinned mirrors and events, the grammar references this handle holds, an owner's grammars

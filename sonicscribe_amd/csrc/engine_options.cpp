@@ -58,6 +58,7 @@ static int opt_request_bias_fill(sonic_engine* e, const char* key, int value) { 
 // refused while the handle has work in hand, as the options above.  forced_fanout = N: the run's R sequences are R / N audio requests with N candidates each
 static int opt_forced_parallel(sonic_engine* e, const char* key, int value) {
     TRY(gen_busy(e, key));
+    if (value && e->opt_draft_verify) return fail(e, SONIC_ERR_INVALID, "forced_parallel: option draft_verify is on: a scoring handle decodes nothing a draft could shorten");
     if (!value && e->opt_forced_align) return fail(e, SONIC_ERR_INVALID, "forced_parallel cannot be switched off while option forced_align is on (the alignment rides on the parallel forced run)");
     e->opt_forced_parallel = value ? 1 : 0; return SONIC_OK;
 }
@@ -65,6 +66,9 @@ static int opt_forced_fanout(sonic_engine* e, const char* key, int value) {
     if (value < 1 || value > e->Bm) return fail(e, SONIC_ERR_INVALID, "forced_fanout: %d is outside 1 .. %d (max_batch)", value, e->Bm);
     e->opt_forced_fanout = value; return SONIC_OK;      // (only read by a parallel run as it starts)
 }
+// draft-verified decoding (sonic_load_tensor "request_draft"): on the owner before its slots are created (they copy it); refused by name on the int8 and
+// fp32 kinds, on a scoring handle and while the handle has work in hand
+static int opt_draft_verify(sonic_engine* e, const char* key, int value) { TRY(gen_busy(e, key)); return draft_enable(e, value ? 1 : 0); }
 // word timestamps on the parallel forced run (include/sonic_hip.h beside sonic_set_forced_ids).  forced_align: only on a scoring handle, never on the
 // fp32 kind (its prefill keeps no roped queries), refused while the handle has work in hand.  align_head = l * 256 + h adds head h of decoder layer l to the selection
 // (-1: back to the default, every head of the last ceil(dec_layers / 2) layers)
@@ -167,6 +171,7 @@ static const OptRow OPTIONS[] = {
     {"forced_fanout", APPLY(opt_forced_fanout)},
     {"forced_align", APPLY(opt_forced_align)},
     {"align_head", APPLY(opt_align_head)},
+    {"draft_verify", APPLY(opt_draft_verify)},
     {"score_chunk_rows", ENG(opt_score_chunk_rows), false, [](int v) { return v < 16 ? 16 : (v > 4096 ? 4096 : v); }},   // score rows per lm_head GEMM + row-kernel launch (the buffer follows at the next parallel run)
     {"ktrace", APPLY(opt_ktrace)},
     {"inject_dev_err", APPLY(opt_inject_dev_err)},
@@ -222,6 +227,14 @@ extern "C" int sonic_debug_read(sonic_engine* e, const char* name, int index, fl
     if (!strcmp(name, "hook_grammar_state")) {      // the rows' states behind the last hook launch that took a grammar (host words: exact in fp32)
         if (n < 0 || n > 64) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
         for (int64_t i = 0; i < n; ++i) out[i] = (float)e->hook_state_out[i];
+        return SONIC_OK;
+    }
+    if (!strcmp(name, "draft_accepted")) {          // a_r of the handle's last prefill (option draft_verify; exact in fp32); zeros behind a prefill without drafts
+        if (n < 0 || n > 64) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
+        if (!e->opt_draft_verify) return fail(e, SONIC_ERR_INVALID, "draft_accepted: option draft_verify is off on this handle");
+        int acc[64] = {0};
+        if (e->draft_last_S > 0 && e->draft_acc) { HIPC(e, stream_sync(e)); HIPC(e, d2h(e, acc, e->draft_acc, 64 * 4)); }
+        for (int64_t i = 0; i < n; ++i) out[i] = (float)acc[i];
         return SONIC_OK;
     }
     for (const DbgRow& r : DEBUG_BUFS) {

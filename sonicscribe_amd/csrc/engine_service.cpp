@@ -42,10 +42,11 @@ __global__ __launch_bounds__(256) void splice_state_kernel(SpliceArgs a) {
     }
     if (a.samp_d && t < 3) a.samp_d[3 * d + t] = a.samp_s[3 * s + t];
     if (a.gram_d && t == 0) { a.gram_d[d] = a.gram_s[s]; ((int*)(a.gram_d + 64))[d] = ((int*)(a.gram_s + 64))[s]; a.gram_s[s] = 0ull; ((int*)(a.gram_s + 64))[s] = -1; }
-    if (a.lp_d && t < a.lp_w) a.lp_d[(long)d * a.out_ld * a.lp_w + t] = a.lp_s[(long)s * a.out_ld * a.lp_w + t];
+    const int cnt = min(max(a.n_new_s[s], 1), a.out_ld);      // the tokens that came out of the prefill: one - or, behind an accepted draft (option draft_verify), several
+    if (a.lp_d) for (int j = t; j < cnt * a.lp_w; j += 256) a.lp_d[(long)d * a.out_ld * a.lp_w + j] = a.lp_s[(long)s * a.out_ld * a.lp_w + j];
+    for (int j = t; j < cnt; j += 256) a.out_d[(long)d * a.out_ld + j] = a.out_s[(long)s * a.out_ld + j];
     if (t == 0) {
         const int fin = a.fin_s[s];
-        a.out_d[(long)d * a.out_ld] = a.out_s[(long)s * a.out_ld];            // the first token came out of the prefill
         a.kv_len_d[d] = a.kv_len_s[s]; a.tok_pos_d[d] = a.tok_pos_s[s]; a.n_new_d[d] = a.n_new_s[s]; a.max_new_d[d] = a.max_new_s[s];
         a.fin_d[d] = fin;
         if (!fin) atomicAdd(a.n_active_d, 1);
@@ -459,15 +460,18 @@ int fetch_locked(sonic_engine* e, int32_t* out_ids, int out_ld, int32_t* out_len
     HIPC(e, d2h_async(e, kvl.data(), e->kv_len, 64 * 4));
     HIPC(e, d2h_async(e, tps.data(), e->tok_pos, 64 * 4));
     HIPC(e, d2h_async(e, fin.data(), e->finished, 64 * 4));
+    std::vector<int> acc(64, 0);      // option draft_verify: the tokens a drafted request took from its draft (it has run that many greedy launches fewer)
+    if (e->draft_last_S > 0 && e->draft_acc) HIPC(e, d2h_async(e, acc.data(), e->draft_acc, 64 * 4));
     HIPC(e, stream_sync(e));
     if (act_err[1] != 0) return fail(e, SONIC_ERR_HIP, "a decode kernel gave up on an in-kernel wait (device error word %d): the batch's tokens are invalid", act_err[1]);
     // invariants of the greedy controller: a running row's context grows by one per launch; a finished row stopped growing with the
     // launch that finished it (kv_len = prompt + tokens - 1), so no row ever leaves its [max_ctx] cache region
     for (int r = 0; r < R && r < (int)e->last_qlen.size(); ++r) {
         const int want_kv = e->last_qlen[r] + nn[r] - (fin[r] ? 1 : 0);
-        const int want_new = e->greedy_calls < e->last_maxnew[r] ? e->greedy_calls : e->last_maxnew[r];
-        const bool pos_ok = nn[r] >= 1 && kvl[r] == want_kv && kvl[r] <= e->max_ctx && (tps[r] == kvl[r] - 1 || (fin[r] && nn[r] == 1));
-        if (!pos_ok || nn[r] > e->last_maxnew[r] || (!fin[r] && nn[r] != e->greedy_calls) || (e->d.n_eos == 0 && nn[r] != want_new))
+        const int calls = e->greedy_calls + acc[r];
+        const int want_new = calls < e->last_maxnew[r] ? calls : e->last_maxnew[r];
+        const bool pos_ok = nn[r] >= 1 && kvl[r] == want_kv && kvl[r] <= e->max_ctx && (tps[r] == kvl[r] - 1 || (fin[r] && nn[r] == 1 + acc[r]));
+        if (!pos_ok || nn[r] > e->last_maxnew[r] || (!fin[r] && nn[r] != calls) || (e->d.n_eos == 0 && nn[r] != want_new))
             return fail(e, SONIC_ERR_HIP, "decoder state check failed for request %d: kv_len %d (expected %d), tok_pos %d, n_new %d, finished %d (budget %d, greedy launches %d)",
                         r, kvl[r], want_kv, tps[r], nn[r], fin[r], e->last_maxnew[r], e->greedy_calls);
     }

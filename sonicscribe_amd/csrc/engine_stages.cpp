@@ -503,6 +503,11 @@ int upload_plan(sonic_engine* e, int R, const HostPlan& hp) {
     HIPC(e, put(e->q_off, hp.q_off.data(), (size_t)R)); HIPC(e, put(e->q_len, hp.q_len.data(), (size_t)R)); HIPC(e, put(e->kv_len, hp.q_len.data(), (size_t)R));
     HIPC(e, put(e->last_row, hp.last_row.data(), (size_t)R)); HIPC(e, put(e->max_new_d, hp.max_new.data(), (size_t)R));
     HIPC(e, put(e->n_active, &R, 1));
+    if (hp.S > 0) {      // option draft_verify: the verify rows' plan, through the pinned mirror that belongs to this staging buffer
+        int* dh = e->draft_plan_h[e->plan_idx];
+        memcpy(dh, hp.draft.data(), hp.draft.size() * 4);
+        HIPC(e, hipMemcpyAsync(e->draft_plan_d, dh, hp.draft.size() * 4, hipMemcpyHostToDevice, e->st));
+    }
     HIPC(e, hipEventRecord(e->plan_ev[e->plan_idx], e->st));       // every copy out of this buffer (win_req included) is older than this event
     e->plan_busy[e->plan_idx] = true;
     return SONIC_OK;
@@ -515,6 +520,35 @@ int reset_row_state(sonic_engine* e, int R, int n_tok) {
     launch_fill_i32(e->step_ctr, 0, 64, e->st);
     if (hist_on(e)) launch_hist_prompt(e->src, e->tok_seq, e->tok_pos_pf, n_tok, e->d.audio_token_id, e->hist, e->max_ctx, e->st);    // the rows' input_ids for the guards / the request bias
     return req_upload(e, R);                                                                                                        // every request's claimed values, or the neutral ones, into its row
+}
+
+// Draft-verified decoding (option draft_verify), behind the prefill's last layer: draft position n of request r is decided by the hidden row at
+// q_off[r] + P - 1 + n.  The S = sum D_r rows are normalised with the final norm into dhn (free behind the last layer), then, in chunks of score_chunk_rows, multiplied
+// by the tied lm_head as one prefill-family GEMM into score_logits and reduced by verify_rows_kernel under the handle's processors; draft_accept_kernel then leaves
+// every drafted request where a prefill of prompt || draft[0 .. a) would have left it.  The head that follows is the one of every prefill
+static void run_draft_verify(sonic_engine* e, int R, const HostPlan& hp) {
+    const sonic_dims& d = e->d;
+    const int S = hp.S;
+    const int* pd = e->draft_plan_d;
+    launch_rmsnorm(e->dx, e->dec_nw, e->dhn, S, d.dec_d, d.dec_rms_eps, pd, e->st, e->dt);
+    VerifyArgs va{};
+    va.logits = e->score_logits; va.ld = d.vocab; va.V = d.vocab; va.dt = e->dt;
+    if (e->gen_on && e->hist) { va.hist = e->hist; va.hist_ld = e->max_ctx; va.rep_penalty = e->gen_penalty; va.ngram = e->gen_ngram; va.suppress = e->gen_suppress_d; va.n_suppress = (int)e->gen_suppress.size(); }
+    va.ver_tok = e->ver_tok; va.ver_rec = e->ver_rec; va.topk = (e->opt_token_logprobs && e->out_lp) ? e->opt_top_logprobs : 0;
+    va.dump = e->run_logits ? e->dump : nullptr; va.out_ld = e->out_cap; va.R = R;
+    const int chunk = std::min(e->opt_score_chunk_rows, e->score_rows_cap);
+    for (int c0 = 0; c0 < S; c0 += chunk) {
+        const int n = std::min(chunk, S - c0);
+        gemm(e, EPI_BIAS, e->dhn + (size_t)c0 * d.dec_d, d.dec_d, e->embed_t, nullptr, (bf16_t*)e->score_logits, d.vocab, n, d.vocab, d.dec_d, nullptr, 0, 1);   // embed_t: launch_tile_weights' tiling, the one GemmArgs.w_tiled reads
+        va.n = n; va.target = pd + S + c0; va.rec = pd + 2 * S + c0; va.hrow = pd + 3 * S + c0; va.hlen = pd + 4 * S + c0;
+        va.ver_tok = e->ver_tok + c0; va.ver_rec = e->ver_rec + (size_t)c0 * lp_width(e);
+        launch_verify_rows(va, e->st);
+    }
+    DraftAcceptArgs da{};
+    da.req = pd + 5 * S; da.draft = pd + S; da.ver_tok = e->ver_tok; da.ver_rec = e->ver_rec; da.lp_w = lp_width(e);
+    da.out_ids = e->out_ids; da.out_lp = (e->opt_token_logprobs && e->out_lp) ? e->out_lp : nullptr; da.out_ld = e->out_cap;
+    da.n_new = e->n_new; da.kv_len = e->kv_len; da.tok_pos = e->tok_pos; da.step_counter = e->step_ctr; da.last_row = e->last_row; da.accepted = e->draft_acc;
+    launch_draft_accept(da, R, e->st);
 }
 
 // head = false (the parallel forced run): the decoder layers only - its score rows are normalised and multiplied by run_forced_parallel
@@ -561,6 +595,7 @@ static int run_prefill(sonic_engine* e, int R, const HostPlan& hp, bool head = t
         if (e->taps_on) HIPC(e, hipMemcpyAsync(e->taps + (size_t)(l + 1) * e->tok_cap * D, e->dx, (size_t)M * D * 2, hipMemcpyDeviceToDevice, e->st));
     }
     if (!head) return SONIC_OK;
+    if (hp.S > 0) run_draft_verify(e, R, hp);      // option draft_verify: the rows' state becomes that of a prefill of prompt || accepted draft, last_row included
     // logits only for the last prompt position of each request (logits_to_keep=1, generation/utils.py:2612-2616)
     launch_rmsnorm(e->dx, e->dec_nw, e->shn, R, D, d.dec_rms_eps, e->last_row, e->st, dt);
     skinny(e, e->shn, D, e->embed_t, e->lslab, R, d.vocab, D, nullptr);
@@ -580,7 +615,26 @@ int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int
     }
     TRY(req_claim(e, R));      // sonic_set_request_bias / _sampling / option request_grammar: this batch consumes what they left whatever becomes of it (ENTER_CONSUME drops it on every other exit)
     HostPlan hp;
-    TRY(plan_requests(e, req_win, R, prompt_ids, prompt_off, max_new, hp));
+    if (R < 1 || R > e->Bm) return fail(e, SONIC_ERR_INVALID, "request count %d out of range 1..%d", R, e->Bm);
+    std::vector<int32_t> x_ids, x_left; std::vector<int64_t> x_off; std::vector<int> dlen;      // option draft_verify: the longer sequences prompt || draft (empty dlen: no draft in this batch)
+    TRY(draft_extend(e, R, prompt_ids, prompt_off, max_new, x_ids, x_off, x_left, dlen));
+    if (dlen.empty()) TRY(plan_requests(e, req_win, R, prompt_ids, prompt_off, max_new, hp));
+    else {
+        TRY(plan_requests(e, req_win, R, x_ids.data(), x_off.data(), x_left.data(), hp));
+        hp.max_steps = 0;
+        for (int r = 0; r < R; ++r) { hp.max_new[r] = max_new[r]; hp.max_steps = std::max(hp.max_steps, (int)max_new[r]); hp.S += dlen[r]; }
+        TRY(draft_alloc(e));
+        // the verify rows (draft_plan_d's layout): hidden row | draft id | record index | request | history length, S of each; then per request D | first row | P | first token
+        const int S = hp.S;
+        hp.draft.assign((size_t)5 * S + 4 * 64, 0);
+        int* w = hp.draft.data(); int* rq = w + (size_t)5 * S;
+        for (int r = 0, s = 0; r < R; ++r) {
+            const int P = hp.q_len[r] - dlen[r];
+            rq[r] = dlen[r]; rq[64 + r] = s; rq[128 + r] = P; rq[192 + r] = hp.q_off[r];
+            for (int n = 0; n < dlen[r]; ++n, ++s) { w[s] = hp.q_off[r] + P - 1 + n; w[S + s] = x_ids[(size_t)x_off[r] + P + n]; w[2 * S + s] = r * e->out_cap + n; w[3 * S + s] = r; w[4 * S + s] = P + n; }
+        }
+    }
+    e->draft_last_S = hp.S;
     {   // staging buffer of this run: the one used two runs ago; its copies are almost always long done (a blocking wait otherwise)
         const int i = e->plan_idx ^ 1;
         if (e->plan_busy[i]) { HIPC(e, hipEventSynchronize(e->plan_ev[i])); e->plan_busy[i] = false; }
@@ -589,8 +643,13 @@ int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int
     if (e->force_d && (e->force_R != R || e->force_ld < hp.max_steps))
         return fail(e, SONIC_ERR_INVALID, "forced ids are [%d][%d] but the run has %d requests / %d steps", e->force_R, e->force_ld, R, hp.max_steps);
     e->R = R; e->max_steps = hp.max_steps; e->last_qlen = hp.q_len; e->last_maxnew = hp.max_new; e->align_last = false;
+    for (size_t r = 0; r < dlen.size(); ++r) e->last_qlen[r] -= dlen[r];      // the PROMPT's length: fetch_locked expects kv_len = prompt + tokens - 1
     if (want_logits) {
-        const size_t need_n = (size_t)hp.max_steps * R * d.vocab;
+        // a drafted row's step counter starts at its accepted count and goes on counting with every launch, also once the row has ended: the dump holds the steps
+        // the longest draft can add (the fetch reads the first max_steps of them, as always)
+        int d_max = 0;
+        for (int D : dlen) d_max = std::max(d_max, D);
+        const size_t need_n = (size_t)(hp.max_steps + d_max) * R * d.vocab;
         if (need_n > e->dump_cap) {
             if (e->dump) (void)hipFree(e->dump);
             e->dump = nullptr; e->dump_cap = 0;
@@ -743,7 +802,7 @@ static void fill_timings(sonic_engine* e, double host_enqueue_first, int steps_d
 
 // the parallel forced run's buffers, at the first such run of the handle or when score_chunk_rows has grown since: the chunk's logits
 // [score_chunk_rows][vocab] in the activation type (fp32 kind: fp32) and the score rows' plan (3 words per row, at most tok_cap rows) on the device and pinned
-static int score_alloc(sonic_engine* e) {
+int score_logits_alloc(sonic_engine* e) {
     const int rows = e->opt_score_chunk_rows;
     const size_t esz = e->f32 ? 4 : 2;
     if (e->score_logits && e->score_rows_cap < rows) {
@@ -756,6 +815,10 @@ static int score_alloc(sonic_engine* e) {
         TRY(dalloc(e, &p, (size_t)rows * e->d.vocab * esz, false));
         e->score_logits = p; e->score_rows_cap = rows;
     }
+    return SONIC_OK;
+}
+static int score_alloc(sonic_engine* e) {
+    TRY(score_logits_alloc(e));
     if (!e->score_plan_d) TRY(dalloc(e, &e->score_plan_d, (size_t)3 * e->tok_cap));
     if (!e->score_plan_h && hipHostMalloc((void**)&e->score_plan_h, ((size_t)3 * e->tok_cap + 4 * 64) * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(e, SONIC_ERR_OOM, "forced_parallel: pinned host memory exhausted"); }
     return SONIC_OK;

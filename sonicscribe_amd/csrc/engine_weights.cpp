@@ -79,6 +79,8 @@ extern "C" int sonic_load_tensor(sonic_engine* e, const char* name, const void* 
         if (name[7] == ':') return gram_create(e, atoi(name + 8), (const int*)data, shape[0]);
         return gram_hook_arm(e, atoi(name + 13), (const int*)data, shape[0]);
     }
+    if (!strcmp(name, "draft.dispatch")) return draft_dispatch_arm(e, data, dtype, shape, ndim);      // ... and the one of the calling thread's next dispatcher submit (no engine lock, as grammar.dispatch)
+    if (!strcmp(name, "request_draft")) return draft_stage_words(e, data, dtype, shape, ndim);      // the drafts of the next prefill's requests (option draft_verify)
     ENTER(e);
     if (e->finalized) return fail(e, SONIC_ERR_INVALID, "weights already finalized");
     std::vector<int64_t> shp(shape, shape + ndim);

@@ -6,6 +6,7 @@
 #include "common.h"
 #include "kernels.h"
 
+#include "guard.h"
 #include "int8_util.h"
 #include "topk.h"
 
@@ -55,15 +56,9 @@
 // scores.  Thread 0 looks the emitted id - argmax, sample or forced id - up among the node's edges by binary search: found, the state is that edge's `next`; not
 // found (a forced id outside the grammar, token 0 of a row whose allowed ids were all banned, any id at -2), it is -2.  A finished row changes nothing; no LDS is
 // added.  GRAMMAR = false is the kernel as it was.
-// tk_insert / tk_merge (the lists and their wave merge) and lp_exp live in topk.h: score.hip shares them
+// tk_insert / tk_merge (the lists and their wave merge) and lp_exp live in topk.h: score.hip shares them; guard_score / guard_set (a score under the
+// history's maps, a bit into one) in guard.h: verify.hip shares them
 extern __shared__ unsigned g_bits[];
-__device__ __forceinline__ float guard_score(float r, unsigned seen, unsigned banned, float p) {
-    if (seen & 1u) r = r < 0.f ? r * p : __fdiv_rn(r, p);
-    return (banned & 1u) ? -INFINITY : r;
-}
-__device__ __forceinline__ void guard_set(unsigned* map, int id, int V) {
-    if ((unsigned)id < (unsigned)V) atomicOr(&map[id >> 5], 1u << (id & 31));
-}
 __device__ __forceinline__ float bias_of(const int* ids, const float* sums, int n, int id) {
     float b = 0.f;
     for (int k = 0; k < n; ++k) if (ids[k] == id) b = sums[k];      // (ids are unique: one group per last id)

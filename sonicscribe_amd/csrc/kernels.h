@@ -165,6 +165,31 @@ void launch_score_rows(const ScoreArgs& a, hipStream_t s);
 // test hook route: the lm_head's fp32 slabs [ksplit][mpad][V] summed in greedy_kernel's order (v + w, then ks = 2 ...) and rounded to the element type: out [B][V]
 void launch_score_slab_rows(const float* slabs, int ksplit, int mpad, int V, int B, void* out, int dt, hipStream_t s);
 
+// Draft-verified decoding (verify.hip; option draft_verify).  verify_rows_kernel<T, GUARD, TOPK>: block i takes row i of `logits` - the lm_head's
+// output for the hidden row that decides one draft position, in the activation type (bf16 / fp16) - and writes ver_tok[i], the first maximum of the row's processed
+// scores (the lower id among equal values; 0 when all are -inf), and ver_rec[i * (1 + 2K) ..], the record of the draft id target[i] in GreedyArgs.out_lp's layout.
+// hist != NULL (GUARD): the scores are guard_score of the logits under the maps of hist[hrow[i] * hist_ld .. + hlen[i]) - the request's prompt and the draft ids in
+// front of the position.  rec[i] = r * out_ld + n names request and position for the dump alone: dump[(n * R + r) * V ..] = the raw row as fp32 (optional)
+struct VerifyArgs {
+    const void* logits; long ld;     // [n][ld] elements of the type `dt` names
+    int V, n, dt;                    // DT_BF16 / DT_F16
+    const int *target, *rec, *hrow, *hlen;
+    const int* hist; int hist_ld;
+    float rep_penalty; int ngram; const int* suppress; int n_suppress;
+    int* ver_tok; float* ver_rec; int topk;
+    float* dump; int out_ld, R;
+};
+void launch_verify_rows(const VerifyArgs& a, hipStream_t s);
+// draft_accept_kernel: block r takes request r = req[r] (draft length D; 0: the block changes nothing but accepted[r] = 0), req[64 + r] (its first verify row),
+// req[128 + r] (prompt length P), req[192 + r] (first packed token).  a = the least n with ver_tok[row0 + n] != draft[row0 + n], else D; out_ids[r][0 .. a) and the
+// records (lp_w floats each; out_lp may be NULL) are copied, n_new = step_counter = a, kv_len = P + a, last_row = first token + P - 1 + a, accepted[r] = a
+struct DraftAcceptArgs {
+    const int *req, *draft, *ver_tok; const float* ver_rec; int lp_w;
+    int* out_ids; float* out_lp; int out_ld;
+    int *n_new, *kv_len, *tok_pos, *step_counter, *last_row, *accepted;
+};
+void launch_draft_accept(const DraftAcceptArgs& a, int R, hipStream_t s);
+
 struct LogmelConst {
     const float* win;      // [400]
     const float* cos_t;    // [400]

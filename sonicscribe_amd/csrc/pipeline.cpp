@@ -30,6 +30,7 @@
 extern "C" int engine_token_logprobs_on(sonic_engine* e);   // engine.cpp
 extern "C" int engine_top_logprobs(sonic_engine* e);        // engine.cpp: option top_logprobs of this handle
 extern "C" int engine_forced_parallel_on(sonic_engine* e);  // engine.cpp: option forced_parallel of this handle (a scoring handle: refused here)
+extern "C" int engine_draft_verify_on(sonic_engine* e);     // engine_generation.cpp: option draft_verify of this handle (the bulk pipeline takes no drafts: refused here)
 extern "C" int engine_fail(sonic_engine* e, int code, const char* msg);   // engine.cpp: the message on a handle (sonic_last_error)
 
 namespace {
@@ -237,6 +238,9 @@ SONIC_API int sonic_pipeline_create(sonic_engine* const* decoders, int n_dec, so
     for (int i = 0; i < n_dec + n_pre; ++i)
         if (engine_forced_parallel_on(i < n_dec ? decoders[i] : prefills[i - n_dec]))
             return engine_fail(decoders[0], SONIC_ERR_INVALID, "sonic_pipeline_create: option forced_parallel is on on a handle: a scoring handle takes no part in the bulk pipeline");
+    for (int i = 0; i < n_dec + n_pre; ++i)
+        if (engine_draft_verify_on(i < n_dec ? decoders[i] : prefills[i - n_dec]))
+            return engine_fail(decoders[0], SONIC_ERR_INVALID, "sonic_pipeline_create: option draft_verify is on on a handle: the bulk pipeline takes no drafts (stage them on a handle's whole batches or its prefill slot)");
     sonic_pipeline* p = new sonic_pipeline();
     p->dec.assign(decoders, decoders + n_dec); p->pre.assign(prefills, prefills + n_pre);
     p->block = block; p->blocks_per_dec = rows_per_decoder / block;

@@ -46,9 +46,10 @@ def step_class(max_new: int) -> int:
 
 
 class Request:
-    __slots__ = ("windows", "prompt", "max_new", "future", "t_submit", "cls", "want_logprobs", "bias", "sampling", "grammar")
+    __slots__ = ("windows", "prompt", "max_new", "future", "t_submit", "cls", "want_logprobs", "bias", "sampling", "grammar", "draft")
 
-    def __init__(self, windows: Sequence[Any], prompt: Sequence[int], max_new: int, want_logprobs: bool = False, bias=None, sampling=None, grammar=None):
+    def __init__(self, windows: Sequence[Any], prompt: Sequence[int], max_new: int, want_logprobs: bool = False, bias=None, sampling=None, grammar=None, draft=None):
+        self.draft = [int(t) for t in draft] if draft is not None and len(draft) else None      # a draft of its transcript (engine option draft_verify): the prefill verifies it; None: none
         self.grammar = grammar                        # its grammar (grammar.CompiledGrammar: a device handle per replica; engine option grammar); None: a free request
         self.sampling = None if sampling is None else (float(sampling[0]), int(sampling[1]))      # its own (temperature, seed) (engine option sampling); None: greedy
         self.windows, self.prompt, self.max_new = list(windows), prompt, int(max_new)
@@ -62,6 +63,32 @@ class Request:
 def _device_grammar(req: "Request", engine):
     """the request's grammar as the handle that lives on `engine`'s weight owner (None: a free request)"""
     return None if req.grammar is None else req.grammar.on(engine)
+
+
+DRAFT_OFF = "a draft needs the engine option draft_verify on every handle (ASRModel(draft_verify=True))"
+
+
+def check_draft(req: "Request", engines) -> None:
+    """ValueError by name unless every handle verifies drafts, and for a draft beside a bias table, a temperature > 0 or a grammar (the library refuses those too)"""
+    if not req.draft:
+        return
+    if not all(getattr(e, "draft_verify", False) for e in engines):
+        raise ValueError(DRAFT_OFF)
+    if req.bias or req.grammar or (req.sampling and req.sampling[0] > 0):
+        raise ValueError("a draft cannot be combined with a bias table, a temperature > 0 or a grammar (the verify pass applies the engine's own processors only)")
+
+
+def request_tokens(req: "Request") -> int:
+    """the tokens the request adds to a prefill: its prompt and its draft"""
+    return len(req.prompt) + (len(req.draft) if req.draft else 0)
+
+
+def fits_tokens(engine, used: int, req: "Request") -> bool:
+    """Handles with option draft_verify count a batch's prompt and draft tokens against tok_cap (what one prefill holds); a request that alone exceeds it goes through
+    and is refused by the engine, by name.  Other handles batch as they always did."""
+    if not getattr(engine, "draft_verify", False) or used == 0:
+        return True
+    return used + request_tokens(req) <= int(engine.tok_cap)
 
 
 GRAMMAR_OFF = "a grammar needs the engine option grammar on every handle (ASRModel(token_logprobs=True, grammar=True))"
@@ -89,6 +116,7 @@ class _Replica:
             return self.busy_windows + sum(len(r.windows) for r in self.q)
 
     def put(self, req: Request):
+        check_draft(req, self.engines)
         with self.cv:
             if self.stop:
                 raise RuntimeError("ASR engine is closed")
@@ -110,11 +138,11 @@ class _Replica:
                 if head.future.set_running_or_notify_cancel():
                     head.future.set_exception(ValueError(f"audio spans {len(head.windows)} windows, engine max_batch is {cap}"))
                 return []
-            batch, used, rest = [], 0, []
+            batch, used, rest, toks = [], 0, [], 0
             for r in self.q:                     # oldest first; same step class as the head; whatever fits
-                if r.cls == head.cls and used + len(r.windows) <= cap:
+                if r.cls == head.cls and used + len(r.windows) <= cap and fits_tokens(self.engine, toks, r):
                     if r.future.set_running_or_notify_cancel():      # RUNNING: cancel() now returns False, set_result cannot raise
-                        batch.append(r); used += len(r.windows)
+                        batch.append(r); used += len(r.windows); toks += request_tokens(r)
                 else:
                     rest.append(r)
             self.q = rest
@@ -149,6 +177,9 @@ class _Replica:
         gram_on = bool(getattr(engine, "grammar", False))
         if gram_on or any(r.grammar for r in batch):      # (likewise: every batch states its grammars, None = a free request)
             kw["request_grammar"] = [_device_grammar(r, engine) for r in batch]
+        draft_on = bool(getattr(engine, "draft_verify", False))
+        if draft_on or any(r.draft for r in batch):        # (likewise: None = no draft)
+            kw["request_draft"] = [r.draft for r in batch]
         try:
             if want:
                 ids, _, lps = engine.transcribe_batch(segs, [r.prompt for r in batch], [r.max_new for r in batch], req_win=req_win, want_logprobs=True, **kw)
@@ -165,6 +196,8 @@ class _Replica:
                     kw1["request_sampling"] = [r.sampling]
                 if gram_on or r.grammar:
                     kw1["request_grammar"] = [_device_grammar(r, engine)]
+                if draft_on or r.draft:
+                    kw1["request_draft"] = [r.draft]
                 try:
                     if r.want_logprobs:
                         one, _, lp1 = engine.transcribe_batch(r.windows, [r.prompt], [r.max_new], req_win=[0, len(r.windows)], want_logprobs=True, **kw1)
@@ -277,6 +310,7 @@ class _ContinuousReplica:
             raise ValueError(GRAMMAR_OFF)
         if req.grammar:
             req.grammar.on(self.engine)                   # (ValueError here for a grammar of another model, not in the prefill thread)
+        check_draft(req, self.engines)
         with self.cv:
             if self.stop:
                 raise RuntimeError("ASR engine is closed")
@@ -296,14 +330,14 @@ class _ContinuousReplica:
                 return [], 0
             self.q = [r for r in self.q if not r.future.cancelled()]
             k = max(range(len(self.free)), key=self.free.__getitem__)        # the emptiest decoder takes the whole prefill batch
-            batch, used, rest = [], 0, []
+            batch, used, rest, toks = [], 0, [], 0
             for r in self.q:                             # oldest first, whatever fits the slot's windows and the free rows; classes mix
                 if len(r.windows) > cap:
                     if r.future.set_running_or_notify_cancel():
                         r.future.set_exception(ValueError(f"audio spans {len(r.windows)} windows, engine max_batch is {cap}"))
-                elif len(batch) < self.free[k] and used + len(r.windows) <= cap and not rest:
+                elif len(batch) < self.free[k] and used + len(r.windows) <= cap and not rest and fits_tokens(self.engine, toks, r):
                     if r.future.set_running_or_notify_cancel():
-                        batch.append(r); used += len(r.windows)
+                        batch.append(r); used += len(r.windows); toks += request_tokens(r)
                 else:
                     rest.append(r)
             self.q = rest
@@ -328,6 +362,8 @@ class _ContinuousReplica:
             eng.set_request_sampling([r.sampling for r in batch])
         if getattr(eng, "grammar", False) or any(r.grammar for r in batch):        # (likewise: None = a free request)
             eng.set_request_grammar([_device_grammar(r, eng) for r in batch])
+        if getattr(eng, "draft_verify", False) or any(r.draft for r in batch):     # (likewise: None = no draft)
+            eng.set_request_draft([r.draft for r in batch])
         # waited for: a splice queued behind a prefill that is still running would hold the decoder's whole stream (every running row) at the
         # event until the prefill is done - final p50 at 128 sessions 438 -> 657 ms when the hand-over came early.  (The bulk pipeline hands over
         # early, sonicscribe_amd/pipeline.py: its next batch is long done when a block frees up.)
@@ -488,6 +524,7 @@ class _NativeContinuousReplica:
         self.bias = all(getattr(e, "request_bias", False) for e in self.engines)      # then a request may bring its own sequence-bias table
         self.samp = all(getattr(e, "sampling", False) for e in self.engines)          # then a request may bring its own (temperature, seed)
         self.gram = all(getattr(e, "grammar", False) for e in self.engines)           # then a request may bring its grammar
+        self.draft = all(getattr(e, "draft_verify", False) for e in self.engines)     # then a request may bring a draft
         self.thread = threading.Thread(target=self._complete_loop, name=f"sonic-dispatch-{index}.complete", daemon=True)
         self.thread.start()
 
@@ -525,6 +562,7 @@ class _NativeContinuousReplica:
             raise ValueError("a temperature needs the engine option sampling on every handle (ASRModel(sampling=True))")
         if req.grammar and not self.gram:
             raise ValueError(GRAMMAR_OFF)
+        check_draft(req, self.engines)
         if req.bias:
             req.bias.check_vocab(self.engine.dims.vocab)
         dev_gram = _device_grammar(req, self.engine)
@@ -553,6 +591,10 @@ class _NativeContinuousReplica:
             temp, seed = _sampling.check_temperature(req.sampling[0]), _sampling.check_seed(req.sampling[1])
         if dev_gram is not None and dev_gram.h is None:
             raise ValueError("grammar: the grammar has been closed")
+        draft_words = None
+        if req.draft:
+            from .engine import pack_dispatch_draft
+            draft_words = pack_dispatch_draft(req.draft)     # sonic_load_tensor "draft.dispatch": n | ids
         with self.lock:
             if self.stop:
                 raise RuntimeError("ASR engine is closed")
@@ -562,6 +604,9 @@ class _NativeContinuousReplica:
                 one = np.zeros(1, np.int32)
                 if self.lib.sonic_load_tensor(self.engine.h, f"grammar.dispatch:{int(dev_gram.id)}".encode(), _p(one), 2, (C.c_int64 * 1)(0), 1) != 0:
                     raise ValueError("grammar: " + (self.lib.sonic_last_error(None) or b"").decode())
+            if draft_words is not None:                  # ... and the draft, the same way ("draft.dispatch": a thread-local, no engine lock)
+                if self.lib.sonic_load_tensor(self.engine.h, b"draft.dispatch", _p(draft_words), 2, (C.c_int64 * 1)(len(draft_words)), 1) != 0:
+                    raise ValueError("draft: " + (self.lib.sonic_last_error(None) or b"").decode())
             if req.sampling:
                 rc = self.lib.sonic_dispatch_submit_sampled(self.h, _p(pcm), _p(offs), ring_arr, _p(start) if any_ring else None, _p(n) if any_ring else None, W,
                                                             _p(prompt), len(prompt), int(req.max_new), temp, seed,
@@ -572,9 +617,9 @@ class _NativeContinuousReplica:
             else:
                 rc = self.lib.sonic_dispatch_submit(self.h, _p(pcm), _p(offs), ring_arr, _p(start) if any_ring else None, _p(n) if any_ring else None, W,
                                                     _p(prompt), len(prompt), int(req.max_new), C.byref(t))
-            if rc != 0 and (req.bias or req.sampling or req.grammar):
+            if rc != 0 and (req.bias or req.sampling or req.grammar or req.draft):
                 msg = (self.lib.sonic_last_error(None) or b"").decode()
-                if "request_bias" in msg or "sonic_dispatch_submit_bias" in msg or "sampling" in msg or "sonic_dispatch_submit_sampled" in msg or "grammar" in msg:
+                if "request_bias" in msg or "sonic_dispatch_submit_bias" in msg or "sampling" in msg or "sonic_dispatch_submit_sampled" in msg or "grammar" in msg or "draft" in msg:
                     raise ValueError(msg)
             if rc != 0:
                 raise RuntimeError("ASR engine failed" if rc not in (1,) else "ASR engine is closed or the request is malformed")
@@ -685,6 +730,8 @@ class _BulkReplica:
             raise TypeError("bulk mode takes host PCM windows or slices of device rings")
         if req.bias:                                      # refused, not dropped: the bulk pipeline (csrc/pipeline.cpp) carries no per-request tables
             raise ValueError("a sequence bias is not supported with bulk=True (the bulk pipeline carries no per-request tables): use the continuous or the batch dispatcher")
+        if req.draft:                                     # likewise (and sonic_pipeline_create refuses handles with option draft_verify)
+            raise ValueError("a draft is not supported with bulk=True (the bulk pipeline verifies no drafts): use the continuous or the batch dispatcher")
         if req.grammar:                                   # likewise: no per-request state travels through the bulk pipeline
             raise ValueError("a grammar is not supported with bulk=True (the bulk pipeline carries no per-request grammar state): use the continuous or the batch dispatcher")
         if req.sampling:                                  # likewise: no per-request values travel through the bulk pipeline
@@ -847,12 +894,15 @@ class Dispatcher:
             return self.replicas[least]                                     # rebalance: the home replica is more than a batch behind
         return self.replicas[home]
 
-    def submit(self, windows, prompt, max_new: int, session: Optional[str] = None, replica: Optional[int] = None, want_logprobs: bool = False, bias=None, sampling=None, grammar=None) -> Future:
+    def submit(self, windows, prompt, max_new: int, session: Optional[str] = None, replica: Optional[int] = None, want_logprobs: bool = False, bias=None, sampling=None, grammar=None,
+               draft=None) -> Future:
         """`replica` pins the request (windows that are slices of a device ring can only be decoded where the ring lives).  want_logprobs: the
         future resolves to (ids, log-probabilities) - the engines need option token_logprobs.  bias: the request's own sequence-bias table
         (reqbias.RequestBias) - the engines need option request_bias; refused with bulk=True.  sampling: the request's own (temperature, seed) - the engines
-        need option sampling; refused with bulk=True.  grammar: the request's grammar.CompiledGrammar - the engines need option grammar; refused with bulk=True."""
-        req = Request(windows, prompt, max_new, want_logprobs, bias, sampling, grammar)
+        need option sampling; refused with bulk=True.  grammar: the request's grammar.CompiledGrammar - the engines need option grammar; refused with bulk=True.
+        draft: token ids the request's transcript is expected to begin with - the engines need option draft_verify; the prefill accepts the prefix the model itself
+        would have emitted and decoding starts behind it; refused with bulk=True and beside a bias table, a temperature > 0 or a grammar."""
+        req = Request(windows, prompt, max_new, want_logprobs, bias, sampling, grammar, draft)
         (self.replicas[replica] if replica is not None else self.pick(session)).put(req)
         return req.future
 

@@ -388,6 +388,7 @@ class Engine(HooksMixin):
         s.grammar = bool(getattr(root, "grammar", False))
         s.forced_parallel = bool(getattr(root, "forced_parallel", False))
         s.forced_align = bool(getattr(root, "forced_align", False))
+        s.draft_verify = bool(getattr(root, "draft_verify", False))
         root._slots.append(s)
         return s
 
@@ -560,14 +561,16 @@ class Engine(HooksMixin):
 
     def transcribe_batch(self, segments: Sequence[Any], prompts: Sequence[Sequence[int]], max_new: Sequence[int],
                          req_win: Optional[Sequence[int]] = None, want_logits: bool = False, want_logprobs: bool = False, request_bias=None, request_sampling=None,
-                         request_grammar=None):
+                         request_grammar=None, request_draft=None):
         """segments: int16 PCM windows (<= 30 s each, already peak-normalised) or RingSlice objects (raw wire PCM resident in a device
         ring; normalised on the device over the windows of their request); one prompt per request. Returns (ids list, logits or None);
         with want_logprobs (option token_logprobs on this handle) one more element: the float32 log-probability of every returned token, per request.
         request_bias: one reqbias.RequestBias or None per request (option request_bias on this handle; set_request_bias).
         request_sampling: one (temperature, seed) or None (greedy) per request (option sampling on this handle; set_request_sampling).
-        request_grammar: one DeviceGrammar or None (free) per request (option grammar on this handle; set_request_grammar)."""
+        request_grammar: one DeviceGrammar or None (free) per request (option grammar on this handle; set_request_grammar).
+        request_draft: one id sequence or None (no draft) per request (option draft_verify on this handle; set_request_draft)."""
         samp = None if request_sampling is None else pack_request_sampling(request_sampling)      # (validated before anything is armed)
+        draft = None if request_draft is None else pack_request_draft(request_draft)
         if any(isinstance(s, RingSlice) for s in segments):
             pcm, offs, rings, start, n = self._pack_mixed(segments)
             ids, poffs = self._pack_prompts(prompts)
@@ -584,6 +587,8 @@ class Engine(HooksMixin):
                 self._arm_sampling(samp)
             if request_grammar is not None:
                 self.set_request_grammar(request_grammar)
+            if draft is not None:
+                self._arm_draft(draft)
             self._check(self.lib.sonic_transcribe_mixed(self.h, _p(pcm), _p(offs), rings, _p(start), _p(n), len(segments), _p(rw), R, _p(ids), _p(poffs),
                                                         _p(mn), _p(out), out_ld, _p(out_len), _p(logits)))
             res = [out[r, : out_len[r]].copy() for r in range(R)]
@@ -603,6 +608,8 @@ class Engine(HooksMixin):
             self._arm_sampling(samp)
         if request_grammar is not None:
             self.set_request_grammar(request_grammar)
+        if draft is not None:
+            self._arm_draft(draft)
         self._check(self.lib.sonic_transcribe_batch(self.h, _p(pcm), _p(offs), len(segments), _p(rw), R, _p(ids), _p(poffs), _p(mn),
                                                     _p(out), out_ld, _p(out_len), _p(logits)))
         res = [out[r, : out_len[r]].copy() for r in range(R)]
@@ -667,19 +674,22 @@ class Engine(HooksMixin):
         self._check(self.lib.sonic_run_staged(self.h, _p(rw), len(prompts), _p(ids), _p(poffs), _p(mn), int(want_logits)))
 
     def prefill(self, prompts: Sequence[Sequence[int]], max_new: Sequence[int], req_win: Optional[Sequence[int]] = None, want_logits: bool = False, wait: bool = True,
-                request_bias=None, request_sampling=None, request_grammar=None):
+                request_bias=None, request_sampling=None, request_grammar=None, request_draft=None):
         """Stage entry point: everything up to and including the first greedy token of the staged batch (sonic_prefill).  wait=False: the
         work is only queued when the call returns (sonic_prefill_enqueue; a following splice_rows orders itself behind it on the device)."""
         ids, poffs = self._pack_prompts(prompts)
         mn = np.ascontiguousarray(max_new, dtype=np.int32)
         rw = _arr(req_win, np.int32)
         samp = None if request_sampling is None else pack_request_sampling(request_sampling)
+        draft = None if request_draft is None else pack_request_draft(request_draft)
         if request_bias is not None:                     # one reqbias.RequestBias or None per request: this prefill consumes them, on success or failure
             self.set_request_bias(request_bias)
         if samp is not None:                             # one (temperature, seed) or None per request: likewise
             self._arm_sampling(samp)
         if request_grammar is not None:                  # one DeviceGrammar or None per request: likewise
             self.set_request_grammar(request_grammar)
+        if draft is not None:                            # one id sequence or None per request: likewise
+            self._arm_draft(draft)
         if not wait:
             self._check(self.lib.sonic_prefill_enqueue(self.h, _p(rw), len(prompts), _p(ids), _p(poffs), _p(mn)))
             return
@@ -797,6 +807,8 @@ class Engine(HooksMixin):
             self.forced_parallel = bool(value)       # (likewise; it may also be set on a slot alone)
         if key == "forced_align":
             self.forced_align = bool(value)          # (likewise: a parallel run's records then carry t_n)
+        if key == "draft_verify":
+            self.draft_verify = bool(value)          # (likewise: a request of this handle may bring a draft)
 
     def set_forced_ids(self, ids):
         """ids: [R][ld] int array (token n of request r) or None to clear; see sonic_set_forced_ids."""
@@ -828,6 +840,22 @@ class Engine(HooksMixin):
         seq_ids, seq_off, bias, req_off = pack_request_bias(tables)
         self._check(self.lib.sonic_set_request_bias(self.h, _p(seq_ids) if seq_ids.size else None, _p(seq_off), _p(bias) if bias.size else None, _p(req_off), len(tables)))
 
+    def _arm_draft(self, words):
+        self._check(self.lib.sonic_load_tensor(self.h, b"request_draft", _p(words), DTYPE_I32, (C.c_int64 * 1)(len(words)), 1))
+
+    def set_request_draft(self, drafts):
+        """The drafts of the requests of the NEXT prefill / run on this handle (sonic_load_tensor "request_draft"), one id sequence or None (no draft)
+        per request; that call consumes them.  The engine accepts the longest prefix of a draft that the model itself would have emitted, takes the model's own token
+        at the first disagreement and decodes on from there.  Needs option draft_verify (SonicError naming it otherwise); the library refuses - it never cuts - a
+        draft that holds an EOS id or the audio placeholder, or more than max_new - 1 ids."""
+        self._arm_draft(pack_request_draft(list(drafts)))
+
+    def draft_accepted(self, R: int) -> np.ndarray:
+        """a_r of this handle's last prefill (sonic_debug_read "draft_accepted"): how many ids of its draft each of the R requests took; tests and diagnostics"""
+        out = np.zeros(max(1, int(R)), np.float32)
+        self._check(self.lib.sonic_debug_read(self.h, b"draft_accepted", 0, _p(out), int(R)))
+        return out[:R].astype(np.int32)
+
     def _arm_sampling(self, packed):
         t, s = packed
         self._check(self.lib.sonic_set_request_sampling(self.h, _p(t), _p(s), len(t)))
@@ -852,6 +880,27 @@ def pack_request_bias(tables):
     seq_off[1:] = np.cumsum(ln)
     bias = np.ascontiguousarray(np.concatenate(vals) if vals else np.zeros(0), dtype=np.float32)
     return seq_ids, seq_off, bias, np.asarray(req_off, dtype=np.int32)
+
+
+def pack_request_draft(drafts):
+    """one draft per request (a sequence of token ids, or None / empty for a request without one) -> the int32 words sonic_load_tensor "request_draft" takes:
+    R | off[0 .. R] | ids"""
+    ds = [np.zeros(0, np.int64) if d is None else np.asarray(list(d), dtype=np.int64).reshape(-1) for d in drafts]
+    if not ds:
+        raise ValueError("request_draft: no request")
+    off = np.concatenate([[0], np.cumsum([len(d) for d in ds])])
+    ids = np.concatenate(ds) if ds else np.zeros(0, np.int64)
+    if ids.size and (ids.min() < -2 ** 31 or ids.max() >= 2 ** 31):      # (what the ids may be is the library's to say: vocabulary, EOS ids, the audio placeholder)
+        raise ValueError("request_draft: token ids must be int32 values")
+    return np.ascontiguousarray(np.concatenate([[len(ds)], off, ids]), dtype=np.int32)
+
+
+def pack_dispatch_draft(draft):
+    """one request's draft -> the int32 words sonic_load_tensor "draft.dispatch" takes: n | ids"""
+    ids = np.asarray(list(draft), dtype=np.int64).reshape(-1)
+    if ids.size and (ids.min() < -2 ** 31 or ids.max() >= 2 ** 31):
+        raise ValueError("draft: token ids must be int32 values")
+    return np.ascontiguousarray(np.concatenate([[ids.size], ids]), dtype=np.int32)
 
 
 def pack_request_sampling(values):

@@ -10,6 +10,10 @@ Per session the reference runs, every >= 64 ms: `process_vad()` (vad_processor_m
 and every decode it triggers is a chunk / sample range of the session's ring in HBM handed to the coalescing dispatcher
 (asr.AudioStream.submit_chunks) - the requests of one tick end up in one device batch per step class.
 
+`cumulative_partials=True` (opt-in; a model built with token_logprobs=True and draft_verify=True): a partial covers the whole segment so far instead
+of its newest 1.28 s, with the segment's previous partial as its draft - the engine verifies that draft in the partial's prefill and decodes only what is new - and
+the final that follows takes the last partial's transcript as its draft.  Its futures resolve to asr.Transcription.  Off, every request is the one described above.
+
 The VAD network is a caller-supplied function: `vad(rows, windows_pcm, thresholds) -> bool[len(rows)]` gets, for every session with
 a complete 640 ms window, that window's int16 samples and the session's current dynamic threshold (Silero stays outside, as in the
 reference: its weights are not available offline).  With `device_vad=True` no window bytes are kept or built on the host: the callable
@@ -30,6 +34,7 @@ PARTIAL_CHUNKS = 20                  # config.py:40 TEMPORARY_TRANSCRIPTION_INTE
 PARTIAL_TOKENS = 15                  # transcription_manager.py:24
 PARTIAL_PERIOD_S = 1.0               # connection_manager.py:89-92
 MAX_SEGMENT_S = 30.0                 # config.py:41 MAX_SEGMENT_DURATION
+DRAFT_HOLDBACK = 2                   # cumulative partials: the last tokens of a partial are the ones the next second of audio most often revises - they stay out of the draft
 
 
 def committed_max_new_tokens(seconds: float) -> int:
@@ -39,8 +44,16 @@ def committed_max_new_tokens(seconds: float) -> int:
 class GatedSessions:
     def __init__(self, model, session_ids: Sequence[str], buffer_seconds: float = 30.0, hotwords: Optional[List[str]] = None,
                  cfg: GateConfig = GateConfig(), device_vad: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
-                 temperature: Optional[float] = None, seed: Optional[int] = None):
+                 temperature: Optional[float] = None, seed: Optional[int] = None, cumulative_partials: bool = False):
         self.model, self.ids, self.hotwords, self.cfg = model, list(session_ids), hotwords, cfg
+        # cumulative partials (module docstring): the current segment's partial futures per session, oldest first; a draft is read from the newest one that is done
+        self.cumulative_partials = bool(cumulative_partials)
+        if self.cumulative_partials:
+            if not getattr(model, "token_logprobs", False) or not getattr(model, "draft_verify", False):
+                raise ValueError("cumulative_partials=True needs a model built with token_logprobs=True and draft_verify=True (the partials' token ids are the next request's draft)")
+            if any(v is not None for v in (sequence_bias, bad_words_ids, hotword_boost, temperature, seed)):
+                raise ValueError("cumulative_partials=True cannot be combined with bias values or a temperature: a draft is verified under the model's own processors only")
+        self._partials: List[List[Future]] = [[] for _ in self.ids]
         # beside the hotwords: the sessions' sequence-bias values (a model built with request_bias=True), handed to every decode only when one is given
         # (likewise the sessions' temperature - a float - and seed, for a model built with sampling=True)
         self._bias_kw = {k: v for k, v in (("sequence_bias", sequence_bias), ("bad_words_ids", bad_words_ids), ("hotword_boost", hotword_boost),
@@ -122,6 +135,7 @@ class GatedSessions:
             if start_id[s] >= 0:                                          # create_speech_segment (connection_manager.py:66-72)
                 self.segment_start[s] = start_id[s]
                 self.segment_start_time[s] = st.chunk_timestamp(int(start_id[s]), now)
+                self._partials[s] = []
                 events.append({"session": self.ids[s], "type": "speech_start", "start_chunk_id": int(start_id[s])})
             if end_id[s] >= 0 and self.segment_start[s] >= 0:             # finalize_current_segment + committed transcription (:74-84)
                 seg0, self.segment_start[s] = int(self.segment_start[s]), -1
@@ -132,6 +146,11 @@ class GatedSessions:
             st = self.streams[s]
             lo, hi = max(int(self.segment_start[s]), st.next_chunk_id - PARTIAL_CHUNKS), st.next_chunk_id - 1   # audio_manager.py:106-114
             self.last_partial[s] = now
+            if self.cumulative_partials:
+                ev = self._cumulative_partial(s, st)
+                if ev is not None:
+                    events.append(ev)
+                continue
             try:
                 first, ns = st.chunk_range_samples(lo, hi)
             except ValueError:
@@ -141,6 +160,34 @@ class GatedSessions:
             events.append({"session": self.ids[s], "type": "partial", "start_chunk_id": lo, "end_chunk_id": hi, "first_sample": first, "n_samples": ns,
                            "future": st.submit_samples(first, ns, PARTIAL_TOKENS, self.hotwords, **self._bias_kw)})
         return events
+
+    def _segment_draft(self, s: int) -> Optional[List[int]]:
+        """the token ids of the segment's most recent partial whose future is done, without EOS ids and without its last DRAFT_HOLDBACK tokens; None: nothing to offer"""
+        eos = set(int(t) for t in self.model.dims.eos_ids)
+        for f in reversed(self._partials[s]):
+            if f.done() and not f.cancelled() and f.exception() is None:
+                ids = [int(t) for t in f.result().token_ids if int(t) not in eos]
+                ids = ids[:max(0, len(ids) - DRAFT_HOLDBACK)]
+                return ids or None
+        return None
+
+    def _cumulative_partial(self, s: int, st) -> Optional[Dict]:
+        """segment start -> newest chunk (at most MAX_SEGMENT_S from the start: what an unsplit final, or a split one's first piece, will cover), the previous partial as
+        its draft, PARTIAL_TOKENS beyond the draft but never more than the committed budget of that much audio"""
+        lo, hi = int(self.segment_start[s]), st.next_chunk_id - 1
+        try:
+            first, ns = st.chunk_range_samples(lo, hi)
+        except ValueError:
+            return None
+        ns = min(ns, int(MAX_SEGMENT_S * self.sr))
+        if ns * 2 < CHUNK_BYTES:
+            return None
+        draft = self._segment_draft(s)
+        budget = min(len(draft or ()) + PARTIAL_TOKENS, committed_max_new_tokens(ns / self.sr))
+        fut = st.submit_samples(first, ns, budget, self.hotwords, detailed=True, draft=draft)
+        self._partials[s].append(fut)
+        return {"session": self.ids[s], "type": "partial", "start_chunk_id": lo, "end_chunk_id": hi, "first_sample": first, "n_samples": ns,
+                "draft_len": len(draft or ()), "max_new_tokens": budget, "future": fut}
 
     def _final(self, s: int, st, seg0: int, end_chunk_id: int) -> List[Dict]:
         try:
@@ -154,18 +201,25 @@ class GatedSessions:
         # segment_duration = min(actual_duration, segment.duration): the timestamp span start chunk -> speech_end_id chunk bounds both the
         # split test and the unsplit request's token budget (connection_manager.py:186-192); the audio itself runs to the NEWEST chunk
         seg_dur = min(ns / self.sr, max(0.0, st.chunk_timestamp(end_chunk_id, time.time()) - float(self.segment_start_time[s])))
+        if seg_dur <= MAX_SEGMENT_S and self.cumulative_partials:          # ... with the last partial's transcript as its draft: only the tail is decoded
+            draft, self._partials[s] = self._segment_draft(s), []
+            return [{"session": self.ids[s], "type": "final", "start_chunk_id": seg0, "end_chunk_id": end_chunk_id, "part": 0, "parts": 1,
+                     "seconds": seg_dur, "first_sample": first, "n_samples": ns, "draft_len": len(draft or ()),
+                     "future": st.submit_samples(first, ns, committed_max_new_tokens(seg_dur), self.hotwords, detailed=True, draft=draft)}]
         if seg_dur <= MAX_SEGMENT_S:                                      # one request, whatever its audio length (the processor windows it)
             return [{"session": self.ids[s], "type": "final", "start_chunk_id": seg0, "end_chunk_id": end_chunk_id, "part": 0, "parts": 1,
                      "seconds": seg_dur, "first_sample": first, "n_samples": ns,
                      "future": st.submit_samples(first, ns, committed_max_new_tokens(seg_dur), self.hotwords, **self._bias_kw)}]
         n_sub = -(-ns // piece)
+        det = {"detailed": True} if self.cumulative_partials else {}      # (every future of this mode is a Transcription; a split final's pieces take no draft)
+        self._partials[s] = []
         for i in range(n_sub):                                            # longer: pieces cut at sample 480000 * i, each with its own duration
             a, b = i * piece, min(ns, (i + 1) * piece)
             if (b - a) * 2 < CHUNK_BYTES * 2:                               # transcribe_committed returns "" below two chunks (:32-33)
                 continue
             out.append({"session": self.ids[s], "type": "final", "start_chunk_id": seg0, "end_chunk_id": end_chunk_id, "part": i, "parts": n_sub,
                         "seconds": (b - a) / self.sr, "first_sample": first + a, "n_samples": b - a,
-                        "future": st.submit_samples(first + a, b - a, committed_max_new_tokens((b - a) / self.sr), self.hotwords, **self._bias_kw)})
+                        "future": st.submit_samples(first + a, b - a, committed_max_new_tokens((b - a) / self.sr), self.hotwords, **self._bias_kw, **det)})
         return out
 
     def close(self):
