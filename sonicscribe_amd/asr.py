@@ -26,7 +26,7 @@ from typing import Any, Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import frontend
+from . import frontend, reqvalues
 from .dispatch import Dispatcher
 from .engine import Engine, MODE_INT8, MODE_NATIVE, SonicError, TokenScores, device_count, device_info
 from .scoring import Score
@@ -254,14 +254,11 @@ class AudioStream:
         if word_timestamps:
             raise ValueError("word_timestamps is not supported on submit() / transcribe_async() / stream decodes: align a finished transcript with ASRModel.align(), or use transcribe(..., word_timestamps=True)")
         m._check_detailed(detailed)
-        bias = m._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost)
-        samp = m._request_sampling(temperature, seed, ladder_ok=False)
-        gram = m._request_grammar(grammar)
-        dr = m._request_draft(draft, int(max_new_tokens), bias, samp, gram)
+        values = m._request_values(hotwords, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, grammar, draft, int(max_new_tokens), ladder_ok=False)
         windows = [self.ring.slice(first + s, e - s) for s, e in frontend.split_windows(n, m.dims)]
         n_audio, _ = frontend.request_audio_tokens(n, m.dims)
         prompt = m.prompt.build(frontend.build_instruction(hotwords), n_audio)
-        return m._dispatch(windows, prompt, int(max_new_tokens), detailed, bias, samp, gram, draft=dr, replica=self.replica)
+        return m._dispatch(windows, prompt, int(max_new_tokens), detailed, *values, replica=self.replica)
 
     def submit_chunks(self, start_chunk_id: int, end_chunk_id: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None,
                       detailed: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
@@ -588,23 +585,24 @@ class ASRModel:
         ids = cut_draft(self._candidate_ids(draft), self._eos_ids(), max_new)
         return ids or None
 
+    def _request_values(self, hotwords, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, grammar, draft, max_new: int, ladder_ok: bool = True):
+        """One call's own values, checked in this order: (bias, samp, gram, draft) as _request_bias, _request_sampling, _request_grammar and _request_draft give
+        them - what _dispatch takes behind `detailed`, and reqvalues.submit_keywords turns into Dispatcher.submit's keywords."""
+        bias = self._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost)
+        samp = self._request_sampling(temperature, seed, ladder_ok=ladder_ok)
+        gram = self._request_grammar(grammar)
+        return bias, samp, gram, self._request_draft(draft, max_new, bias, samp, gram)
+
     def _dispatch(self, windows, prompt, max_new: int, detailed: bool, bias, samp, gram=None, draft=None, **route) -> "Future":
         """One request on the scheduler -> a future of its text (detailed: its Transcription).  samp (from _request_sampling): None, one attempt at a temperature,
         or the fallback ladder - each attempt a new request for the same windows, prompt, table and seed; the future resolves after the last one.  Retries
         are submitted by the model's worker thread, never by a completion callback and never by the caller (fallback.py)."""
         from . import fallback
-        kw = dict(route)
-        if bias:
-            kw["bias"] = bias
-        if gram is not None:
-            kw["grammar"] = gram
-        if draft:
-            kw["draft"] = draft
-        if samp is None:
-            return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=detailed, **kw), self.prompt.decode, detailed, grammar=gram, draft=draft)
-        ts, ladder, seed = samp
-        if not ladder:
-            return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=detailed, sampling=(ts[0], seed), **kw), self.prompt.decode, detailed, ts[0], grammar=gram, draft=draft)
+        kw = dict(route, **reqvalues.submit_keywords(bias, samp, gram, draft))
+        if samp is None or not samp[1]:
+            return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=detailed, **kw), self.prompt.decode, detailed,
+                                0.0 if samp is None else samp[0][0], grammar=gram, draft=draft)
+        ts, _, seed = samp
 
         def one(temperature, seed):
             return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=True, sampling=(temperature, seed), **kw), self.prompt.decode, True, temperature, grammar=gram)
@@ -647,13 +645,10 @@ class ASRModel:
         if word_timestamps:
             raise ValueError("word_timestamps is not supported on submit() / transcribe_async() / stream decodes: align a finished transcript with ASRModel.align(), or use transcribe(..., word_timestamps=True)")
         self._check_detailed(detailed)
-        bias = self._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost)
-        samp = self._request_sampling(temperature, seed)
-        gram = self._request_grammar(grammar)
-        dr = self._request_draft(draft, int(max_new_tokens), bias, samp, gram)
+        values = self._request_values(hotwords, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, grammar, draft, int(max_new_tokens))
         pcm, windows, n_audio = self._prepare(audio_tensor, sampling_rate)
         prompt = self.prompt.build(frontend.build_instruction(hotwords), n_audio)
-        return self._dispatch(windows, prompt, int(max_new_tokens), detailed, bias, samp, gram, draft=dr, session=session)
+        return self._dispatch(windows, prompt, int(max_new_tokens), detailed, *values, session=session)
 
     def open_stream(self, session: str, buffer_seconds: float = 30.0, margin_seconds: float = 10.0, sampling_rate: int = 16000) -> AudioStream:
         """A streaming session whose audio stays on the device (config.py:25 MAX_AUDIO_BUFFER_SECONDS = 30): chunks are appended to a
@@ -747,11 +742,7 @@ class ASRModel:
             dets = [f.result() for f in futs_]
             self._attach_alignment(list(audios), dets, sampling_rate, hotwords)
             return dets
-        bias = self._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost)
-        samp = self._request_sampling(temperature, seed)
-        kw = {"request_bias": [bias] * len(audios)} if bias else {}
-        if samp is not None and not samp[1]:
-            kw["request_sampling"] = [(samp[0][0], samp[2])] * len(audios)
+        bias, samp, _, _ = self._request_values(hotwords, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, None, None, 0)      # (the grammars and drafts: per audio)
         mn = [int(max_new_tokens)] * len(audios) if isinstance(max_new_tokens, int) else [int(x) for x in max_new_tokens]
         drs = [None] * len(audios) if drafts is None else [self._request_draft(d, mn[i], bias, samp, grams[i]) for i, d in enumerate(drafts)]
         segs, req_win, prompts = [], [0], []
@@ -764,16 +755,13 @@ class ASRModel:
         if samp is not None and samp[1]:
             futs = [self._dispatch(segs[req_win[i]:req_win[i + 1]], prompts[i], mn[i], False, bias, samp, grams[i], draft=drs[i]) for i in range(len(audios))]
             return [f.result() for f in futs]
+        subs = [reqvalues.submit_keywords(bias, samp, grams[i], drs[i]) for i in range(len(audios))]
         if len(self.models) == 1 and not self.continuous:
-            if any(g is not None for g in grams):
-                kw["request_grammar"] = [None if g is None else g.on(self.model) for g in grams]
-            if any(drs):
-                kw["request_draft"] = drs
+            # one engine call: a value that some audio brings becomes its keyword's list, None for the audios without it
+            kw = {v.keyword: [v.on(s.get(v.attr), self.model) for s in subs] for v in reqvalues.VALUES if any(v.attr in s for s in subs)}
             ids, _ = self.model.transcribe_batch(segs, prompts, mn, req_win=req_win, **kw)
         else:            # independent segments: spread over the replicas (least-loaded placement), results in input order
-            skw = {"sampling": kw["request_sampling"][0]} if "request_sampling" in kw else {}
-            futs = [self._dispatcher.submit(segs[req_win[i]:req_win[i + 1]], prompts[i], mn[i], **({"bias": bias} if bias else {}), **({"grammar": grams[i]} if grams[i] is not None else {}), **({"draft": drs[i]} if drs[i] else {}), **skw)
-                    for i in range(len(audios))]
+            futs = [self._dispatcher.submit(segs[req_win[i]:req_win[i + 1]], prompts[i], mn[i], **subs[i]) for i in range(len(audios))]
             ids = [f.result() for f in futs]
         return [self.prompt.decode(i).strip() for i in ids]
 

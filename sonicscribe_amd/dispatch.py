@@ -35,7 +35,11 @@ from typing import Any, List, Optional, Sequence
 
 import numpy as np
 
+from . import reqvalues
+from .reqvalues import check_draft  # noqa: F401  (the draft's own refusals live beside the list of the per-request values)
+
 STEP_CLASSES = (16, 64, 256)      # upper bounds of max_new_tokens per bucket; anything larger shares the last bucket
+LOGPROBS_OFF = "log-probabilities need the engine option token_logprobs on every handle (ASRModel(token_logprobs=True))"
 
 
 def step_class(max_new: int) -> int:
@@ -60,24 +64,6 @@ class Request:
         self.cls = step_class(self.max_new)
 
 
-def _device_grammar(req: "Request", engine):
-    """the request's grammar as the handle that lives on `engine`'s weight owner (None: a free request)"""
-    return None if req.grammar is None else req.grammar.on(engine)
-
-
-DRAFT_OFF = "a draft needs the engine option draft_verify on every handle (ASRModel(draft_verify=True))"
-
-
-def check_draft(req: "Request", engines) -> None:
-    """ValueError by name unless every handle verifies drafts, and for a draft beside a bias table, a temperature > 0 or a grammar (the library refuses those too)"""
-    if not req.draft:
-        return
-    if not all(getattr(e, "draft_verify", False) for e in engines):
-        raise ValueError(DRAFT_OFF)
-    if req.bias or req.grammar or (req.sampling and req.sampling[0] > 0):
-        raise ValueError("a draft cannot be combined with a bias table, a temperature > 0 or a grammar (the verify pass applies the engine's own processors only)")
-
-
 def request_tokens(req: "Request") -> int:
     """the tokens the request adds to a prefill: its prompt and its draft"""
     return len(req.prompt) + (len(req.draft) if req.draft else 0)
@@ -86,12 +72,9 @@ def request_tokens(req: "Request") -> int:
 def fits_tokens(engine, used: int, req: "Request") -> bool:
     """Handles with option draft_verify count a batch's prompt and draft tokens against tok_cap (what one prefill holds); a request that alone exceeds it goes through
     and is refused by the engine, by name.  Other handles batch as they always did."""
-    if not getattr(engine, "draft_verify", False) or used == 0:
+    if not getattr(engine, reqvalues.DRAFT.option, False) or used == 0:
         return True
     return used + request_tokens(req) <= int(engine.tok_cap)
-
-
-GRAMMAR_OFF = "a grammar needs the engine option grammar on every handle (ASRModel(token_logprobs=True, grammar=True))"
 
 
 class _Replica:
@@ -116,6 +99,8 @@ class _Replica:
             return self.busy_windows + sum(len(r.windows) for r in self.q)
 
     def put(self, req: Request):
+        # the one replica that refuses only the draft here: a bias table, a temperature or a grammar that the engine does not admit is refused by the engine inside
+        # _run, and the caller sees that error from the future, not from submit
         check_draft(req, self.engines)
         with self.cv:
             if self.stop:
@@ -160,50 +145,32 @@ class _Replica:
         else:
             r.future.set_result(result)
 
-    def _run(self, batch: List[Request], k: int = 0):
-        engine = self.engines[k]
+    @staticmethod
+    def _call(engine, reqs: List[Request], kw: dict) -> list:
+        """one engine call for `reqs` with their own values' keywords `kw` -> one result per request"""
         segs, req_win = [], [0]
-        for r in batch:
+        for r in reqs:
             segs.extend(r.windows)
             req_win.append(len(segs))
-        want = any(r.want_logprobs for r in batch)      # (the keyword only goes to the engine when somebody asked: duck-typed engines need not know it)
-        # (likewise; an engine with option request_bias is ALWAYS told its batch's tables, None for a request without one: a batch never depends on what an
-        # earlier, failed one left behind)
-        stated = bool(getattr(engine, "request_bias", False))
-        kw = {"request_bias": [r.bias for r in batch]} if stated or any(r.bias for r in batch) else {}
-        samp_on = bool(getattr(engine, "sampling", False))
-        if samp_on or any(r.sampling for r in batch):
-            kw["request_sampling"] = [r.sampling for r in batch]
-        gram_on = bool(getattr(engine, "grammar", False))
-        if gram_on or any(r.grammar for r in batch):      # (likewise: every batch states its grammars, None = a free request)
-            kw["request_grammar"] = [_device_grammar(r, engine) for r in batch]
-        draft_on = bool(getattr(engine, "draft_verify", False))
-        if draft_on or any(r.draft for r in batch):        # (likewise: None = no draft)
-            kw["request_draft"] = [r.draft for r in batch]
+        if not any(r.want_logprobs for r in reqs):       # (the keyword only goes to the engine when somebody asked: duck-typed engines need not know it)
+            ids, _ = engine.transcribe_batch(segs, [r.prompt for r in reqs], [r.max_new for r in reqs], req_win=req_win, **kw)
+            return ids
+        ids, _, lps = engine.transcribe_batch(segs, [r.prompt for r in reqs], [r.max_new for r in reqs], req_win=req_win, want_logprobs=True, **kw)
+        return [(i, l) if r.want_logprobs else i for r, i, l in zip(reqs, ids, lps)]
+
+    def _run(self, batch: List[Request], k: int = 0):
+        engine = self.engines[k]
+        kw = reqvalues.keywords(engine, batch)           # (likewise for the requests' own values; an engine with the option on is always told: reqvalues._stated)
         try:
-            if want:
-                ids, _, lps = engine.transcribe_batch(segs, [r.prompt for r in batch], [r.max_new for r in batch], req_win=req_win, want_logprobs=True, **kw)
-                ids = [(i, l) if r.want_logprobs else i for r, i, l in zip(batch, ids, lps)]
-            else:
-                ids, _ = engine.transcribe_batch(segs, [r.prompt for r in batch], [r.max_new for r in batch], req_win=req_win, **kw)
+            ids = self._call(engine, batch, kw)
         except BaseException as ex:              # a per-request validation error must not poison its neighbours: retry one by one
             if len(batch) == 1:
                 self._finish(batch[0], error=ex)
                 return
             for r in batch:
-                kw1 = {"request_bias": [r.bias]} if stated or r.bias else {}
-                if samp_on or r.sampling:
-                    kw1["request_sampling"] = [r.sampling]
-                if gram_on or r.grammar:
-                    kw1["request_grammar"] = [_device_grammar(r, engine)]
-                if draft_on or r.draft:
-                    kw1["request_draft"] = [r.draft]
+                kw1 = reqvalues.keywords(engine, [r])
                 try:
-                    if r.want_logprobs:
-                        one, _, lp1 = engine.transcribe_batch(r.windows, [r.prompt], [r.max_new], req_win=[0, len(r.windows)], want_logprobs=True, **kw1)
-                        one = [(one[0], lp1[0])]
-                    else:
-                        one, _ = engine.transcribe_batch(r.windows, [r.prompt], [r.max_new], req_win=[0, len(r.windows)], **kw1)
+                    one = self._call(engine, [r], kw1)
                 except BaseException as ex2:
                     self._finish(r, error=ex2)
                 else:
@@ -301,16 +268,11 @@ class _ContinuousReplica:
     def put(self, req: Request):
         if req.want_logprobs and not all(getattr(e, "token_logprobs", False) for e in self.engines):
             # refused here: inside the decode thread the failing fetch would take the neighbours' rows with it
-            raise ValueError("log-probabilities need the engine option token_logprobs on every handle (ASRModel(token_logprobs=True))")
-        if req.bias and not all(getattr(e, "request_bias", False) for e in self.engines):
-            raise ValueError("a sequence bias needs the engine option request_bias on every handle (ASRModel(request_bias=True))")
-        if req.sampling and not all(getattr(e, "sampling", False) for e in self.engines):
-            raise ValueError("a temperature needs the engine option sampling on every handle (ASRModel(sampling=True))")
-        if req.grammar and not all(getattr(e, "grammar", False) for e in self.engines):
-            raise ValueError(GRAMMAR_OFF)
+            raise ValueError(LOGPROBS_OFF)
+        reqvalues.refuse_unsupported(req, reqvalues.supported(self.engines))
         if req.grammar:
-            req.grammar.on(self.engine)                   # (ValueError here for a grammar of another model, not in the prefill thread)
-        check_draft(req, self.engines)
+            req.grammar.on(self.engine)                   # (ValueError here for a grammar of another model, not in the prefill thread; ahead of the draft's check -
+        check_draft(req, self.engines)                    # the native replica meets a foreign grammar behind it, when it packs)
         with self.cv:
             if self.stop:
                 raise RuntimeError("ASR engine is closed")
@@ -354,16 +316,9 @@ class _ContinuousReplica:
                 busy = sum(self.n_rows - f for f in self.free) > len(batch)        # rows running or reserved besides this batch's own
             eng.set_option("gemm_small_eff", 0 if busy else 75)
         eng.stage_pcm(segs, req_win)
-        # the tables follow their requests: row i of this prefill is batch[i]; the prefill consumes them.  With the option on every prefill states its tables
+        # the requests' own values follow them: row i of this prefill is batch[i]; the prefill consumes them.  With an option on every prefill states its values
         # (None: none), so a batch never depends on what an earlier, failed one left behind
-        if getattr(eng, "request_bias", False) or any(r.bias for r in batch):
-            eng.set_request_bias([r.bias for r in batch])
-        if getattr(eng, "sampling", False) or any(r.sampling for r in batch):      # (likewise: every prefill states its values, None = greedy)
-            eng.set_request_sampling([r.sampling for r in batch])
-        if getattr(eng, "grammar", False) or any(r.grammar for r in batch):        # (likewise: None = a free request)
-            eng.set_request_grammar([_device_grammar(r, eng) for r in batch])
-        if getattr(eng, "draft_verify", False) or any(r.draft for r in batch):     # (likewise: None = no draft)
-            eng.set_request_draft([r.draft for r in batch])
+        reqvalues.arm(eng, batch)
         # waited for: a splice queued behind a prefill that is still running would hold the decoder's whole stream (every running row) at the
         # event until the prefill is done - final p50 at 128 sessions 438 -> 657 ms when the hand-over came early.  (The bulk pipeline hands over
         # early, sonicscribe_amd/pipeline.py: its next batch is long done when a block frees up.)
@@ -521,10 +476,7 @@ class _NativeContinuousReplica:
         self.stop = False
         self.out_cap = int(engine.max_ctx)
         self.lp = all(getattr(e, "token_logprobs", False) for e in self.engines)      # then completions are collected with their log-probabilities
-        self.bias = all(getattr(e, "request_bias", False) for e in self.engines)      # then a request may bring its own sequence-bias table
-        self.samp = all(getattr(e, "sampling", False) for e in self.engines)          # then a request may bring its own (temperature, seed)
-        self.gram = all(getattr(e, "grammar", False) for e in self.engines)           # then a request may bring its grammar
-        self.draft = all(getattr(e, "draft_verify", False) for e in self.engines)     # then a request may bring a draft
+        self.admits = reqvalues.supported(self.engines)   # per value of reqvalues.VALUES: every handle has its option on, a request may bring it
         self.thread = threading.Thread(target=self._complete_loop, name=f"sonic-dispatch-{index}.complete", daemon=True)
         self.thread.start()
 
@@ -555,17 +507,12 @@ class _NativeContinuousReplica:
         import ctypes as C
         from .engine import RingSlice, _p
         if req.want_logprobs and not self.lp:
-            raise ValueError("log-probabilities need the engine option token_logprobs on every handle (ASRModel(token_logprobs=True))")
-        if req.bias and not self.bias:
-            raise ValueError("a sequence bias needs the engine option request_bias on every handle (ASRModel(request_bias=True))")
-        if req.sampling and not self.samp:
-            raise ValueError("a temperature needs the engine option sampling on every handle (ASRModel(sampling=True))")
-        if req.grammar and not self.gram:
-            raise ValueError(GRAMMAR_OFF)
+            raise ValueError(LOGPROBS_OFF)
+        reqvalues.refuse_unsupported(req, self.admits)
         check_draft(req, self.engines)
         if req.bias:
-            req.bias.check_vocab(self.engine.dims.vocab)
-        dev_gram = _device_grammar(req, self.engine)
+            req.bias.check_vocab(self.engine.dims.vocab)  # (the Python replica leaves this to Engine.set_request_bias, in its prefill thread)
+        dev_gram = None if req.grammar is None else req.grammar.on(self.engine)
         wins = req.windows
         W = len(wins)
         offs = np.zeros(W + 1, np.int64)
@@ -724,18 +671,22 @@ class _BulkReplica:
         with self.cv:
             return sum(len(r.windows) for r in self.q) + sum(sum(len(r.windows) for r in b) for _, b in self.inflight)
 
+    # refused, not dropped: no per-request state travels through the bulk pipeline (csrc/pipeline.cpp; sonic_pipeline_create refuses handles with option
+    # draft_verify).  Request attribute -> text, walked in this order
+    REFUSED = {
+        "bias": "a sequence bias is not supported with bulk=True (the bulk pipeline carries no per-request tables): use the continuous or the batch dispatcher",
+        "draft": "a draft is not supported with bulk=True (the bulk pipeline verifies no drafts): use the continuous or the batch dispatcher",
+        "grammar": "a grammar is not supported with bulk=True (the bulk pipeline carries no per-request grammar state): use the continuous or the batch dispatcher",
+        "sampling": "a temperature is not supported with bulk=True (the bulk pipeline carries no per-request values): use the continuous or the batch dispatcher",
+    }
+
     def put(self, req: Request):
         from .engine import RingSlice
         if not all(isinstance(w, (np.ndarray, RingSlice)) for w in req.windows):
             raise TypeError("bulk mode takes host PCM windows or slices of device rings")
-        if req.bias:                                      # refused, not dropped: the bulk pipeline (csrc/pipeline.cpp) carries no per-request tables
-            raise ValueError("a sequence bias is not supported with bulk=True (the bulk pipeline carries no per-request tables): use the continuous or the batch dispatcher")
-        if req.draft:                                     # likewise (and sonic_pipeline_create refuses handles with option draft_verify)
-            raise ValueError("a draft is not supported with bulk=True (the bulk pipeline verifies no drafts): use the continuous or the batch dispatcher")
-        if req.grammar:                                   # likewise: no per-request state travels through the bulk pipeline
-            raise ValueError("a grammar is not supported with bulk=True (the bulk pipeline carries no per-request grammar state): use the continuous or the batch dispatcher")
-        if req.sampling:                                  # likewise: no per-request values travel through the bulk pipeline
-            raise ValueError("a temperature is not supported with bulk=True (the bulk pipeline carries no per-request values): use the continuous or the batch dispatcher")
+        for attr, text in self.REFUSED.items():
+            if getattr(req, attr):
+                raise ValueError(text)
         with self.cv:
             if self.stop:
                 raise RuntimeError("ASR engine is closed")

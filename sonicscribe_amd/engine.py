@@ -12,6 +12,7 @@ from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import reqvalues
 from .engine_hooks import EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_SWIGLU, HooksMixin, _arr, _p  # noqa: F401
 from .spec import ModelDims
 
@@ -350,6 +351,20 @@ def unpack_logprobs(rec, n: int, K: int, align: bool = False):
     return TokenScores(r[:, 0].copy(), r[:, 1:1 + K].copy(), r[:, 1 + K:].astype(np.int32))
 
 
+# The options a handle mirrors as attributes of the same name, with their type: set_option keeps them current, a slot created from now on copies them (in the
+# library and here).  top_logprobs is the width of every log-probability record the handle returns; forced_parallel and forced_align may also be set on a slot alone;
+# the last four admit the per-request values of reqvalues.VALUES.
+MIRRORED_OPTIONS = {"token_logprobs": bool, "top_logprobs": int, "forced_parallel": bool, "forced_align": bool, **{v.option: bool for v in reqvalues.VALUES}}
+
+
+def copy_mirrored_options(src, dst) -> None:
+    """the mirrored options of `src` onto the slot `dst`, as sonic_slot_create copies them: top_logprobs is 0 on a slot whose token_logprobs is off"""
+    for name, kind in MIRRORED_OPTIONS.items():
+        setattr(dst, name, kind(getattr(src, name, 0)))
+    if not dst.token_logprobs:
+        dst.top_logprobs = 0
+
+
 class Engine(HooksMixin):
     """One model replica on one MI355X."""
 
@@ -381,14 +396,7 @@ class Engine(HooksMixin):
         KV cache, graphs, lock - that shares the owner's weight allocations.  Closed with its owner at the latest."""
         root = self.root
         s = Engine(self.dims, 0, 0, self.max_batch, self.max_ctx, _slot_of=root)
-        s.token_logprobs = bool(getattr(root, "token_logprobs", False))
-        s.top_logprobs = int(getattr(root, "top_logprobs", 0)) if s.token_logprobs else 0
-        s.request_bias = bool(getattr(root, "request_bias", False))
-        s.sampling = bool(getattr(root, "sampling", False))
-        s.grammar = bool(getattr(root, "grammar", False))
-        s.forced_parallel = bool(getattr(root, "forced_parallel", False))
-        s.forced_align = bool(getattr(root, "forced_align", False))
-        s.draft_verify = bool(getattr(root, "draft_verify", False))
+        copy_mirrored_options(root, s)
         root._slots.append(s)
         return s
 
@@ -571,29 +579,12 @@ class Engine(HooksMixin):
         request_draft: one id sequence or None (no draft) per request (option draft_verify on this handle; set_request_draft)."""
         samp = None if request_sampling is None else pack_request_sampling(request_sampling)      # (validated before anything is armed)
         draft = None if request_draft is None else pack_request_draft(request_draft)
-        if any(isinstance(s, RingSlice) for s in segments):
+        if any(isinstance(s, RingSlice) for s in segments):      # the two forms differ in how the audio is packed and in the entry point that takes it
             pcm, offs, rings, start, n = self._pack_mixed(segments)
-            ids, poffs = self._pack_prompts(prompts)
-            R = len(prompts)
-            mn = np.ascontiguousarray(max_new, dtype=np.int32)
-            out_ld = int(mn.max())
-            out = np.zeros((R, out_ld), np.int32)
-            out_len = np.zeros(R, np.int32)
-            rw = _arr(req_win, np.int32)
-            logits = np.zeros((out_ld, R, self.dims.vocab), np.float32) if want_logits else None
-            if request_bias is not None:             # (right ahead of the call that consumes them, on success or failure: nothing in between can raise)
-                self.set_request_bias(request_bias)
-            if samp is not None:
-                self._arm_sampling(samp)
-            if request_grammar is not None:
-                self.set_request_grammar(request_grammar)
-            if draft is not None:
-                self._arm_draft(draft)
-            self._check(self.lib.sonic_transcribe_mixed(self.h, _p(pcm), _p(offs), rings, _p(start), _p(n), len(segments), _p(rw), R, _p(ids), _p(poffs),
-                                                        _p(mn), _p(out), out_ld, _p(out_len), _p(logits)))
-            res = [out[r, : out_len[r]].copy() for r in range(R)]
-            return (res, logits, self._fetch_logprobs(out_len, out_ld)) if want_logprobs else (res, logits)
-        pcm, offs = self._pack_pcm(segments)
+            entry, audio = self.lib.sonic_transcribe_mixed, (_p(pcm), _p(offs), rings, _p(start), _p(n))
+        else:
+            pcm, offs = self._pack_pcm(segments)
+            entry, audio = self.lib.sonic_transcribe_batch, (_p(pcm), _p(offs))
         ids, poffs = self._pack_prompts(prompts)
         R = len(prompts)
         mn = np.ascontiguousarray(max_new, dtype=np.int32)
@@ -602,18 +593,23 @@ class Engine(HooksMixin):
         out_len = np.zeros(R, np.int32)
         rw = _arr(req_win, np.int32)
         logits = np.zeros((out_ld, R, self.dims.vocab), np.float32) if want_logits else None
-        if request_bias is not None:
-            self.set_request_bias(request_bias)
-        if samp is not None:
-            self._arm_sampling(samp)
-        if request_grammar is not None:
-            self.set_request_grammar(request_grammar)
-        if draft is not None:
-            self._arm_draft(draft)
-        self._check(self.lib.sonic_transcribe_batch(self.h, _p(pcm), _p(offs), len(segments), _p(rw), R, _p(ids), _p(poffs), _p(mn),
-                                                    _p(out), out_ld, _p(out_len), _p(logits)))
+        self._arm_requests(request_bias, samp, request_grammar, draft)
+        self._check(entry(self.h, *audio, len(segments), _p(rw), R, _p(ids), _p(poffs), _p(mn), _p(out), out_ld, _p(out_len), _p(logits)))
         res = [out[r, : out_len[r]].copy() for r in range(R)]
         return (res, logits, self._fetch_logprobs(out_len, out_ld)) if want_logprobs else (res, logits)
+
+    def _arm_requests(self, bias, samp_packed, grammar, draft_packed):
+        """The per-request values of the next prefill / run on this handle, None for a value the caller does not state: the call right ahead of the library call
+        that consumes them, on success or failure - nothing in between can raise.  In the order of reqvalues.VALUES; the sampling values and the drafts come packed
+        (pack_request_sampling, pack_request_draft: validated before anything is armed)."""
+        if bias is not None:
+            self.set_request_bias(bias)
+        if samp_packed is not None:
+            self._arm_sampling(samp_packed)
+        if grammar is not None:
+            self.set_request_grammar(grammar)
+        if draft_packed is not None:
+            self._arm_draft(draft_packed)
 
     def score_batch(self, segments: Sequence[Any], prompts: Sequence[Sequence[int]], targets, req_win: Optional[Sequence[int]] = None, fanout: int = 1,
                     want_logits: bool = False, align: bool = False):
@@ -682,14 +678,7 @@ class Engine(HooksMixin):
         rw = _arr(req_win, np.int32)
         samp = None if request_sampling is None else pack_request_sampling(request_sampling)
         draft = None if request_draft is None else pack_request_draft(request_draft)
-        if request_bias is not None:                     # one reqbias.RequestBias or None per request: this prefill consumes them, on success or failure
-            self.set_request_bias(request_bias)
-        if samp is not None:                             # one (temperature, seed) or None per request: likewise
-            self._arm_sampling(samp)
-        if request_grammar is not None:                  # one DeviceGrammar or None per request: likewise
-            self.set_request_grammar(request_grammar)
-        if draft is not None:                            # one id sequence or None per request: likewise
-            self._arm_draft(draft)
+        self._arm_requests(request_bias, samp, request_grammar, draft)      # (as transcribe_batch's keywords: this prefill consumes them, on success or failure)
         if not wait:
             self._check(self.lib.sonic_prefill_enqueue(self.h, _p(rw), len(prompts), _p(ids), _p(poffs), _p(mn)))
             return
@@ -793,22 +782,8 @@ class Engine(HooksMixin):
     # -- product setters
     def set_option(self, key: str, value: int):
         self._check(self.lib.sonic_set_option(self.h, key.encode(), value))
-        if key == "request_bias":
-            self.request_bias = bool(value)          # (likewise)
-        if key == "sampling":
-            self.sampling = bool(value)              # (likewise)
-        if key == "grammar":
-            self.grammar = bool(value)               # (likewise)
-        if key == "top_logprobs":
-            self.top_logprobs = int(value)           # (likewise: the width of every log-probability record this handle returns)
-        if key == "token_logprobs":
-            self.token_logprobs = bool(value)        # (a slot created from now on copies it, in the library and here)
-        if key == "forced_parallel":
-            self.forced_parallel = bool(value)       # (likewise; it may also be set on a slot alone)
-        if key == "forced_align":
-            self.forced_align = bool(value)          # (likewise: a parallel run's records then carry t_n)
-        if key == "draft_verify":
-            self.draft_verify = bool(value)          # (likewise: a request of this handle may bring a draft)
+        if key in MIRRORED_OPTIONS:
+            setattr(self, key, MIRRORED_OPTIONS[key](value))
 
     def set_forced_ids(self, ids):
         """ids: [R][ld] int array (token n of request r) or None to clear; see sonic_set_forced_ids."""

@@ -24,7 +24,7 @@ from typing import Any, Dict, Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import frontend
+from . import frontend, reqvalues
 
 SAMPLE_RATE = 16000                  # config.py:22 AUDIO_SAMPLE_RATE
 DEFAULT_MAX_SEGMENT_S = 30.0         # config.py:41 MAX_SEGMENT_DURATION
@@ -194,15 +194,12 @@ class _FileJob:
             windows = [self.ring.slice(self.first + a + s, e - s) for s, e in frontend.split_windows(n, m.dims)]
             n_audio, _ = frontend.request_audio_tokens(n, m.dims)
             self.requests.append((windows, m.prompt.build(instruction, n_audio), n))
-            if self.samp is not None and self.word_timestamps:      # one temperature: the scheduler's own future carries the tokens
-                self.futures.append(m._dispatcher.submit(windows, m.prompt.build(instruction, n_audio), self.max_new, replica=self.replica, sampling=(self.samp[0][0], self.samp[2]),
-                                                         **({"bias": self.bias} if self.bias else {}), **({"grammar": self.gram} if self.gram is not None else {})))
-                continue
-            if self.samp is not None:              # (a future of the TEXT: the ladder judges texts; records() takes either)
+            if self.samp is not None and not self.word_timestamps:      # (a future of the TEXT: the ladder judges texts; records() takes either)
                 self.futures.append(m._dispatch(windows, m.prompt.build(instruction, n_audio), self.max_new, False, self.bias, self.samp, self.gram, replica=self.replica))
                 continue
-            self.futures.append(m._dispatcher.submit(windows, m.prompt.build(instruction, n_audio), self.max_new, replica=self.replica, **({"bias": self.bias} if self.bias else {}),
-                                                     **({"grammar": self.gram} if self.gram is not None else {})))
+            # the scheduler's own future carries the tokens (with word_timestamps: at the file's one temperature; a ladder was refused when the job was made)
+            self.futures.append(m._dispatcher.submit(windows, m.prompt.build(instruction, n_audio), self.max_new, replica=self.replica,
+                                                     **reqvalues.submit_keywords(self.bias, self.samp, self.gram, None)))
 
     def records(self) -> Iterator[Dict[str, Any]]:
         total_segments = len(self.segments)
