@@ -186,7 +186,28 @@ SONIC_API int sonic_pipeline_stats(sonic_pipeline* p, int64_t* batches_done, int
 SONIC_API const char* sonic_pipeline_last_error(sonic_pipeline* p);
 SONIC_API int sonic_pipeline_destroy(sonic_pipeline* p);
 
-/* ---- weights (names: GlmAsrForConditionalGeneration.state_dict() keys, see sonicscribe_amd/spec.py) ---- */
+/* ---- weights (names: GlmAsrForConditionalGeneration.state_dict() keys, see sonicscribe_amd/spec.py) ----
+ * On a finalized engine the call also carries the named int32 words that need no entry point of their own: "grammar:<id>" / "grammar.dispatch:<id>" /
+ * "grammar.hook:<V>" (DESIGN.md 6.10), "request_draft" / "draft.dispatch" (6.11, beside sonic_set_forced_ids) and "request_forks":
+ *
+ * Row forks (sonic_load_tensor "request_forks"): one prefilled request becomes several rows - N samples of one audio (Whisper's best_of) pay for
+ * log-mel, encoder and prefill once.
+ *   sonic_load_tensor(e, "request_forks", counts, SONIC_DTYPE_I32, {A}, 1): request a of the NEXT prefill on this handle (the entry points sonic_set_request_bias
+ *   names) becomes counts[a] >= 1 rows; that call consumes the counts on success and on failure alike (sonic_run_staged_async keeps them for its run, as a draft).
+ *   No option, no buffer: sonic_memory_info does not move.  Without staged counts, or with every count 1, a prefill launches exactly what it launched before.
+ *   row order, with R' = sum counts: rows 0 .. A-1 are the requests themselves (fork 0), through the decoder layers exactly as without forks; the forks j >= 1
+ *   follow request by request, row(a, j) = A + sum_{b < a} (counts[b] - 1) + (j - 1).  The entry point's R, prompts, budgets and req_win stay per request (A of
+ *   them); sonic_set_request_bias, sonic_set_request_sampling and "request_grammar_begin" / "request_grammar" state their values per ROW, R' of them in row order;
+ *   out_ids / out_len / step_logits, sonic_fetch_*, sonic_decode_step and sonic_splice_rows (src_rows) see R' rows.
+ *   what runs: behind the last decoder layer fork_kv_kernel copies, per forked request, layer and kv head, the kv_len * head_dim elements of K and of V from the
+ *   request's cache row to each fork's row - every 16-byte piece read once and written counts[a] - 1 times - and the row's history where the handle keeps one.  The
+ *   head (final norm through the row map, lm_head, greedy kernel) then runs over R' rows: every fork's first token is drawn from its request's logits under its
+ *   own row's seed, temperature, bias table and grammar.  From there on the rows are ordinary rows of the decode loops.
+ *   refusals (SONIC_ERR_INVALID, the message naming request_forks): a count below 1; more rows than max_batch; the int8 and fp32 kinds; a scoring handle
+ *   ("forced_parallel"); and at the prefill: an A that is not the batch's R; forced ids set (sonic_set_forced_ids); a draft in the same prefill; a per-row stage
+ *   that was given another count than R'.
+ *   sonic_debug_read "kcache" / "vcache" (index = decoder layer, Bm * Hkv * max_ctx * head_dim elements) read the cache; "fork_ms" (n = 1) is the kernel's time in
+ *   the handle's last forked prefill. */
 SONIC_API int sonic_load_tensor(sonic_engine* e, const char* name, const void* data, int dtype, const int64_t* shape, int ndim);
 SONIC_API int sonic_load_synthetic(sonic_engine* e, uint64_t seed);          /* portable generator, sonicscribe_amd/synth.py */
 SONIC_API int sonic_finalize_weights(sonic_engine* e);                        /* packs fused QKV / gate-up, conv im2col order */
@@ -644,7 +665,7 @@ SONIC_API int sonic_bench_gemm(sonic_engine* e, int M, int N, int K, int epi, in
 /* times the decode-step skinny GEMM (variant: 0 LDS-DMA nt, 1 LDS-DMA default policy, 2 registers nt, 3 registers plain, 9 pure-read floor) */
 SONIC_API int sonic_bench_skinny(sonic_engine* e, int M, int N, int K, int variant, int iters, float* us_per_launch);
 /* debug read-back of an internal bf16 activation buffer as fp32 ("prefill_tap" with index = 0 (embeddings) .. dec_layers,
- * "pe", "dx", "dqkv", "dq", "datt", "dact", "enc_x"; "align_probs", "align_matrix": fp32 buffers of the last align run, see sonic_set_forced_ids; "draft_accepted": the accepted counts of the last prefill, see there); tests / diagnostics only */
+ * "pe", "dx", "dqkv", "dq", "datt", "dact", "enc_x"; "align_probs", "align_matrix": fp32 buffers of the last align run, see sonic_set_forced_ids; "draft_accepted": the accepted counts of the last prefill, see there; "kcache" / "vcache" with index = decoder layer: the KV cache [max_batch][kv heads][max_ctx][head_dim]; "fork_ms", see sonic_load_tensor); tests / diagnostics only */
 SONIC_API int sonic_debug_read(sonic_engine* e, const char* name, int index, float* out, int64_t n);
 /* diagnostics: in-kernel timestamps (100 MHz device wall clock) of the decode kernels of one decoder layer, recorded while the option
  * "ktrace" = layer index is set: out[slot][block < 512][8 points], slots 0 qkv, 1 attention, 2 o_proj, 3 gate/up, 4 down */

@@ -92,6 +92,7 @@ class Transcription:
     the model scored, whatever token was emitted: on a greedy request column 0 is the token itself."""
     __slots__ = ("text", "token_ids", "token_logprobs", "avg_logprob", "temperature", "compression_ratio", "attempts", "top_token_ids", "top_logprobs",
                  "draft_len", "draft_matched",      # a request that brought a draft (ASRModel(draft_verify=True); DESIGN.md 6.11): the ids of the draft as it was submitted, and how many of them the transcript begins with; 0 without
+                 "best_of", "fork_index", "fork_avg_logprobs",      # an attempt that drew best_of samples from one forked run (ASRModel(best_of=N); DESIGN.md 6.12): how many, which of them this is, and every sample's avg_logprob in fork order; 1, 0 and this transcript's own otherwise
                  "grammar_status",      # a request decoded under a grammar: grammar.Grammar.walk over token_ids - "accepted", "incomplete" or "left"; None without
                  "words", "token_start", "token_end")      # word_timestamps=True (ASRModel(timestamps=True); DESIGN.md 6.9): timestamps.Word list and the tokens' times (EOS dropped); None without
 
@@ -111,6 +112,7 @@ class Transcription:
         self.top_token_ids = np.zeros((n, 0), np.int32) if top_ids is None else np.asarray(top_ids, np.int32)
         # over all emitted tokens, the EOS that stopped the row included; nothing emitted: nan
         self.avg_logprob = float(np.mean(self.token_logprobs, dtype=np.float64)) if self.token_logprobs.size else float("nan")
+        self.best_of, self.fork_index, self.fork_avg_logprobs = 1, 0, np.asarray([self.avg_logprob], np.float64)
 
     def __repr__(self):
         return f"Transcription(text={self.text!r}, tokens={self.token_ids.size}, avg_logprob={self.avg_logprob:.4f})"
@@ -148,6 +150,35 @@ def check_top_logprobs(top_logprobs, token_logprobs: bool, bulk: bool) -> int:
     if K and bool(bulk):
         raise ValueError("top_logprobs is not supported with bulk=True: the bulk pipeline carries one log-probability per token")
     return K
+
+
+def check_best_of(best_of, max_batch: int, sampling: bool = True, bulk: bool = False) -> int:
+    """ASRModel's best_of argument -> N, or ValueError by name: not an integer in 1 .. max_batch; above 1 without sampling=True or with bulk=True"""
+    if isinstance(best_of, bool) or not isinstance(best_of, (int, np.integer)) or not 1 <= int(best_of) <= int(max_batch):
+        raise ValueError(f"best_of must be an integer in 1 .. {int(max_batch)} (max_batch; got {best_of!r})")
+    N = int(best_of)
+    if N > 1 and not sampling:
+        raise ValueError("best_of > 1 needs sampling=True: the samples are drawn at a temperature (ASRModel(..., token_logprobs=True, sampling=True, best_of=N))")
+    if N > 1 and bool(bulk):
+        raise ValueError("best_of is not supported with bulk=True: the bulk pipeline carries no per-request values")
+    return N
+
+
+def _only_text(fut: "Future") -> "Future[str]":
+    """Future of the text behind a future of a Transcription; cancelling it cancels that one"""
+    out: "Future[str]" = Future()
+
+    def done(f):
+        if out.done():
+            return
+        try:
+            out.set_result(f.result().text)
+        except BaseException as ex:
+            if not out.done():
+                out.set_exception(ex)
+    fut.add_done_callback(done)
+    out.add_done_callback(lambda f: fut.cancel() if f.cancelled() else None)
+    return out
 
 
 def _text_future(inner: "Future", decode, detailed: bool = False, temperature: float = 0.0, grammar=None, draft=None) -> "Future[str]":
@@ -282,7 +313,7 @@ class ASRModel:
                  *, max_batch: int = 32, max_ctx: int = 1024, slots: int = DEFAULT_SLOTS, continuous: bool = DEFAULT_CONTINUOUS, decoders: int = 1, bulk: bool = False, native_dispatch: Optional[bool] = None, token_logprobs: bool = False, top_logprobs: int = 0,
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None,
                  request_bias: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: float = 0.0,
-                 sampling: bool = False, temperature=0.0, seed: int = 0, compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0,
+                 sampling: bool = False, temperature=0.0, seed: int = 0, compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0, best_of: int = 1,
                  scoring: bool = False, timestamps: bool = False, alignment_heads=None, grammar: bool = False, draft_verify: bool = False,
                  _dims: Optional[ModelDims] = None,
                  _synthetic_seed: Optional[int] = None, _allow_synthetic_prompt: bool = False, _options: Optional[Dict[str, int]] = None,
@@ -293,7 +324,9 @@ class ASRModel:
         `hotword_boost` here are defaults for every request and switch `request_bias` on.  `top_logprobs` = K in 1 .. 8 (needs token_logprobs=True; not with
         bulk=True): every `detailed=True` result also carries the K best ids of every step with their log-probabilities.  `sampling` (needs token_logprobs=True): requests may be decoded at a
         temperature with a seed, or down a fallback ladder of temperatures (fallback.py); `temperature` (a float: one attempt; a sequence: the
-        ladder), `seed` and the two thresholds of the ladder here are the defaults of every call.  `scoring` (needs token_logprobs=True): score() / score_batch() give the log-probability of transcripts the caller
+        ladder), `seed` and the two thresholds of the ladder here are the defaults of every call.  `best_of` = N in 2 .. max_batch (needs sampling=True; not with bulk=True): Whisper's
+        best_of - every attempt at a temperature above 0 draws N samples and keeps the one with the highest avg_logprob; the N samples are the rows of one forked run
+        (one encoder pass, one prefill) on one further handle per replica; N is the default of the `best_of=` of transcribe / submit / transcribe_batch.  `scoring` (needs token_logprobs=True): score() / score_batch() give the log-probability of transcripts the caller
         brings, in one prefill pass per run on a handle of their own per replica; off, no such handle exists.  `timestamps` (needs scoring=True): align() and
         word_timestamps=True give the time at which every token and word was spoken, from the decoder's attention onto the audio on that scoring handle (DESIGN.md 6.9);
         `grammar` (needs token_logprobs=True; not with bulk=True): requests may be
@@ -318,6 +351,8 @@ class ASRModel:
             raise ValueError("sampling=True needs token_logprobs=True: the sampling kernels are log-probability kernels, and the fallback ladder reads avg_logprob")
         if self.sampling and bool(bulk):
             raise ValueError("sampling is not supported with bulk=True: the bulk pipeline carries no per-request values")
+        self.best_of = check_best_of(best_of, max_batch, self.sampling, bulk)
+        self._max_batch = int(max_batch)
         # grammar: requests may be restricted to the transcripts of a grammar made by compile_grammar() - a phrase list, or any token automaton (grammar.py;
         # DESIGN.md 6.10; engine option of the same name, behind token_logprobs and before the slots exist)
         self.grammar = bool(grammar)
@@ -462,6 +497,11 @@ class ASRModel:
                     s_.set_option("align_head", l * 256 + h)
         self._score_locks = [threading.Lock() for _ in self._score_engines]
         self._score_next = 0
+        # best_of > 1: one further slot per replica, the fork handle, with the model's options - a sampled attempt's N samples are ONE forked run on it (row forks;
+        # DESIGN.md 6.12), driven by a worker thread per replica: submit() never blocks, and the dispatcher's handles and queues are untouched
+        self._fork_engines: List[Engine] = [eng.slot() for eng in self.models] if self.best_of > 1 else []
+        self._fork_workers = [fallback.Retrier(f"sonic-best-of-{i}") for i in range(len(self._fork_engines))]
+        self._fork_next = 0
         self._slot_engines = [[eng.slot() for _ in range(self.slots - 1)] for eng in self.models]     # same weights, further batches in flight
         self._dispatcher = Dispatcher(self.models, slots=self._slot_engines, continuous=self.continuous, decoders=self.decoders or 1,
                                       adaptive_tiles="gemm_small_eff" not in (_options or {}), bulk=self.bulk, native=native_dispatch)
@@ -593,36 +633,115 @@ class ASRModel:
         gram = self._request_grammar(grammar)
         return bias, samp, gram, self._request_draft(draft, max_new, bias, samp, gram)
 
-    def _dispatch(self, windows, prompt, max_new: int, detailed: bool, bias, samp, gram=None, draft=None, **route) -> "Future":
+    def _request_best_of(self, best_of=None) -> int:
+        """One call's best_of: the constructor's N when the call states none.  ValueError naming best_of for a value on a model built without best_of > 1, and for
+        one outside 1 .. max_batch."""
+        N = int(getattr(self, "best_of", 1))
+        if best_of is None:
+            return N
+        if N <= 1:
+            raise ValueError("best_of= needs a model built with best_of > 1, which holds the fork handle (ASRModel(..., token_logprobs=True, sampling=True, best_of=N))")
+        return check_best_of(best_of, self._max_batch)
+
+    def _fork_replica(self, route) -> int:
+        """the replica whose fork handle takes a forked run: where the request is pinned, else its session's home, else the next in turn"""
+        if route.get("replica") is not None:
+            return int(route["replica"])
+        if route.get("session") is not None:
+            return self._dispatcher.home(route["session"])
+        self._fork_next = (self._fork_next + 1) % len(self._fork_engines)
+        return self._fork_next
+
+    def _forked_run(self, replica: int, windows_per_audio, prompts, budgets, biases, grams, temperature: float, seed: int, n: int) -> List[Transcription]:
+        """ONE forked run on the replica's fork handle (the caller is that replica's worker thread): every audio becomes n rows that share its encoder pass and
+        prefill; fork j decodes at `temperature` with seed sampling.fork_seed(seed, j) under the audio's own bias table, grammar and budget.  Per audio the
+        Transcription fallback.pick_best selects, with best_of, fork_index and fork_avg_logprobs filled in."""
+        from . import fallback, sampling as sampling_
+        eng = self._fork_engines[replica]
+        forks = [n] * len(prompts)
+        rows = Engine.fork_rows(forks)
+        samp, bias_rows, gram_rows = [None] * (n * len(prompts)), [None] * (n * len(prompts)), [None] * (n * len(prompts))
+        for a, rr in enumerate(rows):
+            for j, r in enumerate(rr):
+                samp[r] = (temperature, sampling_.fork_seed(seed, j))
+                bias_rows[r] = biases[a] if biases[a] else None
+                gram_rows[r] = None if grams[a] is None else grams[a].on(eng)
+        kw = {}
+        if any(b is not None for b in bias_rows):
+            kw["request_bias"] = bias_rows
+        if any(g is not None for g in gram_rows):
+            kw["request_grammar"] = gram_rows
+        segs, req_win = [], [0]
+        for w in windows_per_audio:
+            segs.extend(w)
+            req_win.append(len(segs))
+        ids, _, lps = eng.transcribe_batch(segs, prompts, budgets, req_win=req_win, want_logprobs=True, request_sampling=samp, forks=forks, **kw)
+        out = []
+        for a, rr in enumerate(rows):
+            trs = [Transcription(self.prompt.decode(ids[r]).strip(), ids[r], lps[r], temperature) for r in rr]
+            avgs = [t.avg_logprob for t in trs]
+            j = fallback.pick_best(avgs)
+            win = trs[j]
+            win.best_of, win.fork_index, win.fork_avg_logprobs = n, j, np.asarray(avgs, np.float64)
+            if grams[a] is not None:
+                win.grammar_status = grams[a].grammar.walk(win.token_ids)
+            out.append(win)
+        return out
+
+    def _forked_post(self, replica: int, *run_args) -> "Future":
+        """_forked_run(replica, ...) on that replica's worker thread -> a future of its list of winners"""
+        out: "Future" = Future()
+
+        def run():
+            if not out.set_running_or_notify_cancel():
+                return
+            try:
+                out.set_result(self._forked_run(replica, *run_args))
+            except BaseException as ex:
+                out.set_exception(ex)
+        self._fork_workers[replica].post(run)
+        return out
+
+    def _forked_attempt(self, windows, prompt, max_new: int, bias, gram, temperature: float, seed: int, n: int, route) -> "Future":
+        """one request's sampled attempt as a forked run of n rows -> a future of the winning Transcription"""
+        runs = self._forked_post(self._fork_replica(route), [windows], [prompt], [max_new], [bias], [gram], float(temperature), seed, n)
+        out: "Future" = Future()
+
+        def done(f):
+            if out.done():
+                return
+            try:
+                out.set_result(f.result()[0])
+            except BaseException as ex:
+                if not out.done():
+                    out.set_exception(ex)
+        runs.add_done_callback(done)
+        out.add_done_callback(lambda f: runs.cancel() if f.cancelled() else None)
+        return out
+
+    def _dispatch(self, windows, prompt, max_new: int, detailed: bool, bias, samp, gram=None, draft=None, best_of: int = 1, **route) -> "Future":
         """One request on the scheduler -> a future of its text (detailed: its Transcription).  samp (from _request_sampling): None, one attempt at a temperature,
         or the fallback ladder - each attempt a new request for the same windows, prompt, table and seed; the future resolves after the last one.  Retries
-        are submitted by the model's worker thread, never by a completion callback and never by the caller (fallback.py)."""
+        are submitted by the model's worker thread, never by a completion callback and never by the caller (fallback.py).  best_of = n > 1 (from
+        _request_best_of): an attempt at a temperature above 0 is ONE forked run of n samples on the replica's fork handle, whose winner stands for the attempt
+        (_forked_run); an attempt at temperature 0 is the one greedy decode it always was."""
         from . import fallback
         kw = dict(route, **reqvalues.submit_keywords(bias, samp, gram, draft))
+        if samp is not None and not samp[1] and best_of > 1 and samp[0][0] > 0:
+            fut = self._forked_attempt(windows, prompt, max_new, bias, gram, samp[0][0], samp[2], best_of, route)
+            return fut if detailed else _only_text(fut)
         if samp is None or not samp[1]:
             return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=detailed, **kw), self.prompt.decode, detailed,
                                 0.0 if samp is None else samp[0][0], grammar=gram, draft=draft)
         ts, _, seed = samp
 
         def one(temperature, seed):
+            if best_of > 1 and temperature > 0:
+                return self._forked_attempt(windows, prompt, max_new, bias, gram, temperature, seed, best_of, route)
             return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=True, sampling=(temperature, seed), **kw), self.prompt.decode, True, temperature, grammar=gram)
         policy = fallback.FallbackPolicy(ts, self.compression_ratio_threshold, self.logprob_threshold)
         fut = fallback.decode_with_fallback(one, policy, seed, retrier=self._retrier)
-        if detailed:
-            return fut
-        out: "Future[str]" = Future()
-
-        def done(f):
-            if out.done():
-                return
-            try:
-                out.set_result(f.result().text)
-            except BaseException as ex:
-                if not out.done():
-                    out.set_exception(ex)
-        fut.add_done_callback(done)
-        out.add_done_callback(lambda f: fut.cancel() if f.cancelled() else None)
-        return out
+        return fut if detailed else _only_text(fut)
 
     def _check_detailed(self, detailed: bool):
         if detailed and not getattr(self, "token_logprobs", False):
@@ -630,7 +749,7 @@ class ASRModel:
 
     def submit(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None,
                session: Optional[str] = None, detailed: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
-               temperature=None, seed: Optional[int] = None, word_timestamps: bool = False, grammar=None, draft=None) -> "Future[str]":
+               temperature=None, seed: Optional[int] = None, word_timestamps: bool = False, grammar=None, draft=None, best_of: Optional[int] = None) -> "Future[str]":
         """Non-blocking form of transcribe(): queues the request on a replica and returns a Future of the transcript.  `session`
         (e.g. the WebSocket client id) keeps a session's decodes on one GPU.  detailed (a model built with token_logprobs=True): the future
         gives a Transcription - text, token_ids, token_logprobs, avg_logprob - instead of the text.  sequence_bias / bad_words_ids / hotword_boost (a model
@@ -639,16 +758,19 @@ class ASRModel:
         thread never waits for one (_dispatch).  grammar (a model built with grammar=True): what compile_grammar() returned - the transcript is one of its paths;
         a detailed result carries `grammar_status`.  draft (a model built with draft_verify=True): what the transcript is expected to begin with, a string or token
         ids - cut here in front of its first EOS id and at max_new_tokens - 1; the result is the model's own greedy transcript whatever the draft says, a detailed one
-        carries `draft_len` and `draft_matched`.  Not with bias values, a temperature > 0 or a grammar (ValueError)."""
+        carries `draft_len` and `draft_matched`.  Not with bias values, a temperature > 0 or a grammar (ValueError).  best_of (a model built with
+        best_of > 1; default: the constructor's): the samples of every attempt at a temperature above 0, drawn in one forked run; a detailed result carries
+        `best_of`, `fork_index` and `fork_avg_logprobs`."""
         if not hasattr(self, "model"):
             raise RuntimeError("ASR model has been released")
         if word_timestamps:
             raise ValueError("word_timestamps is not supported on submit() / transcribe_async() / stream decodes: align a finished transcript with ASRModel.align(), or use transcribe(..., word_timestamps=True)")
         self._check_detailed(detailed)
+        n_best = self._request_best_of(best_of)
         values = self._request_values(hotwords, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, grammar, draft, int(max_new_tokens))
         pcm, windows, n_audio = self._prepare(audio_tensor, sampling_rate)
         prompt = self.prompt.build(frontend.build_instruction(hotwords), n_audio)
-        return self._dispatch(windows, prompt, int(max_new_tokens), detailed, *values, session=session)
+        return self._dispatch(windows, prompt, int(max_new_tokens), detailed, *values, best_of=n_best, session=session)
 
     def open_stream(self, session: str, buffer_seconds: float = 30.0, margin_seconds: float = 10.0, sampling_rate: int = 16000) -> AudioStream:
         """A streaming session whose audio stays on the device (config.py:25 MAX_AUDIO_BUFFER_SECONDS = 30): chunks are appended to a
@@ -663,16 +785,17 @@ class ASRModel:
     async def transcribe_async(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128,
                                hotwords: Optional[List[str]] = None, session: Optional[str] = None, detailed: bool = False,
                                sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None, seed: Optional[int] = None,
-                               word_timestamps: bool = False, grammar=None, draft=None) -> str:
+                               word_timestamps: bool = False, grammar=None, draft=None, best_of: Optional[int] = None) -> str:
         """Awaitable transcribe() for the asyncio callers (connection_manager.py:127-245): the event loop is not blocked while the
         device works, so all sessions' partial and final decodes can be in flight (and batched) together."""
-        return await asyncio.wrap_future(self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, session, detailed, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, word_timestamps, grammar, draft))
+        return await asyncio.wrap_future(self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, session, detailed, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, word_timestamps, grammar, draft, best_of))
 
     def transcribe(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128,
                    hotwords: Optional[List[str]] = None, return_debug_info: bool = False,
                    sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None, seed: Optional[int] = None,
-                   word_timestamps: bool = False, grammar=None, draft=None) -> Union[str, Dict[str, Any]]:
-        """draft (a model built with draft_verify=True): see submit(); the debug dictionary gains `draft_len` and `draft_matched`.
+                   word_timestamps: bool = False, grammar=None, draft=None, best_of: Optional[int] = None) -> Union[str, Dict[str, Any]]:
+        """best_of (a model built with best_of > 1): see submit(); the debug dictionary gains `best_of` and `fork_index`.
+        draft (a model built with draft_verify=True): see submit(); the debug dictionary gains `draft_len` and `draft_matched`.
         grammar (a model built with grammar=True): what compile_grammar() returned; the debug dictionary gains `grammar_status` (grammar.Grammar.walk over
         the returned ids: "accepted", "incomplete" at a budget that ended inside the grammar, "left").
         word_timestamps (a model built with timestamps=True): the request is decoded as always, then its tokens are aligned on the scoring
@@ -686,7 +809,7 @@ class ASRModel:
         try:
             want = bool((return_debug_info or word_timestamps) and getattr(self, "token_logprobs", False))
             res = self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, detailed=want, sequence_bias=sequence_bias, bad_words_ids=bad_words_ids,
-                              hotword_boost=hotword_boost, temperature=temperature, seed=seed, grammar=grammar, draft=draft).result()
+                              hotword_boost=hotword_boost, temperature=temperature, seed=seed, grammar=grammar, draft=draft, best_of=best_of).result()
             det, transcript = (res, res.text) if want else (None, res)
             if word_timestamps:
                 self._attach_alignment([audio_tensor], [det], sampling_rate, hotwords)
@@ -704,6 +827,8 @@ class ASRModel:
                         info.update({"top_token_ids": det.top_token_ids, "top_logprobs": det.top_logprobs})
                     if getattr(self, "sampling", False):             # a sampling model: what the transcript was decoded at, and the ladder's other measure
                         info.update({"temperature": det.temperature, "compression_ratio": det.compression_ratio})
+                    if getattr(self, "best_of", 1) > 1:              # a best_of model: how many samples the returned attempt drew, and which of them this is
+                        info.update({"best_of": det.best_of, "fork_index": det.fork_index})
                     if grammar is not None:
                         info["grammar_status"] = det.grammar_status
                     if draft is not None:
@@ -722,12 +847,15 @@ class ASRModel:
 
     def transcribe_batch(self, audios: Sequence[Any], sampling_rate: int = 16000, max_new_tokens: Union[int, Sequence[int]] = 128,
                          hotwords: Optional[List[str]] = None, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
-                         temperature=None, seed: Optional[int] = None, word_timestamps: bool = False, grammar=None, drafts=None) -> List[str]:
+                         temperature=None, seed: Optional[int] = None, word_timestamps: bool = False, grammar=None, drafts=None, best_of: Optional[int] = None) -> List[str]:
         """Batched extension (the reference is B=1 per call): one device batch, per-segment results identical to transcribe().  temperature / seed: every
         segment is decoded with them (a sequence: every segment goes down its own ladder, as independent requests on the scheduler).  word_timestamps (a model
         built with timestamps=True): every audio is decoded as its own request, then all are aligned together; the result is a list of Transcription.
         grammar (a model built with grammar=True): one compile_grammar() result for every audio, or a sequence with one (or None) per audio.
-        drafts (a model built with draft_verify=True): one draft (a string, token ids or None) per audio; see submit()."""
+        drafts (a model built with draft_verify=True): one draft (a string, token ids or None) per audio; see submit().
+        best_of (a model built with best_of > 1; default: the constructor's): at one temperature above 0, floor(max_batch / best_of) audios share a forked run on
+        the fork handle and every audio's winner is returned - what transcribe() returns for it; a ladder takes every audio down its own, forked rung by rung."""
+        n_best = self._request_best_of(best_of)
         if drafts is not None and len(drafts) != len(audios):
             raise ValueError(f"{len(audios)} audios but {len(drafts)} drafts")
         grams = list(grammar) if isinstance(grammar, (list, tuple)) else [grammar] * len(audios)
@@ -738,7 +866,7 @@ class ASRModel:
             self._check_timestamps()
             mn_ = [int(max_new_tokens)] * len(audios) if isinstance(max_new_tokens, int) else [int(x) for x in max_new_tokens]
             futs_ = [self.submit(a, sampling_rate, mn_[i], hotwords, detailed=True, sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotword_boost=hotword_boost,
-                                 temperature=temperature, seed=seed, grammar=grams[i], draft=None if drafts is None else drafts[i]) for i, a in enumerate(audios)]
+                                 temperature=temperature, seed=seed, grammar=grams[i], draft=None if drafts is None else drafts[i], best_of=best_of) for i, a in enumerate(audios)]
             dets = [f.result() for f in futs_]
             self._attach_alignment(list(audios), dets, sampling_rate, hotwords)
             return dets
@@ -753,8 +881,17 @@ class ASRModel:
             req_win.append(len(segs))
             prompts.append(self.prompt.build(instruction, n_audio))
         if samp is not None and samp[1]:
-            futs = [self._dispatch(segs[req_win[i]:req_win[i + 1]], prompts[i], mn[i], False, bias, samp, grams[i], draft=drs[i]) for i in range(len(audios))]
+            futs = [self._dispatch(segs[req_win[i]:req_win[i + 1]], prompts[i], mn[i], False, bias, samp, grams[i], draft=drs[i], best_of=n_best) for i in range(len(audios))]
             return [f.result() for f in futs]
+        if samp is not None and n_best > 1 and samp[0][0] > 0:
+            # one temperature above 0: floor(max_batch / best_of) audios per forked run, the runs spread over the replicas' fork handles in turn
+            per = max(1, self._max_batch // n_best)
+            runs = []
+            for g0 in range(0, len(audios), per):
+                g = range(g0, min(g0 + per, len(audios)))
+                runs.append(self._forked_post(self._fork_replica({}), [segs[req_win[i]:req_win[i + 1]] for i in g], [prompts[i] for i in g], [mn[i] for i in g],
+                                              [bias] * len(g), [grams[i] for i in g], samp[0][0], samp[2], n_best))
+            return [t.text for r in runs for t in r.result()]
         subs = [reqvalues.submit_keywords(bias, samp, grams[i], drs[i]) for i in range(len(audios))]
         if len(self.models) == 1 and not self.continuous:
             # one engine call: a value that some audio brings becomes its keyword's list, None for the audios without it
@@ -934,6 +1071,7 @@ class ASRModel:
         info["scoring"] = bool(self.__dict__.get("scoring", False))
         info["grammar"] = bool(self.__dict__.get("grammar", False))
         info["draft_verify"] = bool(self.__dict__.get("draft_verify", False))
+        info["best_of"] = int(self.__dict__.get("best_of", 1))
         info["timestamps"] = bool(self.__dict__.get("timestamps", False))
         g = self.__dict__.get("generation_guards")
         if g is not None:                            # the logits processors in force: the checkpoint's generation_config.json unless the constructor overrode it
@@ -944,6 +1082,8 @@ class ASRModel:
         r = self.__dict__.pop("_retrier", None)
         if r is not None:
             r.close()
+        for w in self.__dict__.pop("_fork_workers", []):      # (a posted run completes first: the worker leaves behind it)
+            w.close()
         c = self.__dict__.pop("_dispatcher", None)
         if c is not None:
             c.close()
@@ -956,6 +1096,7 @@ class ASRModel:
         self.__dict__.pop("model", None)
         self.__dict__.pop("_slot_engines", None)
         self.__dict__.pop("_score_engines", None)
+        self.__dict__.pop("_fork_engines", None)
         for m in self.__dict__.pop("models", []):
             m.close()                                # (an engine closes its slots first)
         if err is not None:

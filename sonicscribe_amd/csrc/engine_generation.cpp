@@ -94,8 +94,10 @@ template <typename W> static int stage_enable(sonic_engine* e, ReqStage<W>& s, i
 template <typename W> static int stage_open(sonic_engine* e, ReqStage<W>& s) { if (s.busy) { HIPC(e, hipEventSynchronize(s.ev)); s.busy = false; } return SONIC_OK; }
 template <typename W> static int stage_sent(sonic_engine* e, ReqStage<W>& s) { HIPC(e, hipEventRecord(s.ev, e->st)); s.busy = true; s.take = false; return SONIC_OK; }
 template <typename W> static void stage_free(ReqStage<W>& s) { if (s.host) (void)hipHostFree(s.host); if (s.ev) (void)hipEventDestroy(s.ev); }
-static int stage_count(sonic_engine* e, int got, int R, const char* setter, const char* what) {
-    return got >= 0 && got != R ? fail(e, SONIC_ERR_INVALID, "%s gave %s for %d requests, the batch has %d", setter, what, got, R) : SONIC_OK;
+static int stage_count(sonic_engine* e, int got, int R, const char* setter, const char* what, bool forked = false) {
+    if (got < 0 || got == R) return SONIC_OK;
+    if (forked) return fail(e, SONIC_ERR_INVALID, "request_forks: %s gave %s for %d rows, the forked batch has %d (per-request values are stated per row, in row order)", setter, what, got, R);
+    return fail(e, SONIC_ERR_INVALID, "%s gave %s for %d requests, the batch has %d", setter, what, got, R);
 }
 // What both setters open with: refused during an asynchronous run (without waiting for the engine lock that run holds), then the lock (`lk`), then refused while
 // the option `opt` (flag `on`) is off.  From here on nothing is pending
@@ -543,6 +545,45 @@ extern "C" int engine_take_dispatch_draft(const int32_t** ids) {
     return (int)g_dispatch_draft.size();
 }
 extern "C" int engine_tok_cap(sonic_engine* e) { return e ? e->tok_cap : 0; }
+// ---- row forks (include/sonic_hip.h beside sonic_load_tensor): one prefilled request becomes several rows - Whisper's best_of draws its N samples
+// from one encoder pass and one prefill.  No option and no buffer: the counts are staged as a draft's words are, and consumed or dropped with them.
+// sonic_load_tensor(e, "request_forks", counts, SONIC_DTYPE_I32, {A}, 1): request a of the next prefill on this handle (the entry points of sonic_set_request_bias)
+// becomes counts[a] >= 1 rows.  Refused by name on the int8 and fp32 kinds and on a scoring handle, for a count below 1 and for more rows than the handle has
+int fork_stage_counts(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim) {
+    { std::lock_guard<std::mutex> ak(e->a_mu); if (e->a_pending || e->a_running) return fail(nullptr, SONIC_ERR_INVALID, "request_forks: an asynchronous run of this handle is in flight"); }
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipGetLastError();
+    e->fork_pending = -1;
+    if (e->i8) return fail(e, SONIC_ERR_INVALID, "request_forks: the int8 kind refuses it (its decode step keeps quantised rows and outlier lists per row that the prefill's head leaves for the sources alone)");
+    if (e->f32) return fail(e, SONIC_ERR_INVALID, "request_forks: the fp32 test kind has no fork kernel; use a bf16 or fp16 handle");
+    if (e->opt_forced_parallel) return fail(e, SONIC_ERR_INVALID, "request_forks: option forced_parallel is on: a scoring handle decodes nothing a fork could sample");
+    if (dtype != SONIC_DTYPE_I32 || ndim != 1 || shape[0] < 1) return fail(e, SONIC_ERR_INVALID, "request_forks: the counts are one row of int32 words, one per request (SONIC_DTYPE_I32, ndim 1)");
+    const int64_t A = shape[0]; const int* w = (const int*)data;
+    if (A > e->Bm || A > 64) return fail(e, SONIC_ERR_INVALID, "request_forks: %lld requests (1 .. %d)", (long long)A, e->Bm);
+    long rows = 0;
+    for (int a = 0; a < (int)A; ++a) {
+        if (w[a] < 1) return fail(e, SONIC_ERR_INVALID, "request_forks: request %d has a fork count of %d (at least 1: the request itself)", a, w[a]);
+        rows += w[a];
+    }
+    if (rows > e->Bm || rows > 64) return fail(e, SONIC_ERR_INVALID, "request_forks: the counts add up to %ld rows, the handle has %d (max_batch)", rows, e->Bm);
+    e->fork_stage.assign(w, w + A);
+    e->fork_pending = (int)A;
+    return SONIC_OK;
+}
+int fork_claim(sonic_engine* e, int R, std::vector<int>& fork_src) {
+    fork_src.clear();
+    const int A = e->fork_pending.exchange(-1);
+    if (A < 0) return SONIC_OK;
+    if (A != R) return fail(e, SONIC_ERR_INVALID, "request_forks: the counts were given for %d requests, the batch has %d", A, R);
+    if (e->force_d) return fail(e, SONIC_ERR_INVALID, "request_forks: forced ids are set on this handle (sonic_set_forced_ids): teacher forcing decides every token, forks would all be the same row");
+    int rows = 0;
+    for (int a = 0; a < A; ++a) rows += e->fork_stage[a];
+    if (rows == A) return SONIC_OK;                          // every count 1: the prefill of today
+    for (int a = 0; a < A; ++a) fork_src.push_back(a);
+    for (int a = 0; a < A; ++a) for (int j = 1; j < e->fork_stage[a]; ++j) fork_src.push_back(a);
+    return SONIC_OK;
+}
+
 extern "C" int engine_draft_verify_on(sonic_engine* e) { return e && e->opt_draft_verify ? 1 : 0; }      // (pipeline.cpp too: the bulk pipeline refuses such a handle)
 
 // HF generate()'s logits processors for greedy decoding, as the checkpoint's generation_config.json (or the caller) sets them: repetition_penalty (1.0 = none),
@@ -572,14 +613,15 @@ extern "C" int sonic_get_generation(sonic_engine* e, float* repetition_penalty, 
 
 // ---- the stages at every point of a request's life.  Each function below names bias, samp and gram once, in that order; no other unit names them together.  (No
 // descriptor table: the stages' words differ in type - int, unsigned, 64-bit - so a table would erase the types to save one line in three per function.)
-int req_claim(sonic_engine* e, int R) {
+int req_claim(sonic_engine* e, int R, bool forked) {
     const int bias_R = e->bias.claim(), samp_R = e->samp.claim(), gram_R = e->gram.claim();
-    TRY(stage_count(e, bias_R, R, "sonic_set_request_bias", "tables"));
-    TRY(stage_count(e, samp_R, R, "sonic_set_request_sampling", "values"));
-    TRY(stage_count(e, gram_R, R, "option request_grammar_begin", "grammars"));
+    TRY(stage_count(e, bias_R, R, "sonic_set_request_bias", "tables", forked));
+    TRY(stage_count(e, samp_R, R, "sonic_set_request_sampling", "values", forked));
+    TRY(stage_count(e, gram_R, R, "option request_grammar_begin", "grammars", forked));
     e->bias.take = bias_R >= 0; e->samp.take = samp_R >= 0; e->gram.take = gram_R >= 0;      // (read by req_upload alone, which only a prefill that got past this reaches)
     const int draft_R = e->draft_pending.exchange(-1);      // the drafts (option draft_verify) are no stage - their words become part of the prefill's plan - but are claimed and dropped with them
     e->draft_take = false;
+    if (forked && draft_R >= 0) return fail(e, SONIC_ERR_INVALID, "request_forks: the same prefill was given drafts (sonic_load_tensor \"request_draft\"): a drafted request takes its first tokens from the verify pass, its forks would have none to share");
     TRY(stage_count(e, draft_R, R, "sonic_load_tensor \"request_draft\"", "drafts"));
     e->draft_take = draft_R >= 0;
     return SONIC_OK;
@@ -588,9 +630,10 @@ const char* req_claim_none(sonic_engine* e) {
     const int bias_R = e->bias.claim(), samp_R = e->samp.claim(), gram_R = e->gram.claim();      // (claim leaves `take` false: the run's upload writes the neutral values)
     if (gram_R >= 0) gram_drop_staged(e);
     e->draft_pending = -1; e->draft_take = false;      // (the option is refused on a scoring handle: nothing can be staged)
+    e->fork_pending = -1;                              // (fork counts likewise)
     return bias_R >= 0 ? "request bias tables (sonic_set_request_bias)" : samp_R >= 0 ? "sampling values (sonic_set_request_sampling)" : gram_R >= 0 ? "grammars (option request_grammar)" : nullptr;
 }
-void req_drop_pending(sonic_engine* e) { e->bias.pending = -1; e->samp.pending = -1; if (e->opt_grammar) gram_drop_staged(e); e->draft_pending = -1; }
+void req_drop_pending(sonic_engine* e) { e->bias.pending = -1; e->samp.pending = -1; if (e->opt_grammar) gram_drop_staged(e); e->draft_pending = -1; e->fork_pending = -1; }
 int req_upload(sonic_engine* e, int R) {      // (in this order: the copies and fills go onto the stream in it)
     TRY(bias_upload(e, R));                   // every request's table, or a zero count, into its row
     TRY(gram_upload(e, R));                   // every request's grammar at its start node, or a free row
@@ -663,4 +706,5 @@ void gen_release(sonic_engine* e) {
     e->grammars.clear();
     stage_free(e->bias); stage_free(e->samp); stage_free(e->gram);
     for (int i = 0; i < 2; ++i) if (e->draft_plan_h[i]) (void)hipHostFree(e->draft_plan_h[i]);
+    for (int i = 0; i < 2; ++i) if (e->fork_ev[i]) (void)hipEventDestroy(e->fork_ev[i]);
 }

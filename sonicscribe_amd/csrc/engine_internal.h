@@ -246,6 +246,12 @@ struct sonic_engine {
     std::vector<int> draft_stage; std::atomic<int> draft_pending{-1}; bool draft_take = false;
     int* draft_plan_d = nullptr; int* draft_plan_h[2] = {nullptr, nullptr}; int* ver_tok = nullptr; float* ver_rec = nullptr; int ver_rec_w = 0; int* draft_acc = nullptr;
     int draft_last_S = 0;
+    // row forks (sonic_load_tensor "request_forks"; fork.hip): request a of the next prefill becomes fork_stage[a] >= 1 rows that share its prefill -
+    // the sources are rows 0 .. A-1, the further forks follow behind them request by request; fork_kv_kernel copies a source's K / V (and history) to its forks behind
+    // the last decoder layer, the head then runs over all the rows.  fork_pending = the staged A (-1: none), claimed and dropped as a draft is; no option, no buffer.
+    // fork_ev: the kernel's bracket in the last forked prefill (fork_timed; sonic_debug_read "fork_ms")
+    std::vector<int> fork_stage; std::atomic<int> fork_pending{-1};
+    hipEvent_t fork_ev[2] = {nullptr, nullptr}; bool fork_timed = false;
     uint64_t spliced = 0;          // rows of the last prefill that sonic_splice_rows handed to a continuous loop (bit r = request r); cleared by every prefill (gen_busy)
     long long* kt = nullptr; int kt_layer = -1;     // diagnostics ("ktrace" option): in-kernel timestamps of one decoder layer's kernels
     int* ring_peak = nullptr;                        // [Bm] per-request max |s| of a ring-staged batch (ingest.hip)
@@ -274,6 +280,8 @@ struct HostPlan {
     int n_tok = 0, max_p = 0, max_steps = 0;
     // option draft_verify: the S verify rows of the batch's drafts (draft_plan_d's layout: 5 x S words, then 4 x 64); S = 0: an ordinary prefill
     std::vector<int> draft; int S = 0;
+    // row forks: the rows of the run (0: the requests are the rows), then per row the request it shares its prefill with (rows 0 .. R-1: themselves)
+    int rows = 0; std::vector<int> fork_src;
 };
 
 #define HIPC(e, call)                                                                                      \
@@ -438,7 +446,7 @@ struct SpliceArgs {
 };
 // The per-request stages (bias, samp, gram) at every point of a request's life, one function per point: the stages are listed in these functions and nowhere else.
 // The caller holds the lock (both locks: the splice)
-int req_claim(sonic_engine* e, int R);              // a prefill begins: it consumes what the setters left; SONIC_ERR_INVALID when a setter was given another count than the batch's R
+int req_claim(sonic_engine* e, int R, bool forked = false);   // a prefill begins: it consumes what the setters left; SONIC_ERR_INVALID when a setter was given another count than the batch's R (forked: R counts rows, and a draft is refused)
 const char* req_claim_none(sonic_engine* e);        // ... a run that applies no processors: consumed all the same; names what was staged (NULL: nothing was)
 int req_upload(sonic_engine* e, int R);             // the prefill's part: the claimed values, or the neutral ones, into the rows' words, on the stream
 void req_greedy_args(const sonic_engine* e, GreedyArgs& g);   // the rows' words into the greedy launch (g.out_lp and g.hist are set)
@@ -458,6 +466,12 @@ int draft_extend(sonic_engine* e, int R, const int32_t* prompt_ids, const int64_
                  std::vector<int32_t>& ids, std::vector<int64_t>& off, std::vector<int32_t>& left, std::vector<int>& dlen);
 int draft_dispatch_arm(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim);   // sonic_load_tensor "draft.dispatch" (no engine lock): the calling thread's next sonic_dispatch_submit* carries the draft
 int draft_alloc(sonic_engine* e);                   // the buffers, at the handle's first drafted prefill (and ver_rec again when top_logprobs has changed since)
+// row forks (sonic_load_tensor "request_forks")
+int fork_stage_counts(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim);   // the fork counts of the next prefill's requests
+// a prefill begins (ahead of req_claim, which then counts rows): the staged counts are consumed - checked against the batch's R requests (SONIC_ERR_INVALID naming
+// request_forks) and returned as the row -> request map (empty: no counts, or all of them 1 - the prefill of today)
+int fork_claim(sonic_engine* e, int R, std::vector<int>& fork_src);
+ForkArgs fork_args(sonic_engine* e, int R, const std::vector<int>& fork_src);      // the copy's one descriptor (run_prefill)
 int score_logits_alloc(sonic_engine* e);            // the chunk's logits [score_chunk_rows][vocab] the parallel forced run and the verify pass share (engine_stages.cpp)
 int gen_inherit(sonic_engine* e, const sonic_engine* root);   // sonic_slot_create: the owner's generation options (token_logprobs .. forced_align) onto the new slot, with their buffers
 void gen_release(sonic_engine* e);                  // sonic_destroy: the stages' pinned mirrors and events, the grammar references this handle holds, an owner's grammars

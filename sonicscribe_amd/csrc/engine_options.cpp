@@ -197,14 +197,18 @@ extern "C" int sonic_set_option(sonic_engine* e, const char* key, int value) {
 }
 
 // The buffers sonic_debug_read serves, one row each: the name, the elements it holds, and where it lives on a 16-bit handle and on the fp32 kind (null: that kind
-// has no such buffer).  prefill_tap is the one row with an index: tap `index` of the taps option prefill_taps recorded
+// has no such buffer).  Rows with an index (n_idx: how many the buffer holds, each `cap` elements): prefill_tap - tap `index` of the taps option prefill_taps
+// recorded - and kcache / vcache - decoder layer `index` of the KV cache, [Bm][Hkv][max_ctx][head_dim]
 struct DbgRow { const char* name; size_t (*cap)(const sonic_engine*); const bf16_t* (*src16)(const sonic_engine*); const float* (*src32)(const sonic_engine*);
-                const float* (*f32_on_16)(const sonic_engine*) = nullptr; };      // f32_on_16: a buffer that is fp32 on a 16-bit handle too (read as it is)
+                const float* (*f32_on_16)(const sonic_engine*) = nullptr;         // f32_on_16: a buffer that is fp32 on a 16-bit handle too (read as it is)
+                int (*n_idx)(const sonic_engine*) = nullptr; };
 #define CAP(x) [](const sonic_engine* e) -> size_t { return x; }
 #define S16(m) [](const sonic_engine* e) -> const bf16_t* { return e->m; }
 #define S32(m) [](const sonic_engine* e) -> const float* { return e->f->m; }
 static const DbgRow DEBUG_BUFS[] = {
-    {"prefill_tap", CAP((size_t)e->tok_cap * e->d.dec_d), S16(taps), [](const sonic_engine* e) -> const float* { return (const float*)e->taps; }},
+    {"prefill_tap", CAP((size_t)e->tok_cap * e->d.dec_d), S16(taps), [](const sonic_engine* e) -> const float* { return (const float*)e->taps; }, nullptr, [](const sonic_engine* e) -> int { return e->d.dec_layers + 1; }},
+    {"kcache", CAP((size_t)e->Bm * e->d.dec_kv_heads * e->max_ctx * e->d.dec_head_dim), S16(Kc), nullptr, nullptr, [](const sonic_engine* e) -> int { return e->d.dec_layers; }},
+    {"vcache", CAP((size_t)e->Bm * e->d.dec_kv_heads * e->max_ctx * e->d.dec_head_dim), S16(Vc), nullptr, nullptr, [](const sonic_engine* e) -> int { return e->d.dec_layers; }},
     {"pe", CAP((size_t)e->Bm * e->Ta * e->d.dec_d), S16(pe), S32(pe)},
     {"dx", CAP((size_t)e->tok_cap * e->d.dec_d), S16(dx), S32(dx)},
     {"dqkv", CAP((size_t)e->tok_cap * e->qkvN), S16(dqkv), nullptr},
@@ -237,11 +241,18 @@ extern "C" int sonic_debug_read(sonic_engine* e, const char* name, int index, fl
         for (int64_t i = 0; i < n; ++i) out[i] = (float)acc[i];
         return SONIC_OK;
     }
+    if (!strcmp(name, "fork_ms")) {                 // fork_kv_kernel's time in the handle's last forked prefill, from the events around it; 0 behind an unforked one
+        if (n != 1) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
+        out[0] = 0.f;
+        if (e->fork_timed) { HIPC(e, stream_sync(e)); HIPC(e, hipEventElapsedTime(&out[0], e->fork_ev[0], e->fork_ev[1])); }
+        return SONIC_OK;
+    }
     for (const DbgRow& r : DEBUG_BUFS) {
         if (strcmp(name, r.name) || !(e->f32 ? (bool)r.src32 : (r.src16 || r.f32_on_16))) continue;
         const bool tap = &r == &DEBUG_BUFS[0];
         if (tap && !e->taps) return fail(e, SONIC_ERR_INVALID, "no taps recorded");
-        const size_t cap = r.cap(e), off = tap ? (size_t)index * cap : 0;
+        if (r.n_idx && (index < 0 || index >= r.n_idx(e))) return fail(e, SONIC_ERR_INVALID, "index %d out of range for buffer %s (0 .. %d)", index, name, r.n_idx(e) - 1);
+        const size_t cap = r.cap(e), off = r.n_idx ? (size_t)index * cap : 0;
         if (n < 0 || (size_t)n > cap) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
         if (!e->f32 && r.f32_on_16) { HIPC(e, stream_sync(e)); if (n > 0) HIPC(e, d2h(e, out, r.f32_on_16(e), (size_t)n * 4)); return SONIC_OK; }
         if (!e->f32) return read_back_16(e, r.src16(e) + off, out, (size_t)n);

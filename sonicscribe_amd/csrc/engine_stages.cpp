@@ -500,9 +500,18 @@ int upload_plan(sonic_engine* e, int R, const HostPlan& hp) {
         o += n; return r;
     };
     HIPC(e, put(e->src, hp.src.data(), M)); HIPC(e, put(e->tok_seq, hp.tok_seq.data(), M)); HIPC(e, put(e->tok_pos_pf, hp.tok_pos.data(), M));
-    HIPC(e, put(e->q_off, hp.q_off.data(), (size_t)R)); HIPC(e, put(e->q_len, hp.q_len.data(), (size_t)R)); HIPC(e, put(e->kv_len, hp.q_len.data(), (size_t)R));
-    HIPC(e, put(e->last_row, hp.last_row.data(), (size_t)R)); HIPC(e, put(e->max_new_d, hp.max_new.data(), (size_t)R));
-    HIPC(e, put(e->n_active, &R, 1));
+    HIPC(e, put(e->q_off, hp.q_off.data(), (size_t)R)); HIPC(e, put(e->q_len, hp.q_len.data(), (size_t)R));
+    if (hp.rows > R) {      // row forks: the greedy loop's words for all the rows - a fork's are those of the request it shares its prefill with
+        const int Rr = hp.rows;
+        std::vector<int> kv((size_t)Rr), last((size_t)Rr), mn((size_t)Rr);
+        for (int r = 0; r < Rr; ++r) { const int a = hp.fork_src[r]; kv[r] = hp.q_len[a]; last[r] = hp.last_row[a]; mn[r] = hp.max_new[a]; }
+        HIPC(e, put(e->kv_len, kv.data(), (size_t)Rr)); HIPC(e, put(e->last_row, last.data(), (size_t)Rr)); HIPC(e, put(e->max_new_d, mn.data(), (size_t)Rr));
+        HIPC(e, put(e->n_active, &Rr, 1));
+    } else {
+        HIPC(e, put(e->kv_len, hp.q_len.data(), (size_t)R));
+        HIPC(e, put(e->last_row, hp.last_row.data(), (size_t)R)); HIPC(e, put(e->max_new_d, hp.max_new.data(), (size_t)R));
+        HIPC(e, put(e->n_active, &R, 1));
+    }
     if (hp.S > 0) {      // option draft_verify: the verify rows' plan, through the pinned mirror that belongs to this staging buffer
         int* dh = e->draft_plan_h[e->plan_idx];
         memcpy(dh, hp.draft.data(), hp.draft.size() * 4);
@@ -551,13 +560,28 @@ static void run_draft_verify(sonic_engine* e, int R, const HostPlan& hp) {
     launch_draft_accept(da, R, e->st);
 }
 
+// Row forks: fork_kv_kernel's descriptor from the row -> request map of a forked prefill - per forked request its row, its first fork's row and
+// its forks' count (the forks of a request are consecutive rows).  The map comes from fork_claim, which has checked the rows against the handle's
+ForkArgs fork_args(sonic_engine* e, int R, const std::vector<int>& fork_src) {
+    const sonic_dims& d = e->d;
+    ForkArgs a{};
+    a.Kc = e->Kc; a.Vc = e->Vc; a.layers = d.dec_layers; a.Bm = e->Bm; a.Hkv = d.dec_kv_heads; a.ctx = e->max_ctx; a.hd = d.dec_head_dim;
+    a.kv_len = e->kv_len; a.hist = hist_on(e) ? e->hist : nullptr;
+    for (int r = R; r < (int)fork_src.size() && r < e->Bm; ++r) {
+        if (a.n_src > 0 && a.src[a.n_src - 1] == fork_src[r]) { a.cnt[a.n_src - 1] += 1; continue; }
+        a.src[a.n_src] = fork_src[r]; a.first[a.n_src] = r; a.cnt[a.n_src] = 1; a.n_src += 1;
+    }
+    return a;
+}
+
 // head = false (the parallel forced run): the decoder layers only - its score rows are normalised and multiplied by run_forced_parallel
 static int run_prefill(sonic_engine* e, int R, const HostPlan& hp, bool head = true) {
     const sonic_dims& d = e->d;
     const int D = d.dec_d, M = hp.n_tok, dt = e->dt;
     const QGroup grp{e->tok_seq, 1, R};        // one reference call = the prompt rows of one request
+    const int Rr = hp.rows > R ? hp.rows : R;      // row forks: the rows of the run; the decoder layers below run over the R requests
     TRY(upload_plan(e, R, hp));
-    TRY(reset_row_state(e, R, M));
+    TRY(reset_row_state(e, Rr, M));
     launch_assemble_embeds(e->src, e->embed, e->pe, e->dx, M, D, e->st);
     e->last_ntok = M;
     if (e->taps_on) {
@@ -596,9 +620,15 @@ static int run_prefill(sonic_engine* e, int R, const HostPlan& hp, bool head = t
     }
     if (!head) return SONIC_OK;
     if (hp.S > 0) run_draft_verify(e, R, hp);      // option draft_verify: the rows' state becomes that of a prefill of prompt || accepted draft, last_row included
-    // logits only for the last prompt position of each request (logits_to_keep=1, generation/utils.py:2612-2616)
-    launch_rmsnorm(e->dx, e->dec_nw, e->shn, R, D, d.dec_rms_eps, e->last_row, e->st, dt);
-    skinny(e, e->shn, D, e->embed_t, e->lslab, R, d.vocab, D, nullptr);
+    if (Rr > R) {      // row forks: every forked request's K / V (and history) into its forks' rows, once, ahead of the head
+        const ForkArgs fa = fork_args(e, R, hp.fork_src);
+        if (e->fork_ev[0]) (void)hipEventRecord(e->fork_ev[0], e->st);
+        launch_fork_kv(fa, hp.max_p, e->st);
+        if (e->fork_ev[1]) { (void)hipEventRecord(e->fork_ev[1], e->st); e->fork_timed = true; }
+    }
+    // logits only for the last prompt position of each request (logits_to_keep=1, generation/utils.py:2612-2616); a fork's row reads its request's position (last_row)
+    launch_rmsnorm(e->dx, e->dec_nw, e->shn, Rr, D, d.dec_rms_eps, e->last_row, e->st, dt);
+    skinny(e, e->shn, D, e->embed_t, e->lslab, Rr, d.vocab, D, nullptr);
     return SONIC_OK;
 }
 
@@ -613,7 +643,10 @@ int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int
         HIPC(e, hipStreamWaitEvent(e->st, e->wait_ev, 0));  // engine's KV cache and row state, which this run is about to overwrite
         e->wait_pending = false;
     }
-    TRY(req_claim(e, R));      // sonic_set_request_bias / _sampling / option request_grammar: this batch consumes what they left whatever becomes of it (ENTER_CONSUME drops it on every other exit)
+    std::vector<int> fork_src;      // row forks (sonic_load_tensor "request_forks"): the row -> request map of a forked batch (empty: the requests are the rows)
+    TRY(fork_claim(e, R, fork_src));
+    const int Rr = fork_src.empty() ? R : (int)fork_src.size();      // the rows of the run: what the per-request stages, the head and the greedy loop count
+    TRY(req_claim(e, Rr, Rr > R));      // sonic_set_request_bias / _sampling / option request_grammar: this batch consumes what they left whatever becomes of it (ENTER_CONSUME drops it on every other exit)
     HostPlan hp;
     if (R < 1 || R > e->Bm) return fail(e, SONIC_ERR_INVALID, "request count %d out of range 1..%d", R, e->Bm);
     std::vector<int32_t> x_ids, x_left; std::vector<int64_t> x_off; std::vector<int> dlen;      // option draft_verify: the longer sequences prompt || draft (empty dlen: no draft in this batch)
@@ -635,6 +668,12 @@ int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int
         }
     }
     e->draft_last_S = hp.S;
+    e->fork_timed = false;
+    if (Rr > R) {
+        if (d.dec_head_dim % 8) return fail(e, SONIC_ERR_INVALID, "request_forks: a head dimension of %d is not a multiple of 8 elements (the copy moves 16-byte pieces)", d.dec_head_dim);
+        hp.rows = Rr; hp.fork_src = fork_src;
+        for (int i = 0; i < 2; ++i) if (!e->fork_ev[i]) HIPC(e, hipEventCreate(&e->fork_ev[i]));
+    }
     {   // staging buffer of this run: the one used two runs ago; its copies are almost always long done (a blocking wait otherwise)
         const int i = e->plan_idx ^ 1;
         if (e->plan_busy[i]) { HIPC(e, hipEventSynchronize(e->plan_ev[i])); e->plan_busy[i] = false; }
@@ -642,14 +681,15 @@ int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int
     }
     if (e->force_d && (e->force_R != R || e->force_ld < hp.max_steps))
         return fail(e, SONIC_ERR_INVALID, "forced ids are [%d][%d] but the run has %d requests / %d steps", e->force_R, e->force_ld, R, hp.max_steps);
-    e->R = R; e->max_steps = hp.max_steps; e->last_qlen = hp.q_len; e->last_maxnew = hp.max_new; e->align_last = false;
+    e->R = Rr; e->max_steps = hp.max_steps; e->last_qlen = hp.q_len; e->last_maxnew = hp.max_new; e->align_last = false;
     for (size_t r = 0; r < dlen.size(); ++r) e->last_qlen[r] -= dlen[r];      // the PROMPT's length: fetch_locked expects kv_len = prompt + tokens - 1
+    for (int r = R; r < Rr; ++r) { e->last_qlen.push_back(hp.q_len[fork_src[r]]); e->last_maxnew.push_back(hp.max_new[fork_src[r]]); }      // (a fork's invariants are its request's)
     if (want_logits) {
         // a drafted row's step counter starts at its accepted count and goes on counting with every launch, also once the row has ended: the dump holds the steps
         // the longest draft can add (the fetch reads the first max_steps of them, as always)
         int d_max = 0;
         for (int D : dlen) d_max = std::max(d_max, D);
-        const size_t need_n = (size_t)(hp.max_steps + d_max) * R * d.vocab;
+        const size_t need_n = (size_t)(hp.max_steps + d_max) * Rr * d.vocab;
         if (need_n > e->dump_cap) {
             if (e->dump) (void)hipFree(e->dump);
             e->dump = nullptr; e->dump_cap = 0;
@@ -675,7 +715,7 @@ int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int
     TRY(e->f32 ? f32_run_encoder(e, e->W, nullptr, nullptr) : run_encoder(e, e->W, nullptr, nullptr, R));
     (void)hipEventRecord(e->ev[2], e->st);
     TRY(e->f32 ? f32_run_prefill(e, R, hp) : run_prefill(e, R, hp));
-    launch_greedy(e->f32 ? f32_greedy_args(e, R, want_logits) : greedy_args(e, R, want_logits), e->st);
+    launch_greedy(e->f32 ? f32_greedy_args(e, Rr, want_logits) : greedy_args(e, Rr, want_logits), e->st);
     (void)hipEventRecord(e->ev[3], e->st);
     e->steps_run = 0; e->greedy_calls = 1; e->spliced = 0;
     return SONIC_OK;

@@ -81,6 +81,7 @@ extern "C" int sonic_load_tensor(sonic_engine* e, const char* name, const void* 
     }
     if (!strcmp(name, "draft.dispatch")) return draft_dispatch_arm(e, data, dtype, shape, ndim);      // ... and the one of the calling thread's next dispatcher submit (no engine lock, as grammar.dispatch)
     if (!strcmp(name, "request_draft")) return draft_stage_words(e, data, dtype, shape, ndim);      // the drafts of the next prefill's requests (option draft_verify)
+    if (!strcmp(name, "request_forks")) return fork_stage_counts(e, data, dtype, shape, ndim);      // the fork counts of the next prefill's requests
     ENTER(e);
     if (e->finalized) return fail(e, SONIC_ERR_INVALID, "weights already finalized");
     std::vector<int64_t> shp(shape, shape + ndim);

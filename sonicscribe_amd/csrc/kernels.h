@@ -190,6 +190,17 @@ struct DraftAcceptArgs {
 };
 void launch_draft_accept(const DraftAcceptArgs& a, int R, hipStream_t s);
 
+// Row forks (fork.hip; sonic_load_tensor "request_forks").  fork_kv_kernel: block (i, layer * Hkv + head, z) reads the first kv_len[src[i]] * hd
+// elements of K and of V of cache row src[i] - [layer][Bm][Hkv][ctx][hd], 16-bit elements - in 16-byte pieces, piece j by thread j % 256 of slice j / 256 % Z, and
+// stores each piece to the cnt[i] rows first[i] .. first[i] + cnt[i] - 1: one load, cnt[i] stores.  Nothing behind those elements is written.  hist != NULL: the
+// blocks of layer 0, head 0 copy hist[src[i]][0 .. kv_len) likewise ([.][ctx] ints).  The caller guarantees src[i] < Bm, first[i] + cnt[i] <= Bm and hd % 8 == 0
+struct ForkArgs {
+    bf16_t *Kc, *Vc; int layers, Bm, Hkv, ctx, hd;
+    int n_src; int src[64], first[64], cnt[64];
+    const int* kv_len; int* hist;
+};
+void launch_fork_kv(const ForkArgs& a, int max_len, hipStream_t s);      // max_len: the longest kv_len among the sources (sizes the grid's third axis)
+
 struct LogmelConst {
     const float* win;      // [400]
     const float* cos_t;    // [400]

@@ -569,16 +569,19 @@ class Engine(HooksMixin):
 
     def transcribe_batch(self, segments: Sequence[Any], prompts: Sequence[Sequence[int]], max_new: Sequence[int],
                          req_win: Optional[Sequence[int]] = None, want_logits: bool = False, want_logprobs: bool = False, request_bias=None, request_sampling=None,
-                         request_grammar=None, request_draft=None):
+                         request_grammar=None, request_draft=None, forks=None):
         """segments: int16 PCM windows (<= 30 s each, already peak-normalised) or RingSlice objects (raw wire PCM resident in a device
         ring; normalised on the device over the windows of their request); one prompt per request. Returns (ids list, logits or None);
         with want_logprobs (option token_logprobs on this handle) one more element: the float32 log-probability of every returned token, per request.
         request_bias: one reqbias.RequestBias or None per request (option request_bias on this handle; set_request_bias).
         request_sampling: one (temperature, seed) or None (greedy) per request (option sampling on this handle; set_request_sampling).
         request_grammar: one DeviceGrammar or None (free) per request (option grammar on this handle; set_request_grammar).
-        request_draft: one id sequence or None (no draft) per request (option draft_verify on this handle; set_request_draft)."""
+        request_draft: one id sequence or None (no draft) per request (option draft_verify on this handle; set_request_draft).
+        forks: one count n_a >= 1 per request (row forks): request a becomes n_a rows that share its encoder pass and prefill and decode on their
+        own.  The four keywords above then take one value per ROW and the results have one entry per row, in the order of fork_rows(forks)."""
         samp = None if request_sampling is None else pack_request_sampling(request_sampling)      # (validated before anything is armed)
         draft = None if request_draft is None else pack_request_draft(request_draft)
+        counts = None if forks is None else self._check_forks(forks, len(prompts), request_bias, samp, request_grammar, request_draft)
         if any(isinstance(s, RingSlice) for s in segments):      # the two forms differ in how the audio is packed and in the entry point that takes it
             pcm, offs, rings, start, n = self._pack_mixed(segments)
             entry, audio = self.lib.sonic_transcribe_mixed, (_p(pcm), _p(offs), rings, _p(start), _p(n))
@@ -586,19 +589,52 @@ class Engine(HooksMixin):
             pcm, offs = self._pack_pcm(segments)
             entry, audio = self.lib.sonic_transcribe_batch, (_p(pcm), _p(offs))
         ids, poffs = self._pack_prompts(prompts)
-        R = len(prompts)
+        A = len(prompts)
+        R = A if counts is None else int(counts.sum())      # the rows of the run: what the library writes results for
         mn = np.ascontiguousarray(max_new, dtype=np.int32)
         out_ld = int(mn.max())
         out = np.zeros((R, out_ld), np.int32)
         out_len = np.zeros(R, np.int32)
         rw = _arr(req_win, np.int32)
         logits = np.zeros((out_ld, R, self.dims.vocab), np.float32) if want_logits else None
-        self._arm_requests(request_bias, samp, request_grammar, draft)
-        self._check(entry(self.h, *audio, len(segments), _p(rw), R, _p(ids), _p(poffs), _p(mn), _p(out), out_ld, _p(out_len), _p(logits)))
+        self._arm_requests(request_bias, samp, request_grammar, draft, counts)
+        self._check(entry(self.h, *audio, len(segments), _p(rw), A, _p(ids), _p(poffs), _p(mn), _p(out), out_ld, _p(out_len), _p(logits)))
         res = [out[r, : out_len[r]].copy() for r in range(R)]
         return (res, logits, self._fetch_logprobs(out_len, out_ld)) if want_logprobs else (res, logits)
 
-    def _arm_requests(self, bias, samp_packed, grammar, draft_packed):
+    @staticmethod
+    def fork_rows(forks) -> List[List[int]]:
+        """The row order of a forked run, stated once: per request the rows of its forks.  Fork 0 of request a is row a; the further forks follow
+        behind the A requests, request by request: fork_rows([3, 1, 2]) == [[0, 3, 4], [1], [2, 5]]."""
+        counts = [int(n) for n in forks]
+        rows, nxt = [], len(counts)
+        for a, n in enumerate(counts):
+            rows.append([a] + list(range(nxt, nxt + n - 1)))
+            nxt += max(n, 1) - 1
+        return rows
+
+    def _check_forks(self, forks, A: int, bias, samp_packed, grammar, draft):
+        """the fork counts of a call as the int32 array the library takes, validated against the call's requests and per-row lists (ValueError naming `forks`)"""
+        counts = [int(n) for n in forks]
+        if len(counts) != A:
+            raise ValueError(f"forks: {len(counts)} counts for {A} requests")
+        if any(n < 1 for n in counts):
+            raise ValueError("forks: every count is at least 1 (the request itself)")
+        rows = sum(counts)
+        if rows > int(getattr(self, "max_batch", 64)):
+            raise ValueError(f"forks: the counts add up to {rows} rows, the handle has {getattr(self, 'max_batch', 64)} (max_batch)")
+        if draft is not None:
+            raise ValueError("forks: a forked run takes no drafts (request_draft)")
+        lists = (("request_bias", bias), ("request_sampling", None if samp_packed is None else samp_packed[0]), ("request_grammar", grammar))
+        for name, values in lists:
+            if values is not None and len(values) != rows:
+                raise ValueError(f"forks: {name} states {len(values)} values, the forked run has {rows} rows (one value per row, in the order of fork_rows)")
+        return np.ascontiguousarray(counts, dtype=np.int32)
+
+    def _arm_forks(self, counts):
+        self._check(self.lib.sonic_load_tensor(self.h, b"request_forks", _p(counts), DTYPE_I32, (C.c_int64 * 1)(len(counts)), 1))
+
+    def _arm_requests(self, bias, samp_packed, grammar, draft_packed, fork_counts=None):
         """The per-request values of the next prefill / run on this handle, None for a value the caller does not state: the call right ahead of the library call
         that consumes them, on success or failure - nothing in between can raise.  In the order of reqvalues.VALUES; the sampling values and the drafts come packed
         (pack_request_sampling, pack_request_draft: validated before anything is armed)."""
@@ -610,6 +646,8 @@ class Engine(HooksMixin):
             self.set_request_grammar(grammar)
         if draft_packed is not None:
             self._arm_draft(draft_packed)
+        if fork_counts is not None:      # row forks (_check_forks): last, right ahead of the consuming call
+            self._arm_forks(fork_counts)
 
     def score_batch(self, segments: Sequence[Any], prompts: Sequence[Sequence[int]], targets, req_win: Optional[Sequence[int]] = None, fanout: int = 1,
                     want_logits: bool = False, align: bool = False):
@@ -670,15 +708,17 @@ class Engine(HooksMixin):
         self._check(self.lib.sonic_run_staged(self.h, _p(rw), len(prompts), _p(ids), _p(poffs), _p(mn), int(want_logits)))
 
     def prefill(self, prompts: Sequence[Sequence[int]], max_new: Sequence[int], req_win: Optional[Sequence[int]] = None, want_logits: bool = False, wait: bool = True,
-                request_bias=None, request_sampling=None, request_grammar=None, request_draft=None):
+                request_bias=None, request_sampling=None, request_grammar=None, request_draft=None, forks=None):
         """Stage entry point: everything up to and including the first greedy token of the staged batch (sonic_prefill).  wait=False: the
-        work is only queued when the call returns (sonic_prefill_enqueue; a following splice_rows orders itself behind it on the device)."""
+        work is only queued when the call returns (sonic_prefill_enqueue; a following splice_rows orders itself behind it on the device).
+        forks: as transcribe_batch's - the handle then holds sum(forks) rows, in the order of fork_rows(forks), for decode_step, fetch_tokens and splice_rows."""
         ids, poffs = self._pack_prompts(prompts)
         mn = np.ascontiguousarray(max_new, dtype=np.int32)
         rw = _arr(req_win, np.int32)
         samp = None if request_sampling is None else pack_request_sampling(request_sampling)
         draft = None if request_draft is None else pack_request_draft(request_draft)
-        self._arm_requests(request_bias, samp, request_grammar, draft)      # (as transcribe_batch's keywords: this prefill consumes them, on success or failure)
+        counts = None if forks is None else self._check_forks(forks, len(prompts), request_bias, samp, request_grammar, request_draft)
+        self._arm_requests(request_bias, samp, request_grammar, draft, counts)      # (as transcribe_batch's keywords: this prefill consumes them, on success or failure)
         if not wait:
             self._check(self.lib.sonic_prefill_enqueue(self.h, _p(rw), len(prompts), _p(ids), _p(poffs), _p(mn)))
             return

@@ -5,6 +5,10 @@ log-probability is too low, it is decoded again at the next temperature, with th
 passes is returned; when every attempt fails the LAST one is returned (Whisper's rule).  A retry is a new request for the same audio: it encodes and
 prefills again (KV reuse across attempts is out of scope).
 
+best_of: on a model built with best_of = N > 1, an attempt at a temperature above 0 draws N samples and keeps the most likely one (pick_best),
+as Whisper and faster-whisper do; the ladder then judges that winner as it judges any attempt.  The N samples are the rows of ONE forked run - one encoder pass,
+one prefill - on a handle of their own, driven by a worker thread per replica (a Retrier); an attempt at temperature 0 is one greedy decode, whatever N.
+
 Retries are never submitted from a completion callback: the dispatchers complete futures on their own threads - the native one while it holds the lock
 that `put` takes, the continuous one on the thread that steps every running row - so a small worker thread (Retrier) judges an attempt and submits the next.
 The thread that called `submit` never blocks.
@@ -26,6 +30,19 @@ def compression_ratio(text: str) -> float:
     """len(utf-8) / len(zlib of it): openai-whisper's measure of repetition.  An empty text has ratio 0 (it never fails the threshold)."""
     raw = text.encode("utf-8")
     return len(raw) / len(zlib.compress(raw)) if raw else 0.0
+
+
+def pick_best(avg_logprobs: Sequence[float]) -> int:
+    """Whisper's MaximumLikelihoodRanker without length penalty: the index of the sample with the highest average log-probability (the mean over its emitted
+    tokens, EOS included, as Transcription.avg_logprob computes it).  Ties go to the lowest index; a nan average (nothing emitted) ranks below every number."""
+    vals = [float(v) for v in avg_logprobs]
+    if not vals:
+        raise ValueError("pick_best: no sample")
+    best = 0
+    for j in range(1, len(vals)):
+        if vals[j] == vals[j] and (vals[best] != vals[best] or vals[j] > vals[best]):
+            best = j
+    return best
 
 
 class FallbackPolicy:

@@ -59,6 +59,13 @@ def check_temperature(t) -> float:
     return v
 
 
+def fork_seed(seed: int, j: int) -> int:
+    """the seed of fork j of a best_of request: (seed + j) mod 2^64 - fork 0 draws with the request's own seed, so best_of = 1 is the request itself"""
+    if isinstance(j, bool) or not isinstance(j, (int, np.integer)) or int(j) < 0:
+        raise ValueError(f"fork index must be a non-negative integer (got {j!r})")
+    return (check_seed(seed) + int(j)) & 0xFFFFFFFFFFFFFFFF
+
+
 def temperatures(temperature) -> Tuple[Tuple[float, ...], bool]:
     """a float (one attempt) or a sequence (the fallback ladder) -> (validated tuple, is it a ladder)"""
     if isinstance(temperature, (int, float, np.floating, np.integer)):
