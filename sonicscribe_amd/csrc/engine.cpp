@@ -2,7 +2,8 @@
 // pipeline on one HIP stream, hipGraph-captured decode step, and the C ABI of include/sonic_hip.h.
 // One engine = one full model replica on one MI355X (replicas, no collectives).
 // This unit: the shared helpers, the constant tables, create / slot / destroy / info / synchronise.  The other sections of the engine live in
-// engine_generation.cpp (what a handle generates with: log-probabilities, guards, the per-request stages), engine_weights.cpp, engine_stages.cpp, engine_f32.cpp,
+// engine_generation.cpp (what a handle generates with: log-probabilities, guards, the per-request stages), engine_weights.cpp, engine_stages.cpp (the forward
+// pass and the whole-batch run around it), engine_decode.cpp (the token step and its loop), engine_score.cpp (the runs that score given tokens), engine_f32.cpp,
 // engine_ingest.cpp, engine_service.cpp, engine_options.cpp and engine_hooks.cpp; engine_internal.h is what they share.
 #include "engine_internal.h"
 

@@ -17,7 +17,7 @@ int lp_alloc(sonic_engine* e) {
 // old one: fetch first (include/sonic_hip.h says so).  The caller holds the lock and has asked gen_busy.
 int top_enable(sonic_engine* e, int K) {
     if (K < 0 || K > 8) return fail(e, SONIC_ERR_INVALID, "top_logprobs: %d is outside 0 .. 8", K);
-    if (K > 0 && !(e->opt_token_logprobs && e->out_lp)) return fail(e, SONIC_ERR_INVALID, "top_logprobs: option token_logprobs must be on first (the alternatives share the log-probability kernels' sum; sonic_set_option(e, \"token_logprobs\", 1))");
+    if (K > 0 && !lp_on(e)) return fail(e, SONIC_ERR_INVALID, "top_logprobs: option token_logprobs must be on first (the alternatives share the log-probability kernels' sum; sonic_set_option(e, \"token_logprobs\", 1))");
     if (K == e->opt_top_logprobs) return SONIC_OK;
     HIPC(e, hipSetDevice(e->device));
     HIPC(e, stream_sync(e));
@@ -28,13 +28,13 @@ int top_enable(sonic_engine* e, int K) {
     return had ? lp_alloc(e) : SONIC_OK;
 }
 int lp_check(sonic_engine* e, const char* who) {
-    if (e->opt_token_logprobs && e->out_lp) return SONIC_OK;
+    if (lp_on(e)) return SONIC_OK;
     return fail(e, SONIC_ERR_INVALID, "%s: option token_logprobs is off on this handle (sonic_set_option(e, \"token_logprobs\", 1) on the owner before its slots are created)", who);
 }
 // dispatch.cpp / pipeline.cpp (same library, not exported): does this handle produce log-probabilities
-extern "C" int engine_token_logprobs_on(sonic_engine* e) { return e && e->opt_token_logprobs && e->out_lp ? 1 : 0; }
+extern "C" int engine_token_logprobs_on(sonic_engine* e) { return e && lp_on(e) ? 1 : 0; }
 // ... and how many alternatives ride along (option top_logprobs: its log-probability records hold 1 + 2K floats per token)
-extern "C" int engine_top_logprobs(sonic_engine* e) { return e && e->opt_token_logprobs && e->out_lp ? e->opt_top_logprobs : 0; }
+extern "C" int engine_top_logprobs(sonic_engine* e) { return e && lp_on(e) ? e->opt_top_logprobs : 0; }
 extern "C" int engine_forced_parallel_on(sonic_engine* e) { return e && e->opt_forced_parallel ? 1 : 0; }      // ... and is it a scoring handle (option forced_parallel: the schedulers refuse it)
 extern "C" int engine_fail(sonic_engine* e, int code, const char* msg) { std::lock_guard<std::mutex> lk(e->mu); return fail(e, code, "%s", msg); }   // a message on a handle, from outside its calls
 
@@ -191,7 +191,7 @@ static int bias_upload(sonic_engine* e, int R) {
 // ---- option sampling: temperature sampling in the greedy kernel by the Gumbel-max identity, one (temperature, seed) per request - what Whisper's
 // decode_with_fallback retries with.  The caller holds the lock and has asked gen_busy.
 int samp_enable(sonic_engine* e, int on) {
-    if (on && !(e->opt_token_logprobs && e->out_lp)) return fail(e, SONIC_ERR_INVALID, "sampling: option token_logprobs must be on first (the sampling kernels are log-probability kernels; sonic_set_option(e, \"token_logprobs\", 1))");
+    if (on && !lp_on(e)) return fail(e, SONIC_ERR_INVALID, "sampling: option token_logprobs must be on first (the sampling kernels are log-probability kernels; sonic_set_option(e, \"token_logprobs\", 1))");
     return stage_enable(e, e->samp, on, &e->opt_sampling, "sampling", SAMP_WORDS, false);                  // (zero-filled: every row starts greedy)
 }
 void samp_pack(unsigned* w, float t, uint64_t seed) { memcpy(&w[0], &t, 4); w[1] = (unsigned)(seed & 0xffffffffull); w[2] = (unsigned)(seed >> 32); }
@@ -346,7 +346,7 @@ static sonic_grammar* gram_ref_id(sonic_engine* root, int id) {
     return nullptr;
 }
 int gram_enable(sonic_engine* e, int on) {
-    if (on && !(e->opt_token_logprobs && e->out_lp)) return fail(e, SONIC_ERR_INVALID, "grammar: option token_logprobs must be on first (the grammar kernels are log-probability kernels; sonic_set_option(e, \"token_logprobs\", 1))");
+    if (on && !lp_on(e)) return fail(e, SONIC_ERR_INVALID, "grammar: option token_logprobs must be on first (the grammar kernels are log-probability kernels; sonic_set_option(e, \"token_logprobs\", 1))");
     if (on && greedy_guard_lds(e->d.vocab) > 60000) return fail(e, SONIC_ERR_UNSUPPORTED, "grammar: a vocabulary of %d ids does not fit the guard bitmaps", e->d.vocab);
     if (!on && e->opt_grammar) { gram_drop_staged(e); for (int r = 0; r < 64; ++r) gram_row_release(e, r); }
     TRY(stage_enable(e, e->gram, on, &e->opt_grammar, "grammar", GRAM_STAGE_WORDS, true));
@@ -505,7 +505,7 @@ int draft_extend(sonic_engine* e, int R, const int32_t* prompt_ids, const int64_
 }
 int draft_alloc(sonic_engine* e) {
     TRY(score_logits_alloc(e));
-    const size_t plan = (size_t)5 * e->tok_cap + 4 * 64;
+    const size_t plan = DraftPlan::words(e->tok_cap);
     if (!e->draft_plan_d) TRY(dalloc(e, &e->draft_plan_d, plan));
     for (int i = 0; i < 2; ++i)
         if (!e->draft_plan_h[i] && hipHostMalloc((void**)&e->draft_plan_h[i], plan * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(e, SONIC_ERR_OOM, "draft_verify: pinned host memory exhausted"); }
@@ -644,7 +644,7 @@ void req_greedy_args(const sonic_engine* e, GreedyArgs& g) {
     if (e->opt_sampling && g.out_lp) g.samp = e->samp.dev;      // (the option is refused without token_logprobs, and token_logprobs cannot leave while it is on)
     if (e->opt_grammar && g.out_lp && g.hist) { g.gram_ref = e->gram.dev; g.gram_state = gram_state_of(e); }      // (likewise; the option brought the history)
 }
-int req_graph_key(const sonic_engine* e) { return (e->opt_request_bias ? 32768 : 0) + (e->opt_sampling ? 65536 : 0) + (e->opt_grammar ? (1 << 21) : 0); }
+int req_graph_key(const sonic_engine* e) { return (e->opt_request_bias ? GK_BIAS : 0) + (e->opt_sampling ? GK_SAMPLE : 0) + (e->opt_grammar ? GK_GRAMMAR : 0); }
 int req_splice_check(sonic_engine* d, sonic_engine* p) {
     const char* opt = nullptr;
     if (d->opt_request_bias != p->opt_request_bias || (d->opt_request_bias && !(p->bias.dev && d->bias.dev && p->hist && d->hist))) opt = "request_bias";

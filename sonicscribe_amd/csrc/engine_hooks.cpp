@@ -114,19 +114,19 @@ static int test_align(sonic_engine* e, const float* q, const float* k, float* ou
     bf16_t* dk = up_bf16(e, tb, k, (size_t)B * Tk * Hkv * 128);
     float* dt_out = tb.get<float>(S); int* rec = tb.get<int>(S);
     if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
-    const size_t tc = (size_t)e->tok_cap;
-    std::vector<int> plan(2 * tc + 4 * 64 + ALIGN_MAX_HEADS, 0), iota(S);
+    std::vector<int> plan(AlignPlan::words(e->tok_cap), 0), iota(S);
+    const AlignPlan ap(plan.data(), e->tok_cap);
     for (int b = 0, s = 0; b < B; ++b) {
-        int* sp = plan.data() + 2 * tc + 4 * b;
+        int* sp = ap.seq + 4 * b;
         sp[0] = s; sp[1] = Tq; sp[2] = 0; sp[3] = Tk;
-        for (int n = 0; n < Tq; ++n, ++s) { plan[s] = s; plan[tc + s] = b; iota[s] = s; }
+        for (int n = 0; n < Tq; ++n, ++s) { ap.qrow[s] = s; ap.rseq[s] = b; iota[s] = s; }
     }
-    for (int h = 0; h < Hq; ++h) plan[2 * tc + 4 * 64 + h] = h;
+    for (int h = 0; h < Hq; ++h) ap.heads[h] = h;
     HIPC(e, h2d(e, e->align_plan_d, plan.data(), plan.size() * 4));
     HIPC(e, h2d(e, rec, iota.data(), (size_t)S * 4));
     e->align_S = S; e->align_nseq = B; e->align_Amax = Tk; e->align_Lmax = Tq; e->align_Htot = Hq; e->align_last_heads = Hq; e->align_last = false;
     fill_words((int*)e->align_M, 0, (size_t)S * Tk, e->st);
-    AlignArgs a = align_probs_args(e, dq, dk, Hkv * 128L, 128, (long)Tk * Hkv * 128, e->align_plan_d + 2 * tc + 4 * 64, Hq, Hq, Hkv, rec);
+    AlignArgs a = align_probs_args(e, dq, dk, Hkv * 128L, 128, (long)Tk * Hkv * 128, AlignPlan(e->align_plan_d, e->tok_cap).heads, Hq, Hq, Hkv, rec);
     a.t_out = dt_out;
     launch_align_probs(a, e->st);
     launch_align_reduce(a, e->st);

@@ -1,5 +1,5 @@
-// What the translation units of the engine (engine.cpp, engine_generation.cpp, engine_weights.cpp, engine_stages.cpp, engine_f32.cpp, engine_ingest.cpp,
-// engine_service.cpp, engine_options.cpp, engine_hooks.cpp) share: the engine struct and its parts, the constants, the error / entry macros and the helpers that
+// What the translation units of the engine (engine.cpp, engine_generation.cpp, engine_weights.cpp, engine_stages.cpp, engine_decode.cpp, engine_score.cpp, engine_f32.cpp,
+// engine_ingest.cpp, engine_service.cpp, engine_options.cpp, engine_hooks.cpp) share: the engine struct and its parts, the constants, the error / entry macros and the helpers that
 // cross a unit boundary.  Not part of the C ABI (include/sonic_hip.h); a function used by one unit only is static there.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -216,19 +216,19 @@ struct sonic_engine {
     // the kernel hooks' grammar (sonic_load_tensor "grammar.hook:<V>", options hook_grammar_state / hook_grammar_eos; engine_hooks.cpp): the packed automaton, the rows'
     // states in, the EOS ids, armed until the next hook launch that has histories and log-probabilities takes it; hook_state_out: that launch's states out (sonic_debug_read)
     std::vector<int> hook_gram; int hook_state_in[64]; std::vector<int> hook_eos; int hook_state_out[64]{};
-    // the parallel forced run (options forced_parallel / forced_fanout / score_chunk_rows; run_forced_parallel, engine_stages.cpp): with forced ids set,
+    // the parallel forced run (options forced_parallel / forced_fanout / score_chunk_rows; run_forced_parallel, engine_score.cpp): with forced ids set,
     // a run is ONE prefill of prompt || forced ids, the lm_head over every forced position as a GEMM per chunk of score rows, and score_rows_kernel per row.
-    // score_logits: the chunk's logits [score_rows_cap][vocab] in the activation type (fp32 kind: fp32); score_plan_d / score_plan_h: per score row its hidden-state
-    // row, its target id and its record index, on the device and in pinned memory (one buffer: the run ends with a stream synchronise).  All three come with the
-    // first parallel run, are counted by sonic_memory_info and go with the handle
+    // score_logits: the chunk's logits [score_rows_cap][vocab] in the activation type (fp32 kind: fp32); score_plan_d / score_plan_h: the score rows' plan (ScorePlan),
+    // on the device and in pinned memory (one buffer: the run ends with a stream synchronise).  All three come with the first parallel run, are counted by
+    // sonic_memory_info and go with the handle
     int opt_forced_parallel = 0, opt_forced_fanout = 1, opt_score_chunk_rows = SCORE_CHUNK_DEFAULT;
     void* score_logits = nullptr; int score_rows_cap = 0; int* score_plan_d = nullptr; int* score_plan_h = nullptr;
     // word timestamps on the parallel forced run (options forced_align / align_head; align.hip).  align_heads: the selected heads as l * 256 + h, sorted
     // (empty: every head of the last ceil(dec_layers / 2) layers).  The buffers come with the first align run, sized to that run (and exchanged for larger ones by a
     // later run that needs more), are counted by sonic_memory_info and go with the handle: align_P 2 x [heads of a layer][S][A_max] and align_M [S][A_max] fp32, the DTW's
-    // int8 trace [S][A_max], align_t [64][out_cap] (t_n beside out_lp's records), the plan (per score row its query row and sequence, per sequence row0 | L | a0 | A,
-    // the selected heads layer by layer) on the device and pinned.  align_live: the prefill under way is an align run's (run_prefill launches align_probs / _reduce
-    // behind the selected layers' RoPE); align_last: the batch in hand is one - its log-probability records carry t_n as one more float (fetch_locked)
+    // int8 trace [S][A_max], align_t [64][out_cap] (t_n beside out_lp's records), the plan (AlignPlan) on the device and pinned.  align_live: the prefill under way is an
+    // align run's (run_prefill launches align_probs / _reduce behind the selected layers' RoPE); align_last: the batch in hand is one - its log-probability records
+    // carry t_n as one more float (fetch_locked)
     int opt_forced_align = 0; std::vector<int> align_heads;
     float *align_P = nullptr, *align_M = nullptr, *align_t = nullptr; signed char* align_trace = nullptr; int *align_plan_d = nullptr, *align_plan_h = nullptr;
     size_t align_P_cap = 0, align_M_cap = 0, align_plan_cap = 0, align_Zoff = 0;      // align_P holds the probabilities and, align_Zoff floats on, the filtered z of one layer's heads
@@ -239,8 +239,7 @@ struct sonic_engine {
     // transcript - the prefill runs over prompt || draft, the lm_head over every draft position as a GEMM per chunk of rows into score_logits (the parallel forced
     // run's chunk buffer), verify_rows_kernel per row, draft_accept_kernel per request, then the unchanged head.  draft_stage: the staged words [R | off[R + 1] | ids]
     // (draft_pending = their R, -1: none; draft_take: the prefill under way consumes them).  The buffers come with the handle's first drafted prefill, are counted by
-    // sonic_memory_info and go with the handle: draft_plan_d, 5 words per verify row (hidden row | draft id | record index | request | history length) and 4 x 64 per
-    // request (draft length | first verify row | prompt length | first packed token), with a pinned mirror beside each of the two plan staging buffers; ver_tok
+    // sonic_memory_info and go with the handle: draft_plan_d, the verify rows' plan (DraftPlan), with a pinned mirror beside each of the two plan staging buffers; ver_tok
     // [tok_cap], ver_rec [tok_cap][lp_width] (ver_rec_w: the width it was allocated at), draft_acc [64] = a_r of the last drafted prefill (draft_last_S: its verify rows; 0: none)
     int opt_draft_verify = 0;
     std::vector<int> draft_stage; std::atomic<int> draft_pending{-1}; bool draft_take = false;
@@ -278,10 +277,38 @@ struct QkvVt { bf16_t* Vt; int n_split, seg_T, vt_ld; long vt_seg_stride; };
 struct HostPlan {
     std::vector<int> src, tok_seq, tok_pos, q_off, q_len, last_row, max_new;
     int n_tok = 0, max_p = 0, max_steps = 0;
-    // option draft_verify: the S verify rows of the batch's drafts (draft_plan_d's layout: 5 x S words, then 4 x 64); S = 0: an ordinary prefill
+    // option draft_verify: the S verify rows of the batch's drafts (draft_plan_d's layout: DraftPlan); S = 0: an ordinary prefill
     std::vector<int> draft; int S = 0;
     // row forks: the rows of the run (0: the requests are the rows), then per row the request it shares its prefill with (rows 0 .. R-1: themselves)
     int rows = 0; std::vector<int> fork_src;
+};
+
+// The three plans of the scoring passes, as the kernels read them: a view over a base pointer - the pinned host image and the device buffer alike - with one
+// member per array.  PLAN_REQ_WORDS: the stride of every per-request array in them; verify.hip, score.hip and align.hip index rq[64 + r], so it is 64
+#define PLAN_REQ_WORDS 64
+static_assert(PLAN_REQ_WORDS == 64, "the kernels read the plans' per-request words at a stride of 64");
+// draft plan (draft_plan_d / draft_plan_h, HostPlan::draft): per verify row its hidden row | draft id | record index | request | history length, S of each; then per
+// request D | first verify row | P | first packed token (req: the four of them as draft_accept_kernel takes them, one pointer)
+struct DraftPlan {
+    int *hidden, *target, *rec, *hrow, *hlen, *req, *dlen, *first, *P, *q_off;
+    DraftPlan(int* b, size_t S) : hidden(b), target(b + S), rec(b + 2 * S), hrow(b + 3 * S), hlen(b + 4 * S), req(b + 5 * S), dlen(req), first(req + PLAN_REQ_WORDS), P(req + 2 * PLAN_REQ_WORDS), q_off(req + 3 * PLAN_REQ_WORDS) {}
+    static size_t words(size_t tok_cap) { return 5 * tok_cap + 4 * PLAN_REQ_WORDS; }
+};
+// score plan (score_plan_d / score_plan_h): per score row its hidden-state row | target | record index, S of each (row_words; all the device buffer holds); then, in
+// the host image, the rows' closing state n_new | finished | tok_pos | n_active (state_words)
+struct ScorePlan {
+    int *hidden, *target, *rec, *n_new, *finished, *tok_pos, *n_active;
+    ScorePlan(int* b, size_t S) : hidden(b), target(b + S), rec(b + 2 * S), n_new(b + 3 * S), finished(n_new + PLAN_REQ_WORDS), tok_pos(n_new + 2 * PLAN_REQ_WORDS), n_active(n_new + 3 * PLAN_REQ_WORDS) {}
+    static size_t row_words(size_t rows) { return 3 * rows; }  static size_t state_words() { return 4 * PLAN_REQ_WORDS; }
+    static size_t words(size_t tok_cap) { return row_words(tok_cap) + state_words(); }
+};
+// align plan (align_plan_d / align_plan_h): per score row its query row and its sequence, tok_cap of each; then per sequence row0 | L | a0 | A (seq, 4 words each); then
+// the selected heads layer by layer (tail_words: seq and heads, which travel as one copy)
+struct AlignPlan {
+    int *qrow, *rseq, *seq, *heads;
+    AlignPlan(int* b, size_t tok_cap) : qrow(b), rseq(b + tok_cap), seq(b + 2 * tok_cap), heads(seq + 4 * PLAN_REQ_WORDS) {}
+    static size_t tail_words() { return 4 * PLAN_REQ_WORDS + ALIGN_MAX_HEADS; }
+    static size_t words(size_t tok_cap) { return 2 * tok_cap + tail_words(); }
 };
 
 #define HIPC(e, call)                                                                                      \
@@ -350,15 +377,38 @@ int run_mel(sonic_engine* e, int W, bool want_f32);
 int run_encoder(sonic_engine* e, int W, float* enc_layers_out, float* enc_out_host, int n_groups);
 int keep_rows(const sonic_dims& d, int n_valid_frames);
 int frames_of(int n_samples);
+int plan_requests(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new, HostPlan& hp, int fan = 1);
+int upload_plan(sonic_engine* e, int R, const HostPlan& hp);       // the prefill's prologue, every kind: the request plan through the pinned staging buffer ...
+int reset_row_state(sonic_engine* e, int R, int n_tok);            // ... and the rows' counters, history, bias tables and sampling values for the greedy loop
+int run_prefill(sonic_engine* e, int R, const HostPlan& hp, bool head = true);
+int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new, bool want_logits);
+int run_all(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new, bool want_logits);
+// what every whole-batch run (run_to_first_token / run_all, run_forced_parallel) begins and ends with
+int run_refuse_unready(sonic_engine* e);            // the entry refusals: weights not finalized, no PCM staged, a continuous loop on this handle
+int run_wait_spliced(sonic_engine* e);              // rows of the previous batch were spliced away: the stream waits for the copy kernels that read them
+int run_pick_plan_buffer(sonic_engine* e);          // plan_h = the staging buffer used two runs ago, once its copies are done
+int run_reserve_dump(sonic_engine* e, bool want_logits, int dump_steps, int cap_steps, int rows);   // the step-logits dump holds cap_steps x rows x vocab; a fetch reads dump_steps of them
+int run_upload_win_req(sonic_engine* e, const int32_t* req_win, int n_groups);   // int8 mode: the window -> outlier group map of the encoder
+void run_zero_host_figures(sonic_engine* e);        // the decode loop's host figures start at zero ...
+int run_close(sonic_engine* e, double host_enqueue_first, int steps_done);   // ... and the run ends: synchronise, the sticky error, the timings
+
+// ------------------------------------------------------------------------------------------ the token step and its loop (engine_decode.cpp)
 void skinny(sonic_engine* e, const bf16_t* X, long ldx, const bf16_t* W, float* P, int M, int N, int K, int* ks_out, long long* kt = nullptr);
 GreedyArgs greedy_args(sonic_engine* e, int R, bool dump);
-void decode_step_i8(sonic_engine* e, int R, bool dump);
-int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off,
-                       const int32_t* max_new, bool want_logits);
 int chunk_graph(sonic_engine* e, int R, int n, hipGraphExec_t* out, bool svc = false);
 int run_decode_steps(sonic_engine* e, int n_steps, int* done_out);
-int run_all(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off,
-            const int32_t* max_new, bool want_logits);
+// the bits of a captured chunk's cache key above the row count (chunk_graph; GK_BIAS, GK_SAMPLE and GK_GRAMMAR are req_graph_key's): the greedy kernel's family and
+// its pointers are part of the capture.  GK_TOPK counts: option top_logprobs = K <= 8 takes bits 17 .. 20
+enum { GK_SVC = 1 << 12, GK_LP = 1 << 13, GK_GUARD = 1 << 14, GK_BIAS = 1 << 15, GK_SAMPLE = 1 << 16, GK_TOPK = 1 << 17, GK_GRAMMAR = 1 << 21 };
+
+// ------------------------------------------------------------------------------------------ scoring given tokens from a prefill (engine_score.cpp)
+int run_forced_parallel(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new, bool want_logits);
+void run_draft_verify(sonic_engine* e, int R, const HostPlan& hp);      // option draft_verify, behind the prefill's last layer (run_prefill)
+int score_logits_alloc(sonic_engine* e);            // the chunk's logits [score_chunk_rows][vocab] the parallel forced run and the verify pass share
+// word timestamps (DESIGN.md 6.9): the launches' one descriptor - Q rows [tok][Hq * 128], K as the strides say, the plan and buffers of the handle - shared by
+// run_prefill / run_forced_parallel and the hook (sonic_test_attention on an align handle)
+AlignArgs align_probs_args(sonic_engine* e, const bf16_t* Q, const bf16_t* K, long k_ld, long k_head_stride, long k_seq_stride, const int* heads, int n_heads, int Hq, int Hkv, const int* rec);
+int align_alloc(sonic_engine* e, int S, int A_max, int heads_per_layer);      // the buffers at (at least) this run's need
 
 // ------------------------------------------------------------------------------------------ SONIC_MODE_F32 (engine_f32.cpp)
 int f32_alloc(sonic_engine* e);
@@ -382,7 +432,7 @@ int fetch_locked(sonic_engine* e, int32_t* out_ids, int out_ld, int32_t* out_len
 void drop_graphs(sonic_engine* e);                  // the captured decode chunks of this handle (engine_options.cpp)
 int read_back_16(sonic_engine* e, const bf16_t* d, float* h, size_t n);   // n elements of a 16-bit device buffer -> fp32 on the host, through a temporary (engine_hooks.cpp; sonic_debug_read)
 
-// ------------------------------------------------------------------------------------------ launch builders and shared launch sequences (engine_stages.cpp)
+// ------------------------------------------------------------------------------------------ launch builders and shared launch sequences (the prefill's: engine_stages.cpp; the token step's: engine_decode.cpp)
 // One builder per launch descriptor: production and the hooks fill SkinnyArgs / DecodeAttnArgs / the prefill's FlashArgs and RopeAppendArgs through these and set
 // what only they need (i8, x_amax, pre_*, err, kt; dq, amax_out, big_out, pf) on the result.
 SkinnyArgs skinny_args(const bf16_t* X, long ldx, const bf16_t* W, float* P, int M, int N, int K, int ksplit, int dt);
@@ -398,16 +448,11 @@ RopeAppendArgs rope_append_args(const bf16_t* qkv, bf16_t* q_out, bf16_t* Kc, bf
 enum { OGU_FUSED = 0, OGU_SPLIT_NORM = 1, OGU_HALF_FUSED = 2, OGU_UNFUSED = 3 };
 struct OGuChain { const bf16_t *att, *Wo; bf16_t* x; const float* ln_w; const bf16_t* Wgu; int gu8; bf16_t *hn, *act; float *ss, *slab; long long *kt_o, *kt_gu; };
 void launch_o_gu(sonic_engine* e, int form, const OGuChain& c, int M, int K, int D, int ff, float eps);
-// word timestamps (DESIGN.md 6.9): the launches' one descriptor - Q rows [tok][Hq * 128], K as the strides say, the plan and buffers of the handle - shared by
-// run_prefill / run_forced_parallel and the hook (sonic_test_attention on an align handle)
-AlignArgs align_probs_args(sonic_engine* e, const bf16_t* Q, const bf16_t* K, long k_ld, long k_head_stride, long k_seq_stride, const int* heads, int n_heads, int Hq, int Hkv, const int* rec);
-int align_alloc(sonic_engine* e, int S, int A_max, int heads_per_layer);      // the buffers at (at least) this run's need
-int upload_plan(sonic_engine* e, int R, const HostPlan& hp);       // the prefill's prologue, every kind: the request plan through the pinned staging buffer ...
-int reset_row_state(sonic_engine* e, int R, int n_tok);            // ... and the rows' counters, history, bias tables and sampling values for the greedy loop
 
 // ------------------------------------------------------------------------------------------ what a handle generates with (engine_generation.cpp)
 // log-probabilities (options token_logprobs / top_logprobs)
 static inline int lp_width(const sonic_engine* e) { return 1 + 2 * e->opt_top_logprobs; }   // floats per token in every log-probability array of this handle
+static inline bool lp_on(const sonic_engine* e) { return e->opt_token_logprobs && e->out_lp; }   // log-probabilities are live on this handle: the option is on and its buffer is there
 int lp_alloc(sonic_engine* e);                      // out_lp on first use
 int top_enable(sonic_engine* e, int K);             // option top_logprobs behind the lock and the busy check: out_lp at its new width
 int lp_check(sonic_engine* e, const char* who);     // SONIC_ERR_INVALID naming the option when token_logprobs is off on this handle
@@ -472,6 +517,5 @@ int fork_stage_counts(sonic_engine* e, const void* data, int dtype, const int64_
 // request_forks) and returned as the row -> request map (empty: no counts, or all of them 1 - the prefill of today)
 int fork_claim(sonic_engine* e, int R, std::vector<int>& fork_src);
 ForkArgs fork_args(sonic_engine* e, int R, const std::vector<int>& fork_src);      // the copy's one descriptor (run_prefill)
-int score_logits_alloc(sonic_engine* e);            // the chunk's logits [score_chunk_rows][vocab] the parallel forced run and the verify pass share (engine_stages.cpp)
 int gen_inherit(sonic_engine* e, const sonic_engine* root);   // sonic_slot_create: the owner's generation options (token_logprobs .. forced_align) onto the new slot, with their buffers
 void gen_release(sonic_engine* e);                  // sonic_destroy: the stages' pinned mirrors and events, the grammar references this handle holds, an owner's grammars

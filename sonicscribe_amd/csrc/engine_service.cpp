@@ -118,7 +118,7 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
     if (!d->svc_on) return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: the destination is not decoding continuously (sonic_service_begin)");
     if ((d->owner ? d->owner : d) != (p->owner ? p->owner : p)) return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: the handles do not share weights");
     if (d->Bm != p->Bm || d->max_ctx != p->max_ctx) return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: the handles differ in max_batch / max_ctx");
-    if (d->opt_token_logprobs && !(p->opt_token_logprobs && p->out_lp))
+    if (d->opt_token_logprobs && !lp_on(p))
         return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: the destination has option token_logprobs on, the source prefilled without it");
     if (d->opt_token_logprobs && d->opt_top_logprobs != p->opt_top_logprobs)
         return fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in option top_logprobs (%d and %d): set it on the owner before its slots are created", p->opt_top_logprobs, d->opt_top_logprobs);
@@ -138,7 +138,7 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
     a.kv_len_s = p->kv_len; a.tok_pos_s = p->tok_pos; a.n_new_s = p->n_new; a.fin_s = p->finished; a.max_new_s = p->max_new_d; a.out_s = p->out_ids; a.out_ld = d->out_cap;
     a.kv_len_d = d->kv_len; a.tok_pos_d = d->tok_pos; a.n_new_d = d->n_new; a.fin_d = d->finished; a.max_new_d = d->max_new_d; a.out_d = d->out_ids; a.n_active_d = d->n_active;
     a.sx_s = p->sx; a.shn_s = p->shn; a.sx_d = d->sx; a.shn_d = d->shn; a.D = dm.dec_d;
-    if (d->opt_token_logprobs && d->out_lp) { a.lp_s = p->out_lp; a.lp_d = d->out_lp; a.lp_w = lp_width(d); }
+    if (lp_on(d)) { a.lp_s = p->out_lp; a.lp_d = d->out_lp; a.lp_w = lp_width(d); }
     if (hist_on(d)) { a.hist_s = p->hist; a.hist_d = d->hist; }
     req_splice_args(d, p, a, src_rows, dst_rows, n);      // the per-request stages' rows; a row's grammar reference is handed over with it
     if (d->i8) { a.hq_s = p->hn_q; a.hq_d = d->hn_q; a.sca_s = p->sca_hn; a.sca_d = d->sca_hn; a.oc_s = p->oc_hn; a.oc_d = d->oc_hn; a.ol_s = p->ol_hn; a.ol_d = d->ol_hn; a.ov_s = p->ov_hn; a.ov_d = d->ov_hn; }

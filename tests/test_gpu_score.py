@@ -328,7 +328,29 @@ def test_refusals(golden):
         plain.close()
 
 
-# ------------------------------------------------------------------------------------------ 10. ASRModel
+# ------------------------------------------------------------------------------------------ 10. the runs' shared prologue, one kind of run after the other
+def test_greedy_score_greedy_on_one_handle(golden):
+    """run_to_first_token and run_forced_parallel begin and end through the same helpers (staging-buffer pick, step-logits dump, closing state): a greedy run, a
+    parallel forced run and the greedy run again on ONE handle.  Each comparison is one deterministic path run twice: bit equality."""
+    _, segs, prompts, force = golden
+    e, fresh = make(max_batch=2), make(max_batch=2)
+    try:
+        ids1, lg1 = e.transcribe_batch(segs, prompts, [4, 4], want_logits=True)
+        ids2, lg2, lp2 = e.score_batch(segs, prompts, force, want_logits=True)
+        ids3, lg3 = e.transcribe_batch(segs, prompts, [4, 4], want_logits=True)
+        ids0, lg0, lp0 = fresh.score_batch(segs, prompts, force, want_logits=True)
+        assert lg1.shape == (4, 2, D.vocab) and lg2.shape == (N, 2, D.vocab)
+        for si in range(2):
+            assert np.array_equal(ids3[si], ids1[si])
+            assert np.array_equal(ids2[si], ids0[si]) and np.array_equal(bits(lp2[si]), bits(lp0[si]))
+        assert np.array_equal(bits(lg3), bits(lg1))
+        assert np.array_equal(bits(lg2), bits(lg0))
+    finally:
+        e.close()
+        fresh.close()
+
+
+# ------------------------------------------------------------------------------------------ 11. ASRModel
 def test_asrmodel_score():
     from sonicscribe_amd.asr import ASRModel
     from sonicscribe_amd.scoring import Score
