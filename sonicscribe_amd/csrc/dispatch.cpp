@@ -16,8 +16,8 @@
 //   * one thread per DECODING handle: splices handed-over rows into its lowest free rows between two chunks, queues chunks over the occupied
 //     rows (sonic_service_step), fetches every row the moment the pipelined check shows it finished (sonic_fetch_rows) and completes its ticket;
 //   * completions are collected by sonic_dispatch_next (blocking, from any thread): the host side keeps one thread that turns them into futures.
-// No thread polls: condition variables here, blocking HIP events inside the engine.  Only the C ABI of include/sonic_hip.h is used, plus the library's
-// own engine_token_logprobs_on (is the option on for a handle: then the rows' log-probabilities are fetched with their ids, sonic_dispatch_next_lp).
+// No thread polls: condition variables here, blocking HIP events inside the engine.  Only the C ABI of include/sonic_hip.h is used, plus what sched_engine.h
+// lists of the library's own (is an option on for a handle, a request's values checked and taken at its submit).
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -32,26 +32,18 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/sonic_hip.h"
-extern "C" int engine_token_logprobs_on(sonic_engine* e);   // engine.cpp
-extern "C" int engine_top_logprobs(sonic_engine* e);        // engine.cpp: option top_logprobs of this handle (K: its log-probability records hold 1 + 2K floats)
-extern "C" int engine_forced_parallel_on(sonic_engine* e);  // engine.cpp: option forced_parallel of this handle (a scoring handle: refused here)
-extern "C" int engine_request_bias_on(sonic_engine* e);     // engine.cpp: option request_bias on this handle
-extern "C" int engine_bias_validate(sonic_engine* e, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n);   // engine.cpp: one request's table against the caps and this handle's vocabulary
-extern "C" int engine_sampling_on(sonic_engine* e);         // engine.cpp: option sampling on this handle
-extern "C" int engine_sampling_validate(float temperature); // engine.cpp: 0 or 1e-3 .. 100 (the message goes to the calling thread's sonic_last_error(NULL))
-extern "C" int engine_grammar_on(sonic_engine* e);          // engine.cpp: option grammar on this handle
-struct sonic_grammar;
-extern "C" sonic_grammar* engine_take_dispatch_grammar(void);   // engine.cpp: the grammar sonic_load_tensor "grammar.dispatch:<id>" armed for this thread's next submit (with a reference), or NULL ...
-extern "C" void engine_grammar_unref(sonic_grammar* g);     // ... and the reference's return
-extern "C" void* engine_grammar_owner(sonic_grammar* g);    // engine.cpp: the weight owner a grammar lives on
-extern "C" int engine_draft_verify_on(sonic_engine* e);     // engine_generation.cpp: option draft_verify on this handle
-extern "C" int engine_take_dispatch_draft(const int32_t** ids);   // ... the draft sonic_load_tensor "draft.dispatch" armed for this thread's next submit (-1: none; else its length)
-extern "C" int engine_tok_cap(sonic_engine* e);             // ... the tokens one prefill of a handle holds
-extern "C" int engine_set_request_grammar(sonic_engine* e, sonic_grammar* const* grammars, int R);   // engine.cpp: a batch's grammars for the handle's next prefill
-extern "C" int engine_thread_fail(int code, const char* msg);   // engine.cpp: the calling thread's sonic_last_error(NULL)
+#include "dispatch_pack.h"
+#include "sched_engine.h"
 
 namespace {
+
+// What a request may bring of its own, in the order of VALUES below
+struct ReqValues {
+    dispatch_pack::BiasTable bias;                                 // its sequence-bias table (sonic_dispatch_submit_bias / _sampled; empty: none)
+    bool sampled = false; float temperature = 0.f; uint64_t seed = 0;   // its (temperature, seed) (sonic_dispatch_submit_sampled); unsampled requests of a batch are greedy
+    sonic_grammar* gram = nullptr;                                 // its grammar ("grammar.dispatch:<id>" ahead of the submit): a reference held from the submit until the request completes
+    std::vector<int32_t> draft;                                    // its draft ("draft.dispatch" ahead of the submit; option draft_verify): the prefill verifies it
+};
 
 struct Req {
     int64_t ticket = 0;
@@ -61,10 +53,7 @@ struct Req {
     std::vector<int32_t> prompt; int max_new = 0;
     int status = -1; std::string err; std::vector<int32_t> ids;    // result
     std::vector<float> lp;                                         // ... and, with option token_logprobs on the handles, every token's log-probability
-    std::vector<int32_t> b_ids, b_off; std::vector<float> b_val;  // its own sequence-bias table (sonic_dispatch_submit_bias): ids, offsets [n + 1] (empty: none), biases
-    bool sampled = false; float temperature = 0.f; uint64_t seed = 0;   // its own (temperature, seed) (sonic_dispatch_submit_sampled); unsampled requests of a batch are greedy
-    sonic_grammar* gram = nullptr;                                 // its grammar ("grammar.dispatch:<id>" ahead of the submit): a reference held from the submit until the request completes
-    std::vector<int32_t> draft;                                    // its draft ("draft.dispatch" ahead of the submit; option draft_verify): the prefill verifies it
+    ReqValues own;                                                 // what it brings of its own
     bool cancelled = false;
 };
 typedef std::shared_ptr<Req> ReqP;
@@ -100,11 +89,50 @@ namespace {
 
 void finish(sonic_dispatch* d, const ReqP& r, int status, const std::string& err) {   // d->mu held
     if (r->status != -1) return;
-    if (r->gram) { engine_grammar_unref(r->gram); r->gram = nullptr; }      // (its row was fetched - and let go of its own reference - or it never reached one)
+    if (r->own.gram) { engine_grammar_unref(r->own.gram); r->own.gram = nullptr; }      // (its row was fetched - and let go of its own reference - or it never reached one)
     r->status = status; r->err = err;
     d->done.push_back(r);
     d->cv_done.notify_all();
 }
+
+// The per-request values, in the order every site arms them: bias, sampling, grammar, draft.  sonicscribe_amd/reqvalues.py (VALUES) is this list's Python twin; a
+// further value is one entry here, its fields in ReqValues and its way into a submit.  brings: does this request bring the value; arm: the batch's values (row i
+// is batch[i]; a request without one: an empty table, greedy, NULL, an empty draft) in the form handle h takes them for its next prefill.  prefill_batch arms a value
+// only when some request of the batch brings it, where the Python replica (reqvalues.arm) states every value whose option is on ahead of every prefill: a
+// difference kept as it is (a consuming call of the engine drops what was staged on every way out, so an unarmed batch starts without values).
+struct Value {
+    bool (*brings)(const ReqValues&);
+    int (*arm)(sonic_engine* h, const std::vector<ReqP>& batch);
+};
+const Value VALUES[] = {
+    {[](const ReqValues& v) { return !v.bias.val.empty(); },
+     [](sonic_engine* h, const std::vector<ReqP>& batch) {
+         std::vector<const dispatch_pack::BiasTable*> ts;
+         for (auto& r : batch) ts.push_back(&r->own.bias);
+         const dispatch_pack::BiasBatch b = dispatch_pack::pack_bias(ts);
+         return sonic_set_request_bias(h, b.seq_ids.data(), b.seq_off.data(), b.bias.data(), b.req_off.data(), (int)batch.size());
+     }},
+    {[](const ReqValues& v) { return v.sampled; },
+     [](sonic_engine* h, const std::vector<ReqP>& batch) {
+         std::vector<float> t; std::vector<uint64_t> sd;
+         for (auto& r : batch) { t.push_back(r->own.sampled ? r->own.temperature : 0.f); sd.push_back(r->own.sampled ? r->own.seed : 0); }
+         return sonic_set_request_sampling(h, t.data(), sd.data(), (int)batch.size());
+     }},
+    {[](const ReqValues& v) { return v.gram != nullptr; },
+     [](sonic_engine* h, const std::vector<ReqP>& batch) {
+         std::vector<sonic_grammar*> gs;
+         for (auto& r : batch) gs.push_back(r->own.gram);
+         return engine_set_request_grammar(h, gs.data(), (int)batch.size());
+     }},
+    {[](const ReqValues& v) { return !v.draft.empty(); },
+     [](sonic_engine* h, const std::vector<ReqP>& batch) {
+         std::vector<const std::vector<int32_t>*> ds;
+         for (auto& r : batch) ds.push_back(&r->own.draft);
+         const std::vector<int32_t> w = dispatch_pack::pack_drafts(ds);
+         const int64_t n = (int64_t)w.size();
+         return sonic_load_tensor(h, "request_draft", w.data(), SONIC_DTYPE_I32, &n, 1);
+     }},
+};
 
 // stage + prefill `batch` on handle h; SONIC_OK or the failing status (message in *err)
 int prefill_batch(sonic_dispatch* d, sonic_engine* h, const std::vector<ReqP>& batch, bool busy, std::string* err) {
@@ -131,42 +159,9 @@ int prefill_batch(sonic_dispatch* d, sonic_engine* h, const std::vector<ReqP>& b
     if (d->adaptive_tiles) (void)sonic_set_option(h, "gemm_small_eff", busy ? 0 : 75);
     int rc = any_ring ? sonic_stage_mixed(h, pcm.data(), off.data(), rings.data(), rstart.data(), rn.data(), W, req_win.data(), R)
                       : sonic_stage_pcm(h, pcm.data(), off.data(), W);
-    bool any_bias = false;
-    for (auto& r : batch) any_bias = any_bias || !r->b_val.empty();
-    if (rc == SONIC_OK && any_bias) {                              // the requests' tables in sonic_set_request_bias's per-batch form; the prefill below consumes them
-        std::vector<int32_t> s_ids, s_off{0}, r_off{0}; std::vector<float> s_val;
-        for (auto& r : batch) {
-            for (size_t i = 0; i + 1 < r->b_off.size(); ++i) {
-                s_ids.insert(s_ids.end(), r->b_ids.begin() + r->b_off[i], r->b_ids.begin() + r->b_off[i + 1]);
-                s_off.push_back((int32_t)s_ids.size());
-            }
-            s_val.insert(s_val.end(), r->b_val.begin(), r->b_val.end());
-            r_off.push_back((int32_t)s_val.size());
-        }
-        rc = sonic_set_request_bias(h, s_ids.data(), s_off.data(), s_val.data(), r_off.data(), R);
-    }
-    bool any_samp = false;
-    for (auto& r : batch) any_samp = any_samp || r->sampled;
-    if (rc == SONIC_OK && any_samp) {                              // the requests' (temperature, seed); the prefill below consumes them
-        std::vector<float> t; std::vector<uint64_t> sd;
-        for (auto& r : batch) { t.push_back(r->sampled ? r->temperature : 0.f); sd.push_back(r->sampled ? r->seed : 0); }
-        rc = sonic_set_request_sampling(h, t.data(), sd.data(), R);
-    }
-    bool any_gram = false;
-    for (auto& r : batch) any_gram = any_gram || r->gram;
-    if (rc == SONIC_OK && any_gram) {                              // the requests' grammars (NULL: a free request); the prefill below consumes them
-        std::vector<sonic_grammar*> gs;
-        for (auto& r : batch) gs.push_back(r->gram);
-        rc = engine_set_request_grammar(h, gs.data(), R);
-    }
-    bool any_draft = false;
-    for (auto& r : batch) any_draft = any_draft || !r->draft.empty();
-    if (rc == SONIC_OK && any_draft) {                             // the requests' drafts as sonic_load_tensor "request_draft" takes them; the prefill below consumes them
-        std::vector<int32_t> w{R, 0};
-        for (auto& r : batch) w.push_back(w.back() + (int32_t)r->draft.size());
-        for (auto& r : batch) w.insert(w.end(), r->draft.begin(), r->draft.end());
-        const int64_t n = (int64_t)w.size();
-        rc = sonic_load_tensor(h, "request_draft", w.data(), SONIC_DTYPE_I32, &n, 1);
+    for (const Value& v : VALUES) {                                // the requests' own values; the prefill below consumes them
+        if (rc != SONIC_OK) break;
+        if (std::any_of(batch.begin(), batch.end(), [&](const ReqP& r) { return v.brings(r->own); })) rc = v.arm(h, batch);
     }
     if (rc == SONIC_OK) rc = sonic_prefill(h, req_win.data(), R, ids.data(), poff.data(), mn.data(), 0);
     if (rc != SONIC_OK && err) *err = sonic_last_error(h);
@@ -215,7 +210,7 @@ void prefill_thread(sonic_dispatch* d, sonic_engine* h) {
                     continue;
                 }
                 if ((int)batch.size() >= d->free_rows[k] || used + r->W > d->pre_cap) break;
-                const long rt = (long)r->prompt.size() + (long)r->draft.size();
+                const long rt = (long)r->prompt.size() + (long)r->own.draft.size();
                 if (d->draft && !batch.empty() && toks + rt > d->tok_cap) break;      // option draft_verify: prompts and drafts together fit one prefill (a request that alone does not is refused by it, by name)
                 d->q.pop_front(); d->queued_windows -= r->W;
                 batch.push_back(r); used += r->W; toks += rt;
@@ -325,41 +320,26 @@ SONIC_API int sonic_dispatch_create(sonic_engine* const* decoders, int n_dec, so
     if (!out) return SONIC_ERR_INVALID;
     *out = nullptr;
     if (!decoders || !prefills || n_dec < 1 || n_pre < 1) return SONIC_ERR_INVALID;
-    int32_t rows = 0, cap = 0;
-    {   // every handle once, all on one weight copy and one device
-        const void* w0 = nullptr; int32_t dev0 = -1;
-        for (int i = 0; i < n_dec + n_pre; ++i) {
-            sonic_engine* h = i < n_dec ? decoders[i] : prefills[i - n_dec];
-            int32_t mb = 0, dev = 0; const void* wid = nullptr;
-            if (!h || sonic_engine_info(h, &mb, nullptr, nullptr, &dev, &wid) != SONIC_OK) return SONIC_ERR_INVALID;
-            for (int j = 0; j < i; ++j) if (h == (j < n_dec ? decoders[j] : prefills[j - n_dec])) return SONIC_ERR_INVALID;
-            if (i == 0) { w0 = wid; dev0 = dev; rows = mb; }
-            if (wid != w0 || dev != dev0) return SONIC_ERR_INVALID;
-            if (i < n_dec) rows = mb < rows ? mb : rows; else cap = (i == n_dec || mb < cap) ? mb : cap;
-        }
-    }
+    sched_handles hs(decoders, n_dec, prefills, n_pre);
+    if (!hs.check()) return SONIC_ERR_INVALID;
+    const int32_t rows = *std::min_element(hs.max_batch.begin(), hs.max_batch.begin() + n_dec), cap = *std::min_element(hs.max_batch.begin() + n_dec, hs.max_batch.end());
     if (rows < 1 || rows > 64 || cap < 1) return SONIC_ERR_INVALID;
-    for (int i = 1; i < n_dec + n_pre; ++i)                     // (a splice between handles of different K would be refused row by row: refuse the set)
-        if (engine_top_logprobs(i < n_dec ? decoders[i] : prefills[i - n_dec]) != engine_top_logprobs(decoders[0]))
-            return engine_thread_fail(SONIC_ERR_INVALID, "sonic_dispatch_create: the handles differ in option top_logprobs (set it on the owner before its slots are created)");
-    for (int i = 0; i < n_dec + n_pre; ++i)
-        if (engine_forced_parallel_on(i < n_dec ? decoders[i] : prefills[i - n_dec]))
-            return engine_thread_fail(SONIC_ERR_INVALID, "sonic_dispatch_create: option forced_parallel is on on a handle: a scoring handle takes no part in the dispatcher");
+    const int K = engine_top_logprobs(decoders[0]);             // (a splice between handles of different K would be refused row by row: refuse the set)
+    if (!hs.every([K](sonic_engine* h) { return engine_top_logprobs(h) == K; }))
+        return engine_thread_fail(SONIC_ERR_INVALID, "sonic_dispatch_create: the handles differ in option top_logprobs (set it on the owner before its slots are created)");
+    if (hs.any(engine_forced_parallel_on))
+        return engine_thread_fail(SONIC_ERR_INVALID, "sonic_dispatch_create: option forced_parallel is on on a handle: a scoring handle takes no part in the dispatcher");
     sonic_dispatch* d = new sonic_dispatch();
     d->dec.assign(decoders, decoders + n_dec); d->pre.assign(prefills, prefills + n_pre);
     d->n_rows = rows; d->pre_cap = cap; d->adaptive_tiles = adaptive_tiles != 0;
-    d->lp = true;
-    for (int i = 0; i < n_dec + n_pre; ++i) d->lp = d->lp && engine_token_logprobs_on(i < n_dec ? decoders[i] : prefills[i - n_dec]);
-    d->lp_w = d->lp ? 1 + 2 * engine_top_logprobs(decoders[0]) : 1;
-    d->bias = true;
-    for (int i = 0; i < n_dec + n_pre; ++i) d->bias = d->bias && engine_request_bias_on(i < n_dec ? decoders[i] : prefills[i - n_dec]);
-    d->samp = true;
-    for (int i = 0; i < n_dec + n_pre; ++i) d->samp = d->samp && engine_sampling_on(i < n_dec ? decoders[i] : prefills[i - n_dec]);
-    d->gram = true;
-    for (int i = 0; i < n_dec + n_pre; ++i) d->gram = d->gram && engine_grammar_on(i < n_dec ? decoders[i] : prefills[i - n_dec]);
-    d->draft = true; d->tok_cap = engine_tok_cap(prefills[0]);
-    for (int i = 0; i < n_dec + n_pre; ++i) d->draft = d->draft && engine_draft_verify_on(i < n_dec ? decoders[i] : prefills[i - n_dec]);
-    for (int i = 0; i < n_pre; ++i) d->tok_cap = std::min(d->tok_cap, engine_tok_cap(prefills[i]));
+    d->lp = hs.every(engine_token_logprobs_on);
+    d->lp_w = d->lp ? 1 + 2 * K : 1;
+    d->bias = hs.every(engine_request_bias_on);
+    d->samp = hs.every(engine_sampling_on);
+    d->gram = hs.every(engine_grammar_on);
+    d->draft = hs.every(engine_draft_verify_on);
+    d->tok_cap = engine_tok_cap(prefills[0]);
+    for (sonic_engine* h : d->pre) d->tok_cap = std::min(d->tok_cap, engine_tok_cap(h));
     d->free_rows.assign(n_dec, rows); d->hand.resize(n_dec);
     for (int i = 0; i < n_dec; ++i) {
         const int rc = sonic_service_begin(d->dec[i]);
@@ -371,12 +351,28 @@ SONIC_API int sonic_dispatch_create(sonic_engine* const* decoders, int n_dec, so
     return SONIC_OK;
 }
 
+// the refusal of a value whose option is not on on every handle; `who` names the entry point (or the armed tensor) that brought it
+static int option_off(const char* who, const char* option) {
+    char m[256]; snprintf(m, sizeof m, "%s: option %s is off on a handle of this dispatcher (set it on the owner before its slots are created)", who, option);
+    return engine_thread_fail(SONIC_ERR_INVALID, m);
+}
+
+// a submit's table arguments, checked (option request_bias - `required`: even for an empty table -, the pointers, the caps and the vocabulary) and copied into *own
+static int take_table(sonic_dispatch* d, const char* who, bool required, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n_seq, ReqValues* own) {
+    if (required && !d->bias) return option_off(who, "request_bias");
+    if (n_seq < 0 || (n_seq > 0 && (!seq_ids || !seq_off || !bias))) return SONIC_ERR_INVALID;
+    if (n_seq == 0) return SONIC_OK;
+    if (!d->bias) return option_off(who, "request_bias");
+    const int rc = engine_bias_validate(d->pre[0], seq_ids, seq_off, bias, n_seq);
+    if (rc == SONIC_OK) own->bias = dispatch_pack::bias_table(seq_ids, seq_off, bias, n_seq);
+    return rc;
+}
+
 // One request of W windows.  Window w: host samples host_pcm[host_off[w] .. host_off[w + 1]) (int16, already peak-normalised over the request, as
 // sonic_stage_pcm takes them) when rings is NULL or rings[w] is NULL, else samples [ring_start[w], ring_start[w] + ring_n[w]) of rings[w] (raw wire
 // PCM, normalised on the device over the request's windows).  Everything is copied before the call returns.
 static int dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, const int64_t* host_off, sonic_ring* const* rings, const int64_t* ring_start,
-                           const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, const int32_t* seq_ids, const int32_t* seq_off,
-                           const float* bias, int n_seq, int64_t* ticket_out, bool sampled = false, float temperature = 0.f, uint64_t seed = 0) {
+                           const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, ReqValues own, int64_t* ticket_out) {
     // the grammar armed on this thread (sonic_load_tensor "grammar.dispatch:<id>"): this submit takes it whatever becomes of it
     struct Armed { sonic_grammar* g; ~Armed() { if (g) engine_grammar_unref(g); } } armed{engine_take_dispatch_grammar()};
     sonic_grammar* gram = armed.g;
@@ -394,28 +390,26 @@ static int dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, const int
         for (int w = 0; w < W; ++w) r->any_ring = r->any_ring || rings[w];
     }
     r->prompt.assign(prompt_ids, prompt_ids + prompt_len); r->max_new = max_new;
-    r->sampled = sampled; r->temperature = temperature; r->seed = seed;
-    if (n_seq > 0) { r->b_off.assign(seq_off, seq_off + n_seq + 1); r->b_ids.assign(seq_ids + seq_off[0], seq_ids + seq_off[n_seq]); r->b_val.assign(bias, bias + n_seq);
-                     for (auto& o : r->b_off) o -= seq_off[0]; }
+    r->own = std::move(own);
     std::unique_lock<std::mutex> lk(d->mu);
     if (d->stop) return SONIC_ERR_INVALID;
     if (d->failed) return d->failed;
     if (n_draft > 0) {
-        if (!d->draft) return engine_thread_fail(SONIC_ERR_INVALID, "draft.dispatch: option draft_verify is off on a handle of this dispatcher (set it on the owner before its slots are created)");
+        if (!d->draft) return option_off("draft.dispatch", "draft_verify");
         if (n_draft > max_new - 1) {
             char m[200]; snprintf(m, sizeof m, "draft.dispatch: the draft holds %d ids, the request's budget of %d tokens leaves room for %d (the last token is the model's own; nothing is truncated)", n_draft, max_new, max_new - 1);
             return engine_thread_fail(SONIC_ERR_INVALID, m);
         }
-        if (n_seq > 0 || (sampled && temperature > 0.f) || gram)
+        if (!r->own.bias.val.empty() || (r->own.sampled && r->own.temperature > 0.f) || gram)
             return engine_thread_fail(SONIC_ERR_INVALID, "draft.dispatch: a drafted request carries no bias table, temperature > 0 or grammar (the verify pass applies the handle's processors only)");
-        r->draft.assign(draft, draft + n_draft);
+        r->own.draft.assign(draft, draft + n_draft);
     }
     if (gram) {
-        if (!d->gram) return engine_thread_fail(SONIC_ERR_INVALID, "grammar.dispatch: option grammar is off on a handle of this dispatcher (set it on the owner before its slots are created)");
+        if (!d->gram) return option_off("grammar.dispatch", "grammar");
         const void* wid = nullptr;
         (void)sonic_engine_info(d->pre[0], nullptr, nullptr, nullptr, nullptr, &wid);
         if (engine_grammar_owner(gram) != wid) return engine_thread_fail(SONIC_ERR_INVALID, "grammar.dispatch: the grammar is not a live grammar of this dispatcher's weight owner");
-        r->gram = gram; armed.g = nullptr;                          // (the request keeps the reference until it completes)
+        r->own.gram = gram; armed.g = nullptr;                      // (the request keeps the reference until it completes)
     }
     r->ticket = d->next_ticket++;
     d->q.push_back(r); d->queued_windows += W; ++d->outstanding;
@@ -426,7 +420,7 @@ static int dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, const int
 
 SONIC_API int sonic_dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, const int64_t* host_off, sonic_ring* const* rings, const int64_t* ring_start,
                                     const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, int64_t* ticket_out) {
-    return dispatch_submit(d, host_pcm, host_off, rings, ring_start, ring_n, W, prompt_ids, prompt_len, max_new, nullptr, nullptr, nullptr, 0, ticket_out);
+    return dispatch_submit(d, host_pcm, host_off, rings, ring_start, ring_n, W, prompt_ids, prompt_len, max_new, ReqValues(), ticket_out);
 }
 // sonic_dispatch_submit with the request's own sequence-bias table (n_seq entries in sonic_set_request_bias's form for one request; the request owns a copy): the
 // prefill thread hands it to the prefill of the batch the request lands in.  SONIC_ERR_INVALID unless every handle of the dispatcher has option request_bias on,
@@ -435,10 +429,9 @@ SONIC_API int sonic_dispatch_submit_bias(sonic_dispatch* d, const int16_t* host_
                                          const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, const int32_t* seq_ids,
                                          const int32_t* seq_off, const float* bias, int n_seq, int64_t* ticket_out) {
     if (!d) return SONIC_ERR_INVALID;
-    if (!d->bias) return engine_thread_fail(SONIC_ERR_INVALID, "sonic_dispatch_submit_bias: option request_bias is off on a handle of this dispatcher (set it on the owner before its slots are created)");
-    if (n_seq < 0 || (n_seq > 0 && (!seq_ids || !seq_off || !bias))) return SONIC_ERR_INVALID;
-    if (n_seq > 0) { const int rc = engine_bias_validate(d->pre[0], seq_ids, seq_off, bias, n_seq); if (rc != SONIC_OK) return rc; }
-    return dispatch_submit(d, host_pcm, host_off, rings, ring_start, ring_n, W, prompt_ids, prompt_len, max_new, seq_ids, seq_off, bias, n_seq, ticket_out);
+    ReqValues own;
+    { const int rc = take_table(d, "sonic_dispatch_submit_bias", true, seq_ids, seq_off, bias, n_seq, &own); if (rc != SONIC_OK) return rc; }
+    return dispatch_submit(d, host_pcm, host_off, rings, ring_start, ring_n, W, prompt_ids, prompt_len, max_new, std::move(own), ticket_out);
 }
 
 // sonic_dispatch_submit with the request's own (temperature, seed), and its sequence-bias table where one is given (n_seq > 0): SONIC_ERR_INVALID unless every
@@ -447,12 +440,12 @@ SONIC_API int sonic_dispatch_submit_sampled(sonic_dispatch* d, const int16_t* ho
                                             const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, float temperature, uint64_t seed,
                                             const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n_seq, int64_t* ticket_out) {
     if (!d) return SONIC_ERR_INVALID;
-    if (!d->samp) return engine_thread_fail(SONIC_ERR_INVALID, "sonic_dispatch_submit_sampled: option sampling is off on a handle of this dispatcher (set it on the owner before its slots are created)");
+    if (!d->samp) return option_off("sonic_dispatch_submit_sampled", "sampling");
     { const int rc = engine_sampling_validate(temperature); if (rc != SONIC_OK) return rc; }
-    if (n_seq < 0 || (n_seq > 0 && (!seq_ids || !seq_off || !bias))) return SONIC_ERR_INVALID;
-    if (n_seq > 0 && !d->bias) return engine_thread_fail(SONIC_ERR_INVALID, "sonic_dispatch_submit_sampled: option request_bias is off on a handle of this dispatcher (set it on the owner before its slots are created)");
-    if (n_seq > 0) { const int rc = engine_bias_validate(d->pre[0], seq_ids, seq_off, bias, n_seq); if (rc != SONIC_OK) return rc; }
-    return dispatch_submit(d, host_pcm, host_off, rings, ring_start, ring_n, W, prompt_ids, prompt_len, max_new, seq_ids, seq_off, bias, n_seq, ticket_out, true, temperature, seed);
+    ReqValues own;
+    own.sampled = true; own.temperature = temperature; own.seed = seed;
+    { const int rc = take_table(d, "sonic_dispatch_submit_sampled", false, seq_ids, seq_off, bias, n_seq, &own); if (rc != SONIC_OK) return rc; }
+    return dispatch_submit(d, host_pcm, host_off, rings, ring_start, ring_n, W, prompt_ids, prompt_len, max_new, std::move(own), ticket_out);
 }
 
 // a request that is still queued leaves the queue (it completes with status SONIC_ERR_INVALID, "cancelled"); one that has reached a handle runs on

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/sonic_hip.h"
+#include "sched_engine.h"      // what dispatch.cpp and pipeline.cpp call: declared once, seen by the definitions
 #include "common.h"
 #include "kernels.h"
 

@@ -11,7 +11,7 @@
 //     chunks (sonic_service_step: blocking, sleeps on an event), fetches the rows of a block the moment the pipelined check shows every row of
 //     it finished, completes the batch's ticket.  An EMPTY loop leaves the next batch to a loop that is running part-filled (two batches in one
 //     64-row loop stream the weights once).
-// No thread polls: every wait is a condition variable or a blocking HIP event inside the engine.  Only the C ABI of include/sonic_hip.h is used (and engine_token_logprobs_on).
+// No thread polls: every wait is a condition variable or a blocking HIP event inside the engine.  Only the C ABI of include/sonic_hip.h is used (and the option queries of sched_engine.h).
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -26,12 +26,7 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/sonic_hip.h"
-extern "C" int engine_token_logprobs_on(sonic_engine* e);   // engine.cpp
-extern "C" int engine_top_logprobs(sonic_engine* e);        // engine.cpp: option top_logprobs of this handle
-extern "C" int engine_forced_parallel_on(sonic_engine* e);  // engine.cpp: option forced_parallel of this handle (a scoring handle: refused here)
-extern "C" int engine_draft_verify_on(sonic_engine* e);     // engine_generation.cpp: option draft_verify of this handle (the bulk pipeline takes no drafts: refused here)
-extern "C" int engine_fail(sonic_engine* e, int code, const char* msg);   // engine.cpp: the message on a handle (sonic_last_error)
+#include "sched_engine.h"
 
 namespace {
 
@@ -219,28 +214,17 @@ SONIC_API int sonic_pipeline_create(sonic_engine* const* decoders, int n_dec, so
     *out = nullptr;
     if (!decoders || !prefills || n_dec < 1 || n_pre < 1 || block < 1 || block > 64 || rows_per_decoder < block || rows_per_decoder > 64) return SONIC_ERR_INVALID;
     // every handle once, all on one weight copy and one device; a decoding handle holds rows_per_decoder rows, a prefill handle one block
-    {
-        const void* w0 = nullptr; int32_t dev0 = -1;
-        for (int i = 0; i < n_dec + n_pre; ++i) {
-            sonic_engine* h = i < n_dec ? decoders[i] : prefills[i - n_dec];
-            int32_t mb = 0, dev = 0; const void* wid = nullptr;
-            if (!h || sonic_engine_info(h, &mb, nullptr, nullptr, &dev, &wid) != SONIC_OK) return SONIC_ERR_INVALID;
-            for (int j = 0; j < i; ++j) if (h == (j < n_dec ? decoders[j] : prefills[j - n_dec])) return SONIC_ERR_INVALID;
-            if (i == 0) { w0 = wid; dev0 = dev; }
-            if (wid != w0 || dev != dev0) return SONIC_ERR_INVALID;
-            if (mb < (i < n_dec ? rows_per_decoder : block)) return SONIC_ERR_INVALID;
-        }
-    }
+    sched_handles hs(decoders, n_dec, prefills, n_pre);
+    if (!hs.check()) return SONIC_ERR_INVALID;
+    for (size_t i = 0; i < hs.h.size(); ++i)
+        if (hs.max_batch[i] < (i < hs.n_dec ? rows_per_decoder : block)) return SONIC_ERR_INVALID;
     // the bulk pipeline's arrays stay narrow (sonic_pipeline_submit_lp: one float per token): a handle whose records are wide is refused, by name
-    for (int i = 0; i < n_dec + n_pre; ++i)
-        if (engine_top_logprobs(i < n_dec ? decoders[i] : prefills[i - n_dec]) > 0)
-            return engine_fail(decoders[0], SONIC_ERR_INVALID, "sonic_pipeline_create: option top_logprobs is on on a handle: the bulk pipeline carries one log-probability per token (set top_logprobs to 0, or use the dispatcher)");
-    for (int i = 0; i < n_dec + n_pre; ++i)
-        if (engine_forced_parallel_on(i < n_dec ? decoders[i] : prefills[i - n_dec]))
-            return engine_fail(decoders[0], SONIC_ERR_INVALID, "sonic_pipeline_create: option forced_parallel is on on a handle: a scoring handle takes no part in the bulk pipeline");
-    for (int i = 0; i < n_dec + n_pre; ++i)
-        if (engine_draft_verify_on(i < n_dec ? decoders[i] : prefills[i - n_dec]))
-            return engine_fail(decoders[0], SONIC_ERR_INVALID, "sonic_pipeline_create: option draft_verify is on on a handle: the bulk pipeline takes no drafts (stage them on a handle's whole batches or its prefill slot)");
+    if (hs.any([](sonic_engine* h) { return engine_top_logprobs(h) > 0; }))
+        return engine_fail(decoders[0], SONIC_ERR_INVALID, "sonic_pipeline_create: option top_logprobs is on on a handle: the bulk pipeline carries one log-probability per token (set top_logprobs to 0, or use the dispatcher)");
+    if (hs.any(engine_forced_parallel_on))
+        return engine_fail(decoders[0], SONIC_ERR_INVALID, "sonic_pipeline_create: option forced_parallel is on on a handle: a scoring handle takes no part in the bulk pipeline");
+    if (hs.any(engine_draft_verify_on))
+        return engine_fail(decoders[0], SONIC_ERR_INVALID, "sonic_pipeline_create: option draft_verify is on on a handle: the bulk pipeline takes no drafts (stage them on a handle's whole batches or its prefill slot)");
     sonic_pipeline* p = new sonic_pipeline();
     p->dec.assign(decoders, decoders + n_dec); p->pre.assign(prefills, prefills + n_pre);
     p->block = block; p->blocks_per_dec = rows_per_decoder / block;

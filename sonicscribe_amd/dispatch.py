@@ -77,6 +77,15 @@ def fits_tokens(engine, used: int, req: "Request") -> bool:
     return used + request_tokens(req) <= int(engine.tok_cap)
 
 
+def batch_windows(reqs):
+    """the windows of a batch's requests in a row -> (segs, req_win): request i's are segs[req_win[i]:req_win[i + 1]]"""
+    segs, req_win = [], [0]
+    for r in reqs:
+        segs.extend(r.windows)
+        req_win.append(len(segs))
+    return segs, req_win
+
+
 class _Replica:
     def __init__(self, engine, index: int, slots: Sequence[Any] = ()):
         self.engine, self.index = engine, index
@@ -148,10 +157,7 @@ class _Replica:
     @staticmethod
     def _call(engine, reqs: List[Request], kw: dict) -> list:
         """one engine call for `reqs` with their own values' keywords `kw` -> one result per request"""
-        segs, req_win = [], [0]
-        for r in reqs:
-            segs.extend(r.windows)
-            req_win.append(len(segs))
+        segs, req_win = batch_windows(reqs)
         if not any(r.want_logprobs for r in reqs):       # (the keyword only goes to the engine when somebody asked: duck-typed engines need not know it)
             ids, _ = engine.transcribe_batch(segs, [r.prompt for r in reqs], [r.max_new for r in reqs], req_win=req_win, **kw)
             return ids
@@ -307,10 +313,7 @@ class _ContinuousReplica:
             return batch, k
 
     def _prefill(self, eng, batch: List[Request]):
-        segs, req_win = [], [0]
-        for r in batch:
-            segs.extend(r.windows)
-            req_win.append(len(segs))
+        segs, req_win = batch_windows(batch)
         if self.adaptive_tiles:
             with self.cv:
                 busy = sum(self.n_rows - f for f in self.free) > len(batch)        # rows running or reserved besides this batch's own
@@ -503,17 +506,10 @@ class _NativeContinuousReplica:
     def load(self) -> int:
         return self._stats()[2]
 
-    def put(self, req: Request):
+    def _pack_audio(self, wins):
+        """a request's windows as the arrays every sonic_dispatch_submit* takes: (host_pcm, host_off, rings, ring_start, ring_n), the last three None without a ring slice"""
         import ctypes as C
-        from .engine import RingSlice, _p
-        if req.want_logprobs and not self.lp:
-            raise ValueError(LOGPROBS_OFF)
-        reqvalues.refuse_unsupported(req, self.admits)
-        check_draft(req, self.engines)
-        if req.bias:
-            req.bias.check_vocab(self.engine.dims.vocab)  # (the Python replica leaves this to Engine.set_request_bias, in its prefill thread)
-        dev_gram = None if req.grammar is None else req.grammar.on(self.engine)
-        wins = req.windows
+        from .engine import RingSlice
         W = len(wins)
         offs = np.zeros(W + 1, np.int64)
         host, rings, start, n, any_ring = [], [], np.zeros(W, np.int64), np.zeros(W, np.int32), False
@@ -529,24 +525,40 @@ class _NativeContinuousReplica:
                 offs[i + 1] = offs[i] + len(a)
         pcm = np.concatenate(host) if host and offs[-1] > 0 else np.zeros(1, np.int16)
         ring_arr = (C.c_void_p * W)(*rings) if any_ring else None
+        return (pcm, offs, ring_arr, start, n) if any_ring else (pcm, offs, None, None, None)
+
+    def put(self, req: Request):
+        import ctypes as C
+        from .engine import _p, pack_dispatch_draft
+        if req.want_logprobs and not self.lp:
+            raise ValueError(LOGPROBS_OFF)
+        reqvalues.refuse_unsupported(req, self.admits)
+        check_draft(req, self.engines)
+        if req.bias:
+            req.bias.check_vocab(self.engine.dims.vocab)  # (the Python replica leaves this to Engine.set_request_bias, in its prefill thread)
+        dev_gram = None if req.grammar is None else req.grammar.on(self.engine)
+        pcm, offs, ring_arr, start, n = self._pack_audio(req.windows)
         prompt = np.ascontiguousarray(req.prompt, dtype=np.int32)
         t = C.c_int64(0)
-        # everything that can raise is packed before the grammar is armed: the arm is the call right ahead of the submit
+        # everything that can raise is packed before the grammar is armed: the arm is the call right ahead of the submit.  The three entry points share their leading
+        # arguments: picked here are the entry point and its own tail (a temperature takes the table along)
         b_ids, b_off, b_val = req.bias.table() if req.bias else (None, None, np.zeros(0, np.float32))
+        table = (_p(b_ids), _p(b_off), _p(b_val) if len(b_val) else None, len(b_val), C.byref(t))
         if req.sampling:
             from . import sampling as _sampling
-            temp, seed = _sampling.check_temperature(req.sampling[0]), _sampling.check_seed(req.sampling[1])
+            submit, tail = self.lib.sonic_dispatch_submit_sampled, (_sampling.check_temperature(req.sampling[0]), _sampling.check_seed(req.sampling[1])) + table
+        elif req.bias:
+            submit, tail = self.lib.sonic_dispatch_submit_bias, table
+        else:
+            submit, tail = self.lib.sonic_dispatch_submit, (C.byref(t),)
         if dev_gram is not None and dev_gram.h is None:
             raise ValueError("grammar: the grammar has been closed")
-        draft_words = None
-        if req.draft:
-            from .engine import pack_dispatch_draft
-            draft_words = pack_dispatch_draft(req.draft)     # sonic_load_tensor "draft.dispatch": n | ids
+        draft_words = pack_dispatch_draft(req.draft) if req.draft else None      # sonic_load_tensor "draft.dispatch": n | ids
         with self.lock:
             if self.stop:
                 raise RuntimeError("ASR engine is closed")
             if dev_gram is not None:
-                # this thread's next submit, whichever of the three below, carries the grammar (sonic_load_tensor "grammar.dispatch:<id>": the owner's registry and a
+                # this thread's next submit, whichever of the three, carries the grammar (sonic_load_tensor "grammar.dispatch:<id>": the owner's registry and a
                 # thread-local, never the lock of an engine - the decode loop holds its handle's for a chunk at a time, and put() must not wait for it)
                 one = np.zeros(1, np.int32)
                 if self.lib.sonic_load_tensor(self.engine.h, f"grammar.dispatch:{int(dev_gram.id)}".encode(), _p(one), 2, (C.c_int64 * 1)(0), 1) != 0:
@@ -554,16 +566,7 @@ class _NativeContinuousReplica:
             if draft_words is not None:                  # ... and the draft, the same way ("draft.dispatch": a thread-local, no engine lock)
                 if self.lib.sonic_load_tensor(self.engine.h, b"draft.dispatch", _p(draft_words), 2, (C.c_int64 * 1)(len(draft_words)), 1) != 0:
                     raise ValueError("draft: " + (self.lib.sonic_last_error(None) or b"").decode())
-            if req.sampling:
-                rc = self.lib.sonic_dispatch_submit_sampled(self.h, _p(pcm), _p(offs), ring_arr, _p(start) if any_ring else None, _p(n) if any_ring else None, W,
-                                                            _p(prompt), len(prompt), int(req.max_new), temp, seed,
-                                                            _p(b_ids), _p(b_off), _p(b_val) if len(b_val) else None, len(b_val), C.byref(t))
-            elif req.bias:
-                rc = self.lib.sonic_dispatch_submit_bias(self.h, _p(pcm), _p(offs), ring_arr, _p(start) if any_ring else None, _p(n) if any_ring else None, W,
-                                                         _p(prompt), len(prompt), int(req.max_new), _p(b_ids), _p(b_off), _p(b_val), len(b_val), C.byref(t))
-            else:
-                rc = self.lib.sonic_dispatch_submit(self.h, _p(pcm), _p(offs), ring_arr, _p(start) if any_ring else None, _p(n) if any_ring else None, W,
-                                                    _p(prompt), len(prompt), int(req.max_new), C.byref(t))
+            rc = submit(self.h, _p(pcm), _p(offs), ring_arr, _p(start), _p(n), len(req.windows), _p(prompt), len(prompt), int(req.max_new), *tail)
             if rc != 0 and (req.bias or req.sampling or req.grammar or req.draft):
                 msg = (self.lib.sonic_last_error(None) or b"").decode()
                 if "request_bias" in msg or "sonic_dispatch_submit_bias" in msg or "sampling" in msg or "sonic_dispatch_submit_sampled" in msg or "grammar" in msg or "draft" in msg:
@@ -571,8 +574,7 @@ class _NativeContinuousReplica:
             if rc != 0:
                 raise RuntimeError("ASR engine failed" if rc not in (1,) else "ASR engine is closed or the request is malformed")
             self.pending[int(t.value)] = req
-        ticket = int(t.value)
-        req.future.add_done_callback(lambda f, ticket=ticket: f.cancelled() and self.h and self.lib.sonic_dispatch_cancel(self.h, ticket))
+        req.future.add_done_callback(lambda f, ticket=int(t.value): f.cancelled() and self.h and self.lib.sonic_dispatch_cancel(self.h, ticket))
 
     def _complete_loop(self):
         import ctypes as C
@@ -717,10 +719,7 @@ class _BulkReplica:
         return batch
 
     def _submit(self, batch: List[Request]):
-        segs, req_win = [], [0]
-        for r in batch:
-            segs.extend(r.windows)
-            req_win.append(len(segs))
+        segs, req_win = batch_windows(batch)
         if any(r.want_logprobs for r in batch):
             return self.pipe.submit([r.prompt for r in batch], [r.max_new for r in batch], segments=segs, req_win=req_win, want_logprobs=True)
         return self.pipe.submit([r.prompt for r in batch], [r.max_new for r in batch], segments=segs, req_win=req_win)

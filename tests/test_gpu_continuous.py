@@ -334,3 +334,55 @@ def test_native_dispatcher_failure_cancel_and_close_paths():
         else:
             assert "closed" in str(f.exception())
     assert 1 <= n_ok <= 16
+
+
+@pytest.mark.parametrize("native", [True, False], ids=["native-dispatch", "python-dispatch"])
+def test_mixed_per_request_values_in_one_prefill(native):
+    """Six requests that each bring another kind of value of their own - a bias table that binds, a temperature with a seed, a grammar, a draft, a table plus a
+    temperature, nothing - prefilled TOGETHER: row i of the prefill must get request i's values and nobody else's.  Each result is its solo run's on the same
+    engine, ids and log-probability bits (rows are independent).  The mix is forced, not hoped for: one prefill slot, and a plug request of max_batch
+    windows is prefilling while the six are submitted; a run in which every request was prefilled alone fails."""
+    from sonicscribe_amd.dispatch import Dispatcher
+    from sonicscribe_amd.grammar import CompiledGrammar
+    from sonicscribe_amd.reqbias import RequestBias
+    from test_gpu_draft import _same, make as make_with_options
+    from test_gpu_grammar import grammar_a
+    d = spec.TINY
+    e = make_with_options(max_batch=8, opts=(("request_bias", 1), ("sampling", 1), ("grammar", 1)))      # + token_logprobs and draft_verify
+    try:
+        segs = [synth.synth_pcm(700 + i, n) for i, n in enumerate((48000, 80000, 64000, 96000, 56000, 72000))]
+        prompts = [prompt_for(d, len(s)) for s in segs]
+        budgets = [9, 12, 11, 14, 10, 7]
+        plain = [e.transcribe_batch([segs[i]], [prompts[i]], [budgets[i]])[0][0] for i in range(6)]
+        gram = CompiledGrammar(grammar_a(), [e])
+        table = lambda i: RequestBias([[[int(plain[i][0]), 210], 1000.0], [[210, 211], 1000.0]])      # binds behind the request's first id
+        own = [dict(bias=table(0)), dict(sampling=(0.7, 1234)), dict(grammar=gram), dict(draft=[int(t) for t in plain[3][:6]]), dict(bias=table(4), sampling=(0.7, 99)), {}]
+        keyword = {"bias": "request_bias", "sampling": "request_sampling", "grammar": "request_grammar", "draft": "request_draft"}
+        solo = []
+        for i in range(6):
+            kw = {keyword[k]: [v.on(e) if k == "grammar" else v] for k, v in own[i].items()}
+            ids, _, lps = e.transcribe_batch([segs[i]], [prompts[i]], [budgets[i]], want_logprobs=True, **kw)
+            solo.append((ids[0], lps[0]))
+        assert not np.array_equal(solo[0][0], plain[0]) and not np.array_equal(solo[2][0], plain[2]), "the table or the grammar binds nowhere: the test shows nothing"
+        assert np.array_equal(solo[3][0], plain[3]) and np.array_equal(solo[5][0], plain[5])
+        plug = [synth.synth_pcm(690, 128000)] * e.max_batch                                               # max_batch windows of 8 s behind one prompt
+        plug_prompt = [1, 17, 23, 5] + [d.audio_token_id] * spec.audio_token_count(e.max_batch * spec.valid_frames(128000)) + [7, 301, 302, 303, 9, 11]
+        slots = [e.slot(), e.slot()]
+        disp = Dispatcher([e], slots=[slots], continuous=True, native=native, decoders=2)                   # two decoding handles, ONE prefill slot
+        rep = disp.replicas[0]
+        assert type(rep).__name__ == ("_NativeContinuousReplica" if native else "_ContinuousReplica") and len(rep.prefill_engines) == 1
+        first = disp.submit(plug, plug_prompt, 4)
+        futs = [disp.submit([segs[i]], prompts[i], budgets[i], want_logprobs=True, **own[i]) for i in range(6)]
+        res = [f.result(timeout=120) for f in futs]
+        assert len(first.result(timeout=120)) >= 1
+        batches = rep.batches
+        disp.close()
+        for s in slots:
+            s.close()
+        gram.close()
+        print(f"mixed per-request values ({'native' if native else 'python'} dispatcher): {batches} prefill batches for the plug and the six requests")
+        for i in range(6):
+            assert np.array_equal(res[i][0], solo[i][0]) and _same(res[i][1], solo[i][1]), (native, i, res[i][0], solo[i][0])
+        assert batches < 7, f"{batches} prefill batches for 7 requests: every request was prefilled alone, the mix was not reached"
+    finally:
+        e.close()
