@@ -556,7 +556,7 @@ SONIC_API int sonic_stage_mixed(sonic_engine* e, const int16_t* host_pcm, const 
  *   table, a temperature > 0 or a grammar (undrafted requests of the same batch may carry them).
  *   A drafted request r with prompt P_r and draft d[0 .. D): the prefill runs over prompt || d, the K/V rows written as a prefill writes them.  Draft position n is
  *   decided from the hidden row at position P - 1 + n: final norm, the tied lm_head as the prefill-family GEMM into the chunk buffer of the parallel forced run
- *   ("score_chunk_rows" rows per launch), one block of verify_rows_kernel per row.  s_n = the row's logits after the handle's processors (sonic_set_generation, HF's
+ *   ("score_chunk_rows" rows per launch), one block of rows_kernel per row.  s_n = the row's logits after the handle's processors (sonic_set_generation, HF's
  *   order) with history prompt || d[0 .. n); t_n = the first maximum of s_n (ties: the lower id; all -inf: 0); a_r = the least n with t_n != d[n], or D.  The request
  *   then stands exactly where a prefill of prompt || d[0 .. a) would have left it, with its first a tokens and their log-probability records already written:
  *   out_ids[r][0 .. a) = d[0 .. a); record n = log_softmax(s_n)[d[n]] and, with "top_logprobs" = K, the K alternatives of s_n, in the handle's layout of 1 + 2K
@@ -576,7 +576,7 @@ SONIC_API int sonic_stage_mixed(sonic_engine* e, const int16_t* host_pcm, const 
  *   thread's NEXT sonic_dispatch_submit* with that draft (n = 0: none) - no engine lock is taken, as for "grammar.dispatch:<id>"; the ids are checked at the arm, the
  *   budget (n <= max_new - 1) and the request's other values at the submit, which refuses unless every handle of the dispatcher has the option on.  With the option
  *   on, the prefill batcher counts prompt + draft tokens against one prefill's capacity.  sonic_pipeline_create refuses a handle with the option on, by name.
- *   test hook: on such a handle sonic_test_greedy_guard WITH force_ids sends its rows to verify_rows_kernel - the slabs become the logits row as on a scoring handle;
+ *   test hook: on such a handle sonic_test_greedy_guard WITH force_ids sends its rows to rows_kernel (its choosing instantiations) - the slabs become the logits row as on a scoring handle;
  *   row b is one draft position with history hist[b][0 .. hist_len[b]) and draft id force_ids[b]; tok_out[b] = t, lp_out B records of 1 + 2K floats; neutral guard
  *   values launch the unguarded instantiation; B may exceed 64 (up to 4096). */
 SONIC_API int sonic_set_forced_ids(sonic_engine* e, const int32_t* ids, int R, int ld);

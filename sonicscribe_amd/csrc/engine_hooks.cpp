@@ -527,48 +527,60 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
     }
     return SONIC_OK;
 }
-// sonic_test_greedy_lp on a handle with option forced_parallel on: the rows go to score_rows_kernel (score.hip) instead.  The slabs are summed over ksplit
-// in the greedy kernel's order and rounded to the handle's element type: those values are the logits row the kernel reads, and logits_out returns them.  force_ids is
-// required; tok_out holds the forced ids, lp_out B records of 1 + 2K floats.  B may exceed 64 on this route (one block per row); mpad stays the slab row stride
-static int test_score(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const int32_t* force_ids, int32_t* tok_out, float* logits_out, float* lp_out) {
-    if (ksplit < 1 || ksplit > 8 || B < 1 || B > 4096 || mpad < B || V < 4 || V % 4 || V > (1 << 24)) return fail(e, SONIC_ERR_INVALID, "bad score test shape");
-    if (!force_ids) return fail(e, SONIC_ERR_INVALID, "forced_parallel: the score rows need their forced ids");
+// The frame of the two hooks that send their rows to rows_kernel (rows.hip) instead of the greedy kernel.  The slabs are summed over ksplit in the greedy kernel's order
+// and rounded to the handle's element type: those values are the logits row the kernel reads, and logits_out returns them.  B may exceed 64 on these routes (one block
+// per row); mpad stays the slab row stride.  rows_check: the shape (the hook's own words), the hook's own refusal, the forced ids.  rows_run: `plan` = the rows'
+// B-word arrays, target | rec and, with `choose`, | hrow | hlen; `hist` (choose only; may be empty) and gt's suppress list go up beside it; tok_out = out_ids
+// (the forced ids), or with `choose` the kernel's choices; lp_out (optional) = B records of 1 + 2K floats
+static int rows_check(sonic_engine* e, const char* shape_msg, const char* refusal, int ksplit, int mpad, int V, int B, const int32_t* force_ids) {
+    if (ksplit < 1 || ksplit > 8 || B < 1 || B > 4096 || mpad < B || V < 4 || V % 4 || V > (1 << 24)) return fail(e, SONIC_ERR_INVALID, "%s", shape_msg);
+    if (refusal) return fail(e, SONIC_ERR_INVALID, "%s", refusal);
     for (int b = 0; b < B; ++b) if (force_ids[b] < 0 || force_ids[b] >= V) return fail(e, SONIC_ERR_INVALID, "forced id %d out of vocabulary", force_ids[b]);
-    const int K = e->opt_top_logprobs, W = 1 + 2 * K, dt = e->f32 ? DT_F32 : e->dt;
-    TmpBuf tb(e->st);
-    float* dl = up_f32(e, tb, slabs, (size_t)ksplit * mpad * V);
-    unsigned char* rows = tb.get<unsigned char>((size_t)B * V * (e->f32 ? 4 : 2));
-    int* plan = tb.get<int>((size_t)2 * B); int* ids = tb.get<int>(B);
-    float* lp = tb.get<float>((size_t)B * W); float* dump = logits_out ? tb.get<float>((size_t)B * V) : nullptr;
-    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
-    std::vector<int> h((size_t)2 * B);
-    for (int b = 0; b < B; ++b) { h[b] = force_ids[b]; h[B + b] = b; }      // record b = sequence b, token 0 (out_ld = 1)
-    HIPC(e, h2d(e, plan, h.data(), h.size() * 4));
-    launch_score_slab_rows(dl, ksplit, mpad, V, B, rows, dt, e->st);
-    ScoreArgs a{};
-    a.logits = rows; a.ld = V; a.V = V; a.n = B; a.dt = dt; a.target = plan; a.rec = plan + B; a.out_ids = ids; a.out_lp = lp; a.topk = K; a.dump = dump; a.out_ld = 1; a.R = B;
-    launch_score_rows(a, e->st);
-    HIPC(e, stream_sync(e));
-    HIPC(e, hipGetLastError());
-    HIPC(e, d2h(e, tok_out, ids, (size_t)B * 4));
-    if (logits_out) HIPC(e, d2h(e, logits_out, dump, (size_t)B * V * 4));
-    HIPC(e, d2h(e, lp_out, lp, (size_t)B * W * 4));
     return SONIC_OK;
 }
-// sonic_test_greedy_guard with forced ids on a handle with option draft_verify on: the rows go to verify_rows_kernel (verify.hip).  Row b is one draft
-// position: its history is hist[b * hist_ld .. + hist_len[b]), its draft id force_ids[b].  The slabs become the logits row as on the score route above; tok_out[b] = the
-// kernel's choice (the first maximum of the processed scores), lp_out[b * (1 + 2K) ..] = the record of force_ids[b].  Neutral parameters and no history launch the
-// unguarded instantiation.  B may exceed 64 (one block per row)
+static int rows_run(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, int dt, int K, const std::vector<int>& plan, bool choose, const std::vector<int>& hist,
+                    const GuardTest* gt, int32_t* tok_out, float* logits_out, float* lp_out) {
+    const int W = 1 + 2 * K;
+    TmpBuf tb(e->st);
+    float* dl = up_f32(e, tb, slabs, (size_t)ksplit * mpad * V);
+    unsigned char* rows = tb.get<unsigned char>((size_t)B * V * (dt == DT_F32 ? 4 : 2));
+    int* dplan = tb.get<int>(plan.size()); int* dh = tb.get<int>(hist.size()); int* gsup = tb.get<int>(256); int* tok = tb.get<int>(B);
+    float* lp = tb.get<float>((size_t)B * W); float* dump = logits_out ? tb.get<float>((size_t)B * V) : nullptr;
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    HIPC(e, h2d(e, dplan, plan.data(), plan.size() * 4));
+    if (!hist.empty()) HIPC(e, h2d(e, dh, hist.data(), hist.size() * 4));
+    if (gt && gt->n_suppress > 0) HIPC(e, h2d(e, gsup, gt->suppress, (size_t)gt->n_suppress * 4));
+    launch_score_slab_rows(dl, ksplit, mpad, V, B, rows, dt, e->st);
+    RowsArgs a{};
+    a.logits = rows; a.ld = V; a.V = V; a.n = B; a.dt = dt; a.target = dplan; a.rec = dplan + B; a.out_lp = lp; a.topk = K; a.dump = dump; a.out_ld = 1; a.R = B;
+    if (choose) { a.choice = tok; a.lp_by_row = true; a.hrow = dplan + 2 * B; a.hlen = dplan + 3 * B; } else a.out_ids = tok;
+    if (gt) { a.hist = dh; a.hist_ld = std::max(gt->hist_ld, 1); a.rep_penalty = gt->penalty; a.ngram = gt->ngram; a.suppress = gsup; a.n_suppress = gt->n_suppress; }
+    launch_rows(a, e->st);
+    HIPC(e, stream_sync(e));
+    HIPC(e, hipGetLastError());
+    HIPC(e, d2h(e, tok_out, tok, (size_t)B * 4));
+    if (logits_out) HIPC(e, d2h(e, logits_out, dump, (size_t)B * V * 4));
+    if (lp_out) HIPC(e, d2h(e, lp_out, lp, (size_t)B * W * 4));
+    return SONIC_OK;
+}
+// sonic_test_greedy_lp on a handle with option forced_parallel on: rows_kernel<T, false, ...>.  force_ids is required; tok_out holds the forced ids
+static int test_score(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const int32_t* force_ids, int32_t* tok_out, float* logits_out, float* lp_out) {
+    TRY(rows_check(e, "bad score test shape", force_ids ? nullptr : "forced_parallel: the score rows need their forced ids", ksplit, mpad, V, B, force_ids));
+    std::vector<int> plan((size_t)2 * B);
+    for (int b = 0; b < B; ++b) { plan[b] = force_ids[b]; plan[B + b] = b; }      // record b = sequence b, token 0 (out_ld = 1)
+    return rows_run(e, slabs, ksplit, mpad, V, B, e->f32 ? DT_F32 : e->dt, e->opt_top_logprobs, plan, false, {}, nullptr, tok_out, logits_out, lp_out);
+}
+// sonic_test_greedy_guard with forced ids on a handle with option draft_verify on: rows_kernel<T, true, ...>.  Row b is one draft position: its
+// history is hist[b * hist_ld .. + hist_len[b]), its draft id force_ids[b]; tok_out[b] = the kernel's choice (the first maximum of the processed scores),
+// lp_out[b * (1 + 2K) ..] = the record of force_ids[b].  Neutral parameters and no history launch the unguarded instantiation
 static int test_verify(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const GuardTest& gt, const int32_t* force_ids, int32_t* tok_out, float* logits_out, float* lp_out) {
-    if (ksplit < 1 || ksplit > 8 || B < 1 || B > 4096 || mpad < B || V < 4 || V % 4 || V > (1 << 24)) return fail(e, SONIC_ERR_INVALID, "bad verify test shape");
-    if (e->f32) return fail(e, SONIC_ERR_INVALID, "draft_verify: the fp32 kind has no verify kernels");
-    for (int b = 0; b < B; ++b) if (force_ids[b] < 0 || force_ids[b] >= V) return fail(e, SONIC_ERR_INVALID, "forced id %d out of vocabulary", force_ids[b]);
+    TRY(rows_check(e, "bad verify test shape", e->f32 ? "draft_verify: the fp32 kind has no verify kernels" : nullptr, ksplit, mpad, V, B, force_ids));
     if (gt.hist_ld < 0 || gt.hist_ld > (1 << 20) || (gt.hist_ld > 0 && !gt.hist) || !(gt.penalty > 0.f) || !std::isfinite(gt.penalty) || gt.ngram < 0 || gt.ngram > 64 ||
         gt.n_suppress < 0 || gt.n_suppress > 256 || (gt.n_suppress > 0 && !gt.suppress) || greedy_guard_lds(V) > 60000)
         return fail(e, SONIC_ERR_INVALID, "bad greedy guard test arguments");
     const int ld = std::max(gt.hist_ld, 1);
     std::vector<int> hh((size_t)B * ld, 0), plan((size_t)4 * B);
-    bool guard = gt.penalty != 1.0f || gt.ngram > 0 || gt.n_suppress > 0;
+    const bool guard = gt.penalty != 1.0f || gt.ngram > 0 || gt.n_suppress > 0;
     for (int b = 0; b < B; ++b) {
         if (gt.hist_len[b] < 0 || gt.hist_len[b] > gt.hist_ld) return fail(e, SONIC_ERR_INVALID, "history length %d outside 0 .. %d", gt.hist_len[b], gt.hist_ld);
         for (int j = 0; j < gt.hist_len[b]; ++j) {
@@ -579,28 +591,7 @@ static int test_verify(sonic_engine* e, const float* slabs, int ksplit, int mpad
         plan[b] = force_ids[b]; plan[B + b] = b; plan[2 * B + b] = b; plan[3 * B + b] = gt.hist_len[b];      // record b = sequence b, token 0 (out_ld = 1)
     }
     for (int i = 0; i < gt.n_suppress; ++i) if (gt.suppress[i] < 0 || gt.suppress[i] >= V) return fail(e, SONIC_ERR_INVALID, "suppressed id %d out of vocabulary", gt.suppress[i]);
-    const int K = lp_out ? e->opt_top_logprobs : 0, W = 1 + 2 * K;
-    TmpBuf tb(e->st);
-    float* dl = up_f32(e, tb, slabs, (size_t)ksplit * mpad * V);
-    unsigned char* rows = tb.get<unsigned char>((size_t)B * V * 2);
-    int* dplan = tb.get<int>(plan.size()); int* dh = tb.get<int>(hh.size()); int* gsup = tb.get<int>(256); int* vt = tb.get<int>(B);
-    float* lp = tb.get<float>((size_t)B * W); float* dump = logits_out ? tb.get<float>((size_t)B * V) : nullptr;
-    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
-    HIPC(e, h2d(e, dplan, plan.data(), plan.size() * 4));
-    HIPC(e, h2d(e, dh, hh.data(), hh.size() * 4));
-    if (gt.n_suppress > 0) HIPC(e, h2d(e, gsup, gt.suppress, (size_t)gt.n_suppress * 4));
-    launch_score_slab_rows(dl, ksplit, mpad, V, B, rows, e->dt, e->st);
-    VerifyArgs a{};
-    a.logits = rows; a.ld = V; a.V = V; a.n = B; a.dt = e->dt; a.target = dplan; a.rec = dplan + B; a.hrow = dplan + 2 * B; a.hlen = dplan + 3 * B;
-    if (guard) { a.hist = dh; a.hist_ld = ld; a.rep_penalty = gt.penalty; a.ngram = gt.ngram; a.suppress = gsup; a.n_suppress = gt.n_suppress; }
-    a.ver_tok = vt; a.ver_rec = lp; a.topk = K; a.dump = dump; a.out_ld = 1; a.R = B;
-    launch_verify_rows(a, e->st);
-    HIPC(e, stream_sync(e));
-    HIPC(e, hipGetLastError());
-    HIPC(e, d2h(e, tok_out, vt, (size_t)B * 4));
-    if (logits_out) HIPC(e, d2h(e, logits_out, dump, (size_t)B * V * 4));
-    if (lp_out) HIPC(e, d2h(e, lp_out, lp, (size_t)B * W * 4));
-    return SONIC_OK;
+    return rows_run(e, slabs, ksplit, mpad, V, B, e->dt, lp_out ? e->opt_top_logprobs : 0, plan, true, hh, guard ? &gt : nullptr, tok_out, logits_out, lp_out);
 }
 extern "C" int sonic_test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, int32_t* tok_out, float* logits_out) {
     if (!e || !slabs || !tok_out) return SONIC_ERR_INVALID;

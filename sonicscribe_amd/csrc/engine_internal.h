@@ -218,7 +218,7 @@ struct sonic_engine {
     // states in, the EOS ids, armed until the next hook launch that has histories and log-probabilities takes it; hook_state_out: that launch's states out (sonic_debug_read)
     std::vector<int> hook_gram; int hook_state_in[64]; std::vector<int> hook_eos; int hook_state_out[64]{};
     // the parallel forced run (options forced_parallel / forced_fanout / score_chunk_rows; run_forced_parallel, engine_score.cpp): with forced ids set,
-    // a run is ONE prefill of prompt || forced ids, the lm_head over every forced position as a GEMM per chunk of score rows, and score_rows_kernel per row.
+    // a run is ONE prefill of prompt || forced ids, the lm_head over every forced position as a GEMM per chunk of score rows, and rows_kernel (rows.hip) per row.
     // score_logits: the chunk's logits [score_rows_cap][vocab] in the activation type (fp32 kind: fp32); score_plan_d / score_plan_h: the score rows' plan (ScorePlan),
     // on the device and in pinned memory (one buffer: the run ends with a stream synchronise).  All three come with the first parallel run, are counted by
     // sonic_memory_info and go with the handle
@@ -236,9 +236,9 @@ struct sonic_engine {
     bool align_live = false, align_last = false;
     int align_S = 0, align_nseq = 0, align_Amax = 0, align_Lmax = 0, align_Htot = 0, align_last_heads = 0;      // of the run under way / the last one
     std::vector<std::vector<int>> align_layer_heads; std::vector<int> align_layer_off;                             // per decoder layer: its selected heads, and where they start in the plan
-    // draft-verified decoding (option draft_verify; sonic_load_tensor "request_draft"; verify.hip): a request of the next prefill may bring a draft of its
+    // draft-verified decoding (option draft_verify; sonic_load_tensor "request_draft"; rows.hip): a request of the next prefill may bring a draft of its
     // transcript - the prefill runs over prompt || draft, the lm_head over every draft position as a GEMM per chunk of rows into score_logits (the parallel forced
-    // run's chunk buffer), verify_rows_kernel per row, draft_accept_kernel per request, then the unchanged head.  draft_stage: the staged words [R | off[R + 1] | ids]
+    // run's chunk buffer), rows_kernel per row, draft_accept_kernel per request, then the unchanged head.  draft_stage: the staged words [R | off[R + 1] | ids]
     // (draft_pending = their R, -1: none; draft_take: the prefill under way consumes them).  The buffers come with the handle's first drafted prefill, are counted by
     // sonic_memory_info and go with the handle: draft_plan_d, the verify rows' plan (DraftPlan), with a pinned mirror beside each of the two plan staging buffers; ver_tok
     // [tok_cap], ver_rec [tok_cap][lp_width] (ver_rec_w: the width it was allocated at), draft_acc [64] = a_r of the last drafted prefill (draft_last_S: its verify rows; 0: none)
@@ -285,7 +285,7 @@ struct HostPlan {
 };
 
 // The three plans of the scoring passes, as the kernels read them: a view over a base pointer - the pinned host image and the device buffer alike - with one
-// member per array.  PLAN_REQ_WORDS: the stride of every per-request array in them; verify.hip, score.hip and align.hip index rq[64 + r], so it is 64
+// member per array.  PLAN_REQ_WORDS: the stride of every per-request array in them; rows.hip and align.hip index rq[64 + r], so it is 64
 #define PLAN_REQ_WORDS 64
 static_assert(PLAN_REQ_WORDS == 64, "the kernels read the plans' per-request words at a stride of 64");
 // draft plan (draft_plan_d / draft_plan_h, HostPlan::draft): per verify row its hidden row | draft id | record index | request | history length, S of each; then per

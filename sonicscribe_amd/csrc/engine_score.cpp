@@ -75,20 +75,20 @@ template <typename F> static void score_pass(sonic_engine* e, const int* row_map
 }
 
 // Draft-verified decoding (option draft_verify), behind the prefill's last layer: draft position n of request r is decided by the hidden row at
-// q_off[r] + P - 1 + n.  The S = sum D_r rows go through the score pass, reduced by verify_rows_kernel under the handle's processors; draft_accept_kernel then leaves
+// q_off[r] + P - 1 + n.  The S = sum D_r rows go through the score pass, reduced by rows_kernel<T, true, ...> (rows.hip) under the handle's processors; draft_accept_kernel then leaves
 // every drafted request where a prefill of prompt || draft[0 .. a) would have left it.  The head that follows is the one of every prefill
 void run_draft_verify(sonic_engine* e, int R, const HostPlan& hp) {
     const sonic_dims& d = e->d;
     const DraftPlan pd(e->draft_plan_d, hp.S);
-    VerifyArgs va{};
+    RowsArgs va{};
     va.logits = e->score_logits; va.ld = d.vocab; va.V = d.vocab; va.dt = e->dt;
     if (e->gen_on && e->hist) { va.hist = e->hist; va.hist_ld = e->max_ctx; va.rep_penalty = e->gen_penalty; va.ngram = e->gen_ngram; va.suppress = e->gen_suppress_d; va.n_suppress = (int)e->gen_suppress.size(); }
     va.topk = lp_on(e) ? e->opt_top_logprobs : 0;
-    va.dump = e->run_logits ? e->dump : nullptr; va.out_ld = e->out_cap; va.R = R;
+    va.dump = e->run_logits ? e->dump : nullptr; va.out_ld = e->out_cap; va.R = R; va.lp_by_row = true;
     score_pass(e, pd.hidden, hp.S, [&](int c0, int n) {
         va.n = n; va.target = pd.target + c0; va.rec = pd.rec + c0; va.hrow = pd.hrow + c0; va.hlen = pd.hlen + c0;
-        va.ver_tok = e->ver_tok + c0; va.ver_rec = e->ver_rec + (size_t)c0 * lp_width(e);
-        launch_verify_rows(va, e->st);
+        va.choice = e->ver_tok + c0; va.out_lp = e->ver_rec + (size_t)c0 * lp_width(e);
+        launch_rows(va, e->st);
     });
     DraftAcceptArgs da{};
     da.req = pd.req; da.draft = pd.target; da.ver_tok = e->ver_tok; da.ver_rec = e->ver_rec; da.lp_w = lp_width(e);
@@ -100,7 +100,7 @@ void run_draft_verify(sonic_engine* e, int R, const HostPlan& hp) {
 // The parallel forced run (option forced_parallel with forced ids set; include/sonic_hip.h beside sonic_set_forced_ids).  Under teacher forcing no
 // input depends on an output, so the run is ONE prefill: sequence r = prompt || forced[r][0 .. L_r - 1), L_r = 1 + the index of the first EOS id among its budget's
 // forced ids (HF's rule; the budget if there is none).  Token n of sequence r is scored by the hidden state at row q_off[r] + P - 1 + n: the S = sum L_r score rows are
-// the rows of the score pass, reduced by score_rows_kernel (score.hip), which also writes the forced ids to out_ids and, if asked, the rows to the step-logits dump.
+// the rows of the score pass, reduced by rows_kernel<T, false, ...> (rows.hip), which also writes the forced ids to out_ids and, if asked, the rows to the step-logits dump.
 // No logits processor is applied.  forced_fanout = N: the R sequences are R / N audio requests (windows, log-mel, encoder, projector once each) with N candidates
 // each; the prefill's outlier groups stay per sequence.  The handle is left holding a finished batch.
 int run_forced_parallel(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new, bool want_logits) {
@@ -222,13 +222,13 @@ int run_forced_parallel(sonic_engine* e, const int32_t* req_win, int R, const in
         launch_align_dtw(align_probs_args(e, e->dq, e->Kc, 128, e->max_ctx * 128L, (long)d.dec_kv_heads * e->max_ctx * 128, nullptr, 0, d.dec_heads, d.dec_kv_heads, pd.rec), e->st);
         e->align_live = false; e->align_last = true;
     }
-    ScoreArgs sa{};
+    RowsArgs sa{};
     sa.logits = e->score_logits; sa.ld = d.vocab; sa.V = d.vocab; sa.dt = e->f32 ? DT_F32 : e->dt;
     sa.out_ids = e->out_ids; sa.out_lp = lp_on(e) ? e->out_lp : nullptr; sa.topk = sa.out_lp ? e->opt_top_logprobs : 0;
     sa.dump = want_logits ? e->dump : nullptr; sa.out_ld = e->out_cap; sa.R = R;
     score_pass(e, pd.hidden, S, [&](int c0, int n) {
         sa.n = n; sa.target = pd.target + c0; sa.rec = pd.rec + c0;
-        launch_score_rows(sa, e->st);
+        launch_rows(sa, e->st);
     });
     // the rows' state as a finished batch: n_new = L, finished, tok_pos = kv_len - 1 (kv_len = prompt + L - 1 is what the plan uploaded), nothing running
     HIPC(e, hipMemcpyAsync(e->n_new, ph.n_new, PLAN_REQ_WORDS * 4, hipMemcpyHostToDevice, e->st));

@@ -6,9 +6,8 @@
 #include "common.h"
 #include "kernels.h"
 
-#include "guard.h"
 #include "int8_util.h"
-#include "topk.h"
+#include "rowlp.h"
 
 // ---------------------------------------------------------------- argmax + greedy controller (generation/utils.py:2894-2936)
 // LP (option token_logprobs): the block also returns log_softmax(l)[tok] of the token it emits.  Every thread keeps the sum lp_s of
@@ -56,8 +55,8 @@
 // scores.  Thread 0 looks the emitted id - argmax, sample or forced id - up among the node's edges by binary search: found, the state is that edge's `next`; not
 // found (a forced id outside the grammar, token 0 of a row whose allowed ids were all banned, any id at -2), it is -2.  A finished row changes nothing; no LDS is
 // added.  GRAMMAR = false is the kernel as it was.
-// tk_insert / tk_merge (the lists and their wave merge) and lp_exp live in topk.h: score.hip shares them; guard_score / guard_set (a score under the
-// history's maps, a bit into one) in guard.h: verify.hip shares them
+// The history's maps, the first-maximum butterfly, the sum's rescale, wave fold and block close, and the lists with their merges and record write live in
+// rowlp.h: rows.hip (rows_kernel) shares them
 extern __shared__ unsigned g_bits[];
 __device__ __forceinline__ float bias_of(const int* ids, const float* sums, int n, int id) {
     float b = 0.f;
@@ -98,10 +97,7 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
     __shared__ float s_tk_hand[TOPK ? 2 : 1];    // thread 0 -> wave 1: the block's maximum M and lp_sum, the values out_lp was formed from ...
     __shared__ int s_tk_col[1];                  // ... and the record's column n_new (-1: a finished row)
     [[maybe_unused]] float tv[8]; [[maybe_unused]] int ti[8]; [[maybe_unused]] float mv = -INFINITY; [[maybe_unused]] int mi = TK_NONE;
-    if constexpr (TOPK) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { tv[k] = -INFINITY; ti[k] = TK_NONE; }
-    }
+    if constexpr (TOPK) tk_init(tv, ti);
     float lp_m = -INFINITY, lp_s = 0.f;      // LP: the thread's sum is lp_s * exp(lp_m); a thread that saw nothing holds (-inf, 0)
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const float* lg = a.logits + (long)b * a.V;
@@ -143,7 +139,7 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
             }
         }
         const int* h = a.hist + (long)b * a.hist_ld;
-        const int len = min(max(a.kv_len[b], 0), a.hist_ld), n = a.ngram;
+        const int len = min(max(a.kv_len[b], 0), a.hist_ld);
         if constexpr (BIAS) {
             // dynamic LDS behind the three maps: the group sums' ids [256], the sums [256], the entries' flags [256] (greedy_guard_lds)
             g_bia = g_bits + 2 * nw; q_id = (int*)(g_bits + 3 * nw); q_sum = (float*)(q_id + BIAS_MAX_ENTRIES);
@@ -168,16 +164,7 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
                 if (any) { q_id[tid] = last; q_sum[tid] = acc; guard_set(g_bia, last, a.V); }
             }
         }
-        for (int j = tid; j < len; j += 1024) guard_set(g_seen, h[j], a.V);
-        if (n > 0) {                              // every n-gram h[j .. j + n) of the history whose first n - 1 ids are the history's last n - 1 bans its last id
-            const int* last = h + len - (n - 1);  // (read only when an n-gram exists: j + n <= len)
-            for (int j = tid; j + n <= len; j += 1024) {
-                bool m = true;
-                for (int k = 0; k < n - 1; ++k) m = m && h[j + k] == last[k];
-                if (m) guard_set(g_ban, h[j + n - 1], a.V);
-            }
-        }
-        for (int j = tid; j < a.n_suppress; j += 1024) guard_set(g_ban, a.suppress[j], a.V);
+        hist_maps(g_seen, g_ban, h, len, a.ngram, a.suppress, a.n_suppress, a.V, tid);
         __syncthreads();
     }
     // four strides per trip with all their slab loads issued first (the rolled form paid one L2 round trip per stride)
@@ -229,7 +216,7 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
             // the trip's values against the maximum so far (`best` covers them): the old sum is rescaled once (exp2(0) = 1 and s * 1 are exact when
             // the maximum did not move), then the terms are added in visiting order.  While nothing finite has been seen (the first trip, or trips
             // of -inf logits only) the sum stays 0: -inf - -inf is not formed, here or in the terms (exp(-inf - finite) = 0 is fine)
-            lp_s = lp_m > -INFINITY ? lp_s * lp_exp(lp_m - LPB) : 0.f; lp_m = LPB;
+            lp_s = lp_rescale(lp_s, lp_m, LPB); lp_m = LPB;
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if (i0 + u * 4096 >= a.V) break;
@@ -238,50 +225,27 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
             }
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
-        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
+    FIRST_MAX_WAVE(best, bi)
     if constexpr (SAMPLE) {
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) rmax = fmaxf(rmax, __shfl_xor(rmax, o, 64));
         if (lane == 0) ss_m[wid] = rmax;
     }
     if constexpr (LP) {
-        // every lane now holds the wave's maximum: bring the lane's sum to it (an empty lane is the identity: 0, not 0 * exp(-inf + inf)) and add
-        // across the wave; the butterfly gives every lane the same tree, and a + b = b + a bit for bit
-        lp_s = lp_m > -INFINITY ? lp_s * lp_exp(lp_m - LPB) : 0.f;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) lp_s += __shfl_xor(lp_s, o, 64);
+        lp_s = lp_wave_fold(lp_s, lp_m, LPB);      // every lane now holds the wave's maximum
         if (lane == 0) ss_lp[wid] = lp_s;
     }
-    if constexpr (TOPK) {
-        tk_merge(tv, ti, a.topk, lane, mv, mi);
-        if (lane < 8) { s_tkv[lane * 16 + wid] = mv; s_tki[lane * 16 + wid] = mi; }
-    }
+    if constexpr (TOPK) tk_stage(tv, ti, a.topk, lane, wid, s_tkv, s_tki, mv, mi);
     if (lane == 0) { sv[wid] = best; si[wid] = bi; }
     __syncthreads();
-    if constexpr (TOPK) if (wid == 1) {              // lane w < 16 takes wave w's list; the merge runs beside thread 0's bookkeeping
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { tv[k] = lane < 16 ? s_tkv[k * 16 + lane] : -INFINITY; ti[k] = lane < 16 ? s_tki[k * 16 + lane] : TK_NONE; }
-        tk_merge(tv, ti, a.topk, lane, mv, mi);
-    }
+    if constexpr (TOPK) if (wid == 1) tk_merge_waves(tv, ti, a.topk, lane, s_tkv, s_tki, mv, mi);      // beside thread 0's bookkeeping
     [[maybe_unused]] int tk_col = -1; [[maybe_unused]] float tk_m = 0.f, tk_sum = 0.f;
     if (tid == 0) {
         for (int w = 1; w < 16; ++w) if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
         float lp_sum = 0.f;
         if constexpr (LP) {
-            float q[16];                          // the 16 waves at the block's maximum (an empty wave: 0), added as a fixed binary tree
-            const float* wm = SAMPLE ? ss_m : sv; // the waves' maxima of the scores the sum ran over
             if constexpr (SAMPLE) for (int w = 1; w < 16; ++w) rmax = fmaxf(rmax, ss_m[w]);
-#pragma unroll
-            for (int w = 0; w < 16; ++w) q[w] = wm[w] > -INFINITY ? ss_lp[w] * lp_exp(wm[w] - LPB) : 0.f;
-#pragma unroll
-            for (int h = 8; h > 0; h >>= 1)
-#pragma unroll
-                for (int w = 0; w < h; ++w) q[w] = q[2 * w] + q[2 * w + 1];
-            lp_sum = q[0];
+            lp_sum = lp_block_close(SAMPLE ? ss_m : sv, ss_lp, LPB);      // the waves' maxima of the scores the sum ran over
         }
         if constexpr (GUARD || SAMPLE) if (bi == 0x7fffffff) bi = 0;      // every score -inf: the first of equal values
         int tok = bi;
@@ -336,13 +300,8 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
         if (tid == 0) { s_tk_hand[0] = tk_m; s_tk_hand[1] = tk_sum; s_tk_col[0] = tk_col; }
     }
     __syncthreads();
-    if constexpr (TOPK) if (wid == 1 && lane < a.topk && s_tk_col[0] >= 0) {
-        const int K = a.topk;
-        float* rec = a.out_lp + ((long)b * a.out_ld + s_tk_col[0]) * (1 + 2 * K);
-        const bool any = mi != TK_NONE;
-        rec[1 + lane] = any ? (float)(((double)mv - (double)s_tk_hand[0]) - log((double)s_tk_hand[1])) : -INFINITY;
-        rec[1 + K + lane] = any ? (float)mi : -1.f;      // (ids stay below 2^24: exact)
-    }
+    if constexpr (TOPK) if (wid == 1 && lane < a.topk && s_tk_col[0] >= 0)
+        tk_record(a.out_lp + ((long)b * a.out_ld + s_tk_col[0]) * (1 + 2 * a.topk), a.topk, lane, mv, mi, s_tk_hand[0], s_tk_hand[1]);
     const T* row = (const T*)a.table + (long)s_tok * a.d;
     T* xo = (T*)a.x;
     if (!a.y || (a.d >> 3) > 1024) {

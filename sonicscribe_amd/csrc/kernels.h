@@ -149,37 +149,28 @@ void launch_greedy(const GreedyArgs& a, hipStream_t s);
 size_t greedy_guard_lds(int V, bool bias = false);     // dynamic LDS of the GUARD instantiations: two bitmaps over the vocabulary; with the request bias a third one and the matched list
 void launch_hist_prompt(const int* src, const int* tok_seq, const int* tok_pos, int n_tok, int audio_id, int* hist, int hist_ld, hipStream_t s);
 
-// The parallel forced run's row kernel (score.hip: score_rows_kernel<T, TOPK>, option forced_parallel): block i takes row i of `logits` - the lm_head's
-// output for one score row, in the activation type - and writes the record of the forced token target[i]: log_softmax(row)[target] and, with topk = K in 1 .. 8,
-// the K best ids of the row by (value descending, id ascending) with their log-probabilities, in the layout GreedyArgs.out_lp has.  rec[i] = r * out_ld + n names
-// the record (sequence r, token n): out_ids[rec] = target, out_lp[rec * (1 + 2K) ..], dump[(n * R + r) * V ..] = the row as fp32 (each optional).  No processor
-// is applied: the row is the raw model distribution at temperature 1
-struct ScoreArgs {
+// The row kernel of the parallel forced run and of draft-verified decoding (rows.hip: rows_kernel<T, CHOOSE, GUARD, TOPK>; options forced_parallel / draft_verify;
+// DESIGN.md 6.8, 6.11): block i takes row i of `logits` - the lm_head's output for one hidden row, in the activation type - and writes the record of the given token
+// target[i]: log_softmax(s)[target] and, with topk = K in 1 .. 8, the K best ids of s by (value descending, id ascending) with their log-probabilities, in the layout
+// GreedyArgs.out_lp has.  rec[i] = r * out_ld + n names sequence r, token n: dump[(n * R + r) * V ..] = the raw row as fp32 and out_ids[rec] = target (each
+// optional); the record goes to out_lp[rec * (1 + 2K) ..], or with lp_by_row to out_lp[i * (1 + 2K) ..] (a staging array: draft_accept_kernel reads it).
+// choice == NULL (the forced run; bf16 / fp16 / fp32): s = the row, the raw model distribution at temperature 1 - no processor is applied.
+// choice != NULL (draft verify; bf16 / fp16): choice[i] = the first maximum of s (the lower id among equal values; 0 when all are -inf); and with hist != NULL
+// (GUARD) s = guard_score of the logits under the maps of hist[hrow[i] * hist_ld .. + hlen[i]) - the request's prompt and the draft ids in front of the position
+struct RowsArgs {
     const void* logits; long ld;     // [n][ld] elements of the type `dt` names
     int V, n, dt;                    // DT_BF16 / DT_F16 / DT_F32
-    const int* target; const int* rec;
-    int* out_ids; float* out_lp; int topk;
+    const int *target, *rec;
+    int* out_ids; float* out_lp; bool lp_by_row; int topk;
     float* dump; int out_ld, R;
+    int* choice;
+    const int *hrow, *hlen, *hist; int hist_ld;      // the guard fields: they count only together with choice
+    float rep_penalty; int ngram; const int* suppress; int n_suppress;
 };
-void launch_score_rows(const ScoreArgs& a, hipStream_t s);
+void launch_rows(const RowsArgs& a, hipStream_t s);
 // test hook route: the lm_head's fp32 slabs [ksplit][mpad][V] summed in greedy_kernel's order (v + w, then ks = 2 ...) and rounded to the element type: out [B][V]
 void launch_score_slab_rows(const float* slabs, int ksplit, int mpad, int V, int B, void* out, int dt, hipStream_t s);
 
-// Draft-verified decoding (verify.hip; option draft_verify).  verify_rows_kernel<T, GUARD, TOPK>: block i takes row i of `logits` - the lm_head's
-// output for the hidden row that decides one draft position, in the activation type (bf16 / fp16) - and writes ver_tok[i], the first maximum of the row's processed
-// scores (the lower id among equal values; 0 when all are -inf), and ver_rec[i * (1 + 2K) ..], the record of the draft id target[i] in GreedyArgs.out_lp's layout.
-// hist != NULL (GUARD): the scores are guard_score of the logits under the maps of hist[hrow[i] * hist_ld .. + hlen[i]) - the request's prompt and the draft ids in
-// front of the position.  rec[i] = r * out_ld + n names request and position for the dump alone: dump[(n * R + r) * V ..] = the raw row as fp32 (optional)
-struct VerifyArgs {
-    const void* logits; long ld;     // [n][ld] elements of the type `dt` names
-    int V, n, dt;                    // DT_BF16 / DT_F16
-    const int *target, *rec, *hrow, *hlen;
-    const int* hist; int hist_ld;
-    float rep_penalty; int ngram; const int* suppress; int n_suppress;
-    int* ver_tok; float* ver_rec; int topk;
-    float* dump; int out_ld, R;
-};
-void launch_verify_rows(const VerifyArgs& a, hipStream_t s);
 // draft_accept_kernel: block r takes request r = req[r] (draft length D; 0: the block changes nothing but accepted[r] = 0), req[64 + r] (its first verify row),
 // req[128 + r] (prompt length P), req[192 + r] (first packed token).  a = the least n with ver_tok[row0 + n] != draft[row0 + n], else D; out_ids[r][0 .. a) and the
 // records (lp_w floats each; out_lp may be NULL) are copied, n_new = step_counter = a, kv_len = P + a, last_row = first token + P - 1 + a, accepted[r] = a

@@ -1,5 +1,5 @@
-"""Draft-verified decoding on the GPU (option draft_verify, sonic_load_tensor "request_draft"; csrc/verify.hip): a request brings a draft of its
-transcript, the prefill runs over prompt || draft, every draft position is decided from the lm_head GEMM's row by verify_rows_kernel under the handle's processors,
+"""Draft-verified decoding on the GPU (option draft_verify, sonic_load_tensor "request_draft"; csrc/rows.hip): a request brings a draft of its
+transcript, the prefill runs over prompt || draft, every draft position is decided from the lm_head GEMM's row by rows_kernel under the handle's processors,
 the longest agreeing prefix is accepted and the unchanged head and greedy loop carry on from the first disagreement.
 
 Fixture margins (tests/golden/tiny_bf16.npz, checked in test_fixture_margins on the host side of this file): s1's greedy margins are 0.172 at step 0 and >= 0.859

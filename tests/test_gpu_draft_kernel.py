@@ -1,10 +1,10 @@
-"""verify_rows_kernel (csrc/verify.hip) through the greedy guard hook on a handle with option draft_verify on: with forced ids the hook sums the
+"""rows_kernel<T, true, GUARD, TOPK> (csrc/rows.hip) through the greedy guard hook on a handle with option draft_verify on: with forced ids the hook sums the
 slabs in the greedy kernel's order, rounds them to the handle's element type - those values are the logits row the kernel reads, and `logits_out` returns them -
 and launches one block per row.  Row b is one draft position: its history is hist[b][:hist_len[b]], its draft id force_ids[b].  The kernel returns the first maximum
 of the processed scores and the record of the draft id: log_softmax(processed)[draft id] and, with option top_logprobs = K, the K best ids with their values.
 
 The choice is exact: np.argmax(GenerationGuards.apply(row, history)), and the token greedy_kernel<T, ., true> picks for the same row on an ordinary handle.
-The record is held to score_rows_kernel's derived bound (tests/test_gpu_score_kernel.py), evaluated over the processed scores: the guards add no
+The record is held to the row kernel's derived bound (tests/test_gpu_score_kernel.py), evaluated over the processed scores: the guards add no
 term, since s * p, s / p (correctly rounded fp32) and -inf are the very values the float64 reference starts from."""
 import math
 

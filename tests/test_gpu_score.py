@@ -1,5 +1,5 @@
 """Transcript scoring in one prefill pass (option forced_parallel, Engine.score_batch, ASRModel.score).  With forced ids set and the option on, a run
-is ONE prefill of prompt || forced ids, the tied lm_head over every forced position as a GEMM per chunk of score rows, and score_rows_kernel (csrc/score.hip) per row.
+is ONE prefill of prompt || forced ids, the tied lm_head over every forced position as a GEMM per chunk of score rows, and rows_kernel (csrc/rows.hip) per row.
 
 References and tolerances:
   * tests/golden/tiny_forced_{bf16,fp32}.npz: two segments (5 s, 20 s), 24 forced ids each, HF's per-step logits under teacher forcing.  bf16: the project's logit

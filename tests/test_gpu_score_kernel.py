@@ -1,4 +1,4 @@
-"""score_rows_kernel (csrc/score.hip) through the greedy log-probability hook on a handle with option forced_parallel on: the hook sums the slabs in
+"""rows_kernel<T, false, false, TOPK> (csrc/rows.hip) through the greedy log-probability hook on a handle with option forced_parallel on: the hook sums the slabs in
 the greedy kernel's order, rounds them to the handle's element type - those values are the logits row the kernel reads, and `logits_out` returns them - and launches
 one block per row.  The kernel returns log_softmax(row)[forced id] and, with option top_logprobs = K, the K best ids of the row with their log-probabilities.
 

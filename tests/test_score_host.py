@@ -103,4 +103,4 @@ def test_contract_is_documented_without_new_entry_points():
     for key in ("forced_parallel", "forced_fanout", "score_chunk_rows"):
         assert key in header, key
         assert len(re.findall(r'\{"%s",' % key, table)) == 1, key
-    assert "score.hip" in open(os.path.join(root, "sonicscribe_amd", "csrc", "Makefile")).read()
+    assert "rows.hip" in open(os.path.join(root, "sonicscribe_amd", "csrc", "Makefile")).read()
