@@ -631,7 +631,7 @@ SONIC_API int sonic_test_decode_attention(sonic_engine* e, const float* q, const
  * per-row kv_len[B] in 1..ctx_max (new token included).  Fused mode (slabs != NULL, q == NULL): q|k|v partial slabs [ksplit][mpad][(Hq + 2 Hkv) * 128] fp32
  * (ksplit 1..8, mpad >= B) and the RoPE table rope_cs [ctx_max][128] fp32 (cos | sin); the kernel sums the slabs, applies RoPE at kv_len - 1 and appends the
  * K / V row.  Given-q mode (q != NULL, slabs == NULL): q [B][Hq * 128], nothing appended.  out [B][Hq * 128]; kcache_out / vcache_out (optional) receive the
- * caches as the launch left them.  Hq / Hkv <= 4.  The int8 dequantising prologue is not reachable from here. */
+ * caches as the launch left them.  Hq / Hkv <= 4.  The int8 dequantising prologue is reached through sonic_test_decode_i8_attn. */
 SONIC_API int sonic_test_decode_attention_cache(sonic_engine* e, const float* q, const float* slabs, int ksplit, int mpad, const float* rope_cs,
                                       const float* kcache, const float* vcache, const int32_t* kv_len, float* out, float* kcache_out, float* vcache_out,
                                       int B, int Hq, int Hkv, int ctx_max);
@@ -659,6 +659,23 @@ SONIC_API int sonic_test_decode_o_gu(sonic_engine* e, const float* att, const fl
 SONIC_API int sonic_test_rope_append(sonic_engine* e, const float* qkv, const float* cs, const int32_t* tok_seq, const int32_t* tok_pos, const int32_t* q_off, const int32_t* q_len,
                                      int n_tok, int B, int Hq, int Hkv, int ctx_max, int vt_ld, int tiled, float* q_out, float* Kc, float* Vc, float* Vt);
 SONIC_API int sonic_test_rope_enc(sonic_engine* e, float* qk, int M, int ld, int T, int heads2, int hd, int rd, const float* cs);
+/* the int8 token step's dequantising consumers, each behind one decode-flavour Linear8bitLt run as the step runs it (int8 engines only; X [M][K] and W [N][K] are fp32
+ * holding fp16 values, 1 <= M <= 64; W is quantised, tiled and - layout 1 - also transposed into the k-major copy on the device; N, K as the int8 skinny GEMM takes them).
+ * info_out (optional) [2] = ksplit as launched, the GEMM's tiling 0 .. 4; slab_sum_out (optional) int32 [M][N] = the int32 slabs summed.  csrc/engine_hooks.cpp has the layouts.
+ *   sonic_test_decode_i8_norm    o_proj / down_proj + add_rmsnorm with a DeqInfo and a QuantOut: x, y [rows_alloc][N] in-out, N <= 2048; form 0 quantises the rows first and
+ *                                lists their outliers, form 1 (the step's default) hands the GEMM the rows' absmax partials amax [M][4] and the consumer those and the counts
+ *                                big [M][4] of their elements >= 6.0 (K <= 32 x the consumer's block size); the five quantiser outputs of y as sonic_test_add_rmsnorm's
+ *   sonic_test_decode_i8_swiglu  gate/up (W [2 ff][K], rows interleaved in groups of 16) + swiglu_quant: act [rows_alloc][ff] in-out, ff <= 8192, and its five quantiser outputs
+ *   sonic_test_decode_i8_attn    q|k|v (X [B][D]) + the fused decode attention with the DeqInfo; caches, rope_cs, kv_len as sonic_test_decode_attention_cache; Hkv <= 4;
+ *                                amax / big [B][4] in-out: the per-kv-head partials of the output rows' absmax without the elements >= 6.0, and their counts */
+SONIC_API int sonic_test_decode_i8_norm(sonic_engine* e, const float* X, const float* W, float* x, const float* norm_w, float eps, float* y, const float* amax, const int32_t* big,
+                                        int M, int N, int K, int rows_alloc, int form, int layout,
+                                        int8_t* q_out, float* sca_out, int32_t* oc_cnt_out, int32_t* oc_list_out, float* oc_val_out, int32_t* info_out, int32_t* slab_sum_out);
+SONIC_API int sonic_test_decode_i8_swiglu(sonic_engine* e, const float* X, const float* W, float* act, int M, int ff, int K, int rows_alloc, int layout,
+                                          int8_t* q_out, float* sca_out, int32_t* oc_cnt_out, int32_t* oc_list_out, float* oc_val_out, int32_t* info_out, int32_t* slab_sum_out);
+SONIC_API int sonic_test_decode_i8_attn(sonic_engine* e, const float* X, const float* Wqkv, const float* rope_cs, const float* kcache, const float* vcache, const int32_t* kv_len,
+                                        float* amax, int32_t* big, float* out, float* kcache_out, float* vcache_out, int B, int D, int Hq, int Hkv, int ctx_max, int layout,
+                                        int32_t* info_out, int32_t* slab_sum_out);
 SONIC_API int sonic_test_layernorm(sonic_engine* e, const float* x, const float* w, const float* b, float* y, int rows, int d, float eps, int rms);
 /* times `iters` launches of the encoder's dominant GEMM shape on the engine stream with HIP events */
 SONIC_API int sonic_bench_gemm(sonic_engine* e, int M, int N, int K, int epi, int iters, float* ms_per_launch);

@@ -266,6 +266,7 @@ void launch_skinny(const SkinnyArgs& a, hipStream_t s);
 int skinny_pick_ksplit(int N, int K);
 bool skinny_pre_eligible(int M, int N, int K);
 int skinny_pick_ksplit_i8(int N, int K);
+int skinny_i8_cfg(int N, int K);     // the int8 skinny GEMM's tiling for a shape (0 .. 4, the table in skinny.hip), -1: not handled
 bool skinny_gu_eligible(int M, int N, int K);
 void launch_skinny_gu(const SkinnyArgs& a, bf16_t* act, hipStream_t s);
 void launch_skinny_gu_norm(const SkinnyArgs& a, bf16_t* act, const float* SS, int nblk, const float* w, float eps, hipStream_t s);

@@ -25,10 +25,17 @@ void skinny(sonic_engine* e, const bf16_t* X, long ldx, const bf16_t* W, float* 
 }
 // int8 decode step: rows X [M][K] x fragment-tiled int8 weights -> int32 slabs (dequantised by the consumer).  amax == null: X holds the quantised rows; else the
 // UNQUANTISED fp16 rows with their gathered absmax partials, and the kernel quantises its X slice while staging it.  (The int8 kernels do not read dt.)
-static int skinny_i8(sonic_engine* e, const void* X, const float* amax, const int8_t* Wt, float* P, int M, int N, int K) {
+int skinny_i8(sonic_engine* e, const void* X, const float* amax, const int8_t* Wt, float* P, int M, int N, int K) {
     SkinnyArgs a = skinny_args((const bf16_t*)X, K, (const bf16_t*)Wt, P, M, N, K, skinny_pick_ksplit_i8(N, K), DT_BF16); a.i8 = 1; a.x_amax = amax;
     launch_skinny(a, e->st);
     return a.ksplit;
+}
+// ... and how its consumer dequantises the slabs: the rows' statistics and outlier lists as their producer left them (q), the projection's weights in every copy it
+// keeps (w), the unquantised rows x16 [.][K].  One row = one reference call = one group.  The step's on-the-fly form sets sca / scan / scan_cnt on the result
+DeqInfo deq_info(const sonic_engine* e, const QuantOut& q, const QW& w, int K, const bf16_t* x16, int N) {
+    DeqInfo dq{}; dq.sca = q.sca; dq.scb = w.scb; dq.cb = w.cb; dq.cbt = w.cbt; dq.cbk = w.cbk; dq.N = N; dq.K = K; dq.x16 = x16; dq.ldx16 = K; dq.oc_cnt = q.oc_cnt; dq.oc_list = q.oc_list; dq.oc_ld = q.oc_ld;
+    dq.row_group = nullptr; dq.group_div = 1; dq.oc_val = q.oc_val; dq.dbg = e->opt_i8_dbg;
+    return dq;
 }
 // a token step's attention for layer l: the q|k|v slabs -> satt, RoPE + KV append fused into the kernel
 static DecodeAttnArgs step_attn_args(sonic_engine* e, int l, int ks, int mpad, int dt) {
@@ -149,11 +156,7 @@ static void decode_step_i8(sonic_engine* e, int R, bool dump) {
     const QuantOut q_hn{e->hn_q, D, e->sca_hn, e->oc_hn, e->ol_hn, D, e->ov_hn};
     const QuantOut q_att{e->att_q, e->QD, e->sca_att, e->oc_att, e->ol_att, e->QD, e->ov_att};
     const QuantOut q_act{e->act_q, FF, e->sca_act, e->oc_act, e->ol_act, FF, e->ov_act};
-    auto deq = [&](const QuantOut& q, const QW& w, int K, const bf16_t* x16, int N) {
-        DeqInfo dq{}; dq.sca = q.sca; dq.scb = w.scb; dq.cb = w.cb; dq.cbt = w.cbt; dq.cbk = w.cbk; dq.N = N; dq.K = K; dq.x16 = x16; dq.ldx16 = K; dq.oc_cnt = q.oc_cnt; dq.oc_list = q.oc_list; dq.oc_ld = q.oc_ld;
-        dq.row_group = nullptr; dq.group_div = 1; dq.oc_val = q.oc_val; dq.dbg = e->opt_i8_dbg;
-        return dq;
-    };
+    auto deq = [&](const QuantOut& q, const QW& w, int K, const bf16_t* x16, int N) { return deq_info(e, q, w, K, x16, N); };
     for (int l = 0; l < d.dec_layers; ++l) {
         const DecLayerW& L = e->dec[l];
         int ks = skinny_i8(e, e->hn_q, nullptr, L.qqkv.cbt, e->slab, R, e->qkvN, D);

@@ -822,3 +822,142 @@ extern "C" int sonic_test_rope_enc(sonic_engine* e, float* qk, int M, int ld, in
     launch_rope_enc(dqk, ld, M, T, heads2, hd, rd, dcs, e->st, e->dt);
     return down_bf16(e, tb, dqk, qk, (size_t)M * ld);
 }
+
+// ------------------------------------------------------------------------------------------ int8 decode step: one decode-flavour Linear8bitLt plus its consumer
+// (tests/test_gpu_int8_decode_glue.py).  X [M][K] and W [N][K] are fp32 holding fp16 values, 1 <= M <= 64.  W is quantised on the device (launch_quant_weights), tiled
+// (launch_tile_weights_i8) and, with layout = 1, also transposed into the k-major copy (launch_transpose_i8); the row-major matrix is not handed on, as in the step.  The
+// Linear runs as decode_step_i8 runs it - skinny_i8 into int32 slabs, the consumer's DeqInfo from deq_info - and the consumer is launched through its own launcher.
+// info_out (optional) [2]: ksplit as launched, the tiling skinny_i8_cfg chose.  slab_sum_out (optional) int32 [M][N]: the slabs summed over ksplit (rows behind M, which
+// the GEMM fills with copies of its last row, are not returned).  Every shape and index is checked before the first launch.
+struct I8Lin { bf16_t* X = nullptr; QW w; QuantOut qx{}; float* P = nullptr; int ks = 0, mpad = 0, cfg = 0; };
+static int i8lin_check(sonic_engine* e, const char* who, int M, int N, int K, int layout) {
+    if (!e->i8) return fail(e, SONIC_ERR_INVALID, "%s needs an engine created with mode int8", who);
+    if (M < 1 || M > 64 || N < 32 || N > (1 << 16) || K < 256 || K > 8192 || (layout != 0 && layout != 1))
+        return fail(e, SONIC_ERR_INVALID, "%s: 1 <= M <= 64, 32 <= N <= 65536, 256 <= K <= 8192, layout 0 (tiled) or 1 (tiled + k-major)", who);
+    if (skinny_i8_cfg(N, K) < 0 || skinny_pick_ksplit_i8(N, K) < 1) return fail(e, SONIC_ERR_INVALID, "%s: N = %d, K = %d is not a shape of the int8 skinny GEMM (N %% 32 == 0, K %% 256 == 0)", who, N, K);
+    return SONIC_OK;
+}
+// uploads, allocations and the weight preparation; qx: the five arrays of the rows' quantised form (form 0: written by launch_quant_rows; scan form: the spill space)
+static int i8lin_prepare(sonic_engine* e, TmpBuf& tb, const float* X, const float* W, int M, int N, int K, int layout, I8Lin* L) {
+    L->cfg = skinny_i8_cfg(N, K); L->ks = skinny_pick_ksplit_i8(N, K); L->mpad = ((M + 15) / 16) * 16;
+    L->X = up_bf16(e, tb, X, (size_t)M * K); bf16_t* dW = up_bf16(e, tb, W, (size_t)N * K);
+    int8_t* cb = tb.get<int8_t>((size_t)N * K); L->w.scb = tb.get<float>(N); L->w.cbt = tb.get<int8_t>((size_t)N * K);
+    if (layout == 1) L->w.cbk = tb.get<int8_t>((size_t)N * K);
+    L->P = tb.get<float>((size_t)L->ks * L->mpad * N);
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    TRY(quant_alloc(e, tb, M, K, &L->qx));
+    launch_quant_weights(dW, cb, L->w.scb, N, K, e->st);
+    launch_tile_weights_i8(cb, L->w.cbt, N, K, e->st);
+    if (layout == 1) launch_transpose_i8(cb, L->w.cbk, N, K, e->st);
+    L->w.cb = nullptr; L->w.cb_rowmajor_kept = false;
+    return SONIC_OK;
+}
+// form 0: launch_quant_rows + skinny_i8 on the codes; amax != null: skinny_i8 quantises the fp16 rows itself
+static void i8lin_run(sonic_engine* e, I8Lin* L, const float* amax, int M, int N, int K) {
+    if (!amax) launch_quant_rows(L->X, K, M, K, L->qx, e->st);
+    L->ks = skinny_i8(e, amax ? (const void*)L->X : (const void*)L->qx.q, amax, L->w.cbt, L->P, M, N, K);
+}
+static int i8lin_report(sonic_engine* e, const I8Lin& L, int M, int N, int32_t* info_out, int32_t* slab_sum_out) {
+    if (info_out) { info_out[0] = L.ks; info_out[1] = L.cfg; }
+    if (!slab_sum_out) return SONIC_OK;
+    HIPC(e, stream_sync(e));
+    HIPC(e, hipGetLastError());
+    std::vector<int32_t> h((size_t)L.ks * L.mpad * N);
+    HIPC(e, d2h(e, h.data(), L.P, h.size() * 4));
+    for (int m = 0; m < M; ++m)
+        for (int n = 0; n < N; ++n) {
+            int64_t s = 0;
+            for (int k = 0; k < L.ks; ++k) s += h[((size_t)k * L.mpad + m) * N + n];
+            slab_sum_out[(size_t)m * N + n] = (int32_t)s;
+        }
+    return SONIC_OK;
+}
+
+// o_proj / down_proj of the int8 step, then launch_add_rmsnorm with the DeqInfo and a QuantOut: x [rows_alloc][N] (in place) and y [rows_alloc][N] go up with the caller's
+// contents; norm_w [N].  form 0: launch_quant_rows -> skinny_i8 -> the listed DeqInfo.  form 1 (the step's default): amax [M][4] = the rows' absmax partials without the
+// elements >= 6.0, big [M][4] = the counts of those elements; skinny_i8 gets the partials, the DeqInfo sca = amax, scan = 1, scan_cnt = big.  The five outputs are the
+// QuantOut of y as sonic_test_add_rmsnorm returns them: q [M][N], sca / oc_cnt [M], oc_list / oc_val [M][N].
+extern "C" int sonic_test_decode_i8_norm(sonic_engine* e, const float* X, const float* W, float* x, const float* norm_w, float eps, float* y, const float* amax, const int32_t* big,
+                                         int M, int N, int K, int rows_alloc, int form, int layout,
+                                         int8_t* q_out, float* sca_out, int32_t* oc_cnt_out, int32_t* oc_list_out, float* oc_val_out, int32_t* info_out, int32_t* slab_sum_out) {
+    if (!e || !X || !W || !x || !norm_w || !y || !q_out || !sca_out || !oc_cnt_out || !oc_list_out || !oc_val_out) return SONIC_ERR_INVALID;
+    ENTER(e);
+    TRY(i8lin_check(e, "sonic_test_decode_i8_norm", M, N, K, layout));
+    const int threads = ((N >> 3) + 63) / 64 * 64;
+    if (N % 8 || N > 2048 || rows_alloc < M || rows_alloc > 4096 || (form != 0 && form != 1))
+        return fail(e, SONIC_ERR_INVALID, "decode_i8_norm: N %% 8 == 0, N <= 2048, rows_alloc >= M, form 0 or 1");
+    if (form == 1 && (!amax || !big || K > 32 * threads)) return fail(e, SONIC_ERR_INVALID, "decode_i8_norm: form 1 needs the partials, the counts and K <= 32 x the block size (%d)", 32 * threads);
+    TmpBuf tb(e->st);
+    I8Lin L;
+    const size_t n = (size_t)rows_alloc * N;
+    bf16_t* dx = up_bf16(e, tb, x, n); bf16_t* dy = up_bf16(e, tb, y, n); float* dw = up_f32(e, tb, norm_w, N);
+    float* damax = form == 1 ? up_f32(e, tb, amax, (size_t)M * 4) : nullptr; int* dbig = form == 1 ? tb.get<int>((size_t)M * 4) : nullptr;
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    if (form == 1) HIPC(e, h2d(e, dbig, big, (size_t)M * 16));
+    TRY(i8lin_prepare(e, tb, X, W, M, N, K, layout, &L));
+    QuantOut qo{};
+    TRY(quant_alloc(e, tb, M, N, &qo));
+    i8lin_run(e, &L, damax, M, N, K);
+    DeqInfo dq = deq_info(e, L.qx, L.w, K, L.X, N);
+    if (form == 1) { dq.sca = damax; dq.scan = 1; dq.scan_cnt = dbig; }
+    launch_add_rmsnorm(dx, L.P, L.ks, L.mpad, dw, dy, M, N, eps, e->st, DT_F16, &dq, &qo);
+    TRY(down_bf16(e, tb, dx, x, n));
+    TRY(down_bf16(e, tb, dy, y, n));
+    TRY(quant_fetch(e, qo, M, N, QuantHost{q_out, sca_out, oc_cnt_out, oc_list_out, oc_val_out}));
+    return i8lin_report(e, L, M, N, info_out, slab_sum_out);
+}
+
+// gate/up of the int8 step (W [2 ff][K], gate / up rows interleaved in groups of 16), then launch_swiglu_quant: act [rows_alloc][ff] goes up with the caller's contents;
+// the five outputs are the QuantOut of act, [M][ff]
+extern "C" int sonic_test_decode_i8_swiglu(sonic_engine* e, const float* X, const float* W, float* act, int M, int ff, int K, int rows_alloc, int layout,
+                                           int8_t* q_out, float* sca_out, int32_t* oc_cnt_out, int32_t* oc_list_out, float* oc_val_out, int32_t* info_out, int32_t* slab_sum_out) {
+    if (!e || !X || !W || !act || !q_out || !sca_out || !oc_cnt_out || !oc_list_out || !oc_val_out) return SONIC_ERR_INVALID;
+    ENTER(e);
+    if (ff < 16 || ff % 16 || ff > 8192 || rows_alloc < M || rows_alloc > 4096) return fail(e, SONIC_ERR_INVALID, "decode_i8_swiglu: ff %% 16 == 0, ff <= 8192, rows_alloc >= M");
+    TRY(i8lin_check(e, "sonic_test_decode_i8_swiglu", M, 2 * ff, K, layout));
+    TmpBuf tb(e->st);
+    I8Lin L;
+    bf16_t* dA = up_bf16(e, tb, act, (size_t)rows_alloc * ff);
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    TRY(i8lin_prepare(e, tb, X, W, M, 2 * ff, K, layout, &L));
+    QuantOut qo{};
+    TRY(quant_alloc(e, tb, M, ff, &qo));
+    i8lin_run(e, &L, nullptr, M, 2 * ff, K);
+    launch_swiglu_quant(L.P, L.ks, L.mpad, ff, dA, M, deq_info(e, L.qx, L.w, K, L.X, 2 * ff), qo, e->st);
+    TRY(down_bf16(e, tb, dA, act, (size_t)rows_alloc * ff));
+    TRY(quant_fetch(e, qo, M, ff, QuantHost{q_out, sca_out, oc_cnt_out, oc_list_out, oc_val_out}));
+    return i8lin_report(e, L, M, 2 * ff, info_out, slab_sum_out);
+}
+
+// q|k|v of the int8 step (X = the hidden rows [B][D], Wqkv [(Hq + 2 Hkv) * 128][D]), then launch_decode_attn in fused mode with the DeqInfo, amax_out and big_out; rope_cs,
+// the caches and kv_len as sonic_test_decode_attention_cache takes them.  amax [B][4] and big [B][4] go up with the caller's contents and come back as the launch left them
+extern "C" int sonic_test_decode_i8_attn(sonic_engine* e, const float* X, const float* Wqkv, const float* rope_cs, const float* kcache, const float* vcache, const int32_t* kv_len,
+                                         float* amax, int32_t* big, float* out, float* kcache_out, float* vcache_out, int B, int D, int Hq, int Hkv, int ctx_max, int layout,
+                                         int32_t* info_out, int32_t* slab_sum_out) {
+    if (!e || !X || !Wqkv || !rope_cs || !kcache || !vcache || !kv_len || !amax || !big || !out) return SONIC_ERR_INVALID;
+    ENTER(e);
+    const int hd = 128;
+    if (Hkv < 1 || Hkv > 4 || Hq < Hkv || Hq % Hkv || Hq / Hkv > 4 || ctx_max < 1 || ctx_max > (1 << 20)) return fail(e, SONIC_ERR_INVALID, "decode_i8_attn: 1 <= Hkv <= 4, Hq / Hkv in 1 .. 4, ctx_max >= 1");
+    const int N = (Hq + 2 * Hkv) * hd;
+    TRY(i8lin_check(e, "sonic_test_decode_i8_attn", B, N, D, layout));
+    for (int b = 0; b < B; ++b)
+        if (kv_len[b] < 1 || kv_len[b] > ctx_max) return fail(e, SONIC_ERR_INVALID, "kv_len[%d] = %d outside 1..%d", b, kv_len[b], ctx_max);
+    TmpBuf tb(e->st);
+    I8Lin L;
+    const size_t nc = (size_t)B * Hkv * ctx_max * hd, no = (size_t)B * Hq * hd;
+    bf16_t* dk = up_bf16(e, tb, kcache, nc); bf16_t* dv = up_bf16(e, tb, vcache, nc); float* dcs = up_f32(e, tb, rope_cs, (size_t)ctx_max * hd);
+    float* damax = up_f32(e, tb, amax, (size_t)B * 4); int* dbig = tb.get<int>((size_t)B * 4);
+    bf16_t* dO = tb.get<bf16_t>(no); int* kl = tb.get<int>(B);
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    HIPC(e, h2d(e, dbig, big, (size_t)B * 16)); HIPC(e, h2d(e, kl, kv_len, (size_t)B * 4));
+    TRY(i8lin_prepare(e, tb, X, Wqkv, B, N, D, layout, &L));
+    i8lin_run(e, &L, nullptr, B, N, D);
+    DecodeAttnArgs da = decode_attn_args(dk, dv, L.P, nullptr, L.ks, L.mpad, dcs, dO, kl, Hq, Hkv, ctx_max, DT_F16);
+    da.dq = deq_info(e, L.qx, L.w, D, L.X, N); da.amax_out = damax; da.big_out = dbig;
+    launch_decode_attn(da, B, e->st);
+    TRY(down_bf16(e, tb, dO, out, no));
+    if (kcache_out) TRY(down_bf16(e, tb, dk, kcache_out, nc));
+    if (vcache_out) TRY(down_bf16(e, tb, dv, vcache_out, nc));
+    HIPC(e, d2h(e, amax, damax, (size_t)B * 16)); HIPC(e, d2h(e, big, dbig, (size_t)B * 16));
+    return i8lin_report(e, L, B, N, info_out, slab_sum_out);
+}

@@ -439,6 +439,10 @@ int read_back_16(sonic_engine* e, const bf16_t* d, float* h, size_t n);   // n e
 SkinnyArgs skinny_args(const bf16_t* X, long ldx, const bf16_t* W, float* P, int M, int N, int K, int ksplit, int dt);
 DecodeAttnArgs decode_attn_args(bf16_t* Kc, bf16_t* Vc, const float* P, const bf16_t* Q, int ksplit, int mpad, const float* cs, bf16_t* O, const int* kv_len,
                                 int Hq, int Hkv, int ctx_max, int dt);
+// the int8 token step (decode_step_i8, the sonic_test_decode_i8_* hooks): one Linear8bitLt = skinny_i8 into exact int32 slabs (amax == null: X holds the quantised rows;
+// else the fp16 rows, quantised while staged from their absmax partials [M][4]; returns ksplit as launched) + the consumer's DeqInfo from deq_info
+int skinny_i8(sonic_engine* e, const void* X, const float* amax, const int8_t* Wt, float* P, int M, int N, int K);
+DeqInfo deq_info(const sonic_engine* e, const QuantOut& q, const QW& w, int K, const bf16_t* x16, int N);
 FlashArgs prefill_flash_args(const bf16_t* Q, const bf16_t* Kc, const bf16_t* Vt, bf16_t* O, const int* q_off, const int* q_len, const int* kv_len,
                              int Hq, int Hkv, int ctx_max, int dt);
 RopeAppendArgs rope_append_args(const bf16_t* qkv, bf16_t* q_out, bf16_t* Kc, bf16_t* Vc, bf16_t* Vt, long vt_ld, const int* tok_seq, const int* tok_pos, const float* cs,

@@ -366,7 +366,7 @@ template <typename KD, int MB> static void launch_skinny_xs(const SkinnyArgs& a,
 //   cfg 3  32 rows x  512   o_proj   64 x 4 = 256 blocks          (K % 512 == 0, <= 8 slices, 32 x 1024 would give < 192 blocks, this <= 320)
 //   cfg 0  32 rows x 1024   q/k/v    96 x 2 = 192 blocks          (K % 1024 == 0)
 //   cfg 4  32 rows x  256   tiny test configurations              (K % 256 == 0)
-static int skinny_i8_cfg(int N, int K) {
+int skinny_i8_cfg(int N, int K) {
     if (N % 32) return -1;
     if (!g_opts.no_skinny_i8_wide) {
         if (K % 1024 == 0 && N % 96 == 0 && (long)(N / 96) * (K / 1024) >= 192) return 1;

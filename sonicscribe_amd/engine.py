@@ -154,6 +154,9 @@ SIGNATURES = {
     "sonic_set_request_sampling": (I, [vp, vp, vp, I]),
     "sonic_dispatch_submit_sampled": (I, [vp] * 6 + [I, vp, I, I, F, U64, vp, vp, vp, I, i64p]),
     "sonic_test_greedy_sample": (I, [vp, vp] + [I] * 4 + [vp, I, vp, F, I, vp, I] + [vp] * 12),
+    "sonic_test_decode_i8_norm": (I, [vp] * 5 + [F] + [vp] * 3 + [I] * 6 + [vp] * 7),
+    "sonic_test_decode_i8_swiglu": (I, [vp] * 4 + [I] * 5 + [vp] * 7),
+    "sonic_test_decode_i8_attn": (I, [vp] * 12 + [I] * 6 + [vp] * 2),
 }
 del I, F, I64, U64, S, vp, ip, i64p, fp, vpp
 EXPORTS = list(SIGNATURES)

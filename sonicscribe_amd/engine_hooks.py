@@ -316,3 +316,61 @@ class HooksMixin:
         assert cs.shape == (T, rd)
         self._check(self.lib.sonic_test_rope_enc(self.h, _p(qk), qk.shape[0], qk.shape[1], int(T), int(heads2), int(hd), int(rd), _p(cs)))
         return qk
+
+    # ---- the int8 token step: one decode-flavour Linear8bitLt plus its consumer (int8 engines; X [M][K], W [N][K] fp16-valued).  layout 0: W tiled; 1: also the
+    # k-major copy.  Every result dict carries "ksplit" and "cfg" (the int8 skinny GEMM's tiling as launched) and, with want_slab, "slab" int32 [M][N]
+    @staticmethod
+    def _i8_info(r, info, slab):
+        r["ksplit"], r["cfg"] = int(info[0]), int(info[1])
+        if slab is not None:
+            r["slab"] = slab
+        return r
+
+    def test_decode_i8_norm(self, X, W, x, norm_w, eps: float, form: int, layout: int, amax=None, big=None, y_init=None, want_slab: bool = False):
+        """o_proj / down_proj -> add_rmsnorm with a DeqInfo and a QuantOut.  x [rows_alloc][N] residual rows, norm_w [N]; y_init [rows_alloc][N] is what the output
+        buffer holds before the launch (default zeros).  form 1: amax [M][4] fp32 partial maxima, big [M][4] int32 counts.  -> dict: x, y [rows_alloc][N] after,
+        quant = (q int8 [M][N], sca [M], oc_cnt [M], oc_list [M][N], oc_val [M][N])"""
+        X = np.ascontiguousarray(X, np.float32); W = np.ascontiguousarray(W, np.float32)
+        M, K = X.shape; N = W.shape[0]
+        x = np.array(x, np.float32, order="C"); w = np.ascontiguousarray(norm_w, np.float32)
+        assert W.shape == (N, K) and x.shape[1] == N and w.shape == (N,)
+        y = np.zeros_like(x) if y_init is None else np.array(y_init, np.float32, order="C")
+        assert y.shape == x.shape
+        am = _arr(amax, np.float32); bg = _arr(big, np.int32)
+        assert (am is None or am.shape == (M, 4)) and (bg is None or bg.shape == (M, 4))
+        qb = _quant_bufs(M, N)
+        info = np.zeros(2, np.int32); slab = np.zeros((M, N), np.int32) if want_slab else None
+        self._check(self.lib.sonic_test_decode_i8_norm(self.h, _p(X), _p(W), _p(x), _p(w), float(eps), _p(y), _p(am), _p(bg), M, N, K, x.shape[0], int(form), int(layout),
+                                                       *[_p(b) for b in qb], _p(info), _p(slab)))
+        return self._i8_info({"x": x, "y": y, "quant": qb}, info, slab)
+
+    def test_decode_i8_swiglu(self, X, Wgu, layout: int, act_init=None, want_slab: bool = False):
+        """gate/up -> swiglu_quant.  Wgu [2 ff][K], gate / up rows interleaved in groups of 16; act_init [rows_alloc][ff] (default: M rows of zeros).
+        -> dict: act [rows_alloc][ff] after, quant = the five quantiser outputs of act's first M rows"""
+        X = np.ascontiguousarray(X, np.float32); W = np.ascontiguousarray(Wgu, np.float32)
+        M, K = X.shape; ff = W.shape[0] // 2
+        assert W.shape == (2 * ff, K)
+        act = np.zeros((M, ff), np.float32) if act_init is None else np.array(act_init, np.float32, order="C")
+        assert act.shape[1] == ff
+        qb = _quant_bufs(M, ff)
+        info = np.zeros(2, np.int32); slab = np.zeros((M, 2 * ff), np.int32) if want_slab else None
+        self._check(self.lib.sonic_test_decode_i8_swiglu(self.h, _p(X), _p(W), _p(act), M, ff, K, act.shape[0], int(layout), *[_p(b) for b in qb], _p(info), _p(slab)))
+        return self._i8_info({"act": act, "quant": qb}, info, slab)
+
+    def test_decode_i8_attn(self, X, Wqkv, rope_cs, kcache, vcache, kv_len, Hq: int, amax, big, layout: int, want_slab: bool = False):
+        """q|k|v -> the fused decode attention with the int8 prologue.  X [B][D] hidden rows, Wqkv [(Hq + 2 Hkv) * 128][D]; rope_cs, kcache, vcache, kv_len as
+        test_decode_attention_cache; amax [B][4] fp32 and big [B][4] int32 as the buffers are before the launch.  -> dict: out [B][Hq][128], kcache, vcache, amax, big after"""
+        X = np.ascontiguousarray(X, np.float32); W = np.ascontiguousarray(Wqkv, np.float32); cs = np.ascontiguousarray(rope_cs, np.float32)
+        kc = np.ascontiguousarray(kcache, np.float32); vc = np.ascontiguousarray(vcache, np.float32)
+        B, D = X.shape
+        _, Hkv, ctx, hd = kc.shape
+        N = (Hq + 2 * Hkv) * 128
+        assert hd == 128 and kc.shape == vc.shape == (B, Hkv, ctx, 128) and W.shape == (N, D) and cs.shape == (ctx, 128)
+        kl = np.ascontiguousarray(kv_len, np.int32)
+        am = np.array(amax, np.float32, order="C"); bg = np.array(big, np.int32, order="C")
+        assert kl.shape == (B,) and am.shape == bg.shape == (B, 4)
+        out = np.empty((B, Hq, 128), np.float32); ko = np.empty_like(kc); vo = np.empty_like(vc)
+        info = np.zeros(2, np.int32); slab = np.zeros((B, N), np.int32) if want_slab else None
+        self._check(self.lib.sonic_test_decode_i8_attn(self.h, _p(X), _p(W), _p(cs), _p(kc), _p(vc), _p(kl), _p(am), _p(bg), _p(out), _p(ko), _p(vo),
+                                                       B, D, Hq, Hkv, ctx, int(layout), _p(info), _p(slab)))
+        return self._i8_info({"out": out, "kcache": ko, "vcache": vo, "amax": am, "big": bg}, info, slab)

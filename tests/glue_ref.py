@@ -269,3 +269,171 @@ def interleave16(Wg, Wu):
 NORM_RANDOM_CASES = [(3, 264, 3), (17, 2048, 8), (64, 2048, 1)]            # (rows, d, ksplit)
 O_RANDOM_CASES = [(5, 256, 256, 2048), (64, 2048, 2048, 2048)]            # (M, K, D, ff)
 NORM_SEED, O_SEED = 2048, 4096
+
+
+# ------------------------------------------------------------------------------------------ the int8 token step: a decode-flavour Linear8bitLt and its consumers
+# (tests/test_gpu_int8_decode_glue.py).  The Linear's spec is oracle.linear_int8(x_row[None], *oracle.quantize_rows(W)), one row per call; what is restated here is the
+# exact integer product the skinny GEMM must deliver, and the data.
+F16_BELOW_6 = F(5.99609375)              # the largest fp16 value below the threshold: not an outlier
+I8_COUNTS = [65, 0, 3, 129, -1, 1, 2, 4, 5, 7, 63, 64, 66]      # outliers of row i: I8_COUNTS[i % 13]; -1: every element of the row
+I8_FIRST = (0, -1, 63, 64)               # where a row's first outliers go: column 0, column K - 1, both sides of a 64-column tile boundary of the tiled weights
+
+
+def int8_product(codes, cb):
+    """codes [M][K] int8 (quant_row's), cb [N][K] int8 -> codes . cb^T as int64 [M][N].  Computed by the float64 BLAS: every partial sum is an integer of
+    magnitude <= K 127^2 < 2^53, so each float64 operation is exact and the result is the int64 product in any order"""
+    codes = np.asarray(codes); cb = np.asarray(cb)
+    assert codes.dtype == np.int8 and cb.dtype == np.int8 and codes.shape[1] == cb.shape[1] and codes.shape[1] * 127 * 127 < 2 ** 53
+    p = codes.astype(np.float64) @ cb.astype(np.float64).T
+    return p.astype(np.int64)
+
+
+def i8_dequant(acc, sca, scb):
+    """the Linear's output for a row WITHOUT outliers from its integer product (oracle/sonic_oracle.c linear_int8): fp16(fma(float(acc), (sca scb) C, 0)) with fp32
+    products in that order.  acc [N] int, sca fp32, scb [N] fp32.  float(acc) scale is rounded once by the fma: computed in float64 (exact: 24 x 24 bits) and rounded"""
+    sc = ((F(sca) * np.asarray(scb, F)).astype(F) * F(6.200012e-05)).astype(F)
+    return rounder("f16")((np.asarray(acc).astype(F).astype(np.float64) * sc.astype(np.float64)).astype(F))
+
+
+def i8_rows(K, M, seed):
+    """M hidden rows of width K, fp16 values: N(0, 1.5) kept below the threshold (|x| <= 5.9), with I8_COUNTS[i % 13] planted outliers in row i - the first four at
+    I8_FIRST, the others anywhere, ascending lists of every length around the consumers' pair / quad walks and the 64-entry LDS stage.  Outliers are a random sign
+    times U(6.5, 12), except that a row's outlier at column 0 is exactly +6.0 or -6.0 (alternating by row); row i gets +-5.99609375 at column 1 of its
+    quarter i % 4 unless an outlier sits there.  -> (X [M][K], n [M] the rows' outlier counts)"""
+    rng = np.random.default_rng(seed)
+    rt = rounder("f16")
+    X = rt(np.clip(rng.standard_normal((M, K)) * 1.5, -5.9, 5.9))
+    n_out = np.zeros(M, np.int64)
+    for i in range(M):
+        n = I8_COUNTS[i % len(I8_COUNTS)]
+        n = K if n < 0 else min(n, K)
+        first = [c % K for c in I8_FIRST][:n]
+        rest = np.setdiff1d(np.arange(K), first)
+        cols = np.concatenate([first, rng.choice(rest, size=n - len(first), replace=False)]).astype(np.int64) if n else np.zeros(0, np.int64)
+        X[i, cols] = rt(rng.choice([-1.0, 1.0], size=n) * rng.uniform(6.5, 12.0, size=n))
+        if n:
+            X[i, 0] = 6.0 if i % 2 == 0 else -6.0
+        c6 = (i % 4) * (K // 4) + 1                                   # (the row's absmax below the threshold: in a different quarter of the row from row to row)
+        if n < K and c6 not in cols:
+            X[i, c6] = F16_BELOW_6 if i % 8 < 4 else -F16_BELOW_6
+        n_out[i] = n
+    return X.astype(F), n_out
+
+
+def i8_weights(N, K, seed, row_scale=None):
+    """W [N][K]: N(0, 0.05) rounded to fp16; row_scale [N] (optional) multiplies the rows first"""
+    w = np.random.default_rng(seed).standard_normal((N, K)) * 0.05
+    if row_scale is not None:
+        w = w * np.asarray(row_scale, np.float64)[:, None]
+    return rounder("f16")(w).astype(F)
+
+
+def i8_partials(X, parts=4):
+    """what a producer that owns a quarter of each row leaves for the on-the-fly form: per quarter the absmax over |x| < 6 (0 where there is none) and the count of
+    the other elements -> (amax [M][4] fp32, big [M][4] int32).  The row's scale is the maximum of its four partials"""
+    X = np.asarray(X, F)
+    M, K = X.shape
+    q = np.abs(X).reshape(M, parts, K // parts)
+    small = q < THRESHOLD
+    return np.where(small, q, F(0)).max(axis=2).astype(F), (~small).sum(axis=2).astype(np.int32)
+
+
+def i8_codes(X, sca=None):
+    """the rows' int8 codes: quant_row's; with sca [M] given, the codes for that scale instead of the row's own (the on-the-fly form quantises with the maximum of
+    the partials, which is 0 where quant_row says -FLT_MIN: both give all-zero codes)"""
+    X = np.asarray(X, F)
+    out = np.zeros(X.shape, np.int8)
+    for i, y in enumerate(X):
+        codes, a, _, _ = quant_row(y)
+        if sca is not None:
+            assert (F(sca[i]) == a) or (not a > 0 and not F(sca[i]) > 0), (i, float(sca[i]), float(a))
+        out[i] = codes
+    return out
+
+
+def head_partials(out, Hkv):
+    """the decode attention's amax_out / big_out from its own output rows out [B][Hq][128]: per kv head h the maximum over that head's G * 128 outputs of
+    (|o| if |o| < 6 else 0), and the number of outputs with not |o| < 6 -> (amax [B][Hkv] fp32, big [B][Hkv] int32)"""
+    o = np.abs(np.asarray(out, F))
+    B = o.shape[0]
+    o = o.reshape(B, Hkv, -1)
+    with np.errstate(invalid="ignore"):
+        small = o < THRESHOLD
+    return np.where(small, o, F(0)).max(axis=2).astype(F), (~small).sum(axis=2).astype(np.int32)
+
+
+# the cases of tests/test_gpu_int8_decode_glue.py: (N, K, ksplit, cfg, forms, rows); tests/test_glue_ref.py checks the ambiguity cap for the norm cases
+I8_SMALL_M = (1, 5, 16, 17, 33, 64)
+I8_LARGE_M = (5, 33)
+I8_NORM_CASES = [(256, 256, 1, 4, (0, 1), I8_SMALL_M), (256, 2304, 9, 4, (0,), I8_SMALL_M), (256, 1024, 2, 3, (0, 1), I8_SMALL_M),
+                 (2048, 2048, 4, 3, (0, 1), I8_LARGE_M), (2048, 6144, 8, 2, (0, 1), I8_LARGE_M)]
+I8_SWIGLU_CASES = [(1024, 768, 3, 4, I8_SMALL_M), (9216, 2048, 2, 1, I8_LARGE_M)]          # N = 2 ff
+I8_SEED = 8192
+
+
+def i8_norm_data(N, K, seed=I8_SEED):
+    """the 64 master rows of a norm case (a launch of M rows takes the first M): X, outlier counts, W, residual rows N(0, 1) with three rows of +-1e4 behind them,
+    norm weight in [0.5, 1.5]"""
+    X, n = i8_rows(K, 64, seed + N + K)
+    W = i8_weights(N, K, seed + 7 * N + K)
+    rng = np.random.default_rng(seed + N + 3 * K)
+    x = rounder("f16")(rng.standard_normal((64, N))).astype(F)
+    return X, n, W, x, rng.uniform(0.5, 1.5, size=N).astype(F)
+
+
+I8_ATTN_CTX = 200
+# (Hq, Hkv, D, ksplit, cfg, rows): TINY's q|k|v (512 x 256), production's (3072 x 2048), and 512 x 2304: nine slabs, the prologue's slab loop from the ninth on
+I8_ATTN_CASES = [(2, 1, 256, 1, 4, I8_SMALL_M), (16, 4, 2048, 2, 0, I8_LARGE_M), (2, 1, 2304, 9, 4, I8_LARGE_M)]
+I8_ATTN_LENS = (I8_ATTN_CTX - 1, 128, 1, 17, 129, 64, 2, 100)
+V_LOUD = 6.5                             # factor of a loud (row, kv head)'s cached value rows
+
+
+def i8_attn_data(Hq, Hkv, D, B, seed=I8_SEED, ctx=I8_ATTN_CTX):
+    """The int8 attention hook's inputs for B rows (the first B of 64 master rows).
+    Hidden rows: i8_rows.  Wqkv: N(0, 0.05) with rows scaled so that q, k and v come out of an outlier-free row with a standard deviation of about 1.2 whatever D is
+    (1.5 x 0.05 x sqrt(D) is 1.2 at D = 256 and 3.4 at 2048: scores of q . k / sqrt(128) with both at 3.4 put most rows under one dominating key, where fp16
+    probabilities leave the normal range that attn_ref's bound presumes), the v rows of the even kv heads three times that (so that new value rows pass 6.0 there).
+    kv_len: 1 for the rows with 63 outliers or more (their q and k are large, see above; with one key the output is the new value row itself), else I8_ATTN_LENS in turn.
+    Caches: keys N(0, 1), values attn_ref.values (fp16: away from zero), +-1e4 from position kv_len - 1 on; the values of (row b, kv head h) with (b + h) even are
+    'loud': V_LOUD |v| with one sign per column, so that the outputs there land on both sides of 6.0, while the other heads of the row stay far below it.
+    -> dict X, n, W, kc, vc, kv_len, cs"""
+    from attn_ref import values
+    rt = rounder("f16")
+    X, n = i8_rows(D, 64, seed + D + Hq)
+    X, n = X[:B], n[:B]
+    base = 1.2 / (1.5 * 0.05 * np.sqrt(D))
+    scale = np.full((Hq + 2 * Hkv, 128), base)
+    scale[Hq + Hkv::2] *= 3.0
+    W = i8_weights((Hq + 2 * Hkv) * 128, D, seed + 11 * D + Hq, scale.reshape(-1))
+    rng = np.random.default_rng(seed + 5 * D + B)
+    kv_len = np.zeros(B, np.int32)
+    j = 0
+    for b in range(B):
+        if n[b] >= 63:
+            kv_len[b] = 1
+        else:
+            kv_len[b] = I8_ATTN_LENS[j % len(I8_ATTN_LENS)]; j += 1
+    pois = rt(np.where(np.arange(B * Hkv * ctx * 128) % 2 == 0, 1e4, -1e4).astype(F)).reshape(B, Hkv, ctx, 128)
+    kc, vc = pois.copy(), -pois
+    sgn = rng.choice([-1.0, 1.0], size=128)
+    for b in range(B):
+        m = int(kv_len[b]) - 1
+        kc[b, :, :m] = rt(rng.standard_normal((Hkv, m, 128))); vc[b, :, :m] = values(rng, (Hkv, m, 128), "f16")
+        for h in range(Hkv):
+            if (b + h) % 2 == 0:
+                vc[b, h, :m] = rt(np.abs(vc[b, h, :m]) * sgn[None, :] * V_LOUD)
+    return dict(X=X, n=n, W=W, kc=kc.astype(F), vc=vc.astype(F), kv_len=kv_len, cs=rope_table(ctx))
+
+
+def f16_subnormal_share(q, k, v, n, scale):
+    """The premise of attn_ref's bound for fp16, checked on the reference alone: a probability below 2^-14 of the row's largest is rounded with an ABSOLUTE error of up
+    to 2^-25, which the bound u (A + |o|) does not know.  q [hd], k / v [n][hd] -> max over the output elements of (2^-25 x sum of |v_i| over those keys) /
+    (u (A + |o|)): the share of the c = 1 bound that term can take (0 where no key is that far down)"""
+    q = np.asarray(q, np.float64); k = np.asarray(k, np.float64)[:n]; v = np.asarray(v, np.float64)[:n]
+    s = (k @ q) * scale
+    e = np.exp(s - s.max())
+    p = e / e.sum()
+    o = p @ v; A = p @ np.abs(v)
+    extra = 2.0 ** -25 * np.abs(v[e < 2.0 ** -14]).sum(axis=0)
+    b = 2.0 ** -11 * (A + np.abs(o))
+    return float(np.max(np.where(extra > 0, extra / np.where(b > 0, b, 1e-300), 0.0)))

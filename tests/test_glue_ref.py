@@ -160,3 +160,109 @@ def test_rope_reference(kind, rd, hd):
         from attn_ref import fused_prologue
         q, k, v = fused_prologue(x.reshape(1, T, 3 * 128), cs, 1, 1, kind)
         assert np.array_equal(q[:, 0], got[:, 0]) and np.array_equal(k[:, 0], got[:, 1]) and np.array_equal(v[:, 0], x[:, 2])
+
+
+# ------------------------------------------------------------------------------------------ the int8 token step's references (tests/test_gpu_int8_decode_glue.py)
+@pytest.fixture(scope="module")
+def orc():
+    from oracle import oracle
+    return oracle
+
+
+def oracle_rows(orc, X, W):
+    """the Linear's spec: one reference call per row"""
+    cb, scb = orc.quantize_rows(W)
+    return np.concatenate([orc.linear_int8(X[i:i + 1], cb, scb) for i in range(X.shape[0])]), cb, scb
+
+
+def test_i8_rows_are_what_they_claim():
+    for K in (256, 768, 2048):
+        X, n = G.i8_rows(K, 64, K)
+        assert representable(X, "f16") and list(n[:13]) == [K if c < 0 else min(c, K) for c in G.I8_COUNTS]
+        for i, y in enumerate(X):
+            cols = G.quant_row(y)[2]
+            assert len(cols) == n[i], (K, i)
+            if n[i] >= 4:
+                assert {0, 63, 64, K - 1} <= set(cols.tolist())
+            if n[i]:
+                assert y[0] == (6.0 if i % 2 == 0 else -6.0)                   # exactly the threshold: an outlier
+            if n[i] < K and abs(y[(i % 4) * (K // 4) + 1]) < 6:
+                assert abs(y[(i % 4) * (K // 4) + 1]) == G.F16_BELOW_6         # the largest fp16 below it: not one
+            if 4 < n[i] < K:
+                assert (y[cols] > 0).any() and (y[cols] < 0).any()
+        am, big = G.i8_partials(X)
+        assert np.array_equal(big.sum(axis=1), n) and set(am.argmax(axis=1)[n < K].tolist()) == {0, 1, 2, 3}
+        for i, y in enumerate(X):                                               # the maximum of the partials is the row's scale (0 for -FLT_MIN: no element below 6)
+            a = G.quant_row(y)[1]
+            assert am[i].max() == (a if a > 0 else 0.0)
+
+
+def test_int8_product_and_dequant_against_the_oracle(orc):
+    """glue_ref.int8_product equals the plain int64 product, and on rows without outliers its dequantisation IS oracle.linear_int8, bit for bit"""
+    rng = np.random.default_rng(3)
+    a = rng.integers(-127, 128, size=(5, 512)).astype(np.int8); b = rng.integers(-127, 128, size=(48, 512)).astype(np.int8)
+    assert np.array_equal(G.int8_product(a, b), np.einsum("mk,nk->mn", a.astype(np.int64), b.astype(np.int64)))
+    full = np.full((1, 8192), 127, np.int8)
+    assert G.int8_product(full, -full)[0, 0] == -8192 * 127 * 127
+    for N, K in [(256, 256), (256, 1024), (1024, 768)]:
+        X, n = G.i8_rows(K, 64, N + K)
+        W = G.i8_weights(N, K, N * K)
+        X = X[n == 0]
+        assert X.shape[0] >= 4
+        lin, cb, scb = oracle_rows(orc, X, W)
+        P = G.int8_product(G.i8_codes(X), cb)
+        for i in range(X.shape[0]):
+            got = G.i8_dequant(P[i], G.quant_row(X[i])[1], scb)
+            assert np.array_equal(got.view(np.uint32), lin[i].view(np.uint32)), (N, K, i)
+
+
+def test_i8_norm_cases_keep_the_ambiguity_cap(orc):
+    """the norm consumer's reference alone - the oracle's rows, the residual add, norm_lo_hi - stays under the fp16 cap for the data and every row count the GPU
+    test uses; the partials of the on-the-fly form put their maximum into each of the four slots"""
+    for N, K, _, _, forms, Ms in G.I8_NORM_CASES:
+        X, n, W, x, w = G.i8_norm_data(N, K)
+        M = max(Ms)
+        lin, _, _ = oracle_rows(orc, X[:M], W)
+        assert np.all(np.isfinite(lin)) and representable(lin, "f16")
+        xn = G.residual_add(x[:M], lin, "f16")
+        lo, hi = G.norm_lo_hi(xn, w, 1e-5, "f16")
+        for m in Ms:
+            ok, share = G.in_pair(lo[:m], lo[:m], hi[:m])
+            assert ok and share <= G.AMBIGUOUS_CAP["f16"], (N, K, m, share)
+        if 1 in forms and M >= 4:
+            assert set(G.i8_partials(X[:M])[0].argmax(axis=1)[n[:M] < K].tolist()) == {0, 1, 2, 3}
+
+
+def test_head_partials():
+    out = np.zeros((2, 4, 128), F)
+    out[0, 0, 5] = -5.5; out[0, 1, 7] = 6.0; out[0, 1, 8] = 3.0; out[0, 3, 0] = np.float32(-7.25); out[1, 2, 127] = G.F16_BELOW_6
+    am, big = G.head_partials(out, 2)
+    assert am.tolist() == [[5.5, 0.0], [0.0, float(G.F16_BELOW_6)]] and big.tolist() == [[1, 1], [0, 0]]
+    am, big = G.head_partials(out, 4)
+    assert am.tolist() == [[5.5, 3.0, 0.0, 0.0], [0.0, 0.0, float(G.F16_BELOW_6), 0.0]] and big.tolist() == [[0, 1, 0, 1], [0, 0, 0, 0]]
+
+
+def test_i8_attn_data_keeps_the_bounds_premise(orc):
+    """the int8 attention cases, from the reference alone: fp16 probabilities that leave the normal range cost at most a quarter of the c = 1 bound (attn_ref's
+    docstring; the data keeps q and k near N(0, 1.2) and gives the rows with many outliers one key), and the outputs put heads on both sides of 6.0"""
+    from attn_ref import attention, fused_prologue
+    scale = 1.0 / np.sqrt(128.0)
+    for Hq, Hkv, D, _, _, Bs in G.I8_ATTN_CASES:
+        B = max(Bs)
+        d = G.i8_attn_data(Hq, Hkv, D, B)
+        assert representable(d["X"], "f16") and representable(d["W"], "f16") and np.abs(d["W"][d["W"] != 0]).min() >= 2.0 ** -24
+        assert set(d["kv_len"].tolist()) >= {1, 128, G.I8_ATTN_CTX - 1} and np.all(d["kv_len"][d["n"] >= 63] == 1)
+        lin, _, _ = oracle_rows(orc, d["X"], d["W"])
+        pos = d["kv_len"] - 1
+        q, k_new, v_new = fused_prologue(lin[None], d["cs"][pos], Hq, Hkv, "f16")
+        kc, vc = d["kc"].copy(), d["vc"].copy()
+        assert np.all(np.abs(kc[np.arange(B), :, pos]) == 1e4) and np.all(np.abs(vc[np.arange(B), :, pos]) == 1e4)      # poison where the kernel appends, and behind
+        kc[np.arange(B), :, pos] = k_new; vc[np.arange(B), :, pos] = v_new
+        out = np.zeros((B, Hq, 128), F)
+        for b in range(B):
+            for h in range(Hq):
+                g = h // (Hq // Hkv)
+                assert G.f16_subnormal_share(q[b, h], kc[b, g], vc[b, g], int(d["kv_len"][b]), scale) <= 0.25, (Hq, D, b, h)
+                out[b, h] = rounder("f16")(attention(q[b, h][None], kc[b, g], vc[b, g], [d["kv_len"][b]], scale)[0][0])
+        am, big = G.head_partials(out, Hkv)
+        assert (big > 0).any() and (big == 0).any() and ((big > 0) & (am > 0)).any()

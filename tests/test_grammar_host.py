@@ -161,13 +161,13 @@ def test_prefix_allowed_tokens_fn_follows_the_generated_ids():
 
 # ------------------------------------------------------------------------------------------ ABI surface and Python refusals
 def test_abi_surface():
-    """the feature adds no entry point (the header, the binding table and exports.map keep their 100 names; the ABI stays 12): a grammar is loaded as an int32
+    """the feature adds no entry point (the header, the binding table and exports.map keep their names, 103 today; the ABI stays 12): a grammar is loaded as an int32
     tensor and everything else is an option of the handle"""
     hdr = open(os.path.join(ROOT, "include", "sonic_hip.h")).read()
     emap = open(os.path.join(ROOT, "sonicscribe_amd", "csrc", "exports.map")).read()
     assert "global: sonic_*" in emap
     declared = set(re.findall(r"\b(sonic_[a-z_0-9]+)\s*\(", hdr))
-    assert len(engine.EXPORTS) == 100 == len(declared) and set(engine.EXPORTS) == declared and engine.EXPORTS == list(engine.SIGNATURES)
+    assert len(engine.EXPORTS) == 103 == len(declared) and set(engine.EXPORTS) == declared and engine.EXPORTS == list(engine.SIGNATURES)
     assert "#define SONIC_ABI_VERSION 12" in hdr and engine.ABI_VERSION == 12
     assert "SONIC_DTYPE_I32 = 2" in hdr and engine.DTYPE_I32 == 2 and '"grammar:<id>"' in hdr and '"grammar.hook:<V>"' in hdr and '"grammar.dispatch:<id>"' in hdr
     src = open(os.path.join(ROOT, "sonicscribe_amd", "csrc", "engine_options.cpp")).read()
