@@ -207,7 +207,19 @@ SONIC_API int sonic_pipeline_destroy(sonic_pipeline* p);
  *   ("forced_parallel"); and at the prefill: an A that is not the batch's R; forced ids set (sonic_set_forced_ids); a draft in the same prefill; a per-row stage
  *   that was given another count than R'.
  *   sonic_debug_read "kcache" / "vcache" (index = decoder layer, Bm * Hkv * max_ctx * head_dim elements) read the cache; "fork_ms" (n = 1) is the kernel's time in
- *   the handle's last forked prefill. */
+ *   the handle's last forked prefill.
+ *
+ * Truncation (option "truncation", sonic_load_tensor "request_truncation" / "truncation.hook"): top_k / top_p / min_p on the temperature-scaled scores
+ * of a sampling row - HF's TopK -> TopP -> MinP warpers - with the cut found inside the greedy kernel.  sonic_set_option(e, "truncation", 1): on the owner before its
+ * slots (they copy it); SONIC_ERR_INVALID naming "sampling" unless that option is on, and while the handle has work in hand; 768 bytes (64 rows x 3 words).
+ *   sonic_load_tensor(e, "request_truncation", values, SONIC_DTYPE_F32, {R, 3}, 2): row r of the NEXT prefill on this handle (the entry points
+ *   sonic_set_request_bias names) draws under top_k = values[3r] (an integer, 0 = off), top_p = values[3r + 1] (in (0, 1], 1 = off), min_p = values[3r + 2] (in [0, 1],
+ *   0 = off); NaN and values out of range are refused by name, nothing is clamped; rows with temperature 0 ignore them.  Consumed or dropped with the sampling values;
+ *   stated per row under forks; a prefill without them has every filter off; sonic_splice_rows copies a row's words and refuses handles whose options differ.
+ *   "truncation.dispatch" (SONIC_DTYPE_F32, {3}: top_k, top_p, min_p) arms the calling thread's NEXT sonic_dispatch_submit_sampled, as "grammar.dispatch:<id>" arms a
+ *   grammar: refused by name unless every handle of the dispatcher has the option, and when the submit that follows is another one.
+ *   "truncation.hook" (same layout, B rows) arms the next sonic_test_greedy_sample launch; sonic_debug_read "hook_truncation" (3B floats) returns its records: the y of
+ *   the last kept id in (y descending, id ascending), that id, the kept count n; (0, -1, V) for a row that was not cut. */
 SONIC_API int sonic_load_tensor(sonic_engine* e, const char* name, const void* data, int dtype, const int64_t* shape, int ndim);
 SONIC_API int sonic_load_synthetic(sonic_engine* e, uint64_t seed);          /* portable generator, sonicscribe_amd/synth.py */
 SONIC_API int sonic_finalize_weights(sonic_engine* e);                        /* packs fused QKV / gate-up, conv im2col order */

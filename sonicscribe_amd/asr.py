@@ -93,6 +93,7 @@ class Transcription:
     __slots__ = ("text", "token_ids", "token_logprobs", "avg_logprob", "temperature", "compression_ratio", "attempts", "top_token_ids", "top_logprobs",
                  "draft_len", "draft_matched",      # a request that brought a draft (ASRModel(draft_verify=True)): the ids of the draft as it was submitted, and how many of them the transcript begins with; 0 without
                  "best_of", "fork_index", "fork_avg_logprobs",      # an attempt that drew best_of samples from one forked run (ASRModel(best_of=N)): how many, which of them this is, and every sample's avg_logprob in fork order; 1, 0 and this transcript's own otherwise
+                 "top_k", "top_p", "min_p",      # what a sampled transcript's tail was cut with (ASRModel(sampling=True, top_k=, top_p=, min_p=)); 0, 1.0, 0.0: nothing, and always at temperature 0
                  "grammar_status",      # a request decoded under a grammar: grammar.Grammar.walk over token_ids - "accepted", "incomplete" or "left"; None without
                  "words", "token_start", "token_end")      # word_timestamps=True (ASRModel(timestamps=True)): timestamps.Word list and the tokens' times (EOS dropped); None without
 
@@ -101,6 +102,7 @@ class Transcription:
         self.text = text
         self.words = self.token_start = self.token_end = self.grammar_status = None
         self.draft_len = self.draft_matched = 0
+        self.top_k, self.top_p, self.min_p = 0, 1.0, 0.0
         self.temperature, self.compression_ratio, self.attempts = float(temperature), compression_ratio(text), 1
         self.token_ids = np.asarray(token_ids, np.int32)
         top_lp = top_ids = None
@@ -181,7 +183,13 @@ def _only_text(fut: "Future") -> "Future[str]":
     return out
 
 
-def _text_future(inner: "Future", decode, detailed: bool = False, temperature: float = 0.0, grammar=None, draft=None) -> "Future[str]":
+def _stamp_cut(tr, temperature: float, cut) -> None:
+    """the (top_k, top_p, min_p) a Transcription was decoded under: the call's at a temperature above 0, none at 0 (greedy rows ignore them)"""
+    if cut and temperature > 0:
+        tr.top_k, tr.top_p, tr.min_p = cut
+
+
+def _text_future(inner: "Future", decode, detailed: bool = False, temperature: float = 0.0, grammar=None, draft=None, cut=()) -> "Future[str]":
     """Future of the transcript behind a dispatcher future of token ids.  Cancelling it (a session that went away) cancels the queued
     request as well, so it never reaches the device.  detailed: the inner future carries (ids, log-probabilities), the result is a Transcription."""
     out: "Future[str]" = Future()
@@ -193,6 +201,7 @@ def _text_future(inner: "Future", decode, detailed: bool = False, temperature: f
             if detailed:
                 ids, lps = f.result()
                 tr = Transcription(decode(ids).strip(), ids, lps, temperature)
+                _stamp_cut(tr, temperature, cut)
                 if grammar is not None:
                     tr.grammar_status = grammar.grammar.walk(tr.token_ids)
                 if draft:
@@ -276,7 +285,7 @@ class AudioStream:
 
     def submit_samples(self, first: int, n: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None, detailed: bool = False,
                        sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature: Optional[float] = None,
-                       seed: Optional[int] = None, word_timestamps: bool = False, grammar=None, draft=None) -> "Future[str]":
+                       seed: Optional[int] = None, word_timestamps: bool = False, grammar=None, draft=None, top_k=None, top_p=None, min_p=None) -> "Future[str]":
         """Transcribe ring samples [first, first + n) (the >30 s split of connection_manager.py:206-214 cuts at byte offsets, not chunks).
         detailed (a model built with token_logprobs=True): the future gives a Transcription instead of the text.  temperature / seed (a model built with
         sampling=True): one attempt at that temperature - a float only, stream decodes take no fallback ladder.  draft (a model built with draft_verify=True): what the
@@ -285,7 +294,7 @@ class AudioStream:
         if word_timestamps:
             raise ValueError("word_timestamps is not supported on submit() / transcribe_async() / stream decodes: align a finished transcript with ASRModel.align(), or use transcribe(..., word_timestamps=True)")
         m._check_detailed(detailed)
-        values = m._request_values(hotwords, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, grammar, draft, int(max_new_tokens), ladder_ok=False)
+        values = m._request_values(hotwords, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, grammar, draft, int(max_new_tokens), ladder_ok=False, cut=(top_k, top_p, min_p))
         windows = [self.ring.slice(first + s, e - s) for s, e in frontend.split_windows(n, m.dims)]
         n_audio, _ = frontend.request_audio_tokens(n, m.dims)
         prompt = m.prompt.build(frontend.build_instruction(hotwords), n_audio)
@@ -293,10 +302,10 @@ class AudioStream:
 
     def submit_chunks(self, start_chunk_id: int, end_chunk_id: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None,
                       detailed: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
-                      temperature: Optional[float] = None, seed: Optional[int] = None, word_timestamps: bool = False, grammar=None, draft=None) -> "Future[str]":
+                      temperature: Optional[float] = None, seed: Optional[int] = None, word_timestamps: bool = False, grammar=None, draft=None, top_k=None, top_p=None, min_p=None) -> "Future[str]":
         """Transcribe chunks start..end inclusive (audio_manager.py:76-79 get_chunks_by_range + :115-123 concatenation)."""
         first, n = self.chunk_range_samples(start_chunk_id, end_chunk_id)
-        return self.submit_samples(first, n, max_new_tokens, hotwords, detailed, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, word_timestamps, grammar, draft)
+        return self.submit_samples(first, n, max_new_tokens, hotwords, detailed, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, word_timestamps, grammar, draft, top_k=top_k, top_p=top_p, min_p=min_p)
 
     async def transcribe_chunks(self, start_chunk_id: int, end_chunk_id: int, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None) -> str:
         return await asyncio.wrap_future(self.submit_chunks(start_chunk_id, end_chunk_id, max_new_tokens, hotwords))
@@ -313,7 +322,7 @@ class ASRModel:
                  *, max_batch: int = 32, max_ctx: int = 1024, slots: int = DEFAULT_SLOTS, continuous: bool = DEFAULT_CONTINUOUS, decoders: int = 1, bulk: bool = False, native_dispatch: Optional[bool] = None, token_logprobs: bool = False, top_logprobs: int = 0,
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None,
                  request_bias: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: float = 0.0,
-                 sampling: bool = False, temperature=0.0, seed: int = 0, compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0, best_of: int = 1,
+                 sampling: bool = False, temperature=0.0, seed: int = 0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0, compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0, best_of: int = 1,
                  scoring: bool = False, timestamps: bool = False, alignment_heads=None, grammar: bool = False, draft_verify: bool = False,
                  _dims: Optional[ModelDims] = None,
                  _synthetic_seed: Optional[int] = None, _allow_synthetic_prompt: bool = False, _options: Optional[Dict[str, int]] = None,
@@ -347,6 +356,9 @@ class ASRModel:
         self.compression_ratio_threshold, self.logprob_threshold = compression_ratio_threshold, logprob_threshold
         if not self.sampling and (any(t != 0.0 for t in ts_) or self._default_seed != 0):
             raise ValueError("temperature / seed need a model built with sampling=True (ASRModel(..., token_logprobs=True, sampling=True))")
+        self._default_cut = sampling_.check_truncation(top_k, top_p, min_p)      # every sampled decode's tail cut: each rung of a ladder above 0, every fork of best_of
+        if not self.sampling and self._default_cut != (0, 1.0, 0.0):
+            raise ValueError("top_k / top_p / min_p need a model built with sampling=True (ASRModel(..., token_logprobs=True, sampling=True))")
         if self.sampling and not token_logprobs:
             raise ValueError("sampling=True needs token_logprobs=True: the sampling kernels are log-probability kernels, and the fallback ladder reads avg_logprob")
         if self.sampling and bool(bulk):
@@ -459,6 +471,7 @@ class ASRModel:
         if self.sampling:
             for eng in self.models:
                 eng.set_option("sampling", 1)
+                eng.set_option("truncation", 1)      # (top_k / top_p / min_p ride on the sampling values; rows that state none take the kernel's branch around the select)
         if self.grammar:
             for eng in self.models:
                 eng.set_option("grammar", 1)
@@ -558,20 +571,27 @@ class ASRModel:
         out = reqbias.combine(self._default_bias, call, hot)
         return out if out else None
 
-    def _request_sampling(self, temperature=None, seed=None, ladder_ok: bool = True):
+    def _request_sampling(self, temperature=None, seed=None, ladder_ok: bool = True, cut=None):
         """One call's sampling: None (a model without the option, nothing asked), or (temperatures, is it a ladder, seed) from the call's values over the
-        constructor's defaults.  ValueError naming sampling when the call gives a value and the model was built without the option."""
+        constructor's defaults, with a fourth member (top_k, top_p, min_p) unless all three are off - such a request states pairs, as it always did.  `cut` in: the
+        call's three values, None for one it does not state.  ValueError naming sampling when the call gives a value and the model was built without the option."""
         from . import sampling as sampling_
+        cut = (None, None, None) if cut is None else tuple(cut)
         if not getattr(self, "sampling", False):
             if temperature is not None or seed is not None:
                 raise ValueError("temperature / seed need a model built with sampling=True (ASRModel(..., token_logprobs=True, sampling=True))")
+            if any(v is not None for v in cut):
+                raise ValueError("top_k / top_p / min_p need a model built with sampling=True (ASRModel(..., token_logprobs=True, sampling=True))")
             return None
         if getattr(self, "bulk", False):
             raise ValueError("a temperature is not supported with bulk=True")
         ts, ladder = sampling_.temperatures(self._default_temperature if temperature is None else temperature)
         if ladder and not ladder_ok:
             raise ValueError("stream decodes take one temperature (a float), not a fallback ladder")
-        return ts, ladder, sampling_.check_seed(self._default_seed if seed is None else seed)
+        dflt = getattr(self, "_default_cut", (0, 1.0, 0.0))
+        c = sampling_.check_truncation(*[d if v is None else v for v, d in zip(cut, dflt)])
+        base = (ts, ladder, sampling_.check_seed(self._default_seed if seed is None else seed))
+        return base if c == (0, 1.0, 0.0) else base + (c,)      # (all three off: the triple it always was)
 
     def compile_grammar(self, phrases_or_grammar, repeat: bool = False):
         """A grammar for `grammar=` of the transcribe calls: a grammar.Grammar, or a list of phrases (grammar.Grammar.from_phrases: each phrase, cleaned as hotwords
@@ -625,11 +645,11 @@ class ASRModel:
         ids = cut_draft(self._candidate_ids(draft), self._eos_ids(), max_new)
         return ids or None
 
-    def _request_values(self, hotwords, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, grammar, draft, max_new: int, ladder_ok: bool = True):
+    def _request_values(self, hotwords, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, grammar, draft, max_new: int, ladder_ok: bool = True, cut=None):
         """One call's own values, checked in this order: (bias, samp, gram, draft) as _request_bias, _request_sampling, _request_grammar and _request_draft give
         them - what _dispatch takes behind `detailed`, and reqvalues.submit_keywords turns into Dispatcher.submit's keywords."""
         bias = self._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost)
-        samp = self._request_sampling(temperature, seed, ladder_ok=ladder_ok)
+        samp = self._request_sampling(temperature, seed, ladder_ok=ladder_ok, cut=cut)
         gram = self._request_grammar(grammar)
         return bias, samp, gram, self._request_draft(draft, max_new, bias, samp, gram)
 
@@ -652,7 +672,7 @@ class ASRModel:
         self._fork_next = (self._fork_next + 1) % len(self._fork_engines)
         return self._fork_next
 
-    def _forked_run(self, replica: int, windows_per_audio, prompts, budgets, biases, grams, temperature: float, seed: int, n: int) -> List[Transcription]:
+    def _forked_run(self, replica: int, windows_per_audio, prompts, budgets, biases, grams, temperature: float, seed: int, n: int, cut=()) -> List[Transcription]:
         """ONE forked run on the replica's fork handle (the caller is that replica's worker thread): every audio becomes n rows that share its encoder pass and
         prefill; fork j decodes at `temperature` with seed sampling.fork_seed(seed, j) under the audio's own bias table, grammar and budget.  Per audio the
         Transcription fallback.pick_best selects, with best_of, fork_index and fork_avg_logprobs filled in."""
@@ -663,7 +683,7 @@ class ASRModel:
         samp, bias_rows, gram_rows = [None] * (n * len(prompts)), [None] * (n * len(prompts)), [None] * (n * len(prompts))
         for a, rr in enumerate(rows):
             for j, r in enumerate(rr):
-                samp[r] = (temperature, sampling_.fork_seed(seed, j))
+                samp[r] = (temperature, sampling_.fork_seed(seed, j)) + tuple(cut)      # (every fork under the same cut)
                 bias_rows[r] = biases[a] if biases[a] else None
                 gram_rows[r] = None if grams[a] is None else grams[a].on(eng)
         kw = {}
@@ -683,6 +703,7 @@ class ASRModel:
             j = fallback.pick_best(avgs)
             win = trs[j]
             win.best_of, win.fork_index, win.fork_avg_logprobs = n, j, np.asarray(avgs, np.float64)
+            _stamp_cut(win, temperature, cut)
             if grams[a] is not None:
                 win.grammar_status = grams[a].grammar.walk(win.token_ids)
             out.append(win)
@@ -702,9 +723,9 @@ class ASRModel:
         self._fork_workers[replica].post(run)
         return out
 
-    def _forked_attempt(self, windows, prompt, max_new: int, bias, gram, temperature: float, seed: int, n: int, route) -> "Future":
+    def _forked_attempt(self, windows, prompt, max_new: int, bias, gram, temperature: float, seed: int, n: int, route, cut=()) -> "Future":
         """one request's sampled attempt as a forked run of n rows -> a future of the winning Transcription"""
-        runs = self._forked_post(self._fork_replica(route), [windows], [prompt], [max_new], [bias], [gram], float(temperature), seed, n)
+        runs = self._forked_post(self._fork_replica(route), [windows], [prompt], [max_new], [bias], [gram], float(temperature), seed, n, cut)
         out: "Future" = Future()
 
         def done(f):
@@ -727,18 +748,19 @@ class ASRModel:
         (_forked_run); an attempt at temperature 0 is the one greedy decode it always was."""
         from . import fallback
         kw = dict(route, **reqvalues.submit_keywords(bias, samp, gram, draft))
+        cut = () if samp is None or len(samp) < 4 else samp[3]      # (top_k, top_p, min_p): every rung of a ladder above 0 and every fork repeat them
         if samp is not None and not samp[1] and best_of > 1 and samp[0][0] > 0:
-            fut = self._forked_attempt(windows, prompt, max_new, bias, gram, samp[0][0], samp[2], best_of, route)
+            fut = self._forked_attempt(windows, prompt, max_new, bias, gram, samp[0][0], samp[2], best_of, route, cut)
             return fut if detailed else _only_text(fut)
         if samp is None or not samp[1]:
             return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=detailed, **kw), self.prompt.decode, detailed,
-                                0.0 if samp is None else samp[0][0], grammar=gram, draft=draft)
-        ts, _, seed = samp
+                                0.0 if samp is None else samp[0][0], grammar=gram, draft=draft, cut=cut)
+        ts, seed = samp[0], samp[2]
 
         def one(temperature, seed):
             if best_of > 1 and temperature > 0:
-                return self._forked_attempt(windows, prompt, max_new, bias, gram, temperature, seed, best_of, route)
-            return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=True, sampling=(temperature, seed), **kw), self.prompt.decode, True, temperature, grammar=gram)
+                return self._forked_attempt(windows, prompt, max_new, bias, gram, temperature, seed, best_of, route, cut)
+            return _text_future(self._dispatcher.submit(windows, prompt, max_new, want_logprobs=True, sampling=(temperature, seed) + (cut if temperature > 0 else ()), **kw), self.prompt.decode, True, temperature, grammar=gram, cut=cut)
         policy = fallback.FallbackPolicy(ts, self.compression_ratio_threshold, self.logprob_threshold)
         fut = fallback.decode_with_fallback(one, policy, seed, retrier=self._retrier)
         return fut if detailed else _only_text(fut)
@@ -749,7 +771,7 @@ class ASRModel:
 
     def submit(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128, hotwords: Optional[List[str]] = None,
                session: Optional[str] = None, detailed: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
-               temperature=None, seed: Optional[int] = None, word_timestamps: bool = False, grammar=None, draft=None, best_of: Optional[int] = None) -> "Future[str]":
+               temperature=None, seed: Optional[int] = None, word_timestamps: bool = False, grammar=None, draft=None, best_of: Optional[int] = None, top_k=None, top_p=None, min_p=None) -> "Future[str]":
         """Non-blocking form of transcribe(): queues the request on a replica and returns a Future of the transcript.  `session`
         (e.g. the WebSocket client id) keeps a session's decodes on one GPU.  detailed (a model built with token_logprobs=True): the future
         gives a Transcription - text, token_ids, token_logprobs, avg_logprob - instead of the text.  sequence_bias / bad_words_ids / hotword_boost (a model
@@ -767,7 +789,7 @@ class ASRModel:
             raise ValueError("word_timestamps is not supported on submit() / transcribe_async() / stream decodes: align a finished transcript with ASRModel.align(), or use transcribe(..., word_timestamps=True)")
         self._check_detailed(detailed)
         n_best = self._request_best_of(best_of)
-        values = self._request_values(hotwords, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, grammar, draft, int(max_new_tokens))
+        values = self._request_values(hotwords, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, grammar, draft, int(max_new_tokens), cut=(top_k, top_p, min_p))
         pcm, windows, n_audio = self._prepare(audio_tensor, sampling_rate)
         prompt = self.prompt.build(frontend.build_instruction(hotwords), n_audio)
         return self._dispatch(windows, prompt, int(max_new_tokens), detailed, *values, best_of=n_best, session=session)
@@ -785,15 +807,15 @@ class ASRModel:
     async def transcribe_async(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128,
                                hotwords: Optional[List[str]] = None, session: Optional[str] = None, detailed: bool = False,
                                sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None, seed: Optional[int] = None,
-                               word_timestamps: bool = False, grammar=None, draft=None, best_of: Optional[int] = None) -> str:
+                               word_timestamps: bool = False, grammar=None, draft=None, best_of: Optional[int] = None, top_k=None, top_p=None, min_p=None) -> str:
         """Awaitable transcribe() for the asyncio callers (connection_manager.py:127-245): the event loop is not blocked while the
         device works, so all sessions' partial and final decodes can be in flight (and batched) together."""
-        return await asyncio.wrap_future(self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, session, detailed, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, word_timestamps, grammar, draft, best_of))
+        return await asyncio.wrap_future(self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, session, detailed, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, word_timestamps, grammar, draft, best_of, top_k=top_k, top_p=top_p, min_p=min_p))
 
     def transcribe(self, audio_tensor, sampling_rate: int = 16000, max_new_tokens: int = 128,
                    hotwords: Optional[List[str]] = None, return_debug_info: bool = False,
                    sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None, seed: Optional[int] = None,
-                   word_timestamps: bool = False, grammar=None, draft=None, best_of: Optional[int] = None) -> Union[str, Dict[str, Any]]:
+                   word_timestamps: bool = False, grammar=None, draft=None, best_of: Optional[int] = None, top_k=None, top_p=None, min_p=None) -> Union[str, Dict[str, Any]]:
         """best_of (a model built with best_of > 1): see submit(); the debug dictionary gains `best_of` and `fork_index`.
         draft (a model built with draft_verify=True): see submit(); the debug dictionary gains `draft_len` and `draft_matched`.
         grammar (a model built with grammar=True): what compile_grammar() returned; the debug dictionary gains `grammar_status` (grammar.Grammar.walk over
@@ -809,7 +831,7 @@ class ASRModel:
         try:
             want = bool((return_debug_info or word_timestamps) and getattr(self, "token_logprobs", False))
             res = self.submit(audio_tensor, sampling_rate, max_new_tokens, hotwords, detailed=want, sequence_bias=sequence_bias, bad_words_ids=bad_words_ids,
-                              hotword_boost=hotword_boost, temperature=temperature, seed=seed, grammar=grammar, draft=draft, best_of=best_of).result()
+                              hotword_boost=hotword_boost, temperature=temperature, seed=seed, grammar=grammar, draft=draft, best_of=best_of, top_k=top_k, top_p=top_p, min_p=min_p).result()
             det, transcript = (res, res.text) if want else (None, res)
             if word_timestamps:
                 self._attach_alignment([audio_tensor], [det], sampling_rate, hotwords)
@@ -826,7 +848,7 @@ class ASRModel:
                     if getattr(self, "top_logprobs", 0):             # a top_logprobs model: the K best ids of every step and their log-probabilities
                         info.update({"top_token_ids": det.top_token_ids, "top_logprobs": det.top_logprobs})
                     if getattr(self, "sampling", False):             # a sampling model: what the transcript was decoded at, and the ladder's other measure
-                        info.update({"temperature": det.temperature, "compression_ratio": det.compression_ratio})
+                        info.update({"temperature": det.temperature, "compression_ratio": det.compression_ratio, "top_k": det.top_k, "top_p": det.top_p, "min_p": det.min_p})
                     if getattr(self, "best_of", 1) > 1:              # a best_of model: how many samples the returned attempt drew, and which of them this is
                         info.update({"best_of": det.best_of, "fork_index": det.fork_index})
                     if grammar is not None:
@@ -847,7 +869,7 @@ class ASRModel:
 
     def transcribe_batch(self, audios: Sequence[Any], sampling_rate: int = 16000, max_new_tokens: Union[int, Sequence[int]] = 128,
                          hotwords: Optional[List[str]] = None, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
-                         temperature=None, seed: Optional[int] = None, word_timestamps: bool = False, grammar=None, drafts=None, best_of: Optional[int] = None) -> List[str]:
+                         temperature=None, seed: Optional[int] = None, word_timestamps: bool = False, grammar=None, drafts=None, best_of: Optional[int] = None, top_k=None, top_p=None, min_p=None) -> List[str]:
         """Batched extension (the reference is B=1 per call): one device batch, per-segment results identical to transcribe().  temperature / seed: every
         segment is decoded with them (a sequence: every segment goes down its own ladder, as independent requests on the scheduler).  word_timestamps (a model
         built with timestamps=True): every audio is decoded as its own request, then all are aligned together; the result is a list of Transcription.
@@ -866,11 +888,11 @@ class ASRModel:
             self._check_timestamps()
             mn_ = [int(max_new_tokens)] * len(audios) if isinstance(max_new_tokens, int) else [int(x) for x in max_new_tokens]
             futs_ = [self.submit(a, sampling_rate, mn_[i], hotwords, detailed=True, sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotword_boost=hotword_boost,
-                                 temperature=temperature, seed=seed, grammar=grams[i], draft=None if drafts is None else drafts[i], best_of=best_of) for i, a in enumerate(audios)]
+                                 temperature=temperature, seed=seed, grammar=grams[i], draft=None if drafts is None else drafts[i], best_of=best_of, top_k=top_k, top_p=top_p, min_p=min_p) for i, a in enumerate(audios)]
             dets = [f.result() for f in futs_]
             self._attach_alignment(list(audios), dets, sampling_rate, hotwords)
             return dets
-        bias, samp, _, _ = self._request_values(hotwords, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, None, None, 0)      # (the grammars and drafts: per audio)
+        bias, samp, _, _ = self._request_values(hotwords, sequence_bias, bad_words_ids, hotword_boost, temperature, seed, None, None, 0, cut=(top_k, top_p, min_p))      # (the grammars and drafts: per audio)
         mn = [int(max_new_tokens)] * len(audios) if isinstance(max_new_tokens, int) else [int(x) for x in max_new_tokens]
         drs = [None] * len(audios) if drafts is None else [self._request_draft(d, mn[i], bias, samp, grams[i]) for i, d in enumerate(drafts)]
         segs, req_win, prompts = [], [0], []
@@ -890,7 +912,7 @@ class ASRModel:
             for g0 in range(0, len(audios), per):
                 g = range(g0, min(g0 + per, len(audios)))
                 runs.append(self._forked_post(self._fork_replica({}), [segs[req_win[i]:req_win[i + 1]] for i in g], [prompts[i] for i in g], [mn[i] for i in g],
-                                              [bias] * len(g), [grams[i] for i in g], samp[0][0], samp[2], n_best))
+                                              [bias] * len(g), [grams[i] for i in g], samp[0][0], samp[2], n_best, samp[3] if len(samp) > 3 else ()))
             return [t.text for r in runs for t in r.result()]
         subs = [reqvalues.submit_keywords(bias, samp, grams[i], drs[i]) for i in range(len(audios))]
         if len(self.models) == 1 and not self.continuous:
@@ -1035,7 +1057,7 @@ class ASRModel:
     def transcribe_file(self, audio, vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                         max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filename: str = "", sampling_rate: int = 16000,
                         sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None, seed: Optional[int] = None,
-                        word_timestamps: bool = False, grammar=None):
+                        word_timestamps: bool = False, grammar=None, top_k=None, top_p=None, min_p=None):
         """The body of the reference's /transcribe/file endpoint (main.py:193-649) as a generator of its records (dicts with the
         reference's keys: initialization, segments_summary, segment_result / segment_error in segment order, final_summary).  `audio`:
         mono int16 PCM at `sampling_rate`, or the reference's float tensor [1, N] of int16 / 32768 values; `vad`: a vad.VADProcessor.  The
@@ -1045,17 +1067,17 @@ class ASRModel:
         from . import filemode
         return filemode.transcribe_file(self, audio, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filename, sampling_rate,
                                         sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotword_boost=hotword_boost, temperature=temperature, seed=seed,
-                                        word_timestamps=word_timestamps, grammar=grammar)
+                                        word_timestamps=word_timestamps, grammar=grammar, top_k=top_k, top_p=top_p, min_p=min_p)
 
     def transcribe_files(self, audios: Sequence[Any], vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                          max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filenames: Optional[Sequence[str]] = None,
                          sampling_rate: int = 16000, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None, temperature=None,
-                         seed: Optional[int] = None, word_timestamps: bool = False, grammar=None):
+                         seed: Optional[int] = None, word_timestamps: bool = False, grammar=None, top_k=None, top_p=None, min_p=None):
         """transcribe_file for several files: all VAD passes in one device call, one record iterator per file (filemode.transcribe_files)."""
         from . import filemode
         return filemode.transcribe_files(self, audios, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filenames, sampling_rate,
                                          sequence_bias=sequence_bias, bad_words_ids=bad_words_ids, hotword_boost=hotword_boost, temperature=temperature, seed=seed,
-                                         word_timestamps=word_timestamps, grammar=grammar)
+                                         word_timestamps=word_timestamps, grammar=grammar, top_k=top_k, top_p=top_p, min_p=min_p)
 
     def get_model_info(self) -> Dict[str, Any]:
         """asr.py:490-513: the reference's keys for a GPU device (`cuda_version` carries the HIP runtime version: torch.version.cuda is

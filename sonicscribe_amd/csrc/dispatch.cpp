@@ -41,6 +41,7 @@ namespace {
 struct ReqValues {
     dispatch_pack::BiasTable bias;                                 // its sequence-bias table (sonic_dispatch_submit_bias / _sampled; empty: none)
     bool sampled = false; float temperature = 0.f; uint64_t seed = 0;   // its (temperature, seed) (sonic_dispatch_submit_sampled); unsampled requests of a batch are greedy
+    bool cut = false; float trunc[3] = {0.f, 1.f, 0.f};            // ... and its (top_k, top_p, min_p) ("truncation.dispatch" ahead of that submit; option truncation): they ride on the sampling values
     sonic_grammar* gram = nullptr;                                 // its grammar ("grammar.dispatch:<id>" ahead of the submit): a reference held from the submit until the request completes
     std::vector<int32_t> draft;                                    // its draft ("draft.dispatch" ahead of the submit; option draft_verify): the prefill verifies it
 };
@@ -69,6 +70,7 @@ struct sonic_dispatch {
     int lp_w = 1;                                                  // ... and their records hold this many floats per token (1 + 2K, option top_logprobs: equal on all)
     bool bias = false;                                             // every handle has option request_bias on
     bool samp = false;                                             // every handle has option sampling on
+    bool trunc = false;                                            // every handle has option truncation on
     bool gram = false;                                             // every handle has option grammar on
     bool draft = false; int tok_cap = 0;                           // every handle has option draft_verify on; then a batch's prompts and drafts are counted against tok_cap
     std::mutex mu;
@@ -116,7 +118,14 @@ const Value VALUES[] = {
      [](sonic_engine* h, const std::vector<ReqP>& batch) {
          std::vector<float> t; std::vector<uint64_t> sd;
          for (auto& r : batch) { t.push_back(r->own.sampled ? r->own.temperature : 0.f); sd.push_back(r->own.sampled ? r->own.seed : 0); }
-         return sonic_set_request_sampling(h, t.data(), sd.data(), (int)batch.size());
+         const int rc = sonic_set_request_sampling(h, t.data(), sd.data(), (int)batch.size());
+         bool any = false;
+         for (auto& r : batch) any = any || r->own.cut;
+         if (rc != SONIC_OK || !any) return rc;
+         std::vector<float> rows;                                   // a batch in which some request cuts its tail: every row's three values, off for the others
+         for (auto& r : batch) { const float off[3] = {0.f, 1.f, 0.f}; const float* v = r->own.cut ? r->own.trunc : off; rows.insert(rows.end(), v, v + 3); }
+         const int64_t shape[2] = {(int64_t)batch.size(), 3};
+         return sonic_load_tensor(h, "request_truncation", rows.data(), SONIC_DTYPE_F32, shape, 2);
      }},
     {[](const ReqValues& v) { return v.gram != nullptr; },
      [](sonic_engine* h, const std::vector<ReqP>& batch) {
@@ -336,6 +345,7 @@ SONIC_API int sonic_dispatch_create(sonic_engine* const* decoders, int n_dec, so
     d->lp_w = d->lp ? 1 + 2 * K : 1;
     d->bias = hs.every(engine_request_bias_on);
     d->samp = hs.every(engine_sampling_on);
+    d->trunc = hs.every(engine_truncation_on);
     d->gram = hs.every(engine_grammar_on);
     d->draft = hs.every(engine_draft_verify_on);
     d->tok_cap = engine_tok_cap(prefills[0]);
@@ -378,6 +388,7 @@ static int dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, const int
     sonic_grammar* gram = armed.g;
     const int32_t* draft = nullptr;
     const int n_draft = engine_take_dispatch_draft(&draft);        // ... and the draft ("draft.dispatch"), likewise
+    float cut_row[3]; const bool cut = engine_take_dispatch_truncation(cut_row) != 0;      // ... and the cut ("truncation.dispatch"), likewise
     if (!d || !ticket_out || W < 1 || !prompt_ids || prompt_len < 1 || max_new < 1 || !host_off) return SONIC_ERR_INVALID;
     if (rings && (!ring_start || !ring_n)) return SONIC_ERR_INVALID;
     auto r = std::make_shared<Req>();
@@ -394,6 +405,11 @@ static int dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, const int
     std::unique_lock<std::mutex> lk(d->mu);
     if (d->stop) return SONIC_ERR_INVALID;
     if (d->failed) return d->failed;
+    if (cut) {
+        if (!d->trunc) return option_off("truncation.dispatch", "truncation");
+        if (!r->own.sampled) return engine_thread_fail(SONIC_ERR_INVALID, "truncation.dispatch: the submit that followed is not sonic_dispatch_submit_sampled (top_k / top_p / min_p cut what a sampling request draws from)");
+        r->own.cut = true; memcpy(r->own.trunc, cut_row, sizeof cut_row);
+    }
     if (n_draft > 0) {
         if (!d->draft) return option_off("draft.dispatch", "draft_verify");
         if (n_draft > max_new - 1) {

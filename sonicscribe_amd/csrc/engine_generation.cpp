@@ -191,6 +191,7 @@ static int bias_upload(sonic_engine* e, int R) {
 // ---- option sampling: temperature sampling in the greedy kernel by the Gumbel-max identity, one (temperature, seed) per request - what Whisper's
 // decode_with_fallback retries with.  The caller holds the lock and has asked gen_busy.
 int samp_enable(sonic_engine* e, int on) {
+    if (!on && e->opt_truncation) return fail(e, SONIC_ERR_INVALID, "sampling cannot be switched off while option truncation is on (the filters cut what a sampling row draws from)");
     if (on && !lp_on(e)) return fail(e, SONIC_ERR_INVALID, "sampling: option token_logprobs must be on first (the sampling kernels are log-probability kernels; sonic_set_option(e, \"token_logprobs\", 1))");
     return stage_enable(e, e->samp, on, &e->opt_sampling, "sampling", SAMP_WORDS, false);                  // (zero-filled: every row starts greedy)
 }
@@ -232,6 +233,83 @@ static int samp_upload(sonic_engine* e, int R) {
     HIPC(e, hipMemcpyAsync(e->samp.dev, e->samp.host, (size_t)SAMP_WORDS * 4, hipMemcpyHostToDevice, e->st));
     return stage_sent(e, e->samp);
 }
+// ---- option truncation: top_k / top_p / min_p on the temperature-scaled scores of a sampling row - HF's TopK / TopP / MinP warpers - with the cut
+// found inside the greedy kernel (truncsel.h).  The caller holds the lock and has asked gen_busy.
+int trunc_enable(sonic_engine* e, int on) {
+    if (on && !(e->opt_sampling && e->samp.dev)) return fail(e, SONIC_ERR_INVALID, "truncation: option sampling must be on first (the filters cut what a sampling row draws from; sonic_set_option(e, \"sampling\", 1))");
+    if (on && greedy_guard_lds(e->d.vocab, true) + greedy_trunc_lds() > 60000) return fail(e, SONIC_ERR_UNSUPPORTED, "truncation: a vocabulary of %d ids does not fit the select's histogram beside the guard and bias bitmaps", e->d.vocab);
+    return stage_enable(e, e->trunc, on, &e->opt_truncation, "truncation", TRUNC_STAGE_WORDS, false);      // (zero-filled: every row starts with the three filters off)
+}
+int trunc_pack(sonic_engine* e, const char* who, const float* v, int row, unsigned* w) {
+    const float k = v[0], p = v[1], m = v[2];
+    if (!(k >= 0.f && k <= 16777216.f) || k != floorf(k)) return fail(e, SONIC_ERR_INVALID, "%s: top_k %g of row %d is invalid (an integer in 0 .. 2^24, 0 = off; nothing is clamped)", who, (double)k, row);
+    if (!(p > 0.f && p <= 1.f)) return fail(e, SONIC_ERR_INVALID, "%s: top_p %g of row %d is invalid (a value in (0, 1], 1 = off; nothing is clamped)", who, (double)p, row);
+    if (!(m >= 0.f && m <= 1.f)) return fail(e, SONIC_ERR_INVALID, "%s: min_p %g of row %d is invalid (a value in [0, 1], 0 = off; nothing is clamped)", who, (double)m, row);
+    w[0] = (unsigned)k;
+    w[1] = 0u; if (p < 1.f) memcpy(&w[1], &p, 4);
+    w[2] = 0u; if (m > 0.f) { const float lnm = m < 1.f ? (float)log((double)m) : -0.f; memcpy(&w[2], &lnm, 4); }      // (ln 1 travels as -0.0: y_max + -0.0 = y_max, and the word is not the "off" word)
+    return SONIC_OK;
+}
+static int trunc_rows_check(const char* who, int dtype, const int64_t* shape, int ndim, int max_rows, sonic_engine* e) {
+    if (dtype != SONIC_DTYPE_F32 || ndim != 2 || shape[0] < 1 || shape[1] != 3) return fail(e, SONIC_ERR_INVALID, "%s: the values are float32 rows [top_k | top_p | min_p], one per row of the batch (SONIC_DTYPE_F32, shape {R, 3})", who);
+    if (shape[0] > max_rows || shape[0] > 64) return fail(e, SONIC_ERR_INVALID, "%s: %lld rows (1 .. %d)", who, (long long)shape[0], max_rows < 64 ? max_rows : 64);
+    return SONIC_OK;
+}
+// sonic_load_tensor(e, "request_truncation", values, SONIC_DTYPE_F32, {R, 3}, 2): (top_k, top_p, min_p) of the R rows of the next prefill on this handle (the entry
+// points of sonic_set_request_bias), which consumes them: a later batch starts with the filters off.  Stated per row under forks, as every per-request value
+int trunc_stage_rows(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim) {
+    std::unique_lock<std::mutex> lk; TRY(stage_enter(e, lk, "request_truncation", "truncation", e->opt_truncation, e->trunc));
+    TRY(trunc_rows_check("request_truncation", dtype, shape, ndim, e->Bm, e));
+    unsigned w[TRUNC_STAGE_WORDS] = {0u};
+    for (int r = 0; r < (int)shape[0]; ++r) TRY(trunc_pack(e, "request_truncation", (const float*)data + 3 * r, r, w + 3 * r));
+    HIPC(e, hipSetDevice(e->device));
+    TRY(stage_open(e, e->trunc));
+    memcpy(e->trunc.host, w, sizeof w);
+    e->trunc.pending = (int)shape[0];
+    return SONIC_OK;
+}
+int trunc_hook_arm(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim) {
+    TRY(trunc_rows_check("truncation.hook", dtype, shape, ndim, 64, nullptr));
+    std::vector<unsigned> w((size_t)TRUNC_STAGE_WORDS, 0u);
+    for (int r = 0; r < (int)shape[0]; ++r) TRY(trunc_pack(nullptr, "truncation.hook", (const float*)data + 3 * r, r, w.data() + 3 * r));
+    std::lock_guard<std::mutex> lk(e->mu);
+    e->hook_trunc.swap(w);
+    return SONIC_OK;
+}
+static int trunc_upload(sonic_engine* e, int R) {
+    if (!e->opt_truncation) return SONIC_OK;
+    if (!e->trunc.take && e->opt_trunc_fill) {
+        // option truncation_fill (drivers that only pass integers: bench.py --opt; tools/ab_truncation.sh): every request of a batch without values gets top_k = 50, top_p = 0.9
+        TRY(stage_open(e, e->trunc));
+        const float v[3] = {50.f, 0.9f, 0.f};
+        for (int i = 0; i < TRUNC_STAGE_WORDS; ++i) e->trunc.host[i] = 0u;
+        for (int r = 0; r < R && r < 64; ++r) TRY(trunc_pack(e, "truncation_fill", v, r, e->trunc.host + 3 * r));
+        e->trunc.take = true;
+    }
+    if (!e->trunc.take) { launch_fill_i32((int*)e->trunc.dev, 0, TRUNC_STAGE_WORDS, e->st); return SONIC_OK; } // a batch without values: every filter off
+    HIPC(e, hipMemcpyAsync(e->trunc.dev, e->trunc.host, (size_t)TRUNC_STAGE_WORDS * 4, hipMemcpyHostToDevice, e->st));
+    return stage_sent(e, e->trunc);
+}
+// sonic_load_tensor "truncation.dispatch" on any handle of a dispatcher's weight owner, float32 {3} = (top_k, top_p, min_p): the calling thread's NEXT sonic_dispatch_submit*
+// carries that row, which takes it whatever becomes of the submit (a submit that is not sonic_dispatch_submit_sampled refuses it by name).  A thread-local and no
+// engine lock, as "grammar.dispatch:<id>".  The values are checked here; that every handle of the dispatcher has the option, at the submit
+static thread_local float g_dispatch_trunc[3];
+static thread_local bool g_dispatch_trunc_armed = false;
+int trunc_dispatch_arm(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim) {
+    g_dispatch_trunc_armed = false;
+    if (dtype != SONIC_DTYPE_F32 || ndim != 1 || shape[0] != 3) return fail(nullptr, SONIC_ERR_INVALID, "truncation.dispatch: the values are one float32 row [top_k | top_p | min_p] (SONIC_DTYPE_F32, shape {3})");
+    if (!e->opt_truncation) return fail(nullptr, SONIC_ERR_INVALID, "truncation.dispatch: option truncation is off on this handle (sonic_set_option(e, \"truncation\", 1) on the owner before its slots are created)");
+    unsigned w[3];
+    TRY(trunc_pack(nullptr, "truncation.dispatch", (const float*)data, 0, w));
+    memcpy(g_dispatch_trunc, data, sizeof g_dispatch_trunc); g_dispatch_trunc_armed = true;
+    return SONIC_OK;
+}
+extern "C" int engine_take_dispatch_truncation(float* row) {
+    if (!g_dispatch_trunc_armed) return 0;
+    g_dispatch_trunc_armed = false; memcpy(row, g_dispatch_trunc, sizeof g_dispatch_trunc);
+    return 1;
+}
+extern "C" int engine_truncation_on(sonic_engine* e) { return e && e->opt_truncation && e->trunc.dev ? 1 : 0; }
 extern "C" int engine_sampling_on(sonic_engine* e) { return e && e->opt_sampling && e->samp.dev ? 1 : 0; }
 // ---- option grammar: a request's transcript restricted to the paths of a deterministic token automaton - HF's prefix_allowed_tokens_fn
 // (PrefixConstrainedLogitsProcessor), Vosk's `grammar` - with the mask and the state transition inside the greedy kernel.  Grammars live on the weight owner.
@@ -611,14 +689,15 @@ extern "C" int sonic_get_generation(sonic_engine* e, float* repetition_penalty, 
     return SONIC_OK;
 }
 
-// ---- the stages at every point of a request's life.  Each function below names bias, samp and gram once, in that order; no other unit names them together.  (No
+// ---- the stages at every point of a request's life.  Each function below names bias, samp, gram and trunc once, in that order; no other unit names them together.  (No
 // descriptor table: the stages' words differ in type - int, unsigned, 64-bit - so a table would erase the types to save one line in three per function.)
 int req_claim(sonic_engine* e, int R, bool forked) {
-    const int bias_R = e->bias.claim(), samp_R = e->samp.claim(), gram_R = e->gram.claim();
+    const int bias_R = e->bias.claim(), samp_R = e->samp.claim(), gram_R = e->gram.claim(), trunc_R = e->trunc.claim();
     TRY(stage_count(e, bias_R, R, "sonic_set_request_bias", "tables", forked));
     TRY(stage_count(e, samp_R, R, "sonic_set_request_sampling", "values", forked));
     TRY(stage_count(e, gram_R, R, "option request_grammar_begin", "grammars", forked));
-    e->bias.take = bias_R >= 0; e->samp.take = samp_R >= 0; e->gram.take = gram_R >= 0;      // (read by req_upload alone, which only a prefill that got past this reaches)
+    TRY(stage_count(e, trunc_R, R, "sonic_load_tensor \"request_truncation\"", "values", forked));
+    e->bias.take = bias_R >= 0; e->samp.take = samp_R >= 0; e->gram.take = gram_R >= 0; e->trunc.take = trunc_R >= 0;      // (read by req_upload alone, which only a prefill that got past this reaches)
     const int draft_R = e->draft_pending.exchange(-1);      // the drafts (option draft_verify) are no stage - their words become part of the prefill's plan - but are claimed and dropped with them
     e->draft_take = false;
     if (forked && draft_R >= 0) return fail(e, SONIC_ERR_INVALID, "request_forks: the same prefill was given drafts (sonic_load_tensor \"request_draft\"): a drafted request takes its first tokens from the verify pass, its forks would have none to share");
@@ -627,28 +706,31 @@ int req_claim(sonic_engine* e, int R, bool forked) {
     return SONIC_OK;
 }
 const char* req_claim_none(sonic_engine* e) {
-    const int bias_R = e->bias.claim(), samp_R = e->samp.claim(), gram_R = e->gram.claim();      // (claim leaves `take` false: the run's upload writes the neutral values)
+    const int bias_R = e->bias.claim(), samp_R = e->samp.claim(), gram_R = e->gram.claim(), trunc_R = e->trunc.claim();      // (claim leaves `take` false: the run's upload writes the neutral values)
     if (gram_R >= 0) gram_drop_staged(e);
     e->draft_pending = -1; e->draft_take = false;      // (the option is refused on a scoring handle: nothing can be staged)
     e->fork_pending = -1;                              // (fork counts likewise)
-    return bias_R >= 0 ? "request bias tables (sonic_set_request_bias)" : samp_R >= 0 ? "sampling values (sonic_set_request_sampling)" : gram_R >= 0 ? "grammars (option request_grammar)" : nullptr;
+    return bias_R >= 0 ? "request bias tables (sonic_set_request_bias)" : samp_R >= 0 ? "sampling values (sonic_set_request_sampling)" : gram_R >= 0 ? "grammars (option request_grammar)" : trunc_R >= 0 ? "truncation values (sonic_load_tensor \"request_truncation\")" : nullptr;
 }
-void req_drop_pending(sonic_engine* e) { e->bias.pending = -1; e->samp.pending = -1; if (e->opt_grammar) gram_drop_staged(e); e->draft_pending = -1; e->fork_pending = -1; }
+void req_drop_pending(sonic_engine* e) { e->bias.pending = -1; e->samp.pending = -1; e->trunc.pending = -1; if (e->opt_grammar) gram_drop_staged(e); e->draft_pending = -1; e->fork_pending = -1; }
 int req_upload(sonic_engine* e, int R) {      // (in this order: the copies and fills go onto the stream in it)
     TRY(bias_upload(e, R));                   // every request's table, or a zero count, into its row
     TRY(gram_upload(e, R));                   // every request's grammar at its start node, or a free row
-    return samp_upload(e, R);                 // every request's (temperature, seed), or zeros: greedy
+    TRY(samp_upload(e, R));                   // every request's (temperature, seed), or zeros: greedy
+    return trunc_upload(e, R);                // every row's (top_k, top_p, min_p), or zeros: the filters off
 }
 void req_greedy_args(const sonic_engine* e, GreedyArgs& g) {
     if (e->opt_request_bias) g.bias_tab = e->bias.dev;
     if (e->opt_sampling && g.out_lp) g.samp = e->samp.dev;      // (the option is refused without token_logprobs, and token_logprobs cannot leave while it is on)
+    if (e->opt_truncation && g.samp) g.trunc = e->trunc.dev;   // (the option is refused without sampling, and sampling cannot leave while it is on)
     if (e->opt_grammar && g.out_lp && g.hist) { g.gram_ref = e->gram.dev; g.gram_state = gram_state_of(e); }      // (likewise; the option brought the history)
 }
-int req_graph_key(const sonic_engine* e) { return (e->opt_request_bias ? GK_BIAS : 0) + (e->opt_sampling ? GK_SAMPLE : 0) + (e->opt_grammar ? GK_GRAMMAR : 0); }
+int req_graph_key(const sonic_engine* e) { return (e->opt_request_bias ? GK_BIAS : 0) + (e->opt_sampling ? GK_SAMPLE : 0) + (e->opt_grammar ? GK_GRAMMAR : 0) + (e->opt_truncation ? GK_TRUNC : 0); }
 int req_splice_check(sonic_engine* d, sonic_engine* p) {
     const char* opt = nullptr;
     if (d->opt_request_bias != p->opt_request_bias || (d->opt_request_bias && !(p->bias.dev && d->bias.dev && p->hist && d->hist))) opt = "request_bias";
     else if (d->opt_sampling != p->opt_sampling || (d->opt_sampling && !(p->samp.dev && d->samp.dev))) opt = "sampling";
+    else if (d->opt_truncation != p->opt_truncation || (d->opt_truncation && !(p->trunc.dev && d->trunc.dev))) opt = "truncation";
     else if (d->opt_grammar != p->opt_grammar || (d->opt_grammar && !(p->gram.dev && d->gram.dev))) opt = "grammar";
     else if (d->opt_draft_verify != p->opt_draft_verify) opt = "draft_verify";
     return opt ? fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in option %s: set it on the owner before its slots are created", opt) : SONIC_OK;
@@ -656,6 +738,7 @@ int req_splice_check(sonic_engine* d, sonic_engine* p) {
 void req_splice_args(sonic_engine* d, sonic_engine* p, SpliceArgs& a, const int32_t* src_rows, const int32_t* dst_rows, int n) {
     if (d->opt_request_bias) { a.bias_s = p->bias.dev; a.bias_d = d->bias.dev; }
     if (d->opt_sampling) { a.samp_s = p->samp.dev; a.samp_d = d->samp.dev; }
+    if (d->opt_truncation) { a.trunc_s = p->trunc.dev; a.trunc_d = d->trunc.dev; }
     if (d->opt_grammar) {
         a.gram_s = p->gram.dev; a.gram_d = d->gram.dev;
         for (int i = 0; i < n; ++i) {                      // the row is handed over and its reference with it: the source row is free (the kernel resets its words)
@@ -691,6 +774,8 @@ int gen_inherit(sonic_engine* e, const sonic_engine* root) {
     e->opt_bias_fill = root->opt_bias_fill;
     if (root->opt_sampling) TRY(samp_enable(e, 1));
     e->opt_samp_fill_milli = root->opt_samp_fill_milli;
+    if (root->opt_truncation) TRY(trunc_enable(e, 1));
+    e->opt_trunc_fill = root->opt_trunc_fill;
     if (root->opt_grammar) TRY(gram_enable(e, 1));
     e->opt_forced_parallel = root->opt_forced_parallel; e->opt_forced_fanout = root->opt_forced_fanout; e->opt_score_chunk_rows = root->opt_score_chunk_rows;      // (the buffers come with the slot's first parallel run)
     e->opt_forced_align = root->opt_forced_align; e->align_heads = root->align_heads;      // (likewise)
@@ -704,7 +789,7 @@ void gen_release(sonic_engine* e) {
     for (int r = 0; r < 64; ++r) gram_row_release(e, r);
     for (sonic_grammar* g : e->grammars) { (void)hipFree(g->dev); delete g; }
     e->grammars.clear();
-    stage_free(e->bias); stage_free(e->samp); stage_free(e->gram);
+    stage_free(e->bias); stage_free(e->samp); stage_free(e->gram); stage_free(e->trunc);
     for (int i = 0; i < 2; ++i) if (e->draft_plan_h[i]) (void)hipHostFree(e->draft_plan_h[i]);
     for (int i = 0; i < 2; ++i) if (e->fork_ev[i]) (void)hipEventDestroy(e->fork_ev[i]);
 }

@@ -481,6 +481,14 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
         if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
         HIPC(e, h2d(e, gsamp, w.data(), w.size() * 4));
     }
+    unsigned* gtrunc = nullptr;                                                   // an armed hook truncation (sonic_load_tensor "truncation.hook"): this sampling launch takes it
+    if (sp && !e->hook_trunc.empty()) {
+        std::vector<unsigned> w; w.swap(e->hook_trunc);
+        if (greedy_guard_lds(V, gt && gt->bias) + greedy_trunc_lds() > 60000) return fail(e, SONIC_ERR_INVALID, "truncation.hook: a vocabulary of %d ids does not fit the select's histogram beside the bitmaps", V);
+        gtrunc = tb.get<unsigned>(2 * (size_t)TRUNC_STAGE_WORDS);                 // the rows' words, then their records
+        if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+        HIPC(e, h2d(e, gtrunc, w.data(), w.size() * 4));
+    }
     int* gdev = nullptr; unsigned long long* gref = nullptr;
     if (gr) {
         gdev = tb.get<int>(gblob.size()); gref = tb.get<unsigned long long>(GRAM_STAGE_WORDS);
@@ -504,11 +512,13 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
     g.n_active = st + 512; g.n_eos = 0; g.pad_id = 0; g.logits_dump = dump; g.dump_stride_step = (long)B * V; g.step_counter = dump ? st + 320 : nullptr;
     g.out_lp = lp; g.force_ids = fd; g.force_ld = old; g.topk = lp ? e->opt_top_logprobs : 0;
     if (sp) { g.samp = gsamp; g.noise_out = gnoise; g.dt = e->f32 ? DT_F32 : e->dt; }
+    if (gtrunc) { g.trunc = gtrunc; g.trunc_rec = gtrunc + TRUNC_STAGE_WORDS; }
     if (gt) { g.hist = ghist; g.hist_ld = gld; g.rep_penalty = gt->penalty; g.ngram = gt->ngram; g.suppress = gsup; g.n_suppress = gt->n_suppress; g.bias_tab = gbias; }
     if (gr) { g.gram_ref = gref; g.gram_state = (int*)(gref + 64); g.n_eos = gr->n_eos; for (int i = 0; i < gr->n_eos; ++i) g.eos[i] = gr->eos[i]; g.dt = e->f32 ? DT_F32 : e->dt; }
     launch_greedy(g, e->st);
     HIPC(e, stream_sync(e));
     HIPC(e, hipGetLastError());
+    if (gtrunc) HIPC(e, d2h(e, e->hook_trunc_rec, gtrunc + TRUNC_STAGE_WORDS, (size_t)B * 3 * 4));
     if (gr) {
         std::vector<unsigned long long> w((size_t)GRAM_STAGE_WORDS);
         HIPC(e, d2h(e, w.data(), gref, w.size() * 8));

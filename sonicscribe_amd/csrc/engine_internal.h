@@ -205,6 +205,14 @@ struct sonic_engine {
     int opt_sampling = 0;
     int opt_samp_fill_milli = 0;   // measurement aid (option sampling_fill_milli, tools/ab_sampling.sh): a prefill that was given no values decodes request r at this temperature (in thousandths) with seed r
     ReqStage<unsigned> samp;
+    // option truncation (sonic_load_tensor "request_truncation"; greedy_kernel<T, true, ., ., true, ., ., true>): every row's top_k, top_p bits and lnm bits,
+    // trunc.dev[TRUNC_STAGE_WORDS] (kernels.h); allocated by the option, which needs option sampling.  opt_trunc_fill: measurement aid (option truncation_fill,
+    // tools/ab_truncation.sh): a prefill that was given no values decodes every request with top_k = 50, top_p = 0.9
+    int opt_truncation = 0, opt_trunc_fill = 0;
+    ReqStage<unsigned> trunc;
+    // the kernel hooks' truncation (sonic_load_tensor "truncation.hook", float32 [B][3]): armed until the next sonic_test_greedy_sample launch takes it; hook_trunc_rec:
+    // that launch's records (sonic_debug_read "hook_truncation")
+    std::vector<unsigned> hook_trunc; unsigned hook_trunc_rec[64 * 3]{};
     // option grammar (options request_grammar_begin / request_grammar; greedy_kernel<T, true, true, ., ., ., true>): gram.dev holds GRAM_STAGE_WORDS 64-bit words - the 64
     // rows' grammar references (device addresses; 0: a free row), then their 64 state words (int: -1 free, n >= 0 a node, -2 left); allocated, with hist, by the
     // option.  gram_staged / gram_row: the references (sonic_grammar::refs) the staged requests and the rows of this handle hold - taken by the setter, moved to the
@@ -400,7 +408,7 @@ int chunk_graph(sonic_engine* e, int R, int n, hipGraphExec_t* out, bool svc = f
 int run_decode_steps(sonic_engine* e, int n_steps, int* done_out);
 // the bits of a captured chunk's cache key above the row count (chunk_graph; GK_BIAS, GK_SAMPLE and GK_GRAMMAR are req_graph_key's): the greedy kernel's family and
 // its pointers are part of the capture.  GK_TOPK counts: option top_logprobs = K <= 8 takes bits 17 .. 20
-enum { GK_SVC = 1 << 12, GK_LP = 1 << 13, GK_GUARD = 1 << 14, GK_BIAS = 1 << 15, GK_SAMPLE = 1 << 16, GK_TOPK = 1 << 17, GK_GRAMMAR = 1 << 21 };
+enum { GK_SVC = 1 << 12, GK_LP = 1 << 13, GK_GUARD = 1 << 14, GK_BIAS = 1 << 15, GK_SAMPLE = 1 << 16, GK_TOPK = 1 << 17, GK_GRAMMAR = 1 << 21, GK_TRUNC = 1 << 22 };
 
 // ------------------------------------------------------------------------------------------ scoring given tokens from a prefill (engine_score.cpp)
 int run_forced_parallel(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new, bool want_logits);
@@ -468,6 +476,13 @@ static inline bool hist_on(const sonic_engine* e) { return e->gen_on || e->opt_r
 // the three per-request stages' switches (engine_options.cpp) and what the hooks and sonic_load_tensor share with them
 int bias_enable(sonic_engine* e, int on);           // option request_bias behind the lock and the busy check: hist, the tables and their staging buffer on first use
 int samp_enable(sonic_engine* e, int on);           // option sampling behind the lock and the busy check: the rows' words and their staging buffer on first use
+int trunc_enable(sonic_engine* e, int on);          // option truncation behind the lock and the busy check: refused by name unless sampling is on; the rows' words and their staging buffer on first use
+// one row's (top_k, top_p, min_p) as "request_truncation" states it -> the three words the kernel reads; SONIC_ERR_INVALID naming `who`, the row and the parameter for a
+// NaN or a value out of range (message on e, or the calling thread's for e = NULL); nothing is clamped
+int trunc_pack(sonic_engine* e, const char* who, const float* v, int row, unsigned* w);
+int trunc_stage_rows(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim);   // sonic_load_tensor "request_truncation": the values of the next prefill's rows
+int trunc_dispatch_arm(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim); // sonic_load_tensor "truncation.dispatch" (no engine lock): the calling thread's next sonic_dispatch_submit_sampled carries the row
+int trunc_hook_arm(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim);     // sonic_load_tensor "truncation.hook": the next sonic_test_greedy_sample launch's rows
 int gram_enable(sonic_engine* e, int on);           // option grammar behind the lock and the busy check: hist, the rows' references and state words and their staging buffer on first use
 // one request's table as sonic_set_request_bias takes it -> its BIAS_ROW_WORDS device words, grouped and ordered as the kernel reads them; *count = its entries.
 // SONIC_ERR_INVALID (message on e, naming `who`) for more than BIAS_MAX_ENTRIES entries, a length outside 1 .. BIAS_MAX_LEN, an id outside [0, V), a NaN or +inf bias
@@ -487,6 +502,7 @@ struct SpliceArgs {
     const int* hist_s; int* hist_d;                      // generation guards on the destination: the row's history (prompt + first token) travels with it, [.][ctx]
     const int* bias_s; int* bias_d;                      // option request_bias on both: the row's table travels with it (count first, then only the used entries)
     const unsigned* samp_s; unsigned* samp_d;            // option sampling on both: the row's temperature and seed travel with it (its step index is n_new)
+    const unsigned* trunc_s; unsigned* trunc_d;          // option truncation on both: the row's three words travel with it
     unsigned long long* gram_s; unsigned long long* gram_d;            // option grammar on both: the row's grammar reference and its state word (behind the 64 references) MOVE with it: the source row is free afterwards
     const float* lp_s; float* lp_d; int lp_w;            // option token_logprobs on the destination: the first token's log-probability record (lp_w floats: 1, or 1 + 2K with
                                                          // option top_logprobs) travels with its id

@@ -33,6 +33,10 @@ static int opt_sampling_fill_milli(sonic_engine* e, const char* key, int value) 
 }
 // grammar-constrained decoding (options request_grammar_begin / request_grammar): on the owner before its slots are created (they copy it), after token_logprobs (refused by
 // name otherwise); allocates the rows' history, if nothing else has, and their references and state words.  Refused while the handle has work in hand
+// top_k / top_p / min_p (sonic_load_tensor "request_truncation"): on the owner before its slots are created (they copy it), after sampling (refused by name
+// otherwise); allocates the rows' words.  Refused while the handle has work in hand.  truncation_fill: measurement aid (trunc_upload, engine_generation.cpp)
+static int opt_truncation(sonic_engine* e, const char* key, int value) { TRY(gen_busy(e, key)); return trunc_enable(e, value ? 1 : 0); }
+static int opt_truncation_fill(sonic_engine* e, const char* key, int value) { TRY(gen_busy(e, key)); e->opt_trunc_fill = value ? 1 : 0; return SONIC_OK; }
 static int opt_grammar(sonic_engine* e, const char* key, int value) { TRY(gen_busy(e, key)); return gram_enable(e, value ? 1 : 0); }
 // ... and the values that travel through the options, since the feature adds no entry point: the grammars of the requests of the next prefill (begin = R requests, all
 // free; then request << 16 | grammar id per constrained request), the kernel hooks' row states and EOS ids
@@ -160,6 +164,8 @@ static const OptRow OPTIONS[] = {
     {"gen_suppress_token", APPLY(opt_gen)},
     {"sampling", APPLY(opt_sampling)},
     {"sampling_fill_milli", APPLY(opt_sampling_fill_milli)},
+    {"truncation", APPLY(opt_truncation)},
+    {"truncation_fill", APPLY(opt_truncation_fill)},
     {"grammar", APPLY(opt_grammar)},
     {"request_grammar_begin", APPLY(opt_request_grammar_begin)},
     {"request_grammar", APPLY(opt_request_grammar)},
@@ -231,6 +237,11 @@ extern "C" int sonic_debug_read(sonic_engine* e, const char* name, int index, fl
     if (!strcmp(name, "hook_grammar_state")) {      // the rows' states behind the last hook launch that took a grammar (host words: exact in fp32)
         if (n < 0 || n > 64) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
         for (int64_t i = 0; i < n; ++i) out[i] = (float)e->hook_state_out[i];
+        return SONIC_OK;
+    }
+    if (!strcmp(name, "hook_truncation")) {         // the rows' records behind the last hook launch that took a truncation: [y of the last kept id | that id | n] (host words; ids and counts exact in fp32)
+        if (n < 0 || n > 64 * 3) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
+        for (int64_t i = 0; i < n; ++i) { if (i % 3 == 0) memcpy(&out[i], &e->hook_trunc_rec[i], 4); else out[i] = (float)(int)e->hook_trunc_rec[i]; }
         return SONIC_OK;
     }
     if (!strcmp(name, "draft_accepted")) {          // a_r of the handle's last prefill (option draft_verify; exact in fp32); zeros behind a prefill without drafts

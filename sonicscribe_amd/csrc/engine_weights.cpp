@@ -82,6 +82,9 @@ extern "C" int sonic_load_tensor(sonic_engine* e, const char* name, const void* 
     if (!strcmp(name, "draft.dispatch")) return draft_dispatch_arm(e, data, dtype, shape, ndim);      // ... and the one of the calling thread's next dispatcher submit (no engine lock, as grammar.dispatch)
     if (!strcmp(name, "request_draft")) return draft_stage_words(e, data, dtype, shape, ndim);      // the drafts of the next prefill's requests (option draft_verify)
     if (!strcmp(name, "request_forks")) return fork_stage_counts(e, data, dtype, shape, ndim);      // the fork counts of the next prefill's requests
+    if (!strcmp(name, "request_truncation")) return trunc_stage_rows(e, data, dtype, shape, ndim);      // top_k / top_p / min_p of the next prefill's rows (option truncation)
+    if (!strcmp(name, "truncation.dispatch")) return trunc_dispatch_arm(e, data, dtype, shape, ndim);      // ... of the calling thread's next sonic_dispatch_submit_sampled (no engine lock, as grammar.dispatch)
+    if (!strcmp(name, "truncation.hook")) return trunc_hook_arm(e, data, dtype, shape, ndim);      // ... and of the next sonic_test_greedy_sample launch
     ENTER(e);
     if (e->finalized) return fail(e, SONIC_ERR_INVALID, "weights already finalized");
     std::vector<int64_t> shp(shape, shape + ndim);

@@ -8,6 +8,7 @@
 
 #include "int8_util.h"
 #include "rowlp.h"
+#include "truncsel.h"
 
 // ---------------------------------------------------------------- argmax + greedy controller (generation/utils.py:2894-2936)
 // LP (option token_logprobs): the block also returns log_softmax(l)[tok] of the token it emits.  Every thread keeps the sum lp_s of
@@ -55,6 +56,13 @@
 // scores.  Thread 0 looks the emitted id - argmax, sample or forced id - up among the node's edges by binary search: found, the state is that edge's `next`; not
 // found (a forced id outside the grammar, token 0 of a row whose allowed ids were all banned, any id at -2), it is -2.  A finished row changes nothing; no LDS is
 // added.  GRAMMAR = false is the kernel as it was.
+// TRUNC (option truncation; SAMPLE only): top_k / top_p / min_p on y = fdiv_rn(s, t), HF's warpers behind TemperatureLogitsWarper.  Row b reads
+// GreedyArgs.trunc[3b ..]: top_k, the bits of top_p (0: off), the bits of lnm = float32(log(min_p)) (0: off; min_p = 1 is sent as -0.0).  A row with t = 0 or all
+// three words 0 takes a block-uniform branch around everything below and runs the SAMPLE code.  Else the block finds the row's maximum of y, then the cut (kc, ic) -
+// a key of y and an id - by the radix selects of truncsel.h, each pass recomputing y from the slabs (L2-resident) under the maps the prologue left in LDS; the loop's
+// compare then admits an id only if trunc_keeps(key(y), id, kc, ic): the first maximum of y + g over the kept prefix.  The LP sum, out_lp, the alternatives and the
+// dump see the untruncated scores.  With trunc_rec (test hook) one more pass counts the kept ids and finds the last of them in (y descending, id ascending):
+// trunc_rec[3b ..] = the bits of its y, its id, n (an uncut row: 0, ~0, V).  TRUNC = false is the kernel as it was.
 // The history's maps, the first-maximum butterfly, the sum's rescale, wave fold and block close, and the lists with their merges and record write live in
 // rowlp.h: rows.hip (rows_kernel) shares them
 extern __shared__ unsigned g_bits[];
@@ -80,8 +88,9 @@ __device__ __forceinline__ float gumbel_of(unsigned word) {
     return -logf(-logf(u));
 }
 #define LPB (SAMPLE ? rmax : best)      // what the LP sum is taken against: the running maximum of s
-template <typename T, bool LP, bool GUARD = false, bool BIAS = false, bool SAMPLE = false, bool TOPK = false, bool GRAMMAR = false>
+template <typename T, bool LP, bool GUARD = false, bool BIAS = false, bool SAMPLE = false, bool TOPK = false, bool GRAMMAR = false, bool TRUNC = false>
 __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
+    static_assert(SAMPLE || !TRUNC, "truncation lives in the sampling instantiations (it cuts what they draw from)");
     static_assert(!GRAMMAR || (LP && GUARD), "the grammar lives in the log-probability guard instantiations (it reuses their banned map)");
     static_assert(LP || !TOPK, "the alternatives live in the log-probability instantiations (they share their sum)");
     static_assert(GUARD || !BIAS, "the request bias lives in the guard instantiations (it needs their history)");
@@ -96,6 +105,9 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
     __shared__ int s_tki[TOPK ? 128 : 1];        // ... and their ids
     __shared__ float s_tk_hand[TOPK ? 2 : 1];    // thread 0 -> wave 1: the block's maximum M and lp_sum, the values out_lp was formed from ...
     __shared__ int s_tk_col[1];                  // ... and the record's column n_new (-1: a finished row)
+    __shared__ tr_u64 s_trh[TRUNC ? TRUNC_BINS : 1];      // TRUNC: the select's histogram ...
+    __shared__ tr_u64 s_trw[TRUNC ? 16 : 1];              // ... the waves' totals of its scan (and the waves' maxima of y) ...
+    __shared__ tr_u64 s_trr[TRUNC ? 4 : 1];               // ... and what a scan found
     [[maybe_unused]] float tv[8]; [[maybe_unused]] int ti[8]; [[maybe_unused]] float mv = -INFINITY; [[maybe_unused]] int mi = TK_NONE;
     if constexpr (TOPK) tk_init(tv, ti);
     float lp_m = -INFINITY, lp_s = 0.f;      // LP: the thread's sum is lp_s * exp(lp_m); a thread that saw nothing holds (-inf, 0)
@@ -167,6 +179,68 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
         hist_maps(g_seen, g_ban, h, len, a.ngram, a.suppress, a.n_suppress, a.V, tid);
         __syncthreads();
     }
+    [[maybe_unused]] unsigned kc = 0u; [[maybe_unused]] int ic = TRUNC_ID_ALL; [[maybe_unused]] bool cut = false;      // TRUNC: the row's cut; cut = false: every id is kept
+    if constexpr (TRUNC) {
+        const unsigned* tw = a.trunc + 3 * b;
+        if (noisy && (tw[0] | tw[1] | tw[2]) != 0u) {      // block-uniform: the barriers below are reached by every thread or by none
+            // the four y of group i: the loop's own arithmetic (slab sum in its order, rT, bias, guard_score, the correctly rounded quotient), without the noise
+            auto y4 = [&](int i, float (&y)[4]) {
+                f32x4 t = *(const f32x4*)(lg + i);
+                for (int ks = 1; ks < a.ksplit; ++ks) t += *(const f32x4*)(lg + ks * ks_stride + i);
+                [[maybe_unused]] unsigned sb = 0u, bb = 0u, qb = 0u;
+                if constexpr (GUARD) { sb = g_seen[i >> 5] >> (i & 31); bb = g_ban[i >> 5] >> (i & 31); }
+                if constexpr (BIAS) qb = (g_bia[i >> 5] >> (i & 31)) & 15u;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float r = rT<T>(t[j]);
+                    if constexpr (BIAS) if ((qb >> j) & 1u) r += bias_of(q_id, q_sum, q_n, i + j);
+                    if constexpr (GUARD) r = guard_score(r, sb >> j, bb >> j, a.rep_penalty);
+                    y[j] = __fdiv_rn(r, temp);
+                }
+            };
+            float ym = -INFINITY;
+            for (int i = tid * 4; i < a.V; i += 4096) {
+                float y[4];
+                y4(i, y);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) ym = fmaxf(ym, y[j]);
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) ym = fmaxf(ym, __shfl_xor(ym, o, 64));
+            float* const wmax = (float*)s_trw;
+            if (lane == 0) wmax[wid] = ym;
+            __syncthreads();
+#pragma unroll
+            for (int w = 0; w < 16; ++w) ym = fmaxf(ym, wmax[w]);
+            __syncthreads();                                   // (s_trw is the scans' from here on)
+            if (ym > -INFINITY) {                              // (a row of -inf only keeps everything: token 0, as without the cut)
+                trunc_cut(y4, a.V, tid, tw, ym, s_trh, s_trw, s_trr, kc, ic);
+                cut = true;
+                if (a.trunc_rec) {                             // the record: the kept ids counted, and the last of them - the lowest key, there the highest id
+                    if (tid == 0) { s_trr[0] = 0ull; s_trr[1] = ~0ull; }
+                    __syncthreads();
+                    tr_u64 cnt = 0ull, low = ~0ull;
+                    for (int i = tid * 4; i < a.V; i += 4096) {
+                        float y[4];
+                        y4(i, y);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const unsigned key = trunc_key(y[j]);
+                            if (trunc_keeps(key, i + j, kc, ic)) { ++cnt; const tr_u64 v = ((tr_u64)key << 32) | (tr_u64)(0xffffffffu - (unsigned)(i + j)); low = v < low ? v : low; }
+                        }
+                    }
+                    if (cnt) { atomicAdd(&s_trr[0], cnt); atomicMin(&s_trr[1], low); }
+                    __syncthreads();
+                    if (tid == 0) {
+                        a.trunc_rec[3 * b] = __float_as_uint(trunc_unkey((unsigned)(s_trr[1] >> 32)));
+                        a.trunc_rec[3 * b + 1] = 0xffffffffu - (unsigned)(s_trr[1] & 0xffffffffull);
+                        a.trunc_rec[3 * b + 2] = (unsigned)s_trr[0];
+                    }
+                }
+            }
+        }
+        if (!cut && a.trunc_rec && tid == 0) { a.trunc_rec[3 * b] = 0u; a.trunc_rec[3 * b + 1] = ~0u; a.trunc_rec[3 * b + 2] = (unsigned)a.V; }
+    }
     // four strides per trip with all their slab loads issued first (the rolled form paid one L2 round trip per stride)
     constexpr int U = 4;
     for (int i0 = tid * 4; i0 < a.V; i0 += 1024 * 4 * U) {
@@ -201,7 +275,12 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
                 if (dump) dump[i + j] = r;
                 if constexpr (BIAS) if ((qb >> j) & 1u) r += bias_of(q_id, q_sum, q_n, i + j);      // HF's order: the bias first, the penalty sees the biased score
                 if constexpr (GUARD) r = guard_score(r, sb >> j, bb >> j, a.rep_penalty);
-                if constexpr (SAMPLE) {
+                if constexpr (TRUNC) {
+                    const float q = noisy ? __fdiv_rn(r, temp) : r;
+                    const float y = noisy ? q + gz[j] : r;
+                    if (y > best && (!cut || trunc_keeps(trunc_key(q), i + j, kc, ic))) { best = y; bi = i + j; }      // the first maximum over the kept ids
+                    rmax = fmaxf(rmax, r);
+                } else if constexpr (SAMPLE) {
                     const float y = noisy ? __fdiv_rn(r, temp) + gz[j] : r;      // (-inf stays -inf: g is finite)
                     if (y > best) { best = y; bi = i + j; }
                     rmax = fmaxf(rmax, r);                                       // (t == 0: rmax == best, bit for bit)
@@ -349,13 +428,18 @@ __global__ void hist_prompt_kernel(const int* src, const int* tok_seq, const int
 void launch_hist_prompt(const int* src, const int* tok_seq, const int* tok_pos, int n_tok, int audio_id, int* hist, int hist_ld, hipStream_t s) {
     if (n_tok > 0) hipLaunchKernelGGL(hist_prompt_kernel, dim3((n_tok + 255) / 256), dim3(256), 0, s, src, tok_seq, tok_pos, n_tok, audio_id, hist, hist_ld);
 }
+// static LDS of the largest TRUNC instantiation (the TOPK twins; `; LDSByteSize` of the assembly): the histogram's 16 384 bytes, the scans' words, the lists' 1 300 and
+// the reductions' - what the options' and the hook's 60 000-byte gate adds to the dynamic maps
+size_t greedy_trunc_lds() { return 17848; }
+static_assert(TRUNC_LDS_BYTES + 1464 == 17848, "greedy_trunc_lds: the histogram is part of the figure");
 size_t greedy_guard_lds(int V, bool bias) { return (size_t)(bias ? 3 : 2) * ((V + 31) / 32) * 4 + (bias ? (size_t)3 * BIAS_MAX_ENTRIES * 4 : 0); }
 // One family of the table below: its grid, block and LDS request, for fp32 rows (SONIC_MODE_F32: fp32 logits, table and rows) and for the 16-bit kinds
-template <bool LP, bool GUARD, bool BIAS, bool SAMPLE, bool TOPK = false, bool GRAMMAR = false>
+template <bool LP, bool GUARD, bool BIAS, bool SAMPLE, bool TOPK = false, bool GRAMMAR = false, bool TRUNC = false>
 static void greedy_launch(const GreedyArgs& a, hipStream_t s) {
+    if constexpr (SAMPLE && !TRUNC) if (a.trunc) return greedy_launch<LP, GUARD, BIAS, SAMPLE, TOPK, GRAMMAR, true>(a, s);      // trunc (counts only together with samp) = option truncation: the family's TRUNC twin
     const size_t lds = GUARD ? greedy_guard_lds(a.V, BIAS) : 0;      // GUARD: two vocabulary bitmaps of dynamic LDS; BIAS: a third and the matched list; GRAMMAR: nothing more
-    if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, LP, GUARD, BIAS, SAMPLE, TOPK, GRAMMAR>), dim3(a.B), dim3(1024), lds, s, a); return; }
-    DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, LP, GUARD, BIAS, SAMPLE, TOPK, GRAMMAR>), dim3(a.B), dim3(1024), lds, s, a));
+    if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, LP, GUARD, BIAS, SAMPLE, TOPK, GRAMMAR, TRUNC>), dim3(a.B), dim3(1024), lds, s, a); return; }
+    DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, LP, GUARD, BIAS, SAMPLE, TOPK, GRAMMAR, TRUNC>), dim3(a.B), dim3(1024), lds, s, a));
 }
 // The twenty-three families, chosen from the arguments: out_lp = option token_logprobs, hist = generation guards, bias_tab (counts only together with hist) = request
 // bias, samp (counts only together with out_lp) = option sampling, topk in 1 .. 8 (counts only together with out_lp) = option top_logprobs, gram_state with gram_ref

@@ -125,6 +125,10 @@ struct GreedyArgs {
     // (nodes N, edges E), then node_off[N + 1], edge_tok[E] (ascending inside a node), edge_next[E].  Needs out_lp and hist.  (Ahead of the sampling fields, which
     // stay the struct's last.)
     int* gram_state; const unsigned long long* gram_ref;
+    // truncation (greedy_kernel<T, true, ., ., true, ., ., true>, option truncation).  trunc = NULL: off; else three words per row, 64 rows: top_k
+    // (0: off), the bits of top_p (0: off), the bits of lnm = float32(log(min_p)) (0: off; min_p = 1 is -0.0).  trunc_rec: optional, three words per row (test hook;
+    // production passes NULL): the bits of the y of the last kept id in (y descending, id ascending), that id, the kept count n.  Needs samp.  (Ahead of the sampling fields, as the grammar's)
+    const unsigned* trunc; unsigned* trunc_rec;
     // temperature sampling (greedy_kernel<T, true, ., ., true>, option sampling).  noise_out: optional [B][V], the Gumbel value the kernel added at
     // every id of a row with t > 0 (test hook; production passes NULL, as for the dump).  samp = NULL: off; else three words per row, 64 rows: the bits of the row's
     // fp32 temperature (0: greedy), its seed's low word, its high word.  The row's step index is n_new[row].  Needs out_lp.  Last: every offset above is what it was
@@ -136,6 +140,7 @@ struct GreedyArgs {
     int topk;
 };
 #define SAMP_WORDS (64 * 3)
+#define TRUNC_STAGE_WORDS (64 * 3)
 #define GRAM_HEAD 2
 #define GRAM_MAX_NODES 65536
 #define GRAM_MAX_EDGES 1048576
@@ -146,6 +151,7 @@ struct GreedyArgs {
 #define BIAS_ROW_WORDS (BIAS_MAX_ENTRIES * BIAS_ENTRY_WORDS)
 #define BIAS_TAB_WORDS (64 + 64 * BIAS_ROW_WORDS)
 void launch_greedy(const GreedyArgs& a, hipStream_t s);
+size_t greedy_trunc_lds();                              // LDS the TRUNC instantiations add to it (the select's histogram)
 size_t greedy_guard_lds(int V, bool bias = false);     // dynamic LDS of the GUARD instantiations: two bitmaps over the vocabulary; with the request bias a third one and the matched list
 void launch_hist_prompt(const int* src, const int* tok_seq, const int* tok_pos, int n_tok, int audio_id, int* hist, int hist_ld, hipStream_t s);
 

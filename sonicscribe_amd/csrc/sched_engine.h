@@ -17,6 +17,8 @@ int engine_top_logprobs(sonic_engine* e);                      // K: its log-pro
 int engine_forced_parallel_on(sonic_engine* e);                // a scoring handle: both schedulers refuse it
 int engine_request_bias_on(sonic_engine* e);
 int engine_sampling_on(sonic_engine* e);
+int engine_truncation_on(sonic_engine* e);                     // option truncation
+int engine_take_dispatch_truncation(float* row);               // "truncation.dispatch": 1 and the armed (top_k, top_p, min_p) in row[0 .. 3), or 0 (none)
 int engine_grammar_on(sonic_engine* e);
 int engine_draft_verify_on(sonic_engine* e);                   // (the bulk pipeline takes no drafts: refused there)
 int engine_tok_cap(sonic_engine* e);                           // the tokens one prefill of the handle holds

@@ -49,13 +49,24 @@ def step_class(max_new: int) -> int:
     return len(STEP_CLASSES)
 
 
+def _cut_of(sampling) -> tuple:
+    """() for a (temperature, seed) pair, the validated (top_k, top_p, min_p) of a 5-tuple (ValueError naming the parameter; nothing is clamped)"""
+    if len(sampling) == 2:
+        return ()
+    if len(sampling) != 5:
+        raise ValueError(f"sampling: {tuple(sampling)!r} is neither (temperature, seed) nor (temperature, seed, top_k, top_p, min_p)")
+    from . import sampling as _sampling
+    return _sampling.check_truncation(*sampling[2:])
+
+
 class Request:
     __slots__ = ("windows", "prompt", "max_new", "future", "t_submit", "cls", "want_logprobs", "bias", "sampling", "grammar", "draft")
 
     def __init__(self, windows: Sequence[Any], prompt: Sequence[int], max_new: int, want_logprobs: bool = False, bias=None, sampling=None, grammar=None, draft=None):
         self.draft = [int(t) for t in draft] if draft is not None and len(draft) else None      # a draft of its transcript (engine option draft_verify): the prefill verifies it; None: none
         self.grammar = grammar                        # its grammar (grammar.CompiledGrammar: a device handle per replica; engine option grammar); None: a free request
-        self.sampling = None if sampling is None else (float(sampling[0]), int(sampling[1]))      # its own (temperature, seed) (engine option sampling); None: greedy
+        # its own (temperature, seed), or (temperature, seed, top_k, top_p, min_p) (engine options sampling / truncation; DESIGN.md 6.13); None: greedy
+        self.sampling = None if sampling is None else (float(sampling[0]), int(sampling[1])) + _cut_of(sampling)
         self.windows, self.prompt, self.max_new = list(windows), prompt, int(max_new)
         self.bias = bias if bias else None            # its own sequence-bias table (reqbias.RequestBias; engine option request_bias): it travels with the request
         self.want_logprobs = bool(want_logprobs)      # the future resolves to (ids, float32 log-probabilities) instead of ids (engine option token_logprobs)
@@ -554,6 +565,10 @@ class _NativeContinuousReplica:
         if dev_gram is not None and dev_gram.h is None:
             raise ValueError("grammar: the grammar has been closed")
         draft_words = pack_dispatch_draft(req.draft) if req.draft else None      # sonic_load_tensor "draft.dispatch": n | ids
+        cut_row = None
+        if req.sampling and len(req.sampling) == 5:                                # sonic_load_tensor "truncation.dispatch": top_k | top_p | min_p
+            from . import sampling as _sampling
+            cut_row = _sampling.truncation_words(*req.sampling[2:])
         with self.lock:
             if self.stop:
                 raise RuntimeError("ASR engine is closed")
@@ -566,10 +581,13 @@ class _NativeContinuousReplica:
             if draft_words is not None:                  # ... and the draft, the same way ("draft.dispatch": a thread-local, no engine lock)
                 if self.lib.sonic_load_tensor(self.engine.h, b"draft.dispatch", _p(draft_words), 2, (C.c_int64 * 1)(len(draft_words)), 1) != 0:
                     raise ValueError("draft: " + (self.lib.sonic_last_error(None) or b"").decode())
+            if cut_row is not None:                      # ... and the cut of a sampled request ("truncation.dispatch": a thread-local, no engine lock)
+                if self.lib.sonic_load_tensor(self.engine.h, b"truncation.dispatch", _p(cut_row), 0, (C.c_int64 * 1)(3), 1) != 0:
+                    raise ValueError("sampling: " + (self.lib.sonic_last_error(None) or b"").decode())
             rc = submit(self.h, _p(pcm), _p(offs), ring_arr, _p(start), _p(n), len(req.windows), _p(prompt), len(prompt), int(req.max_new), *tail)
             if rc != 0 and (req.bias or req.sampling or req.grammar or req.draft):
                 msg = (self.lib.sonic_last_error(None) or b"").decode()
-                if "request_bias" in msg or "sonic_dispatch_submit_bias" in msg or "sampling" in msg or "sonic_dispatch_submit_sampled" in msg or "grammar" in msg or "draft" in msg:
+                if "truncation" in msg or "request_bias" in msg or "sonic_dispatch_submit_bias" in msg or "sampling" in msg or "sonic_dispatch_submit_sampled" in msg or "grammar" in msg or "draft" in msg:
                     raise ValueError(msg)
             if rc != 0:
                 raise RuntimeError("ASR engine failed" if rc not in (1,) else "ASR engine is closed or the request is malformed")

@@ -649,8 +649,10 @@ class Engine(HooksMixin):
             self.set_request_grammar(grammar)
         if draft_packed is not None:
             self._arm_draft(draft_packed)
-        if fork_counts is not None:      # row forks (_check_forks): last, right ahead of the consuming call
+        if fork_counts is not None:      # row forks (_check_forks): right ahead of the consuming call
             self._arm_forks(fork_counts)
+        if samp_packed is not None and len(samp_packed) == 3:      # top_k / top_p / min_p of rows stated as 5-tuples (option truncation): likewise
+            self._arm_truncation(samp_packed[2])
 
     def score_batch(self, segments: Sequence[Any], prompts: Sequence[Sequence[int]], targets, req_win: Optional[Sequence[int]] = None, fanout: int = 1,
                     want_logits: bool = False, align: bool = False):
@@ -875,13 +877,21 @@ class Engine(HooksMixin):
         return out[:R].astype(np.int32)
 
     def _arm_sampling(self, packed):
-        t, s = packed
+        t, s = packed[0], packed[1]
         self._check(self.lib.sonic_set_request_sampling(self.h, _p(t), _p(s), len(t)))
+
+    def _arm_truncation(self, rows):
+        self._check(self.lib.sonic_load_tensor(self.h, b"request_truncation", _p(rows), DTYPE_F32, (C.c_int64 * 2)(len(rows), 3), 2))
 
     def set_request_sampling(self, values):
         """The (temperature, seed) of the requests of the NEXT prefill / run on this handle (sonic_set_request_sampling), one pair or None (greedy) per request; that
-        call consumes them.  Needs option sampling (SonicError naming it otherwise).  ValueError for a temperature that is neither 0 nor in [1e-3, 100]."""
-        self._arm_sampling(pack_request_sampling(list(values)))
+        call consumes them.  Needs option sampling (SonicError naming it otherwise).  ValueError for a temperature that is neither 0 nor in [1e-3, 100].
+        A request may instead state (temperature, seed, top_k, top_p, min_p) (sampling.check_truncation names a value out of range): the batch's
+        rows of (top_k, top_p, min_p) then follow as sonic_load_tensor "request_truncation", which needs option truncation.  Pairs alone make today's calls."""
+        packed = pack_request_sampling(list(values))
+        self._arm_sampling(packed)
+        if len(packed) == 3:
+            self._arm_truncation(packed[2])
 
 
 def pack_request_bias(tables):
@@ -922,10 +932,18 @@ def pack_dispatch_draft(draft):
 
 
 def pack_request_sampling(values):
-    """one (temperature, seed) per request, or None for a greedy one -> sonic_set_request_sampling's arrays, validated (sampling.check_temperature / check_seed)"""
+    """one (temperature, seed) per request, or None for a greedy one -> sonic_set_request_sampling's arrays, validated (sampling.check_temperature / check_seed).
+    When a request states (temperature, seed, top_k, top_p, min_p) a third element follows: float32 [R][3], the rows of sonic_load_tensor "request_truncation"
+    (sampling.pack_truncation; a request without the three values has them off)"""
     from . import sampling
-    vals = [(0.0, 0) if v is None else v for v in values]
-    return sampling.pack_sampling([v[0] for v in vals], [v[1] for v in vals])
+    vals = [(0.0, 0) if v is None else tuple(v) for v in values]
+    for v in vals:
+        if len(v) not in (2, 5):
+            raise ValueError(f"request_sampling: {v!r} is neither (temperature, seed) nor (temperature, seed, top_k, top_p, min_p)")
+    t, s = sampling.pack_sampling([v[0] for v in vals], [v[1] for v in vals])
+    if all(len(v) == 2 for v in vals):
+        return t, s
+    return t, s, sampling.pack_truncation([v[2:] if len(v) == 5 else (0, 1.0, 0.0) for v in vals])
 
 
 def device_info(device_id: int = 0) -> dict:

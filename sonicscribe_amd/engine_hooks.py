@@ -172,6 +172,31 @@ class HooksMixin:
         return self._greedy("greedy_sample", slabs, B, True, True, force_ids, (hist, hist_len, repetition_penalty, no_repeat_ngram_size, suppress_tokens), tables,
                             (temperature, seed, step), want_noise)
 
+    def arm_truncation_hook(self, rows):
+        """sonic_load_tensor "truncation.hook": float32 [B][3] rows of (top_k, top_p, min_p) for the next test_greedy_sample launch on this handle (also the one inside
+        test_greedy_grammar); the library validates them (SonicError naming the parameter)"""
+        from .engine import DTYPE_F32, SonicError
+        rows = np.ascontiguousarray(rows, np.float32).reshape(-1, 3)
+        if self.lib.sonic_load_tensor(self.h, b"truncation.hook", _p(rows), DTYPE_F32, (C.c_int64 * 2)(len(rows), 3), 2) != 0:
+            raise SonicError((self.lib.sonic_last_error(None) or b"").decode())
+
+    def read_truncation_hook(self, B: int):
+        """sonic_debug_read "hook_truncation": the records of the last launch that took a truncation -> (the bits of the y of the last kept id [B] (uint32), that
+        id [B], the kept count n [B]); a row that took the branch around the select (t = 0, the three filters off, or scores of -inf only) reports (0, -1, V)"""
+        rec = np.zeros(64 * 3, np.float32)
+        self._check(self.lib.sonic_debug_read(self.h, b"hook_truncation", 0, _p(rec), 3 * B))
+        rec = rec[: 3 * B].reshape(B, 3)
+        return np.ascontiguousarray(rec[:, 0]).view(np.uint32), rec[:, 1].astype(np.int64), rec[:, 2].astype(np.int64)
+
+    def test_greedy_truncation(self, slabs, B: int, temperature, seed, step, truncation, **kw):
+        """The TRUNC instantiations of the greedy kernel: `truncation`, one (top_k, top_p, min_p) per row (sampling.pack_truncation validates them),
+        is armed on the handle and the test_greedy_sample launch that follows (its keywords: **kw) takes it -> test_greedy_sample's four results and the rows' records"""
+        from . import sampling
+        rows = sampling.pack_truncation(list(truncation))
+        assert rows.shape == (B, 3)
+        self.arm_truncation_hook(rows)
+        return self.test_greedy_sample(slabs, B, temperature, seed, step, **kw) + (self.read_truncation_hook(B),)
+
     def test_greedy_grammar(self, slabs, B: int, grammar, state_in, eos_ids=(), hist=None, hist_len=None, tables=None, samp=None, repetition_penalty: float = 1.0,
                             no_repeat_ngram_size: int = 0, suppress_tokens=(), force_ids=None, want_noise: bool = True):
         """The grammar instantiations of the greedy kernel in this handle's type (include/sonic_hip.h beside sonic_test_greedy_sample): the automaton is armed on the

@@ -114,7 +114,7 @@ class _FileJob:
     """One file on the device: its ring, its plan and its queued decodes."""
 
     def __init__(self, model, audio, vad, vad_enabled: bool, hotwords, max_segment_duration, max_new_tokens: int, filename: str,
-                 sampling_rate: int = SAMPLE_RATE, sequence_bias=None, bad_words_ids=None, hotword_boost=None, temperature=None, seed=None, word_timestamps: bool = False, grammar=None):
+                 sampling_rate: int = SAMPLE_RATE, sequence_bias=None, bad_words_ids=None, hotword_boost=None, temperature=None, seed=None, word_timestamps: bool = False, grammar=None, top_k=None, top_p=None, min_p=None):
         if not hasattr(model, "model"):
             raise RuntimeError("ASR model has been released")
         # word_timestamps (a model built with timestamps=True; DESIGN.md 6.9): every segment's tokens are aligned on the replica's scoring handle as its record is
@@ -124,7 +124,7 @@ class _FileJob:
             model._check_timestamps()
         # the file's temperature (a float) or fallback ladder (a sequence) and seed (a model built with sampling=True; ASRModel._request_sampling): every segment
         # of the file is decoded with them, each as its own request
-        self.samp = model._request_sampling(temperature, seed) if hasattr(model, "_request_sampling") else None
+        self.samp = model._request_sampling(temperature, seed, cut=(top_k, top_p, min_p)) if hasattr(model, "_request_sampling") else None
         # the file's sequence-bias table (a model built with request_bias=True; ASRModel._request_bias): every segment of the file carries it
         self.bias = model._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost) if hasattr(model, "_request_bias") else None
         # the file's grammar (a model built with grammar=True; ASRModel.compile_grammar): every segment of the file is decoded under it, from its start node
@@ -297,10 +297,10 @@ def _detect(vad, jobs: Sequence[_FileJob]) -> List[Any]:
 def transcribe_file(model, audio, vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                     max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filename: str = "",
                     sampling_rate: int = SAMPLE_RATE, sequence_bias=None, bad_words_ids=None, hotword_boost=None, temperature=None, seed=None,
-                    word_timestamps: bool = False, grammar=None) -> Iterator[Dict[str, Any]]:
+                    word_timestamps: bool = False, grammar=None, top_k=None, top_p=None, min_p=None) -> Iterator[Dict[str, Any]]:
     """Generator of the reference's file-mode records for one file (see ASRModel.transcribe_file)."""
     job = _FileJob(model, audio, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filename, sampling_rate, sequence_bias, bad_words_ids, hotword_boost,
-                   temperature, seed, word_timestamps, grammar)
+                   temperature, seed, word_timestamps, grammar, top_k=top_k, top_p=top_p, min_p=min_p)
     try:
         ts = vad.detect_voice_activity_ring(job.ring, job.first, job.total)[0] if job.wants_vad else None
         job.plan(ts)
@@ -314,7 +314,7 @@ def transcribe_file(model, audio, vad, vad_enabled: bool = True, hotwords: Optio
 def transcribe_files(model, audios: Sequence[Any], vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                      max_segment_duration: Optional[float] = None, max_new_tokens: int = 256,
                      filenames: Optional[Sequence[str]] = None, sampling_rate: int = SAMPLE_RATE, sequence_bias=None, bad_words_ids=None,
-                     hotword_boost=None, temperature=None, seed=None, word_timestamps: bool = False, grammar=None) -> List[FileRecords]:
+                     hotword_boost=None, temperature=None, seed=None, word_timestamps: bool = False, grammar=None, top_k=None, top_p=None, min_p=None) -> List[FileRecords]:
     """One record iterator per file; the VAD of all files runs in one device call and every file's segments are queued before the call
     returns.  Each iterator must be exhausted or closed (its ring lives until then)."""
     names = list(filenames) if filenames is not None else [""] * len(audios)
@@ -322,7 +322,7 @@ def transcribe_files(model, audios: Sequence[Any], vad, vad_enabled: bool = True
     try:
         for a, name in zip(audios, names):
             jobs.append(_FileJob(model, a, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, name, sampling_rate, sequence_bias, bad_words_ids, hotword_boost,
-                                 temperature, seed, word_timestamps, grammar))
+                                 temperature, seed, word_timestamps, grammar, top_k=top_k, top_p=top_p, min_p=min_p))
         for job, ts in zip(jobs, _detect(vad, jobs)):
             job.plan(ts)
         for job in jobs:

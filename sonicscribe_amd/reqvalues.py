@@ -18,7 +18,7 @@ VALUES = (
     ReqValue("bias", "request_bias", "request_bias", "set_request_bias",
              "a sequence bias needs the engine option request_bias on every handle (ASRModel(request_bias=True))", lambda table, engine: table),
     ReqValue("sampling", "sampling", "request_sampling", "set_request_sampling",
-             "a temperature needs the engine option sampling on every handle (ASRModel(sampling=True))", lambda pair, engine: pair),
+             "a temperature needs the engine option sampling on every handle (ASRModel(sampling=True))", lambda pair, engine: pair),      # ((t, seed), or (t, seed, top_k, top_p, min_p): passed through unchanged)
     # (a grammar.CompiledGrammar holds a device handle per weight owner: the one that serves `engine`; None: a free request)
     ReqValue("grammar", "grammar", "request_grammar", "set_request_grammar",
              "a grammar needs the engine option grammar on every handle (ASRModel(token_logprobs=True, grammar=True))", lambda g, engine: None if g is None else g.on(engine)),
@@ -72,14 +72,14 @@ def check_draft(req, engines) -> None:
 
 
 def submit_keywords(bias, samp, gram, draft) -> dict:
-    """One call's own values, as ASRModel._request_values resolves them (samp: None, or (temperatures, is it a ladder, seed)), as the keywords of Dispatcher.submit.
+    """One call's own values, as ASRModel._request_values resolves them (samp: None, or (temperatures, is it a ladder, seed[, (top_k, top_p, min_p)])), as the keywords of Dispatcher.submit.
     Each only when the request brings it - stub dispatchers need not know the others: `bias` a non-empty table, `sampling` for one temperature (a fallback ladder
     states it attempt by attempt: ASRModel._dispatch), `grammar`, `draft` a non-empty one."""
     kw = {}
     if bias:
         kw["bias"] = bias
     if samp is not None and not samp[1]:
-        kw["sampling"] = (samp[0][0], samp[2])
+        kw["sampling"] = (samp[0][0], samp[2]) + (tuple(samp[3]) if len(samp) > 3 and samp[0][0] > 0 else ())      # (top_k, top_p, min_p) behind the pair when the call cuts the tail (DESIGN.md 6.13)
     if gram is not None:
         kw["grammar"] = gram
     if draft:

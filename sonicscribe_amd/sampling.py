@@ -117,3 +117,111 @@ def pack_sampling(temperature: Sequence[float], seed: Sequence[int]) -> Tuple[np
     if t.shape != s.shape:
         raise ValueError("one temperature and one seed per request")
     return t, s
+
+
+# ---------------------------------------------------------------- truncation: top_k, top_p, min_p
+"""The contract.  A request with t > 0 may bring top_k (integer >= 0, 0 = off), top_p (in (0, 1], 1 = off) and min_p (in [0, 1], 0 = off); rows with t = 0 ignore them.
+y_i = fdiv_rn(s_i, t) in fp32, s the fully processed score.  The ids are ordered by (y descending, id ascending); every filter keeps a prefix of that order and the
+kept set is the shortest of the three prefixes - HF's chain TopK -> TopP -> MinP, each later filter stated on the renormalised survivors of the earlier ones:
+  top_k  every id with y_i >= the k-th largest y (HF's `scores < kth` keeps the ties; k >= the number of finite scores removes nothing)
+  top_p  over the top_k survivors K, masses w_i = exp(y_i - y_max): rank r is kept iff the mass of ranks 0 .. r - 1 is < top_p * mass(K) (HF's
+         `cumulative_probs <= 1 - top_p` on the ascending sort, rewritten; rank 0 always stays).  Equal values at the boundary go by the lower id (HF leaves them to
+         torch.sort)
+  min_p  every id with y_i >= fadd_rn(y_max, lnm), lnm = float32(log(min_p)) (HF's `p_i < min_p * p_max` in the log domain)
+A row whose scores are all -inf keeps everything.  The token is the first maximum of y_i + g_i over the kept ids: an exact draw from the renormalised truncated
+distribution.  The kernel accumulates the masses in fixed point (2^-32) from the hardware exponential: its normalised cumulative mass is within EPS_MASS of float64."""
+TOP_K_MAX = (1 << 31) - 1
+# |c_kernel(r) - c(r)| <= EPS_MASS, c(r) = mass of ranks 0 .. r - 1 over mass(K), for vocabularies up to 65 536 ids (DESIGN.md 6.13).  A term is
+# rint(exp2(fl(fl(y - y_max) * fl(log2 e))) * 2^32): three roundings of 2^-24 on an argument of at most 33 in size (a term beyond it is below half a quantum) move it
+# by 33 * 3 * 2^-24 = 5.9e-6, the exponential by ln 2 times that, 4.09e-6, relative; v_exp_f32 adds 1 ulp, 2^-23 = 1.2e-7: rho = 4.21e-6 per term, hence per sum.  The
+# rounding to the quantum adds at most V / 2 quanta to a sum, and mass(K) is at least 2^32 quanta (the maximum's own term is exactly 2^32): V * 2^-33 each for the
+# numerator and the denominator.  A quotient of two such sums moves by 2 rho + 2 V 2^-33 = 8.42e-6 + 1.53e-5 = 2.37e-5 at V = 65 536; the threshold's own rounding
+# (the product top_p * mass in float64, then one quantum) is below 2^-31.  Rounded up
+EPS_MASS = 2.4e-5
+
+
+def check_truncation(top_k=0, top_p=1.0, min_p=0.0) -> Tuple[int, float, float]:
+    """(top_k, top_p, min_p) validated: nothing is clamped (ValueError names the parameter; NaN included)"""
+    if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 0 <= int(top_k) <= TOP_K_MAX:
+        raise ValueError(f"top_k {top_k!r} is invalid: an integer in 0 .. 2^31 - 1 (0 = off)")
+    try:
+        p, m = float(top_p), float(min_p)
+    except (TypeError, ValueError):
+        raise ValueError(f"top_p {top_p!r} / min_p {min_p!r} is not a number") from None
+    if not 0.0 < p <= 1.0 or not 0.0 < float(np.float32(p)) <= 1.0:
+        raise ValueError(f"top_p {top_p!r} is invalid: a value in (0, 1] (1 = off), also when rounded to float32")
+    if not 0.0 <= m <= 1.0:
+        raise ValueError(f"min_p {min_p!r} is invalid: a value in [0, 1] (0 = off)")
+    return int(top_k), p, m
+
+
+def truncation_words(top_k=0, top_p=1.0, min_p=0.0) -> np.ndarray:
+    """the row of "request_truncation": float32 [top_k, top_p, min_p] (top_k must be exact in float32: up to 2^24, beyond that it is off for every vocabulary
+    the kernel serves and is sent as 2^24)"""
+    k, p, m = check_truncation(top_k, top_p, min_p)
+    return np.array([min(k, 1 << 24), p, m], np.float32)
+
+
+def log_min_p(min_p: float) -> np.float32:
+    """lnm of the contract: float32(log(min_p)) (min_p = 0: -inf, the filter is off)"""
+    with np.errstate(divide="ignore"):
+        return np.float32(np.log(np.float64(np.float32(min_p))))
+
+
+def quotient(scores_f32, t: float) -> np.ndarray:
+    """y of the truncation contract: fdiv_rn(s, t) in fp32 (numpy's float32 division is correctly rounded); -0.0 counts as +0.0"""
+    with np.errstate(invalid="ignore"):
+        y = (np.asarray(scores_f32, np.float32) / np.float32(t)).astype(np.float32)
+    return y + np.float32(0.0)
+
+
+def truncation_order(y) -> np.ndarray:
+    """the ids by (y descending, id ascending)"""
+    return np.argsort(-np.asarray(y, np.float64), kind="stable")
+
+
+def truncation_counts(y, top_k=0, top_p=1.0, min_p=0.0, p_shift: float = 0.0) -> Tuple[int, int, int]:
+    """(n_k, n_p, n_m): the lengths of the three prefixes of truncation_order(y) (V where a filter is off).  p_shift moves top_p for the tests' bracket
+    n(p - eps) <= n_kernel <= n(p + eps); the masses are float64"""
+    k, p, m = check_truncation(top_k, top_p, min_p)
+    y = np.asarray(y, np.float32)
+    V = y.shape[0]
+    ymax = y.max() if V else np.float32(-np.inf)
+    if not np.isfinite(ymax):                      # every score -inf: nothing is removed
+        return V, V, V
+    ys = y[truncation_order(y)]
+    n_k = V
+    if 0 < k < V:
+        n_k = int(np.count_nonzero(ys >= ys[k - 1]))
+    n_p = V
+    if np.float32(p) < 1.0:
+        w = np.exp(ys[:n_k].astype(np.float64) - np.float64(ymax))
+        before = np.concatenate([[0.0], np.cumsum(w)[:-1]])
+        thr = (np.float64(np.float32(p)) + p_shift) * w.sum()
+        n_p = max(1, int(np.count_nonzero(before < thr)))      # (before is non-decreasing: the kept ranks are a prefix)
+    n_m = V
+    if m > 0.0:
+        n_m = int(np.count_nonzero(ys >= np.float32(ymax + log_min_p(m))))
+    return n_k, n_p, n_m
+
+
+def truncation_kept(scores_f32, t: float, top_k=0, top_p=1.0, min_p=0.0, p_shift: float = 0.0) -> np.ndarray:
+    """the kept ids in the contract's order: the first min(n_k, n_p, n_m) of truncation_order(y)"""
+    y = quotient(scores_f32, check_temperature(t))
+    return truncation_order(y)[: min(truncation_counts(y, top_k, top_p, min_p, p_shift))]
+
+
+def sample_truncated(scores_f32, t: float, seed: int, step: int, top_k=0, top_p=1.0, min_p=0.0) -> int:
+    """the token of the contract with exact noise: the first maximum of y + g over the kept ids (t = 0: greedy, the three parameters are ignored)"""
+    t = check_temperature(t)
+    s = np.asarray(scores_f32, np.float32)
+    if t == 0.0:
+        return int(np.argmax(s))
+    kept = np.sort(truncation_kept(s, t, top_k, top_p, min_p))
+    yy = perturbed(s, t, seed, step)[kept]
+    return int(kept[int(np.argmax(yy))])
+
+
+def pack_truncation(values: Sequence) -> np.ndarray:
+    """per-request (top_k, top_p, min_p) -> float32 [R][3] for sonic_load_tensor "request_truncation", validated"""
+    return np.stack([truncation_words(*v) for v in values]).astype(np.float32).reshape(-1, 3)

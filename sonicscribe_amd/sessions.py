@@ -44,20 +44,21 @@ def committed_max_new_tokens(seconds: float) -> int:
 class GatedSessions:
     def __init__(self, model, session_ids: Sequence[str], buffer_seconds: float = 30.0, hotwords: Optional[List[str]] = None,
                  cfg: GateConfig = GateConfig(), device_vad: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: Optional[float] = None,
-                 temperature: Optional[float] = None, seed: Optional[int] = None, cumulative_partials: bool = False):
+                 temperature: Optional[float] = None, seed: Optional[int] = None, cumulative_partials: bool = False,
+                 top_k: Optional[int] = None, top_p: Optional[float] = None, min_p: Optional[float] = None):
         self.model, self.ids, self.hotwords, self.cfg = model, list(session_ids), hotwords, cfg
         # cumulative partials (module docstring): the current segment's partial futures per session, oldest first; a draft is read from the newest one that is done
         self.cumulative_partials = bool(cumulative_partials)
         if self.cumulative_partials:
             if not getattr(model, "token_logprobs", False) or not getattr(model, "draft_verify", False):
                 raise ValueError("cumulative_partials=True needs a model built with token_logprobs=True and draft_verify=True (the partials' token ids are the next request's draft)")
-            if any(v is not None for v in (sequence_bias, bad_words_ids, hotword_boost, temperature, seed)):
+            if any(v is not None for v in (sequence_bias, bad_words_ids, hotword_boost, temperature, seed, top_k, top_p, min_p)):
                 raise ValueError("cumulative_partials=True cannot be combined with bias values or a temperature: a draft is verified under the model's own processors only")
         self._partials: List[List[Future]] = [[] for _ in self.ids]
         # beside the hotwords: the sessions' sequence-bias values (a model built with request_bias=True), handed to every decode only when one is given
         # (likewise the sessions' temperature - a float - and seed, for a model built with sampling=True)
         self._bias_kw = {k: v for k, v in (("sequence_bias", sequence_bias), ("bad_words_ids", bad_words_ids), ("hotword_boost", hotword_boost),
-                                           ("temperature", temperature), ("seed", seed)) if v is not None}
+                                           ("temperature", temperature), ("seed", seed), ("top_k", top_k), ("top_p", top_p), ("min_p", min_p)) if v is not None}
         self.device_vad = bool(device_vad)            # opt-in: windows are ring ranges, `recent` stays empty
         n = len(self.ids)
         self.streams = [model.open_stream(s, buffer_seconds) for s in self.ids]
