@@ -113,8 +113,8 @@ def as_pcm16(audio) -> np.ndarray:
 class _FileJob:
     """One file on the device: its ring, its plan and its queued decodes."""
 
-    def __init__(self, model, audio, vad, vad_enabled: bool, hotwords, max_segment_duration, max_new_tokens: int, filename: str,
-                 sampling_rate: int = SAMPLE_RATE, sequence_bias=None, bad_words_ids=None, hotword_boost=None, temperature=None, seed=None, word_timestamps: bool = False, grammar=None, top_k=None, top_p=None, min_p=None):
+    def __init__(self, model, call: reqvalues.CallKeywords, audio, vad, vad_enabled: bool, hotwords, max_segment_duration, max_new_tokens: int, filename: str,
+                 sampling_rate: int = SAMPLE_RATE, word_timestamps: bool = False):
         if not hasattr(model, "model"):
             raise RuntimeError("ASR model has been released")
         # word_timestamps (a model built with timestamps=True; DESIGN.md 6.9): every segment's tokens are aligned on the replica's scoring handle as its record is
@@ -124,11 +124,12 @@ class _FileJob:
             model._check_timestamps()
         # the file's temperature (a float) or fallback ladder (a sequence) and seed (a model built with sampling=True; ASRModel._request_sampling): every segment
         # of the file is decoded with them, each as its own request
-        self.samp = model._request_sampling(temperature, seed, cut=(top_k, top_p, min_p)) if hasattr(model, "_request_sampling") else None
+        samp = model._request_sampling(call.temperature, call.seed, cut=(call.top_k, call.top_p, call.min_p)) if hasattr(model, "_request_sampling") else None
         # the file's sequence-bias table (a model built with request_bias=True; ASRModel._request_bias): every segment of the file carries it
-        self.bias = model._request_bias(hotwords, sequence_bias, bad_words_ids, hotword_boost) if hasattr(model, "_request_bias") else None
+        bias = model._request_bias(hotwords, call.sequence_bias, call.bad_words_ids, call.hotword_boost) if hasattr(model, "_request_bias") else None
         # the file's grammar (a model built with grammar=True; ASRModel.compile_grammar): every segment of the file is decoded under it, from its start node
-        self.gram = model._request_grammar(grammar) if grammar is not None else None
+        gram = model._request_grammar(call.grammar) if call.grammar is not None else None
+        self.values = reqvalues.CallValues(bias, samp, gram)      # (resolved in file mode's own order: sampling ahead of the table; no draft, one sample)
         self.model, self.filename = model, filename
         self.vad_enabled, self.hotwords = bool(vad_enabled), list(hotwords) if hotwords else None
         self.max_seg = float(max_segment_duration or DEFAULT_MAX_SEGMENT_S)
@@ -164,7 +165,7 @@ class _FileJob:
         except BaseException:
             self.release()
             raise
-        if self.word_timestamps and self.samp is not None and self.samp[1]:
+        if self.word_timestamps and samp is not None and samp.ladder:
             self.release()
             raise ValueError("word_timestamps is not supported with a fallback ladder of temperatures in file mode (the ladder's futures carry texts, not tokens): pass one temperature")
         self.futures: List[Any] = []
@@ -194,12 +195,12 @@ class _FileJob:
             windows = [self.ring.slice(self.first + a + s, e - s) for s, e in frontend.split_windows(n, m.dims)]
             n_audio, _ = frontend.request_audio_tokens(n, m.dims)
             self.requests.append((windows, m.prompt.build(instruction, n_audio), n))
-            if self.samp is not None and not self.word_timestamps:      # (a future of the TEXT: the ladder judges texts; records() takes either)
-                self.futures.append(m._dispatch(windows, m.prompt.build(instruction, n_audio), self.max_new, False, self.bias, self.samp, self.gram, replica=self.replica))
+            if self.values.samp is not None and not self.word_timestamps:      # (a future of the TEXT: the ladder judges texts; records() takes either)
+                self.futures.append(m._dispatch(windows, m.prompt.build(instruction, n_audio), self.max_new, False, self.values, replica=self.replica))
                 continue
             # the scheduler's own future carries the tokens (with word_timestamps: at the file's one temperature; a ladder was refused when the job was made)
             self.futures.append(m._dispatcher.submit(windows, m.prompt.build(instruction, n_audio), self.max_new, replica=self.replica,
-                                                     **reqvalues.submit_keywords(self.bias, self.samp, self.gram, None)))
+                                                     **reqvalues.submit_keywords(self.values)))
 
     def records(self) -> Iterator[Dict[str, Any]]:
         total_segments = len(self.segments)
@@ -294,13 +295,11 @@ def _detect(vad, jobs: Sequence[_FileJob]) -> List[Any]:
     return out
 
 
-def transcribe_file(model, audio, vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
+def transcribe_file(model, call: reqvalues.CallKeywords, audio, vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                     max_segment_duration: Optional[float] = None, max_new_tokens: int = 256, filename: str = "",
-                    sampling_rate: int = SAMPLE_RATE, sequence_bias=None, bad_words_ids=None, hotword_boost=None, temperature=None, seed=None,
-                    word_timestamps: bool = False, grammar=None, top_k=None, top_p=None, min_p=None) -> Iterator[Dict[str, Any]]:
-    """Generator of the reference's file-mode records for one file (see ASRModel.transcribe_file)."""
-    job = _FileJob(model, audio, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filename, sampling_rate, sequence_bias, bad_words_ids, hotword_boost,
-                   temperature, seed, word_timestamps, grammar, top_k=top_k, top_p=top_p, min_p=min_p)
+                    sampling_rate: int = SAMPLE_RATE, word_timestamps: bool = False) -> Iterator[Dict[str, Any]]:
+    """Generator of the reference's file-mode records for one file (see ASRModel.transcribe_file, which builds `call` from its keywords)."""
+    job = _FileJob(model, call, audio, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, filename, sampling_rate, word_timestamps)
     try:
         ts = vad.detect_voice_activity_ring(job.ring, job.first, job.total)[0] if job.wants_vad else None
         job.plan(ts)
@@ -311,18 +310,16 @@ def transcribe_file(model, audio, vad, vad_enabled: bool = True, hotwords: Optio
     yield from job.records()
 
 
-def transcribe_files(model, audios: Sequence[Any], vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
+def transcribe_files(model, call: reqvalues.CallKeywords, audios: Sequence[Any], vad, vad_enabled: bool = True, hotwords: Optional[List[str]] = None,
                      max_segment_duration: Optional[float] = None, max_new_tokens: int = 256,
-                     filenames: Optional[Sequence[str]] = None, sampling_rate: int = SAMPLE_RATE, sequence_bias=None, bad_words_ids=None,
-                     hotword_boost=None, temperature=None, seed=None, word_timestamps: bool = False, grammar=None, top_k=None, top_p=None, min_p=None) -> List[FileRecords]:
+                     filenames: Optional[Sequence[str]] = None, sampling_rate: int = SAMPLE_RATE, word_timestamps: bool = False) -> List[FileRecords]:
     """One record iterator per file; the VAD of all files runs in one device call and every file's segments are queued before the call
     returns.  Each iterator must be exhausted or closed (its ring lives until then)."""
     names = list(filenames) if filenames is not None else [""] * len(audios)
     jobs: List[_FileJob] = []
     try:
         for a, name in zip(audios, names):
-            jobs.append(_FileJob(model, a, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, name, sampling_rate, sequence_bias, bad_words_ids, hotword_boost,
-                                 temperature, seed, word_timestamps, grammar, top_k=top_k, top_p=top_p, min_p=min_p))
+            jobs.append(_FileJob(model, call, a, vad, vad_enabled, hotwords, max_segment_duration, max_new_tokens, name, sampling_rate, word_timestamps))
         for job, ts in zip(jobs, _detect(vad, jobs)):
             job.plan(ts)
         for job in jobs:

@@ -71,17 +71,26 @@ def check_draft(req, engines) -> None:
         raise ValueError("a draft cannot be combined with a bias table, a temperature > 0 or a grammar (the verify pass applies the engine's own processors only)")
 
 
-def submit_keywords(bias, samp, gram, draft) -> dict:
-    """One call's own values, as ASRModel._request_values resolves them (samp: None, or (temperatures, is it a ladder, seed[, (top_k, top_p, min_p)])), as the keywords of Dispatcher.submit.
-    Each only when the request brings it - stub dispatchers need not know the others: `bias` a non-empty table, `sampling` for one temperature (a fallback ladder
-    states it attempt by attempt: ASRModel._dispatch), `grammar`, `draft` a non-empty one."""
+# Above the scheduler.  The generation keywords of one call as its public entry received them, None for one the caller did not state or the entry does not take (file mode has no draft
+# or best_of, streams no best_of).  Every entry of ASRModel and AudioStream builds it once; from there on only the record travels.  A further keyword is one field
+# here, the entries' signatures and constructions, and its line in ASRModel._request_values.
+CallKeywords = namedtuple("CallKeywords", "sequence_bias bad_words_ids hotword_boost temperature seed grammar draft best_of top_k top_p min_p", defaults=(None,) * 11)
+# One call's own values as ASRModel._request_values resolves them: `bias` a reqbias.RequestBias or None, `samp` a sampling.CallSampling or None (a model without the
+# option), `gram` a grammar.CompiledGrammar or None, `draft` its token ids or None, `best_of` the samples of an attempt at a temperature above 0.
+CallValues = namedtuple("CallValues", "bias samp gram draft best_of", defaults=(None, None, None, None, 1))
+
+
+def submit_keywords(values: CallValues) -> dict:
+    """One call's own values as the keywords of Dispatcher.submit.  Each only when the request brings it - stub dispatchers need not know the others: `bias` a
+    non-empty table, `sampling` for one temperature (a fallback ladder states it attempt by attempt: ASRModel._dispatch; (top_k, top_p, min_p) behind the pair when the
+    call cuts the tail), `grammar`, `draft` a non-empty one."""
     kw = {}
-    if bias:
-        kw["bias"] = bias
-    if samp is not None and not samp[1]:
-        kw["sampling"] = (samp[0][0], samp[2]) + (tuple(samp[3]) if len(samp) > 3 and samp[0][0] > 0 else ())      # (top_k, top_p, min_p) behind the pair when the call cuts the tail (DESIGN.md 6.13)
-    if gram is not None:
-        kw["grammar"] = gram
-    if draft:
-        kw["draft"] = draft
+    if values.bias:
+        kw["bias"] = values.bias
+    if values.samp is not None and not values.samp.ladder:
+        kw["sampling"] = values.samp.attempt(values.samp.temperatures[0])
+    if values.gram is not None:
+        kw["grammar"] = values.gram
+    if values.draft:
+        kw["draft"] = values.draft
     return kw

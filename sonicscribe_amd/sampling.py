@@ -9,13 +9,14 @@ within EPS_G of the float64 value below.
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence, Tuple, Union
+from typing import NamedTuple, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
 PHILOX_M0, PHILOX_M1 = 0xD2511F53, 0xCD9E8D57
 PHILOX_W0, PHILOX_W1 = 0x9E3779B9, 0xBB67AE85
 T_MIN, T_MAX = 1e-3, 100.0
+NO_CUT = (0, 1.0, 0.0)      # (top_k, top_p, min_p) that cut nothing
 # |g_kernel - g| <= EPS_G.  The device logf is the hardware's base-2 logarithm (v_log_f32: 1 ulp, so a relative error of at most 2^-23) times ln 2 in extended
 # precision, rounded once (2^-24): a relative error r <= 1.5 * 2^-23 (+ second-order terms).  L = -logf(u), u exact: L = L_exact * (1 + d), |d| <= r, which moves
 # ln(L) by at most r (absolute); the outer logf adds r * |g|, |g| <= 16.64.  (1 + 16.64) * 1.5 * 2^-23 = 3.154e-6, rounded up.
@@ -74,6 +75,25 @@ def temperatures(temperature) -> Tuple[Tuple[float, ...], bool]:
     if not ts:
         raise ValueError("temperature: an empty sequence")
     return ts, True
+
+
+class CallSampling(NamedTuple):
+    """One call's sampling as ASRModel._request_sampling resolves it: the temperatures (one, or the fallback ladder's), whether they are a ladder, the seed and the
+    (top_k, top_p, min_p) of every sampled decode - always a triple, NO_CUT when the call cuts nothing."""
+    temperatures: Tuple[float, ...]
+    ladder: bool
+    seed: int
+    cut: Tuple[int, float, float] = NO_CUT
+
+    @property
+    def cuts(self) -> bool:      # does the call cut the tail at all
+        return tuple(self.cut) != NO_CUT
+
+    def attempt(self, t: float, seed: Optional[int] = None) -> tuple:
+        """What the scheduler is told for one attempt at temperature t (seed: a fork's own, else the call's): the pair (t, seed) at t = 0 - greedy rows ignore the
+        cut - and for a call that cuts nothing, as such requests always stated; (t, seed, top_k, top_p, min_p) otherwise."""
+        pair = (t, self.seed if seed is None else seed)
+        return pair + tuple(self.cut) if self.cuts and t > 0 else pair
 
 
 def uniforms(seed: int, step: int, V: int) -> np.ndarray:

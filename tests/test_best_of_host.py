@@ -8,6 +8,8 @@ import pytest
 
 from sonicscribe_amd import asr, engine, fallback, sampling, spec
 from sonicscribe_amd.reqbias import RequestBias
+from sonicscribe_amd.reqvalues import CallValues
+from sonicscribe_amd.sampling import CallSampling
 
 from test_dispatch import seg
 from test_reqvalues_host import ENTRY, _consume, _engine, _names
@@ -133,11 +135,11 @@ def _model(best_of=3, lp_of_seed=None, logprob_threshold=-1.0):
 def test_temperature_zero_never_forks():
     m = _model(lp_of_seed={})
     try:
-        tr = m._dispatch([seg(1)], [1, 2, 3], 4, True, None, ((0.0,), False, 5), best_of=3).result(timeout=5)
+        tr = m._dispatch([seg(1)], [1, 2, 3], 4, True, CallValues(samp=CallSampling((0.0,), False, 5), best_of=3)).result(timeout=5)
         assert m._fork_engines[0].calls == [] and len(m._dispatcher.calls) == 1
         assert (tr.best_of, tr.fork_index) == (1, 0) and tr.fork_avg_logprobs.tolist() == [tr.avg_logprob] and tr.token_ids.tolist() == [7, 8]
         # ... nor does a call that asks for one sample
-        m._dispatch([seg(1)], [1, 2, 3], 4, True, None, ((0.8,), False, 5), best_of=1).result(timeout=5)
+        m._dispatch([seg(1)], [1, 2, 3], 4, True, CallValues(samp=CallSampling((0.8,), False, 5), best_of=1)).result(timeout=5)
         assert m._fork_engines[0].calls == [] and m._dispatcher.calls[-1]["sampling"] == (0.8, 5)
     finally:
         m.__dict__.clear()
@@ -147,7 +149,7 @@ def test_a_sampled_attempt_is_one_forked_run_and_the_best_fork_wins():
     m = _model(lp_of_seed={41: -3.0, 42: -0.5, 43: -0.5})
     try:
         bias = RequestBias([[[5], 1.0]])
-        tr = m._dispatch([seg(1), seg(2)], [1, 2, 3], 4, True, bias, ((0.8,), False, 41), best_of=3).result(timeout=5)
+        tr = m._dispatch([seg(1), seg(2)], [1, 2, 3], 4, True, CallValues(bias, CallSampling((0.8,), False, 41), best_of=3)).result(timeout=5)
         assert m._dispatcher.calls == [] and len(m._fork_engines[0].calls) == 1
         c = m._fork_engines[0].calls[0]
         assert c["forks"] == [3] and c["sampling"] == [(0.8, 41), (0.8, 42), (0.8, 43)] and c["n_segs"] == 2 and c["req_win"] == [0, 2] and c["max_new"] == [4]
@@ -156,7 +158,7 @@ def test_a_sampled_attempt_is_one_forked_run_and_the_best_fork_wins():
         assert tr.fork_avg_logprobs.tolist() == [-3.0, -0.5, -0.5] and tr.avg_logprob == -0.5
         # the seeds wrap; the text alone when the caller asked for no details
         m._fork_engines[0].lp = {2 ** 64 - 1: -1.0, 0: -2.0}
-        text = m._dispatch([seg(1)], [1, 2, 3], 4, False, None, ((0.5,), False, 2 ** 64 - 1), best_of=2).result(timeout=5)
+        text = m._dispatch([seg(1)], [1, 2, 3], 4, False, CallValues(samp=CallSampling((0.5,), False, 2 ** 64 - 1), best_of=2)).result(timeout=5)
         assert m._fork_engines[0].calls[-1]["sampling"] == [(0.5, 2 ** 64 - 1), (0.5, 0)] and isinstance(text, str)
     finally:
         m.__dict__.clear()
@@ -165,7 +167,7 @@ def test_a_sampled_attempt_is_one_forked_run_and_the_best_fork_wins():
 def test_the_ladder_forks_only_its_sampled_rungs():
     m = _model(lp_of_seed={9: -0.25, 10: -0.125, 11: -4.0}, logprob_threshold=-1.0)      # the greedy attempt averages -2: it fails the threshold
     try:
-        tr = m._dispatch([seg(1)], [1, 2, 3], 4, True, None, ((0.0, 0.8, 1.0), True, 9), best_of=3).result(timeout=5)
+        tr = m._dispatch([seg(1)], [1, 2, 3], 4, True, CallValues(samp=CallSampling((0.0, 0.8, 1.0), True, 9), best_of=3)).result(timeout=5)
         assert len(m._dispatcher.calls) == 1 and m._dispatcher.calls[0]["sampling"] == (0.0, 9)
         assert [c["sampling"] for c in m._fork_engines[0].calls] == [[(0.8, 9), (0.8, 10), (0.8, 11)]]      # the winner passed: no third rung
         assert (tr.attempts, tr.temperature, tr.best_of, tr.fork_index) == (2, 0.8, 3, 1) and tr.avg_logprob == -0.125

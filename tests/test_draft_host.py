@@ -11,6 +11,7 @@ import pytest
 
 from sonicscribe_amd import asr, dispatch, engine, sessions, spec
 from sonicscribe_amd.dispatch import Dispatcher, Request
+from sonicscribe_amd.sampling import CallSampling
 from sonicscribe_amd.sessions import DRAFT_HOLDBACK, PARTIAL_TOKENS, GatedSessions, committed_max_new_tokens
 
 from test_dispatch import StubEngine, StubPool, seg
@@ -67,10 +68,10 @@ def test_asrmodel_refusals_by_name():
     with pytest.raises(ValueError, match="draft= cannot be combined with bias values"):
         m._request_draft([5, 6], 24, bias=object())
     with pytest.raises(ValueError, match="draft= cannot be combined with a temperature ladder"):
-        m._request_draft([5, 6], 24, samp=((0.0, 0.4), True, 0))
+        m._request_draft([5, 6], 24, samp=CallSampling((0.0, 0.4), True, 0))
     with pytest.raises(ValueError, match="temperature > 0"):
-        m._request_draft([5, 6], 24, samp=((0.7,), False, 0))
-    assert m._request_draft([5, 6], 24, samp=((0.0,), False, 0)) == [5, 6]                   # greedy is greedy
+        m._request_draft([5, 6], 24, samp=CallSampling((0.7,), False, 0))
+    assert m._request_draft([5, 6], 24, samp=CallSampling((0.0,), False, 0)) == [5, 6]                   # greedy is greedy
     with pytest.raises(ValueError, match="draft= cannot be combined with a grammar"):
         m._request_draft([5, 6], 24, gram=object())
     with pytest.raises(ValueError, match="draft_verify is not supported with mode='int8'"):

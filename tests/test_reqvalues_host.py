@@ -12,6 +12,7 @@ import pytest
 from sonicscribe_amd import dispatch, engine, reqvalues, spec
 from sonicscribe_amd.dispatch import Dispatcher, Request
 from sonicscribe_amd.reqbias import RequestBias
+from sonicscribe_amd.sampling import CallSampling
 
 from test_dispatch import StubEngine, StubPool, seg
 
@@ -32,10 +33,11 @@ def test_the_list_names_what_the_sites_use():
 
 def test_submit_keywords_only_what_the_request_brings():
     g = object()
-    assert reqvalues.submit_keywords(None, None, None, None) == {}
-    assert reqvalues.submit_keywords(RequestBias(), ((0.0, 0.4), True, 3), None, []) == {}              # an empty table, a ladder, an empty draft: nothing
-    assert reqvalues.submit_keywords("b", ((0.3,), False, 9), g, [4, 5]) == {"bias": "b", "sampling": (0.3, 9), "grammar": g, "draft": [4, 5]}
-    assert reqvalues.submit_keywords(None, ((0.0,), False, 0), None, None) == {"sampling": (0.0, 0)}    # a greedy single temperature is still stated
+    CV, CS = reqvalues.CallValues, CallSampling
+    assert reqvalues.submit_keywords(CV(None, None, None, None)) == {}
+    assert reqvalues.submit_keywords(CV(RequestBias(), CS((0.0, 0.4), True, 3), None, [])) == {}              # an empty table, a ladder, an empty draft: nothing
+    assert reqvalues.submit_keywords(CV("b", CS((0.3,), False, 9), g, [4, 5])) == {"bias": "b", "sampling": (0.3, 9), "grammar": g, "draft": [4, 5]}
+    assert reqvalues.submit_keywords(CV(None, CS((0.0,), False, 0), None, None)) == {"sampling": (0.0, 0)}    # a greedy single temperature is still stated
 
 
 # ------------------------------------------------------------------------------------------ the batch replica's keywords

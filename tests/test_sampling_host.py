@@ -194,8 +194,9 @@ def test_surface_and_model_refusals():
         with pytest.raises(ValueError, match="sampling"):
             m._request_sampling(**kw)
     m.sampling, m._default_temperature, m._default_seed = True, 0.0, 5
-    assert m._request_sampling() == ((0.0,), False, 5) and m._request_sampling(0.3, 9) == ((0.3,), False, 9)
-    assert m._request_sampling((0.0, 0.4)) == ((0.0, 0.4), True, 5)
+    CS = sampling.CallSampling
+    assert m._request_sampling() == CS((0.0,), False, 5, (0, 1.0, 0.0)) and m._request_sampling(0.3, 9) == CS((0.3,), False, 9, (0, 1.0, 0.0))
+    assert m._request_sampling((0.0, 0.4)) == CS(temperatures=(0.0, 0.4), ladder=True, seed=5, cut=(0, 1.0, 0.0))
     with pytest.raises(ValueError, match="ladder"):
         m._request_sampling((0.0, 0.4), ladder_ok=False)
     with pytest.raises(ValueError, match="temperature"):

@@ -227,16 +227,17 @@ WIN = [np.zeros(1600, np.int16)]
 def test_model_resolves_the_call_over_the_defaults():
     m = _model(cut=(50, 0.9, 0.0))
     try:
-        assert m._request_sampling(0.7, 3) == ((0.7,), False, 3, (50, 0.9, 0.0))                      # the constructor's defaults
-        assert m._request_sampling(0.7, 3, cut=(None, 0.5, 0.1)) == ((0.7,), False, 3, (50, 0.5, 0.1))  # a call overrides what it states
-        assert m._request_sampling(0.7, 3, cut=(0, 1.0, None)) == ((0.7,), False, 3)                   # all off: the triple it always was, and pairs downstream
+        CS, values = sampling.CallSampling, lambda samp: reqvalues.CallValues(None, samp, None, None)
+        assert m._request_sampling(0.7, 3) == CS((0.7,), False, 3, (50, 0.9, 0.0))                      # the constructor's defaults
+        assert m._request_sampling(0.7, 3, cut=(None, 0.5, 0.1)) == CS((0.7,), False, 3, (50, 0.5, 0.1))  # a call overrides what it states
+        assert m._request_sampling(0.7, 3, cut=(0, 1.0, None)) == CS((0.7,), False, 3, (0, 1.0, 0.0))    # all off: the cut that cuts nothing, and pairs downstream
         for bad, name in (((-1, None, None), "top_k"), ((None, 0.0, None), "top_p"), ((None, None, float("nan")), "min_p")):
             with pytest.raises(ValueError, match=name):
                 m._request_sampling(0.7, 3, cut=bad)
         # what the schedulers are told: a pair at temperature 0 (greedy rows ignore the cut), the 5-tuple above it
-        assert reqvalues.submit_keywords(None, m._request_sampling(0.7, 3), None, None) == {"sampling": (0.7, 3, 50, 0.9, 0.0)}
-        assert reqvalues.submit_keywords(None, m._request_sampling(0.0, 3), None, None) == {"sampling": (0.0, 3)}
-        assert reqvalues.submit_keywords(None, _model()._request_sampling(0.7, 3), None, None) == {"sampling": (0.7, 3)}
+        assert reqvalues.submit_keywords(values(m._request_sampling(0.7, 3))) == {"sampling": (0.7, 3, 50, 0.9, 0.0)}
+        assert reqvalues.submit_keywords(values(m._request_sampling(0.0, 3))) == {"sampling": (0.0, 3)}
+        assert reqvalues.submit_keywords(values(_model()._request_sampling(0.7, 3))) == {"sampling": (0.7, 3)}
     finally:
         m.__dict__.clear()
 
@@ -244,17 +245,17 @@ def test_model_resolves_the_call_over_the_defaults():
 def test_every_rung_above_zero_and_every_fork_repeat_the_values():
     m = _model(cut=(50, 0.9, 0.05))
     try:
-        tr = m._dispatch(WIN, [1, 2, 3], 4, True, None, m._request_sampling((0.0, 0.4, 0.8), 9)).result(timeout=5)      # every attempt averages -2: all three are tried
+        tr = m._dispatch(WIN, [1, 2, 3], 4, True, reqvalues.CallValues(samp=m._request_sampling((0.0, 0.4, 0.8), 9))).result(timeout=5)      # every attempt averages -2: all three are tried
         assert [c["sampling"] for c in m._dispatcher.calls] == [(0.0, 9), (0.4, 9, 50, 0.9, 0.05), (0.8, 9, 50, 0.9, 0.05)]
         assert (tr.attempts, tr.temperature, tr.top_k, tr.top_p, tr.min_p) == (3, 0.8, 50, 0.9, 0.05)
-        one = m._dispatch(WIN, [1, 2, 3], 4, True, None, m._request_sampling(0.0, 9)).result(timeout=5)
+        one = m._dispatch(WIN, [1, 2, 3], 4, True, reqvalues.CallValues(samp=m._request_sampling(0.0, 9))).result(timeout=5)
         assert (one.top_k, one.top_p, one.min_p) == (0, 1.0, 0.0)                                                      # temperature 0: the values were not used
     finally:
         m.__dict__.clear()
     m = _model(best_of=3, cut=(0, 1.0, 0.0))
     try:
         samp = m._request_sampling((0.0, 0.8), 41, cut=(5, None, None))
-        tr = m._dispatch(WIN, [1, 2, 3], 4, True, None, samp, best_of=3).result(timeout=5)
+        tr = m._dispatch(WIN, [1, 2, 3], 4, True, reqvalues.CallValues(samp=samp, best_of=3)).result(timeout=5)
         assert m._dispatcher.calls[0]["sampling"] == (0.0, 41) and len(m._dispatcher.calls) == 1
         assert m._fork_engines[0].calls == [[(0.8, 41, 5, 1.0, 0.0), (0.8, 42, 5, 1.0, 0.0), (0.8, 43, 5, 1.0, 0.0)]]     # the forks differ in their seeds alone
         assert (tr.best_of, tr.top_k, tr.top_p, tr.min_p) == (3, 5, 1.0, 0.0)
