@@ -6,13 +6,13 @@ import numpy as np
 import pytest
 
 import attn_ref as R
+from gpu_common import load_oracle
 from sonicscribe_amd import synth
 
 
 @pytest.fixture(scope="module")
 def orc():
-    from oracle import oracle
-    return oracle
+    return load_oracle()
 
 
 def bf(x):

@@ -1,14 +1,13 @@
 """Draft-verified decoding on the host (no device): the packed words of "request_draft" and "draft.dispatch", ASRModel's cut rules and refusals,
 draft_matched, batch fitting that counts draft tokens (with the stub engines of tests/test_dispatch.py), GatedSessions(cumulative_partials=True) with a stub
 model, and the header: the feature adds no entry point and leaves the ABI version alone."""
-import os
-import re
 import threading
 from concurrent.futures import Future
 
 import numpy as np
 import pytest
 
+import abi_pins
 from sonicscribe_amd import asr, dispatch, engine, sessions, spec
 from sonicscribe_amd.dispatch import Dispatcher, Request
 from sonicscribe_amd.sampling import CallSampling
@@ -16,8 +15,6 @@ from sonicscribe_amd.sessions import DRAFT_HOLDBACK, PARTIAL_TOKENS, GatedSessio
 
 from test_dispatch import StubEngine, StubPool, seg
 from test_sessions import StubModel, StubStream, energy_vad, loud
-
-HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "sonic_hip.h")
 
 
 # ------------------------------------------------------------------------------------------ the words
@@ -257,9 +254,4 @@ def test_cumulative_partials_refusals():
 
 # ------------------------------------------------------------------------------------------ the header
 def test_no_new_entry_point_and_the_same_abi():
-    hdr = open(HEADER).read()
-    text = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S))
-    assert len(re.findall(r"\bSONIC_API\b[^;]*?\bsonic_\w+\s*\(", text)) == 103 == len(engine.EXPORTS)
-    assert re.search(r"#define SONIC_ABI_VERSION 12\b", hdr) and engine.ABI_VERSION == 12
-    for word in ("draft_verify", "request_draft", "draft.dispatch", "draft_accepted"):
-        assert word in hdr, word
+    abi_pins.check_surface(header_strings=("draft_verify", "request_draft", "draft.dispatch", "draft_accepted"))

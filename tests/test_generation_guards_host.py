@@ -7,6 +7,7 @@ import re
 import numpy as np
 import pytest
 
+from gpu_common import same_bits
 from sonicscribe_amd import genconfig
 from sonicscribe_amd.genconfig import GenerationGuards
 
@@ -43,10 +44,6 @@ def scores_for(rng, history):
     for k, v in zip(h, (0.0, -0.0, 3.0e38, -3.0e38, -1.75, 2.5)):
         s[k] = np.float32(v)
     return s
-
-
-def same_bits(a, b):
-    return a.dtype == b.dtype == np.float32 and np.array_equal(a.view(np.int32), b.view(np.int32))
 
 
 def histories(n):

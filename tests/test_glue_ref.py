@@ -5,6 +5,7 @@ import pytest
 
 import glue_ref as G
 from attn_ref import U, rounder, rope_table
+from gpu_common import load_oracle
 
 KINDS = ["bf16", "f16"]
 F = np.float32
@@ -165,8 +166,7 @@ def test_rope_reference(kind, rd, hd):
 # ------------------------------------------------------------------------------------------ the int8 token step's references (tests/test_gpu_int8_decode_glue.py)
 @pytest.fixture(scope="module")
 def orc():
-    from oracle import oracle
-    return oracle
+    return load_oracle()
 
 
 def oracle_rows(orc, X, W):

@@ -12,54 +12,35 @@ References and tolerances:
   * live transformers (eager attention, output_attentions): the rule of tests/test_gpu_fp32_distance.py with its factor 1.25
 """
 import os
+from functools import partial
 
 import numpy as np
 import pytest
 
 import align_ref as R
 import glue_ref as G
+import gpu_common
+from gpu_common import bits, flags, forced_ids, load_golden, make_engine
 from sonicscribe_amd import frontend, spec, synth
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
 D = spec.TINY
 N = 24
 F = np.float32
 PRE, SUF = [1, 17, 23, 5], [7, 301, 302, 303, 9, 11]
 FACTOR = 1.25      # tests/test_gpu_fp32_distance.py's: no further from the fp32 truth than 1.25 x the reference's own bf16 path
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def prompt_for(n):
-    return PRE + [D.audio_token_id] * spec.audio_token_count(spec.valid_frames(n)) + SUF
+prompt_for = partial(gpu_common.prompt_for, D, prefix=PRE, suffix=SUF)
 
 
 def make(mode=0, max_batch=4, heads=(), align=True, K=0, lp=True):
-    from sonicscribe_amd.engine import Engine
-    e = Engine(D, 0, mode, max_batch=max_batch, max_ctx=1024)
-    if lp:
-        e.set_option("token_logprobs", 1)
-    if K:
-        e.set_option("top_logprobs", K)
-    e.set_option("forced_parallel", 1)
-    if align:
-        e.set_option("forced_align", 1)
-    for l, h in heads:
-        e.set_option("align_head", l * 256 + h)
-    e.load_synthetic(SEED)
-    return e
+    opts = flags((lp, "token_logprobs", 1), (K, "top_logprobs", K), (True, "forced_parallel", 1), (align, "forced_align", 1))
+    return make_engine(D, mode, max_batch, 1024, opts + [("align_head", l * 256 + h) for l, h in heads])
 
 
 @pytest.fixture(scope="module")
 def golden(golden_dir):
-    g = np.load(os.path.join(golden_dir, "tiny_forced_bf16.npz"))
-    segs = [synth.synth_pcm(int(g[f"s{i}_seg_index"]), int(g[f"s{i}_n_samples"])) for i in range(2)]
-    prompts = [g[f"s{i}_prompt_ids"] for i in range(2)]
-    force = np.stack([g[f"s{i}_force_ids"] for i in range(2)]).astype(np.int32)
-    return segs, prompts, force
+    g, segs, prompts = load_golden(golden_dir, "tiny_forced_bf16.npz")
+    return segs, prompts, forced_ids(g)
 
 
 @pytest.fixture(scope="module")

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import align_ref as R
+from gpu_common import bits
 from sonicscribe_amd import spec
 
 pytestmark = pytest.mark.gpu
@@ -28,10 +29,6 @@ def handle(request):
     e.set_option("forced_align", 1)
     yield request.param, e
     e.close()
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 @pytest.mark.parametrize("shape", R.KERNEL_SHAPES, ids=lambda s: "x".join(map(str, s)))

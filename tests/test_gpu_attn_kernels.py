@@ -18,7 +18,8 @@ import numpy as np
 import pytest
 
 import attn_ref as R
-from sonicscribe_amd import spec
+from gpu_common import make_engine
+from sonicscribe_amd.engine import MODE_F16
 
 pytestmark = pytest.mark.gpu
 
@@ -31,18 +32,14 @@ SPIKE = 3.5                    # k = 3.5 q: score 3.5 |q|^2 / sqrt(128) ~ 40 nat
 
 @pytest.fixture(scope="module")
 def eng():
-    from sonicscribe_amd.engine import Engine
-    e = Engine(spec.TINY, 0, max_batch=4, max_ctx=256)
-    e.load_synthetic(20260128)
+    e = make_engine(max_ctx=256)
     yield e
     e.close()
 
 
 @pytest.fixture(scope="module")
 def eng16():
-    from sonicscribe_amd.engine import Engine, MODE_F16
-    e = Engine(spec.TINY, 0, MODE_F16, max_batch=4, max_ctx=256)
-    e.load_synthetic(20260128)
+    e = make_engine(mode=MODE_F16, max_ctx=256)
     yield e
     e.close()
 
@@ -393,10 +390,8 @@ def test_prefill_random_and_late_dominant_key(E, kind, Hq, Hkv, variant):
 
 def test_prefill_default_variant_is_deterministic():
     """an engine nobody has set a knob on runs what production runs: inside the bound, the same bits on a rerun"""
-    from sonicscribe_amd.engine import Engine
-    e = Engine(spec.TINY, 0, max_batch=4, max_ctx=256)
+    e = make_engine(max_ctx=256)
     try:
-        e.load_synthetic(20260128)
         rng = np.random.default_rng(16)
         q, kc, vc, q_off, q_len, kv_len, n_tok, offs, _ = prefill_random(rng, "bf16", 16, 4)
         a = run_prefill(e, q, kc, vc, q_off, q_len, kv_len, n_tok)

@@ -11,11 +11,10 @@ from dataclasses import replace
 import numpy as np
 import pytest
 
+from gpu_common import SEED, load_oracle, make_engine
 from sonicscribe_amd import spec, synth
 
 pytestmark = pytest.mark.gpu
-
-SEED = 20260128
 
 
 def bf(x):
@@ -24,17 +23,14 @@ def bf(x):
 
 @pytest.fixture(scope="module")
 def eng():
-    from sonicscribe_amd.engine import Engine
-    e = Engine(spec.TINY, 0, max_batch=16, max_ctx=512)
-    e.load_synthetic(SEED)
+    e = make_engine(max_batch=16, max_ctx=512)
     yield e
     e.close()
 
 
 @pytest.fixture(scope="module")
 def orc():
-    from oracle import oracle
-    return oracle
+    return load_oracle()
 
 
 def tiny_prompt(n_samples, d=spec.TINY, pre=(1, 17, 23, 5), suf=(7, 301, 302, 303, 9, 11)):

@@ -4,6 +4,7 @@ only; submit() and transcribe_batch() agree with transcribe(); a model built wit
 import numpy as np
 import pytest
 
+from gpu_common import same_bits
 from sonicscribe_amd import fallback, spec, synth
 from sonicscribe_amd.asr import ASRModel
 
@@ -13,11 +14,6 @@ N_NEW, T, SEED0 = 12, 0.8, 2 ** 64 - 2      # (the third fork's seed wraps to 0)
 
 def wav(i, n):
     return synth.synth_pcm(i, n).astype(np.float32) / 32768.0
-
-
-def _same_bits(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.dtype == b.dtype == np.float32 and a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 @pytest.fixture(scope="module")
@@ -44,9 +40,9 @@ def test_the_winner_is_the_best_of_the_plain_decodes(model, plain):
     a = wav(31, 80000)
     info = model.transcribe(a, max_new_tokens=N_NEW, temperature=T, seed=SEED0, best_of=3, return_debug_info=True)
     assert (info["best_of"], info["fork_index"], info["temperature"]) == (3, j, T)
-    assert np.array_equal(info["token_ids"], plain[j].token_ids) and _same_bits(info["token_logprobs"], plain[j].token_logprobs) and info["transcript"] == plain[j].text
+    assert np.array_equal(info["token_ids"], plain[j].token_ids) and same_bits(info["token_logprobs"], plain[j].token_logprobs) and info["transcript"] == plain[j].text
     det = model.submit(a, max_new_tokens=N_NEW, detailed=True, temperature=T, seed=SEED0, best_of=3).result(timeout=120)      # submit() resolves to the same
-    assert np.array_equal(det.token_ids, plain[j].token_ids) and _same_bits(det.token_logprobs, plain[j].token_logprobs)
+    assert np.array_equal(det.token_ids, plain[j].token_ids) and same_bits(det.token_logprobs, plain[j].token_logprobs)
     assert (det.best_of, det.fork_index, det.attempts) == (3, j, 1) and det.fork_avg_logprobs.tolist() == avgs
     # the constructor's N is the default; two samples are the first two of three
     dflt = model.submit(a, max_new_tokens=N_NEW, detailed=True, temperature=T, seed=SEED0).result(timeout=120)
@@ -68,7 +64,7 @@ def test_the_ladder_forks_its_sampled_rung(model, plain):
     finally:
         model.logprob_threshold = keep
     assert (det.attempts, det.temperature, det.best_of, det.fork_index) == (2, T, 3, j)
-    assert np.array_equal(det.token_ids, plain[j].token_ids) and _same_bits(det.token_logprobs, plain[j].token_logprobs)
+    assert np.array_equal(det.token_ids, plain[j].token_ids) and same_bits(det.token_logprobs, plain[j].token_logprobs)
 
 
 def test_transcribe_batch_packs_forked_runs(model):

@@ -8,21 +8,14 @@ from dataclasses import replace
 import numpy as np
 import pytest
 
+from gpu_common import make_engine, prompt_for
 from sonicscribe_amd import spec, synth
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
-
-
-def prompt_for(d, n_samples):
-    return [1, 17, 23, 5] + [d.audio_token_id] * spec.audio_token_count(spec.valid_frames(n_samples)) + [7, 301, 302, 303, 9, 11]
 
 
 def make(d, max_batch, mode=0, max_ctx=512):
-    from sonicscribe_amd.engine import Engine
-    e = Engine(d, 0, mode, max_batch=max_batch, max_ctx=max_ctx)
-    e.load_synthetic(SEED)
-    return e
+    return make_engine(d, mode, max_batch, max_ctx)
 
 
 def drain(dec, rows, limit=2000):

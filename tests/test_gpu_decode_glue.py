@@ -13,7 +13,8 @@ import numpy as np
 import pytest
 
 import glue_ref as G
-from sonicscribe_amd import spec
+from gpu_common import bits, make_engine
+from sonicscribe_amd.engine import MODE_F16
 
 pytestmark = pytest.mark.gpu
 
@@ -24,18 +25,14 @@ EPS = 1e-5
 
 @pytest.fixture(scope="module")
 def eng():
-    from sonicscribe_amd.engine import Engine
-    e = Engine(spec.TINY, 0, max_batch=4, max_ctx=256)
-    e.load_synthetic(20260128)
+    e = make_engine(max_ctx=256)
     yield e
     e.close()
 
 
 @pytest.fixture(scope="module")
 def eng16():
-    from sonicscribe_amd.engine import Engine, MODE_F16
-    e = Engine(spec.TINY, 0, MODE_F16, max_batch=4, max_ctx=256)
-    e.load_synthetic(20260128)
+    e = make_engine(mode=MODE_F16, max_ctx=256)
     yield e
     e.close()
 
@@ -47,10 +44,6 @@ def E(eng, eng16):
     yield lambda kind: engines[kind]
     for e in engines.values():
         e.set_option("gu64_two_pass", 0); e.set_option("o64_16rows", 0)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
 
 
 def same(got, want, what):

@@ -5,44 +5,21 @@ the longest agreeing prefix is accepted and the unchanged head and greedy loop c
 Fixture margins (tests/golden/tiny_bf16.npz, checked in test_fixture_margins on the host side of this file): s1's greedy margins are 0.172 at step 0 and >= 0.859
 afterwards, s0's >= 0.219 over its first ten steps - above twice the 0.0625 logit tolerance the project holds the prefill and the step path to, so a draft of the
 fixture's own ids must be accepted in full whichever of the two paths decides a position."""
-import os
-
 import numpy as np
 import pytest
 
-from sonicscribe_amd import spec, synth
+from gpu_common import SEED, bits, flags, load_golden, make_engine
+from sonicscribe_amd import spec
 from sonicscribe_amd.genconfig import GenerationGuards
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
 TOL = 0.0625
 ALL3 = dict(repetition_penalty=1.3, no_repeat_ngram_size=2, suppress_tokens=[304, 10])      # tests/test_gpu_generation_guards.py: they bind on the fixture's rows
 
 
-def prompt_for(d, n):
-    return [1, 17, 23, 5] + [d.audio_token_id] * spec.audio_token_count(spec.valid_frames(n)) + [7, 301, 302, 303, 9, 11]
-
-
 def make(mode=0, max_batch=4, max_ctx=1024, lp=True, guards=None, draft=True, top=0, opts=()):
-    from sonicscribe_amd.engine import Engine
-    e = Engine(spec.TINY, 0, mode, max_batch=max_batch, max_ctx=max_ctx)
-    if lp:
-        e.set_option("token_logprobs", 1)
-    if top:
-        e.set_option("top_logprobs", top)
-    if guards:
-        e.set_generation(**guards)
-    for k, v in opts:
-        e.set_option(k, v)
-    if draft:
-        e.set_option("draft_verify", 1)
-    e.load_synthetic(SEED)
-    return e
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a, np.float32)
-    return a.view(np.uint32)
+    first = flags((lp, "token_logprobs", 1), (top, "top_logprobs", top), (guards, "generation", guards))
+    return make_engine(spec.TINY, mode, max_batch, max_ctx, first + list(opts) + flags((draft, "draft_verify", 1)))
 
 
 def _same(a, b):
@@ -50,15 +27,13 @@ def _same(a, b):
         return all(_same(x, y) for x, y in zip(a, b))
     a, b = np.asarray(a), np.asarray(b)
     if a.dtype == np.float32:
-        return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
+        return a.shape == b.shape and np.array_equal(bits(a), bits(b))
     return np.array_equal(a, b)
 
 
 @pytest.fixture(scope="module")
 def golden(golden_dir):
-    g = np.load(os.path.join(golden_dir, "tiny_bf16.npz"))
-    segs = [synth.synth_pcm(int(g[f"s{i}_seg_index"]), int(g[f"s{i}_n_samples"])) for i in range(2)]
-    prompts = [[int(t) for t in g[f"s{i}_prompt_ids"]] for i in range(2)]
+    g, segs, prompts = load_golden(golden_dir, int_prompts=True)
     return g, segs, prompts, int(g["n_new"])
 
 

@@ -6,17 +6,13 @@ of the processed scores and the record of the draft id: log_softmax(processed)[d
 The choice is exact: np.argmax(GenerationGuards.apply(row, history)), and the token greedy_kernel<T, ., true> picks for the same row on an ordinary handle.
 The record is held to the row kernel's derived bound (tests/test_gpu_score_kernel.py), evaluated over the processed scores: the guards add no
 term, since s * p, s / p (correctly rounded fp32) and -inf are the very values the float64 reference starts from."""
-import math
-
 import numpy as np
 import pytest
 
-from sonicscribe_amd import spec
+from gpu_common import flags, make_engine, ref_log_softmax, score_bound, slabs
 from sonicscribe_amd.genconfig import GenerationGuards
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
-U = 2.0 ** -24
 KINDS = {"bf16": 0, "fp16": 2}
 HLD = 40
 GUARDS = {"neutral": {}, "penalty": dict(repetition_penalty=1.5), "ngram1": dict(no_repeat_ngram_size=1), "ngram2": dict(no_repeat_ngram_size=2),
@@ -24,43 +20,16 @@ GUARDS = {"neutral": {}, "penalty": dict(repetition_penalty=1.5), "ngram1": dict
           "all3": dict(repetition_penalty=1.3, no_repeat_ngram_size=2, suppress_tokens=[5, 2])}
 
 
-def score_bound(V, ref64):
-    n_t = math.ceil(V / 16384) * 16
-    c = 3 * (math.ceil(n_t / 16) - 1) + 2 + 16 + 1
-    return (n_t + c + 2.25 * math.log(V)) * U + U * np.abs(ref64)
-
-
-def ref_log_softmax(row):
-    l = np.asarray(row, np.float64)
-    m = l.max()
-    return l - (m + np.log(np.exp(l - m).sum()))
-
-
 @pytest.fixture(scope="module", params=list(KINDS))
 def engs(request):
-    from sonicscribe_amd.engine import Engine
     out = []
     for draft in (1, 0):
-        e = Engine(spec.TINY, 0, KINDS[request.param], max_batch=2, max_ctx=512)
-        e.set_option("token_logprobs", 1)
-        if draft:
-            e.set_option("draft_verify", 1)
-        e.load_synthetic(SEED)
+        e = make_engine(mode=KINDS[request.param], max_batch=2, max_ctx=512, options=[("token_logprobs", 1)] + flags((draft, "draft_verify", 1)))
         e.kind = request.param
         out.append(e)
     yield out
     for e in out:
         e.close()
-
-
-def _slabs(rows, ks, mpad):
-    V = rows[0].shape[0]
-    w = {1: [1.0], 2: [0.5, 0.5], 3: [0.5, 0.25, 0.25]}[ks]              # exact splits
-    s = np.zeros((ks, mpad, V), np.float32)
-    for b, r in enumerate(rows):
-        for k in range(ks):
-            s[k, b] = r * np.float32(w[k])
-    return s
 
 
 def _bf16(x):
@@ -96,7 +65,7 @@ def _check(engs, V, B, ks, gname, seed, K=0):
     g = GenerationGuards(**guards)
     rows, hist, hlen = _case(V, B, seed)
     mpad = (B + 15) // 16 * 16
-    s = _slabs(rows, ks, mpad)
+    s = slabs(rows, ks, mpad)
     rng = np.random.default_rng(seed + 1)
     force = rng.integers(0, V, B).astype(np.int32)
     force[0] = 1                                                          # (a seen id on the rows that have a history)
@@ -106,7 +75,7 @@ def _check(engs, V, B, ks, gname, seed, K=0):
     # hold bf16 values, which fp16 represents exactly)
     for b0 in range(0, B, 64):
         n = min(64, B - b0)
-        tok_g, raw_g, _ = plain.test_greedy_guard(_slabs(rows[b0:b0 + n], ks, (n + 15) // 16 * 16), n, hist[b0:b0 + n], hlen[b0:b0 + n], want_lp=True, **guards)
+        tok_g, raw_g, _ = plain.test_greedy_guard(slabs(rows[b0:b0 + n], ks, (n + 15) // 16 * 16), n, hist[b0:b0 + n], hlen[b0:b0 + n], want_lp=True, **guards)
         assert np.array_equal(raw_g.view(np.uint32), raw[b0:b0 + n].view(np.uint32)), "both kernels read the same rows"
         assert np.array_equal(tok_g, tok[b0:b0 + n]), (ev.kind, V, B, gname, "verify kernel and greedy kernel disagree")
     worst = 0.0
@@ -166,7 +135,7 @@ def test_every_id_banned_gives_token_zero(engs):
     ev = engs[0]
     V = 8
     rows = [np.linspace(-1, 1, V).astype(np.float32)]
-    tok, raw, lp = ev.test_greedy_guard(_slabs(rows, 1, 16), 1, np.zeros((1, HLD), np.int32), np.zeros(1, np.int32), force_ids=np.array([3], np.int32), want_lp=True,
+    tok, raw, lp = ev.test_greedy_guard(slabs(rows, 1, 16), 1, np.zeros((1, HLD), np.int32), np.zeros(1, np.int32), force_ids=np.array([3], np.int32), want_lp=True,
                                         suppress_tokens=list(range(V)))
     assert int(tok[0]) == 0 and not np.isfinite(lp[0])                    # torch.argmax of equal values; no finite score to normalise by
 
@@ -181,7 +150,7 @@ def test_unaligned_rows_take_the_same_order(engs):
     rows = [row, row, row]
     hist = np.tile(np.arange(HLD, dtype=np.int32) % 7, (3, 1)); hlen = np.full(3, HLD, np.int32)
     force = np.full(3, 5, np.int32)
-    tok, raw, lp = ev.test_greedy_guard(_slabs(rows, 1, 16), 3, hist, hlen, force_ids=force, want_lp=True, **GUARDS["all3"])
+    tok, raw, lp = ev.test_greedy_guard(slabs(rows, 1, 16), 3, hist, hlen, force_ids=force, want_lp=True, **GUARDS["all3"])
     assert tok[0] == tok[1] == tok[2] and len(set(lp.view(np.uint32).tolist())) == 1
     proc = GenerationGuards(**GUARDS["all3"]).apply(raw[1], hist[1])
     assert int(tok[1]) == int(np.argmax(proc))
@@ -201,7 +170,7 @@ def test_same_bits_whatever_the_batch(engs):
         hist = np.zeros((B, HLD), np.int32); hlen = np.zeros(B, np.int32)
         hist[at] = h; hlen[at] = HLD
         force = np.full(B, 7, np.int32); force[at] = 321
-        tok, _, lp = ev.test_greedy_guard(_slabs(rows, 1, (B + 15) // 16 * 16), B, hist, hlen, force_ids=force, want_lp=True, **GUARDS["all3"])
+        tok, _, lp = ev.test_greedy_guard(slabs(rows, 1, (B + 15) // 16 * 16), B, hist, hlen, force_ids=force, want_lp=True, **GUARDS["all3"])
         return int(tok[at]), int(lp[at:at + 1].view(np.uint32)[0])
     assert rec([row], 0) == rec(others[:2] + [row], 2) == rec(others + [row], 64)
 

@@ -7,7 +7,9 @@ hundreds of nats above everything before it."""
 import numpy as np
 import pytest
 
-from sonicscribe_amd import spec, synth
+from gpu_common import load_oracle, make_engine
+from sonicscribe_amd import synth
+from sonicscribe_amd.engine import MODE_F16
 
 pytestmark = pytest.mark.gpu
 
@@ -18,9 +20,7 @@ def bf(x):
 
 @pytest.fixture(scope="module")
 def eng():
-    from sonicscribe_amd.engine import Engine
-    e = Engine(spec.TINY, 0, max_batch=4, max_ctx=256)
-    e.load_synthetic(20260128)
+    e = make_engine(max_ctx=256)
     yield e
     e.set_option("flash_enc", 1)
     e.close()
@@ -28,17 +28,14 @@ def eng():
 
 @pytest.fixture(scope="module")
 def eng16():
-    from sonicscribe_amd.engine import Engine, MODE_F16
-    e = Engine(spec.TINY, 0, MODE_F16, max_batch=4, max_ctx=256)
-    e.load_synthetic(20260128)
+    e = make_engine(mode=MODE_F16, max_ctx=256)
     yield e
     e.close()
 
 
 @pytest.fixture(scope="module")
 def orc():
-    from oracle import oracle
-    return oracle
+    return load_oracle()
 
 
 def ref_attention(orc, q, k, v):

@@ -3,33 +3,31 @@ row of a forked run is the solo run of its (audio, temperature, seed) - ids, log
 guards, per-row bias tables and grammars, after a splice; the refusals by name; fork_kv_kernel's copy read back from the cache, element by element."""
 import ctypes
 import dataclasses
+from functools import partial
 
 import numpy as np
 import pytest
 
+import gpu_common
+from gpu_common import SEED, flags, make_engine, same_bits, six
 from sonicscribe_amd import spec, synth
 from sonicscribe_amd.engine import Engine, SonicError
 from sonicscribe_amd.grammar import Grammar
 from sonicscribe_amd.reqbias import RequestBias
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
 D = spec.TINY
 EOS = list(D.eos_ids)
 FORKS = [3, 1, 2]
 BUDGETS = [14, 20, 9]
 # one (temperature, seed) per ROW, in the order of Engine.fork_rows(FORKS) = [[0, 3, 4], [1], [2, 5]]
 SAMP = [(0.0, 1), (0.9, 12), (1.0, 0x123456789ABCDEF0), (0.8, 21), (1.2, 22), (0.7, 33)]
-
-
-def prompt_for(n_samples_per_window):
-    n = sum(spec.audio_token_count(spec.valid_frames(s)) for s in n_samples_per_window)
-    return [1, 17, 23, 5] + [D.audio_token_id] * n + [7, 301, 302, 303, 9, 11]
+prompt_for = partial(gpu_common.prompt_for, D)      # (window lengths of one request)
 
 
 def audios():
-    """three requests as in tests/test_gpu_sampling.py::_six, the second one of two windows: (windows per request, prompts, req_win)"""
-    seg = [synth.synth_pcm(700 + i, n) for i, n in enumerate((48000, 200000, 80000, 64000, 120000, 96000))]
+    """three requests from gpu_common.six, the second one of two windows: (windows per request, prompts, req_win)"""
+    seg = six()[0]
     wins = [[seg[0]], [seg[2], seg[3]], [seg[4]]]
     return wins, [prompt_for([len(w) for w in ws]) for ws in wins]
 
@@ -41,22 +39,8 @@ def flat(wins):
 
 
 def make(bias=False, grammar=False, guards=None):
-    e = Engine(D, 0, 0, max_batch=8, max_ctx=1024)
-    e.set_option("token_logprobs", 1)
-    e.set_option("sampling", 1)
-    if bias:
-        e.set_option("request_bias", 1)
-    if grammar:
-        e.set_option("grammar", 1)
-    if guards:
-        e.set_generation(**guards)
-    e.load_synthetic(SEED)
-    return e
-
-
-def _same_bits(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.dtype == b.dtype == np.float32 and a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    return make_engine(D, 0, 8, 1024, [("token_logprobs", 1), ("sampling", 1)]
+                       + flags((bias, "request_bias", 1), (grammar, "grammar", 1), (guards, "generation", guards)))
 
 
 def row_source():
@@ -94,9 +78,9 @@ def check_rows(got_ids, got_lp, want, got_logits=None, what=""):
     assert len(got_ids) == len(want) == sum(FORKS)
     for r, (ids, lg, lp) in enumerate(want):
         assert np.array_equal(got_ids[r], ids), (what, r, got_ids[r].tolist(), ids.tolist())
-        assert _same_bits(got_lp[r], lp), (what, r)
+        assert same_bits(got_lp[r], lp), (what, r)
         if got_logits is not None:
-            assert _same_bits(got_logits[:len(ids), r], lg), (what, r)
+            assert same_bits(got_logits[:len(ids), r], lg), (what, r)
 
 
 @pytest.fixture(scope="module")
@@ -126,7 +110,7 @@ def test_rows_equal_their_solo_runs(eng, solo):
     assert lg_e.shape == (max(BUDGETS), 6, D.vocab)
     check_rows(ids_e, lp_e, solo, lg_e, what="eager")
     # the forks of one audio are drawn from the same first logits
-    assert _same_bits(lg_e[0, 0], lg_e[0, 3]) and _same_bits(lg_e[0, 0], lg_e[0, 4]) and _same_bits(lg_e[0, 2], lg_e[0, 5])
+    assert same_bits(lg_e[0, 0], lg_e[0, 3]) and same_bits(lg_e[0, 0], lg_e[0, 4]) and same_bits(lg_e[0, 2], lg_e[0, 5])
 
 
 # ------------------------------------------------------------------------------------------ 2. guards, per-row bias tables, grammars
@@ -150,7 +134,7 @@ def test_guards_bias_and_grammars_per_row():
         ref = [e.transcribe_batch(wins[0], [prompts[0]], [12], want_logprobs=True, request_sampling=[samp2[j]], request_grammar=[g]) for j, g in enumerate((da, db))]
         ids, _, lps = e.transcribe_batch(wins[0], [prompts[0]], [12], want_logprobs=True, request_sampling=samp2, request_grammar=[da, db], forks=[2])
         for j, g in enumerate((ga, gb)):
-            assert np.array_equal(ids[j], ref[j][0][0]) and _same_bits(lps[j], ref[j][2][0]), j
+            assert np.array_equal(ids[j], ref[j][0][0]) and same_bits(lps[j], ref[j][2][0]), j
             assert g.walk(ids[j]) == "accepted", (j, ids[j])
         da.close(); db.close()                                   # every row has ended and was fetched: nothing refers to the grammars
     finally:
@@ -168,7 +152,7 @@ def test_capacity_and_refusals(eng):
     one = lambda **kw: eng.transcribe_batch(wins[0], [prompts[0]], [6], want_logprobs=True, **kw)
     base = _plain(eng)
     ids, _, lp = one(forks=[8])                                  # R' == max_batch
-    assert len(ids) == 8 and all(np.array_equal(i, base[0][0]) for i in ids) and all(_same_bits(x, base[2][0]) for x in lp)
+    assert len(ids) == 8 and all(np.array_equal(i, base[0][0]) for i in ids) and all(same_bits(x, base[2][0]) for x in lp)
     # the wrapper validates before anything is armed
     for bad, kw in (("9 rows", dict(forks=[9])), ("at least 1", dict(forks=[0])), ("2 counts", dict(forks=[1, 1])), ("request_sampling", dict(forks=[2], request_sampling=[(0.5, 1)])),
                     ("drafts", dict(forks=[2], request_draft=[[5]]))):
@@ -197,7 +181,7 @@ def test_capacity_and_refusals(eng):
     with pytest.raises(ValueError, match="do not match"):
         eng.transcribe_batch(wins[0], [prompts[0][:-8]], [6])
     again = _plain(eng)
-    assert len(again[0]) == 1 and np.array_equal(again[0][0], base[0][0]) and _same_bits(again[2][0], base[2][0])
+    assert len(again[0]) == 1 and np.array_equal(again[0][0], base[0][0]) and same_bits(again[2][0], base[2][0])
     # the kinds and handles that have no forks
     for mode, text in ((1, "int8"), (3, "fp32")):
         k = Engine(D, 0, mode, max_batch=2, max_ctx=1024)
@@ -251,7 +235,7 @@ def test_forked_prefill_spliced(eng, solo):
                 break
         assert len(got) == len(want)
         for dst, src in want.items():
-            assert np.array_equal(got[dst][0], solo[src][0]) and _same_bits(got[dst][1], solo[src][2]), (dst, src)
+            assert np.array_equal(got[dst][0], solo[src][0]) and same_bits(got[dst][1], solo[src][2]), (dst, src)
     finally:
         eng.service_end()
         pre.close()
@@ -329,7 +313,7 @@ def test_counts_of_one_are_no_counts(eng, solo):
     a = eng.transcribe_batch(segs, prompts, BUDGETS, req_win=rw, want_logits=True, want_logprobs=True, request_sampling=samp)
     b = eng.transcribe_batch(segs, prompts, BUDGETS, req_win=rw, want_logits=True, want_logprobs=True, request_sampling=samp, forks=[1, 1, 1])
     for r in range(3):
-        assert np.array_equal(a[0][r], b[0][r]) and _same_bits(a[2][r], b[2][r]) and _same_bits(a[1][:len(a[0][r]), r], b[1][:len(a[0][r]), r])
+        assert np.array_equal(a[0][r], b[0][r]) and same_bits(a[2][r], b[2][r]) and same_bits(a[1][:len(a[0][r]), r], b[1][:len(a[0][r]), r])
         assert np.array_equal(a[0][r], solo[r][0])
     forked(eng, SAMP, False)
     assert eng.memory_info() == mem

@@ -15,19 +15,15 @@ from dataclasses import replace
 import numpy as np
 import pytest
 
+from gpu_common import SEED, prompt_for
 from sonicscribe_amd import frontend, spec, synth
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
 
 
 def f16_ulp(x):
     x = np.maximum(np.abs(np.asarray(x, np.float64)), 2.0 ** -14)
     return 2.0 ** (np.floor(np.log2(x)) - 10)
-
-
-def prompt_for(d, n):
-    return [1, 17, 23, 5] + [d.audio_token_id] * spec.audio_token_count(spec.valid_frames(n)) + [7, 301, 302, 303, 9, 11]
 
 
 def check(tag, hip, o16, o32, ulps16, abs32):

@@ -10,10 +10,10 @@ from dataclasses import replace
 import numpy as np
 import pytest
 
+from gpu_common import SEED, make_engine
 from sonicscribe_amd import frontend, spec, synth
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
 FACTOR = 1.25
 
 
@@ -28,9 +28,7 @@ def closer_than_reference_bf16(name, hip, g32, g16):
 
 @pytest.fixture(scope="module")
 def eng():
-    from sonicscribe_amd.engine import Engine
-    e = Engine(spec.TINY, 0, max_batch=4, max_ctx=1024)
-    e.load_synthetic(SEED)
+    e = make_engine()
     yield e
     e.close()
 

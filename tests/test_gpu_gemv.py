@@ -12,15 +12,10 @@ from dataclasses import replace
 import numpy as np
 import pytest
 
+from gpu_common import SEED, prompt_for
 from sonicscribe_amd import spec, synth
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
-
-
-def prompt_for(d, n, tail=()):
-    return [1, 17, 23, 5] + [d.audio_token_id] * spec.audio_token_count(spec.valid_frames(n)) + [7, 301, 302, 303, 9, 11] + list(tail)
-
 
 FULLW = replace(spec.FULL, enc_layers=1, dec_layers=2, vocab=1024, audio_token_id=1000, eos_ids=())     # full-width layers (the shapes the GEMV chain is built for), shallow
 

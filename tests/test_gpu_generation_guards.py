@@ -1,60 +1,24 @@
 """Generation guards on the GPU (sonic_set_generation; greedy_kernel<T, LP, true>): HF's repetition_penalty, no_repeat_ngram_size and
 suppress_tokens inside the greedy kernel.  The reference is sonicscribe_amd.genconfig.GenerationGuards.apply, which tests/test_generation_guards_host.py
 holds bit for bit against HF's own processors: the emitted token must be np.argmax (first maximum) of apply(raw logits the kernel dumped, history),
-exactly.  Log-probabilities are held to DESIGN.md 6.3's derived bound (tests/test_gpu_logprobs.py lp_bound), evaluated over the processed scores."""
+exactly.  Log-probabilities are held to DESIGN.md 6.3's derived bound (tests/gpu_common.py lp_bound), evaluated over the processed scores."""
 import json
-import math
 import os
 
 import numpy as np
 import pytest
 
+from gpu_common import SEED, check_lp, flags, load_golden, make_engine, prompt_for, same_bits, slabs
 from sonicscribe_amd import spec, synth
 from sonicscribe_amd.genconfig import GenerationGuards
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
-U = 2.0 ** -24
 ALL3 = dict(repetition_penalty=1.3, no_repeat_ngram_size=2, suppress_tokens=[304, 10])
 PENALTY_THAT_BINDS = 1.5            # on tiny_bf16.npz both rows leave the fixture's ids at the second token (1.2 moves s0 only, 1.1 at step 10)
 
 
-def lp_bound(V, ref64):
-    n_t = math.ceil(V / 4096) * 4
-    c = 3 * (math.ceil(n_t / 16) - 1) + 2 + 16 + 1
-    return (n_t + c + 2.25 * math.log(V)) * U + U * np.abs(ref64)
-
-
-def ref_logprob(scores, tok):
-    l = np.asarray(scores, np.float64)
-    m = l.max()
-    return l[int(tok)] - (m + np.log(np.exp(l - m).sum()))
-
-
-def check_lp(tag, lp, processed, tok):
-    """lp against the float64 log-softmax of the processed scores at tok; a banned token: exactly -inf (HF's value)"""
-    if np.isneginf(processed[int(tok)]):
-        assert np.isneginf(lp), (tag, lp)
-        return 0.0
-    ref = ref_logprob(processed, tok)
-    ratio = abs(float(lp) - ref) / lp_bound(len(processed), ref)
-    assert np.isfinite(lp) and ratio <= 1.0, (tag, float(lp), ref, ratio)
-    return ratio
-
-
-def prompt_for(d, n):
-    return [1, 17, 23, 5] + [d.audio_token_id] * spec.audio_token_count(spec.valid_frames(n)) + [7, 301, 302, 303, 9, 11]
-
-
 def make(d=spec.TINY, mode=0, max_batch=4, max_ctx=1024, lp=False, guards=None):
-    from sonicscribe_amd.engine import Engine
-    e = Engine(d, 0, mode, max_batch=max_batch, max_ctx=max_ctx)
-    if lp:
-        e.set_option("token_logprobs", 1)
-    if guards:
-        e.set_generation(**guards)
-    e.load_synthetic(SEED)
-    return e
+    return make_engine(d, mode, max_batch, max_ctx, flags((lp, "token_logprobs", 1), (guards, "generation", guards)))
 
 
 @pytest.fixture(scope="module")
@@ -66,23 +30,11 @@ def eng():
 
 @pytest.fixture(scope="module")
 def golden(golden_dir):
-    g = np.load(os.path.join(golden_dir, "tiny_bf16.npz"))
-    segs = [synth.synth_pcm(int(g[f"s{i}_seg_index"]), int(g[f"s{i}_n_samples"])) for i in range(2)]
-    prompts = [[int(t) for t in g[f"s{i}_prompt_ids"]] for i in range(2)]
+    g, segs, prompts = load_golden(golden_dir, int_prompts=True)
     return g, segs, prompts, int(g["n_new"])
 
 
 # ------------------------------------------------------------------------------------------ 1. the kernel hook, exact
-def _slabs(rows, ks, mpad=16):
-    V = rows[0].shape[0]
-    w = {1: [1.0], 2: [0.5, 0.5], 3: [0.5, 0.25, 0.25]}[ks]
-    s = np.zeros((ks, mpad, V), np.float32)
-    for b, r in enumerate(rows):
-        for k in range(ks):
-            s[k, b] = r * np.float32(w[k])
-    return s
-
-
 def _ids(V):
     """A: in row 1's history (the last id: the last partial vector at V = 16388); C: in no history; Z: continuation of (x, y); S: suppressed; A2 < C: in row 2's history"""
     return dict(A=V - 1, C=V // 2, Z=V - 2, x=1, y=2, S=V - 3, A2=3)
@@ -100,7 +52,7 @@ def _histories(V, rng):
 
 
 def _check_rows(eng, V, ks, rows, hist, hlen, guards, want_lp=False, force=None, tag=""):
-    s = _slabs(rows, ks)
+    s = slabs(rows, ks)
     tok, raw, lp = eng.test_greedy_guard(s, 3, hist, hlen, force_ids=force, want_lp=want_lp, **guards)
     tok0, raw0 = eng.test_greedy(s, 3, want_logits=True)
     assert np.array_equal(raw.view(np.uint32), raw0.view(np.uint32)), (tag, "the dump is the raw logits")
@@ -218,10 +170,6 @@ def test_end_to_end_eager(golden, name):
 
 
 # ------------------------------------------------------------------------------------------ 3. the same bits on every path
-def _same_bits(a, b):
-    return a.dtype == b.dtype == np.float32 and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 def test_invariance_engine_paths():
     d = spec.TINY
     segs = [synth.synth_pcm(700 + i, n) for i, n in enumerate((48000, 200000, 80000))]
@@ -240,8 +188,8 @@ def test_invariance_engine_paths():
         assert lg is None and e.timings()["host_decode_launches"] < max(budgets) - 1
         ids1, _, lp1 = e.transcribe_batch([segs[2]], [prompts[2]], [budgets[2]], want_logprobs=True)                     # alone vs row 2 of 3
         for r in range(3):
-            assert np.array_equal(ids3[r], ids_e[r]) and _same_bits(lp3[r], lp_e[r]), r
-        assert np.array_equal(ids1[0], ids3[2]) and _same_bits(lp1[0], lp3[2])
+            assert np.array_equal(ids3[r], ids_e[r]) and same_bits(lp3[r], lp_e[r]), r
+        assert np.array_equal(ids1[0], ids3[2]) and same_bits(lp1[0], lp3[2])
         # spliced into a continuous loop mid-flight: the history travels with the row
         pre = e.slot()
         assert pre.get_generation() == e.get_generation()
@@ -265,7 +213,7 @@ def test_invariance_engine_paths():
                     break
             assert len(got) == 3
             for row, req in rows.items():
-                assert np.array_equal(got[row][0], ids3[req]) and _same_bits(got[row][1], lp3[req]), (row, req)
+                assert np.array_equal(got[row][0], ids3[req]) and same_bits(got[row][1], lp3[req]), (row, req)
         finally:
             e.service_end()
             pre.close()
@@ -291,12 +239,12 @@ def test_invariance_native_dispatcher_and_bulk_pipeline():
         res = [f.result(timeout=60) for f in [disp.submit([segs[i]], prompts[i], budgets[i], want_logprobs=True) for i in range(3)]]
         disp.close()
         for i in range(3):
-            assert np.array_equal(res[i][0], solo[i][0][0]) and _same_bits(res[i][1], solo[i][2][0]), i
+            assert np.array_equal(res[i][0], solo[i][0][0]) and same_bits(res[i][1], solo[i][2][0]), i
         bulk = Dispatcher([e], slots=[slots], bulk=True, decoders=1)
         res = [f.result(timeout=60) for f in [bulk.submit([segs[i]], prompts[i], budgets[i], want_logprobs=True) for i in range(3)]]
         bulk.close()
         for i in range(3):
-            assert np.array_equal(res[i][0], solo[i][0][0]) and _same_bits(res[i][1], solo[i][2][0]), i
+            assert np.array_equal(res[i][0], solo[i][0][0]) and same_bits(res[i][1], solo[i][2][0]), i
     finally:
         e.close(); plain.close()
 
@@ -369,7 +317,7 @@ def test_off_is_off_and_refusals(golden):
         got = off.transcribe_batch(segs, prompts, [n_new, n_new], want_logprobs=True)
         a0 = off.memory_info()[0]
         for si in range(2):
-            assert np.array_equal(got[0][si], want[0][si]) and _same_bits(got[2][si], want[2][si])
+            assert np.array_equal(got[0][si], want[0][si]) and same_bits(got[2][si], want[2][si])
         assert plain.memory_info()[0] == a0                                          # nothing was allocated for the neutral values
         # on, then back to the neutral values: the plain run's bits again
         off.set_generation(1.3, 2, [304])
@@ -379,7 +327,7 @@ def test_off_is_off_and_refusals(golden):
         off.set_generation(1.0, 0, [])
         got = off.transcribe_batch(segs, prompts, [n_new, n_new], want_logprobs=True)
         for si in range(2):
-            assert np.array_equal(got[0][si], want[0][si]) and _same_bits(got[2][si], want[2][si])
+            assert np.array_equal(got[0][si], want[0][si]) and same_bits(got[2][si], want[2][si])
         # refusals: values out of range
         V = spec.TINY.vocab
         for bad in ((0.0, 0, []), (-1.0, 0, []), (float("inf"), 0, []), (float("nan"), 0, []), (1.1, -1, []), (1.1, 65, []), (1.1, 0, [V]), (1.1, 0, [-1]),

@@ -4,18 +4,16 @@ the refusals; HF generate(prefix_allowed_tokens_fn=...) on the CPU against the f
 
 The synthetic model's free-running transcript repeats one id (304 or 10, tests/golden/tiny_bf16.npz) and never ends: none of the grammars below contains it."""
 import itertools
-import os
 
 import numpy as np
 import pytest
 
+from gpu_common import SEED, check_lp, flags, load_golden, make_engine, prompt_for, same_bits, six
 from sonicscribe_amd import spec, synth
 from sonicscribe_amd.genconfig import GenerationGuards
 from sonicscribe_amd.grammar import Grammar
-from test_gpu_request_bias import _same_bits, check_lp, prompt_for  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
 D = spec.TINY
 EOS = list(D.eos_ids)
 LEVELS = ([205, 411, 500], [206, 412, 501], [207, 413, 502], [208, 414, 503], [209, 415, 504])
@@ -32,14 +30,7 @@ def grammar_b():
 
 
 def make(mode=0, max_batch=8, grammar=True, lp=True):
-    from sonicscribe_amd.engine import Engine
-    e = Engine(D, 0, mode, max_batch=max_batch, max_ctx=1024)
-    if lp:
-        e.set_option("token_logprobs", 1)
-    if grammar:
-        e.set_option("grammar", 1)
-    e.load_synthetic(SEED)
-    return e
+    return make_engine(D, mode, max_batch, 1024, flags((lp, "token_logprobs", 1), (grammar, "grammar", 1)))
 
 
 def masked(raw, hist, g, state):
@@ -64,9 +55,7 @@ def identity(ids, logits, prompts, grams, budgets, lps=None):
 
 @pytest.fixture(scope="module")
 def golden(golden_dir):
-    g = np.load(os.path.join(golden_dir, "tiny_bf16.npz"))
-    segs = [synth.synth_pcm(int(g[f"s{i}_seg_index"]), int(g[f"s{i}_n_samples"])) for i in range(2)]
-    prompts = [[int(t) for t in g[f"s{i}_prompt_ids"]] for i in range(2)]
+    g, segs, prompts = load_golden(golden_dir, int_prompts=True)
     return g, segs, prompts, int(g["n_new"])
 
 
@@ -100,10 +89,7 @@ def test_every_step_is_the_masked_argmax(golden, mode):
 
 # ------------------------------------------------------------------------------------------ 2. the same bits on every path
 def _six():
-    segs = [synth.synth_pcm(700 + i, n) for i, n in enumerate((48000, 200000, 80000, 64000, 120000, 96000))]
-    prompts = [prompt_for(D, len(s)) for s in segs]
-    budgets = [9, 17, 11, 3, 13, 7]
-    return segs, prompts, budgets
+    return six() + ([9, 17, 11, 3, 13, 7],)
 
 
 def test_invariance_all_paths():
@@ -130,9 +116,9 @@ def test_invariance_all_paths():
         slot = e.slot()                                                                                                                     # a batch slot
         ids_s, _, lp_s = slot.transcribe_batch(segs, prompts, budgets, want_logprobs=True, request_grammar=dev)
         for r in range(6):
-            assert np.array_equal(ids_g[r], ids_e[r]) and _same_bits(lp_g[r], lp_e[r]), r
-            assert np.array_equal(solo[r][0][0], ids_e[r]) and _same_bits(solo[r][2][0], lp_e[r]), r
-            assert np.array_equal(ids_s[r], ids_e[r]) and _same_bits(lp_s[r], lp_e[r]), r
+            assert np.array_equal(ids_g[r], ids_e[r]) and same_bits(lp_g[r], lp_e[r]), r
+            assert np.array_equal(solo[r][0][0], ids_e[r]) and same_bits(solo[r][2][0], lp_e[r]), r
+            assert np.array_equal(ids_s[r], ids_e[r]) and same_bits(lp_s[r], lp_e[r]), r
         slot.close()
         # prefill, then splice into a continuous handle: reference and state travel with the row.  Rows 0, 1, 2 of the loop are neighbours: grammar A, grammar B and a
         # free row; the second prefill's rows land beside them in another order than they were prefilled in
@@ -157,7 +143,7 @@ def test_invariance_all_paths():
                     break
             assert len(got) == 6
             for row, req in rows.items():
-                assert np.array_equal(got[row][0], ids_e[req]) and _same_bits(got[row][1], lp_e[req]), (row, req)
+                assert np.array_equal(got[row][0], ids_e[req]) and same_bits(got[row][1], lp_e[req]), (row, req)
         finally:
             e.service_end()
             pre.close()
@@ -172,7 +158,7 @@ def test_invariance_all_paths():
             for s in slots:
                 s.close()
             for i in range(6):
-                assert np.array_equal(res[i][0], ids_e[i]) and _same_bits(res[i][1], lp_e[i]), (native, i)
+                assert np.array_equal(res[i][0], ids_e[i]) and same_bits(res[i][1], lp_e[i]), (native, i)
         # the batch dispatcher (no continuous loop)
         slots = [e.slot()]
         disp = Dispatcher([e], slots=[slots], continuous=False)
@@ -180,7 +166,7 @@ def test_invariance_all_paths():
         disp.close()
         slots[0].close()
         for i in range(6):
-            assert np.array_equal(res[i][0], ids_e[i]) and _same_bits(res[i][1], lp_e[i]), ("batch dispatcher", i)
+            assert np.array_equal(res[i][0], ids_e[i]) and same_bits(res[i][1], lp_e[i]), ("batch dispatcher", i)
         ca.close(); cb.close()                                   # straight after the last result: every row that referred to them was fetched, handed over or has ended
     finally:
         e.close()
@@ -202,7 +188,7 @@ def test_model_entry_points_and_streams():
         free = m.transcribe(wav, max_new_tokens=12, return_debug_info=True)
         assert "grammar_status" not in free and ca.grammar.walk(free["token_ids"]) == "left"
         det = m.submit(wav, max_new_tokens=12, detailed=True, grammar=ca).result(timeout=120)
-        assert det.grammar_status == "accepted" and np.array_equal(det.token_ids, info["token_ids"]) and _same_bits(det.token_logprobs, info["token_logprobs"])
+        assert det.grammar_status == "accepted" and np.array_equal(det.token_ids, info["token_ids"]) and same_bits(det.token_logprobs, info["token_logprobs"])
         short = m.submit(wav, max_new_tokens=3, detailed=True, grammar=ca).result(timeout=120)
         assert short.grammar_status == "incomplete" and np.array_equal(short.token_ids, det.token_ids[:3])
         assert m.transcribe(wav, max_new_tokens=12, grammar=ca) == info["transcript"]
@@ -220,10 +206,10 @@ def test_model_entry_points_and_streams():
                 st.add_audio_chunk(raw[o:o + 2048])
             sd = st.submit_chunks(0, st.next_chunk_id - 1, max_new_tokens=12, detailed=True, grammar=ca).result(timeout=120)
             assert sd.grammar_status == "accepted" and ca.grammar.walk(sd.token_ids) == "accepted"
-            assert np.array_equal(sd.token_ids, det.token_ids) and _same_bits(sd.token_logprobs, det.token_logprobs), "the stream's decode is submit()'s, bit for bit"
+            assert np.array_equal(sd.token_ids, det.token_ids) and same_bits(sd.token_logprobs, det.token_logprobs), "the stream's decode is submit()'s, bit for bit"
             first, n = st.chunk_range_samples(0, st.next_chunk_id - 1)
             ss = st.submit_samples(first, n, max_new_tokens=12, detailed=True, grammar=ca).result(timeout=120)
-            assert np.array_equal(ss.token_ids, sd.token_ids) and _same_bits(ss.token_logprobs, sd.token_logprobs)
+            assert np.array_equal(ss.token_ids, sd.token_ids) and same_bits(ss.token_logprobs, sd.token_logprobs)
         finally:
             st.close()
         assert m.get_model_info()["grammar"] is True

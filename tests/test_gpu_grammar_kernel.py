@@ -15,16 +15,15 @@ and 59264 (the production vocabulary); 1, 2 and 3 slabs."""
 import numpy as np
 import pytest
 
-from sonicscribe_amd import spec
+from gpu_common import SEED, check_lp, make_engine, same_bits, slabs
 from sonicscribe_amd.genconfig import GenerationGuards
 from sonicscribe_amd.grammar import Grammar
 from sonicscribe_amd.reqbias import RequestBias
-from test_gpu_request_bias import _histories, _slabs, check_lp  # noqa: E402
-from test_gpu_sampling_kernel import bf16_exact, same_bits, select  # noqa: E402
+from test_gpu_request_bias import _histories  # noqa: E402
+from test_gpu_sampling_kernel import bf16_exact, select  # noqa: E402
 from test_gpu_top_logprobs_kernel import check_alternatives  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
 B = 4
 NEG = np.float32("-inf")
 SIZES = (8, 1000, 16388, 59264)
@@ -36,15 +35,12 @@ GUARDS = dict(repetition_penalty=1.3, no_repeat_ngram_size=2)
 
 @pytest.fixture(scope="module")
 def engines():
-    from sonicscribe_amd.engine import Engine
     es = {}
 
     def get(mode, topk=0):
         if mode not in es:
-            e = Engine(spec.TINY, 0, mode, max_batch=B, max_ctx=1024)      # the hook takes everything but top_logprobs as arguments
-            e.load_synthetic(SEED)
-            e.set_option("token_logprobs", 1)
-            es[mode] = e
+            es[mode] = make_engine(mode=mode, max_batch=B)                 # the hook takes everything but top_logprobs as arguments
+            es[mode].set_option("token_logprobs", 1)
         es[mode].set_option("top_logprobs", topk)
         return es[mode]
     yield get
@@ -99,7 +95,7 @@ def test_masked_argmax_lp_and_state(engines, cases, V, mode):
     guards = GenerationGuards(**GUARDS, suppress_tokens=[int(kids[1])])
     tables = [RequestBias([[[int(kids[0])], 1.5]]), None, RequestBias([[[int(kids[-1])], 0.75], [[outside[0]], 3.0]], bad_words_ids=[[int(kids[2])]]), RequestBias([[[eos[0]], 0.5]])]
     for ks in (1, 2, 3):
-        s = _slabs(rows, ks)
+        s = slabs(rows, ks)
         for fam, tb in (("guard", None), ("bias", tables)):
             tok, raw, lp, _, so = eng.test_greedy_grammar(s, B, g, STATES, eos, hist=hist, hist_len=hlen, tables=tb, suppress_tokens=[int(kids[1])], **GUARDS)
             for b in range(B):
@@ -127,7 +123,7 @@ def test_alternatives_over_the_masked_scores(engines, cases, V, mode):
     tables = [None, RequestBias([[[one], -1.0]]), RequestBias([[[int(kids[1])], 2.0]]), None]
     for ks in (1, 2, 3):
         for fam, tb in (("guard", None), ("bias", tables)):
-            tok, raw, lp, _, so = eng.test_greedy_grammar(_slabs(rows, ks), B, g, STATES, eos, hist=hist, hist_len=hlen, tables=tb, **GUARDS)
+            tok, raw, lp, _, so = eng.test_greedy_grammar(slabs(rows, ks), B, g, STATES, eos, hist=hist, hist_len=hlen, tables=tb, **GUARDS)
             for b in range(B):
                 m = masked(g, eos, raw[b], hist[b, :hlen[b]], tb[b] if tb else None, guards, STATES[b])
                 check_alternatives((fam, V, mode, ks, b), m, lp.top_logprobs[b], lp.top_ids[b], 8)
@@ -143,7 +139,7 @@ def test_forced_ids_and_rows_with_every_allowed_id_banned(engines, cases, V, mod
     eng = engines(mode)
     g, eos, rows, hist, hlen, kids, outside, one = cases(V)
     for ks in (1, 2, 3):
-        s = _slabs(rows, ks)
+        s = slabs(rows, ks)
         # a forced id outside the grammar: the state is -2 and the id's masked score -inf; inside it: the edge is followed
         off = np.array([outside[0], outside[1], outside[0], int(kids[0])], np.int32)
         tok, raw, lp, _, so = eng.test_greedy_grammar(s, B, g, STATES, eos, hist=hist, hist_len=hlen, force_ids=off)
@@ -175,7 +171,7 @@ def test_sampling_draws_from_the_masked_scores(engines, cases, V, mode):
     tables = [None, None, RequestBias([[[int(kids[2])], 2.0]]), None]
     for ks in (1, 2, 3):
         for fam, tb in (("guard", None), ("bias", tables)):
-            tok, raw, lp, noise, so = eng.test_greedy_grammar(_slabs(rows, ks), B, g, STATES, eos, hist=hist, hist_len=hlen, tables=tb, samp=(t, seeds, steps), **GUARDS)
+            tok, raw, lp, noise, so = eng.test_greedy_grammar(slabs(rows, ks), B, g, STATES, eos, hist=hist, hist_len=hlen, tables=tb, samp=(t, seeds, steps), **GUARDS)
             for b in range(B):
                 m = masked(g, eos, raw[b], hist[b, :hlen[b]], tb[b] if tb else None, guards, STATES[b])
                 want, _ = select(m, t[b], noise[b])
@@ -189,7 +185,7 @@ def test_free_rows_give_the_bits_of_the_families_without_the_flag(engines, cases
     """all eight GRAMMAR families with every row free against their non-grammar families: tokens, raw dump, lp, alternatives and noise bit for bit; states stay -1"""
     V = 16388
     g, eos, rows, hist, hlen, kids, outside, one = cases(V)
-    s = _slabs(rows, 2)
+    s = slabs(rows, 2)
     free = np.full(B, -1, np.int32)
     tables = [RequestBias([[[int(kids[0])], 1.5]]), None, RequestBias([[[7], 9.0]], bad_words_ids=[[int(np.argmax(rows[2]))]]), None]
     samp = ([0.7, 0.0, 2.0, 1.0], [3, 4, 5, 6], [0, 1, 2, 3])

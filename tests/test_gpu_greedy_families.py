@@ -9,17 +9,16 @@ the largest three-bitmap LDS request).  Rows are uniform(-4, 4) from a fixed see
 three SAMPLE families run in the handle's type (bf16, fp16, the fp32 kind), the other six hooks launch the bf16 kernels whatever the handle, and values
 that are exact in all three types make every launch see the same scores.
 
-Log-probabilities: DESIGN.md 6.3's derived bound (lp_bound of test_gpu_request_bias.py), against float64 log_softmax of the processed scores."""
+Log-probabilities: DESIGN.md 6.3's derived bound (lp_bound of gpu_common.py), against float64 log_softmax of the processed scores."""
 import numpy as np
 import pytest
 
-from sonicscribe_amd import spec
+from gpu_common import SEED, check_lp, make_engine, same_bits, slabs
 from sonicscribe_amd.reqbias import RequestBias
-from test_gpu_request_bias import _histories, check_lp  # noqa: E402
-from test_gpu_sampling_kernel import bf16_exact, same_bits, select, slabs  # noqa: E402
+from test_gpu_request_bias import _histories  # noqa: E402
+from test_gpu_sampling_kernel import bf16_exact, select  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
 B = 4
 NEG = np.float32("-inf")
 SHAPES = pytest.mark.parametrize("V,ks", [(V, ks) for V in (8, 16388, 59264) for ks in (1, 2)])
@@ -40,14 +39,11 @@ def launches(flag=None):
 
 @pytest.fixture(scope="module")
 def engines():
-    from sonicscribe_amd.engine import Engine
     es = {}
 
     def get(mode):
         if mode not in es:
-            e = Engine(spec.TINY, 0, MODES[mode], max_batch=B, max_ctx=1024)      # the hooks take everything as arguments: no option plays a part
-            e.load_synthetic(SEED)
-            es[mode] = e
+            es[mode] = make_engine(mode=MODES[mode], max_batch=B)                  # the hooks take everything as arguments: no option plays a part
         return es[mode]
     yield get
     for e in es.values():

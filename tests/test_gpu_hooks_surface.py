@@ -5,10 +5,10 @@ sonic_encode returns - both read the same buffer)."""
 import numpy as np
 import pytest
 
+from gpu_common import make_engine, prompt_for
 from sonicscribe_amd import spec, synth
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
 D = spec.TINY
 BM, CTX = 1, 512
 TOK_CAP = BM * min(CTX, D.max_audio_tokens + 256)
@@ -24,14 +24,11 @@ CAP32 = {"prefill_tap": TOK_CAP * D.dec_d, "pe": BM * D.max_audio_tokens * D.dec
 
 def _pcm_prompt():
     pcm = synth.synth_pcm(10, 80000)
-    return pcm, [1, 17, 23, 5] + [D.audio_token_id] * spec.audio_token_count(spec.valid_frames(len(pcm))) + [7, 301, 302, 303, 9, 11]
+    return pcm, prompt_for(D, len(pcm))
 
 
 def _engine(mode):
-    from sonicscribe_amd.engine import Engine
-    e = Engine(D, 0, mode, max_batch=BM, max_ctx=CTX)
-    e.load_synthetic(SEED)
-    return e
+    return make_engine(D, mode, BM, CTX)
 
 
 @pytest.fixture(scope="module")

@@ -13,10 +13,11 @@ from dataclasses import replace
 import numpy as np
 import pytest
 
+from gpu_common import SEED, load_oracle, make_engine
 from sonicscribe_amd import spec, synth
+from sonicscribe_amd.engine import MODE_INT8
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
 
 
 def f16(x):
@@ -25,17 +26,14 @@ def f16(x):
 
 @pytest.fixture(scope="module")
 def eng8():
-    from sonicscribe_amd.engine import Engine, MODE_INT8
-    e = Engine(spec.TINY, 0, MODE_INT8, max_batch=8, max_ctx=512)
-    e.load_synthetic(SEED)
+    e = make_engine(mode=MODE_INT8, max_batch=8, max_ctx=512)
     yield e
     e.close()
 
 
 @pytest.fixture(scope="module")
 def orc():
-    from oracle import oracle
-    return oracle
+    return load_oracle()
 
 
 def _ref_linear(orc, X, W, bias, group_rows):

@@ -20,9 +20,10 @@ import pytest
 
 import attn_ref as R
 import glue_ref as G
-from sonicscribe_amd import spec
+from gpu_common import bits, load_oracle, make_engine
+from sonicscribe_amd.engine import MODE_INT8
 from test_gpu_attn_kernels import SCALE, decode_ratio
-from test_gpu_decode_glue import bits, check_quant, poison, same
+from test_gpu_decode_glue import check_quant, poison, same
 
 pytestmark = pytest.mark.gpu
 
@@ -33,17 +34,14 @@ KIND = "f16"
 
 @pytest.fixture(scope="module")
 def eng8():
-    from sonicscribe_amd.engine import Engine, MODE_INT8
-    e = Engine(spec.TINY, 0, MODE_INT8, max_batch=4, max_ctx=256)
-    e.load_synthetic(20260128)
+    e = make_engine(mode=MODE_INT8, max_ctx=256)
     yield e
     e.close()
 
 
 @pytest.fixture(scope="module")
 def orc():
-    from oracle import oracle
-    return oracle
+    return load_oracle()
 
 
 _REF = {}
@@ -130,7 +128,7 @@ def test_norm_consumer(eng8, orc, N, K, ks, cfg, forms, M):
 
 
 def test_norm_consumer_refusals(eng8):
-    from sonicscribe_amd.engine import Engine, SonicError
+    from sonicscribe_amd.engine import SonicError
     z = lambda *s: np.zeros(s, F)
     ok = dict(X=z(2, 256), W=z(256, 256), x=z(2, 256), norm_w=z(256), eps=EPS, form=0, layout=0)
     eng8.test_decode_i8_norm(**ok)
@@ -143,9 +141,8 @@ def test_norm_consumer_refusals(eng8):
                 dict(X=z(2, 4096), W=z(256, 4096), form=1, amax=z(2, 4), big=np.zeros((2, 4), np.int32))):     # K > 32 x 64 threads: the scan cannot cover the row
         with pytest.raises(SonicError):
             eng8.test_decode_i8_norm(**dict(ok, **bad))
-    e = Engine(spec.TINY, 0, max_batch=1, max_ctx=256)
+    e = make_engine(max_batch=1, max_ctx=256)
     try:
-        e.load_synthetic(20260128)
         with pytest.raises(SonicError, match="mode int8"):
             e.test_decode_i8_norm(**ok)
     finally:

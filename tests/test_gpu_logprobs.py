@@ -1,48 +1,21 @@
 """Per-token log-probabilities (option token_logprobs; greedy_kernel<T, true>): for every emitted token the engine returns
 log_softmax(l)[tok] of the logits l that step's argmax compared - HF compute_transition_scores(..., normalize_logits=True) of a greedy generate().
 
-Accuracy is asserted against a bound DERIVED from the kernel (DESIGN.md 6.3 goes through it line by line), not measured: with u = 2^-24, V the
-vocabulary, n_t = ceil(V / 4096) * 4 the elements one thread adds and ref64 the float64 log-softmax of the very fp32 logits the kernel compared,
-
-    |lp - ref64| <= (n_t + 3 * (ceil(n_t / 16) - 1) + 2 + 16 + 1 + 2.25 * ln V) * u + u * |ref64|
-
-  n_t                     the adds a thread's first term goes through, one rounding each
-  3 * (trips - 1)         one rescale of the running sum per later trip of the unrolled loop: v_exp_f32 (1 ulp <= 2 u) and a multiply
-  2                       v_exp_f32 of the term itself
-  16                      the merges: lane -> wave maximum (3), six butterfly adds, wave -> block maximum (3), four levels of the tree over 16 waves
-  1                       second-order terms and the fp64 tail (log, subtractions)
-  2.25 ln V               the arguments of exp: r - max rounds (u |x|; exact for bf16 / fp16 logits), x * log2(e) rounds (u |x|) with a constant that is
-                          0.22 u off; along a term's path the shifts add up to x_i = l_i - max(l), and sum_i p_i |x_i| = H(p) - log(sum) <= ln V
-  u |ref64|               the one rounding of the fp64 result to fp32
-The tests print the worst observed error / bound (a report; DESIGN.md quotes it).  Against the reference fixtures the bound is the project's own
-logit tolerance (tests/test_gpu_parity.py: 4 * 2^-6) twice, because log-sum-exp is 1-Lipschitz in the sup norm: 0.125."""
+Accuracy is asserted against a bound DERIVED from the kernel, not measured: tests/gpu_common.py lp_bound, with its derivation (DESIGN.md 6.3 goes through the
+kernel line by line).  The tests print the worst observed error / bound (a report; DESIGN.md quotes it).  Against the reference fixtures the bound is the
+project's own logit tolerance (tests/test_gpu_parity.py: 4 * 2^-6) twice, because log-sum-exp is 1-Lipschitz in the sup norm: 0.125."""
 import math
 import os
 
 import numpy as np
 import pytest
 
+from gpu_common import U, flags, load_golden, lp_bound, make_engine, prompt_for, ref_logprob, same_bits, slabs
 from sonicscribe_amd import spec, synth
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
-U = 2.0 ** -24
 TOL_FIXTURE = 2 * 4 * 2.0 ** -6
 WORST = {}
-
-
-def lp_bound(V, ref64):
-    n_t = math.ceil(V / 4096) * 4
-    c = 3 * (math.ceil(n_t / 16) - 1) + 2 + 16 + 1
-    return (n_t + c + 2.25 * math.log(V)) * U + U * np.abs(ref64)
-
-
-def ref_logprob(logits, tok):
-    """float64 log-softmax of fp32 logits [.., V] at tok [..]"""
-    l = np.asarray(logits, np.float64)
-    m = l.max(axis=-1, keepdims=True)
-    lse = m[..., 0] + np.log(np.exp(l - m).sum(axis=-1))
-    return np.take_along_axis(l, np.asarray(tok)[..., None].astype(np.int64), axis=-1)[..., 0] - lse
 
 
 def check_bound(tag, lp, logits, tok):
@@ -56,17 +29,8 @@ def check_bound(tag, lp, logits, tok):
     return ref
 
 
-def prompt_for(d, n):
-    return [1, 17, 23, 5] + [d.audio_token_id] * spec.audio_token_count(spec.valid_frames(n)) + [7, 301, 302, 303, 9, 11]
-
-
 def make(d=spec.TINY, mode=0, max_batch=4, max_ctx=1024, lp=True):
-    from sonicscribe_amd.engine import Engine
-    e = Engine(d, 0, mode, max_batch=max_batch, max_ctx=max_ctx)
-    if lp:
-        e.set_option("token_logprobs", 1)
-    e.load_synthetic(SEED)
-    return e
+    return make_engine(d, mode, max_batch, max_ctx, flags((lp, "token_logprobs", 1)))
 
 
 @pytest.fixture(scope="module")
@@ -78,9 +42,7 @@ def eng():
 
 @pytest.fixture(scope="module")
 def golden(golden_dir):
-    g = np.load(os.path.join(golden_dir, "tiny_bf16.npz"))
-    segs = [synth.synth_pcm(int(g[f"s{i}_seg_index"]), int(g[f"s{i}_n_samples"])) for i in range(2)]
-    prompts = [g[f"s{i}_prompt_ids"] for i in range(2)]
+    g, segs, prompts = load_golden(golden_dir)
     return g, segs, prompts, int(g["n_new"])
 
 
@@ -107,23 +69,13 @@ def _rows(V, rng):
     return {"equal": equal, "ramp": ramp, "spike": spike, "far": far, "dup": dup, "masked": masked}, p1
 
 
-def _slabs(rows, ks, mpad=16):
-    V = rows[0].shape[0]
-    w = {1: [1.0], 2: [0.5, 0.5], 3: [0.5, 0.25, 0.25]}[ks]                          # exact splits of a value with a few spare mantissa bits
-    s = np.zeros((ks, mpad, V), np.float32)
-    for b, r in enumerate(rows):
-        for k in range(ks):
-            s[k, b] = r * np.float32(w[k])
-    return s
-
-
 @pytest.mark.parametrize("V", [8, 1024, 16388, 59264])
 def test_kernel_hook_bound(eng, V):
     rng = np.random.default_rng(V)
     rows, p1 = _rows(V, rng)
     for ks in (1, 2, 3):
         for names in (("equal", "ramp", "spike"), ("far", "dup", "spike"), ("masked", "equal", "dup")):
-            s = _slabs([rows[n] for n in names], ks)
+            s = slabs([rows[n] for n in names], ks)
             tok, lg, lp = eng.test_greedy_lp(s, 3)
             tok0, lg0 = eng.test_greedy(s, 3, want_logits=True)
             assert np.array_equal(tok, tok0) and np.array_equal(lg.view(np.uint32), lg0.view(np.uint32)), (V, ks, names)
@@ -136,7 +88,7 @@ def test_kernel_hook_bound(eng, V):
                     assert tok[b] == p1
         # forced ids that are not the maximum: l[forced] - logsumexp, the forced logit recomputed from the slabs
         names = ("spike", "far", "dup")
-        s = _slabs([rows[n] for n in names], ks)
+        s = slabs([rows[n] for n in names], ks)
         force = ((s.sum(axis=0)[:3].argmax(axis=1) + V // 2 + 1) % V).astype(np.int32)
         tok, lg, lp = eng.test_greedy_lp(s, 3, force_ids=force)
         assert np.array_equal(tok, force) and np.all(force != lg.argmax(axis=1))
@@ -207,10 +159,6 @@ def test_teacher_forcing(eng, golden_dir):
 
 
 # ------------------------------------------------------------------------------------------ 5. invariance, bit for bit
-def _same_bits(a, b):
-    return a.dtype == b.dtype == np.float32 and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 def test_invariance_engine_paths(eng):
     d = spec.TINY
     segs = [synth.synth_pcm(700 + i, n) for i, n in enumerate((48000, 200000, 80000))]
@@ -218,16 +166,16 @@ def test_invariance_engine_paths(eng):
     budgets = [5, 17, 11]
     ids1, _, lp1 = eng.transcribe_batch([segs[2]], [prompts[2]], [budgets[2]], want_logprobs=True)                # alone
     ids3, _, lp3 = eng.transcribe_batch(segs, prompts, budgets, want_logprobs=True)                                # row 2 of 3, unequal budgets
-    assert np.array_equal(ids1[0], ids3[2]) and _same_bits(lp1[0], lp3[2])
+    assert np.array_equal(ids1[0], ids3[2]) and same_bits(lp1[0], lp3[2])
     for r in range(3):
         assert len(lp3[r]) == len(ids3[r]) == budgets[r] and np.all(np.isfinite(lp3[r]))
     # entries at or beyond a row's n_new are not written on the host
     buf = np.full((3, 20), np.nan, np.float32)
     eng._check(eng.lib.sonic_fetch_logprobs(eng.h, buf.ctypes.data, 20))
     for r in range(3):
-        assert _same_bits(buf[r, :budgets[r]].copy(), lp3[r]) and np.all(np.isnan(buf[r, budgets[r]:]))
+        assert same_bits(buf[r, :budgets[r]].copy(), lp3[r]) and np.all(np.isnan(buf[r, budgets[r]:]))
     ids_f, lp_f = eng.fetch_tokens(3, 20, want_logprobs=True)
-    assert all(np.array_equal(ids_f[r], ids3[r]) and _same_bits(lp_f[r], lp3[r]) for r in range(3))
+    assert all(np.array_equal(ids_f[r], ids3[r]) and same_bits(lp_f[r], lp3[r]) for r in range(3))
     # spliced into a continuous loop: the first token's entry comes from the prefill handle
     pre = eng.slot()
     eng.service_begin()
@@ -247,7 +195,7 @@ def test_invariance_engine_paths(eng):
                 break
         assert len(got) == 2
         for row, req in rows.items():
-            assert np.array_equal(got[row][0], ids3[req]) and _same_bits(got[row][1], lp3[req]), (row, req)
+            assert np.array_equal(got[row][0], ids3[req]) and same_bits(got[row][1], lp3[req]), (row, req)
     finally:
         eng.service_end()
         pre.close()
@@ -330,7 +278,7 @@ def test_invariance_native_dispatcher_and_bulk_pipeline():
         res = [f.result(timeout=60) for f in futs]
         disp.close()
         for i in (0, 2):
-            assert np.array_equal(res[i][0], solo[i][0][0]) and _same_bits(res[i][1], solo[i][2][0]), i
+            assert np.array_equal(res[i][0], solo[i][0][0]) and same_bits(res[i][1], solo[i][2][0]), i
         assert isinstance(res[1], np.ndarray) and np.array_equal(res[1], solo[1][0][0])
         bulk = Dispatcher([e], slots=[slots], bulk=True, decoders=1)
         futs = [bulk.submit([segs[i]], prompts[i], budgets[i], want_logprobs=True) for i in range(3)]
@@ -338,7 +286,7 @@ def test_invariance_native_dispatcher_and_bulk_pipeline():
         plain = bulk.submit([segs[2]], prompts[2], budgets[2]).result(timeout=60)
         bulk.close()
         for i in range(3):
-            assert np.array_equal(res[i][0], solo[i][0][0]) and _same_bits(res[i][1], solo[i][2][0]), i
+            assert np.array_equal(res[i][0], solo[i][0][0]) and same_bits(res[i][1], solo[i][2][0]), i
         assert np.array_equal(plain, solo[2][0][0])
     finally:
         e.close()
@@ -388,7 +336,7 @@ def test_asrmodel_surface():
         assert np.all(info["token_logprobs"] <= 0) and info["avg_logprob"] == pytest.approx(float(np.mean(info["token_logprobs"], dtype=np.float64)))
         assert info["confidence"] == math.exp(info["avg_logprob"]) and 0 < info["confidence"] <= 1
         r = m.submit(wav, max_new_tokens=12, detailed=True).result(timeout=60)
-        assert isinstance(r, Transcription) and r.text == info["transcript"] and _same_bits(r.token_logprobs, info["token_logprobs"])
+        assert isinstance(r, Transcription) and r.text == info["transcript"] and same_bits(r.token_logprobs, info["token_logprobs"])
         assert m.submit(wav, max_new_tokens=12).result(timeout=60) == info["transcript"]
         st = m.open_stream("s")
         pcm = synth.synth_pcm(31, 80000)

@@ -4,10 +4,10 @@ when a knob that changes the captured kernels moves (a decode after no_fused_gu 
 import numpy as np
 import pytest
 
+from gpu_common import make_engine, prompt_for
 from sonicscribe_amd import spec, synth
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
 
 KEYS = [
     "skinny_variant", "gemm_force128", "no_fused_gu", "no_fused_gu64", "gu64_two_pass", "gu64_split_norm", "ktrace_wave", "no_skinny768", "no_skinny48",
@@ -20,18 +20,16 @@ CLAMPED = ["gemm256_persist_cus", "gemm256_gm", "decode_lookahead", "decode_chun
 
 
 def test_option_table():
-    from sonicscribe_amd.engine import Engine, SonicError
+    from sonicscribe_amd.engine import SonicError
     d = spec.TINY
     pcm = synth.synth_pcm(10, 80000)
-    prompt = [1, 17, 23, 5] + [d.audio_token_id] * spec.audio_token_count(spec.valid_frames(len(pcm))) + [7, 301, 302, 303, 9, 11]
+    prompt = prompt_for(d, len(pcm))
     n_new = 12
-    ref = Engine(d, 0, max_batch=2, max_ctx=512)               # the untouched engine
-    ref.load_synthetic(SEED)
+    ref = make_engine(d, max_batch=2, max_ctx=512)             # the untouched engine
     want = ref.transcribe_batch([pcm], [prompt], [n_new])[0][0]
     ref.close()
 
-    e = Engine(d, 0, max_batch=2, max_ctx=512)
-    e.load_synthetic(SEED)
+    e = make_engine(d, max_batch=2, max_ctx=512)
     assert np.array_equal(e.transcribe_batch([pcm], [prompt], [n_new])[0][0], want)      # captures the default decode graphs
     e.set_option("no_fused_gu", 1)
     e.transcribe_batch([pcm], [prompt], [n_new])                                         # captures the unfused form

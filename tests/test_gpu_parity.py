@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+from gpu_common import SEED, load_oracle, make_engine
 from sonicscribe_amd import spec, synth
 
 pytestmark = pytest.mark.gpu
@@ -22,17 +23,14 @@ def bf(x):
 
 @pytest.fixture(scope="module")
 def eng():
-    from sonicscribe_amd.engine import Engine
-    e = Engine(spec.TINY, 0, max_batch=16, max_ctx=512)
-    e.load_synthetic(20260128)
+    e = make_engine(max_batch=16, max_ctx=512)
     yield e
     e.close()
 
 
 @pytest.fixture(scope="module")
 def orc():
-    from oracle import oracle
-    return oracle
+    return load_oracle()
 
 
 def ulp_tol(ref, n_ulp=2.0):
@@ -432,7 +430,7 @@ def test_eos_stops_row(eng):
     ids, _ = eng.transcribe_batch([seg], [prompt], [8])
     d2 = replace(spec.TINY, eos_ids=(int(ids[0][2]), 991, 992))
     e2 = Engine(d2, 0, max_batch=2, max_ctx=512)
-    e2.load_synthetic(20260128)
+    e2.load_synthetic(SEED)
     ids2, _ = e2.transcribe_batch([seg, seg], [prompt, prompt], [8, 3])
     first = int(np.argmax(ids[0] == ids[0][2]))
     assert np.array_equal(ids2[0], ids[0][: first + 1])      # stops right after emitting EOS

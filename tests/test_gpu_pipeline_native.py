@@ -8,14 +8,10 @@ from dataclasses import replace
 import numpy as np
 import pytest
 
+from gpu_common import SEED, prompt_for
 from sonicscribe_amd import spec, synth
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
-
-
-def prompt_for(d, n_samples, tail=()):
-    return [1, 17, 23, 5] + [d.audio_token_id] * spec.audio_token_count(spec.valid_frames(n_samples)) + [7, 301, 302, 303, 9, 11] + list(tail)
 
 
 @pytest.mark.parametrize("dims,mode,n_dec", [(replace(spec.TINY, eos_ids=()), 0, 2), (replace(spec.FULL, enc_layers=2, dec_layers=2, eos_ids=()), 0, 1),

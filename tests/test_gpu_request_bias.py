@@ -2,44 +2,18 @@
 SequenceBiasLogitsProcessor / NoBadWordsLogitsProcessor inside the greedy kernel, one table per row.  The reference is the numpy chain
 `GenerationGuards.apply(RequestBias.apply(raw, history), history)`, which tests/test_request_bias_host.py holds bit for bit against HF's own classes: the emitted
 token must be np.argmax (first maximum) of the chain over the raw logits the kernel dumped, exactly.  Log-probabilities are held to DESIGN.md 6.3's derived bound
-(tests/test_gpu_logprobs.py lp_bound, the same derivation: the bias adds no rounding to the sum, it changes the scores the sum is taken over), evaluated over
+(tests/gpu_common.py lp_bound, the same derivation: the bias adds no rounding to the sum, it changes the scores the sum is taken over), evaluated over
 the processed scores."""
-import math
-import os
-
 import numpy as np
 import pytest
 
+from gpu_common import check_lp, flags, load_golden, make_engine, prompt_for, same_bits, six, slabs
 from sonicscribe_amd import spec, synth
 from sonicscribe_amd.genconfig import GenerationGuards
 from sonicscribe_amd.reqbias import RequestBias
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
-U = 2.0 ** -24
 NEG = float("-inf")
-
-
-def lp_bound(V, ref64):
-    n_t = math.ceil(V / 4096) * 4
-    c = 3 * (math.ceil(n_t / 16) - 1) + 2 + 16 + 1
-    return (n_t + c + 2.25 * math.log(V)) * U + U * np.abs(ref64)
-
-
-def ref_logprob(scores, tok):
-    l = np.asarray(scores, np.float64)
-    m = l.max()
-    return l[int(tok)] - (m + np.log(np.exp(l - m).sum()))
-
-
-def check_lp(tag, lp, processed, tok):
-    if np.isneginf(processed[int(tok)]):
-        assert np.isneginf(lp), (tag, lp)
-        return 0.0
-    ref = ref_logprob(processed, tok)
-    ratio = abs(float(lp) - ref) / lp_bound(len(processed), ref)
-    assert np.isfinite(lp) and ratio <= 1.0, (tag, float(lp), ref, ratio)
-    return ratio
 
 
 def order_triple():
@@ -56,25 +30,8 @@ def chain(raw, hist, bias, guards=None):
     return (guards or GenerationGuards()).apply(s, hist)
 
 
-def prompt_for(d, n):
-    return [1, 17, 23, 5] + [d.audio_token_id] * spec.audio_token_count(spec.valid_frames(n)) + [7, 301, 302, 303, 9, 11]
-
-
 def make(d=spec.TINY, mode=0, max_batch=4, max_ctx=1024, lp=False, bias=True, guards=None):
-    from sonicscribe_amd.engine import Engine
-    e = Engine(d, 0, mode, max_batch=max_batch, max_ctx=max_ctx)
-    if lp:
-        e.set_option("token_logprobs", 1)
-    if bias:
-        e.set_option("request_bias", 1)
-    if guards:
-        e.set_generation(**guards)
-    e.load_synthetic(SEED)
-    return e
-
-
-def _same_bits(a, b):
-    return a.dtype == b.dtype == np.float32 and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    return make_engine(d, mode, max_batch, max_ctx, flags((lp, "token_logprobs", 1), (bias, "request_bias", 1), (guards, "generation", guards)))
 
 
 @pytest.fixture(scope="module")
@@ -92,23 +49,11 @@ def engines():
 
 @pytest.fixture(scope="module")
 def golden(golden_dir):
-    g = np.load(os.path.join(golden_dir, "tiny_bf16.npz"))
-    segs = [synth.synth_pcm(int(g[f"s{i}_seg_index"]), int(g[f"s{i}_n_samples"])) for i in range(2)]
-    prompts = [[int(t) for t in g[f"s{i}_prompt_ids"]] for i in range(2)]
+    g, segs, prompts = load_golden(golden_dir, int_prompts=True)
     return g, segs, prompts, int(g["n_new"])
 
 
 # ------------------------------------------------------------------------------------------ 1. the kernel hook, exact
-def _slabs(rows, ks, mpad=16):
-    V = rows[0].shape[0]
-    w = {1: [1.0], 2: [0.5, 0.5], 3: [0.5, 0.25, 0.25]}[ks]
-    s = np.zeros((ks, mpad, V), np.float32)
-    for b, r in enumerate(rows):
-        for k in range(ks):
-            s[k, b] = r * np.float32(w[k])
-    return s
-
-
 def _edges(V):
     """the group and trip edges of the loop: first id, last id of the first f32x4 group, both sides of the first stride, the last id"""
     return sorted({0, 3, V - 1} | ({4095, 4096} if V > 4096 else set()))
@@ -147,7 +92,7 @@ def _big_table(V, h, winner, rng):
 
 
 def _run(eng, V, ks, rows, hist, hlen, tables, guards=None, want_lp=False, force=None, tag=""):
-    s = _slabs(rows, ks)
+    s = slabs(rows, ks)
     B = len(rows)
     g = GenerationGuards(**(guards or {}))
     tok, raw, lp = eng.test_greedy_bias(s, B, hist[:B], hlen[:B], tables, force_ids=force, want_lp=want_lp, **(guards or {}))
@@ -241,10 +186,10 @@ def test_neutral_guard_identity(engines):
         for ks in (1, 2, 3):
             rows = [rng.uniform(-4.0, 4.0, V).astype(np.float32) for _ in range(4)]
             rows[1][V // 2] = -0.0
-            s = _slabs(rows, ks)
+            s = slabs(rows, ks)
             tok, raw, lp = eng.test_greedy_bias(s, 4, hist, hlen, [None, RequestBias(), None, None], want_lp=True)
             tok0, raw0, lp0 = eng.test_greedy_lp(s, 4)
-            assert np.array_equal(tok, tok0) and _same_bits(raw, raw0) and _same_bits(lp, lp0), (V, ks)
+            assert np.array_equal(tok, tok0) and same_bits(raw, raw0) and same_bits(lp, lp0), (V, ks)
 
 
 # ------------------------------------------------------------------------------------------ 2. end to end at TINY
@@ -309,11 +254,7 @@ def test_modes_identity(mode, golden):
 
 # ------------------------------------------------------------------------------------------ 3. the same bits on every path
 def _six():
-    d = spec.TINY
-    segs = [synth.synth_pcm(700 + i, n) for i, n in enumerate((48000, 200000, 80000, 64000, 120000, 96000))]
-    prompts = [prompt_for(d, len(s)) for s in segs]
-    budgets = [5, 17, 11, 9, 13, 7]
-    return segs, prompts, budgets
+    return six() + ([5, 17, 11, 9, 13, 7],)
 
 
 def test_invariance_all_paths():
@@ -344,8 +285,8 @@ def test_invariance_all_paths():
         ids_g, _, lp_g = e.transcribe_batch(segs, prompts, budgets, want_logprobs=True, request_bias=tables)                               # one batch, hipGraph loop
         solo = [e.transcribe_batch([segs[i]], [prompts[i]], [budgets[i]], want_logprobs=True, request_bias=[tables[i]]) for i in range(6)]  # solo runs
         for r in range(6):
-            assert np.array_equal(ids_g[r], ids_e[r]) and _same_bits(lp_g[r], lp_e[r]), r
-            assert np.array_equal(solo[r][0][0], ids_e[r]) and _same_bits(solo[r][2][0], lp_e[r]), r
+            assert np.array_equal(ids_g[r], ids_e[r]) and same_bits(lp_g[r], lp_e[r]), r
+            assert np.array_equal(solo[r][0][0], ids_e[r]) and same_bits(solo[r][2][0], lp_e[r]), r
         # prefill, then splice into a continuous handle: the table travels with the row (rows land in another order than they were prefilled in)
         pre = e.slot()
         e.service_begin()
@@ -368,7 +309,7 @@ def test_invariance_all_paths():
                     break
             assert len(got) == 6
             for row, req in rows.items():
-                assert np.array_equal(got[row][0], ids_e[req]) and _same_bits(got[row][1], lp_e[req]), (row, req)
+                assert np.array_equal(got[row][0], ids_e[req]) and same_bits(got[row][1], lp_e[req]), (row, req)
         finally:
             e.service_end()
             pre.close()
@@ -383,7 +324,7 @@ def test_invariance_all_paths():
             for s in slots:
                 s.close()
             for i in range(6):
-                assert np.array_equal(res[i][0], ids_e[i]) and _same_bits(res[i][1], lp_e[i]), (native, i)
+                assert np.array_equal(res[i][0], ids_e[i]) and same_bits(res[i][1], lp_e[i]), (native, i)
     finally:
         e.close()
 

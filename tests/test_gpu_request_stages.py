@@ -5,17 +5,17 @@ every grammar reference is handed back by the last fetch."""
 import numpy as np
 import pytest
 
+from gpu_common import prompt_for, same_bits
 from sonicscribe_amd import synth
 from sonicscribe_amd.reqbias import RequestBias
 from test_gpu_grammar import D, grammar_a, grammar_b, make  # noqa: E402
-from test_gpu_request_bias import _same_bits, prompt_for  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 
 def _same(got, want, tag):
     for r in range(len(want[0])):
-        assert np.array_equal(got[0][r], want[0][r]) and _same_bits(got[1][r], want[1][r]), (tag, r, got[0][r].tolist(), want[0][r].tolist())
+        assert np.array_equal(got[0][r], want[0][r]) and same_bits(got[1][r], want[1][r]), (tag, r, got[0][r].tolist(), want[0][r].tolist())
 
 
 def test_three_stages_together():

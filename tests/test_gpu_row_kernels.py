@@ -6,23 +6,18 @@ bits on both routes, and the verify route's token the row's first maximum."""
 import numpy as np
 import pytest
 
-from sonicscribe_amd import spec
-from test_gpu_draft_kernel import HLD, _case, _slabs  # noqa: E402
+from gpu_common import make_engine, slabs
+from test_gpu_draft_kernel import HLD, _case  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
 KINDS = {"bf16": 0, "fp16": 2}
 
 
 @pytest.fixture(scope="module", params=list(KINDS))
 def routes(request):
-    from sonicscribe_amd.engine import Engine
     out = []
     for option in ("forced_parallel", "draft_verify"):
-        e = Engine(spec.TINY, 0, KINDS[request.param], max_batch=2, max_ctx=512)
-        e.set_option("token_logprobs", 1)
-        e.set_option(option, 1)
-        e.load_synthetic(SEED)
+        e = make_engine(mode=KINDS[request.param], max_batch=2, max_ctx=512, options=(("token_logprobs", 1), (option, 1)))
         e.kind = request.param
         out.append(e)
     yield out
@@ -47,7 +42,7 @@ def test_choice_changes_no_arithmetic(routes, V, B, K):
         force = np.random.default_rng(V + B + 1).integers(0, V, B).astype(np.int32)
         hist, hlen = np.zeros((B, HLD), np.int32), np.zeros(B, np.int32)
         for ks in (1, 3):
-            s = _slabs(rows, ks, (B + 15) // 16 * 16)
+            s = slabs(rows, ks, (B + 15) // 16 * 16)
             tok_s, raw_s, sc_s = score.test_greedy_lp(s, B, force_ids=force)
             tok_v, raw_v, sc_v = verify.test_greedy_guard(s, B, hist, hlen, force_ids=force, want_lp=True)
             assert np.array_equal(tok_s, force)

@@ -1,50 +1,18 @@
 """Temperature sampling end to end on the GPU (option sampling, sonic_set_request_sampling), on TINY with `token_logprobs` and `sampling` on:
 greedy decoding unchanged, every step replayed from the raw logits against the definition (sonicscribe_amd/sampling.py), the same bits on every path, seeds,
 the fallback ladder through ASRModel, refusals, memory."""
-import math
-
 import numpy as np
 import pytest
 
+from gpu_common import SEED, flags, lp_bound, make_engine, same_bits, six
 from sonicscribe_amd import sampling, spec, synth
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
 FIXED_SEEDS = (1, 2, 3, 4, 5, 6, 7, 8)
 
 
-def lp_bound(V, ref64):
-    """the existing log-probability tests' bound (tests/test_gpu_request_bias.py)"""
-    n_t = math.ceil(V / 4096) * 4
-    c = 3 * (math.ceil(n_t / 16) - 1) + 2 + 16 + 1
-    return (n_t + c + 2.25 * math.log(V)) * 2.0 ** -24 + 2.0 ** -24 * np.abs(ref64)
-
-
-def prompt_for(d, n):
-    return [1, 17, 23, 5] + [d.audio_token_id] * spec.audio_token_count(spec.valid_frames(n)) + [7, 301, 302, 303, 9, 11]
-
-
 def make(mode=0, max_batch=8, max_ctx=1024, lp=True, samp=True):
-    from sonicscribe_amd.engine import Engine
-    e = Engine(spec.TINY, 0, mode, max_batch=max_batch, max_ctx=max_ctx)
-    if lp:
-        e.set_option("token_logprobs", 1)
-    if samp:
-        e.set_option("sampling", 1)
-    e.load_synthetic(SEED)
-    return e
-
-
-def _same_bits(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.dtype == b.dtype == np.float32 and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def _six():
-    d = spec.TINY
-    segs = [synth.synth_pcm(700 + i, n) for i, n in enumerate((48000, 200000, 80000, 64000, 120000, 96000))]
-    prompts = [prompt_for(d, len(s)) for s in segs]
-    return segs, prompts
+    return make_engine(spec.TINY, mode, max_batch, max_ctx, flags((lp, "token_logprobs", 1), (samp, "sampling", 1)))
 
 
 @pytest.fixture(scope="module")
@@ -56,7 +24,7 @@ def eng():
 
 def test_greedy_unchanged(eng):
     """temperature 0 - stated per request, or no values at all - gives the ids and log-probability bits of a handle without the option"""
-    segs, prompts = _six()
+    segs, prompts = six()
     budgets = [12] * 6
     off = make(samp=False)
     try:
@@ -68,7 +36,7 @@ def test_greedy_unchanged(eng):
     ids3, _, lp3 = eng.transcribe_batch(segs, prompts, budgets, want_logprobs=True, request_sampling=[None, (0.0, 1), None, None, (0.0, 2), None])
     for r in range(6):
         for ids, lp in ((ids1, lp1), (ids2, lp2), (ids3, lp3)):
-            assert np.array_equal(ids[r], ids0[r]) and _same_bits(lp[r], lp0[r]), r
+            assert np.array_equal(ids[r], ids0[r]) and same_bits(lp[r], lp0[r]), r
 
 
 def test_replay_against_the_definition(eng):
@@ -76,7 +44,7 @@ def test_replay_against_the_definition(eng):
     contract's y with exact noise, u one fp32 spacing at max |y| (the kernel's y = q + g is rounded once per candidate: half a spacing on either side of the
     compare).  Steps where that set has more than one member may be at most 2 % of the steps checked: the definition alone gives a top-two gap below 1e-2 in about
     0.5 % of draws at the full vocabulary, and the window here is some 1e-5 wide.  At least 100 steps are checked."""
-    segs, prompts = _six()
+    segs, prompts = six()
     budgets = [20] * 6
     checked = ambiguous = 0
     for t in (1.0, 0.2):
@@ -104,7 +72,7 @@ def test_replay_against_the_definition(eng):
 def test_invariance_all_paths(eng):
     """the same (audio, t, seed): alone; as row 5 of a batch of other requests with other seeds; through the continuous schedulers; after sonic_splice_rows"""
     from sonicscribe_amd.dispatch import Dispatcher
-    segs, prompts = _six()
+    segs, prompts = six()
     budgets = [5, 17, 11, 9, 13, 15]
     samp = [(0.7, 11), (1.0, 12), (0.0, 13), (0.3, 14), (1.5, 15), (1.0, 0x123456789ABCDEF0)]
     want_ids, _, want_lp = eng.transcribe_batch([segs[5]], [prompts[5]], [budgets[5]], want_logprobs=True, request_sampling=[samp[5]])      # alone
@@ -112,10 +80,10 @@ def test_invariance_all_paths(eng):
     greedy, _ = eng.transcribe_batch([segs[5]], [prompts[5]], [budgets[5]])
     assert not np.array_equal(greedy[0], want_ids), "t = 1 left the greedy path nowhere: the test shows nothing"
     ids_b, _, lp_b = eng.transcribe_batch(segs, prompts, budgets, want_logprobs=True, request_sampling=samp)                                 # row 5 of a batch (hipGraph loop)
-    assert np.array_equal(ids_b[5], want_ids) and _same_bits(lp_b[5], want_lp)
+    assert np.array_equal(ids_b[5], want_ids) and same_bits(lp_b[5], want_lp)
     ids_e, _, lp_e = eng.transcribe_batch(segs, prompts, budgets, want_logits=True, want_logprobs=True, request_sampling=samp)               # ... and eager
     for r in range(6):
-        assert np.array_equal(ids_e[r], ids_b[r]) and _same_bits(lp_e[r], lp_b[r]), r
+        assert np.array_equal(ids_e[r], ids_b[r]) and same_bits(lp_e[r], lp_b[r]), r
     # prefill on a slot, then splice into a continuous handle: the words travel with the row, into another row than the one it was prefilled in
     pre = eng.slot()
     assert pre.sampling
@@ -135,7 +103,7 @@ def test_invariance_all_paths(eng):
                 break
         assert len(got) == 3
         for row, req in rows.items():
-            assert np.array_equal(got[row][0], ids_b[req]) and _same_bits(got[row][1], lp_b[req]), (row, req)
+            assert np.array_equal(got[row][0], ids_b[req]) and same_bits(got[row][1], lp_b[req]), (row, req)
     finally:
         eng.service_end()
         pre.close()
@@ -150,11 +118,11 @@ def test_invariance_all_paths(eng):
         for s in slots:
             s.close()
         for i in range(6):
-            assert np.array_equal(res[i][0], ids_b[i]) and _same_bits(res[i][1], lp_b[i]), (native, i)
+            assert np.array_equal(res[i][0], ids_b[i]) and same_bits(res[i][1], lp_b[i]), (native, i)
 
 
 def test_seeds_differ(eng):
-    segs, prompts = _six()
+    segs, prompts = six()
     runs = [eng.transcribe_batch([segs[0]], [prompts[0]], [16], request_sampling=[(1.0, s)])[0][0].tolist() for s in FIXED_SEEDS]
     again = eng.transcribe_batch([segs[0]], [prompts[0]], [16], request_sampling=[(1.0, FIXED_SEEDS[0])])[0][0].tolist()
     print(f"seeds: {len({tuple(r) for r in runs})} distinct transcripts of {len(runs)}")
@@ -185,11 +153,11 @@ def test_ladder_end_to_end():
     m = ASRModel.from_synthetic(spec.TINY, max_batch=4, max_ctx=1024, token_logprobs=True, sampling=True, logprob_threshold=0.0)
     try:
         r0 = m.submit(wav, max_new_tokens=12, detailed=True).result(timeout=60)                       # the defaults: one greedy attempt
-        assert r0.attempts == 1 and r0.temperature == 0.0 and np.array_equal(r0.token_ids, greedy.token_ids) and _same_bits(r0.token_logprobs, greedy.token_logprobs)
+        assert r0.attempts == 1 and r0.temperature == 0.0 and np.array_equal(r0.token_ids, greedy.token_ids) and same_bits(r0.token_logprobs, greedy.token_logprobs)
         r = m.submit(wav, max_new_tokens=12, detailed=True, temperature=temps, seed=5).result(timeout=120)
         assert isinstance(r, Transcription) and r.attempts == len(temps) and r.temperature == temps[-1]
         one = m.submit(wav, max_new_tokens=12, detailed=True, temperature=temps[-1], seed=5).result(timeout=60)   # the same (audio, t, seed) as the last attempt
-        assert one.attempts == 1 and np.array_equal(one.token_ids, r.token_ids) and _same_bits(one.token_logprobs, r.token_logprobs) and one.text == r.text
+        assert one.attempts == 1 and np.array_equal(one.token_ids, r.token_ids) and same_bits(one.token_logprobs, r.token_logprobs) and one.text == r.text
         assert m.submit(wav, max_new_tokens=12, temperature=temps, seed=5).result(timeout=120) == r.text
         assert m.transcribe_batch([wav, wav], max_new_tokens=12, temperature=temps, seed=5) == [r.text, r.text]
         assert m.transcribe_batch([wav], max_new_tokens=12, temperature=temps[-1], seed=5) == [r.text]
@@ -215,7 +183,7 @@ def test_ladder_end_to_end():
 def test_refusals_and_memory():
     from sonicscribe_amd.dispatch import Dispatcher
     from sonicscribe_amd.engine import Engine, SonicError
-    segs, prompts = _six()
+    segs, prompts = six()
     e = Engine(spec.TINY, 0, 0, max_batch=32, max_ctx=1024)
     try:
         with pytest.raises(SonicError, match="token_logprobs"):                # the option without token_logprobs, by name

@@ -4,35 +4,19 @@ history)` (the processed scores, held bit for bit against HF by the host tests).
 
 Inputs are bf16-exact values of moderate size, so the rounding to the handle's type changes none of them: the existing hooks (which launch the bf16 kernels whatever
 the handle) see the same scores as the sampling hook does."""
-import math
-
 import numpy as np
 import pytest
 
-from sonicscribe_amd import sampling, spec
+from gpu_common import lp_bound, make_engine, ref_logprob, same_bits, slabs
+from sonicscribe_amd import sampling
 from sonicscribe_amd.genconfig import GenerationGuards
 from sonicscribe_amd.reqbias import RequestBias
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
-U = 2.0 ** -24
 NEG = float("-inf")
 MODES = pytest.mark.parametrize("mode", [0, 2, 3], ids=["bf16", "f16", "f32"])
 SEEDS = (0, 1, 0x123456789ABCDEF0)
 STEPS = (0, 7, 1000)
-
-
-def lp_bound(V, ref64):
-    """the existing log-probability tests' bound (tests/test_gpu_request_bias.py)"""
-    n_t = math.ceil(V / 4096) * 4
-    c = 3 * (math.ceil(n_t / 16) - 1) + 2 + 16 + 1
-    return (n_t + c + 2.25 * math.log(V)) * U + U * np.abs(ref64)
-
-
-def ref_logprob(scores, tok):
-    l = np.asarray(scores, np.float64)
-    m = l.max()
-    return l[int(tok)] - (m + np.log(np.exp(l - m).sum()))
 
 
 def check_lp(tag, lp, processed, tok):
@@ -49,16 +33,6 @@ def bf16_exact(x):
     return (x.view(np.uint32) & np.uint32(0xFFFF0000)).view(np.float32)
 
 
-def slabs(rows, ks):
-    V, mpad = rows[0].shape[0], max(16, len(rows))
-    w = {1: [1.0], 2: [0.5, 0.5]}[ks]
-    s = np.zeros((ks, mpad, V), np.float32)
-    for b, r in enumerate(rows):
-        for k in range(ks):
-            s[k, b] = r * np.float32(w[k])
-    return s
-
-
 def chain(raw, hist, table, guards):
     s = table.apply(raw, hist) if table is not None else np.array(raw, np.float32)
     return guards.apply(s, hist)
@@ -72,21 +46,13 @@ def select(s, t, noise):
     return int(np.argmax(y)), y
 
 
-def same_bits(a, b):
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
 @pytest.fixture(scope="module")
 def engines():
-    from sonicscribe_amd.engine import Engine
     es = {}
 
     def get(mode):
         if mode not in es:
-            e = Engine(spec.TINY, 0, mode, max_batch=4, max_ctx=1024)      # the hook takes everything as arguments: no option plays a part in it
-            e.load_synthetic(SEED)
-            es[mode] = e
+            es[mode] = make_engine(mode=mode)                              # the hook takes everything as arguments: no option plays a part in it
         return es[mode]
     yield get
     for e in es.values():
@@ -239,7 +205,7 @@ def test_distribution(engines, mode):
     eng = engines(mode)
     V, B = 16, 64
     sc = (0.5 * np.arange(V) - 4).astype(np.float32)
-    s = slabs([sc] * B, 1)
+    s = slabs([sc] * B, 1, mpad=B)
     p = np.exp(sc.astype(np.float64) / 2)
     p /= p.sum()
     e = p * 4096

@@ -11,63 +11,30 @@ References and tolerances:
 
 Figures printed for DESIGN.md 6.8 (one MI355X): the first 12 records of the 24-token run were bit-equal to a 12-token run on both segments; the parallel run against
 the step-by-step forced run: max |d lp| = 0.015, max |d logit| = 0.031."""
-import math
-import os
+from functools import partial
 
 import numpy as np
 import pytest
 
+import gpu_common
+from gpu_common import bits, flags, forced_ids, load_golden, make_engine, ref_logprob, score_bound
 from sonicscribe_amd import spec, synth
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
 D = spec.TINY
-U = 2.0 ** -24
 TOL_LOGIT = 4 * 2.0 ** -6
 TOL_FIXTURE = 2 * 4 * 2.0 ** -6
 N = 24
-
-
-def score_bound(V, ref64):
-    n_t = math.ceil(V / 16384) * 16
-    c = 3 * (math.ceil(n_t / 16) - 1) + 2 + 16 + 1
-    return (n_t + c + 2.25 * math.log(V)) * U + U * np.abs(ref64)
-
-
-def ref_logprob(logits, tok):
-    """float64 log-softmax of fp32 logits [.., V] at tok [..]"""
-    l = np.asarray(logits, np.float64)
-    m = l.max(axis=-1, keepdims=True)
-    lse = m[..., 0] + np.log(np.exp(l - m).sum(axis=-1))
-    return np.take_along_axis(l, np.asarray(tok)[..., None].astype(np.int64), axis=-1)[..., 0] - lse
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def prompt_for(n):
-    return [1, 17, 23, 5] + [D.audio_token_id] * spec.audio_token_count(spec.valid_frames(n)) + [7, 301, 302, 303, 9, 11]
+prompt_for = partial(gpu_common.prompt_for, D)
 
 
 def make(mode=0, max_batch=4, max_ctx=1024, lp=True, parallel=True, opts=()):
-    from sonicscribe_amd.engine import Engine
-    e = Engine(D, 0, mode, max_batch=max_batch, max_ctx=max_ctx)
-    if lp:
-        e.set_option("token_logprobs", 1)
-    for k, v in opts:
-        e.set_option(k, v)
-    if parallel:
-        e.set_option("forced_parallel", 1)
-    e.load_synthetic(SEED)
-    return e
+    return make_engine(D, mode, max_batch, max_ctx, flags((lp, "token_logprobs", 1)) + list(opts) + flags((parallel, "forced_parallel", 1)))
 
 
 def load(golden_dir, name):
-    g = np.load(os.path.join(golden_dir, name))
-    segs = [synth.synth_pcm(int(g[f"s{i}_seg_index"]), int(g[f"s{i}_n_samples"])) for i in range(2)]
-    prompts = [g[f"s{i}_prompt_ids"] for i in range(2)]
-    force = np.stack([g[f"s{i}_force_ids"] for i in range(2)]).astype(np.int32)
+    g, segs, prompts = load_golden(golden_dir, name)
+    force = forced_ids(g)
     assert force.shape == (2, N)
     return g, segs, prompts, force
 

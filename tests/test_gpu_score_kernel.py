@@ -14,38 +14,15 @@ import math
 import numpy as np
 import pytest
 
-from sonicscribe_amd import spec
+from gpu_common import make_engine, ref_log_softmax, ref_logprob, score_bound, slabs
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
-U = 2.0 ** -24
 KINDS = {"bf16": 0, "fp16": 2, "fp32": 3}
-
-
-def score_bound(V, ref64):
-    n_t = math.ceil(V / 16384) * 16
-    c = 3 * (math.ceil(n_t / 16) - 1) + 2 + 16 + 1
-    return (n_t + c + 2.25 * math.log(V)) * U + U * np.abs(ref64)
-
-
-def ref_log_softmax(logits):
-    """float64 log-softmax of fp32 logits [B][V]"""
-    l = np.asarray(logits, np.float64)
-    m = l.max(axis=-1, keepdims=True)
-    return l - (m + np.log(np.exp(l - m).sum(axis=-1, keepdims=True)))
-
-
-def ref_logprob(logits, tok):
-    return np.take_along_axis(ref_log_softmax(logits), np.asarray(tok)[..., None].astype(np.int64), axis=-1)[..., 0]
 
 
 @pytest.fixture(scope="module", params=list(KINDS))
 def eng(request):
-    from sonicscribe_amd.engine import Engine
-    e = Engine(spec.TINY, 0, KINDS[request.param], max_batch=2, max_ctx=512)
-    e.set_option("token_logprobs", 1)
-    e.set_option("forced_parallel", 1)
-    e.load_synthetic(SEED)
+    e = make_engine(mode=KINDS[request.param], max_batch=2, max_ctx=512, options=(("token_logprobs", 1), ("forced_parallel", 1)))
     e.kind = request.param
     yield e
     e.close()
@@ -66,16 +43,6 @@ def _rows(V, rng):
             ("ramp", ramp, V // 2), ("tied", tied, V // 2)]
 
 
-def _slabs(rows, ks, mpad):
-    V = rows[0].shape[0]
-    w = {1: [1.0], 2: [0.5, 0.5], 3: [0.5, 0.25, 0.25]}[ks]              # exact splits
-    s = np.zeros((ks, mpad, V), np.float32)
-    for b, r in enumerate(rows):
-        for k in range(ks):
-            s[k, b] = r * np.float32(w[k])
-    return s
-
-
 def _batch(V, B, seed):
     rng = np.random.default_rng(seed)
     kinds = _rows(V, rng)
@@ -91,7 +58,7 @@ def _batch(V, B, seed):
 def _run(e, V, B, ks, seed):
     names, rows, tgt = _batch(V, B, seed)
     mpad = (B + 15) // 16 * 16
-    s = _slabs(rows, ks, mpad)
+    s = slabs(rows, ks, mpad)
     # the argmax target is taken on the values the kernel will read: a first pass returns them (targets are then fixed for the asserted pass)
     if any(t is None for t in tgt):
         _, lg0, _ = e.test_greedy_lp(s, B, force_ids=np.zeros(B, np.int32))
@@ -168,7 +135,7 @@ def test_same_bits_whatever_the_batch(eng, K):
         def rec(rows, at):
             B = len(rows)
             force = np.full(B, 7, np.int32); force[at] = t
-            _, _, out = eng.test_greedy_lp(_slabs(rows, 1, (B + 15) // 16 * 16), B, force_ids=force)
+            _, _, out = eng.test_greedy_lp(slabs(rows, 1, (B + 15) // 16 * 16), B, force_ids=force)
             parts = [out] if K == 0 else list(out)
             return [np.ascontiguousarray(p[at]).reshape(-1).view(np.uint32) for p in parts]
         alone, of3, of65 = rec([row], 0), rec(others[:2] + [row], 2), rec(others + [row], 64)

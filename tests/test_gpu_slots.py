@@ -12,21 +12,14 @@ from dataclasses import replace
 import numpy as np
 import pytest
 
+from gpu_common import make_engine, prompt_for
 from sonicscribe_amd import frontend, spec, synth
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
-
-
-def prompt_for(d, n_samples, suf=(7, 301, 302, 303, 9, 11)):
-    return [1, 17, 23, 5] + [d.audio_token_id] * spec.audio_token_count(spec.valid_frames(n_samples)) + list(suf)
 
 
 def make(d, max_batch=8, max_ctx=512, mode=0):
-    from sonicscribe_amd.engine import Engine
-    e = Engine(d, 0, mode, max_batch=max_batch, max_ctx=max_ctx)
-    e.load_synthetic(SEED)
-    return e
+    return make_engine(d, mode, max_batch, max_ctx)
 
 
 FULLW = replace(spec.FULL, enc_layers=2, dec_layers=2, eos_ids=())      # full-width layers (256x256 GEMMs, fused decode kernels), shallow

@@ -18,6 +18,7 @@ from dataclasses import replace
 import numpy as np
 import pytest
 
+from gpu_common import make_engine
 from sonicscribe_amd import spec, synth
 
 pytestmark = pytest.mark.gpu
@@ -57,8 +58,7 @@ def test_step_forms_launch_counts_and_bit_exact_pairs():
     for R, option, _ in cases:
         got[R, option], logits[R, option] = _run(e, d, R, option)
     e.close()
-    e8 = Engine(spec.TINY, 0, MODE_INT8, max_batch=8, max_ctx=512)
-    e8.load_synthetic(20260128)
+    e8 = make_engine(mode=MODE_INT8, max_batch=8, max_ctx=512)
     got["int8", None], _ = _run(e8, spec.TINY, 2)
     e8.close()
     print("decode_launches_per_layer:", got)

@@ -8,37 +8,20 @@ families, the -1 / -inf fill) are tests/test_gpu_top_logprobs_kernel.py."""
 import numpy as np
 import pytest
 
+from gpu_common import SEED, bits, check_lp, flags, make_engine, prompt_for
 from sonicscribe_amd import spec, synth
 from sonicscribe_amd.engine import TokenScores
-from test_gpu_request_bias import check_lp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
 K = 8
 D = spec.TINY
 SEGS = [synth.synth_pcm(700 + i, n) for i, n in enumerate((48000, 200000, 80000, 64000))]
 BUDGETS = [5, 17, 11, 16]
-
-
-def prompt_for(d, n):
-    return [1, 17, 23, 5] + [d.audio_token_id] * spec.audio_token_count(spec.valid_frames(n)) + [7, 301, 302, 303, 9, 11]
-
-
 PROMPTS = [prompt_for(D, len(s)) for s in SEGS]
 
 
 def make(k=K, max_batch=4):
-    from sonicscribe_amd.engine import Engine
-    e = Engine(D, 0, 0, max_batch=max_batch, max_ctx=1024)
-    e.set_option("token_logprobs", 1)
-    if k:
-        e.set_option("top_logprobs", k)
-    e.load_synthetic(SEED)
-    return e
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+    return make_engine(D, 0, max_batch, 1024, [("token_logprobs", 1)] + flags((k, "top_logprobs", k)))
 
 
 def same(a: TokenScores, b: TokenScores):

@@ -14,14 +14,13 @@ vocabulary), 1 and 2 slabs.  Rows are uniform(-4, 4) cut to bf16 precision: abou
 import numpy as np
 import pytest
 
-from sonicscribe_amd import spec
+from gpu_common import SEED, check_lp, make_engine, same_bits, slabs
 from sonicscribe_amd.genconfig import GenerationGuards
 from sonicscribe_amd.reqbias import RequestBias
-from test_gpu_request_bias import _histories, check_lp  # noqa: E402
-from test_gpu_sampling_kernel import bf16_exact, same_bits, slabs  # noqa: E402
+from test_gpu_request_bias import _histories  # noqa: E402
+from test_gpu_sampling_kernel import bf16_exact  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
 B = 4
 K = 8
 NEG = np.float32("-inf")
@@ -34,9 +33,7 @@ GUARDS = GenerationGuards(repetition_penalty=1.3, no_repeat_ngram_size=2)
 @pytest.fixture(scope="module")
 def eng():
     """one bf16 handle; the option is switched between launches (the hooks leave no work in hand)"""
-    from sonicscribe_amd.engine import Engine
-    e = Engine(spec.TINY, 0, 0, max_batch=B, max_ctx=1024)
-    e.load_synthetic(SEED)
+    e = make_engine(max_batch=B)
     e.set_option("token_logprobs", 1)
     yield e
     e.close()

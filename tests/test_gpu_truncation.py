@@ -5,38 +5,15 @@ kernel test's rule 3."""
 import numpy as np
 import pytest
 
+from gpu_common import flags, make_engine, same_bits, six
 from sonicscribe_amd import sampling, spec, synth
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
 CUT = (5, 0.9, 0.05)
 
 
-def prompt_for(d, n):
-    return [1, 17, 23, 5] + [d.audio_token_id] * spec.audio_token_count(spec.valid_frames(n)) + [7, 301, 302, 303, 9, 11]
-
-
 def make(mode=0, trunc=True, samp=True, max_batch=8):
-    from sonicscribe_amd.engine import Engine
-    e = Engine(spec.TINY, 0, mode, max_batch=max_batch, max_ctx=1024)
-    e.set_option("token_logprobs", 1)
-    if samp:
-        e.set_option("sampling", 1)
-    if trunc:
-        e.set_option("truncation", 1)
-    e.load_synthetic(SEED)
-    return e
-
-
-def _same_bits(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.dtype == b.dtype == np.float32 and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def _six():
-    d = spec.TINY
-    segs = [synth.synth_pcm(700 + i, n) for i, n in enumerate((48000, 200000, 80000, 64000, 120000, 96000))]
-    return segs, [prompt_for(d, len(s)) for s in segs]
+    return make_engine(spec.TINY, mode, max_batch, 1024, [("token_logprobs", 1)] + flags((samp, "sampling", 1), (trunc, "truncation", 1)))
 
 
 @pytest.fixture(scope="module")
@@ -49,7 +26,7 @@ def eng():
 @pytest.fixture(scope="module")
 def solo(eng):
     """request 5 at (t, seed, CUT), alone: what every other path must reproduce; and the same request untruncated and greedy"""
-    segs, prompts = _six()
+    segs, prompts = six()
     ids, _, lp = eng.transcribe_batch([segs[5]], [prompts[5]], [15], want_logprobs=True, request_sampling=[(1.0, 77) + CUT])
     free, _, _ = eng.transcribe_batch([segs[5]], [prompts[5]], [15], want_logprobs=True, request_sampling=[(1.0, 77)])
     greedy, _, glp = eng.transcribe_batch([segs[5]], [prompts[5]], [15], want_logprobs=True)
@@ -60,27 +37,27 @@ def solo(eng):
 @pytest.mark.parametrize("mode", [0, 1, 2, 3], ids=["bf16", "int8", "f16", "f32"])
 def test_a_prefix_of_one_is_greedy(mode):
     """top_p = 1e-6 at t = 0.8 emits the greedy row's ids and log-probability bits: a prefix of one id is the first maximum; every kind goes through the same greedy_args"""
-    segs, prompts = _six()
+    segs, prompts = six()
     e = make(mode)
     try:
         g, _, glp = e.transcribe_batch(segs[:3], prompts[:3], [10, 10, 10], want_logprobs=True)
         ids, _, lp = e.transcribe_batch(segs[:3], prompts[:3], [10, 10, 10], want_logprobs=True, request_sampling=[(0.8, 5, 0, 1e-6, 0.0), (0.8, 6, 40, 1e-6, 0.0), (0.8, 7, 0, 1e-6, 0.3)])
         for r in range(3):
-            assert np.array_equal(ids[r], g[r]) and _same_bits(lp[r], glp[r]), (mode, r)
+            assert np.array_equal(ids[r], g[r]) and same_bits(lp[r], glp[r]), (mode, r)
     finally:
         e.close()
 
 
 def test_same_bits_on_the_graph_and_the_eager_path_and_the_replay(eng, solo):
-    segs, prompts = _six()
+    segs, prompts = six()
     want_ids, want_lp, _, _ = solo
     budgets = [5, 17, 11, 9, 13, 15]
     samp = [(0.7, 11, 50, 0.9, 0.0), (1.0, 12), (0.0, 13, 3, 0.5, 0.5), (0.3, 14, 0, 1.0, 0.2), None, (1.0, 77) + CUT]
     ids_b, _, lp_b = eng.transcribe_batch(segs, prompts, budgets, want_logprobs=True, request_sampling=samp)                         # row 5 of a batch, hipGraph chunks
-    assert np.array_equal(ids_b[5], want_ids) and _same_bits(lp_b[5], want_lp)
+    assert np.array_equal(ids_b[5], want_ids) and same_bits(lp_b[5], want_lp)
     ids_e, logits, lp_e = eng.transcribe_batch(segs, prompts, budgets, want_logits=True, want_logprobs=True, request_sampling=samp)   # ... and eager
     for r in range(6):
-        assert np.array_equal(ids_e[r], ids_b[r]) and _same_bits(lp_e[r], lp_b[r]), r
+        assert np.array_equal(ids_e[r], ids_b[r]) and same_bits(lp_e[r], lp_b[r]), r
     # neighbouring rows keep their own values: row 1 (a pair) and row 4 (None) are the untruncated and the greedy run of their request
     one, _ = eng.transcribe_batch([segs[1]], [prompts[1]], [17], request_sampling=[(1.0, 12)])
     four, _ = eng.transcribe_batch([segs[4]], [prompts[4]], [13])
@@ -108,13 +85,13 @@ def test_same_bits_on_the_graph_and_the_eager_path_and_the_replay(eng, solo):
 
 
 def test_step_wise_spliced_and_forked(eng, solo):
-    segs, prompts = _six()
+    segs, prompts = six()
     want_ids, want_lp, _, _ = solo
     # prefill / decode_step / fetch_tokens
     eng.stage_pcm([segs[5]]); eng.prefill([prompts[5]], [15], request_sampling=[(1.0, 77) + CUT])
     eng.decode_step(100)
     ids, lp = eng.fetch_tokens(1, 15, want_logprobs=True)
-    assert np.array_equal(ids[0], want_ids) and _same_bits(lp[0], want_lp)
+    assert np.array_equal(ids[0], want_ids) and same_bits(lp[0], want_lp)
     # a prefill without staged words after one with them is untruncated
     free, _, flp = eng.transcribe_batch([segs[5]], [prompts[5]], [15], want_logprobs=True, request_sampling=[(1.0, 77)])
     assert not np.array_equal(free[0], want_ids)
@@ -134,28 +111,28 @@ def test_step_wise_spliced_and_forked(eng, solo):
                     got[r] = (x, y)
             if len(got) == 2:
                 break
-        assert len(got) == 2 and np.array_equal(got[6][0], want_ids) and _same_bits(got[6][1], want_lp)
+        assert len(got) == 2 and np.array_equal(got[6][0], want_ids) and same_bits(got[6][1], want_lp)
     finally:
         eng.service_end()
         pre.close()
     # forks [3, 1] with per-fork values: rows 0, 2, 3 are request 5's forks, row 1 is request 0
     rows = [(1.0, 77) + CUT, (0.5, 3, 2, 1.0, 0.0), (1.0, 77), (1.0, 78) + CUT]
     ids, _, lp = eng.transcribe_batch([segs[5], segs[0]], [prompts[5], prompts[0]], [15, 5], want_logprobs=True, request_sampling=rows, forks=[3, 1])
-    assert np.array_equal(ids[0], want_ids) and _same_bits(lp[0], want_lp)
-    assert np.array_equal(ids[2], free[0]) and _same_bits(lp[2], flp[0])
+    assert np.array_equal(ids[0], want_ids) and same_bits(lp[0], want_lp)
+    assert np.array_equal(ids[2], free[0]) and same_bits(lp[2], flp[0])
     other, _, olp = eng.transcribe_batch([segs[5]], [prompts[5]], [15], want_logprobs=True, request_sampling=[(1.0, 78) + CUT])
-    assert np.array_equal(ids[3], other[0]) and _same_bits(lp[3], olp[0])
+    assert np.array_equal(ids[3], other[0]) and same_bits(lp[3], olp[0])
 
 
 def test_through_the_native_dispatcher_and_the_python_one(eng, solo):
     """the (t, seed, 5, 0.9, 0.05) request among pairs and greedy requests on both continuous schedulers: its solo run's ids and log-probability bits"""
     from sonicscribe_amd.dispatch import Dispatcher
-    segs, prompts = _six()
+    segs, prompts = six()
     want_ids, want_lp, _, _ = solo
     budgets = [5, 17, 11, 9, 13, 15]
     samp = [(0.7, 11, 50, 0.9, 0.0), (1.0, 12), None, (0.3, 14, 0, 1.0, 0.2), (0.0, 15, 3, 0.5, 0.5), (1.0, 77) + CUT]
     ids_b, _, lp_b = eng.transcribe_batch(segs, prompts, budgets, want_logprobs=True, request_sampling=samp)
-    assert np.array_equal(ids_b[5], want_ids) and _same_bits(lp_b[5], want_lp)
+    assert np.array_equal(ids_b[5], want_ids) and same_bits(lp_b[5], want_lp)
     for native in (False, True):
         slots = [eng.slot(), eng.slot()]
         disp = Dispatcher([eng], slots=[slots], continuous=True, native=native)
@@ -168,7 +145,7 @@ def test_through_the_native_dispatcher_and_the_python_one(eng, solo):
             for s in slots:
                 s.close()
         for i in range(6):
-            assert np.array_equal(res[i][0], ids_b[i]) and _same_bits(res[i][1], lp_b[i]), (native, i)
+            assert np.array_equal(res[i][0], ids_b[i]) and same_bits(res[i][1], lp_b[i]), (native, i)
 
 
 def test_model_keywords_end_to_end():
@@ -190,11 +167,11 @@ def test_model_keywords_end_to_end():
         cut = m.submit(wav, max_new_tokens=12, detailed=True, temperature=1.0, seed=5).result(timeout=60)                        # the constructor's defaults
         same = m.submit(wav, max_new_tokens=12, detailed=True, temperature=1.0, seed=5, top_k=5, top_p=0.9, min_p=0.0).result(timeout=60)
         assert (free.top_k, free.top_p, free.min_p) == (0, 1.0, 0.0) and (cut.top_k, cut.top_p, cut.min_p) == (5, 0.9, 0.0)
-        assert np.array_equal(cut.token_ids, same.token_ids) and _same_bits(cut.token_logprobs, same.token_logprobs)
+        assert np.array_equal(cut.token_ids, same.token_ids) and same_bits(cut.token_logprobs, same.token_logprobs)
         assert not np.array_equal(cut.token_ids, free.token_ids), "the cut changed nothing at t = 1: the test shows nothing"
         one = m.submit(wav, max_new_tokens=12, detailed=True, temperature=1.0, seed=5, top_p=1e-6).result(timeout=60)             # a prefix of one: the greedy transcript
         greedy = m.submit(wav, max_new_tokens=12, detailed=True).result(timeout=60)
-        assert np.array_equal(one.token_ids, greedy.token_ids) and _same_bits(one.token_logprobs, greedy.token_logprobs) and (greedy.top_k, greedy.top_p) == (0, 1.0)
+        assert np.array_equal(one.token_ids, greedy.token_ids) and same_bits(one.token_logprobs, greedy.token_logprobs) and (greedy.top_k, greedy.top_p) == (0, 1.0)
         assert m.transcribe_batch([wav], max_new_tokens=12, temperature=1.0, seed=5) == [cut.text]
         info = m.transcribe(wav, max_new_tokens=12, return_debug_info=True, temperature=1.0, seed=5, min_p=0.01)
         assert (info["top_k"], info["top_p"], info["min_p"]) == (5, 0.9, 0.01)
@@ -205,7 +182,7 @@ def test_model_keywords_end_to_end():
 def test_memory_and_refusals():
     from sonicscribe_amd.engine import DTYPE_F32, SonicError
     import ctypes as C
-    segs, prompts = _six()
+    segs, prompts = six()
     e = make(trunc=False, samp=False, max_batch=32)      # (32 rows: the bulk pipeline's block, for its refusal below)
     try:
         with pytest.raises(SonicError, match="sampling"):                     # refused by name unless sampling is on

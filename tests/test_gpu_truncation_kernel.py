@@ -11,64 +11,34 @@ Every row is held to five rules (check_row):
   5. log-probability          out_lp is within the existing lp_bound of log_softmax(s)[tok] over the untruncated scores
 Logit scales: Zipf-like rows s = -1.5 ln(rank) (+ jitter), for which the id at the 0.9 boundary carries about 1e-3 of the mass - forty times EPS_MASS - so the
 reference alone is unambiguous on almost every row; and rows with a few dominant ids whose cut is unambiguous by a wide margin."""
-import math
-
 import numpy as np
 import pytest
 
-from sonicscribe_amd import sampling, spec
+from gpu_common import lp_bound, make_engine, ref_logprob, same_bits, slabs
+from sonicscribe_amd import sampling
 from sonicscribe_amd.genconfig import GenerationGuards
 from sonicscribe_amd.grammar import Grammar
 from sonicscribe_amd.reqbias import RequestBias
 
 pytestmark = pytest.mark.gpu
-SEED = 20260128
-U = 2.0 ** -24
 NEG = float("-inf")
 MODES = pytest.mark.parametrize("mode", [0, 2, 3], ids=["bf16", "f16", "f32"])
 OFF = (0, 1.0, 0.0)
 
 
-def lp_bound(V, ref64):
-    """the existing log-probability tests' bound (tests/test_gpu_request_bias.py)"""
-    n_t = math.ceil(V / 4096) * 4
-    c = 3 * (math.ceil(n_t / 16) - 1) + 2 + 16 + 1
-    return (n_t + c + 2.25 * math.log(V)) * U + U * np.abs(ref64)
-
-
 def check_lp(tag, lp, processed, tok):
-    l = np.asarray(processed, np.float64)
-    m = l.max()
-    ref = l[int(tok)] - (m + np.log(np.exp(l - m).sum()))
-    ratio = abs(float(lp) - ref) / lp_bound(len(l), ref)
+    ref = ref_logprob(processed, tok)
+    ratio = abs(float(lp) - ref) / lp_bound(len(processed), ref)
     assert np.isfinite(lp) and ratio <= 1.0, (tag, float(lp), ref, ratio)
-
-
-def slabs(rows, ks):
-    V, mpad = rows[0].shape[0], max(16, len(rows))
-    w = {1: [1.0], 2: [0.5, 0.5]}[ks]
-    s = np.zeros((ks, mpad, V), np.float32)
-    for b, r in enumerate(rows):
-        for k in range(ks):
-            s[k, b] = r * np.float32(w[k])
-    return s
-
-
-def same_bits(a, b):
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 @pytest.fixture(scope="module")
 def engines():
-    from sonicscribe_amd.engine import Engine
     es = {}
 
     def get(mode):
         if mode not in es:
-            e = Engine(spec.TINY, 0, mode, max_batch=4, max_ctx=1024)      # the hook takes everything as arguments: no option plays a part in it
-            e.load_synthetic(SEED)
-            es[mode] = e
+            es[mode] = make_engine(mode=mode)                              # the hook takes everything as arguments: no option plays a part in it
         return es[mode]
     yield get
     for e in es.values():
@@ -271,12 +241,8 @@ def test_rows_off_and_row_independence(engines, family, mode):
 def test_with_top_logprobs(family, mode):
     """option top_logprobs = 8 on the handle: the hooks launch the TRUNC x TOPK instantiations.  The alternatives and out_lp carry the bits of the untruncated
     launch (the cut changes the draw, never the record), and the token obeys rule 4"""
-    from sonicscribe_amd.engine import Engine
-    eng = Engine(spec.TINY, 0, mode, max_batch=4, max_ctx=1024)
+    eng = make_engine(mode=mode, options=(("token_logprobs", 1), ("top_logprobs", 8)))
     try:
-        eng.set_option("token_logprobs", 1)
-        eng.set_option("top_logprobs", 8)
-        eng.load_synthetic(SEED)
         V = 16388
         rng = np.random.default_rng(33)
         hist, hlen, guards, tables = _family(V, family, rng)

@@ -7,6 +7,7 @@ import threading
 import numpy as np
 import pytest
 
+from gpu_common import make_engine
 from sonicscribe_amd import spec, synth, vad_net
 
 pytestmark = pytest.mark.gpu
@@ -26,9 +27,7 @@ def vad():
 
 @pytest.fixture(scope="module")
 def eng():
-    from sonicscribe_amd.engine import Engine
-    e = Engine(spec.TINY, 0, max_batch=2, max_ctx=512)
-    e.load_synthetic(20260128)
+    e = make_engine(max_batch=2, max_ctx=512)
     yield e
     e.close()
 

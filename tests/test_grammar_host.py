@@ -7,6 +7,7 @@ import re
 import numpy as np
 import pytest
 
+import abi_pins
 from sonicscribe_amd import engine, genconfig
 from sonicscribe_amd.genconfig import GenerationGuards
 from sonicscribe_amd.grammar import MAX_EDGES, MAX_NODES, CompiledGrammar, Grammar
@@ -161,18 +162,11 @@ def test_prefix_allowed_tokens_fn_follows_the_generated_ids():
 
 # ------------------------------------------------------------------------------------------ ABI surface and Python refusals
 def test_abi_surface():
-    """the feature adds no entry point (the header, the binding table and exports.map keep their names, 103 today; the ABI stays 12): a grammar is loaded as an int32
-    tensor and everything else is an option of the handle"""
-    hdr = open(os.path.join(ROOT, "include", "sonic_hip.h")).read()
-    emap = open(os.path.join(ROOT, "sonicscribe_amd", "csrc", "exports.map")).read()
-    assert "global: sonic_*" in emap
-    declared = set(re.findall(r"\b(sonic_[a-z_0-9]+)\s*\(", hdr))
-    assert len(engine.EXPORTS) == 103 == len(declared) and set(engine.EXPORTS) == declared and engine.EXPORTS == list(engine.SIGNATURES)
-    assert "#define SONIC_ABI_VERSION 12" in hdr and engine.ABI_VERSION == 12
-    assert "SONIC_DTYPE_I32 = 2" in hdr and engine.DTYPE_I32 == 2 and '"grammar:<id>"' in hdr and '"grammar.hook:<V>"' in hdr and '"grammar.dispatch:<id>"' in hdr
-    src = open(os.path.join(ROOT, "sonicscribe_amd", "csrc", "engine_options.cpp")).read()
-    for key in ("grammar", "request_grammar_begin", "request_grammar", "hook_grammar_state", "hook_grammar_eos"):
-        assert '{"%s", APPLY(opt_%s)}' % (key, key) in src and key in hdr, key
+    """the feature adds no entry point (the header, the binding table and exports.map keep their names and the ABI its version: tests/abi_pins.py): a grammar is
+    loaded as an int32 tensor and everything else is an option of the handle"""
+    abi_pins.check_surface(options=("grammar", "request_grammar_begin", "request_grammar", "hook_grammar_state", "hook_grammar_eos"),
+                           header_strings=("SONIC_DTYPE_I32 = 2", '"grammar:<id>"', '"grammar.hook:<V>"', '"grammar.dispatch:<id>"'))
+    assert engine.DTYPE_I32 == 2
     import test_binding_signatures
     assert test_binding_signatures.mismatches(engine.SIGNATURES) == []
     k = open(os.path.join(ROOT, "sonicscribe_amd", "csrc", "greedy.hip")).read()

@@ -3,33 +3,21 @@ bound at version 12; the result object's mean covers every emitted token (EOS in
 `want_logprobs` request to (ids, log-probabilities) over stub engines and leave the other requests - and engines that never heard of the keyword -
 alone; `detailed=True` on a model without the flag raises.  The GPU half is tests/test_gpu_logprobs.py."""
 import math
-import os
-import re
 import threading
 from concurrent.futures import Future
 
 import numpy as np
 import pytest
 
-from sonicscribe_amd import asr, engine
+import abi_pins
+from sonicscribe_amd import asr
 from sonicscribe_amd.dispatch import Dispatcher, Request
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["sonic_fetch_logprobs", "sonic_fetch_rows_lp", "sonic_dispatch_next_lp", "sonic_pipeline_submit_lp", "sonic_test_greedy_lp"]
 
 
 def test_abi_header_exports_and_binding_agree():
-    hdr = open(os.path.join(ROOT, "include", "sonic_hip.h")).read()
-    declared = set(re.findall(r"\b(sonic_[a-z_0-9]+)\s*\(", hdr))
-    for name in NEW:
-        assert name in declared and name in engine.EXPORTS, name
-    assert engine.ABI_VERSION == 12 == int(re.search(r"#define SONIC_ABI_VERSION (\d+)", hdr).group(1))
-    assert "global: sonic_*" in open(os.path.join(ROOT, "sonicscribe_amd", "csrc", "exports.map")).read()
-    assert "connection_manager.py:159,274" in hdr                      # the reference interface the new entries stand in for
-    if os.path.exists(engine.LIB_PATH):
-        import ctypes as C
-        lib = C.CDLL(engine.LIB_PATH)
-        assert lib.sonic_abi_version() == 12 and all(hasattr(lib, n) for n in NEW)
+    abi_pins.check_surface(names=NEW, header_strings=("connection_manager.py:159,274",))      # the reference interface the new entries stand in for
 
 
 def test_transcription_object():

@@ -1,22 +1,16 @@
 """Per-request sequence bias, host side (sonicscribe_amd/reqbias.py): RequestBias.apply against HF's own SequenceBiasLogitsProcessor and
 NoBadWordsLogitsProcessor, bit for bit; the chain order against HF's LogitsProcessorList; caps and validation; the hotword policy; the ABI surface; the Python
 statement of the continuous dispatcher with stub engines."""
-import os
-import re
 import threading
 
 import numpy as np
 import pytest
 
+import abi_pins
+from gpu_common import bits
 from sonicscribe_amd import engine, reqbias
 from sonicscribe_amd.genconfig import GenerationGuards
 from sonicscribe_amd.reqbias import RequestBias
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def hf_bias(sequence_bias, bad_words, eos, scores, hist):
@@ -164,14 +158,8 @@ def test_hotword_policy_with_a_stub_tokenizer():
 
 
 def test_abi_surface():
-    names = ("sonic_set_request_bias", "sonic_dispatch_submit_bias", "sonic_test_greedy_bias")
-    hdr = open(os.path.join(ROOT, "include", "sonic_hip.h")).read()
-    emap = open(os.path.join(ROOT, "sonicscribe_amd", "csrc", "exports.map")).read()
-    pat = re.search(r"global:\s*([^;]+);", emap).group(1).strip()
-    for n in names:
-        assert re.search(r"SONIC_API int " + n + r"\(", hdr) and n in engine.EXPORTS and re.fullmatch(pat.replace("*", ".*"), n)
-    assert re.search(r"#define SONIC_ABI_VERSION 12\b", hdr) and engine.ABI_VERSION == 12
-    assert all(hasattr(engine.Engine, m) for m in ("set_request_bias", "test_greedy_bias"))
+    abi_pins.check_surface(names=("sonic_set_request_bias", "sonic_dispatch_submit_bias", "sonic_test_greedy_bias"),
+                           engine_methods=("set_request_bias", "test_greedy_bias"))
     ids, off, b, req = engine.pack_request_bias([None, RequestBias([[[5, 6], 1.0], [[7], 2.0]]), RequestBias(), RequestBias(bad_words_ids=[[9]])])
     assert req.tolist() == [0, 0, 2, 2, 3] and off.tolist() == [0, 2, 3, 4] and ids.tolist() == [5, 6, 7, 9] and b[:2].tolist() == [1.0, 2.0] and np.isneginf(b[2])
 

@@ -2,14 +2,13 @@
 that order, its tie rules and edge rows, the range checks by name, the calls Engine makes for pairs and for 5-tuples (on a recording library), and the pinned
 counts of the C ABI."""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 
 from concurrent.futures import Future
 
+import abi_pins
 from sonicscribe_amd import asr, engine, fallback, reqvalues, sampling, spec
 from sonicscribe_amd.dispatch import Request, _BulkReplica
 
@@ -297,9 +296,5 @@ def test_refusals_name_sampling_and_bulk():
 
 # ------------------------------------------------------------------------------------------ the C ABI's pins
 def test_abi_counts_hold():
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    assert len(engine.EXPORTS) == 103
-    header = open(os.path.join(root, "include", "sonic_hip.h")).read()
-    assert re.search(r"#define\s+SONIC_ABI_VERSION\s+12\b", header)
-    assert len(re.findall(r"\bSONIC_API\b[^;]*?\bsonic_\w+\s*\(", header)) == 103 and engine.EXPORTS == list(engine.SIGNATURES)
+    abi_pins.check_surface()
     assert "truncation" not in engine.MIRRORED_OPTIONS and len(engine.MIRRORED_OPTIONS) == 8
