@@ -518,6 +518,17 @@ SONIC_API int sonic_stage_mixed(sonic_engine* e, const int16_t* host_pcm, const 
  *   "forced_fanout" = N (1 .. max_batch, default 1; read as a parallel run starts): the call's R sequences are R / N audio requests with N candidate sequences
  *   each - sequence r takes its audio rows from audio request r / N, req_win has R / N + 1 entries (NULL: W == R / N), and log-mel, encoder and projector run once
  *   per audio request.  R not divisible by N: SONIC_ERR_INVALID.  Each sequence prefills its own prompt; only the encoder is shared.
+ *   "forced_share_prompt" = 1 (default 0; read as a parallel run starts; adds no entry point and no struct): the N sequences of a group also share ONE
+ *   prefill of their prompt.  The first sequence of a group is packed as ever, prompt || ids[0 .. L - 1), in its cache row; every other one packs only ids[0 .. L - 1)
+ *   (L - 1 rows at positions P .. P + L - 2 of its own cache row; none for L = 1), and its attention reads keys [0, P) from the first one's row.  Token 0 of every
+ *   sequence of a group is scored from the first one's hidden row P - 1, token n >= 1 from the sequence's own row.  The run counts A * P + sum(L_r - 1) tokens against
+ *   one prefill where it counted sum(P + L_r - 1); results, the EOS rule and R <= max_batch are what they were, rows end with kv_len = P + L - 1.  Not bit-equal to the
+ *   unshared form (the attention's key tiles differ).  Refusals (SONIC_ERR_INVALID naming forced_share_prompt): set without "forced_parallel" (which can then not be
+ *   switched off), on an int8 handle, on the fp32 kind, beside "forced_align" (either way round), while the handle has work in hand; at the run, the sequences of a
+ *   group bringing different prompt ids (the message names the first two that differ).  Slots copy it.  sonic_debug_read "score_tokens" (1 value): the packed tokens
+ *   of the handle's last parallel forced run, in either form.
+ *   test hook: sonic_load_tensor "share_prompt.hook" (int32 [2][B]: pre_row | pre_len) arms the next sonic_test_prefill_attention on the handle: sequence b's keys
+ *   [0, pre_len[b]) are then those of cache row pre_row[b] (0 <= pre_row < B, 0 <= pre_len <= kv_len - q_len), through the builder the run uses.
  *   refusals (SONIC_ERR_INVALID, the message naming the cause): prompts and forced ids together beyond one prefill (the message says how many tokens were asked
  *   and how many fit); the audio placeholder id among the forced ids; and the existing checks (placeholder count, vocabulary, prompt + max_new <= max_ctx).
  *   "forced_parallel" is refused while the handle has work in hand (the rule of sonic_set_generation).  Slots copy it from their owner; it may also be set on a
@@ -707,7 +718,7 @@ SONIC_API int sonic_debug_ktrace(sonic_engine* e, int64_t* out, int64_t n);
  * "decode_attn_occ2" (experiments that lost: profiles/round6_*), "f32_synth_bf16" (SONIC_MODE_F32: sonic_load_synthetic writes the bf16-rounded values),
  * "inject_dev_err" (tests: sets / clears the device error word); "token_logprobs" (not an experiment: per-token log-probabilities, see sonic_fetch_logprobs);
  * "top_logprobs" (not an experiment either: the K best alternatives of every step in the same records, see sonic_fetch_logprobs);
- * "forced_parallel", "forced_fanout", "score_chunk_rows" (not experiments: forced runs as one prefill pass - scoring given transcripts - see sonic_set_forced_ids);
+ * "forced_parallel", "forced_fanout", "forced_share_prompt", "score_chunk_rows" (not experiments: forced runs as one prefill pass - scoring given transcripts - see sonic_set_forced_ids);
  * "forced_align", "align_head" (not experiments: word timestamps on that pass, see sonic_set_forced_ids);
  * "draft_verify" (not an experiment: a request's draft is verified in its prefill pass, see sonic_set_forced_ids) */
 SONIC_API int sonic_set_option(sonic_engine* e, const char* key, int value);

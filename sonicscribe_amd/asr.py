@@ -75,9 +75,12 @@ def check_best_of(best_of, max_batch: int, sampling: bool = True, bulk: bool = F
 # The constructor's refusals of a feature without what it needs: (feature, does the model `m` break the rule, the text).  ASRModel.__init__ walks them feature by
 # feature, top to bottom, each feature behind the check of its own values - so, for a call that breaks two rules, in this order: mode, top_logprobs
 # (check_top_logprobs: range, token_logprobs, bulk), the values of temperature / seed / thresholds, "temperature", the values of top_k / top_p / min_p, "truncation",
-# "sampling", best_of (check_best_of: range, sampling, bulk), "grammar", "draft_verify", "scoring", timestamps (timestamps.check_timestamps), the device - all ahead
+# "sampling", best_of (check_best_of: range, sampling, bulk), "grammar", "draft_verify", "scoring", score_share_prompt (check_share_prompt), timestamps (timestamps.check_timestamps), the device - all ahead
 # of any engine.  "request_bias" alone comes behind the loading: the defaults that switch it on are checked against the checkpoint's vocabulary.
 _NEEDS_SAMPLING = " need a model built with sampling=True (ASRModel(..., token_logprobs=True, sampling=True))"
+# (the two models whose scoring handles cannot share a prompt, DESIGN.md 6.14: the constructor and score(..., share_prompt=True) say the same)
+_SHARE_INT8 = "share_prompt is not supported with mode='int8': its prefill finds outlier columns per sequence, and a shared prompt belongs to several"
+_SHARE_ALIGN = "share_prompt is not supported on a model built with timestamps=True: its scoring handles align, and the alignment reads a sequence's audio keys from its own rows"
 _REFUSALS = (
     ("temperature", lambda m: not m.sampling and (any(t != 0.0 for t in sampling_.temperatures(m._default_temperature)[0]) or m._default_seed != 0), "temperature / seed" + _NEEDS_SAMPLING),
     ("truncation", lambda m: not m.sampling and m._default_cut != NO_CUT, "top_k / top_p / min_p" + _NEEDS_SAMPLING),
@@ -92,6 +95,17 @@ _REFUSALS = (
 )
 
 
+def check_share_prompt(share, scoring: bool, mode: str, timestamps: bool) -> bool:
+    """score_share_prompt as ASRModel takes it: ValueError without scoring=True, with mode="int8" and with timestamps=True"""
+    if not share:
+        return False
+    if not scoring:
+        raise ValueError("score_share_prompt=True needs scoring=True: it is the scoring handle's prefill that shares the prompt (ASRModel(..., token_logprobs=True, scoring=True, score_share_prompt=True))")
+    if mode == "int8" or timestamps:
+        raise ValueError(_SHARE_INT8 if mode == "int8" else _SHARE_ALIGN)
+    return True
+
+
 def _flatten(windows_per_request):
     """windows per request -> (all windows in a row, req_win: request i owns windows req_win[i] .. req_win[i + 1] - 1), as Engine.transcribe_batch / score_batch take them"""
     segs, req_win = [], [0]
@@ -104,7 +118,8 @@ def _flatten(windows_per_request):
 # --------------------------------------------------------------------------------------- façade
 class ASRModel:
     # the feature flags' "off" values: what a model reads that was never built (the host tests make one with ASRModel.__new__ and set what they need)
-    sampling = grammar = draft_verify = request_bias = scoring = timestamps = bulk = token_logprobs = continuous = False
+    sampling = grammar = draft_verify = request_bias = scoring = score_share_prompt = timestamps = bulk = token_logprobs = continuous = False
+    mode = "native"
     top_logprobs, best_of, slots = 0, 1, 1
 
     def __init__(self, checkpoint_dir: str, device: str = "cuda", mode: str = "native",
@@ -113,7 +128,7 @@ class ASRModel:
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None,
                  request_bias: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: float = 0.0,
                  sampling: bool = False, temperature=0.0, seed: int = 0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0, compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0, best_of: int = 1,
-                 scoring: bool = False, timestamps: bool = False, alignment_heads=None, grammar: bool = False, draft_verify: bool = False,
+                 scoring: bool = False, score_share_prompt: bool = False, timestamps: bool = False, alignment_heads=None, grammar: bool = False, draft_verify: bool = False,
                  _dims: Optional[ModelDims] = None,
                  _synthetic_seed: Optional[int] = None, _allow_synthetic_prompt: bool = False, _options: Optional[Dict[str, int]] = None,
                  _engine_mode: Optional[int] = None):
@@ -126,7 +141,8 @@ class ASRModel:
         ladder), `seed` and the two thresholds of the ladder here are the defaults of every call.  `best_of` = N in 2 .. max_batch (needs sampling=True; not with bulk=True): Whisper's
         best_of - every attempt at a temperature above 0 draws N samples and keeps the one with the highest avg_logprob; the N samples are the rows of one forked run
         (one encoder pass, one prefill) on one further handle per replica; N is the default of the `best_of=` of transcribe / submit / transcribe_batch.  `scoring` (needs token_logprobs=True): score() / score_batch() give the log-probability of transcripts the caller
-        brings, in one prefill pass per run on a handle of their own per replica; off, no such handle exists.  `timestamps` (needs scoring=True): align() and
+        brings, in one prefill pass per run on a handle of their own per replica; off, no such handle exists.  `score_share_prompt` (needs scoring=True; not with
+        mode="int8", not with timestamps=True): the candidates of one audio also share ONE prefill of their prompt - the default of the `share_prompt=` of score() / score_batch().  `timestamps` (needs scoring=True): align() and
         word_timestamps=True give the time at which every token and word was spoken, from the decoder's attention onto the audio on that scoring handle (DESIGN.md 6.9);
         `grammar` (needs token_logprobs=True; not with bulk=True): requests may be
         restricted to the transcripts of a grammar - compile_grammar() of a phrase list or of a grammar.Grammar, passed as `grammar=` of the transcribe calls; the mask and
@@ -150,6 +166,7 @@ class ASRModel:
         self.best_of = check_best_of(best_of, max_batch, self.sampling, bulk)
         self._max_batch = int(max_batch)
         self._refuse("grammar", "draft_verify", "scoring")
+        self.score_share_prompt = check_share_prompt(score_share_prompt, self.scoring, mode, self.timestamps)
         self._grammars: List[Any] = []      # what compile_grammar() made, closed with the model
         self.alignment_heads = timestamps_.check_timestamps(self.timestamps, self.scoring, alignment_heads, *((_dims.dec_layers, _dims.dec_heads) if _dims is not None else ()))
         dev = str(device)
@@ -661,36 +678,46 @@ class ASRModel:
             return [int(t) for t in self.prompt.processor.tokenizer.encode(cand, add_special_tokens=False)]
         return [int(t) for t in np.asarray(cand).reshape(-1)]
 
-    def score(self, audio, candidates, sampling_rate: int = 16000, hotwords: Optional[List[str]] = None, append_eos: bool = True) -> List["Score"]:
+    def share_prompt_refusal(self) -> Optional[str]:
+        """why this model's scoring handles cannot share a prompt, or None: the library refuses the same by the option's name"""
+        return _SHARE_INT8 if self.mode == "int8" else _SHARE_ALIGN if self.timestamps else None
+
+    def score(self, audio, candidates, sampling_rate: int = 16000, hotwords: Optional[List[str]] = None, append_eos: bool = True,
+              share_prompt: Optional[bool] = None) -> List["Score"]:
         """The log-probability of each candidate transcript given the audio: n-best / hotword-list rescoring, keyword verification, comparing an edited
         transcript with the greedy one.  A candidate is a string (tokenised with the checkpoint's tokenizer) or a sequence of token ids.  The prompt is the one
         transcribe() builds (same hotword sentence, same audio-token count); all candidates share one encoder pass.  append_eos: the first EOS id is appended as a
         last target, so that hypotheses of different length compare as HF's sequence scores do.  The scores are those of the raw model distribution at temperature
-        1: no logits processor (repetition penalty, bias, ...) is applied, whatever the model carries.  Needs a model built with scoring=True."""
-        return self.score_batch([audio], [candidates], sampling_rate, hotwords, append_eos)[0]
+        1: no logits processor (repetition penalty, bias, ...) is applied, whatever the model carries.  Needs a model built with scoring=True.  share_prompt (None: the
+        model's score_share_prompt): the candidates also share one prefill of the prompt, so a long list costs its candidates' own tokens and fits fewer runs
+        (DESIGN.md 6.14); the scores agree with the unshared ones to the attention's rounding, not bit for bit."""
+        return self.score_batch([audio], [candidates], sampling_rate, hotwords, append_eos, share_prompt)[0]
 
     def score_batch(self, audios: Sequence[Any], candidates_per_audio: Sequence[Sequence[Any]], sampling_rate: int = 16000,
-                    hotwords: Optional[List[str]] = None, append_eos: bool = True) -> List[List["Score"]]:
+                    hotwords: Optional[List[str]] = None, append_eos: bool = True, share_prompt: Optional[bool] = None) -> List[List["Score"]]:
         """score() for several audios, each with its own candidates: as few runs as hold them (scoring.plan_runs), the same bits as one call per audio."""
         self._check_live()
         if not self.scoring or not self._score_engines:
             raise ValueError("score() needs a model built with scoring=True (ASRModel(..., token_logprobs=True, scoring=True))")
         if len(audios) != len(candidates_per_audio):
             raise ValueError(f"{len(audios)} audios but {len(candidates_per_audio)} candidate lists")
+        share = self.score_share_prompt if share_prompt is None else bool(share_prompt)
+        if share and self.share_prompt_refusal():
+            raise ValueError(self.share_prompt_refusal())
         eos = self._eos_ids()
         wins_of, prompts, _ = self._prepare_all(audios, sampling_rate, hotwords)
         targets = [[scoring_.with_eos(self._candidate_ids(c), eos, append_eos) for c in cands] for cands in candidates_per_audio]
         i = self._score_next % len(self._score_engines)
         self._score_next += 1
         eng = self._score_engines[i]
-        runs = scoring_.plan_runs([len(p) for p in prompts], [[len(t) for t in ts] for ts in targets], eng.max_batch, eng.tok_cap, eng.max_ctx)
+        runs = scoring_.plan_runs([len(p) for p in prompts], [[len(t) for t in ts] for ts in targets], eng.max_batch, eng.tok_cap, eng.max_ctx, share_prompt=share)
         dummy = next(t for t in range(self.dims.vocab) if t != self.dims.audio_token_id and t not in eos)
         out: List[List[Optional[scoring_.Score]]] = [[None] * len(ts) for ts in targets]
         with self._score_locks[i]:
             for run in runs:
                 segs, req_win = _flatten(wins_of[a] for a, _ in run.groups)
                 run_prompts = [prompts[a] for a, part in run.groups for _ in part]
-                ids, _, lps = eng.score_batch(segs, run_prompts, scoring_.run_targets(run, targets, dummy), req_win=req_win, fanout=run.fanout)
+                ids, _, lps = eng.score_batch(segs, run_prompts, scoring_.run_targets(run, targets, dummy), req_win=req_win, fanout=run.fanout, share_prompt=share)
                 r = 0
                 for a, part in run.groups:
                     for c in part:

@@ -46,7 +46,18 @@ template <int HD> __device__ __forceinline__ int kswz(int row) {  // swizzle ter
 
 // VAR (A/B, option "flash_variant"): bit 0 = two LDS tile buffers, one barrier per key tile; bit 1 = accumulators rescaled only when a
 // running maximum of the wave moved
-template <typename T, int HD, bool CAUSAL, int VAR>
+// PFX (the parallel forced run's shared prompt, option forced_share_prompt): keys [0, pre_len[b]) of sequence b come from cache row pre_row[b], keys
+// [pre_len[b], kv_len) from row b itself; the caller guarantees pre_len <= kv_len - q_len (the prefix lies in front of the first query, so the causal rule and the
+// causal tile count hold as they stand) and pre_row[b] < B.  Every tile comes from ONE row, so the loaders stay what they are with a block-uniform base: the loop
+// first takes the ceil(pre_len / 64) tiles of the prefix from row pre_row[b], keys >= pre_len masked, then the tiles from floor(pre_len / 64) on from row b, keys <
+// pre_len masked.  The tile that holds pre_len is taken twice unless pre_len % 64 == 0 - once per row, with complementary masks - which is what keeps a K row and a
+// 16-byte V^T chunk of 8 keys from ever mixing two rows (pre_len % 8 != 0).  Masked positions are read (their probability is exactly 0), as keys >= kv_len always were:
+// what stands there - a sharer's row below pre_len holds whatever earlier runs left - must be finite, which a cache that is zero-filled at allocation and written by
+// these kernels alone is.  No turn of the loop is masked entirely for a real query, which the online softmax (and LAZY's "alpha == 1: skip the rescale") relies on:
+// every prefix tile holds a key < pre_len, and every query sees the whole prefix; the first own-row tile, pre_len >> 6, holds key pre_len itself, which is at or in
+// front of every query's position (pre_len <= kv_len - q_len); the later own-row tiles are the ordinary causal ones.
+// The PFX statements stand apart from the others (if constexpr) so that the instantiations without it compile to what they were, instruction for instruction.
+template <typename T, int HD, bool CAUSAL, int VAR, bool PFX = false>
 __global__ __launch_bounds__(256) void flash_attn_kernel(FlashArgs a) {
     constexpr bool DB = (VAR & 1) != 0, LAZY = (VAR & 2) != 0;
     typedef typename ET<T>::v8 V8;
@@ -105,9 +116,28 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(FlashArgs a) {
         n_tiles = min(n_tiles, last_q / 64 + 1);
     }
 
+    // PFX: turn kt < n_pre of the loop is tile kt of the prefix row, the others are the tiles from pre_len / 64 on of the sequence's own row; n_tiles counts the turns
+    int pre_len = 0, n_pre = 0; const T *Kp = K, *Vtp = Vt;
+    if constexpr (PFX) {
+        pre_len = a.pre_len[b]; n_pre = (pre_len + 63) >> 6; n_tiles += n_pre - (pre_len >> 6);
+        Kp = (const T*)a.K + (long)a.pre_row[b] * a.k_seq_stride + (long)kh * a.k_head_stride;
+        Vtp = (const T*)a.Vt + (long)a.pre_row[b] * a.vt_seq_stride + (long)kh * a.vt_head_stride;
+    }
     // register-staged prefetch (issue-early / write-late)
     V8 kreg[KV_PASSES], vreg[KV_PASSES];
     auto issue = [&](int kt) {
+        if constexpr (PFX) {
+            const int key0 = (kt >= n_pre ? kt - n_pre + (pre_len >> 6) : kt) * 64;
+            const T* Kt = kt < n_pre ? Kp : K;
+            const T* Vtt = kt < n_pre ? Vtp : Vt;
+#pragma unroll
+            for (int p = 0; p < KV_PASSES; ++p) {      // (the loads below, from the turn's row)
+                const int idx = p * 256 + tid;
+                kreg[p] = *(const V8*)(Kt + (long)(key0 + idx / KCH) * a.k_ld + (idx % KCH) * 8);
+                vreg[p] = *(const V8*)(Vtt + (long)(idx >> 3) * a.vt_ld + key0 + (idx & 7) * 8);
+            }
+            return;
+        }
         const int key0 = kt * 64;
 #pragma unroll
         for (int p = 0; p < KV_PASSES; ++p) {
@@ -151,7 +181,7 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(FlashArgs a) {
         }
         const char* sK = smem + (DB ? (kt & 1) : 0) * (KT_BYTES + VT_BYTES);
         const char* sV = sK + KT_BYTES;
-        const int key0 = kt * 64;
+        const int key0 = PFX ? (kt >= n_pre ? kt - n_pre + (pre_len >> 6) : kt) * 64 : kt * 64;
 
         // ---- S^T = K . Q^T   (st[ks][sb][qb][j]: key = key0 + ks*32 + 8*fg + 4*sb + j, query = qb*16 + fr)
         f32x4 st[2][2][2];
@@ -176,7 +206,8 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(FlashArgs a) {
         // commutes with the scaling) and the scale is folded into the exponent: p = exp2(s * c - m * c), c = scale * log2(e), one FMA
         // and one v_exp_f32 per score.  Tiles that need no masking (all but the last key tile / the causal diagonal) take a branch
         // without the per-element compares and selects.
-        const bool edge = (key0 + 64 > kv_len) || (CAUSAL && (key0 + 63 > q0 + wid * 32 + qpos_off));
+        const bool edge = PFX ? (kt < n_pre ? key0 + 64 > pre_len : key0 < pre_len || key0 + 64 > kv_len || key0 + 63 > q0 + wid * 32 + qpos_off)
+                              : (key0 + 64 > kv_len) || (CAUSAL && (key0 + 63 > q0 + wid * 32 + qpos_off));
         V8 pf[2][2];
         const float cexp = a.scale * 1.44269504088896341f;
         float alph[2];
@@ -192,6 +223,7 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(FlashArgs a) {
                             for (int j = 0; j < 4; ++j) {
                                 const int key = key0 + ks * 32 + 8 * fg + 4 * sb + j;
                                 bool ok = key < kv_len;
+                                if constexpr (PFX) ok = kt < n_pre ? key < pre_len : (ok && key >= pre_len);
                                 if (CAUSAL) ok = ok && (key <= qrow[qb] + qpos_off);
                                 st[ks][sb][qb][j] = ok ? st[ks][sb][qb][j] : -1e30f;
                             }
@@ -277,6 +309,10 @@ void launch_flash(const FlashArgs& a, int hd, bool causal, int B, int max_q, hip
     // LDS-DMA tiles, running maximum fixed after the first key tile)
     if (hd == 64 && !causal && g_opts.flash_enc > 0 && a.Hq == a.Hkv) { launch_flash_enc(a, B, max_q, g_opts.flash_enc - 1, s); return; }
     dim3 grid((max_q + 127) / 128, a.Hq, B);
+    if (a.pre_row) {      // a shared prefix (prefill_flash_args: head dim 128, causal): one form, the default variant's, whatever flash_variant says
+        DT_SWITCH(a.dt, T, hipLaunchKernelGGL((flash_attn_kernel<T, 128, true, 2, true>), grid, dim3(256), 0, s, a));
+        return;
+    }
     switch (g_opts.flash_variant & 3) {
         case 1: launch_flash_v<1>(a, hd, causal, grid, s); break;
         case 2: launch_flash_v<2>(a, hd, causal, grid, s); break;

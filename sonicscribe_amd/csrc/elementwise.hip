@@ -481,7 +481,8 @@ __global__ __launch_bounds__(256) void rope_append_pf_kernel(RopeAppendArgs a) {
     if (!a.Vt) return;
     __syncthreads();
     // V^T[b][kvh][hd][pos]: row (kvh, hd) of the tile = TT consecutive positions starting at the tile's first position (prompt positions are 0 .. P-1,
-    // so p0 is a multiple of 16: the row piece is 32 bytes, 16-byte aligned whenever vt_ld is a multiple of 8)
+    // so p0 is a multiple of 16: the row piece is 32 bytes, 16-byte aligned whenever vt_ld is a multiple of 8).  A sequence packed from a later position on (the
+    // suffix rows of option forced_share_prompt: q_len counts its packed rows, tok_pos says where they sit) takes the element-wise stores unless that position is a multiple of 8
     const int pos0 = a.tok_pos[tok0];
     for (int rr = threadIdx.x; rr < VW; rr += blockDim.x) {
         T* vt = (T*)a.Vt + ((long)b * a.Hkv * HD + rr) * a.vt_ld + pos0;

@@ -333,7 +333,7 @@ static int alloc_state(sonic_engine* e) {
     // (the row-fetch stream st_io is created by the first sonic_service_begin: hardware queues are dealt to streams in creation order, and the main
     //  streams of an engine and its slots should take the first ones - see probe_hw_queues)
     if (hipEventCreateWithFlags(&e->xfer_ev, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&e->splice_ev, hipEventDisableTiming) != hipSuccess) { e->err = "hipEventCreate failed"; return SONIC_ERR_HIP; }
-    e->plan_cap = 3 * tc + 8 * 64;
+    e->plan_cap = 3 * tc + 10 * 64;      // (three words per token; seven per request, a word and the 64 of run_upload_win_req behind them)
     for (int i = 0; i < 2; ++i) {
         if (hipHostMalloc((void**)&e->plan_buf[i], e->plan_cap * 4, hipHostMallocDefault) != hipSuccess) { e->err = "hipHostMalloc failed"; return SONIC_ERR_HIP; }
         if (hipEventCreateWithFlags(&e->plan_ev[i], (getenv("SONIC_SPIN_SYNC") ? 0 : hipEventBlockingSync) | hipEventDisableTiming) != hipSuccess) { e->err = "hipEventCreate failed"; return SONIC_ERR_HIP; }

@@ -779,6 +779,7 @@ int gen_inherit(sonic_engine* e, const sonic_engine* root) {
     if (root->opt_grammar) TRY(gram_enable(e, 1));
     e->opt_forced_parallel = root->opt_forced_parallel; e->opt_forced_fanout = root->opt_forced_fanout; e->opt_score_chunk_rows = root->opt_score_chunk_rows;      // (the buffers come with the slot's first parallel run)
     e->opt_forced_align = root->opt_forced_align; e->align_heads = root->align_heads;      // (likewise)
+    e->opt_forced_share_prompt = root->opt_forced_share_prompt;      // (likewise)
     e->opt_draft_verify = root->opt_draft_verify;      // (the buffers come with the slot's first drafted prefill)
     return SONIC_OK;
 }

@@ -220,12 +220,22 @@ extern "C" int sonic_test_decode_attention_cache(sonic_engine* e, const float* q
     return SONIC_OK;
 }
 
+// sonic_load_tensor "share_prompt.hook": int32 [2][B] = pre_row | pre_len, armed until the next sonic_test_prefill_attention takes it (that call checks it against its shapes)
+int share_hook_arm(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim) {
+    if (dtype != SONIC_DTYPE_I32 || ndim != 2 || shape[0] != 2 || shape[1] < 1 || shape[1] > 4096)
+        return fail(nullptr, SONIC_ERR_INVALID, "share_prompt.hook: int32 [2][B] (pre_row | pre_len), 1 <= B <= 4096");
+    std::lock_guard<std::mutex> lk(e->mu);
+    e->hook_share.assign((const int*)data, (const int*)data + 2 * shape[1]);
+    return SONIC_OK;
+}
 // The causal attention of the prefill through run_prefill()'s own descriptor builder (prefill_flash_args): packed ragged queries (q_off / q_len / kv_len), K in cache layout, V^T with the
-// context as its leading dimension, head dim 128.  `out` [n_tok][Hq * 128] is uploaded first, so rows the kernel leaves alone keep the caller's values.
+// context as its leading dimension, head dim 128.  `out` [n_tok][Hq * 128] is uploaded first, so rows the kernel leaves alone keep the caller's values.  An armed
+// "share_prompt.hook" is consumed: sequence b's keys [0, pre_len[b]) are then those of cache row pre_row[b] (the shared-prefix kernel of option forced_share_prompt)
 extern "C" int sonic_test_prefill_attention(sonic_engine* e, const float* q, const float* kcache, const float* vt, const int32_t* q_off, const int32_t* q_len,
                                             const int32_t* kv_len, float* out, int n_tok, int B, int Hq, int Hkv, int ctx_max) {
     if (!e || !q || !kcache || !vt || !q_off || !q_len || !kv_len || !out) return SONIC_ERR_INVALID;
     ENTER(e);
+    std::vector<int> share; share.swap(e->hook_share);      // (an armed "share_prompt.hook" is consumed whatever becomes of the call)
     const int hd = 128;
     if (e->f32) return fail(e, SONIC_ERR_INVALID, "prefill attention hook needs a 16-bit engine");
     if (B < 1 || B > 4096 || n_tok < 1 || Hkv < 1 || Hq < Hkv || Hq % Hkv || ctx_max < 64 || ctx_max % 64) return fail(e, SONIC_ERR_INVALID, "bad prefill attention test shape");
@@ -235,13 +245,18 @@ extern "C" int sonic_test_prefill_attention(sonic_engine* e, const float* q, con
             return fail(e, SONIC_ERR_INVALID, "sequence %d: q_off %d, q_len %d, kv_len %d do not fit %d tokens / a context of %d", b, q_off[b], q_len[b], kv_len[b], n_tok, ctx_max);
         max_p = q_len[b] > max_p ? q_len[b] : max_p;
     }
+    if (!share.empty() && share.size() != (size_t)2 * B) return fail(e, SONIC_ERR_INVALID, "share_prompt.hook: armed for %zu sequences, the launch has %d", share.size() / 2, B);
+    for (int b = 0; b < B && !share.empty(); ++b)
+        if (share[b] < 0 || share[b] >= B || share[B + b] < 0 || share[B + b] > kv_len[b] - q_len[b])
+            return fail(e, SONIC_ERR_INVALID, "share_prompt.hook: sequence %d: pre_row %d outside 0 .. %d or pre_len %d outside 0 .. kv_len - q_len = %d", b, share[b], B - 1, share[B + b], kv_len[b] - q_len[b]);
     TmpBuf tb(e->st);
     const size_t nq = (size_t)n_tok * Hq * hd, nc = (size_t)B * Hkv * ctx_max * hd;
     bf16_t* dq = up_bf16(e, tb, q, nq); bf16_t* dk = up_bf16(e, tb, kcache, nc); bf16_t* dvt = up_bf16(e, tb, vt, nc); bf16_t* dO = up_bf16(e, tb, out, nq);
-    int* di = tb.get<int>((size_t)3 * B);
+    int* di = tb.get<int>((size_t)5 * B);
     if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
     HIPC(e, h2d(e, di, q_off, (size_t)B * 4)); HIPC(e, h2d(e, di + B, q_len, (size_t)B * 4)); HIPC(e, h2d(e, di + 2 * B, kv_len, (size_t)B * 4));
-    launch_flash(prefill_flash_args(dq, dk, dvt, dO, di, di + B, di + 2 * B, Hq, Hkv, ctx_max, e->dt), hd, true, B, max_p, e->st);
+    if (!share.empty()) HIPC(e, h2d(e, di + 3 * B, share.data(), (size_t)2 * B * 4));
+    launch_flash(prefill_flash_args(dq, dk, dvt, dO, di, di + B, di + 2 * B, Hq, Hkv, ctx_max, e->dt, share.empty() ? nullptr : di + 3 * B, di + 4 * B), hd, true, B, max_p, e->st);
     return down_bf16(e, tb, dO, out, nq);
 }
 

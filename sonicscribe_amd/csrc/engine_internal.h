@@ -232,6 +232,10 @@ struct sonic_engine {
     // sonic_memory_info and go with the handle
     int opt_forced_parallel = 0, opt_forced_fanout = 1, opt_score_chunk_rows = SCORE_CHUNK_DEFAULT;
     void* score_logits = nullptr; int score_rows_cap = 0; int* score_plan_d = nullptr; int* score_plan_h = nullptr;
+    // option forced_share_prompt: the candidates of one audio share ONE prefill of their prompt.  pre_row [2][64]: the sequences' pre_row | pre_len on
+    // the device (with the handle's first shared run); score_tokens: the packed tokens of the last parallel forced run (sonic_debug_read "score_tokens"); hook_share: the
+    // kernel hook's pre_row | pre_len (sonic_load_tensor "share_prompt.hook"), armed until the next sonic_test_prefill_attention takes it
+    int opt_forced_share_prompt = 0; int* pre_row = nullptr; int score_tokens = 0; std::vector<int> hook_share;
     // word timestamps on the parallel forced run (options forced_align / align_head; align.hip).  align_heads: the selected heads as l * 256 + h, sorted
     // (empty: every head of the last ceil(dec_layers / 2) layers).  The buffers come with the first align run, sized to that run (and exchanged for larger ones by a
     // later run that needs more), are counted by sonic_memory_info and go with the handle: align_P 2 x [heads of a layer][S][A_max] and align_M [S][A_max] fp32, the DTW's
@@ -286,6 +290,9 @@ struct QkvVt { bf16_t* Vt; int n_split, seg_T, vt_ld; long vt_seg_stride; };
 struct HostPlan {
     std::vector<int> src, tok_seq, tok_pos, q_off, q_len, last_row, max_new;
     int n_tok = 0, max_p = 0, max_steps = 0;
+    // option forced_share_prompt (empty otherwise): q_len then counts a sequence's PACKED rows (a sharer's: its suffix alone, at positions from its
+    // group's prompt length on), kv_len its keys, and keys [0, pre_len) of a sequence are those of cache row pre_row
+    std::vector<int> kv_len, pre_row, pre_len;
     // option draft_verify: the S verify rows of the batch's drafts (draft_plan_d's layout: DraftPlan); S = 0: an ordinary prefill
     std::vector<int> draft; int S = 0;
     // row forks: the rows of the run (0: the requests are the rows), then per row the request it shares its prefill with (rows 0 .. R-1: themselves)
@@ -386,7 +393,7 @@ int run_mel(sonic_engine* e, int W, bool want_f32);
 int run_encoder(sonic_engine* e, int W, float* enc_layers_out, float* enc_out_host, int n_groups);
 int keep_rows(const sonic_dims& d, int n_valid_frames);
 int frames_of(int n_samples);
-int plan_requests(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new, HostPlan& hp, int fan = 1);
+int plan_requests(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new, HostPlan& hp, int fan = 1, const int32_t* pos0 = nullptr);
 int upload_plan(sonic_engine* e, int R, const HostPlan& hp);       // the prefill's prologue, every kind: the request plan through the pinned staging buffer ...
 int reset_row_state(sonic_engine* e, int R, int n_tok);            // ... and the rows' counters, history, bias tables and sampling values for the greedy loop
 int run_prefill(sonic_engine* e, int R, const HostPlan& hp, bool head = true);
@@ -452,7 +459,7 @@ DecodeAttnArgs decode_attn_args(bf16_t* Kc, bf16_t* Vc, const float* P, const bf
 int skinny_i8(sonic_engine* e, const void* X, const float* amax, const int8_t* Wt, float* P, int M, int N, int K);
 DeqInfo deq_info(const sonic_engine* e, const QuantOut& q, const QW& w, int K, const bf16_t* x16, int N);
 FlashArgs prefill_flash_args(const bf16_t* Q, const bf16_t* Kc, const bf16_t* Vt, bf16_t* O, const int* q_off, const int* q_len, const int* kv_len,
-                             int Hq, int Hkv, int ctx_max, int dt);
+                             int Hq, int Hkv, int ctx_max, int dt, const int* pre_row = nullptr, const int* pre_len = nullptr);
 RopeAppendArgs rope_append_args(const bf16_t* qkv, bf16_t* q_out, bf16_t* Kc, bf16_t* Vc, bf16_t* Vt, long vt_ld, const int* tok_seq, const int* tok_pos, const float* cs,
                                 int Hq, int Hkv, int ctx_max, int n_tok, int dt, const int* q_off, const int* q_len, int n_seq, int max_p);
 // the o_proj -> RMSNorm -> gate/up chain of a decoder layer (decode_step, sonic_test_decode_o_gu): its forms, and its buffers in the order of OGuChain's fields -
@@ -483,6 +490,7 @@ int trunc_pack(sonic_engine* e, const char* who, const float* v, int row, unsign
 int trunc_stage_rows(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim);   // sonic_load_tensor "request_truncation": the values of the next prefill's rows
 int trunc_dispatch_arm(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim); // sonic_load_tensor "truncation.dispatch" (no engine lock): the calling thread's next sonic_dispatch_submit_sampled carries the row
 int trunc_hook_arm(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim);     // sonic_load_tensor "truncation.hook": the next sonic_test_greedy_sample launch's rows
+int share_hook_arm(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim);     // sonic_load_tensor "share_prompt.hook" (engine_hooks.cpp): the next sonic_test_prefill_attention launch's pre_row | pre_len
 int gram_enable(sonic_engine* e, int on);           // option grammar behind the lock and the busy check: hist, the rows' references and state words and their staging buffer on first use
 // one request's table as sonic_set_request_bias takes it -> its BIAS_ROW_WORDS device words, grouped and ordered as the kernel reads them; *count = its entries.
 // SONIC_ERR_INVALID (message on e, naming `who`) for more than BIAS_MAX_ENTRIES entries, a length outside 1 .. BIAS_MAX_LEN, an id outside [0, V), a NaN or +inf bias

@@ -64,7 +64,18 @@ static int opt_forced_parallel(sonic_engine* e, const char* key, int value) {
     TRY(gen_busy(e, key));
     if (value && e->opt_draft_verify) return fail(e, SONIC_ERR_INVALID, "forced_parallel: option draft_verify is on: a scoring handle decodes nothing a draft could shorten");
     if (!value && e->opt_forced_align) return fail(e, SONIC_ERR_INVALID, "forced_parallel cannot be switched off while option forced_align is on (the alignment rides on the parallel forced run)");
+    if (!value && e->opt_forced_share_prompt) return fail(e, SONIC_ERR_INVALID, "forced_parallel cannot be switched off while option forced_share_prompt is on (the shared prompt is the parallel forced run's)");
     e->opt_forced_parallel = value ? 1 : 0; return SONIC_OK;
+}
+// forced_share_prompt: the forced_fanout candidates of one audio share ONE prefill of their prompt - only on a scoring handle of the bf16 / fp16 kinds
+// without forced_align; refused while the handle has work in hand.  (Read by a parallel run as it starts, which also checks that a group's prompts are one prompt.)
+static int opt_forced_share_prompt(sonic_engine* e, const char* key, int value) {
+    TRY(gen_busy(e, key));
+    if (value && !e->opt_forced_parallel) return fail(e, SONIC_ERR_INVALID, "forced_share_prompt: option forced_parallel must be on first (the shared prompt is the parallel forced run's; sonic_set_option(e, \"forced_parallel\", 1))");
+    if (value && e->i8) return fail(e, SONIC_ERR_INVALID, "forced_share_prompt: not on an int8 handle (its prefill finds outlier columns per sequence - one sequence = one reference call - and a shared prompt belongs to several)");
+    if (value && e->f32) return fail(e, SONIC_ERR_INVALID, "forced_share_prompt: the fp32 kind has no shared-prefix attention kernel; use a bf16 or fp16 handle");
+    if (value && e->opt_forced_align) return fail(e, SONIC_ERR_INVALID, "forced_share_prompt: option forced_align is on (the alignment kernels read a sequence's audio keys from its own row)");
+    e->opt_forced_share_prompt = value ? 1 : 0; return SONIC_OK;
 }
 static int opt_forced_fanout(sonic_engine* e, const char* key, int value) {
     if (value < 1 || value > e->Bm) return fail(e, SONIC_ERR_INVALID, "forced_fanout: %d is outside 1 .. %d (max_batch)", value, e->Bm);
@@ -79,6 +90,7 @@ static int opt_draft_verify(sonic_engine* e, const char* key, int value) { TRY(g
 static int opt_forced_align(sonic_engine* e, const char* key, int value) {
     TRY(gen_busy(e, key));
     if (value && e->f32) return fail(e, SONIC_ERR_INVALID, "forced_align: the fp32 kind has no alignment kernels (its prefill keeps no roped queries); use a bf16 or int8-mode handle");
+    if (value && e->opt_forced_share_prompt) return fail(e, SONIC_ERR_INVALID, "forced_align: option forced_share_prompt is on (the alignment kernels read a sequence's audio keys from its own row); switch it off first");
     if (value && !e->opt_forced_parallel) return fail(e, SONIC_ERR_INVALID, "forced_align: option forced_parallel must be on first (the alignment rides on the parallel forced run; sonic_set_option(e, \"forced_parallel\", 1))");
     e->opt_forced_align = value ? 1 : 0;
     if (!value) e->align_last = false;
@@ -175,6 +187,7 @@ static const OptRow OPTIONS[] = {
     {"request_bias_fill", APPLY(opt_request_bias_fill)},
     {"forced_parallel", APPLY(opt_forced_parallel)},
     {"forced_fanout", APPLY(opt_forced_fanout)},
+    {"forced_share_prompt", APPLY(opt_forced_share_prompt)},
     {"forced_align", APPLY(opt_forced_align)},
     {"align_head", APPLY(opt_align_head)},
     {"draft_verify", APPLY(opt_draft_verify)},
@@ -250,6 +263,11 @@ extern "C" int sonic_debug_read(sonic_engine* e, const char* name, int index, fl
         int acc[64] = {0};
         if (e->draft_last_S > 0 && e->draft_acc) { HIPC(e, stream_sync(e)); HIPC(e, d2h(e, acc, e->draft_acc, 64 * 4)); }
         for (int64_t i = 0; i < n; ++i) out[i] = (float)acc[i];
+        return SONIC_OK;
+    }
+    if (!strcmp(name, "score_tokens")) {            // the packed tokens of the handle's last parallel forced run, shared prompt or not (exact in fp32: at most tok_cap)
+        if (n != 1) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
+        out[0] = (float)e->score_tokens;
         return SONIC_OK;
     }
     if (!strcmp(name, "fork_ms")) {                 // fork_kv_kernel's time in the handle's last forked prefill, from the events around it; 0 behind an unforked one

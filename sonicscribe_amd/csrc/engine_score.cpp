@@ -21,6 +21,7 @@ int score_logits_alloc(sonic_engine* e) {
 }
 static int score_alloc(sonic_engine* e) {
     TRY(score_logits_alloc(e));
+    if (e->opt_forced_share_prompt && !e->pre_row) TRY(dalloc(e, &e->pre_row, 2 * 64));
     if (!e->score_plan_d) TRY(dalloc(e, &e->score_plan_d, ScorePlan::row_words(e->tok_cap)));
     if (!e->score_plan_h && hipHostMalloc((void**)&e->score_plan_h, ScorePlan::words(e->tok_cap) * 4, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(e, SONIC_ERR_OOM, "forced_parallel: pinned host memory exhausted"); }
     return SONIC_OK;
@@ -119,8 +120,19 @@ int run_forced_parallel(sonic_engine* e, const int32_t* req_win, int R, const in
     }
     if (e->force_R != R || e->force_ld < max_steps || e->force_h.size() != (size_t)e->force_R * e->force_ld)
         return fail(e, SONIC_ERR_INVALID, "forced ids are [%d][%d] but the run has %d requests / %d steps", e->force_R, e->force_ld, R, max_steps);
+    // option forced_share_prompt: the first sequence of every group of N packs prompt || forced[0 .. L - 1) as ever, the others only their forced[0 .. L - 1),
+    // at positions P on of their own cache row - their attention reads keys [0, P) from the first one's row.  The option's own setter has refused the kinds and options
+    // that cannot share (engine_options.cpp: forced_align among them, either way round, so `align` below is never true beside it); what is left to check is that a
+    // group's prompts ARE one prompt
+    const bool share = e->opt_forced_share_prompt != 0;
+    for (int r = 0; share && r < R; ++r) {
+        const int o = r - r % N;
+        const int64_t n = prompt_off[r + 1] - prompt_off[r];
+        if (n != prompt_off[o + 1] - prompt_off[o] || memcmp(prompt_ids + prompt_off[r], prompt_ids + prompt_off[o], (size_t)n * 4))
+            return fail(e, SONIC_ERR_INVALID, "forced_share_prompt: sequences %d and %d of one group bring different prompts (the candidates of one audio share ONE prompt)", o, r);
+    }
     // the longer sequences: prompt || forced[0 .. L - 1); their budget max_new - (L - 1) keeps plan_requests' context check at prompt + max_new
-    std::vector<int32_t> ids, left(R), L(R); std::vector<int64_t> off(R + 1, 0);
+    std::vector<int32_t> ids, left(R), L(R), pos0(R, 0); std::vector<int64_t> off(R + 1, 0);
     long asked = 0;
     for (int r = 0; r < R; ++r) {
         const int* f = e->force_h.data() + (size_t)r * e->force_ld;
@@ -134,14 +146,21 @@ int run_forced_parallel(sonic_engine* e, const int32_t* req_win, int R, const in
             if (f[n] == d.audio_token_id) return fail(e, SONIC_ERR_INVALID, "forced_parallel: forced id %d of sequence %d is the audio placeholder id %d, which cannot be a target", n, r, d.audio_token_id);
         const int64_t p0 = prompt_off[r], p1 = prompt_off[r + 1];
         if (p1 - p0 < 1) return fail(e, SONIC_ERR_INVALID, "request %d has an empty prompt", r);
-        ids.insert(ids.end(), prompt_ids + p0, prompt_ids + p1);
+        const bool suffix = share && r % N;
+        if (suffix) pos0[r] = (int32_t)(p1 - p0);
+        else ids.insert(ids.end(), prompt_ids + p0, prompt_ids + p1);
         ids.insert(ids.end(), f, f + l - 1);
         off[r + 1] = (int64_t)ids.size(); L[r] = l; left[r] = max_new[r] - (l - 1);
-        asked += (p1 - p0) + l - 1;
+        asked += (suffix ? 0 : p1 - p0) + l - 1;
     }
     if (asked > e->tok_cap) return fail(e, SONIC_ERR_INVALID, "forced_parallel: the run asks for %ld tokens (prompts and forced ids), %d fit one prefill (tok_cap)", asked, e->tok_cap);
     HostPlan hp;
-    TRY(plan_requests(e, req_win, R, ids.data(), off.data(), left.data(), hp, N));
+    TRY(plan_requests(e, req_win, R, ids.data(), off.data(), left.data(), hp, N, share ? pos0.data() : nullptr));
+    if (share) {
+        hp.pre_row.resize(R); hp.pre_len = pos0;
+        for (int r = 0; r < R; ++r) hp.pre_row[r] = r - r % N;      // (the first of a group reads its own row: pre_len 0)
+    }
+    e->score_tokens = hp.n_tok;
     for (int r = 0; r < R; ++r) hp.max_new[r] = max_new[r];
     hp.max_steps = max_steps;
     if (max_steps > e->out_cap) return fail(e, SONIC_ERR_INVALID, "max_new_tokens too large");
@@ -186,7 +205,9 @@ int run_forced_parallel(sonic_engine* e, const int32_t* req_win, int R, const in
     for (int r = 0, s = 0; r < R; ++r) {
         const int P = e->last_qlen[r];
         const int* f = e->force_h.data() + (size_t)r * e->force_ld;
-        for (int n = 0; n < L[r]; ++n, ++s) { ph.hidden[s] = hp.q_off[r] + P - 1 + n; ph.target[s] = f[n]; ph.rec[s] = r * e->out_cap + n; }
+        // (a shared prompt: token 0 of every sequence of a group is scored from the ONE hidden row the prompt ends in - the first sequence's - and token n >= 1 of a suffix from its row n - 1)
+        const int o = share ? r - r % N : r, h0 = hp.q_off[o] + P - 1;
+        for (int n = 0; n < L[r]; ++n, ++s) { ph.hidden[s] = (o == r || n == 0) ? h0 + n : hp.q_off[r] + n - 1; ph.target[s] = f[n]; ph.rec[s] = r * e->out_cap + n; }
         ph.n_new[r] = L[r]; ph.finished[r] = 1; ph.tok_pos[r] = P + L[r] - 2;
     }
     for (int r = R; r < PLAN_REQ_WORDS; ++r) ph.finished[r] = 0;

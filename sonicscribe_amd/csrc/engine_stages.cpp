@@ -185,9 +185,10 @@ int frames_of(int n_samples) { return n_samples > 0 ? (n_samples + 159) / 160 : 
 
 // ------------------------------------------------------------------------------------------ the prefill's launch descriptors: one builder each (production and the hooks)
 // the prefill's causal attention: packed ragged queries, K in cache layout [B][Hkv][ctx_max][128], V^T [B][Hkv][128][ctx_max]
+// pre_row / pre_len (option forced_share_prompt): sequence b's keys [0, pre_len[b]) are those of cache row pre_row[b]; null: every sequence reads its own row
 FlashArgs prefill_flash_args(const bf16_t* Q, const bf16_t* Kc, const bf16_t* Vt, bf16_t* O, const int* q_off, const int* q_len, const int* kv_len,
-                             int Hq, int Hkv, int ctx_max, int dt) {
-    FlashArgs f{}; f.dt = dt;
+                             int Hq, int Hkv, int ctx_max, int dt, const int* pre_row, const int* pre_len) {
+    FlashArgs f{}; f.dt = dt; f.pre_row = pre_row; f.pre_len = pre_row ? pre_len : nullptr;
     f.Q = Q; f.q_ld = Hq * 128L; f.K = Kc; f.k_ld = 128; f.Vt = Vt; f.vt_ld = ctx_max; f.O = O; f.o_ld = Hq * 128L;
     f.k_seq_stride = (long)Hkv * ctx_max * 128; f.k_head_stride = ctx_max * 128L; f.vt_seq_stride = (long)Hkv * 128 * ctx_max; f.vt_head_stride = 128L * ctx_max;
     f.q_off = q_off; f.q_len = q_len; f.kv_len = kv_len; f.Hq = Hq; f.Hkv = Hkv; f.scale = 1.0f / sqrtf(128.f);
@@ -203,8 +204,10 @@ RopeAppendArgs rope_append_args(const bf16_t* qkv, bf16_t* q_out, bf16_t* Kc, bf
     return ra;
 }
 
-// fan (the parallel forced run's forced_fanout; 1 otherwise): sequence r takes its audio rows from audio request r / fan - req_win then has R / fan + 1 entries
-int plan_requests(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new, HostPlan& hp, int fan) {
+// fan (the parallel forced run's forced_fanout; 1 otherwise): sequence r takes its audio rows from audio request r / fan - req_win then has R / fan + 1 entries.
+// pos0 (its option forced_share_prompt; null otherwise): sequence r's ids sit at positions pos0[r] on.  pos0[r] > 0: the ids are the suffix behind a prompt another
+// sequence packs (pre_row / pre_len are the caller's to fill) - none is an audio placeholder, there may be none at all, and hp.kv_len / hp.q_len tell keys from rows
+int plan_requests(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new, HostPlan& hp, int fan, const int32_t* pos0) {
     const sonic_dims& d = e->d;
     const int W = e->W, A = R / fan;
     if (R < 1 || R > e->Bm) return fail(e, SONIC_ERR_INVALID, "request count %d out of range 1..%d", R, e->Bm);
@@ -214,16 +217,17 @@ int plan_requests(sonic_engine* e, const int32_t* req_win, int R, const int32_t*
     for (int r = 0; r < R; ++r) {
         const int w0 = req_win ? req_win[r / fan] : r / fan, w1 = req_win ? req_win[r / fan + 1] : r / fan + 1;
         if (w1 <= w0) return fail(e, SONIC_ERR_INVALID, "request %d has no audio window", r);
+        const int at = pos0 ? pos0[r] : 0;
         std::vector<int> rows;  // audio rows of this request in order
-        for (int w = w0; w < w1; ++w) {
+        for (int w = w0; w < w1 && at == 0; ++w) {
             const int k = keep_rows(d, frames_of(e->n_samples_h[w]));
             for (int j = 0; j < k; ++j) rows.push_back(w * e->Ta + j);
         }
         const int64_t p0 = prompt_off[r], p1 = prompt_off[r + 1];
         const int P = (int)(p1 - p0);
-        if (P < 1) return fail(e, SONIC_ERR_INVALID, "request %d has an empty prompt", r);
+        if (P < 1 && at == 0) return fail(e, SONIC_ERR_INVALID, "request %d has an empty prompt", r);
         if (max_new[r] < 1) return fail(e, SONIC_ERR_INVALID, "max_new_tokens must be >= 1");
-        if (P + max_new[r] > e->max_ctx) return fail(e, SONIC_ERR_INVALID, "prompt (%d) + max_new_tokens (%d) exceeds max_ctx (%d)", P, max_new[r], e->max_ctx);
+        if (at + P + max_new[r] > e->max_ctx) return fail(e, SONIC_ERR_INVALID, "prompt (%d) + max_new_tokens (%d) exceeds max_ctx (%d)", at + P, max_new[r], e->max_ctx);
         if (max_new[r] > e->out_cap) return fail(e, SONIC_ERR_INVALID, "max_new_tokens too large");
         size_t used = 0; int n_ph = 0;
         for (int i = 0; i < P; ++i) n_ph += (prompt_ids[p0 + i] == d.audio_token_id);
@@ -237,8 +241,9 @@ int plan_requests(sonic_engine* e, const int32_t* req_win, int R, const int32_t*
                 if (id < 0 || id >= d.vocab) return fail(e, SONIC_ERR_INVALID, "token id %d out of vocabulary", id);
                 hp.src.push_back(id);
             }
-            hp.tok_seq.push_back(r); hp.tok_pos.push_back(i);
+            hp.tok_seq.push_back(r); hp.tok_pos.push_back(at + i);
         }
+        if (pos0) hp.kv_len.push_back(at + P);
         hp.n_tok += P;
         hp.last_row[r] = hp.n_tok - 1;
         hp.max_new[r] = max_new[r];
@@ -270,10 +275,11 @@ int upload_plan(sonic_engine* e, int R, const HostPlan& hp) {
         HIPC(e, put(e->kv_len, kv.data(), (size_t)Rr)); HIPC(e, put(e->last_row, last.data(), (size_t)Rr)); HIPC(e, put(e->max_new_d, mn.data(), (size_t)Rr));
         HIPC(e, put(e->n_active, &Rr, 1));
     } else {
-        HIPC(e, put(e->kv_len, hp.q_len.data(), (size_t)R));
+        HIPC(e, put(e->kv_len, hp.pre_row.empty() ? hp.q_len.data() : hp.kv_len.data(), (size_t)R));
         HIPC(e, put(e->last_row, hp.last_row.data(), (size_t)R)); HIPC(e, put(e->max_new_d, hp.max_new.data(), (size_t)R));
         HIPC(e, put(e->n_active, &R, 1));
     }
+    if (!hp.pre_row.empty()) { HIPC(e, put(e->pre_row, hp.pre_row.data(), (size_t)R)); HIPC(e, put(e->pre_row + 64, hp.pre_len.data(), (size_t)R)); }      // option forced_share_prompt
     if (hp.S > 0) {      // option draft_verify: the verify rows' plan, through the pinned mirror that belongs to this staging buffer
         int* dh = e->draft_plan_h[e->plan_idx];
         memcpy(dh, hp.draft.data(), hp.draft.size() * 4);
@@ -343,7 +349,10 @@ int run_prefill(sonic_engine* e, int R, const HostPlan& hp, bool head) {
             launch_align_reduce(aa, e->st);
             e->align_last_heads = aa.n_heads;
         }
-        const FlashArgs f = prefill_flash_args(e->dq, e->Kc + kvoff, e->Vts, e->datt, e->q_off, e->q_len, e->q_len, d.dec_heads, d.dec_kv_heads, e->max_ctx, dt);
+        // (a shared plan, option forced_share_prompt: the append above has taken every row's position from tok_pos, in tiles of a sequence's PACKED rows; the attention tells keys from rows)
+        const bool shared = !hp.pre_row.empty();
+        const FlashArgs f = prefill_flash_args(e->dq, e->Kc + kvoff, e->Vts, e->datt, e->q_off, e->q_len, shared ? e->kv_len : e->q_len, d.dec_heads, d.dec_kv_heads, e->max_ctx, dt,
+                                               shared ? e->pre_row : nullptr, shared ? e->pre_row + 64 : nullptr);
         launch_flash(f, 128, true, R, hp.max_p, e->st);
         lin(EPI_BIAS_RESID, e->datt, e->QD, L.wo, L.wo_t, 0, L.qo, e->dx, D, D, e->QD, e->dx, D, false);
         const bool pq2 = rmsnorm_q(e, e->dx, L.ln2, e->dhn, M, D, d.dec_rms_eps, grp);

@@ -85,6 +85,7 @@ extern "C" int sonic_load_tensor(sonic_engine* e, const char* name, const void* 
     if (!strcmp(name, "request_truncation")) return trunc_stage_rows(e, data, dtype, shape, ndim);      // top_k / top_p / min_p of the next prefill's rows (option truncation)
     if (!strcmp(name, "truncation.dispatch")) return trunc_dispatch_arm(e, data, dtype, shape, ndim);      // ... of the calling thread's next sonic_dispatch_submit_sampled (no engine lock, as grammar.dispatch)
     if (!strcmp(name, "truncation.hook")) return trunc_hook_arm(e, data, dtype, shape, ndim);      // ... and of the next sonic_test_greedy_sample launch
+    if (!strcmp(name, "share_prompt.hook")) return share_hook_arm(e, data, dtype, shape, ndim);      // pre_row | pre_len of the next sonic_test_prefill_attention launch (option forced_share_prompt's kernel)
     ENTER(e);
     if (e->finalized) return fail(e, SONIC_ERR_INVALID, "weights already finalized");
     std::vector<int64_t> shp(shape, shape + ndim);

@@ -47,6 +47,9 @@ struct FlashArgs {
     float scale;
     int dt;                                // DT_BF16 / DT_F16
     long long* dbg;                        // diagnostics (tools/flash_enc_bench): per block {shader clock, 100 MHz clock} at entry and exit; null in production
+    // optional [B] each (head dim 128, causal; flash_attn_kernel<.., PFX>): keys [0, pre_len[b]) of sequence b are those of cache row pre_row[b], the others its own;
+    // pre_len[b] <= kv_len[b] - q_len[b], pre_len = 0: an ordinary sequence.  Last: every offset above is what it was
+    const int* pre_row; const int* pre_len;
 };
 void launch_flash(const FlashArgs& a, int hd, bool causal, int B, int max_q, hipStream_t s);
 void launch_flash_enc(const FlashArgs& a, int B, int max_q, int mode, hipStream_t s);   // attn_enc.hip: head dim 64, no mask (the encoder)

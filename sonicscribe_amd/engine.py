@@ -655,14 +655,16 @@ class Engine(HooksMixin):
             self._arm_truncation(samp_packed[2])
 
     def score_batch(self, segments: Sequence[Any], prompts: Sequence[Sequence[int]], targets, req_win: Optional[Sequence[int]] = None, fanout: int = 1,
-                    want_logits: bool = False, align: bool = False):
+                    want_logits: bool = False, align: bool = False, share_prompt: bool = False):
         """Score given continuations in ONE prefill pass (the parallel forced run; needs option forced_parallel on this handle).  targets: one id
         sequence per prompt, or an int array [R][ld] padded with any valid id beyond a sequence's own length when all share a length - sequence r is scored up to
         and including its first EOS id (HF's rule).  fanout = N: the R sequences are R / N audio requests with N candidates each; `segments` / `req_win` then
         describe the R / N audio requests, which go through log-mel, encoder and projector once.  No logits processor is applied: the log-probabilities are those
         of the raw model distribution at temperature 1.  Returns what transcribe_batch(..., want_logprobs=True) returns: (ids list, logits [ld][R][V] or None,
         per sequence its float32 log-probabilities - with option top_logprobs a TokenScores); the log-probabilities need option token_logprobs (None without).
-        align (needs options forced_align and token_logprobs on this handle): per sequence an AlignedScores, whose `times` are t_n per token."""
+        align (needs options forced_align and token_logprobs on this handle): per sequence an AlignedScores, whose `times` are t_n per token.
+        share_prompt (option forced_share_prompt for this call): the N sequences of a group bring the same prompt, and it is prefilled once per group -
+        the run then holds A * P + sum(L - 1) tokens where it held sum(P + L - 1).  Not on an int8 or fp32 handle, not beside forced_align (SonicError by name)."""
         if not getattr(self, "forced_parallel", False):
             raise SonicError("score_batch needs option forced_parallel on this handle (set_option('forced_parallel', 1))")
         if align and not (getattr(self, "forced_align", False) and getattr(self, "token_logprobs", False)):
@@ -674,12 +676,16 @@ class Engine(HooksMixin):
         self.set_option("forced_fanout", int(fanout))
         self.set_forced_ids(forced)
         try:
+            if share_prompt:
+                self.set_option("forced_share_prompt", 1)
             want_lp = bool(getattr(self, "token_logprobs", False))
             self._lp_align = bool(getattr(self, "forced_align", False))      # (an align handle's parallel run returns the wide records, asked for or not)
             out = self.transcribe_batch(segments, prompts, [int(n) for n in lens], req_win=req_win, want_logits=want_logits, want_logprobs=want_lp)
         finally:
             self._lp_align = False
             self.set_forced_ids(None)
+            if share_prompt:
+                self.set_option("forced_share_prompt", 0)
         if want_lp and getattr(self, "forced_align", False) and not align:      # the caller asked for scores alone: what a handle without the option returns
             K = int(getattr(self, "top_logprobs", 0))
             out = (out[0], out[1], [a.lp if K == 0 else TokenScores(a.lp, a.top_logprobs, a.top_ids) for a in out[2]])

@@ -262,15 +262,26 @@ class HooksMixin:
                                                                B, Hq, Hkv, ctx))
         return out, ko, vo
 
-    def test_prefill_attention(self, q, kcache, vt, q_off, q_len, kv_len, out_init=None):
+    def arm_share_prompt_hook(self, pre_row, pre_len):
+        """sonic_load_tensor "share_prompt.hook": int32 [2][B] = pre_row | pre_len for the next test_prefill_attention launch on this handle, which then runs the
+        shared-prefix kernel and validates them against its shapes"""
+        from .engine import DTYPE_I32, SonicError
+        w = np.ascontiguousarray(np.stack([np.asarray(pre_row, np.int32), np.asarray(pre_len, np.int32)]), np.int32)
+        if self.lib.sonic_load_tensor(self.h, b"share_prompt.hook", _p(w), DTYPE_I32, (C.c_int64 * 2)(2, w.shape[1]), 2) != 0:
+            raise SonicError((self.lib.sonic_last_error(None) or b"").decode())
+
+    def test_prefill_attention(self, q, kcache, vt, q_off, q_len, kv_len, out_init=None, pre_row=None, pre_len=None):
         """The prefill's causal attention with run_prefill's strides.  q [n_tok][Hq][128] packed, kcache [B][Hkv][ctx_max][128], vt [B][Hkv][128][ctx_max],
-        q_off / q_len / kv_len [B].  out_init [n_tok][Hq][128] is what the output buffer holds before the launch (default zeros).  -> [n_tok][Hq][128]"""
+        q_off / q_len / kv_len [B].  out_init [n_tok][Hq][128] is what the output buffer holds before the launch (default zeros).  pre_row / pre_len [B]: armed as
+        the share-prompt hook first - sequence b's keys [0, pre_len[b]) are those of cache row pre_row[b].  -> [n_tok][Hq][128]"""
         q = np.ascontiguousarray(q, np.float32); kc = np.ascontiguousarray(kcache, np.float32); vt = np.ascontiguousarray(vt, np.float32)
         n_tok, Hq, hd = q.shape
         B, Hkv, ctx, _ = kc.shape
         assert hd == 128 and kc.shape[3] == 128 and vt.shape == (B, Hkv, 128, ctx)
         qo, ql, kl = (np.ascontiguousarray(x, np.int32) for x in (q_off, q_len, kv_len))
         assert qo.shape == ql.shape == kl.shape == (B,)
+        if pre_row is not None:
+            self.arm_share_prompt_hook(pre_row, pre_len)
         out = np.zeros_like(q) if out_init is None else np.array(out_init, np.float32, order="C")
         assert out.shape == q.shape
         self._check(self.lib.sonic_test_prefill_attention(self.h, _p(q), _p(kc), _p(vt), _p(qo), _p(ql), _p(kl), _p(out), n_tok, B, Hq, Hkv, ctx))

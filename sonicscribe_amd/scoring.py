@@ -82,12 +82,14 @@ class Run(NamedTuple):
     groups: List[Tuple[int, List[Optional[int]]]]
 
 
-def plan_runs(prompt_lens: Sequence[int], cand_lens: Sequence[Sequence[int]], max_batch: int, tok_cap: int, max_ctx: int) -> List[Run]:
+def plan_runs(prompt_lens: Sequence[int], cand_lens: Sequence[Sequence[int]], max_batch: int, tok_cap: int, max_ctx: int, share_prompt: bool = False) -> List[Run]:
     """Split A audios with their candidates over runs.  prompt_lens[a]: audio a's prompt tokens; cand_lens[a][c]: the target ids of its candidate c.  A run holds
     at most max_batch sequences and tok_cap tokens, a sequence of P prompt tokens and L targets counting P + L - 1 (the last target is only scored, never fed); a
     dummy is one target: P tokens.  Every run has ONE fan-out N: the largest candidate count, capped by max_batch and by how many of the longest sequence fit
     tok_cap; an audio with more candidates appears in several groups, its last group padded with dummies.  ValueError for a candidate that cannot be scored at
-    all: prompt + targets beyond max_ctx, or one sequence beyond tok_cap."""
+    all: prompt + targets beyond max_ctx, or one sequence beyond tok_cap.
+    share_prompt (engine option forced_share_prompt): a group prefills its prompt once - it counts P + the sum of its candidates' L - 1, a dummy
+    counts nothing, and N is capped by how many suffixes of the longest candidate fit tok_cap beside the longest prompt."""
     A = len(prompt_lens)
     if A != len(cand_lens):
         raise ValueError(f"{A} audios but {len(cand_lens)} candidate lists")
@@ -105,13 +107,22 @@ def plan_runs(prompt_lens: Sequence[int], cand_lens: Sequence[Sequence[int]], ma
     most = max((len(c) for c in cand_lens), default=0)
     if most == 0:
         return []
-    N = max(1, min(int(max_batch), most, tok_cap // longest))
+    if share_prompt:
+        p_max = max(int(p) for p in prompt_lens)
+        l_max = max(int(L) for c in cand_lens for L in c)
+        fit = (tok_cap - p_max) // max(1, l_max - 1)      # P + N (L - 1) <= tok_cap for the longest P and L: no group of N outgrows a run
+    else:
+        fit = tok_cap // longest
+    N = max(1, min(int(max_batch), most, fit))
     groups: List[Tuple[int, List[Optional[int]], int]] = []        # (audio, candidates, tokens)
     for a in range(A):
         idx = list(range(len(cand_lens[a])))
         for i in range(0, len(idx), N):
             part: List[Optional[int]] = list(idx[i:i + N])
-            tokens = sum(prompt_lens[a] + cand_lens[a][c] - 1 for c in part) + (N - len(part)) * prompt_lens[a]
+            if share_prompt:
+                tokens = prompt_lens[a] + sum(cand_lens[a][c] - 1 for c in part)
+            else:
+                tokens = sum(prompt_lens[a] + cand_lens[a][c] - 1 for c in part) + (N - len(part)) * prompt_lens[a]
             groups.append((a, part + [None] * (N - len(part)), int(tokens)))
     runs: List[Run] = []
     cur: List[Tuple[int, List[Optional[int]]]] = []

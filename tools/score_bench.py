@@ -1,10 +1,12 @@
-"""What scoring given transcripts costs, host call to return -> profiles/score_bench.json (a record, not a test; DESIGN.md 6.8 quotes it).
+"""What scoring given transcripts costs, host call to return -> profiles/score_bench.json (a record, not a test; DESIGN.md 6.8 and 6.14 quote it).
 
-Full dimensions, synthetic weights, one 20 s segment, 8 candidates of 150 tokens each.  Three measurements on ONE handle:
+Full dimensions, synthetic weights, one 20 s segment.  First shape, 8 candidates of 150 tokens each, four measurements on ONE handle:
   (a) fanout    the parallel forced run with forced_fanout = 8: one encoder pass, eight sequences in one prefill
   (b) staged8   the parallel forced run with the audio staged eight times: eight encoder passes
   (c) stepwise  the same eight sequences through the step-by-step forced run (option forced_parallel off): the eager decode loop, one step per token
-Wall time per call: warm-up rounds, then the three forms alternating round by round (so drift hits all of them alike); median, 10th / 90th percentile and the
+  (d) shared    (a) with forced_share_prompt: the prompt is prefilled once, seven sequences pack only their own tokens
+Second shape ("phrase_list"), 32 candidates of 6 tokens each on a handle of max_batch 32: (a) and (d) alone.
+Wall time per call: warm-up rounds, then the forms alternating round by round (so drift hits all of them alike); median, 10th / 90th percentile and the
 count are reported for each, and the device's own stage times of the last round.  Nothing is asserted.
 
     python tools/score_bench.py [--rounds 7] [--warmup 2] [--candidates 8] [--tokens 150] [--tiny]
@@ -29,19 +31,13 @@ def spread(xs):
     return {"median_ms": round(statistics.median(xs) * 1e3, 3), "p10_ms": round(xs[len(xs) // 10] * 1e3, 3), "p90_ms": round(xs[(len(xs) * 9) // 10] * 1e3, 3), "n": len(xs)}
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--candidates", type=int, default=8)
-    ap.add_argument("--tokens", type=int, default=150)
-    ap.add_argument("--seconds", type=float, default=20.0)
-    ap.add_argument("--tiny", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "score_bench.json"))
-    a = ap.parse_args()
+def bits_equal(a, b):
+    return bool(np.array_equal(a.astype(np.float32).view(np.uint32), b.astype(np.float32).view(np.uint32)))
+
+
+def measure(d, a, C, n_tok, which):
+    """the forms named in `which` on one handle of max_batch max(8, C), alternating -> the shape's record"""
     from sonicscribe_amd.engine import Engine
-    d = spec.TINY if a.tiny else spec.FULL
-    C, n_tok = a.candidates, a.tokens
     eng = Engine(d, 0, 0, max_batch=max(8, C), max_ctx=1024)
     eng.set_option("token_logprobs", 1)
     eng.load_synthetic(20260128)
@@ -58,6 +54,10 @@ def main():
         eng.set_option("forced_parallel", 1)
         return eng.score_batch([pcm], [prompt] * C, force, fanout=C)
 
+    def shared():
+        eng.set_option("forced_parallel", 1)
+        return eng.score_batch([pcm], [prompt] * C, force, fanout=C, share_prompt=True)
+
     def staged():
         eng.set_option("forced_parallel", 1)
         return eng.score_batch([pcm] * C, [prompt] * C, force)
@@ -69,12 +69,12 @@ def main():
             return eng.transcribe_batch([pcm] * C, [prompt] * C, [n_tok] * C, want_logprobs=True)
         finally:
             eng.set_forced_ids(None)
-    forms = [("fanout", fanout), ("staged8", staged), ("stepwise", stepwise)]
+    every = {"fanout": fanout, "staged8": staged, "stepwise": stepwise, "shared": shared}
+    forms = [(k, every[k]) for k in which]
     t = {k: [] for k, _ in forms}
-    dev = {}
-    last = {}
+    dev, last, tokens = {}, {}, {}
     for r in range(a.warmup + a.rounds):
-        order = forms[r % 3:] + forms[:r % 3]
+        order = forms[r % len(forms):] + forms[:r % len(forms)]
         for name, fn in order:
             t0 = time.perf_counter()
             out = fn()
@@ -84,17 +84,40 @@ def main():
                 t[name].append(dt)
                 tm = eng.timings()
                 dev[name] = {k: round(float(tm[k]), 3) for k in ("mel_ms", "encoder_ms", "prefill_ms", "decode_ms", "total_ms")}
+                if name in ("fanout", "shared"):
+                    tokens[name] = int(eng.debug_read("score_tokens", (1,))[0])
     mem1 = eng.memory_info()[0]
+    eng.close()
     lp = {k: np.concatenate([np.asarray(x, np.float64) for x in v[2]]) for k, v in last.items()}
     rec = {"dims": "tiny" if a.tiny else "full", "seconds": a.seconds, "candidates": C, "tokens": n_tok, "prompt_tokens": len(prompt),
-           "rounds": a.rounds, "warmup": a.warmup, "wall": {k: spread(v) for k, v in t.items()}, "device_last_round": dev,
-           "fanout_equals_staged8_bits": bool(np.array_equal(lp["fanout"].astype(np.float32).view(np.uint32), lp["staged8"].astype(np.float32).view(np.uint32))),
-           "max_abs_dlp_parallel_vs_stepwise": float(np.abs(lp["fanout"] - lp["stepwise"]).max()),
+           "rounds": a.rounds, "warmup": a.warmup, "wall": {k: spread(v) for k, v in t.items()}, "device_last_round": dev, "prefill_tokens": tokens,
            "score_buffers_bytes": int(mem1 - mem0)}
     w = rec["wall"]
-    rec["stepwise_over_fanout"] = round(w["stepwise"]["median_ms"] / w["fanout"]["median_ms"], 2)
-    rec["staged8_over_fanout"] = round(w["staged8"]["median_ms"] / w["fanout"]["median_ms"], 2)
-    eng.close()
+    if "staged8" in lp:
+        rec["fanout_equals_staged8_bits"] = bits_equal(lp["fanout"], lp["staged8"])
+        rec["staged8_over_fanout"] = round(w["staged8"]["median_ms"] / w["fanout"]["median_ms"], 2)
+    if "stepwise" in lp:
+        rec["max_abs_dlp_parallel_vs_stepwise"] = float(np.abs(lp["fanout"] - lp["stepwise"]).max())
+        rec["stepwise_over_fanout"] = round(w["stepwise"]["median_ms"] / w["fanout"]["median_ms"], 2)
+    rec["max_abs_dlp_shared_vs_fanout"] = float(np.abs(lp["shared"] - lp["fanout"]).max())
+    rec["shared_equals_fanout_bits"] = bits_equal(lp["shared"], lp["fanout"])
+    rec["shared_over_fanout"] = round(w["shared"]["median_ms"] / w["fanout"]["median_ms"], 3)
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--candidates", type=int, default=8)
+    ap.add_argument("--tokens", type=int, default=150)
+    ap.add_argument("--seconds", type=float, default=20.0)
+    ap.add_argument("--tiny", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "score_bench.json"))
+    a = ap.parse_args()
+    d = spec.TINY if a.tiny else spec.FULL
+    rec = measure(d, a, a.candidates, a.tokens, ("fanout", "staged8", "stepwise", "shared"))
+    rec["phrase_list"] = measure(d, a, 32, 6, ("fanout", "shared"))
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(rec, f, indent=1)
