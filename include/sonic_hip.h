@@ -188,7 +188,33 @@ SONIC_API int sonic_pipeline_destroy(sonic_pipeline* p);
 
 /* ---- weights (names: GlmAsrForConditionalGeneration.state_dict() keys, see sonicscribe_amd/spec.py) ----
  * On a finalized engine the call also carries the named int32 words that need no entry point of their own: "grammar:<id>" / "grammar.dispatch:<id>" /
- * "grammar.hook:<V>" (DESIGN.md 6.10), "request_draft" / "draft.dispatch" (6.11, beside sonic_set_forced_ids) and "request_forks":
+ * "grammar.hook:<V>" (DESIGN.md 6.10), "request_draft" / "draft.dispatch" (6.11, beside sonic_set_forced_ids), "request_forks" and "lm:<id>" / "lm.hook:<V>" /
+ * "lm.hook.step":
+ *
+ * Shallow fusion (options lm / lm_weight): a backoff n-gram language model over the model's own tokens, added to every step's scores inside the decode
+ * loops.  One hypothesis, no search; an option of a handle, not a value of a request.
+ *   sonic_load_tensor(e, "lm:<id>", words, SONIC_DTYPE_I32, {n}, 1), id in 1 .. 65535, creates the model on e's weight owner (shape {0}: destroys it - refused by
+ *   name while a handle's option lm refers to it); it takes the owner's registry lock, not the engine lock, and its bytes are counted by sonic_memory_info.
+ *   words (floats as their bits): V | N | E | order | start | uni[V] f32 | node_off[N + 1] | bo_next[N] | bo_w[N] f32 | edge_tok[E] | edge_next[E] | edge_w[E] f32.
+ *   Node 0 is the empty context; a node's edges ascend strictly by token id; bo_next[0] = -1 and 0 <= bo_next[n] < n (nodes are numbered by context length), a
+ *   chain has at most order - 1 links; uni[w], the root's log-probability (natural log) of every id, and all weights are finite; root edges serve the transition
+ *   only and carry uni's bits; order <= 8, N <= 4 194 304, E <= 16 777 216, V = the model's vocabulary; a node may have no edge.  Every violation is
+ *   SONIC_ERR_INVALID naming the rule (the calling thread's sonic_last_error(NULL)); nothing is truncated.
+ *   scores of a row at node n, all in fp32 with separately rounded operations, L = lm_weight: c_0 = n, c_{j+1} = bo_next[c_j] down to c_k = 0; A_0 = +0,
+ *   A_{j+1} = A_j + bo_w[c_j]; add[w] = L * (A_k + uni[w]) for every w; then for j = k - 1 down to 0, in that order, add[edge_tok[e]] = L * (A_j + edge_w[e]) for
+ *   every edge e of c_j: the longest context that lists an id wins.  transition on the emitted token t: t is searched among the node's edges - found, the state is
+ *   edge_next; else the search repeats at bo_next, and ends at the root; a token outside [0, V) ends at the root.
+ *   option lm = id (0: off; after token_logprobs; on the owner before its slots are created - they copy it), option lm_weight = the bits of the fp32 L, finite and >= 0.
+ *   lm switches the rows' history on as grammar does and allocates two state words per row and the vector buffer, max_batch x V fp32.  lm_step_kernel (one block per
+ *   row) then runs right ahead of every greedy launch - prefill, decode steps of every kind, captured or not - consuming the row's pending token and writing its
+ *   vector; the greedy kernel's LM instantiations form rT(logit) + add[w] ahead of the request bias (then penalty, bans, temperature).  The step logits stay raw; the
+ *   log-probabilities, the alternatives and the truncation see the fused scores.  sonic_splice_rows moves the two words and refuses handles whose lm or lm_weight
+ *   differ.  Refused by name: lm beside grammar or draft_verify (and the reverse), row forks and sonic_pipeline_create on such a handle; a scoring handle
+ *   (forced_parallel) ignores it.  The int8 and fp32 kinds support it (same greedy families).
+ *   hooks: "lm.hook:<V>" arms an automaton validated against V (shape {0}: disarms); options hook_lm_state = row << 24 | state, hook_lm_tok = row << 24 | (token + 1)
+ *   (0: none pending) and hook_lm_weight = the bits set the rows' words; "lm.hook.step" (one `finished` word per row) launches lm_step_kernel alone;
+ *   sonic_debug_read "hook_lm_state" / "hook_lm_tok" / "hook_lm_add" read the states, pending tokens and vectors [rows][V].  The next guard / bias / sample hook
+ *   launch of that V with log-probabilities takes the vector through its family's LM instantiation and leaves the emitted ids in the pending tokens.
  *
  * Row forks (sonic_load_tensor "request_forks"): one prefilled request becomes several rows - N samples of one audio (Whisper's best_of) pay for
  * log-mel, encoder and prefill once.

@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import asyncio
 import math
+import os
 import threading
 import time
 from concurrent.futures import Future
@@ -27,7 +28,7 @@ from typing import Any, Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import fallback, frontend, genconfig, grammar as grammar_, reqbias, reqvalues, sampling as sampling_, scoring as scoring_, timestamps as timestamps_, weights
+from . import fallback, frontend, genconfig, grammar as grammar_, ngram as ngram_, reqbias, reqvalues, sampling as sampling_, scoring as scoring_, timestamps as timestamps_, weights
 from .dispatch import Dispatcher
 from .engine import Engine, MODE_INT8, MODE_NATIVE, SonicError, TokenScores, device_count, device_info
 from .prompts import HFPrompt, SyntheticPrompt
@@ -95,6 +96,27 @@ _REFUSALS = (
 )
 
 
+def check_lm(lm, lm_weight, token_logprobs: bool, bulk: bool, grammar: bool, draft_verify: bool, best_of: int) -> float:
+    """ASRModel's lm / lm_weight arguments -> the fp32 weight, or ValueError by name: a weight that is not finite and >= 0; lm= without token_logprobs=True, or beside
+    bulk=True, grammar=True, draft_verify=True or best_of > 1 (the library's own refusals, DESIGN.md 6.15, ahead of any engine)"""
+    w = ngram_.check_weight(lm_weight)
+    if lm is None:
+        return w
+    if not isinstance(lm, (ngram_.NGramLM, str, os.PathLike)):
+        raise ValueError("lm= takes an ngram.NGramLM or the path of an ARPA file")
+    if not token_logprobs:
+        raise ValueError("lm= needs token_logprobs=True: the language model's kernels are log-probability kernels (ASRModel(..., token_logprobs=True, lm=...))")
+    if bulk:
+        raise ValueError("lm is not supported with bulk=True: the bulk pipeline carries no language-model state")
+    if grammar:
+        raise ValueError("lm is not supported with grammar=True: a grammar decides and a language model weighs - the kernels hold one of the two")
+    if draft_verify:
+        raise ValueError("lm is not supported with draft_verify=True: the verify pass knows no language model")
+    if int(best_of) > 1:
+        raise ValueError("lm is not supported with best_of > 1: a row fork copies no language-model state")
+    return w
+
+
 def check_share_prompt(share, scoring: bool, mode: str, timestamps: bool) -> bool:
     """score_share_prompt as ASRModel takes it: ValueError without scoring=True, with mode="int8" and with timestamps=True"""
     if not share:
@@ -121,6 +143,7 @@ class ASRModel:
     sampling = grammar = draft_verify = request_bias = scoring = score_share_prompt = timestamps = bulk = token_logprobs = continuous = False
     mode = "native"
     top_logprobs, best_of, slots = 0, 1, 1
+    lm, lm_weight = None, 0.0
 
     def __init__(self, checkpoint_dir: str, device: str = "cuda", mode: str = "native",
                  cpu_threads: Optional[int] = None, cpu_interop_threads: Optional[int] = None,
@@ -128,7 +151,7 @@ class ASRModel:
                  repetition_penalty: Optional[float] = None, no_repeat_ngram_size: Optional[int] = None, suppress_tokens: Optional[Sequence[int]] = None,
                  request_bias: bool = False, sequence_bias=None, bad_words_ids=None, hotword_boost: float = 0.0,
                  sampling: bool = False, temperature=0.0, seed: int = 0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0, compression_ratio_threshold: Optional[float] = 2.4, logprob_threshold: Optional[float] = -1.0, best_of: int = 1,
-                 scoring: bool = False, score_share_prompt: bool = False, timestamps: bool = False, alignment_heads=None, grammar: bool = False, draft_verify: bool = False,
+                 scoring: bool = False, score_share_prompt: bool = False, timestamps: bool = False, alignment_heads=None, grammar: bool = False, draft_verify: bool = False, lm=None, lm_weight: float = 0.3,
                  _dims: Optional[ModelDims] = None,
                  _synthetic_seed: Optional[int] = None, _allow_synthetic_prompt: bool = False, _options: Optional[Dict[str, int]] = None,
                  _engine_mode: Optional[int] = None):
@@ -148,7 +171,10 @@ class ASRModel:
         restricted to the transcripts of a grammar - compile_grammar() of a phrase list or of a grammar.Grammar, passed as `grammar=` of the transcribe calls; the mask and
         the state run inside the greedy kernel.  `draft_verify` (not with mode="int8", not with bulk=True): requests may bring a draft of their transcript
         as `draft=` of the transcribe calls - a previous partial, a first-pass model's output, an edited transcript; the prefill accepts the prefix the model itself would
-        have emitted and decoding starts behind it, so a right draft costs one prefill instead of its tokens' steps and a wrong one only its prefill rows.  `alignment_heads`: the [layer, head] pairs to read (None: the `alignment_heads` entry of the checkpoint's generation_config.json, else every head of the last half of the layers).  The arguments with a leading underscore are not part of the
+        have emitted and decoding starts behind it, so a right draft costs one prefill instead of its tokens' steps and a wrong one only its prefill rows.  `lm` (needs
+        token_logprobs=True; not with bulk=True, grammar=True, draft_verify=True or best_of > 1): shallow fusion - an ngram.NGramLM over the model's own tokens, or the
+        path of an ARPA file (ngram.NGramLM.from_arpa over the tokenizer's pieces, or decimal ids), whose log-probabilities times `lm_weight` are added to every step's
+        scores inside the decode loops of every entry point; token_logprobs, avg_logprob and the ladder's logprob_threshold are then over the fused scores.  `alignment_heads`: the [layer, head] pairs to read (None: the `alignment_heads` entry of the checkpoint's generation_config.json, else every head of the last half of the layers).  The arguments with a leading underscore are not part of the
         supported surface: they exist for the test-suite and the benchmark and may change without notice.  `_engine_mode` in particular (an engine.MODE_*
         value in place of the one `mode` selects) is unsupported outside the tests: MODE_F32 has no slots, so it needs slots=1, continuous=False."""
         # -- 1. the arguments, in _REFUSALS' order; no device is touched
@@ -166,6 +192,7 @@ class ASRModel:
         self.best_of = check_best_of(best_of, max_batch, self.sampling, bulk)
         self._max_batch = int(max_batch)
         self._refuse("grammar", "draft_verify", "scoring")
+        self.lm_weight = check_lm(lm, lm_weight, self.token_logprobs, self.bulk, self.grammar, self.draft_verify, self.best_of)
         self.score_share_prompt = check_share_prompt(score_share_prompt, self.scoring, mode, self.timestamps)
         self._grammars: List[Any] = []      # what compile_grammar() made, closed with the model
         self.alignment_heads = timestamps_.check_timestamps(self.timestamps, self.scoring, alignment_heads, *((_dims.dec_layers, _dims.dec_heads) if _dims is not None else ()))
@@ -242,6 +269,12 @@ class ASRModel:
                     eng.set_generation(*v)
                 else:
                     eng.set_option(k, v)
+        # lm: the automaton onto every replica, the options lm_weight / lm on its owner - every slot made below copies them (a scoring slot ignores them)
+        if lm is not None:
+            tok = self.prompt.processor.tokenizer if isinstance(self.prompt, HFPrompt) else None
+            self.lm = ngram_.load(lm, self.dims.vocab, eos_ids=self._eos_ids(), token_id=None if tok is None else (lambda s, _v=tok.get_vocab(): _v.get(s)))
+            for eng in self.models:
+                eng.set_lm(eng.lm_create(self.lm), self.lm_weight)
         # -- 4. the handles and the dispatcher
         self._retrier = fallback.Retrier()
         self.model = self.models[0]                  # main.py:84-86 checks and deletes `.model`
@@ -603,6 +636,8 @@ class ASRModel:
                         info.update({"temperature": det.temperature, "compression_ratio": det.compression_ratio, "top_k": det.top_k, "top_p": det.top_p, "min_p": det.min_p})
                     if self.best_of > 1:              # a best_of model: how many samples the returned attempt drew, and which of them this is
                         info.update({"best_of": det.best_of, "fork_index": det.fork_index})
+                    if self.lm is not None:           # an lm model: the weight, and what the language model alone says of the returned ids
+                        info.update({"lm_weight": self.lm_weight, "lm_logprob": self.lm.walk(det.token_ids)[1]})
                     if grammar is not None:
                         info["grammar_status"] = det.grammar_status
                     if draft is not None:
@@ -677,6 +712,13 @@ class ASRModel:
                 raise ValueError("a text candidate needs a tokenizer (a checkpoint with its processor): the synthetic prompt has none - pass token ids")
             return [int(t) for t in self.prompt.processor.tokenizer.encode(cand, add_special_tokens=False)]
         return [int(t) for t in np.asarray(cand).reshape(-1)]
+
+    def lm_score(self, text_or_ids) -> float:
+        """The sum of the language model's log-probabilities (natural log, unweighted) over a transcript - a string, tokenised with the checkpoint's tokenizer, or
+        token ids - walked from the model's start node (ngram.NGramLM.walk).  Needs a model built with lm=."""
+        if self.lm is None:
+            raise ValueError("lm_score needs a model built with lm= (ASRModel(..., token_logprobs=True, lm=...))")
+        return float(self.lm.walk(self._candidate_ids(text_or_ids))[1])
 
     def share_prompt_refusal(self) -> Optional[str]:
         """why this model's scoring handles cannot share a prompt, or None: the library refuses the same by the option's name"""
@@ -819,7 +861,8 @@ class ASRModel:
                      "gpu_memory_total_mb": di["total_bytes"] / 1024 ** 2})
         info.update({"engine": "sonicscribe_amd/gfx950", "replicas": len(self.__dict__.get("models", [])), "slots_per_replica": self.slots, "continuous": self.continuous, "bulk": self.bulk,
                      "weights_mb": self.model.weight_bytes() / 1024 ** 2 if hasattr(self, "model") else 0.0})
-        info.update({"scoring": self.scoring, "grammar": self.grammar, "draft_verify": self.draft_verify, "best_of": self.best_of, "timestamps": self.timestamps})
+        info.update({"scoring": self.scoring, "grammar": self.grammar, "draft_verify": self.draft_verify, "best_of": self.best_of, "timestamps": self.timestamps,
+                     "lm": self.lm is not None, "lm_weight": self.lm_weight if self.lm is not None else 0.0})
         g = self.__dict__.get("generation_guards")
         if g is not None:                            # the logits processors in force: the checkpoint's generation_config.json unless the constructor overrode it
             info.update(g.as_dict())

@@ -134,6 +134,7 @@ static void decode_step_gemv(sonic_engine* e, int R, bool dump) {
     gv(GEMV_SLAB_NORM, e->sx, D, e->embed_t, d.vocab, D, e->dec_nw, e->lslab, nullptr, nullptr);
     GreedyArgs g = greedy_args(e, R, dump);
     g.ksplit = 1;
+    lm_step(e, R);                                                  // option lm: the rows' vectors right ahead of the launch that adds them
     launch_greedy(g, e->st);
 }
 // experiment (decode_prefetch bits 0 / 1): the attention launch covers R x Hkv of the 256 CUs - the others stream the weights of the kernels behind it
@@ -184,6 +185,7 @@ static void decode_step_i8(sonic_engine* e, int R, bool dump) {
         launch_add_rmsnorm(e->sx, e->slab, ks, mpad, nw, e->shn, R, D, d.dec_rms_eps, e->st, DT_F16, &dq, &q_hn);
     }
     skinny(e, e->shn, D, e->embed_t, e->lslab, R, d.vocab, D, nullptr);   // lm_head is not swapped (asr.py:177): fp16 skinny GEMM
+    lm_step(e, R);
     launch_greedy(greedy_args(e, R, dump), e->st);
 }
 
@@ -229,6 +231,7 @@ static void decode_step(sonic_engine* e, int R, bool dump) {
     }
     if (f.pre) skinny_pre(e->embed_t, e->lslab, d.vocab, e->dec_nw, nullptr, nullptr, nullptr);   // tied lm_head behind the last layer's slabs (the updated residual is not needed again)
     else skinny(e, e->shn, D, e->embed_t, e->lslab, R, d.vocab, D, nullptr);                    // tied lm_head (modeling_glmasr.py:517)
+    lm_step(e, R);
     launch_greedy(greedy_args(e, R, dump), e->st);
 }
 
@@ -237,7 +240,7 @@ static void decode_step(sonic_engine* e, int R, bool dump) {
 // svc: the chunk belongs to a continuous decode loop (sonic_service_*), i.e. it runs beside a prefill slot and other loops by design - decode_step then
 // picks the forms that cost the fewest CU-microseconds rather than the shortest chain (gu64_split_norm).  Same bits either way; cached separately.
 int chunk_graph(sonic_engine* e, int R, int n, hipGraphExec_t* out, bool svc) {
-    const std::pair<int, int> key{R + (svc ? GK_SVC : 0) + (e->opt_token_logprobs ? GK_LP : 0) + (e->gen_on ? GK_GUARD : 0) + e->opt_top_logprobs * GK_TOPK + req_graph_key(e), n};   // (the LP / GUARD / BIAS / SAMPLE / TOPK / GRAMMAR greedy kernel and its pointers are part of the capture)
+    const std::pair<int, int> key{R + (svc ? GK_SVC : 0) + (e->opt_token_logprobs ? GK_LP : 0) + (e->gen_on ? GK_GUARD : 0) + e->opt_top_logprobs * GK_TOPK + req_graph_key(e), n};   // (the LP / GUARD / BIAS / SAMPLE / TOPK / GRAMMAR / LM greedy kernel and its pointers are part of the capture)
     auto it = e->graphs.find(key);
     if (it != e->graphs.end()) { *out = it->second; return SONIC_OK; }
     hipGraph_t g = nullptr; hipGraphExec_t gx = nullptr;

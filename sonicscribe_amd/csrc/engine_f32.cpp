@@ -189,5 +189,6 @@ void f32_score_logits(sonic_engine* e, int row0, int n, float* logits) {
 void decode_step_f32(sonic_engine* e, int R, bool dump) {
     f32_decoder_layers(e, R, e->seq_iota, e->tok_pos);
     f32_lm_head(e, R, nullptr);
+    lm_step(e, R);
     launch_greedy(f32_greedy_args(e, R, dump), e->st);
 }

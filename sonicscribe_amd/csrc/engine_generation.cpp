@@ -424,6 +424,7 @@ static sonic_grammar* gram_ref_id(sonic_engine* root, int id) {
     return nullptr;
 }
 int gram_enable(sonic_engine* e, int on) {
+    if (on && e->opt_lm) return fail(e, SONIC_ERR_INVALID, "grammar: option lm is on: a grammar decides and a language model weighs - the kernels hold one of the two (weighted grammars are not built)");
     if (on && !lp_on(e)) return fail(e, SONIC_ERR_INVALID, "grammar: option token_logprobs must be on first (the grammar kernels are log-probability kernels; sonic_set_option(e, \"token_logprobs\", 1))");
     if (on && greedy_guard_lds(e->d.vocab) > 60000) return fail(e, SONIC_ERR_UNSUPPORTED, "grammar: a vocabulary of %d ids does not fit the guard bitmaps", e->d.vocab);
     if (!on && e->opt_grammar) { gram_drop_staged(e); for (int r = 0; r < 64; ++r) gram_row_release(e, r); }
@@ -517,6 +518,7 @@ extern "C" int engine_thread_fail(int code, const char* msg) { return fail(nullp
 // ---- option draft_verify (include/sonic_hip.h beside sonic_set_forced_ids): HF generate()'s assisted / prompt-lookup decoding with the draft given by
 // the caller.  The caller holds the lock and has asked gen_busy.  No buffer comes with the option: draft_alloc brings them at the handle's first drafted prefill
 int draft_enable(sonic_engine* e, int on) {
+    if (on && e->opt_lm) return fail(e, SONIC_ERR_INVALID, "draft_verify: option lm is on: the verify pass (rows_kernel) knows no language model");
     if (on && e->i8) return fail(e, SONIC_ERR_INVALID, "draft_verify: the int8 kind refuses it (its prefill finds the outlier columns over the rows of a request: a draft would change the group, and with it the prompt's own values)");
     if (on && e->f32) return fail(e, SONIC_ERR_INVALID, "draft_verify: the fp32 test kind has no verify kernels; use a bf16 or fp16 handle");
     if (on && e->opt_forced_parallel) return fail(e, SONIC_ERR_INVALID, "draft_verify: option forced_parallel is on: a scoring handle decodes nothing a draft could shorten");
@@ -634,6 +636,7 @@ int fork_stage_counts(sonic_engine* e, const void* data, int dtype, const int64_
     e->fork_pending = -1;
     if (e->i8) return fail(e, SONIC_ERR_INVALID, "request_forks: the int8 kind refuses it (its decode step keeps quantised rows and outlier lists per row that the prefill's head leaves for the sources alone)");
     if (e->f32) return fail(e, SONIC_ERR_INVALID, "request_forks: the fp32 test kind has no fork kernel; use a bf16 or fp16 handle");
+    if (e->opt_lm) return fail(e, SONIC_ERR_INVALID, "request_forks: option lm is on: the fork copies no language-model state");
     if (e->opt_forced_parallel) return fail(e, SONIC_ERR_INVALID, "request_forks: option forced_parallel is on: a scoring handle decodes nothing a fork could sample");
     if (dtype != SONIC_DTYPE_I32 || ndim != 1 || shape[0] < 1) return fail(e, SONIC_ERR_INVALID, "request_forks: the counts are one row of int32 words, one per request (SONIC_DTYPE_I32, ndim 1)");
     const int64_t A = shape[0]; const int* w = (const int*)data;
@@ -689,6 +692,136 @@ extern "C" int sonic_get_generation(sonic_engine* e, float* repetition_penalty, 
     return SONIC_OK;
 }
 
+// ---- options lm / lm_weight: shallow fusion with a backoff n-gram language model over the model's own tokens - NeMo's n-gram fusion for BPE models, ESPnet's
+// ngram_weight - as a weighted automaton on the device: lm_step_kernel (lm.hip) turns a row's state into its additive vector right ahead of every greedy launch, the
+// greedy kernel's LM instantiations add it.  Models live on the weight owner, as grammars do; a handle's option names one by id.
+// The validation, rule by rule in the words of sonicscribe_amd/ngram.py (NGramLM.validate); the message is the calling thread's (sonic_last_error(NULL))
+int lm_check(const char* who, const int* w, int64_t n, int vocab) {
+    if (n < LM_WIRE_HEAD) return fail(nullptr, SONIC_ERR_INVALID, "%s: %lld words do not hold the header [V | N | E | order | start]", who, (long long)n);
+    const int V = w[0], N = w[1], E = w[2], order = w[3], start = w[4];
+    if (V < 1 || N < 1 || E < 0 || n != (int64_t)LM_WIRE_HEAD + V + ((int64_t)N + 1) + 2 * (int64_t)N + 3 * (int64_t)E)
+        return fail(nullptr, SONIC_ERR_INVALID, "%s: %lld words, the header (V %d, N %d, E %d) asks for %lld", who, (long long)n, V, N, E, (long long)((int64_t)LM_WIRE_HEAD + V + ((int64_t)N + 1) + 2 * (int64_t)N + 3 * (int64_t)E));
+    if (V != vocab) return fail(nullptr, SONIC_ERR_INVALID, "%s: the automaton's vocabulary is %d, the model's %d", who, V, vocab);
+    if (order < 1 || order > LM_MAX_ORDER) return fail(nullptr, SONIC_ERR_INVALID, "%s: order %d is outside 1 .. %d", who, order, LM_MAX_ORDER);
+    if (N > LM_MAX_NODES) return fail(nullptr, SONIC_ERR_INVALID, "%s: %d nodes (1 .. %d; nothing is truncated)", who, N, LM_MAX_NODES);
+    if (E > LM_MAX_EDGES) return fail(nullptr, SONIC_ERR_INVALID, "%s: %d edges (0 .. %d; nothing is truncated)", who, E, LM_MAX_EDGES);
+    if (start < 0 || start >= N) return fail(nullptr, SONIC_ERR_INVALID, "%s: start node %d (0 .. %d)", who, start, N - 1);
+    const int* uni = w + LM_WIRE_HEAD; const int* off = uni + V; const int* bo_next = off + N + 1; const int* bo_w = bo_next + N;
+    const int* tok = bo_w + N; const int* nxt = tok + E; const int* ew = nxt + E;
+    auto finite = [](int bits) { return (bits & 0x7f800000) != 0x7f800000; };
+    for (int i = 0; i < V; ++i) if (!finite(uni[i])) return fail(nullptr, SONIC_ERR_INVALID, "%s: uni[%d] is not finite", who, i);
+    if (off[0] != 0) return fail(nullptr, SONIC_ERR_INVALID, "%s: node_off[0] is %d, not 0", who, off[0]);
+    if (off[N] != E) return fail(nullptr, SONIC_ERR_INVALID, "%s: node_off[%d] is %d, not the edge count %d", who, N, off[N], E);
+    for (int i = 0; i < N; ++i) if (off[i + 1] < off[i]) return fail(nullptr, SONIC_ERR_INVALID, "%s: node_off is not monotone at node %d", who, i);
+    if (bo_next[0] != -1) return fail(nullptr, SONIC_ERR_INVALID, "%s: bo_next[0] is %d, not -1 (node 0 is the root)", who, bo_next[0]);
+    for (int i = 1; i < N; ++i) if (bo_next[i] < 0 || bo_next[i] >= i) return fail(nullptr, SONIC_ERR_INVALID, "%s: bo_next[%d] is %d (0 .. %d: nodes are numbered by context length)", who, i, bo_next[i], i - 1);
+    {
+        std::vector<unsigned char> depth((size_t)N, 0);
+        for (int i = 1; i < N; ++i) {
+            depth[i] = (unsigned char)(depth[bo_next[i]] + 1);
+            if (depth[i] > order - 1) return fail(nullptr, SONIC_ERR_INVALID, "%s: the backoff chain of node %d has %d links (at most order - 1 = %d)", who, i, (int)depth[i], order - 1);
+        }
+    }
+    for (int i = 0; i < N; ++i) if (!finite(bo_w[i])) return fail(nullptr, SONIC_ERR_INVALID, "%s: bo_w[%d] is not finite", who, i);
+    for (int k = 0; k < E; ++k) if (tok[k] < 0 || tok[k] >= V) return fail(nullptr, SONIC_ERR_INVALID, "%s: token id %d is out of vocabulary (%d)", who, tok[k], V);
+    for (int i = 0; i < N; ++i) for (int k = off[i] + 1; k < off[i + 1]; ++k) if (tok[k] <= tok[k - 1]) return fail(nullptr, SONIC_ERR_INVALID, "%s: the edges of node %d are not sorted and unique by token id", who, i);
+    for (int k = 0; k < E; ++k) if (nxt[k] < 0 || nxt[k] >= N) return fail(nullptr, SONIC_ERR_INVALID, "%s: an edge leads to node %d (0 .. %d)", who, nxt[k], N - 1);
+    for (int k = 0; k < E; ++k) if (!finite(ew[k])) return fail(nullptr, SONIC_ERR_INVALID, "%s: edge_w[%d] is not finite", who, k);
+    for (int k = 0; k < off[1]; ++k) if (ew[k] != uni[tok[k]]) return fail(nullptr, SONIC_ERR_INVALID, "%s: root edge %d (token %d) does not carry the bits of uni[%d]", who, k, tok[k], tok[k]);
+    return SONIC_OK;
+}
+void lm_to_device_words(const int* w, std::vector<int>& out) {
+    const int64_t n = (int64_t)LM_WIRE_HEAD + w[0] + ((int64_t)w[1] + 1) + 2 * (int64_t)w[1] + 3 * (int64_t)w[2];
+    out.assign((size_t)(n - LM_WIRE_HEAD + LM_HEAD), 0);
+    memcpy(out.data(), w, LM_WIRE_HEAD * 4);
+    memcpy(out.data() + LM_HEAD, w + LM_WIRE_HEAD, (size_t)(n - LM_WIRE_HEAD) * 4);
+}
+// sonic_load_tensor(e, "lm:<id>", words, SONIC_DTYPE_I32, {n}, 1): created once on a weight owner (a slot's call lands on its owner) under an id the caller chooses;
+// n = 0 destroys it, refused by name while a handle's option lm refers to it; what is left when the owner goes is freed with it.  Takes the owner's registry lock,
+// not the engine lock, as gram_create
+int lm_create(sonic_engine* e, int id, const int* words, int64_t n) {
+    sonic_engine* root = e->owner ? e->owner : e;
+    if (!root->finalized) return fail(nullptr, SONIC_ERR_INVALID, "lm: the engine's weights are not finalized");
+    if (id < 1 || id > 65535) return fail(nullptr, SONIC_ERR_INVALID, "lm: id %d is outside 1 .. 65535", id);
+    if (n == 0) {
+        sonic_lm* m = nullptr;
+        {
+            std::lock_guard<std::mutex> lk(root->gram_mu);
+            auto it = std::find_if(root->lms.begin(), root->lms.end(), [&](sonic_lm* x) { return x->id == id; });
+            if (it == root->lms.end()) return fail(nullptr, SONIC_ERR_INVALID, "lm: %d is not a live language model of this engine", id);
+            m = *it;
+            const int r = m->refs.load();
+            if (r > 0) return fail(nullptr, SONIC_ERR_INVALID, "lm: %d is in use: option lm of %d handle%s refer%s to it (set it to 0 there, or destroy the handles, first)", id, r, r == 1 ? "" : "s", r == 1 ? "s" : "");
+            root->lms.erase(it);
+        }
+        root->gram_bytes -= m->bytes;
+        if (hipSetDevice(root->device) == hipSuccess) (void)hipFree(m->dev);
+        (void)hipGetLastError();
+        delete m;
+        return SONIC_OK;
+    }
+    TRY(lm_check("lm", words, n, root->d.vocab));
+    std::vector<int> w; lm_to_device_words(words, w);
+    if (hipSetDevice(root->device) != hipSuccess) { (void)hipGetLastError(); return fail(nullptr, SONIC_ERR_HIP, "lm: hipSetDevice failed"); }
+    sonic_lm* m = new sonic_lm();
+    m->root = root; m->id = id; m->V = words[0]; m->N = words[1]; m->E = words[2]; m->order = words[3]; m->start = words[4]; m->bytes = (int64_t)w.size() * 4;
+    if (hipMalloc((void**)&m->dev, w.size() * 4) != hipSuccess) { (void)hipGetLastError(); delete m; return fail(nullptr, SONIC_ERR_OOM, "HIP out of memory (language model of %d nodes and %d edges)", words[1], words[2]); }
+    if (hipMemcpy(m->dev, w.data(), w.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(m->dev); delete m; return fail(nullptr, SONIC_ERR_HIP, "lm: upload failed"); }
+    {
+        std::lock_guard<std::mutex> lk(root->gram_mu);
+        for (sonic_lm* x : root->lms) if (x->id == id) { (void)hipFree(m->dev); delete m; return fail(nullptr, SONIC_ERR_INVALID, "lm: id %d is taken by a live language model of this engine", id); }
+        root->lms.push_back(m);
+    }
+    root->gram_bytes += m->bytes;
+    return SONIC_OK;
+}
+static void lm_unref(sonic_engine* e) { if (e->lm) { e->lm->refs.fetch_sub(1); e->lm = nullptr; } e->opt_lm = 0; }
+// option lm = id (0: off).  The caller holds the lock and has asked gen_busy
+int lm_select(sonic_engine* e, int id, sonic_engine* owner) {
+    if (id == 0) { lm_unref(e); drop_graphs(e); return SONIC_OK; }
+    if (id < 1 || id > 65535) return fail(e, SONIC_ERR_INVALID, "lm: id %d is outside 0 .. 65535", id);
+    if (!lp_on(e)) return fail(e, SONIC_ERR_INVALID, "lm: option token_logprobs must be on first (the language model's kernels are log-probability kernels; sonic_set_option(e, \"token_logprobs\", 1))");
+    if (e->opt_grammar) return fail(e, SONIC_ERR_INVALID, "lm: option grammar is on: a grammar decides and a language model weighs - the kernels hold one of the two (weighted grammars are not built)");
+    if (e->opt_draft_verify) return fail(e, SONIC_ERR_INVALID, "lm: option draft_verify is on: the verify pass (rows_kernel) knows no language model");
+    if (greedy_guard_lds(e->d.vocab, true) + greedy_trunc_lds() > 60000) return fail(e, SONIC_ERR_UNSUPPORTED, "lm: a vocabulary of %d ids does not fit the guard bitmaps", e->d.vocab);
+    sonic_engine* root = owner ? owner : e->owner ? e->owner : e;      // (owner: a slot under construction, which does not know its owner yet)
+    sonic_lm* m = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(root->gram_mu);
+        for (sonic_lm* x : root->lms) if (x->id == id) { x->refs.fetch_add(1); m = x; break; }
+    }
+    if (!m) return fail(e, SONIC_ERR_INVALID, "lm: %d is not a live language model of this handle's weight owner (sonic_load_tensor \"lm:<id>\" first)", id);
+    HIPC(e, hipSetDevice(e->device));
+    HIPC(e, stream_sync(e));
+    int s = SONIC_OK;
+    if (!e->hist) s = dalloc(e, &e->hist, (size_t)64 * e->max_ctx);
+    if (s == SONIC_OK && !e->lm_words) s = dalloc(e, &e->lm_words, (size_t)128);
+    if (s == SONIC_OK && !e->lm_add) s = dalloc(e, &e->lm_add, (size_t)e->Bm * e->d.vocab);
+    if (s != SONIC_OK) { m->refs.fetch_sub(1); return s; }
+    lm_unref(e);
+    e->lm = m; e->opt_lm = id;
+    launch_fill_i32(e->lm_words, m->start, 64, e->st); launch_fill_i32(e->lm_words + 64, -1, 64, e->st);
+    HIPC(e, stream_sync(e));
+    drop_graphs(e);                                      // the kernels and their arguments are part of every captured chunk
+    return SONIC_OK;
+}
+int lm_set_weight(sonic_engine* e, int bits) {
+    float w; memcpy(&w, &bits, 4);
+    if (!std::isfinite(w) || w < 0.f || (bits & 0x80000000)) return fail(e, SONIC_ERR_INVALID, "lm_weight: the value carries the bits of an fp32 weight, finite and >= 0 (got %g)", (double)w);
+    e->lm_weight = w;
+    drop_graphs(e);                                      // (an argument of the captured lm_step_kernel launches)
+    return SONIC_OK;
+}
+void lm_prefill_rows(sonic_engine* e, int R) {
+    if (!lm_live(e)) return;
+    launch_fill_i32(e->lm_words, e->lm->start, R, e->st); launch_fill_i32(e->lm_words + 64, -1, R, e->st);
+}
+void lm_step(sonic_engine* e, int R) {
+    if (!lm_live(e)) return;
+    launch_lm_step(LmArgs{e->lm->dev, e->lm_words, e->lm_words + 64, e->finished, e->lm_add, e->lm_weight, R}, e->st);
+}
+extern "C" int engine_lm_on(sonic_engine* e) { return e && e->opt_lm ? 1 : 0; }      // (pipeline.cpp: the bulk pipeline refuses such a handle)
+
 // ---- the stages at every point of a request's life.  Each function below names bias, samp, gram and trunc once, in that order; no other unit names them together.  (No
 // descriptor table: the stages' words differ in type - int, unsigned, 64-bit - so a table would erase the types to save one line in three per function.)
 int req_claim(sonic_engine* e, int R, bool forked) {
@@ -724,8 +857,9 @@ void req_greedy_args(const sonic_engine* e, GreedyArgs& g) {
     if (e->opt_sampling && g.out_lp) g.samp = e->samp.dev;      // (the option is refused without token_logprobs, and token_logprobs cannot leave while it is on)
     if (e->opt_truncation && g.samp) g.trunc = e->trunc.dev;   // (the option is refused without sampling, and sampling cannot leave while it is on)
     if (e->opt_grammar && g.out_lp && g.hist) { g.gram_ref = e->gram.dev; g.gram_state = gram_state_of(e); }      // (likewise; the option brought the history)
+    if (lm_live(e) && g.out_lp && g.hist) { g.lm_add = e->lm_add; g.lm_tok = e->lm_words + 64; }      // (option lm - no stage: a handle's option - rides here with the families' other pointers)
 }
-int req_graph_key(const sonic_engine* e) { return (e->opt_request_bias ? GK_BIAS : 0) + (e->opt_sampling ? GK_SAMPLE : 0) + (e->opt_grammar ? GK_GRAMMAR : 0) + (e->opt_truncation ? GK_TRUNC : 0); }
+int req_graph_key(const sonic_engine* e) { return (e->opt_request_bias ? GK_BIAS : 0) + (e->opt_sampling ? GK_SAMPLE : 0) + (e->opt_grammar ? GK_GRAMMAR : 0) + (e->opt_truncation ? GK_TRUNC : 0) + (e->opt_lm ? GK_LM : 0); }
 int req_splice_check(sonic_engine* d, sonic_engine* p) {
     const char* opt = nullptr;
     if (d->opt_request_bias != p->opt_request_bias || (d->opt_request_bias && !(p->bias.dev && d->bias.dev && p->hist && d->hist))) opt = "request_bias";
@@ -733,12 +867,15 @@ int req_splice_check(sonic_engine* d, sonic_engine* p) {
     else if (d->opt_truncation != p->opt_truncation || (d->opt_truncation && !(p->trunc.dev && d->trunc.dev))) opt = "truncation";
     else if (d->opt_grammar != p->opt_grammar || (d->opt_grammar && !(p->gram.dev && d->gram.dev))) opt = "grammar";
     else if (d->opt_draft_verify != p->opt_draft_verify) opt = "draft_verify";
+    else if (d->opt_lm != p->opt_lm || (d->opt_lm && !(lm_live(p) && lm_live(d)))) opt = "lm";
+    else if (d->opt_lm && memcmp(&d->lm_weight, &p->lm_weight, 4)) opt = "lm_weight";
     return opt ? fail(d, SONIC_ERR_INVALID, "sonic_splice_rows: source and destination differ in option %s: set it on the owner before its slots are created", opt) : SONIC_OK;
 }
 void req_splice_args(sonic_engine* d, sonic_engine* p, SpliceArgs& a, const int32_t* src_rows, const int32_t* dst_rows, int n) {
     if (d->opt_request_bias) { a.bias_s = p->bias.dev; a.bias_d = d->bias.dev; }
     if (d->opt_sampling) { a.samp_s = p->samp.dev; a.samp_d = d->samp.dev; }
     if (d->opt_truncation) { a.trunc_s = p->trunc.dev; a.trunc_d = d->trunc.dev; }
+    if (lm_live(d)) { a.lm_s = p->lm_words; a.lm_d = d->lm_words; }
     if (d->opt_grammar) {
         a.gram_s = p->gram.dev; a.gram_d = d->gram.dev;
         for (int i = 0; i < n; ++i) {                      // the row is handed over and its reference with it: the source row is free (the kernel resets its words)
@@ -780,6 +917,7 @@ int gen_inherit(sonic_engine* e, const sonic_engine* root) {
     e->opt_forced_parallel = root->opt_forced_parallel; e->opt_forced_fanout = root->opt_forced_fanout; e->opt_score_chunk_rows = root->opt_score_chunk_rows;      // (the buffers come with the slot's first parallel run)
     e->opt_forced_align = root->opt_forced_align; e->align_heads = root->align_heads;      // (likewise)
     e->opt_forced_share_prompt = root->opt_forced_share_prompt;      // (likewise)
+    if (root->opt_lm) { e->lm_weight = root->lm_weight; TRY(lm_select(e, root->opt_lm, const_cast<sonic_engine*>(root))); }
     e->opt_draft_verify = root->opt_draft_verify;      // (the buffers come with the slot's first drafted prefill)
     return SONIC_OK;
 }
@@ -789,6 +927,9 @@ void gen_release(sonic_engine* e) {
     gram_drop_staged(e);
     for (int r = 0; r < 64; ++r) gram_row_release(e, r);
     for (sonic_grammar* g : e->grammars) { (void)hipFree(g->dev); delete g; }
+    lm_unref(e);
+    for (sonic_lm* m : e->lms) { (void)hipFree(m->dev); delete m; }
+    e->lms.clear();
     e->grammars.clear();
     stage_free(e->bias); stage_free(e->samp); stage_free(e->gram); stage_free(e->trunc);
     for (int i = 0; i < 2; ++i) if (e->draft_plan_h[i]) (void)hipHostFree(e->draft_plan_h[i]);

@@ -416,6 +416,51 @@ struct SampTest { const float* temperature; const uint64_t* seed; const int32_t*
 // hook_grammar_eos) is taken by the next launch that has histories and log-probabilities, in the handle's own type: row b enters at its state (-1: a free row, -2: it has
 // left), eos: the ids a row at -2 may still emit (they also end a row, as the handle's do); the states out are read with sonic_debug_read "hook_grammar_state"
 struct GramTest { const int32_t* state_in; const int32_t* eos; int n_eos; int32_t* state_out; };
+// The language-model hooks (lm_step_kernel, lm.hip, and greedy_kernel<T, true, true, BIAS, SAMPLE, TOPK, false, ., true>).  sonic_load_tensor "lm.hook:<V>" arms an
+// automaton, validated against V as a model's is against its vocabulary: every row at the start node, no token pending, weight 0; options hook_lm_state / hook_lm_tok /
+// hook_lm_weight set the rows' words and the weight.  sonic_load_tensor "lm.hook.step" (one finished flag per row) launches lm_step_kernel alone over those rows; the
+// states, pending tokens and vectors it left are read with sonic_debug_read "hook_lm_state" / "hook_lm_tok" / "hook_lm_add".  While a vector stands, the greedy hooks
+// that have histories and log-probabilities and the vector's shape (V, at most its rows) launch their family's LM instantiation on it, in the handle's own type, and
+// leave the emitted ids in the rows' pending tokens.  One launch takes the vector: the next one needs a step of its own.  Arming again (shape {0}: disarming) drops it
+int lm_hook_arm(sonic_engine* e, int V, const int* words, int64_t n) {
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipGetLastError();
+    HIPC(e, hipSetDevice(e->device));
+    e->hook_lm_rows = 0; e->hook_lm_V = 0; e->hook_lm_N = 0;
+    if (n == 0) { if (e->hook_lm) TRY(dfree(e, &e->hook_lm, e->hook_lm_cap)); e->hook_lm = nullptr; e->hook_lm_cap = 0; return SONIC_OK; }
+    if (V < 4 || V % 4 || V > (1 << 24)) return fail(e, SONIC_ERR_INVALID, "lm.hook: vocabulary %d (a multiple of 4 in 4 .. 2^24)", V);
+    TRY(lm_check("lm.hook", words, n, V));
+    std::vector<int> w; lm_to_device_words(words, w);
+    if (e->hook_lm && e->hook_lm_cap < w.size()) { TRY(dfree(e, &e->hook_lm, e->hook_lm_cap)); e->hook_lm = nullptr; }
+    if (!e->hook_lm) { TRY(dalloc(e, &e->hook_lm, w.size(), false)); e->hook_lm_cap = w.size(); }
+    if (!e->hook_lm_words) TRY(dalloc(e, &e->hook_lm_words, (size_t)128));
+    HIPC(e, h2d(e, e->hook_lm, w.data(), w.size() * 4));
+    HIPC(e, stream_sync(e));
+    e->hook_lm_V = V; e->hook_lm_N = words[1]; e->hook_lm_weight = 0.f;
+    for (int b = 0; b < 64; ++b) { e->hook_lm_in[b] = words[4]; e->hook_lm_in[64 + b] = -1; }
+    return SONIC_OK;
+}
+int lm_hook_step(sonic_engine* e, const int* finished, int64_t B) {
+    std::lock_guard<std::mutex> lk(e->mu);
+    (void)hipGetLastError();
+    HIPC(e, hipSetDevice(e->device));
+    if (!e->hook_lm || !e->hook_lm_V) return fail(e, SONIC_ERR_INVALID, "lm.hook.step: arm a hook language model first (sonic_load_tensor \"lm.hook:<V>\")");
+    if (B < 1 || B > 64) return fail(e, SONIC_ERR_INVALID, "lm.hook.step: %lld rows (1 .. 64)", (long long)B);
+    const size_t need = (size_t)64 * e->hook_lm_V;
+    if (e->hook_lm_add && e->hook_lm_add_cap < need) { TRY(dfree(e, &e->hook_lm_add, e->hook_lm_add_cap)); e->hook_lm_add = nullptr; }
+    if (!e->hook_lm_add) { TRY(dalloc(e, &e->hook_lm_add, need)); e->hook_lm_add_cap = need; }
+    TmpBuf tb(e->st);
+    int* fin = tb.get<int>(64);
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    HIPC(e, hipMemsetAsync(e->hook_lm_add, 0, (size_t)B * e->hook_lm_V * 4, e->st));      // (a finished row's vector reads as zeros: "nothing written")
+    HIPC(e, h2d(e, fin, finished, (size_t)B * 4));
+    HIPC(e, h2d(e, e->hook_lm_words, e->hook_lm_in, sizeof e->hook_lm_in));
+    launch_lm_step(LmArgs{e->hook_lm, e->hook_lm_words, e->hook_lm_words + 64, fin, e->hook_lm_add, e->hook_lm_weight, (int)B}, e->st);
+    HIPC(e, stream_sync(e));
+    HIPC(e, hipGetLastError());
+    e->hook_lm_rows = (int)B;
+    return SONIC_OK;
+}
 static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad, int V, int B, const int32_t* force_ids, int32_t* tok_out, float* logits_out, float* lp_out,
                        const GuardTest* gt = nullptr, const SampTest* sp = nullptr) {
     if (ksplit < 1 || ksplit > 8 || B < 1 || B > 64 || mpad < B || V < 4 || V % 4) return fail(e, SONIC_ERR_INVALID, "bad greedy test shape");
@@ -436,10 +481,12 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
         gtest = GramTest{e->hook_state_in, geos.data(), (int)geos.size(), e->hook_state_out};
         gr = &gtest;
     }
+    const bool lmh = !gr && gt && lp_out && e->hook_lm_add && e->hook_lm_words && e->hook_lm_V == V && e->hook_lm_rows >= B;      // a standing hook vector of this shape: this launch takes it
+    if (lmh) e->hook_lm_rows = 0;
     TmpBuf tb(e->st);
     const size_t n = (size_t)ksplit * mpad * V;
     float* dl = up_f32(e, tb, slabs, n);
-    bf16_t* table = tb.get<bf16_t>((size_t)V * 8 * (sp || gr ? 2 : 1)); bf16_t* x = tb.get<bf16_t>((size_t)64 * 8 * (sp || gr ? 2 : 1));      // (sp, gr: rows of 8 floats in the fp32 kind)
+    bf16_t* table = tb.get<bf16_t>((size_t)V * 8 * (sp || gr || lmh ? 2 : 1)); bf16_t* x = tb.get<bf16_t>((size_t)64 * 8 * (sp || gr || lmh ? 2 : 1));      // (sp, gr, lmh: rows of 8 floats in the fp32 kind)
     int* st = tb.get<int>(64 * 8 + 4); int* ids = tb.get<int>((size_t)64 * old);
     float* dump = logits_out ? tb.get<float>((size_t)B * V) : nullptr;
     float* lp = lp_out ? tb.get<float>((size_t)64 * old * lw_) : nullptr;
@@ -530,6 +577,7 @@ static int test_greedy(sonic_engine* e, const float* slabs, int ksplit, int mpad
     if (gtrunc) { g.trunc = gtrunc; g.trunc_rec = gtrunc + TRUNC_STAGE_WORDS; }
     if (gt) { g.hist = ghist; g.hist_ld = gld; g.rep_penalty = gt->penalty; g.ngram = gt->ngram; g.suppress = gsup; g.n_suppress = gt->n_suppress; g.bias_tab = gbias; }
     if (gr) { g.gram_ref = gref; g.gram_state = (int*)(gref + 64); g.n_eos = gr->n_eos; for (int i = 0; i < gr->n_eos; ++i) g.eos[i] = gr->eos[i]; g.dt = e->f32 ? DT_F32 : e->dt; }
+    if (lmh) { g.lm_add = e->hook_lm_add; g.lm_tok = e->hook_lm_words + 64; g.dt = e->f32 ? DT_F32 : e->dt; }
     launch_greedy(g, e->st);
     HIPC(e, stream_sync(e));
     HIPC(e, hipGetLastError());

@@ -76,6 +76,9 @@ template <typename W> struct ReqStage {
 // dev: GRAM_HEAD words (N, E), node_off[N + 1], edge_tok[E], edge_next[E] (kernels.h GreedyArgs.gram_ref).  refs: the requests that refer to it - staged
 // (option request_grammar, a dispatcher's queue) or on a row; the destroy refuses while it is above zero
 struct sonic_grammar { sonic_engine* root = nullptr; int id = 0; int* dev = nullptr; int N = 0, E = 0; int64_t bytes = 0; std::atomic<int> refs{0}; };
+// A language model (sonic_load_tensor "lm:<id>"): a backoff n-gram automaton on the device, created on a weight owner and shared by all of its handles.
+// dev: LM_HEAD words, then the arrays as lm_step_kernel reads them (kernels.h LmArgs).  refs: the handles whose option lm names it; the destroy refuses while it is above zero
+struct sonic_lm { sonic_engine* root = nullptr; int id = 0; int* dev = nullptr; int V = 0, N = 0, E = 0, order = 0, start = 0; int64_t bytes = 0; std::atomic<int> refs{0}; };
 struct sonic_engine {
     sonic_dims d;
     int device = 0, mode = 0, Bm = 0, max_ctx = 0;
@@ -225,6 +228,16 @@ struct sonic_engine {
     // the kernel hooks' grammar (sonic_load_tensor "grammar.hook:<V>", options hook_grammar_state / hook_grammar_eos; engine_hooks.cpp): the packed automaton, the rows'
     // states in, the EOS ids, armed until the next hook launch that has histories and log-probabilities takes it; hook_state_out: that launch's states out (sonic_debug_read)
     std::vector<int> hook_gram; int hook_state_in[64]; std::vector<int> hook_eos; int hook_state_out[64]{};
+    // option lm / lm_weight (lm_step_kernel + greedy_kernel<T, true, true, ., ., ., false, ., true>): shallow fusion with the n-gram model `lm` of the weight
+    // owner (a reference, sonic_lm::refs) at weight lm_weight.  lm_words[128]: the rows' state words, then their pending tokens (-1: none); lm_add[max_batch][vocab] fp32:
+    // the rows' vectors, rebuilt every step.  Both come, with hist, with the option's first use, are counted by sonic_memory_info and go with the handle.  An option of
+    // the handle, not a value of a request: nothing is staged.  Owner only: `lms`, the registry (guarded by gram_mu, freed with the owner at the latest)
+    int opt_lm = 0; float lm_weight = 0.f; sonic_lm* lm = nullptr; int* lm_words = nullptr; float* lm_add = nullptr;
+    std::vector<sonic_lm*> lms;
+    // the kernel hooks' language model (sonic_load_tensor "lm.hook:<V>", options hook_lm_state / hook_lm_tok / hook_lm_weight; engine_hooks.cpp): the device blob in lm_step_kernel's
+    // layout, the rows' words in (host) and out (device, [state 64 | tok 64]) and the vector [64][V] the last "lm.hook.step" left: the greedy hooks that have histories and
+    // log-probabilities take it while it is armed
+    int* hook_lm = nullptr; size_t hook_lm_cap = 0; int hook_lm_V = 0, hook_lm_N = 0; int hook_lm_in[128]; float hook_lm_weight = 0.f; int* hook_lm_words = nullptr; float* hook_lm_add = nullptr; size_t hook_lm_add_cap = 0; int hook_lm_rows = 0;
     // the parallel forced run (options forced_parallel / forced_fanout / score_chunk_rows; run_forced_parallel, engine_score.cpp): with forced ids set,
     // a run is ONE prefill of prompt || forced ids, the lm_head over every forced position as a GEMM per chunk of score rows, and rows_kernel (rows.hip) per row.
     // score_logits: the chunk's logits [score_rows_cap][vocab] in the activation type (fp32 kind: fp32); score_plan_d / score_plan_h: the score rows' plan (ScorePlan),
@@ -415,7 +428,7 @@ int chunk_graph(sonic_engine* e, int R, int n, hipGraphExec_t* out, bool svc = f
 int run_decode_steps(sonic_engine* e, int n_steps, int* done_out);
 // the bits of a captured chunk's cache key above the row count (chunk_graph; GK_BIAS, GK_SAMPLE and GK_GRAMMAR are req_graph_key's): the greedy kernel's family and
 // its pointers are part of the capture.  GK_TOPK counts: option top_logprobs = K <= 8 takes bits 17 .. 20
-enum { GK_SVC = 1 << 12, GK_LP = 1 << 13, GK_GUARD = 1 << 14, GK_BIAS = 1 << 15, GK_SAMPLE = 1 << 16, GK_TOPK = 1 << 17, GK_GRAMMAR = 1 << 21, GK_TRUNC = 1 << 22 };
+enum { GK_SVC = 1 << 12, GK_LP = 1 << 13, GK_GUARD = 1 << 14, GK_BIAS = 1 << 15, GK_SAMPLE = 1 << 16, GK_TOPK = 1 << 17, GK_GRAMMAR = 1 << 21, GK_TRUNC = 1 << 22, GK_LM = 1 << 23 };
 
 // ------------------------------------------------------------------------------------------ scoring given tokens from a prefill (engine_score.cpp)
 int run_forced_parallel(sonic_engine* e, const int32_t* req_win, int R, const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new, bool want_logits);
@@ -479,7 +492,18 @@ int lp_check(sonic_engine* e, const char* who);     // SONIC_ERR_INVALID naming 
 // generation guards (sonic_set_generation)
 int gen_apply(sonic_engine* e, float penalty, int ngram, const int32_t* suppress, int n_suppress);   // sonic_set_generation behind the lock and the busy check
 int gen_busy(sonic_engine* e, const char* who);     // that busy check: SONIC_ERR_INVALID while the handle has work in hand
-static inline bool hist_on(const sonic_engine* e) { return e->gen_on || e->opt_request_bias || e->opt_grammar; }   // the rows' input_ids are kept: a guard, the request bias or the grammar's kernels read them
+static inline bool hist_on(const sonic_engine* e) { return e->gen_on || e->opt_request_bias || e->opt_grammar || e->opt_lm; }   // the rows' input_ids are kept: a guard, the request bias, the grammar's or the language model's kernels read them
+// shallow fusion (options lm / lm_weight)
+static inline bool lm_live(const sonic_engine* e) { return e->opt_lm && e->lm && e->lm_words && e->lm_add && !e->opt_forced_parallel; }   // this handle decodes under its language model (a scoring handle ignores it)
+int lm_create(sonic_engine* e, int id, const int* words, int64_t n);     // sonic_load_tensor "lm:<id>": the packed automaton, validated, onto e's weight owner; n = 0 destroys it
+int lm_check(const char* who, const int* words, int64_t n, int vocab);   // that validation: SONIC_ERR_INVALID on the calling thread naming the broken rule
+void lm_to_device_words(const int* words, std::vector<int>& out);       // the wire blob -> the device layout (LM_HEAD words in front)
+int lm_select(sonic_engine* e, int id, sonic_engine* owner = nullptr);   // option lm behind the lock and the busy check (owner: the weight owner of a slot under construction): the reference, hist, the rows' words and the vector buffer on first use
+int lm_set_weight(sonic_engine* e, int bits);       // option lm_weight: the bits of a finite fp32 >= 0
+void lm_prefill_rows(sonic_engine* e, int R);       // a prefill's rows start at (start, no pending token)
+void lm_step(sonic_engine* e, int R);               // lm_step_kernel right ahead of a greedy launch (nothing when the handle has no live model)
+int lm_hook_arm(sonic_engine* e, int V, const int* words, int64_t n);    // sonic_load_tensor "lm.hook:<V>": the hooks' automaton, validated against V; every row at the start node, no pending token, weight 0
+int lm_hook_step(sonic_engine* e, const int* finished, int64_t B);       // sonic_load_tensor "lm.hook.step": lm_step_kernel alone over B rows of the armed hook model (engine_hooks.cpp)
 // the three per-request stages' switches (engine_options.cpp) and what the hooks and sonic_load_tensor share with them
 int bias_enable(sonic_engine* e, int on);           // option request_bias behind the lock and the busy check: hist, the tables and their staging buffer on first use
 int samp_enable(sonic_engine* e, int on);           // option sampling behind the lock and the busy check: the rows' words and their staging buffer on first use
@@ -511,6 +535,7 @@ struct SpliceArgs {
     const int* bias_s; int* bias_d;                      // option request_bias on both: the row's table travels with it (count first, then only the used entries)
     const unsigned* samp_s; unsigned* samp_d;            // option sampling on both: the row's temperature and seed travel with it (its step index is n_new)
     const unsigned* trunc_s; unsigned* trunc_d;          // option truncation on both: the row's three words travel with it
+    const int* lm_s; int* lm_d;                          // option lm on both: the row's state word and pending token travel with it ([state 64 | tok 64])
     unsigned long long* gram_s; unsigned long long* gram_d;            // option grammar on both: the row's grammar reference and its state word (behind the 64 references) MOVE with it: the source row is free afterwards
     const float* lp_s; float* lp_d; int lp_w;            // option token_logprobs on the destination: the first token's log-probability record (lp_w floats: 1, or 1 + 2K with
                                                          // option top_logprobs) travels with its id

@@ -7,6 +7,7 @@ static int opt_token_logprobs(sonic_engine* e, const char*, int value) {      //
     const int v = value ? 1 : 0;
     if (!v && e->opt_sampling) return fail(e, SONIC_ERR_INVALID, "token_logprobs cannot be switched off while option sampling is on (its kernels are log-probability kernels)");
     if (!v && e->opt_grammar) return fail(e, SONIC_ERR_INVALID, "token_logprobs cannot be switched off while option grammar is on (its kernels are log-probability kernels)");
+    if (!v && e->opt_lm) return fail(e, SONIC_ERR_INVALID, "token_logprobs cannot be switched off while option lm is on (its kernels are log-probability kernels)");
     if (!v && e->opt_top_logprobs) return fail(e, SONIC_ERR_INVALID, "token_logprobs cannot be switched off while option top_logprobs is on (its kernels are log-probability kernels)");
     e->opt_token_logprobs = v; drop_graphs(e);
     return v ? lp_alloc(e) : SONIC_OK;      // first use: 64 x out_cap fp32
@@ -38,6 +39,21 @@ static int opt_sampling_fill_milli(sonic_engine* e, const char* key, int value) 
 static int opt_truncation(sonic_engine* e, const char* key, int value) { TRY(gen_busy(e, key)); return trunc_enable(e, value ? 1 : 0); }
 static int opt_truncation_fill(sonic_engine* e, const char* key, int value) { TRY(gen_busy(e, key)); e->opt_trunc_fill = value ? 1 : 0; return SONIC_OK; }
 static int opt_grammar(sonic_engine* e, const char* key, int value) { TRY(gen_busy(e, key)); return gram_enable(e, value ? 1 : 0); }
+// shallow fusion: lm = the id of a language model of the weight owner (sonic_load_tensor "lm:<id>"; 0: off), lm_weight = the bits of the fp32 weight, finite
+// and >= 0.  On the owner before its slots are created (they copy both), after token_logprobs (refused by name otherwise; also beside grammar and draft_verify);
+// allocates the rows' history, if nothing else has, their state words and the vector buffer.  Refused while the handle has work in hand
+static int opt_lm(sonic_engine* e, const char* key, int value) { TRY(gen_busy(e, key)); return lm_select(e, value); }
+static int opt_lm_weight(sonic_engine* e, const char* key, int value) { TRY(gen_busy(e, key)); return lm_set_weight(e, value); }
+// the kernel hooks' rows (an armed "lm.hook:<V>"): hook_lm_state = row << 24 | state, hook_lm_tok = row << 24 | (token + 1) (0: none pending), hook_lm_weight = the bits
+static int opt_hook_lm(sonic_engine* e, const char* key, int value) {
+    if (!e->hook_lm || !e->hook_lm_V) return fail(e, SONIC_ERR_INVALID, "%s: arm a hook language model first (sonic_load_tensor \"lm.hook:<V>\")", key);
+    if (!strcmp(key, "hook_lm_weight")) { float w; memcpy(&w, &value, 4); if (!std::isfinite(w) || value < 0) return fail(e, SONIC_ERR_INVALID, "hook_lm_weight: the bits of a finite fp32 >= 0"); e->hook_lm_weight = w; return SONIC_OK; }
+    const int b = (value >> 24) & 63, v = value & 0xffffff;
+    if (value < 0) return fail(e, SONIC_ERR_INVALID, "%s: row %d, value %d", key, b, v);
+    if (!strcmp(key, "hook_lm_state")) { if (v >= e->hook_lm_N) return fail(e, SONIC_ERR_INVALID, "hook_lm_state: row %d, state %d of %d nodes", b, v, e->hook_lm_N); e->hook_lm_in[b] = v; }
+    else e->hook_lm_in[64 + b] = v - 1;      // (a token outside the vocabulary is the kernel's to handle)
+    return SONIC_OK;
+}
 // ... and the values that travel through the options, since the feature adds no entry point: the grammars of the requests of the next prefill (begin = R requests, all
 // free; then request << 16 | grammar id per constrained request), the kernel hooks' row states and EOS ids
 static int opt_request_grammar_begin(sonic_engine* e, const char*, int value) { return gram_stage_begin(e, value); }
@@ -179,6 +195,11 @@ static const OptRow OPTIONS[] = {
     {"truncation", APPLY(opt_truncation)},
     {"truncation_fill", APPLY(opt_truncation_fill)},
     {"grammar", APPLY(opt_grammar)},
+    {"lm", APPLY(opt_lm)},
+    {"lm_weight", APPLY(opt_lm_weight)},
+    {"hook_lm_state", APPLY(opt_hook_lm)},
+    {"hook_lm_tok", APPLY(opt_hook_lm)},
+    {"hook_lm_weight", APPLY(opt_hook_lm)},
     {"request_grammar_begin", APPLY(opt_request_grammar_begin)},
     {"request_grammar", APPLY(opt_request_grammar)},
     {"hook_grammar_state", APPLY(opt_hook_grammar_state)},
@@ -250,6 +271,17 @@ extern "C" int sonic_debug_read(sonic_engine* e, const char* name, int index, fl
     if (!strcmp(name, "hook_grammar_state")) {      // the rows' states behind the last hook launch that took a grammar (host words: exact in fp32)
         if (n < 0 || n > 64) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
         for (int64_t i = 0; i < n; ++i) out[i] = (float)e->hook_state_out[i];
+        return SONIC_OK;
+    }
+    if (!strcmp(name, "hook_lm_state") || !strcmp(name, "hook_lm_tok")) {      // the rows' words as the last hook launch left them (exact in fp32: below 2^24)
+        if (n < 0 || n > 64 || !e->hook_lm_words) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
+        int w[128]; HIPC(e, stream_sync(e)); HIPC(e, d2h(e, w, e->hook_lm_words, sizeof w));
+        for (int64_t i = 0; i < n; ++i) out[i] = (float)w[(name[8] == 's' ? 0 : 64) + i];
+        return SONIC_OK;
+    }
+    if (!strcmp(name, "hook_lm_add")) {          // the vectors [rows][V] the last \"lm.hook.step\" left
+        if (n < 0 || !e->hook_lm_add || (size_t)n > (size_t)e->hook_lm_rows * e->hook_lm_V) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
+        HIPC(e, stream_sync(e)); if (n > 0) HIPC(e, d2h(e, out, e->hook_lm_add, (size_t)n * 4));
         return SONIC_OK;
     }
     if (!strcmp(name, "hook_truncation")) {         // the rows' records behind the last hook launch that took a truncation: [y of the last kept id | that id | n] (host words; ids and counts exact in fp32)

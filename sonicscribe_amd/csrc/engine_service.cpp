@@ -42,6 +42,7 @@ __global__ __launch_bounds__(256) void splice_state_kernel(SpliceArgs a) {
     }
     if (a.samp_d && t < 3) a.samp_d[3 * d + t] = a.samp_s[3 * s + t];
     if (a.trunc_d && t < 3) a.trunc_d[3 * d + t] = a.trunc_s[3 * s + t];
+    if (a.lm_d && t == 0) { a.lm_d[d] = a.lm_s[s]; a.lm_d[64 + d] = a.lm_s[64 + s]; }      // the language model's state and pending token
     if (a.gram_d && t == 0) { a.gram_d[d] = a.gram_s[s]; ((int*)(a.gram_d + 64))[d] = ((int*)(a.gram_s + 64))[s]; a.gram_s[s] = 0ull; ((int*)(a.gram_s + 64))[s] = -1; }
     const int cnt = min(max(a.n_new_s[s], 1), a.out_ld);      // the tokens that came out of the prefill: one - or, behind an accepted draft (option draft_verify), several
     if (a.lp_d) for (int j = t; j < cnt * a.lp_w; j += 256) a.lp_d[(long)d * a.out_ld * a.lp_w + j] = a.lp_s[(long)s * a.out_ld * a.lp_w + j];

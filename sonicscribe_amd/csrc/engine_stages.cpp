@@ -473,6 +473,8 @@ int run_to_first_token(sonic_engine* e, const int32_t* req_win, int R, const int
     TRY(e->f32 ? f32_run_encoder(e, e->W, nullptr, nullptr) : run_encoder(e, e->W, nullptr, nullptr, R));
     (void)hipEventRecord(e->ev[2], e->st);
     TRY(e->f32 ? f32_run_prefill(e, R, hp) : run_prefill(e, R, hp));
+    lm_prefill_rows(e, Rr);                      // option lm: the rows start at the model's start node, no token pending ...
+    lm_step(e, Rr);                              // ... and their vectors stand ahead of the first token's launch
     launch_greedy(e->f32 ? f32_greedy_args(e, Rr, want_logits) : greedy_args(e, Rr, want_logits), e->st);
     (void)hipEventRecord(e->ev[3], e->st);
     e->steps_run = 0; e->greedy_calls = 1; e->spliced = 0;

@@ -79,6 +79,14 @@ extern "C" int sonic_load_tensor(sonic_engine* e, const char* name, const void* 
         if (name[7] == ':') return gram_create(e, atoi(name + 8), (const int*)data, shape[0]);
         return gram_hook_arm(e, atoi(name + 13), (const int*)data, shape[0]);
     }
+    // language models, likewise: "lm:<id>" creates (shape {0}: destroys) one on the weight owner; "lm.hook:<V>" arms the kernel hooks' automaton and
+    // "lm.hook.step" (one finished flag per row) launches lm_step_kernel alone on it
+    if (!strncmp(name, "lm:", 3) || !strncmp(name, "lm.hook:", 8) || !strcmp(name, "lm.hook.step")) {
+        if (dtype != SONIC_DTYPE_I32 || ndim != 1 || shape[0] < 0) return fail(nullptr, SONIC_ERR_INVALID, "%s: a language model is one row of int32 words (SONIC_DTYPE_I32, ndim 1)", name);
+        if (name[2] == ':') return lm_create(e, atoi(name + 3), (const int*)data, shape[0]);
+        if (name[7] == ':') return lm_hook_arm(e, atoi(name + 8), (const int*)data, shape[0]);
+        return lm_hook_step(e, (const int*)data, shape[0]);
+    }
     if (!strcmp(name, "draft.dispatch")) return draft_dispatch_arm(e, data, dtype, shape, ndim);      // ... and the one of the calling thread's next dispatcher submit (no engine lock, as grammar.dispatch)
     if (!strcmp(name, "request_draft")) return draft_stage_words(e, data, dtype, shape, ndim);      // the drafts of the next prefill's requests (option draft_verify)
     if (!strcmp(name, "request_forks")) return fork_stage_counts(e, data, dtype, shape, ndim);      // the fork counts of the next prefill's requests

@@ -1,7 +1,7 @@
 // The greedy controller: fused argmax over the lm_head's partial slabs + HF's greedy loop bookkeeping + the next step's embedding row and
-// first RMSNorm, one block per row.  One kernel body, templated on the activation dtype T and six flags - LP (per-token log-probabilities), GUARD (HF's logits
+// first RMSNorm, one block per row.  One kernel body, templated on the activation dtype T and eight flags - LP (per-token log-probabilities), GUARD (HF's logits
 // processors), BIAS (per-request sequence bias), SAMPLE (temperature sampling), TOPK (the best alternatives of every step), GRAMMAR (a token automaton per
-// request) - in the twenty-three combinations launch_greedy's table lists; and the prefill's kernel
+// request), TRUNC (top_k / top_p / min_p), LM (shallow fusion with an n-gram language model) - in the thirty-one combinations launch_greedy's table lists; and the prefill's kernel
 // that writes a request's prompt ids into its history row for GUARD / BIAS.  Shares quant_emit_row (int8_util.h) with the decode-step consumers of elementwise.hip.
 #include "common.h"
 #include "kernels.h"
@@ -63,6 +63,12 @@
 // compare then admits an id only if trunc_keeps(key(y), id, kc, ic): the first maximum of y + g over the kept prefix.  The LP sum, out_lp, the alternatives and the
 // dump see the untruncated scores.  With trunc_rec (test hook) one more pass counts the kept ids and finds the last of them in (y descending, id ascending):
 // trunc_rec[3b ..] = the bits of its y, its id, n (an uncut row: 0, ~0, V).  TRUNC = false is the kernel as it was.
+// LM (option lm; LP and GUARD only, never with GRAMMAR): shallow fusion.  GreedyArgs.lm_add[b][V] is the fp32 vector lm_step_kernel (lm.hip) built from the
+// row's LM state right ahead of this launch; the loop reads it as f32x4 next to the slabs and forms r = rT(logit) + add[i] ahead of the request bias - the first
+// processor of the chain, so bias, penalty, bans and temperature see the fused score, and so do the compare, the LP sum, out_lp, the alternatives and the truncation.
+// The same add stands in the three places that form a score: the loop, y4 of the TRUNC twins, the recomputation of the emitted token's score.  The dump stays raw.
+// Thread 0 leaves the emitted id - argmax, sample or forced id - in lm_tok[b] for the next lm_step_kernel; a finished row writes nothing.  No LDS is added.
+// LM = false is the kernel as it was.
 // The history's maps, the first-maximum butterfly, the sum's rescale, wave fold and block close, and the lists with their merges and record write live in
 // rowlp.h: rows.hip (rows_kernel) shares them
 extern __shared__ unsigned g_bits[];
@@ -88,8 +94,9 @@ __device__ __forceinline__ float gumbel_of(unsigned word) {
     return -logf(-logf(u));
 }
 #define LPB (SAMPLE ? rmax : best)      // what the LP sum is taken against: the running maximum of s
-template <typename T, bool LP, bool GUARD = false, bool BIAS = false, bool SAMPLE = false, bool TOPK = false, bool GRAMMAR = false, bool TRUNC = false>
+template <typename T, bool LP, bool GUARD = false, bool BIAS = false, bool SAMPLE = false, bool TOPK = false, bool GRAMMAR = false, bool TRUNC = false, bool LM = false>
 __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
+    static_assert(!LM || (LP && GUARD && !GRAMMAR), "the language model lives in the log-probability guard instantiations without a grammar (one family per line of the table)");
     static_assert(SAMPLE || !TRUNC, "truncation lives in the sampling instantiations (it cuts what they draw from)");
     static_assert(!GRAMMAR || (LP && GUARD), "the grammar lives in the log-probability guard instantiations (it reuses their banned map)");
     static_assert(LP || !TOPK, "the alternatives live in the log-probability instantiations (they share their sum)");
@@ -113,6 +120,8 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
     float lp_m = -INFINITY, lp_s = 0.f;      // LP: the thread's sum is lp_s * exp(lp_m); a thread that saw nothing holds (-inf, 0)
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const float* lg = a.logits + (long)b * a.V;
+    [[maybe_unused]] const float* lm = nullptr;      // LM: the row's additive vector
+    if constexpr (LM) lm = a.lm_add + (long)b * a.V;
     const long ks_stride = (long)a.mpad * a.V;
     float* dump = a.logits_dump ? a.logits_dump + (long)a.step_counter[b] * a.dump_stride_step + (long)b * a.V : nullptr;
     float best = -INFINITY; int bi = 0x7fffffff;
@@ -190,9 +199,12 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
                 [[maybe_unused]] unsigned sb = 0u, bb = 0u, qb = 0u;
                 if constexpr (GUARD) { sb = g_seen[i >> 5] >> (i & 31); bb = g_ban[i >> 5] >> (i & 31); }
                 if constexpr (BIAS) qb = (g_bia[i >> 5] >> (i & 31)) & 15u;
+                [[maybe_unused]] f32x4 la = {0.f, 0.f, 0.f, 0.f};
+                if constexpr (LM) la = *(const f32x4*)(lm + i);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     float r = rT<T>(t[j]);
+                    if constexpr (LM) r += la[j];
                     if constexpr (BIAS) if ((qb >> j) & 1u) r += bias_of(q_id, q_sum, q_n, i + j);
                     if constexpr (GUARD) r = guard_score(r, sb >> j, bb >> j, a.rep_penalty);
                     y[j] = __fdiv_rn(r, temp);
@@ -245,11 +257,13 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
     constexpr int U = 4;
     for (int i0 = tid * 4; i0 < a.V; i0 += 1024 * 4 * U) {
         f32x4 v[U], w[U];
+        [[maybe_unused]] f32x4 la[LM ? U : 1];      // LM: the groups of the row's vector, requested with the slabs
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int i = i0 + u * 4096, ic = i < a.V ? i : 0;
             v[u] = *(const f32x4*)(lg + ic);
             w[u] = *(const f32x4*)(lg + (a.ksplit > 1 ? ks_stride : 0) + ic);
+            if constexpr (LM) la[u] = *(const f32x4*)(lm + ic);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -273,6 +287,7 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
             for (int j = 0; j < 4; ++j) {
                 float r = rT<T>(t[j]);              // logits are T in the reference, compared as fp32
                 if (dump) dump[i + j] = r;
+                if constexpr (LM) r += la[u][j];    // shallow fusion: the first processor, behind the dump (raw logits)
                 if constexpr (BIAS) if ((qb >> j) & 1u) r += bias_of(q_id, q_sum, q_n, i + j);      // HF's order: the bias first, the penalty sees the biased score
                 if constexpr (GUARD) r = guard_score(r, sb >> j, bb >> j, a.rep_penalty);
                 if constexpr (TRUNC) {
@@ -342,6 +357,7 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
                     if (a.ksplit > 1) f += lg[ks_stride + tok];
                     for (int ks = 2; ks < a.ksplit; ++ks) f += lg[ks * ks_stride + tok];
                     lt = rT<T>(f);
+                    if constexpr (LM) lt += lm[tok];
                     if constexpr (BIAS) if ((g_bia[tok >> 5] >> (tok & 31)) & 1u) lt += bias_of(q_id, q_sum, q_n, tok);
                     if constexpr (GUARD) lt = guard_score(lt, g_seen[tok >> 5] >> (tok & 31), g_ban[tok >> 5] >> (tok & 31), a.rep_penalty);
                 }
@@ -349,6 +365,7 @@ __global__ __launch_bounds__(1024) void greedy_kernel(GreedyArgs a) {
                 if constexpr (TOPK) { tk_col = a.n_new[b]; tk_m = LPB; tk_sum = lp_sum; }
             }
             if constexpr (GUARD) { const int pos = a.kv_len[b]; if (pos >= 0 && pos < a.hist_ld) a.hist[(long)b * a.hist_ld + pos] = tok; }   // the token's position
+            if constexpr (LM) a.lm_tok[b] = tok;         // the next lm_step_kernel consumes it
             if constexpr (GRAMMAR) if (gst != -1) {      // the transition: the emitted id among the node's ascending edge tokens, by bisection
                 int ns = -2, lo = g_lo, hi = g_hi;
                 while (lo < hi) { const int mid = (lo + hi) >> 1; if (g_tok[mid] < tok) lo = mid + 1; else hi = mid; }
@@ -434,16 +451,16 @@ size_t greedy_trunc_lds() { return 17848; }
 static_assert(TRUNC_LDS_BYTES + 1464 == 17848, "greedy_trunc_lds: the histogram is part of the figure");
 size_t greedy_guard_lds(int V, bool bias) { return (size_t)(bias ? 3 : 2) * ((V + 31) / 32) * 4 + (bias ? (size_t)3 * BIAS_MAX_ENTRIES * 4 : 0); }
 // One family of the table below: its grid, block and LDS request, for fp32 rows (SONIC_MODE_F32: fp32 logits, table and rows) and for the 16-bit kinds
-template <bool LP, bool GUARD, bool BIAS, bool SAMPLE, bool TOPK = false, bool GRAMMAR = false, bool TRUNC = false>
+template <bool LP, bool GUARD, bool BIAS, bool SAMPLE, bool TOPK = false, bool GRAMMAR = false, bool TRUNC = false, bool LM = false>
 static void greedy_launch(const GreedyArgs& a, hipStream_t s) {
-    if constexpr (SAMPLE && !TRUNC) if (a.trunc) return greedy_launch<LP, GUARD, BIAS, SAMPLE, TOPK, GRAMMAR, true>(a, s);      // trunc (counts only together with samp) = option truncation: the family's TRUNC twin
+    if constexpr (SAMPLE && !TRUNC) if (a.trunc) return greedy_launch<LP, GUARD, BIAS, SAMPLE, TOPK, GRAMMAR, true, LM>(a, s);      // trunc (counts only together with samp) = option truncation: the family's TRUNC twin
     const size_t lds = GUARD ? greedy_guard_lds(a.V, BIAS) : 0;      // GUARD: two vocabulary bitmaps of dynamic LDS; BIAS: a third and the matched list; GRAMMAR: nothing more
-    if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, LP, GUARD, BIAS, SAMPLE, TOPK, GRAMMAR, TRUNC>), dim3(a.B), dim3(1024), lds, s, a); return; }
-    DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, LP, GUARD, BIAS, SAMPLE, TOPK, GRAMMAR, TRUNC>), dim3(a.B), dim3(1024), lds, s, a));
+    if (a.dt == DT_F32) { hipLaunchKernelGGL((greedy_kernel<float, LP, GUARD, BIAS, SAMPLE, TOPK, GRAMMAR, TRUNC, LM>), dim3(a.B), dim3(1024), lds, s, a); return; }
+    DT_SWITCH(a.dt, T, hipLaunchKernelGGL((greedy_kernel<T, LP, GUARD, BIAS, SAMPLE, TOPK, GRAMMAR, TRUNC, LM>), dim3(a.B), dim3(1024), lds, s, a));
 }
-// The twenty-three families, chosen from the arguments: out_lp = option token_logprobs, hist = generation guards, bias_tab (counts only together with hist) = request
+// The thirty-one families, chosen from the arguments: out_lp = option token_logprobs, hist = generation guards, bias_tab (counts only together with hist) = request
 // bias, samp (counts only together with out_lp) = option sampling, topk in 1 .. 8 (counts only together with out_lp) = option top_logprobs, gram_state with gram_ref
-// (counts only together with out_lp and hist) = option grammar.  One line per family: a combination that is not listed is not instantiated.
+// (counts only together with out_lp and hist) = option grammar, lm_add with lm_tok (likewise; never beside a grammar) = option lm.  One line per family: a combination that is not listed is not instantiated.
 void launch_greedy(const GreedyArgs& a, hipStream_t s) {
     const bool lp = a.out_lp != nullptr, guard = a.hist != nullptr, bias = guard && a.bias_tab, sample = lp && a.samp, topk = lp && a.topk >= 1 && a.topk <= 8;
     const bool gram = lp && guard && a.gram_state && a.gram_ref;
@@ -457,6 +474,17 @@ void launch_greedy(const GreedyArgs& a, hipStream_t s) {
         if (sample)                  return greedy_launch<true,  true,  false, true,  false, true >(a, s);
         if (bias)                    return greedy_launch<true,  true,  true,  false, false, true >(a, s);
         return greedy_launch<true,  true,  false, false, false, true >(a, s);
+    }
+    if (lp && guard && a.lm_add && a.lm_tok) {
+        //                                        LP     GUARD  BIAS   SAMPLE TOPK   GRAMMAR TRUNC LM
+        if (topk && sample && bias)  return greedy_launch<true,  true,  true,  true,  true,  false, false, true >(a, s);
+        if (topk && sample)          return greedy_launch<true,  true,  false, true,  true,  false, false, true >(a, s);
+        if (topk && bias)            return greedy_launch<true,  true,  true,  false, true,  false, false, true >(a, s);
+        if (topk)                    return greedy_launch<true,  true,  false, false, true,  false, false, true >(a, s);
+        if (sample && bias)          return greedy_launch<true,  true,  true,  true,  false, false, false, true >(a, s);
+        if (sample)                  return greedy_launch<true,  true,  false, true,  false, false, false, true >(a, s);
+        if (bias)                    return greedy_launch<true,  true,  true,  false, false, false, false, true >(a, s);
+        return greedy_launch<true,  true,  false, false, false, false, false, true >(a, s);
     }
     //                                        LP     GUARD  BIAS   SAMPLE TOPK
     if (topk && sample && bias)  return greedy_launch<true,  true,  true,  true,  true >(a, s);

@@ -128,6 +128,10 @@ struct GreedyArgs {
     // (nodes N, edges E), then node_off[N + 1], edge_tok[E] (ascending inside a node), edge_next[E].  Needs out_lp and hist.  (Ahead of the sampling fields, which
     // stay the struct's last.)
     int* gram_state; const unsigned long long* gram_ref;
+    // shallow fusion (greedy_kernel<T, true, true, ., ., ., false, ., true>, option lm); lm_add = NULL: off.  lm_add[B][V]: the vector lm_step_kernel
+    // (lm.hip) left for the row, added to the rounded logit ahead of the request bias; lm_tok[64]: thread 0 leaves the emitted id there for the next lm_step_kernel.
+    // Needs out_lp and hist; never together with gram_state.  (Ahead of the sampling fields, as the grammar's)
+    const float* lm_add; int* lm_tok;
     // truncation (greedy_kernel<T, true, ., ., true, ., ., true>, option truncation).  trunc = NULL: off; else three words per row, 64 rows: top_k
     // (0: off), the bits of top_p (0: off), the bits of lnm = float32(log(min_p)) (0: off; min_p = 1 is -0.0).  trunc_rec: optional, three words per row (test hook;
     // production passes NULL): the bits of the y of the last kept id in (y descending, id ascending), that id, the kept count n.  Needs samp.  (Ahead of the sampling fields, as the grammar's)
@@ -154,7 +158,19 @@ struct GreedyArgs {
 #define BIAS_ROW_WORDS (BIAS_MAX_ENTRIES * BIAS_ENTRY_WORDS)
 #define BIAS_TAB_WORDS (64 + 64 * BIAS_ROW_WORDS)
 void launch_greedy(const GreedyArgs& a, hipStream_t s);
-size_t greedy_trunc_lds();                              // LDS the TRUNC instantiations add to it (the select's histogram)
+// Shallow fusion (lm.hip; option lm): one block of 1024 threads per row.  blob: the automaton on the device - LM_HEAD words (V, N, E, order, start and
+// three words of padding, so that uni sits on a 16-byte boundary), then uni[V] | node_off[N + 1] | bo_next[N] | bo_w[N] | edge_tok[E] | edge_next[E] | edge_w[E] as
+// sonic_load_tensor "lm:<id>" validated them.  A row that is not `finished` first consumes its pending token (tok[row] >= 0: the transition of the contract, by a
+// wave-wide 64-ary search per chain level; then tok[row] = -1), then writes add[row][V] = weight * (A + log-probability) for its state: a dense pass over uni, then one
+// pass per chain level from the shortest context to the longest, barriers in between.  A finished row writes nothing
+#define LM_HEAD 8
+#define LM_WIRE_HEAD 5
+#define LM_MAX_ORDER 8
+#define LM_MAX_NODES 4194304
+#define LM_MAX_EDGES 16777216
+struct LmArgs { const int* blob; int* state; int* tok; const int* finished; float* add; float weight; int B; };
+void launch_lm_step(const LmArgs& a, hipStream_t s);
+size_t greedy_trunc_lds();                             // LDS the TRUNC instantiations add to it (the select's histogram)
 size_t greedy_guard_lds(int V, bool bias = false);     // dynamic LDS of the GUARD instantiations: two bitmaps over the vocabulary; with the request bias a third one and the matched list
 void launch_hist_prompt(const int* src, const int* tok_seq, const int* tok_pos, int n_tok, int audio_id, int* hist, int hist_ld, hipStream_t s);
 

@@ -223,6 +223,8 @@ SONIC_API int sonic_pipeline_create(sonic_engine* const* decoders, int n_dec, so
         return engine_fail(decoders[0], SONIC_ERR_INVALID, "sonic_pipeline_create: option top_logprobs is on on a handle: the bulk pipeline carries one log-probability per token (set top_logprobs to 0, or use the dispatcher)");
     if (hs.any(engine_forced_parallel_on))
         return engine_fail(decoders[0], SONIC_ERR_INVALID, "sonic_pipeline_create: option forced_parallel is on on a handle: a scoring handle takes no part in the bulk pipeline");
+    if (hs.any(engine_lm_on))
+        return engine_fail(decoders[0], SONIC_ERR_INVALID, "sonic_pipeline_create: option lm is on on a handle: the bulk pipeline carries no language-model state");
     if (hs.any(engine_draft_verify_on))
         return engine_fail(decoders[0], SONIC_ERR_INVALID, "sonic_pipeline_create: option draft_verify is on on a handle: the bulk pipeline takes no drafts (stage them on a handle's whole batches or its prefill slot)");
     sonic_pipeline* p = new sonic_pipeline();

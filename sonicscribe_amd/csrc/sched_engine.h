@@ -20,7 +20,8 @@ int engine_sampling_on(sonic_engine* e);
 int engine_truncation_on(sonic_engine* e);                     // option truncation
 int engine_take_dispatch_truncation(float* row);               // "truncation.dispatch": 1 and the armed (top_k, top_p, min_p) in row[0 .. 3), or 0 (none)
 int engine_grammar_on(sonic_engine* e);
-int engine_draft_verify_on(sonic_engine* e);                   // (the bulk pipeline takes no drafts: refused there)
+int engine_lm_on(sonic_engine* e);                             // option lm (the bulk pipeline carries no language-model state: refused there)
+int engine_draft_verify_on(sonic_engine* e);                  // (the bulk pipeline takes no drafts: refused there)
 int engine_tok_cap(sonic_engine* e);                           // the tokens one prefill of the handle holds
 // one request's values, checked at its submit (the message goes to the calling thread's sonic_last_error(NULL))
 int engine_bias_validate(sonic_engine* e, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n);   // a table against the caps and this handle's vocabulary

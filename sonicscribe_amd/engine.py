@@ -322,6 +322,45 @@ class DeviceGrammar:
                     self.engine._grammars.remove(self)
 
 
+class DeviceLM:
+    """An ngram.NGramLM on the device (sonic_load_tensor "lm:<id>"): lives on a weight owner under `id` and serves every handle of it whose option lm
+    names it; `lm` is the host automaton it was made from.  close() raises SonicError while a handle's option refers to it; the owner's close() takes what is left."""
+
+    def __init__(self, engine: "Engine", lm):
+        root = engine.root
+        self.engine, self.lm = root, lm
+        words = np.ascontiguousarray(lm.pack(), dtype=np.int32)
+        with _GRAMMAR_IDS:
+            if not hasattr(root, "_lms"):
+                root._lms = []
+            used = {m.id for m in root._lms}
+            self.id = next(i for i in range(1, 65536) if i not in used)
+            self._load(words)
+            self.h = self.id
+            root._lms.append(self)
+
+    def _load(self, words: np.ndarray):
+        shape = (C.c_int64 * 1)(len(words))
+        w = words if len(words) else np.zeros(1, np.int32)
+        rc = self.engine.lib.sonic_load_tensor(self.engine.h, f"lm:{self.id}".encode(), _p(w), DTYPE_I32, shape, 1)
+        if rc != 0:
+            raise SonicError((self.engine.lib.sonic_last_error(None) or b"").decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            with _GRAMMAR_IDS:
+                if getattr(self.engine, "h", None):
+                    self._load(np.zeros(0, np.int32))        # shape {0}: destroy
+                self.h = None
+                if self in getattr(self.engine, "_lms", []):
+                    self.engine._lms.remove(self)
+
+
+def weight_bits(weight: float) -> int:
+    """an fp32 weight as the int32 option lm_weight carries"""
+    return int(np.array([weight], np.float32).view(np.int32)[0])
+
+
 class TokenScores(NamedTuple):
     """A request's log-probabilities on a handle with option top_logprobs = K > 0: `lp` [n] float32 (the emitted tokens'), `top_logprobs` [n, K] float32 and
     `top_ids` [n, K] int32 - at every step the K best ids by (score descending, id ascending) among the ids with a finite score, with their log-probabilities;
@@ -435,6 +474,9 @@ class Engine(HooksMixin):
             for g in list(getattr(self, "_grammars", ())):   # the library frees the grammars with their owner: the handles die here
                 g.h = None
             self._grammars = []
+            for m in list(getattr(self, "_lms", ())):        # ... and the language models likewise
+                m.h = None
+            self._lms = []
             self.lib.sonic_destroy(self.h)
             self.h = None
             if self.owner is not None and self in self.owner._slots:
@@ -448,6 +490,21 @@ class Engine(HooksMixin):
     def grammar_create(self, grammar) -> "DeviceGrammar":
         """a grammar.Grammar onto this engine's weight owner (sonic_load_tensor "grammar:<id>"): one handle for every slot and every request"""
         return DeviceGrammar(self, grammar)
+
+    def lm_create(self, lm) -> "DeviceLM":
+        """an ngram.NGramLM onto this engine's weight owner (sonic_load_tensor "lm:<id>"): one handle for every slot"""
+        return DeviceLM(self, lm)
+
+    def set_lm(self, lm: Optional["DeviceLM"], weight: float = 0.0):
+        """Shallow fusion on this handle (options lm_weight / lm): every decode of it adds weight x the model's log-probabilities to its scores.  None: off.
+        On the owner before its slots are created (they copy both).  Needs option token_logprobs (SonicError naming it otherwise)."""
+        if lm is None:
+            self.set_option("lm", 0)
+            return
+        if lm.h is None:
+            raise SonicError("lm: the language model has been closed")
+        self.set_option("lm_weight", weight_bits(weight))
+        self.set_option("lm", lm.id)
 
     def set_request_grammar(self, grammars):
         """The grammars of the requests of the NEXT prefill / run on this handle (options request_grammar_begin / request_grammar), one DeviceGrammar or None (a free

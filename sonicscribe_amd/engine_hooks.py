@@ -228,6 +228,59 @@ class HooksMixin:
         self._check(self.lib.sonic_debug_read(self.h, b"hook_grammar_state", 0, _p(so), B))
         return tok, lg, lp, noise, so[:B].astype(np.int32)
 
+    def arm_lm_hook(self, lm, V: Optional[int] = None):
+        """sonic_load_tensor "lm.hook:<V>": an ngram.NGramLM (or its packed words) for the language-model hooks of this handle, validated against V (SonicError in the
+        library's words); every row at the start node, no token pending, weight 0.  None disarms"""
+        from .engine import DTYPE_I32, SonicError
+        w = np.zeros(0, np.int32) if lm is None else np.ascontiguousarray(lm.pack() if hasattr(lm, "pack") else lm, dtype=np.int32)
+        V = int(V if V is not None else (w[0] if len(w) else 0))
+        self._lm_hook_V = V
+        if self.lib.sonic_load_tensor(self.h, f"lm.hook:{V}".encode(), _p(w if len(w) else np.zeros(1, np.int32)), DTYPE_I32, (C.c_int64 * 1)(len(w)), 1) != 0:
+            raise SonicError((self.lib.sonic_last_error(None) or b"").decode())
+
+    def test_lm_step(self, B: int, state_in, tok_in, weight: float, finished=None, want_add: bool = True):
+        """lm_step_kernel alone over B rows of the armed hook model: row b enters at state_in[b] with the pending token tok_in[b] (-1: none) ->
+        (state out [B], pending token out [B], the vectors [B][V] float32 - zeros for a finished row - or None)"""
+        from .engine import DTYPE_I32, SonicError, weight_bits
+        self._check(self.lib.sonic_set_option(self.h, b"hook_lm_weight", weight_bits(weight)))
+        for b in range(B):
+            self._check(self.lib.sonic_set_option(self.h, b"hook_lm_state", (b << 24) | int(state_in[b])))
+            self._check(self.lib.sonic_set_option(self.h, b"hook_lm_tok", (b << 24) | (int(tok_in[b]) + 1)))
+        fin = np.zeros(B, np.int32) if finished is None else np.ascontiguousarray(finished, np.int32)
+        assert fin.shape == (B,)
+        if self.lib.sonic_load_tensor(self.h, b"lm.hook.step", _p(fin), DTYPE_I32, (C.c_int64 * 1)(B), 1) != 0:
+            raise SonicError((self.lib.sonic_last_error(self.h) or self.lib.sonic_last_error(None) or b"").decode())
+        st, tk = self.read_lm_hook(B)
+        add = None
+        if want_add:
+            V = int(self._lm_hook_V)
+            add = self.debug_read("hook_lm_add", (B, V))
+        return st, tk, add
+
+    def read_lm_hook(self, B: int):
+        """sonic_debug_read "hook_lm_state" / "hook_lm_tok": the rows' words as the last language-model hook launch left them"""
+        return self.debug_read("hook_lm_state", (B,)).astype(np.int32), self.debug_read("hook_lm_tok", (B,)).astype(np.int32)
+
+    def test_greedy_lm(self, slabs, B: int, lm, state_in, weight: float, tok_in=None, hist=None, hist_len=None, tables=None, samp=None, repetition_penalty: float = 1.0,
+                       no_repeat_ngram_size: int = 0, suppress_tokens=(), force_ids=None, want_noise: bool = True):
+        """The LM instantiations of the greedy kernel in this handle's type: `lm` (an ngram.NGramLM) is armed, lm_step_kernel builds the rows' vectors at state_in
+        and `weight`, and the guard / bias / sample hook launch that follows takes them.  tables: the bias families; samp = (temperature, seed, step): the sampling
+        families -> (token [B], RAW logits [B][V], log-probability over the fused scores [B] - a TokenScores with option top_logprobs -, Gumbel noise [B][V] or None,
+        the vectors [B][V], the rows' pending tokens behind the launch [B])"""
+        V = np.asarray(slabs).shape[2]
+        self.arm_lm_hook(lm, V)
+        _, _, add = self.test_lm_step(B, state_in, [-1] * B if tok_in is None else tok_in, weight)
+        h = np.zeros((B, 1), np.int32) if hist is None else np.ascontiguousarray(hist, np.int32).reshape(B, -1)
+        hl = np.zeros(B, np.int32) if hist_len is None else np.ascontiguousarray(hist_len, np.int32)
+        guard = (h, hl, repetition_penalty, no_repeat_ngram_size, suppress_tokens)
+        if samp is not None:
+            tok, lg, lp, noise = self._greedy("greedy_sample", slabs, B, True, True, force_ids, guard, tables, samp, want_noise)
+        elif tables is not None:
+            tok, lg, lp, noise = self._greedy("greedy_bias", slabs, B, True, True, force_ids, guard, list(tables))
+        else:
+            tok, lg, lp, noise = self._greedy("greedy_guard", slabs, B, True, True, force_ids, guard)
+        return tok, lg, lp, noise, add, self.read_lm_hook(B)[1]
+
     def test_linear_int8(self, X, W, bias=None, resid=None, group_rows=None, epi=EPI_BIAS):
         """One Linear8bitLt call; X [M][K], W [N][K] fp16-valued. group_rows: rows per reference call (default: all rows one call)."""
         X = np.ascontiguousarray(X, np.float32); W = np.ascontiguousarray(W, np.float32)
