@@ -137,8 +137,10 @@ SONIC_API const char* sonic_last_error(sonic_engine* e); /* e may be NULL: error
 /* name (NUL-terminated, truncated to name_cap), total / currently free device memory, hipRuntimeGetVersion(); any output may be NULL */
 SONIC_API int sonic_device_info(int device_id, char* name, int name_cap, int64_t* total_bytes, int64_t* free_bytes, int32_t* hip_runtime_version);
 /* How many hardware queues the HIP runtime of THIS process gives its streams on the device (measured once per device: eight probe streams with a
- * 300 us spin kernel each; streams that share a queue run in order), what GPU_MAX_HW_QUEUES says now (0 = unset) and how many an engine with slots
- * wants (8).  The runtime reads the variable at its first call only: in the reference's process torch initialises it (backend/asr.py:53
+ * 300 us spin kernel each; streams that share a queue run in order), what GPU_MAX_HW_QUEUES says now (0 = unset) and how many an engine with slots,
+ * device rings and VAD wants (8).  Every handle owns ONE stream - finished rows of a continuous loop leave through a pinned mirror, not a stream of their
+ * own - so a bulk pipeline of D decoding and P prefill handles needs D + P queues: the default 3 + 1 fits the runtime's own default of four; each device
+ * ring, the resampler and a VAD add a stream of theirs.  The runtime reads the variable at its first call only: in the reference's process torch initialises it (backend/asr.py:53
  * `torch.cuda.is_available()`), so the host sets GPU_MAX_HW_QUEUES=8 in its environment - the library never writes the
  * environment, and the first sonic_create warns on stderr when the measured count is below the wanted one (SONIC_QUIET=1 silences it). */
 SONIC_API int sonic_runtime_info(int device_id, int32_t* hw_queues, int32_t* hw_queues_env, int32_t* hw_queues_wanted);

@@ -9,7 +9,7 @@ __version__ = "0.1.0"
 import os as _os
 
 # More hardware queues for the HIP runtime than its default of 4 (read once, at the runtime's first call; a value the user set stays): an
-# engine's handles own two streams each, and streams that share a hardware queue run in order (csrc/engine.cpp probe_hw_queues / sonic_runtime_info have
-# the measurement).  Set here as well as in the library's constructor so that a process which imports this package before it touches
+# engine's handles, device rings, resampler and VAD own one stream each, and streams that share a hardware queue run in order (csrc/engine.cpp
+# probe_hw_queues / sonic_runtime_info have the measurement; the bulk pipeline's 3 + 1 handles alone fit the default four).  Set here as well as in the library's constructor so that a process which imports this package before it touches
 # torch.cuda gets it even when torch initialises the runtime first.
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")

@@ -141,8 +141,10 @@ static int build_constants(sonic_engine* e) {
 
 // ------------------------------------------------------------------------------------------ create / destroy
 // The HIP runtime spreads a process's streams over GPU_MAX_HW_QUEUES hardware queues (default 4), round-robin in creation order; streams that
-// share a queue execute in order.  An engine with two slots owns six streams (one main + one fetch stream per handle), plus one per device
-// ring: with four queues the prefill slot's stream landed on the queue of a decoding handle and the bulk pipeline lost 7 % (141 vs 151
+// share a queue execute in order.  A handle owns ONE stream (finished rows leave through a pinned mirror, engine_service.cpp: the fetch stream every decoding
+// handle had is gone), so a bulk pipeline of D decoding + P prefill handles owns D + P streams and the default 3x64+1 fits four queues: 4 and 8 queues measure
+// the same there (profiles/hwq4_pipeline_ab.txt).  More handles than queues, or device rings, resampler and VAD streams beside them, still alias: when every
+// handle also had a fetch stream, the prefill slot's stream landed on the queue of a decoding handle and the bulk pipeline lost 7 % (141 vs 151
 // segments/s, profiles/round4_hw_queues.txt).  The runtime reads the variable once, at its first call, so it is the HOST PROCESS that has to set GPU_MAX_HW_QUEUES=8
 // before anything touches HIP (`import sonicscribe_amd` and bench.py do it with setdefault).  The library itself no longer writes the
 // environment (round 4's constructor did: setenv from a library constructor races with other threads' getenv and silently did nothing when torch
@@ -189,7 +191,8 @@ static int probe_hw_queues(int device) {
     if (q > 0 && q < SONIC_HW_QUEUES_WANTED && !getenv("SONIC_QUIET")) {
         const char* env = getenv("GPU_MAX_HW_QUEUES");
         fprintf(stderr, "[sonic_hip] device %d: the HIP runtime of this process has %d hardware queue(s) for its streams (GPU_MAX_HW_QUEUES=%s%s); an engine with "
-                        "slots wants %d - streams that share a queue run in order (the bulk pipeline measured 141 instead of 152 segments/s on 4 queues).  Set "
+                        "slots, device rings and VAD wants %d - streams that share a queue run in order, and every handle, ring and VAD owns one (a bulk pipeline of D decoding + "
+                        "P prefill handles alone needs D + P: the default 3x64+1 fits 4).  Set "
                         "GPU_MAX_HW_QUEUES=8 in the environment BEFORE the process first touches HIP / torch.cuda.\n", device, q, env ? env : "unset",
                 env && atoi(env) >= SONIC_HW_QUEUES_WANTED ? ": set after the runtime had started" : "", SONIC_HW_QUEUES_WANTED);
     }
@@ -300,7 +303,7 @@ static int alloc_state(sonic_engine* e) {
     A(dalloc(e, &e->satt, (size_t)64 * e->QD)); A(dalloc(e, &e->sact, (size_t)64 * d.dec_ff));
     A(dalloc(e, &e->kv_len, 64)); A(dalloc(e, &e->tok_pos, 64)); A(dalloc(e, &e->n_new, 64)); A(dalloc(e, &e->finished, 64));
     A(dalloc(e, &e->max_new_d, 64)); A(dalloc(e, &e->n_active, 4)); A(dalloc(e, &e->out_ids, (size_t)64 * e->out_cap));
-    A(dalloc(e, &e->step_ctr, 64)); A(dalloc(e, &e->seq_iota, 64));
+    A(dalloc(e, &e->step_ctr, 64)); A(dalloc(e, &e->seq_iota, 64)); A(dalloc(e, &e->mirrored, 64));
     if (e->i8) {
         // widest Linear8bitLt input: encoder MLP (enc_ff), projector (enc_d * merge), decoder MLP (dec_ff)
         int kmax = d.enc_ff; if (C * d.merge > kmax) kmax = C * d.merge; if (d.dec_ff > kmax) kmax = d.dec_ff; if (2 * d.dec_d > kmax) kmax = 2 * d.dec_d;
@@ -330,8 +333,6 @@ static int alloc_state(sonic_engine* e) {
     }
     if (hipHostMalloc((void**)&e->n_active_h, (CHK_RING + 1) * 4, hipHostMallocDefault) != hipSuccess) { e->err = "hipHostMalloc failed"; return SONIC_ERR_HIP; }
     if (hipHostMalloc((void**)&e->svc_h, (size_t)CHK_RING * SVC_WORDS * 4, hipHostMallocDefault) != hipSuccess) { e->err = "hipHostMalloc failed"; return SONIC_ERR_HIP; }
-    // (the row-fetch stream st_io is created by the first sonic_service_begin: hardware queues are dealt to streams in creation order, and the main
-    //  streams of an engine and its slots should take the first ones - see probe_hw_queues)
     if (hipEventCreateWithFlags(&e->xfer_ev, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&e->splice_ev, hipEventDisableTiming) != hipSuccess) { e->err = "hipEventCreate failed"; return SONIC_ERR_HIP; }
     e->plan_cap = 3 * tc + 10 * 64;      // (three words per token; seven per request, a word and the 64 of run_upload_win_req behind them)
     for (int i = 0; i < 2; ++i) {
@@ -402,7 +403,7 @@ extern "C" int sonic_slot_create(sonic_engine* parent, sonic_engine** out) {
     e->lc = root->lc; e->enc_cs = root->enc_cs; e->dec_cs = root->dec_cs;
     e->opts = root->opts; e->opt_no_graph = root->opt_no_graph; e->opt_no_fused_rope = root->opt_no_fused_rope; e->opt_no_gelu_lut = root->opt_no_gelu_lut;
     e->opt_i8_defer_thr = root->opt_i8_defer_thr; e->opt_i8_no_xq = root->opt_i8_no_xq; e->opt_i8_no_lnq = root->opt_i8_no_lnq; e->opt_i8_no_qkv_fuse = root->opt_i8_no_qkv_fuse;
-    e->opt_decode_chunk = root->opt_decode_chunk; e->opt_no_pre_norm = root->opt_no_pre_norm; e->opt_decode_gemv = root->opt_decode_gemv;
+    e->opt_decode_chunk = root->opt_decode_chunk; e->opt_no_pre_norm = root->opt_no_pre_norm; e->opt_decode_gemv = root->opt_decode_gemv; e->opt_fetch_stream = root->opt_fetch_stream;
     if ((s = gen_inherit(e, root)) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }      // the owner's generation options, with their buffers
     e->weight_bytes = 0; e->finalized = true; e->owner = root;
     root->slots.push_back(e);
@@ -460,9 +461,11 @@ extern "C" void sonic_destroy(sonic_engine* e) {
     if (e->n_active_h) (void)hipHostFree(e->n_active_h);
     for (int i = 0; i < 2; ++i) { if (e->plan_buf[i]) (void)hipHostFree(e->plan_buf[i]); if (e->plan_ev[i]) (void)hipEventDestroy(e->plan_ev[i]); }
     if (e->svc_h) (void)hipHostFree(e->svc_h);
+    if (e->svc_out_h) (void)hipHostFree(e->svc_out_h);
+    if (e->svc_lp_h) (void)hipHostFree(e->svc_lp_h);
     if (e->score_plan_h) (void)hipHostFree(e->score_plan_h);
     if (e->align_plan_h) (void)hipHostFree(e->align_plan_h);
-    if (e->st_io) { (void)hipStreamSynchronize(e->st_io); (void)hipStreamDestroy(e->st_io); }
+    if (e->st_io) { (void)hipStreamSynchronize(e->st_io); (void)hipStreamDestroy(e->st_io); }      // (only a handle that fetched with option fetch_stream has one)
     if (e->xfer_ev) (void)hipEventDestroy(e->xfer_ev);
     if (e->splice_ev) (void)hipEventDestroy(e->splice_ev);
     for (auto& v : e->ev) if (v) (void)hipEventDestroy(v);

@@ -173,7 +173,14 @@ struct sonic_engine {
     int* svc_h = nullptr;                                          // pinned ring [CHK_RING][SVC_WORDS]: finished[64] | n_new[64] | n_active
     int svc_fin[64]{}, svc_nn[64]{}, svc_active = 0; int64_t svc_seq = 0;   // the newest check read: state after chunk number svc_seq
     hipEvent_t sync_ev = nullptr;                                  // blocking-sync event behind stream_sync()
-    hipStream_t st_io = nullptr;                                   // row fetches (a finished row's ids are stable: no ordering against the queued chunks needed)
+    // the finished rows' mirror: the kernel behind every chunk (service_status_kernel) copies a row's ids (and log-probability records) into pinned host
+    // memory in the chunk that finds it finished, so a fetch is a memcpy behind the check's event - no copy command, no stream, no wait
+    int* svc_out_h = nullptr;                                      // pinned [64][out_cap], allocated by the first sonic_service_begin
+    float* svc_lp_h = nullptr; int svc_lp_w = 0;                   // pinned [64][out_cap * lp_width] (option token_logprobs), for records svc_lp_w floats wide
+    int* mirrored = nullptr;                                       // device [64]: the row's tokens are in the mirror (cleared by a splice; free rows: 1)
+    int64_t spliced_seq[64]{};                                     // chunks queued before the row's last splice: its mirror is valid once svc_seq is larger and svc_fin[row]
+    int opt_fetch_stream = 0;                                      // 1 (A/B): no mirror; rows are fetched by copy commands on a stream of their own, as before the mirror
+    hipStream_t st_io = nullptr;                                   // ... that stream, created by the first sonic_service_begin with fetch_stream = 1 (the default path owns ONE stream per handle)
     hipEvent_t xfer_ev = nullptr, splice_ev = nullptr, wait_ev = nullptr; bool wait_pending = false;   // cross-handle ordering of a splice
 
     // sonic_run_staged_async / sonic_wait: a worker thread of the engine's own runs the batch, the caller's thread returns at once
@@ -540,6 +547,7 @@ struct SpliceArgs {
     const float* lp_s; float* lp_d; int lp_w;            // option token_logprobs on the destination: the first token's log-probability record (lp_w floats: 1, or 1 + 2K with
                                                          // option top_logprobs) travels with its id
     int *kv_len_d, *tok_pos_d, *n_new_d, *fin_d, *max_new_d, *out_d, *n_active_d;
+    int* mirrored_d;                                     // the destination's mirror flags: a spliced row's tokens are not in the pinned mirror yet
     const bf16_t *sx_s, *shn_s; bf16_t *sx_d, *shn_d; int D;
     const int8_t* hq_s; int8_t* hq_d; const float *sca_s, *ov_s; float *sca_d, *ov_d; const int *oc_s, *ol_s; int *oc_d, *ol_d;   // int8 mode: layer 0's quantised input row
 };

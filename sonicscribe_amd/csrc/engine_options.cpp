@@ -122,6 +122,14 @@ static int opt_align_head(sonic_engine* e, const char* key, int value) {
     e->align_heads.insert(std::upper_bound(e->align_heads.begin(), e->align_heads.end(), value), value);      // sorted: layer by layer, heads ascending
     return SONIC_OK;
 }
+// fetch_stream (A/B, default 0): 1 = finished rows leave as before the pinned mirror (engine_service.cpp) - copy commands on a stream of the handle's own, created by
+// sonic_service_begin, and a wait - and the bulk pipeline queues a chunk ahead of every fetch again.  Same ids either way.  On the owner before its slots are
+// created (they copy it); refused while the handle decodes continuously (its loop mirrors rows or does not, from sonic_service_begin on)
+static int opt_fetch_stream(sonic_engine* e, const char* key, int value) {
+    if (e->svc_on) return fail(e, SONIC_ERR_INVALID, "%s: this handle is decoding continuously (sonic_service_end first)", key);
+    e->opt_fetch_stream = value ? 1 : 0; return SONIC_OK;
+}
+extern "C" int engine_fetch_stream_on(sonic_engine* e) { return e && e->opt_fetch_stream ? 1 : 0; }      // (pipeline.cpp: the order of chunk and fetch at a hand-over)
 // the two knobs that do device work
 static int opt_ktrace(sonic_engine* e, const char*, int value) {              // diagnostics: record in-kernel timestamps of decoder layer `value` (-1: off); sonic_debug_ktrace reads them
     HIPC(e, hipSetDevice(e->device));
@@ -212,6 +220,7 @@ static const OptRow OPTIONS[] = {
     {"forced_align", APPLY(opt_forced_align)},
     {"align_head", APPLY(opt_align_head)},
     {"draft_verify", APPLY(opt_draft_verify)},
+    {"fetch_stream", APPLY(opt_fetch_stream)},
     {"score_chunk_rows", ENG(opt_score_chunk_rows), false, [](int v) { return v < 16 ? 16 : (v > 4096 ? 4096 : v); }},   // score rows per lm_head GEMM + row-kernel launch (the buffer follows at the next parallel run)
     {"ktrace", APPLY(opt_ktrace)},
     {"inject_dev_err", APPLY(opt_inject_dev_err)},

@@ -51,6 +51,7 @@ __global__ __launch_bounds__(256) void splice_state_kernel(SpliceArgs a) {
         const int fin = a.fin_s[s];
         a.kv_len_d[d] = a.kv_len_s[s]; a.tok_pos_d[d] = a.tok_pos_s[s]; a.n_new_d[d] = a.n_new_s[s]; a.max_new_d[d] = a.max_new_s[s];
         a.fin_d[d] = fin;
+        if (a.mirrored_d) a.mirrored_d[d] = 0;      // the new occupant's tokens are not in the pinned mirror (service_status_kernel copies them when it finds the row finished)
         if (!fin) atomicAdd(a.n_active_d, 1);
     }
 }
@@ -59,15 +60,52 @@ __global__ __launch_bounds__(256) void splice_state_kernel(SpliceArgs a) {
 __global__ void release_row_kernel(int* kv_len, int* tok_pos, int* finished, int row, int* gram_state) { kv_len[row] = 1; tok_pos[row] = 0; finished[row] = 1; if (gram_state) gram_state[row] = -1; }
 // the pipelined check of the continuous loop: finished | n_new | n_active -> one record in pinned host memory (a kernel's stores instead of
 // three copy commands between every two chunks)
-__global__ void service_status_kernel(const int* finished, const int* n_new, const int* n_active, int* out) {
-    const int t = threadIdx.x;
+// ... and, in the same launch, the finished rows' mirror: block r < m.rows looks at row r and, in the chunk that finds it finished, copies its n_new ids (and
+// log-probability records) from out_ids / out_lp into the pinned arrays the host fetches from (plain vector stores, as the record's); a chunk in which no row
+// finishes copies nothing.  The last block writes the record.  The host reads both only behind the chunk's event.  (m.rows == 0: option fetch_stream, no mirror)
+struct MirrorArgs { const int* out_ids; const float* out_lp; int* mirrored; int* ids_h; float* lp_h; int out_cap, lp_w, rows; };
+__global__ __launch_bounds__(256) void service_status_kernel(const int* finished, const int* n_new, const int* n_active, int* out, MirrorArgs m) {
+    const int t = threadIdx.x, row = blockIdx.x;
+    if (row < m.rows) {
+        if (!finished[row] || m.mirrored[row]) return;      // (the same answer for the whole block)
+        const int n = min(max(n_new[row], 0), m.out_cap);
+        const long o = (long)row * m.out_cap;
+        for (int j = t; j < n; j += 256) m.ids_h[o + j] = m.out_ids[o + j];
+        if (m.lp_h) for (int j = t; j < n * m.lp_w; j += 256) m.lp_h[o * m.lp_w + j] = m.out_lp[o * m.lp_w + j];
+        __syncthreads();                                    // every thread has read the flag
+        if (t == 0) m.mirrored[row] = 1;
+        return;
+    }
     if (t < 64) { out[t] = finished[t]; out[64 + t] = n_new[t]; }
     if (t == 0) out[128] = *n_active;
 }
-__global__ void service_reset_kernel(int* kv_len, int* tok_pos, int* n_new, int* finished, int* max_new, int* n_active) {
+__global__ void service_reset_kernel(int* kv_len, int* tok_pos, int* n_new, int* finished, int* max_new, int* n_active, int* mirrored) {
     const int b = threadIdx.x;
-    if (b < 64) { kv_len[b] = 1; tok_pos[b] = 0; n_new[b] = 0; finished[b] = 1; max_new[b] = 1; }
+    if (b < 64) { kv_len[b] = 1; tok_pos[b] = 0; n_new[b] = 0; finished[b] = 1; max_new[b] = 1; mirrored[b] = 1; }      // (a free row has nothing to mirror)
     if (b == 0) *n_active = 0;
+}
+// the pinned mirror of one continuously decoding handle, at the widths its options ask for now (sonic_service_begin)
+static int mirror_alloc(sonic_engine* e) {
+    if (!e->svc_out_h) HIPC(e, hipHostMalloc((void**)&e->svc_out_h, (size_t)64 * e->out_cap * 4, hipHostMallocDefault));
+    const int w = lp_on(e) ? lp_width(e) : 0;
+    if (w != e->svc_lp_w) {
+        if (e->svc_lp_h) { (void)hipHostFree(e->svc_lp_h); e->svc_lp_h = nullptr; }
+        e->svc_lp_w = 0;
+        if (w) { HIPC(e, hipHostMalloc((void**)&e->svc_lp_h, (size_t)64 * e->out_cap * w * 4, hipHostMallocDefault)); e->svc_lp_w = w; }
+    }
+    return SONIC_OK;
+}
+// the mirror holds what a fetch of this row asks for: a check newer than the row's splice has shown it finished (and the records are as wide as the handle's)
+static inline bool mirror_valid(const sonic_engine* e, int row, bool want_lp) {
+    if (e->opt_fetch_stream || !e->svc_out_h || e->svc_checked < 1) return false;
+    if (want_lp && !(e->svc_lp_h && e->svc_lp_w == lp_width(e))) return false;
+    return e->svc_seq > e->spliced_seq[row] && e->svc_fin[row];
+}
+// option fetch_stream (A/B): the handle's second stream, as every decoding handle had before the mirror
+static int fetch_stream(sonic_engine* e, hipStream_t* st) {
+    if (!e->st_io) HIPC(e, hipStreamCreateWithFlags(&e->st_io, hipStreamNonBlocking));
+    *st = e->st_io;
+    return SONIC_OK;
 }
 
 extern "C" int sonic_service_begin(sonic_engine* e) {
@@ -77,9 +115,10 @@ extern "C" int sonic_service_begin(sonic_engine* e) {
     if (!e->finalized) return fail(e, SONIC_ERR_INVALID, "weights not finalized");
     if (e->svc_on) return SONIC_OK;
     if (e->opt_forced_parallel) return fail(e, SONIC_ERR_INVALID, "sonic_service_begin: option forced_parallel is on: a scoring handle does not decode continuously");
-    if (!e->st_io) HIPC(e, hipStreamCreateWithFlags(&e->st_io, hipStreamNonBlocking));
+    TRY(mirror_alloc(e));
+    if (e->opt_fetch_stream) { hipStream_t s; TRY(fetch_stream(e, &s)); }      // (A/B: where every decoding handle's second stream used to be created)
     HIPC(e, stream_sync(e));
-    hipLaunchKernelGGL(service_reset_kernel, dim3(1), dim3(64), 0, e->st, e->kv_len, e->tok_pos, e->n_new, e->finished, e->max_new_d, e->n_active);
+    hipLaunchKernelGGL(service_reset_kernel, dim3(1), dim3(64), 0, e->st, e->kv_len, e->tok_pos, e->n_new, e->finished, e->max_new_d, e->n_active, e->mirrored);
     if (e->force_d) return fail(e, SONIC_ERR_INVALID, "teacher forcing is set: clear it before continuous decoding");
     req_rows_free(e);                                       // the pool starts with free rows
     hipGraphExec_t gx = nullptr;                            // the chunk graphs exist before the first splice: nothing captures on this stream later
@@ -92,7 +131,7 @@ extern "C" int sonic_service_begin(sonic_engine* e) {
     }
     HIPC(e, stream_sync(e));
     e->svc_launched = e->svc_checked = 0; e->svc_seq = 0; e->svc_active = 0;
-    for (int b = 0; b < 64; ++b) { e->svc_fin[b] = 1; e->svc_nn[b] = 0; }
+    for (int b = 0; b < 64; ++b) { e->svc_fin[b] = 1; e->svc_nn[b] = 0; e->spliced_seq[b] = 0; }
     e->R = 0; e->greedy_calls = 0;
     e->svc_on = true;
     return SONIC_OK;
@@ -140,6 +179,7 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
     a.kv_len_s = p->kv_len; a.tok_pos_s = p->tok_pos; a.n_new_s = p->n_new; a.fin_s = p->finished; a.max_new_s = p->max_new_d; a.out_s = p->out_ids; a.out_ld = d->out_cap;
     a.kv_len_d = d->kv_len; a.tok_pos_d = d->tok_pos; a.n_new_d = d->n_new; a.fin_d = d->finished; a.max_new_d = d->max_new_d; a.out_d = d->out_ids; a.n_active_d = d->n_active;
     a.sx_s = p->sx; a.shn_s = p->shn; a.sx_d = d->sx; a.shn_d = d->shn; a.D = dm.dec_d;
+    a.mirrored_d = d->mirrored;
     if (lp_on(d)) { a.lp_s = p->out_lp; a.lp_d = d->out_lp; a.lp_w = lp_width(d); }
     if (hist_on(d)) { a.hist_s = p->hist; a.hist_d = d->hist; }
     req_splice_args(d, p, a, src_rows, dst_rows, n);      // the per-request stages' rows; a row's grammar reference is handed over with it
@@ -154,6 +194,7 @@ extern "C" int sonic_splice_rows(sonic_engine* d, sonic_engine* p, int n, const 
     p->wait_ev = d->splice_ev; p->wait_pending = true;
     HIPC(d, hipGetLastError());
     for (int i = 0; i < n; ++i) p->spliced |= 1ull << src_rows[i];      // (gen_busy: a prefill slot whose rows have all left is free again)
+    for (int i = 0; i < n; ++i) d->spliced_seq[dst_rows[i]] = d->svc_launched;      // (the mirror of these rows describes their new occupants behind a later check)
     if (seq_out) *seq_out = d->svc_launched;
     return SONIC_OK;
 }
@@ -196,7 +237,12 @@ extern "C" int sonic_service_step(sonic_engine* e, int n_chunks, int rows, int32
             HIPC(e, hipGraphLaunch(gx, e->st));
             const int slot = (int)(e->svc_launched % CHK_RING);
             int* w = e->svc_h + (size_t)slot * SVC_WORDS;
-            hipLaunchKernelGGL(service_status_kernel, dim3(1), dim3(64), 0, e->st, e->finished, e->n_new, e->n_active, w);
+            MirrorArgs m{};                                 // all Bm rows, whatever the chunk stepped: a row spliced as finished (budget 1) is mirrored by the next chunk too
+            if (!e->opt_fetch_stream && e->svc_out_h && e->mirrored) {
+                m.out_ids = e->out_ids; m.mirrored = e->mirrored; m.ids_h = e->svc_out_h; m.out_cap = e->out_cap; m.rows = e->Bm;
+                if (e->svc_lp_h && e->out_lp) { m.out_lp = e->out_lp; m.lp_h = e->svc_lp_h; m.lp_w = e->svc_lp_w; }
+            }
+            hipLaunchKernelGGL(service_status_kernel, dim3(m.rows + 1), dim3(256), 0, e->st, e->finished, e->n_new, e->n_active, w, m);
             HIPC(e, hipEventRecord(e->chk_ev[slot], e->st));
             ++e->svc_launched;
         }
@@ -221,9 +267,14 @@ extern "C" int sonic_fetch_row(sonic_engine* e, int row, int n, int32_t* out_ids
     if (row < 0 || row >= e->Bm || n < 0 || n > e->out_cap) return fail(e, SONIC_ERR_INVALID, "sonic_fetch_row: row %d / %d tokens out of range", row, n);
     // (a row the newest check saw running is running: releasing it would leave the count of running rows one too high for good)
     if (e->svc_checked > 0 && !e->svc_fin[row]) return fail(e, SONIC_ERR_INVALID, "sonic_fetch_row: row %d has not finished (sonic_service_step's finished[])", row);
-    if (n > 0) {
-        HIPC(e, hipMemcpyAsync(out_ids, e->out_ids + (size_t)row * e->out_cap, (size_t)n * 4, hipMemcpyDeviceToHost, e->st_io));
-        HIPC(e, hipStreamSynchronize(e->st_io));
+    if (n > 0 && mirror_valid(e, row, false)) memcpy(out_ids, e->svc_out_h + (size_t)row * e->out_cap, (size_t)n * 4);
+    else if (n > 0) {
+        // no check has shown this occupant finished (a direct user of the C ABI that fetches without stepping): the copy goes behind everything queued on the
+        // handle's stream - slow, rare, correct.  Option fetch_stream: the stream of their own the fetches had before the mirror (a finished row's ids are stable)
+        hipStream_t st = e->st;
+        if (e->opt_fetch_stream) TRY(fetch_stream(e, &st));
+        HIPC(e, hipMemcpyAsync(out_ids, e->out_ids + (size_t)row * e->out_cap, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+        HIPC(e, st == e->st ? stream_sync(e) : hipStreamSynchronize(st));
     }
     hipLaunchKernelGGL(release_row_kernel, dim3(1), dim3(1), 0, e->st, e->kv_len, e->tok_pos, e->finished, row, req_release_state(e));
     req_row_release(e, row);                                // (a finished row changes no state and reads no automaton that matters: its reference can go)
@@ -249,12 +300,24 @@ static int fetch_rows_locked(sonic_engine* e, int n, const int32_t* rows, const 
         for (int j = 0; j < i; ++j) if (rows[j] == row) return fail(e, SONIC_ERR_INVALID, "sonic_fetch_rows: row %d named twice", row);
         a.dst[i] = row;
     }
-    for (int i = 0; i < n; ++i)
-        if (counts[i] > 0) {
-            HIPC(e, hipMemcpyAsync(out_ids + (size_t)i * out_ld, e->out_ids + (size_t)rows[i] * e->out_cap, (size_t)counts[i] * 4, hipMemcpyDeviceToHost, e->st_io));
-            if (out_lp) HIPC(e, hipMemcpyAsync(out_lp + (size_t)i * out_ld * w, e->out_lp + (size_t)rows[i] * e->out_cap * w, (size_t)counts[i] * w * 4, hipMemcpyDeviceToHost, e->st_io));
+    // a row a check has shown finished since its splice is in the pinned mirror (service_status_kernel): a memcpy.  The others (fetched without stepping, by a direct
+    // user of the C ABI) are copied behind everything queued on the handle's stream - or, with option fetch_stream, every row on the old stream of their own
+    hipStream_t st = e->st;
+    if (e->opt_fetch_stream) TRY(fetch_stream(e, &st));
+    bool queued = false;
+    for (int i = 0; i < n; ++i) {
+        if (counts[i] <= 0) continue;
+        const size_t ro = (size_t)rows[i] * e->out_cap;
+        if (mirror_valid(e, rows[i], out_lp != nullptr)) {
+            memcpy(out_ids + (size_t)i * out_ld, e->svc_out_h + ro, (size_t)counts[i] * 4);
+            if (out_lp) memcpy(out_lp + (size_t)i * out_ld * w, e->svc_lp_h + ro * w, (size_t)counts[i] * w * 4);
+            continue;
         }
-    HIPC(e, hipStreamSynchronize(e->st_io));
+        HIPC(e, hipMemcpyAsync(out_ids + (size_t)i * out_ld, e->out_ids + ro, (size_t)counts[i] * 4, hipMemcpyDeviceToHost, st));
+        if (out_lp) HIPC(e, hipMemcpyAsync(out_lp + (size_t)i * out_ld * w, e->out_lp + ro * w, (size_t)counts[i] * w * 4, hipMemcpyDeviceToHost, st));
+        queued = true;
+    }
+    if (queued) HIPC(e, st == e->st ? stream_sync(e) : hipStreamSynchronize(st));
     hipLaunchKernelGGL(release_rows_kernel, dim3(1), dim3(64), 0, e->st, e->kv_len, e->tok_pos, e->finished, a, n, req_release_state(e));
     for (int i = 0; i < n; ++i) req_row_release(e, rows[i]);
     HIPC(e, hipGetLastError());

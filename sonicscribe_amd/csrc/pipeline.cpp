@@ -9,7 +9,8 @@
 //     has queued the splice of its rows (the handle's buffers are the splice's source until then);
 //   * one thread per decoding handle: splices handed-over batches into free row blocks of its continuously decoding handle, queues decode
 //     chunks (sonic_service_step: blocking, sleeps on an event), fetches the rows of a block the moment the pipelined check shows every row of
-//     it finished, completes the batch's ticket.  An EMPTY loop leaves the next batch to a loop that is running part-filled (two batches in one
+//     it finished (a memcpy from the handle's pinned mirror: the next batch's splice goes in front of the very next chunk), completes the batch's
+//     ticket.  An EMPTY loop leaves the next batch to a loop that is running part-filled (two batches in one
 //     64-row loop stream the weights once).
 // No thread polls: every wait is a condition variable or a blocking HIP event inside the engine.  Only the C ABI of include/sonic_hip.h is used (and the option queries of sched_engine.h).
 #include <stdint.h>
@@ -115,6 +116,7 @@ void prefill_thread(sonic_pipeline* p, sonic_engine* h) {
 void decode_thread(sonic_pipeline* p, int k) {
     sonic_engine* d = p->dec[k];
     const int nb = p->blocks_per_dec, B = p->block;
+    const bool chunk_before_fetch = engine_fetch_stream_on(d) != 0;
     struct Occ { std::shared_ptr<Batch> b; int64_t valid_after = 0; };
     std::vector<Occ> occ(nb);
     int n_occ = 0;
@@ -165,7 +167,7 @@ void decode_thread(sonic_pipeline* p, int k) {
                 p->decoder_idle_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ti0).count();
             }
         }
-        // ---- one chunk for the occupied rows; a second one before fetching when other blocks keep running
+        // ---- one chunk for the occupied rows
         int top = 0;
         for (int i = 0; i < nb; ++i) if (occ[i].b) top = (i + 1) * B;
         int64_t seq = 0; int32_t nact = 0;
@@ -179,8 +181,10 @@ void decode_thread(sonic_pipeline* p, int k) {
             for (int r = 0; r < occ[i].b->R; ++r) all_fin = all_fin && fin[i * B + r];
             if (all_fin) done.push_back(i);
         }
-        if (!done.empty() && (int)done.size() < n_occ) {
-            // fetching a block's rows takes this thread about as long as a chunk takes the device: the other block's next chunk goes out first
+        // A finished block's rows are in the handle's pinned mirror: the fetch is a memcpy, and the next hand-over's splice goes in front of the very next chunk
+        // (the block idles through the one chunk that was queued ahead of the check, no more).  Option fetch_stream (A/B): the fetch is copy commands and a wait
+        if (chunk_before_fetch && !done.empty() && (int)done.size() < n_occ) {
+            // ... fetching a block's rows then takes this thread about as long as a chunk takes the device: the other block's next chunk goes out first
             int32_t f2[64], n2[64]; int64_t s2 = 0;
             rc = sonic_service_step(d, 1, top, f2, n2, &s2, &nact);
             if (rc != SONIC_OK) { fail_all(rc); return; }

@@ -22,7 +22,8 @@ int engine_take_dispatch_truncation(float* row);               // "truncation.di
 int engine_grammar_on(sonic_engine* e);
 int engine_lm_on(sonic_engine* e);                             // option lm (the bulk pipeline carries no language-model state: refused there)
 int engine_draft_verify_on(sonic_engine* e);                  // (the bulk pipeline takes no drafts: refused there)
-int engine_tok_cap(sonic_engine* e);                           // the tokens one prefill of the handle holds
+int engine_fetch_stream_on(sonic_engine* e);                   // option fetch_stream (A/B): its fetches take about a chunk's time, the bulk pipeline queues a chunk ahead of them
+int engine_tok_cap(sonic_engine* e);                          // the tokens one prefill of the handle holds
 // one request's values, checked at its submit (the message goes to the calling thread's sonic_last_error(NULL))
 int engine_bias_validate(sonic_engine* e, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n);   // a table against the caps and this handle's vocabulary
 int engine_sampling_validate(float temperature);               // 0 or 1e-3 .. 100

@@ -26,12 +26,14 @@ import numpy as np
 
 
 class ContinuousPipeline:
-    def __init__(self, decoders: Sequence[Any], prefills: Sequence[Any], block: int = 32, pair: bool = True):
+    def __init__(self, decoders: Sequence[Any], prefills: Sequence[Any], block: int = 32, pair: bool = True, fetch_stream: bool = False):
         """decoders / prefills: engine handles sharing one weight copy (an Engine and its slot()s), all with the same max_batch; a decoder holds
-        max_batch // block batches at a time.  Decoders are put into continuous mode here and taken out by close()."""
+        max_batch // block batches at a time.  Decoders are put into continuous mode here and taken out by close().  fetch_stream: the handles
+        have engine option fetch_stream on (A/B): a fetch then takes about a chunk's time, and a decoder queues one more chunk ahead of it."""
         if not decoders or not prefills:
             raise ValueError("at least one decoder and one prefill slot")
         self.decoders, self.prefills, self.block, self.pair = list(decoders), list(prefills), int(block), bool(pair)
+        self.fetch_stream = bool(fetch_stream)
         self.blocks = [list(range(i, i + self.block)) for i in range(0, (self.decoders[0].max_batch // self.block) * self.block, self.block)]
         if not self.blocks:
             raise ValueError("max_batch is smaller than a block")
@@ -104,8 +106,10 @@ class ContinuousPipeline:
                     fin, nn, seq, _ = d.service_step(1, (max(occupied) + 1) * self.block)
                     steps = 1
                     done_blocks = [b for b, va in occupied.items() if seq > va and all(fin[r] for r in self.blocks[b])]
-                    if done_blocks and len(done_blocks) < len(occupied):
-                        # fetching a block's rows takes this thread about as long as a chunk takes the device: the other block's next chunk goes
+                    # a finished block's rows are in the handle's pinned mirror: the fetch is a memcpy, and the next hand-over's splice goes in
+                    # front of the very next chunk.  With option fetch_stream (A/B) the fetch is copy commands and a wait:
+                    if self.fetch_stream and done_blocks and len(done_blocks) < len(occupied):
+                        # fetching a block's rows then takes this thread about as long as a chunk takes the device: the other block's next chunk goes
                         # out first, or the stream runs dry under the fetches (and the engine answers by queueing ever deeper)
                         d.service_step(1, (max(occupied) + 1) * self.block)
                         steps += 1
