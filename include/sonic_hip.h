@@ -53,10 +53,10 @@
  *   sonic_set_request_bias     `hotwords` of a request as a bias on the scores: HF's sequence_bias / bad_words_ids
  *                              (SequenceBiasLogitsProcessor, NoBadWordsLogitsProcessor; generation/logits_process.py),
  *                              one table per request                                                      backend/asr.py:303-333
- *   sonic_dispatch_submit_bias / sonic_test_greedy_bias   (the same through the dispatcher; test hook of the kernel behind it)
+ *   sonic_test_greedy_bias     (test hook of the kernel behind it; through the dispatcher: sonic_dispatch_request's seq_ids .. n_seq)
  *   sonic_set_request_sampling temperature sampling with a seed per request (HF's TemperatureLogitsWarper + multinomial as one Gumbel-max draw): what
  *                              openai-whisper's decode_with_fallback retries a poor segment with
- *   sonic_dispatch_submit_sampled / sonic_test_greedy_sample   (the same through the dispatcher; test hook of the kernel behind it)
+ *   sonic_test_greedy_sample   (test hook of the kernel behind it; through the dispatcher: sonic_dispatch_request's sampled, temperature, seed)
  */
 #ifndef SONIC_HIP_H
 #define SONIC_HIP_H
@@ -68,7 +68,7 @@ extern "C" {
 /* The library is built with -fvisibility=hidden: these declarations are its whole dynamic symbol table (tests/test_host_logic.py checks
  * `nm -D` against this header).  SONIC_ABI_VERSION moves whenever a signature or a struct layout below changes. */
 #define SONIC_API __attribute__((visibility("default")))
-#define SONIC_ABI_VERSION 12
+#define SONIC_ABI_VERSION 13
 SONIC_API int sonic_abi_version(void);
 
 typedef struct sonic_engine sonic_engine;
@@ -189,8 +189,8 @@ SONIC_API const char* sonic_pipeline_last_error(sonic_pipeline* p);
 SONIC_API int sonic_pipeline_destroy(sonic_pipeline* p);
 
 /* ---- weights (names: GlmAsrForConditionalGeneration.state_dict() keys, see sonicscribe_amd/spec.py) ----
- * On a finalized engine the call also carries the named int32 words that need no entry point of their own: "grammar:<id>" / "grammar.dispatch:<id>" /
- * "grammar.hook:<V>" (DESIGN.md 6.10), "request_draft" / "draft.dispatch" (6.11, beside sonic_set_forced_ids), "request_forks" and "lm:<id>" / "lm.hook:<V>" /
+ * On a finalized engine the call also carries the named int32 words that need no entry point of their own: "grammar:<id>" /
+ * "grammar.hook:<V>" (DESIGN.md 6.10), "request_draft" (6.11, beside sonic_set_forced_ids), "request_forks" and "lm:<id>" / "lm.hook:<V>" /
  * "lm.hook.step":
  *
  * Shallow fusion (options lm / lm_weight): a backoff n-gram language model over the model's own tokens, added to every step's scores inside the decode
@@ -244,8 +244,7 @@ SONIC_API int sonic_pipeline_destroy(sonic_pipeline* p);
  *   sonic_set_request_bias names) draws under top_k = values[3r] (an integer, 0 = off), top_p = values[3r + 1] (in (0, 1], 1 = off), min_p = values[3r + 2] (in [0, 1],
  *   0 = off); NaN and values out of range are refused by name, nothing is clamped; rows with temperature 0 ignore them.  Consumed or dropped with the sampling values;
  *   stated per row under forks; a prefill without them has every filter off; sonic_splice_rows copies a row's words and refuses handles whose options differ.
- *   "truncation.dispatch" (SONIC_DTYPE_F32, {3}: top_k, top_p, min_p) arms the calling thread's NEXT sonic_dispatch_submit_sampled, as "grammar.dispatch:<id>" arms a
- *   grammar: refused by name unless every handle of the dispatcher has the option, and when the submit that follows is another one.
+ *   dispatcher: sonic_dispatch_request's cut, top_k, top_p, min_p.
  *   "truncation.hook" (same layout, B rows) arms the next sonic_test_greedy_sample launch; sonic_debug_read "hook_truncation" (3B floats) returns its records: the y of
  *   the last kept id in (y descending, id ascending), that id, the kept count n; (0, -1, V) for a row that was not cut. */
 SONIC_API int sonic_load_tensor(sonic_engine* e, const char* name, const void* data, int dtype, const int64_t* shape, int ndim);
@@ -334,7 +333,8 @@ SONIC_API int sonic_set_generation(sonic_engine* e, float repetition_penalty, in
  *   sonic_set_request_bias: the tables of the R requests of the NEXT sonic_prefill / sonic_prefill_enqueue / sonic_run_staged[_async] / sonic_transcribe_* on this
  *       handle, which consumes them on success and on failure alike - a sonic_transcribe_* that fails while staging drops them too (a later batch starts without tables).  Request r owns entries req_off[r] .. req_off[r + 1]; entry i is
  *       seq_ids[seq_off[i] .. seq_off[i + 1]) with bias[i].  SONIC_ERR_INVALID, nothing truncated: the option is off (the message names it), more than 256
- *       entries in a request, a sequence outside 1 .. 8 ids, an id outside the vocabulary, a NaN or +inf bias; at the prefill, an R that is not the batch's. */
+ *       entries in a request, a sequence outside 1 .. 8 ids, an id outside the vocabulary, a NaN or +inf bias; at the prefill, an R that is not the batch's.
+ *   dispatcher: sonic_dispatch_request's seq_ids, seq_off, bias, n_seq. */
 SONIC_API int sonic_set_request_bias(sonic_engine* e, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, const int32_t* req_off, int R);
 /* Temperature sampling.  A request with temperature t > 0 and a 64-bit seed emits, as its n-th token (n = 0 for the prefill's), the first maximum over
  * the vocabulary of y_i = fdiv_rn(s_i, t) + g_i in fp32: s the fully processed score (request bias, repetition penalty, bans: HF's order, then its
@@ -348,7 +348,8 @@ SONIC_API int sonic_set_request_bias(sonic_engine* e, const int32_t* seq_ids, co
  *       copies a row's words and refuses handles whose options differ.
  *   sonic_set_request_sampling: the values of the R requests of the NEXT prefill on this handle (the entry points sonic_set_request_bias names), which consumes them
  *       on success and on failure alike; a batch without values is greedy.  SONIC_ERR_INVALID, nothing clamped: the option is off (the message names it), a
- *       temperature that is neither 0 nor in [1e-3, 100] (NaN included); at the prefill, an R that is not the batch's. */
+ *       temperature that is neither 0 nor in [1e-3, 100] (NaN included); at the prefill, an R that is not the batch's.
+ *   dispatcher: sonic_dispatch_request's sampled, temperature, seed. */
 SONIC_API int sonic_set_request_sampling(sonic_engine* e, const float* temperature, const uint64_t* seed, int R);
 /* Grammar-constrained decoding: a request's transcript restricted to the paths of a deterministic token automaton - HF's prefix_allowed_tokens_fn
  * (PrefixConstrainedLogitsProcessor), Vosk's `grammar`, the strict mode of a phrase list - with the mask and the state transition inside the greedy kernel.  The
@@ -378,10 +379,7 @@ SONIC_API int sonic_set_request_sampling(sonic_engine* e, const float* temperatu
  *       this handle (the entry points sonic_set_request_bias names); that prefill consumes them on success and on failure alike and starts every constrained row at
  *       node 0.  SONIC_ERR_INVALID: option grammar is off (the message names it), an id that is no live grammar of the handle's weight owner; at the prefill, an R
  *       that is not the batch's.  A scoring handle (option forced_parallel) refuses staged grammars, and consumes them, as it does bias tables.
- *   dispatcher: sonic_load_tensor with the name "grammar.dispatch:<id>" (shape {0}; id 0 disarms) on any handle of the dispatcher's weight owner arms the calling
- *       thread's NEXT sonic_dispatch_submit, _bias or _sampled with that grammar; the submit takes it whatever becomes of it; SONIC_ERR_INVALID unless every handle
- *       of the dispatcher has option grammar on.  The call takes no engine lock (a decoding handle holds its own for a chunk at a time).  The request holds a
- *       reference until it completes. */
+ *   dispatcher: sonic_dispatch_request's grammar_id; the request holds a reference from its submit until it completes. */
 /* the values in force on this handle; at most `cap` ids are copied to suppress, *n_suppress is their full count (any pointer may be NULL) */
 SONIC_API int sonic_get_generation(sonic_engine* e, float* repetition_penalty, int32_t* no_repeat_ngram_size, int32_t* suppress, int cap, int32_t* n_suppress);
 /* sonic_run_staged without blocking the caller: the arguments are copied, a worker thread owned by the handle runs the batch, the call
@@ -436,20 +434,32 @@ SONIC_API int sonic_fetch_rows_lp(sonic_engine* d, int n, const int32_t* rows, c
 typedef struct sonic_dispatch sonic_dispatch;
 struct sonic_ring;
 SONIC_API int sonic_dispatch_create(sonic_engine* const* decoders, int n_dec, sonic_engine* const* prefills, int n_pre, int adaptive_tiles, sonic_dispatch** out);
-SONIC_API int sonic_dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, const int64_t* host_off, struct sonic_ring* const* rings, const int64_t* ring_start,
-                                    const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, int64_t* ticket_out);
-/* sonic_dispatch_submit with the request's own sequence-bias table (one request's entries in sonic_set_request_bias's form; the request owns a copy).  The table
- * reaches the prefill of whichever batch the request lands in.  SONIC_ERR_INVALID unless every handle of the dispatcher has option request_bias on, and for a
- * table that breaks the caps; sonic_last_error(NULL) of the calling thread says which. */
-SONIC_API int sonic_dispatch_submit_bias(sonic_dispatch* d, const int16_t* host_pcm, const int64_t* host_off, struct sonic_ring* const* rings, const int64_t* ring_start,
-                                         const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, const int32_t* seq_ids,
-                                         const int32_t* seq_off, const float* bias, int n_seq, int64_t* ticket_out);
-/* sonic_dispatch_submit with the request's own (temperature, seed) and, for n_seq > 0, its sequence-bias table as sonic_dispatch_submit_bias takes it.
- * SONIC_ERR_INVALID unless every handle of the dispatcher has option sampling on (and request_bias, for a table), and for an invalid temperature;
- * sonic_last_error(NULL) of the calling thread says which. */
-SONIC_API int sonic_dispatch_submit_sampled(sonic_dispatch* d, const int16_t* host_pcm, const int64_t* host_off, struct sonic_ring* const* rings, const int64_t* ring_start,
-                                            const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, float temperature, uint64_t seed,
-                                            const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n_seq, int64_t* ticket_out);
+/* One request, whole: its audio, its prompt and budget, and the values it brings of its own.  All-zero is "none" for every value: a zeroed record with size, the
+ * audio, the prompt and the budget filled in is a plain greedy request.  The submit copies everything before it returns.  A value is refused (SONIC_ERR_INVALID, the
+ * calling thread's sonic_last_error(NULL) starting with the value's name) unless every handle of the dispatcher has the value's option on, and when it is invalid. */
+typedef struct sonic_dispatch_request {
+    int64_t size;                                /* sizeof(sonic_dispatch_request) as the caller compiled it: refused unless it is the library's */
+    /* the audio, W >= 1 windows.  Window w: host samples host_pcm[host_off[w] .. host_off[w + 1]) (int16, already peak-normalised over the request, as sonic_stage_pcm
+     * takes them; 0 == host_off[0] <= ... <= host_off[W]) when rings or rings[w] is NULL, else samples [ring_start[w], ring_start[w] + ring_n[w]) of rings[w] (raw
+     * wire PCM, normalised on the device over the request's windows) */
+    const int16_t* host_pcm; const int64_t* host_off;
+    struct sonic_ring* const* rings; const int64_t* ring_start; const int32_t* ring_n;
+    int32_t W;
+    const int32_t* prompt_ids; int32_t prompt_len;
+    int32_t max_new;
+    /* "request_bias:" its sequence-bias table, n_seq entries in sonic_set_request_bias's form for one request; n_seq = 0: none */
+    const int32_t* seq_ids; const int32_t* seq_off; const float* bias; int32_t n_seq;
+    /* "sampling:" sampled != 0: it draws under (temperature, seed) as a request of sonic_set_request_sampling; 0: greedy, the two are not read */
+    int32_t sampled; float temperature; uint64_t seed;
+    /* "truncation:" cut != 0: its draws are cut by (top_k, top_p, min_p), a row of "request_truncation" (top_k an integer value); only beside sampled */
+    int32_t cut; float top_k, top_p, min_p;
+    /* "grammar:" 0: none, else the id of a live grammar ("grammar:<id>") of the dispatcher's weight owner */
+    int32_t grammar_id;
+    /* "draft:" its draft (option draft_verify), n_draft ids that fit the vocabulary and the budget (n_draft <= max_new - 1) and are neither the audio placeholder
+     * nor an EOS id; n_draft = 0: none.  A drafted request carries no table, temperature > 0 or grammar */
+    const int32_t* draft_ids; int32_t n_draft;
+} sonic_dispatch_request;
+SONIC_API int sonic_dispatch_submit(sonic_dispatch* d, const sonic_dispatch_request* r, int64_t* ticket_out);
 SONIC_API int sonic_dispatch_cancel(sonic_dispatch* d, int64_t ticket);                 /* queued requests only */
 /* next completed request in completion order; blocks up to timeout_ms (< 0: until one completes or the dispatcher is closed and drained); *ticket_out = 0: none */
 SONIC_API int sonic_dispatch_next(sonic_dispatch* d, int timeout_ms, int64_t* ticket_out, int32_t* status_out, int32_t* out_ids, int out_cap, int32_t* n_out,
@@ -588,11 +598,11 @@ SONIC_API int sonic_stage_mixed(sonic_engine* e, const int16_t* host_pcm, const 
  *   test hook: on such a handle sonic_test_attention(q [B][Tq][Hq * 128], k [B][Tk][Hkv * 128], v = NULL, out, B, Tq, Tk, Hq, Hkv, hd = 128, causal = 0) runs the
  *   three kernels on caller data - all Hq heads, the audio run being all Tk keys - and out is [B][Tq][Tk + 1]: the matrix's row, then t_n.
  *
- * Draft-verified decoding (option "draft_verify", sonic_load_tensor "request_draft" / "draft.dispatch", sonic_debug_read "draft_accepted"): HF
+ * Draft-verified decoding (option "draft_verify", sonic_load_tensor "request_draft", sonic_debug_read "draft_accepted"): HF
  * generate()'s assisted / prompt-lookup decoding with the draft brought by the caller - a previous partial of the same audio, a first-pass model, an edited transcript.
  * The engine accepts the longest prefix of the draft that the model itself would have emitted, takes the model's own token at the first disagreement and carries on in
  * the ordinary greedy loop, without leaving the device.  Every emitted token is an argmax of the model's processed scores; a wrong draft costs its prefill rows.  The
- * feature adds no entry point and no struct: it travels as an option, two named int32 "tensors" and a sonic_debug_read name.
+ * feature adds no entry point and no struct: it travels as an option, a named int32 "tensor" and a sonic_debug_read name.
  *   "draft_verify" = 1: set on the owner before its slots are created (they copy it).  Refused (SONIC_ERR_INVALID by name) while the handle has work in hand (the
  *   rule of sonic_set_generation); on the int8 kind, whose prefill quantises per request group, so that a draft would change the group; on the fp32 test kind; on a
  *   scoring handle ("forced_parallel", which in turn is refused while this option is on).  With the option off, or on with no draft staged, the engine launches
@@ -623,10 +633,8 @@ SONIC_API int sonic_stage_mixed(sonic_engine* e, const int16_t* host_pcm, const 
  *   overwritten by the head and the loop as always.
  *   sonic_debug_read(e, "draft_accepted", 0, out, R): a_r of the handle's last prefill as fp32 values (zeros behind a prefill without drafts); tests and diagnostics.
  *   sonic_splice_rows refuses handles whose "draft_verify" differ, and copies a row's first n_new ids and records - for every row without an accepted draft that is one.
- *   dispatcher: sonic_load_tensor(e, "draft.dispatch", words = [n | ids], SONIC_DTYPE_I32, {n + 1}, 1) on any handle of the dispatcher's weight owner arms the calling
- *   thread's NEXT sonic_dispatch_submit* with that draft (n = 0: none) - no engine lock is taken, as for "grammar.dispatch:<id>"; the ids are checked at the arm, the
- *   budget (n <= max_new - 1) and the request's other values at the submit, which refuses unless every handle of the dispatcher has the option on.  With the option
- *   on, the prefill batcher counts prompt + draft tokens against one prefill's capacity.  sonic_pipeline_create refuses a handle with the option on, by name.
+ *   dispatcher: sonic_dispatch_request's draft_ids, n_draft.  With the option on, the prefill batcher counts prompt + draft tokens against one prefill's capacity.
+ *   sonic_pipeline_create refuses a handle with the option on, by name.
  *   test hook: on such a handle sonic_test_greedy_guard WITH force_ids sends its rows to rows_kernel (its choosing instantiations) - the slabs become the logits row as on a scoring handle;
  *   row b is one draft position with history hist[b][0 .. hist_len[b]) and draft id force_ids[b]; tok_out[b] = t, lp_out B records of 1 + 2K floats; neutral guard
  *   values launch the unguarded instantiation; B may exceed 64 (up to 4096). */

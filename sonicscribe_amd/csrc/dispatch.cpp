@@ -39,11 +39,11 @@ namespace {
 
 // What a request may bring of its own, in the order of VALUES below
 struct ReqValues {
-    dispatch_pack::BiasTable bias;                                 // its sequence-bias table (sonic_dispatch_submit_bias / _sampled; empty: none)
-    bool sampled = false; float temperature = 0.f; uint64_t seed = 0;   // its (temperature, seed) (sonic_dispatch_submit_sampled); unsampled requests of a batch are greedy
-    bool cut = false; float trunc[3] = {0.f, 1.f, 0.f};            // ... and its (top_k, top_p, min_p) ("truncation.dispatch" ahead of that submit; option truncation): they ride on the sampling values
-    sonic_grammar* gram = nullptr;                                 // its grammar ("grammar.dispatch:<id>" ahead of the submit): a reference held from the submit until the request completes
-    std::vector<int32_t> draft;                                    // its draft ("draft.dispatch" ahead of the submit; option draft_verify): the prefill verifies it
+    dispatch_pack::BiasTable bias;                                 // its sequence-bias table (the record's seq_ids .. n_seq; empty: none)
+    bool sampled = false; float temperature = 0.f; uint64_t seed = 0;   // its (temperature, seed); unsampled requests of a batch are greedy
+    bool cut = false; float trunc[3] = {0.f, 1.f, 0.f};            // ... and its (top_k, top_p, min_p) (option truncation): they ride on the sampling values
+    sonic_grammar* gram = nullptr;                                 // its grammar (grammar_id): a reference held from the submit until the request completes
+    std::vector<int32_t> draft;                                    // its draft (option draft_verify): the prefill verifies it
 };
 
 struct Req {
@@ -361,107 +361,92 @@ SONIC_API int sonic_dispatch_create(sonic_engine* const* decoders, int n_dec, so
     return SONIC_OK;
 }
 
-// the refusal of a value whose option is not on on every handle; `who` names the entry point (or the armed tensor) that brought it
+// the refusal of a value (named by `who`, the lead-in of every refusal of it) whose option is not on on every handle
 static int option_off(const char* who, const char* option) {
     char m[256]; snprintf(m, sizeof m, "%s: option %s is off on a handle of this dispatcher (set it on the owner before its slots are created)", who, option);
     return engine_thread_fail(SONIC_ERR_INVALID, m);
 }
 
-// a submit's table arguments, checked (option request_bias - `required`: even for an empty table -, the pointers, the caps and the vocabulary) and copied into *own
-static int take_table(sonic_dispatch* d, const char* who, bool required, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n_seq, ReqValues* own) {
-    if (required && !d->bias) return option_off(who, "request_bias");
-    if (n_seq < 0 || (n_seq > 0 && (!seq_ids || !seq_off || !bias))) return SONIC_ERR_INVALID;
-    if (n_seq == 0) return SONIC_OK;
-    if (!d->bias) return option_off(who, "request_bias");
-    const int rc = engine_bias_validate(d->pre[0], seq_ids, seq_off, bias, n_seq);
-    if (rc == SONIC_OK) own->bias = dispatch_pack::bias_table(seq_ids, seq_off, bias, n_seq);
-    return rc;
-}
-
-// One request of W windows.  Window w: host samples host_pcm[host_off[w] .. host_off[w + 1]) (int16, already peak-normalised over the request, as
-// sonic_stage_pcm takes them) when rings is NULL or rings[w] is NULL, else samples [ring_start[w], ring_start[w] + ring_n[w]) of rings[w] (raw wire
-// PCM, normalised on the device over the request's windows).  Everything is copied before the call returns.
-static int dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, const int64_t* host_off, sonic_ring* const* rings, const int64_t* ring_start,
-                           const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, ReqValues own, int64_t* ticket_out) {
-    // the grammar armed on this thread (sonic_load_tensor "grammar.dispatch:<id>"): this submit takes it whatever becomes of it
-    struct Armed { sonic_grammar* g; ~Armed() { if (g) engine_grammar_unref(g); } } armed{engine_take_dispatch_grammar()};
-    sonic_grammar* gram = armed.g;
-    const int32_t* draft = nullptr;
-    const int n_draft = engine_take_dispatch_draft(&draft);        // ... and the draft ("draft.dispatch"), likewise
-    float cut_row[3]; const bool cut = engine_take_dispatch_truncation(cut_row) != 0;      // ... and the cut ("truncation.dispatch"), likewise
-    if (!d || !ticket_out || W < 1 || !prompt_ids || prompt_len < 1 || max_new < 1 || !host_off) return SONIC_ERR_INVALID;
-    if (rings && (!ring_start || !ring_n)) return SONIC_ERR_INVALID;
+// One request (include/sonic_hip.h sonic_dispatch_request), checked in ONE order and then queued; a refusal leaves nothing behind, here or on the calling thread:
+//   1. NULL pointers and the record's size;
+//   2. the audio and the prompt;
+//   3. the values it brings, in the order of VALUES: bias, sampling with its cut, grammar, draft - for each, that its option is on on every handle, then its validity
+//      (the message starts with the value's name: request_bias, sampling, truncation, grammar, draft);
+//   4. under the lock: closed, failed, and the request joins the queue.
+// Everything is copied before the call returns.
+SONIC_API int sonic_dispatch_submit(sonic_dispatch* d, const sonic_dispatch_request* q, int64_t* ticket_out) {
+    if (!d || !q || !ticket_out) return SONIC_ERR_INVALID;
+    if (q->size != (int64_t)sizeof *q) {
+        char m[160]; snprintf(m, sizeof m, "sonic_dispatch_submit: sonic_dispatch_request.size is %lld, this library's record has %zu bytes", (long long)q->size, sizeof *q);
+        return engine_thread_fail(SONIC_ERR_INVALID, m);
+    }
+    const int W = q->W;
+    if (W < 1 || !q->prompt_ids || q->prompt_len < 1 || q->max_new < 1 || !q->host_off) return SONIC_ERR_INVALID;
+    if (q->rings && (!q->ring_start || !q->ring_n)) return SONIC_ERR_INVALID;
+    if (!dispatch_pack::offsets_ok(q->host_off, W) || (q->host_off[W] > 0 && !q->host_pcm)) return SONIC_ERR_INVALID;
+    ReqValues own;
+    struct Held { sonic_grammar* g; ~Held() { if (g) engine_grammar_unref(g); } } held{nullptr};      // the grammar's reference, until the request is queued
+    if (q->n_seq < 0 || (q->n_seq > 0 && (!q->seq_ids || !q->seq_off || !q->bias))) return SONIC_ERR_INVALID;
+    if (q->n_seq > 0) {
+        if (!d->bias) return option_off("request_bias", "request_bias");
+        const int rc = engine_bias_validate(d->pre[0], q->seq_ids, q->seq_off, q->bias, q->n_seq);
+        if (rc != SONIC_OK) return rc;
+        own.bias = dispatch_pack::bias_table(q->seq_ids, q->seq_off, q->bias, q->n_seq);
+    }
+    if (q->sampled) {
+        if (!d->samp) return option_off("sampling", "sampling");
+        const int rc = engine_sampling_validate(q->temperature);
+        if (rc != SONIC_OK) return rc;
+        own.sampled = true; own.temperature = q->temperature; own.seed = q->seed;
+    }
+    if (q->cut) {
+        if (!d->trunc) return option_off("truncation", "truncation");
+        if (!q->sampled) return engine_thread_fail(SONIC_ERR_INVALID, "truncation: the request is not sampled (top_k / top_p / min_p cut what a sampling request draws from)");
+        const float row[3] = {q->top_k, q->top_p, q->min_p};
+        const int rc = engine_truncation_validate(row);
+        if (rc != SONIC_OK) return rc;
+        own.cut = true; memcpy(own.trunc, row, sizeof row);
+    }
+    if (q->grammar_id != 0) {
+        if (!d->gram) return option_off("grammar", "grammar");
+        held.g = engine_grammar_ref_id(d->pre[0], q->grammar_id);
+        if (!held.g) {
+            char m[128]; snprintf(m, sizeof m, "grammar: %d is not a live grammar of this dispatcher's weight owner", (int)q->grammar_id);
+            return engine_thread_fail(SONIC_ERR_INVALID, m);
+        }
+    }
+    if (q->n_draft < 0 || (q->n_draft > 0 && !q->draft_ids)) return SONIC_ERR_INVALID;
+    if (q->n_draft > 0) {
+        if (!d->draft) return option_off("draft", "draft_verify");
+        const int rc = engine_draft_validate(d->pre[0], q->draft_ids, q->n_draft);
+        if (rc != SONIC_OK) return rc;
+        if (q->n_draft > q->max_new - 1) {
+            char m[200]; snprintf(m, sizeof m, "draft: the draft holds %d ids, the request's budget of %d tokens leaves room for %d (the last token is the model's own; nothing is truncated)", (int)q->n_draft, (int)q->max_new, (int)q->max_new - 1);
+            return engine_thread_fail(SONIC_ERR_INVALID, m);
+        }
+        if (!own.bias.val.empty() || (own.sampled && own.temperature > 0.f) || held.g)
+            return engine_thread_fail(SONIC_ERR_INVALID, "draft: a drafted request carries no bias table, temperature > 0 or grammar (the verify pass applies the handle's processors only)");
+        own.draft.assign(q->draft_ids, q->draft_ids + q->n_draft);
+    }
     auto r = std::make_shared<Req>();
     r->W = W;
-    r->off.assign(host_off, host_off + W + 1);
-    if (r->off[0] != 0) return SONIC_ERR_INVALID;
-    if (r->off[W] > 0) { if (!host_pcm) return SONIC_ERR_INVALID; r->pcm.assign(host_pcm, host_pcm + r->off[W]); }
-    if (rings) {
-        r->rings.assign(rings, rings + W); r->ring_start.assign(ring_start, ring_start + W); r->ring_n.assign(ring_n, ring_n + W);
-        for (int w = 0; w < W; ++w) r->any_ring = r->any_ring || rings[w];
+    r->off.assign(q->host_off, q->host_off + W + 1);
+    if (r->off[W] > 0) r->pcm.assign(q->host_pcm, q->host_pcm + r->off[W]);
+    if (q->rings) {
+        r->rings.assign(q->rings, q->rings + W); r->ring_start.assign(q->ring_start, q->ring_start + W); r->ring_n.assign(q->ring_n, q->ring_n + W);
+        for (int w = 0; w < W; ++w) r->any_ring = r->any_ring || q->rings[w];
     }
-    r->prompt.assign(prompt_ids, prompt_ids + prompt_len); r->max_new = max_new;
+    r->prompt.assign(q->prompt_ids, q->prompt_ids + q->prompt_len); r->max_new = q->max_new;
     r->own = std::move(own);
     std::unique_lock<std::mutex> lk(d->mu);
     if (d->stop) return SONIC_ERR_INVALID;
     if (d->failed) return d->failed;
-    if (cut) {
-        if (!d->trunc) return option_off("truncation.dispatch", "truncation");
-        if (!r->own.sampled) return engine_thread_fail(SONIC_ERR_INVALID, "truncation.dispatch: the submit that followed is not sonic_dispatch_submit_sampled (top_k / top_p / min_p cut what a sampling request draws from)");
-        r->own.cut = true; memcpy(r->own.trunc, cut_row, sizeof cut_row);
-    }
-    if (n_draft > 0) {
-        if (!d->draft) return option_off("draft.dispatch", "draft_verify");
-        if (n_draft > max_new - 1) {
-            char m[200]; snprintf(m, sizeof m, "draft.dispatch: the draft holds %d ids, the request's budget of %d tokens leaves room for %d (the last token is the model's own; nothing is truncated)", n_draft, max_new, max_new - 1);
-            return engine_thread_fail(SONIC_ERR_INVALID, m);
-        }
-        if (!r->own.bias.val.empty() || (r->own.sampled && r->own.temperature > 0.f) || gram)
-            return engine_thread_fail(SONIC_ERR_INVALID, "draft.dispatch: a drafted request carries no bias table, temperature > 0 or grammar (the verify pass applies the handle's processors only)");
-        r->own.draft.assign(draft, draft + n_draft);
-    }
-    if (gram) {
-        if (!d->gram) return option_off("grammar.dispatch", "grammar");
-        const void* wid = nullptr;
-        (void)sonic_engine_info(d->pre[0], nullptr, nullptr, nullptr, nullptr, &wid);
-        if (engine_grammar_owner(gram) != wid) return engine_thread_fail(SONIC_ERR_INVALID, "grammar.dispatch: the grammar is not a live grammar of this dispatcher's weight owner");
-        r->own.gram = gram; armed.g = nullptr;                      // (the request keeps the reference until it completes)
-    }
+    r->own.gram = held.g; held.g = nullptr;                        // (the request keeps the reference until it completes)
     r->ticket = d->next_ticket++;
     d->q.push_back(r); d->queued_windows += W; ++d->outstanding;
     *ticket_out = r->ticket;
     d->cv.notify_all();
     return SONIC_OK;
-}
-
-SONIC_API int sonic_dispatch_submit(sonic_dispatch* d, const int16_t* host_pcm, const int64_t* host_off, sonic_ring* const* rings, const int64_t* ring_start,
-                                    const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, int64_t* ticket_out) {
-    return dispatch_submit(d, host_pcm, host_off, rings, ring_start, ring_n, W, prompt_ids, prompt_len, max_new, ReqValues(), ticket_out);
-}
-// sonic_dispatch_submit with the request's own sequence-bias table (n_seq entries in sonic_set_request_bias's form for one request; the request owns a copy): the
-// prefill thread hands it to the prefill of the batch the request lands in.  SONIC_ERR_INVALID unless every handle of the dispatcher has option request_bias on,
-// and for a table that breaks the caps; sonic_last_error(NULL) of the calling thread says which
-SONIC_API int sonic_dispatch_submit_bias(sonic_dispatch* d, const int16_t* host_pcm, const int64_t* host_off, sonic_ring* const* rings, const int64_t* ring_start,
-                                         const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, const int32_t* seq_ids,
-                                         const int32_t* seq_off, const float* bias, int n_seq, int64_t* ticket_out) {
-    if (!d) return SONIC_ERR_INVALID;
-    ReqValues own;
-    { const int rc = take_table(d, "sonic_dispatch_submit_bias", true, seq_ids, seq_off, bias, n_seq, &own); if (rc != SONIC_OK) return rc; }
-    return dispatch_submit(d, host_pcm, host_off, rings, ring_start, ring_n, W, prompt_ids, prompt_len, max_new, std::move(own), ticket_out);
-}
-
-// sonic_dispatch_submit with the request's own (temperature, seed), and its sequence-bias table where one is given (n_seq > 0): SONIC_ERR_INVALID unless every
-// handle of the dispatcher has option sampling on (and request_bias for a table), and for a temperature that is neither 0 nor in 1e-3 .. 100
-SONIC_API int sonic_dispatch_submit_sampled(sonic_dispatch* d, const int16_t* host_pcm, const int64_t* host_off, sonic_ring* const* rings, const int64_t* ring_start,
-                                            const int32_t* ring_n, int W, const int32_t* prompt_ids, int prompt_len, int max_new, float temperature, uint64_t seed,
-                                            const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n_seq, int64_t* ticket_out) {
-    if (!d) return SONIC_ERR_INVALID;
-    if (!d->samp) return option_off("sonic_dispatch_submit_sampled", "sampling");
-    { const int rc = engine_sampling_validate(temperature); if (rc != SONIC_OK) return rc; }
-    ReqValues own;
-    own.sampled = true; own.temperature = temperature; own.seed = seed;
-    { const int rc = take_table(d, "sonic_dispatch_submit_sampled", false, seq_ids, seq_off, bias, n_seq, &own); if (rc != SONIC_OK) return rc; }
-    return dispatch_submit(d, host_pcm, host_off, rings, ring_start, ring_n, W, prompt_ids, prompt_len, max_new, std::move(own), ticket_out);
 }
 
 // a request that is still queued leaves the queue (it completes with status SONIC_ERR_INVALID, "cancelled"); one that has reached a handle runs on

@@ -8,6 +8,13 @@
 
 namespace dispatch_pack {
 
+// a submit's host_off over W >= 1 windows: 0 == off[0] <= off[1] <= ... <= off[W], so that every window is a range of the request's samples
+inline bool offsets_ok(const int64_t* off, int W) {
+    if (off[0] != 0) return false;
+    for (int w = 0; w < W; ++w) if (off[w + 1] < off[w]) return false;
+    return true;
+}
+
 // one request's sequence-bias table: sequence i is ids[off[i] .. off[i + 1]) with bias val[i]; off[0] == 0; off empty: no table
 struct BiasTable { std::vector<int32_t> ids, off; std::vector<float> val; };
 

@@ -290,25 +290,8 @@ static int trunc_upload(sonic_engine* e, int R) {
     HIPC(e, hipMemcpyAsync(e->trunc.dev, e->trunc.host, (size_t)TRUNC_STAGE_WORDS * 4, hipMemcpyHostToDevice, e->st));
     return stage_sent(e, e->trunc);
 }
-// sonic_load_tensor "truncation.dispatch" on any handle of a dispatcher's weight owner, float32 {3} = (top_k, top_p, min_p): the calling thread's NEXT sonic_dispatch_submit*
-// carries that row, which takes it whatever becomes of the submit (a submit that is not sonic_dispatch_submit_sampled refuses it by name).  A thread-local and no
-// engine lock, as "grammar.dispatch:<id>".  The values are checked here; that every handle of the dispatcher has the option, at the submit
-static thread_local float g_dispatch_trunc[3];
-static thread_local bool g_dispatch_trunc_armed = false;
-int trunc_dispatch_arm(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim) {
-    g_dispatch_trunc_armed = false;
-    if (dtype != SONIC_DTYPE_F32 || ndim != 1 || shape[0] != 3) return fail(nullptr, SONIC_ERR_INVALID, "truncation.dispatch: the values are one float32 row [top_k | top_p | min_p] (SONIC_DTYPE_F32, shape {3})");
-    if (!e->opt_truncation) return fail(nullptr, SONIC_ERR_INVALID, "truncation.dispatch: option truncation is off on this handle (sonic_set_option(e, \"truncation\", 1) on the owner before its slots are created)");
-    unsigned w[3];
-    TRY(trunc_pack(nullptr, "truncation.dispatch", (const float*)data, 0, w));
-    memcpy(g_dispatch_trunc, data, sizeof g_dispatch_trunc); g_dispatch_trunc_armed = true;
-    return SONIC_OK;
-}
-extern "C" int engine_take_dispatch_truncation(float* row) {
-    if (!g_dispatch_trunc_armed) return 0;
-    g_dispatch_trunc_armed = false; memcpy(row, g_dispatch_trunc, sizeof g_dispatch_trunc);
-    return 1;
-}
+// dispatch.cpp (same library, not exported): one request's (top_k, top_p, min_p) checked at its submit, the message to the calling thread's sonic_last_error(NULL)
+extern "C" int engine_truncation_validate(const float* row) { unsigned w[3]; return trunc_pack(nullptr, "truncation", row, 0, w); }
 extern "C" int engine_truncation_on(sonic_engine* e) { return e && e->opt_truncation && e->trunc.dev ? 1 : 0; }
 extern "C" int engine_sampling_on(sonic_engine* e) { return e && e->opt_sampling && e->samp.dev ? 1 : 0; }
 // ---- option grammar: a request's transcript restricted to the paths of a deterministic token automaton - HF's prefix_allowed_tokens_fn
@@ -475,18 +458,6 @@ extern "C" int engine_set_request_grammar(sonic_engine* e, sonic_grammar* const*
     gram_stage_words(e);
     return SONIC_OK;
 }
-// sonic_load_tensor "grammar.dispatch:<id>" on any handle of a dispatcher's weight owner: the calling thread's NEXT sonic_dispatch_submit* carries that grammar (0: none;
-// the registry's lock and a thread-local, never the engine lock: a decoding handle holds that one for a chunk at a time), which takes it - and its
-// reference - whatever becomes of the submit
-static thread_local sonic_grammar* g_dispatch_gram = nullptr;
-int gram_dispatch_arm(sonic_engine* e, int id) {
-    gram_unref(g_dispatch_gram); g_dispatch_gram = nullptr;
-    if (id == 0) return SONIC_OK;
-    g_dispatch_gram = gram_ref_id(e->owner ? e->owner : e, id);
-    if (!g_dispatch_gram) return fail(nullptr, SONIC_ERR_INVALID, "grammar.dispatch: %d is not a live grammar of this handle's weight owner", id);
-    return SONIC_OK;
-}
-extern "C" sonic_grammar* engine_take_dispatch_grammar(void) { sonic_grammar* g = g_dispatch_gram; g_dispatch_gram = nullptr; return g; }
 static int gram_upload(sonic_engine* e, int R) {
     (void)R;
     if (!e->opt_grammar) return SONIC_OK;
@@ -500,18 +471,19 @@ static int gram_upload(sonic_engine* e, int R) {
     HIPC(e, hipMemcpyAsync(e->gram.dev, e->gram.host, (size_t)GRAM_STAGE_WORDS * 8, hipMemcpyHostToDevice, e->st));
     return stage_sent(e, e->gram);
 }
-// dispatch.cpp (same library, not exported): the option on a handle; whose grammar it is; a queued request's reference handed back
+// dispatch.cpp (same library, not exported): the option on a handle; a submitted request's reference (the registry's lock, never the engine lock: a decoding handle
+// holds that one for a chunk at a time) and its return
 extern "C" int engine_grammar_on(sonic_engine* e) { return e && e->opt_grammar && e->gram.dev ? 1 : 0; }
-extern "C" void* engine_grammar_owner(sonic_grammar* g) { return g ? (void*)g->root : nullptr; }
+extern "C" sonic_grammar* engine_grammar_ref_id(sonic_engine* e, int id) { return e ? gram_ref_id(e->owner ? e->owner : e, id) : nullptr; }
 extern "C" void engine_grammar_unref(sonic_grammar* g) { gram_unref(g); }
-extern "C" int engine_sampling_validate(float temperature) { return samp_check(nullptr, "sonic_dispatch_submit_sampled", &temperature, 1); }
+extern "C" int engine_sampling_validate(float temperature) { return samp_check(nullptr, "sampling", &temperature, 1); }
 // dispatch.cpp (same library, not exported): is the option on for a handle; is one request's table well-formed for it (the message lands on the handle)
 extern "C" int engine_request_bias_on(sonic_engine* e) { return e && e->opt_request_bias && e->bias.dev ? 1 : 0; }
 // (the handle is only read for its vocabulary: the message goes to the calling thread's sonic_last_error(NULL), no lock is needed)
 extern "C" int engine_bias_validate(sonic_engine* e, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n) {
     if (!e) return SONIC_ERR_INVALID;
     std::vector<int> row((size_t)BIAS_ROW_WORDS); int cnt = 0;
-    return bias_pack(nullptr, "sonic_dispatch_submit_bias", seq_ids, seq_off, bias, n, e->d.vocab, row.data(), &cnt);
+    return bias_pack(nullptr, "request_bias", seq_ids, seq_off, bias, n, e->d.vocab, row.data(), &cnt);
 }
 extern "C" int engine_thread_fail(int code, const char* msg) { return fail(nullptr, code, "%s", msg); }
 
@@ -595,34 +567,18 @@ int draft_alloc(sonic_engine* e) {
     if (!e->draft_acc) TRY(dalloc(e, &e->draft_acc, (size_t)64));
     return SONIC_OK;
 }
-// sonic_load_tensor "draft.dispatch" on any handle of a dispatcher's weight owner, words = [n | ids]: the calling thread's NEXT sonic_dispatch_submit* carries that draft
-// (n = 0: none), which takes it whatever becomes of the submit.  A thread-local and no engine lock, as "grammar.dispatch:<id>": a decoding handle holds its lock for a
-// chunk at a time.  The ids are checked here, against the handle's model; the budget and the dispatcher's handles at the submit
-static thread_local std::vector<int32_t> g_dispatch_draft;
-static thread_local bool g_dispatch_draft_armed = false;
-int draft_dispatch_arm(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim) {
-    g_dispatch_draft.clear(); g_dispatch_draft_armed = false;
-    if (dtype != SONIC_DTYPE_I32 || ndim != 1 || shape[0] < 1) return fail(nullptr, SONIC_ERR_INVALID, "draft.dispatch: a draft is one row of int32 words [n | ids] (SONIC_DTYPE_I32, ndim 1)");
-    const int* w = (const int*)data;
-    if (w[0] < 0 || (int64_t)w[0] != shape[0] - 1) return fail(nullptr, SONIC_ERR_INVALID, "draft.dispatch: the words name %d ids and hold %lld", w[0], (long long)(shape[0] - 1));
-    if (!e->opt_draft_verify) return fail(nullptr, SONIC_ERR_INVALID, "draft.dispatch: option draft_verify is off on this handle (sonic_set_option(e, \"draft_verify\", 1) on the owner before its slots are created)");
-    for (int k = 1; k <= w[0]; ++k) {
-        const int id = w[k];
-        if (id < 0 || id >= e->d.vocab) return fail(nullptr, SONIC_ERR_INVALID, "draft.dispatch: token id %d is out of vocabulary (%d)", id, e->d.vocab);
-        if (id == e->d.audio_token_id) return fail(nullptr, SONIC_ERR_INVALID, "draft.dispatch: token id %d is the audio placeholder, which cannot be emitted", id);
+// dispatch.cpp (same library, not exported): one request's draft checked at its submit against the handle's model (which is only read: no lock; the message goes to the
+// calling thread's sonic_last_error(NULL)); the tokens one prefill of a handle holds
+extern "C" int engine_draft_validate(sonic_engine* e, const int32_t* ids, int n) {
+    if (!e || !ids) return SONIC_ERR_INVALID;
+    for (int k = 0; k < n; ++k) {
+        const int id = ids[k];
+        if (id < 0 || id >= e->d.vocab) return fail(nullptr, SONIC_ERR_INVALID, "draft: token id %d is out of vocabulary (%d)", id, e->d.vocab);
+        if (id == e->d.audio_token_id) return fail(nullptr, SONIC_ERR_INVALID, "draft: token id %d is the audio placeholder, which cannot be emitted", id);
         for (int q = 0; q < e->d.n_eos; ++q)
-            if (id == e->d.eos[q]) return fail(nullptr, SONIC_ERR_INVALID, "draft.dispatch: token id %d is an EOS id of this handle (a draft ends in front of it; nothing is truncated)", id);
+            if (id == e->d.eos[q]) return fail(nullptr, SONIC_ERR_INVALID, "draft: token id %d is an EOS id of this handle (a draft ends in front of it; nothing is truncated)", id);
     }
-    if (w[0] == 0) return SONIC_OK;
-    g_dispatch_draft.assign(w + 1, w + 1 + w[0]); g_dispatch_draft_armed = true;
     return SONIC_OK;
-}
-// dispatch.cpp (same library, not exported): the draft armed for this thread's next submit (-1: none; else its length, the ids valid until the thread arms again);
-// whether the option is on for a handle; the tokens one prefill of a handle holds
-extern "C" int engine_take_dispatch_draft(const int32_t** ids) {
-    if (!g_dispatch_draft_armed) return -1;
-    g_dispatch_draft_armed = false; *ids = g_dispatch_draft.data();
-    return (int)g_dispatch_draft.size();
 }
 extern "C" int engine_tok_cap(sonic_engine* e) { return e ? e->tok_cap : 0; }
 // ---- row forks (include/sonic_hip.h beside sonic_load_tensor): one prefilled request becomes several rows - Whisper's best_of draws its N samples

@@ -519,7 +519,6 @@ int trunc_enable(sonic_engine* e, int on);          // option truncation behind 
 // NaN or a value out of range (message on e, or the calling thread's for e = NULL); nothing is clamped
 int trunc_pack(sonic_engine* e, const char* who, const float* v, int row, unsigned* w);
 int trunc_stage_rows(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim);   // sonic_load_tensor "request_truncation": the values of the next prefill's rows
-int trunc_dispatch_arm(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim); // sonic_load_tensor "truncation.dispatch" (no engine lock): the calling thread's next sonic_dispatch_submit_sampled carries the row
 int trunc_hook_arm(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim);     // sonic_load_tensor "truncation.hook": the next sonic_test_greedy_sample launch's rows
 int share_hook_arm(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim);     // sonic_load_tensor "share_prompt.hook" (engine_hooks.cpp): the next sonic_test_prefill_attention launch's pre_row | pre_len
 int gram_enable(sonic_engine* e, int on);           // option grammar behind the lock and the busy check: hist, the rows' references and state words and their staging buffer on first use
@@ -532,7 +531,6 @@ int gram_create(sonic_engine* e, int id, const int* words, int64_t n);   // soni
 int gram_hook_arm(sonic_engine* e, int V, const int* words, int64_t n);  // sonic_load_tensor "grammar.hook:<V>": the hooks' automaton, validated against V; every row free, no EOS ids
 int gram_stage_begin(sonic_engine* e, int R);       // option request_grammar_begin: R requests staged for the next prefill, all free (the caller holds the lock)
 int gram_stage_row(sonic_engine* e, int value);     // option request_grammar = request << 16 | grammar id: that staged request refers to that grammar
-int gram_dispatch_arm(sonic_engine* e, int id);     // sonic_load_tensor "grammar.dispatch:<id>" (no engine lock): the calling thread's next sonic_dispatch_submit* carries grammar `id` of e's owner
 // the splice's one descriptor (splice_kv_kernel / splice_state_kernel, engine_service.cpp, which fills the rest of it); declared here for req_splice_args
 struct SpliceArgs {
     const bf16_t *Ks, *Vs; bf16_t *Kd, *Vd; int layers, Bm, Hkv, ctx, hd;
@@ -571,7 +569,6 @@ int draft_stage_words(sonic_engine* e, const void* data, int dtype, const int64_
 // requests' longer sequences prompt || draft (ids, off), the budgets plan_requests checks them with (left) and the draft lengths (dlen).  dlen stays empty otherwise
 int draft_extend(sonic_engine* e, int R, const int32_t* prompt_ids, const int64_t* prompt_off, const int32_t* max_new,
                  std::vector<int32_t>& ids, std::vector<int64_t>& off, std::vector<int32_t>& left, std::vector<int>& dlen);
-int draft_dispatch_arm(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim);   // sonic_load_tensor "draft.dispatch" (no engine lock): the calling thread's next sonic_dispatch_submit* carries the draft
 int draft_alloc(sonic_engine* e);                   // the buffers, at the handle's first drafted prefill (and ver_rec again when top_logprobs has changed since)
 // row forks (sonic_load_tensor "request_forks")
 int fork_stage_counts(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim);   // the fork counts of the next prefill's requests

@@ -72,8 +72,7 @@ static int raw_alloc(sonic_engine* e, const std::string& name, const std::vector
 extern "C" int sonic_load_tensor(sonic_engine* e, const char* name, const void* data, int dtype, const int64_t* shape, int ndim) {
     if (!e || !name || !data || !shape) return SONIC_ERR_INVALID;
     // grammars are int32 "tensors" of a finalized engine: "grammar:<id>" creates (shape {0}: destroys) one on the weight owner, without the
-    // engine lock; "grammar.dispatch:<id>" arms the calling thread's next dispatcher submit, likewise; "grammar.hook:<V>" arms the kernel hooks' automaton
-    if (!strncmp(name, "grammar.dispatch:", 17)) return gram_dispatch_arm(e, atoi(name + 17));      // (the calling thread's next dispatcher submit; no words are read)
+    // engine lock; "grammar.hook:<V>" arms the kernel hooks' automaton
     if (!strncmp(name, "grammar:", 8) || !strncmp(name, "grammar.hook:", 13)) {
         if (dtype != SONIC_DTYPE_I32 || ndim != 1 || shape[0] < 0) return fail(nullptr, SONIC_ERR_INVALID, "%s: a grammar is one row of int32 words (SONIC_DTYPE_I32, ndim 1)", name);
         if (name[7] == ':') return gram_create(e, atoi(name + 8), (const int*)data, shape[0]);
@@ -87,11 +86,9 @@ extern "C" int sonic_load_tensor(sonic_engine* e, const char* name, const void* 
         if (name[7] == ':') return lm_hook_arm(e, atoi(name + 8), (const int*)data, shape[0]);
         return lm_hook_step(e, (const int*)data, shape[0]);
     }
-    if (!strcmp(name, "draft.dispatch")) return draft_dispatch_arm(e, data, dtype, shape, ndim);      // ... and the one of the calling thread's next dispatcher submit (no engine lock, as grammar.dispatch)
     if (!strcmp(name, "request_draft")) return draft_stage_words(e, data, dtype, shape, ndim);      // the drafts of the next prefill's requests (option draft_verify)
     if (!strcmp(name, "request_forks")) return fork_stage_counts(e, data, dtype, shape, ndim);      // the fork counts of the next prefill's requests
     if (!strcmp(name, "request_truncation")) return trunc_stage_rows(e, data, dtype, shape, ndim);      // top_k / top_p / min_p of the next prefill's rows (option truncation)
-    if (!strcmp(name, "truncation.dispatch")) return trunc_dispatch_arm(e, data, dtype, shape, ndim);      // ... of the calling thread's next sonic_dispatch_submit_sampled (no engine lock, as grammar.dispatch)
     if (!strcmp(name, "truncation.hook")) return trunc_hook_arm(e, data, dtype, shape, ndim);      // ... and of the next sonic_test_greedy_sample launch
     if (!strcmp(name, "share_prompt.hook")) return share_hook_arm(e, data, dtype, shape, ndim);      // pre_row | pre_len of the next sonic_test_prefill_attention launch (option forced_share_prompt's kernel)
     ENTER(e);

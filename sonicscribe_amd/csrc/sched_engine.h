@@ -18,7 +18,6 @@ int engine_forced_parallel_on(sonic_engine* e);                // a scoring hand
 int engine_request_bias_on(sonic_engine* e);
 int engine_sampling_on(sonic_engine* e);
 int engine_truncation_on(sonic_engine* e);                     // option truncation
-int engine_take_dispatch_truncation(float* row);               // "truncation.dispatch": 1 and the armed (top_k, top_p, min_p) in row[0 .. 3), or 0 (none)
 int engine_grammar_on(sonic_engine* e);
 int engine_lm_on(sonic_engine* e);                             // option lm (the bulk pipeline carries no language-model state: refused there)
 int engine_draft_verify_on(sonic_engine* e);                  // (the bulk pipeline takes no drafts: refused there)
@@ -27,11 +26,11 @@ int engine_tok_cap(sonic_engine* e);                          // the tokens one 
 // one request's values, checked at its submit (the message goes to the calling thread's sonic_last_error(NULL))
 int engine_bias_validate(sonic_engine* e, const int32_t* seq_ids, const int32_t* seq_off, const float* bias, int n);   // a table against the caps and this handle's vocabulary
 int engine_sampling_validate(float temperature);               // 0 or 1e-3 .. 100
-// what sonic_load_tensor armed for the calling thread's next submit
-sonic_grammar* engine_take_dispatch_grammar(void);             // "grammar.dispatch:<id>": the grammar with a reference, or NULL ...
+int engine_truncation_validate(const float* row);              // one (top_k, top_p, min_p)
+int engine_draft_validate(sonic_engine* e, const int32_t* ids, int n);   // a draft's ids against this handle's model: in the vocabulary, neither the audio placeholder nor an EOS id
+// (none of the four takes an engine lock - a decoding handle holds its own for a chunk at a time -, and neither do the next two: the owner's registry lock alone)
+sonic_grammar* engine_grammar_ref_id(sonic_engine* e, int id); // grammar `id` of e's weight owner with a reference, or NULL (no such live grammar) ...
 void engine_grammar_unref(sonic_grammar* g);                   // ... and the reference's return
-void* engine_grammar_owner(sonic_grammar* g);                  // the weight owner a grammar lives on
-int engine_take_dispatch_draft(const int32_t** ids);           // "draft.dispatch": its length (-1: none)
 int engine_set_request_grammar(sonic_engine* e, sonic_grammar* const* grammars, int R);   // a batch's grammars (NULL: a free request) for the handle's next prefill
 // a message from outside a handle's calls: to the calling thread's sonic_last_error(NULL) / on a handle (sonic_last_error(e)); returns code
 int engine_thread_fail(int code, const char* msg);

@@ -518,7 +518,7 @@ class _NativeContinuousReplica:
         return self._stats()[2]
 
     def _pack_audio(self, wins):
-        """a request's windows as the arrays every sonic_dispatch_submit* takes: (host_pcm, host_off, rings, ring_start, ring_n), the last three None without a ring slice"""
+        """a request's windows as the arrays sonic_dispatch_request takes: (host_pcm, host_off, rings, ring_start, ring_n), the last three None without a ring slice"""
         import ctypes as C
         from .engine import RingSlice
         W = len(wins)
@@ -540,7 +540,7 @@ class _NativeContinuousReplica:
 
     def put(self, req: Request):
         import ctypes as C
-        from .engine import _p, pack_dispatch_draft
+        from .engine import DispatchRequest, _p, pack_request_draft
         if req.want_logprobs and not self.lp:
             raise ValueError(LOGPROBS_OFF)
         reqvalues.refuse_unsupported(req, self.admits)
@@ -550,44 +550,33 @@ class _NativeContinuousReplica:
         dev_gram = None if req.grammar is None else req.grammar.on(self.engine)
         pcm, offs, ring_arr, start, n = self._pack_audio(req.windows)
         prompt = np.ascontiguousarray(req.prompt, dtype=np.int32)
-        t = C.c_int64(0)
-        # everything that can raise is packed before the grammar is armed: the arm is the call right ahead of the submit.  The three entry points share their leading
-        # arguments: picked here are the entry point and its own tail (a temperature takes the table along)
-        b_ids, b_off, b_val = req.bias.table() if req.bias else (None, None, np.zeros(0, np.float32))
-        table = (_p(b_ids), _p(b_off), _p(b_val) if len(b_val) else None, len(b_val), C.byref(t))
+        # one record (include/sonic_hip.h sonic_dispatch_request): all-zero is a request without values of its own.  The arrays it points to live until the call returns
+        r = DispatchRequest(host_pcm=_p(pcm), host_off=_p(offs), rings=C.addressof(ring_arr) if ring_arr is not None else None, ring_start=_p(start), ring_n=_p(n),
+                            W=len(req.windows), prompt_ids=_p(prompt), prompt_len=len(prompt), max_new=int(req.max_new))
+        if req.bias:
+            b_ids, b_off, b_val = req.bias.table()
+            r.seq_ids, r.seq_off, r.bias, r.n_seq = _p(b_ids), _p(b_off), _p(b_val), len(b_val)
         if req.sampling:
             from . import sampling as _sampling
-            submit, tail = self.lib.sonic_dispatch_submit_sampled, (_sampling.check_temperature(req.sampling[0]), _sampling.check_seed(req.sampling[1])) + table
-        elif req.bias:
-            submit, tail = self.lib.sonic_dispatch_submit_bias, table
-        else:
-            submit, tail = self.lib.sonic_dispatch_submit, (C.byref(t),)
-        if dev_gram is not None and dev_gram.h is None:
-            raise ValueError("grammar: the grammar has been closed")
-        draft_words = pack_dispatch_draft(req.draft) if req.draft else None      # sonic_load_tensor "draft.dispatch": n | ids
-        cut_row = None
-        if req.sampling and len(req.sampling) == 5:                                # sonic_load_tensor "truncation.dispatch": top_k | top_p | min_p
-            from . import sampling as _sampling
-            cut_row = _sampling.truncation_words(*req.sampling[2:])
+            r.sampled, r.temperature, r.seed = 1, _sampling.check_temperature(req.sampling[0]), _sampling.check_seed(req.sampling[1])
+        if dev_gram is not None:
+            if dev_gram.h is None:
+                raise ValueError("grammar: the grammar has been closed")
+            r.grammar_id = int(dev_gram.id)
+        if req.draft:
+            draft = pack_request_draft([req.draft])[3:]  # (R | off[0 .. 1] | ids: the ids, refused unless they are int32 values)
+            r.draft_ids, r.n_draft = _p(draft), len(draft)
+        if req.sampling and len(req.sampling) == 5:      # ... with its cut: the row of "request_truncation"
+            r.cut, (r.top_k, r.top_p, r.min_p) = 1, _sampling.truncation_words(*req.sampling[2:])
+        t = C.c_int64(0)
         with self.lock:
             if self.stop:
                 raise RuntimeError("ASR engine is closed")
-            if dev_gram is not None:
-                # this thread's next submit, whichever of the three, carries the grammar (sonic_load_tensor "grammar.dispatch:<id>": the owner's registry and a
-                # thread-local, never the lock of an engine - the decode loop holds its handle's for a chunk at a time, and put() must not wait for it)
-                one = np.zeros(1, np.int32)
-                if self.lib.sonic_load_tensor(self.engine.h, f"grammar.dispatch:{int(dev_gram.id)}".encode(), _p(one), 2, (C.c_int64 * 1)(0), 1) != 0:
-                    raise ValueError("grammar: " + (self.lib.sonic_last_error(None) or b"").decode())
-            if draft_words is not None:                  # ... and the draft, the same way ("draft.dispatch": a thread-local, no engine lock)
-                if self.lib.sonic_load_tensor(self.engine.h, b"draft.dispatch", _p(draft_words), 2, (C.c_int64 * 1)(len(draft_words)), 1) != 0:
-                    raise ValueError("draft: " + (self.lib.sonic_last_error(None) or b"").decode())
-            if cut_row is not None:                      # ... and the cut of a sampled request ("truncation.dispatch": a thread-local, no engine lock)
-                if self.lib.sonic_load_tensor(self.engine.h, b"truncation.dispatch", _p(cut_row), 0, (C.c_int64 * 1)(3), 1) != 0:
-                    raise ValueError("sampling: " + (self.lib.sonic_last_error(None) or b"").decode())
-            rc = submit(self.h, _p(pcm), _p(offs), ring_arr, _p(start), _p(n), len(req.windows), _p(prompt), len(prompt), int(req.max_new), *tail)
+            rc = self.lib.sonic_dispatch_submit(self.h, C.byref(r), C.byref(t))
             if rc != 0 and (req.bias or req.sampling or req.grammar or req.draft):
+                # a refused value is the caller's mistake: its message starts with the value's name (csrc/dispatch.cpp sonic_dispatch_submit)
                 msg = (self.lib.sonic_last_error(None) or b"").decode()
-                if "truncation" in msg or "request_bias" in msg or "sonic_dispatch_submit_bias" in msg or "sampling" in msg or "sonic_dispatch_submit_sampled" in msg or "grammar" in msg or "draft" in msg:
+                if msg.startswith(tuple(v.lead + ":" for v in reqvalues.VALUES) + ("truncation:",)):
                     raise ValueError(msg)
             if rc != 0:
                 raise RuntimeError("ASR engine failed" if rc not in (1,) else "ASR engine is closed or the request is malformed")

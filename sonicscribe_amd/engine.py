@@ -23,7 +23,7 @@ MODE_NATIVE, MODE_INT8, MODE_F16, MODE_F32 = 0, 1, 2, 3
 DTYPE_F32, DTYPE_BF16, DTYPE_I32 = 0, 1, 2
 SONIC_ERR_MISMATCH, SONIC_ERR_UNSUPPORTED = 4, 5
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 class SonicDims(C.Structure):
@@ -47,6 +47,23 @@ class SonicTimings(C.Structure):
         ("host_prefill_enqueue_ms", C.c_float), ("host_decode_launch_ms", C.c_float), ("host_decode_wait_ms", C.c_float), ("host_decode_launches", C.c_int32),
         ("decode_lookahead", C.c_int32), ("decode_launches_per_layer", C.c_int32),
     ]
+
+
+class DispatchRequest(C.Structure):
+    """sonic_dispatch_request: one request as sonic_dispatch_submit takes it.  A fresh record is all-zero - a request that brings no value of its own - with `size` set"""
+    _fields_ = [
+        ("size", C.c_int64),
+        ("host_pcm", C.c_void_p), ("host_off", C.c_void_p), ("rings", C.c_void_p), ("ring_start", C.c_void_p), ("ring_n", C.c_void_p), ("W", C.c_int32),
+        ("prompt_ids", C.c_void_p), ("prompt_len", C.c_int32), ("max_new", C.c_int32),
+        ("seq_ids", C.c_void_p), ("seq_off", C.c_void_p), ("bias", C.c_void_p), ("n_seq", C.c_int32),
+        ("sampled", C.c_int32), ("temperature", C.c_float), ("seed", C.c_uint64),
+        ("cut", C.c_int32), ("top_k", C.c_float), ("top_p", C.c_float), ("min_p", C.c_float),
+        ("grammar_id", C.c_int32),
+        ("draft_ids", C.c_void_p), ("n_draft", C.c_int32),
+    ]
+
+    def __init__(self, **kw):
+        super().__init__(size=C.sizeof(DispatchRequest), **kw)
 
 
 # Every export of include/sonic_hip.h: name -> (return type, argument types).  The one place the binding states the C signatures; tests/test_binding_signatures.py
@@ -115,7 +132,7 @@ SIGNATURES = {
     "sonic_runtime_info": (I, [I, ip, ip, ip]),
     "sonic_engine_info": (I, [vp] + [ip] * 4 + [vpp]),
     "sonic_dispatch_create": (I, [vp, I, vp, I, I, vpp]),
-    "sonic_dispatch_submit": (I, [vp] * 6 + [I, vp, I, I, i64p]),
+    "sonic_dispatch_submit": (I, [vp, C.POINTER(DispatchRequest), i64p]),
     "sonic_dispatch_cancel": (I, [vp, I64]),
     "sonic_dispatch_next": (I, [vp, I, i64p, ip, vp, I, ip, S, I]),
     "sonic_dispatch_stats": (I, [vp, i64p, i64p, ip, ip]),
@@ -149,10 +166,8 @@ SIGNATURES = {
     "sonic_test_rope_append": (I, [vp] * 7 + [I] * 7 + [vp] * 4),
     "sonic_test_rope_enc": (I, [vp, vp] + [I] * 6 + [vp]),
     "sonic_set_request_bias": (I, [vp] * 5 + [I]),
-    "sonic_dispatch_submit_bias": (I, [vp] * 6 + [I, vp, I, I, vp, vp, vp, I, i64p]),
     "sonic_test_greedy_bias": (I, [vp, vp] + [I] * 4 + [vp, I, vp, F, I, vp, I] + [vp] * 8),
     "sonic_set_request_sampling": (I, [vp, vp, vp, I]),
-    "sonic_dispatch_submit_sampled": (I, [vp] * 6 + [I, vp, I, I, F, U64, vp, vp, vp, I, i64p]),
     "sonic_test_greedy_sample": (I, [vp, vp] + [I] * 4 + [vp, I, vp, F, I, vp, I] + [vp] * 12),
     "sonic_test_decode_i8_norm": (I, [vp] * 5 + [F] + [vp] * 3 + [I] * 6 + [vp] * 7),
     "sonic_test_decode_i8_swiglu": (I, [vp] * 4 + [I] * 5 + [vp] * 7),
@@ -984,14 +999,6 @@ def pack_request_draft(drafts):
     if ids.size and (ids.min() < -2 ** 31 or ids.max() >= 2 ** 31):      # (what the ids may be is the library's to say: vocabulary, EOS ids, the audio placeholder)
         raise ValueError("request_draft: token ids must be int32 values")
     return np.ascontiguousarray(np.concatenate([[len(ds)], off, ids]), dtype=np.int32)
-
-
-def pack_dispatch_draft(draft):
-    """one request's draft -> the int32 words sonic_load_tensor "draft.dispatch" takes: n | ids"""
-    ids = np.asarray(list(draft), dtype=np.int64).reshape(-1)
-    if ids.size and (ids.min() < -2 ** 31 or ids.max() >= 2 ** 31):
-        raise ValueError("draft: token ids must be int32 values")
-    return np.ascontiguousarray(np.concatenate([[ids.size], ids]), dtype=np.int32)
 
 
 def pack_request_sampling(values):

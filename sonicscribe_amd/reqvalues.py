@@ -11,19 +11,20 @@ from collections import namedtuple
 # setter:  the method of a handle that arms the values of its next prefill
 # off:     the refusal of a request that brings the value to handles without the option
 # on:      (the request's value, a handle) -> the value as that handle takes it
-ReqValue = namedtuple("ReqValue", "attr option keyword setter off on")
+# lead:    what the native dispatcher's refusals of the value start with, ahead of a colon (csrc/dispatch.cpp sonic_dispatch_submit)
+ReqValue = namedtuple("ReqValue", "attr option keyword setter off on lead")
 
 # in the order every site arms them and states their keywords
 VALUES = (
     ReqValue("bias", "request_bias", "request_bias", "set_request_bias",
-             "a sequence bias needs the engine option request_bias on every handle (ASRModel(request_bias=True))", lambda table, engine: table),
+             "a sequence bias needs the engine option request_bias on every handle (ASRModel(request_bias=True))", lambda table, engine: table, "request_bias"),
     ReqValue("sampling", "sampling", "request_sampling", "set_request_sampling",
-             "a temperature needs the engine option sampling on every handle (ASRModel(sampling=True))", lambda pair, engine: pair),      # ((t, seed), or (t, seed, top_k, top_p, min_p): passed through unchanged)
+             "a temperature needs the engine option sampling on every handle (ASRModel(sampling=True))", lambda pair, engine: pair, "sampling"),      # ((t, seed), or (t, seed, top_k, top_p, min_p): passed through unchanged; the cut's refusals start with "truncation")
     # (a grammar.CompiledGrammar holds a device handle per weight owner: the one that serves `engine`; None: a free request)
     ReqValue("grammar", "grammar", "request_grammar", "set_request_grammar",
-             "a grammar needs the engine option grammar on every handle (ASRModel(token_logprobs=True, grammar=True))", lambda g, engine: None if g is None else g.on(engine)),
+             "a grammar needs the engine option grammar on every handle (ASRModel(token_logprobs=True, grammar=True))", lambda g, engine: None if g is None else g.on(engine), "grammar"),
     ReqValue("draft", "draft_verify", "request_draft", "set_request_draft",
-             "a draft needs the engine option draft_verify on every handle (ASRModel(draft_verify=True))", lambda ids, engine: ids),
+             "a draft needs the engine option draft_verify on every handle (ASRModel(draft_verify=True))", lambda ids, engine: ids, "draft"),
 )
 DRAFT = VALUES[3]
 

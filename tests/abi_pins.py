@@ -7,8 +7,8 @@ import re
 
 from sonicscribe_amd import engine
 
-ABI_VERSION = 12
-N_EXPORTS = 103
+ABI_VERSION = 13
+N_EXPORTS = 101
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "sonic_hip.h")

@@ -1,5 +1,5 @@
 """The native dispatcher's packers (sonicscribe_amd/csrc/dispatch_pack.h: pure host code) against engine.pack_request_bias and engine.pack_request_draft, the two
-packers of one format, word for word.  A stand-alone C++ program with its own main is built with the address and undefined-behaviour sanitizers and run as a child
+packers of one format, word for word; and its check of a submit's window offsets.  A stand-alone C++ program with its own main is built with the address and undefined-behaviour sanitizers and run as a child
 process: it reads batches from stdin and prints the packed arrays.  Nothing is loaded into this process."""
 import os
 import shutil
@@ -56,6 +56,10 @@ int main() {
             std::vector<const std::vector<int32_t>*> ds;
             for (auto& d : own) ds.push_back(&d);
             line("words", dispatch_pack::pack_drafts(ds));
+        } else if (kind == "offsets") {                         // R = W windows: W + 1 offsets, exactly that many allocated (a read past them is the sanitizer's to report)
+            std::vector<int64_t> off(R + 1);
+            for (auto& x : off) std::cin >> x;
+            printf("ok %d\n", dispatch_pack::offsets_ok(off.data(), R) ? 1 : 0);
         } else {
             return 2;
         }
@@ -75,6 +79,18 @@ DRAFT_BATCHES = {
     "three requests, the first and the last empty": [[], [5, 6, 7], []],
     "one request": [[41, 42]],
     "one request without a draft": [[]],
+}
+
+
+# a submit's host_off -> does the submit take it: 0 == off[0] <= off[1] <= ... <= off[W]
+OFFSETS = {
+    "monotone": ([0, 16000, 16000, 48000], True),
+    "not starting at 0": ([1, 16000, 32000], False),
+    "one decreasing step in the middle": ([0, 32000, 16000, 48000], False),
+    "last entry below an earlier one": ([0, 16000, 32000, 8000], False),
+    "one window": ([0, 16000], True),
+    "one window, decreasing": ([0, -1], False),
+    "one empty window (a ring slice)": ([0, 0], True),
 }
 
 
@@ -137,3 +153,9 @@ def test_every_batch_in_one_run(packer):
     """the program's state does not leak from one batch into the next"""
     text = "".join(_bias_input(b) for b in BIAS_BATCHES.values())
     assert packer(text) == [ln for b in BIAS_BATCHES.values() for ln in _bias_expected(b)]
+
+
+@pytest.mark.parametrize("name", list(OFFSETS))
+def test_window_offsets(packer, name):
+    off, ok = OFFSETS[name]
+    assert packer(f"offsets {len(off) - 1}\n{_words(off)}\n") == [f"ok {int(ok)}"]

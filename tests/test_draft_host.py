@@ -1,4 +1,4 @@
-"""Draft-verified decoding on the host (no device): the packed words of "request_draft" and "draft.dispatch", ASRModel's cut rules and refusals,
+"""Draft-verified decoding on the host (no device): the packed words of "request_draft", ASRModel's cut rules and refusals,
 draft_matched, batch fitting that counts draft tokens (with the stub engines of tests/test_dispatch.py), GatedSessions(cumulative_partials=True) with a stub
 model, and the header: the feature adds no entry point and leaves the ABI version alone."""
 import threading
@@ -27,9 +27,6 @@ def test_packed_words():
         engine.pack_request_draft([])
     with pytest.raises(ValueError, match="int32"):
         engine.pack_request_draft([[2 ** 31]])
-    d = engine.pack_dispatch_draft([8, 9, 10])
-    assert d.dtype == np.int32 and d.tolist() == [3, 8, 9, 10]                               # n | ids
-    assert engine.pack_dispatch_draft([]).tolist() == [0]
 
 
 def test_request_keeps_its_draft():
@@ -254,4 +251,5 @@ def test_cumulative_partials_refusals():
 
 # ------------------------------------------------------------------------------------------ the header
 def test_no_new_entry_point_and_the_same_abi():
-    abi_pins.check_surface(header_strings=("draft_verify", "request_draft", "draft.dispatch", "draft_accepted"))
+    abi_pins.check_surface(names=("sonic_dispatch_submit",), header_strings=("draft_verify", "request_draft", "const int32_t* draft_ids; int32_t n_draft;", "draft_accepted"))
+    assert [f for f, _ in engine.DispatchRequest._fields_][-2:] == ["draft_ids", "n_draft"]

@@ -396,6 +396,7 @@ def test_asrmodel_submit_and_streams(golden):
 def test_dispatcher_and_pipeline_refusals(golden):
     import ctypes as C
     from sonicscribe_amd.dispatch import Dispatcher
+    from sonicscribe_amd.engine import DispatchRequest
     g, segs, prompts, n_new = golden
     ref = [int(t) for t in g["s1_new_ids"]]
     off = make(draft=False)
@@ -406,8 +407,10 @@ def test_dispatcher_and_pipeline_refusals(golden):
             disp.submit([segs[1]], prompts[1], n_new, draft=ref[:3])
         rep = disp.replicas[0]                                                 # ... and the library's own answer, not only the Python check in front of it
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        w = np.asarray([2, 10, 10], np.int32)
-        assert rep.lib.sonic_load_tensor(off.h, b"draft.dispatch", vp(w), 2, (C.c_int64 * 1)(3), 1) == 1
+        pcm = np.ascontiguousarray(segs[1], np.int16); offs = np.array([0, len(pcm)], np.int64); pr = np.ascontiguousarray(prompts[1], np.int32)
+        w = np.asarray([10, 10], np.int32); tk = C.c_int64(0)
+        rec = DispatchRequest(host_pcm=vp(pcm), host_off=vp(offs), W=1, prompt_ids=vp(pr), prompt_len=len(pr), max_new=n_new, draft_ids=vp(w), n_draft=2)
+        assert rep.lib.sonic_dispatch_submit(rep.h, C.byref(rec), C.byref(tk)) == 1
         assert b"option draft_verify is off" in rep.lib.sonic_last_error(None)
         disp.close()
     finally:
@@ -425,5 +428,33 @@ def test_dispatcher_and_pipeline_refusals(golden):
         disp.close()
         with pytest.raises(Exception, match="option draft_verify is on on a handle"):
             Dispatcher([e], slots=[slots], bulk=True, decoders=1)
+    finally:
+        e.close()
+
+
+def test_refused_records_leave_nothing_behind(golden):
+    """every value's option on: three records refused from one thread - each with its own message - leave nothing for the plain request that thread submits next"""
+    import ctypes as C
+    from sonicscribe_amd.dispatch import Dispatcher
+    from sonicscribe_amd.engine import DispatchRequest
+    g, segs, prompts, n_new = golden
+    ref = [int(t) for t in g["s1_new_ids"]]
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    e = make(opts=(("sampling", 1), ("truncation", 1), ("grammar", 1)))
+    try:
+        slots = [e.slot(), e.slot()]
+        disp = Dispatcher([e], slots=[slots], continuous=True, native=True)
+        rep = disp.replicas[0]
+        pcm = np.ascontiguousarray(segs[1], np.int16); offs = np.array([0, len(pcm)], np.int64); pr = np.ascontiguousarray(prompts[1], np.int32)
+        w = np.asarray(ref[:5], np.int32); tk = C.c_int64(0)
+        record = lambda max_new=n_new, **kw: DispatchRequest(host_pcm=vp(pcm), host_off=vp(offs), W=1, prompt_ids=vp(pr), prompt_len=len(pr), max_new=max_new, **kw)
+        for rec, msg in ((record(grammar_id=999), b"grammar: 999 is not a live grammar"),
+                         (record(cut=1, top_k=5, top_p=0.9), b"truncation: the request is not sampled"),
+                         (record(4, draft_ids=vp(w), n_draft=5), b"draft: the draft holds 5 ids, the request's budget of 4 tokens leaves room for 3")):
+            assert rep.lib.sonic_dispatch_submit(rep.h, C.byref(rec), C.byref(tk)) == 1 and msg in rep.lib.sonic_last_error(None), (msg, rep.lib.sonic_last_error(None))
+        plain = disp.submit([segs[1]], prompts[1], n_new).result(timeout=120)
+        assert np.array_equal(plain, ref)                                      # the fixture's solo ids: no grammar, no cut, no draft came along
+        assert rep.free_rows == rep.n_rows and rep.load() == 0
+        disp.close()
     finally:
         e.close()

@@ -229,7 +229,7 @@ def test_model_entry_points_and_streams():
 def test_off_is_off_and_refusals(golden):
     import ctypes as C
     from sonicscribe_amd.dispatch import Dispatcher
-    from sonicscribe_amd.engine import SonicError
+    from sonicscribe_amd.engine import DispatchRequest, SonicError
     from sonicscribe_amd.grammar import CompiledGrammar
     g, segs, prompts, n_new = golden
     ga = grammar_a()
@@ -260,12 +260,9 @@ def test_off_is_off_and_refusals(golden):
         tk = C.c_int64(0)
         pcm = np.ascontiguousarray(segs[0], np.int16); offs = np.array([0, len(pcm)], np.int64); pr = np.ascontiguousarray(prompts[0], np.int32)
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        one = np.zeros(1, np.int32)
-        arm = lambda i: rep.lib.sonic_load_tensor(off.h, b"grammar.dispatch:%d" % i, vp(one), 2, (C.c_int64 * 1)(0), 1)
-        assert arm(da.id) == 0                                                 # armed for this thread's next submit, which refuses it and takes it
-        rc = rep.lib.sonic_dispatch_submit(rep.h, vp(pcm), vp(offs), None, None, None, 1, vp(pr), len(pr), 4, C.byref(tk))
-        assert rc == 1 and b"option grammar is off" in rep.lib.sonic_last_error(None)
-        assert arm(999) == 1 and b"grammar.dispatch: 999 is not a live grammar" in rep.lib.sonic_last_error(None)
+        submit = lambda i: rep.lib.sonic_dispatch_submit(rep.h, C.byref(DispatchRequest(host_pcm=vp(pcm), host_off=vp(offs), W=1, prompt_ids=vp(pr), prompt_len=len(pr),
+                                                                                          max_new=4, grammar_id=i)), C.byref(tk))
+        assert submit(da.id) == 1 and b"option grammar is off" in rep.lib.sonic_last_error(None)      # a live grammar, handles without the option
         disp.close()
         for s in slots:
             s.close()
@@ -281,6 +278,13 @@ def test_off_is_off_and_refusals(golden):
         assert a2 - a1 == 64 * 1024 * 4 + 96 * 8
         with pytest.raises(SonicError, match="token_logprobs cannot be switched off"):
             off.set_option("token_logprobs", 0)
+        slots = [off.slot(), off.slot()]                                       # with the option on, the dispatcher looks the id up on its own weight owner
+        disp = Dispatcher([off], slots=[slots], continuous=True, native=True)
+        rep = disp.replicas[0]
+        assert submit(999) == 1 and b"grammar: 999 is not a live grammar" in rep.lib.sonic_last_error(None)
+        disp.close()
+        for s in slots:
+            s.close()
         # a grammar of another weight owner is refused, by the setter and by the dispatcher
         foreign = other.grammar_create(ga)
         with pytest.raises(SonicError, match="weight owner"):

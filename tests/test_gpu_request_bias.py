@@ -333,7 +333,7 @@ def test_invariance_all_paths():
 def test_off_is_off_and_refusals(golden):
     import ctypes as C
     from sonicscribe_amd.dispatch import Dispatcher
-    from sonicscribe_amd.engine import SonicError
+    from sonicscribe_amd.engine import DispatchRequest, SonicError
     g, segs, prompts, n_new = golden
     off = make(lp=True, bias=False)
     try:
@@ -354,7 +354,8 @@ def test_off_is_off_and_refusals(golden):
         tk = C.c_int64(0)
         pcm = np.ascontiguousarray(segs[0], np.int16); offs = np.array([0, len(pcm)], np.int64); pr = np.ascontiguousarray(prompts[0], np.int32)
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
-        rc = rep.lib.sonic_dispatch_submit_bias(rep.h, vp(pcm), vp(offs), None, None, None, 1, vp(pr), len(pr), 4, vp(i), vp(o), vp(b), 1, C.byref(tk))
+        rec = DispatchRequest(host_pcm=vp(pcm), host_off=vp(offs), W=1, prompt_ids=vp(pr), prompt_len=len(pr), max_new=4, seq_ids=vp(i), seq_off=vp(o), bias=vp(b), n_seq=1)
+        rc = rep.lib.sonic_dispatch_submit(rep.h, C.byref(rec), C.byref(tk))
         assert rc == 1 and b"request_bias" in rep.lib.sonic_last_error(None)
         disp.close()
         for s in slots:

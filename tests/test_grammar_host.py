@@ -165,7 +165,8 @@ def test_abi_surface():
     """the feature adds no entry point (the header, the binding table and exports.map keep their names and the ABI its version: tests/abi_pins.py): a grammar is
     loaded as an int32 tensor and everything else is an option of the handle"""
     abi_pins.check_surface(options=("grammar", "request_grammar_begin", "request_grammar", "hook_grammar_state", "hook_grammar_eos"),
-                           header_strings=("SONIC_DTYPE_I32 = 2", '"grammar:<id>"', '"grammar.hook:<V>"', '"grammar.dispatch:<id>"'))
+                           header_strings=("SONIC_DTYPE_I32 = 2", '"grammar:<id>"', '"grammar.hook:<V>"', "int32_t grammar_id;"), names=("sonic_dispatch_submit",))
+    assert "grammar_id" in [f for f, _ in engine.DispatchRequest._fields_]
     assert engine.DTYPE_I32 == 2
     import test_binding_signatures
     assert test_binding_signatures.mismatches(engine.SIGNATURES) == []

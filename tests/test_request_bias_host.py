@@ -158,8 +158,10 @@ def test_hotword_policy_with_a_stub_tokenizer():
 
 
 def test_abi_surface():
-    abi_pins.check_surface(names=("sonic_set_request_bias", "sonic_dispatch_submit_bias", "sonic_test_greedy_bias"),
+    abi_pins.check_surface(names=("sonic_set_request_bias", "sonic_dispatch_submit", "sonic_test_greedy_bias"),
+                           header_strings=("const int32_t* seq_ids; const int32_t* seq_off; const float* bias; int32_t n_seq;",),      # the dispatcher's way: fields of sonic_dispatch_request
                            engine_methods=("set_request_bias", "test_greedy_bias"))
+    assert [f for f, _ in engine.DispatchRequest._fields_][10:14] == ["seq_ids", "seq_off", "bias", "n_seq"]
     ids, off, b, req = engine.pack_request_bias([None, RequestBias([[[5, 6], 1.0], [[7], 2.0]]), RequestBias(), RequestBias(bad_words_ids=[[9]])])
     assert req.tolist() == [0, 0, 2, 2, 3] and off.tolist() == [0, 2, 3, 4] and ids.tolist() == [5, 6, 7, 9] and b[:2].tolist() == [1.0, 2.0] and np.isneginf(b[2])
 
