@@ -741,7 +741,10 @@ SONIC_API int sonic_bench_gemm(sonic_engine* e, int M, int N, int K, int epi, in
 /* times the decode-step skinny GEMM (variant: 0 LDS-DMA nt, 1 LDS-DMA default policy, 2 registers nt, 3 registers plain, 9 pure-read floor) */
 SONIC_API int sonic_bench_skinny(sonic_engine* e, int M, int N, int K, int variant, int iters, float* us_per_launch);
 /* debug read-back of an internal bf16 activation buffer as fp32 ("prefill_tap" with index = 0 (embeddings) .. dec_layers,
- * "pe", "dx", "dqkv", "dq", "datt", "dact", "enc_x"; "align_probs", "align_matrix": fp32 buffers of the last align run, see sonic_set_forced_ids; "draft_accepted": the accepted counts of the last prefill, see there; "kcache" / "vcache" with index = decoder layer: the KV cache [max_batch][kv heads][max_ctx][head_dim]; "fork_ms", see sonic_load_tensor); tests / diagnostics only */
+ * "pe", "dx", "dqkv", "dq", "datt", "dact", "enc_x"; "align_probs", "align_matrix": fp32 buffers of the last align run, see sonic_set_forced_ids; "draft_accepted": the accepted counts of the last prefill, see there; "kcache" / "vcache" with index = decoder layer: the KV cache [max_batch][kv heads][max_ctx][head_dim]; "fork_ms", see sonic_load_tensor;
+ * mode fp8 (option "fp8_weights"): "fp8_step_builds" (n = 1: token steps built in the fp8 form since the option was set), "fp8_scales" / "fp8_matrix" with index = layer * 4 +
+ * {0 q|k|v, 1 o_proj, 2 gate/up, 3 down_proj} or 4 * dec_layers for the lm_head: the rows' scales, and a prefix of the e4m3 copy as fp32 scale * code, row-major in the
+ * row order of the tiled copy); tests / diagnostics only */
 SONIC_API int sonic_debug_read(sonic_engine* e, const char* name, int index, float* out, int64_t n);
 /* diagnostics: in-kernel timestamps (100 MHz device wall clock) of the decode kernels of one decoder layer, recorded while the option
  * "ktrace" = layer index is set: out[slot][block < 512][8 points], slots 0 qkv, 1 attention, 2 o_proj, 3 gate/up, 4 down */
@@ -756,7 +759,12 @@ SONIC_API int sonic_debug_ktrace(sonic_engine* e, int64_t* out, int64_t n);
  * "top_logprobs" (not an experiment either: the K best alternatives of every step in the same records, see sonic_fetch_logprobs);
  * "forced_parallel", "forced_fanout", "forced_share_prompt", "score_chunk_rows" (not experiments: forced runs as one prefill pass - scoring given transcripts - see sonic_set_forced_ids);
  * "forced_align", "align_head" (not experiments: word timestamps on that pass, see sonic_set_forced_ids);
- * "draft_verify" (not an experiment: a request's draft is verified in its prefill pass, see sonic_set_forced_ids) */
+ * "draft_verify" (not an experiment: a request's draft is verified in its prefill pass, see sonic_set_forced_ids);
+ * "fp8_weights" (not an experiment: mode fp8, DESIGN.md 6.16 - value 1, once, on a finalized bf16 weight owner before its slots exist: every decoder matrix and the
+ * embedding are snapped in place onto a per-row power-of-two-scaled OCP e4m3 grid, the e4m3 copies (one byte per weight, four per row) are added to
+ * sonic_weight_bytes / sonic_memory_info, and token steps of <= 4 rows stream them; refused by name on int8 / fp16 / fp32 handles, on a slot, on an owner with slots,
+ * while the handle has work in hand, and for 0 after 1), "fp8_chain" (0 / 1, only with fp8_weights on, which sets it to 1: 0 runs the snapped model on the default
+ * chains - full batch invariance, no byte saving; with 1 a request's low bits depend on whether its step ran at <= 4 rows, as with "decode_gemv") */
 SONIC_API int sonic_set_option(sonic_engine* e, const char* key, int value);
 
 /* ---- Silero VAD network (silero-vad 5.x / 6.x, 16 kHz branch; csrc/vad.hip, layer table in sonicscribe_amd/vad_net.py) ----

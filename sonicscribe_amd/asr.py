@@ -18,6 +18,7 @@ sessions' decodes in flight (INTEGRATION.md shows the change in transcription_ma
 from __future__ import annotations
 
 import asyncio
+import json
 import math
 import os
 import threading
@@ -128,6 +129,21 @@ def check_share_prompt(share, scoring: bool, mode: str, timestamps: bool) -> boo
     return True
 
 
+def check_fp8_checkpoint(checkpoint_dir) -> None:
+    """mode="fp8" snaps the checkpoint's OWN bfloat16 values (W' is exact in bfloat16), so the mode asks of its checkpoint, ahead of any device,
+    what the other modes find out while loading: ValueError by name when the directory has no config.json, or when that file states a torch_dtype other than
+    bfloat16 (a float16 / float32 checkpoint would be rounded to bfloat16 first, and the snapped model would not be the one the caller quantised in their head)"""
+    path = os.path.join(str(checkpoint_dir), "config.json")
+    if not os.path.isfile(path):
+        raise ValueError(f"mode='fp8' needs a bfloat16 checkpoint to snap: {path} not found")
+    with open(path, "r", encoding="utf-8") as f:
+        cfg = json.load(f)
+    stated = [c.get("torch_dtype", c.get("dtype")) for c in (cfg, cfg.get("text_config") or {}) if isinstance(c, dict)]
+    wrong = [str(t) for t in stated if t is not None and str(t).replace("torch.", "") != "bfloat16"]
+    if wrong:
+        raise ValueError(f"mode='fp8' needs a bfloat16 checkpoint to snap: {path} states torch_dtype {wrong[0]}")
+
+
 def _flatten(windows_per_request):
     """windows per request -> (all windows in a row, req_win: request i owns windows req_win[i] .. req_win[i + 1] - 1), as Engine.transcribe_batch / score_batch take them"""
     segs, req_win = [], [0]
@@ -178,8 +194,14 @@ class ASRModel:
         supported surface: they exist for the test-suite and the benchmark and may change without notice.  `_engine_mode` in particular (an engine.MODE_*
         value in place of the one `mode` selects) is unsupported outside the tests: MODE_F32 has no slots, so it needs slots=1, continuous=False."""
         # -- 1. the arguments, in _REFUSALS' order; no device is touched
-        if mode not in ["native", "int8"]:
-            raise ValueError("mode must be either 'native' or 'int8'")            # asr.py:46-47
+        if mode not in ["native", "int8", "fp8"]:
+            raise ValueError("mode must be either 'native' or 'int8'")            # asr.py:46-47 ("fp8" is this library's third: weight-only e4m3, DESIGN.md 6.16)
+        if mode == "fp8" and _engine_mode is not None:
+            raise ValueError("mode='fp8' is not supported with _engine_mode: it is a bf16 model (engine.MODE_NATIVE) whose decoder weights are snapped to e4m3")
+        if mode == "fp8" and not int((_options or {}).get("fp8_weights", 1)):
+            raise ValueError("mode='fp8' is not supported with _options fp8_weights=0: the mode is that option (fp8_chain=0 runs the snapped model on the default chains)")
+        if mode == "fp8" and _synthetic_seed is None:
+            check_fp8_checkpoint(checkpoint_dir)
         self.mode, self.bulk, self.token_logprobs = mode, bool(bulk), bool(token_logprobs)
         self.sampling, self.grammar, self.draft_verify, self.scoring, self.timestamps = bool(sampling), bool(grammar), bool(draft_verify), bool(scoring), bool(timestamps)
         self.top_logprobs = check_top_logprobs(top_logprobs, token_logprobs, bulk)
@@ -208,8 +230,8 @@ class ASRModel:
             raise RuntimeError(f"HIP device {spec_} not available ({n_dev} visible)")
         self.device_index = self.device_indices[0]
         self.device = f"cuda:{self.device_index}" if len(self.device_indices) == 1 else "cuda:" + ",".join(map(str, self.device_indices))
-        self.model_dtype = "bfloat16" if mode == "native" else "float16"                     # asr.py:61
-        emode = MODE_NATIVE if mode == "native" else MODE_INT8
+        self.model_dtype = "bfloat16" if mode in ("native", "fp8") else "float16"            # asr.py:61
+        emode = MODE_NATIVE if mode in ("native", "fp8") else MODE_INT8      # fp8: a bf16 engine whose option fp8_weights is set first, below
         if _engine_mode is not None:                 # tests only, unsupported (docstring): another kind behind the same façade
             emode = int(_engine_mode)
         self.checkpoint_dir = Path(checkpoint_dir)
@@ -259,6 +281,9 @@ class ASRModel:
         # none take the kernel's branch around the select); grammar; draft_verify.  Only what is on is set: off, nothing changes
         g = self.generation_guards
         options = [(k, int(v)) for k, v in (_options or {}).items()]
+        if mode == "fp8":        # first among the options, on every replica before any slot exists: the weights are snapped once, the slots share them
+            options = [("fp8_weights", 1)] + [kv for kv in options if kv[0] != "fp8_weights"]
+        options.sort(key=lambda kv: kv[0] != "fp8_weights")      # (stable: a caller's fp8_weights goes ahead of its fp8_chain whatever order they came in)
         options += [(k, v) for k, v in (("token_logprobs", int(self.token_logprobs)), ("top_logprobs", self.top_logprobs),
                                         ("generation", (g.repetition_penalty, g.no_repeat_ngram_size, g.suppress_tokens) if g.active else None),
                                         ("request_bias", int(self.request_bias)), ("sampling", int(self.sampling)), ("truncation", int(self.sampling)),
@@ -863,6 +888,9 @@ class ASRModel:
                      "weights_mb": self.model.weight_bytes() / 1024 ** 2 if hasattr(self, "model") else 0.0})
         info.update({"scoring": self.scoring, "grammar": self.grammar, "draft_verify": self.draft_verify, "best_of": self.best_of, "timestamps": self.timestamps,
                      "lm": self.lm is not None, "lm_weight": self.lm_weight if self.lm is not None else 0.0})
+        if self.mode == "fp8" and hasattr(self, "model"):      # mode fp8: what the e4m3 copies add to weights_mb, and the token steps the dispatcher's handles built in the fp8 form
+            handles = list(self.models) + [s for ss in self.__dict__.get("_slot_engines", []) for s in ss]
+            info.update({"fp8_weights_mb": self.model.fp8_info()["extra_weight_bytes"] / 1024 ** 2, "fp8_step_builds": sum(h.fp8_info()["step_builds"] for h in handles)})
         g = self.__dict__.get("generation_guards")
         if g is not None:                            # the logits processors in force: the checkpoint's generation_config.json unless the constructor overrode it
             info.update(g.as_dict())

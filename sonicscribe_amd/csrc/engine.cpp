@@ -404,6 +404,7 @@ extern "C" int sonic_slot_create(sonic_engine* parent, sonic_engine** out) {
     e->opts = root->opts; e->opt_no_graph = root->opt_no_graph; e->opt_no_fused_rope = root->opt_no_fused_rope; e->opt_no_gelu_lut = root->opt_no_gelu_lut;
     e->opt_i8_defer_thr = root->opt_i8_defer_thr; e->opt_i8_no_xq = root->opt_i8_no_xq; e->opt_i8_no_lnq = root->opt_i8_no_lnq; e->opt_i8_no_qkv_fuse = root->opt_i8_no_qkv_fuse;
     e->opt_decode_chunk = root->opt_decode_chunk; e->opt_no_pre_norm = root->opt_no_pre_norm; e->opt_decode_gemv = root->opt_decode_gemv; e->opt_fetch_stream = root->opt_fetch_stream;
+    e->opt_fp8_weights = root->opt_fp8_weights; e->opt_fp8_chain = root->opt_fp8_chain; e->embed8 = root->embed8; e->embed_sc = root->embed_sc;      // mode fp8: the owner's e4m3 copies (the layers' ride in `dec`)
     if ((s = gen_inherit(e, root)) != SONIC_OK) { g_create_err = e->err; sonic_destroy(e); return s; }      // the owner's generation options, with their buffers
     e->weight_bytes = 0; e->finalized = true; e->owner = root;
     root->slots.push_back(e);

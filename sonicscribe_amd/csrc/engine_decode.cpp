@@ -93,13 +93,15 @@ void launch_o_gu(sonic_engine* e, int form, const OGuChain& c, int M, int K, int
 
 // The form of the 16-bit token step for R rows, decided once: the layer loop and step_launches_per_layer read it.
 //   gemv        1 - 4 rows, opt-in (decode_gemv): the GEMV chain
+//   fp8         1 - 4 rows, mode fp8 with its chain on (fp8_weights / fp8_chain) and every shape eligible: the GEMV chain on the e4m3 copies - the same five launches,
+//               the same bits as `gemv` on the snapped weights.  Where it is not eligible the snapped model runs the forms below
 //   fuse_gu / fuse_o   the fused gate/up kernel, and the fused o_proj in front of it, take the shape (launch_o_gu's forms)
 //   pre         <= 2 rows (the B = 1 call shape of BASELINE configs 1 and 5; round 6): no standalone add+RMSNorm launch behind down_proj - the next q|k|v projection
 //               (and, behind the last layer, the lm_head) sums the slabs, adds the residual and normalises its rows itself (skinny_xs_kernel<.., PRE>, the same
 //               arithmetic statement by statement: same bits).  down_proj then writes its slabs to slab2 (the consumer writes slab while other blocks of it still
 //               read) and the residual stream alternates between sx and sx2
 //   split_norm  33 .. 64 rows, on request or inside a continuous loop's graph (gu64_split_norm): OGU_SPLIT_NORM.  Never with pre (rows), so its rows are in sx
-struct StepForm { bool gemv, pre, fuse_o, fuse_gu, split_norm; };
+struct StepForm { bool gemv, fp8, pre, fuse_o, fuse_gu, split_norm; };
 static StepForm step_form(sonic_engine* e, int R) {
     const sonic_dims& d = e->d;
     const int D = d.dec_d;
@@ -109,6 +111,8 @@ static StepForm step_form(sonic_engine* e, int R) {
     StepForm f{};
     f.gemv = e->opt_decode_gemv && R <= GEMV_MAX_ROWS && gu8 && gemv_eligible(R, e->qkvN, D, GEMV_SLAB_NORM) && gemv_eligible(R, D, e->QD, GEMV_RESID) &&
              gemv_eligible(R, 2 * d.dec_ff, D, GEMV_SWIGLU_NORM) && gemv_eligible(R, D, d.dec_ff, GEMV_RESID) && gemv_eligible(R, d.vocab, D, GEMV_SLAB_NORM);
+    f.fp8 = fp8_chain_on(e) && R <= GEMV_MAX_ROWS && gu8 && e->dec[0].gu8 && e->embed8 && gemv_fp8_eligible(R, e->qkvN, D, GEMV_SLAB_NORM) && gemv_fp8_eligible(R, D, e->QD, GEMV_RESID) &&
+            gemv_fp8_eligible(R, 2 * d.dec_ff, D, GEMV_SWIGLU_NORM) && gemv_fp8_eligible(R, D, d.dec_ff, GEMV_RESID) && gemv_fp8_eligible(R, d.vocab, D, GEMV_SLAB_NORM);
     f.fuse_gu = gu8 && skinny_gu_eligible(R, 2 * d.dec_ff, D);
     f.fuse_o = f.fuse_gu && skinny_o_eligible(R, D, e->QD);
     f.pre = f.fuse_o && !e->opt_no_pre_norm && skinny_pre_eligible(R, e->qkvN, D) && skinny_pre_eligible(R, d.vocab, D) && D % 8 == 0;
@@ -116,22 +120,24 @@ static StepForm step_form(sonic_engine* e, int R) {
     return f;
 }
 // 1 - 4 rows, opt-in (gemv.hip): q|k|v (norm inside) -> attention -> o_proj (+ residual) -> gate/up (norm inside, SwiGLU) -> down_proj (+ residual); lm_head (norm inside)
-static void decode_step_gemv(sonic_engine* e, int R, bool dump) {
+// fp8: the same chain on the e4m3 copies and the rows' scales (gemv_fp8.hip; mode fp8)
+static void decode_step_gemv(sonic_engine* e, int R, bool dump, bool fp8) {
     const sonic_dims& d = e->d;
     const int D = d.dec_d, mpad = ((R + 15) / 16) * 16, dt = e->dt;
-    auto gv = [&](int mode, const bf16_t* X, long ldx, const bf16_t* W, int N, int K, const float* nw, float* P, bf16_t* resid, bf16_t* act) {
+    auto gv = [&](int mode, const bf16_t* X, long ldx, const bf16_t* W, const unsigned char* W8, const float* sc, int N, int K, const float* nw, float* P, bf16_t* resid, bf16_t* act) {
         GemvArgs g{}; g.X = X; g.ldx = ldx; g.W = W; g.M = R; g.N = N; g.K = K; g.dt = dt; g.norm_w = nw; g.eps = d.dec_rms_eps; g.P = P; g.resid = resid; g.ldr = D; g.act = act;
-        launch_gemv(g, mode, e->st);
+        if (fp8) launch_gemv_fp8(GemvFp8Args{g, W8, sc}, mode, e->st);
+        else launch_gemv(g, mode, e->st);
     };
     for (int l = 0; l < d.dec_layers; ++l) {
         const DecLayerW& L = e->dec[l];
-        gv(GEMV_SLAB_NORM, e->sx, D, L.wqkv_t, e->qkvN, D, L.ln1, e->slab, nullptr, nullptr);
+        gv(GEMV_SLAB_NORM, e->sx, D, L.wqkv_t, L.qkv8, L.qkv_sc, e->qkvN, D, L.ln1, e->slab, nullptr, nullptr);
         launch_decode_attn(step_attn_args(e, l, 1, mpad, dt), R, e->st);
-        gv(GEMV_RESID, e->satt, e->QD, L.wo_t, D, e->QD, nullptr, nullptr, e->sx, nullptr);
-        gv(GEMV_SWIGLU_NORM, e->sx, D, L.wgu_t8, 2 * d.dec_ff, D, L.ln2, nullptr, nullptr, e->sact);
-        gv(GEMV_RESID, e->sact, d.dec_ff, L.wdown_t, D, d.dec_ff, nullptr, nullptr, e->sx, nullptr);
+        gv(GEMV_RESID, e->satt, e->QD, L.wo_t, L.o8, L.o_sc, D, e->QD, nullptr, nullptr, e->sx, nullptr);
+        gv(GEMV_SWIGLU_NORM, e->sx, D, L.wgu_t8, L.gu8, L.gu_sc, 2 * d.dec_ff, D, L.ln2, nullptr, nullptr, e->sact);
+        gv(GEMV_RESID, e->sact, d.dec_ff, L.wdown_t, L.down8, L.down_sc, D, d.dec_ff, nullptr, nullptr, e->sx, nullptr);
     }
-    gv(GEMV_SLAB_NORM, e->sx, D, e->embed_t, d.vocab, D, e->dec_nw, e->lslab, nullptr, nullptr);
+    gv(GEMV_SLAB_NORM, e->sx, D, e->embed_t, e->embed8, e->embed_sc, d.vocab, D, e->dec_nw, e->lslab, nullptr, nullptr);
     GreedyArgs g = greedy_args(e, R, dump);
     g.ksplit = 1;
     lm_step(e, R);                                                  // option lm: the rows' vectors right ahead of the launch that adds them
@@ -197,8 +203,9 @@ static void decode_step(sonic_engine* e, int R, bool dump) {
     const int D = d.dec_d, mpad = ((R + 15) / 16) * 16, dt = e->dt;
     const StepForm f = step_form(e, R);
     const int ogu = !f.fuse_gu ? OGU_UNFUSED : !f.fuse_o ? OGU_HALF_FUSED : f.split_norm ? OGU_SPLIT_NORM : OGU_FUSED;
-    e->step_launches_per_layer = f.gemv ? 5 : !f.fuse_o ? 8 : f.pre ? 5 : f.split_norm ? 7 : 6;
-    if (f.gemv) { decode_step_gemv(e, R, dump); return; }
+    e->step_launches_per_layer = (f.gemv || f.fp8) ? 5 : !f.fuse_o ? 8 : f.pre ? 5 : f.split_norm ? 7 : 6;
+    if (f.fp8) { ++e->fp8_step_builds; decode_step_gemv(e, R, dump, true); return; }
+    if (f.gemv) { decode_step_gemv(e, R, dump, false); return; }
     if (D > 8192) launch_rmsnorm(e->sx, e->dec[0].ln1, e->shn, R, D, d.dec_rms_eps, nullptr, e->st, dt);   // else: done by the greedy kernel of the previous step
     bf16_t* resid = e->sx;                               // where the residual rows live right now
     int ks, ks_down = 0;

@@ -43,7 +43,9 @@ struct EncLayerW { float *ln1w, *ln1b, *bqkv, *bo, *ln2w, *ln2b, *b1, *b2; bf16_
 #define KT_SLOT_BLOCKS 512                                   // "ktrace" diagnostics: blocks recorded per kernel slot, 8 timestamps each
 struct DecLayerW { float *ln1, *ln2; bf16_t *wqkv, *wo, *wgu, *wdown;          // row-major (prefill GEMM)
                    bf16_t *wqkv_t, *wo_t, *wgu_t, *wgu_t8, *wdown_t;                    // fragment-tiled copies (decode skinny GEMM)
-                   QW qqkv, qo, qgu, qdown; };
+                   QW qqkv, qo, qgu, qdown;
+                   // mode fp8 (option fp8_weights): the e4m3 copies beside the bf16 tiles (gu8: of wgu_t8, or of wgu_t where that is the layer's copy) and the rows' scales [N]
+                   unsigned char *qkv8 = nullptr, *o8 = nullptr, *gu8 = nullptr, *down8 = nullptr; float *qkv_sc = nullptr, *o_sc = nullptr, *gu_sc = nullptr, *down_sc = nullptr; };
 
 // SONIC_MODE_F32 (test only, f32kind.hip): fp32 weights as loaded (torch Linear layout, nothing packed but the conv taps) and fp32 activation buffers
 struct F32EncL { float *ln1w, *ln1b, *wq, *bq, *wk, *wv, *bv, *wo, *bo, *ln2w, *ln2b, *w1, *b1, *w2, *b2; };
@@ -196,6 +198,12 @@ struct sonic_engine {
     int opt_f32_synth_bf16 = 0;    // SONIC_MODE_F32: sonic_load_synthetic writes the bf16-rounded values (the weights a bf16 engine gets from the same seed) as fp32
     int opt_decode_gemv = 0;       // 1: token steps of <= 4 rows run the GEMV chain (gemv.hip: five launches per layer, no MFMA tiles); opt-in - another summation order than the
                                    // MFMA chain, so a request's low bits then depend on whether its step had <= 4 rows.  Measured slower than the MFMA chain (profiles/round6_gemv_ab.txt): an experiment, off
+    // mode fp8.  opt_fp8_weights: the owner's decoder matrices and embedding were snapped onto their e4m3 grids in place (W'), the e4m3 copies exist
+    // (DecLayerW, embed8 / embed_sc) - set once on a bf16 owner before its slots exist (they copy both values and share the copies), never cleared.  opt_fp8_chain
+    // (switched on with it; the A/B): token steps of <= 4 rows stream the e4m3 copies (gemv_fp8.hip) where every shape is eligible - the bits of the bf16 GEMV chain
+    // on W', i.e. decode_gemv's caveat: another summation order than the MFMA chain.  fp8_step_builds: token steps this handle built in that form since the option was set
+    int opt_fp8_weights = 0, opt_fp8_chain = 0; int64_t fp8_step_builds = 0;
+    unsigned char* embed8 = nullptr; float* embed_sc = nullptr;
     int opt_no_pre_norm = 0;       // 1: never the PRE form of the <= 2-row decode step (standalone add+RMSNorm launches as for more rows; A/B - same bits)
     int opt_decode_chunk = 2;      // token steps per captured graph = granularity of the early-stop check (sonic_set_option "decode_chunk")
     int opt_token_logprobs = 0;    // 1: every greedy launch also writes log_softmax(logits)[token] to out_lp (greedy_kernel<T, true>); set on the owner before
@@ -465,6 +473,7 @@ int resample_bank_get(sonic_engine* root, int64_t in_rate, int64_t out_rate, RsB
 void resample_release(sonic_engine* e);
 void async_shutdown(sonic_engine* e);
 int fetch_locked(sonic_engine* e, int32_t* out_ids, int out_ld, int32_t* out_len, float* step_logits, float* out_lp = nullptr);
+static inline bool fp8_chain_on(const sonic_engine* e) { return e->opt_fp8_weights && e->opt_fp8_chain; }
 void drop_graphs(sonic_engine* e);                  // the captured decode chunks of this handle (engine_options.cpp)
 int read_back_16(sonic_engine* e, const bf16_t* d, float* h, size_t n);   // n elements of a 16-bit device buffer -> fp32 on the host, through a temporary (engine_hooks.cpp; sonic_debug_read)
 

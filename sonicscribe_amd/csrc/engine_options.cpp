@@ -130,6 +130,67 @@ static int opt_fetch_stream(sonic_engine* e, const char* key, int value) {
     e->opt_fetch_stream = value ? 1 : 0; return SONIC_OK;
 }
 extern "C" int engine_fetch_stream_on(sonic_engine* e) { return e && e->opt_fetch_stream ? 1 : 0; }      // (pipeline.cpp: the order of chunk and fetch at a hand-over)
+// mode fp8: matrix m of the snapped set - layer * 4 + {0 q|k|v, 1 o_proj, 2 gate/up, 3 down_proj}, 4 * layers = the tied lm_head - as the bf16 tiles,
+// the e4m3 copy and the scales' slots of this handle with its shape; false past the last one
+struct Fp8Mat { bf16_t* wt; unsigned char** w8; float** sc; int N, K; };
+static bool fp8_mat(sonic_engine* e, int m, Fp8Mat* out) {
+    const sonic_dims& d = e->d;
+    if (m < 0 || m > 4 * d.dec_layers) return false;
+    if (m == 4 * d.dec_layers) { *out = Fp8Mat{e->embed_t, &e->embed8, &e->embed_sc, d.vocab, d.dec_d}; return true; }
+    DecLayerW& L = e->dec[m / 4];
+    switch (m % 4) {
+        case 0: *out = Fp8Mat{L.wqkv_t, &L.qkv8, &L.qkv_sc, e->qkvN, d.dec_d}; break;
+        case 1: *out = Fp8Mat{L.wo_t, &L.o8, &L.o_sc, d.dec_d, e->QD}; break;
+        case 2: *out = Fp8Mat{L.wgu_t8 ? L.wgu_t8 : L.wgu_t, &L.gu8, &L.gu_sc, 2 * d.dec_ff, d.dec_d}; break;
+        default: *out = Fp8Mat{L.wdown_t, &L.down8, &L.down_sc, d.dec_d, d.dec_ff}; break;
+    }
+    return true;
+}
+// fp8_weights = 1: every decoder matrix and the embedding of a finalized bf16 weight owner are snapped onto their rows' e4m3 grids in place (fp8_snap_kernel), the
+// e4m3 copies and scales are allocated beside them (N K + 4 N bytes each, part of weight_bytes and of sonic_memory_info), the graphs are dropped and fp8_chain goes
+// on.  Once, before the owner's slots exist (they share the weights and copy both values); 0 after 1 is refused: the weights cannot be un-snapped
+static int opt_fp8_weights(sonic_engine* e, const char* key, int value) {
+    if (e->i8 || e->f32 || e->dt != DT_BF16) return fail(e, SONIC_ERR_INVALID, "%s: only on a bf16 handle (this one is of the %s kind): the e4m3 grid is snapped into bf16 weights", key, e->i8 ? "int8" : e->f32 ? "fp32" : "fp16");
+    if (e->owner) return fail(e, SONIC_ERR_INVALID, "%s: this handle is a slot: set the option on the weight owner before its slots are created (they share its weights)", key);
+    if (!e->slots.empty()) return fail(e, SONIC_ERR_INVALID, "%s: the owner already has %d slot(s): set the option before sonic_slot_create (the slots share the weights and copy the option)", key, (int)e->slots.size());
+    TRY(gen_busy(e, key));      // an asynchronous run, a continuous loop, a batch in hand: they read the weights
+    if (!value) return e->opt_fp8_weights ? fail(e, SONIC_ERR_INVALID, "%s cannot be switched off: the weights were snapped in place and cannot be un-snapped (option fp8_chain = 0 runs the snapped model on the default chains)", key) : (int)SONIC_OK;
+    if (e->opt_fp8_weights) return SONIC_OK;
+    if (!e->finalized) return fail(e, SONIC_ERR_INVALID, "%s: the weights are not finalized", key);
+    const int n_mat = 4 * e->d.dec_layers + 1;
+    Fp8Mat mt{};
+    for (int m = 0; m < n_mat; ++m) {
+        fp8_mat(e, m, &mt);
+        if (!mt.wt) return fail(e, SONIC_ERR_INVALID, "%s: decoder matrix %d has no fragment-tiled copy", key, m);
+        if (mt.N % 16 || mt.K % 64) return fail(e, SONIC_ERR_INVALID, "%s: decoder matrix %d is %d x %d: the e4m3 tiling needs rows in 16s and K in 64s", key, m, mt.N, mt.K);
+    }
+    for (const DecLayerW& L : e->dec)
+        if (L.wqkv || L.wo || L.wgu || L.wdown) return fail(e, SONIC_ERR_INVALID, "%s: this handle keeps row-major decoder weights (SONIC_KEEP_ROWMAJOR), which the snap does not rewrite", key);
+    HIPC(e, hipSetDevice(e->device));
+    for (int m = 0; m < n_mat; ++m) {      // everything is allocated before anything is rewritten: out of memory leaves the bf16 model as it was
+        fp8_mat(e, m, &mt);
+        if (!*mt.w8) TRY(dalloc(e, mt.w8, (size_t)mt.N * mt.K, false));
+        if (!*mt.sc) TRY(dalloc(e, mt.sc, (size_t)mt.N, false));
+    }
+    for (int m = 0; m < n_mat; ++m) {
+        fp8_mat(e, m, &mt);
+        launch_fp8_snap(mt.wt, *mt.w8, *mt.sc, m == n_mat - 1 ? e->embed : nullptr, mt.N, mt.K, e->st);      // the token lookup's row-major embedding takes the lm_head's W' too
+        e->weight_bytes += (int64_t)mt.N * mt.K + (int64_t)mt.N * 4;
+    }
+    HIPC(e, hipGetLastError());
+    HIPC(e, stream_sync(e));
+    e->opt_fp8_weights = 1; e->opt_fp8_chain = 1; e->fp8_step_builds = 0;
+    drop_graphs(e);
+    return SONIC_OK;
+}
+// fp8_chain (the A/B of mode fp8): 1 = token steps of <= 4 rows stream the e4m3 copies, 0 = the snapped model on the default chains (full batch invariance, no byte saving)
+static int opt_fp8_chain(sonic_engine* e, const char* key, int value) {
+    if (!e->opt_fp8_weights) return fail(e, SONIC_ERR_INVALID, "%s: option fp8_weights must be on first (sonic_set_option(e, \"fp8_weights\", 1) on the weight owner)", key);
+    if (value != 0 && value != 1) return fail(e, SONIC_ERR_INVALID, "%s: %d is neither 0 nor 1", key, value);
+    if (e->svc_on) return fail(e, SONIC_ERR_INVALID, "%s: this handle is decoding continuously (sonic_service_end first)", key);
+    e->opt_fp8_chain = value; drop_graphs(e);
+    return SONIC_OK;
+}
 // the two knobs that do device work
 static int opt_ktrace(sonic_engine* e, const char*, int value) {              // diagnostics: record in-kernel timestamps of decoder layer `value` (-1: off); sonic_debug_ktrace reads them
     HIPC(e, hipSetDevice(e->device));
@@ -221,6 +282,8 @@ static const OptRow OPTIONS[] = {
     {"align_head", APPLY(opt_align_head)},
     {"draft_verify", APPLY(opt_draft_verify)},
     {"fetch_stream", APPLY(opt_fetch_stream)},
+    {"fp8_weights", APPLY(opt_fp8_weights)},
+    {"fp8_chain", APPLY(opt_fp8_chain)},
     {"score_chunk_rows", ENG(opt_score_chunk_rows), false, [](int v) { return v < 16 ? 16 : (v > 4096 ? 4096 : v); }},   // score rows per lm_head GEMM + row-kernel launch (the buffer follows at the next parallel run)
     {"ktrace", APPLY(opt_ktrace)},
     {"inject_dev_err", APPLY(opt_inject_dev_err)},
@@ -315,6 +378,28 @@ extern "C" int sonic_debug_read(sonic_engine* e, const char* name, int index, fl
         if (n != 1) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
         out[0] = 0.f;
         if (e->fork_timed) { HIPC(e, stream_sync(e)); HIPC(e, hipEventElapsedTime(&out[0], e->fork_ev[0], e->fork_ev[1])); }
+        return SONIC_OK;
+    }
+    if (!strcmp(name, "fp8_step_builds")) {         // token steps this handle built in the fp8 form since option fp8_weights was set (exact in fp32 below 2^24)
+        if (n != 1) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
+        out[0] = (float)e->fp8_step_builds;
+        return SONIC_OK;
+    }
+    if (!strcmp(name, "fp8_scales") || !strcmp(name, "fp8_matrix")) {      // mode fp8, matrix `index` (fp8_mat): its rows' scales, or a prefix of its e4m3 copy as fp32 s q, row-major in the tiled copy's row order
+        Fp8Mat mt{};
+        if (!e->opt_fp8_weights) return fail(e, SONIC_ERR_INVALID, "%s: option fp8_weights is off on this handle", name);
+        if (!fp8_mat(e, index, &mt)) return fail(e, SONIC_ERR_INVALID, "index %d out of range for buffer %s (0 .. %d)", index, name, 4 * e->d.dec_layers);
+        const bool sc = name[4] == 's';
+        if (n < 0 || (size_t)n > (sc ? (size_t)mt.N : (size_t)mt.N * mt.K)) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
+        if (n == 0) return SONIC_OK;
+        if (sc) { HIPC(e, stream_sync(e)); HIPC(e, d2h(e, out, *mt.sc, (size_t)n * 4)); return SONIC_OK; }
+        float* tmp = nullptr;
+        HIPC(e, hipMalloc((void**)&tmp, (size_t)n * 4));
+        launch_fp8_read(*mt.w8, *mt.sc, tmp, mt.K, (long)n, e->st);
+        hipError_t r = stream_sync(e);
+        if (r == hipSuccess) r = d2h(e, out, tmp, (size_t)n * 4);
+        (void)hipFree(tmp);
+        HIPC(e, r);
         return SONIC_OK;
     }
     for (const DbgRow& r : DEBUG_BUFS) {

@@ -123,7 +123,7 @@ extern "C" int sonic_service_begin(sonic_engine* e) {
     req_rows_free(e);                                       // the pool starts with free rows
     hipGraphExec_t gx = nullptr;                            // the chunk graphs exist before the first splice: nothing captures on this stream later
     if (e->Bm >= 2 && !e->i8) TRY(chunk_graph(e, 2, e->opt_decode_chunk > 0 ? e->opt_decode_chunk : 1, &gx, true));   // a pool with at most two occupied rows (round 6: five launches per layer)
-    if (e->Bm >= 4 && !e->i8 && e->opt_decode_gemv) TRY(chunk_graph(e, 4, e->opt_decode_chunk > 0 ? e->opt_decode_chunk : 1, &gx, true));   // ... four, on the GEMV chain (opt-in)
+    if (e->Bm >= 4 && !e->i8 && (e->opt_decode_gemv || fp8_chain_on(e))) TRY(chunk_graph(e, 4, e->opt_decode_chunk > 0 ? e->opt_decode_chunk : 1, &gx, true));   // ... four, on the GEMV chain (opt-in) or the fp8 chain (mode fp8)
     for (int R = 16; ; R += 16) {                           // one per 16 rows (sonic_service_step runs as many rows as are occupied)
         const int r = R < e->Bm ? R : e->Bm;
         TRY(chunk_graph(e, r, e->opt_decode_chunk > 0 ? e->opt_decode_chunk : 1, &gx, true));
@@ -211,7 +211,7 @@ extern "C" int sonic_service_step(sonic_engine* e, int n_chunks, int rows, int32
     int R = rows <= 0 || rows > e->Bm ? e->Bm : (rows + 15) / 16 * 16;
     if (R > e->Bm) R = e->Bm;
     if (rows > 0 && rows <= 2 && e->Bm >= 2 && !e->i8) R = 2;      // one or two sessions' rows: the <= 2-row step (same bits per row as any other row count)
-    else if (rows > 0 && rows <= 4 && e->Bm >= 4 && !e->i8 && e->opt_decode_gemv) R = 4;
+    else if (rows > 0 && rows <= 4 && e->Bm >= 4 && !e->i8 && (e->opt_decode_gemv || fp8_chain_on(e))) R = 4;
     auto read_check = [&](bool block) -> int {
         const int i = (int)(e->svc_checked % CHK_RING);
         if (!block) { const hipError_t q = hipEventQuery(e->chk_ev[i]); if (q == hipErrorNotReady) { (void)hipGetLastError(); return 0; } if (q != hipSuccess) return -1; }

@@ -369,3 +369,14 @@ struct GemvArgs {
 };
 void launch_gemv(const GemvArgs& a, int mode, hipStream_t s);
 bool gemv_eligible(int M, int N, int K, int mode);
+// ---- mode fp8 (gemv_fp8.hip; options fp8_weights / fp8_chain): the snap of a tiled bf16 matrix onto its e4m3 grid, and the GEMV chain on the e4m3 copies ----
+struct GemvFp8Args {
+    GemvArgs g;                      // as launch_gemv takes it, bf16 only; g.W is not read
+    const unsigned char* W8;         // [N][K] e4m3 codes in the e4m3 tiling (tile_weights.hip)
+    const float* scales;             // [N] the rows' power-of-two scales, in the tiled copy's row order
+};
+void launch_gemv_fp8(const GemvFp8Args& a, int mode, hipStream_t s);
+bool gemv_fp8_eligible(int M, int N, int K, int mode);
+// wt [N][K] tiled bf16 -> W' in place, its codes w8 and scales [N]; rowmajor (or null): a row-major bf16 copy of the same matrix in the same row order, overwritten with W' too.  N % 16 == 0, K % 64 == 0
+void launch_fp8_snap(bf16_t* wt, unsigned char* w8, float* scales, bf16_t* rowmajor, int N, int K, hipStream_t s);
+void launch_fp8_read(const unsigned char* w8, const float* scales, float* out, int K, long count, hipStream_t s);      // out[idx] = s q of element idx of [N][K], fp32

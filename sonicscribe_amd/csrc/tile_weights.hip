@@ -31,6 +31,11 @@ void launch_tile_weights(const bf16_t* w, bf16_t* wt, int N, int K, hipStream_t 
     hipLaunchKernelGGL(tile_weights_kernel, dim3((n + 255) / 256), dim3(256), 0, s, w, wt, N, K);
 }
 
+// e4m3 variant (mode fp8; written by fp8_snap_kernel in gemv_fp8.hip from a bf16 tiled copy, whose row order - plain or the gate/up 8-row interleave - it keeps):
+// one byte per weight, a (16-row, 64-k) tile is 1 KiB = 64 lanes x 16 bytes.  Lane (kc, n%16) of the bf16 tiling owns k = u*32 + kc*8 + e of k-step u; its e4m3
+// piece holds those 8 k of the TWO consecutive k-steps u = 2p (bytes 0 .. 7) and u = 2p + 1 (bytes 8 .. 15), so a lane still issues 16-byte loads: element (n, k)
+// goes to (((n/16)*(K/64) + k/64)*64 + ((k%32)/8)*16 + n%16)*16 + ((k/32)%2)*8 + k%8.  K % 64 == 0.
+
 // int8 variant: a (16-row, 64-k) MFMA A-operand tile of v_mfma_i32_16x16x64_i8 is 1 KiB; element (n, k) goes to
 // ((n/16)*(K/64) + k/64)*1024 + (((k%64)/16)*16 + n%16)*16 + k%16
 __global__ void tile_weights_i8_kernel(const int8_t* w, int8_t* wt, int N, int K) {

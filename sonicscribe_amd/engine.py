@@ -588,6 +588,23 @@ class Engine(HooksMixin):
     def weight_bytes(self) -> int:
         return int(self.lib.sonic_weight_bytes(self.h))
 
+    def fp8_info(self) -> Dict[str, int]:
+        """mode fp8 (option fp8_weights), over sonic_debug_read: the token steps this handle built in the fp8 form since the option was set, the
+        number of snapped matrices (index m of fp8_scales / fp8_matrix: layer * 4 + {0 q|k|v, 1 o_proj, 2 gate/up, 3 down_proj}, the last one the lm_head) and what
+        their e4m3 copies and scales add to the owner's weight bytes.  SonicError on a handle without the option."""
+        from . import fp8
+        self.debug_read("fp8_scales", (1,), 0)      # (the library refuses this read by the option's name where it is off)
+        return {"step_builds": int(self.debug_read("fp8_step_builds", (1,))[0]),
+                "matrices": 4 * self.dims.dec_layers + 1, "extra_weight_bytes": fp8.extra_weight_bytes(self.dims)}
+
+    def fp8_scales(self, m: int, n: int) -> np.ndarray:
+        """the first n row scales of snapped matrix m, in the row order of its tiled copy"""
+        return self.debug_read("fp8_scales", (n,), m)
+
+    def fp8_matrix(self, m: int, rows: int, K: int) -> np.ndarray:
+        """the first `rows` rows [rows][K] of snapped matrix m's e4m3 copy as fp32 scale * code, in the row order of its tiled copy"""
+        return self.debug_read("fp8_matrix", (rows, K), m)
+
     # -- stages
     @staticmethod
     def _pack_pcm(segments: Sequence[np.ndarray]) -> Tuple[np.ndarray, np.ndarray]:
