@@ -645,6 +645,37 @@ SONIC_API int sonic_synchronize(sonic_engine* e);
 /* ---- single-kernel test hooks (host fp32 in/out, converted to bf16 on device; used by tests/ only) ---- */
 SONIC_API int sonic_test_gemm(sonic_engine* e, const float* A, const float* W, const float* bias, const float* resid, float* C,
                     int M, int N, int K, int epi);
+/* The GEMM form hook: one MFMA GEMM in a launch form production uses, on the handle's own type (bf16, fp16, or int8 through the Linear8bitLt path).  It adds no entry
+ * point: like the language-model hooks it travels as named "tensors" of sonic_load_tensor and names of sonic_debug_read (a 16-bit or int8 handle; any state of its weights).
+ *   stage    sonic_load_tensor "gemm.form:A" / ":W" / ":bias" / ":resid" / ":rope" / ":C" / ":Vt", SONIC_DTYPE_F32, ndim 1 (shape {0}: drops it): fp32 values of the element type
+ *   run      sonic_load_tensor "gemm.form.run", SONIC_DTYPE_I32, ndim 1: the words of one sonic_gemm_form record (all-zero = the dense form of sonic_test_gemm, `size` set
+ *            as in sonic_dispatch_request).  Refused by name (SONIC_ERR_INVALID) when the record contradicts itself or a staged buffer has another size than it asks for.
+ *            The run consumes A, W, bias, resid and rope; C and Vt stay, holding what the launch left
+ *   read     sonic_debug_read "gemm_form_c" / "gemm_form_vt" (a prefix of the buffer); "gemm_route" (n = 4 or 5): the route of the calling thread's last launch_gemm, host
+ *            only - rows on the 256x256 tile, rows on the 128x128 kernel, that kernel's launch shape 0 / 1 / 2, the CU count the decision used; both row counts
+ *            non-zero: the ragged-tail split; a fifth value: whether the thread's last int8 linear armed the deferral of long outlier lists.  The GEMM tests
+ *            assert the kernel they mean to test from it.
+ *   A      flat, (batch - 1) * strideA + (M - 1) * lda + K elements (conv forms: the padded [W][rows + 2][ch] buffer; lda < K = overlapping rows)
+ *   W      [N][K] row-major; w_tiled: tiled on the device by launch_tile_weights (int8: launch_tile_weights_i8 of the quantised codes), gu8 (EPI_SWIGLU, w_tiled):
+ *          by launch_tile_weights_gu8 from the 16-row-interleaved gate/up matrix
+ *   C      in-out, c_row_offset * ldc + (batch - 1) * strideC + (M + 8) * ldc elements: uploaded, the GEMM writes at row c_row_offset of every batch, all read back
+ *   resid  [M][ldr] for EPI_BIAS_RESID; resid_in_place: R = C (the residual is what the caller put into C), no resid staged
+ *   EPI_QKV_VT (4): columns < n_split -> C (ldc), the rest transposed per segment of seg_T rows into Vt [ceil(M / seg_T)][N - n_split][vt_ld], in-out like C;
+ *          rope [seg_T][32] cos | sin with rope_ncols: fused into the epilogue exactly when the encoder would (256x256 tile, not under no_fused_rope / gemm_force128).
+ *          int8: the Linear8bitLt q|k|v of the encoder, asked for C [M + 8][N] (ldc = N) as run_encoder asks - when the engine fuses, columns < n_split come back
+ *          rotated, the V columns untouched and V^T in Vt; else all N columns plain and Vt untouched (the caller runs the two passes)
+ *   int8   X in groups of group_rows rows (0: one group), batch <= 1 */
+typedef struct sonic_gemm_form {
+    int32_t size;                                /* sizeof(sonic_gemm_form) as the caller compiled it */
+    int32_t M, N, K, epi;
+    int32_t lda, ldc, ldr;                       /* 0: dense (K, the output width, the output width) */
+    int32_t batch, strideA, strideC, c_row_offset;
+    int32_t w_tiled, gu8;
+    int32_t resid_in_place;
+    int32_t n_split, seg_T, vt_ld, rope_ncols;
+    int32_t group_rows;
+    int32_t gelu_arith;                          /* EPI_BIAS_GELU, 16-bit: launch without the GELU table, as the conv stem does */
+} sonic_gemm_form;
 SONIC_API int sonic_test_skinny(sonic_engine* e, const float* X, const float* W, float* C, int M, int N, int K);
 SONIC_API int sonic_test_skinny_gu(sonic_engine* e, const float* X, const float* Wgu_interleaved, float* act, int M, int N, int K);
 /* the argmax + greedy controller on caller-provided lm_head partial slabs [ksplit][mpad][V] fp32: token picked per row

@@ -261,6 +261,12 @@ struct SkinnyArgs {
         const unsigned kt_i_ = __builtin_amdgcn_readfirstlane((blockIdx.y * gridDim.x + blockIdx.x) * 8u + (unsigned)(slot)); \
         kt_p_[kt_i_] = wall_clock64(); } } while (0)
 
+// The route of one launch_gemm call: rows [0, rows256) go to the 256x256 tile, the rows128 rows behind them to the 128x128 kernel at launch shape shape128 (0 / 1 / 2,
+// gemm.hip gemm128_shape); both non-zero is the ragged-tail split.  cus: the CU count the decision used.  launch_gemm launches from gemm_plan's record and keeps the
+// last one per thread (sonic_debug_read "gemm_route": the tests assert the kernel they mean to test from it).
+struct GemmPlan { int rows256, rows128, shape128, cus; };
+GemmPlan gemm_plan(const GemmArgs& a, int epi);
+extern thread_local GemmPlan g_last_gemm_plan;
 void launch_gemm(const GemmArgs& a, int epi, hipStream_t s);
 void launch_skinny(const SkinnyArgs& a, hipStream_t s);
 int skinny_pick_ksplit(int N, int K);

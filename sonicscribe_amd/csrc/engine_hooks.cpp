@@ -366,6 +366,27 @@ extern "C" int sonic_bench_skinny(sonic_engine* e, int M, int N, int K, int vari
     *us_per_launch = ms * 1e3f / iters;
     return SONIC_OK;
 }
+// The engine's own quantisation scratch is sized for its model, not for a test: buffers of the test's shape (M rows of K, at most 64 groups) stand in for the call
+struct I8Scratch {
+    sonic_engine* e; int8_t* s_qa; float* s_sca; unsigned char* s_fl; int *s_occ, *s_ocl; int s_k;
+    I8Scratch(sonic_engine* e_, TmpBuf& tb, int M, int K) : e(e_), s_qa(e_->qa), s_sca(e_->q_sca), s_fl(e_->q_flags), s_occ(e_->q_oc_cnt), s_ocl(e_->q_oc_list), s_k(e_->q_kmax) {
+        e->qa = tb.get<int8_t>((size_t)M * K + 4096); e->q_sca = tb.get<float>(M);
+        e->q_flags = tb.get<unsigned char>((size_t)64 * K + 64); e->q_oc_cnt = tb.get<int>(64); e->q_oc_list = tb.get<int>((size_t)64 * K); e->q_kmax = K;
+    }
+    ~I8Scratch() { e->qa = s_qa; e->q_sca = s_sca; e->q_flags = s_fl; e->q_oc_cnt = s_occ; e->q_oc_list = s_ocl; e->q_kmax = s_k; }
+    I8Scratch(const I8Scratch&) = delete; I8Scratch& operator=(const I8Scratch&) = delete;
+};
+// W [N][K] (fp16) quantised row-wise on the device; tiled: only the fragment-tiled copy is handed on, as a decoder projection's since round 5
+static QW i8_quant_weights(sonic_engine* e, TmpBuf& tb, const bf16_t* dW, int N, int K, bool tiled) {
+    QW q;
+    int8_t* cb = tb.get<int8_t>((size_t)N * K); q.scb = tb.get<float>(N);
+    int8_t* cbt = tiled ? tb.get<int8_t>((size_t)N * K) : nullptr;
+    if (tb.bad()) return q;
+    launch_quant_weights(dW, cb, q.scb, N, K, e->st);
+    if (tiled) { launch_tile_weights_i8(cb, cbt, N, K, e->st); q.cbt = cbt; q.cb_rowmajor_kept = false; }
+    else q.cb = cb;
+    return q;
+}
 // One Linear8bitLt (LLM.int8, threshold 6.0) through the engine's kernels: W [N][K] is quantised row-wise on the device, X [M][K] is
 // cut into groups of `group_rows` rows (one group = one reference call: its outlier columns are found over its rows), then the int8
 // MFMA GEMM with the dequantising epilogue `epi` (EPI_BIAS / _GELU / _RESID / _SWIGLU).  Inputs are fp32 holding fp16 values.
@@ -382,19 +403,158 @@ extern "C" int sonic_test_linear_int8(sonic_engine* e, const float* X, const flo
     float* db = bias ? up_f32(e, tb, bias, N) : nullptr;
     bf16_t* dR = resid ? up_bf16(e, tb, resid, (size_t)M * Nout) : nullptr;
     bf16_t* dC = tb.get<bf16_t>((size_t)M * Nout);
-    int8_t* cb = tb.get<int8_t>((size_t)N * K); float* scb = tb.get<float>(N);
-    int8_t* qa = tb.get<int8_t>((size_t)M * K + 4096); float* sca = tb.get<float>(M);
     if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
-    launch_quant_weights(dW, cb, scb, N, K, e->st);
-    QW q; q.cb = cb; q.scb = scb;
-    unsigned char* fl = tb.get<unsigned char>((size_t)64 * K + 64); int* occ = tb.get<int>(64); int* ocl = tb.get<int>((size_t)64 * K);
+    I8Scratch sc(e, tb, M, K);
+    const QW q = i8_quant_weights(e, tb, dW, N, K, false);
     if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
-    // the engine's own scratch is sized for its model, not for this test: swap in buffers of the test's shape for the call
-    int8_t* s_qa = e->qa; float* s_sca = e->q_sca; unsigned char* s_fl = e->q_flags; int *s_occ = e->q_oc_cnt, *s_ocl = e->q_oc_list; const int s_k = e->q_kmax;
-    e->qa = qa; e->q_sca = sca; e->q_flags = fl; e->q_oc_cnt = occ; e->q_oc_list = ocl; e->q_kmax = K;
     qlinear(e, epi, dX, K, nullptr, q, db, dC, Nout, M, N, K, dR, Nout, QGroup{nullptr, group_rows, (M + group_rows - 1) / group_rows});
-    e->qa = s_qa; e->q_sca = s_sca; e->q_flags = s_fl; e->q_oc_cnt = s_occ; e->q_oc_list = s_ocl; e->q_kmax = s_k;
     return down_bf16(e, tb, dC, out, (size_t)M * Nout);
+}
+
+// One GEMM in a production launch form (include/sonic_hip.h has the record and the buffers): what sonic_test_gemm cannot express - pitched and overlapping rows, the
+// batched conv-stem forms, the fragment-tiled weight copies, R == C, the q|k|v epilogue with its V^T and fused RoPE - on the engine's own type.
+static int gemm_form_check(sonic_engine* e, const sonic_gemm_form& f, const float* resid, const float* rope, const float* Vt) {
+    const char* bad = nullptr;
+    const bool qkv = f.epi == EPI_QKV_VT;
+    const int Nout = f.epi == EPI_SWIGLU ? f.N / 2 : qkv ? f.n_split : f.N;
+    const int lda = f.lda ? f.lda : f.K, ldc = f.ldc ? f.ldc : Nout, ldr = f.ldr ? f.ldr : Nout, batch = f.batch > 0 ? f.batch : 1;
+    if (f.size != (int32_t)sizeof(sonic_gemm_form)) bad = "size is not sizeof(sonic_gemm_form)";
+    else if (e->f32) bad = "needs a 16-bit or int8 engine";
+    else if (f.M < 1 || f.N < 16 || f.N % 16 || f.K < 64 || f.K % (e->i8 ? 128 : 64)) bad = "M >= 1, N a multiple of 16, K a multiple of 64 (int8: 128)";
+    else if (f.epi < EPI_BIAS || f.epi > EPI_QKV_VT) bad = "epi is none of 0 .. 4";
+    else if (f.epi == EPI_SWIGLU && f.N % 32) bad = "EPI_SWIGLU needs N % 32 == 0";
+    else if (lda < 8 || lda % 8 || ldc < Nout || ldc % 4 || f.c_row_offset < 0) bad = "lda a multiple of 8, ldc >= the output width and a multiple of 4, c_row_offset >= 0";
+    else if (f.batch < 0 || (batch > 1 && (f.strideA < 1 || f.strideC < (long)(f.c_row_offset + f.M) * ldc || f.strideA % 8 || f.strideC % 8))) bad = "batch > 1 needs strideA >= 1 and strideC >= (c_row_offset + M) * ldc, multiples of 8";
+    else if (batch <= 1 && (f.strideA || f.strideC)) bad = "strideA / strideC without batch > 1";
+    else if (batch > 1 && (f.epi == EPI_BIAS_RESID || qkv || e->i8)) bad = "batch > 1 with a residual, the q|k|v epilogue or an int8 engine";
+    else if (f.gu8 && !(f.w_tiled && f.epi == EPI_SWIGLU)) bad = "gu8 without w_tiled and EPI_SWIGLU";
+    else if (f.gu8 && e->i8) bad = "gu8 on an int8 engine";
+    else if (f.gelu_arith && (f.epi != EPI_BIAS_GELU || e->i8)) bad = "gelu_arith without a 16-bit EPI_BIAS_GELU";
+    else if (f.w_tiled && e->i8 && f.epi == EPI_BIAS_GELU) bad = "int8 EPI_BIAS_GELU from the tiled copy (gemm_lin compiles the tiled outlier gather out of the GELU epilogue: no decoder linear has one)";
+    else if (f.epi == EPI_BIAS_RESID ? (f.resid_in_place ? resid != nullptr : resid == nullptr) : (f.resid_in_place || resid)) bad = "EPI_BIAS_RESID takes exactly one of resid and resid_in_place, the other epilogues neither";
+    else if (f.epi == EPI_BIAS_RESID && !f.resid_in_place && (ldr < Nout || ldr % 4)) bad = "ldr >= N and a multiple of 4";
+    else if (f.ldr && (f.epi != EPI_BIAS_RESID || f.resid_in_place)) bad = "ldr without a separate residual";
+    else if (!qkv && (f.n_split || f.seg_T || f.vt_ld || f.rope_ncols || rope || Vt)) bad = "q|k|v fields without EPI_QKV_VT";
+    else if (qkv && (!Vt || f.n_split < 128 || f.n_split % 128 || f.n_split >= f.N || f.seg_T < 4 || f.seg_T % 4 || f.M % 4 || f.vt_ld < f.seg_T || f.vt_ld % 8))
+        bad = "EPI_QKV_VT needs Vt, 0 < n_split < N a multiple of 128, seg_T and M multiples of 4, vt_ld >= seg_T a multiple of 8";
+    else if (qkv && (rope ? (f.rope_ncols < 64 || f.rope_ncols % 64 || f.rope_ncols > f.n_split) : f.rope_ncols != 0)) bad = "rope needs 64 <= rope_ncols <= n_split, a multiple of 64 (and rope_ncols needs rope)";
+    else if (qkv && e->i8 && (!rope || f.ldc)) bad = "int8 q|k|v needs rope and the dense ldc";
+    else if (e->i8 ? (f.group_rows < 0 || (f.M + (f.group_rows ? f.group_rows : f.M) - 1) / (f.group_rows ? f.group_rows : f.M) > 64) : f.group_rows != 0) bad = "group_rows: int8 engines only, at most 64 groups";
+    return bad ? fail(e, SONIC_ERR_INVALID, "gemm.form.run: %s", bad) : SONIC_OK;
+}
+struct FormSizes { size_t a, c, vt, r; };
+static FormSizes gemm_form_sizes(const sonic_engine* e, const sonic_gemm_form& f) {      // (of a record gemm_form_check accepts, but for the buffers it cannot see yet)
+    const bool qkv = f.epi == EPI_QKV_VT;
+    const int Nout = f.epi == EPI_SWIGLU ? f.N / 2 : qkv ? f.n_split : f.N, batch = f.batch > 0 ? f.batch : 1;
+    const long lda = f.lda ? f.lda : f.K, ldr = f.ldr ? f.ldr : Nout, ldc = (qkv && e->i8) ? f.N : f.ldc ? f.ldc : Nout;
+    FormSizes z;
+    z.a = (size_t)(batch - 1) * f.strideA + (size_t)(f.M - 1) * lda + f.K;
+    z.c = (size_t)f.c_row_offset * ldc + (size_t)(batch - 1) * f.strideC + (size_t)(f.M + 8) * ldc;
+    z.vt = qkv ? (size_t)((f.M + f.seg_T - 1) / f.seg_T) * (f.N - f.n_split) * f.vt_ld : 0;
+    z.r = (size_t)f.M * ldr;
+    return z;
+}
+// the launch itself, under the caller's lock: buffers as the header lays them out, C and Vt in-out
+static int gemm_form_launch(sonic_engine* e, const sonic_gemm_form& f, const float* A, const float* W, const float* bias, const float* resid, const float* rope,
+                            float* C, float* Vt) {
+    TRY(gemm_form_check(e, f, resid, rope, Vt));
+    const int M = f.M, N = f.N, K = f.K, epi = f.epi, batch = f.batch > 0 ? f.batch : 1;
+    const bool qkv = epi == EPI_QKV_VT;
+    const int Nout = epi == EPI_SWIGLU ? N / 2 : qkv ? f.n_split : N;
+    const long lda = f.lda ? f.lda : K, ldr = f.ldr ? f.ldr : Nout;
+    long ldc = f.ldc ? f.ldc : Nout;
+    if (qkv && e->i8) ldc = N;                               // room for the un-fused [M][N] form; the fused one is asked to write it at the pitch it then uses
+    const size_t a_elems = (size_t)(batch - 1) * f.strideA + (size_t)(M - 1) * lda + K;
+    const size_t c_elems = (size_t)f.c_row_offset * ldc + (size_t)(batch - 1) * f.strideC + (size_t)(M + 8) * ldc;
+    const int n_seg = qkv ? (M + f.seg_T - 1) / f.seg_T : 0;
+    const size_t vt_elems = qkv ? (size_t)n_seg * (N - f.n_split) * f.vt_ld : 0;
+    TmpBuf tb(e->st);
+    bf16_t* dA = up_bf16(e, tb, A, a_elems, 4096); bf16_t* dW = up_bf16(e, tb, W, (size_t)N * K);
+    float* db = bias ? up_f32(e, tb, bias, N) : nullptr;
+    bf16_t* dR = resid ? up_bf16(e, tb, resid, (size_t)M * ldr) : nullptr;
+    bf16_t* dC = up_bf16(e, tb, C, c_elems);
+    bf16_t* dVt = qkv ? up_bf16(e, tb, Vt, vt_elems) : nullptr;
+    float* dcs = rope ? up_f32(e, tb, rope, (size_t)f.seg_T * 32) : nullptr;
+    if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+    bf16_t* c0 = dC + (size_t)f.c_row_offset * ldc;
+    const bf16_t* R = f.resid_in_place ? c0 : dR;
+    const long ldR = f.resid_in_place ? ldc : ldr;
+    if (e->i8) {
+        I8Scratch sc(e, tb, M, K);
+        const QW q = i8_quant_weights(e, tb, dW, N, K, f.w_tiled != 0);
+        if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+        const int gr = f.group_rows ? f.group_rows : M;
+        const QGroup grp{nullptr, gr, (M + gr - 1) / gr};
+        if (qkv) {
+            const QkvVt vt{dVt, f.n_split, f.seg_T, f.vt_ld, (long)(N - f.n_split) * f.vt_ld};
+            // as run_encoder: the linear is asked for [M][N] row-major; when the engine fuses, q | k land rotated in its first n_split columns and V in Vt
+            qlinear(e, EPI_BIAS, dA, lda, nullptr, q, db, c0, ldc, M, N, K, nullptr, 0, grp, dcs, f.seg_T, f.rope_ncols, false, &vt);
+        } else {
+            qlinear(e, epi, dA, lda, nullptr, q, db, c0, ldc, M, N, K, R, ldR, grp);
+        }
+    } else {
+        bf16_t* dWt = f.w_tiled ? tb.get<bf16_t>((size_t)N * K) : nullptr;
+        if (tb.bad()) return fail(e, SONIC_ERR_OOM, "HIP out of memory in test hook");
+        if (f.gu8) launch_tile_weights_gu8(dW, dWt, N, K, e->st);
+        else if (f.w_tiled) launch_tile_weights(dW, dWt, N, K, e->st);
+        GemmArgs a{};
+        a.A = dA; a.lda = lda; a.W = f.w_tiled ? dWt : dW; a.C = c0; a.ldc = ldc; a.bias = db; a.R = R; a.ldr = ldR; a.M = M; a.N = N; a.K = K; a.dt = e->dt;
+        a.batch = batch; a.strideA = f.strideA; a.strideC = f.strideC;
+        a.w_tiled = f.w_tiled != 0; a.gu8 = f.gu8 != 0;
+        a.gelu_lut = (e->opt_no_gelu_lut || f.gelu_arith) ? nullptr : e->gelu_lut;      // (the conv stem launches without the table)
+        if (qkv) {
+            a.Vt = dVt; a.n_split = f.n_split; a.seg_T = f.seg_T; a.vt_ld = f.vt_ld; a.vt_seg_stride = (long)(N - f.n_split) * f.vt_ld;
+            if (dcs && enc_qkv_fuses_rope(e, a)) { a.rope_cs = dcs; a.rope_T = f.seg_T; a.rope_ncols = f.rope_ncols; }
+        }
+        launch_gemm(a, epi, e->st);
+    }
+    TRY(down_bf16(e, tb, dC, C, c_elems));
+    if (qkv) TRY(down_bf16(e, tb, dVt, Vt, vt_elems));
+    return SONIC_OK;
+}
+// sonic_load_tensor "gemm.form:<buffer>": one of the hook's seven host buffers (fp32, ndim 1; shape {0} drops it)
+static const char* const FORM_BUFS[7] = {"A", "W", "bias", "resid", "rope", "C", "Vt"};
+int gemm_form_stage(sonic_engine* e, const char* which, const void* data, int dtype, const int64_t* shape, int ndim) {
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (dtype != SONIC_DTYPE_F32 || ndim != 1 || shape[0] < 0) return fail(e, SONIC_ERR_INVALID, "gemm.form:%s: a buffer is one row of fp32 values (SONIC_DTYPE_F32, ndim 1)", which);
+    for (int i = 0; i < 7; ++i)
+        if (!strcmp(which, FORM_BUFS[i])) { e->hook_form[i].assign((const float*)data, (const float*)data + shape[0]); return SONIC_OK; }
+    return fail(e, SONIC_ERR_INVALID, "gemm.form:%s: the buffers are A, W, bias, resid, rope, C, Vt", which);
+}
+// sonic_load_tensor "gemm.form.run": the record's words; the staged inputs are consumed whatever way the call leaves, C and Vt keep what the launch left
+int gemm_form_run(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim) {
+    ENTER(e);
+    struct Drop { sonic_engine* e; ~Drop() { for (int i = 0; i < 5; ++i) std::vector<float>().swap(e->hook_form[i]); } } drop{e};
+    sonic_gemm_form f;
+    if (dtype != SONIC_DTYPE_I32 || ndim != 1 || shape[0] != (int64_t)(sizeof f / 4)) return fail(e, SONIC_ERR_INVALID, "gemm.form.run: the record is %d int32 words (SONIC_DTYPE_I32, ndim 1)", (int)(sizeof f / 4));
+    memcpy(&f, data, sizeof f);
+    std::vector<float>* b = e->hook_form;
+    if (b[0].empty() || b[1].empty()) return fail(e, SONIC_ERR_INVALID, "gemm.form.run: stage A and W first (sonic_load_tensor \"gemm.form:A\", \"gemm.form:W\")");
+    const bool qkv = f.epi == EPI_QKV_VT;
+    TRY(gemm_form_check(e, f, b[3].empty() ? nullptr : b[3].data(), b[4].empty() ? nullptr : b[4].data(), b[6].empty() ? nullptr : b[6].data()));
+    const FormSizes z = gemm_form_sizes(e, f);
+    if (b[5].empty()) b[5].assign(z.c, 0.f);
+    if (b[0].size() < z.a || b[1].size() != (size_t)f.N * f.K || (!b[2].empty() && b[2].size() != (size_t)f.N) || (!b[3].empty() && b[3].size() != z.r) ||
+        (!b[4].empty() && b[4].size() != (size_t)f.seg_T * 32) || b[5].size() != z.c || b[6].size() != z.vt)
+        return fail(e, SONIC_ERR_INVALID, "gemm.form.run: a staged buffer has another size than the record asks for (A >= %zu, W %zu, bias %d, resid %zu, rope %d, C %zu, Vt %zu)",
+                    z.a, (size_t)f.N * f.K, f.N, z.r, f.seg_T * 32, z.c, z.vt);
+    return gemm_form_launch(e, f, b[0].data(), b[1].data(), b[2].empty() ? nullptr : b[2].data(), b[3].empty() ? nullptr : b[3].data(), b[4].empty() ? nullptr : b[4].data(),
+                            b[5].data(), qkv ? b[6].data() : nullptr);
+}
+// sonic_debug_read "gemm_form_c" / "gemm_form_vt" / "gemm_route" (under the caller's lock); returns -1 for any other name
+int gemm_form_read(sonic_engine* e, const char* name, float* out, int64_t n) {
+    if (!strcmp(name, "gemm_route")) {          // the calling thread's last launch_gemm (host only; exact in fp32: row counts below 2^24)
+        if (n != 4 && n != 5) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
+        const GemmPlan p = g_last_gemm_plan;
+        out[0] = (float)p.rows256; out[1] = (float)p.rows128; out[2] = (float)p.shape128; out[3] = (float)p.cus;
+        if (n == 5) out[4] = (float)g_last_qlinear_defer;      // the last int8 linear of this thread armed the deferral (rows with long outlier lists left to the side product)
+        return SONIC_OK;
+    }
+    const int i = !strcmp(name, "gemm_form_c") ? 5 : !strcmp(name, "gemm_form_vt") ? 6 : -1;
+    if (i < 0) return -1;
+    if (n < 0 || (size_t)n > e->hook_form[i].size()) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
+    if (n > 0) memcpy(out, e->hook_form[i].data(), (size_t)n * 4);
+    return SONIC_OK;
 }
 
 // greedy_kernel on caller-provided lm_head partial slabs [ksplit][mpad][V] (fp32): returns the token each row picks (first maximum of

@@ -249,6 +249,7 @@ struct sonic_engine {
     // the handle, not a value of a request: nothing is staged.  Owner only: `lms`, the registry (guarded by gram_mu, freed with the owner at the latest)
     int opt_lm = 0; float lm_weight = 0.f; sonic_lm* lm = nullptr; int* lm_words = nullptr; float* lm_add = nullptr;
     std::vector<sonic_lm*> lms;
+    std::vector<float> hook_form[7];      // the GEMM form hook's host buffers A, W, bias, resid, rope, C, Vt (sonic_load_tensor "gemm.form:<buffer>"; engine_hooks.cpp)
     // the kernel hooks' language model (sonic_load_tensor "lm.hook:<V>", options hook_lm_state / hook_lm_tok / hook_lm_weight; engine_hooks.cpp): the device blob in lm_step_kernel's
     // layout, the rows' words in (host) and out (device, [state 64 | tok 64]) and the vector [64][V] the last "lm.hook.step" left: the greedy hooks that have histories and
     // log-probabilities take it while it is armed
@@ -417,6 +418,8 @@ void gemm(sonic_engine* e, int epi, const bf16_t* A, long lda, const bf16_t* W, 
 bool qlinear(sonic_engine* e, int epi, const bf16_t* X, long ldx, const bf16_t* w16, const QW& q, const float* bias, bf16_t* C, long ldc,
              int M, int N, int K, const bf16_t* R, long ldr, const QGroup& grp, const float* rope_cs = nullptr, int rope_T = 0, int rope_ncols = 0,
              bool prequant = false, const QkvVt* vt = nullptr);
+extern thread_local int g_last_qlinear_defer;   // whether the calling thread's last int8 qlinear handed rows to the outlier side product (sonic_debug_read "gemm_route", fifth value; tests)
+bool enc_qkv_fuses_rope(sonic_engine* e, const GemmArgs& a);   // the q|k|v launch of a 16-bit encoder layer takes the RoPE into its epilogue (also the form hook's rule)
 int run_mel(sonic_engine* e, int W, bool want_f32);
 int run_encoder(sonic_engine* e, int W, float* enc_layers_out, float* enc_out_host, int n_groups);
 int keep_rows(const sonic_dims& d, int n_valid_frames);
@@ -519,6 +522,9 @@ int lm_set_weight(sonic_engine* e, int bits);       // option lm_weight: the bit
 void lm_prefill_rows(sonic_engine* e, int R);       // a prefill's rows start at (start, no pending token)
 void lm_step(sonic_engine* e, int R);               // lm_step_kernel right ahead of a greedy launch (nothing when the handle has no live model)
 int lm_hook_arm(sonic_engine* e, int V, const int* words, int64_t n);    // sonic_load_tensor "lm.hook:<V>": the hooks' automaton, validated against V; every row at the start node, no pending token, weight 0
+int gemm_form_stage(sonic_engine* e, const char* which, const void* data, int dtype, const int64_t* shape, int ndim);   // sonic_load_tensor "gemm.form:<buffer>" (engine_hooks.cpp)
+int gemm_form_run(sonic_engine* e, const void* data, int dtype, const int64_t* shape, int ndim);                          // sonic_load_tensor "gemm.form.run": one GEMM in a production launch form
+int gemm_form_read(sonic_engine* e, const char* name, float* out, int64_t n);                                             // sonic_debug_read "gemm_form_c" / "gemm_form_vt" / "gemm_route"; -1: another name
 int lm_hook_step(sonic_engine* e, const int* finished, int64_t B);       // sonic_load_tensor "lm.hook.step": lm_step_kernel alone over B rows of the armed hook model (engine_hooks.cpp)
 // the three per-request stages' switches (engine_options.cpp) and what the hooks and sonic_load_tensor share with them
 int bias_enable(sonic_engine* e, int on);           // option request_bias behind the lock and the busy check: hist, the tables and their staging buffer on first use

@@ -340,6 +340,7 @@ static const DbgRow DEBUG_BUFS[] = {
 extern "C" int sonic_debug_read(sonic_engine* e, const char* name, int index, float* out, int64_t n) {
     if (!e || !name || !out) return SONIC_ERR_INVALID;
     ENTER(e);
+    if (!strncmp(name, "gemm_", 5)) { const int r = gemm_form_read(e, name, out, n); if (r >= 0) return r; }      // the GEMM form hook's C / Vt and the route witness
     if (!strcmp(name, "hook_grammar_state")) {      // the rows' states behind the last hook launch that took a grammar (host words: exact in fp32)
         if (n < 0 || n > 64) return fail(e, SONIC_ERR_INVALID, "read of %lld elements exceeds buffer %s", (long long)n, name);
         for (int64_t i = 0; i < n; ++i) out[i] = (float)e->hook_state_out[i];

@@ -42,6 +42,7 @@ static bool rmsnorm_q(sonic_engine* e, const bf16_t* x, const float* w, bf16_t* 
     launch_rmsnorm(x, w, y, M, d, eps, nullptr, e->st, e->dt);
     return false;
 }
+thread_local int g_last_qlinear_defer = 0;
 bool qlinear(sonic_engine* e, int epi, const bf16_t* X, long ldx, const bf16_t* w16, const QW& q, const float* bias, bf16_t* C, long ldc,
              int M, int N, int K, const bf16_t* R, long ldr, const QGroup& grp, const float* rope_cs, int rope_T, int rope_ncols,
              bool prequant, const QkvVt* vt) {
@@ -66,10 +67,14 @@ bool qlinear(sonic_engine* e, int epi, const bf16_t* X, long ldx, const bf16_t* 
     // more than `i8_defer_thr` outlier columns are finished by the dense side product instead of the epilogue's per-element list walk
     const bool defer = epi == EPI_BIAS_RESID && e->defer_tmp && e->opt_i8_defer_thr >= 0 && (size_t)M * ldc <= e->defer_cap;
     if (defer) { a.q.defer_out = e->defer_tmp; a.q.defer_thr = e->opt_i8_defer_thr; }
+    g_last_qlinear_defer = defer;
     launch_gemm(a, epi, e->st);
     if (defer) launch_i8_outlier_side(a, e->st);
     return fuse;
 }
+
+// the 16-bit q|k|v GEMM rotates q / k in its epilogue only on the 256x256 tile (launch_gemm sends every eligible EPI_QKV_VT there unless gemm_force128)
+bool enc_qkv_fuses_rope(sonic_engine* e, const GemmArgs& a) { return !e->opt_no_fused_rope && !g_opts.gemm_force128 && gemm256_eligible(a, EPI_QKV_VT); }
 
 int run_mel(sonic_engine* e, int W, bool want_f32) {
     const sonic_dims& d = e->d;
@@ -130,7 +135,7 @@ int run_encoder(sonic_engine* e, int W, float* enc_layers_out, float* enc_out_ho
             a.A = e->ln; a.lda = C; a.W = L.wqkv; a.bias = L.bqkv; a.C = e->qk; a.ldc = 2L * C; a.M = M; a.N = 3 * C; a.K = C; a.batch = 1; a.dt = dt;
             a.Vt = e->vt; a.n_split = 2 * C; a.seg_T = T; a.vt_ld = e->Tp; a.vt_seg_stride = (long)C * e->Tp;
             // partial RoPE of q / k in the GEMM's epilogue (the rotation pairs are in one lane's accumulators): no separate HBM pass
-            const bool roped = e->hd_e == 64 && d.enc_rotary_dim == 32 && !e->opt_no_fused_rope && !g_opts.gemm_force128 && gemm256_eligible(a, EPI_QKV_VT);
+            const bool roped = e->hd_e == 64 && d.enc_rotary_dim == 32 && enc_qkv_fuses_rope(e, a);
             if (roped) { a.rope_cs = e->enc_cs; a.rope_T = T; a.rope_ncols = 2 * C; }
             mark(0);
             launch_gemm(a, EPI_QKV_VT, e->st);

@@ -86,6 +86,8 @@ extern "C" int sonic_load_tensor(sonic_engine* e, const char* name, const void* 
         if (name[7] == ':') return lm_hook_arm(e, atoi(name + 8), (const int*)data, shape[0]);
         return lm_hook_step(e, (const int*)data, shape[0]);
     }
+    if (!strncmp(name, "gemm.form:", 10)) return gemm_form_stage(e, name + 10, data, dtype, shape, ndim);      // the GEMM form hook's buffers and its launch (include/sonic_hip.h)
+    if (!strcmp(name, "gemm.form.run")) return gemm_form_run(e, data, dtype, shape, ndim);
     if (!strcmp(name, "request_draft")) return draft_stage_words(e, data, dtype, shape, ndim);      // the drafts of the next prefill's requests (option draft_verify)
     if (!strcmp(name, "request_forks")) return fork_stage_counts(e, data, dtype, shape, ndim);      // the fork counts of the next prefill's requests
     if (!strcmp(name, "request_truncation")) return trunc_stage_rows(e, data, dtype, shape, ndim);      // top_k / top_p / min_p of the next prefill's rows (option truncation)

@@ -268,7 +268,7 @@ void launch_gemm256(const GemmArgs& a, int epi, hipStream_t s);
 void launch_gemm256p(const GemmArgs& a, int epi, int cus, hipStream_t s);
 thread_local LaunchOpts g_opts;
 
-static void launch_gemm128(const GemmArgs& a, int epi, hipStream_t s);
+static void launch_gemm128(const GemmArgs& a, int epi, int shape, hipStream_t s);
 static int device_cus() {
     static int n = 0;
     if (!n) { int dev = 0; hipDeviceProp_t p; n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256; }
@@ -285,47 +285,76 @@ static void launch_tile256(const GemmArgs& a, int epi, hipStream_t s) {
 // the encoder: 30 .. 120 tiles per linear on 256 CUs).  The 128x128 kernel cuts the same problem into four times as many tiles, two to a CU,
 // at about `gemm_small_eff` % of the big kernel's per-CU rate when both are full: it gets the GEMM whenever its tile rounds, priced that way,
 // are fewer.  Both kernels produce the same bits (tests/test_gpu_parity.py test_gemm256_path), so the choice never shows in a result.  Not the
-// q|k|v epilogue: its fused RoPE exists only on the 256x256 tile, and rotating before the bf16 rounding is not the separate pass's arithmetic.
-static bool small_grid_prefers128(const GemmArgs& a, int epi) {
+// q|k|v epilogue: its fused RoPE exists only on the 256x256 tile (it rotates the rounded linear with the separate pass's operations - the same bits,
+// tests/test_gpu_gemm_forms.py - but the 128x128 kernel would need that pass back).
+static bool small_grid_prefers128(const GemmArgs& a, int epi, long cus) {
     const int eff = g_opts.gemm_small_eff;
     if (eff <= 0 || epi == EPI_QKV_VT) return false;
-    const long cus = device_cus(), batch = a.batch > 0 ? a.batch : 1;
+    const long batch = a.batch > 0 ? a.batch : 1;
     const long t256 = (long)((a.M + 255) / 256) * ((a.N + 255) / 256) * batch, t128 = (long)((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN) * batch;
     const long r256 = (t256 + cus - 1) / cus, r128 = (t128 + 2 * cus - 1) / (2 * cus);
     return r128 * 50 < r256 * eff;      // a round of 128x128 tiles is half the work per CU of a round of 256x256 tiles
 }
-void launch_gemm(const GemmArgs& a, int epi, hipStream_t s) {
-    if (!g_opts.gemm_force128 && gemm256_eligible(a, epi) && !small_grid_prefers128(a, epi)) {
+// shape of a 128x128-kernel launch over M rows: 0 = 128 x 128 tiles, two-stage ring, two blocks per CU; 1 = 32 x 64 tiles, four-stage ring (grids of 128 x 128 tiles
+// that would leave half of the CUs idle); 2 = 32 x 32 tiles (when even the 32 x 64 grid covers at most half of the CUs; not for the SwiGLU epilogue, whose gate / up
+// pairs need 32 columns per wave: it stays at 1).  The q|k|v epilogue exists at shape 0 only.
+static int gemm128_shape(const GemmArgs& a, int M, int epi, int cus) {
+    if (epi == EPI_QKV_VT) return 0;
+    const int tilesM = (M + BM - 1) / BM, tilesN = (a.N + BN - 1) / BN;
+    const int batch = a.batch > 0 ? a.batch : 1;
+    int shape = (!g_opts.gemm128_shallow && (long)tilesM * tilesN * batch <= cus / 2 && a.K / (128 / (a.q.sca ? 1 : 2)) >= 4) ? 1 : 0;
+    if (shape == 1 && epi != EPI_SWIGLU && (long)((M + 31) / 32) * ((a.N + 63) / 64) * batch <= cus / 2) shape = 2;
+    return shape;
+}
+// The whole routing decision of one GEMM, in one place: launch_gemm launches from it and nothing else decides (the route witness of the tests reads the same record).
+GemmPlan gemm_plan(const GemmArgs& a, int epi) {
+    GemmPlan p{0, a.M, 0, device_cus()};
+    if (!g_opts.gemm_force128 && gemm256_eligible(a, epi) && !small_grid_prefers128(a, epi, p.cus)) {
+        p.rows256 = a.M; p.rows128 = 0;
         // Wave quantisation: a 256x256 tile occupies a whole CU, so (tiles mod CUs) small means a nearly empty extra round (prefill at
         // M = 8320: 33 x 8 = 264 tiles on 256 CUs, two rounds for 1.03).  If cutting the ragged last <= 128 rows off saves a round, those
         // rows go to the 128x128 kernel instead (same math per row; rows are independent in every epilogue but QKV+V^T).
-        const int cus = device_cus(), ntn = (a.N + 255) / 256, Mm = (a.M / 256) * 256, tail = a.M - Mm;
+        const int cus = p.cus, ntn = (a.N + 255) / 256, Mm = (a.M / 256) * 256, tail = a.M - Mm;
         if (tail > 0 && tail <= 128 && Mm >= 512 && epi != EPI_QKV_VT && a.batch <= 1) {
             const long full = (long)((a.M + 255) / 256) * ntn, main_tiles = (long)(Mm / 256) * ntn;
-            if ((main_tiles + cus - 1) / cus < (full + cus - 1) / cus) {
-                GemmArgs m = a; m.M = Mm;
-                launch_tile256(m, epi, s);
-                GemmArgs t = a; t.M = tail; t.C = a.C + (long)Mm * a.ldc;
-                if (a.R) t.R = a.R + (long)Mm * a.ldr;
-                if (a.q.sca) {
-                    // int8 GEMM: A is int8 (1 byte per element) and the per-row quantisation data travels with the rows - scales,
-                    // unquantised activations of the outlier columns, and the row -> group (request) index.  (Leaving them at row 0
-                    // gave the tail rows the scales and outlier lists of the FIRST rows of the batch: the last request of some batch
-                    // compositions differed from its solo result, found by tools/find_batch_dependence.py.)
-                    t.A = (const bf16_t*)((const int8_t*)a.A + (long)Mm * a.lda);
-                    t.q.sca = a.q.sca + Mm; t.q.x16 = a.q.x16 + (long)Mm * a.q.ldx16; t.q.row_off = a.q.row_off + Mm;
-                    if (a.q.defer_out) t.q.defer_out = a.q.defer_out + (long)Mm * a.ldc;
-                } else {
-                    t.A = a.A + (long)Mm * a.lda;
-                }
-                launch_gemm128(t, epi, s);
-                return;
-            }
+            if ((main_tiles + cus - 1) / cus < (full + cus - 1) / cus) { p.rows256 = Mm; p.rows128 = tail; }
         }
-        launch_tile256(a, epi, s);
+    }
+    if (p.rows128 > 0) p.shape128 = gemm128_shape(a, p.rows128, epi, p.cus);
+    return p;
+}
+thread_local GemmPlan g_last_gemm_plan{0, 0, 0, 0};
+void launch_gemm(const GemmArgs& a, int epi, hipStream_t s) {
+    if (a.q.sca && a.w_tiled && epi == EPI_BIAS_GELU) {
+        // gemm_lin<KD, false> compiles the tiled outlier gather out of the GELU epilogue (int8_util.h): such a launch would add outlier columns read at row-major
+        // addresses of a tiled copy.  No caller has one (the decoder's tiled linears use SwiGLU); one that appears must not get wrong numbers quietly
+        fprintf(stderr, "[sonic_hip] launch_gemm: int8 EPI_BIAS_GELU from a fragment-tiled W is not compiled (gemm_lin WK); give the GELU linear the row-major codes\n");
+        abort();
+    }
+    const GemmPlan p = gemm_plan(a, epi);
+    g_last_gemm_plan = p;
+    if (p.rows256 > 0 && p.rows128 > 0) {          // the ragged-tail split: rows [0, rows256) on the big tile, the rest on the 128x128 kernel
+        const int Mm = p.rows256;
+        GemmArgs m = a; m.M = Mm;
+        launch_tile256(m, epi, s);
+        GemmArgs t = a; t.M = p.rows128; t.C = a.C + (long)Mm * a.ldc;
+        if (a.R) t.R = a.R + (long)Mm * a.ldr;
+        if (a.q.sca) {
+            // int8 GEMM: A is int8 (1 byte per element) and the per-row quantisation data travels with the rows - scales,
+            // unquantised activations of the outlier columns, and the row -> group (request) index.  (Leaving them at row 0
+            // gave the tail rows the scales and outlier lists of the FIRST rows of the batch: the last request of some batch
+            // compositions differed from its solo result, found by tools/find_batch_dependence.py.)
+            t.A = (const bf16_t*)((const int8_t*)a.A + (long)Mm * a.lda);
+            t.q.sca = a.q.sca + Mm; t.q.x16 = a.q.x16 + (long)Mm * a.q.ldx16; t.q.row_off = a.q.row_off + Mm;
+            if (a.q.defer_out) t.q.defer_out = a.q.defer_out + (long)Mm * a.ldc;
+        } else {
+            t.A = a.A + (long)Mm * a.lda;
+        }
+        launch_gemm128(t, epi, p.shape128, s);
         return;
     }
-    launch_gemm128(a, epi, s);
+    if (p.rows256 > 0) launch_tile256(a, epi, s);
+    else launch_gemm128(a, epi, p.shape128, s);
 }
 template <typename KD, int EPI, int NS, int WM, int WN> static void launch_gemm128_v(const GemmArgs& a, hipStream_t s) {
     constexpr int TBM = 32 * WM, TBN = 32 * WN;
@@ -334,20 +363,14 @@ template <typename KD, int EPI, int NS, int WM, int WN> static void launch_gemm1
     const int tilesM = (a.M + TBM - 1) / TBM, tilesN = (a.N + TBN - 1) / TBN;
     hipLaunchKernelGGL((gemm_kernel<KD, EPI, NS, WM, WN>), dim3(tilesM * tilesN, 1, a.batch > 0 ? a.batch : 1), dim3(256), lds, s, a);
 }
-// shape of the launch: 0 = 128 x 128 tiles, two-stage ring, two blocks per CU; 1 = 32 x 64 tiles, four-stage ring (grids of 128 x 128 tiles
-// that would leave half of the CUs idle); 2 = 32 x 32 tiles (when even the 32 x 64 grid covers at most half of the CUs; not for the SwiGLU
-// epilogue, whose gate / up pairs need 32 columns per wave)
+// shape of the launch: gemm128_shape
 template <typename KD, int EPI> static void launch_gemm128_e(const GemmArgs& a, int shape, hipStream_t s) {
     if constexpr (EPI == EPI_QKV_VT) launch_gemm128_v<KD, EPI, 2, 4, 4>(a, s);
     else if (shape == 2 && EPI != EPI_SWIGLU) launch_gemm128_v<KD, EPI, 4, 1, EPI == EPI_SWIGLU ? 2 : 1>(a, s);
     else if (shape >= 1) launch_gemm128_v<KD, EPI, 4, 1, 2>(a, s);
     else launch_gemm128_v<KD, EPI, 2, 4, 4>(a, s);
 }
-static void launch_gemm128(const GemmArgs& a, int epi, hipStream_t s) {
-    const int tilesM = (a.M + BM - 1) / BM, tilesN = (a.N + BN - 1) / BN;
-    const int batch = a.batch > 0 ? a.batch : 1;
-    int shape = (!g_opts.gemm128_shallow && (long)tilesM * tilesN * batch <= device_cus() / 2 && a.K / (128 / (a.q.sca ? 1 : 2)) >= 4) ? 1 : 0;
-    if (shape == 1 && (long)((a.M + 31) / 32) * ((a.N + 63) / 64) * batch <= device_cus() / 2) shape = 2;
+static void launch_gemm128(const GemmArgs& a, int epi, int shape, hipStream_t s) {
     KD_SWITCH(a, KD, {
         switch (epi) {
             case EPI_BIAS: launch_gemm128_e<KD, EPI_BIAS>(a, shape, s); break;

@@ -13,7 +13,7 @@ from typing import Any, Dict, List, NamedTuple, Optional, Sequence, Tuple
 import numpy as np
 
 from . import reqvalues
-from .engine_hooks import EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_SWIGLU, HooksMixin, _arr, _p  # noqa: F401
+from .engine_hooks import EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_SWIGLU, EPI_QKV_VT, GemmForm, HooksMixin, _arr, _p  # noqa: F401
 from .spec import ModelDims
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -429,6 +429,7 @@ class Engine(HooksMixin):
         self.lib = load_library()
         self.dims = dims
         self.max_batch, self.max_ctx = max_batch, max_ctx
+        self.mode = _slot_of.mode if _slot_of is not None else mode
         self._cd = make_dims(dims)
         self.owner: Optional["Engine"] = _slot_of       # a slot keeps its weight owner alive
         self._slots: List["Engine"] = []

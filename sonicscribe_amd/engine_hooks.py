@@ -7,7 +7,17 @@ from typing import Optional
 
 import numpy as np
 
-EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_SWIGLU = 0, 1, 2, 3
+EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESID, EPI_SWIGLU, EPI_QKV_VT = 0, 1, 2, 3, 4
+
+
+class GemmForm(C.Structure):
+    """sonic_gemm_form: one GEMM launch form, the words of sonic_load_tensor "gemm.form.run".  A fresh record is all-zero - the dense form of sonic_test_gemm - with `size` set"""
+    _fields_ = [(n, C.c_int32) for n in (
+        "size", "M", "N", "K", "epi", "lda", "ldc", "ldr", "batch", "strideA", "strideC", "c_row_offset", "w_tiled", "gu8", "resid_in_place",
+        "n_split", "seg_T", "vt_ld", "rope_ncols", "group_rows", "gelu_arith")]
+
+    def __init__(self, **kw):
+        super().__init__(size=C.sizeof(GemmForm), **kw)
 
 
 def _p(a: Optional[np.ndarray]):
@@ -33,6 +43,54 @@ class HooksMixin:
         r = _arr(resid, np.float32)
         self._check(self.lib.sonic_test_gemm(self.h, _p(A), _p(W), _p(b), _p(r), _p(out), M, N, K, epi))
         return out
+
+    def debug_gemm_route(self) -> dict:
+        """sonic_debug_read "gemm_route": the route of this thread's last launch_gemm -> {"rows256", "rows128", "shape128", "cus"} and "deferred": whether its last
+        int8 linear armed the deferral of long outlier lists; host only"""
+        out = np.zeros(5, np.float32)
+        self._check(self.lib.sonic_debug_read(self.h, b"gemm_route", 0, _p(out), 5))
+        return dict(zip(("rows256", "rows128", "shape128", "cus", "deferred"), (int(v) for v in out)))
+
+    def _form_tensor(self, name: bytes, a, dtype: int):
+        a = np.zeros(0, np.float32) if a is None else np.ascontiguousarray(a).reshape(-1)
+        self._check(self.lib.sonic_load_tensor(self.h, name, _p(a if a.size else np.zeros(1, a.dtype)), dtype, (C.c_int64 * 1)(a.size), 1))
+
+    def test_gemm_form(self, A, W, bias=None, resid=None, rope=None, C_fill=None, Vt_fill=None, **form):
+        """The GEMM form hook (sonic_load_tensor "gemm.form:<buffer>" / "gemm.form.run", sonic_debug_read "gemm_form_c" / "gemm_form_vt"): one GEMM in a production launch
+        form on the handle's own type.  A: flat; W [N][K]; form: the fields of GemmForm beside M / N / K
+        (N, K from W; M is required).  C_fill / Vt_fill: what the pitched buffers hold before the launch (an array of the buffer's size, or a scalar; default 0).
+        Returns the whole pitched C as [rows][ldc] - row c_row_offset of batch 0 is its first GEMM row, at least 8 rows follow the last - and, for EPI_QKV_VT,
+        (C, Vt [segments][N - n_split][vt_ld]); on an int8 handle the q|k|v buffer is [rows][N].  Nothing stays staged on the handle."""
+        W = np.ascontiguousarray(W, np.float32)
+        N, K = W.shape
+        f = GemmForm(N=N, K=K, **form)
+        M, epi, batch = f.M, f.epi, max(f.batch, 1)
+        n_out = N // 2 if epi == EPI_SWIGLU else f.n_split if epi == EPI_QKV_VT else N
+        lda, ldc = f.lda or K, N if (self.mode == 1 and epi == EPI_QKV_VT) else (f.ldc or n_out)
+        A = np.ascontiguousarray(A, np.float32).reshape(-1)
+        assert M >= 1 and A.size >= (batch - 1) * f.strideA + (M - 1) * lda + K, "A is shorter than the form reads"
+        c_elems = f.c_row_offset * ldc + (batch - 1) * f.strideC + (M + 8) * ldc
+        Cb = np.empty(c_elems, np.float32)
+        Cb[:] = 0.0 if C_fill is None else np.asarray(C_fill, np.float32).reshape(-1)
+        r = _arr(resid, np.float32)
+        assert r is None or r.size == M * (f.ldr or n_out)
+        cs = _arr(rope, np.float32)
+        Vt = None
+        if epi == EPI_QKV_VT:
+            assert f.seg_T > 0 and (cs is None or cs.shape == (f.seg_T, 32))
+            Vt = np.empty((-(-M // f.seg_T), N - f.n_split, f.vt_ld), np.float32)
+            Vt[:] = 0.0 if Vt_fill is None else np.asarray(Vt_fill, np.float32).reshape(Vt.shape if np.ndim(Vt_fill) else ())
+        from .engine import DTYPE_F32, DTYPE_I32
+        for name, a in ((b"A", A), (b"W", W), (b"bias", _arr(bias, np.float32)), (b"resid", r), (b"rope", cs), (b"C", Cb), (b"Vt", Vt)):
+            self._form_tensor(b"gemm.form:" + name, a, DTYPE_F32)
+        self._form_tensor(b"gemm.form.run", np.frombuffer(bytes(f), np.int32), DTYPE_I32)
+        self._check(self.lib.sonic_debug_read(self.h, b"gemm_form_c", 0, _p(Cb), Cb.size))
+        if Vt is not None:
+            self._check(self.lib.sonic_debug_read(self.h, b"gemm_form_vt", 0, _p(Vt), Vt.size))
+        for name in (b"C", b"Vt"):
+            self._form_tensor(b"gemm.form:" + name, None, DTYPE_F32)
+        Cb = Cb.reshape(-1, ldc) if c_elems % ldc == 0 else Cb
+        return (Cb, Vt) if epi == EPI_QKV_VT else Cb
 
     def test_skinny(self, X, W):
         X = np.ascontiguousarray(X, np.float32); W = np.ascontiguousarray(W, np.float32)

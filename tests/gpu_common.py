@@ -1,5 +1,5 @@
 """What the GPU test files share (imported like glue_ref.py; not a conftest, not collected): the synthetic seed, prompts, engines with their options in a given
-order, bit comparisons, the float64 log-softmax reference, the derived log-probability bounds, the kernel hooks' slabs, the six invariance segments and the loaders
+order, the GEMM routing options with the assertions on the route witness, bit comparisons, the float64 log-softmax reference, the derived log-probability bounds, the kernel hooks' slabs, the six invariance segments and the loaders
 behind the `orc` / `golden` fixtures.  tests/test_common_host.py pins every one of them on the CPU.
 
 The log-probability bound (DESIGN.md 6.3 goes through the kernel line by line).  With u = 2^-24, V the vocabulary, n_t = ceil(V / 4096) * 4 the elements one
@@ -18,6 +18,7 @@ thread adds and ref64 the float64 log-softmax of the very fp32 scores the kernel
 Guards, bias, sampling, truncation and grammar add no rounding to the sum, they change the scores it is taken over: their tests evaluate the same bound over the
 processed scores.  The row kernel of scoring and draft verify walks a row in strides of 16384 with 16 elements per thread and trip; the
 derivation is the same with n_t = ceil(V / 16384) * 16 (score_bound)."""
+import contextlib
 import math
 import os
 
@@ -62,6 +63,44 @@ def six(d=spec.TINY):
     """the six synthetic segments of the invariance tests with their prompts"""
     segs = [synth.synth_pcm(700 + i, n) for i, n in enumerate((48000, 200000, 80000, 64000, 120000, 96000))]
     return segs, [prompt_for(d, len(s)) for s in segs]
+
+
+# ------------------------------------------------------------------------------------------ GEMM routes (csrc/gemm.hip gemm_plan; Engine.debug_gemm_route is the witness)
+ROUTE_DEFAULTS = {"gemm_small_eff": 75, "gemm_force128": 0, "gemm128_shallow": 0, "no_fused_rope": 0, "i8_no_qkv_fuse": 0}
+BIG_TILE = {"gemm_small_eff": 0}            # every eligible GEMM on the 256x256 tile
+FORCE128 = {"gemm_force128": 1}             # ... on the 128x128 kernel, at the launch shape its grid selects
+SHALLOW128 = {"gemm_force128": 1, "gemm128_shallow": 1}     # ... at its 128x128 two-stage shape
+
+
+@contextlib.contextmanager
+def route_options(eng, opts):
+    """the routing options `opts` (keys of ROUTE_DEFAULTS) set on eng for the block, their defaults restored behind it whatever happens inside"""
+    assert set(opts) <= set(ROUTE_DEFAULTS), sorted(set(opts) - set(ROUTE_DEFAULTS))
+    try:
+        for k, v in opts.items():
+            eng.set_option(k, v)
+        yield
+    finally:
+        for k in opts:
+            eng.set_option(k, ROUTE_DEFAULTS[k])
+
+
+def assert_big_tile(eng, M, split=None):
+    """the calling thread's last GEMM ran on the 256x256 tile: all M rows, or - split = (rows256, rows128) - exactly that ragged-tail split; split = "any": all rows
+    but a tail of at most 128 that the 128x128 kernel took (the shapes whose split depends on the chip's CU count)"""
+    r = eng.debug_gemm_route()
+    if split == "any":
+        assert r["rows256"] >= 512 and r["rows256"] + r["rows128"] == M and r["rows128"] <= 128 and r["rows256"] % 256 == (0 if r["rows128"] else M % 256), (M, r)
+    else:
+        assert (r["rows256"], r["rows128"]) == ((M, 0) if split is None else tuple(split)), (M, split, r)
+    return r
+
+
+def assert_128(eng, M, shape=None):
+    """the calling thread's last GEMM ran on the 128x128 kernel alone, at launch shape `shape` (0 / 1 / 2) when one is given"""
+    r = eng.debug_gemm_route()
+    assert r["rows256"] == 0 and r["rows128"] == M and (shape is None or r["shape128"] == shape), (M, shape, r)
+    return r
 
 
 # ------------------------------------------------------------------------------------------ bits

@@ -92,6 +92,43 @@ def test_flags_keep_their_order():
     assert C.flags((1, "a", 1), (0, "b", 2), ({"x": 1}, "generation", {"x": 1}), (None, "c", 3), (8, "d", 8)) == [("a", 1), ("generation", {"x": 1}), ("d", 8)]
 
 
+class _RouteEngine:
+    """what route_options and the route assertions use of an Engine: set_option and debug_gemm_route"""
+    def __init__(self, route):
+        self.route, self.calls = dict(zip(("rows256", "rows128", "shape128", "cus"), route)), []
+
+    def set_option(self, key, value):
+        self.calls.append((key, value))
+
+    def debug_gemm_route(self):
+        return dict(self.route)
+
+
+def test_route_options_restore_and_route_assertions_refuse():
+    """the options of the GEMM tests go back to the library's defaults (csrc/common.h LaunchOpts, engine_options.cpp) even when the block raises, and each route
+    assertion refuses every route but the one it names - a test whose shape stopped reaching its kernel fails instead of passing on the other one"""
+    assert C.ROUTE_DEFAULTS == {"gemm_small_eff": 75, "gemm_force128": 0, "gemm128_shallow": 0, "no_fused_rope": 0, "i8_no_qkv_fuse": 0}
+    src = open(abi_pins.CSRC + "/common.h").read()
+    assert "int gemm_small_eff = 75;" in src and "int gemm_force128 = 0;" in src and "int gemm128_shallow = 0;" in src
+    e = _RouteEngine((0, 0, 0, 256))
+    with pytest.raises(RuntimeError):
+        with C.route_options(e, C.SHALLOW128):
+            raise RuntimeError("inside")
+    assert e.calls == [("gemm_force128", 1), ("gemm128_shallow", 1), ("gemm_force128", 0), ("gemm128_shallow", 0)]
+    with pytest.raises(AssertionError):
+        with C.route_options(e, {"no_such_route_option": 1}):
+            pass
+    assert (C.BIG_TILE, C.FORCE128) == ({"gemm_small_eff": 0}, {"gemm_force128": 1})
+    big, small, split = _RouteEngine((520, 0, 0, 256)), _RouteEngine((0, 520, 2, 256)), _RouteEngine((8192, 128, 0, 256))
+    assert C.assert_big_tile(big, 520)["rows256"] == 520 and C.assert_128(small, 520, 2)["shape128"] == 2 and C.assert_128(small, 520)
+    C.assert_big_tile(split, 8320, split=(8192, 128)); C.assert_big_tile(split, 8320, split="any"); C.assert_big_tile(big, 520, split="any")
+    for fn in (lambda: C.assert_big_tile(small, 520), lambda: C.assert_big_tile(small, 520, split="any"), lambda: C.assert_big_tile(split, 8320),
+               lambda: C.assert_big_tile(big, 520, split=(512, 8)), lambda: C.assert_big_tile(big, 521, split="any"), lambda: C.assert_128(big, 520),
+               lambda: C.assert_128(small, 520, 1), lambda: C.assert_128(split, 8320), lambda: C.assert_128(small, 519)):
+        with pytest.raises(AssertionError):
+            fn()
+
+
 def test_check_surface_and_that_it_checks(monkeypatch):
     abi_pins.check_surface()
     abi_pins.check_surface(names=("sonic_set_option",), options=("token_logprobs",), header_strings=("SONIC_API",), engine_methods=("set_option",))

@@ -7,13 +7,14 @@ operation order, so a Linear8bitLt on identical inputs must agree bit for bit.  
 (LayerNorm, attention, GELU) differ in fp32 summation order; a 1-ulp fp16 difference on an activation can move an int8 code by one,
 so whole-model logits are compared with a stated bound.
 """
+import contextlib
 import os
 from dataclasses import replace
 
 import numpy as np
 import pytest
 
-from gpu_common import SEED, load_oracle, make_engine
+from gpu_common import BIG_TILE, FORCE128, SEED, assert_128, assert_big_tile, load_oracle, make_engine, route_options
 from sonicscribe_amd import spec, synth
 from sonicscribe_amd.engine import MODE_INT8
 
@@ -36,6 +37,19 @@ def orc():
     return load_oracle()
 
 
+def _routes(eng8, M, N, K):
+    """The routes a Linear8bitLt test runs its shape on, as context managers: shapes the 256x256 int8 kernel takes (M >= 512, N >= 256, K >= 512: four 128-wide k
+    tiles) run on it AND on the 128x128 kernel, each asserted from the route witness once the block's last GEMM has run; the others run once, at the default route"""
+    @contextlib.contextmanager
+    def routed(opts, check):
+        with route_options(eng8, opts):
+            yield
+            check(eng8, M)
+    if M >= 512 and N >= 256 and K >= 512:
+        return [routed(BIG_TILE, lambda e, m: assert_big_tile(e, m, split="any")), routed(FORCE128, assert_128)]
+    return [contextlib.nullcontext()]
+
+
 def _ref_linear(orc, X, W, bias, group_rows):
     cb, scb = orc.quantize_rows(W)
     out = np.empty((X.shape[0], W.shape[0]), np.float32)
@@ -53,11 +67,13 @@ def test_linear8bit_bias_exact(eng8, orc, M, N, K, group_rows):
     rng = np.random.default_rng(M + N + K)
     X = f16(rng.standard_normal((M, K)) * 1.2); W = f16(rng.standard_normal((N, K)) * 0.06); b = f16(rng.standard_normal(N) * 0.1)
     X[0, 3] = 6.0; X[M // 2, K - 1] = -11.5; X[M - 1, 64] = 7.25; X[M // 2, 17] = 5.99609375  # 6.0 itself is an outlier, the fp16 below it is not
-    got = eng8.test_linear_int8(X, W, b, group_rows=group_rows)
     ref = _ref_linear(orc, X, W, b, group_rows)
-    assert np.array_equal(got, ref), (np.abs(got - ref).max(), int((got != ref).sum()))
     dense = X.astype(np.float64) @ W.T.astype(np.float64) + b
-    assert np.abs(got - dense).max() < 0.02 * np.sqrt(K)                                      # and it is a sane approximation of the fp product (int8 noise ~ sqrt(K))
+    for route in _routes(eng8, M, N, K):
+        with route:
+            got = eng8.test_linear_int8(X, W, b, group_rows=group_rows)
+        assert np.array_equal(got, ref), (np.abs(got - ref).max(), int((got != ref).sum()))
+        assert np.abs(got - dense).max() < 0.02 * np.sqrt(K)                                  # and it is a sane approximation of the fp product (int8 noise ~ sqrt(K))
 
 
 def test_linear8bit_int8_mfma_layout(eng8, orc):
@@ -81,12 +97,8 @@ def test_linear8bit_epilogues(eng8, orc):
         X[5, 9] = 8.0
         R = f16(rng.standard_normal((M, N)))
         lin = _ref_linear(orc, X, W, b, M)
-        got = eng8.test_linear_int8(X, W, b, resid=R, epi=EPI_BIAS_RESID)
-        assert np.array_equal(got, f16(lin + R))
         erf = np.vectorize(math.erf)
         gelu = f16((0.5 * lin * (1.0 + erf(lin.astype(np.float64) / math.sqrt(2.0)))).astype(np.float32))
-        got = eng8.test_linear_int8(X, W, b, epi=EPI_BIAS_GELU)
-        assert np.abs(got - gelu).max() <= 2.0 ** -10 * max(1.0, float(np.abs(gelu).max()))    # 1 fp16 ulp (fast erf / exp in the epilogue)
         ff = N // 2
         Wg = W[:ff]; Wu = W[ff:]
         Wi = np.empty_like(W)
@@ -94,8 +106,16 @@ def test_linear8bit_epilogues(eng8, orc):
             Wi[32 * g:32 * g + 16] = Wg[16 * g:16 * g + 16]; Wi[32 * g + 16:32 * g + 32] = Wu[16 * g:16 * g + 16]
         gg = _ref_linear(orc, X, Wg, None, M); uu = _ref_linear(orc, X, Wu, None, M)
         ref = f16(f16(gg / (1.0 + np.exp(-gg.astype(np.float64))).astype(np.float32)) * uu)
-        got = eng8.test_linear_int8(X, Wi, None, epi=EPI_SWIGLU)
-        assert np.abs(got - ref).max() <= 2.0 ** -9 * max(1.0, float(np.abs(ref).max()))
+        for epi in (EPI_BIAS_RESID, EPI_BIAS_GELU, EPI_SWIGLU):              # (the shape of the second round runs each on both kernels, witnessed)
+            for route in _routes(eng8, M, N, K):
+                with route:
+                    got = eng8.test_linear_int8(X, Wi if epi == EPI_SWIGLU else W, None if epi == EPI_SWIGLU else b, resid=R if epi == EPI_BIAS_RESID else None, epi=epi)
+                if epi == EPI_BIAS_RESID:
+                    assert np.array_equal(got, f16(lin + R))
+                elif epi == EPI_BIAS_GELU:
+                    assert np.abs(got - gelu).max() <= 2.0 ** -10 * max(1.0, float(np.abs(gelu).max()))    # 1 fp16 ulp (fast erf / exp in the epilogue)
+                else:
+                    assert np.abs(got - ref).max() <= 2.0 ** -9 * max(1.0, float(np.abs(ref).max()))
 
 
 def test_linear8bit_long_outlier_lists_go_to_the_dense_side_product(eng8, orc):
@@ -115,24 +135,29 @@ def test_linear8bit_long_outlier_lists_go_to_the_dense_side_product(eng8, orc):
     cols1 = rng.choice(K, 5, replace=False)
     X[G + rng.integers(0, G, 5), cols1] = f16(rng.uniform(6.5, 9.0, 5))
     ref = f16(_ref_linear(orc, X, W, b, G) + R)
-    got = eng8.test_linear_int8(X, W, b, resid=R, group_rows=G, epi=EPI_BIAS_RESID)
     lin = _ref_linear(orc, X, W, b, G)                              # the module output before the residual: the rounding that may move is ITS last one
 
     def ulp16(v):
         return np.maximum(2.0 ** (np.floor(np.log2(np.maximum(np.abs(v), 2.0 ** -14))) - 10), 2.0 ** -24)
     ulp = ulp16(lin) + ulp16(ref)                                   # one ulp of fp16(v + sum), carried through fp16(. + R)
-    diff = np.abs(got - ref)
-    assert (diff <= ulp).all(), float((diff / ulp).max())
-    assert np.array_equal(got[G:], ref[G:])                         # the short list stayed on the exact path
-    frac = float((diff[:G] > 0).mean())
-    print(f"deferred request: {frac * 100:.3f} % of the elements differ from the ascending-k sum (by one fp16 ulp)")
-    assert frac < 0.02
+    for route in _routes(eng8, M, N, K):                            # the 256x256 tile (its DEFER instantiation exists only in this epilogue) and the 128x128 kernel
+        with route:
+            got = eng8.test_linear_int8(X, W, b, resid=R, group_rows=G, epi=EPI_BIAS_RESID)
+        assert eng8.debug_gemm_route()["deferred"] == 1             # the deferral was armed: without it the result is exact and the bound below proves nothing
+        diff = np.abs(got - ref)
+        assert (diff <= ulp).all(), float((diff / ulp).max())
+        assert np.array_equal(got[G:], ref[G:])                     # the short list stayed on the exact path
+        frac = float((diff[:G] > 0).mean())
+        print(f"deferred request: {frac * 100:.3f} % of the elements differ from the ascending-k sum (by one fp16 ulp)")
+        assert frac < 0.02
     eng8.set_option("i8_defer_thr", -1)
     try:
-        exact = eng8.test_linear_int8(X, W, b, resid=R, group_rows=G, epi=EPI_BIAS_RESID)
+        for route in _routes(eng8, M, N, K):
+            with route:
+                exact = eng8.test_linear_int8(X, W, b, resid=R, group_rows=G, epi=EPI_BIAS_RESID)
+            assert eng8.debug_gemm_route()["deferred"] == 0 and np.array_equal(exact, ref)
     finally:
         eng8.set_option("i8_defer_thr", 8)
-    assert np.array_equal(exact, ref)
 
 
 def _prompt(n_samples, d):

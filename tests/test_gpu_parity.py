@@ -11,7 +11,7 @@ import os
 import numpy as np
 import pytest
 
-from gpu_common import SEED, load_oracle, make_engine
+from gpu_common import BIG_TILE, FORCE128, SEED, assert_128, assert_big_tile, load_oracle, make_engine, route_options
 from sonicscribe_amd import spec, synth
 
 pytestmark = pytest.mark.gpu
@@ -98,30 +98,39 @@ def test_gemm_epilogues(eng, orc):
 @pytest.mark.parametrize("M,N,K,epi", [(1024, 512, 256, 0), (777, 384, 512, 1), (2048, 256, 1280, 2), (600, 1280, 320, 0), (520, 512, 256, 3),
                                        (8320, 2048, 256, 2), (8300, 2048, 256, 3)])   # last two: ragged tail rows cut off to the 128x128 kernel
 def test_gemm256_path(eng, M, N, K, epi):
-    """Shapes large enough for the 256x256 multi-phase kernel (M >= 512, N >= 256, K >= 256), ragged edges included."""
+    """Shapes large enough for the 256x256 multi-phase kernel (M >= 512, N >= 256, K >= 256), ragged edges included.  The first product runs with
+    gemm_small_eff = 0 - the default sends grids that under-fill the chip to the 128x128 kernel - and the route witness says which kernel each product took."""
     import math
     rng = np.random.default_rng(M + N)
     A = bf(rng.standard_normal((M, K)) * 0.5); W = bf(rng.standard_normal((N, K)) * 0.2); b = bf(rng.standard_normal(N) * 0.1)
     lin = lambda bias: bf((A.astype(np.float64) @ W.T.astype(np.float64) + bias).astype(np.float32))
+    R = bf(rng.standard_normal((M, N))) if epi == 2 else None
+    run = lambda: eng.test_gemm(A, W, None if epi == 3 else b, resid=R, epi=epi)
+
+    def run_big():
+        with route_options(eng, BIG_TILE):
+            out = run()
+            assert_big_tile(eng, M, split="any")          # all rows, or all but the ragged tail the 128x128 kernel takes where that saves a round of tiles
+        return out
+    got = run_big()
     if epi == 0:
-        got, ref = eng.test_gemm(A, W, b), lin(b)
+        ref = lin(b)
     elif epi == 1:
         l = lin(b); erf = np.vectorize(math.erf)
-        got, ref = eng.test_gemm(A, W, b, epi=1), bf((0.5 * l * (1.0 + erf(l.astype(np.float64) / math.sqrt(2.0)))).astype(np.float32))
+        ref = bf((0.5 * l * (1.0 + erf(l.astype(np.float64) / math.sqrt(2.0)))).astype(np.float32))
     elif epi == 2:
-        R = bf(rng.standard_normal((M, N)))
-        got, ref = eng.test_gemm(A, W, b, resid=R, epi=2), bf(lin(b) + R)
+        ref = bf(lin(b) + R)
         ref_mag = np.abs(lin(b)) + np.abs(R)      # the residual add can cancel: tolerance follows the addends
     else:
         ff = N // 2
         g = lin(0.0)
         idx_g = np.concatenate([np.arange(32 * i, 32 * i + 16) for i in range(ff // 16)]); idx_u = idx_g + 16
         gg, uu = g[:, idx_g], g[:, idx_u]
-        got, ref = eng.test_gemm(A, W, epi=3), bf(bf(gg / (1.0 + np.exp(-gg))) * uu)
+        ref = bf(bf(gg / (1.0 + np.exp(-gg))) * uu)
     bad = np.abs(got - ref) > ulp_tol(ref_mag if epi == 2 else ref, 4) + 1e-3
     if bad.any():      # footprint of the failure: which tiles, and what the wrong values look like
         rows = np.where(bad.any(1))[0]; cols = np.where(bad.any(0))[0]
-        again = eng.test_gemm(A, W, None if epi == 3 else b, resid=(R if epi == 2 else None), epi=epi)
+        again = run_big()
         msg = (f"{int(bad.sum())} bad elements, max err {np.abs(got - ref).max():.3f}; rows {rows.min()}..{rows.max()} ({len(rows)}), cols {cols.min()}..{cols.max()} "
                              f"({len(cols)}); row tiles {sorted(set((rows // 256).tolist()))[:12]}, col tiles {sorted(set((cols // 256).tolist()))[:12]}; "
                              f"bad values are zero: {bool(np.all(got[bad] == 0))}; a rerun is clean: {bool(not (np.abs(again - ref) > ulp_tol(ref_mag if epi == 2 else ref, 4) + 1e-3).any())}; "
@@ -134,14 +143,14 @@ def test_gemm256_path(eng, M, N, K, epi):
         except OSError:
             pass
         raise AssertionError(msg)
-    eng.set_option("gemm_force128", 1)
-    try:
-        old = eng.test_gemm(A, W, None if epi == 3 else b, resid=(R if epi == 2 else None), epi=epi)
-    finally:
-        eng.set_option("gemm_force128", 0)
+    with route_options(eng, FORCE128):
+        old = run()
+        assert_128(eng, M)
     # Both kernels accumulate every output element over k in the same order (32-wide MFMA steps, ascending) and share the epilogue
     # arithmetic (the GELU table included), so a row's result does not depend on which kernel its batch size selects: bit-identical.
     assert np.array_equal(old.view(np.uint32), got.view(np.uint32)), float(np.mean(old != got))
+    default = run()                                   # whichever kernel the default route picks for this grid on this chip: the same bits again
+    assert np.array_equal(default.view(np.uint32), got.view(np.uint32)), (eng.debug_gemm_route(), float(np.mean(default != got)))
 
 
 def test_gelu_table_bit_exact(eng, orc):
@@ -158,9 +167,15 @@ def test_gelu_table_bit_exact(eng, orc):
     W[128:192] *= 8.0                                            # columns that leave the table at the top (|x| >= 16)
     l = bf((A.astype(np.float64) @ W.T.astype(np.float64) + b).astype(np.float32))
     assert (np.abs(l) >= 16).any() and ((np.abs(l) < 2.0 ** -14) & (l != 0)).any() and (l == 0).any()
-    got = eng.test_gemm(A, W, b, epi=1)
     ref = orc.gelu(l, bf16=True)
+    with route_options(eng, BIG_TILE):                           # the table in LDS (256x256 tile)
+        got = eng.test_gemm(A, W, b, epi=1)
+        assert_big_tile(eng, M)
     assert np.array_equal(got.view(np.uint32), ref.view(np.uint32)), (int((got != ref).sum()), np.abs(got - ref).max())
+    with route_options(eng, FORCE128):                           # the same table read from global memory (128x128 kernel)
+        got128 = eng.test_gemm(A, W, b, epi=1)
+        assert_128(eng, M)
+    assert np.array_equal(got128.view(np.uint32), ref.view(np.uint32)), (int((got128 != ref).sum()), np.abs(got128 - ref).max())
     eng.set_option("no_gelu_lut", 1)
     try:
         arith = eng.test_gemm(A, W, b, epi=1)
